@@ -1,16 +1,22 @@
 #!/usr/bin/env python3
 """bench.py -- single-stream decode of RWKV-6-World-7B Q4_0 (BASELINE.json's metric) through librwkv.so on MI355X.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" is one decoded token: one pass of the hot path (embedding row, 32 x (time mixing + channel mixing), ln_out, head,
 on-device argmax) with weights and recurrent state already resident in HBM.  Weights are synthetic (seeded random blocks
 with the tensor names / shapes / dtypes of the real checkpoint; no checkpoint is available offline), the decode is greedy.
 
-Prints ONE JSON line (rank 0) with the contract's keys plus
-  "roofline":     the dominant kernel (quantised single-token projection) timed per launch with HIP events on its stream,
-  "cpu_baseline": the CPU oracle (a port of the reference's ggml CPU algorithm) timed on the host cores, N = 1 only.
+Prints ONE JSON line (rank 0) with the contract's keys. A plain run sets up, warms up, times the steps and prints; with --full the line
+also carries what takes runs of its own (N = 1 only):
+  "roofline":      the dominant kernel timed per launch with HIP events on its stream,
+  "cpu_baseline":  the CPU oracle (a port of the reference's ggml CPU algorithm) timed on the host cores,
+  "parity":        GPU vs CPU oracle on the benchmarked file, bit for bit,
+  "abi", "load":   the rate through the unmodified rwkv_eval ABI, the cold file -> HBM load,
+  "other_configs": the other BASELINE decode configurations (default config only);
+--mode prefill adds "fast_arms" and --chain "multi_stream" the same way.
+--dump-outputs DIR writes what the timed path computed in its last step as DIR/<name>.npy (float32 / float64), at most 64 MB in all.
 """
 import argparse
 import json
@@ -113,7 +119,29 @@ def parse_args():
     ap.add_argument("--no-other-configs", action="store_true",
                     help="skip the other_configs block of the default line (BASELINE C2 / C4 / C3-decode measured beside the headline)")
     ap.add_argument("--chain-devices", default=None, help="device list of --chain (default 0-(N-1); e.g. 0,0 runs two stages on one GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline (roofline profile, CPU baseline + oracle parity, ABI rate, cold load, other configs, "
+                         "prefill fast arms, chain multi-stream); the options above that tune those legs act only with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """Writes {name: array} as out_dir/<name>.npy, float32 (float64 for integer arrays such as token ids). Beyond DUMP_LIMIT_BYTES in all,
+    every array keeps the same share of its elements: a fixed, seeded sample of flat indices (the same for two builds of the project)."""
+    import numpy as np
+    conv = {k: np.ascontiguousarray(v, dtype=np.float64 if np.asarray(v).dtype.kind in "iub" else np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in conv.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in conv.items():
+        if total > DUMP_LIMIT_BYTES:
+            k = max(1, v.size * DUMP_LIMIT_BYTES // total)
+            v = v.ravel()[np.sort(np.random.default_rng(42).choice(v.size, size=k, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), v)
 
 
 def ensure_model_file(args, synth, rank, barrier):
@@ -252,6 +280,7 @@ def other_configs(args, pkg, lib, synth, torch):
         try:
             sub = argparse.Namespace(**vars(args))
             sub.config, sub.dtype, sub.steps, sub.warmup, sub.abi_tokens, sub.cpu_seconds, sub.parity_tokens, sub.quiet_fail = cfg, dtype, 128, 8, 0, 4.0, 32, True
+            sub.dump_outputs = None
             os.environ["RWKV_BENCH_NO_COLD"] = "1"
             path, spec = ensure_model_file(sub, synth, 0, lambda: None)
             r = bench_decode(sub, pkg, lib, path, spec, torch)
@@ -271,7 +300,7 @@ def other_configs(args, pkg, lib, synth, torch):
 def bench_decode(args, pkg, lib, path, spec, torch):
     """One step = one decoded token (embedding row, every layer, ln_out, head, on-device argmax), state resident in HBM."""
     import numpy as np
-    load = load_leg(pkg, lib, path, spec)
+    load = load_leg(pkg, lib, path, spec) if args.full else {}
     t0 = time.time()
     model = pkg.RWKVModel(lib, path, thread_count=1, gpu_layer_count=spec.n_layer + 1)
     load_s = time.time() - t0
@@ -287,6 +316,9 @@ def bench_decode(args, pkg, lib, path, spec, torch):
     toks, ev_ms = model.decode_greedy(first, args.steps)
     torch.cuda.synchronize()
     wall_s = time.perf_counter() - t0
+    if args.dump_outputs:
+        # what a caller of the timed path receives: the greedy token ids, the last token's logits, the recurrent state after it
+        dump_outputs(args.dump_outputs, {"tokens": toks, "logits": model.logits_store(), "state": model.state_store()})
     tok_s = args.steps / wall_s
     path_id = model.decode_path()
     result = {
@@ -299,6 +331,9 @@ def bench_decode(args, pkg, lib, path, spec, torch):
                 "hip_event_ms_per_token": ev_ms / args.steps},
         "load_seconds": load_s, "load": load,
     }
+    if not args.full:
+        model.free()
+        return result
     if not args.no_profile:
         p = model.profile_decode(first, min(args.steps, 32))
         if p["launches"] > 0:
@@ -427,6 +462,9 @@ def bench_prefill(args, pkg, lib, path, spec, torch):
         logits = model.eval_resident(prompt, want_logits=True)
     torch.cuda.synchronize()
     wall_s = time.perf_counter() - t0
+    if args.dump_outputs:
+        # what a caller of the timed pass receives: the logits after the prompt, the recurrent state after it
+        dump_outputs(args.dump_outputs, {"logits": logits, "state": model.state_store()})
     tok_s = args.steps * T / wall_s
     flops = model.prefill_flops(T)
     result = {
@@ -437,6 +475,9 @@ def bench_prefill(args, pkg, lib, path, spec, torch):
                    "layers": spec.n_layer, "n_embed": spec.n_embed, "n_vocab": spec.n_vocab, "seq_len": T, "parallelism": "1 GPU"},
         "load_seconds": load_s,
     }
+    if not args.full:
+        model.free()
+        return result
     peak = MFMA_I8_PEAK_TOPS if args.dtype.startswith("Q") else MFMA_F16_PEAK_TOPS
     # the opt-in arms (RWKV_MI_SEQ_Q=fast RWKV_MI_SEQ_F16=mfma) timed the same way, as a side figure: `value` is the product's default
     with seq_arms("fast"):
@@ -554,6 +595,20 @@ def bench_chain(args, pkg, lib, path, spec, torch):
     front.state_load(None)
     toks, ms = front.decode_greedy(first, args.steps)
     single_tok_s = args.steps / (ms / 1e3)
+    if args.dump_outputs:
+        # what a caller of the timed path receives: the greedy token ids, the recurrent state after them
+        dump_outputs(args.dump_outputs, {"tokens": toks, "state": front.state_store()})
+    result = {
+        "metric": "tokens/sec single-stream decode", "value": single_tok_s, "unit": "tokens/s", "n_gpus": n, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms / args.steps, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+        "dtype": DTYPE_DESC.get(args.dtype, args.dtype), "data": "synthetic",
+        "config": {"workload": f"{spec.name} {args.dtype} single-stream greedy decode through a layer chain of {n} stage(s) in one process "
+                               f"(RWKV_MI_DEVICES={devices}; C++ decode loop, one direct launch per stage, the residual stream stored by a stage's last layer in the next stage's buffer)",
+                   "layers": spec.n_layer, "n_embed": spec.n_embed, "n_vocab": spec.n_vocab, "parallelism": f"pp{n} (one process)"},
+    }
+    if not args.full:
+        front.free()
+        return result
     # N decode streams through the same chain
     streams = [front] + [front.clone() for _ in range(max(1, n) - 1)]
     firsts = [(1103515245 * (j + 1)) % spec.n_vocab for j in range(len(streams))]
@@ -563,16 +618,8 @@ def bench_chain(args, pkg, lib, path, spec, torch):
     for m in streams:
         m.state_load(None)
     mtoks, mms = pkg.RWKVModel.decode_greedy_streams(streams, firsts, args.steps)
-    result = {
-        "metric": "tokens/sec single-stream decode", "value": single_tok_s, "unit": "tokens/s", "n_gpus": n, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": ms / args.steps, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-        "dtype": DTYPE_DESC.get(args.dtype, args.dtype), "data": "synthetic",
-        "config": {"workload": f"{spec.name} {args.dtype} single-stream greedy decode through a layer chain of {n} stage(s) in one process "
-                               f"(RWKV_MI_DEVICES={devices}; C++ decode loop, one direct launch per stage, the residual stream stored by a stage's last layer in the next stage's buffer)",
-                   "layers": spec.n_layer, "n_embed": spec.n_embed, "n_vocab": spec.n_vocab, "parallelism": f"pp{n} (one process)"},
-        "multi_stream": {"streams": len(streams), "tokens_per_s_aggregate": len(streams) * args.steps / (mms / 1e3), "ms_per_step": mms / args.steps,
-                         "note": "independent decode streams (clones) interleaved through the same chain: aggregate throughput"},
-    }
+    result["multi_stream"] = {"streams": len(streams), "tokens_per_s_aggregate": len(streams) * args.steps / (mms / 1e3), "ms_per_step": mms / args.steps,
+                              "note": "independent decode streams (clones) interleaved through the same chain: aggregate throughput"}
     if args.parity_tokens > 0:
         # the chain against a one-device context of the same file (itself checked against the CPU oracle by the N = 1 line and tests/)
         k = min(args.parity_tokens, args.steps)
@@ -631,6 +678,8 @@ def main():
         args.chain = True
     elif world > 1 and world != args.gpus:
         raise SystemExit(f"[bench] --gpus {args.gpus} but WORLD_SIZE={world}")
+    if world > 1 and args.dump_outputs:
+        raise SystemExit("[bench] --dump-outputs: not available for the torch.distributed.run pipeline (use --chain)")
 
     backend = os.environ.get("RWKV_BENCH_BACKEND", "nccl")   # "gloo" only for smoke-testing the N > 1 path on a single GPU
     torch.cuda.set_device(local_rank % max(1, torch.cuda.device_count()))
@@ -663,7 +712,7 @@ def main():
         result = bench_prefill(args, pkg, lib, path, spec, torch)
     else:
         result = bench_decode(args, pkg, lib, path, spec, torch)
-        if args.config == "rwkv6-7b" and args.dtype == "Q4_0" and not args.no_other_configs:
+        if args.full and args.config == "rwkv6-7b" and args.dtype == "Q4_0" and not args.no_other_configs:
             result["other_configs"] = other_configs(args, pkg, lib, synth, torch)
     if rank == 0:
         print(json.dumps(result))

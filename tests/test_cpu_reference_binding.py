@@ -1,8 +1,8 @@
 """The reference's own ctypes wrapper (python/rwkv_cpp/rwkv_cpp_shared_library.py:49-107) bound, unmodified, to librwkv.so.
 
-It is imported BY PATH from /root/reference (never copied); that mount only exists in the dev container, where there is no GPU,
-so this covers what can be checked without one: every symbol / signature the wrapper declares resolves in librwkv.so, the
-non-compute entry points answer, and failures surface the way the wrapper expects (NULL -> ValueError). On the GPU box the
+It is imported BY PATH from oracle/_ref/py/, where __graft_entry__.build() stages it unmodified (`make -C oracle ref_py`, git-ignored)
+when the reference sources are present; this covers what can be checked without a GPU: every symbol / signature the wrapper declares
+resolves in librwkv.so, the non-compute entry points answer, and failures surface the way the wrapper expects (NULL -> ValueError). On the GPU box the
 compute side of the boundary is exercised by the reference's C programs (tests/test_gpu_reference_programs.py) and by
 rwkv.cpp_amd/rwkv_cpp.py, which mirrors this wrapper method for method."""
 import importlib.util
@@ -11,9 +11,10 @@ import os
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_PY = "/root/reference/python/rwkv_cpp"
+REF_PY = os.path.join(ROOT, "oracle", "_ref", "py")
 
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF_PY), reason="reference mount absent (GPU box): nothing to import")
+pytestmark = pytest.mark.skipif(not os.path.isfile(os.path.join(REF_PY, "rwkv_cpp_shared_library.py")),
+                                reason="oracle/_ref/py is not staged (build() stages it where the reference sources exist): nothing to import")
 
 
 def _ref_module(name):

@@ -4,7 +4,7 @@
 # chain against a one-device context inside each run.
 cd "$(dirname "$0")/.."; T=${1:-r06c5}; O=gpurun_out/$T; mkdir -p $O
 export TMPDIR=/tmp RWKV_BENCH_DIR=/tmp
-B="timeout 600 python bench.py --config rwkv6-7b --dtype Q8_0 --cpu-seconds 0 --abi-tokens 0 --no-profile --no-other-configs --steps 96 --warmup 8"
+B="timeout 600 python bench.py --full --config rwkv6-7b --dtype Q8_0 --cpu-seconds 0 --abi-tokens 0 --no-profile --no-other-configs --steps 96 --warmup 8"
 $B > $O/one.json 2> $O/one.err
 for devs in 0,0 0,0,0,0 0,0,0,0,0,0,0,0; do n=$(echo $devs | tr ',' '\n' | wc -l); $B --gpus $n --chain --chain-devices $devs > $O/chain$n.json 2> $O/chain$n.err; done
 python - $O <<'PY' | tee $O/c5_chain.txt

@@ -16,7 +16,7 @@ KS=$(python -c "import bench; print(bench.kernel_source_stamp(2))")
 for c in "rwkv6-7b 7b" "rwkv6-1b6 1b6"; do cfg=${c% *}; n=${c#* }
   ( cd /tmp
     for ctr in FETCH_SIZE WRITE_SIZE; do
-      RWKV_MI_NO_AUTOTUNE=1 RWKV_MI_PERSIST=ring RWKV_BENCH_NO_COLD=1 timeout 300 rocprofv3 --pmc $ctr --output-format csv -d $R/$O/pmc_${n}_$ctr -o p -- python $R/bench.py --config $cfg --dtype Q4_0 --steps 8 --warmup 2 --cpu-seconds 0 --abi-tokens 0 --no-profile --parity-tokens 0 --no-other-configs > /dev/null 2> $R/$O/pmc_${n}_$ctr.err
+      RWKV_MI_NO_AUTOTUNE=1 RWKV_MI_PERSIST=ring RWKV_BENCH_NO_COLD=1 timeout 300 rocprofv3 --pmc $ctr --output-format csv -d $R/$O/pmc_${n}_$ctr -o p -- python $R/bench.py --full --config $cfg --dtype Q4_0 --steps 8 --warmup 2 --cpu-seconds 0 --abi-tokens 0 --no-profile --parity-tokens 0 --no-other-configs > /dev/null 2> $R/$O/pmc_${n}_$ctr.err
     done )
   python tools/pmc_summary.py $O/pmc_${n}_FETCH_SIZE $O/pmc_${n}_WRITE_SIZE k6_ring $cfg:Q4_0:path2:kind2 profiles/pmc_traffic.json $KS | tee $O/pmc_${n}_summary.txt
 done
@@ -25,8 +25,8 @@ ln -sfn pmc_7b_FETCH_SIZE $O/pmc_fetch; ln -sfn pmc_7b_WRITE_SIZE $O/pmc_write
 bash tools/gpu_pmc_p47.sh $T/pmc47 > $O/pmc47.log 2>&1; tail -2 $O/pmc47.log
 cp profiles/pmc_traffic.json $O/pmc_traffic.json
 RWKV_FINAL_SKIP_SUITE=1 RWKV_FINAL_SKIP_PMC=1 bash tools/gpu_final.sh $T
-SECONDS=0; timeout 600 python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench.py (no flags) wall: ${SECONDS}s" | tee $O/bench_default_wall.txt
-( cd /tmp; timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof_1b6 -o decode -- python $R/bench.py --config rwkv6-1b6 --dtype Q4_0 --steps 64 --warmup 8 --cpu-seconds 0 --abi-tokens 0 --no-profile > /dev/null 2> $R/$O/rocprof_1b6.err )
+SECONDS=0; timeout 600 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench.py (no flags) wall: ${SECONDS}s" | tee $O/bench_default_wall.txt
+( cd /tmp; timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof_1b6 -o decode -- python $R/bench.py --full --config rwkv6-1b6 --dtype Q4_0 --steps 64 --warmup 8 --cpu-seconds 0 --abi-tokens 0 --no-profile > /dev/null 2> $R/$O/rocprof_1b6.err )
 timeout 200 python tools/trace_p47.py rwkv4-169m Q5_1 11 > $O/p47_phase_trace_v4_169m.txt 2>&1
 timeout 300 python tools/trace_p47.py rwkv7-2b9 Q5_1 9 > $O/p47_phase_trace_v7_2b9.txt 2>&1
 timeout 300 python tools/abi_pinned.py > $O/abi_pinned.txt 2>&1

@@ -18,6 +18,6 @@ PY
 for c in "rwkv7-2b9 Q5_1" "rwkv6-1b6 FP16" "rwkv6-1b6 FP32"; do set -- $c
   for fx in default split split2 wide; do
     if [ $fx = default ]; then unset RWKV_MI_FX; else export RWKV_MI_FX=$fx; fi
-    timeout 600 python bench.py --mode prefill --config $1 --dtype $2 --steps 3 --warmup 1 --cpu-seconds 0 > $O/prefill_$1_$2.$fx.json 2> $O/prefill_$1_$2.$fx.err; line $O/prefill_$1_$2.$fx.json
+    timeout 600 python bench.py --full --mode prefill --config $1 --dtype $2 --steps 3 --warmup 1 --cpu-seconds 0 > $O/prefill_$1_$2.$fx.json 2> $O/prefill_$1_$2.$fx.err; line $O/prefill_$1_$2.$fx.json
   done
 done 2>&1 | tee $O/fx_forms.txt

@@ -6,7 +6,7 @@
 cd "$(dirname "$0")/.."; T=${1:-r06h}; O=gpurun_out/$T; mkdir -p $O
 export TMPDIR=/tmp RWKV_BENCH_DIR=/tmp
 [ -n "${RWKV_HOP_SKIP_TESTS:-}" ] || ( timeout 900 python -m pytest tests/test_gpu_pipeline_cpp.py tests/test_gpu_pipeline.py tests/test_gpu_ipc_ranks.py tests/test_gpu_mega.py tests/test_gpu_persist_v47.py -x -q -m gpu -p no:cacheprovider 2>&1 | tail -8 ) | tee $O/pytest_pipeline.txt
-B="timeout 400 python bench.py --cpu-seconds 0 --abi-tokens 0 --no-profile --no-other-configs"
+B="timeout 400 python bench.py --full --cpu-seconds 0 --abi-tokens 0 --no-profile --no-other-configs"
 line() { python - "$1" <<'PY'
 import json,sys
 try:

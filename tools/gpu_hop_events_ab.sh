@@ -1,7 +1,7 @@
 cd /root/repo; O=gpurun_out/r06h3; mkdir -p $O
 export TMPDIR=/tmp RWKV_BENCH_DIR=/tmp
 ( timeout 900 python -m pytest tests/test_gpu_pipeline_cpp.py tests/test_gpu_pipeline.py tests/test_gpu_ipc_ranks.py -x -q -m gpu -p no:cacheprovider 2>&1 | tail -3 ) | tee $O/pytest.txt
-B="timeout 400 python bench.py --cpu-seconds 0 --abi-tokens 0 --no-profile --no-other-configs --steps 128 --warmup 16"
+B="timeout 400 python bench.py --full --cpu-seconds 0 --abi-tokens 0 --no-profile --no-other-configs --steps 128 --warmup 16"
 line() { python - "$1" <<'PY'
 import json,sys
 try:

@@ -12,7 +12,7 @@ for set in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS
            "SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_WAIT_ANY SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_INSTS_VMEM_RD" \
            "SQ_INSTS_SMEM SQ_INSTS_BRANCH SQ_IFETCH SQ_INST_CYCLES_VMEM SQ_LDS_BANK_CONFLICT SQ_INSTS_VMEM_WR SQ_WAVES"; do
   i=$((i+1))
-  RWKV_MI_PERSIST=$kind timeout 200 rocprofv3 --pmc $set --output-format csv -d $R/$O/${kind}_p$i -o p -- python $R/bench.py --steps 6 --warmup 2 --cpu-seconds 0 --abi-tokens 0 --no-profile --parity-tokens 0 > /dev/null 2> $R/$O/${kind}_p$i.err
+  RWKV_MI_PERSIST=$kind timeout 200 rocprofv3 --pmc $set --output-format csv -d $R/$O/${kind}_p$i -o p -- python $R/bench.py --full --steps 6 --warmup 2 --cpu-seconds 0 --abi-tokens 0 --no-profile --parity-tokens 0 > /dev/null 2> $R/$O/${kind}_p$i.err
 done
 done
 cd $R

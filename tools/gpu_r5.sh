@@ -15,7 +15,7 @@ for l in sys.stdin.read().strip().splitlines()[-1:]:
 "; }
 bench_one() {   # name config dtype extra...
   local n=$1 c=$2 t=$3; shift 3
-  timeout 300 python bench.py --config $c --dtype $t --steps 256 --warmup 16 --cpu-seconds 0 "$@" > $O/bench_$n.json 2> $O/bench_$n.err; tail -1 $O/bench_$n.json | line $n
+  timeout 300 python bench.py --full --config $c --dtype $t --steps 256 --warmup 16 --cpu-seconds 0 "$@" > $O/bench_$n.json 2> $O/bench_$n.err; tail -1 $O/bench_$n.json | line $n
 }
 case $STEP in
 p47all)
@@ -35,7 +35,7 @@ p47trace)
   timeout 300 python tools/trace_p47.py rwkv7-2b9 Q5_1 9 > $O/trace_v7.txt 2>&1; cat $O/trace_v7.txt | tail -45
   R=$PWD
   for c in "v4 rwkv4-169m" "v7 rwkv7-2b9"; do n=${c% *}; cfg=${c#* }
-    ( cd /tmp && rm -rf /tmp/prof_$n && timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/prof_$n -o p -- python $R/bench.py --config $cfg --dtype Q5_1 --steps 64 --warmup 8 --cpu-seconds 0 --abi-tokens 0 --no-profile > /tmp/prof_$n.log 2>&1 ) || tail -3 /tmp/prof_$n.log
+    ( cd /tmp && rm -rf /tmp/prof_$n && timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/prof_$n -o p -- python $R/bench.py --full --config $cfg --dtype Q5_1 --steps 64 --warmup 8 --cpu-seconds 0 --abi-tokens 0 --no-profile > /tmp/prof_$n.log 2>&1 ) || tail -3 /tmp/prof_$n.log
     f=$(find /tmp/prof_$n -name "*kernel_stats.csv" | head -1); if [ -n "$f" ]; then cp $f $O/decode_${n}_kernel_stats.csv; head -8 $f | cut -c1-160; fi
   done
   ;;
@@ -67,12 +67,12 @@ ab)     # A/B/A/B of lib/ against a variant build of persist_v47.hip in lib_b/ (
   if [ -n "${TRACE_V7:-}" ]; then timeout 300 python tools/trace_p47.py rwkv7-2b9 Q5_1 9 > $O/trace_v7_l9.txt 2>&1; sed -n 2,31p $O/trace_v7_l9.txt; fi
   ;;
 pffdbg)
-  for d in 0 1 2 3 4 7; do RWKV_MI_PFF_DBG=$d timeout 200 python bench.py --config rwkv6-1b6 --dtype Q4_0 --mode prefill --steps 4 --warmup 1 --cpu-seconds 0 --parity-tokens 0 2>/dev/null | python -c "
+  for d in 0 1 2 3 4 7; do RWKV_MI_PFF_DBG=$d timeout 200 python bench.py --full --config rwkv6-1b6 --dtype Q4_0 --mode prefill --steps 4 --warmup 1 --cpu-seconds 0 --parity-tokens 0 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']; print('dbg $d', round(d['value'],1), 'tok/s', round(d['ms_per_step'],3), 'ms', 'gemm avg us', round(r['avg_launch_us'],2), flush=True)"; done
   ;;
 prefillbench)
-  for a in fast exact; do RWKV_MI_SEQ_Q=$a timeout 300 python bench.py --config rwkv6-1b6 --dtype Q4_0 --mode prefill --steps 5 --warmup 2 --cpu-seconds 0 --parity-tokens 0 2>/dev/null | python -c "
+  for a in fast exact; do RWKV_MI_SEQ_Q=$a timeout 300 python bench.py --full --config rwkv6-1b6 --dtype Q4_0 --mode prefill --steps 5 --warmup 2 --cpu-seconds 0 --parity-tokens 0 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']; print('$a', round(d['value'],1), 'tok/s', round(d['ms_per_step'],3), 'ms', 'gemm avg us', round(r['avg_launch_us'],2), 'TOP/s', round(r['achieved'],1), flush=True)"; done
   ;;
@@ -83,13 +83,13 @@ import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d.get('roofline',{}); p=d.get('parity',{})
 print('$1', round(d['value'],1), d['unit'], round(d['ms_per_step'],3), 'ms/pass', 'gemm TOP/s', round(r.get('achieved',0),1), 'avg_us', round(r.get('avg_launch_us',0),2), 'launches', r.get('launches'), 'parity', p.get('equal'), p.get('exact_arm_bit_identical'), json.dumps(p.get('timed_arm',{}))[:400], flush=True)
 "; }
-  timeout 400 python bench.py --config rwkv6-1b6 --dtype Q4_0 --mode prefill --steps 5 --warmup 2 --cpu-seconds 25 --parity-tokens ${PARITY:-128} > $O/prefill_1b6_q4_0.json 2> $O/prefill_1b6.err; tail -1 $O/prefill_1b6_q4_0.json | pline 1b6
-  RWKV_MI_SEQ_Q=exact timeout 400 python bench.py --config rwkv6-1b6 --dtype Q4_0 --mode prefill --steps 5 --warmup 2 --cpu-seconds 0 --parity-tokens 0 > $O/prefill_1b6_q4_0_exact.json 2>> $O/prefill_1b6.err; tail -1 $O/prefill_1b6_q4_0_exact.json | pline 1b6-exact
-  timeout 400 python bench.py --config rwkv7-2b9 --dtype Q5_1 --mode prefill --steps 3 --warmup 1 --cpu-seconds 8 --parity-tokens 128 > $O/prefill_7v_2b9_q5_1.json 2> $O/prefill_2b9.err; tail -1 $O/prefill_7v_2b9_q5_1.json | pline 2b9
+  timeout 400 python bench.py --full --config rwkv6-1b6 --dtype Q4_0 --mode prefill --steps 5 --warmup 2 --cpu-seconds 25 --parity-tokens ${PARITY:-128} > $O/prefill_1b6_q4_0.json 2> $O/prefill_1b6.err; tail -1 $O/prefill_1b6_q4_0.json | pline 1b6
+  RWKV_MI_SEQ_Q=exact timeout 400 python bench.py --full --config rwkv6-1b6 --dtype Q4_0 --mode prefill --steps 5 --warmup 2 --cpu-seconds 0 --parity-tokens 0 > $O/prefill_1b6_q4_0_exact.json 2>> $O/prefill_1b6.err; tail -1 $O/prefill_1b6_q4_0_exact.json | pline 1b6-exact
+  timeout 400 python bench.py --full --config rwkv7-2b9 --dtype Q5_1 --mode prefill --steps 3 --warmup 1 --cpu-seconds 8 --parity-tokens 128 > $O/prefill_7v_2b9_q5_1.json 2> $O/prefill_2b9.err; tail -1 $O/prefill_7v_2b9_q5_1.json | pline 2b9
   ;;
 default)
   # the driver's own command: headline + other_configs, timed
-  SECONDS=0; timeout 600 python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench.py (no flags) wall: ${SECONDS}s"; tail -1 $O/bench_default.json | line default
+  SECONDS=0; timeout 600 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench.py (no flags) wall: ${SECONDS}s"; tail -1 $O/bench_default.json | line default
   python - <<PY
 import json
 d=json.loads(open("$O/bench_default.json").read().strip().splitlines()[-1])

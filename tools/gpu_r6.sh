@@ -12,7 +12,7 @@ for l in sys.stdin.read().strip().splitlines()[-1:]:
 "; }
 bench_one() {   # name config dtype extra...
   local n=$1 c=$2 t=$3; shift 3
-  timeout 300 python bench.py --config $c --dtype $t --steps ${STEPS:-256} --warmup 16 --cpu-seconds 0 --abi-tokens 0 --no-other-configs "$@" > $O/bench_$n.json 2> $O/bench_$n.err; tail -1 $O/bench_$n.json | line $n
+  timeout 300 python bench.py --full --config $c --dtype $t --steps ${STEPS:-256} --warmup 16 --cpu-seconds 0 --abi-tokens 0 --no-other-configs "$@" > $O/bench_$n.json 2> $O/bench_$n.err; tail -1 $O/bench_$n.json | line $n
 }
 case $STEP in
 diag)   # where round 5's kernel stands on this box + the watch-path microbenchmark + the tl poll without its watch stage
@@ -41,7 +41,7 @@ ab)     # A/B/A/B of lib/ against variant builds in lib_<x>/ (tools/build_varian
 fold)   # embedding + ln0 + argmax inside k6_ring: tests, parity against the CPU oracle, A/B against the separate launches (RWKV_MI_RING_NO_EMBED=1) and variants
   export RWKV_MI_NO_AUTOTUNE=1 RWKV_MI_PERSIST=ring
   timeout 900 python -X faulthandler -m pytest tests/test_gpu_mega.py tests/test_gpu_sampling.py tests/test_gpu_abi_stream.py -m gpu -x -q -p no:cacheprovider > $O/pytest.txt 2>&1; tail -4 $O/pytest.txt
-  timeout 300 python bench.py --config rwkv6-7b --dtype Q4_0 --steps 256 --warmup 16 --cpu-seconds 4 --parity-tokens 24 --abi-tokens 8 --no-other-configs > $O/bench_parity.json 2> $O/bench_parity.err; tail -1 $O/bench_parity.json | line parity
+  timeout 300 python bench.py --full --config rwkv6-7b --dtype Q4_0 --steps 256 --warmup 16 --cpu-seconds 4 --parity-tokens 24 --abi-tokens 8 --no-other-configs > $O/bench_parity.json 2> $O/bench_parity.err; tail -1 $O/bench_parity.json | line parity
   for rep in 1 2; do
     bench_one main_$rep rwkv6-7b Q4_0 --parity-tokens 0
     RWKV_MI_RING_NO_EMBED=1 bench_one noembed_$rep rwkv6-7b Q4_0 --parity-tokens 0
@@ -55,8 +55,8 @@ import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d.get('roofline',{}); p=d.get('parity',{}); f=d.get('fast_arms',{})
 print('\$1', round(d['value'],1), d['unit'], round(d['ms_per_step'],3), 'ms/pass', 'gemm TOP/s', round(r.get('achieved',0),1), '| fast arms', round(f.get('tokens_per_s',0),1), 'tok/s', round(f.get('gemm_TOPs_in_launches',0),1), 'TOP/s | parity', p.get('equal'), p.get('default_arms_bit_identical'), json.dumps(p.get('fast_arms',{}))[:700], flush=True)
 " | sed "s/^\\\$1/$1/"; }
-  timeout 500 python bench.py --config rwkv6-1b6 --dtype Q4_0 --mode prefill --steps 5 --warmup 2 --cpu-seconds 25 --parity-tokens ${PARITY:-128} > $O/prefill_1b6_q4_0.json 2> $O/prefill_1b6.err; tail -1 $O/prefill_1b6_q4_0.json | pline 1b6; tail -2 $O/prefill_1b6.err
-  timeout 500 python bench.py --config rwkv7-2b9 --dtype Q5_1 --mode prefill --steps 3 --warmup 1 --cpu-seconds 8 --parity-tokens 128 > $O/prefill_7v_2b9_q5_1.json 2> $O/prefill_2b9.err; tail -1 $O/prefill_7v_2b9_q5_1.json | pline 2b9; tail -2 $O/prefill_2b9.err
+  timeout 500 python bench.py --full --config rwkv6-1b6 --dtype Q4_0 --mode prefill --steps 5 --warmup 2 --cpu-seconds 25 --parity-tokens ${PARITY:-128} > $O/prefill_1b6_q4_0.json 2> $O/prefill_1b6.err; tail -1 $O/prefill_1b6_q4_0.json | pline 1b6; tail -2 $O/prefill_1b6.err
+  timeout 500 python bench.py --full --config rwkv7-2b9 --dtype Q5_1 --mode prefill --steps 3 --warmup 1 --cpu-seconds 8 --parity-tokens 128 > $O/prefill_7v_2b9_q5_1.json 2> $O/prefill_2b9.err; tail -1 $O/prefill_7v_2b9_q5_1.json | pline 2b9; tail -2 $O/prefill_2b9.err
   ;;
 sweep)  # the ring kernel's run-time knobs once more (records taken ahead in G and the deferred quantisation moved the balance): one box, alternating
   export RWKV_MI_NO_AUTOTUNE=1 RWKV_MI_PERSIST=ring

@@ -6,7 +6,7 @@ O=gpurun_out/r02a; mkdir -p $O
 export TMPDIR=/tmp RWKV_BENCH_DIR=/tmp
 ( timeout 1500 python -m pytest tests -m gpu -q -x --timeout 600 2>&1 | tail -25 ) > $O/pytest.txt
 echo "pytest done: $(tail -1 $O/pytest.txt)"
-B="timeout 600 python bench.py"
+B="timeout 600 python bench.py --full"
 $B --steps 128 --warmup 16 > $O/bench_7b_q4_0_nt.json 2> $O/bench_7b_q4_0_nt.err; tail -c 600 $O/bench_7b_q4_0_nt.json
 RWKV_LIB_DIR=lib_plain $B --steps 128 --warmup 16 --cpu-seconds 0 --abi-tokens 0 > $O/bench_7b_q4_0_plain.json 2> $O/bench_7b_q4_0_plain.err
 RWKV_MI_NO_MEGA=1 $B --steps 64 --warmup 8 --cpu-seconds 0 --abi-tokens 0 > $O/bench_7b_q4_0_fused_nt.json 2>/dev/null

@@ -16,6 +16,6 @@ except Exception as e:
 PY
 }
 for c in "rwkv7-2b9 Q5_1 3 128" "rwkv6-1b6 FP16 3 64" "rwkv6-1b6 FP32 3 64"; do set -- $c
-  timeout 600 python bench.py --mode prefill --config $1 --dtype $2 --steps $3 --warmup 1 --cpu-seconds 12 --parity-tokens $4 > $O/prefill_$1_$2.json 2> $O/prefill_$1_$2.err; line $O/prefill_$1_$2.json
-  RWKV_MI_SEQ_F=valu timeout 600 python bench.py --mode prefill --config $1 --dtype $2 --steps $3 --warmup 1 --cpu-seconds 0 > $O/prefill_$1_$2.valu.json 2> $O/prefill_$1_$2.valu.err; line $O/prefill_$1_$2.valu.json
+  timeout 600 python bench.py --full --mode prefill --config $1 --dtype $2 --steps $3 --warmup 1 --cpu-seconds 12 --parity-tokens $4 > $O/prefill_$1_$2.json 2> $O/prefill_$1_$2.err; line $O/prefill_$1_$2.json
+  RWKV_MI_SEQ_F=valu timeout 600 python bench.py --full --mode prefill --config $1 --dtype $2 --steps $3 --warmup 1 --cpu-seconds 0 > $O/prefill_$1_$2.valu.json 2> $O/prefill_$1_$2.valu.err; line $O/prefill_$1_$2.valu.json
 done 2>&1 | tee $O/seq_f_exact.txt

@@ -135,6 +135,33 @@ RWKV_API const float * rwkv_mi_logits_device_ptr(const struct rwkv_context * ctx
  * Diagnostic, read-only: bench.py places its parity run across the 16-bit wrap with it. 0 if path 2 is off. */
 RWKV_API uint32_t rwkv_mi_decode_generation(struct rwkv_context * ctx);
 
+/* ---- Batched decode: n independent sequences per pass over the weights ----
+ * A batch owns n_slots device-resident states ([2][n_slots][state_len], double-buffered with a parity per slot) for ctx's model, and
+ * its own stream, scratch and [n_slots][n_vocab] logits buffer. Single-device contexts only (not a RWKV_MI_DEVICES chain). It must be
+ * freed before ctx; errors are reported on ctx (rwkv_get_last_error). One batch object is not thread-safe.
+ * Each row of a call is bit-identical to rwkv_eval of that sequence alone. A call reads each named slot's current buffer, writes the
+ * other one and flips the slot's parity only when the pass succeeded; slots not named are untouched. A call returns false with
+ * RWKV_ERROR_ARGS and changes no slot when n == 0, n > n_slots, a slot index is out of range or repeated, or a token is >= n_vocab.
+ * On a device that also runs a persistent decode kernel, batch passes and persistent launches are ordered on the device, never concurrent. */
+struct rwkv_mi_batch;
+RWKV_API struct rwkv_mi_batch * rwkv_mi_batch_create(struct rwkv_context * ctx, size_t n_slots);
+RWKV_API void rwkv_mi_batch_free(struct rwkv_mi_batch * batch);
+/* host state (or a fresh state when NULL) into a slot / a slot into host memory (FP32[rwkv_get_state_len]) */
+RWKV_API bool rwkv_mi_batch_state_load(struct rwkv_mi_batch * batch, size_t slot, const float * state_in);
+RWKV_API bool rwkv_mi_batch_state_store(struct rwkv_mi_batch * batch, size_t slot, float * state_out);
+/* device-to-device: a context's resident state into a slot, and a slot into a context's resident state (prefill on a context, then join
+ * the batch). ctx must be a single-device context of the same device and state size. */
+RWKV_API bool rwkv_mi_batch_state_from_context(struct rwkv_mi_batch * batch, size_t slot, struct rwkv_context * ctx);
+RWKV_API bool rwkv_mi_batch_state_to_context(struct rwkv_mi_batch * batch, size_t slot, struct rwkv_context * ctx);
+/* One token for each of n slots in ONE pass over the weights: row i = slots[i] fed tokens[i].
+ * logits_out: [n][n_vocab] in call order, or NULL to skip the head. */
+RWKV_API bool rwkv_mi_batch_eval(struct rwkv_mi_batch * batch, const uint32_t * slots, const uint32_t * tokens, size_t n, float * logits_out);
+/* Greedy loop on the device: as rwkv_mi_decode_greedy on each slot, all n advancing together (the argmax of each row feeds that row's
+ * next embedding lookup, no host round trip). tokens_out: [n][n_tokens] (may be NULL); elapsed_ms as rwkv_mi_decode_greedy. A failure
+ * after the first pass leaves the named slots' states unspecified. */
+RWKV_API bool rwkv_mi_batch_decode_greedy(struct rwkv_mi_batch * batch, const uint32_t * slots, const uint32_t * first_tokens, size_t n,
+                                          size_t n_tokens, uint32_t * tokens_out, float * elapsed_ms);
+
 #if defined(__cplusplus)
 }
 #endif

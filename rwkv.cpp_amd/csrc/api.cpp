@@ -594,3 +594,220 @@ RWKV_API uint32_t rwkv_mi_decode_generation(struct rwkv_context * ctx) {
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------
+// Batched decode (rwkv_mi_batch_*): n sequences per pass over the weights. The slots' states are [2][n_slots][state_len] in HBM with a
+// parity per slot; a pass reads slot s at buffer parity[s] and writes buffer parity[s] ^ 1 through a row table ({in, out} per row,
+// uploaded through pinned staging). The pass itself is the per-op Runner in row mode on the batch's own context (engine.hip forward_rows).
+// ---------------------------------------------------------------------------------------------------------------
+struct rwkv_mi_batch {
+    rwkv_context * ctx = nullptr;      // the caller's context: model, device, error word
+    rwkv_context * run = nullptr;      // the batch's own context (stream, scratch, tokens, logits)
+    size_t n_slots = 0;
+    int64_t state_len = 0;
+    float * states = nullptr;          // [2][n_slots][state_len]
+    std::vector<uint8_t> parity;
+    RowState * d_rows = nullptr;       // [2][n_slots]: the row tables of a call (the greedy loop alternates between the two)
+    RowState * h_rows = nullptr;       // pinned staging of the same
+
+    float * slot_buf(size_t slot, int p) const { return states + ((size_t) p * n_slots + slot) * (size_t) state_len; }
+};
+
+// errors of the batch's own context are reported on the caller's
+static bool batch_fail_through(rwkv_mi_batch * B) { B->ctx->last_error |= B->run->last_error; B->run->last_error = 0; return false; }
+
+#define BATCH_HIP_OK(B, CALL) \
+    do { hipError_t e_ = (CALL); RW_CTX_CHECK((B)->ctx, RWKV_ERROR_GRAPH, false, e_ == hipSuccess, "HIP error: %s", hipGetErrorString(e_)); } while (0)
+
+// n, slots and tokens of a call: no slot changes when they are rejected
+static bool batch_check_call(rwkv_mi_batch * B, const uint32_t * slots, const uint32_t * tokens, size_t n) {
+    rwkv_context * ctx = B->ctx;
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, slots != nullptr && tokens != nullptr, "slots or tokens is NULL");
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, n > 0 && n <= B->n_slots, "n (%zu) must be in 1 .. %zu", n, B->n_slots);
+    const size_t n_vocab = (size_t) ctx->model->n_vocab();
+    std::vector<uint8_t> seen(B->n_slots, 0);
+    for (size_t i = 0; i < n; i++) {
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, slots[i] < B->n_slots, "slot %" PRIu32 " at index %zu is out of range (0 .. %zu)", slots[i], i, B->n_slots - 1);
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, !seen[slots[i]], "slot %" PRIu32 " appears twice", slots[i]);
+        seen[slots[i]] = 1;
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, tokens[i] < n_vocab, "Token at index %zu (%" PRIu32 ") is out of range (0 .. %zu)", i, tokens[i], n_vocab - 1);
+    }
+    return true;
+}
+
+// row tables of the n named slots (table 0: current -> other buffer, table 1: the reverse) and the tokens into the batch's device words
+static bool batch_upload(rwkv_mi_batch * B, const uint32_t * slots, const uint32_t * tokens, size_t n, int tables) {
+    rwkv_context * run = B->run;
+    BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));   // (the previous call's copies may still read the staging)
+    for (int tb = 0; tb < tables; tb++)
+        for (size_t i = 0; i < n; i++) {
+            const int p = B->parity[slots[i]] ^ tb;
+            B->h_rows[(size_t) tb * B->n_slots + i] = RowState{B->slot_buf(slots[i], p), B->slot_buf(slots[i], p ^ 1)};
+        }
+    memcpy(run->h_tokens, tokens, n * sizeof(uint32_t));
+    for (int tb = 0; tb < tables; tb++)
+        BATCH_HIP_OK(B, hipMemcpyAsync(B->d_rows + (size_t) tb * B->n_slots, B->h_rows + (size_t) tb * B->n_slots, n * sizeof(RowState), hipMemcpyHostToDevice, run->stream));
+    BATCH_HIP_OK(B, hipMemcpyAsync(run->d_tokens, run->h_tokens, n * sizeof(uint32_t), hipMemcpyHostToDevice, run->stream));
+    return true;
+}
+
+extern "C" {
+
+RWKV_API void rwkv_mi_batch_free(struct rwkv_mi_batch * B) {
+    if (!B) return;
+    if (B->run) {
+        (void) hipSetDevice(B->run->model->device);
+        (void) hipStreamSynchronize(B->run->stream);
+    }
+    if (B->states) (void) hipFree(B->states);
+    if (B->d_rows) (void) hipFree(B->d_rows);
+    if (B->h_rows) (void) hipHostFree(B->h_rows);
+    batch_context_destroy(B->run);
+    delete B;
+}
+
+RWKV_API struct rwkv_mi_batch * rwkv_mi_batch_create(struct rwkv_context * ctx, size_t n_slots) {
+    RW_CHECK(RWKV_ERROR_ARGS, nullptr, ctx != nullptr, "ctx is NULL");
+    ctx->last_error = RWKV_ERROR_NONE;
+    RW_NO_PIPELINE(ctx, nullptr);
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, nullptr, n_slots > 0 && n_slots <= ((size_t) 1 << 20), "n_slots (%zu) out of range", n_slots);
+    Model & m = *ctx->model;
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS | RWKV_ERROR_UNSUPPORTED, nullptr, m.has_embed && m.has_head, "a batch needs a whole model (embedding and head)");
+    std::unique_ptr<rwkv_mi_batch, void (*)(rwkv_mi_batch *)> B(new (std::nothrow) rwkv_mi_batch(), rwkv_mi_batch_free);
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, nullptr, B != nullptr, "out of memory");
+    B->ctx = ctx;
+    B->n_slots = n_slots;
+    B->state_len = m.state_len();
+    B->parity.assign(n_slots, 0);
+    RW_CTX_CHECK(ctx, RWKV_ERROR_GRAPH, nullptr, hipSetDevice(m.device) == hipSuccess, "hipSetDevice failed");
+    B->run = batch_context_create(&m, (int64_t) n_slots);
+    RW_CTX_CHECK(ctx, RWKV_ERROR_CTX | RWKV_ERROR_ALLOC, nullptr, B->run != nullptr, "cannot create the batch's stream / buffers (device memory?)");
+    B->run->print_errors = ctx->print_errors;
+    const size_t sbytes = (size_t) B->state_len * sizeof(float);
+    hipError_t e = hipMalloc((void **) &B->states, 2 * n_slots * sbytes);
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, nullptr, e == hipSuccess, "cannot allocate %zu slot states: %s", n_slots, hipGetErrorString(e));
+    e = hipMalloc((void **) &B->d_rows, 2 * n_slots * sizeof(RowState));
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, nullptr, e == hipSuccess, "HIP error: %s", hipGetErrorString(e));
+    e = hipHostMalloc((void **) &B->h_rows, 2 * n_slots * sizeof(RowState), hipHostMallocDefault);
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, nullptr, e == hipSuccess, "HIP error: %s", hipGetErrorString(e));
+    // every slot starts from the fresh state (both buffers: a slot's first pass reads buffer 0)
+    for (size_t s = 0; s < n_slots; s++) {
+        float * dst = B->slot_buf(s, 0);
+        if (m.arch_major >= 5) e = hipMemsetAsync(dst, 0, sbytes, B->run->stream);
+        else { launch_fill_state_v4(dst, m.n_layer(), m.n_embed(), B->run->stream); e = hipGetLastError(); }
+        if (e != hipSuccess) break;
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(B->run->stream);
+    RW_CTX_CHECK(ctx, RWKV_ERROR_GRAPH, nullptr, e == hipSuccess, "HIP error: %s", hipGetErrorString(e));
+    return B.release();
+}
+
+RWKV_API bool rwkv_mi_batch_state_load(struct rwkv_mi_batch * B, size_t slot, const float * state_in) {
+    rwkv_context * ctx = B->ctx;
+    ctx->last_error = RWKV_ERROR_NONE;
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, slot < B->n_slots, "slot %zu is out of range", slot);
+    const Model & m = *ctx->model;
+    BATCH_HIP_OK(B, hipSetDevice(m.device));
+    hipStream_t st = B->run->stream;
+    BATCH_HIP_OK(B, hipStreamSynchronize(st));
+    float * dst = B->slot_buf(slot, B->parity[slot]);
+    const size_t sbytes = (size_t) B->state_len * sizeof(float);
+    if (state_in) BATCH_HIP_OK(B, hipMemcpyAsync(dst, state_in, sbytes, hipMemcpyHostToDevice, st));
+    else if (m.arch_major >= 5) BATCH_HIP_OK(B, hipMemsetAsync(dst, 0, sbytes, st));
+    else { launch_fill_state_v4(dst, m.n_layer(), m.n_embed(), st); BATCH_HIP_OK(B, hipGetLastError()); }
+    BATCH_HIP_OK(B, hipStreamSynchronize(st));
+    return true;
+}
+
+RWKV_API bool rwkv_mi_batch_state_store(struct rwkv_mi_batch * B, size_t slot, float * state_out) {
+    rwkv_context * ctx = B->ctx;
+    ctx->last_error = RWKV_ERROR_NONE;
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, slot < B->n_slots && state_out != nullptr, "slot %zu is out of range or state_out is NULL", slot);
+    BATCH_HIP_OK(B, hipSetDevice(ctx->model->device));
+    hipStream_t st = B->run->stream;
+    BATCH_HIP_OK(B, hipMemcpyAsync(state_out, B->slot_buf(slot, B->parity[slot]), (size_t) B->state_len * sizeof(float), hipMemcpyDeviceToHost, st));
+    BATCH_HIP_OK(B, hipStreamSynchronize(st));
+    return true;
+}
+
+// a context whose resident state can be exchanged with the batch's slots: one device, same device, same state size
+static bool batch_peer_ok(rwkv_mi_batch * B, size_t slot, rwkv_context * other) {
+    rwkv_context * ctx = B->ctx;
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, slot < B->n_slots && other != nullptr, "slot %zu is out of range or the context is NULL", slot);
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS | RWKV_ERROR_UNSUPPORTED, false, other->stages.empty(), "a RWKV_MI_DEVICES chain cannot exchange state with a batch");
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, other->model->device == ctx->model->device && other->model->state_len() == B->state_len,
+                 "the context is on another device or has another state size");
+    return true;
+}
+
+RWKV_API bool rwkv_mi_batch_state_from_context(struct rwkv_mi_batch * B, size_t slot, struct rwkv_context * other) {
+    B->ctx->last_error = RWKV_ERROR_NONE;
+    if (!batch_peer_ok(B, slot, other)) return false;
+    BATCH_HIP_OK(B, hipSetDevice(other->model->device));
+    BATCH_HIP_OK(B, hipStreamSynchronize(other->stream));     // (the context's last step has written its state)
+    hipStream_t st = B->run->stream;
+    BATCH_HIP_OK(B, hipMemcpyAsync(B->slot_buf(slot, B->parity[slot]), other->state[other->cur], (size_t) B->state_len * sizeof(float), hipMemcpyDeviceToDevice, st));
+    BATCH_HIP_OK(B, hipStreamSynchronize(st));
+    return true;
+}
+
+RWKV_API bool rwkv_mi_batch_state_to_context(struct rwkv_mi_batch * B, size_t slot, struct rwkv_context * other) {
+    B->ctx->last_error = RWKV_ERROR_NONE;
+    if (!batch_peer_ok(B, slot, other)) return false;
+    BATCH_HIP_OK(B, hipSetDevice(other->model->device));
+    hipStream_t st = B->run->stream;
+    BATCH_HIP_OK(B, hipStreamSynchronize(st));
+    BATCH_HIP_OK(B, hipMemcpyAsync(other->state[other->cur], B->slot_buf(slot, B->parity[slot]), (size_t) B->state_len * sizeof(float), hipMemcpyDeviceToDevice, other->stream));
+    BATCH_HIP_OK(B, hipStreamSynchronize(other->stream));
+    return true;
+}
+
+RWKV_API bool rwkv_mi_batch_eval(struct rwkv_mi_batch * B, const uint32_t * slots, const uint32_t * tokens, size_t n, float * logits_out) {
+    rwkv_context * ctx = B->ctx;
+    ctx->last_error = RWKV_ERROR_NONE;
+    if (!batch_check_call(B, slots, tokens, n)) return false;
+    rwkv_context * run = B->run;
+    run->print_errors = ctx->print_errors;
+    BATCH_HIP_OK(B, hipSetDevice(ctx->model->device));
+    if (!batch_upload(B, slots, tokens, n, 1)) return false;
+    if (!forward_rows(run, B->d_rows, (int64_t) n, logits_out != nullptr)) return batch_fail_through(B);
+    if (logits_out) BATCH_HIP_OK(B, hipMemcpyAsync(logits_out, run->d_logits, n * (size_t) ctx->model->n_vocab() * sizeof(float), hipMemcpyDeviceToHost, run->stream));
+    BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));
+    for (size_t i = 0; i < n; i++) B->parity[slots[i]] ^= 1;
+    return true;
+}
+
+RWKV_API bool rwkv_mi_batch_decode_greedy(struct rwkv_mi_batch * B, const uint32_t * slots, const uint32_t * first_tokens, size_t n,
+                                          size_t n_tokens, uint32_t * tokens_out, float * elapsed_ms) {
+    rwkv_context * ctx = B->ctx;
+    ctx->last_error = RWKV_ERROR_NONE;
+    if (!batch_check_call(B, slots, first_tokens, n)) return false;
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, n_tokens > 0, "n_tokens is 0");
+    rwkv_context * run = B->run;
+    run->print_errors = ctx->print_errors;
+    const int64_t n_vocab = ctx->model->n_vocab();
+    BATCH_HIP_OK(B, hipSetDevice(ctx->model->device));
+    struct DevBuf { uint32_t * p = nullptr; ~DevBuf() { if (p) (void) hipFree(p); } } hist;   // [n_tokens][n], freed on every exit
+    BATCH_HIP_OK(B, hipMalloc((void **) &hist.p, n_tokens * n * sizeof(uint32_t)));
+    if (!batch_upload(B, slots, first_tokens, n, 2)) return false;
+    BATCH_HIP_OK(B, hipEventRecord(run->ev0, run->stream));
+    for (size_t i = 0; i < n_tokens; i++) {
+        // step i reads the buffers step i - 1 wrote: the two row tables alternate; the argmax of each row lands where its next embedding reads it
+        if (!forward_rows(run, B->d_rows + (i & 1) * B->n_slots, (int64_t) n, true)) {
+            (void) hipStreamSynchronize(run->stream);
+            return batch_fail_through(B);
+        }
+        launch_argmax_rows(run->d_logits, (int64_t) n, n_vocab, run->d_tokens, hist.p + i * n, run->stream);
+    }
+    BATCH_HIP_OK(B, hipEventRecord(run->ev1, run->stream));
+    std::vector<uint32_t> h(tokens_out ? n_tokens * n : 0);
+    if (tokens_out) BATCH_HIP_OK(B, hipMemcpyAsync(h.data(), hist.p, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream));
+    BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));
+    if (elapsed_ms) BATCH_HIP_OK(B, hipEventElapsedTime(elapsed_ms, run->ev0, run->ev1));
+    for (size_t r = 0; r < n && tokens_out; r++)
+        for (size_t i = 0; i < n_tokens; i++) tokens_out[r * n_tokens + i] = h[i * n + r];
+    if (n_tokens & 1) for (size_t i = 0; i < n; i++) B->parity[slots[i]] ^= 1;
+    return true;
+}
+
+}  // extern "C"

@@ -393,6 +393,11 @@ struct Runner {
     rwkv_context::Buf & b;
 
     bool failed = false;   // a launch of the pass could not be made (allocation failure): its outputs are not valid
+    // Row mode (batched decode, rwkv_mi_batch_*): row t is its own sequence; its state is rows[t] (device table) instead of the context's
+    // state[cur] -> state[cur ^ 1]. The single-token paths (persistent / fused) are never taken, T == 1 included.
+    const RowState * rows = nullptr;
+    const float * s_in = nullptr;   // (not row mode) the state the pass reads / writes
+    float * s_out = nullptr;
 
     // inputs quantised ahead of their products, several per launch (sequence mode): source pointer -> tile image
     struct Pre { const float * x = nullptr; int wtype = -1; int64_t K = 0; TileAct ta; } pre[5];
@@ -410,6 +415,7 @@ struct Runner {
     void drop_pre() { for (auto & e : pre) e = Pre(); }
     // tile images for n outputs of a fused mix (sequence mode, all consumers quantised with `wtype`): registered like prequant's
     bool fused_outs(int n, float * const * keys, int wtype, TileAct * tas) {
+        if (rows) return false;   // (row mode: the quantising mixes carry across rows; k_mix_rows + prequant instead)
         if (!(dtype_quantized(wtype) && T >= k_mfma_min_tokens && b.tiles[0] && D % 256 == 0 && n <= 5)) return false;
         for (auto & e : pre) e = Pre();
         for (int i = 0; i < n; i++) { tas[i] = tile_act_at(b.tiles[i], T, D); pre[i].x = keys[i]; pre[i].wtype = wtype; pre[i].K = D; pre[i].ta = tas[i]; }
@@ -483,10 +489,19 @@ struct Runner {
         drop_pre();
     }
     // WKV-5/6: long sequences on the lane-pipelined kernel (one wave per value column), otherwise one wave per head
+    // (so: offset of the layer's WKV state in a state buffer)
     void wkv6(const float * r, const float * k, const float * v, const float * u, int u_per_chan, const float * w, int w_mode,
-              const float * state_in, float * state_out, float * out) {
-        if (S == 64 && T >= k_mfma_min_tokens) launch_wkv6_seq(r, k, v, u, u_per_chan, w, w_mode, state_in, state_out, out, T, H, st);
-        else launch_wkv6(r, k, v, u, u_per_chan, w, w_mode, state_in, state_out, out, T, H, S, st);
+              int64_t so, float * out) {
+        if (rows) launch_wkv6_rows(r, k, v, u, u_per_chan, w, w_mode, rows, so, out, T, H, S, st);
+        else if (S == 64 && T >= k_mfma_min_tokens) launch_wkv6_seq(r, k, v, u, u_per_chan, w, w_mode, s_in + so, s_out + so, out, T, H, st);
+        else launch_wkv6(r, k, v, u, u_per_chan, w, w_mode, s_in + so, s_out + so, out, T, H, S, st);
+    }
+    // token-shift mix whose carry sits at offset co of a state buffer
+    void carry(MixArgs & a, int64_t co) const { if (!rows) { a.carry_in = s_in + co; a.carry_out = s_out + co; } }
+    void mix(MixArgs a, int64_t co) {
+        if (rows) { launch_mix_rows(a, rows, co, T, D, st); return; }
+        carry(a, co);
+        launch_mix(a, T, D, st);
     }
     static const float * f(const DevTensor * t) { return (const float *) t->data; }
     static Epi epi(int op, const float * bias = nullptr, const float * res = nullptr, const float * aux = nullptr) {
@@ -494,9 +509,9 @@ struct Runner {
     }
 
     // channel mixing (rwkv_ffn_v4_v5 :484-511, rwkv_ffn_v6 :513-531, rwkv_ffn_v7 :533-543)
-    void ffn(const LayerW & L, const float * sin, float * sout) {
+    void ffn(const LayerW & L, int64_t so) {
         launch_layernorm(b.x, T, D, f(L.ln2_w), f(L.ln2_b), b.xn, st);
-        MixArgs a; a.xn = b.xn; a.carry_in = sin; a.carry_out = sout;
+        MixArgs a; a.xn = b.xn; carry(a, so);
         if (m.arch_major <= 5) { a.mode = 0; a.n_out = 2; a.coef[0] = f(L.ffn_time_mix_k); a.coef[1] = f(L.ffn_time_mix_r); }
         else if (m.arch_major == 6) { a.mode = 1; a.n_out = 2; a.coef[0] = f(L.ffn_time_maa_k); a.coef[1] = f(L.ffn_time_maa_r); }
         else { a.mode = 1; a.n_out = 1; a.coef[0] = f(L.ffn_x_k); }
@@ -507,7 +522,7 @@ struct Runner {
             a.out[0] = nullptr; a.out[1] = nullptr;
             launch_mix_seq_q(a, T, D, st, tas, L.ffn_key->type);
         } else {
-            launch_mix(a, T, D, st);
+            mix(a, so);
             if (m.arch_major != 7) { const float * xs[2] = {b.m[0], b.m[1]}; prequant(2, xs, D, L.ffn_key->type); }
         }
         // Sequence mode, exact arm: the key product's only consumer is the value product, so its epilogue writes relu(k)^2 straight as that
@@ -532,42 +547,43 @@ struct Runner {
     }
 
     // rwkv_att_v4 (:163-197)
-    void att_v4(const LayerW & L, const float * sin, float * sout) {
+    void att_v4(const LayerW & L, int64_t so) {
         launch_layernorm(b.x, T, D, f(L.ln1_w), f(L.ln1_b), b.xn, st);
-        MixArgs a; a.xn = b.xn; a.carry_in = sin + D; a.carry_out = sout + D; a.mode = 0; a.n_out = 3;
+        MixArgs a; a.xn = b.xn; a.mode = 0; a.n_out = 3;
         a.coef[0] = f(L.att_time_mix_k); a.coef[1] = f(L.att_time_mix_v); a.coef[2] = f(L.att_time_mix_r);
         a.out[0] = b.m[0]; a.out[1] = b.m[1]; a.out[2] = b.m[2];
-        launch_mix(a, T, D, st);
+        mix(a, so + D);
         mm(L.att_receptance, b.m[2], b.r, epi(EPI_SIGMOID));
         mm(L.att_key, b.m[0], b.k);
         mm(L.att_value, b.m[1], b.v);
-        launch_wkv4(b.k, b.v, b.r, f(L.att_time_first), f(L.att_time_decay), sin + 2 * D, sin + 3 * D, sin + 4 * D,
-                    sout + 2 * D, sout + 3 * D, sout + 4 * D, b.out, T, D, st);
+        if (rows) launch_wkv4_rows(b.k, b.v, b.r, f(L.att_time_first), f(L.att_time_decay), rows, so + 2 * D, b.out, T, D, st);
+        else launch_wkv4(b.k, b.v, b.r, f(L.att_time_first), f(L.att_time_decay), s_in + so + 2 * D, s_in + so + 3 * D, s_in + so + 4 * D,
+                         s_out + so + 2 * D, s_out + so + 3 * D, s_out + so + 4 * D, b.out, T, D, st);
         mm(L.att_output, b.out, b.x, epi(EPI_ADD_RES, nullptr, b.x));
     }
 
     // rwkv_att_v5 (:199-292)
-    void att_v5(const LayerW & L, const float * sin, float * sout) {
+    void att_v5(const LayerW & L, int64_t so) {
         const bool v52 = m.arch_minor >= 2;
         launch_layernorm(b.x, T, D, f(L.ln1_w), f(L.ln1_b), b.xn, st);
-        MixArgs a; a.xn = b.xn; a.carry_in = sin + D; a.carry_out = sout + D; a.mode = 0; a.n_out = v52 ? 4 : 3;
+        MixArgs a; a.xn = b.xn; a.mode = 0; a.n_out = v52 ? 4 : 3;
         a.coef[0] = f(L.att_time_mix_k); a.coef[1] = f(L.att_time_mix_v); a.coef[2] = f(L.att_time_mix_r);
         if (v52) a.coef[3] = f(L.att_time_mix_g);
         for (int i = 0; i < 4; i++) a.out[i] = b.m[i];
-        launch_mix(a, T, D, st);
+        mix(a, so + D);
         mm(L.att_receptance, b.m[2], b.r);
         mm(L.att_key, b.m[0], b.k);
         mm(L.att_value, b.m[1], b.v);
         if (v52) mm(L.att_gate, b.m[3], b.g, epi(EPI_SILU));
         wkv6(b.r, b.k, b.v, v52 ? f(L.att_time_faaaa) : f(L.att_time_first), v52 ? 1 : 0, f(L.att_time_decay), v52 ? 1 : 0,
-             sin + 2 * D, sout + 2 * D, b.out);
+             so + 2 * D, b.out);
         gn_out(L, 1e-5f, v52 ? b.g : nullptr);
     }
 
     // rwkv_att_v6 (:294-385)
-    void att_v6(const LayerW & L, const float * sin, float * sout) {
+    void att_v6(const LayerW & L, int64_t so) {
         launch_layernorm(b.x, T, D, f(L.ln1_w), f(L.ln1_b), b.xn, st);
-        MixArgs a; a.xn = b.xn; a.carry_in = sin + D; a.carry_out = sout + D; a.mode = 1; a.n_out = 1;
+        MixArgs a; a.xn = b.xn; carry(a, so + D); a.mode = 1; a.n_out = 1;
         a.coef[0] = f(L.att_time_maa_x); a.out[0] = b.m[5]; a.sx = b.sx;
         {
             // sequence mode: the mix's only consumer is the W1 product -- it writes that product's quantised input image (and sx, which the
@@ -575,8 +591,8 @@ struct Runner {
             TileAct ta[1];
             if (fused_outs(1, a.out, L.att_time_maa_w1->type, ta) && getenv("RWKV_MI_NO_MIX_QUANT") == nullptr) {
                 MixArgs q = a; q.out[0] = nullptr;
-                if (!launch_mix_seq_q(q, T, D, st, ta, L.att_time_maa_w1->type)) { drop_pre(); launch_mix(a, T, D, st); }
-            } else { drop_pre(); launch_mix(a, T, D, st); }
+                if (!launch_mix_seq_q(q, T, D, st, ta, L.att_time_maa_w1->type)) { drop_pre(); mix(a, so + D); }
+            } else { drop_pre(); mix(a, so + D); }
         }
         const int64_t R5 = L.att_time_maa_w1->ne[1], R = R5 / 5;
         mm(L.att_time_maa_w1, b.m[5], b.lr1, epi(EPI_TANH));
@@ -611,16 +627,16 @@ struct Runner {
         drop_pre();
         // decay_w2 consumes [T][DR] rows of lr2
         mm(L.att_time_decay_w2, b.lr2, b.w, epi(EPI_V6_DECAY, f(L.att_time_decay)));
-        wkv6(b.r, b.k, b.v, f(L.att_time_faaaa), 1, b.w, 2, sin + 2 * D, sout + 2 * D, b.out);
+        wkv6(b.r, b.k, b.v, f(L.att_time_faaaa), 1, b.w, 2, so + 2 * D, b.out);
         gn_out(L, 64e-5f, b.g);
     }
 
     // rwkv_att_v7 (:387-482)
-    void att_v7(const LayerW & L, int layer, const float * sin, float * sout) {
+    void att_v7(const LayerW & L, int layer, int64_t so) {
         launch_layernorm(b.x, T, D, f(L.ln1_w), f(L.ln1_b), b.xn, st);
-        MixArgs a; a.xn = b.xn; a.carry_in = sin + D; a.carry_out = sout + D; a.mode = 1; a.n_out = 6;
+        MixArgs a; a.xn = b.xn; a.mode = 1; a.n_out = 6;
         for (int i = 0; i < 6; i++) { a.coef[i] = f(L.att_x_rwkvag) + (int64_t) i * D; a.out[i] = b.m[i]; }  // r, w, k, v, a, g
-        launch_mix(a, T, D, st);
+        mix(a, so + D);
         mm(L.att_receptance, b.m[0], b.r);
         mm(L.att_g1, b.m[5], b.lr1, epi(EPI_SIGMOID));
         mm(L.att_g2, b.lr1, b.g);
@@ -639,22 +655,25 @@ struct Runner {
             launch_v7_vmix(b.v, b.v_first, b.sx, T * D, st);
         }
         static const bool no_seq7 = getenv("RWKV_MI_NO_WKV7_SEQ") != nullptr;   // (measurement aid: the single-token form over the whole sequence)
-        if (S == 64 && T >= k_mfma_min_tokens && !no_seq7) launch_wkv7_seq(b.r, b.w, b.t0, b.v, b.t1, b.t2, sin + 2 * D, sout + 2 * D, b.out, T, H, st);
-        else launch_wkv7(b.r, b.w, b.t0, b.v, b.t1, b.t2, sin + 2 * D, sout + 2 * D, b.out, T, H, S, st);
+        if (rows) launch_wkv7_rows(b.r, b.w, b.t0, b.v, b.t1, b.t2, rows, so + 2 * D, b.out, T, H, S, st);
+        else if (S == 64 && T >= k_mfma_min_tokens && !no_seq7) launch_wkv7_seq(b.r, b.w, b.t0, b.v, b.t1, b.t2, s_in + so + 2 * D, s_out + so + 2 * D, b.out, T, H, st);
+        else launch_wkv7(b.r, b.w, b.t0, b.v, b.t1, b.t2, s_in + so + 2 * D, s_out + so + 2 * D, b.out, T, H, S, st);
         launch_groupnorm(b.out, f(L.att_ln_x_w), f(L.att_ln_x_b), 64e-5f, b.g, b.t0, b.r, b.v, f(L.att_r_k), T, H, S, st);
         mm(L.att_output, b.out, b.x, epi(EPI_ADD_RES, nullptr, b.x));
     }
 
     void run_embed() {
-        if (T == 1 && ctx->mega && m.has_embed && mega_v6_folds_embed(ctx->mega)) return;   // inside the persistent launch
+        if (!rows && T == 1 && ctx->mega && m.has_embed && mega_v6_folds_embed(ctx->mega)) return;   // inside the persistent launch
         if (m.has_embed) launch_embed_ln0(*m.emb, ctx->d_tokens, T, D, f(m.ln0_w), f(m.ln0_b), b.x, st);
     }
     // layers [lb, le) of the stage (absolute layer ids); returns true when the launch also produced the logits (ring kernel, last layers)
     bool run_layers(uint32_t lb, uint32_t le, bool want_logits) {
         const float * sin = ctx->state[ctx->cur];
         float * sout = ctx->state[ctx->cur ^ 1];
+        s_in = sin; s_out = sout;
         const int64_t per_layer = m.state_per_layer();
-        if (T == 1 && ctx->mega) {
+        const bool one = T == 1 && !rows;   // (the single-token paths work on the context's own state)
+        if (one && ctx->mega) {
             const bool whole = lb == m.layer_begin && le == m.layer_end;
             const bool head_done = want_logits && m.has_head && le == m.layer_end && mega_v6_folds_head(ctx->mega);
             const float * s0 = sin + (int64_t) m.layer_begin * per_layer;
@@ -673,23 +692,28 @@ struct Runner {
         }
         for (uint32_t i = lb; i < le; i++) {
             const LayerW & L = m.layers[i];
-            const float * li = sin + (int64_t) i * per_layer;
-            float * lo = sout + (int64_t) i * per_layer;
-            if (T == 1 && ctx->fused_v6) { fused_v6_layer(m, L, b.x, li, lo, ctx->fused_scratch, st, &ctx->prof); continue; }
-            if (T == 1 && ctx->fused_v4) { fused_v4_layer(m, L, b.x, li, lo, ctx->fused_scratch, st, &ctx->prof); continue; }
-            if (T == 1 && ctx->fused_v7) { fused_v7_layer(m, L, (int) i, b.x, b.v_first, li, lo, ctx->fused_scratch, st, &ctx->prof); continue; }
+            const int64_t so = (int64_t) i * per_layer;
+            if (one && ctx->fused_v6) { fused_v6_layer(m, L, b.x, sin + so, sout + so, ctx->fused_scratch, st, &ctx->prof); continue; }
+            if (one && ctx->fused_v4) { fused_v4_layer(m, L, b.x, sin + so, sout + so, ctx->fused_scratch, st, &ctx->prof); continue; }
+            if (one && ctx->fused_v7) { fused_v7_layer(m, L, (int) i, b.x, b.v_first, sin + so, sout + so, ctx->fused_scratch, st, &ctx->prof); continue; }
             switch (m.arch_major) {
-                case 4: att_v4(L, li, lo); break;
-                case 5: att_v5(L, li, lo); break;
-                case 6: att_v6(L, li, lo); break;
-                case 7: att_v7(L, (int) i, li, lo); break;
+                case 4: att_v4(L, so); break;
+                case 5: att_v5(L, so); break;
+                case 6: att_v6(L, so); break;
+                case 7: att_v7(L, (int) i, so); break;
                 default: break;
             }
-            ffn(L, li, lo);
+            ffn(L, so);
         }
         return false;
     }
     void run_head() {
+        if (rows) {
+            // row mode: every row is the last token of its sequence -- ln_out on all rows, one product with T rows into [T][n_vocab]
+            launch_layernorm(b.x, T, D, f(m.ln_out_w), f(m.ln_out_b), b.xn, st);
+            mm(m.head, b.xn, ctx->d_logits);
+            return;
+        }
         // ln_out on the last token only, then the head projection (rwkv_graph.inc:704-708, 851-854)
         launch_layernorm(b.x + (T - 1) * D, 1, D, f(m.ln_out_w), f(m.ln_out_b), b.xlast, st);
         const int64_t Tsave = T; T = 1;
@@ -725,6 +749,58 @@ bool forward(rwkv_context * ctx, int64_t T, bool want_logits) {
     ctx->cur ^= 1;
     HIP_CTX_OK(ctx, hipGetLastError());
     RW_CTX_CHECK(ctx, RWKV_ERROR_GRAPH | RWKV_ERROR_ALLOC, false, !r.failed, "a sequence-mode product could not be launched (out of device memory for the tile-major weight image?)");
+    return true;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Batched decode (api.cpp, rwkv_mi_batch_*). The batch runs on a context of its own (batch_context_create): the model, a stream, scratch,
+// token words and a [rows][n_vocab] logits buffer -- no state, no persistent kernel, no fused layers, no graphs. Growing its scratch
+// therefore never drops the captured graphs of the caller's context.
+// Ordering: the batch takes part in the per-device chain of persistent launches (engine.hip top). It counts as one more member, so a
+// persistent context on the device records every launch's completion; each pass first waits on the device's latest persistent launch and
+// then leaves its own completion as the event the next persistent launch waits on. A batch pass never runs beside a persistent kernel.
+// ---------------------------------------------------------------------------------------------------------------
+rwkv_context * batch_context_create(Model * m, int64_t max_rows) {
+    rwkv_context * c = new (std::nothrow) rwkv_context();
+    if (!c) return nullptr;
+    c->model = m;
+    m->refcount++;
+    c->use_graph = false;
+    bool ok = hipSetDevice(m->device) == hipSuccess &&
+              hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) == hipSuccess &&
+              hipMalloc((void **) &c->d_logits, (size_t) max_rows * (size_t) m->n_vocab() * sizeof(float)) == hipSuccess &&
+              hipMalloc((void **) &c->d_tokens, (size_t) max_rows * sizeof(uint32_t)) == hipSuccess &&
+              hipHostMalloc((void **) &c->h_tokens, (size_t) max_rows * sizeof(uint32_t), hipHostMallocDefault) == hipSuccess &&
+              hipEventCreate(&c->ev0) == hipSuccess && hipEventCreate(&c->ev1) == hipSuccess &&
+              hipEventCreateWithFlags(&c->mega_done, hipEventDisableTiming) == hipSuccess;
+    if (!ok) { destroy_context(c); return nullptr; }
+    c->d_tokens_cap = c->h_tokens_cap = max_rows;
+    prefill_prepare_current_device();
+    // (a persistent context already on the device recorded nothing while it was alone: drain it once)
+    if (mega_chain_count(c, +1) > 1) (void) hipDeviceSynchronize();
+    return c;
+}
+
+void batch_context_destroy(rwkv_context * c) {
+    if (!c) return;
+    (void) hipSetDevice(c->model->device);
+    if (c->stream) (void) hipStreamSynchronize(c->stream);
+    mega_chain_forget(c);
+    mega_chain_count(c, -1);
+    destroy_context(c);
+}
+
+// One pass of T rows, row t = one token (ctx->d_tokens[t]) of the sequence whose state is d_rows[t]. Logits: ctx->d_logits[T][n_vocab].
+bool forward_rows(rwkv_context * ctx, const RowState * d_rows, int64_t T, bool want_logits) {
+    if (!ensure_scratch(ctx, T)) return false;
+    Model & m = *ctx->model;
+    Runner r{ctx, m, ctx->stream, T, m.n_embed(), m.head_count, m.head_size, ctx->b};
+    r.rows = d_rows;
+    mega_chain_begin(ctx);
+    r.run(want_logits);
+    mega_chain_end(ctx);
+    HIP_CTX_OK(ctx, hipGetLastError());
+    RW_CTX_CHECK(ctx, RWKV_ERROR_GRAPH | RWKV_ERROR_ALLOC, false, !r.failed, "a batched product could not be launched (out of device memory for the tile-major weight image?)");
     return true;
 }
 

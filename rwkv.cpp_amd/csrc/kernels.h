@@ -120,6 +120,21 @@ void launch_fill_state_v4(float * state, int64_t n_layer, int64_t D, hipStream_t
 // argmax over logits[n] -> *out (first index of the maximum), used by the on-device greedy decode loop
 void launch_argmax(const float * logits, int64_t n, uint32_t * out, hipStream_t st);
 
+// ---- batched decode (batch.hip): row t of a pass is its own sequence; its recurrent state lives in its own slot ----
+// rows[t].in / rows[t].out: the slot's state buffers (read / written); the kernels add the offset of the state component themselves.
+struct RowState { const float * in; float * out; };
+// k_mix with x_prev = rows[t].in[co + d]; writes rows[t].out[co + d] = xn[t][d]
+void launch_mix_rows(const MixArgs & a, const RowState * rows, int64_t co, int64_t T, int64_t D, hipStream_t st);
+// one single-token WKV step per row; so = offset of the layer's WKV state inside a slot (RWKV-4: aa, bb, pp at so, so + D, so + 2 D)
+void launch_wkv4_rows(const float * k, const float * v, const float * r, const float * time_first, const float * time_decay,
+                      const RowState * rows, int64_t so, float * out, int64_t T, int64_t D, hipStream_t st);
+void launch_wkv6_rows(const float * r, const float * k, const float * v, const float * u, int u_per_chan, const float * w, int w_mode,
+                      const RowState * rows, int64_t so, float * out, int64_t T, int64_t H, int64_t S, hipStream_t st);
+void launch_wkv7_rows(const float * r, const float * w, const float * k, const float * v, const float * a, const float * b,
+                      const RowState * rows, int64_t so, float * out, int64_t T, int64_t H, int64_t S, hipStream_t st);
+// argmax of each of T rows of logits[T][n] -> out[t] (and hist[t] when hist != nullptr); k_argmax's rule
+void launch_argmax_rows(const float * logits, int64_t T, int64_t n, uint32_t * out, uint32_t * hist, hipStream_t st);
+
 // load-time transpose of att.time_maa_w2: [5][D][R] -> [5][R][D]
 void launch_transpose_w2(const float * src, float * dst, int64_t D, int64_t R, hipStream_t st);
 

@@ -210,6 +210,12 @@ bool state_to_host(rwkv_context * ctx, float * state_out);
 // x_in / x_out: residual stream hand-off for pipeline stages (nullptr on a full model). Logits land in ctx->d_logits.
 bool forward(rwkv_context * ctx, int64_t T, bool want_logits);
 
+// batched decode (engine.hip): the batch's own context (model, stream, scratch, tokens, [max_rows][n_vocab] logits; a member of the per-device
+// chain of persistent launches) and one pass of T rows, row t from state d_rows[t].in into d_rows[t].out
+rwkv_context * batch_context_create(Model * m, int64_t max_rows);
+void batch_context_destroy(rwkv_context * c);
+bool forward_rows(rwkv_context * ctx, const RowState * d_rows, int64_t T, bool want_logits);
+
 // fused RWKV-6 decode layer (fused_v6.hip)
 bool   fused_v6_supported(const Model & m);
 size_t fused_v6_scratch_bytes(const Model & m);

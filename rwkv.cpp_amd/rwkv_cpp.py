@@ -150,6 +150,24 @@ class RWKVSharedLibrary:
         L.rwkv_mi_stage_run.argtypes = [ctypes.POINTER(c_ctx), ctypes.c_size_t, P_UINT32, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                         P_UINT32, P_FLOAT]
         L.rwkv_mi_stage_run.restype = ctypes.c_bool
+        # batched decode (rwkv_mi_batch_*)
+        c_batch = ctypes.c_void_p
+        L.rwkv_mi_batch_create.argtypes = [c_ctx, ctypes.c_size_t]
+        L.rwkv_mi_batch_create.restype = c_batch
+        L.rwkv_mi_batch_free.argtypes = [c_batch]
+        L.rwkv_mi_batch_free.restype = None
+        L.rwkv_mi_batch_state_load.argtypes = [c_batch, ctypes.c_size_t, P_FLOAT]
+        L.rwkv_mi_batch_state_load.restype = ctypes.c_bool
+        L.rwkv_mi_batch_state_store.argtypes = [c_batch, ctypes.c_size_t, P_FLOAT]
+        L.rwkv_mi_batch_state_store.restype = ctypes.c_bool
+        L.rwkv_mi_batch_state_from_context.argtypes = [c_batch, ctypes.c_size_t, c_ctx]
+        L.rwkv_mi_batch_state_from_context.restype = ctypes.c_bool
+        L.rwkv_mi_batch_state_to_context.argtypes = [c_batch, ctypes.c_size_t, c_ctx]
+        L.rwkv_mi_batch_state_to_context.restype = ctypes.c_bool
+        L.rwkv_mi_batch_eval.argtypes = [c_batch, P_UINT32, P_UINT32, ctypes.c_size_t, P_FLOAT]
+        L.rwkv_mi_batch_eval.restype = ctypes.c_bool
+        L.rwkv_mi_batch_decode_greedy.argtypes = [c_batch, P_UINT32, P_UINT32, ctypes.c_size_t, ctypes.c_size_t, P_UINT32, P_FLOAT]
+        L.rwkv_mi_batch_decode_greedy.restype = ctypes.c_bool
 
     # --- rwkv.h ---------------------------------------------------------------------------------------------
 
@@ -445,4 +463,82 @@ class RWKVModel:
 
     def __del__(self) -> None:
         if hasattr(self, "_valid") and self._valid:
+            self.free()
+
+
+def _u32(values) -> np.ndarray:
+    return np.ascontiguousarray(np.asarray(values, dtype=np.int64).astype(np.uint32))
+
+
+class RWKVBatch:
+    """n_slots device-resident sequences of one model advanced together, one pass over the weights per step (rwkv_mi_batch_*).
+
+    Row i of a call is slot slots[i] fed tokens[i]; every row equals rwkv_eval of that sequence alone, bit for bit. Bound to `model`'s
+    context (a single-device one); free it before the model. Not thread-safe."""
+
+    def __init__(self, model: RWKVModel, n_slots: int) -> None:
+        self._model = model
+        self._L = model._library.library
+        self.n_slots = int(n_slots)
+        self._ptr = self._L.rwkv_mi_batch_create(model._ctx.ptr, self.n_slots)
+        if not self._ptr:
+            raise ValueError(f"rwkv_mi_batch_create failed (error flags {model._library.rwkv_get_last_error(model._ctx)})")
+        self._state_len = model.state_len
+        self._n_vocab = model.n_vocab
+        self.last_error = 0
+
+    def _fail(self, what: str):
+        self.last_error = self._model._library.rwkv_get_last_error(self._model._ctx)   # (reported on the model's context)
+        raise ValueError(f"{what} failed (error flags {self.last_error})")
+
+    def state_load(self, slot: int, state_in: Optional[np.ndarray] = None) -> None:
+        self._model._check(state_in, "state_in", self._state_len)
+        if not self._L.rwkv_mi_batch_state_load(self._ptr, slot, ctypes.cast(_ptr(state_in), P_FLOAT)):
+            self._fail("rwkv_mi_batch_state_load")
+
+    def state_store(self, slot: int) -> np.ndarray:
+        s = np.empty(self._state_len, dtype=np.float32)
+        if not self._L.rwkv_mi_batch_state_store(self._ptr, slot, ctypes.cast(s.ctypes.data, P_FLOAT)):
+            self._fail("rwkv_mi_batch_state_store")
+        return s
+
+    def from_context(self, slot: int, model: RWKVModel) -> None:
+        """The resident state of `model`'s context (e.g. after a prefill) into a slot, device to device."""
+        if not self._L.rwkv_mi_batch_state_from_context(self._ptr, slot, model._ctx.ptr):
+            self._fail("rwkv_mi_batch_state_from_context")
+
+    def to_context(self, slot: int, model: RWKVModel) -> None:
+        """A slot into the resident state of `model`'s context, device to device."""
+        if not self._L.rwkv_mi_batch_state_to_context(self._ptr, slot, model._ctx.ptr):
+            self._fail("rwkv_mi_batch_state_to_context")
+
+    def eval(self, slots: List[int], tokens: List[int], want_logits: bool = True) -> Optional[np.ndarray]:
+        """One token per named slot in one pass; logits [n][n_vocab] in call order (None when want_logits is False)."""
+        s, t = _u32(slots), _u32(tokens)
+        if s.size != t.size:
+            raise ValueError("slots and tokens differ in length")
+        out = np.empty((s.size, self._n_vocab), dtype=np.float32) if want_logits else None
+        if not self._L.rwkv_mi_batch_eval(self._ptr, s.ctypes.data_as(P_UINT32), t.ctypes.data_as(P_UINT32), s.size, ctypes.cast(_ptr(out), P_FLOAT)):
+            self._fail("rwkv_mi_batch_eval")
+        return out
+
+    def decode_greedy(self, slots: List[int], first_tokens: List[int], n_tokens: int) -> Tuple[np.ndarray, float]:
+        """Greedy loop on the device for every named slot: tokens [n][n_tokens], elapsed milliseconds."""
+        s, t = _u32(slots), _u32(first_tokens)
+        if s.size != t.size:
+            raise ValueError("slots and first_tokens differ in length")
+        out = np.empty((s.size, n_tokens), dtype=np.uint32)
+        ms = ctypes.c_float(0.0)
+        if not self._L.rwkv_mi_batch_decode_greedy(self._ptr, s.ctypes.data_as(P_UINT32), t.ctypes.data_as(P_UINT32), s.size, n_tokens,
+                                                   ctypes.cast(out.ctypes.data, P_UINT32), ctypes.byref(ms)):
+            self._fail("rwkv_mi_batch_decode_greedy")
+        return out, float(ms.value)
+
+    def free(self) -> None:
+        if self._ptr:
+            self._L.rwkv_mi_batch_free(self._ptr)
+            self._ptr = None
+
+    def __del__(self) -> None:
+        if getattr(self, "_ptr", None):
             self.free()

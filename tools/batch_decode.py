@@ -1,0 +1,86 @@
+#!/usr/bin/env python3
+"""Batched greedy decode (rwkv_mi_batch_decode_greedy) swept over the batch size, against single-stream rwkv_mi_decode_greedy.
+
+    python tools/batch_decode.py MODEL_PATH [--config rwkv6-7b] [--dtype Q4_0] [--n 1,2,4,...] [--tokens 32] [--warmup 4]
+
+MODEL_PATH is written with synth.write_model (seed 42) unless it exists with its ".ok" marker. Prints one JSON record per n:
+  ms_per_step           one batched step (n tokens, one pass over the weights), from HIP events around the device loop
+  tokens_per_s          aggregate n / step time; per_seq_tokens_per_s = 1 / step time
+  alg_bytes_per_step    weights once + n x (state read + write + embedding row + logits), from shapes
+  step_fraction_of_8TBs that figure over the step time, as a fraction of 8 TB/s -- a figure of the whole step, not of one kernel
+and first one record with the single-stream rate measured in the same process.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+HBM_PEAK_BS = 8.0e12
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("model_path")
+    ap.add_argument("--config", default="rwkv6-7b")
+    ap.add_argument("--dtype", default="Q4_0")
+    ap.add_argument("--n", default="1,2,4,8,16,32,64,128")
+    ap.add_argument("--tokens", type=int, default=32, help="steps of each timed loop")
+    ap.add_argument("--warmup", type=int, default=4, help="steps of the warm-up loop of every n")
+    args = ap.parse_args()
+
+    import __graft_entry__ as graft
+    pkg = graft.load_package()
+    from rwkv_cpp_amd import synth
+
+    spec = synth.CONFIGS[args.config]
+    marker = args.model_path + ".ok"
+    if not (os.path.exists(args.model_path) and os.path.exists(marker)):
+        t = time.time()
+        info = synth.write_model(args.model_path, spec, args.dtype, seed=42)
+        with open(marker, "w") as f:
+            f.write(json.dumps(info))
+        print(f"[batch_decode] wrote {args.model_path}: {info['bytes'] / 1e9:.2f} GB in {time.time() - t:.1f}s", file=sys.stderr)
+
+    pkg.build_library()
+    lib = pkg.load_rwkv_shared_library()
+    m = pkg.RWKVModel(lib, args.model_path, thread_count=1, gpu_layer_count=99)
+    ns = [int(x) for x in args.n.split(",")]
+    V, D, state_len = m.n_vocab, m.n_embed, m.state_len
+    weight_bytes = int(lib.library.rwkv_mi_weight_bytes(m._ctx.ptr))
+    emb_row = 2 * D                                   # F16 embedding row
+    per_seq = 2 * 4 * state_len + emb_row + 4 * V     # state read + write, embedding row, logits
+    weights_once = weight_bytes - V * emb_row         # every matrix once; of the embedding only the rows the tokens select
+
+    # single stream, same process
+    m.state_load(None)
+    m.decode_greedy(1, args.warmup)
+    _, ms1 = m.decode_greedy(2, args.tokens)
+    single = args.tokens / (ms1 / 1e3)
+    print(json.dumps({"mode": "single_stream", "decode_path": m.decode_path(), "ms_per_token": round(ms1 / args.tokens, 4),
+                      "tokens_per_s": round(single, 1)}), flush=True)
+
+    b = pkg.RWKVBatch(m, max(ns))
+    for n in ns:   # warm-up of every n first (tile-major weight images, scratch growth)
+        b.decode_greedy(list(range(n)), [(7 * i + 1) % V for i in range(n)], args.warmup)
+    for n in ns:
+        slots = list(range(n))
+        for s in slots:
+            b.state_load(s, None)
+        _, ms = b.decode_greedy(slots, [(7 * i + 1) % V for i in range(n)], args.tokens)
+        step_ms = ms / args.tokens
+        alg = weights_once + n * per_seq
+        rec = {"mode": "batch", "n": n, "ms_per_step": round(step_ms, 4), "tokens_per_s": round(n / (step_ms / 1e3), 1),
+               "per_seq_tokens_per_s": round(1e3 / step_ms, 1), "vs_single_stream": round(n / (step_ms / 1e3) / single, 3),
+               "alg_bytes_per_step": alg, "step_fraction_of_8TBs": round(alg / (step_ms / 1e3) / HBM_PEAK_BS, 4),
+               "steps": args.tokens, "config": args.config, "dtype": args.dtype}
+        print(json.dumps(rec), flush=True)
+    b.free()
+    m.free()
+
+
+if __name__ == "__main__":
+    main()

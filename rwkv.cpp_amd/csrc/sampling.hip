@@ -4,7 +4,7 @@
 // never leaves the device (rwkv_mi_decode_sample). Semantics follow sample_probs() statement by statement:
 //   probs = softmax(logits);  top_p == 0 -> 1;  temperature == 0 -> argmax;
 //   top_p < 1: cutoff = the probability at which the descending cumulative sum first exceeds top_p; probs < cutoff -> 0;
-//   temperature != 1: probs = probs^(1/temperature);  probs /= sum;  token = first index whose cumulative probability exceeds u.
+//   temperature != 1: probs = (probs / max probs)^(1/temperature);  probs /= sum;  token = first index whose cumulative probability exceeds u.
 // The cut-off is found without sorting: the largest threshold t (bisection over the float bit pattern, 31 reductions) with
 // sum{p >= t} > top_p is exactly that probability. Sums are f32 in a fixed order (per-thread contiguous chunks, then a tree): runs
 // are reproducible; against numpy's sequential cumsum the result can differ only when u or top_p falls within rounding of a boundary.
@@ -99,7 +99,9 @@ __global__ __launch_bounds__(1024) void k_sample(const float * __restrict__ logi
         for (int i = i0; i < i1; i++) {
             float p = probs[i];
             if (__float_as_uint(p) < cutoff_bits) p = 0.0f;
-            else if (temperature != 1.0f) p = p > 0.0f ? powf(p, it) : 0.0f;
+            // (p * total = p / p_max: the power of the probability relative to the largest one -- the same distribution after the
+            //  renormalisation below, without p^(1/temperature) underflowing to zero for every token at a low temperature and a large vocabulary)
+            else if (temperature != 1.0f) p = p > 0.0f ? powf(p * total, it) : 0.0f;
             probs[i] = p;
             part += p;
         }

@@ -303,7 +303,7 @@ RWKV_API bool rwkv_mi_decode_greedy(struct rwkv_context * ctx, uint32_t first_to
         if (!ok) break;
         if (in_launch) continue;
         // next token = argmax(logits), written where the embedding kernel reads it; no host round trip
-        if (folded_argmax_target(ctx) != ctx->d_tokens) launch_argmax(ctx->d_logits, (int64_t) n_vocab, ctx->d_tokens, ctx->stream);
+        if (folded_argmax_target(ctx) != ctx->d_tokens) launch_argmax(ctx->d_logits, 1, (int64_t) n_vocab, ctx->d_tokens, nullptr, ctx->stream);
         if (hipMemcpyAsync(d_hist + i, ctx->d_tokens, sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) ok = false;
     }
     if (in_launch && ctx->mega) {
@@ -391,7 +391,7 @@ RWKV_API bool rwkv_mi_profile_decode(struct rwkv_context * ctx, uint32_t first_t
         const bool ok = forward(ctx, 1, true);
         pf.on = false;
         if (!ok) return false;
-        if (folded_argmax_target(ctx) != ctx->d_tokens) launch_argmax(ctx->d_logits, (int64_t) n_vocab, ctx->d_tokens, ctx->stream);
+        if (folded_argmax_target(ctx) != ctx->d_tokens) launch_argmax(ctx->d_logits, 1, (int64_t) n_vocab, ctx->d_tokens, nullptr, ctx->stream);
         HIP_CTX_OK(ctx, hipStreamSynchronize(ctx->stream));
         for (size_t k = 0; k < pf.used; k++) {
             float ms = 0.0f;
@@ -558,7 +558,7 @@ RWKV_API bool rwkv_mi_stage_step(struct rwkv_context * ctx, const uint32_t * d_t
         HIP_CTX_OK(ctx, hipMemcpyAsync(x_out, ctx->b.x, D * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
         if (m.arch_major == 7) HIP_CTX_OK(ctx, hipMemcpyAsync(x_out + D, ctx->b.v_first, D * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
     } else if (d_next_token) {
-        launch_argmax(ctx->d_logits, m.n_vocab(), d_next_token, ctx->stream);
+        launch_argmax(ctx->d_logits, 1, m.n_vocab(), d_next_token, nullptr, ctx->stream);
     }
     return true;
 }
@@ -797,7 +797,7 @@ RWKV_API bool rwkv_mi_batch_decode_greedy(struct rwkv_mi_batch * B, const uint32
             (void) hipStreamSynchronize(run->stream);
             return batch_fail_through(B);
         }
-        launch_argmax_rows(run->d_logits, (int64_t) n, n_vocab, run->d_tokens, hist.p + i * n, run->stream);
+        launch_argmax(run->d_logits, (int64_t) n, n_vocab, run->d_tokens, hist.p + i * n, run->stream);
     }
     BATCH_HIP_OK(B, hipEventRecord(run->ev1, run->stream));
     std::vector<uint32_t> h(tokens_out ? n_tokens * n : 0);

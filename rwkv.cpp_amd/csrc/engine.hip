@@ -393,11 +393,9 @@ struct Runner {
     rwkv_context::Buf & b;
 
     bool failed = false;   // a launch of the pass could not be made (allocation failure): its outputs are not valid
-    // Row mode (batched decode, rwkv_mi_batch_*): row t is its own sequence; its state is rows[t] (device table) instead of the context's
-    // state[cur] -> state[cur ^ 1]. The single-token paths (persistent / fused) are never taken, T == 1 included.
-    const RowState * rows = nullptr;
-    const float * s_in = nullptr;   // (not row mode) the state the pass reads / writes
-    float * s_out = nullptr;
+    // The state the pass reads / writes: the context's state[cur] -> state[cur ^ 1], or in row mode (batched decode, rwkv_mi_batch_*)
+    // state.rows, where row t is its own sequence. Row mode never takes the single-token paths (persistent / fused), T == 1 included.
+    StateRef state;
 
     // inputs quantised ahead of their products, several per launch (sequence mode): source pointer -> tile image
     struct Pre { const float * x = nullptr; int wtype = -1; int64_t K = 0; TileAct ta; } pre[5];
@@ -415,7 +413,7 @@ struct Runner {
     void drop_pre() { for (auto & e : pre) e = Pre(); }
     // tile images for n outputs of a fused mix (sequence mode, all consumers quantised with `wtype`): registered like prequant's
     bool fused_outs(int n, float * const * keys, int wtype, TileAct * tas) {
-        if (rows) return false;   // (row mode: the quantising mixes carry across rows; k_mix_rows + prequant instead)
+        if (state.rows) return false;   // (row mode: the quantising mixes carry across rows; k_mix_rows + prequant instead)
         if (!(dtype_quantized(wtype) && T >= k_mfma_min_tokens && b.tiles[0] && D % 256 == 0 && n <= 5)) return false;
         for (auto & e : pre) e = Pre();
         for (int i = 0; i < n; i++) { tas[i] = tile_act_at(b.tiles[i], T, D); pre[i].x = keys[i]; pre[i].wtype = wtype; pre[i].K = D; pre[i].ta = tas[i]; }
@@ -492,17 +490,11 @@ struct Runner {
     // (so: offset of the layer's WKV state in a state buffer)
     void wkv6(const float * r, const float * k, const float * v, const float * u, int u_per_chan, const float * w, int w_mode,
               int64_t so, float * out) {
-        if (rows) launch_wkv6_rows(r, k, v, u, u_per_chan, w, w_mode, rows, so, out, T, H, S, st);
-        else if (S == 64 && T >= k_mfma_min_tokens) launch_wkv6_seq(r, k, v, u, u_per_chan, w, w_mode, s_in + so, s_out + so, out, T, H, st);
-        else launch_wkv6(r, k, v, u, u_per_chan, w, w_mode, s_in + so, s_out + so, out, T, H, S, st);
+        if (!state.rows && S == 64 && T >= k_mfma_min_tokens) launch_wkv6_seq(r, k, v, u, u_per_chan, w, w_mode, state.in + so, state.out + so, out, T, H, st);
+        else launch_wkv6(r, k, v, u, u_per_chan, w, w_mode, state.at(so), out, T, H, S, st);
     }
     // token-shift mix whose carry sits at offset co of a state buffer
-    void carry(MixArgs & a, int64_t co) const { if (!rows) { a.carry_in = s_in + co; a.carry_out = s_out + co; } }
-    void mix(MixArgs a, int64_t co) {
-        if (rows) { launch_mix_rows(a, rows, co, T, D, st); return; }
-        carry(a, co);
-        launch_mix(a, T, D, st);
-    }
+    void mix(const MixArgs & a, int64_t co) { launch_mix(a, state.at(co), T, D, st); }
     static const float * f(const DevTensor * t) { return (const float *) t->data; }
     static Epi epi(int op, const float * bias = nullptr, const float * res = nullptr, const float * aux = nullptr) {
         Epi e; e.op = op; e.bias = bias; e.res = res; e.aux = aux; return e;
@@ -511,7 +503,7 @@ struct Runner {
     // channel mixing (rwkv_ffn_v4_v5 :484-511, rwkv_ffn_v6 :513-531, rwkv_ffn_v7 :533-543)
     void ffn(const LayerW & L, int64_t so) {
         launch_layernorm(b.x, T, D, f(L.ln2_w), f(L.ln2_b), b.xn, st);
-        MixArgs a; a.xn = b.xn; carry(a, so);
+        MixArgs a; a.xn = b.xn;
         if (m.arch_major <= 5) { a.mode = 0; a.n_out = 2; a.coef[0] = f(L.ffn_time_mix_k); a.coef[1] = f(L.ffn_time_mix_r); }
         else if (m.arch_major == 6) { a.mode = 1; a.n_out = 2; a.coef[0] = f(L.ffn_time_maa_k); a.coef[1] = f(L.ffn_time_maa_r); }
         else { a.mode = 1; a.n_out = 1; a.coef[0] = f(L.ffn_x_k); }
@@ -519,7 +511,7 @@ struct Runner {
         TileAct tas[5];
         if ((m.arch_major == 7 || L.ffn_receptance->type == L.ffn_key->type) && L.ffn_key->cols() == D && fused_outs(a.n_out, a.out, L.ffn_key->type, tas)) {
             // sequence mode: the mix writes its outputs (RWKV-7: its one output) as quantised tile images (their only consumers are the products below)
-            a.out[0] = nullptr; a.out[1] = nullptr;
+            a.out[0] = nullptr; a.out[1] = nullptr; a.carry_in = state.in + so; a.carry_out = state.out + so;
             launch_mix_seq_q(a, T, D, st, tas, L.ffn_key->type);
         } else {
             mix(a, so);
@@ -556,9 +548,7 @@ struct Runner {
         mm(L.att_receptance, b.m[2], b.r, epi(EPI_SIGMOID));
         mm(L.att_key, b.m[0], b.k);
         mm(L.att_value, b.m[1], b.v);
-        if (rows) launch_wkv4_rows(b.k, b.v, b.r, f(L.att_time_first), f(L.att_time_decay), rows, so + 2 * D, b.out, T, D, st);
-        else launch_wkv4(b.k, b.v, b.r, f(L.att_time_first), f(L.att_time_decay), s_in + so + 2 * D, s_in + so + 3 * D, s_in + so + 4 * D,
-                         s_out + so + 2 * D, s_out + so + 3 * D, s_out + so + 4 * D, b.out, T, D, st);
+        launch_wkv4(b.k, b.v, b.r, f(L.att_time_first), f(L.att_time_decay), state.at(so + 2 * D), b.out, T, D, st);
         mm(L.att_output, b.out, b.x, epi(EPI_ADD_RES, nullptr, b.x));
     }
 
@@ -583,14 +573,14 @@ struct Runner {
     // rwkv_att_v6 (:294-385)
     void att_v6(const LayerW & L, int64_t so) {
         launch_layernorm(b.x, T, D, f(L.ln1_w), f(L.ln1_b), b.xn, st);
-        MixArgs a; a.xn = b.xn; carry(a, so + D); a.mode = 1; a.n_out = 1;
+        MixArgs a; a.xn = b.xn; a.mode = 1; a.n_out = 1;
         a.coef[0] = f(L.att_time_maa_x); a.out[0] = b.m[5]; a.sx = b.sx;
         {
             // sequence mode: the mix's only consumer is the W1 product -- it writes that product's quantised input image (and sx, which the
             // five mixes read) instead of f32 values for a quantiser launch
             TileAct ta[1];
             if (fused_outs(1, a.out, L.att_time_maa_w1->type, ta) && getenv("RWKV_MI_NO_MIX_QUANT") == nullptr) {
-                MixArgs q = a; q.out[0] = nullptr;
+                MixArgs q = a; q.out[0] = nullptr; q.carry_in = state.in + so + D; q.carry_out = state.out + so + D;
                 if (!launch_mix_seq_q(q, T, D, st, ta, L.att_time_maa_w1->type)) { drop_pre(); mix(a, so + D); }
             } else { drop_pre(); mix(a, so + D); }
         }
@@ -655,24 +645,23 @@ struct Runner {
             launch_v7_vmix(b.v, b.v_first, b.sx, T * D, st);
         }
         static const bool no_seq7 = getenv("RWKV_MI_NO_WKV7_SEQ") != nullptr;   // (measurement aid: the single-token form over the whole sequence)
-        if (rows) launch_wkv7_rows(b.r, b.w, b.t0, b.v, b.t1, b.t2, rows, so + 2 * D, b.out, T, H, S, st);
-        else if (S == 64 && T >= k_mfma_min_tokens && !no_seq7) launch_wkv7_seq(b.r, b.w, b.t0, b.v, b.t1, b.t2, s_in + so + 2 * D, s_out + so + 2 * D, b.out, T, H, st);
-        else launch_wkv7(b.r, b.w, b.t0, b.v, b.t1, b.t2, s_in + so + 2 * D, s_out + so + 2 * D, b.out, T, H, S, st);
+        if (!state.rows && S == 64 && T >= k_mfma_min_tokens && !no_seq7) launch_wkv7_seq(b.r, b.w, b.t0, b.v, b.t1, b.t2, state.in + so + 2 * D, state.out + so + 2 * D, b.out, T, H, st);
+        else launch_wkv7(b.r, b.w, b.t0, b.v, b.t1, b.t2, state.at(so + 2 * D), b.out, T, H, S, st);
         launch_groupnorm(b.out, f(L.att_ln_x_w), f(L.att_ln_x_b), 64e-5f, b.g, b.t0, b.r, b.v, f(L.att_r_k), T, H, S, st);
         mm(L.att_output, b.out, b.x, epi(EPI_ADD_RES, nullptr, b.x));
     }
 
     void run_embed() {
-        if (!rows && T == 1 && ctx->mega && m.has_embed && mega_v6_folds_embed(ctx->mega)) return;   // inside the persistent launch
+        if (!state.rows && T == 1 && ctx->mega && m.has_embed && mega_v6_folds_embed(ctx->mega)) return;   // inside the persistent launch
         if (m.has_embed) launch_embed_ln0(*m.emb, ctx->d_tokens, T, D, f(m.ln0_w), f(m.ln0_b), b.x, st);
     }
     // layers [lb, le) of the stage (absolute layer ids); returns true when the launch also produced the logits (ring kernel, last layers)
     bool run_layers(uint32_t lb, uint32_t le, bool want_logits) {
         const float * sin = ctx->state[ctx->cur];
         float * sout = ctx->state[ctx->cur ^ 1];
-        s_in = sin; s_out = sout;
+        state.in = sin; state.out = sout;
         const int64_t per_layer = m.state_per_layer();
-        const bool one = T == 1 && !rows;   // (the single-token paths work on the context's own state)
+        const bool one = T == 1 && !state.rows;   // (the single-token paths work on the context's own state)
         if (one && ctx->mega) {
             const bool whole = lb == m.layer_begin && le == m.layer_end;
             const bool head_done = want_logits && m.has_head && le == m.layer_end && mega_v6_folds_head(ctx->mega);
@@ -708,7 +697,7 @@ struct Runner {
         return false;
     }
     void run_head() {
-        if (rows) {
+        if (state.rows) {
             // row mode: every row is the last token of its sequence -- ln_out on all rows, one product with T rows into [T][n_vocab]
             launch_layernorm(b.x, T, D, f(m.ln_out_w), f(m.ln_out_b), b.xn, st);
             mm(m.head, b.xn, ctx->d_logits);
@@ -795,7 +784,7 @@ bool forward_rows(rwkv_context * ctx, const RowState * d_rows, int64_t T, bool w
     if (!ensure_scratch(ctx, T)) return false;
     Model & m = *ctx->model;
     Runner r{ctx, m, ctx->stream, T, m.n_embed(), m.head_count, m.head_size, ctx->b};
-    r.rows = d_rows;
+    r.state.rows = d_rows;
     mega_chain_begin(ctx);
     r.run(want_logits);
     mega_chain_end(ctx);

@@ -54,6 +54,18 @@ void launch_embed_ln0(const DevTensor & emb, const uint32_t * tokens, int64_t T,
 // y[t,:] = norm(x[t,:], 1e-5) * w + b                                                     (rwkv_operators.inc:93-97)
 void launch_layernorm(const float * x, int64_t T, int64_t D, const float * w, const float * b, float * y, hipStream_t st);
 
+// Where a recurrence (token-shift carry, WKV state) reads and writes its state component, at offset `off` of the state buffers:
+//   a sequence (rows == nullptr): token t continues from token t-1; the state goes in -> out;
+//   rows (batched decode): row t is its own sequence; its state goes rows[t].in -> rows[t].out, a device table of the rows' slots.
+struct RowState { const float * in; float * out; };
+struct StateRef {
+    const float * in = nullptr;
+    float * out = nullptr;
+    const RowState * rows = nullptr;
+    int64_t off = 0;
+    StateRef at(int64_t o) const { return StateRef{in, out, rows, off + o}; }
+};
+
 // Token-shift mixes (rwkv_carry_x + the lerps, rwkv_graph.inc:56-82,93-109,214-241,402-413,488-501,516-521,536-538).
 // x_prev[t] = t ? xn[t-1] : carry_in.   mode 0: out_f = xn*c_f + (x_prev - x_prev*c_f)   (v4, v5)
 //                                       mode 1: out_f = (x_prev - xn)*c_f + xn           (v6 xxx / ffn, v7)
@@ -68,7 +80,8 @@ struct MixArgs {
     float * sx = nullptr;
     int mode = 0;
 };
-void launch_mix(const MixArgs & a, int64_t T, int64_t D, hipStream_t st);
+// the carry is that of `s`: a.carry_in / a.carry_out are set from it (rows: x_prev = rows[t].in[off + d], rows[t].out[off + d] = xn[t][d])
+void launch_mix(MixArgs a, const StateRef & s, int64_t T, int64_t D, hipStream_t st);
 
 // v6 data-dependent mix, second stage (rwkv_graph.inc:323-346): for f in (w,k,v,r,g):
 //   out_f[t,d] = (sum_m W2[f][d][m] * tl[t][f*R+m] + maa_f[d]) * sx[t,d] + xn[t,d]
@@ -82,19 +95,18 @@ struct V6Mix2Args {
 };
 void launch_v6_mix2(const V6Mix2Args & a, int64_t T, int64_t D, int64_t R, hipStream_t st);
 
-// RWKV-4 WKV recurrence fused with r * wkv (rwkv_graph.inc:119-161,178-195). r is already sigmoid'ed.
+// RWKV-4 WKV recurrence fused with r * wkv (rwkv_graph.inc:119-161,178-195). r is already sigmoid'ed. State: aa, bb, pp at off, off + D, off + 2 D.
 void launch_wkv4(const float * k, const float * v, const float * r, const float * time_first, const float * time_decay,
-                 const float * aa_in, const float * bb_in, const float * pp_in, float * aa_out, float * bb_out, float * pp_out,
-                 float * out, int64_t T, int64_t D, hipStream_t st);
+                 const StateRef & s, float * out, int64_t T, int64_t D, hipStream_t st);
 
 // RWKV-5/6 WKV recurrence (ggml_rwkv_wkv6; rwkv_graph.inc:275,370). state[h][i=key][j=value].
 // u: [H] (u_per_chan = 0) or [H*S]; w: [H] (w_mode 0), [H*S] (w_mode 1) or per token [T][H*S] (w_mode 2).
 void launch_wkv6(const float * r, const float * k, const float * v, const float * u, int u_per_chan, const float * w, int w_mode,
-                 const float * state_in, float * state_out, float * out, int64_t T, int64_t H, int64_t S, hipStream_t st);
+                 const StateRef & s, float * out, int64_t T, int64_t H, int64_t S, hipStream_t st);
 
 // RWKV-7 WKV recurrence (rwkv_operators_wkv_v7.inc:37-107). state[h][i=value][j=key]; a = -kk, b = kk*a_gate.
 void launch_wkv7(const float * r, const float * w, const float * k, const float * v, const float * a, const float * b,
-                 const float * state_in, float * state_out, float * out, int64_t T, int64_t H, int64_t S, hipStream_t st);
+                 const StateRef & s, float * out, int64_t T, int64_t H, int64_t S, hipStream_t st);
 // sequence form, head size 64 (prefill.hip): four rows per wave, the row's two ordered sums as DPP chains
 bool launch_wkv7_seq(const float * r, const float * w, const float * k, const float * v, const float * a, const float * b,
                      const float * state_in, float * state_out, float * out, int64_t T, int64_t H, hipStream_t st);
@@ -117,23 +129,9 @@ void launch_mul(float * y, const float * a, const float * b, int64_t n, hipStrea
 void launch_copy_f32(float * dst, const float * src, int64_t n, hipStream_t st);
 void launch_fill_state_v4(float * state, int64_t n_layer, int64_t D, hipStream_t st);      // zeros + pp = -1e30
 
-// argmax over logits[n] -> *out (first index of the maximum), used by the on-device greedy decode loop
-void launch_argmax(const float * logits, int64_t n, uint32_t * out, hipStream_t st);
-
-// ---- batched decode (batch.hip): row t of a pass is its own sequence; its recurrent state lives in its own slot ----
-// rows[t].in / rows[t].out: the slot's state buffers (read / written); the kernels add the offset of the state component themselves.
-struct RowState { const float * in; float * out; };
-// k_mix with x_prev = rows[t].in[co + d]; writes rows[t].out[co + d] = xn[t][d]
-void launch_mix_rows(const MixArgs & a, const RowState * rows, int64_t co, int64_t T, int64_t D, hipStream_t st);
-// one single-token WKV step per row; so = offset of the layer's WKV state inside a slot (RWKV-4: aa, bb, pp at so, so + D, so + 2 D)
-void launch_wkv4_rows(const float * k, const float * v, const float * r, const float * time_first, const float * time_decay,
-                      const RowState * rows, int64_t so, float * out, int64_t T, int64_t D, hipStream_t st);
-void launch_wkv6_rows(const float * r, const float * k, const float * v, const float * u, int u_per_chan, const float * w, int w_mode,
-                      const RowState * rows, int64_t so, float * out, int64_t T, int64_t H, int64_t S, hipStream_t st);
-void launch_wkv7_rows(const float * r, const float * w, const float * k, const float * v, const float * a, const float * b,
-                      const RowState * rows, int64_t so, float * out, int64_t T, int64_t H, int64_t S, hipStream_t st);
-// argmax of each of T rows of logits[T][n] -> out[t] (and hist[t] when hist != nullptr); k_argmax's rule
-void launch_argmax_rows(const float * logits, int64_t T, int64_t n, uint32_t * out, uint32_t * hist, hipStream_t st);
+// argmax of each row of logits[rows][n] -> out[row] (first index of the maximum; NaN never wins), and hist[row] unless hist is nullptr.
+// Feeds the next embedding lookup of the on-device greedy decode loops.
+void launch_argmax(const float * logits, int64_t rows, int64_t n, uint32_t * out, uint32_t * hist, hipStream_t st);
 
 // load-time transpose of att.time_maa_w2: [5][D][R] -> [5][R][D]
 void launch_transpose_w2(const float * src, float * dst, int64_t D, int64_t R, hipStream_t st);

@@ -821,26 +821,43 @@ void launch_layernorm(const float * x, int64_t T, int64_t D, const float * w, co
 // Token-shift mixes
 // ---------------------------------------------------------------------------------------------------------------
 
+// the lerps of element idx (channel d) given x and x_prev; k_mix and k_mix_rows differ only in where x_prev comes from and the carry goes
+__device__ __forceinline__ void mix_elem(const MixArgs & a, int64_t idx, int64_t d, float x, float xp) {
+    if (a.mode == 0) {
+        for (int f = 0; f < a.n_out; f++) { const float c = a.coef[f][d]; const float xc = x * c, pc = xp * c; a.out[f][idx] = xc + (xp - pc); }
+    } else {
+        const float sx = xp - x;
+        if (a.sx) a.sx[idx] = sx;
+        for (int f = 0; f < a.n_out; f++) { const float sc = sx * a.coef[f][d]; a.out[f][idx] = sc + x; }
+    }
+}
+
 __global__ __launch_bounds__(256) void k_mix(MixArgs a, int64_t T, int64_t D) {
     const int64_t n = T * D;
     for (int64_t idx = (int64_t) blockIdx.x * 256 + threadIdx.x; idx < n; idx += (int64_t) gridDim.x * 256) {
         const int64_t t = idx / D, d = idx - t * D;
         const float x = a.xn[idx];
-        const float xp = (t == 0) ? a.carry_in[d] : a.xn[idx - D];
-        if (a.mode == 0) {
-            for (int f = 0; f < a.n_out; f++) { const float c = a.coef[f][d]; const float xc = x * c, pc = xp * c; a.out[f][idx] = xc + (xp - pc); }
-        } else {
-            const float sx = xp - x;
-            if (a.sx) a.sx[idx] = sx;
-            for (int f = 0; f < a.n_out; f++) { const float sc = sx * a.coef[f][d]; a.out[f][idx] = sc + x; }
-        }
+        mix_elem(a, idx, d, x, (t == 0) ? a.carry_in[d] : a.xn[idx - D]);
         if (t == T - 1) a.carry_out[d] = x;
     }
 }
 
-void launch_mix(const MixArgs & a, int64_t T, int64_t D, hipStream_t st) {
+// every row is the last token of its sequence: x_prev = rows[t].in[co + d], and rows[t].out[co + d] = x
+__global__ __launch_bounds__(256) void k_mix_rows(MixArgs a, const RowState * __restrict__ rows, int64_t co, int64_t T, int64_t D) {
+    const int64_t n = T * D;
+    for (int64_t idx = (int64_t) blockIdx.x * 256 + threadIdx.x; idx < n; idx += (int64_t) gridDim.x * 256) {
+        const int64_t t = idx / D, d = idx - t * D;
+        const float x = a.xn[idx];
+        mix_elem(a, idx, d, x, rows[t].in[co + d]);
+        rows[t].out[co + d] = x;
+    }
+}
+
+void launch_mix(MixArgs a, const StateRef & s, int64_t T, int64_t D, hipStream_t st) {
     const int64_t n = T * D;
     const unsigned grid = (unsigned) ((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
+    if (s.rows) { hipLaunchKernelGGL(k_mix_rows, dim3(grid), dim3(256), 0, st, a, s.rows, s.off, T, D); return; }
+    a.carry_in = s.in + s.off; a.carry_out = s.out + s.off;
     hipLaunchKernelGGL(k_mix, dim3(grid), dim3(256), 0, st, a, T, D);
 }
 
@@ -868,18 +885,21 @@ void launch_v6_mix2(const V6Mix2Args & a, int64_t T, int64_t D, int64_t R, hipSt
 
 // ---------------------------------------------------------------------------------------------------------------
 // WKV recurrences. Sequential in t inside the kernel; the state stays in registers across the tokens of a call.
+// Each recurrence is one __device__ body over tokens [t0, t1) from state_in to state_out, with two entry points:
+//   k_wkvX       (grid H, or channel blocks for RWKV-4): one sequence, body(state_in, state_out, 0, T);
+//   k_wkvX_rows  (grid (H, T)): row t is its own sequence (batched decode), body(rows[t].in + so, rows[t].out + so, t, t + 1).
+// A row therefore performs exactly the statements of one single-token step, in the same order. The bodies' pointers are plain: the
+// entry points' parameters carry __restrict__ (on the row forms' slot pointers it raised k_wkv7_rows<64> from 86 to 126 VGPRs).
 // ---------------------------------------------------------------------------------------------------------------
 
-__global__ __launch_bounds__(256) void k_wkv4(const float * __restrict__ k, const float * __restrict__ v, const float * __restrict__ r,
-                                              const float * __restrict__ tf, const float * __restrict__ td,
-                                              const float * __restrict__ aa_in, const float * __restrict__ bb_in, const float * __restrict__ pp_in,
-                                              float * __restrict__ aa_out, float * __restrict__ bb_out, float * __restrict__ pp_out,
-                                              float * __restrict__ out, int64_t T, int64_t D) {
+// RWKV-4: one thread per channel i; the state is aa, bb, pp at [0, D), [D, 2 D), [2 D, 3 D)
+__device__ __forceinline__ void wkv4_body(const float * k, const float * v, const float * r, const float * tf, const float * td,
+                                          const float * state_in, float * state_out, float * out, int64_t t0, int64_t t1, int64_t D) {
     const int64_t i = (int64_t) blockIdx.x * 256 + threadIdx.x;
     if (i >= D) return;
-    float aa = aa_in[i], bb = bb_in[i], pp = pp_in[i];
+    float aa = state_in[i], bb = state_in[D + i], pp = state_in[2 * D + i];
     const float u = tf[i], w = td[i];
-    for (int64_t t = 0; t < T; t++) {
+    for (int64_t t = t0; t < t1; t++) {
         const float kk = k[t * D + i], vv = v[t * D + i];
         float ww = u + kk;
         float qq = fmaxf(pp, ww);
@@ -894,23 +914,35 @@ __global__ __launch_bounds__(256) void k_wkv4(const float * __restrict__ k, cons
         pp = qq;
         out[t * D + i] = r[t * D + i] * (a / b);
     }
-    aa_out[i] = aa; bb_out[i] = bb; pp_out[i] = pp;
+    state_out[i] = aa; state_out[D + i] = bb; state_out[2 * D + i] = pp;
+}
+
+__global__ __launch_bounds__(256) void k_wkv4(const float * __restrict__ k, const float * __restrict__ v, const float * __restrict__ r,
+                                              const float * __restrict__ tf, const float * __restrict__ td,
+                                              const float * __restrict__ state_in, float * __restrict__ state_out, float * __restrict__ out,
+                                              int64_t T, int64_t D) {
+    wkv4_body(k, v, r, tf, td, state_in, state_out, out, 0, T, D);
+}
+
+__global__ __launch_bounds__(256) void k_wkv4_rows(const float * __restrict__ k, const float * __restrict__ v, const float * __restrict__ r,
+                                                   const float * __restrict__ tf, const float * __restrict__ td, const RowState * __restrict__ rows,
+                                                   int64_t so, float * __restrict__ out, int64_t D) {
+    const int64_t t = blockIdx.y;
+    wkv4_body(k, v, r, tf, td, rows[t].in + so, rows[t].out + so, out, t, t + 1, D);
 }
 
 void launch_wkv4(const float * k, const float * v, const float * r, const float * time_first, const float * time_decay,
-                 const float * aa_in, const float * bb_in, const float * pp_in, float * aa_out, float * bb_out, float * pp_out,
-                 float * out, int64_t T, int64_t D, hipStream_t st) {
-    hipLaunchKernelGGL(k_wkv4, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, st, k, v, r, time_first, time_decay,
-                       aa_in, bb_in, pp_in, aa_out, bb_out, pp_out, out, T, D);
+                 const StateRef & s, float * out, int64_t T, int64_t D, hipStream_t st) {
+    const unsigned nb = (unsigned) ((D + 255) / 256);
+    if (s.rows) hipLaunchKernelGGL(k_wkv4_rows, dim3(nb, (unsigned) T), dim3(256), 0, st, k, v, r, time_first, time_decay, s.rows, s.off, out, D);
+    else hipLaunchKernelGGL(k_wkv4, dim3(nb), dim3(256), 0, st, k, v, r, time_first, time_decay, s.in + s.off, s.out + s.off, out, T, D);
 }
 
 // wkv6: one wave per head, lane j owns value column j of state[h][:, j] (SREG = S when S is a supported compile-time
 // size, else the state column is kept in global memory -- generic path for unusual head sizes).
 template <int S>
-__global__ __launch_bounds__(64) void k_wkv6(const float * __restrict__ r, const float * __restrict__ k, const float * __restrict__ v,
-                                             const float * __restrict__ u, int u_per_chan, const float * __restrict__ w, int w_mode,
-                                             const float * __restrict__ state_in, float * __restrict__ state_out, float * __restrict__ out,
-                                             int64_t T, int64_t H) {
+__device__ __forceinline__ void wkv6_body(const float * r, const float * k, const float * v, const float * u, int u_per_chan, const float * w, int w_mode,
+                                          const float * state_in, float * state_out, float * out, int64_t t0, int64_t t1, int64_t H) {
     __shared__ float l_r[S], l_k[S], l_u[S], l_w[S];
     const int64_t h = blockIdx.x;
     const int j = threadIdx.x;
@@ -924,7 +956,7 @@ __global__ __launch_bounds__(64) void k_wkv6(const float * __restrict__ r, const
         l_u[j] = u_per_chan ? u[h * S + j] : u[h];
         if (w_mode < 2) l_w[j] = (w_mode == 1) ? w[h * S + j] : w[h];
     }
-    for (int64_t t = 0; t < T; t++) {
+    for (int64_t t = t0; t < t1; t++) {
         __syncthreads();
         if (j < S) {
             l_r[j] = r[t * D + h * S + j];
@@ -952,15 +984,14 @@ __global__ __launch_bounds__(64) void k_wkv6(const float * __restrict__ r, const
     }
 }
 
-__global__ __launch_bounds__(256) void k_wkv6_generic(const float * __restrict__ r, const float * __restrict__ k, const float * __restrict__ v,
-                                                      const float * __restrict__ u, int u_per_chan, const float * __restrict__ w, int w_mode,
-                                                      const float * __restrict__ state_in, float * __restrict__ state_out, float * __restrict__ out,
-                                                      int64_t T, int64_t H, int64_t S) {
+__device__ __forceinline__ void wkv6_body_generic(const float * r, const float * k, const float * v, const float * u, int u_per_chan,
+                                                  const float * w, int w_mode,
+                                                  const float * state_in, float * state_out, float * out, int64_t t0, int64_t t1, int64_t H, int64_t S) {
     const int64_t h = blockIdx.x;
     const int64_t D = H * S;
     for (int64_t j = threadIdx.x; j < S; j += blockDim.x) {
-        for (int64_t t = 0; t < T; t++) {
-            const float * sin = (t == 0) ? state_in : state_out;
+        for (int64_t t = t0; t < t1; t++) {
+            const float * sin = (t == t0) ? state_in : state_out;
             const float vj = v[t * D + h * S + j];
             float o = 0.0f;
             for (int64_t i = 0; i < S; i++) {
@@ -978,23 +1009,56 @@ __global__ __launch_bounds__(256) void k_wkv6_generic(const float * __restrict__
     }
 }
 
+template <int S>
+__global__ __launch_bounds__(64) void k_wkv6(const float * __restrict__ r, const float * __restrict__ k, const float * __restrict__ v,
+                                             const float * __restrict__ u, int u_per_chan, const float * __restrict__ w, int w_mode,
+                                             const float * __restrict__ state_in, float * __restrict__ state_out, float * __restrict__ out,
+                                             int64_t T, int64_t H) {
+    wkv6_body<S>(r, k, v, u, u_per_chan, w, w_mode, state_in, state_out, out, 0, T, H);
+}
+
+template <int S>
+__global__ __launch_bounds__(64) void k_wkv6_rows(const float * __restrict__ r, const float * __restrict__ k, const float * __restrict__ v,
+                                                  const float * __restrict__ u, int u_per_chan, const float * __restrict__ w, int w_mode,
+                                                  const RowState * __restrict__ rows, int64_t so, float * __restrict__ out, int64_t H) {
+    const int64_t t = blockIdx.y;
+    wkv6_body<S>(r, k, v, u, u_per_chan, w, w_mode, rows[t].in + so, rows[t].out + so, out, t, t + 1, H);
+}
+
+__global__ __launch_bounds__(256) void k_wkv6_generic(const float * __restrict__ r, const float * __restrict__ k, const float * __restrict__ v,
+                                                      const float * __restrict__ u, int u_per_chan, const float * __restrict__ w, int w_mode,
+                                                      const float * __restrict__ state_in, float * __restrict__ state_out, float * __restrict__ out,
+                                                      int64_t T, int64_t H, int64_t S) {
+    wkv6_body_generic(r, k, v, u, u_per_chan, w, w_mode, state_in, state_out, out, 0, T, H, S);
+}
+
+__global__ __launch_bounds__(256) void k_wkv6_rows_generic(const float * __restrict__ r, const float * __restrict__ k, const float * __restrict__ v,
+                                                           const float * __restrict__ u, int u_per_chan, const float * __restrict__ w, int w_mode,
+                                                           const RowState * __restrict__ rows, int64_t so, float * __restrict__ out, int64_t H, int64_t S) {
+    const int64_t t = blockIdx.y;
+    wkv6_body_generic(r, k, v, u, u_per_chan, w, w_mode, rows[t].in + so, rows[t].out + so, out, t, t + 1, H, S);
+}
+
 void launch_wkv6(const float * r, const float * k, const float * v, const float * u, int u_per_chan, const float * w, int w_mode,
-                 const float * state_in, float * state_out, float * out, int64_t T, int64_t H, int64_t S, hipStream_t st) {
+                 const StateRef & s, float * out, int64_t T, int64_t H, int64_t S, hipStream_t st) {
+    const dim3 grid((unsigned) H, s.rows ? (unsigned) T : 1u);
+    auto go = [&](auto seq, auto row, unsigned block, auto... generic_s) {
+        if (s.rows) hipLaunchKernelGGL(row, grid, dim3(block), 0, st, r, k, v, u, u_per_chan, w, w_mode, s.rows, s.off, out, H, generic_s...);
+        else hipLaunchKernelGGL(seq, grid, dim3(block), 0, st, r, k, v, u, u_per_chan, w, w_mode, s.in + s.off, s.out + s.off, out, T, H, generic_s...);
+    };
     switch (S) {
-        case 64: hipLaunchKernelGGL((k_wkv6<64>), dim3((unsigned) H), dim3(64), 0, st, r, k, v, u, u_per_chan, w, w_mode, state_in, state_out, out, T, H); break;
-        case 32: hipLaunchKernelGGL((k_wkv6<32>), dim3((unsigned) H), dim3(64), 0, st, r, k, v, u, u_per_chan, w, w_mode, state_in, state_out, out, T, H); break;
-        case 16: hipLaunchKernelGGL((k_wkv6<16>), dim3((unsigned) H), dim3(64), 0, st, r, k, v, u, u_per_chan, w, w_mode, state_in, state_out, out, T, H); break;
-        case 8:  hipLaunchKernelGGL((k_wkv6<8>),  dim3((unsigned) H), dim3(64), 0, st, r, k, v, u, u_per_chan, w, w_mode, state_in, state_out, out, T, H); break;
-        default: hipLaunchKernelGGL(k_wkv6_generic, dim3((unsigned) H), dim3(256), 0, st, r, k, v, u, u_per_chan, w, w_mode, state_in, state_out, out, T, H, S); break;
+        case 64: go(k_wkv6<64>, k_wkv6_rows<64>, 64); break;
+        case 32: go(k_wkv6<32>, k_wkv6_rows<32>, 64); break;
+        case 16: go(k_wkv6<16>, k_wkv6_rows<16>, 64); break;
+        case 8:  go(k_wkv6<8>, k_wkv6_rows<8>, 64); break;
+        default: go(k_wkv6_generic, k_wkv6_rows_generic, 256, S); break;
     }
 }
 
 // wkv7: one wave per head, lane i owns value row i of state[h][i, :].
 template <int S>
-__global__ __launch_bounds__(64) void k_wkv7(const float * __restrict__ r, const float * __restrict__ w, const float * __restrict__ k,
-                                             const float * __restrict__ v, const float * __restrict__ a, const float * __restrict__ b,
-                                             const float * __restrict__ state_in, float * __restrict__ state_out, float * __restrict__ out,
-                                             int64_t T, int64_t H) {
+__device__ __forceinline__ void wkv7_body(const float * r, const float * w, const float * k, const float * v, const float * a, const float * b,
+                                          const float * state_in, float * state_out, float * out, int64_t t0, int64_t t1, int64_t H) {
     __shared__ float l_r[S], l_w[S], l_k[S], l_a[S], l_b[S];
     const int64_t h = blockIdx.x;
     const int i = threadIdx.x;
@@ -1007,7 +1071,7 @@ __global__ __launch_bounds__(64) void k_wkv7(const float * __restrict__ r, const
             s[j] = q.x; s[j + 1] = q.y; s[j + 2] = q.z; s[j + 3] = q.w;
         }
     }
-    for (int64_t t = 0; t < T; t++) {
+    for (int64_t t = t0; t < t1; t++) {
         __syncthreads();
         if (i < S) {
             const int64_t o = t * D + h * S + i;
@@ -1037,15 +1101,13 @@ __global__ __launch_bounds__(64) void k_wkv7(const float * __restrict__ r, const
     }
 }
 
-__global__ __launch_bounds__(256) void k_wkv7_generic(const float * __restrict__ r, const float * __restrict__ w, const float * __restrict__ k,
-                                                      const float * __restrict__ v, const float * __restrict__ a, const float * __restrict__ b,
-                                                      const float * __restrict__ state_in, float * __restrict__ state_out, float * __restrict__ out,
-                                                      int64_t T, int64_t H, int64_t S) {
+__device__ __forceinline__ void wkv7_body_generic(const float * r, const float * w, const float * k, const float * v, const float * a, const float * b,
+                                                  const float * state_in, float * state_out, float * out, int64_t t0, int64_t t1, int64_t H, int64_t S) {
     const int64_t h = blockIdx.x;
     const int64_t D = H * S;
     for (int64_t i = threadIdx.x; i < S; i += blockDim.x) {
-        for (int64_t t = 0; t < T; t++) {
-            const float * sin = (t == 0) ? state_in : state_out;
+        for (int64_t t = t0; t < t1; t++) {
+            const float * sin = (t == t0) ? state_in : state_out;
             const int64_t base = t * D + h * S;
             const float vi = v[base + i];
             float sa = 0.0f;
@@ -1062,12 +1124,47 @@ __global__ __launch_bounds__(256) void k_wkv7_generic(const float * __restrict__
     }
 }
 
+template <int S>
+__global__ __launch_bounds__(64) void k_wkv7(const float * __restrict__ r, const float * __restrict__ w, const float * __restrict__ k,
+                                             const float * __restrict__ v, const float * __restrict__ a, const float * __restrict__ b,
+                                             const float * __restrict__ state_in, float * __restrict__ state_out, float * __restrict__ out,
+                                             int64_t T, int64_t H) {
+    wkv7_body<S>(r, w, k, v, a, b, state_in, state_out, out, 0, T, H);
+}
+
+template <int S>
+__global__ __launch_bounds__(64) void k_wkv7_rows(const float * __restrict__ r, const float * __restrict__ w, const float * __restrict__ k,
+                                                  const float * __restrict__ v, const float * __restrict__ a, const float * __restrict__ b,
+                                                  const RowState * __restrict__ rows, int64_t so, float * __restrict__ out, int64_t H) {
+    const int64_t t = blockIdx.y;
+    wkv7_body<S>(r, w, k, v, a, b, rows[t].in + so, rows[t].out + so, out, t, t + 1, H);
+}
+
+__global__ __launch_bounds__(256) void k_wkv7_generic(const float * __restrict__ r, const float * __restrict__ w, const float * __restrict__ k,
+                                                      const float * __restrict__ v, const float * __restrict__ a, const float * __restrict__ b,
+                                                      const float * __restrict__ state_in, float * __restrict__ state_out, float * __restrict__ out,
+                                                      int64_t T, int64_t H, int64_t S) {
+    wkv7_body_generic(r, w, k, v, a, b, state_in, state_out, out, 0, T, H, S);
+}
+
+__global__ __launch_bounds__(256) void k_wkv7_rows_generic(const float * __restrict__ r, const float * __restrict__ w, const float * __restrict__ k,
+                                                           const float * __restrict__ v, const float * __restrict__ a, const float * __restrict__ b,
+                                                           const RowState * __restrict__ rows, int64_t so, float * __restrict__ out, int64_t H, int64_t S) {
+    const int64_t t = blockIdx.y;
+    wkv7_body_generic(r, w, k, v, a, b, rows[t].in + so, rows[t].out + so, out, t, t + 1, H, S);
+}
+
 void launch_wkv7(const float * r, const float * w, const float * k, const float * v, const float * a, const float * b,
-                 const float * state_in, float * state_out, float * out, int64_t T, int64_t H, int64_t S, hipStream_t st) {
+                 const StateRef & s, float * out, int64_t T, int64_t H, int64_t S, hipStream_t st) {
+    const dim3 grid((unsigned) H, s.rows ? (unsigned) T : 1u);
+    auto go = [&](auto seq, auto row, unsigned block, auto... generic_s) {
+        if (s.rows) hipLaunchKernelGGL(row, grid, dim3(block), 0, st, r, w, k, v, a, b, s.rows, s.off, out, H, generic_s...);
+        else hipLaunchKernelGGL(seq, grid, dim3(block), 0, st, r, w, k, v, a, b, s.in + s.off, s.out + s.off, out, T, H, generic_s...);
+    };
     switch (S) {
-        case 64: hipLaunchKernelGGL((k_wkv7<64>), dim3((unsigned) H), dim3(64), 0, st, r, w, k, v, a, b, state_in, state_out, out, T, H); break;
-        case 32: hipLaunchKernelGGL((k_wkv7<32>), dim3((unsigned) H), dim3(64), 0, st, r, w, k, v, a, b, state_in, state_out, out, T, H); break;
-        default: hipLaunchKernelGGL(k_wkv7_generic, dim3((unsigned) H), dim3(256), 0, st, r, w, k, v, a, b, state_in, state_out, out, T, H, S); break;
+        case 64: go(k_wkv7<64>, k_wkv7_rows<64>, 64); break;
+        case 32: go(k_wkv7<32>, k_wkv7_rows<32>, 64); break;
+        default: go(k_wkv7_generic, k_wkv7_rows_generic, 256, S); break;
     }
 }
 
@@ -1176,9 +1273,12 @@ void launch_fill_state_v4(float * state, int64_t n_layer, int64_t D, hipStream_t
     hipLaunchKernelGGL(k_fill_state_v4, dim3(grid), dim3(256), 0, st, state, n_layer, D);
 }
 
-__global__ __launch_bounds__(1024) void k_argmax(const float * __restrict__ logits, int64_t n, uint32_t * __restrict__ out) {
+// one workgroup per row of logits[rows][n]
+__global__ __launch_bounds__(1024) void k_argmax(const float * __restrict__ logits_all, int64_t n, uint32_t * __restrict__ out, uint32_t * __restrict__ hist) {
     __shared__ float l_v[16];
     __shared__ int l_i[16];
+    const int64_t row = blockIdx.x;
+    const float * __restrict__ logits = logits_all + row * n;
     float best = -INFINITY;
     int bi = 0x7fffffff;
     int64_t i = threadIdx.x;
@@ -1207,11 +1307,13 @@ __global__ __launch_bounds__(1024) void k_argmax(const float * __restrict__ logi
             if (l_v[w] > best || (l_v[w] == best && l_i[w] < bi)) { best = l_v[w]; bi = l_i[w]; }
         // (no element compared greater than -inf: every logit is NaN or -inf, e.g. after a poll time-out of the persistent kernel on a
         //  shared GPU. The token feeds the next embedding lookup on the device: it must stay a row of the table.)
-        *out = bi == 0x7fffffff ? 0u : (uint32_t) bi;
+        const uint32_t tok = bi == 0x7fffffff ? 0u : (uint32_t) bi;
+        out[row] = tok;
+        if (hist) hist[row] = tok;
     }
 }
-void launch_argmax(const float * logits, int64_t n, uint32_t * out, hipStream_t st) {
-    hipLaunchKernelGGL(k_argmax, dim3(1), dim3(1024), 0, st, logits, n, out);
+void launch_argmax(const float * logits, int64_t rows, int64_t n, uint32_t * out, uint32_t * hist, hipStream_t st) {
+    hipLaunchKernelGGL(k_argmax, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, out, hist);
 }
 
 // load-time transpose of the v6 mix matrix: [5][D][R] (file) -> [5][R][D], so that lanes read consecutive d

@@ -65,9 +65,9 @@ static bool fetch_outputs(rwkv_context * ctx, float * state_out, float * logits_
     if (state_out && !state_to_host(ctx, state_out)) return false;
     if (logits_out) HIP_CTX_OK(ctx, hipMemcpyAsync(logits_out, ctx->d_logits, (size_t) ctx->model->n_vocab() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     // (a control-word copy that could not even be enqueued leaves a stale "not aborted" mirror: treated as an abort)
-    const bool ctl_ok = !ctx->mega || mega_v6_ctl_fetch(ctx->mega, ctx->stream);
+    const bool ctl_ok = !ctx->mega || ctx->mega->ctl.fetch(ctx->stream);
     HIP_CTX_OK(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->mega && (!ctl_ok || mega_v6_aborted_cached(ctx->mega))) {
+    if (ctx->mega && (!ctl_ok || ctx->mega->ctl.aborted_cached())) {
         recover_from_abort(ctx);
         if (aborted) { *aborted = true; return true; }
         RW_CTX_CHECK(ctx, RWKV_ERROR_GRAPH, false, false, "%s", k_abort_msg);
@@ -293,9 +293,9 @@ RWKV_API bool rwkv_mi_decode_greedy(struct rwkv_context * ctx, uint32_t first_to
     uint32_t * d_hist = hist.p;
     HIP_CTX_OK(ctx, hipStreamSynchronize(ctx->stream));
     // persist_v47.hip: the launch itself picks the token, leaves it where its own embedding lookup reads it and appends it to the history
-    const bool in_launch = folded_argmax_target(ctx) == ctx->d_tokens && mega_v6_set_history(ctx->mega, d_hist, n_tokens, ctx->stream);
+    const bool in_launch = folded_argmax_target(ctx) == ctx->d_tokens && ctx->mega->set_history(d_hist, n_tokens, ctx->stream);
     // (every exit from here on takes the history pointer out of the kernel's control words again: d_hist is freed when this function returns)
-    struct HistGuard { rwkv_context * c; bool on; ~HistGuard() { if (on && c->mega) (void) mega_v6_set_history(c->mega, nullptr, 0, c->stream); } } hist_guard{ctx, in_launch};
+    struct HistGuard { rwkv_context * c; bool on; ~HistGuard() { if (on && c->mega) (void) c->mega->set_history(nullptr, 0, c->stream); } } hist_guard{ctx, in_launch};
     HIP_CTX_OK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
     bool ok = true;
     for (size_t i = 0; i < n_tokens && ok; i++) {
@@ -308,7 +308,7 @@ RWKV_API bool rwkv_mi_decode_greedy(struct rwkv_context * ctx, uint32_t first_to
     }
     if (in_launch && ctx->mega) {
         const bool drained = hipEventRecord(ctx->ev1, ctx->stream) == hipSuccess && hipStreamSynchronize(ctx->stream) == hipSuccess;
-        ok = mega_v6_set_history(ctx->mega, nullptr, 0, ctx->stream) && drained && ok;
+        ok = ctx->mega->set_history(nullptr, 0, ctx->stream) && drained && ok;
         hist_guard.on = false;
         if (ok && elapsed_ms) ok = hipEventElapsedTime(elapsed_ms, ctx->ev0, ctx->ev1) == hipSuccess;
         if (ok && tokens_out) ok = hipMemcpyAsync(tokens_out, d_hist, n_tokens * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
@@ -472,18 +472,26 @@ RWKV_API void rwkv_mi_set_graph_enabled(struct rwkv_context * ctx, bool enabled)
 
 RWKV_API bool rwkv_mi_decode_healthy(struct rwkv_context * ctx) {
     if (hipSetDevice(ctx->model->device) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) return false;
-    return !(ctx->mega && mega_v6_aborted(ctx->mega, ctx->stream));
+    return !(ctx->mega && ctx->mega->ctl.aborted(ctx->stream));
 }
 
 RWKV_API int rwkv_mi_decode_path(const struct rwkv_context * ctx) { return ctx->mega ? 2 : ((ctx->fused_v6 || ctx->fused_v7 || ctx->fused_v4) ? 1 : 0); }
-RWKV_API int rwkv_mi_persist_kind(const struct rwkv_context * ctx) { return mega_v6_kind((ctx->stages.empty() ? ctx : ctx->stages.front())->mega); }   // (a chain: its first stage's)
+// the documented values of rwkv_mi_persist_kind (include/rwkv_mi355x.h) for the kernel a context holds
+static int public_persist_kind(const rwkv_context * c) {
+    switch (c->mega ? c->mega->kind() : DecodePath::Unmeasured) {
+        case DecodePath::Regs: return 1;
+        case DecodePath::Ring: return 2;
+        case DecodePath::K47:  return 3;
+        default:               return 0;
+    }
+}
+RWKV_API int rwkv_mi_persist_kind(const struct rwkv_context * ctx) { return public_persist_kind(ctx->stages.empty() ? ctx : ctx->stages.front()); }   // (a chain: its first stage's)
 // "persist: ring | regs | k47 | none; <why>": which persistent kernel serves this context's single-token steps and what decided it
 // (geometry / device / environment at creation, the calibration's figures, a fall-back after a poll time-out). Valid until the next call on ctx.
 RWKV_API const char * rwkv_mi_persist_info(struct rwkv_context * ctx) {
     static thread_local std::string out;
     rwkv_context * c = ctx->stages.empty() ? ctx : ctx->stages.front();
-    const int k = mega_v6_kind(c->mega);
-    out = std::string("persist: ") + (k == 2 ? "ring" : (k == 1 ? "regs" : (k == 3 ? "k47" : "none")));
+    out = std::string("persist: ") + decode_path_name(c->mega ? c->mega->kind() : DecodePath::Unmeasured);
     if (!c->persist_note.empty()) out += "; " + c->persist_note;
     return out.c_str();
 }
@@ -578,11 +586,11 @@ RWKV_API const float * rwkv_mi_logits_device_ptr(const struct rwkv_context * ctx
 RWKV_API bool rwkv_mi_trace_phases(struct rwkv_context * ctx, uint32_t token, int layer, int n, long long * out) {
     if (!ctx->mega) return false;
     const bool g = ctx->use_graph; ctx->use_graph = false;
-    bool ok = mega_v6_trace(ctx->mega, layer, out, false);
+    bool ok = ctx->mega->trace(layer, out, false);
     for (int i = 0; i < n && ok; i++) ok = run_tokens(ctx, &token, 1, true);
     (void) hipStreamSynchronize(ctx->stream);
     ctx->use_graph = g;
-    return ok && mega_v6_trace(ctx->mega, layer, out, true);
+    return ok && ctx->mega->trace(layer, out, true);
 }
 
 // The persistent decode kernel's hand-over generation (it advances by 8 per layer and launch; the kernel compares its low 16 bits).
@@ -590,7 +598,7 @@ RWKV_API bool rwkv_mi_trace_phases(struct rwkv_context * ctx, uint32_t token, in
 RWKV_API uint32_t rwkv_mi_decode_generation(struct rwkv_context * ctx) {
     rwkv_context * c = ctx->stages.empty() ? ctx : ctx->stages.front();
     if (!c->mega || hipSetDevice(c->model->device) != hipSuccess) return 0;
-    return mega_v6_generation(c->mega, c->stream);
+    return c->mega->ctl.generation(c->stream);
 }
 
 }  // extern "C"

@@ -79,7 +79,6 @@ static void mega_chain_forget(rwkv_context * ctx) {
 }
 
 // what decided a context's single-token path, in words (rwkv_mi_persist_info)
-static const char * kind_name(int k) { return k == 2 ? "ring" : (k == 1 ? "regs" : (k == 3 ? "k47" : "none")); }
 static void note(rwkv_context * ctx, const char * fmt, ...) {
     char buf[320];
     va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
@@ -88,113 +87,81 @@ static void note(rwkv_context * ctx, const char * fmt, ...) {
 }
 
 // Which single-token path is fastest depends on the device: the persistent kernels are bound by cross-XCD hand-over latency, the
-// seven-launch path by launch boundaries (measured: 1.5-1.6 ms vs 2.6 ms per token on most MI355X boxes, but on some boxes four of
-// the eight XCDs lag and a chain of all-to-all hand-overs runs at their pace: 3.4 ms vs 2.9 ms). A few eager tokens on zeroed state
-// settle it per context at creation: the persistent kernel on the LDS-DMA weight ring (ring_v6.hip), the one on register prefetch
-// (mega_v6.hip; only built for the comparison when RWKV_MI_PERSIST does not name one) and the seven launches are timed, the fastest
-// stays, the others are freed. The state is (re)initialised by every caller afterwards.
-static void calibrate_decode_path(rwkv_context * ctx) {
-    if (!ctx->mega || !ctx->fused_v6) return;
-    const char * e = getenv("RWKV_MI_NO_AUTOTUNE");
-    if (e && e[0] == '1') return;
+// per-layer launches by launch boundaries (RWKV-6, measured: 1.5-1.6 ms vs 2.6 ms per token on most MI355X boxes, but on some boxes
+// four of the eight XCDs lag and a chain of all-to-all hand-overs runs at their pace: 3.4 ms vs 2.9 ms). A few eager tokens settle it
+// per context at creation: every persistent candidate in cand, then the per-layer launches (fused_v6.hip / fused_v7.hip), 2 warm + 6
+// timed tokens each; the fastest stays in ctx->mega, the others are freed. RWKV-6 times on state zeroed once, RWKV-4 / RWKV-7 from a
+// fresh state per timing. The state is (re)initialised by every caller afterwards.
+static void calibrate_decode_path(rwkv_context * ctx, std::vector<std::unique_ptr<PersistentDecoder>> cand) {
     Model & m = *ctx->model;
+    const bool v6 = m.arch_major == 6;
     uint32_t * tok = nullptr;
-    if (hipMalloc((void **) &tok, 256) != hipSuccess) return;
+    if (hipMalloc((void **) &tok, 256) != hipSuccess) { ctx->mega = std::move(cand[0]); return; }
     const size_t sbytes = (size_t) m.state_len() * sizeof(float);
     bool ok = hipMemsetAsync(tok, 0, 256, ctx->stream) == hipSuccess;
-    for (int i = 0; i < 2; i++) ok = ok && hipMemsetAsync(ctx->state[i], 0, sbytes, ctx->stream) == hipSuccess;
+    for (int i = 0; v6 && i < 2; i++) ok = ok && hipMemsetAsync(ctx->state[i], 0, sbytes, ctx->stream) == hipSuccess;
     uint32_t * saved_tokens = ctx->d_tokens;
     ctx->d_tokens = tok;
-    // candidates: [0] the handle create_context made, [1] the other persistent kernel (when the environment names none), fused = nullptr
-    void * cand[2] = {ctx->mega, nullptr};
-    const char * pk = getenv("RWKV_MI_PERSIST");
-    // (the register-prefetch kernel only where it has been seen within 2 % of the ring: D = 2048 -- profiles/r04y_prefill_1b6_q4_0_kernel_stats.csv
-    //  calibration rows, 710 vs 726 us; at D = 4096 / 2560 the ring wins by 10 % and more and timing a third path cost every context
-    //  creation ~15 ms. RWKV_MI_PERSIST=regs still names it.)
-    if (!(pk && pk[0]) && mega_v6_kind(cand[0]) == 2 && m.n_embed() == 2048) cand[1] = mega_v6_create_kind(m, 1);
-    // (with logits: the ring kernel runs ln_out + head inside its launch, the other paths as launches of their own -- part of what is compared)
-    auto run = [&](void * h, int n) { ctx->mega = h; for (int i = 0; i < n && ok; i++) ok = forward(ctx, 1, m.has_head); };
-    auto timed = [&](void * h) -> float {
-        run(h, 2);
-        ok = ok && hipEventRecord(ctx->ev0, ctx->stream) == hipSuccess;
-        run(h, 6);
-        ok = ok && hipEventRecord(ctx->ev1, ctx->stream) == hipSuccess && hipStreamSynchronize(ctx->stream) == hipSuccess;
-        float ms = 0.0f;
-        ok = ok && hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1) == hipSuccess;
-        return ms;
-    };
-    float t[2] = {1e30f, 1e30f};
-    bool bad[2] = {false, true};
-    for (int i = 0; i < 2; i++) {
-        if (!cand[i]) continue;
-        t[i] = timed(cand[i]);
-        bad[i] = !ok || mega_v6_aborted(cand[i], ctx->stream);
-        if (bad[i]) { if (mega_v6_aborted_cached(cand[i])) (void) mega_v6_clear_abort(cand[i], ctx->stream); ok = true; t[i] = 1e30f; }
-    }
-    const float t_fused = timed(nullptr);
-    (void) hipStreamSynchronize(ctx->stream);
-    ctx->d_tokens = saved_tokens;
-    ctx->cur = 0;
-    ctx->last_error = 0;
-    (void) hipFree(tok);
-    const int best = t[1] < t[0] ? 1 : 0;
-    const bool keep = ok && !bad[best] && !(t_fused < 0.97f * t[best]);
-    for (int i = 0; i < 2; i++) if (cand[i] && bad[i]) note(ctx, "calibration: the %s kernel timed out (not every workgroup resident)", kind_name(mega_v6_kind(cand[i])));
-    if (cand[best] && !bad[best]) note(ctx, "calibration: %s %.3f ms / token against %.3f ms for the per-layer launches: %s", kind_name(mega_v6_kind(cand[best])), t[best] / 6.0f, t_fused / 6.0f, keep ? "kept" : "dropped");
-    for (int i = 0; i < 2; i++) if (cand[i] && !(keep && i == best)) mega_v6_destroy(cand[i]);
-    ctx->mega = keep ? cand[best] : nullptr;
-    if (ok) m.decode_choice.store(keep ? mega_v6_kind(cand[best]) : 3);
-    if (!keep) { mega_chain_forget(ctx); mega_chain_count(ctx, -1); }
-}
-
-// The same question for RWKV-4 / RWKV-7: the persistent launch of persist_v47.hip against the fused per-layer launches (fused_v7.hip).
-static void calibrate_decode_path_v47(rwkv_context * ctx) {
-    if (!ctx->mega) return;
-    const char * e = getenv("RWKV_MI_NO_AUTOTUNE");
-    if (e && e[0] == '1') return;
-    Model & m = *ctx->model;
-    uint32_t * tok = nullptr;
-    if (hipMalloc((void **) &tok, 256) != hipSuccess) return;
-    bool ok = hipMemsetAsync(tok, 0, 256, ctx->stream) == hipSuccess;
-    uint32_t * saved_tokens = ctx->d_tokens;
-    ctx->d_tokens = tok;
-    void * const h = ctx->mega;
-    auto timed = [&](void * hh) -> float {
-        ctx->mega = hh;
-        ctx->cur = 0;
-        ok = ok && state_from_host(ctx, nullptr);
+    // (with logits: a kernel that folds ln_out + head runs them inside its launch, the other paths as launches of their own -- part of what is compared)
+    auto timed = [&](std::unique_ptr<PersistentDecoder> & h) -> float {
+        ctx->mega.swap(h);
+        if (!v6) { ctx->cur = 0; ok = ok && state_from_host(ctx, nullptr); }
         for (int i = 0; i < 2 && ok; i++) ok = forward(ctx, 1, m.has_head);
         ok = ok && hipEventRecord(ctx->ev0, ctx->stream) == hipSuccess;
         for (int i = 0; i < 6 && ok; i++) ok = forward(ctx, 1, m.has_head);
         ok = ok && hipEventRecord(ctx->ev1, ctx->stream) == hipSuccess && hipStreamSynchronize(ctx->stream) == hipSuccess;
         float ms = 0.0f;
         ok = ok && hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1) == hipSuccess;
+        ctx->mega.swap(h);
         return ms;
     };
-    float t_p = timed(h);
-    bool bad = !ok || mega_v6_aborted(h, ctx->stream);
-    if (bad) { if (mega_v6_aborted_cached(h)) (void) mega_v6_clear_abort(h, ctx->stream); ok = true; t_p = 1e30f; }
-    float t_fused = timed(nullptr);
-    // six tokens each on a device that may be busy: a margin under 10 % is timed once more and the smaller figures decide (the choice is kept for
-    // every later context of the model)
-    if (!bad && ok && fabsf(t_fused - t_p) < 0.10f * t_p) {
-        const float p2 = timed(h);
-        const bool bad2 = !ok || mega_v6_aborted(h, ctx->stream);
-        if (bad2) { if (mega_v6_aborted_cached(h)) (void) mega_v6_clear_abort(h, ctx->stream); ok = true; bad = true; t_p = 1e30f; }
-        else { t_p = p2 < t_p ? p2 : t_p; const float f2 = timed(nullptr); t_fused = f2 < t_fused ? f2 : t_fused; }
+    // a candidate whose timing failed or whose poll timed out is out: its abort word is cleared and the comparison goes on without it
+    auto timed_out = [&](PersistentDecoder & h) {
+        const bool bad = !ok || h.ctl.aborted(ctx->stream);
+        if (bad) { if (h.ctl.aborted_cached()) (void) h.ctl.clear_abort(ctx->stream); ok = true; }
+        return bad;
+    };
+    std::unique_ptr<PersistentDecoder> launches;   // (no persistent kernel: the per-layer launches)
+    std::vector<float> t(cand.size(), 1e30f);
+    std::vector<char> bad(cand.size(), 0);
+    size_t best = 0;
+    for (size_t i = 0; i < cand.size(); i++) {
+        t[i] = timed(cand[i]);
+        bad[i] = timed_out(*cand[i]);
+        if (bad[i]) t[i] = 1e30f;
+        if (t[i] < t[best]) best = i;
+    }
+    float t_fused = timed(launches);
+    // RWKV-4 / RWKV-7: six tokens each on a device that may be busy: a margin under 10 % is timed once more and the smaller figures decide (the
+    // choice is kept for every later context of the model)
+    if (!v6 && !bad[best] && ok && fabsf(t_fused - t[best]) < 0.10f * t[best]) {
+        const float p2 = timed(cand[best]);
+        if (timed_out(*cand[best])) { bad[best] = 1; t[best] = 1e30f; }
+        else { t[best] = p2 < t[best] ? p2 : t[best]; const float f2 = timed(launches); t_fused = f2 < t_fused ? f2 : t_fused; }
     }
     (void) hipStreamSynchronize(ctx->stream);
     ctx->d_tokens = saved_tokens;
     ctx->cur = 0;
     ctx->last_error = 0;
     (void) hipFree(tok);
-    const bool keep = ok && !bad && !(t_fused < 0.97f * t_p);
-    if (bad) note(ctx, "calibration: the k47 kernel timed out (not every workgroup resident)");
-    else note(ctx, "calibration: k47 %.3f ms / token against %.3f ms for the per-layer launches: %s", t_p / 6.0f, t_fused / 6.0f, keep ? "kept" : "dropped");
-    if (!keep) mega_v6_destroy(h);
-    ctx->mega = keep ? h : nullptr;
-    if (ok) m.decode_choice.store(keep ? 4 : 3);
-    if (!keep) { mega_chain_forget(ctx); mega_chain_count(ctx, -1); }
+    const bool keep = ok && !bad[best] && !(t_fused < 0.97f * t[best]);
+    for (size_t i = 0; i < cand.size(); i++) if (bad[i]) note(ctx, "calibration: the %s kernel timed out (not every workgroup resident)", decode_path_name(cand[i]->kind()));
+    if (!bad[best]) note(ctx, "calibration: %s %.3f ms / token against %.3f ms for the per-layer launches: %s", decode_path_name(cand[best]->kind()), t[best] / 6.0f, t_fused / 6.0f, keep ? "kept" : "dropped");
+    if (ok) m.decode_choice.store(keep ? cand[best]->kind() : DecodePath::Launches);
+    if (keep) ctx->mega = std::move(cand[best]);
+    else { mega_chain_forget(ctx); mega_chain_count(ctx, -1); }
+}
+
+// The persistent kernel a new context of m starts from (nullptr: none qualifies). known: what an earlier context of the model measured.
+// RWKV-6, nothing measured yet: RWKV_MI_PERSIST = ring | regs names the kernel; by default the LDS-DMA ring, else the register prefetch.
+static PersistentDecoder * create_decoder(const Model & m, DecodePath known) {
+    if (m.arch_major != 6) return p47_create(m);
+    if (known == DecodePath::Regs) return mega_v6_create(m);
+    if (known == DecodePath::Ring) return ring_v6_create(m);
+    const char * pk = getenv("RWKV_MI_PERSIST");
+    const bool want_ring = !(pk && strcmp(pk, "regs") == 0), want_regs = !(pk && strcmp(pk, "ring") == 0);
+    if (want_ring) { PersistentDecoder * r = ring_v6_create(m); if (r || !want_regs) return r; }
+    return mega_v6_create(m);
 }
 
 // After a poll time-out of the persistent kernel (the device was shared): the stream is drained, the abort word cleared, the
@@ -202,13 +169,12 @@ static void calibrate_decode_path_v47(rwkv_context * ctx) {
 // step READ is intact (the kernel only writes the other one): the caller may flip `cur` back and repeat the step.
 void recover_from_abort(rwkv_context * ctx) {
     if (!ctx->mega) return;
-    note(ctx, "a poll of the %s kernel timed out at run time (not every workgroup resident: is the GPU shared?): fell back to the per-layer launches", kind_name(mega_v6_kind(ctx->mega)));
+    note(ctx, "a poll of the %s kernel timed out at run time (not every workgroup resident: is the GPU shared?): fell back to the per-layer launches", decode_path_name(ctx->mega->kind()));
     (void) hipStreamSynchronize(ctx->stream);
-    (void) mega_v6_clear_abort(ctx->mega, ctx->stream);
+    (void) ctx->mega->ctl.clear_abort(ctx->stream);
     mega_chain_forget(ctx);
     mega_chain_count(ctx, -1);
-    mega_v6_destroy(ctx->mega);
-    ctx->mega = nullptr;
+    ctx->mega.reset();
     for (int a = 0; a < 2; a++) for (int b = 0; b < 2; b++) if (ctx->graph_exec[a][b]) { (void) hipGraphExecDestroy(ctx->graph_exec[a][b]); ctx->graph_exec[a][b] = nullptr; }
 }
 
@@ -245,15 +211,6 @@ rwkv_context * create_context(Model * m, uint32_t n_threads) {
     if (!(nf && nf[0] == '1') && fused_v6_supported(*m)) {
         if ((e = hipMalloc(&ctx->fused_scratch, fused_v6_scratch_bytes(*m))) != hipSuccess) return fail(e);
         ctx->fused_v6 = true;
-        const char * nm = getenv("RWKV_MI_NO_MEGA");
-        const int known = m->decode_choice.load();      // (what an earlier context of this model measured)
-        if (!(nm && nm[0] == '1') && known != 3) ctx->mega = known ? mega_v6_create_kind(*m, known) : mega_v6_create(*m);
-        if (nm && nm[0] == '1') note(ctx.get(), "RWKV_MI_NO_MEGA=1");
-        else if (known == 3) note(ctx.get(), "an earlier context of this model measured the per-layer launches faster");
-        else if (!ctx->mega) { const char * why = persist_unavailable_reason(*m); note(ctx.get(), "%s", why ? why : "the persistent kernel could not be built (device memory?)"); }
-        // a second persistent context on this device: launches the first one made while it was alone carry no completion event
-        if (ctx->mega && mega_chain_count(ctx.get(), +1) > 1) (void) hipDeviceSynchronize();
-        if (!known) calibrate_decode_path(ctx.get());
     }
     if (!(nf && nf[0] == '1') && fused_v7_supported(*m)) {
         if ((e = hipMalloc(&ctx->fused_scratch, fused_v7_scratch_bytes(*m))) != hipSuccess) return fail(e);
@@ -263,16 +220,24 @@ rwkv_context * create_context(Model * m, uint32_t n_threads) {
         if ((e = hipMalloc(&ctx->fused_scratch, fused_v4_scratch_bytes(*m))) != hipSuccess) return fail(e);
         ctx->fused_v4 = true;
     }
-    if (ctx->fused_v7 || ctx->fused_v4) {
-        // one persistent launch per token (persist_v47.hip) where the geometry has a variant; the fused launches stay as the fall-back
-        const char * nm = getenv("RWKV_MI_NO_MEGA");
-        const int known = m->decode_choice.load();
-        if (!(nm && nm[0] == '1') && known != 3) ctx->mega = p47_create(*m);
+    if (ctx->fused_v6 || ctx->fused_v7 || ctx->fused_v4) {
+        // one persistent launch per token where the model and the device have a variant; the fused launches stay as the fall-back
+        const char * nm = getenv("RWKV_MI_NO_MEGA"), * na = getenv("RWKV_MI_NO_AUTOTUNE"), * pk = getenv("RWKV_MI_PERSIST");
+        const DecodePath known = m->decode_choice.load();      // (what an earlier context of this model measured)
+        std::vector<std::unique_ptr<PersistentDecoder>> cand;   // the persistent candidates, in the order they are timed
+        if (!(nm && nm[0] == '1') && known != DecodePath::Launches) if (PersistentDecoder * h = create_decoder(*m, known)) cand.emplace_back(h);
         if (nm && nm[0] == '1') note(ctx.get(), "RWKV_MI_NO_MEGA=1");
-        else if (known == 3) note(ctx.get(), "an earlier context of this model measured the per-layer launches faster");
-        else if (!ctx->mega) { const char * why = persist_unavailable_reason(*m); note(ctx.get(), "%s", why ? why : "the persistent kernel could not be built (device memory?)"); }
-        if (ctx->mega && mega_chain_count(ctx.get(), +1) > 1) (void) hipDeviceSynchronize();
-        if (!known) calibrate_decode_path_v47(ctx.get());
+        else if (known == DecodePath::Launches) note(ctx.get(), "an earlier context of this model measured the per-layer launches faster");
+        else if (cand.empty()) { const char * why = persist_unavailable_reason(*m); note(ctx.get(), "%s", why ? why : "the persistent kernel could not be built (device memory?)"); }
+        // a second persistent context on this device: launches the first one made while it was alone carry no completion event
+        if (!cand.empty() && mega_chain_count(ctx.get(), +1) > 1) (void) hipDeviceSynchronize();
+        if (!cand.empty() && known == DecodePath::Unmeasured && !(na && na[0] == '1')) {
+            // (the register-prefetch kernel beside the ring only where it has been seen within 2 % of it: D = 2048 -- profiles/r04y_prefill_1b6_q4_0_kernel_stats.csv
+            //  calibration rows, 710 vs 726 us; at D = 4096 / 2560 the ring wins by 10 % and more and timing a third path cost every context
+            //  creation ~15 ms. RWKV_MI_PERSIST=regs still names it.)
+            if (!(pk && pk[0]) && cand[0]->kind() == DecodePath::Ring && m->n_embed() == 2048) if (PersistentDecoder * h = mega_v6_create(*m)) cand.emplace_back(h);
+            calibrate_decode_path(ctx.get(), std::move(cand));
+        } else if (!cand.empty()) ctx->mega = std::move(cand[0]);
     }
     if (!ctx->fused_v6 && !ctx->fused_v7 && !ctx->fused_v4) { const char * why = persist_unavailable_reason(*m); note(ctx.get(), "%s", (nf && nf[0] == '1') ? "RWKV_MI_NO_FUSED=1" : (why ? why : "no fused layer for this model")); }
     // A new context starts from the reference's fresh state (rwkv_eval.inc:224-241), whatever the calibration left behind:
@@ -295,7 +260,7 @@ void destroy_context(rwkv_context * ctx) {
     for (int i = 0; i < 2; i++) if (ctx->state[i]) (void) hipFree(ctx->state[i]);
     if (ctx->scratch) (void) hipFree(ctx->scratch);
     if (ctx->fused_scratch) (void) hipFree(ctx->fused_scratch);
-    if (ctx->mega) { mega_chain_forget(ctx); mega_chain_count(ctx, -1); mega_v6_destroy(ctx->mega); }
+    if (ctx->mega) { mega_chain_forget(ctx); mega_chain_count(ctx, -1); ctx->mega.reset(); }
     if (ctx->mega_done) (void) hipEventDestroy(ctx->mega_done);
     if (ctx->d_tokens) (void) hipFree(ctx->d_tokens);
     if (ctx->d_logits) (void) hipFree(ctx->d_logits);
@@ -652,7 +617,7 @@ struct Runner {
     }
 
     void run_embed() {
-        if (!state.rows && T == 1 && ctx->mega && m.has_embed && mega_v6_folds_embed(ctx->mega)) return;   // inside the persistent launch
+        if (!state.rows && T == 1 && ctx->mega && m.has_embed && ctx->mega->folds_embed()) return;   // inside the persistent launch
         if (m.has_embed) launch_embed_ln0(*m.emb, ctx->d_tokens, T, D, f(m.ln0_w), f(m.ln0_b), b.x, st);
     }
     // layers [lb, le) of the stage (absolute layer ids); returns true when the launch also produced the logits (ring kernel, last layers)
@@ -663,20 +628,14 @@ struct Runner {
         const int64_t per_layer = m.state_per_layer();
         const bool one = T == 1 && !state.rows;   // (the single-token paths work on the context's own state)
         if (one && ctx->mega) {
-            const bool whole = lb == m.layer_begin && le == m.layer_end;
-            const bool head_done = want_logits && m.has_head && le == m.layer_end && mega_v6_folds_head(ctx->mega);
+            const bool whole = lb == m.layer_begin && le == m.layer_end;   // (only a whole-stage launch is profiled)
+            const bool head_done = want_logits && m.has_head && le == m.layer_end && ctx->mega->folds_head();
             const float * s0 = sin + (int64_t) m.layer_begin * per_layer;
             float * o0 = sout + (int64_t) m.layer_begin * per_layer;
-            // (persist_v47.hip: the launch starts from the token id and ends with the argmax where the stage has embedding / head)
-            const uint32_t * tok = (lb == m.layer_begin && m.has_embed && mega_v6_folds_embed(ctx->mega)) ? ctx->d_tokens : nullptr;
+            // (the launch starts from the token id and ends with the argmax where the stage has embedding / head and the kernel folds them)
+            const uint32_t * tok = (lb == m.layer_begin && m.has_embed && ctx->mega->folds_embed()) ? ctx->d_tokens : nullptr;
             uint32_t * ntok = ctx->ntok_out ? ctx->ntok_out : (tok ? ctx->d_tokens : ctx->d_next_token);    // the greedy loops read the next token where the embedding reads it
-            if (whole) mega_v6_forward(ctx->mega, b.x, s0, o0, st, &ctx->prof, head_done ? ctx->d_logits : nullptr, b.v_first, tok, ntok);
-            else {
-                // (a range's state pointers are those of ITS first layer for persist_v47.hip, of the stage's first layer for the ring kernel)
-                const bool own_base = mega_v6_kind(ctx->mega) == 3;
-                const int64_t so = own_base ? (int64_t) (lb - m.layer_begin) * per_layer : 0;
-                mega_v6_forward_range(ctx->mega, b.x, s0 + so, o0 + so, st, nullptr, head_done ? ctx->d_logits : nullptr, (int) (lb - m.layer_begin), (int) (le - m.layer_begin), b.v_first, tok, ntok);
-            }
+            ctx->mega->forward_range(b.x, b.v_first, s0, o0, st, whole ? &ctx->prof : nullptr, head_done ? ctx->d_logits : nullptr, (int) (lb - m.layer_begin), (int) (le - m.layer_begin), tok, ntok);
             return head_done;
         }
         for (uint32_t i = lb; i < le; i++) {
@@ -721,8 +680,8 @@ struct Runner {
 // Where a single-token step that produces logits has ALSO left their argmax (persist_v47.hip folds it into the launch), or nullptr: the
 // greedy loops then need no argmax launch -- and no copy when that is where their next step reads the token.
 uint32_t * folded_argmax_target(const rwkv_context * ctx) {
-    if (!ctx->mega || !ctx->model->has_head || !mega_v6_folds_argmax(ctx->mega)) return nullptr;
-    return (ctx->model->has_embed && mega_v6_folds_embed(ctx->mega)) ? ctx->d_tokens : ctx->d_next_token;
+    if (!ctx->mega || !ctx->model->has_head || !ctx->mega->folds_argmax()) return nullptr;
+    return (ctx->model->has_embed && ctx->mega->folds_embed()) ? ctx->d_tokens : ctx->d_next_token;
 }
 
 int64_t handoff_len(const Model & m) { return m.arch_major == 7 ? 2 * m.n_embed() : m.n_embed(); }
@@ -867,7 +826,7 @@ bool forward_streamed_eligible(const rwkv_context * ctx) {
     if ((e && e[0] == '0') || !ctx->stages.empty() || !ctx->owns_stream) return false;
     const Model & m = *ctx->model;
     if (m.layer_end - m.layer_begin < 2 || !m.has_embed || !m.has_head) return false;
-    if (ctx->mega && !mega_v6_has_range(ctx->mega)) return false;     // (the register-prefetch kernel has no layer-range launch)
+    if (ctx->mega && !ctx->mega->has_range()) return false;     // (the register-prefetch kernel has no layer-range launch)
     if (e && e[0] == '1') return true;
     return (size_t) m.state_len() * sizeof(float) >= ((size_t) 4 << 20);   // small states: the serial copies are already cheap
 }
@@ -971,7 +930,7 @@ bool forward_streamed(rwkv_context * ctx, bool want_logits, const float * h_in, 
     if (chained) mega_chain_end(ctx);
     if (ok && want_logits && !head_done) r.run_head();
     if (ok && h_logits) ok = hipMemcpyAsync(h_logits, ctx->d_logits, (size_t) m.n_vocab() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
-    const bool ctl_ok = !ctx->mega || mega_v6_ctl_fetch(ctx->mega, ctx->stream);
+    const bool ctl_ok = !ctx->mega || ctx->mega->ctl.fetch(ctx->stream);
     const bool sync_ok = hipStreamSynchronize(ctx->stream) == hipSuccess;
     {   // the download thread must be done with this call whatever happened above (it holds the caller's pointer)
         std::unique_lock<std::mutex> lk(a->mu);
@@ -983,21 +942,21 @@ bool forward_streamed(rwkv_context * ctx, bool want_logits, const float * h_in, 
     ctx->cur ^= 1;
     RW_CTX_CHECK(ctx, RWKV_ERROR_GRAPH, false, ok && sync_ok, "HIP error in the streamed rwkv_eval: %s", hipGetErrorString(hipGetLastError()));
     RW_CTX_CHECK(ctx, RWKV_ERROR_GRAPH | RWKV_ERROR_ALLOC, false, !r.failed, "a product could not be launched");
-    if (ctx->mega && (!ctl_ok || mega_v6_aborted_cached(ctx->mega))) { recover_from_abort(ctx); *aborted = true; }
+    if (ctx->mega && (!ctl_ok || ctx->mega->ctl.aborted_cached())) { recover_from_abort(ctx); *aborted = true; }
     return true;
 }
 
 // A single-token step that is ONE persistent launch issued directly (no graph): no embedding launch in front of it (none to do, or folded)
 // and no head launches behind it (none wanted, or folded). A whole model additionally folds the argmax (the greedy loops' condition since
 // round 5); a pipeline stage qualifies since round 6 -- a chain of N stages paid N replays of a one-node graph per token
-// (RWKV_MI_STAGE_GRAPH=1 restores that for A/B). runner.cpp relies on this: only a direct launch sees a changed mega_v6_set_x_out.
+// (RWKV_MI_STAGE_GRAPH=1 restores that for A/B). runner.cpp relies on this: only a direct launch sees a changed set_x_out.
 bool single_launch_step(const rwkv_context * ctx, bool want_logits) {
     if (!ctx->mega) return false;
     const Model & mm = *ctx->model;
     static const bool replay = getenv("RWKV_MI_STAGE_GRAPH") != nullptr;
-    const bool one_launch = (!mm.has_embed || mega_v6_folds_embed(ctx->mega)) && (!(want_logits && mm.has_head) || mega_v6_folds_head(ctx->mega));
+    const bool one_launch = (!mm.has_embed || ctx->mega->folds_embed()) && (!(want_logits && mm.has_head) || ctx->mega->folds_head());
     if (!one_launch) return false;
-    return (mm.has_embed && mm.has_head) ? mega_v6_folds_argmax(ctx->mega) : !replay;
+    return (mm.has_embed && mm.has_head) ? ctx->mega->folds_argmax() : !replay;
 }
 
 // Single-token step through a captured hipGraph: one graph per (state parity, logits on/off), replayed per token so

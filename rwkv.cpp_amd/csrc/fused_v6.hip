@@ -461,24 +461,6 @@ size_t fused_v6_scratch_bytes(const Model & m) {
     return 9 * up(D * 4) + up(2048 * 4) + up(256 * 4) + 5 * up(qvec_bytes(D)) + up(qvec_bytes(D)) + up(qvec_bytes(F)) + 4096;
 }
 
-// Launch, optionally bracketed by the kernel's own start/stop timestamps (hipExtLaunchKernelGGL events: the dispatch's
-// begin/end as the profiler sees them, no host-side event overhead inside the interval).
-template <typename Kern, typename Param>
-static void launch6(rwkv_context::Prof * pf, uint64_t bytes, Kern kernel, dim3 grid, dim3 block, size_t shmem, hipStream_t st, const Param & prm) {
-    if (pf && pf->on && bytes) {
-        if (pf->used * 2 + 2 > pf->events.size()) {
-            hipEvent_t a = nullptr, c = nullptr;
-            (void) hipEventCreate(&a); (void) hipEventCreate(&c);
-            pf->events.push_back(a); pf->events.push_back(c); pf->bytes.push_back(0);
-        }
-        pf->bytes[pf->used] = bytes;
-        hipExtLaunchKernelGGL(kernel, grid, block, (uint32_t) shmem, st, pf->events[pf->used * 2], pf->events[pf->used * 2 + 1], 0, prm);
-        pf->used++;
-    } else {
-        hipLaunchKernelGGL(kernel, grid, block, shmem, st, prm);
-    }
-}
-
 template <int FMT>
 static void fused_v6_layer_t(const Model & m, const LayerW & L, float * x, const float * sin, float * sout, void * scratch, hipStream_t st, rwkv_context::Prof * pf) {
     const int64_t D = m.n_embed(), F = L.ffn_key->ne[1], H = m.head_count;
@@ -499,34 +481,34 @@ static void fused_v6_layer_t(const Model & m, const LayerW & L, float * x, const
 
     const int gridA = (int) ((R5 + 3) / 4);
     P6A a{x, f(L.ln1_w), f(L.ln1_b), sin + D, f(L.att_time_maa_x), sout + D, s.xn, s.sx, planes(L.att_time_maa_w1), R5, s.tl, D};
-    launch6(pf, 0, k6_att_prep<FMT>, dim3((unsigned) gridA), dim3(1024), (size_t) D * 4 + qbD + 512 * 8, st, a);
+    launch_profiled(pf, 0, k6_att_prep<FMT>, dim3((unsigned) gridA), dim3(1024), (size_t) D * 4 + qbD + 512 * 8, st, a);
 
     P6B b{f(L.att_time_maa_w2), s.tl, {f(L.att_time_maa_w), f(L.att_time_maa_k), f(L.att_time_maa_v), f(L.att_time_maa_r), f(L.att_time_maa_g)},
           s.sx, s.xn, s.act5, D, R, s.act_stride};
-    launch6(pf, 0, k6_mix2, dim3((unsigned) (5 * D / 256)), dim3(256), 0, st, b);
+    launch_profiled(pf, 0, k6_mix2, dim3((unsigned) (5 * D / 256)), dim3(256), 0, st, b);
 
     P6C c{{planes(L.att_receptance), planes(L.att_key), planes(L.att_value), planes(L.att_gate), planes(L.att_time_decay_w1)},
           s.act5, s.act_stride, {s.r, s.k, s.v, s.g, s.dl}, D, DR};
     const uint64_t actD = qvec_bytes(D);
-    launch6(pf, L.att_receptance->nbytes + L.att_key->nbytes + L.att_value->nbytes + L.att_gate->nbytes + L.att_time_decay_w1->nbytes + 5 * actD + (4 * D + DR) * 4,
+    launch_profiled(pf, L.att_receptance->nbytes + L.att_key->nbytes + L.att_value->nbytes + L.att_gate->nbytes + L.att_time_decay_w1->nbytes + 5 * actD + (4 * D + DR) * 4,
             k6_rkvgw<FMT>, dim3((unsigned) (4 * (D / 32) + (DR + 31) / 32)), dim3(256), qbD, st, c);
 
     P6D d{s.dl, planes(L.att_time_decay_w2), f(L.att_time_decay), f(L.att_time_faaaa), s.r, s.k, s.v, s.g, sin + 2 * D, sout + 2 * D,
           f(L.att_ln_x_w), f(L.att_ln_x_b), s.yq, D, DR};
-    if (DR == 128) launch6(pf, 0, k6_wkv<FMT, 4>, dim3((unsigned) H), dim3(64), 0, st, d);
-    else launch6(pf, 0, k6_wkv<FMT, 2>, dim3((unsigned) H), dim3(64), 0, st, d);
+    if (DR == 128) launch_profiled(pf, 0, k6_wkv<FMT, 4>, dim3((unsigned) H), dim3(64), 0, st, d);
+    else launch_profiled(pf, 0, k6_wkv<FMT, 2>, dim3((unsigned) H), dim3(64), 0, st, d);
 
     P6E e{planes(L.att_output), s.yq, x, nullptr, D, D};
-    launch6(pf, L.att_output->nbytes + actD + D * 8, k6_proj_res<FMT, 4, 2, false>, dim3((unsigned) ((D + 15) / 16)), dim3(256), qbD, st, e);
+    launch_profiled(pf, L.att_output->nbytes + actD + D * 8, k6_proj_res<FMT, 4, 2, false>, dim3((unsigned) ((D + 15) / 16)), dim3(256), qbD, st, e);
 
     const int64_t groups = F / 32 + D / 32;
     const int gpb = (int) ((groups + 255) / 256) < 3 ? (int) ((groups + 255) / 256) : 3;   // ~one workgroup per CU: the prologue runs once per CU
     P6F ff{x, f(L.ln2_w), f(L.ln2_b), sin, f(L.ffn_time_maa_k), f(L.ffn_time_maa_r), sout, planes(L.ffn_key), planes(L.ffn_receptance), s.kq, s.rr, D, F, gpb, 1, D};
-    launch6(pf, L.ffn_key->nbytes + L.ffn_receptance->nbytes + D * 12 + qvec_bytes(F) + D * 4, k6_ffn_kr<FMT>, dim3((unsigned) ((groups + gpb - 1) / gpb)), dim3(512),
+    launch_profiled(pf, L.ffn_key->nbytes + L.ffn_receptance->nbytes + D * 12 + qvec_bytes(F) + D * 4, k6_ffn_kr<FMT>, dim3((unsigned) ((groups + gpb - 1) / gpb)), dim3(512),
             (size_t) D * 4 + 2 * qbD + 512 * 8 + (size_t) gpb * 32 * 4, st, ff);
 
     P6E g{planes(L.ffn_value), s.kq, x, s.rr, D, F};
-    launch6(pf, L.ffn_value->nbytes + qvec_bytes(F) + D * 12, k6_proj_res<FMT, 4, 4, true>, dim3((unsigned) ((D + 15) / 16)), dim3(256), ((qvec_bytes(F) + 15) / 16) * 16, st, g);
+    launch_profiled(pf, L.ffn_value->nbytes + qvec_bytes(F) + D * 12, k6_proj_res<FMT, 4, 4, true>, dim3((unsigned) ((D + 15) / 16)), dim3(256), ((qvec_bytes(F) + 15) / 16) * 16, st, g);
 }
 
 // ---- the projection / channel-mixing launches shared with the other architectures' fused layers (fused_v7.hip, fused_v4.hip) ----
@@ -537,10 +519,10 @@ static void fused_proj_res_t(const DevTensor * W, const void * act, float * x, c
     const size_t shm = ((qvec_bytes(K) + 15) / 16) * 16;
     // rows per wave: 4 unless that leaves CUs without a workgroup (N / 16 workgroups), then 2
     const bool small = (N + 15) / 16 < 224;
-    if (long_rows && small) launch6(pf, bytes, k6_proj_res<FMT, 2, 4, true>, dim3((unsigned) ((N + 7) / 8)), dim3(256), shm, st, e);
-    else if (long_rows) launch6(pf, bytes, k6_proj_res<FMT, 4, 4, true>, dim3((unsigned) ((N + 15) / 16)), dim3(256), shm, st, e);
-    else if (small) launch6(pf, bytes, k6_proj_res<FMT, 2, 2, false>, dim3((unsigned) ((N + 7) / 8)), dim3(256), shm, st, e);
-    else launch6(pf, bytes, k6_proj_res<FMT, 4, 2, false>, dim3((unsigned) ((N + 15) / 16)), dim3(256), shm, st, e);
+    if (long_rows && small) launch_profiled(pf, bytes, k6_proj_res<FMT, 2, 4, true>, dim3((unsigned) ((N + 7) / 8)), dim3(256), shm, st, e);
+    else if (long_rows) launch_profiled(pf, bytes, k6_proj_res<FMT, 4, 4, true>, dim3((unsigned) ((N + 15) / 16)), dim3(256), shm, st, e);
+    else if (small) launch_profiled(pf, bytes, k6_proj_res<FMT, 2, 2, false>, dim3((unsigned) ((N + 7) / 8)), dim3(256), shm, st, e);
+    else launch_profiled(pf, bytes, k6_proj_res<FMT, 4, 2, false>, dim3((unsigned) ((N + 15) / 16)), dim3(256), shm, st, e);
 }
 void fused_proj_res(int fmt, const DevTensor * W, const void * act, float * x, const float * rgate, int64_t N, int64_t K, bool long_rows, hipStream_t st, rwkv_context::Prof * pf) {
     switch (fmt) {
@@ -560,7 +542,7 @@ static void fused_ffn_kr_t(const float * x, const float * ln_w, const float * ln
     const int gpb = (int) ((groups + 255) / 256) < 3 ? (int) ((groups + 255) / 256) : 3;   // (one group per workgroup with two workgroups per CU measured slower)
     const size_t qbD = ((qvec_bytes(D) + 15) / 16) * 16;
     P6F ff{x, ln_w, ln_b, xx_in, maa_k, maa_r, xx_out, planes(wk), wr ? planes(wr) : planes(wk), k_out, r_out, D, F, gpb, mix_mode, r_rows};
-    launch6(pf, wk->nbytes + (wr ? wr->nbytes : 0) + D * 12 + qvec_bytes(F) + r_rows * 4, k6_ffn_kr<FMT>, dim3((unsigned) ((groups + gpb - 1) / gpb)), dim3(512),
+    launch_profiled(pf, wk->nbytes + (wr ? wr->nbytes : 0) + D * 12 + qvec_bytes(F) + r_rows * 4, k6_ffn_kr<FMT>, dim3((unsigned) ((groups + gpb - 1) / gpb)), dim3(512),
             (size_t) D * 4 + 2 * qbD + 512 * 8 + (size_t) gpb * 32 * 4, st, ff);
 }
 void fused_ffn_kr(int fmt, const float * x, const float * ln_w, const float * ln_b, const float * xx_in, float * xx_out, const float * maa_k, const float * maa_r, int mix_mode,

@@ -444,22 +444,6 @@ size_t fused_v7_scratch_bytes(const Model & m) {
     return 4 * up(D * 4) + 4 * up(512 * 4) + up(qvec_bytes(D)) + up(qvec_bytes(F)) + 4096;
 }
 
-template <typename Kern, typename Param>
-static void launch7(rwkv_context::Prof * pf, uint64_t bytes, Kern kernel, dim3 grid, dim3 block, size_t shmem, hipStream_t st, const Param & prm) {
-    if (pf && pf->on && bytes) {
-        if (pf->used * 2 + 2 > pf->events.size()) {
-            hipEvent_t a = nullptr, c = nullptr;
-            (void) hipEventCreate(&a); (void) hipEventCreate(&c);
-            pf->events.push_back(a); pf->events.push_back(c); pf->bytes.push_back(0);
-        }
-        pf->bytes[pf->used] = bytes;
-        hipExtLaunchKernelGGL(kernel, grid, block, (uint32_t) shmem, st, pf->events[pf->used * 2], pf->events[pf->used * 2 + 1], 0, prm);
-        pf->used++;
-    } else {
-        hipLaunchKernelGGL(kernel, grid, block, shmem, st, prm);
-    }
-}
-
 // the shared projection / channel-mixing kernels live in fused_v6.hip
 void fused_proj_res(int fmt, const DevTensor * W, const void * act, float * x, const float * rgate, int64_t N, int64_t K, bool long_rows, hipStream_t st, rwkv_context::Prof * pf);
 void fused_ffn_kr(int fmt, const float * x, const float * ln_w, const float * ln_b, const float * xx_in, float * xx_out, const float * maa_k, const float * maa_r, int mix_mode,
@@ -498,7 +482,7 @@ static void fused_v7_layer_t(const Model & m, const LayerW & L, int layer, float
     }
     a.out_q[0] = r; a.out_q[1] = k; a.out_q[2] = v; a.D = D;
     a.lr_groups = (int) lr_groups;
-    launch7(pf, L.att_receptance->nbytes + L.att_key->nbytes + L.att_value->nbytes + lr_bytes + 7 * D * 4, k7_att_in<FMT, LRF16>,
+    launch_profiled(pf, L.att_receptance->nbytes + L.att_key->nbytes + L.att_value->nbytes + lr_bytes + 7 * D * 4, k7_att_in<FMT, LRF16>,
             dim3((unsigned) (3 * (D / 32) + lr_groups)), dim3(256), (size_t) D * 4 + qbD + 512 * 8, st, a);
 
     P7B b{};
@@ -508,7 +492,7 @@ static void fused_v7_layer_t(const Model & m, const LayerW & L, int layer, float
     b.lnx_w = f(L.att_ln_x_w); b.lnx_b = f(L.att_ln_x_b);
     b.v_first = v_first; b.layer0 = layer == 0 ? 1 : 0;
     b.state_in = sin + 2 * D; b.state_out = sout + 2 * D; b.y_out = yq; b.D = D;
-    launch7(pf, 0, k7_head<LRF16>, dim3((unsigned) H), dim3(512), 0, st, b);
+    launch_profiled(pf, 0, k7_head<LRF16>, dim3((unsigned) H), dim3(512), 0, st, b);
 
     fused_proj_res(FMT, L.att_output, yq, x, nullptr, D, D, false, st, pf);
     fused_ffn_kr(FMT, x, f(L.ln2_w), f(L.ln2_b), sin, sout, f(L.ffn_x_k), f(L.ffn_x_k), 1, L.ffn_key, nullptr, kq, nullptr, D, F, st, pf);
@@ -620,12 +604,12 @@ static void fused_v4_layer_t(const Model & m, const LayerW & L, float * x, const
     a.coef_q[0] = f(L.att_time_mix_r); a.coef_q[1] = f(L.att_time_mix_k); a.coef_q[2] = f(L.att_time_mix_v);
     a.mix_mode = 0; a.epi_q[0] = 1; a.epi_q[1] = a.epi_q[2] = 0;
     a.out_q[0] = r; a.out_q[1] = k; a.out_q[2] = v; a.D = D; a.lr_groups = 0;
-    launch7(pf, L.att_receptance->nbytes + L.att_key->nbytes + L.att_value->nbytes + 7 * D * 4, k7_att_in<FMT, true>,
+    launch_profiled(pf, L.att_receptance->nbytes + L.att_key->nbytes + L.att_value->nbytes + 7 * D * 4, k7_att_in<FMT, true>,
             dim3((unsigned) (3 * (D / 32))), dim3(256), (size_t) D * 4 + qbD + 512 * 8, st, a);
 
     P4C c{k, v, r, f(L.att_time_first), f(L.att_time_decay), sin + 2 * D, sin + 3 * D, sin + 4 * D, sout + 2 * D, sout + 3 * D, sout + 4 * D,
           planes(L.att_output), x, D};
-    launch7(pf, L.att_output->nbytes + 12 * D * 4, k4_wkv_out<FMT>, dim3((unsigned) ((D + 15) / 16)), dim3(256), qbD, st, c);
+    launch_profiled(pf, L.att_output->nbytes + 12 * D * 4, k4_wkv_out<FMT>, dim3((unsigned) ((D + 15) / 16)), dim3(256), qbD, st, c);
 
     fused_ffn_kr(FMT, x, f(L.ln2_w), f(L.ln2_b), sin, sout, f(L.ffn_time_mix_k), f(L.ffn_time_mix_r), 0, L.ffn_key, L.ffn_receptance, kq, rr, D, F, st, pf);
     fused_proj_res(FMT, L.ffn_value, kq, x, rr, D, F, true, st, pf);

@@ -22,7 +22,6 @@
 // every workgroup drains without waiting, and the host reports the step as failed (it never hangs the device).
 #include "persist.h"
 
-#include <cstring>
 
 namespace rwkvmi {
 
@@ -765,18 +764,28 @@ __global__ void k_block_w2(const float * __restrict__ src, float * __restrict__ 
     }
 }
 
-struct MegaV6 {
-    int kind = 1;                 // 1: this file's kernel, 2: ring_v6.hip's (its handle starts with the same member)
+struct MegaV6 : PersistentDecoder {
     float * w2b = nullptr;
     M6Layer * d_layers = nullptr;
     void * xch = nullptr;
-    unsigned * ctl = nullptr;
-    unsigned * h_ctl = nullptr;   // pinned host mirror of ctl[0..1], refreshed by mega_v6_ctl_fetch on the caller's stream
     M6P proto{};
-    long long * trace = nullptr;
     int variant = -1, n_blocks = 0;
     size_t lds = 0;
-    uint64_t bytes = 0;   // algorithmic bytes of one launch: every layer tensor once + the recurrent state read and written
+    uint64_t algo_bytes = 0;   // algorithmic bytes of one launch: every layer tensor once + the recurrent state read and written
+
+    ~MegaV6() override;
+    DecodePath kind() const override { return DecodePath::Regs; }
+    uint64_t bytes() const override { return algo_bytes; }
+    bool has_range() const override { return false; }   // one launch always covers every layer of the stage; nothing is folded into it
+    bool folds_embed() const override { return false; }
+    bool folds_head() const override { return false; }
+    bool folds_argmax() const override { return false; }
+    bool set_history(uint32_t *, size_t, hipStream_t) override { return false; }
+    bool set_x_out(float * to) override { return to == nullptr; }
+    void forward_range(float * x, float * v_first, const float * sin, float * sout, hipStream_t st, DecodeProf * pf, float * logits, int l0, int l1,
+                       const uint32_t * tok, uint32_t * next_tok) override;
+    // cycle stamps of one layer (16 per wave); out must hold n_blocks * 8 * 32 values
+    bool trace(int layer, long long * out, bool fetch) override { return trace_into(proto.trace, proto.trace_layer, layer, (size_t) n_blocks * 8 * 32, 0, out, fetch); }
 };
 
 typedef void (*MegaKernel)(M6P);
@@ -811,34 +820,14 @@ static int mega_variant(const Model & m, int n_cu) {
     return -1;
 }
 
-static bool is_ring(void * h) { return h && *(const int *) h == 2; }
-static bool is_p47(void * h) { return h && *(const int *) h == 3; }
-
-void mega_v6_destroy(void * h) {
-    if (is_ring(h)) { ring_v6_destroy(h); return; }
-    if (is_p47(h)) { p47_destroy(h); return; }
-    MegaV6 * mg = (MegaV6 *) h;
-    if (!mg) return;
-    if (mg->d_layers) (void) hipFree(mg->d_layers);
-    if (mg->w2b) (void) hipFree(mg->w2b);
-    if (mg->xch) (void) hipFree(mg->xch);
-    if (mg->ctl) (void) hipFree(mg->ctl);
-    if (mg->h_ctl) (void) hipHostFree(mg->h_ctl);
-    if (mg->trace) (void) hipFree(mg->trace);
-    delete mg;
+MegaV6::~MegaV6() {
+    if (d_layers) (void) hipFree(d_layers);
+    if (w2b) (void) hipFree(w2b);
+    if (xch) (void) hipFree(xch);
 }
 
 // Returns nullptr when the model / device does not qualify (the caller keeps the seven-launch path).
-// RWKV_MI_PERSIST = ring | regs picks one of the two persistent kernels; by default the LDS-DMA ring kernel (ring_v6.hip) is tried first.
-void * mega_v6_create(const Model & m) {
-    const char * pk = getenv("RWKV_MI_PERSIST");
-    const bool want_ring = !(pk && strcmp(pk, "regs") == 0), want_regs = !(pk && strcmp(pk, "ring") == 0);
-    if (want_ring) { void * r = ring_v6_create(m); if (r || !want_regs) return r; }
-    return mega_v6_create_kind(m, 1);
-}
-
-void * mega_v6_create_kind(const Model & m, int kind) {
-    if (kind == 2) return ring_v6_create(m);
+PersistentDecoder * mega_v6_create(const Model & m) {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, m.device) != hipSuccess) return nullptr;
     const int NB = prop.multiProcessorCount;
@@ -887,7 +876,7 @@ void * mega_v6_create_kind(const Model & m, int kind) {
         for (const DevTensor * t : all) if (t) bytes += t->nbytes;
         bytes += 2 * (uint64_t) m.state_per_layer() * sizeof(float);
     }
-    mg->bytes = bytes;
+    mg->algo_bytes = bytes;
     if (!in_arena) { delete mg; return nullptr; }
     const int64_t nbD = D / 32, nbF = F / 32;
     const int64_t PAD = 2048;   // polls read whole 64-lane rounds: keep every buffer readable past its end
@@ -899,145 +888,29 @@ void * mega_v6_create_kind(const Model & m, int kind) {
     bool ok = hipMalloc((void **) &mg->d_layers, hl.size() * sizeof(M6Layer)) == hipSuccess
            && hipMemcpy(mg->d_layers, hl.data(), hl.size() * sizeof(M6Layer), hipMemcpyHostToDevice) == hipSuccess
            && hipMalloc(&mg->xch, (size_t) units * 16) == hipSuccess && hipMemset(mg->xch, 0, (size_t) units * 16) == hipSuccess
-           && hipMalloc((void **) &mg->ctl, 256) == hipSuccess
-           && hipHostMalloc((void **) &mg->h_ctl, 64, hipHostMallocDefault) == hipSuccess;
-    if (ok) { mg->h_ctl[0] = 8u; mg->h_ctl[1] = 0u; }
-    const unsigned init[2] = {8u, 0u};
-    ok = ok && hipMemcpy(mg->ctl, init, sizeof(init), hipMemcpyHostToDevice) == hipSuccess;
-    if (!ok) { mega_v6_destroy(mg); return nullptr; }
+           && mg->ctl.alloc(8u);
+    if (!ok) { delete mg; return nullptr; }
     M6P & q = mg->proto;
     q.layers = mg->d_layers; q.n_layers = (int) hl.size();
     q.arena = abase; q.w2b = mg->w2b;
-    if (hipDeviceSynchronize() != hipSuccess) { mega_v6_destroy(mg); return nullptr; }
+    if (hipDeviceSynchronize() != hipSuccess) { delete mg; return nullptr; }
     q.state_stride = m.state_per_layer();
     q.xch = mg->xch; q.xch_bytes = (unsigned) (units * 16);
     int u = 0;
     int * slots[9] = {&q.tl, &q.act5, &q.rkvg, &q.dl, &q.yq, &q.xatt, &q.kq, &q.rr, &q.xffn};
     for (int i = 0; i < 9; i++) { *slots[i] = u; u += (int) sizes[i]; }
     q.act_stride = act_stride;
-    q.ctl = mg->ctl;
+    q.ctl = mg->ctl.dev;
     q.F = (int) F; q.DR = (int) DR; q.R = (int) R; q.H = (int) m.head_count;
     q.gpb = (int) ((nbF + NB - 1) / NB);
     return mg;
 }
 
-// debug: cycle stamps of one layer (16 per wave) for the next launches; out must hold n_blocks * 8 * 32 values
-bool mega_v6_trace(void * h, int layer, long long * out, bool fetch) {
-    if (is_ring(h)) return ring_v6_trace(h, layer, out, fetch);
-    if (is_p47(h)) return p47_trace(h, layer, out, fetch);
-    MegaV6 * mg = (MegaV6 *) h;
-    const size_t n = (size_t) mg->n_blocks * 8 * 32;
-    if (!mg->trace) { if (hipMalloc((void **) &mg->trace, n * 8) != hipSuccess) return false; (void) hipMemset(mg->trace, 0, n * 8); }
-    mg->proto.trace = mg->trace; mg->proto.trace_layer = layer;
-    if (fetch) return hipMemcpy(out, mg->trace, n * 8, hipMemcpyDeviceToHost) == hipSuccess;
-    return true;
-}
-
-int mega_v6_kind(void * h) { return h ? *(const int *) h : 0; }
-uint64_t mega_v6_bytes(void * h) { if (is_ring(h)) return ring_v6_bytes(h); if (is_p47(h)) return p47_bytes(h); return ((MegaV6 *) h)->bytes; }
-
 // sin / sout: state of the stage's FIRST layer. One launch covers every layer of the stage.
-bool mega_v6_folds_head(void * h) { return (is_ring(h) && ring_v6_folds_head(h)) || (is_p47(h) && p47_folds_head(h)); }
-
-bool mega_v6_has_range(void * h) { return is_ring(h) || is_p47(h); }
-bool mega_v6_folds_embed(void * h) { return (is_p47(h) && p47_folds_embed(h)) || (is_ring(h) && ring_v6_folds_embed(h)); }
-bool mega_v6_folds_argmax(void * h) { return (is_p47(h) && p47_folds_head(h)) || (is_ring(h) && ring_v6_folds_argmax(h)); }
-bool mega_v6_set_history(void * h, uint32_t * hist, size_t n, hipStream_t st) {
-    if (is_p47(h)) return p47_set_history(h, hist, n, st);
-    return is_ring(h) && ring_v6_set_history(h, hist, n, st);
-}
-// Pipeline stages: the launch that runs the stage's last layer writes the residual stream to x_out (the NEXT stage's input buffer, on this
-// or on a peer device) instead of back into its own x; nullptr restores the in-place form. false: this kernel has no such output.
-bool mega_v6_set_x_out(void * h, float * x_out) {
-    if (is_ring(h)) { ring_v6_set_x_out(h, x_out); return true; }
-    if (is_p47(h)) { p47_set_x_out(h, x_out); return true; }
-    return x_out == nullptr;
-}
-void mega_v6_forward_range(void * h, float * x, const float * sin, float * sout, hipStream_t st, rwkv_context::Prof * pf, float * logits, int l0, int l1, float * v_first,
-                           const uint32_t * tok, uint32_t * next_tok) {
-    if (is_p47(h)) { p47_forward_range(h, x, v_first, sin, sout, st, pf, l0, l1, logits, tok, next_tok); return; }
-    ring_v6_forward_range(h, x, sin, sout, st, pf, logits, l0, l1, tok, next_tok);
-}
-
-void mega_v6_forward(void * h, float * x, const float * sin, float * sout, hipStream_t st, rwkv_context::Prof * pf, float * logits, float * v_first,
-                     const uint32_t * tok, uint32_t * next_tok) {
-    if (is_ring(h)) { ring_v6_forward(h, x, sin, sout, st, pf, logits, tok, next_tok); return; }
-    if (is_p47(h)) { p47_forward_range(h, x, v_first, sin, sout, st, pf, 0, p47_layers(h), logits, tok, next_tok); return; }
-    MegaV6 * mg = (MegaV6 *) h;
-    M6P q = mg->proto;
+void MegaV6::forward_range(float * x, float *, const float * sin, float * sout, hipStream_t st, DecodeProf * pf, float *, int, int, const uint32_t *, uint32_t *) {
+    M6P q = proto;
     q.x = x; q.sin = sin; q.sout = sout;
-    const MegaKernel fn = g_variants[mg->variant].fn;
-    if (pf && pf->on) {
-        if (pf->used * 2 + 2 > pf->events.size()) {
-            hipEvent_t a = nullptr, c = nullptr;
-            (void) hipEventCreate(&a); (void) hipEventCreate(&c);
-            pf->events.push_back(a); pf->events.push_back(c); pf->bytes.push_back(0);
-        }
-        pf->bytes[pf->used] = mg->bytes;
-        hipExtLaunchKernelGGL(fn, dim3((unsigned) mg->n_blocks), dim3(512), (uint32_t) mg->lds, st, pf->events[pf->used * 2], pf->events[pf->used * 2 + 1], 0, q);
-        pf->used++;
-    } else {
-        hipLaunchKernelGGL(fn, dim3((unsigned) mg->n_blocks), dim3(512), mg->lds, st, q);
-    }
-}
-
-// The abort word (a poll timed out: co-residency lost or a bug; results since then are not valid) is read through a pinned
-// host mirror: an asynchronous copy on the caller's stream, checked after the caller's own stream synchronisation. (A
-// blocking hipMemcpy would go through the legacy null stream and couple every blocking stream of the process.)
-bool mega_v6_ctl_fetch(void * h, hipStream_t st) {
-    if (is_ring(h)) return ring_v6_ctl_fetch(h, st);
-    if (is_p47(h)) return p47_ctl_fetch(h, st);
-    MegaV6 * mg = (MegaV6 *) h;
-    return hipMemcpyAsync(mg->h_ctl, mg->ctl, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, st) == hipSuccess;
-}
-bool mega_v6_aborted_cached(void * h) { if (is_ring(h)) return ring_v6_aborted_cached(h); if (is_p47(h)) return p47_aborted_cached(h); return ((MegaV6 *) h)->h_ctl[1] != 0; }
-bool mega_v6_aborted(void * h, hipStream_t st) {
-    if (!mega_v6_ctl_fetch(h, st) || hipStreamSynchronize(st) != hipSuccess) return true;
-    return mega_v6_aborted_cached(h);
-}
-// clears the abort word (after the caller has drained the stream), so that the handle -- or the context that drops it -- is usable again
-bool mega_v6_clear_abort(void * h, hipStream_t st) {
-    if (is_ring(h)) return ring_v6_clear_abort(h, st);
-    if (is_p47(h)) return p47_clear_abort(h, st);
-    MegaV6 * mg = (MegaV6 *) h;
-    mg->h_ctl[1] = 0u;
-    return hipMemsetAsync(mg->ctl + 1, 0, sizeof(unsigned), st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
-}
-unsigned * mega_v6_ctl(void * h) { return is_ring(h) ? ring_v6_ctl(h) : (is_p47(h) ? p47_ctl(h) : ((MegaV6 *) h)->ctl); }
-// Test hook: the abort word set from the host, as a poll that timed out would set it -- the next launch drains at once, the host finds the
-// word behind it and the context falls back to the per-layer launches (engine.hip, recover_from_abort).
-bool mega_v6_force_abort(void * h, hipStream_t st) {
-    if (!h || hipStreamSynchronize(st) != hipSuccess) return false;
-    const unsigned one = 1u;
-    return hipMemcpy(mega_v6_ctl(h) + 1, &one, sizeof(one), hipMemcpyHostToDevice) == hipSuccess;
-}
-// Why no persistent kernel serves this model on this device (nullptr: one does). The kernels give every CU one workgroup and hand vectors
-// over between them inside the launch: they need all 256 CUs of an unpartitioned MI355X (a CPX / DPX partition or another part reports
-// fewer), quantised matrices of one format, 64-wide heads and a geometry that has an instantiation.
-const char * persist_unavailable_reason(const Model & m) {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, m.device) != hipSuccess) return "the device properties could not be read";
-    static thread_local char buf[160];
-    if (prop.multiProcessorCount != 256) { snprintf(buf, sizeof buf, "the device reports %d CUs: the persistent kernels need all 256 of an unpartitioned MI355X (SPX mode)", prop.multiProcessorCount); return buf; }
-    if (m.head_size != 64) return "head size is not 64";
-    if (m.arch_major == 5) return "RWKV-5 has no persistent kernel (per-op launches)";
-    const int t = (int) m.header.data_type;
-    if (t == T_F32 || t == T_F16) return "FP32 / FP16 files run the per-op launches (the persistent kernels stream quantised matrices)";
-    return "no instantiation for this geometry (n_embed / ffn size / ranks / vocabulary)";
-}
-// the tag generation the next launch starts from (ctl[0]), through the pinned mirror
-unsigned mega_v6_generation(void * h, hipStream_t st) {
-    if (!mega_v6_ctl_fetch(h, st) || hipStreamSynchronize(st) != hipSuccess) return 0;
-    if (is_p47(h)) return p47_generation_cached(h);
-    return is_ring(h) ? ring_v6_generation_cached(h) : ((MegaV6 *) h)->h_ctl[0];
-}
-// Test hook: presets the rolling tag generation (ctl[0]; the kernel compares its low 16 bits), e.g. just below a 16-bit wrap.
-bool mega_v6_set_tag(void * h, unsigned base, hipStream_t st) {
-    if (is_ring(h)) return ring_v6_set_tag(h, base, st);
-    if (is_p47(h)) return p47_set_tag(h, base, st);
-    MegaV6 * mg = (MegaV6 *) h;
-    if (hipStreamSynchronize(st) != hipSuccess) return false;
-    return hipMemcpy(mg->ctl, &base, sizeof(unsigned), hipMemcpyHostToDevice) == hipSuccess;
+    launch_profiled(pf, algo_bytes, g_variants[variant].fn, dim3((unsigned) n_blocks), dim3(512), lds, st, q);
 }
 
 }  // namespace rwkvmi

@@ -8,6 +8,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "persist_host.h"
 
 namespace rwkvmi {
 
@@ -37,11 +38,10 @@ struct Model {
     int arch_major = 4, arch_minor = 0;
     int64_t head_count = 0, head_size = 0, ffn_size = 0;
     int64_t max_lowrank = 0;  // widest intermediate of a low-rank pair (v6 5*r, decay rank; v7 ranks)
-    // Single-token path the first context of this model measured as fastest on its device (engine.hip, calibrate_decode_path):
-    // 0 not measured, 1 persistent kernel on register prefetch, 2 persistent kernel on the LDS-DMA ring, 3 seven launches per layer
-    // (RWKV-6; RWKV-4 / RWKV-7: 4 persistent kernel of persist_v47.hip, 3 the fused per-layer launches).
-    // Clones reuse it instead of timing every path again.
-    mutable std::atomic<int> decode_choice{0};
+    // Single-token path the first context of this model measured as fastest on its device (engine.hip, calibrate_decode_path): a
+    // persistent kernel (RWKV-6: Regs or Ring; RWKV-4 / RWKV-7: K47) or the fused per-layer launches. Clones reuse it instead of
+    // timing every path again.
+    mutable std::atomic<DecodePath> decode_choice{DecodePath::Unmeasured};
 
     // Device images a decode path derives from the weights alone (ring_v6.hip: the per-workgroup weight streams, the blocked W2, the
     // layer table): built by the first context that needs them, shared by every context of the model, freed with the last holder.
@@ -181,19 +181,11 @@ struct rwkv_context {
     bool  fused_v7 = false;   // fused RWKV-7 layer (fused_v7.hip)
     bool  fused_v4 = false;   // fused RWKV-4 / RWKV-5 layer (fused_v4.hip)
     void * fused_scratch = nullptr;
-    // persistent whole-stage decode kernel (mega_v6.hip) when the model and the device qualify; takes precedence
-    void * mega = nullptr;
+    // persistent whole-stage decode kernel (persist_host.h) when the model and the device qualify; takes precedence
+    std::unique_ptr<rwkvmi::PersistentDecoder> mega;
 
-    // Live per-launch timing of the dominant kernel (the quantised single-token projection) with HIP events on this
-    // context's stream; filled by rwkv_mi_profile_decode, used by bench.py's roofline figure.
-    struct Prof {
-        bool on = false;
-        std::vector<hipEvent_t> events;  // pairs
-        std::vector<uint64_t> bytes;     // per pair
-        size_t used = 0;
-        double total_ms = 0.0;
-        uint64_t launches = 0, total_bytes = 0;
-    } prof;
+    using Prof = rwkvmi::DecodeProf;
+    Prof prof;
 };
 
 namespace rwkvmi {
@@ -228,71 +220,11 @@ void   fused_v7_layer(const Model & m, const LayerW & L, int layer, float * x, f
 bool   fused_v4_supported(const Model & m);
 size_t fused_v4_scratch_bytes(const Model & m);
 void   fused_v4_layer(const Model & m, const LayerW & L, float * x, const float * sin, float * sout, void * scratch, hipStream_t st, rwkv_context::Prof * pf);
-// persistent single-launch RWKV-6 decode over all layers of the stage (mega_v6.hip)
-void *   mega_v6_create(const Model & m);   // nullptr: not applicable. RWKV_MI_PERSIST = ring | regs names the kernel (default: ring, else regs)
-void *   mega_v6_create_kind(const Model & m, int kind);   // 1: register prefetch, 2: LDS-DMA weight ring
-void     mega_v6_destroy(void * h);
-// logits != nullptr and mega_v6_folds_head(h): ln_out + the head projection run inside the launch (the caller skips its own)
-void     mega_v6_forward(void * h, float * x, const float * sin, float * sout, hipStream_t st, rwkv_context::Prof * pf, float * logits = nullptr, float * v_first = nullptr,
-                         const uint32_t * tok = nullptr, uint32_t * next_tok = nullptr);
-// a layer range [l0, l1) of the stage (ring_v6.hip and persist_v47.hip have one; indices into the stage's own layers)
-void     mega_v6_forward_range(void * h, float * x, const float * sin, float * sout, hipStream_t st, rwkv_context::Prof * pf, float * logits, int l0, int l1, float * v_first = nullptr,
-                               const uint32_t * tok = nullptr, uint32_t * next_tok = nullptr);
-bool     mega_v6_has_range(void * h);
-bool     mega_v6_folds_embed(void * h);      // the launch starts from the token id: the caller skips its embedding + ln0 launch
-bool     mega_v6_folds_argmax(void * h);     // a launch that produces logits also writes their argmax to next_tok
-bool     mega_v6_set_history(void * h, uint32_t * hist, size_t n, hipStream_t st);   // (folds_argmax) tokens appended on the device (at most n), no copy per token
-bool     mega_v6_folds_head(void * h);
-bool     mega_v6_set_x_out(void * h, float * x_out);        // the stage's last layer leaves x there (pipeline hops without a copy); nullptr: in place
-bool     mega_v6_ctl_fetch(void * h, hipStream_t st);       // async copy of the control words into the pinned mirror
-bool     mega_v6_aborted_cached(void * h);                  // the mirror's abort word (valid after the stream was synchronised)
-bool     mega_v6_aborted(void * h, hipStream_t st);         // fetch + synchronise + check
-bool     mega_v6_clear_abort(void * h, hipStream_t st);
-bool     mega_v6_force_abort(void * h, hipStream_t st);   // test hook: sets the abort word as a timed-out poll would
-unsigned * mega_v6_ctl(void * h);
-unsigned * p47_ctl(void * h);
-unsigned * ring_v6_ctl(void * h);
+// the persistent decode kernels (persist_host.h), one creator each. nullptr: the model / device does not qualify
+PersistentDecoder * mega_v6_create(const Model & m);   // RWKV-6, register prefetch (mega_v6.hip)
+PersistentDecoder * ring_v6_create(const Model & m);   // RWKV-6, LDS-DMA weight ring (ring_v6.hip)
+PersistentDecoder * p47_create(const Model & m);       // RWKV-4 / RWKV-7 (persist_v47.hip)
 const char * persist_unavailable_reason(const Model & m);   // nullptr: a persistent kernel exists for this model on this device
-bool     mega_v6_set_tag(void * h, unsigned base, hipStream_t st);
-unsigned mega_v6_generation(void * h, hipStream_t st);   // the hand-over generation the next launch starts from
-uint64_t mega_v6_bytes(void * h);
-bool     mega_v6_trace(void * h, int layer, long long * out, bool fetch);
-int      mega_v6_kind(void * h);            // 1: register prefetch (mega_v6.hip), 2: LDS-DMA weight ring (ring_v6.hip), 3: RWKV-4 / RWKV-7 (persist_v47.hip)
-// persistent single-launch RWKV-4 / RWKV-7 decode (persist_v47.hip); reached through the mega_v6_* entry points
-void *   p47_create(const Model & m);
-void     p47_destroy(void * h);
-void     p47_forward_range(void * h, float * x, float * v_first, const float * sin, float * sout, hipStream_t st, rwkv_context::Prof * pf, int l0, int l1,
-                           float * logits = nullptr, const uint32_t * tok = nullptr, uint32_t * next_tok = nullptr);
-bool     p47_folds_embed(void * h);
-bool     p47_folds_head(void * h);
-bool     p47_set_history(void * h, uint32_t * hist, size_t n, hipStream_t st);
-void     p47_set_x_out(void * h, float * x_out);
-int      p47_layers(void * h);
-bool     p47_ctl_fetch(void * h, hipStream_t st);
-bool     p47_aborted_cached(void * h);
-unsigned p47_generation_cached(void * h);
-bool     p47_clear_abort(void * h, hipStream_t st);
-bool     p47_set_tag(void * h, unsigned base, hipStream_t st);
-uint64_t p47_bytes(void * h);
-bool     p47_trace(void * h, int layer, long long * out, bool fetch);
-// the same persistent launch on the LDS-DMA weight ring (ring_v6.hip); reached through the mega_v6_* entry points
-void *   ring_v6_create(const Model & m);
-void     ring_v6_destroy(void * h);
-void     ring_v6_forward(void * h, float * x, const float * sin, float * sout, hipStream_t st, rwkv_context::Prof * pf, float * logits, const uint32_t * tok = nullptr, uint32_t * next_tok = nullptr);
-void     ring_v6_forward_range(void * h, float * x, const float * sin, float * sout, hipStream_t st, rwkv_context::Prof * pf, float * logits, int l0, int l1,
-                               const uint32_t * tok = nullptr, uint32_t * next_tok = nullptr);
-bool     ring_v6_folds_head(void * h);
-bool     ring_v6_folds_embed(void * h);
-bool     ring_v6_folds_argmax(void * h);
-bool     ring_v6_set_history(void * h, uint32_t * hist, size_t n, hipStream_t st);
-void     ring_v6_set_x_out(void * h, float * x_out);
-bool     ring_v6_ctl_fetch(void * h, hipStream_t st);
-bool     ring_v6_aborted_cached(void * h);
-unsigned ring_v6_generation_cached(void * h);
-bool     ring_v6_clear_abort(void * h, hipStream_t st);
-bool     ring_v6_set_tag(void * h, unsigned base, hipStream_t st);
-uint64_t ring_v6_bytes(void * h);
-bool     ring_v6_trace(void * h, int layer, long long * out, bool fetch);
 // ---- layer pipeline in one process (pipeline.cpp) ----
 bool upload_tokens_for(rwkv_context * ctx, const uint32_t * tokens, size_t n);   // api.cpp: pinned staging + async copy into ctx->d_tokens
 rwkv_context * pipeline_create(const char * path, uint32_t n_threads, const char * devices);

@@ -1601,20 +1601,26 @@ __global__ __launch_bounds__(576) void k47_persist(P47 p) {
 #define P47_CALM_DEFAULT 1
 #endif
 
-struct P47Handle {
-    int kind = 3;                 // (mega_v6.hip dispatches on the first member: 1 register prefetch v6, 2 ring v6, 3 this file)
+struct P47Handle : PersistentDecoder {
     P47Layer * d_layers = nullptr;
     void * xch = nullptr;
-    unsigned * ctl = nullptr;
-    unsigned * h_ctl = nullptr;
     P47 proto{};
-    long long * trace = nullptr;
     int variant = -1, n_blocks = 0, n_layers = 0, n_cu = 0;
     size_t lds = 0;
     std::vector<uint64_t> layer_bytes;   // algorithmic bytes per layer: every tensor once + the recurrent state read and written
     bool fold_embed = false, fold_head = false;
     uint64_t embed_bytes = 0, head_bytes = 0;
-    float * x_out = nullptr;      // p47_set_x_out (pipeline stages, runner.cpp)
+
+    ~P47Handle() override;
+    DecodePath kind() const override { return DecodePath::K47; }
+    uint64_t bytes() const override { uint64_t s = embed_bytes + head_bytes; for (uint64_t b : layer_bytes) s += b; return s; }
+    bool folds_embed() const override { return fold_embed; }
+    bool folds_head() const override { return fold_head; }
+    bool folds_argmax() const override { return fold_head; }
+    void forward_range(float * x, float * v_first, const float * sin, float * sout, hipStream_t st, DecodeProf * pf, float * logits, int l0, int l1,
+                       const uint32_t * tok, uint32_t * next_tok) override;
+    // real-time-counter stamps of one layer (16 per wave, 9 waves per workgroup); out holds 256 * 9 * 16 values
+    bool trace(int layer, long long * out, bool fetch) override { return trace_into(proto.trace, proto.trace_layer, layer, (size_t) 256 * 9 * 16, 0, out, fetch); }
 };
 
 typedef void (*P47Kernel)(P47);
@@ -1666,19 +1672,13 @@ static int p47_variant(const Model & m, int n_cu) {
     return -1;
 }
 
-void p47_destroy(void * h) {
-    P47Handle * g = (P47Handle *) h;
-    if (!g) return;
-    if (g->d_layers) (void) hipFree(g->d_layers);
-    if (g->xch) (void) hipFree(g->xch);
-    if (g->ctl) (void) hipFree(g->ctl);
-    if (g->h_ctl) (void) hipHostFree(g->h_ctl);
-    if (g->trace) (void) hipFree(g->trace);
-    delete g;
+P47Handle::~P47Handle() {
+    if (d_layers) (void) hipFree(d_layers);
+    if (xch) (void) hipFree(xch);
 }
 
 // Returns nullptr when the model / device does not qualify (the caller keeps the fused per-layer launches).
-void * p47_create(const Model & m) {
+PersistentDecoder * p47_create(const Model & m) {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, m.device) != hipSuccess) return nullptr;
     const int v = p47_variant(m, prop.multiProcessorCount);
@@ -1751,12 +1751,8 @@ void * p47_create(const Model & m) {
     bool ok = hipMalloc((void **) &g->d_layers, hl.size() * sizeof(P47Layer)) == hipSuccess
            && hipMemcpy(g->d_layers, hl.data(), hl.size() * sizeof(P47Layer), hipMemcpyHostToDevice) == hipSuccess
            && hipMalloc(&g->xch, (size_t) units * 16) == hipSuccess && hipMemset(g->xch, 0, (size_t) units * 16) == hipSuccess
-           && hipMalloc((void **) &g->ctl, 256) == hipSuccess && hipMemset(g->ctl, 0, 256) == hipSuccess   // (ctl[2..5]: the greedy history words)
-           && hipHostMalloc((void **) &g->h_ctl, 64, hipHostMallocDefault) == hipSuccess;
-    if (ok) { g->h_ctl[0] = 16u; g->h_ctl[1] = 0u; }
-    const unsigned init[2] = {16u, 0u};
-    ok = ok && hipMemcpy(g->ctl, init, sizeof(init), hipMemcpyHostToDevice) == hipSuccess;
-    if (!ok) { p47_destroy(g); return nullptr; }
+           && g->ctl.alloc(16u);
+    if (!ok) { delete g; return nullptr; }
     P47 & q = g->proto;
     q.layers = g->d_layers; q.l0 = 0; q.l1 = g->n_layers;
     q.arena = abase;
@@ -1765,7 +1761,7 @@ void * p47_create(const Model & m) {
     int u = 0;
     int * slots[7] = {&q.u_a, &q.u_lr1, &q.u_y, &q.u_xatt, &q.u_kq, &q.u_xffn, &q.u_am};
     for (int i = 0; i < 7; i++) { *slots[i] = u; u += (int) sizes[i]; }
-    q.ctl = g->ctl;
+    q.ctl = g->ctl.dev;
     q.V = (int) m.n_vocab();
     // embedding + ln0 and ln_out + head + argmax inside the launch where the stage has them in a dtype the kernel reads (RWKV_MI_P47_NOFOLD=1: measurement aid)
     const char * nofold = getenv("RWKV_MI_P47_NOFOLD");
@@ -1784,79 +1780,26 @@ void * p47_create(const Model & m) {
     // long waits (spare and head workgroups) on one unit instead of the full-width poll; RWKV_MI_P47_CALM=0..3 selects which (measurement aid)
     const char * calm = getenv("RWKV_MI_P47_CALM");
     q.calm = calm && calm[0] >= '0' && calm[0] <= '9' ? atoi(calm) : P47_CALM_DEFAULT;
-    if (!in_arena) { p47_destroy(g); return nullptr; }
+    if (!in_arena) { delete g; return nullptr; }
     return g;
 }
 
-uint64_t p47_bytes(void * h) { P47Handle * g = (P47Handle *) h; uint64_t s = g->embed_bytes + g->head_bytes; for (uint64_t b : g->layer_bytes) s += b; return s; }
-
-// layers [l0, l1) of the stage (indices into the stage's own layer table); sin / sout: state of layer l0. tok (device): the launch starts
-// from LN0(emb[*tok]) instead of x when it begins at the stage's first layer and the handle folds the embedding; logits (device): ln_out +
-// head + argmax (into next_tok) run inside the launch when it ends at the stage's last layer and the handle folds the head.
-bool p47_folds_embed(void * h) { return ((P47Handle *) h)->fold_embed; }
-bool p47_folds_head(void * h) { return ((P47Handle *) h)->fold_head; }
-void p47_forward_range(void * h, float * x, float * v_first, const float * sin, float * sout, hipStream_t st, rwkv_context::Prof * pf, int l0, int l1,
-                       float * logits, const uint32_t * tok, uint32_t * next_tok) {
-    P47Handle * g = (P47Handle *) h;
-    P47 q = g->proto;
-    q.x = x; q.v_first = v_first; q.sin = sin; q.sout = sout; q.l0 = l0; q.l1 = l1;
-    q.x_out = (g->x_out && l1 == g->n_layers) ? g->x_out : x;
-    q.tok = (g->fold_embed && l0 == 0) ? tok : nullptr;
-    q.logits = (g->fold_head && l1 == g->n_layers) ? logits : nullptr;
+// layers [l0, l1) of the stage (indices into the stage's own layer table); sin / sout: state of the stage's first layer. tok (device): the
+// launch starts from LN0(emb[*tok]) instead of x when it begins at the stage's first layer and the handle folds the embedding; logits
+// (device): ln_out + head + argmax (into next_tok) run inside the launch when it ends at the stage's last layer and the handle folds the head.
+void P47Handle::forward_range(float * x, float * v_first, const float * sin, float * sout, hipStream_t st, DecodeProf * pf, float * logits, int l0, int l1,
+                              const uint32_t * tok, uint32_t * next_tok) {
+    P47 q = proto;
+    q.x = x; q.v_first = v_first; q.l0 = l0; q.l1 = l1;
+    q.sin = sin + (long long) l0 * q.state_stride; q.sout = sout + (long long) l0 * q.state_stride;   // (the kernel takes the state of ITS first layer)
+    q.x_out = (x_out && l1 == n_layers) ? x_out : x;
+    q.tok = (fold_embed && l0 == 0) ? tok : nullptr;
+    q.logits = (fold_head && l1 == n_layers) ? logits : nullptr;
     q.next_tok = next_tok;
-    const unsigned grid = (unsigned) (q.logits ? g->n_cu : g->n_blocks);
-    const P47Kernel fn = g_p47[g->variant].fn;
-    if (pf && pf->on) {
-        if (pf->used * 2 + 2 > pf->events.size()) {
-            hipEvent_t a = nullptr, c = nullptr;
-            (void) hipEventCreate(&a); (void) hipEventCreate(&c);
-            pf->events.push_back(a); pf->events.push_back(c); pf->bytes.push_back(0);
-        }
-        uint64_t bytes = (q.tok ? g->embed_bytes : 0) + (q.logits ? g->head_bytes : 0);
-        for (int i = l0; i < l1; i++) bytes += g->layer_bytes[(size_t) i];
-        pf->bytes[pf->used] = bytes;
-        hipExtLaunchKernelGGL(fn, dim3(grid), dim3(576), (uint32_t) g->lds, st, pf->events[pf->used * 2], pf->events[pf->used * 2 + 1], 0, q);
-        pf->used++;
-    } else {
-        hipLaunchKernelGGL(fn, dim3(grid), dim3(576), g->lds, st, q);
-    }
-}
-// greedy loops: the kernel appends every token it picks to hist (device memory, n entries) from position 0; nullptr switches it off
-bool p47_set_history(void * h, uint32_t * hist, size_t n, hipStream_t st) {
-    P47Handle * g = (P47Handle *) h;
-    const unsigned long long a = (unsigned long long) hist;
-    const unsigned w[5] = {hist ? 1u : 0u, 0u, (unsigned) (a & 0xFFFFFFFFull), (unsigned) (a >> 32), hist ? (unsigned) (n > 0xFFFFFFFFull ? 0xFFFFFFFFull : n) : 0u};   // (ctl[6]: capacity)
-    return hipMemcpyAsync(g->ctl + 2, w, sizeof(w), hipMemcpyHostToDevice, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
-}
-int p47_layers(void * h) { return ((P47Handle *) h)->n_layers; }
-
-void p47_set_x_out(void * h, float * x_out) { ((P47Handle *) h)->x_out = x_out; }
-
-bool p47_ctl_fetch(void * h, hipStream_t st) {
-    P47Handle * g = (P47Handle *) h;
-    return hipMemcpyAsync(g->h_ctl, g->ctl, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, st) == hipSuccess;
-}
-unsigned * p47_ctl(void * h) { return ((P47Handle *) h)->ctl; }
-bool p47_aborted_cached(void * h) { return ((P47Handle *) h)->h_ctl[1] != 0; }
-unsigned p47_generation_cached(void * h) { return ((P47Handle *) h)->h_ctl[0]; }
-bool p47_clear_abort(void * h, hipStream_t st) {
-    P47Handle * g = (P47Handle *) h;
-    g->h_ctl[1] = 0u;
-    return hipMemsetAsync(g->ctl + 1, 0, sizeof(unsigned), st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
-}
-bool p47_set_tag(void * h, unsigned base, hipStream_t st) {
-    P47Handle * g = (P47Handle *) h;
-    if (hipStreamSynchronize(st) != hipSuccess) return false;
-    return hipMemcpy(g->ctl, &base, sizeof(unsigned), hipMemcpyHostToDevice) == hipSuccess;
-}
-// real-time-counter stamps of one layer (16 per wave, 9 waves per workgroup) for the next launches; out holds n_blocks * 9 * 16 values
-bool p47_trace(void * h, int layer, long long * out, bool fetch) {
-    P47Handle * g = (P47Handle *) h;
-    const size_t n = (size_t) 256 * 9 * 16;
-    if (!g->trace) { if (hipMalloc((void **) &g->trace, n * 8) != hipSuccess) return false; (void) hipMemset(g->trace, 0, n * 8); }
-    g->proto.trace = g->trace; g->proto.trace_layer = layer;
-    if (fetch) return hipMemcpy(out, g->trace, n * 8, hipMemcpyDeviceToHost) == hipSuccess;
-    return true;
+    const unsigned grid = (unsigned) (q.logits ? n_cu : n_blocks);
+    uint64_t bytes = (q.tok ? embed_bytes : 0) + (q.logits ? head_bytes : 0);
+    for (int i = l0; i < l1; i++) bytes += layer_bytes[(size_t) i];
+    launch_profiled(pf, bytes, g_p47[variant].fn, dim3(grid), dim3(576), lds, st, q);
 }
 
 }  // namespace rwkvmi

@@ -214,7 +214,7 @@ bool pipeline_eval(rwkv_context * front, const uint32_t * tokens, size_t n, size
     if (logits_out && hipMemcpyAsync(logits_out, tail->d_logits, (size_t) tail->model->n_vocab() * sizeof(float), hipMemcpyDeviceToHost, tail->stream) != hipSuccess) return fail(tail);
     for (rwkv_context * c : st) {
         if (hipSetDevice(c->model->device) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return fail(c);
-        if (c->mega && mega_v6_aborted(c->mega, c->stream)) { recover_from_abort(c); front->last_error |= RWKV_ERROR_GRAPH; return false; }
+        if (c->mega && c->mega->ctl.aborted(c->stream)) { recover_from_abort(c); front->last_error |= RWKV_ERROR_GRAPH; return false; }
     }
     return true;
 }

@@ -2048,16 +2048,22 @@ struct RingShared {
     int64_t D = 0, F = 0, DR = 0, R = 0;
 };
 
-struct RingV6 {
-    int kind = 2;                 // (first member: mega_v6.hip's entry points dispatch on it)
+struct RingV6 : PersistentDecoder {
     const Model * model = nullptr;
     RingShared * sh = nullptr;
     void * xch = nullptr;
-    unsigned * ctl = nullptr;
-    unsigned * h_ctl = nullptr;
     R6P proto{};
-    long long * trace = nullptr;
-    float * x_out = nullptr;      // ring_v6_set_x_out: the last layer's x goes there instead of back into the launch's x (pipeline stages, runner.cpp)
+
+    ~RingV6() override;
+    DecodePath kind() const override { return DecodePath::Ring; }
+    uint64_t bytes() const override { return sh->bytes; }
+    bool folds_embed() const override { return sh->embed; }
+    bool folds_head() const override { return sh->head; }
+    bool folds_argmax() const override { return sh->head; }
+    void forward_range(float * x, float * v_first, const float * sin, float * sout, hipStream_t st, DecodeProf * pf, float * logits, int l0, int l1,
+                       const uint32_t * tok, uint32_t * next_tok) override;
+    // cycle stamps of one layer (16 per wave), n_blocks * 8 * 32 values (+ the loader's round samples of two workgroups)
+    bool trace(int layer, long long * out, bool fetch) override { return trace_into(proto.trace, proto.trace_layer, layer, (size_t) sh->n_blocks * 8 * 32, 2 * 512 * 4, out, fetch); }
 };
 
 typedef void (*RingKernel)(R6P);
@@ -2244,20 +2250,14 @@ static void ring_shared_release(const Model & m, RingShared * rs) {
     ring_shared_free(rs);
 }
 
-void ring_v6_destroy(void * h) {
-    RingV6 * rg = (RingV6 *) h;
-    if (!rg) return;
-    if (rg->xch) (void) hipFree(rg->xch);
-    if (rg->ctl) (void) hipFree(rg->ctl);
-    if (rg->h_ctl) (void) hipHostFree(rg->h_ctl);
-    if (rg->trace) (void) hipFree(rg->trace);
-    if (rg->model) ring_shared_release(*rg->model, rg->sh);
-    delete rg;
+RingV6::~RingV6() {
+    if (xch) (void) hipFree(xch);
+    if (model) ring_shared_release(*model, sh);
 }
 
 // Returns nullptr when the model / device does not qualify (the caller tries the register-prefetch kernel, then the seven launches).
 // Per context: the exchange arena, the control words, the trace buffer. Everything derived from the weights is shared (RingShared).
-void * ring_v6_create(const Model & m) {
+PersistentDecoder * ring_v6_create(const Model & m) {
     RingShared * rs = ring_shared_acquire(m);
     if (!rs) return nullptr;
     RingV6 * rg = new RingV6();
@@ -2272,12 +2272,8 @@ void * ring_v6_create(const Model & m) {
     int64_t units = 0;
     for (int64_t z : sizes) units += z;
     bool ok = hipMalloc(&rg->xch, (size_t) units * 16) == hipSuccess && hipMemset(rg->xch, 0, (size_t) units * 16) == hipSuccess
-      && hipMalloc((void **) &rg->ctl, 256) == hipSuccess && hipMemset(rg->ctl, 0, 256) == hipSuccess   // (ctl[2..6]: the greedy history words)
-      && hipHostMalloc((void **) &rg->h_ctl, 64, hipHostMallocDefault) == hipSuccess;
-    if (ok) { rg->h_ctl[0] = 8u; rg->h_ctl[1] = 0u; }
-    const unsigned init[2] = {8u, 0u};
-    ok = ok && hipMemcpy(rg->ctl, init, sizeof(init), hipMemcpyHostToDevice) == hipSuccess;
-    if (!ok || hipDeviceSynchronize() != hipSuccess) { ring_v6_destroy(rg); return nullptr; }
+      && rg->ctl.alloc(8u);
+    if (!ok || hipDeviceSynchronize() != hipSuccess) { delete rg; return nullptr; }
     R6P & q = rg->proto;
     q.layers = rs->d_layers; q.n_layers = rs->n_layers; q.layer0 = 0; q.layers_total = rs->n_layers;
     q.arena = (const unsigned char *) m.arena; q.w2b = rs->w2b;
@@ -2287,7 +2283,7 @@ void * ring_v6_create(const Model & m) {
     int * slots[9] = {&q.tl, &q.act5, &q.rkvg, &q.dl, &q.yq, &q.xatt, &q.kq, &q.xffn, &q.am};
     for (int i = 0; i < 9; i++) { *slots[i] = u; u += (int) sizes[i]; }
     q.act_stride = (int) act_stride;
-    q.ctl = rg->ctl;
+    q.ctl = rg->ctl.dev;
     q.stream = rs->stream; q.cus = rs->d_cus;
     q.F = (int) F; q.DR = (int) rs->DR; q.R = (int) rs->R; q.H = (int) m.head_count;
     q.ring_bytes = (unsigned) rs->ring; q.mirror_bytes = (unsigned) rs->mirror;
@@ -2314,88 +2310,21 @@ void * ring_v6_create(const Model & m) {
     return rg;
 }
 
-bool ring_v6_trace(void * h, int layer, long long * out, bool fetch) {
-    RingV6 * rg = (RingV6 *) h;
-    const size_t n = (size_t) rg->sh->n_blocks * 8 * 32, extra = 2 * 512 * 4;   // (+ the loader's round samples of two workgroups)
-    if (!rg->trace) { if (hipMalloc((void **) &rg->trace, (n + extra) * 8) != hipSuccess) return false; (void) hipMemset(rg->trace, 0, (n + extra) * 8); }
-    rg->proto.trace = rg->trace; rg->proto.trace_layer = layer;
-    if (fetch) {
-        if (const char * path = getenv("RWKV_MI_RING_LTRACE")) {   // measurement aid: the loader samples as raw int64 [2][512][4]
-            std::vector<long long> buf(extra);
-            if (hipMemcpy(buf.data(), rg->trace + n, extra * 8, hipMemcpyDeviceToHost) == hipSuccess) {
-                if (FILE * f = fopen(path, "wb")) { fwrite(buf.data(), 8, extra, f); fclose(f); }
-            }
-        }
-        return hipMemcpy(out, rg->trace, n * 8, hipMemcpyDeviceToHost) == hipSuccess;
-    }
-    return true;
-}
-
-uint64_t ring_v6_bytes(void * h) { return ((RingV6 *) h)->sh->bytes; }
-
-bool ring_v6_folds_head(void * h) { return ((RingV6 *) h)->sh->head; }
-
-// logits != nullptr (only when ring_v6_folds_head): ln_out + head run inside the launch and the logits land there
-void ring_v6_forward(void * h, float * x, const float * sin, float * sout, hipStream_t st, rwkv_context::Prof * pf, float * logits, const uint32_t * tok, uint32_t * next_tok) {
-    ring_v6_forward_range(h, x, sin, sout, st, pf, logits, 0, ((RingV6 *) h)->sh->n_layers, tok, next_tok);
-}
-bool ring_v6_folds_embed(void * h) { return ((RingV6 *) h)->sh->embed; }
-bool ring_v6_folds_argmax(void * h) { return ((RingV6 *) h)->sh->head; }
-// greedy loops: the kernel appends every token it picks to hist (device memory, n entries) from position 0; nullptr switches it off
-bool ring_v6_set_history(void * h, uint32_t * hist, size_t n, hipStream_t st) {
-    RingV6 * rg = (RingV6 *) h;
-    const unsigned long long a = (unsigned long long) hist;
-    const unsigned w[5] = {hist ? 1u : 0u, 0u, (unsigned) (a & 0xFFFFFFFFull), (unsigned) (a >> 32), hist ? (unsigned) (n > 0xFFFFFFFFull ? 0xFFFFFFFFull : n) : 0u};
-    return hipMemcpyAsync(rg->ctl + 2, w, sizeof(w), hipMemcpyHostToDevice, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
-}
-
 // Layers [l0, l1) of the stage in one launch (sin / sout: state of the stage's FIRST layer; x: the residual stream in plain memory, read
 // by the first and written by the last layer of the launch). logits (only with l1 == the stage's last layer): ln_out + head inside.
-// tok (only with l0 == 0 and ring_v6_folds_embed): the launch starts from the token id; next_tok (only with logits): where the argmax of the logits lands.
-void ring_v6_forward_range(void * h, float * x, const float * sin, float * sout, hipStream_t st, rwkv_context::Prof * pf, float * logits, int l0, int l1,
+// tok (only with l0 == 0 and folds_embed): the launch starts from the token id; next_tok (only with logits): where the argmax of the logits lands.
+void RingV6::forward_range(float * x, float *, const float * sin, float * sout, hipStream_t st, DecodeProf * pf, float * logits, int l0, int l1,
                            const uint32_t * tok, uint32_t * next_tok) {
-    RingV6 * rg = (RingV6 *) h;
-    R6P q = rg->proto;
+    R6P q = proto;
     q.x = x;
-    q.x_out = (rg->x_out && l1 == rg->sh->n_layers) ? rg->x_out : x;
-    q.tok = (rg->sh->embed && l0 == 0) ? tok : nullptr;
-    q.layers = rg->sh->d_layers + l0; q.n_layers = l1 - l0; q.layer0 = l0; q.layers_total = rg->sh->n_layers;
+    q.x_out = (x_out && l1 == sh->n_layers) ? x_out : x;
+    q.tok = (sh->embed && l0 == 0) ? tok : nullptr;
+    q.layers = sh->d_layers + l0; q.n_layers = l1 - l0; q.layer0 = l0; q.layers_total = sh->n_layers;
     q.sin = sin + (long long) l0 * q.state_stride; q.sout = sout + (long long) l0 * q.state_stride;
-    q.logits = (rg->sh->head && l1 == rg->sh->n_layers) ? logits : nullptr;
+    q.logits = (sh->head && l1 == sh->n_layers) ? logits : nullptr;
     q.next_tok = q.logits ? next_tok : nullptr;
-    const RingKernel fn = g_ring_variants[rg->sh->variant].fn;
-    if (pf && pf->on) {
-        if (pf->used * 2 + 2 > pf->events.size()) {
-            hipEvent_t a = nullptr, c = nullptr;
-            (void) hipEventCreate(&a); (void) hipEventCreate(&c);
-            pf->events.push_back(a); pf->events.push_back(c); pf->bytes.push_back(0);
-        }
-        pf->bytes[pf->used] = rg->sh->bytes * (uint64_t) (l1 - l0) / (uint64_t) rg->sh->n_layers + (q.logits ? rg->sh->bytes_head : 0) + (q.tok ? rg->sh->bytes_embed : 0);
-        hipExtLaunchKernelGGL(fn, dim3((unsigned) rg->sh->n_blocks), dim3(512), (uint32_t) rg->sh->lds, st, pf->events[pf->used * 2], pf->events[pf->used * 2 + 1], 0, q);
-        pf->used++;
-    } else {
-        hipLaunchKernelGGL(fn, dim3((unsigned) rg->sh->n_blocks), dim3(512), rg->sh->lds, st, q);
-    }
-}
-
-void ring_v6_set_x_out(void * h, float * x_out) { ((RingV6 *) h)->x_out = x_out; }
-
-bool ring_v6_ctl_fetch(void * h, hipStream_t st) {
-    RingV6 * rg = (RingV6 *) h;
-    return hipMemcpyAsync(rg->h_ctl, rg->ctl, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, st) == hipSuccess;
-}
-unsigned * ring_v6_ctl(void * h) { return ((RingV6 *) h)->ctl; }
-bool ring_v6_aborted_cached(void * h) { return ((RingV6 *) h)->h_ctl[1] != 0; }
-unsigned ring_v6_generation_cached(void * h) { return ((RingV6 *) h)->h_ctl[0]; }
-bool ring_v6_clear_abort(void * h, hipStream_t st) {
-    RingV6 * rg = (RingV6 *) h;
-    rg->h_ctl[1] = 0u;
-    return hipMemsetAsync(rg->ctl + 1, 0, sizeof(unsigned), st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
-}
-bool ring_v6_set_tag(void * h, unsigned base, hipStream_t st) {
-    RingV6 * rg = (RingV6 *) h;
-    if (hipStreamSynchronize(st) != hipSuccess) return false;
-    return hipMemcpy(rg->ctl, &base, sizeof(unsigned), hipMemcpyHostToDevice) == hipSuccess;
+    const uint64_t bytes = sh->bytes * (uint64_t) (l1 - l0) / (uint64_t) sh->n_layers + (q.logits ? sh->bytes_head : 0) + (q.tok ? sh->bytes_embed : 0);
+    launch_profiled(pf, bytes, g_ring_variants[sh->variant].fn, dim3((unsigned) sh->n_blocks), dim3(512), sh->lds, st, q);
 }
 
 }  // namespace rwkvmi

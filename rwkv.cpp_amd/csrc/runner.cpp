@@ -79,7 +79,7 @@ struct LocalHop : Hop {
     // all three (pipeline.cpp's consumed_ev, same reason). A send waits for the latest release, also the first send of the token
     // feedback: the first stage's token word holds the seed token until its first iteration has read it.
     // Round 6, second step: where the sender's kernel can reach the receiver's buffer (one device, or peer access from the sender's
-    // device), the stage's last layer stores the residual stream THERE (mega_v6_set_x_out) and the hop is two event operations: no copy
+    // device), the stage's last layer stores the residual stream THERE (PersistentDecoder::set_x_out) and the hop is two event operations: no copy
     // kernel between the stages (11 us from the end of the launch to the start of the copy, 4.7 us of copy, 17 us to the start of the next
     // stage's launch in profiles/r06_hop_trace.txt).
     std::vector<Slot> slots;   // [stream][message]
@@ -394,14 +394,14 @@ void hist_on(StagePart & p) {
         rwkv_context * c = p.h[j];
         if (!c->mega || !c->model->has_head || folded_argmax_target(c) == nullptr) continue;
         if (hipSetDevice(c->model->device) != hipSuccess) continue;
-        if (mega_v6_set_history(c->mega, p.d_hist + j * p.n_tokens, p.n_tokens, c->stream)) p.hist_in_launch[j] = 1;
+        if (c->mega->set_history(p.d_hist + j * p.n_tokens, p.n_tokens, c->stream)) p.hist_in_launch[j] = 1;
     }
 }
 void hist_off(StagePart & p) {
     for (size_t j = 0; j < p.hist_in_launch.size(); j++) {
         rwkv_context * c = p.h[j];
         if (!p.hist_in_launch[j] || !c->mega) continue;
-        if (hipSetDevice(c->model->device) == hipSuccess) (void) mega_v6_set_history(c->mega, nullptr, 0, c->stream);
+        if (hipSetDevice(c->model->device) == hipSuccess) (void) c->mega->set_history(nullptr, 0, c->stream);
         p.hist_in_launch[j] = 0;
     }
 }
@@ -416,11 +416,11 @@ void x_direct_on(StagePart & p) {
         rwkv_context * c = p.h[j];
         void * tgt = p.out->direct_target((int) j, 0);
         if (!tgt || !c->mega || c->model->has_head || !(!c->use_graph || single_launch_step(c, false))) continue;
-        if (mega_v6_set_x_out(c->mega, (float *) tgt)) p.x_direct[j] = 1;
+        if (c->mega->set_x_out((float *) tgt)) p.x_direct[j] = 1;
     }
 }
 void x_direct_off(StagePart & p) {
-    for (size_t j = 0; j < p.x_direct.size(); j++) if (p.x_direct[j] && p.h[j]->mega) (void) mega_v6_set_x_out(p.h[j]->mega, nullptr);
+    for (size_t j = 0; j < p.x_direct.size(); j++) if (p.x_direct[j] && p.h[j]->mega) (void) p.h[j]->mega->set_x_out(nullptr);
     p.x_direct.clear(); p.tok_direct.clear();
 }
 // (last stage) the token feedback the same way: a launch that folds the argmax AND appends to the history itself (hist_on) can leave the token
@@ -454,7 +454,7 @@ bool drain(StagePart & p, rwkv_context * err) {
     bool ok = true;
     for (rwkv_context * c : p.h) {
         if (hipSetDevice(c->model->device) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) { ok = false; continue; }
-        if (c->mega && mega_v6_aborted(c->mega, c->stream)) { recover_from_abort(c); ok = false; }
+        if (c->mega && c->mega->ctl.aborted(c->stream)) { recover_from_abort(c); ok = false; }
     }
     if (!ok) err->last_error |= RWKV_ERROR_GRAPH;
     return ok;

@@ -162,6 +162,27 @@ RWKV_API bool rwkv_mi_batch_eval(struct rwkv_mi_batch * batch, const uint32_t * 
 RWKV_API bool rwkv_mi_batch_decode_greedy(struct rwkv_mi_batch * batch, const uint32_t * slots, const uint32_t * first_tokens, size_t n,
                                           size_t n_tokens, uint32_t * tokens_out, float * elapsed_ms);
 
+/* Sampling in the batch, on the device: one row of parameters per row of the call, with the meaning of rwkv_mi_sample's arguments
+ * (temperature == 0: argmax; top_p == 0 means 1; u in [0, 1): the caller's uniform number; u < 0: the generator uniform01(seed, counter)).
+ * The batch owns ONE DRAW COUNTER PER SLOT (zero at rwkv_mi_batch_create): a row's draw reads and advances the counter of its slot, not of
+ * its position in the call, by one per draw that is not an argmax -- a sequence's random stream does not depend on who else is in the pass
+ * or in which order the slots are named. rwkv_mi_batch_eval and rwkv_mi_batch_decode_greedy never touch the counters.
+ * Besides what every batch call rejects, the two sampling calls return false with RWKV_ERROR_ARGS and change no slot, parity or counter when
+ * params (or sampled_out) is NULL, a temperature is < 0, a top_p is outside [0, 1], a u is >= 1, or any of the three is NaN. */
+struct rwkv_mi_sample_params { float temperature; float top_p; float u; uint64_t seed; };   /* 24 bytes */
+/* One token for each of n slots in one pass (as rwkv_mi_batch_eval), then one sampled token per row from that row's logits, on the
+ * device. sampled_out: [n]. logits_out: [n][n_vocab] or NULL (the head runs either way). Only 4 n bytes have to cross PCIe. */
+RWKV_API bool rwkv_mi_batch_eval_sample(struct rwkv_mi_batch * batch, const uint32_t * slots, const uint32_t * tokens, size_t n,
+                                        const struct rwkv_mi_sample_params * params /* [n] */, uint32_t * sampled_out, float * logits_out);
+/* Sampling loop on the device: as rwkv_mi_decode_sample on each slot, all n advancing together. Resets the named slots' draw
+ * counters to 0 first (as rwkv_mi_decode_sample resets its context's). params[i].u is ignored: the generator draws.
+ * tokens_out: [n][n_tokens] (may be NULL); elapsed_ms, parity and failure rules as rwkv_mi_batch_decode_greedy. */
+RWKV_API bool rwkv_mi_batch_decode_sample(struct rwkv_mi_batch * batch, const uint32_t * slots, const uint32_t * first_tokens, size_t n,
+                                          size_t n_tokens, const struct rwkv_mi_sample_params * params /* [n] */,
+                                          uint32_t * tokens_out, float * elapsed_ms);
+/* Sets a slot's draw counter (a new request in a reused slot: 0; resuming a recorded sequence: its count). */
+RWKV_API bool rwkv_mi_batch_rng_seek(struct rwkv_mi_batch * batch, size_t slot, uint64_t counter);
+
 #if defined(__cplusplus)
 }
 #endif

@@ -10,6 +10,9 @@ from .rwkv_cpp import (  # noqa: F401
     RWKVContext,
     RWKVModel,
     RWKVSharedLibrary,
+    SAMPLE_HOOKS_LIB_PATH,
+    SampleParams,
     build_library,
     load_rwkv_shared_library,
+    sample_params,
 )

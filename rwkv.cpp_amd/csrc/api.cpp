@@ -322,7 +322,7 @@ RWKV_API bool rwkv_mi_decode_greedy(struct rwkv_context * ctx, uint32_t first_to
 }
 
 static bool ensure_sampler(rwkv_context * ctx) {
-    if (!ctx->d_probs) HIP_CTX_OK(ctx, hipMalloc((void **) &ctx->d_probs, (size_t) ctx->model->n_vocab() * sizeof(float)));
+    if (!ctx->d_probs) HIP_CTX_OK(ctx, hipMalloc((void **) &ctx->d_probs, sample_scratch_floats(ctx->model->n_vocab()) * sizeof(float)));
     if (!ctx->d_rng_counter) {
         HIP_CTX_OK(ctx, hipMalloc((void **) &ctx->d_rng_counter, 64));
         HIP_CTX_OK(ctx, hipMemsetAsync(ctx->d_rng_counter, 0, 64, ctx->stream));
@@ -617,6 +617,10 @@ struct rwkv_mi_batch {
     std::vector<uint8_t> parity;
     RowState * d_rows = nullptr;       // [2][n_slots]: the row tables of a call (the greedy loop alternates between the two)
     RowState * h_rows = nullptr;       // pinned staging of the same
+    unsigned long long * d_counters = nullptr;   // [n_slots]: one draw counter per slot (sampling calls), zero at creation
+    SampleRow * d_srows = nullptr;     // [n_slots]: the sampler's row table of a call (parameters + the counter of the row's slot); with its pinned
+    SampleRow * h_srows = nullptr;     // staging and the sampler's scratch ([n_slots] vectors of probabilities) allocated by the first sampling call
+    float * d_probs = nullptr;
 
     float * slot_buf(size_t slot, int p) const { return states + ((size_t) p * n_slots + slot) * (size_t) state_len; }
 };
@@ -659,6 +663,42 @@ static bool batch_upload(rwkv_mi_batch * B, const uint32_t * slots, const uint32
     return true;
 }
 
+// the sampling arguments of a call (checked after batch_check_call, before anything changes)
+static bool batch_check_params(rwkv_mi_batch * B, const rwkv_mi_sample_params * params, size_t n, bool u_used) {
+    rwkv_context * ctx = B->ctx;
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, params != nullptr, "params is NULL");
+    for (size_t i = 0; i < n; i++) {
+        const rwkv_mi_sample_params & p = params[i];
+        // (written so that a NaN fails each comparison)
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, p.temperature >= 0.0f && p.top_p >= 0.0f && p.top_p <= 1.0f && (!u_used || p.u < 1.0f),
+                     "bad sampling arguments at index %zu (temperature %g, top_p %g, u %g)", i, (double) p.temperature, (double) p.top_p, (double) p.u);
+    }
+    return true;
+}
+
+// scratch and row table of the sampler: on the first sampling call of the batch
+static bool batch_ensure_sampler(rwkv_mi_batch * B) {
+    rwkv_context * ctx = B->ctx;
+    if (B->d_probs && B->d_srows && B->h_srows) return true;
+    hipError_t e = hipSuccess;
+    if (!B->d_probs) e = hipMalloc((void **) &B->d_probs, B->n_slots * sample_scratch_floats(ctx->model->n_vocab()) * sizeof(float));
+    if (e == hipSuccess && !B->d_srows) e = hipMalloc((void **) &B->d_srows, B->n_slots * sizeof(SampleRow));
+    if (e == hipSuccess && !B->h_srows) e = hipHostMalloc((void **) &B->h_srows, B->n_slots * sizeof(SampleRow), hipHostMallocDefault);
+    if (e != hipSuccess) (void) hipGetLastError();
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the sampler's scratch for %zu slots: %s", B->n_slots, hipGetErrorString(e));
+    return true;
+}
+
+// the sampler's row table of the n named slots, one upload per call (after batch_upload: the stream has been drained, the staging is free)
+static bool batch_upload_params(rwkv_mi_batch * B, const uint32_t * slots, const rwkv_mi_sample_params * params, size_t n, bool generator_only) {
+    for (size_t i = 0; i < n; i++) {
+        B->h_srows[i] = SampleRow{params[i], B->d_counters + slots[i]};
+        if (generator_only) B->h_srows[i].p.u = -1.0f;
+    }
+    BATCH_HIP_OK(B, hipMemcpyAsync(B->d_srows, B->h_srows, n * sizeof(SampleRow), hipMemcpyHostToDevice, B->run->stream));
+    return true;
+}
+
 extern "C" {
 
 RWKV_API void rwkv_mi_batch_free(struct rwkv_mi_batch * B) {
@@ -670,6 +710,10 @@ RWKV_API void rwkv_mi_batch_free(struct rwkv_mi_batch * B) {
     if (B->states) (void) hipFree(B->states);
     if (B->d_rows) (void) hipFree(B->d_rows);
     if (B->h_rows) (void) hipHostFree(B->h_rows);
+    if (B->d_counters) (void) hipFree(B->d_counters);
+    if (B->d_srows) (void) hipFree(B->d_srows);
+    if (B->h_srows) (void) hipHostFree(B->h_srows);
+    if (B->d_probs) (void) hipFree(B->d_probs);
     batch_context_destroy(B->run);
     delete B;
 }
@@ -698,6 +742,10 @@ RWKV_API struct rwkv_mi_batch * rwkv_mi_batch_create(struct rwkv_context * ctx, 
     RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, nullptr, e == hipSuccess, "HIP error: %s", hipGetErrorString(e));
     e = hipHostMalloc((void **) &B->h_rows, 2 * n_slots * sizeof(RowState), hipHostMallocDefault);
     RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, nullptr, e == hipSuccess, "HIP error: %s", hipGetErrorString(e));
+    e = hipMalloc((void **) &B->d_counters, n_slots * sizeof(unsigned long long));
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, nullptr, e == hipSuccess, "HIP error: %s", hipGetErrorString(e));
+    e = hipMemsetAsync(B->d_counters, 0, n_slots * sizeof(unsigned long long), B->run->stream);
+    RW_CTX_CHECK(ctx, RWKV_ERROR_GRAPH, nullptr, e == hipSuccess, "HIP error: %s", hipGetErrorString(e));
     // every slot starts from the fresh state (both buffers: a slot's first pass reads buffer 0)
     for (size_t s = 0; s < n_slots; s++) {
         float * dst = B->slot_buf(s, 0);
@@ -815,6 +863,74 @@ RWKV_API bool rwkv_mi_batch_decode_greedy(struct rwkv_mi_batch * B, const uint32
     for (size_t r = 0; r < n && tokens_out; r++)
         for (size_t i = 0; i < n_tokens; i++) tokens_out[r * n_tokens + i] = h[i * n + r];
     if (n_tokens & 1) for (size_t i = 0; i < n; i++) B->parity[slots[i]] ^= 1;
+    return true;
+}
+
+RWKV_API bool rwkv_mi_batch_eval_sample(struct rwkv_mi_batch * B, const uint32_t * slots, const uint32_t * tokens, size_t n,
+                                        const struct rwkv_mi_sample_params * params, uint32_t * sampled_out, float * logits_out) {
+    rwkv_context * ctx = B->ctx;
+    ctx->last_error = RWKV_ERROR_NONE;
+    if (!batch_check_call(B, slots, tokens, n) || !batch_check_params(B, params, n, true)) return false;
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, sampled_out != nullptr, "sampled_out is NULL");
+    rwkv_context * run = B->run;
+    run->print_errors = ctx->print_errors;
+    BATCH_HIP_OK(B, hipSetDevice(ctx->model->device));
+    if (!batch_ensure_sampler(B)) return false;
+    if (!batch_upload(B, slots, tokens, n, 1) || !batch_upload_params(B, slots, params, n, false)) return false;
+    // each row's token lands in the batch's token word of that row: the 4 n bytes that go back to the host
+    const RowSampler sampler{B->d_srows, B->d_probs, nullptr};
+    if (!forward_rows(run, B->d_rows, (int64_t) n, true, &sampler)) { (void) hipStreamSynchronize(run->stream); return batch_fail_through(B); }
+    BATCH_HIP_OK(B, hipMemcpyAsync(run->h_tokens, run->d_tokens, n * sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream));
+    if (logits_out) BATCH_HIP_OK(B, hipMemcpyAsync(logits_out, run->d_logits, n * (size_t) ctx->model->n_vocab() * sizeof(float), hipMemcpyDeviceToHost, run->stream));
+    BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));
+    memcpy(sampled_out, run->h_tokens, n * sizeof(uint32_t));
+    for (size_t i = 0; i < n; i++) B->parity[slots[i]] ^= 1;
+    return true;
+}
+
+RWKV_API bool rwkv_mi_batch_decode_sample(struct rwkv_mi_batch * B, const uint32_t * slots, const uint32_t * first_tokens, size_t n,
+                                          size_t n_tokens, const struct rwkv_mi_sample_params * params, uint32_t * tokens_out, float * elapsed_ms) {
+    rwkv_context * ctx = B->ctx;
+    ctx->last_error = RWKV_ERROR_NONE;
+    if (!batch_check_call(B, slots, first_tokens, n) || !batch_check_params(B, params, n, false)) return false;
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, n_tokens > 0, "n_tokens is 0");
+    rwkv_context * run = B->run;
+    run->print_errors = ctx->print_errors;
+    BATCH_HIP_OK(B, hipSetDevice(ctx->model->device));
+    if (!batch_ensure_sampler(B)) return false;
+    struct DevBuf { uint32_t * p = nullptr; ~DevBuf() { if (p) (void) hipFree(p); } } hist;   // [n_tokens][n], freed on every exit
+    BATCH_HIP_OK(B, hipMalloc((void **) &hist.p, n_tokens * n * sizeof(uint32_t)));
+    if (!batch_upload(B, slots, first_tokens, n, 2) || !batch_upload_params(B, slots, params, n, true)) return false;
+    launch_sample_seek_rows(B->d_srows, (int64_t) n, 0ull, run->stream);   // the named slots' streams start over
+    BATCH_HIP_OK(B, hipEventRecord(run->ev0, run->stream));
+    for (size_t i = 0; i < n_tokens; i++) {
+        // as the greedy loop: the two row tables alternate; each row's sampled token lands where its next embedding lookup reads it
+        const RowSampler sampler{B->d_srows, B->d_probs, hist.p + i * n};
+        if (!forward_rows(run, B->d_rows + (i & 1) * B->n_slots, (int64_t) n, true, &sampler)) {
+            (void) hipStreamSynchronize(run->stream);
+            return batch_fail_through(B);
+        }
+    }
+    BATCH_HIP_OK(B, hipEventRecord(run->ev1, run->stream));
+    std::vector<uint32_t> h(tokens_out ? n_tokens * n : 0);
+    if (tokens_out) BATCH_HIP_OK(B, hipMemcpyAsync(h.data(), hist.p, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream));
+    BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));
+    if (elapsed_ms) BATCH_HIP_OK(B, hipEventElapsedTime(elapsed_ms, run->ev0, run->ev1));
+    for (size_t r = 0; r < n && tokens_out; r++)
+        for (size_t i = 0; i < n_tokens; i++) tokens_out[r * n_tokens + i] = h[i * n + r];
+    if (n_tokens & 1) for (size_t i = 0; i < n; i++) B->parity[slots[i]] ^= 1;
+    return true;
+}
+
+RWKV_API bool rwkv_mi_batch_rng_seek(struct rwkv_mi_batch * B, size_t slot, uint64_t counter) {
+    rwkv_context * ctx = B->ctx;
+    ctx->last_error = RWKV_ERROR_NONE;
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, slot < B->n_slots, "slot %zu is out of range", slot);
+    BATCH_HIP_OK(B, hipSetDevice(ctx->model->device));
+    hipStream_t st = B->run->stream;
+    const unsigned long long v = counter;
+    BATCH_HIP_OK(B, hipMemcpyAsync(B->d_counters + slot, &v, sizeof(v), hipMemcpyHostToDevice, st));
+    BATCH_HIP_OK(B, hipStreamSynchronize(st));
     return true;
 }
 

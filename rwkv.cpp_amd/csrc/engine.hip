@@ -739,13 +739,18 @@ void batch_context_destroy(rwkv_context * c) {
 }
 
 // One pass of T rows, row t = one token (ctx->d_tokens[t]) of the sequence whose state is d_rows[t]. Logits: ctx->d_logits[T][n_vocab].
-bool forward_rows(rwkv_context * ctx, const RowState * d_rows, int64_t T, bool want_logits) {
+// sample: the T sampler workgroups (sampling.hip, k_sample_rows) follow the head INSIDE the chain bracket. Each of them is 1024 threads,
+// a CU's worth of waves, so up to T CUs are taken while they run; the completion event mega_chain_end records is what the device's next
+// persistent launch waits on, and with the sampler in front of it that launch still finds every CU free ("a batch pass never runs beside
+// a persistent kernel" holds for the sampler too). The greedy loop's argmax stays where it was, after the bracket.
+bool forward_rows(rwkv_context * ctx, const RowState * d_rows, int64_t T, bool want_logits, const RowSampler * sample) {
     if (!ensure_scratch(ctx, T)) return false;
     Model & m = *ctx->model;
     Runner r{ctx, m, ctx->stream, T, m.n_embed(), m.head_count, m.head_size, ctx->b};
     r.state.rows = d_rows;
     mega_chain_begin(ctx);
     r.run(want_logits);
+    if (sample && want_logits && !r.failed) launch_sample_rows(ctx->d_logits, T, (int) m.n_vocab(), sample->table, sample->probs, ctx->d_tokens, sample->hist, ctx->stream);
     mega_chain_end(ctx);
     HIP_CTX_OK(ctx, hipGetLastError());
     RW_CTX_CHECK(ctx, RWKV_ERROR_GRAPH | RWKV_ERROR_ALLOC, false, !r.failed, "a batched product could not be launched (out of device memory for the tile-major weight image?)");

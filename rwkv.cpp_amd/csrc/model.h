@@ -9,6 +9,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "persist_host.h"
+#include "rwkv_mi355x.h"
 
 namespace rwkvmi {
 
@@ -107,6 +108,14 @@ constexpr int64_t k_mfma_min_tokens = 32;   // sequence calls of at least this m
 // counter is advanced on the device). The token is written to out_token (and to hist[hist_pos] when hist is given).
 void launch_sample(const float * logits, int n, float temperature, float top_p, float u, unsigned long long seed, unsigned long long * counter,
                    float * probs, uint32_t * out_token, uint32_t * hist, int hist_pos, hipStream_t st);
+// probs: scratch of sample_scratch_floats(n) floats (the vocabulary rounded up to whole chunks of the 1024 threads: the kernel keeps it transposed).
+inline size_t sample_scratch_floats(int64_t n) { return (size_t) ((n + 1023) / 1024) * 1024; }
+// The row form (batched decode): one workgroup per row of logits[rows][n], row r with table[r]'s parameters and draw counter (the counter
+// of the row's SLOT). probs: [rows][sample_scratch_floats(n)] scratch. Row r's token goes to tokens[r] (the word its next embedding lookup
+// reads) and, when hist is given, to hist[r].
+struct SampleRow { rwkv_mi_sample_params p; unsigned long long * counter; };
+void launch_sample_rows(const float * logits, int64_t rows, int n, const SampleRow * table, float * probs, uint32_t * tokens, uint32_t * hist, hipStream_t st);
+void launch_sample_seek_rows(const SampleRow * table, int64_t rows, unsigned long long value, hipStream_t st);   // *table[r].counter = value
 
 // Loads [layer_begin, layer_end) of the file (layer_end == UINT32_MAX: all layers) onto the current HIP device.
 // Returns nullptr with the thread-local error set, like the reference loader (rwkv_model_loading.inc:288-419).
@@ -149,7 +158,7 @@ struct rwkv_context {
     int64_t    d_tokens_cap = 0;
     float *    d_logits = nullptr;
     uint32_t * d_next_token = nullptr;
-    float *    d_probs = nullptr;                 // sampler scratch (n_vocab floats), allocated on first use
+    float *    d_probs = nullptr;                 // sampler scratch (sample_scratch_floats(n_vocab) floats), allocated on first use
     unsigned long long * d_rng_counter = nullptr;
 
     // pinned host staging for tokens / logits
@@ -206,7 +215,9 @@ bool forward(rwkv_context * ctx, int64_t T, bool want_logits);
 // chain of persistent launches) and one pass of T rows, row t from state d_rows[t].in into d_rows[t].out
 rwkv_context * batch_context_create(Model * m, int64_t max_rows);
 void batch_context_destroy(rwkv_context * c);
-bool forward_rows(rwkv_context * ctx, const RowState * d_rows, int64_t T, bool want_logits);
+// sample: when given, one sampled token per row from the pass's logits (launch_sample_rows), launched inside the pass's place in the chain
+struct RowSampler { const SampleRow * table; float * probs; uint32_t * hist; };
+bool forward_rows(rwkv_context * ctx, const RowState * d_rows, int64_t T, bool want_logits, const RowSampler * sample = nullptr);
 
 // fused RWKV-6 decode layer (fused_v6.hip)
 bool   fused_v6_supported(const Model & m);

@@ -8,6 +8,8 @@
 // The cut-off is found without sorting: the largest threshold t (bisection over the float bit pattern, 31 reductions) with
 // sum{p >= t} > top_p is exactly that probability. Sums are f32 in a fixed order (per-thread contiguous chunks, then a tree): runs
 // are reproducible; against numpy's sequential cumsum the result can differ only when u or top_p falls within rounding of a boundary.
+// Batched decode samples every row of a pass in one launch of k_sample_rows: one workgroup per row, per-row parameters and the draw
+// counter of the row's slot from a device table (rwkv_mi_batch_eval_sample / _decode_sample).
 #include "kdev.h"
 #include "model.h"
 
@@ -33,34 +35,49 @@ __device__ __forceinline__ float uniform01(unsigned long long seed, unsigned lon
     return (float) (z >> 40) * (1.0f / 16777216.0f);
 }
 
-__global__ __launch_bounds__(1024) void k_sample(const float * __restrict__ logits, int n, float temperature, float top_p, float u_in,
-                                                 unsigned long long seed, unsigned long long * counter /* read and advanced by thread 0; may be NULL */,
-                                                 float * __restrict__ probs, uint32_t * __restrict__ out_token, uint32_t * __restrict__ hist, int hist_pos) {
+// f(j) over a thread's chunk, in the order of j
+template <class F>
+__device__ __forceinline__ void for_chunk(int cnt, F && f) { for (int j = 0; j < cnt; j++) f(j); }
+
+// One body, two entry points (the convention of the recurrence kernels and their row forms): k_sample hands it its arguments,
+// k_sample_rows the pointers and parameters of row blockIdx.x. Everything the workgroup does -- chunks, summation order, bisection, scan,
+// draw -- is this function, so a row of the batch picks bit for bit the token the single-context sampler picks from the same logits.
+// The scratch vector is laid out for the passes, not for the reader: token i0 + j of thread tid lives at probs[j * 1024 + tid], so the 64 lanes
+// of a load touch two cache lines instead of 64 (a thread's chunk is contiguous in the logits; ~35 passes run over the probabilities).
+__device__ __forceinline__ void sample_body(const float * __restrict__ logits, int n, float temperature, float top_p, float u_in,
+                                            unsigned long long seed, unsigned long long * counter /* read and advanced by thread 0; may be NULL */,
+                                            float * __restrict__ probs /* scratch of C * 1024 >= n floats, C = ceil(n / 1024) */,
+                                            uint32_t * __restrict__ out_token, uint32_t * __restrict__ hist_word /* may be NULL */) {
     __shared__ float red[32];
     __shared__ float l_scan[1024];
-    __shared__ int l_pick;
+    __shared__ int l_pick, l_last;
     __shared__ unsigned long long l_ctr;
     const int tid = threadIdx.x, NT = blockDim.x;
     const int C = (n + NT - 1) / NT;                 // contiguous chunk per thread
     const int i0 = tid * C, i1 = i0 + C < n ? i0 + C : n;
+    const int cnt = i1 - i0;                         // (<= 0 for the threads behind the end)
+    struct { float * mem; int nt;
+             __device__ __forceinline__ float get(int j) const { return mem[(size_t) j * nt]; }
+             __device__ __forceinline__ void set(int j, float v) { mem[(size_t) j * nt] = v; } } pr{probs + tid, NT};
+    const float * lg = logits + i0;
     // softmax
     float m = -INFINITY;
-    for (int i = i0; i < i1; i++) m = fmaxf(m, logits[i]);
+    for_chunk(cnt, [&](int j) { m = fmaxf(m, lg[j]); });
     for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, WAVE));
     if ((tid & 63) == 0) red[tid >> 6] = m;
     __syncthreads();
     for (int w = 0; w < (NT >> 6); w++) m = fmaxf(m, red[w]);
     float part = 0.0f;
-    for (int i = i0; i < i1; i++) { const float e = det_expf(logits[i] - m); probs[i] = e; part += e; }
+    for_chunk(cnt, [&](int j) { const float e = det_expf(lg[j] - m); pr.set(j, e); part += e; });
     const float total = block_sum_f(part, red);
     const float inv = 1.0f / total;
-    for (int i = i0; i < i1; i++) probs[i] *= inv;
+    for_chunk(cnt, [&](int j) { pr.set(j, pr.get(j) * inv); });
     if (top_p == 0.0f) top_p = 1.0f;
     int pick = -1;
     if (temperature == 0.0f) {
         // argmax, first index of the maximum
         float best = -1.0f; int bi = 0x7fffffff;
-        for (int i = i0; i < i1; i++) if (probs[i] > best) { best = probs[i]; bi = i; }
+        for_chunk(cnt, [&](int j) { const float p = pr.get(j); if (p > best) { best = p; bi = i0 + j; } });
         for (int o = 32; o > 0; o >>= 1) {
             const float ov = __shfl_xor(best, o, WAVE); const int oi = __shfl_xor(bi, o, WAVE);
             if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
@@ -82,13 +99,13 @@ __global__ __launch_bounds__(1024) void k_sample(const float * __restrict__ logi
             // (when not even the sum over ALL probabilities exceeds top_p -- float rounding of the softmax -- the reference's
             //  argmax over an all-false mask is 0: the cut-off is the LARGEST probability, i.e. 1 * inv)
             float g0 = 0.0f;
-            for (int i = i0; i < i1; i++) g0 += probs[i];
+            for_chunk(cnt, [&](int j) { g0 += pr.get(j); });
             g0 = block_sum_f(g0, red);
             const bool none = !(g0 > top_p);
             for (int bit = 30; bit >= 0; bit--) {
                 const unsigned cand = T | (1u << bit);
                 float g = 0.0f;
-                for (int i = i0; i < i1; i++) { const float p = probs[i]; g += __float_as_uint(p) >= cand ? p : 0.0f; }
+                for_chunk(cnt, [&](int j) { const float p = pr.get(j); g += __float_as_uint(p) >= cand ? p : 0.0f; });
                 g = block_sum_f(g, red);
                 if (g > top_p) T = cand;
             }
@@ -96,15 +113,15 @@ __global__ __launch_bounds__(1024) void k_sample(const float * __restrict__ logi
         }
         const float it = 1.0f / temperature;
         part = 0.0f;
-        for (int i = i0; i < i1; i++) {
-            float p = probs[i];
+        for_chunk(cnt, [&](int j) {
+            float p = pr.get(j);
             if (__float_as_uint(p) < cutoff_bits) p = 0.0f;
             // (p * total = p / p_max: the power of the probability relative to the largest one -- the same distribution after the
             //  renormalisation below, without p^(1/temperature) underflowing to zero for every token at a low temperature and a large vocabulary)
             else if (temperature != 1.0f) p = p > 0.0f ? powf(p * total, it) : 0.0f;
-            probs[i] = p;
+            pr.set(j, p);
             part += p;
-        }
+        });
         // inclusive scan of the per-thread sums (Hillis-Steele), then the thread whose range holds u * total walks its chunk
         l_scan[tid] = part;
         __syncthreads();
@@ -115,7 +132,7 @@ __global__ __launch_bounds__(1024) void k_sample(const float * __restrict__ logi
             __syncthreads();
         }
         const float all = l_scan[NT - 1];
-        if (tid == 0) { l_ctr = counter ? *counter : 0ull; l_pick = 0x7fffffff; }
+        if (tid == 0) { l_ctr = counter ? *counter : 0ull; l_pick = 0x7fffffff; l_last = 0; }
         __syncthreads();
         const unsigned long long ctr = l_ctr;
         const float u = (u_in >= 0.0f ? u_in : uniform01(seed, ctr)) * all;
@@ -125,28 +142,55 @@ __global__ __launch_bounds__(1024) void k_sample(const float * __restrict__ logi
             //  lowest candidate index wins)
             float acc = before;
             int found = -1, last_pos = -1;
-            for (int i = i0; i < i1; i++) { acc += probs[i]; if (probs[i] > 0.0f) last_pos = i; if (found < 0 && acc > u) found = i; }
+            for_chunk(cnt, [&](int j) { const float p = pr.get(j); acc += p; if (p > 0.0f) last_pos = i0 + j; if (found < 0 && acc > u) found = i0 + j; });
             const int cand = found >= 0 ? found : last_pos;   // (acc can fall short of l_scan[tid] by rounding: the chunk's last candidate)
             if (cand >= 0) atomicMin(&l_pick, cand);
         }
         __syncthreads();
-        if (l_pick == 0x7fffffff && tid == 0) {
-            // u landed on / beyond the total through rounding: the last token with non-zero probability
-            int lp = 0;
-            for (int i = n - 1; i >= 0; i--) if (probs[i] > 0.0f) { lp = i; break; }
-            l_pick = lp;
-        }
-        __syncthreads();
-        pick = l_pick;
+        if (l_pick == 0x7fffffff) {
+            // u landed on / beyond the total through rounding: the last token with non-zero probability (0 when there is none)
+            int lp = -1;
+            for_chunk(cnt, [&](int j) { if (pr.get(j) > 0.0f) lp = i0 + j; });
+            if (lp > 0) atomicMax(&l_last, lp);
+            __syncthreads();
+            pick = l_last;
+        } else pick = l_pick;
         if (tid == 0 && counter) *counter = ctr + 1;
     }
     if (pick < 0 || pick >= n) pick = 0;   // (all-NaN probabilities: the token must stay a row of the embedding table)
-    if (tid == 0) { *out_token = (uint32_t) pick; if (hist) hist[hist_pos] = (uint32_t) pick; }
+    if (tid == 0) { *out_token = (uint32_t) pick; if (hist_word) *hist_word = (uint32_t) pick; }
+}
+
+__global__ __launch_bounds__(1024) void k_sample(const float * __restrict__ logits, int n, float temperature, float top_p, float u_in,
+                                                 unsigned long long seed, unsigned long long * counter,
+                                                 float * __restrict__ probs, uint32_t * __restrict__ out_token, uint32_t * __restrict__ hist, int hist_pos) {
+    sample_body(logits, n, temperature, top_p, u_in, seed, counter, probs, out_token, hist ? hist + hist_pos : nullptr);
+}
+
+// Row form: grid = rows, one workgroup per row; row r's probabilities in its own stretch of the scratch (stride floats apart, the batch owns it).
+__global__ __launch_bounds__(1024) void k_sample_rows(const float * __restrict__ logits, int n, const SampleRow * __restrict__ table,
+                                                      float * __restrict__ probs, size_t stride, uint32_t * __restrict__ tokens, uint32_t * __restrict__ hist) {
+    const size_t r = blockIdx.x;
+    const rwkv_mi_sample_params p = table[r].p;
+    sample_body(logits + r * (size_t) n, n, p.temperature, p.top_p, p.u, p.seed, table[r].counter, probs + r * stride, tokens + r, hist ? hist + r : nullptr);
+}
+
+__global__ __launch_bounds__(64) void k_sample_seek_rows(const SampleRow * __restrict__ table, int rows, unsigned long long value) {
+    const int r = blockIdx.x * 64 + threadIdx.x;
+    if (r < rows) *table[r].counter = value;
 }
 
 void launch_sample(const float * logits, int n, float temperature, float top_p, float u, unsigned long long seed, unsigned long long * counter,
                    float * probs, uint32_t * out_token, uint32_t * hist, int hist_pos, hipStream_t st) {
     hipLaunchKernelGGL(k_sample, dim3(1), dim3(1024), 0, st, logits, n, temperature, top_p, u, seed, counter, probs, out_token, hist, hist_pos);
+}
+
+void launch_sample_rows(const float * logits, int64_t rows, int n, const SampleRow * table, float * probs, uint32_t * tokens, uint32_t * hist, hipStream_t st) {
+    hipLaunchKernelGGL(k_sample_rows, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, table, probs, sample_scratch_floats(n), tokens, hist);
+}
+
+void launch_sample_seek_rows(const SampleRow * table, int64_t rows, unsigned long long value, hipStream_t st) {
+    hipLaunchKernelGGL(k_sample_seek_rows, dim3((unsigned) ((rows + 63) / 64)), dim3(64), 0, st, table, (int) rows, value);
 }
 
 }  // namespace rwkvmi

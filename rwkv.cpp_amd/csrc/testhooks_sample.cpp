@@ -1,0 +1,46 @@
+// testhooks_sample.cpp -- the sampler's entry point for tests/ ONLY (include/rwkv_testhooks_sample.h). `make` links it with every product
+// object into a third library, lib/librwkv_testhooks_sample.so; neither librwkv.so nor librwkv_testhooks.so carries it.
+#include "model.h"
+#include "rwkv_mi355x.h"
+#include "rwkv_testhooks_sample.h"
+
+#include <vector>
+
+using namespace rwkvmi;
+
+extern "C" {
+
+// Test hook: both entry points of the sampler on standalone logits; row r draws with counters[r].
+RWKV_API bool rwkv_mi_test_sample_rows(const float * logits, int64_t n_rows, int64_t n_vocab, const struct rwkv_mi_sample_params * params,
+                                       uint64_t * counters, int rows_kernel, uint32_t * tokens_out) {
+    g_last_error = RWKV_ERROR_NONE;
+    RW_CHECK(RWKV_ERROR_ARGS, false, logits && params && tokens_out && n_rows > 0 && n_rows <= 65535 && n_vocab > 0 && n_vocab <= (int64_t) 1 << 24, "bad arguments");
+    const size_t R = (size_t) n_rows, V = (size_t) n_vocab;
+    float *d_logits = nullptr, *d_probs = nullptr;
+    unsigned long long * d_ctr = nullptr;
+    SampleRow * d_table = nullptr;
+    uint32_t * d_tok = nullptr;
+    std::vector<SampleRow> table(R);
+    bool ok = hipMalloc((void **) &d_logits, R * V * 4) == hipSuccess && hipMalloc((void **) &d_probs, R * sample_scratch_floats(n_vocab) * 4) == hipSuccess &&
+              hipMalloc((void **) &d_ctr, R * 8) == hipSuccess && hipMalloc((void **) &d_table, R * sizeof(SampleRow)) == hipSuccess &&
+              hipMalloc((void **) &d_tok, R * 4) == hipSuccess &&
+              hipMemcpy(d_logits, logits, R * V * 4, hipMemcpyHostToDevice) == hipSuccess &&
+              (counters ? hipMemcpy(d_ctr, counters, R * 8, hipMemcpyHostToDevice) : hipMemset(d_ctr, 0, R * 8)) == hipSuccess;
+    if (ok) {
+        for (size_t r = 0; r < R; r++) table[r] = SampleRow{params[r], d_ctr + r};
+        ok = hipMemcpy(d_table, table.data(), R * sizeof(SampleRow), hipMemcpyHostToDevice) == hipSuccess;
+    }
+    if (ok) {
+        if (rows_kernel) launch_sample_rows(d_logits, n_rows, (int) n_vocab, d_table, d_probs, d_tok, nullptr, nullptr);
+        else for (size_t r = 0; r < R; r++)
+            launch_sample(d_logits + r * V, (int) n_vocab, params[r].temperature, params[r].top_p, params[r].u, params[r].seed, d_ctr + r,
+                          d_probs, d_tok + r, nullptr, 0, nullptr);
+        ok = hipDeviceSynchronize() == hipSuccess && hipMemcpy(tokens_out, d_tok, R * 4, hipMemcpyDeviceToHost) == hipSuccess &&
+             (!counters || hipMemcpy(counters, d_ctr, R * 8, hipMemcpyDeviceToHost) == hipSuccess);
+    }
+    for (void * p : {(void *) d_logits, (void *) d_probs, (void *) d_ctr, (void *) d_table, (void *) d_tok}) if (p) (void) hipFree(p);
+    RW_CHECK(RWKV_ERROR_GRAPH, false, ok, "HIP error: %s", hipGetErrorString(hipGetLastError()));
+    return true;
+}
+
+}  // extern "C"

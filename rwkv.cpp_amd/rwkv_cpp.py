@@ -19,10 +19,20 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG_DIR, os.environ.get("RWKV_LIB_DIR", "lib"), "librwkv.so")
 # tests/ only: the same objects + csrc/testhooks.cpp (include/rwkv_testhooks.h); the product library does not export test entry points
 HOOKS_LIB_PATH = os.path.join(PKG_DIR, os.environ.get("RWKV_LIB_DIR", "lib"), "librwkv_testhooks.so")
+# tests/ only: the same objects + csrc/testhooks_sample.cpp (include/rwkv_testhooks_sample.h): the sampler kernel on caller-supplied logits
+SAMPLE_HOOKS_LIB_PATH = os.path.join(PKG_DIR, os.environ.get("RWKV_LIB_DIR", "lib"), "librwkv_testhooks_sample.so")
 
 QUANTIZED_FORMAT_NAMES = ("Q4_0", "Q4_1", "Q5_0", "Q5_1", "Q8_0")
 P_FLOAT = ctypes.POINTER(ctypes.c_float)
 P_UINT32 = ctypes.POINTER(ctypes.c_uint32)
+
+
+class SampleParams(ctypes.Structure):
+    """struct rwkv_mi_sample_params (include/rwkv_mi355x.h): one row's sampling parameters, 24 bytes."""
+    _fields_ = [("temperature", ctypes.c_float), ("top_p", ctypes.c_float), ("u", ctypes.c_float), ("seed", ctypes.c_uint64)]
+
+
+P_SAMPLE_PARAMS = ctypes.POINTER(SampleParams)
 
 
 def build_library(force: bool = False) -> str:
@@ -168,6 +178,15 @@ class RWKVSharedLibrary:
         L.rwkv_mi_batch_eval.restype = ctypes.c_bool
         L.rwkv_mi_batch_decode_greedy.argtypes = [c_batch, P_UINT32, P_UINT32, ctypes.c_size_t, ctypes.c_size_t, P_UINT32, P_FLOAT]
         L.rwkv_mi_batch_decode_greedy.restype = ctypes.c_bool
+        L.rwkv_mi_batch_eval_sample.argtypes = [c_batch, P_UINT32, P_UINT32, ctypes.c_size_t, P_SAMPLE_PARAMS, P_UINT32, P_FLOAT]
+        L.rwkv_mi_batch_eval_sample.restype = ctypes.c_bool
+        L.rwkv_mi_batch_decode_sample.argtypes = [c_batch, P_UINT32, P_UINT32, ctypes.c_size_t, ctypes.c_size_t, P_SAMPLE_PARAMS, P_UINT32, P_FLOAT]
+        L.rwkv_mi_batch_decode_sample.restype = ctypes.c_bool
+        L.rwkv_mi_batch_rng_seek.argtypes = [c_batch, ctypes.c_size_t, ctypes.c_uint64]
+        L.rwkv_mi_batch_rng_seek.restype = ctypes.c_bool
+        if hasattr(L, "rwkv_mi_test_sample_rows"):   # (librwkv_testhooks_sample.so only)
+            L.rwkv_mi_test_sample_rows.argtypes = [P_FLOAT, ctypes.c_int64, ctypes.c_int64, P_SAMPLE_PARAMS, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int, P_UINT32]
+            L.rwkv_mi_test_sample_rows.restype = ctypes.c_bool
 
     # --- rwkv.h ---------------------------------------------------------------------------------------------
 
@@ -470,6 +489,22 @@ def _u32(values) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(values, dtype=np.int64).astype(np.uint32))
 
 
+def sample_params(n: int, temperature, top_p, u=-1.0, seed=0):
+    """[n] struct rwkv_mi_sample_params; each argument is a scalar (every row) or a sequence of length n."""
+    def rows(v, what):
+        a = np.asarray(v)
+        if a.ndim == 0:
+            return [a.item()] * n
+        if a.shape != (n,):
+            raise ValueError(f"{what} must be a scalar or a sequence of length {n}")
+        return a.tolist()
+    t, p, us, sd = rows(temperature, "temperature"), rows(top_p, "top_p"), rows(u, "u"), rows(seed, "seed")
+    arr = (SampleParams * n)()
+    for i in range(n):
+        arr[i] = SampleParams(float(t[i]), float(p[i]), float(us[i]), int(sd[i]) & 0xFFFFFFFFFFFFFFFF)
+    return arr
+
+
 class RWKVBatch:
     """n_slots device-resident sequences of one model advanced together, one pass over the weights per step (rwkv_mi_batch_*).
 
@@ -533,6 +568,39 @@ class RWKVBatch:
                                                    ctypes.cast(out.ctypes.data, P_UINT32), ctypes.byref(ms)):
             self._fail("rwkv_mi_batch_decode_greedy")
         return out, float(ms.value)
+
+    def eval_sample(self, slots: List[int], tokens: List[int], temperature=1.0, top_p=0.8, u=-1.0, seed=0, want_logits: bool = False):
+        """One token per named slot in one pass, then one token sampled per row on the device: tokens [n] (and the logits [n][n_vocab]
+        when want_logits). temperature, top_p, u, seed: a scalar (every row) or a sequence of length n. u < 0 draws from the slot's
+        own stream uniform01(seed, counter of the slot)."""
+        s, t = _u32(slots), _u32(tokens)
+        if s.size != t.size:
+            raise ValueError("slots and tokens differ in length")
+        params = sample_params(s.size, temperature, top_p, u, seed)
+        out = np.empty(s.size, dtype=np.uint32)
+        logits = np.empty((s.size, self._n_vocab), dtype=np.float32) if want_logits else None
+        if not self._L.rwkv_mi_batch_eval_sample(self._ptr, s.ctypes.data_as(P_UINT32), t.ctypes.data_as(P_UINT32), s.size, params,
+                                                 out.ctypes.data_as(P_UINT32), ctypes.cast(_ptr(logits), P_FLOAT)):
+            self._fail("rwkv_mi_batch_eval_sample")
+        return (out, logits) if want_logits else out
+
+    def decode_sample(self, slots: List[int], first_tokens: List[int], n_tokens: int, temperature=1.0, top_p=0.8, seed=0) -> Tuple[np.ndarray, float]:
+        """Sampling loop on the device for every named slot (their draw counters start from 0): tokens [n][n_tokens], elapsed milliseconds."""
+        s, t = _u32(slots), _u32(first_tokens)
+        if s.size != t.size:
+            raise ValueError("slots and first_tokens differ in length")
+        params = sample_params(s.size, temperature, top_p, -1.0, seed)
+        out = np.empty((s.size, n_tokens), dtype=np.uint32)
+        ms = ctypes.c_float(0.0)
+        if not self._L.rwkv_mi_batch_decode_sample(self._ptr, s.ctypes.data_as(P_UINT32), t.ctypes.data_as(P_UINT32), s.size, n_tokens, params,
+                                                   ctypes.cast(out.ctypes.data, P_UINT32), ctypes.byref(ms)):
+            self._fail("rwkv_mi_batch_decode_sample")
+        return out, float(ms.value)
+
+    def rng_seek(self, slot: int, counter: int) -> None:
+        """Sets a slot's draw counter (0 for a new request in a reused slot)."""
+        if not self._L.rwkv_mi_batch_rng_seek(self._ptr, slot, counter):
+            self._fail("rwkv_mi_batch_rng_seek")
 
     def free(self) -> None:
         if self._ptr:

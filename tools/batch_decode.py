@@ -9,6 +9,12 @@ MODEL_PATH is written with synth.write_model (seed 42) unless it exists with its
   alg_bytes_per_step    weights once + n x (state read + write + embedding row + logits), from shapes
   step_fraction_of_8TBs that figure over the step time, as a fraction of 8 TB/s -- a figure of the whole step, not of one kernel
 and first one record with the single-stream rate measured in the same process.
+
+--sample adds, beside each greedy record, the sampling loop two ways (temperature 1.0, top-p 0.8, seed = row, the same number of steps):
+  mode batch_sample        rwkv_mi_batch_decode_sample, the loop on the device (HIP events, as the greedy loop); sampler_ms_per_step is
+                           its step minus the greedy step of the same n
+  mode batch_host_sample   what has to be done without it: RWKVBatch.eval with the logits to the host, then sample_probs of the
+                           reference's python/sampling.py restated in NumPy on each row; host clock around the loop
 """
 import argparse
 import json
@@ -22,6 +28,26 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_BS = 8.0e12
 
 
+def host_sample(logits, temperature, top_p, rng):
+    """The reference's sample_probs on one row of logits (softmax, top-p cut-off, temperature power, renormalise, draw), NumPy on the host."""
+    import numpy as np
+    x = logits - logits.max()
+    probs = np.exp(x)
+    probs /= probs.sum()
+    if top_p == 0.0:
+        top_p = 1.0
+    if temperature == 0.0:
+        return int(np.argmax(probs))
+    if top_p < 1.0:
+        sorted_probs = np.sort(probs)[::-1]
+        cutoff = float(sorted_probs[np.argmax(np.cumsum(sorted_probs) > top_p)])
+        probs[probs < cutoff] = 0
+    if temperature != 1.0:
+        probs = np.power(probs, 1.0 / temperature)
+    probs = probs / probs.sum()
+    return int(rng.choice(a=len(probs), p=probs))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("model_path")
@@ -30,6 +56,7 @@ def main():
     ap.add_argument("--n", default="1,2,4,8,16,32,64,128")
     ap.add_argument("--tokens", type=int, default=32, help="steps of each timed loop")
     ap.add_argument("--warmup", type=int, default=4, help="steps of the warm-up loop of every n")
+    ap.add_argument("--sample", action="store_true", help="also time the sampling loop: on the device, and through the host")
     args = ap.parse_args()
 
     import __graft_entry__ as graft
@@ -78,6 +105,33 @@ def main():
                "alg_bytes_per_step": alg, "step_fraction_of_8TBs": round(alg / (step_ms / 1e3) / HBM_PEAK_BS, 4),
                "steps": args.tokens, "config": args.config, "dtype": args.dtype}
         print(json.dumps(rec), flush=True)
+        if not args.sample:
+            continue
+        import numpy as np
+        first = [(7 * i + 1) % V for i in range(n)]
+        for s in slots:
+            b.state_load(s, None)
+        b.decode_sample(slots, first, args.warmup, 1.0, 0.8, slots)   # (the first sampling call allocates the sampler's scratch)
+        for s in slots:
+            b.state_load(s, None)
+        _, ms_s = b.decode_sample(slots, first, args.tokens, 1.0, 0.8, slots)
+        dev_ms = ms_s / args.tokens
+        print(json.dumps({"mode": "batch_sample", "n": n, "ms_per_step": round(dev_ms, 4), "greedy_ms_per_step": round(step_ms, 4),
+                          "sampler_ms_per_step": round(dev_ms - step_ms, 4), "tokens_per_s": round(n / (dev_ms / 1e3), 1),
+                          "temperature": 1.0, "top_p": 0.8, "steps": args.tokens, "config": args.config, "dtype": args.dtype}), flush=True)
+        rngs = [np.random.default_rng(i) for i in range(n)]
+        for s in slots:
+            b.state_load(s, None)
+        toks = list(first)
+        for timed in (False, True):
+            t0 = time.perf_counter()
+            for _ in range(args.tokens if timed else args.warmup):
+                lg = b.eval(slots, toks)
+                toks = [host_sample(lg[i], 1.0, 0.8, rngs[i]) for i in range(n)]
+            host_ms = (time.perf_counter() - t0) * 1e3 / args.tokens
+        print(json.dumps({"mode": "batch_host_sample", "n": n, "ms_per_step": round(host_ms, 4), "device_sample_ms_per_step": round(dev_ms, 4),
+                          "host_over_device": round(host_ms / dev_ms, 2), "logits_bytes_per_step": 4 * n * V,
+                          "temperature": 1.0, "top_p": 0.8, "steps": args.tokens, "config": args.config, "dtype": args.dtype}), flush=True)
     b.free()
     m.free()
 

@@ -150,7 +150,8 @@ RWKV_API void rwkv_mi_batch_free(struct rwkv_mi_batch * batch);
 RWKV_API bool rwkv_mi_batch_state_load(struct rwkv_mi_batch * batch, size_t slot, const float * state_in);
 RWKV_API bool rwkv_mi_batch_state_store(struct rwkv_mi_batch * batch, size_t slot, float * state_out);
 /* device-to-device: a context's resident state into a slot, and a slot into a context's resident state (prefill on a context, then join
- * the batch). ctx must be a single-device context of the same device and state size. */
+ * the batch; rwkv_mi_batch_eval_ragged below takes a prompt in without the extra pass). ctx must be a single-device context of the same
+ * device and state size. */
 RWKV_API bool rwkv_mi_batch_state_from_context(struct rwkv_mi_batch * batch, size_t slot, struct rwkv_context * ctx);
 RWKV_API bool rwkv_mi_batch_state_to_context(struct rwkv_mi_batch * batch, size_t slot, struct rwkv_context * ctx);
 /* One token for each of n slots in ONE pass over the weights: row i = slots[i] fed tokens[i].
@@ -182,6 +183,29 @@ RWKV_API bool rwkv_mi_batch_decode_sample(struct rwkv_mi_batch * batch, const ui
                                           uint32_t * tokens_out, float * elapsed_ms);
 /* Sets a slot's draw counter (a new request in a reused slot: 0; resuming a recorded sequence: its count). */
 RWKV_API bool rwkv_mi_batch_rng_seek(struct rwkv_mi_batch * batch, size_t slot, uint64_t counter);
+
+/* ---- Ragged passes: prompts and decode rows in one pass over the weights ----
+ * Row i of a call names slot slots[i] and feeds it lens[i] >= 1 CONSECUTIVE tokens; the pass runs all T = sum(lens) tokens in one walk over
+ * the weights. A row with lens[i] == 1 is a decode row of rwkv_mi_batch_eval; a longer one is a prompt, or a chunk of one, taken in
+ * without a separate context. tokens: the rows' tokens back to back, T words.
+ * Each named slot ends with the state rwkv_eval_sequence gives on that slot's tokens alone from its current state -- the state of repeated
+ * rwkv_eval, bit for bit -- and its logits (those of the row's LAST token) are bit-identical as well, however a prompt is cut into chunks
+ * and whoever else is in the pass. The matrix-core product path is chosen on T, not on n: 31 prompts of 2 tokens are one 62-token pass.
+ * Under the opt-in arms RWKV_MI_SEQ_Q=fast and RWKV_MI_SEQ_F16=mfma a ragged pass of T >= 32 tokens has the stated tolerance of sequence
+ * mode instead; it is not bit-identical there.
+ * Parity, untouched slots and ordering against a persistent kernel: as every batch call. Besides what rwkv_mi_batch_eval rejects, a call
+ * returns false with RWKV_ERROR_ARGS and changes no slot, parity or counter when lens is NULL, a lens[i] is 0, any of the T tokens is
+ * >= n_vocab, or the lengths add up to more than INT32_MAX. When the scratch (or the token words) for T tokens cannot be allocated it
+ * returns false with RWKV_ERROR_ALLOC and changes no slot.
+ * logits_out: [n][n_vocab] in call order, or NULL to skip the head. */
+RWKV_API bool rwkv_mi_batch_eval_ragged(struct rwkv_mi_batch * batch, const uint32_t * slots, const uint32_t * lens, const uint32_t * tokens,
+                                        size_t n, float * logits_out);
+/* The same, then one sampled token per row from that row's last-token logits, with the per-slot draw counters and the argument rules of
+ * rwkv_mi_batch_eval_sample. EVERY row is sampled: give a row that is a non-final chunk of a prompt temperature == 0 -- it is then an
+ * argmax, and an argmax does not advance its slot's draw counter, so the slot's random stream is that of its decode steps alone. */
+RWKV_API bool rwkv_mi_batch_eval_ragged_sample(struct rwkv_mi_batch * batch, const uint32_t * slots, const uint32_t * lens, const uint32_t * tokens,
+                                               size_t n, const struct rwkv_mi_sample_params * params /* [n] */, uint32_t * sampled_out,
+                                               float * logits_out);
 
 #if defined(__cplusplus)
 }

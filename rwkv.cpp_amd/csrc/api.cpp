@@ -621,6 +621,13 @@ struct rwkv_mi_batch {
     SampleRow * d_srows = nullptr;     // [n_slots]: the sampler's row table of a call (parameters + the counter of the row's slot); with its pinned
     SampleRow * h_srows = nullptr;     // staging and the sampler's scratch ([n_slots] vectors of probabilities) allocated by the first sampling call
     float * d_probs = nullptr;
+    // ragged passes (rwkv_mi_batch_eval_ragged*): the tables of a call -- segments, the short ones again, seg_of[T], last[n] -- in one device
+    // buffer with its pinned staging, grown to the largest call so far; the long segments stay on the host (each is a launch of its own)
+    uint8_t * d_seg = nullptr;
+    uint8_t * h_seg = nullptr;
+    size_t seg_cap = 0;
+    std::vector<SegState> long_segs;
+    SegPass pass;
 
     float * slot_buf(size_t slot, int p) const { return states + ((size_t) p * n_slots + slot) * (size_t) state_len; }
 };
@@ -699,6 +706,86 @@ static bool batch_upload_params(rwkv_mi_batch * B, const uint32_t * slots, const
     return true;
 }
 
+// ---- ragged passes: row i feeds lens[i] consecutive tokens to slot slots[i] ----
+
+// n, slots, lens and the sum(lens) tokens of a call: no slot changes when they are rejected. *T_out = sum(lens).
+static bool batch_check_ragged(rwkv_mi_batch * B, const uint32_t * slots, const uint32_t * lens, const uint32_t * tokens, size_t n, size_t * T_out) {
+    rwkv_context * ctx = B->ctx;
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, slots != nullptr && lens != nullptr && tokens != nullptr, "slots, lens or tokens is NULL");
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, n > 0 && n <= B->n_slots, "n (%zu) must be in 1 .. %zu", n, B->n_slots);
+    const size_t n_vocab = (size_t) ctx->model->n_vocab();
+    std::vector<uint8_t> seen(B->n_slots, 0);
+    uint64_t T = 0;
+    for (size_t i = 0; i < n; i++) {
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, slots[i] < B->n_slots, "slot %" PRIu32 " at index %zu is out of range (0 .. %zu)", slots[i], i, B->n_slots - 1);
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, !seen[slots[i]], "slot %" PRIu32 " appears twice", slots[i]);
+        seen[slots[i]] = 1;
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, lens[i] > 0, "lens[%zu] is 0", i);
+        T += lens[i];
+        // (token positions are 32-bit words of the segment table)
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, T <= (uint64_t) INT32_MAX, "the lengths add up to more than %d tokens", INT32_MAX);
+    }
+    for (size_t t = 0; t < (size_t) T; t++)
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, tokens[t] < n_vocab, "Token at index %zu (%" PRIu32 ") is out of range (0 .. %zu)", t, tokens[t], n_vocab - 1);
+    *T_out = (size_t) T;
+    return true;
+}
+
+// the token words and the tables of a ragged call, grown where needed (new buffers first: a failure leaves the batch as it was), then
+// filled and uploaded: one copy for the tables, one for the tokens
+static bool batch_upload_ragged(rwkv_mi_batch * B, const uint32_t * slots, const uint32_t * lens, const uint32_t * tokens, size_t n, size_t T) {
+    rwkv_context * ctx = B->ctx;
+    rwkv_context * run = B->run;
+    const Model & m = *ctx->model;
+    BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));   // (the previous call's copies may still read the staging)
+    if ((int64_t) T > run->d_tokens_cap) {
+        uint32_t * d = nullptr, * h = nullptr;
+        hipError_t e = hipMalloc((void **) &d, T * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipHostMalloc((void **) &h, T * sizeof(uint32_t), hipHostMallocDefault);
+        if (e != hipSuccess) { if (d) (void) hipFree(d); (void) hipGetLastError(); }
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the token words of %zu tokens: %s", T, hipGetErrorString(e));
+        (void) hipFree(run->d_tokens); (void) hipHostFree(run->h_tokens);
+        run->d_tokens = d; run->h_tokens = h; run->d_tokens_cap = run->h_tokens_cap = (int64_t) T;
+    }
+    size_t n_short = 0;
+    for (size_t i = 0; i < n; i++) if (!seg_takes_seq_kernel(m, lens[i])) n_short++;
+    const size_t off_short = n * sizeof(SegState), off_seg_of = off_short + n_short * sizeof(SegState), off_last = off_seg_of + T * sizeof(int32_t);
+    const size_t bytes = off_last + n * sizeof(int32_t);
+    if (bytes > B->seg_cap) {
+        uint8_t * d = nullptr, * h = nullptr;
+        hipError_t e = hipMalloc((void **) &d, bytes);
+        if (e == hipSuccess) e = hipHostMalloc((void **) &h, bytes, hipHostMallocDefault);
+        if (e != hipSuccess) { if (d) (void) hipFree(d); (void) hipGetLastError(); }
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the segment tables of %zu tokens: %s", T, hipGetErrorString(e));
+        if (B->d_seg) (void) hipFree(B->d_seg);
+        if (B->h_seg) (void) hipHostFree(B->h_seg);
+        B->d_seg = d; B->h_seg = h; B->seg_cap = bytes;
+    }
+    SegState * segs = (SegState *) B->h_seg, * shorts = (SegState *) (B->h_seg + off_short);
+    int32_t * seg_of = (int32_t *) (B->h_seg + off_seg_of), * last = (int32_t *) (B->h_seg + off_last);
+    B->long_segs.clear();
+    int32_t t = 0;
+    size_t k = 0;
+    for (size_t i = 0; i < n; i++) {
+        const int p = B->parity[slots[i]];
+        const SegState g{B->slot_buf(slots[i], p), B->slot_buf(slots[i], p ^ 1), t, t + (int32_t) lens[i]};
+        segs[i] = g;
+        if (seg_takes_seq_kernel(m, lens[i])) B->long_segs.push_back(g); else shorts[k++] = g;
+        for (int32_t j = g.t0; j < g.t1; j++) seg_of[j] = (int32_t) i;
+        last[i] = g.t1 - 1;
+        t = g.t1;
+    }
+    memcpy(run->h_tokens, tokens, T * sizeof(uint32_t));
+    BATCH_HIP_OK(B, hipMemcpyAsync(B->d_seg, B->h_seg, bytes, hipMemcpyHostToDevice, run->stream));
+    BATCH_HIP_OK(B, hipMemcpyAsync(run->d_tokens, run->h_tokens, T * sizeof(uint32_t), hipMemcpyHostToDevice, run->stream));
+    SegPass & ps = B->pass;
+    ps.d_segs = (const SegState *) B->d_seg; ps.d_short = (const SegState *) (B->d_seg + off_short);
+    ps.d_seg_of = (const int32_t *) (B->d_seg + off_seg_of); ps.d_last = (const int32_t *) (B->d_seg + off_last);
+    ps.h_long = B->long_segs.data();
+    ps.n = (int64_t) n; ps.n_short = (int64_t) n_short; ps.n_long = (int64_t) B->long_segs.size();
+    return true;
+}
+
 extern "C" {
 
 RWKV_API void rwkv_mi_batch_free(struct rwkv_mi_batch * B) {
@@ -714,6 +801,8 @@ RWKV_API void rwkv_mi_batch_free(struct rwkv_mi_batch * B) {
     if (B->d_srows) (void) hipFree(B->d_srows);
     if (B->h_srows) (void) hipHostFree(B->h_srows);
     if (B->d_probs) (void) hipFree(B->d_probs);
+    if (B->d_seg) (void) hipFree(B->d_seg);
+    if (B->h_seg) (void) hipHostFree(B->h_seg);
     batch_context_destroy(B->run);
     delete B;
 }
@@ -880,6 +969,46 @@ RWKV_API bool rwkv_mi_batch_eval_sample(struct rwkv_mi_batch * B, const uint32_t
     // each row's token lands in the batch's token word of that row: the 4 n bytes that go back to the host
     const RowSampler sampler{B->d_srows, B->d_probs, nullptr};
     if (!forward_rows(run, B->d_rows, (int64_t) n, true, &sampler)) { (void) hipStreamSynchronize(run->stream); return batch_fail_through(B); }
+    BATCH_HIP_OK(B, hipMemcpyAsync(run->h_tokens, run->d_tokens, n * sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream));
+    if (logits_out) BATCH_HIP_OK(B, hipMemcpyAsync(logits_out, run->d_logits, n * (size_t) ctx->model->n_vocab() * sizeof(float), hipMemcpyDeviceToHost, run->stream));
+    BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));
+    memcpy(sampled_out, run->h_tokens, n * sizeof(uint32_t));
+    for (size_t i = 0; i < n; i++) B->parity[slots[i]] ^= 1;
+    return true;
+}
+
+RWKV_API bool rwkv_mi_batch_eval_ragged(struct rwkv_mi_batch * B, const uint32_t * slots, const uint32_t * lens, const uint32_t * tokens, size_t n,
+                                        float * logits_out) {
+    rwkv_context * ctx = B->ctx;
+    ctx->last_error = RWKV_ERROR_NONE;
+    size_t T = 0;
+    if (!batch_check_ragged(B, slots, lens, tokens, n, &T)) return false;
+    rwkv_context * run = B->run;
+    run->print_errors = ctx->print_errors;
+    BATCH_HIP_OK(B, hipSetDevice(ctx->model->device));
+    if (!batch_upload_ragged(B, slots, lens, tokens, n, T)) return false;
+    if (!forward_segs(run, B->pass, (int64_t) T, logits_out != nullptr)) { (void) hipStreamSynchronize(run->stream); return batch_fail_through(B); }
+    if (logits_out) BATCH_HIP_OK(B, hipMemcpyAsync(logits_out, run->d_logits, n * (size_t) ctx->model->n_vocab() * sizeof(float), hipMemcpyDeviceToHost, run->stream));
+    BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));
+    for (size_t i = 0; i < n; i++) B->parity[slots[i]] ^= 1;
+    return true;
+}
+
+RWKV_API bool rwkv_mi_batch_eval_ragged_sample(struct rwkv_mi_batch * B, const uint32_t * slots, const uint32_t * lens, const uint32_t * tokens, size_t n,
+                                               const struct rwkv_mi_sample_params * params, uint32_t * sampled_out, float * logits_out) {
+    rwkv_context * ctx = B->ctx;
+    ctx->last_error = RWKV_ERROR_NONE;
+    size_t T = 0;
+    if (!batch_check_ragged(B, slots, lens, tokens, n, &T) || !batch_check_params(B, params, n, true)) return false;
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, sampled_out != nullptr, "sampled_out is NULL");
+    rwkv_context * run = B->run;
+    run->print_errors = ctx->print_errors;
+    BATCH_HIP_OK(B, hipSetDevice(ctx->model->device));
+    if (!batch_ensure_sampler(B)) return false;
+    if (!batch_upload_ragged(B, slots, lens, tokens, n, T) || !batch_upload_params(B, slots, params, n, false)) return false;
+    // row i's token lands in the batch's token word i (the pass has read all T of them by then): the 4 n bytes that go back to the host
+    const RowSampler sampler{B->d_srows, B->d_probs, nullptr};
+    if (!forward_segs(run, B->pass, (int64_t) T, true, &sampler)) { (void) hipStreamSynchronize(run->stream); return batch_fail_through(B); }
     BATCH_HIP_OK(B, hipMemcpyAsync(run->h_tokens, run->d_tokens, n * sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream));
     if (logits_out) BATCH_HIP_OK(B, hipMemcpyAsync(logits_out, run->d_logits, n * (size_t) ctx->model->n_vocab() * sizeof(float), hipMemcpyDeviceToHost, run->stream));
     BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));

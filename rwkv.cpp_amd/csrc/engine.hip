@@ -360,7 +360,14 @@ struct Runner {
     bool failed = false;   // a launch of the pass could not be made (allocation failure): its outputs are not valid
     // The state the pass reads / writes: the context's state[cur] -> state[cur ^ 1], or in row mode (batched decode, rwkv_mi_batch_*)
     // state.rows, where row t is its own sequence. Row mode never takes the single-token paths (persistent / fused), T == 1 included.
+    // Segment mode (ragged batch pass, seg != nullptr): state.segs / state.seg_of, the T tokens are seg->n runs of consecutive tokens, each
+    // run on its own slot. Everything between the recurrences is per token and runs over all T tokens as in sequence mode (the product
+    // path is chosen on T); the token-shift mixes take the carry per segment (k_mix_segs), the WKV recurrences run per segment. No
+    // single-token path here either.
     StateRef state;
+    const SegPass * seg = nullptr;
+    // the WKV state of the segments the _segs kernels run (seg->d_short), at offset so
+    StateRef seg_short(int64_t so) const { StateRef s = state.at(so); s.segs = seg->d_short; s.n_segs = seg->n_short; return s; }
 
     // inputs quantised ahead of their products, several per launch (sequence mode): source pointer -> tile image
     struct Pre { const float * x = nullptr; int wtype = -1; int64_t K = 0; TileAct ta; } pre[5];
@@ -377,8 +384,10 @@ struct Runner {
     }
     void drop_pre() { for (auto & e : pre) e = Pre(); }
     // tile images for n outputs of a fused mix (sequence mode, all consumers quantised with `wtype`): registered like prequant's
-    bool fused_outs(int n, float * const * keys, int wtype, TileAct * tas) {
+    // carries: the kernel that would write them takes x_prev from the row above (k_mix_seq_q) -- it has no segment form
+    bool fused_outs(int n, float * const * keys, int wtype, TileAct * tas, bool carries = true) {
         if (state.rows) return false;   // (row mode: the quantising mixes carry across rows; k_mix_rows + prequant instead)
+        if (state.segs && carries) return false;   // (segment mode: k_mix_segs + prequant; the per-token quantising kernels stay)
         if (!(dtype_quantized(wtype) && T >= k_mfma_min_tokens && b.tiles[0] && D % 256 == 0 && n <= 5)) return false;
         for (auto & e : pre) e = Pre();
         for (int i = 0; i < n; i++) { tas[i] = tile_act_at(b.tiles[i], T, D); pre[i].x = keys[i]; pre[i].wtype = wtype; pre[i].K = D; pre[i].ta = tas[i]; }
@@ -445,7 +454,7 @@ struct Runner {
     // input image itself (k_groupnorm_seq_q), the f32 values never leave the chip
     void gn_out(const LayerW & L, float eps, const float * gate) {
         TileAct ta[1]; float * keys[1] = {b.out};
-        if (fused_outs(1, keys, L.att_output->type, ta) && !ctx->prof.on &&
+        if (fused_outs(1, keys, L.att_output->type, ta, false) && !ctx->prof.on &&
             launch_groupnorm_seq_q(b.out, f(L.att_ln_x_w), f(L.att_ln_x_b), eps, gate, T, H, S, ta[0], L.att_output->type, st)) {}
         else { drop_pre(); launch_groupnorm(b.out, f(L.att_ln_x_w), f(L.att_ln_x_b), eps, gate, nullptr, nullptr, nullptr, nullptr, T, H, S, st); }
         mm(L.att_output, b.out, b.x, epi(EPI_ADD_RES, nullptr, b.x));
@@ -455,6 +464,17 @@ struct Runner {
     // (so: offset of the layer's WKV state in a state buffer)
     void wkv6(const float * r, const float * k, const float * v, const float * u, int u_per_chan, const float * w, int w_mode,
               int64_t so, float * out) {
+        if (seg) {
+            // segments of at least k_mfma_min_tokens tokens (head size 64): the lane-pipelined kernel on their token range, one launch each;
+            // all the others in one launch of the per-head form. Both perform the serial body's statements per token, so they mix freely.
+            for (int64_t i = 0; i < seg->n_long; i++) {
+                const SegState & g = seg->h_long[i];
+                const int64_t o = (int64_t) g.t0 * D;
+                launch_wkv6_seq(r + o, k + o, v + o, u, u_per_chan, w_mode == 2 ? w + o : w, w_mode, g.in + so, g.out + so, out + o, g.t1 - g.t0, H, st);
+            }
+            if (seg->n_short) launch_wkv6(r, k, v, u, u_per_chan, w, w_mode, seg_short(so), out, T, H, S, st);
+            return;
+        }
         if (!state.rows && S == 64 && T >= k_mfma_min_tokens) launch_wkv6_seq(r, k, v, u, u_per_chan, w, w_mode, state.in + so, state.out + so, out, T, H, st);
         else launch_wkv6(r, k, v, u, u_per_chan, w, w_mode, state.at(so), out, T, H, S, st);
     }
@@ -513,7 +533,7 @@ struct Runner {
         mm(L.att_receptance, b.m[2], b.r, epi(EPI_SIGMOID));
         mm(L.att_key, b.m[0], b.k);
         mm(L.att_value, b.m[1], b.v);
-        launch_wkv4(b.k, b.v, b.r, f(L.att_time_first), f(L.att_time_decay), state.at(so + 2 * D), b.out, T, D, st);
+        launch_wkv4(b.k, b.v, b.r, f(L.att_time_first), f(L.att_time_decay), seg ? seg_short(so + 2 * D) : state.at(so + 2 * D), b.out, T, D, st);
         mm(L.att_output, b.out, b.x, epi(EPI_ADD_RES, nullptr, b.x));
     }
 
@@ -561,7 +581,7 @@ struct Runner {
             const int wt = L.att_receptance->type;
             TileAct tas[5];
             if (L.att_key->type == wt && L.att_value->type == wt && L.att_gate->type == wt && L.att_time_decay_w1->type == wt &&
-                (R == 32 || R == 64) && fused_outs(5, v.out, wt, tas)) {
+                (R == 32 || R == 64) && fused_outs(5, v.out, wt, tas, false)) {
                 // sequence mode: the five mixed inputs leave the kernel as quantised tile images (their only consumers are products)
                 for (int i = 0; i < 5; i++) v.out[i] = nullptr;
                 fused_q = launch_v6_mix2_seq(v, T, D, R, st, tas, wt);
@@ -610,14 +630,22 @@ struct Runner {
             launch_v7_vmix(b.v, b.v_first, b.sx, T * D, st);
         }
         static const bool no_seq7 = getenv("RWKV_MI_NO_WKV7_SEQ") != nullptr;   // (measurement aid: the single-token form over the whole sequence)
-        if (!state.rows && S == 64 && T >= k_mfma_min_tokens && !no_seq7) launch_wkv7_seq(b.r, b.w, b.t0, b.v, b.t1, b.t2, state.in + so + 2 * D, state.out + so + 2 * D, b.out, T, H, st);
+        if (seg) {
+            for (int64_t i = 0; i < seg->n_long; i++) {   // (as wkv6: long segments on the sequence kernel, the rest in one _segs launch)
+                const SegState & g = seg->h_long[i];
+                const int64_t o = (int64_t) g.t0 * D;
+                launch_wkv7_seq(b.r + o, b.w + o, b.t0 + o, b.v + o, b.t1 + o, b.t2 + o, g.in + so + 2 * D, g.out + so + 2 * D, b.out + o, g.t1 - g.t0, H, st);
+            }
+            if (seg->n_short) launch_wkv7(b.r, b.w, b.t0, b.v, b.t1, b.t2, seg_short(so + 2 * D), b.out, T, H, S, st);
+        }
+        else if (!state.rows && S == 64 && T >= k_mfma_min_tokens && !no_seq7) launch_wkv7_seq(b.r, b.w, b.t0, b.v, b.t1, b.t2, state.in + so + 2 * D, state.out + so + 2 * D, b.out, T, H, st);
         else launch_wkv7(b.r, b.w, b.t0, b.v, b.t1, b.t2, state.at(so + 2 * D), b.out, T, H, S, st);
         launch_groupnorm(b.out, f(L.att_ln_x_w), f(L.att_ln_x_b), 64e-5f, b.g, b.t0, b.r, b.v, f(L.att_r_k), T, H, S, st);
         mm(L.att_output, b.out, b.x, epi(EPI_ADD_RES, nullptr, b.x));
     }
 
     void run_embed() {
-        if (!state.rows && T == 1 && ctx->mega && m.has_embed && ctx->mega->folds_embed()) return;   // inside the persistent launch
+        if (!state.rows && !seg && T == 1 && ctx->mega && m.has_embed && ctx->mega->folds_embed()) return;   // inside the persistent launch
         if (m.has_embed) launch_embed_ln0(*m.emb, ctx->d_tokens, T, D, f(m.ln0_w), f(m.ln0_b), b.x, st);
     }
     // layers [lb, le) of the stage (absolute layer ids); returns true when the launch also produced the logits (ring kernel, last layers)
@@ -626,7 +654,7 @@ struct Runner {
         float * sout = ctx->state[ctx->cur ^ 1];
         state.in = sin; state.out = sout;
         const int64_t per_layer = m.state_per_layer();
-        const bool one = T == 1 && !state.rows;   // (the single-token paths work on the context's own state)
+        const bool one = T == 1 && !state.rows && !seg;   // (the single-token paths work on the context's own state)
         if (one && ctx->mega) {
             const bool whole = lb == m.layer_begin && le == m.layer_end;   // (only a whole-stage launch is profiled)
             const bool head_done = want_logits && m.has_head && le == m.layer_end && ctx->mega->folds_head();
@@ -660,6 +688,14 @@ struct Runner {
             // row mode: every row is the last token of its sequence -- ln_out on all rows, one product with T rows into [T][n_vocab]
             launch_layernorm(b.x, T, D, f(m.ln_out_w), f(m.ln_out_b), b.xn, st);
             mm(m.head, b.xn, ctx->d_logits);
+            return;
+        }
+        if (seg) {
+            // segment mode: ln_out on the last token of each segment (gathered), one product with seg->n rows into [n][n_vocab]
+            launch_layernorm_gather(b.x, seg->d_last, seg->n, D, f(m.ln_out_w), f(m.ln_out_b), b.xn, st);
+            const int64_t Tsave = T; T = seg->n;
+            mm(m.head, b.xn, ctx->d_logits);
+            T = Tsave;
             return;
         }
         // ln_out on the last token only, then the head projection (rwkv_graph.inc:704-708, 851-854)
@@ -754,6 +790,32 @@ bool forward_rows(rwkv_context * ctx, const RowState * d_rows, int64_t T, bool w
     mega_chain_end(ctx);
     HIP_CTX_OK(ctx, hipGetLastError());
     RW_CTX_CHECK(ctx, RWKV_ERROR_GRAPH | RWKV_ERROR_ALLOC, false, !r.failed, "a batched product could not be launched (out of device memory for the tile-major weight image?)");
+    return true;
+}
+
+// Which recurrence a segment of `len` tokens of a ragged pass takes: the sequence kernels (k_wkv6_seq / k_wkv7_seq, head size 64) from
+// k_mfma_min_tokens tokens on, as sequence mode decides for a whole call; the per-head _segs form otherwise (RWKV-4 always).
+bool seg_takes_seq_kernel(const Model & m, int64_t len) {
+    static const bool no_seq7 = getenv("RWKV_MI_NO_WKV7_SEQ") != nullptr;
+    if (m.arch_major < 5 || m.head_size != 64 || len < k_mfma_min_tokens) return false;
+    return !(m.arch_major == 7 && no_seq7);
+}
+
+// One ragged pass of T tokens (ctx->d_tokens) in p.n segments: segment i = tokens [t0, t1) of the sequence whose state goes
+// segs[i].in -> segs[i].out. Logits: ctx->d_logits[n][n_vocab], those of each segment's last token. The pass takes the place in the
+// per-device chain that forward_rows takes, the sampler included.
+bool forward_segs(rwkv_context * ctx, const SegPass & p, int64_t T, bool want_logits, const RowSampler * sample) {
+    if (!ensure_scratch(ctx, T)) { (void) hipGetLastError(); ctx->last_error |= RWKV_ERROR_ALLOC; return false; }
+    Model & m = *ctx->model;
+    Runner r{ctx, m, ctx->stream, T, m.n_embed(), m.head_count, m.head_size, ctx->b};
+    r.seg = &p;
+    r.state.segs = p.d_segs; r.state.n_segs = p.n; r.state.seg_of = p.d_seg_of;
+    mega_chain_begin(ctx);
+    r.run(want_logits);
+    if (sample && want_logits && !r.failed) launch_sample_rows(ctx->d_logits, p.n, (int) m.n_vocab(), sample->table, sample->probs, ctx->d_tokens, sample->hist, ctx->stream);
+    mega_chain_end(ctx);
+    HIP_CTX_OK(ctx, hipGetLastError());
+    RW_CTX_CHECK(ctx, RWKV_ERROR_GRAPH | RWKV_ERROR_ALLOC, false, !r.failed, "a product of the ragged pass could not be launched (out of device memory for the tile-major weight image?)");
     return true;
 }
 

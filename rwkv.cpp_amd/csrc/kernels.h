@@ -53,17 +53,25 @@ void launch_quantize_act(const float * x, int64_t T, int64_t K, const QAct & out
 void launch_embed_ln0(const DevTensor & emb, const uint32_t * tokens, int64_t T, int64_t D, const float * w, const float * b, float * x, hipStream_t st);
 // y[t,:] = norm(x[t,:], 1e-5) * w + b                                                     (rwkv_operators.inc:93-97)
 void launch_layernorm(const float * x, int64_t T, int64_t D, const float * w, const float * b, float * y, hipStream_t st);
+// the same on n gathered rows: y[i,:] = norm(x[idx[i],:], 1e-5) * w + b   (ragged pass: the last token of each segment, in front of the head)
+void launch_layernorm_gather(const float * x, const int32_t * idx, int64_t n, int64_t D, const float * w, const float * b, float * y, hipStream_t st);
 
 // Where a recurrence (token-shift carry, WKV state) reads and writes its state component, at offset `off` of the state buffers:
-//   a sequence (rows == nullptr): token t continues from token t-1; the state goes in -> out;
-//   rows (batched decode): row t is its own sequence; its state goes rows[t].in -> rows[t].out, a device table of the rows' slots.
+//   a sequence (rows == nullptr, segs == nullptr): token t continues from token t-1; the state goes in -> out;
+//   rows (batched decode): row t is its own sequence; its state goes rows[t].in -> rows[t].out, a device table of the rows' slots;
+//   segments (ragged batch pass): tokens [t0, t1) of the pass are consecutive tokens of one sequence whose state goes segs[i].in ->
+//   segs[i].out; seg_of[t] names the segment of token t (the token-shift mixes are launched over tokens, the WKV forms over segments).
 struct RowState { const float * in; float * out; };
+struct SegState { const float * in; float * out; int32_t t0, t1; };
 struct StateRef {
     const float * in = nullptr;
     float * out = nullptr;
     const RowState * rows = nullptr;
     int64_t off = 0;
-    StateRef at(int64_t o) const { return StateRef{in, out, rows, off + o}; }
+    const SegState * segs = nullptr;    // device table of n_segs segments
+    int64_t n_segs = 0;
+    const int32_t * seg_of = nullptr;   // [T], indexes the table the mixes are given
+    StateRef at(int64_t o) const { StateRef s = *this; s.off = off + o; return s; }
 };
 
 // Token-shift mixes (rwkv_carry_x + the lerps, rwkv_graph.inc:56-82,93-109,214-241,402-413,488-501,516-521,536-538).
@@ -80,7 +88,8 @@ struct MixArgs {
     float * sx = nullptr;
     int mode = 0;
 };
-// the carry is that of `s`: a.carry_in / a.carry_out are set from it (rows: x_prev = rows[t].in[off + d], rows[t].out[off + d] = xn[t][d])
+// the carry is that of `s`: a.carry_in / a.carry_out are set from it (rows: x_prev = rows[t].in[off + d], rows[t].out[off + d] = xn[t][d];
+// segments: x_prev = t == seg.t0 ? seg.in[off + d] : xn[t-1][d], and seg.out[off + d] = xn[t][d] at t == seg.t1 - 1, seg = segs[seg_of[t]])
 void launch_mix(MixArgs a, const StateRef & s, int64_t T, int64_t D, hipStream_t st);
 
 // v6 data-dependent mix, second stage (rwkv_graph.inc:323-346): for f in (w,k,v,r,g):

@@ -808,6 +808,17 @@ __global__ __launch_bounds__(256) void k_layernorm(const float * __restrict__ x,
     block_layernorm(l_row, D, w, b, 1e-5f, y + t * D, red);
 }
 
+// n gathered rows of x (ragged pass: the last token of each segment): row idx[i] -> y[i]
+__global__ __launch_bounds__(256) void k_layernorm_gather(const float * __restrict__ x, const int32_t * __restrict__ idx, int64_t D,
+                                                          const float * __restrict__ w, const float * __restrict__ b, float * __restrict__ y) {
+    extern __shared__ __attribute__((aligned(16))) float l_row[];
+    __shared__ double red[257];
+    const int64_t t = idx[blockIdx.x];
+    for (int64_t i = threadIdx.x; i < D; i += 256) l_row[i] = x[t * D + i];
+    __syncthreads();
+    block_layernorm(l_row, D, w, b, 1e-5f, y + (int64_t) blockIdx.x * D, red);
+}
+
 void launch_embed_ln0(const DevTensor & emb, const uint32_t * tokens, int64_t T, int64_t D, const float * w, const float * b, float * x, hipStream_t st) {
     EmbView e{emb.type, emb.data, emb.qs, emb.qh, emb.sc, emb.rows()};
     hipLaunchKernelGGL(k_embed_ln0, dim3((unsigned) T), dim3(256), (size_t) D * sizeof(float), st, e, tokens, D, w, b, x);
@@ -815,6 +826,10 @@ void launch_embed_ln0(const DevTensor & emb, const uint32_t * tokens, int64_t T,
 
 void launch_layernorm(const float * x, int64_t T, int64_t D, const float * w, const float * b, float * y, hipStream_t st) {
     hipLaunchKernelGGL(k_layernorm, dim3((unsigned) T), dim3(256), (size_t) D * sizeof(float), st, x, D, w, b, y);
+}
+
+void launch_layernorm_gather(const float * x, const int32_t * idx, int64_t n, int64_t D, const float * w, const float * b, float * y, hipStream_t st) {
+    hipLaunchKernelGGL(k_layernorm_gather, dim3((unsigned) n), dim3(256), (size_t) D * sizeof(float), st, x, idx, D, w, b, y);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -853,9 +868,23 @@ __global__ __launch_bounds__(256) void k_mix_rows(MixArgs a, const RowState * __
     }
 }
 
+// segments (ragged pass): token t belongs to seg = segs[seg_of[t]]; its first token continues from the slot, its last one leaves the carry there
+__global__ __launch_bounds__(256) void k_mix_segs(MixArgs a, const SegState * __restrict__ segs, const int32_t * __restrict__ seg_of, int64_t co,
+                                                  int64_t T, int64_t D) {
+    const int64_t n = T * D;
+    for (int64_t idx = (int64_t) blockIdx.x * 256 + threadIdx.x; idx < n; idx += (int64_t) gridDim.x * 256) {
+        const int64_t t = idx / D, d = idx - t * D;
+        const SegState seg = segs[seg_of[t]];
+        const float x = a.xn[idx];
+        mix_elem(a, idx, d, x, (t == seg.t0) ? seg.in[co + d] : a.xn[idx - D]);
+        if (t == seg.t1 - 1) seg.out[co + d] = x;
+    }
+}
+
 void launch_mix(MixArgs a, const StateRef & s, int64_t T, int64_t D, hipStream_t st) {
     const int64_t n = T * D;
     const unsigned grid = (unsigned) ((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
+    if (s.segs) { hipLaunchKernelGGL(k_mix_segs, dim3(grid), dim3(256), 0, st, a, s.segs, s.seg_of, s.off, T, D); return; }
     if (s.rows) { hipLaunchKernelGGL(k_mix_rows, dim3(grid), dim3(256), 0, st, a, s.rows, s.off, T, D); return; }
     a.carry_in = s.in + s.off; a.carry_out = s.out + s.off;
     hipLaunchKernelGGL(k_mix, dim3(grid), dim3(256), 0, st, a, T, D);
@@ -885,9 +914,10 @@ void launch_v6_mix2(const V6Mix2Args & a, int64_t T, int64_t D, int64_t R, hipSt
 
 // ---------------------------------------------------------------------------------------------------------------
 // WKV recurrences. Sequential in t inside the kernel; the state stays in registers across the tokens of a call.
-// Each recurrence is one __device__ body over tokens [t0, t1) from state_in to state_out, with two entry points:
+// Each recurrence is one __device__ body over tokens [t0, t1) from state_in to state_out, with three entry points:
 //   k_wkvX       (grid H, or channel blocks for RWKV-4): one sequence, body(state_in, state_out, 0, T);
-//   k_wkvX_rows  (grid (H, T)): row t is its own sequence (batched decode), body(rows[t].in + so, rows[t].out + so, t, t + 1).
+//   k_wkvX_rows  (grid (H, T)): row t is its own sequence (batched decode), body(rows[t].in + so, rows[t].out + so, t, t + 1);
+//   k_wkvX_segs  (grid (H, n_segs)): segment i is tokens [t0, t1) of its own sequence (ragged pass), body(segs[i].in + so, segs[i].out + so, t0, t1).
 // A row therefore performs exactly the statements of one single-token step, in the same order. The bodies' pointers are plain: the
 // entry points' parameters carry __restrict__ (on the row forms' slot pointers it raised k_wkv7_rows<64> from 86 to 126 VGPRs).
 // ---------------------------------------------------------------------------------------------------------------
@@ -931,9 +961,17 @@ __global__ __launch_bounds__(256) void k_wkv4_rows(const float * __restrict__ k,
     wkv4_body(k, v, r, tf, td, rows[t].in + so, rows[t].out + so, out, t, t + 1, D);
 }
 
+__global__ __launch_bounds__(256) void k_wkv4_segs(const float * __restrict__ k, const float * __restrict__ v, const float * __restrict__ r,
+                                                   const float * __restrict__ tf, const float * __restrict__ td, const SegState * __restrict__ segs,
+                                                   int64_t so, float * __restrict__ out, int64_t D) {
+    const SegState seg = segs[blockIdx.y];
+    wkv4_body(k, v, r, tf, td, seg.in + so, seg.out + so, out, seg.t0, seg.t1, D);
+}
+
 void launch_wkv4(const float * k, const float * v, const float * r, const float * time_first, const float * time_decay,
                  const StateRef & s, float * out, int64_t T, int64_t D, hipStream_t st) {
     const unsigned nb = (unsigned) ((D + 255) / 256);
+    if (s.segs) { hipLaunchKernelGGL(k_wkv4_segs, dim3(nb, (unsigned) s.n_segs), dim3(256), 0, st, k, v, r, time_first, time_decay, s.segs, s.off, out, D); return; }
     if (s.rows) hipLaunchKernelGGL(k_wkv4_rows, dim3(nb, (unsigned) T), dim3(256), 0, st, k, v, r, time_first, time_decay, s.rows, s.off, out, D);
     else hipLaunchKernelGGL(k_wkv4, dim3(nb), dim3(256), 0, st, k, v, r, time_first, time_decay, s.in + s.off, s.out + s.off, out, T, D);
 }
@@ -1039,8 +1077,37 @@ __global__ __launch_bounds__(256) void k_wkv6_rows_generic(const float * __restr
     wkv6_body_generic(r, k, v, u, u_per_chan, w, w_mode, rows[t].in + so, rows[t].out + so, out, t, t + 1, H, S);
 }
 
+template <int S>
+__global__ __launch_bounds__(64) void k_wkv6_segs(const float * __restrict__ r, const float * __restrict__ k, const float * __restrict__ v,
+                                                  const float * __restrict__ u, int u_per_chan, const float * __restrict__ w, int w_mode,
+                                                  const SegState * __restrict__ segs, int64_t so, float * __restrict__ out, int64_t H) {
+    const SegState seg = segs[blockIdx.y];
+    wkv6_body<S>(r, k, v, u, u_per_chan, w, w_mode, seg.in + so, seg.out + so, out, seg.t0, seg.t1, H);
+}
+
+__global__ __launch_bounds__(256) void k_wkv6_segs_generic(const float * __restrict__ r, const float * __restrict__ k, const float * __restrict__ v,
+                                                           const float * __restrict__ u, int u_per_chan, const float * __restrict__ w, int w_mode,
+                                                           const SegState * __restrict__ segs, int64_t so, float * __restrict__ out, int64_t H, int64_t S) {
+    const SegState seg = segs[blockIdx.y];
+    wkv6_body_generic(r, k, v, u, u_per_chan, w, w_mode, seg.in + so, seg.out + so, out, seg.t0, seg.t1, H, S);
+}
+
 void launch_wkv6(const float * r, const float * k, const float * v, const float * u, int u_per_chan, const float * w, int w_mode,
                  const StateRef & s, float * out, int64_t T, int64_t H, int64_t S, hipStream_t st) {
+    if (s.segs) {
+        const dim3 sgrid((unsigned) H, (unsigned) s.n_segs);
+        auto go = [&](auto kern, unsigned block, auto... generic_s) {
+            hipLaunchKernelGGL(kern, sgrid, dim3(block), 0, st, r, k, v, u, u_per_chan, w, w_mode, s.segs, s.off, out, H, generic_s...);
+        };
+        switch (S) {
+            case 64: go(k_wkv6_segs<64>, 64); break;
+            case 32: go(k_wkv6_segs<32>, 64); break;
+            case 16: go(k_wkv6_segs<16>, 64); break;
+            case 8:  go(k_wkv6_segs<8>, 64); break;
+            default: go(k_wkv6_segs_generic, 256, S); break;
+        }
+        return;
+    }
     const dim3 grid((unsigned) H, s.rows ? (unsigned) T : 1u);
     auto go = [&](auto seq, auto row, unsigned block, auto... generic_s) {
         if (s.rows) hipLaunchKernelGGL(row, grid, dim3(block), 0, st, r, k, v, u, u_per_chan, w, w_mode, s.rows, s.off, out, H, generic_s...);
@@ -1154,8 +1221,35 @@ __global__ __launch_bounds__(256) void k_wkv7_rows_generic(const float * __restr
     wkv7_body_generic(r, w, k, v, a, b, rows[t].in + so, rows[t].out + so, out, t, t + 1, H, S);
 }
 
+template <int S>
+__global__ __launch_bounds__(64) void k_wkv7_segs(const float * __restrict__ r, const float * __restrict__ w, const float * __restrict__ k,
+                                                  const float * __restrict__ v, const float * __restrict__ a, const float * __restrict__ b,
+                                                  const SegState * __restrict__ segs, int64_t so, float * __restrict__ out, int64_t H) {
+    const SegState seg = segs[blockIdx.y];
+    wkv7_body<S>(r, w, k, v, a, b, seg.in + so, seg.out + so, out, seg.t0, seg.t1, H);
+}
+
+__global__ __launch_bounds__(256) void k_wkv7_segs_generic(const float * __restrict__ r, const float * __restrict__ w, const float * __restrict__ k,
+                                                           const float * __restrict__ v, const float * __restrict__ a, const float * __restrict__ b,
+                                                           const SegState * __restrict__ segs, int64_t so, float * __restrict__ out, int64_t H, int64_t S) {
+    const SegState seg = segs[blockIdx.y];
+    wkv7_body_generic(r, w, k, v, a, b, seg.in + so, seg.out + so, out, seg.t0, seg.t1, H, S);
+}
+
 void launch_wkv7(const float * r, const float * w, const float * k, const float * v, const float * a, const float * b,
                  const StateRef & s, float * out, int64_t T, int64_t H, int64_t S, hipStream_t st) {
+    if (s.segs) {
+        const dim3 sgrid((unsigned) H, (unsigned) s.n_segs);
+        auto go = [&](auto kern, unsigned block, auto... generic_s) {
+            hipLaunchKernelGGL(kern, sgrid, dim3(block), 0, st, r, w, k, v, a, b, s.segs, s.off, out, H, generic_s...);
+        };
+        switch (S) {
+            case 64: go(k_wkv7_segs<64>, 64); break;
+            case 32: go(k_wkv7_segs<32>, 64); break;
+            default: go(k_wkv7_segs_generic, 256, S); break;
+        }
+        return;
+    }
     const dim3 grid((unsigned) H, s.rows ? (unsigned) T : 1u);
     auto go = [&](auto seq, auto row, unsigned block, auto... generic_s) {
         if (s.rows) hipLaunchKernelGGL(row, grid, dim3(block), 0, st, r, w, k, v, a, b, s.rows, s.off, out, H, generic_s...);

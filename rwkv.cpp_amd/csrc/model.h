@@ -219,6 +219,18 @@ void batch_context_destroy(rwkv_context * c);
 struct RowSampler { const SampleRow * table; float * probs; uint32_t * hist; };
 bool forward_rows(rwkv_context * ctx, const RowState * d_rows, int64_t T, bool want_logits, const RowSampler * sample = nullptr);
 
+// Ragged batch pass: row i of the call is a SEGMENT, tokens [t0, t1) of the pass, consecutive tokens of one slot's sequence.
+struct SegPass {
+    const SegState * d_segs = nullptr;    // device: the n segments in call order (what d_seg_of indexes: the token-shift mixes)
+    const int32_t *  d_seg_of = nullptr;  // device: [T], the segment of each token
+    const int32_t *  d_last = nullptr;    // device: [n], the last token of each segment (the head's rows)
+    const SegState * d_short = nullptr;   // device: the n_short segments the _segs recurrences run ...
+    const SegState * h_long = nullptr;    // ... host: the n_long others, each on a sequence kernel over its token range (seg_takes_seq_kernel)
+    int64_t n = 0, n_short = 0, n_long = 0;
+};
+bool seg_takes_seq_kernel(const Model & m, int64_t len);
+bool forward_segs(rwkv_context * ctx, const SegPass & p, int64_t T, bool want_logits, const RowSampler * sample = nullptr);
+
 // fused RWKV-6 decode layer (fused_v6.hip)
 bool   fused_v6_supported(const Model & m);
 size_t fused_v6_scratch_bytes(const Model & m);

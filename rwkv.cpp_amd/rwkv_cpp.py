@@ -184,6 +184,10 @@ class RWKVSharedLibrary:
         L.rwkv_mi_batch_decode_sample.restype = ctypes.c_bool
         L.rwkv_mi_batch_rng_seek.argtypes = [c_batch, ctypes.c_size_t, ctypes.c_uint64]
         L.rwkv_mi_batch_rng_seek.restype = ctypes.c_bool
+        L.rwkv_mi_batch_eval_ragged.argtypes = [c_batch, P_UINT32, P_UINT32, P_UINT32, ctypes.c_size_t, P_FLOAT]
+        L.rwkv_mi_batch_eval_ragged.restype = ctypes.c_bool
+        L.rwkv_mi_batch_eval_ragged_sample.argtypes = [c_batch, P_UINT32, P_UINT32, P_UINT32, ctypes.c_size_t, P_SAMPLE_PARAMS, P_UINT32, P_FLOAT]
+        L.rwkv_mi_batch_eval_ragged_sample.restype = ctypes.c_bool
         if hasattr(L, "rwkv_mi_test_sample_rows"):   # (librwkv_testhooks_sample.so only)
             L.rwkv_mi_test_sample_rows.argtypes = [P_FLOAT, ctypes.c_int64, ctypes.c_int64, P_SAMPLE_PARAMS, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int, P_UINT32]
             L.rwkv_mi_test_sample_rows.restype = ctypes.c_bool
@@ -596,6 +600,41 @@ class RWKVBatch:
                                                    ctypes.cast(out.ctypes.data, P_UINT32), ctypes.byref(ms)):
             self._fail("rwkv_mi_batch_decode_sample")
         return out, float(ms.value)
+
+    @staticmethod
+    def _ragged(slots, token_lists):
+        """slots, lens and the rows' tokens back to back (the lengths are passed on as they are: an empty row is rejected by the library)"""
+        s = _u32(slots)
+        rows = [_u32(r).reshape(-1) for r in token_lists]
+        if s.size != len(rows):
+            raise ValueError("slots and token_lists differ in length")
+        lens = _u32([r.size for r in rows])
+        toks = np.ascontiguousarray(np.concatenate(rows)) if rows else _u32([])
+        return s, lens, toks
+
+    def eval_ragged(self, slots: List[int], token_lists: List[List[int]], want_logits: bool = True) -> Optional[np.ndarray]:
+        """token_lists[i] (one token or many: a prompt, or a chunk of one) to slot slots[i], all rows in ONE pass over the weights; logits
+        [n][n_vocab] of each row's last token in call order (None when want_logits is False). Every row equals rwkv_eval_sequence of its
+        tokens alone, bit for bit."""
+        s, lens, toks = self._ragged(slots, token_lists)
+        out = np.empty((s.size, self._n_vocab), dtype=np.float32) if want_logits else None
+        if not self._L.rwkv_mi_batch_eval_ragged(self._ptr, s.ctypes.data_as(P_UINT32), lens.ctypes.data_as(P_UINT32), toks.ctypes.data_as(P_UINT32),
+                                                 s.size, ctypes.cast(_ptr(out), P_FLOAT)):
+            self._fail("rwkv_mi_batch_eval_ragged")
+        return out
+
+    def eval_ragged_sample(self, slots: List[int], token_lists: List[List[int]], temperature=1.0, top_p=0.8, u=-1.0, seed=0, want_logits: bool = False):
+        """As eval_ragged, then one token sampled per row from its last-token logits on the device: tokens [n] (and the logits when
+        want_logits). The parameters as eval_sample takes them. Every row is sampled: give a non-final prompt chunk temperature 0 (an
+        argmax, which leaves the slot's draw counter where it was)."""
+        s, lens, toks = self._ragged(slots, token_lists)
+        params = sample_params(s.size, temperature, top_p, u, seed)
+        out = np.empty(s.size, dtype=np.uint32)
+        logits = np.empty((s.size, self._n_vocab), dtype=np.float32) if want_logits else None
+        if not self._L.rwkv_mi_batch_eval_ragged_sample(self._ptr, s.ctypes.data_as(P_UINT32), lens.ctypes.data_as(P_UINT32), toks.ctypes.data_as(P_UINT32),
+                                                        s.size, params, out.ctypes.data_as(P_UINT32), ctypes.cast(_ptr(logits), P_FLOAT)):
+            self._fail("rwkv_mi_batch_eval_ragged_sample")
+        return (out, logits) if want_logits else out
 
     def rng_seek(self, slot: int, counter: int) -> None:
         """Sets a slot's draw counter (0 for a new request in a reused slot)."""

@@ -15,6 +15,13 @@ and first one record with the single-stream rate measured in the same process.
                            its step minus the greedy step of the same n
   mode batch_host_sample   what has to be done without it: RWKVBatch.eval with the logits to the host, then sample_probs of the
                            reference's python/sampling.py restated in NumPy on each row; host clock around the loop
+
+--ragged times the ragged pass (rwkv_mi_batch_eval_ragged*) instead, host clock around complete calls (each ends with its stream drained),
+the smallest of --reps runs after one warm-up run of the same shape, both sides in this process and run; records also go to --out:
+  mode ragged_ingest   N prompts of L tokens: one ragged pass (logits of every prompt's last token to the host) against the way without
+                       it, N x (rwkv_mi_eval_resident on a context with its logits, then rwkv_mi_batch_state_from_context)
+  mode ragged_join     a 64-row decode step (sampled on the device, temperature 0) that also carries prompt chunks, against the same
+                       decode step alone plus the chunks pre-filled on a context and copied in
 """
 import argparse
 import json
@@ -48,6 +55,86 @@ def host_sample(logits, temperature, top_p, rng):
     return int(rng.choice(a=len(probs), p=probs))
 
 
+def ragged(pkg, m, args):
+    V = m.n_vocab
+    sink = open(args.out, "a") if args.out else None
+
+    def emit(rec):
+        rec.update({"reps": args.reps, "config": args.config, "dtype": args.dtype})
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if sink:
+            sink.write(line + "\n")
+            sink.flush()
+
+    def prompt(i, L):
+        return [(7 * i + 13 * j + 1) % V for j in range(L)]
+
+    def best(run, reset):
+        times = []
+        for k in range(args.reps + 1):   # (run 0: warm-up -- tile-major weight images, scratch growth)
+            reset()
+            t0 = time.perf_counter()
+            run()
+            times.append((time.perf_counter() - t0) * 1e3)
+        return min(times[1:])
+
+    def prefill_and_copy(b, slot, toks):
+        m.eval_resident(toks, want_logits=True)
+        b.from_context(slot, m)
+
+    b = pkg.RWKVBatch(m, 66)
+    for N in (1, 8, 32):
+        for L in (16, 128, 512):
+            slots = list(range(N))
+            prompts = [prompt(i, L) for i in slots]
+
+            def fresh():
+                for s in slots:
+                    b.state_load(s, None)
+                m.state_load(None)
+
+            def separate():
+                for i in slots:
+                    if i:
+                        m.state_load(None)   # (a new request starts from the fresh state; part of this way of doing it)
+                    prefill_and_copy(b, i, prompts[i])
+
+            r_ms = best(lambda: b.eval_ragged(slots, prompts), fresh)
+            s_ms = best(separate, fresh)
+            emit({"mode": "ragged_ingest", "N": N, "L": L, "T": N * L, "ragged_ms": round(r_ms, 3), "separate_ms": round(s_ms, 3),
+                  "separate_over_ragged": round(s_ms / r_ms, 2), "ragged_tokens_per_s": round(N * L / (r_ms / 1e3), 1)})
+
+    dec = list(range(64))
+    dec_toks = [(7 * i + 1) % V for i in dec]
+
+    def fresh_all():
+        for s in range(66):
+            b.state_load(s, None)
+        m.state_load(None)
+
+    d_ms = best(lambda: b.eval_sample(dec, dec_toks, 0.0, 0.8, -1.0, 0), fresh_all)
+    for chunks in ([64], [512], [64, 512]):
+        extra = list(range(64, 64 + len(chunks)))
+        rows = [[t] for t in dec_toks] + [prompt(s, L) for s, L in zip(extra, chunks)]
+
+        def separate():
+            b.eval_sample(dec, dec_toks, 0.0, 0.8, -1.0, 0)
+            for s, L in zip(extra, chunks):
+                if s != extra[0]:
+                    m.state_load(None)
+                prefill_and_copy(b, s, prompt(s, L))
+
+        r_ms = best(lambda: b.eval_ragged_sample(dec + extra, rows, 0.0, 0.8, -1.0, 0), fresh_all)
+        s_ms = best(separate, fresh_all)
+        emit({"mode": "ragged_join", "decode_rows": 64, "chunks": chunks, "T": 64 + sum(chunks), "decode_step_alone_ms": round(d_ms, 3),
+              "ragged_ms": round(r_ms, 3), "chunk_cost_in_the_pass_ms": round(r_ms - d_ms, 3), "separate_ms": round(s_ms, 3),
+              "chunk_cost_separate_ms": round(s_ms - d_ms, 3), "separate_over_ragged": round(s_ms / r_ms, 2)})
+    b.free()
+    if sink:
+        sink.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("model_path")
@@ -57,6 +144,9 @@ def main():
     ap.add_argument("--tokens", type=int, default=32, help="steps of each timed loop")
     ap.add_argument("--warmup", type=int, default=4, help="steps of the warm-up loop of every n")
     ap.add_argument("--sample", action="store_true", help="also time the sampling loop: on the device, and through the host")
+    ap.add_argument("--ragged", action="store_true", help="time the ragged pass: prompt ingestion and joining a decode step (see above)")
+    ap.add_argument("--reps", type=int, default=3, help="--ragged: timed runs of each shape (the smallest is reported)")
+    ap.add_argument("--out", default=None, help="--ragged: also append the records to this file")
     args = ap.parse_args()
 
     import __graft_entry__ as graft
@@ -75,6 +165,10 @@ def main():
     pkg.build_library()
     lib = pkg.load_rwkv_shared_library()
     m = pkg.RWKVModel(lib, args.model_path, thread_count=1, gpu_layer_count=99)
+    if args.ragged:
+        ragged(pkg, m, args)
+        m.free()
+        return
     ns = [int(x) for x in args.n.split(",")]
     V, D, state_len = m.n_vocab, m.n_embed, m.state_len
     weight_bytes = int(lib.library.rwkv_mi_weight_bytes(m._ctx.ptr))

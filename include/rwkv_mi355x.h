@@ -207,6 +207,62 @@ RWKV_API bool rwkv_mi_batch_eval_ragged_sample(struct rwkv_mi_batch * batch, con
                                                size_t n, const struct rwkv_mi_sample_params * params /* [n] */, uint32_t * sampled_out,
                                                float * logits_out);
 
+/* ---- Presence / frequency penalties and logit bias in the device sampler ----
+ * What the reference's chat program does before every draw (chat_with_bot.py:243-258: for each token n generated so far in this response,
+ * logits[n] -= PRESENCE_PENALTY + token_counts[n] * FREQUENCY_PENALTY, defaults 0.2 / 0.2) and what sample_logits' logit_bias adds
+ * (sampling.py:27-36; chat_with_bot.py:78,233 forbids a newline with it), on the device, between the head and the next embedding lookup.
+ * Per sequence -- per slot of a batch, or per context -- the device keeps two tables:
+ *   count[n_vocab]  uint32, the OCCURRENCE TABLE, zero at creation;
+ *   bias[n_vocab]   float, the BIAS TABLE, absent until set.
+ * A penalised draw reads, instead of the logit l[j],
+ *   adj[j] = (l[j] - (presence + (float) count[j] * frequency)) + bias[j]
+ * every operation rounded to f32 in that order, no contraction (the reference's order: the penalty is taken from the logits, then
+ * sample_probs adds the bias). As the reference's loop runs over the tokens that HAVE occurred, the penalty is taken where count[j] > 0
+ * only: a token that has not occurred keeps l[j] (+ bias[j]); the presence penalty is what separates the two. The bias add is skipped
+ * for a sequence without a bias. A count is exact as a float below 2^24.
+ * Everything after that is the sampler of rwkv_mi_sample: softmax, top-p cut-off, temperature power, draw, and the draw-counter rule.
+ * When the row's `record` is non-zero the chosen token's count goes up by one AFTER the draw, argmax or not: the draw of step i sees the
+ * counts of the steps before it. A row with record == 0 updates nothing -- give a non-final prompt chunk of a ragged pass
+ * temperature == 0 AND record == 0. The logits are never modified: logits_out and rwkv_mi_logits_store return the model's logits.
+ * With presence == frequency == 0 and no bias, adj[j] == l[j] bit for bit and the token is the one the plain call picks.
+ * The calls above (rwkv_mi_sample, rwkv_mi_batch_eval_sample, ...) never read or touch counts or bias.
+ * THE TWO PENALISED LOOPS CONTINUE: they reset neither the counts nor the draw counters, and every step records (penalties[i].record is
+ * not read there). A new request calls counts_reset and rng_seek(.., 0) first; decoding 16 + 16 tokens equals decoding 32, bit for bit.
+ * Batches allocate their tables ([n_slots][n_vocab] each) on the first call of this family (RWKV_ERROR_ALLOC when they cannot be),
+ * contexts likewise; rwkv_mi_batch_free / rwkv_free release them. Not on RWKV_MI_DEVICES chains.
+ * Besides what their plain counterparts reject, these calls return false with RWKV_ERROR_ARGS and change no slot, parity, draw counter,
+ * count or bias when penalties is NULL, a presence or frequency is not finite, a bias id is >= n_vocab or repeated, a bias value is NaN
+ * or +inf (-inf and large negatives such as the chat program's -999999999 are allowed), a token of counts_add is >= n_vocab, or a slot
+ * is out of range. */
+struct rwkv_mi_penalty_params { float presence; float frequency; uint32_t record; };   /* 12 bytes */
+RWKV_API bool rwkv_mi_batch_counts_reset(struct rwkv_mi_batch * batch, size_t slot);
+/* count[tokens[i]] += 1 for each of the n tokens (resuming a recorded response); n == 0 changes nothing */
+RWKV_API bool rwkv_mi_batch_counts_add(struct rwkv_mi_batch * batch, size_t slot, const uint32_t * tokens, size_t n);
+RWKV_API bool rwkv_mi_batch_counts_store(struct rwkv_mi_batch * batch, size_t slot, uint32_t * counts_out /* [n_vocab] */);
+/* REPLACES the slot's bias by bias[ids[i]] = values[i], zero elsewhere; n == 0 clears it (the slot has no bias again) */
+RWKV_API bool rwkv_mi_batch_logit_bias_set(struct rwkv_mi_batch * batch, size_t slot, const uint32_t * ids, const float * values, size_t n);
+/* rwkv_mi_batch_eval_sample / _eval_ragged_sample / _decode_sample with the penalised draw; penalties: [n], one row per row of the call */
+RWKV_API bool rwkv_mi_batch_eval_sample_penalized(struct rwkv_mi_batch * batch, const uint32_t * slots, const uint32_t * tokens, size_t n,
+                                                  const struct rwkv_mi_sample_params * params /* [n] */, const struct rwkv_mi_penalty_params * penalties /* [n] */,
+                                                  uint32_t * sampled_out, float * logits_out);
+RWKV_API bool rwkv_mi_batch_eval_ragged_sample_penalized(struct rwkv_mi_batch * batch, const uint32_t * slots, const uint32_t * lens, const uint32_t * tokens,
+                                                         size_t n, const struct rwkv_mi_sample_params * params /* [n] */,
+                                                         const struct rwkv_mi_penalty_params * penalties /* [n] */, uint32_t * sampled_out, float * logits_out);
+RWKV_API bool rwkv_mi_batch_decode_sample_penalized(struct rwkv_mi_batch * batch, const uint32_t * slots, const uint32_t * first_tokens, size_t n,
+                                                    size_t n_tokens, const struct rwkv_mi_sample_params * params /* [n] */,
+                                                    const struct rwkv_mi_penalty_params * penalties /* [n] */, uint32_t * tokens_out, float * elapsed_ms);
+/* The single context: one occurrence table and one bias table per context (a clone has its own), the same rules. */
+RWKV_API bool rwkv_mi_counts_reset(struct rwkv_context * ctx);
+RWKV_API bool rwkv_mi_counts_add(struct rwkv_context * ctx, const uint32_t * tokens, size_t n);
+RWKV_API bool rwkv_mi_counts_store(struct rwkv_context * ctx, uint32_t * counts_out /* [n_vocab] */);
+RWKV_API bool rwkv_mi_logit_bias_set(struct rwkv_context * ctx, const uint32_t * ids, const float * values, size_t n);
+/* Sets the context's draw counter (rwkv_mi_decode_sample resets it to 0 itself; the penalised loop does not). */
+RWKV_API bool rwkv_mi_rng_seek(struct rwkv_context * ctx, uint64_t counter);
+RWKV_API bool rwkv_mi_sample_penalized(struct rwkv_context * ctx, float temperature, float top_p, float u, uint64_t seed,
+                                       float presence, float frequency, uint32_t record, uint32_t * token_out);
+RWKV_API bool rwkv_mi_decode_sample_penalized(struct rwkv_context * ctx, uint32_t first_token, size_t n_tokens, float temperature, float top_p, uint64_t seed,
+                                              float presence, float frequency, uint32_t * tokens_out, float * elapsed_ms);
+
 #if defined(__cplusplus)
 }
 #endif

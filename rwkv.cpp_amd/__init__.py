@@ -6,6 +6,7 @@ repo root to sys.path and use `importlib.import_module("rwkv.cpp_amd")` is NOT p
 from .rwkv_cpp import (  # noqa: F401
     HOOKS_LIB_PATH,
     LIB_PATH,
+    PenaltyParams,
     RWKVBatch,
     RWKVContext,
     RWKVModel,
@@ -14,5 +15,6 @@ from .rwkv_cpp import (  # noqa: F401
     SampleParams,
     build_library,
     load_rwkv_shared_library,
+    penalty_params,
     sample_params,
 )

@@ -4,6 +4,7 @@
 #include "rwkv_mi355x.h"
 
 #include <cinttypes>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -373,6 +374,184 @@ RWKV_API bool rwkv_mi_decode_sample(struct rwkv_context * ctx, uint32_t first_to
     return true;
 }
 
+// ---- penalised sampling (rwkv_mi_*_penalized, rwkv_mi_*counts_*, rwkv_mi_*logit_bias_set): what contexts and batches share ----
+
+// the arguments of counts_add / logit_bias_set / a penalty (checked before anything changes; errors are reported on ctx)
+static bool check_count_tokens(rwkv_context * ctx, const uint32_t * tokens, size_t n) {
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, tokens != nullptr || n == 0, "tokens is NULL");
+    const size_t n_vocab = (size_t) ctx->model->n_vocab();
+    for (size_t i = 0; i < n; i++)
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, tokens[i] < n_vocab, "Token at index %zu (%" PRIu32 ") is out of range (0 .. %zu)", i, tokens[i], n_vocab - 1);
+    return true;
+}
+
+static bool check_bias(rwkv_context * ctx, const uint32_t * ids, const float * values, size_t n) {
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, n == 0 || (ids != nullptr && values != nullptr), "ids or values is NULL");
+    const size_t n_vocab = (size_t) ctx->model->n_vocab();
+    std::vector<uint8_t> seen(n ? n_vocab : 0, 0);
+    for (size_t i = 0; i < n; i++) {
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, ids[i] < n_vocab, "bias id at index %zu (%" PRIu32 ") is out of range (0 .. %zu)", i, ids[i], n_vocab - 1);
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, !seen[ids[i]], "bias id %" PRIu32 " appears twice", ids[i]);
+        seen[ids[i]] = 1;
+        // (NaN fails the comparison; -inf and large negatives forbid a token and are allowed)
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, values[i] < INFINITY, "bias value at index %zu (%g) is NaN or +inf", i, (double) values[i]);
+    }
+    return true;
+}
+
+static bool check_penalty(rwkv_context * ctx, float presence, float frequency, size_t index) {
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, std::isfinite(presence) && std::isfinite(frequency),
+                 "the penalty at index %zu is not finite (presence %g, frequency %g)", index, (double) presence, (double) frequency);
+    return true;
+}
+
+// host words into a temporary device buffer on `st`; freed on scope exit (after the caller has drained the stream)
+struct DevWords {
+    void * p = nullptr;
+    ~DevWords() { if (p) (void) hipFree(p); }
+    bool upload(const void * src, size_t bytes, hipStream_t st) {
+        return hipMalloc(&p, bytes) == hipSuccess && hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, st) == hipSuccess;
+    }
+};
+
+// count[tokens[i]] += 1 on the device (arguments checked); drains st
+static bool table_counts_add(rwkv_context * ctx, uint32_t * count, const uint32_t * tokens, size_t n, hipStream_t st) {
+    if (n == 0) return true;
+    DevWords d;
+    bool ok = d.upload(tokens, n * sizeof(uint32_t), st);
+    if (ok) launch_count_add(count, (const uint32_t *) d.p, (int64_t) n, (int) ctx->model->n_vocab(), st);
+    ok = ok && hipGetLastError() == hipSuccess;
+    ok = hipStreamSynchronize(st) == hipSuccess && ok;
+    RW_CTX_CHECK(ctx, RWKV_ERROR_GRAPH, false, ok, "HIP error: %s", hipGetErrorString(hipGetLastError()));
+    return true;
+}
+
+// bias = 0, then bias[ids[i]] = values[i] on the device (arguments checked, n > 0); drains st
+static bool table_bias_set(rwkv_context * ctx, float * bias, const uint32_t * ids, const float * values, size_t n, hipStream_t st) {
+    const int64_t n_vocab = ctx->model->n_vocab();
+    DevWords di, dv;
+    bool ok = di.upload(ids, n * sizeof(uint32_t), st) && dv.upload(values, n * sizeof(float), st) &&
+              hipMemsetAsync(bias, 0, (size_t) n_vocab * sizeof(float), st) == hipSuccess;
+    if (ok) launch_bias_scatter(bias, (const uint32_t *) di.p, (const float *) dv.p, (int64_t) n, (int) n_vocab, st);
+    ok = ok && hipGetLastError() == hipSuccess;
+    ok = hipStreamSynchronize(st) == hipSuccess && ok;
+    RW_CTX_CHECK(ctx, RWKV_ERROR_GRAPH, false, ok, "HIP error: %s", hipGetErrorString(hipGetLastError()));
+    return true;
+}
+
+// the context's occurrence and bias tables: on the first call of the family
+static bool ensure_penalty(rwkv_context * ctx) {
+    const size_t V = (size_t) ctx->model->n_vocab();
+    for (void ** t : {(void **) &ctx->d_counts, (void **) &ctx->d_bias}) {
+        if (*t) continue;
+        void * d = nullptr;
+        hipError_t e = hipMalloc(&d, V * 4);
+        if (e != hipSuccess) (void) hipGetLastError();
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the penalty tables: %s", hipGetErrorString(e));
+        e = hipMemsetAsync(d, 0, V * 4, ctx->stream);
+        if (e != hipSuccess) (void) hipFree(d);
+        HIP_CTX_OK(ctx, e);
+        *t = d;
+    }
+    return true;
+}
+
+// what every call of the single-context family starts with
+static bool penalty_call(rwkv_context * ctx) {
+    ctx->last_error = RWKV_ERROR_NONE;
+    RW_NO_PIPELINE(ctx, false);
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, ctx->model->has_head, "this stage has no head");
+    return true;
+}
+
+RWKV_API bool rwkv_mi_counts_reset(struct rwkv_context * ctx) {
+    if (!penalty_call(ctx)) return false;
+    HIP_CTX_OK(ctx, hipSetDevice(ctx->model->device));
+    if (!ensure_penalty(ctx)) return false;
+    HIP_CTX_OK(ctx, hipMemsetAsync(ctx->d_counts, 0, (size_t) ctx->model->n_vocab() * sizeof(uint32_t), ctx->stream));
+    HIP_CTX_OK(ctx, hipStreamSynchronize(ctx->stream));
+    return true;
+}
+
+RWKV_API bool rwkv_mi_counts_add(struct rwkv_context * ctx, const uint32_t * tokens, size_t n) {
+    if (!penalty_call(ctx) || !check_count_tokens(ctx, tokens, n)) return false;
+    HIP_CTX_OK(ctx, hipSetDevice(ctx->model->device));
+    if (!ensure_penalty(ctx)) return false;
+    return table_counts_add(ctx, ctx->d_counts, tokens, n, ctx->stream);
+}
+
+RWKV_API bool rwkv_mi_counts_store(struct rwkv_context * ctx, uint32_t * counts_out) {
+    if (!penalty_call(ctx)) return false;
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, counts_out != nullptr, "counts_out is NULL");
+    HIP_CTX_OK(ctx, hipSetDevice(ctx->model->device));
+    if (!ensure_penalty(ctx)) return false;
+    HIP_CTX_OK(ctx, hipMemcpyAsync(counts_out, ctx->d_counts, (size_t) ctx->model->n_vocab() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_CTX_OK(ctx, hipStreamSynchronize(ctx->stream));
+    return true;
+}
+
+RWKV_API bool rwkv_mi_logit_bias_set(struct rwkv_context * ctx, const uint32_t * ids, const float * values, size_t n) {
+    if (!penalty_call(ctx) || !check_bias(ctx, ids, values, n)) return false;
+    HIP_CTX_OK(ctx, hipSetDevice(ctx->model->device));
+    if (!ensure_penalty(ctx)) return false;
+    if (n == 0) { HIP_CTX_OK(ctx, hipStreamSynchronize(ctx->stream)); ctx->has_bias = false; return true; }
+    ctx->has_bias = true;   // (a failure below leaves a table that is cleared or half written: it is not read as "no bias")
+    return table_bias_set(ctx, ctx->d_bias, ids, values, n, ctx->stream);
+}
+
+RWKV_API bool rwkv_mi_rng_seek(struct rwkv_context * ctx, uint64_t counter) {
+    ctx->last_error = RWKV_ERROR_NONE;
+    RW_NO_PIPELINE(ctx, false);
+    HIP_CTX_OK(ctx, hipSetDevice(ctx->model->device));
+    if (!ensure_sampler(ctx)) return false;
+    const unsigned long long v = counter;
+    HIP_CTX_OK(ctx, hipMemcpyAsync(ctx->d_rng_counter, &v, sizeof(v), hipMemcpyHostToDevice, ctx->stream));
+    HIP_CTX_OK(ctx, hipStreamSynchronize(ctx->stream));
+    return true;
+}
+
+// rwkv_mi_sample on the adjusted logits (the context's counts and bias); record: the chosen token is counted
+RWKV_API bool rwkv_mi_sample_penalized(struct rwkv_context * ctx, float temperature, float top_p, float u, uint64_t seed,
+                                       float presence, float frequency, uint32_t record, uint32_t * token_out) {
+    if (!penalty_call(ctx)) return false;
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, temperature >= 0.0f && top_p >= 0.0f && top_p <= 1.0f && u < 1.0f && token_out, "bad sampling arguments");
+    if (!check_penalty(ctx, presence, frequency, 0)) return false;
+    HIP_CTX_OK(ctx, hipSetDevice(ctx->model->device));
+    if (!ensure_sampler(ctx) || !ensure_penalty(ctx)) return false;
+    launch_pen_sample(ctx->d_logits, (int) ctx->model->n_vocab(), temperature, top_p, u, seed, ctx->d_rng_counter, presence, frequency, record,
+                      ctx->d_counts, ctx->has_bias ? ctx->d_bias : nullptr, ctx->d_probs, ctx->d_next_token, nullptr, 0, ctx->stream);
+    HIP_CTX_OK(ctx, hipMemcpyAsync(token_out, ctx->d_next_token, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_CTX_OK(ctx, hipStreamSynchronize(ctx->stream));
+    return true;
+}
+
+// rwkv_mi_decode_sample with the penalised draw, every step recorded. It CONTINUES: neither the counts nor the draw counter are reset.
+RWKV_API bool rwkv_mi_decode_sample_penalized(struct rwkv_context * ctx, uint32_t first_token, size_t n_tokens, float temperature, float top_p, uint64_t seed,
+                                              float presence, float frequency, uint32_t * tokens_out, float * elapsed_ms) {
+    if (!penalty_call(ctx)) return false;
+    const size_t n_vocab = (size_t) ctx->model->n_vocab();
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, first_token < n_vocab && n_tokens > 0, "bad arguments");
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, temperature >= 0.0f && top_p >= 0.0f && top_p <= 1.0f, "bad sampling arguments");
+    if (!check_penalty(ctx, presence, frequency, 0)) return false;
+    HIP_CTX_OK(ctx, hipSetDevice(ctx->model->device));
+    if (!ensure_sampler(ctx) || !ensure_penalty(ctx) || !upload_tokens(ctx, &first_token, 1)) return false;
+    struct DevBuf { uint32_t * p = nullptr; ~DevBuf() { if (p) (void) hipFree(p); } } hist;
+    HIP_CTX_OK(ctx, hipMalloc((void **) &hist.p, n_tokens * sizeof(uint32_t)));
+    HIP_CTX_OK(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_CTX_OK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    const float * bias = ctx->has_bias ? ctx->d_bias : nullptr;
+    for (size_t i = 0; i < n_tokens; i++) {
+        if (!forward_decode(ctx, true)) return false;
+        launch_pen_sample(ctx->d_logits, (int) n_vocab, temperature, top_p, -1.0f, seed, ctx->d_rng_counter, presence, frequency, 1u, ctx->d_counts, bias,
+                          ctx->d_probs, ctx->d_tokens, hist.p, (int) i, ctx->stream);
+    }
+    HIP_CTX_OK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+    if (tokens_out) HIP_CTX_OK(ctx, hipMemcpyAsync(tokens_out, hist.p, n_tokens * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (!fetch_outputs(ctx, nullptr, nullptr)) return false;
+    if (elapsed_ms) HIP_CTX_OK(ctx, hipEventElapsedTime(elapsed_ms, ctx->ev0, ctx->ev1));
+    return true;
+}
+
 // Eager (graph-free) greedy decode with a HIP-event pair around every launch of the dominant kernel.
 // out[0] = summed kernel time (ms), out[1] = launches, out[2] = summed algorithmic bytes, out[3] = wall ms of the loop.
 RWKV_API bool rwkv_mi_profile_decode(struct rwkv_context * ctx, uint32_t first_token, size_t n_tokens, double * out) {
@@ -621,6 +800,13 @@ struct rwkv_mi_batch {
     SampleRow * d_srows = nullptr;     // [n_slots]: the sampler's row table of a call (parameters + the counter of the row's slot); with its pinned
     SampleRow * h_srows = nullptr;     // staging and the sampler's scratch ([n_slots] vectors of probabilities) allocated by the first sampling call
     float * d_probs = nullptr;
+    // penalised sampling (rwkv_mi_batch_*_penalized): one occurrence table and one bias table per slot, [n_slots][n_vocab] each, and the penalised
+    // row table of a call with its pinned staging -- allocated by the first call of that family. has_bias[slot]: a bias has been set and not cleared
+    uint32_t * d_counts = nullptr;
+    float * d_bias = nullptr;
+    std::vector<uint8_t> has_bias;
+    PenaltyRow * d_prows = nullptr;
+    PenaltyRow * h_prows = nullptr;
     // ragged passes (rwkv_mi_batch_eval_ragged*): the tables of a call -- segments, the short ones again, seg_of[T], last[n] -- in one device
     // buffer with its pinned staging, grown to the largest call so far; the long segments stay on the host (each is a launch of its own)
     uint8_t * d_seg = nullptr;
@@ -703,6 +889,57 @@ static bool batch_upload_params(rwkv_mi_batch * B, const uint32_t * slots, const
         if (generator_only) B->h_srows[i].p.u = -1.0f;
     }
     BATCH_HIP_OK(B, hipMemcpyAsync(B->d_srows, B->h_srows, n * sizeof(SampleRow), hipMemcpyHostToDevice, B->run->stream));
+    return true;
+}
+
+// the penalties of a call (checked with the other arguments, before anything changes)
+static bool batch_check_penalties(rwkv_mi_batch * B, const rwkv_mi_penalty_params * penalties, size_t n) {
+    RW_CTX_CHECK(B->ctx, RWKV_ERROR_ARGS, false, penalties != nullptr, "penalties is NULL");
+    for (size_t i = 0; i < n; i++) if (!check_penalty(B->ctx, penalties[i].presence, penalties[i].frequency, i)) return false;
+    return true;
+}
+
+// the slots' occurrence and bias tables (zeroed), the penalised row table and the sampler's scratch: on the first call of the family
+static bool batch_ensure_penalty(rwkv_mi_batch * B) {
+    rwkv_context * ctx = B->ctx;
+    if (!batch_ensure_sampler(B)) return false;
+    const size_t words = B->n_slots * (size_t) ctx->model->n_vocab();
+    hipError_t e = hipSuccess;
+    for (void ** t : {(void **) &B->d_counts, (void **) &B->d_bias}) {
+        if (*t || e != hipSuccess) continue;
+        void * d = nullptr;
+        e = hipMalloc(&d, words * 4);
+        if (e != hipSuccess) break;
+        if (hipMemsetAsync(d, 0, words * 4, B->run->stream) != hipSuccess || hipStreamSynchronize(B->run->stream) != hipSuccess) { (void) hipFree(d); e = hipErrorOutOfMemory; break; }
+        *t = d;
+    }
+    if (e == hipSuccess && !B->d_prows) e = hipMalloc((void **) &B->d_prows, B->n_slots * sizeof(PenaltyRow));
+    if (e == hipSuccess && !B->h_prows) e = hipHostMalloc((void **) &B->h_prows, B->n_slots * sizeof(PenaltyRow), hipHostMallocDefault);
+    if (e != hipSuccess) (void) hipGetLastError();
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the penalty tables of %zu slots: %s", B->n_slots, hipGetErrorString(e));
+    return true;
+}
+
+// the penalised row table of the n named slots (after batch_upload: the stream has been drained, the staging is free). loop: the generator
+// draws and every step records
+static bool batch_upload_penalty_rows(rwkv_mi_batch * B, const uint32_t * slots, const rwkv_mi_sample_params * params, const rwkv_mi_penalty_params * penalties,
+                                      size_t n, bool loop) {
+    const size_t V = (size_t) B->ctx->model->n_vocab();
+    for (size_t i = 0; i < n; i++) {
+        const size_t s = slots[i];
+        B->h_prows[i] = PenaltyRow{params[i], B->d_counters + s, penalties[i].presence, penalties[i].frequency, loop ? 1u : penalties[i].record,
+                                   B->d_counts + s * V, B->has_bias[s] ? B->d_bias + s * V : nullptr};
+        if (loop) B->h_prows[i].p.u = -1.0f;
+    }
+    BATCH_HIP_OK(B, hipMemcpyAsync(B->d_prows, B->h_prows, n * sizeof(PenaltyRow), hipMemcpyHostToDevice, B->run->stream));
+    return true;
+}
+
+// what the calls on one slot's tables start with
+static bool batch_slot_call(rwkv_mi_batch * B, size_t slot) {
+    rwkv_context * ctx = B->ctx;
+    ctx->last_error = RWKV_ERROR_NONE;
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, slot < B->n_slots, "slot %zu is out of range", slot);
     return true;
 }
 
@@ -801,6 +1038,10 @@ RWKV_API void rwkv_mi_batch_free(struct rwkv_mi_batch * B) {
     if (B->d_srows) (void) hipFree(B->d_srows);
     if (B->h_srows) (void) hipHostFree(B->h_srows);
     if (B->d_probs) (void) hipFree(B->d_probs);
+    if (B->d_counts) (void) hipFree(B->d_counts);
+    if (B->d_bias) (void) hipFree(B->d_bias);
+    if (B->d_prows) (void) hipFree(B->d_prows);
+    if (B->h_prows) (void) hipHostFree(B->h_prows);
     if (B->d_seg) (void) hipFree(B->d_seg);
     if (B->h_seg) (void) hipHostFree(B->h_seg);
     batch_context_destroy(B->run);
@@ -820,6 +1061,7 @@ RWKV_API struct rwkv_mi_batch * rwkv_mi_batch_create(struct rwkv_context * ctx, 
     B->n_slots = n_slots;
     B->state_len = m.state_len();
     B->parity.assign(n_slots, 0);
+    B->has_bias.assign(n_slots, 0);
     RW_CTX_CHECK(ctx, RWKV_ERROR_GRAPH, nullptr, hipSetDevice(m.device) == hipSuccess, "hipSetDevice failed");
     B->run = batch_context_create(&m, (int64_t) n_slots);
     RW_CTX_CHECK(ctx, RWKV_ERROR_CTX | RWKV_ERROR_ALLOC, nullptr, B->run != nullptr, "cannot create the batch's stream / buffers (device memory?)");
@@ -1060,6 +1302,122 @@ RWKV_API bool rwkv_mi_batch_rng_seek(struct rwkv_mi_batch * B, size_t slot, uint
     const unsigned long long v = counter;
     BATCH_HIP_OK(B, hipMemcpyAsync(B->d_counters + slot, &v, sizeof(v), hipMemcpyHostToDevice, st));
     BATCH_HIP_OK(B, hipStreamSynchronize(st));
+    return true;
+}
+
+RWKV_API bool rwkv_mi_batch_counts_reset(struct rwkv_mi_batch * B, size_t slot) {
+    if (!batch_slot_call(B, slot)) return false;
+    BATCH_HIP_OK(B, hipSetDevice(B->ctx->model->device));
+    if (!batch_ensure_penalty(B)) return false;
+    const size_t V = (size_t) B->ctx->model->n_vocab();
+    BATCH_HIP_OK(B, hipMemsetAsync(B->d_counts + slot * V, 0, V * sizeof(uint32_t), B->run->stream));
+    BATCH_HIP_OK(B, hipStreamSynchronize(B->run->stream));
+    return true;
+}
+
+RWKV_API bool rwkv_mi_batch_counts_add(struct rwkv_mi_batch * B, size_t slot, const uint32_t * tokens, size_t n) {
+    if (!batch_slot_call(B, slot) || !check_count_tokens(B->ctx, tokens, n)) return false;
+    BATCH_HIP_OK(B, hipSetDevice(B->ctx->model->device));
+    if (!batch_ensure_penalty(B)) return false;
+    return table_counts_add(B->ctx, B->d_counts + slot * (size_t) B->ctx->model->n_vocab(), tokens, n, B->run->stream);
+}
+
+RWKV_API bool rwkv_mi_batch_counts_store(struct rwkv_mi_batch * B, size_t slot, uint32_t * counts_out) {
+    if (!batch_slot_call(B, slot)) return false;
+    RW_CTX_CHECK(B->ctx, RWKV_ERROR_ARGS, false, counts_out != nullptr, "counts_out is NULL");
+    BATCH_HIP_OK(B, hipSetDevice(B->ctx->model->device));
+    if (!batch_ensure_penalty(B)) return false;
+    const size_t V = (size_t) B->ctx->model->n_vocab();
+    BATCH_HIP_OK(B, hipMemcpyAsync(counts_out, B->d_counts + slot * V, V * sizeof(uint32_t), hipMemcpyDeviceToHost, B->run->stream));
+    BATCH_HIP_OK(B, hipStreamSynchronize(B->run->stream));
+    return true;
+}
+
+RWKV_API bool rwkv_mi_batch_logit_bias_set(struct rwkv_mi_batch * B, size_t slot, const uint32_t * ids, const float * values, size_t n) {
+    if (!batch_slot_call(B, slot) || !check_bias(B->ctx, ids, values, n)) return false;
+    BATCH_HIP_OK(B, hipSetDevice(B->ctx->model->device));
+    if (!batch_ensure_penalty(B)) return false;
+    if (n == 0) { BATCH_HIP_OK(B, hipStreamSynchronize(B->run->stream)); B->has_bias[slot] = 0; return true; }
+    B->has_bias[slot] = 1;   // (a failure below leaves a table that is cleared or half written: it is not read as "no bias")
+    return table_bias_set(B->ctx, B->d_bias + slot * (size_t) B->ctx->model->n_vocab(), ids, values, n, B->run->stream);
+}
+
+RWKV_API bool rwkv_mi_batch_eval_sample_penalized(struct rwkv_mi_batch * B, const uint32_t * slots, const uint32_t * tokens, size_t n,
+                                                  const struct rwkv_mi_sample_params * params, const struct rwkv_mi_penalty_params * penalties,
+                                                  uint32_t * sampled_out, float * logits_out) {
+    rwkv_context * ctx = B->ctx;
+    ctx->last_error = RWKV_ERROR_NONE;
+    if (!batch_check_call(B, slots, tokens, n) || !batch_check_params(B, params, n, true) || !batch_check_penalties(B, penalties, n)) return false;
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, sampled_out != nullptr, "sampled_out is NULL");
+    rwkv_context * run = B->run;
+    run->print_errors = ctx->print_errors;
+    BATCH_HIP_OK(B, hipSetDevice(ctx->model->device));
+    if (!batch_ensure_penalty(B)) return false;
+    if (!batch_upload(B, slots, tokens, n, 1) || !batch_upload_penalty_rows(B, slots, params, penalties, n, false)) return false;
+    const RowSampler sampler{nullptr, B->d_probs, nullptr, B->d_prows};
+    if (!forward_rows(run, B->d_rows, (int64_t) n, true, &sampler)) { (void) hipStreamSynchronize(run->stream); return batch_fail_through(B); }
+    BATCH_HIP_OK(B, hipMemcpyAsync(run->h_tokens, run->d_tokens, n * sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream));
+    if (logits_out) BATCH_HIP_OK(B, hipMemcpyAsync(logits_out, run->d_logits, n * (size_t) ctx->model->n_vocab() * sizeof(float), hipMemcpyDeviceToHost, run->stream));
+    BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));
+    memcpy(sampled_out, run->h_tokens, n * sizeof(uint32_t));
+    for (size_t i = 0; i < n; i++) B->parity[slots[i]] ^= 1;
+    return true;
+}
+
+RWKV_API bool rwkv_mi_batch_eval_ragged_sample_penalized(struct rwkv_mi_batch * B, const uint32_t * slots, const uint32_t * lens, const uint32_t * tokens,
+                                                         size_t n, const struct rwkv_mi_sample_params * params,
+                                                         const struct rwkv_mi_penalty_params * penalties, uint32_t * sampled_out, float * logits_out) {
+    rwkv_context * ctx = B->ctx;
+    ctx->last_error = RWKV_ERROR_NONE;
+    size_t T = 0;
+    if (!batch_check_ragged(B, slots, lens, tokens, n, &T) || !batch_check_params(B, params, n, true) || !batch_check_penalties(B, penalties, n)) return false;
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, sampled_out != nullptr, "sampled_out is NULL");
+    rwkv_context * run = B->run;
+    run->print_errors = ctx->print_errors;
+    BATCH_HIP_OK(B, hipSetDevice(ctx->model->device));
+    if (!batch_ensure_penalty(B)) return false;
+    if (!batch_upload_ragged(B, slots, lens, tokens, n, T) || !batch_upload_penalty_rows(B, slots, params, penalties, n, false)) return false;
+    const RowSampler sampler{nullptr, B->d_probs, nullptr, B->d_prows};
+    if (!forward_segs(run, B->pass, (int64_t) T, true, &sampler)) { (void) hipStreamSynchronize(run->stream); return batch_fail_through(B); }
+    BATCH_HIP_OK(B, hipMemcpyAsync(run->h_tokens, run->d_tokens, n * sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream));
+    if (logits_out) BATCH_HIP_OK(B, hipMemcpyAsync(logits_out, run->d_logits, n * (size_t) ctx->model->n_vocab() * sizeof(float), hipMemcpyDeviceToHost, run->stream));
+    BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));
+    memcpy(sampled_out, run->h_tokens, n * sizeof(uint32_t));
+    for (size_t i = 0; i < n; i++) B->parity[slots[i]] ^= 1;
+    return true;
+}
+
+// The penalised loop CONTINUES: the named slots' counts and draw counters are where the caller left them, and every step records.
+RWKV_API bool rwkv_mi_batch_decode_sample_penalized(struct rwkv_mi_batch * B, const uint32_t * slots, const uint32_t * first_tokens, size_t n,
+                                                    size_t n_tokens, const struct rwkv_mi_sample_params * params,
+                                                    const struct rwkv_mi_penalty_params * penalties, uint32_t * tokens_out, float * elapsed_ms) {
+    rwkv_context * ctx = B->ctx;
+    ctx->last_error = RWKV_ERROR_NONE;
+    if (!batch_check_call(B, slots, first_tokens, n) || !batch_check_params(B, params, n, false) || !batch_check_penalties(B, penalties, n)) return false;
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, n_tokens > 0, "n_tokens is 0");
+    rwkv_context * run = B->run;
+    run->print_errors = ctx->print_errors;
+    BATCH_HIP_OK(B, hipSetDevice(ctx->model->device));
+    if (!batch_ensure_penalty(B)) return false;
+    struct DevBuf { uint32_t * p = nullptr; ~DevBuf() { if (p) (void) hipFree(p); } } hist;   // [n_tokens][n], freed on every exit
+    BATCH_HIP_OK(B, hipMalloc((void **) &hist.p, n_tokens * n * sizeof(uint32_t)));
+    if (!batch_upload(B, slots, first_tokens, n, 2) || !batch_upload_penalty_rows(B, slots, params, penalties, n, true)) return false;
+    BATCH_HIP_OK(B, hipEventRecord(run->ev0, run->stream));
+    for (size_t i = 0; i < n_tokens; i++) {
+        const RowSampler sampler{nullptr, B->d_probs, hist.p + i * n, B->d_prows};
+        if (!forward_rows(run, B->d_rows + (i & 1) * B->n_slots, (int64_t) n, true, &sampler)) {
+            (void) hipStreamSynchronize(run->stream);
+            return batch_fail_through(B);
+        }
+    }
+    BATCH_HIP_OK(B, hipEventRecord(run->ev1, run->stream));
+    std::vector<uint32_t> h(tokens_out ? n_tokens * n : 0);
+    if (tokens_out) BATCH_HIP_OK(B, hipMemcpyAsync(h.data(), hist.p, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream));
+    BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));
+    if (elapsed_ms) BATCH_HIP_OK(B, hipEventElapsedTime(elapsed_ms, run->ev0, run->ev1));
+    for (size_t r = 0; r < n && tokens_out; r++)
+        for (size_t i = 0; i < n_tokens; i++) tokens_out[r * n_tokens + i] = h[i * n + r];
+    if (n_tokens & 1) for (size_t i = 0; i < n; i++) B->parity[slots[i]] ^= 1;
     return true;
 }
 

@@ -267,6 +267,8 @@ void destroy_context(rwkv_context * ctx) {
     if (ctx->d_next_token) (void) hipFree(ctx->d_next_token);
     if (ctx->d_probs) (void) hipFree(ctx->d_probs);
     if (ctx->d_rng_counter) (void) hipFree(ctx->d_rng_counter);
+    if (ctx->d_counts) (void) hipFree(ctx->d_counts);
+    if (ctx->d_bias) (void) hipFree(ctx->d_bias);
     if (ctx->h_tokens) (void) hipHostFree(ctx->h_tokens);
     if (ctx->ev0) (void) hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void) hipEventDestroy(ctx->ev1);
@@ -786,7 +788,10 @@ bool forward_rows(rwkv_context * ctx, const RowState * d_rows, int64_t T, bool w
     r.state.rows = d_rows;
     mega_chain_begin(ctx);
     r.run(want_logits);
-    if (sample && want_logits && !r.failed) launch_sample_rows(ctx->d_logits, T, (int) m.n_vocab(), sample->table, sample->probs, ctx->d_tokens, sample->hist, ctx->stream);
+    if (sample && want_logits && !r.failed) {
+        if (sample->ptable) launch_pen_sample_rows(ctx->d_logits, T, (int) m.n_vocab(), sample->ptable, sample->probs, ctx->d_tokens, sample->hist, ctx->stream);
+        else launch_sample_rows(ctx->d_logits, T, (int) m.n_vocab(), sample->table, sample->probs, ctx->d_tokens, sample->hist, ctx->stream);
+    }
     mega_chain_end(ctx);
     HIP_CTX_OK(ctx, hipGetLastError());
     RW_CTX_CHECK(ctx, RWKV_ERROR_GRAPH | RWKV_ERROR_ALLOC, false, !r.failed, "a batched product could not be launched (out of device memory for the tile-major weight image?)");
@@ -812,7 +817,10 @@ bool forward_segs(rwkv_context * ctx, const SegPass & p, int64_t T, bool want_lo
     r.state.segs = p.d_segs; r.state.n_segs = p.n; r.state.seg_of = p.d_seg_of;
     mega_chain_begin(ctx);
     r.run(want_logits);
-    if (sample && want_logits && !r.failed) launch_sample_rows(ctx->d_logits, p.n, (int) m.n_vocab(), sample->table, sample->probs, ctx->d_tokens, sample->hist, ctx->stream);
+    if (sample && want_logits && !r.failed) {
+        if (sample->ptable) launch_pen_sample_rows(ctx->d_logits, p.n, (int) m.n_vocab(), sample->ptable, sample->probs, ctx->d_tokens, sample->hist, ctx->stream);
+        else launch_sample_rows(ctx->d_logits, p.n, (int) m.n_vocab(), sample->table, sample->probs, ctx->d_tokens, sample->hist, ctx->stream);
+    }
     mega_chain_end(ctx);
     HIP_CTX_OK(ctx, hipGetLastError());
     RW_CTX_CHECK(ctx, RWKV_ERROR_GRAPH | RWKV_ERROR_ALLOC, false, !r.failed, "a product of the ragged pass could not be launched (out of device memory for the tile-major weight image?)");

@@ -116,6 +116,16 @@ inline size_t sample_scratch_floats(int64_t n) { return (size_t) ((n + 1023) / 1
 struct SampleRow { rwkv_mi_sample_params p; unsigned long long * counter; };
 void launch_sample_rows(const float * logits, int64_t rows, int n, const SampleRow * table, float * probs, uint32_t * tokens, uint32_t * hist, hipStream_t st);
 void launch_sample_seek_rows(const SampleRow * table, int64_t rows, unsigned long long value, hipStream_t st);   // *table[r].counter = value
+// The penalised forms (rwkv_mi_*_penalized): the same draw on adj[j] = (logits[j] - (presence + (float) count[j] * frequency)) + bias[j]
+// (the penalty where count[j] > 0 only; bias == NULL: no bias), then count[token] += 1 when record is set. count: the sequence's occurrence table ([n] words), bias: its bias
+// table ([n] floats). The row table carries them per row, beside the sampler's parameters and the draw counter of the row's slot.
+struct PenaltyRow { rwkv_mi_sample_params p; unsigned long long * counter; float presence; float frequency; uint32_t record; uint32_t * count; const float * bias; };
+void launch_pen_sample(const float * logits, int n, float temperature, float top_p, float u, unsigned long long seed, unsigned long long * counter,
+                       float presence, float frequency, uint32_t record, uint32_t * count, const float * bias,
+                       float * probs, uint32_t * out_token, uint32_t * hist, int hist_pos, hipStream_t st);
+void launch_pen_sample_rows(const float * logits, int64_t rows, int n, const PenaltyRow * table, float * probs, uint32_t * tokens, uint32_t * hist, hipStream_t st);
+void launch_count_add(uint32_t * count, const uint32_t * tokens, int64_t n, int n_vocab, hipStream_t st);                        // count[tokens[i]] += 1
+void launch_bias_scatter(float * bias, const uint32_t * ids, const float * values, int64_t n, int n_vocab, hipStream_t st);     // bias[ids[i]] = values[i]
 
 // Loads [layer_begin, layer_end) of the file (layer_end == UINT32_MAX: all layers) onto the current HIP device.
 // Returns nullptr with the thread-local error set, like the reference loader (rwkv_model_loading.inc:288-419).
@@ -160,6 +170,9 @@ struct rwkv_context {
     uint32_t * d_next_token = nullptr;
     float *    d_probs = nullptr;                 // sampler scratch (sample_scratch_floats(n_vocab) floats), allocated on first use
     unsigned long long * d_rng_counter = nullptr;
+    uint32_t * d_counts = nullptr;                // penalised sampling (rwkv_mi_*_penalized): the context's occurrence table [n_vocab] and its bias table
+    float *    d_bias = nullptr;                  // [n_vocab], allocated by the first call of that family; has_bias: a bias has been set and not cleared
+    bool       has_bias = false;
 
     // pinned host staging for tokens / logits
     uint32_t * h_tokens = nullptr;
@@ -216,7 +229,8 @@ bool forward(rwkv_context * ctx, int64_t T, bool want_logits);
 rwkv_context * batch_context_create(Model * m, int64_t max_rows);
 void batch_context_destroy(rwkv_context * c);
 // sample: when given, one sampled token per row from the pass's logits (launch_sample_rows), launched inside the pass's place in the chain
-struct RowSampler { const SampleRow * table; float * probs; uint32_t * hist; };
+// (ptable: the penalised row table; when given, launch_pen_sample_rows takes the place of launch_sample_rows and `table` is not read)
+struct RowSampler { const SampleRow * table; float * probs; uint32_t * hist; const PenaltyRow * ptable = nullptr; };
 bool forward_rows(rwkv_context * ctx, const RowState * d_rows, int64_t T, bool want_logits, const RowSampler * sample = nullptr);
 
 // Ragged batch pass: row i of the call is a SEGMENT, tokens [t0, t1) of the pass, consecutive tokens of one slot's sequence.

@@ -10,6 +10,12 @@
 // are reproducible; against numpy's sequential cumsum the result can differ only when u or top_p falls within rounding of a boundary.
 // Batched decode samples every row of a pass in one launch of k_sample_rows: one workgroup per row, per-row parameters and the draw
 // counter of the row's slot from a device table (rwkv_mi_batch_eval_sample / _decode_sample).
+// Penalised draws (k_pen_sample / k_pen_sample_rows, rwkv_mi_*_penalized): the same body reads, instead of the logit l[j],
+//   adj[j] = (l[j] - (presence + (float) count[j] * frequency)) + bias[j]      where count[j] > 0;      l[j] + bias[j] elsewhere
+// (the reference's chat program, chat_with_bot.py:246-247 -- its loop runs over the tokens that have occurred -- then sample_logits'
+// logit_bias, sampling.py:27-36; every operation rounded to f32 in that order) from the sequence's occurrence table count[n] and its
+// optional bias table, and counts the chosen token afterwards.
+// The logits themselves are never written.
 #include "kdev.h"
 #include "model.h"
 
@@ -39,15 +45,48 @@ __device__ __forceinline__ float uniform01(unsigned long long seed, unsigned lon
 template <class F>
 __device__ __forceinline__ void for_chunk(int cnt, F && f) { for (int j = 0; j < cnt; j++) f(j); }
 
+// A thread's view of the scratch vector: element j of its chunk (the layout is explained at sample_body).
+struct ProbVec {
+    float * mem; int nt;
+    __device__ __forceinline__ float get(int j) const { return mem[(size_t) j * nt]; }
+    __device__ __forceinline__ void set(int j, float v) const { mem[(size_t) j * nt] = v; }
+};
+
+// Where sample_body takes the logit of element j of the thread's chunk from: first() in the pass that finds the maximum, again() in the
+// pass that exponentiates. The plain source loads the logit both times.
+struct PlainLogits {
+    const float * lg;
+    __device__ __forceinline__ float first(int j, const ProbVec &) const { return lg[j]; }
+    __device__ __forceinline__ float again(int j, const ProbVec &) const { return lg[j]; }
+};
+// The penalised source: first() computes the adjusted logit and STASHES it in the scratch vector, again() reads it back (the pass that
+// exponentiates overwrites the element it has just read). Against recomputing it in the second pass: a thread's chunk is contiguous in
+// the three tables, so the 64 lanes of a load touch 64 cache lines each time, while the scratch is laid out for the passes -- the stash
+// costs one coalesced store and load per element and saves three such loads; the arithmetic is the same either way.
+struct PenalisedLogits {
+    const float * lg; const uint32_t * count; const float * bias /* may be NULL */; float presence, frequency;
+    __device__ __forceinline__ float first(int j, const ProbVec & pr) const {
+        float a = lg[j];
+        const uint32_t c = count[j];
+        if (c) a = a - (presence + (float) c * frequency);   // (the reference's loop runs over the tokens that have occurred)
+        if (bias) a = a + bias[j];
+        pr.set(j, a);
+        return a;
+    }
+    __device__ __forceinline__ float again(int j, const ProbVec & pr) const { return pr.get(j); }
+};
+
 // One body, two entry points (the convention of the recurrence kernels and their row forms): k_sample hands it its arguments,
 // k_sample_rows the pointers and parameters of row blockIdx.x. Everything the workgroup does -- chunks, summation order, bisection, scan,
 // draw -- is this function, so a row of the batch picks bit for bit the token the single-context sampler picks from the same logits.
 // The scratch vector is laid out for the passes, not for the reader: token i0 + j of thread tid lives at probs[j * 1024 + tid], so the 64 lanes
 // of a load touch two cache lines instead of 64 (a thread's chunk is contiguous in the logits; ~35 passes run over the probabilities).
-__device__ __forceinline__ void sample_body(const float * __restrict__ logits, int n, float temperature, float top_p, float u_in,
-                                            unsigned long long seed, unsigned long long * counter /* read and advanced by thread 0; may be NULL */,
-                                            float * __restrict__ probs /* scratch of C * 1024 >= n floats, C = ceil(n / 1024) */,
-                                            uint32_t * __restrict__ out_token, uint32_t * __restrict__ hist_word /* may be NULL */) {
+// make_src(i0): the logit source of the thread whose chunk starts at token i0 (PlainLogits or PenalisedLogits).
+template <class MakeSrc>
+__device__ __forceinline__ int sample_body(MakeSrc && make_src, int n, float temperature, float top_p, float u_in,
+                                           unsigned long long seed, unsigned long long * counter /* read and advanced by thread 0; may be NULL */,
+                                           float * __restrict__ probs /* scratch of C * 1024 >= n floats, C = ceil(n / 1024) */,
+                                           uint32_t * __restrict__ out_token, uint32_t * __restrict__ hist_word /* may be NULL */) {
     __shared__ float red[32];
     __shared__ float l_scan[1024];
     __shared__ int l_pick, l_last;
@@ -56,19 +95,17 @@ __device__ __forceinline__ void sample_body(const float * __restrict__ logits, i
     const int C = (n + NT - 1) / NT;                 // contiguous chunk per thread
     const int i0 = tid * C, i1 = i0 + C < n ? i0 + C : n;
     const int cnt = i1 - i0;                         // (<= 0 for the threads behind the end)
-    struct { float * mem; int nt;
-             __device__ __forceinline__ float get(int j) const { return mem[(size_t) j * nt]; }
-             __device__ __forceinline__ void set(int j, float v) { mem[(size_t) j * nt] = v; } } pr{probs + tid, NT};
-    const float * lg = logits + i0;
+    const ProbVec pr{probs + tid, NT};
+    const auto src = make_src(i0);
     // softmax
     float m = -INFINITY;
-    for_chunk(cnt, [&](int j) { m = fmaxf(m, lg[j]); });
+    for_chunk(cnt, [&](int j) { m = fmaxf(m, src.first(j, pr)); });
     for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, WAVE));
     if ((tid & 63) == 0) red[tid >> 6] = m;
     __syncthreads();
     for (int w = 0; w < (NT >> 6); w++) m = fmaxf(m, red[w]);
     float part = 0.0f;
-    for_chunk(cnt, [&](int j) { const float e = det_expf(lg[j] - m); pr.set(j, e); part += e; });
+    for_chunk(cnt, [&](int j) { const float e = det_expf(src.again(j, pr) - m); pr.set(j, e); part += e; });
     const float total = block_sum_f(part, red);
     const float inv = 1.0f / total;
     for_chunk(cnt, [&](int j) { pr.set(j, pr.get(j) * inv); });
@@ -159,12 +196,13 @@ __device__ __forceinline__ void sample_body(const float * __restrict__ logits, i
     }
     if (pick < 0 || pick >= n) pick = 0;   // (all-NaN probabilities: the token must stay a row of the embedding table)
     if (tid == 0) { *out_token = (uint32_t) pick; if (hist_word) *hist_word = (uint32_t) pick; }
+    return pick;
 }
 
 __global__ __launch_bounds__(1024) void k_sample(const float * __restrict__ logits, int n, float temperature, float top_p, float u_in,
                                                  unsigned long long seed, unsigned long long * counter,
                                                  float * __restrict__ probs, uint32_t * __restrict__ out_token, uint32_t * __restrict__ hist, int hist_pos) {
-    sample_body(logits, n, temperature, top_p, u_in, seed, counter, probs, out_token, hist ? hist + hist_pos : nullptr);
+    sample_body([=](int i0) { return PlainLogits{logits + i0}; }, n, temperature, top_p, u_in, seed, counter, probs, out_token, hist ? hist + hist_pos : nullptr);
 }
 
 // Row form: grid = rows, one workgroup per row; row r's probabilities in its own stretch of the scratch (stride floats apart, the batch owns it).
@@ -172,7 +210,41 @@ __global__ __launch_bounds__(1024) void k_sample_rows(const float * __restrict__
                                                       float * __restrict__ probs, size_t stride, uint32_t * __restrict__ tokens, uint32_t * __restrict__ hist) {
     const size_t r = blockIdx.x;
     const rwkv_mi_sample_params p = table[r].p;
-    sample_body(logits + r * (size_t) n, n, p.temperature, p.top_p, p.u, p.seed, table[r].counter, probs + r * stride, tokens + r, hist ? hist + r : nullptr);
+    const float * lg = logits + r * (size_t) n;
+    sample_body([=](int i0) { return PlainLogits{lg + i0}; }, n, p.temperature, p.top_p, p.u, p.seed, table[r].counter, probs + r * stride, tokens + r, hist ? hist + r : nullptr);
+}
+
+// The penalised entry points: the same body on the adjusted logits, then -- when `record` is set -- the chosen token's count goes up by
+// one (thread 0, after the draw, argmax or not: the draw of step i has seen the counts of the steps before it).
+__global__ __launch_bounds__(1024) void k_pen_sample(const float * __restrict__ logits, int n, float temperature, float top_p, float u_in,
+                                                     unsigned long long seed, unsigned long long * counter, float presence, float frequency, uint32_t record,
+                                                     uint32_t * count, const float * __restrict__ bias,
+                                                     float * __restrict__ probs, uint32_t * __restrict__ out_token, uint32_t * __restrict__ hist, int hist_pos) {
+    const int pick = sample_body([=](int i0) { return PenalisedLogits{logits + i0, count + i0, bias ? bias + i0 : nullptr, presence, frequency}; },
+                                 n, temperature, top_p, u_in, seed, counter, probs, out_token, hist ? hist + hist_pos : nullptr);
+    if (threadIdx.x == 0 && record) count[pick] += 1u;
+}
+
+__global__ __launch_bounds__(1024) void k_pen_sample_rows(const float * __restrict__ logits, int n, const PenaltyRow * __restrict__ table,
+                                                          float * __restrict__ probs, size_t stride, uint32_t * __restrict__ tokens, uint32_t * __restrict__ hist) {
+    const size_t r = blockIdx.x;
+    const PenaltyRow row = table[r];
+    const float * lg = logits + r * (size_t) n;
+    const int pick = sample_body([=](int i0) { return PenalisedLogits{lg + i0, row.count + i0, row.bias ? row.bias + i0 : nullptr, row.presence, row.frequency}; },
+                                 n, row.p.temperature, row.p.top_p, row.p.u, row.p.seed, row.counter, probs + r * stride, tokens + r, hist ? hist + r : nullptr);
+    if (threadIdx.x == 0 && row.record) row.count[pick] += 1u;
+}
+
+// count[tokens[i]] += 1 for a list of tokens (rwkv_mi_*counts_add: a token may come more than once)
+__global__ __launch_bounds__(256) void k_count_add(uint32_t * __restrict__ count, const uint32_t * __restrict__ tokens, int64_t n, int n_vocab) {
+    const int64_t i = (int64_t) blockIdx.x * 256 + threadIdx.x;
+    if (i < n && tokens[i] < (uint32_t) n_vocab) atomicAdd(count + tokens[i], 1u);
+}
+
+// bias[ids[i]] = values[i] (rwkv_mi_*logit_bias_set, into a table the caller has cleared; the ids are distinct)
+__global__ __launch_bounds__(256) void k_bias_scatter(float * __restrict__ bias, const uint32_t * __restrict__ ids, const float * __restrict__ values, int64_t n, int n_vocab) {
+    const int64_t i = (int64_t) blockIdx.x * 256 + threadIdx.x;
+    if (i < n && ids[i] < (uint32_t) n_vocab) bias[ids[i]] = values[i];
 }
 
 __global__ __launch_bounds__(64) void k_sample_seek_rows(const SampleRow * __restrict__ table, int rows, unsigned long long value) {
@@ -187,6 +259,25 @@ void launch_sample(const float * logits, int n, float temperature, float top_p, 
 
 void launch_sample_rows(const float * logits, int64_t rows, int n, const SampleRow * table, float * probs, uint32_t * tokens, uint32_t * hist, hipStream_t st) {
     hipLaunchKernelGGL(k_sample_rows, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, table, probs, sample_scratch_floats(n), tokens, hist);
+}
+
+void launch_pen_sample(const float * logits, int n, float temperature, float top_p, float u, unsigned long long seed, unsigned long long * counter,
+                       float presence, float frequency, uint32_t record, uint32_t * count, const float * bias,
+                       float * probs, uint32_t * out_token, uint32_t * hist, int hist_pos, hipStream_t st) {
+    hipLaunchKernelGGL(k_pen_sample, dim3(1), dim3(1024), 0, st, logits, n, temperature, top_p, u, seed, counter, presence, frequency, record, count, bias,
+                       probs, out_token, hist, hist_pos);
+}
+
+void launch_pen_sample_rows(const float * logits, int64_t rows, int n, const PenaltyRow * table, float * probs, uint32_t * tokens, uint32_t * hist, hipStream_t st) {
+    hipLaunchKernelGGL(k_pen_sample_rows, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, table, probs, sample_scratch_floats(n), tokens, hist);
+}
+
+void launch_count_add(uint32_t * count, const uint32_t * tokens, int64_t n, int n_vocab, hipStream_t st) {
+    if (n > 0) hipLaunchKernelGGL(k_count_add, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, st, count, tokens, n, n_vocab);
+}
+
+void launch_bias_scatter(float * bias, const uint32_t * ids, const float * values, int64_t n, int n_vocab, hipStream_t st) {
+    if (n > 0) hipLaunchKernelGGL(k_bias_scatter, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, st, bias, ids, values, n, n_vocab);
 }
 
 void launch_sample_seek_rows(const SampleRow * table, int64_t rows, unsigned long long value, hipStream_t st) {

@@ -23,6 +23,10 @@ HOOKS_LIB_PATH = os.path.join(PKG_DIR, os.environ.get("RWKV_LIB_DIR", "lib"), "l
 SAMPLE_HOOKS_LIB_PATH = os.path.join(PKG_DIR, os.environ.get("RWKV_LIB_DIR", "lib"), "librwkv_testhooks_sample.so")
 
 QUANTIZED_FORMAT_NAMES = ("Q4_0", "Q4_1", "Q5_0", "Q5_1", "Q8_0")
+PENALTY_SYMBOLS = ("rwkv_mi_batch_counts_reset", "rwkv_mi_batch_counts_add", "rwkv_mi_batch_counts_store", "rwkv_mi_batch_logit_bias_set",
+                   "rwkv_mi_batch_eval_sample_penalized", "rwkv_mi_batch_eval_ragged_sample_penalized", "rwkv_mi_batch_decode_sample_penalized",
+                   "rwkv_mi_counts_reset", "rwkv_mi_counts_add", "rwkv_mi_counts_store", "rwkv_mi_logit_bias_set", "rwkv_mi_rng_seek",
+                   "rwkv_mi_sample_penalized", "rwkv_mi_decode_sample_penalized")
 P_FLOAT = ctypes.POINTER(ctypes.c_float)
 P_UINT32 = ctypes.POINTER(ctypes.c_uint32)
 
@@ -33,6 +37,14 @@ class SampleParams(ctypes.Structure):
 
 
 P_SAMPLE_PARAMS = ctypes.POINTER(SampleParams)
+
+
+class PenaltyParams(ctypes.Structure):
+    """struct rwkv_mi_penalty_params (include/rwkv_mi355x.h): one row's presence / frequency penalty and its record flag, 12 bytes."""
+    _fields_ = [("presence", ctypes.c_float), ("frequency", ctypes.c_float), ("record", ctypes.c_uint32)]
+
+
+P_PENALTY_PARAMS = ctypes.POINTER(PenaltyParams)
 
 
 def build_library(force: bool = False) -> str:
@@ -188,6 +200,27 @@ class RWKVSharedLibrary:
         L.rwkv_mi_batch_eval_ragged.restype = ctypes.c_bool
         L.rwkv_mi_batch_eval_ragged_sample.argtypes = [c_batch, P_UINT32, P_UINT32, P_UINT32, ctypes.c_size_t, P_SAMPLE_PARAMS, P_UINT32, P_FLOAT]
         L.rwkv_mi_batch_eval_ragged_sample.restype = ctypes.c_bool
+        # penalised sampling: per-slot / per-context occurrence and bias tables
+        L.rwkv_mi_batch_counts_reset.argtypes = [c_batch, ctypes.c_size_t]
+        L.rwkv_mi_batch_counts_add.argtypes = [c_batch, ctypes.c_size_t, P_UINT32, ctypes.c_size_t]
+        L.rwkv_mi_batch_counts_store.argtypes = [c_batch, ctypes.c_size_t, P_UINT32]
+        L.rwkv_mi_batch_logit_bias_set.argtypes = [c_batch, ctypes.c_size_t, P_UINT32, P_FLOAT, ctypes.c_size_t]
+        L.rwkv_mi_batch_eval_sample_penalized.argtypes = [c_batch, P_UINT32, P_UINT32, ctypes.c_size_t, P_SAMPLE_PARAMS, P_PENALTY_PARAMS, P_UINT32, P_FLOAT]
+        L.rwkv_mi_batch_eval_ragged_sample_penalized.argtypes = [c_batch, P_UINT32, P_UINT32, P_UINT32, ctypes.c_size_t, P_SAMPLE_PARAMS, P_PENALTY_PARAMS,
+                                                                 P_UINT32, P_FLOAT]
+        L.rwkv_mi_batch_decode_sample_penalized.argtypes = [c_batch, P_UINT32, P_UINT32, ctypes.c_size_t, ctypes.c_size_t, P_SAMPLE_PARAMS, P_PENALTY_PARAMS,
+                                                            P_UINT32, P_FLOAT]
+        L.rwkv_mi_counts_reset.argtypes = [c_ctx]
+        L.rwkv_mi_counts_add.argtypes = [c_ctx, P_UINT32, ctypes.c_size_t]
+        L.rwkv_mi_counts_store.argtypes = [c_ctx, P_UINT32]
+        L.rwkv_mi_logit_bias_set.argtypes = [c_ctx, P_UINT32, P_FLOAT, ctypes.c_size_t]
+        L.rwkv_mi_rng_seek.argtypes = [c_ctx, ctypes.c_uint64]
+        L.rwkv_mi_sample_penalized.argtypes = [c_ctx, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_uint64, ctypes.c_float, ctypes.c_float,
+                                               ctypes.c_uint32, P_UINT32]
+        L.rwkv_mi_decode_sample_penalized.argtypes = [c_ctx, ctypes.c_uint32, ctypes.c_size_t, ctypes.c_float, ctypes.c_float, ctypes.c_uint64,
+                                                      ctypes.c_float, ctypes.c_float, P_UINT32, P_FLOAT]
+        for name in PENALTY_SYMBOLS:
+            getattr(L, name).restype = ctypes.c_bool
         if hasattr(L, "rwkv_mi_test_sample_rows"):   # (librwkv_testhooks_sample.so only)
             L.rwkv_mi_test_sample_rows.argtypes = [P_FLOAT, ctypes.c_int64, ctypes.c_int64, P_SAMPLE_PARAMS, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int, P_UINT32]
             L.rwkv_mi_test_sample_rows.restype = ctypes.c_bool
@@ -418,6 +451,52 @@ class RWKVModel:
             raise ValueError("rwkv_mi_decode_sample failed")
         return out, float(ms.value)
 
+    # --- penalised sampling: the context's occurrence table and bias table (include/rwkv_mi355x.h) ---
+
+    def _mi(self, name: str, *args) -> None:
+        if not getattr(self._library.library, name)(self._ctx.ptr, *args):
+            self.last_error = self._library.rwkv_get_last_error(self._ctx)
+            raise ValueError(f"{name} failed (error flags {self.last_error})")
+
+    def counts_reset(self) -> None:
+        self._mi("rwkv_mi_counts_reset")
+
+    def counts_add(self, tokens: List[int]) -> None:
+        """count[t] += 1 for every t of `tokens` (resuming a recorded response)."""
+        t = _u32(tokens).reshape(-1)
+        self._mi("rwkv_mi_counts_add", t.ctypes.data_as(P_UINT32), t.size)
+
+    def counts(self) -> np.ndarray:
+        """The context's occurrence table, uint32 [n_vocab]."""
+        out = np.empty(self.n_vocab, dtype=np.uint32)
+        self._mi("rwkv_mi_counts_store", out.ctypes.data_as(P_UINT32))
+        return out
+
+    def set_logit_bias(self, bias: dict) -> None:
+        """Replaces the context's logit bias by {token id: value}; an empty dict clears it (sampling.py's logit_bias)."""
+        ids, values = _bias_arrays(bias)
+        self._mi("rwkv_mi_logit_bias_set", ids.ctypes.data_as(P_UINT32), values.ctypes.data_as(P_FLOAT), ids.size)
+
+    def rng_seek(self, counter: int) -> None:
+        """Sets the context's draw counter (0 for a new request)."""
+        self._mi("rwkv_mi_rng_seek", counter)
+
+    def sample_penalized(self, temperature: float = 1.0, top_p: float = 0.8, u: float = -1.0, seed: int = 0, presence: float = 0.2,
+                         frequency: float = 0.2, record: bool = True) -> int:
+        """sample() on the logits less presence + count * frequency, plus the bias; the chosen token is counted when `record`."""
+        tok = ctypes.c_uint32(0)
+        self._mi("rwkv_mi_sample_penalized", temperature, top_p, u, seed, presence, frequency, 1 if record else 0, ctypes.byref(tok))
+        return int(tok.value)
+
+    def decode_sample_penalized(self, first_token: int, n_tokens: int, temperature: float = 1.0, top_p: float = 0.8, seed: int = 0,
+                                presence: float = 0.2, frequency: float = 0.2) -> Tuple[np.ndarray, float]:
+        """decode_sample() with the penalised draw, every step recorded. It continues: call counts_reset() and rng_seek(0) for a new request."""
+        out = np.empty(n_tokens, dtype=np.uint32)
+        ms = ctypes.c_float(0.0)
+        self._mi("rwkv_mi_decode_sample_penalized", first_token, n_tokens, temperature, top_p, seed, presence, frequency,
+                 ctypes.cast(out.ctypes.data, P_UINT32), ctypes.byref(ms))
+        return out, float(ms.value)
+
     def profile_decode(self, first_token: int, n_tokens: int) -> dict:
         out = (ctypes.c_double * 4)()
         if not self._library.library.rwkv_mi_profile_decode(self._ctx.ptr, first_token, n_tokens, out):
@@ -507,6 +586,30 @@ def sample_params(n: int, temperature, top_p, u=-1.0, seed=0):
     for i in range(n):
         arr[i] = SampleParams(float(t[i]), float(p[i]), float(us[i]), int(sd[i]) & 0xFFFFFFFFFFFFFFFF)
     return arr
+
+
+def _rows(n: int, v, what: str) -> list:
+    a = np.asarray(v)
+    if a.ndim == 0:
+        return [a.item()] * n
+    if a.shape != (n,):
+        raise ValueError(f"{what} must be a scalar or a sequence of length {n}")
+    return a.tolist()
+
+
+def penalty_params(n: int, presence, frequency, record=True):
+    """[n] struct rwkv_mi_penalty_params; each argument is a scalar (every row) or a sequence of length n."""
+    pr, fr, rec = _rows(n, presence, "presence"), _rows(n, frequency, "frequency"), _rows(n, record, "record")
+    arr = (PenaltyParams * n)()
+    for i in range(n):
+        arr[i] = PenaltyParams(float(pr[i]), float(fr[i]), 1 if rec[i] else 0)
+    return arr
+
+
+def _bias_arrays(bias: dict):
+    ids = _u32(list(bias.keys())).reshape(-1)
+    values = np.ascontiguousarray(np.asarray(list(bias.values()), dtype=np.float64).astype(np.float32)).reshape(-1)
+    return ids, values
 
 
 class RWKVBatch:
@@ -640,6 +743,78 @@ class RWKVBatch:
         """Sets a slot's draw counter (0 for a new request in a reused slot)."""
         if not self._L.rwkv_mi_batch_rng_seek(self._ptr, slot, counter):
             self._fail("rwkv_mi_batch_rng_seek")
+
+    # --- penalised sampling: one occurrence table and one bias table per slot (include/rwkv_mi355x.h) ---
+
+    def counts_reset(self, slot: int) -> None:
+        if not self._L.rwkv_mi_batch_counts_reset(self._ptr, slot):
+            self._fail("rwkv_mi_batch_counts_reset")
+
+    def counts_add(self, slot: int, tokens: List[int]) -> None:
+        """count[t] += 1 in the slot's occurrence table for every t of `tokens` (resuming a recorded response)."""
+        t = _u32(tokens).reshape(-1)
+        if not self._L.rwkv_mi_batch_counts_add(self._ptr, slot, t.ctypes.data_as(P_UINT32), t.size):
+            self._fail("rwkv_mi_batch_counts_add")
+
+    def counts(self, slot: int) -> np.ndarray:
+        """The slot's occurrence table, uint32 [n_vocab]."""
+        out = np.empty(self._n_vocab, dtype=np.uint32)
+        if not self._L.rwkv_mi_batch_counts_store(self._ptr, slot, out.ctypes.data_as(P_UINT32)):
+            self._fail("rwkv_mi_batch_counts_store")
+        return out
+
+    def set_logit_bias(self, slot: int, bias: dict) -> None:
+        """Replaces the slot's logit bias by {token id: value}; an empty dict clears it."""
+        ids, values = _bias_arrays(bias)
+        if not self._L.rwkv_mi_batch_logit_bias_set(self._ptr, slot, ids.ctypes.data_as(P_UINT32), values.ctypes.data_as(P_FLOAT), ids.size):
+            self._fail("rwkv_mi_batch_logit_bias_set")
+
+    def eval_sample_penalized(self, slots: List[int], tokens: List[int], temperature=1.0, top_p=0.8, u=-1.0, seed=0, presence=0.2, frequency=0.2,
+                              record=True, want_logits: bool = False):
+        """eval_sample with each row's logits less presence + count * frequency of its slot, plus the slot's bias; a row with `record`
+        counts its token afterwards. presence, frequency, record: a scalar (every row) or a sequence of length n."""
+        s, t = _u32(slots), _u32(tokens)
+        if s.size != t.size:
+            raise ValueError("slots and tokens differ in length")
+        params = sample_params(s.size, temperature, top_p, u, seed)
+        pens = penalty_params(s.size, presence, frequency, record)
+        out = np.empty(s.size, dtype=np.uint32)
+        logits = np.empty((s.size, self._n_vocab), dtype=np.float32) if want_logits else None
+        if not self._L.rwkv_mi_batch_eval_sample_penalized(self._ptr, s.ctypes.data_as(P_UINT32), t.ctypes.data_as(P_UINT32), s.size, params, pens,
+                                                           out.ctypes.data_as(P_UINT32), ctypes.cast(_ptr(logits), P_FLOAT)):
+            self._fail("rwkv_mi_batch_eval_sample_penalized")
+        return (out, logits) if want_logits else out
+
+    def eval_ragged_sample_penalized(self, slots: List[int], token_lists: List[List[int]], temperature=1.0, top_p=0.8, u=-1.0, seed=0, presence=0.2,
+                                     frequency=0.2, record=True, want_logits: bool = False):
+        """eval_ragged_sample with the penalised draw. Give a non-final prompt chunk temperature 0 AND record False: nothing of the slot's
+        draw counter or counts moves then."""
+        s, lens, toks = self._ragged(slots, token_lists)
+        params = sample_params(s.size, temperature, top_p, u, seed)
+        pens = penalty_params(s.size, presence, frequency, record)
+        out = np.empty(s.size, dtype=np.uint32)
+        logits = np.empty((s.size, self._n_vocab), dtype=np.float32) if want_logits else None
+        if not self._L.rwkv_mi_batch_eval_ragged_sample_penalized(self._ptr, s.ctypes.data_as(P_UINT32), lens.ctypes.data_as(P_UINT32),
+                                                                  toks.ctypes.data_as(P_UINT32), s.size, params, pens, out.ctypes.data_as(P_UINT32),
+                                                                  ctypes.cast(_ptr(logits), P_FLOAT)):
+            self._fail("rwkv_mi_batch_eval_ragged_sample_penalized")
+        return (out, logits) if want_logits else out
+
+    def decode_sample_penalized(self, slots: List[int], first_tokens: List[int], n_tokens: int, temperature=1.0, top_p=0.8, seed=0, presence=0.2,
+                                frequency=0.2) -> Tuple[np.ndarray, float]:
+        """decode_sample with the penalised draw, every step recorded: tokens [n][n_tokens], elapsed milliseconds. It continues -- neither
+        the counts nor the draw counters are reset; call counts_reset(slot) and rng_seek(slot, 0) for a new request."""
+        s, t = _u32(slots), _u32(first_tokens)
+        if s.size != t.size:
+            raise ValueError("slots and first_tokens differ in length")
+        params = sample_params(s.size, temperature, top_p, -1.0, seed)
+        pens = penalty_params(s.size, presence, frequency, True)
+        out = np.empty((s.size, n_tokens), dtype=np.uint32)
+        ms = ctypes.c_float(0.0)
+        if not self._L.rwkv_mi_batch_decode_sample_penalized(self._ptr, s.ctypes.data_as(P_UINT32), t.ctypes.data_as(P_UINT32), s.size, n_tokens, params,
+                                                             pens, ctypes.cast(out.ctypes.data, P_UINT32), ctypes.byref(ms)):
+            self._fail("rwkv_mi_batch_decode_sample_penalized")
+        return out, float(ms.value)
 
     def free(self) -> None:
         if self._ptr:

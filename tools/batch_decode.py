@@ -16,6 +16,13 @@ and first one record with the single-stream rate measured in the same process.
   mode batch_host_sample   what has to be done without it: RWKVBatch.eval with the logits to the host, then sample_probs of the
                            reference's python/sampling.py restated in NumPy on each row; host clock around the loop
 
+--sample --penalties adds two more arms in the same run, shapes and n (presence 0.2, frequency 0.2 -- the reference chat program's defaults --
+every step recorded), and appends its records to --out when given:
+  mode batch_sample_penalized       rwkv_mi_batch_decode_sample_penalized, the loop on the device; penalty_ms_per_step is its step minus the
+                                    plain sampled step of the same n and run
+  mode batch_host_sample_penalized  the host path doing the same job: the logits to the host, chat_with_bot.py:246-247 on each row, then
+                                    sample_probs in NumPy; host clock around the loop
+
 --ragged times the ragged pass (rwkv_mi_batch_eval_ragged*) instead, host clock around complete calls (each ends with its stream drained),
 the smallest of --reps runs after one warm-up run of the same shape, both sides in this process and run; records also go to --out:
   mode ragged_ingest   N prompts of L tokens: one ragged pass (logits of every prompt's last token to the host) against the way without
@@ -144,9 +151,10 @@ def main():
     ap.add_argument("--tokens", type=int, default=32, help="steps of each timed loop")
     ap.add_argument("--warmup", type=int, default=4, help="steps of the warm-up loop of every n")
     ap.add_argument("--sample", action="store_true", help="also time the sampling loop: on the device, and through the host")
+    ap.add_argument("--penalties", action="store_true", help="with --sample: also time the penalised sampling loop, on the device and through the host")
     ap.add_argument("--ragged", action="store_true", help="time the ragged pass: prompt ingestion and joining a decode step (see above)")
     ap.add_argument("--reps", type=int, default=3, help="--ragged: timed runs of each shape (the smallest is reported)")
-    ap.add_argument("--out", default=None, help="--ragged: also append the records to this file")
+    ap.add_argument("--out", default=None, help="--ragged, --penalties: also append the records to this file")
     args = ap.parse_args()
 
     import __graft_entry__ as graft
@@ -226,6 +234,49 @@ def main():
         print(json.dumps({"mode": "batch_host_sample", "n": n, "ms_per_step": round(host_ms, 4), "device_sample_ms_per_step": round(dev_ms, 4),
                           "host_over_device": round(host_ms / dev_ms, 2), "logits_bytes_per_step": 4 * n * V,
                           "temperature": 1.0, "top_p": 0.8, "steps": args.tokens, "config": args.config, "dtype": args.dtype}), flush=True)
+        if not args.penalties:
+            continue
+        presence, frequency = 0.2, 0.2   # (chat_with_bot.py:31-33)
+
+        def new_request():
+            for s in slots:
+                b.state_load(s, None)
+                b.counts_reset(s)
+                b.rng_seek(s, 0)
+
+        new_request()
+        b.decode_sample_penalized(slots, first, args.warmup, 1.0, 0.8, slots, presence, frequency)   # (the first call allocates the tables)
+        new_request()
+        _, ms_p = b.decode_sample_penalized(slots, first, args.tokens, 1.0, 0.8, slots, presence, frequency)
+        pen_ms = ms_p / args.tokens
+        recs = [{"mode": "batch_sample_penalized", "n": n, "ms_per_step": round(pen_ms, 4), "sampled_ms_per_step": round(dev_ms, 4),
+                 "penalty_ms_per_step": round(pen_ms - dev_ms, 4), "greedy_ms_per_step": round(step_ms, 4), "tokens_per_s": round(n / (pen_ms / 1e3), 1)}]
+        rngs = [np.random.default_rng(i) for i in range(n)]
+        for s in slots:
+            b.state_load(s, None)
+        toks = list(first)
+        for timed in (False, True):
+            token_counts = [{} for _ in range(n)]
+            t0 = time.perf_counter()
+            for _ in range(args.tokens if timed else args.warmup):
+                lg = b.eval(slots, toks)
+                for i in range(n):
+                    row, tc = lg[i], token_counts[i]
+                    for k in tc:
+                        row[k] -= presence + tc[k] * frequency
+                    toks[i] = host_sample(row, 1.0, 0.8, rngs[i])
+                    tc[toks[i]] = tc.get(toks[i], 0) + 1
+            host_p_ms = (time.perf_counter() - t0) * 1e3 / args.tokens
+        recs.append({"mode": "batch_host_sample_penalized", "n": n, "ms_per_step": round(host_p_ms, 4), "device_ms_per_step": round(pen_ms, 4),
+                     "host_over_device": round(host_p_ms / pen_ms, 2), "logits_bytes_per_step": 4 * n * V})
+        for rec in recs:
+            rec.update({"presence": presence, "frequency": frequency, "temperature": 1.0, "top_p": 0.8, "steps": args.tokens,
+                        "config": args.config, "dtype": args.dtype})
+            line = json.dumps(rec)
+            print(line, flush=True)
+            if args.out:
+                with open(args.out, "a") as f:
+                    f.write(line + "\n")
     b.free()
     m.free()
 

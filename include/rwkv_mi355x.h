@@ -207,6 +207,38 @@ RWKV_API bool rwkv_mi_batch_eval_ragged_sample(struct rwkv_mi_batch * batch, con
                                                size_t n, const struct rwkv_mi_sample_params * params /* [n] */, uint32_t * sampled_out,
                                                float * logits_out);
 
+/* ---- Scoring: the model's prediction at EVERY position of given text, in one pass ----
+ * rwkv_eval_sequence and rwkv_mi_eval_resident report the logits of the last token only. Perplexity (the reference's
+ * python/measure_pexplexity.py calls rwkv_eval once per token) and the log-probability of given text (multiple choice, the log-probs of a
+ * prompt, checking a draft) need the prediction after each token. These calls run the tokens through the sequence path once and put the
+ * head on all positions, in chunks of R rows (R = 64 MiB of logits: 256 rows at 65536 tokens, at least 32, at most 1024; RWKV_MI_SCORE_ROWS
+ * overrides it, read when a context's or batch's first scoring call allocates the chunk); a kernel reduces every row on the device to
+ *   argmax[t]  = the index of the largest logit after tokens[t], the lowest index among equals (the rule of the greedy loops), and
+ *   logprob[t] = (float) ((double) l[target] - (m + log(sum_j exp((double) l[j] - m)))),  l = the logits after tokens[t], m = their maximum,
+ * the sum accumulated in float64 in a fixed order (no atomics) and the result rounded to f32 once: a log-prob depends on its row's logits
+ * and its target only, bit for bit, not on the chunking, the other rows or the run. Against float64 arithmetic on the same logits it is off
+ * by at most one f32 ulp of the result plus 2^-32. A target of RWKV_MI_NO_TARGET gives 0.
+ * Each position's logits equal rwkv_eval's at that token bit for bit, the state afterwards equals rwkv_eval_sequence's, however the call is
+ * cut -- on the default arms. Under the opt-in arms RWKV_MI_SEQ_Q=fast and RWKV_MI_SEQ_F16=mfma, the per-position logits (and what is
+ * derived from them) have sequence mode's stated tolerance instead.
+ * The buffers are allocated by the first scoring call of a context / batch (RWKV_ERROR_ALLOC, nothing changed, when they cannot be) and
+ * released by rwkv_free / rwkv_mi_batch_free. */
+#define RWKV_MI_NO_TARGET UINT32_MAX
+/* Feeds n_tokens tokens from the resident state (as rwkv_mi_eval_resident: state updated, pieces of 1024) and reports the model's
+ * prediction AFTER EACH of them. targets[t] (< n_vocab, or RWKV_MI_NO_TARGET) is scored against the logits after tokens[t].
+ * logprobs_out [n_tokens], argmax_out [n_tokens], logits_all_out [n_tokens][n_vocab]: each may be NULL; targets may be NULL iff logprobs_out is
+ * (targets without logprobs_out are checked and otherwise ignored). With every output NULL the call is rwkv_mi_eval_resident(.., NULL).
+ * Afterwards the context's own logits are those of the last token: rwkv_mi_sample and rwkv_mi_logits_store work as after rwkv_mi_eval_resident.
+ * Returns false with RWKV_ERROR_ARGS, nothing changed, for what rwkv_mi_eval_resident rejects (a RWKV_MI_DEVICES chain included), for a
+ * target >= n_vocab that is not RWKV_MI_NO_TARGET, and for logprobs_out without targets. */
+RWKV_API bool rwkv_mi_score_resident(struct rwkv_context * ctx, const uint32_t * tokens, size_t n_tokens, const uint32_t * targets,
+                                     float * logprobs_out, uint32_t * argmax_out, float * logits_all_out);
+/* The ragged form: row i feeds lens[i] tokens to slot slots[i] (rules, parity and rejections of rwkv_mi_batch_eval_ragged, plus the two
+ * target rules above); targets / logprobs_out / argmax_out are [T = sum(lens)] in token order. Each slot's values equal
+ * rwkv_mi_score_resident of its tokens alone, bit for bit. With both outputs NULL the call is rwkv_mi_batch_eval_ragged(.., NULL). */
+RWKV_API bool rwkv_mi_batch_score_ragged(struct rwkv_mi_batch * batch, const uint32_t * slots, const uint32_t * lens, const uint32_t * tokens,
+                                         const uint32_t * targets, size_t n, float * logprobs_out, uint32_t * argmax_out);
+
 /* ---- Presence / frequency penalties and logit bias in the device sampler ----
  * What the reference's chat program does before every draw (chat_with_bot.py:243-258: for each token n generated so far in this response,
  * logits[n] -= PRESENCE_PENALTY + token_counts[n] * FREQUENCY_PENALTY, defaults 0.2 / 0.2) and what sample_logits' logit_bias adds

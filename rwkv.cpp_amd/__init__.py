@@ -6,6 +6,7 @@ repo root to sys.path and use `importlib.import_module("rwkv.cpp_amd")` is NOT p
 from .rwkv_cpp import (  # noqa: F401
     HOOKS_LIB_PATH,
     LIB_PATH,
+    NO_TARGET,
     PenaltyParams,
     RWKVBatch,
     RWKVContext,

@@ -281,6 +281,61 @@ RWKV_API bool rwkv_mi_eval_resident(struct rwkv_context * ctx, const uint32_t * 
     return fetch_outputs(ctx, nullptr, logits_out);
 }
 
+// the targets of a scoring call (checked with the other arguments, before anything changes)
+static bool check_targets(rwkv_context * ctx, const uint32_t * targets, size_t n, const float * logprobs_out) {
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, targets != nullptr || logprobs_out == nullptr, "logprobs_out is given without targets");
+    const size_t n_vocab = (size_t) ctx->model->n_vocab();
+    for (size_t i = 0; targets && i < n; i++)
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, targets[i] < n_vocab || targets[i] == RWKV_MI_NO_TARGET,
+                     "Target at index %zu (%" PRIu32 ") is out of range (0 .. %zu, or RWKV_MI_NO_TARGET)", i, targets[i], n_vocab - 1);
+    return true;
+}
+
+// Per-position scoring from the resident state: the pieces of run_tokens, each with the head on every row (engine.hip, ScorePass); a
+// 1-token piece takes the single-token path as ever and its row is scored from ctx->d_logits.
+RWKV_API bool rwkv_mi_score_resident(struct rwkv_context * ctx, const uint32_t * tokens, size_t n_tokens, const uint32_t * targets,
+                                     float * logprobs_out, uint32_t * argmax_out, float * logits_all_out) {
+    ctx->last_error = RWKV_ERROR_NONE;
+    RW_NO_PIPELINE(ctx, false);
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, tokens != nullptr && n_tokens > 0, "tokens is NULL or empty");
+    const size_t n_vocab = (size_t) ctx->model->n_vocab();
+    for (size_t i = 0; i < n_tokens; i++) RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, tokens[i] < n_vocab, "Token at index %zu is out of range", i);
+    if (!check_targets(ctx, targets, n_tokens, logprobs_out)) return false;
+    if (!logprobs_out && !argmax_out && !logits_all_out) {   // nothing to report: rwkv_mi_eval_resident without logits
+        if (!run_tokens(ctx, tokens, n_tokens, false)) return false;
+        return fetch_outputs(ctx, nullptr, nullptr);
+    }
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, ctx->model->has_head, "this stage has no head");
+    HIP_CTX_OK(ctx, hipSetDevice(ctx->model->device));
+    if (!ensure_score(ctx, (int64_t) (n_tokens < k_max_tokens_per_pass ? n_tokens : k_max_tokens_per_pass))) return false;
+    size_t done = 0;
+    while (done < n_tokens) {
+        const size_t step = (n_tokens - done) < k_max_tokens_per_pass ? (n_tokens - done) : k_max_tokens_per_pass;
+        if (!upload_tokens(ctx, tokens + done, step)) return false;   // (drains the stream: the staging of the targets is free as well)
+        if (logprobs_out) {
+            memcpy(ctx->h_score_targets, targets + done, step * sizeof(uint32_t));
+            HIP_CTX_OK(ctx, hipMemcpyAsync(ctx->d_score_targets, ctx->h_score_targets, step * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+        }
+        if (step == 1) {
+            if (!forward_decode(ctx, true)) return false;
+            launch_score_rows(ctx->d_logits, 1, (int) n_vocab, logprobs_out ? ctx->d_score_targets : nullptr, logprobs_out ? ctx->d_score_logprobs : nullptr,
+                              argmax_out ? ctx->d_score_argmax : nullptr, ctx->stream);
+            if (logits_all_out) HIP_CTX_OK(ctx, hipMemcpyAsync(logits_all_out + done * n_vocab, ctx->d_logits, n_vocab * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+        } else {
+            ScorePass sp;
+            sp.targets = sp.logprobs = logprobs_out != nullptr;
+            sp.argmax = argmax_out != nullptr;
+            sp.h_logits_all = logits_all_out ? logits_all_out + done * n_vocab : nullptr;
+            sp.keep_last = done + step == n_tokens;
+            if (!forward(ctx, (int64_t) step, true, &sp)) return false;
+        }
+        if (logprobs_out) HIP_CTX_OK(ctx, hipMemcpyAsync(logprobs_out + done, ctx->d_score_logprobs, step * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+        if (argmax_out) HIP_CTX_OK(ctx, hipMemcpyAsync(argmax_out + done, ctx->d_score_argmax, step * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        done += step;
+    }
+    return fetch_outputs(ctx, nullptr, nullptr);
+}
+
 RWKV_API bool rwkv_mi_decode_greedy(struct rwkv_context * ctx, uint32_t first_token, size_t n_tokens, uint32_t * tokens_out, float * elapsed_ms) {
     ctx->last_error = RWKV_ERROR_NONE;
     const size_t n_vocab = (size_t) ctx->model->n_vocab();
@@ -1231,6 +1286,34 @@ RWKV_API bool rwkv_mi_batch_eval_ragged(struct rwkv_mi_batch * B, const uint32_t
     if (!batch_upload_ragged(B, slots, lens, tokens, n, T)) return false;
     if (!forward_segs(run, B->pass, (int64_t) T, logits_out != nullptr)) { (void) hipStreamSynchronize(run->stream); return batch_fail_through(B); }
     if (logits_out) BATCH_HIP_OK(B, hipMemcpyAsync(logits_out, run->d_logits, n * (size_t) ctx->model->n_vocab() * sizeof(float), hipMemcpyDeviceToHost, run->stream));
+    BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));
+    for (size_t i = 0; i < n; i++) B->parity[slots[i]] ^= 1;
+    return true;
+}
+
+// The ragged pass with the head on every token (engine.hip, ScorePass): T rows of log-probs / argmax in token order.
+RWKV_API bool rwkv_mi_batch_score_ragged(struct rwkv_mi_batch * B, const uint32_t * slots, const uint32_t * lens, const uint32_t * tokens, const uint32_t * targets,
+                                         size_t n, float * logprobs_out, uint32_t * argmax_out) {
+    rwkv_context * ctx = B->ctx;
+    ctx->last_error = RWKV_ERROR_NONE;
+    size_t T = 0;
+    if (!batch_check_ragged(B, slots, lens, tokens, n, &T) || !check_targets(ctx, targets, T, logprobs_out)) return false;
+    rwkv_context * run = B->run;
+    run->print_errors = ctx->print_errors;
+    BATCH_HIP_OK(B, hipSetDevice(ctx->model->device));
+    const bool scoring = logprobs_out || argmax_out;
+    if (scoring && !ensure_score(run, (int64_t) T)) return batch_fail_through(B);
+    if (!batch_upload_ragged(B, slots, lens, tokens, n, T)) return false;   // (drains the stream: the staging of the targets is free as well)
+    if (logprobs_out) {
+        memcpy(run->h_score_targets, targets, T * sizeof(uint32_t));
+        BATCH_HIP_OK(B, hipMemcpyAsync(run->d_score_targets, run->h_score_targets, T * sizeof(uint32_t), hipMemcpyHostToDevice, run->stream));
+    }
+    ScorePass sp;
+    sp.targets = sp.logprobs = logprobs_out != nullptr;
+    sp.argmax = argmax_out != nullptr;
+    if (!forward_segs(run, B->pass, (int64_t) T, scoring, nullptr, scoring ? &sp : nullptr)) { (void) hipStreamSynchronize(run->stream); return batch_fail_through(B); }
+    if (logprobs_out) BATCH_HIP_OK(B, hipMemcpyAsync(logprobs_out, run->d_score_logprobs, T * sizeof(float), hipMemcpyDeviceToHost, run->stream));
+    if (argmax_out) BATCH_HIP_OK(B, hipMemcpyAsync(argmax_out, run->d_score_argmax, T * sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream));
     BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));
     for (size_t i = 0; i < n; i++) B->parity[slots[i]] ^= 1;
     return true;

@@ -269,6 +269,11 @@ void destroy_context(rwkv_context * ctx) {
     if (ctx->d_rng_counter) (void) hipFree(ctx->d_rng_counter);
     if (ctx->d_counts) (void) hipFree(ctx->d_counts);
     if (ctx->d_bias) (void) hipFree(ctx->d_bias);
+    if (ctx->d_score) (void) hipFree(ctx->d_score);
+    if (ctx->d_score_targets) (void) hipFree(ctx->d_score_targets);
+    if (ctx->h_score_targets) (void) hipHostFree(ctx->h_score_targets);
+    if (ctx->d_score_logprobs) (void) hipFree(ctx->d_score_logprobs);
+    if (ctx->d_score_argmax) (void) hipFree(ctx->d_score_argmax);
     if (ctx->h_tokens) (void) hipHostFree(ctx->h_tokens);
     if (ctx->ev0) (void) hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void) hipEventDestroy(ctx->ev1);
@@ -323,6 +328,50 @@ bool ensure_scratch(rwkv_context * ctx, int64_t T) {
     return true;
 }
 
+// Scoring buffers of a context (model.h, ScorePass): everything new is allocated before anything old is released.
+bool ensure_score(rwkv_context * ctx, int64_t rows) {
+    const size_t V = (size_t) ctx->model->n_vocab();
+    float * chunk = nullptr;
+    int64_t R = ctx->score_R;
+    hipError_t e = hipSuccess;
+    if (!ctx->d_score) {
+        R = (int64_t) (((size_t) 64 << 20) / (4 * V));
+        R = R < 32 ? 32 : (R > 1024 ? 1024 : R);
+        // (read here, once per context: tests force many chunks on small models with it)
+        if (const char * v = getenv("RWKV_MI_SCORE_ROWS")) { const long long n = atoll(v); if (n >= 1) R = (int64_t) n; }
+        e = hipMalloc((void **) &chunk, (size_t) R * V * sizeof(float));
+    }
+    uint32_t * dt = nullptr, * ht = nullptr, * da = nullptr;
+    float * dl = nullptr;
+    const int64_t cap = rows < 1024 ? 1024 : rows;
+    const bool grow = rows > ctx->score_cap;
+    if (grow) {
+        if (e == hipSuccess) e = hipMalloc((void **) &dt, (size_t) cap * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipHostMalloc((void **) &ht, (size_t) cap * sizeof(uint32_t), hipHostMallocDefault);
+        if (e == hipSuccess) e = hipMalloc((void **) &dl, (size_t) cap * sizeof(float));
+        if (e == hipSuccess) e = hipMalloc((void **) &da, (size_t) cap * sizeof(uint32_t));
+        if (e == hipSuccess && ctx->score_cap) e = hipStreamSynchronize(ctx->stream);   // (an earlier call's copies may still use the old words)
+    }
+    if (e != hipSuccess) {
+        if (chunk) (void) hipFree(chunk);
+        if (dt) (void) hipFree(dt);
+        if (ht) (void) hipHostFree(ht);
+        if (dl) (void) hipFree(dl);
+        if (da) (void) hipFree(da);
+        (void) hipGetLastError();
+    }
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the scoring buffers (%lld rows of %zu logits): %s", (long long) R, V, hipGetErrorString(e));
+    if (chunk) { ctx->d_score = chunk; ctx->score_R = R; }
+    if (grow) {
+        if (ctx->d_score_targets) (void) hipFree(ctx->d_score_targets);
+        if (ctx->h_score_targets) (void) hipHostFree(ctx->h_score_targets);
+        if (ctx->d_score_logprobs) (void) hipFree(ctx->d_score_logprobs);
+        if (ctx->d_score_argmax) (void) hipFree(ctx->d_score_argmax);
+        ctx->d_score_targets = dt; ctx->h_score_targets = ht; ctx->d_score_logprobs = dl; ctx->d_score_argmax = da; ctx->score_cap = cap;
+    }
+    return true;
+}
+
 std::atomic<int> g_test_fail_state_init{0};   // (tests: librwkv_testhooks.so arms it; the next state initialisation fails once)
 
 bool state_from_host(rwkv_context * ctx, const float * state_in) {
@@ -359,6 +408,7 @@ struct Runner {
     int64_t T, D, H, S;
     rwkv_context::Buf & b;
 
+    bool copy_failed = false;   // score mode: a copy of the head's logits could not be enqueued
     bool failed = false;   // a launch of the pass could not be made (allocation failure): its outputs are not valid
     // The state the pass reads / writes: the context's state[cur] -> state[cur ^ 1], or in row mode (batched decode, rwkv_mi_batch_*)
     // state.rows, where row t is its own sequence. Row mode never takes the single-token paths (persistent / fused), T == 1 included.
@@ -368,6 +418,7 @@ struct Runner {
     // single-token path here either.
     StateRef state;
     const SegPass * seg = nullptr;
+    const ScorePass * score = nullptr;   // score mode: the head runs on every row of the pass (run_head_score)
     // the WKV state of the segments the _segs kernels run (seg->d_short), at offset so
     StateRef seg_short(int64_t so) const { StateRef s = state.at(so); s.segs = seg->d_short; s.n_segs = seg->n_short; return s; }
 
@@ -685,7 +736,29 @@ struct Runner {
         }
         return false;
     }
+    // score mode (sequence and segment mode): ln_out and the head on ALL T rows, a chunk of ctx->score_R rows at a time -- the chunk's
+    // logits, k_score_rows on them, optionally their copy to the host; the product is chosen on the chunk's row count like row mode's head
+    void run_head_score() {
+        const int64_t Tall = T, R = ctx->score_R, V = m.n_vocab();
+        drop_pre();
+        int64_t rows = 0;
+        for (int64_t r0 = 0; r0 < Tall; r0 += R) {
+            rows = Tall - r0 < R ? Tall - r0 : R;
+            launch_layernorm(b.x + r0 * D, rows, D, f(m.ln_out_w), f(m.ln_out_b), b.xn, st);
+            T = rows;
+            mm(m.head, b.xn, ctx->d_score);
+            T = Tall;
+            launch_score_rows(ctx->d_score, rows, (int) V, score->targets ? ctx->d_score_targets + r0 : nullptr,
+                              score->logprobs ? ctx->d_score_logprobs + r0 : nullptr, score->argmax ? ctx->d_score_argmax + r0 : nullptr, st);
+            if (score->h_logits_all &&
+                hipMemcpyAsync(score->h_logits_all + r0 * V, ctx->d_score, (size_t) (rows * V) * sizeof(float), hipMemcpyDeviceToHost, st) != hipSuccess) copy_failed = true;
+        }
+        // the context's own logits are those of the last token, as after a plain pass (the sampler and rwkv_mi_logits_store read them)
+        if (score->keep_last &&
+            hipMemcpyAsync(ctx->d_logits, ctx->d_score + (rows - 1) * V, (size_t) V * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) copy_failed = true;
+    }
     void run_head() {
+        if (score) { run_head_score(); return; }
         if (state.rows) {
             // row mode: every row is the last token of its sequence -- ln_out on all rows, one product with T rows into [T][n_vocab]
             launch_layernorm(b.x, T, D, f(m.ln_out_w), f(m.ln_out_b), b.xn, st);
@@ -724,10 +797,12 @@ uint32_t * folded_argmax_target(const rwkv_context * ctx) {
 
 int64_t handoff_len(const Model & m) { return m.arch_major == 7 ? 2 * m.n_embed() : m.n_embed(); }
 
-bool forward(rwkv_context * ctx, int64_t T, bool want_logits) {
+bool forward(rwkv_context * ctx, int64_t T, bool want_logits, const ScorePass * score) {
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, !score || (T > 1 && ctx->d_score), "a scoring pass needs its buffers and at least two tokens");
     if (!ensure_scratch(ctx, T)) return false;
     Model & m = *ctx->model;
     Runner r{ctx, m, ctx->stream, T, m.n_embed(), m.head_count, m.head_size, ctx->b};
+    r.score = score;
     const bool chained = T == 1 && ctx->mega;
     if (chained) mega_chain_begin(ctx);
     r.run(want_logits);
@@ -735,6 +810,7 @@ bool forward(rwkv_context * ctx, int64_t T, bool want_logits) {
     ctx->cur ^= 1;
     HIP_CTX_OK(ctx, hipGetLastError());
     RW_CTX_CHECK(ctx, RWKV_ERROR_GRAPH | RWKV_ERROR_ALLOC, false, !r.failed, "a sequence-mode product could not be launched (out of device memory for the tile-major weight image?)");
+    RW_CTX_CHECK(ctx, RWKV_ERROR_GRAPH, false, !r.copy_failed, "a copy of the scoring pass's logits could not be enqueued");
     return true;
 }
 
@@ -809,11 +885,13 @@ bool seg_takes_seq_kernel(const Model & m, int64_t len) {
 // One ragged pass of T tokens (ctx->d_tokens) in p.n segments: segment i = tokens [t0, t1) of the sequence whose state goes
 // segs[i].in -> segs[i].out. Logits: ctx->d_logits[n][n_vocab], those of each segment's last token. The pass takes the place in the
 // per-device chain that forward_rows takes, the sampler included.
-bool forward_segs(rwkv_context * ctx, const SegPass & p, int64_t T, bool want_logits, const RowSampler * sample) {
+bool forward_segs(rwkv_context * ctx, const SegPass & p, int64_t T, bool want_logits, const RowSampler * sample, const ScorePass * score) {
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, !score || (!sample && ctx->d_score), "a scoring pass needs its buffers and takes no sampler");
     if (!ensure_scratch(ctx, T)) { (void) hipGetLastError(); ctx->last_error |= RWKV_ERROR_ALLOC; return false; }
     Model & m = *ctx->model;
     Runner r{ctx, m, ctx->stream, T, m.n_embed(), m.head_count, m.head_size, ctx->b};
     r.seg = &p;
+    r.score = score;
     r.state.segs = p.d_segs; r.state.n_segs = p.n; r.state.seg_of = p.d_seg_of;
     mega_chain_begin(ctx);
     r.run(want_logits);
@@ -824,6 +902,7 @@ bool forward_segs(rwkv_context * ctx, const SegPass & p, int64_t T, bool want_lo
     mega_chain_end(ctx);
     HIP_CTX_OK(ctx, hipGetLastError());
     RW_CTX_CHECK(ctx, RWKV_ERROR_GRAPH | RWKV_ERROR_ALLOC, false, !r.failed, "a product of the ragged pass could not be launched (out of device memory for the tile-major weight image?)");
+    RW_CTX_CHECK(ctx, RWKV_ERROR_GRAPH, false, !r.copy_failed, "a copy of the scoring pass's logits could not be enqueued");
     return true;
 }
 

@@ -142,6 +142,11 @@ void launch_fill_state_v4(float * state, int64_t n_layer, int64_t D, hipStream_t
 // Feeds the next embedding lookup of the on-device greedy decode loops.
 void launch_argmax(const float * logits, int64_t rows, int64_t n, uint32_t * out, uint32_t * hist, hipStream_t st);
 
+// Scoring (score.hip, k_score_rows): per row of logits[rows][n], argmax[row] by launch_argmax's rule and
+//   logprobs[row] = (float) ((double) l[targets[row]] - (m + log(sum_j exp((double) l[j] - m)))),  m = the row maximum, the sum in float64 in a fixed order;
+// a row whose target is UINT32_MAX (or >= n) gets 0. targets, logprobs and argmax may each be nullptr (targets == nullptr: every logprob is 0).
+void launch_score_rows(const float * logits, int64_t rows, int n, const uint32_t * targets, float * logprobs, uint32_t * argmax, hipStream_t st);
+
 // load-time transpose of att.time_maa_w2: [5][D][R] -> [5][R][D]
 void launch_transpose_w2(const float * src, float * dst, int64_t D, int64_t R, hipStream_t st);
 

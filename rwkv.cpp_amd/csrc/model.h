@@ -173,6 +173,16 @@ struct rwkv_context {
     uint32_t * d_counts = nullptr;                // penalised sampling (rwkv_mi_*_penalized): the context's occurrence table [n_vocab] and its bias table
     float *    d_bias = nullptr;                  // [n_vocab], allocated by the first call of that family; has_bias: a bias has been set and not cleared
     bool       has_bias = false;
+    // scoring (rwkv_mi_score_resident / rwkv_mi_batch_score_ragged; engine.hip ensure_score), allocated by the first scoring call: the chunk
+    // of the all-position head, [score_R][n_vocab] logits, and the per-row words of a pass for score_cap rows -- targets in (with their
+    // pinned staging), log-probs and argmax out
+    float *    d_score = nullptr;
+    int64_t    score_R = 0;
+    uint32_t * d_score_targets = nullptr;
+    uint32_t * h_score_targets = nullptr;
+    float *    d_score_logprobs = nullptr;
+    uint32_t * d_score_argmax = nullptr;
+    int64_t    score_cap = 0;
 
     // pinned host staging for tokens / logits
     uint32_t * h_tokens = nullptr;
@@ -222,7 +232,25 @@ bool state_to_host(rwkv_context * ctx, float * state_out);
 
 // Runs T tokens (already in ctx->d_tokens) through the layers of this stage. Reads state[cur], writes state[cur^1], flips cur.
 // x_in / x_out: residual stream hand-off for pipeline stages (nullptr on a full model). Logits land in ctx->d_logits.
-bool forward(rwkv_context * ctx, int64_t T, bool want_logits);
+// score: the head runs on EVERY row of the pass instead of the last one (see ScorePass); T >= 2 (a single token goes through forward_decode
+// and is scored from ctx->d_logits by the caller).
+struct ScorePass;
+bool forward(rwkv_context * ctx, int64_t T, bool want_logits, const ScorePass * score = nullptr);
+
+// Score mode of a pass (forward, forward_segs): ln_out and the head over all T rows in chunks of ctx->score_R rows into ctx->d_score, each
+// chunk followed by k_score_rows (score.hip) on the per-row words of the context -- row t of the pass reads ctx->d_score_targets[t] and writes
+// ctx->d_score_logprobs[t] / ctx->d_score_argmax[t] -- and, when h_logits_all is given, by a copy of the chunk's logits to the host. The
+// product kernel is chosen on the chunk's row count, as row mode's head chooses it on T: on the default arms both sides of the 32-row
+// threshold are bit-identical per row, so the chunking cannot be seen in the result. keep_last: the last row's logits also go to
+// ctx->d_logits, where the sampler and rwkv_mi_logits_store read them. ensure_score(ctx, T) must have succeeded.
+struct ScorePass {
+    bool targets = false, logprobs = false, argmax = false;   // which of the per-row words are read / written
+    float * h_logits_all = nullptr;                           // host [T][n_vocab], or nullptr
+    bool keep_last = false;
+};
+// the chunk buffer (first call: score_R = clamp(64 MiB / (4 n_vocab), 32, 1024) rows, or RWKV_MI_SCORE_ROWS >= 1) and per-row words for
+// `rows` rows; false with RWKV_ERROR_ALLOC, nothing changed, when they cannot be allocated
+bool ensure_score(rwkv_context * ctx, int64_t rows);
 
 // batched decode (engine.hip): the batch's own context (model, stream, scratch, tokens, [max_rows][n_vocab] logits; a member of the per-device
 // chain of persistent launches) and one pass of T rows, row t from state d_rows[t].in into d_rows[t].out
@@ -243,7 +271,7 @@ struct SegPass {
     int64_t n = 0, n_short = 0, n_long = 0;
 };
 bool seg_takes_seq_kernel(const Model & m, int64_t len);
-bool forward_segs(rwkv_context * ctx, const SegPass & p, int64_t T, bool want_logits, const RowSampler * sample = nullptr);
+bool forward_segs(rwkv_context * ctx, const SegPass & p, int64_t T, bool want_logits, const RowSampler * sample = nullptr, const ScorePass * score = nullptr);
 
 // fused RWKV-6 decode layer (fused_v6.hip)
 bool   fused_v6_supported(const Model & m);

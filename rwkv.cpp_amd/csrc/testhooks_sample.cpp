@@ -1,8 +1,10 @@
-// testhooks_sample.cpp -- the sampler's entry point for tests/ ONLY (include/rwkv_testhooks_sample.h). `make` links it with every product
+// testhooks_sample.cpp -- the sampler's entry point for tests/ ONLY (include/rwkv_testhooks_sample.h) and the scoring kernel's
+// (include/rwkv_testhooks_score.h). `make` links it with every product
 // object into a third library, lib/librwkv_testhooks_sample.so; neither librwkv.so nor librwkv_testhooks.so carries it.
 #include "model.h"
 #include "rwkv_mi355x.h"
 #include "rwkv_testhooks_sample.h"
+#include "rwkv_testhooks_score.h"
 
 #include <vector>
 
@@ -39,6 +41,28 @@ RWKV_API bool rwkv_mi_test_sample_rows(const float * logits, int64_t n_rows, int
              (!counters || hipMemcpy(counters, d_ctr, R * 8, hipMemcpyDeviceToHost) == hipSuccess);
     }
     for (void * p : {(void *) d_logits, (void *) d_probs, (void *) d_ctr, (void *) d_table, (void *) d_tok}) if (p) (void) hipFree(p);
+    RW_CHECK(RWKV_ERROR_GRAPH, false, ok, "HIP error: %s", hipGetErrorString(hipGetLastError()));
+    return true;
+}
+
+// Test hook: the scoring kernel on standalone logits.
+RWKV_API bool rwkv_test_score_rows(const float * logits, int64_t rows, int64_t n_vocab, const uint32_t * targets, float * logprobs_out, uint32_t * argmax_out) {
+    g_last_error = RWKV_ERROR_NONE;
+    RW_CHECK(RWKV_ERROR_ARGS, false, logits && rows > 0 && rows <= 65535 && n_vocab > 0 && n_vocab <= (int64_t) 1 << 24, "bad arguments");
+    const size_t R = (size_t) rows, V = (size_t) n_vocab;
+    float * d_logits = nullptr, * d_lp = nullptr;
+    uint32_t * d_tgt = nullptr, * d_am = nullptr;
+    bool ok = hipMalloc((void **) &d_logits, R * V * 4) == hipSuccess && hipMalloc((void **) &d_lp, R * 4) == hipSuccess &&
+              hipMalloc((void **) &d_tgt, R * 4) == hipSuccess && hipMalloc((void **) &d_am, R * 4) == hipSuccess &&
+              hipMemcpy(d_logits, logits, R * V * 4, hipMemcpyHostToDevice) == hipSuccess &&
+              (!targets || hipMemcpy(d_tgt, targets, R * 4, hipMemcpyHostToDevice) == hipSuccess);
+    if (ok) {
+        launch_score_rows(d_logits, rows, (int) n_vocab, targets ? d_tgt : nullptr, logprobs_out ? d_lp : nullptr, argmax_out ? d_am : nullptr, nullptr);
+        ok = hipDeviceSynchronize() == hipSuccess &&
+             (!logprobs_out || hipMemcpy(logprobs_out, d_lp, R * 4, hipMemcpyDeviceToHost) == hipSuccess) &&
+             (!argmax_out || hipMemcpy(argmax_out, d_am, R * 4, hipMemcpyDeviceToHost) == hipSuccess);
+    }
+    for (void * p : {(void *) d_logits, (void *) d_lp, (void *) d_tgt, (void *) d_am}) if (p) (void) hipFree(p);
     RW_CHECK(RWKV_ERROR_GRAPH, false, ok, "HIP error: %s", hipGetErrorString(hipGetLastError()));
     return true;
 }

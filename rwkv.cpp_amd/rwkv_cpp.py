@@ -27,6 +27,8 @@ PENALTY_SYMBOLS = ("rwkv_mi_batch_counts_reset", "rwkv_mi_batch_counts_add", "rw
                    "rwkv_mi_batch_eval_sample_penalized", "rwkv_mi_batch_eval_ragged_sample_penalized", "rwkv_mi_batch_decode_sample_penalized",
                    "rwkv_mi_counts_reset", "rwkv_mi_counts_add", "rwkv_mi_counts_store", "rwkv_mi_logit_bias_set", "rwkv_mi_rng_seek",
                    "rwkv_mi_sample_penalized", "rwkv_mi_decode_sample_penalized")
+SCORE_SYMBOLS = ("rwkv_mi_score_resident", "rwkv_mi_batch_score_ragged")
+NO_TARGET = 0xFFFFFFFF   # RWKV_MI_NO_TARGET: a position that is not scored (its log-prob is 0)
 P_FLOAT = ctypes.POINTER(ctypes.c_float)
 P_UINT32 = ctypes.POINTER(ctypes.c_uint32)
 
@@ -221,6 +223,15 @@ class RWKVSharedLibrary:
                                                       ctypes.c_float, ctypes.c_float, P_UINT32, P_FLOAT]
         for name in PENALTY_SYMBOLS:
             getattr(L, name).restype = ctypes.c_bool
+        # scoring: log-prob / argmax at every position
+        if hasattr(L, "rwkv_mi_score_resident"):   # (absent from older A/B builds loaded through RWKV_LIB_DIR)
+            L.rwkv_mi_score_resident.argtypes = [c_ctx, P_UINT32, ctypes.c_size_t, P_UINT32, P_FLOAT, P_UINT32, P_FLOAT]
+            L.rwkv_mi_batch_score_ragged.argtypes = [c_batch, P_UINT32, P_UINT32, P_UINT32, P_UINT32, ctypes.c_size_t, P_FLOAT, P_UINT32]
+            for name in SCORE_SYMBOLS:
+                getattr(L, name).restype = ctypes.c_bool
+        if hasattr(L, "rwkv_test_score_rows"):   # (librwkv_testhooks_sample.so only)
+            L.rwkv_test_score_rows.argtypes = [P_FLOAT, ctypes.c_int64, ctypes.c_int64, P_UINT32, P_FLOAT, P_UINT32]
+            L.rwkv_test_score_rows.restype = ctypes.c_bool
         if hasattr(L, "rwkv_mi_test_sample_rows"):   # (librwkv_testhooks_sample.so only)
             L.rwkv_mi_test_sample_rows.argtypes = [P_FLOAT, ctypes.c_int64, ctypes.c_int64, P_SAMPLE_PARAMS, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int, P_UINT32]
             L.rwkv_mi_test_sample_rows.restype = ctypes.c_bool
@@ -414,6 +425,36 @@ class RWKVModel:
         if not self._library.library.rwkv_mi_eval_resident(self._ctx.ptr, arr, len(tokens), ctypes.cast(_ptr(logits), P_FLOAT)):
             raise ValueError("rwkv_mi_eval_resident failed")
         return logits
+
+    def score_resident(self, tokens: List[int], targets: Optional[List[int]] = None, want_argmax: bool = True, want_logits: bool = False):
+        """Feeds `tokens` from the resident state (as eval_resident) and reports the prediction after EACH of them, from one pass:
+        (logprobs, argmax, logits). logprobs[t] = log P(targets[t] | tokens[..t]) as float32 (0 where targets[t] is NO_TARGET; None without
+        targets), argmax[t] the most likely next token (None unless want_argmax), logits [n][n_vocab] (None unless want_logits)."""
+        t = _u32(tokens).reshape(-1)
+        tg = None if targets is None else _u32(targets).reshape(-1)
+        if tg is not None and tg.size != t.size:
+            raise ValueError("tokens and targets differ in length")
+        logprobs = np.empty(t.size, dtype=np.float32) if tg is not None else None
+        argmax = np.empty(t.size, dtype=np.uint32) if want_argmax else None
+        logits = np.empty((t.size, self._logits_buffer_element_count), dtype=np.float32) if want_logits else None
+        self._mi("rwkv_mi_score_resident", t.ctypes.data_as(P_UINT32), t.size, ctypes.cast(_ptr(tg), P_UINT32), ctypes.cast(_ptr(logprobs), P_FLOAT),
+                 ctypes.cast(_ptr(argmax), P_UINT32), ctypes.cast(_ptr(logits), P_FLOAT))
+        return logprobs, argmax, logits
+
+    def perplexity(self, tokens: List[int], ignore_first_n_tokens: int = 0) -> Tuple[float, float]:
+        """(mean loss, exp(mean loss)) of `tokens` from the resident state -- the loop of the reference's measure_pexplexity.py:71-85 in one
+        pass: tokens[:-1] are fed, position i is scored against tokens[i + 1] and counts when ignore_first_n_tokens == 0 or
+        i + 1 >= ignore_first_n_tokens; the mean is taken in float64 on the host."""
+        t = _u32(tokens).reshape(-1)
+        if t.size < 2:
+            raise ValueError("perplexity needs at least two tokens")
+        logprobs, _, _ = self.score_resident(t[:-1], t[1:], want_argmax=False)
+        i = np.arange(t.size - 1)
+        counted = (i + 1 >= ignore_first_n_tokens) if ignore_first_n_tokens else np.ones(t.size - 1, dtype=bool)
+        if not counted.any():
+            raise ValueError("ignore_first_n_tokens leaves no position to count")
+        loss = float(-(logprobs[counted].astype(np.float64)).sum() / int(counted.sum()))
+        return loss, float(np.exp(loss))
 
     def decode_greedy(self, first_token: int, n_tokens: int) -> Tuple[np.ndarray, float]:
         out = np.empty(n_tokens, dtype=np.uint32)
@@ -738,6 +779,25 @@ class RWKVBatch:
                                                         s.size, params, out.ctypes.data_as(P_UINT32), ctypes.cast(_ptr(logits), P_FLOAT)):
             self._fail("rwkv_mi_batch_eval_ragged_sample")
         return (out, logits) if want_logits else out
+
+    def score_ragged(self, slots: List[int], token_lists: List[List[int]], target_lists: Optional[List[List[int]]] = None, want_argmax: bool = True):
+        """token_lists[i] to slot slots[i], all rows in ONE pass (as eval_ragged), with the prediction after EVERY token: (list of logprob
+        arrays, list of argmax arrays), one array per row; target_lists[i][t] is scored against the logits after token_lists[i][t]. Each row
+        equals RWKVModel.score_resident of its tokens alone, bit for bit. A list is None when it was not asked for."""
+        s, lens, toks = self._ragged(slots, token_lists)
+        tg = None
+        if target_lists is not None:
+            rows = [_u32(r).reshape(-1) for r in target_lists]
+            if [r.size for r in rows] != lens.tolist():
+                raise ValueError("token_lists and target_lists differ in shape")
+            tg = np.ascontiguousarray(np.concatenate(rows)) if rows else _u32([])
+        logprobs = np.empty(toks.size, dtype=np.float32) if tg is not None else None
+        argmax = np.empty(toks.size, dtype=np.uint32) if want_argmax else None
+        if not self._L.rwkv_mi_batch_score_ragged(self._ptr, s.ctypes.data_as(P_UINT32), lens.ctypes.data_as(P_UINT32), toks.ctypes.data_as(P_UINT32),
+                                                  ctypes.cast(_ptr(tg), P_UINT32), s.size, ctypes.cast(_ptr(logprobs), P_FLOAT), ctypes.cast(_ptr(argmax), P_UINT32)):
+            self._fail("rwkv_mi_batch_score_ragged")
+        cuts = np.cumsum(lens.astype(np.int64))[:-1]
+        return (None if logprobs is None else np.split(logprobs, cuts)), (None if argmax is None else np.split(argmax, cuts))
 
     def rng_seek(self, slot: int, counter: int) -> None:
         """Sets a slot's draw counter (0 for a new request in a reused slot)."""

@@ -14,6 +14,17 @@ using namespace rwkvmi;
 #define HIP_CTX_OK(CTX, CALL) \
     do { hipError_t e_ = (CALL); RW_CTX_CHECK((CTX), RWKV_ERROR_GRAPH, false, e_ == hipSuccess, "HIP error: %s", hipGetErrorString(e_)); } while (0)
 
+// A temporary device buffer of a call, freed on every exit from its scope (after the caller has drained the stream that uses it).
+template <typename T> struct DevBuf {
+    T * p = nullptr;
+    ~DevBuf() { if (p) (void) hipFree(p); }
+    hipError_t alloc(size_t count) { return hipMalloc((void **) &p, count * sizeof(T)); }
+    // host words into the buffer on `st`
+    bool upload(const T * src, size_t count, hipStream_t st) {
+        return alloc(count) == hipSuccess && hipMemcpyAsync(p, src, count * sizeof(T), hipMemcpyHostToDevice, st) == hipSuccess;
+    }
+};
+
 // Sequence calls are cut into pieces of at most this many tokens internally (bounds scratch memory; results do not
 // depend on the cut because every kernel is per-token order-preserving).
 static const size_t k_max_tokens_per_pass = 1024;
@@ -344,8 +355,8 @@ RWKV_API bool rwkv_mi_decode_greedy(struct rwkv_context * ctx, uint32_t first_to
     if (!ctx->stages.empty()) { struct rwkv_context * one[1] = {ctx}; return pipeline_decode_greedy(one, 1, &first_token, n_tokens, tokens_out, elapsed_ms); }
     HIP_CTX_OK(ctx, hipSetDevice(ctx->model->device));
     if (!upload_tokens(ctx, &first_token, 1)) return false;
-    struct DevBuf { uint32_t * p = nullptr; ~DevBuf() { if (p) (void) hipFree(p); } } hist;   // freed on every exit
-    HIP_CTX_OK(ctx, hipMalloc((void **) &hist.p, n_tokens * sizeof(uint32_t)));
+    DevBuf<uint32_t> hist;   // freed on every exit
+    HIP_CTX_OK(ctx, hist.alloc(n_tokens));
     uint32_t * d_hist = hist.p;
     HIP_CTX_OK(ctx, hipStreamSynchronize(ctx->stream));
     // persist_v47.hip: the launch itself picks the token, leaves it where its own embedding lookup reads it and appends it to the history
@@ -386,49 +397,6 @@ static bool ensure_sampler(rwkv_context * ctx) {
     return true;
 }
 
-// Samples one token from the logits of the last evaluation on the device (reference: python/sampling.py sample_logits, run there on
-// the host after downloading the logits). u in [0, 1): the caller's uniform random number; u < 0: the context's generator (seed).
-RWKV_API bool rwkv_mi_sample(struct rwkv_context * ctx, float temperature, float top_p, float u, uint64_t seed, uint32_t * token_out) {
-    ctx->last_error = RWKV_ERROR_NONE;
-    RW_NO_PIPELINE(ctx, false);
-    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, temperature >= 0.0f && top_p >= 0.0f && top_p <= 1.0f && u < 1.0f && token_out, "bad sampling arguments");
-    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, ctx->model->has_head, "this stage has no head");
-    HIP_CTX_OK(ctx, hipSetDevice(ctx->model->device));
-    if (!ensure_sampler(ctx)) return false;
-    launch_sample(ctx->d_logits, (int) ctx->model->n_vocab(), temperature, top_p, u, seed, ctx->d_rng_counter, ctx->d_probs, ctx->d_next_token, nullptr, 0, ctx->stream);
-    HIP_CTX_OK(ctx, hipMemcpyAsync(token_out, ctx->d_next_token, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_CTX_OK(ctx, hipStreamSynchronize(ctx->stream));
-    return true;
-}
-
-// Sampling decode loop entirely on the device: feeds first_token, then n_tokens - 1 times a token sampled (temperature, top_p, generator
-// seeded with `seed`) from the previous logits. tokens_out[i] = token sampled after step i.
-RWKV_API bool rwkv_mi_decode_sample(struct rwkv_context * ctx, uint32_t first_token, size_t n_tokens, float temperature, float top_p, uint64_t seed,
-                                    uint32_t * tokens_out, float * elapsed_ms) {
-    ctx->last_error = RWKV_ERROR_NONE;
-    RW_NO_PIPELINE(ctx, false);
-    const size_t n_vocab = (size_t) ctx->model->n_vocab();
-    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, first_token < n_vocab && n_tokens > 0, "bad arguments");
-    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, temperature >= 0.0f && top_p >= 0.0f && top_p <= 1.0f, "bad sampling arguments");
-    HIP_CTX_OK(ctx, hipSetDevice(ctx->model->device));
-    if (!upload_tokens(ctx, &first_token, 1) || !ensure_sampler(ctx)) return false;
-    HIP_CTX_OK(ctx, hipMemsetAsync(ctx->d_rng_counter, 0, 8, ctx->stream));
-    struct DevBuf { uint32_t * p = nullptr; ~DevBuf() { if (p) (void) hipFree(p); } } hist;
-    HIP_CTX_OK(ctx, hipMalloc((void **) &hist.p, n_tokens * sizeof(uint32_t)));
-    HIP_CTX_OK(ctx, hipStreamSynchronize(ctx->stream));
-    HIP_CTX_OK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    for (size_t i = 0; i < n_tokens; i++) {
-        if (!forward_decode(ctx, true)) return false;
-        // the sampled token is written where the embedding kernel of the next step reads it
-        launch_sample(ctx->d_logits, (int) n_vocab, temperature, top_p, -1.0f, seed, ctx->d_rng_counter, ctx->d_probs, ctx->d_tokens, hist.p, (int) i, ctx->stream);
-    }
-    HIP_CTX_OK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-    if (tokens_out) HIP_CTX_OK(ctx, hipMemcpyAsync(tokens_out, hist.p, n_tokens * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (!fetch_outputs(ctx, nullptr, nullptr)) return false;
-    if (elapsed_ms) HIP_CTX_OK(ctx, hipEventElapsedTime(elapsed_ms, ctx->ev0, ctx->ev1));
-    return true;
-}
-
 // ---- penalised sampling (rwkv_mi_*_penalized, rwkv_mi_*counts_*, rwkv_mi_*logit_bias_set): what contexts and batches share ----
 
 // the arguments of counts_add / logit_bias_set / a penalty (checked before anything changes; errors are reported on ctx)
@@ -460,21 +428,12 @@ static bool check_penalty(rwkv_context * ctx, float presence, float frequency, s
     return true;
 }
 
-// host words into a temporary device buffer on `st`; freed on scope exit (after the caller has drained the stream)
-struct DevWords {
-    void * p = nullptr;
-    ~DevWords() { if (p) (void) hipFree(p); }
-    bool upload(const void * src, size_t bytes, hipStream_t st) {
-        return hipMalloc(&p, bytes) == hipSuccess && hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, st) == hipSuccess;
-    }
-};
-
 // count[tokens[i]] += 1 on the device (arguments checked); drains st
 static bool table_counts_add(rwkv_context * ctx, uint32_t * count, const uint32_t * tokens, size_t n, hipStream_t st) {
     if (n == 0) return true;
-    DevWords d;
-    bool ok = d.upload(tokens, n * sizeof(uint32_t), st);
-    if (ok) launch_count_add(count, (const uint32_t *) d.p, (int64_t) n, (int) ctx->model->n_vocab(), st);
+    DevBuf<uint32_t> d;
+    bool ok = d.upload(tokens, n, st);
+    if (ok) launch_count_add(count, d.p, (int64_t) n, (int) ctx->model->n_vocab(), st);
     ok = ok && hipGetLastError() == hipSuccess;
     ok = hipStreamSynchronize(st) == hipSuccess && ok;
     RW_CTX_CHECK(ctx, RWKV_ERROR_GRAPH, false, ok, "HIP error: %s", hipGetErrorString(hipGetLastError()));
@@ -484,10 +443,10 @@ static bool table_counts_add(rwkv_context * ctx, uint32_t * count, const uint32_
 // bias = 0, then bias[ids[i]] = values[i] on the device (arguments checked, n > 0); drains st
 static bool table_bias_set(rwkv_context * ctx, float * bias, const uint32_t * ids, const float * values, size_t n, hipStream_t st) {
     const int64_t n_vocab = ctx->model->n_vocab();
-    DevWords di, dv;
-    bool ok = di.upload(ids, n * sizeof(uint32_t), st) && dv.upload(values, n * sizeof(float), st) &&
-              hipMemsetAsync(bias, 0, (size_t) n_vocab * sizeof(float), st) == hipSuccess;
-    if (ok) launch_bias_scatter(bias, (const uint32_t *) di.p, (const float *) dv.p, (int64_t) n, (int) n_vocab, st);
+    DevBuf<uint32_t> di;
+    DevBuf<float> dv;
+    bool ok = di.upload(ids, n, st) && dv.upload(values, n, st) && hipMemsetAsync(bias, 0, (size_t) n_vocab * sizeof(float), st) == hipSuccess;
+    if (ok) launch_bias_scatter(bias, di.p, dv.p, (int64_t) n, (int) n_vocab, st);
     ok = ok && hipGetLastError() == hipSuccess;
     ok = hipStreamSynchronize(st) == hipSuccess && ok;
     RW_CTX_CHECK(ctx, RWKV_ERROR_GRAPH, false, ok, "HIP error: %s", hipGetErrorString(hipGetLastError()));
@@ -565,46 +524,92 @@ RWKV_API bool rwkv_mi_rng_seek(struct rwkv_context * ctx, uint64_t counter) {
     return true;
 }
 
-// rwkv_mi_sample on the adjusted logits (the context's counts and bias); record: the chosen token is counted
-RWKV_API bool rwkv_mi_sample_penalized(struct rwkv_context * ctx, float temperature, float top_p, float u, uint64_t seed,
-                                       float presence, float frequency, uint32_t record, uint32_t * token_out) {
-    if (!penalty_call(ctx)) return false;
-    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, temperature >= 0.0f && top_p >= 0.0f && top_p <= 1.0f && u < 1.0f && token_out, "bad sampling arguments");
-    if (!check_penalty(ctx, presence, frequency, 0)) return false;
+// the penalty of a single-context draw: the context's counts and bias enter the logits; record: the chosen token is counted
+struct Penalty { float presence, frequency; uint32_t record; };
+
+// one draw from the context's logits into *out (and hist[hist_pos] when hist is given), on the adjusted logits when pen is given
+static void launch_draw(rwkv_context * ctx, float temperature, float top_p, float u, uint64_t seed, const Penalty * pen, uint32_t * out, uint32_t * hist, int hist_pos) {
+    const int n_vocab = (int) ctx->model->n_vocab();
+    if (pen) launch_pen_sample(ctx->d_logits, n_vocab, temperature, top_p, u, seed, ctx->d_rng_counter, pen->presence, pen->frequency, pen->record, ctx->d_counts,
+                               ctx->has_bias ? ctx->d_bias : nullptr, ctx->d_probs, out, hist, hist_pos, ctx->stream);
+    else launch_sample(ctx->d_logits, n_vocab, temperature, top_p, u, seed, ctx->d_rng_counter, ctx->d_probs, out, hist, hist_pos, ctx->stream);
+}
+
+// rwkv_mi_sample / rwkv_mi_sample_penalized behind their argument checks
+static bool sample_once(rwkv_context * ctx, float temperature, float top_p, float u, uint64_t seed, const Penalty * pen, uint32_t * token_out) {
     HIP_CTX_OK(ctx, hipSetDevice(ctx->model->device));
-    if (!ensure_sampler(ctx) || !ensure_penalty(ctx)) return false;
-    launch_pen_sample(ctx->d_logits, (int) ctx->model->n_vocab(), temperature, top_p, u, seed, ctx->d_rng_counter, presence, frequency, record,
-                      ctx->d_counts, ctx->has_bias ? ctx->d_bias : nullptr, ctx->d_probs, ctx->d_next_token, nullptr, 0, ctx->stream);
+    if (!ensure_sampler(ctx) || (pen && !ensure_penalty(ctx))) return false;
+    launch_draw(ctx, temperature, top_p, u, seed, pen, ctx->d_next_token, nullptr, 0);
     HIP_CTX_OK(ctx, hipMemcpyAsync(token_out, ctx->d_next_token, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIP_CTX_OK(ctx, hipStreamSynchronize(ctx->stream));
     return true;
 }
 
-// rwkv_mi_decode_sample with the penalised draw, every step recorded. It CONTINUES: neither the counts nor the draw counter are reset.
-RWKV_API bool rwkv_mi_decode_sample_penalized(struct rwkv_context * ctx, uint32_t first_token, size_t n_tokens, float temperature, float top_p, uint64_t seed,
-                                              float presence, float frequency, uint32_t * tokens_out, float * elapsed_ms) {
-    if (!penalty_call(ctx)) return false;
-    const size_t n_vocab = (size_t) ctx->model->n_vocab();
-    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, first_token < n_vocab && n_tokens > 0, "bad arguments");
-    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, temperature >= 0.0f && top_p >= 0.0f && top_p <= 1.0f, "bad sampling arguments");
-    if (!check_penalty(ctx, presence, frequency, 0)) return false;
-    HIP_CTX_OK(ctx, hipSetDevice(ctx->model->device));
-    if (!ensure_sampler(ctx) || !ensure_penalty(ctx) || !upload_tokens(ctx, &first_token, 1)) return false;
-    struct DevBuf { uint32_t * p = nullptr; ~DevBuf() { if (p) (void) hipFree(p); } } hist;
-    HIP_CTX_OK(ctx, hipMalloc((void **) &hist.p, n_tokens * sizeof(uint32_t)));
+// The sampling decode loop entirely on the device, for a context whose first token is uploaded and whose tables are allocated: n_tokens times a
+// step and a draw from its logits (the generator seeded with `seed`; every step recorded when pen is given). tokens_out[i] = token sampled after step i.
+static bool decode_sample_loop(rwkv_context * ctx, size_t n_tokens, float temperature, float top_p, uint64_t seed, const Penalty * pen,
+                               uint32_t * tokens_out, float * elapsed_ms) {
+    DevBuf<uint32_t> hist;
+    HIP_CTX_OK(ctx, hist.alloc(n_tokens));
     HIP_CTX_OK(ctx, hipStreamSynchronize(ctx->stream));
     HIP_CTX_OK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    const float * bias = ctx->has_bias ? ctx->d_bias : nullptr;
     for (size_t i = 0; i < n_tokens; i++) {
         if (!forward_decode(ctx, true)) return false;
-        launch_pen_sample(ctx->d_logits, (int) n_vocab, temperature, top_p, -1.0f, seed, ctx->d_rng_counter, presence, frequency, 1u, ctx->d_counts, bias,
-                          ctx->d_probs, ctx->d_tokens, hist.p, (int) i, ctx->stream);
+        // the sampled token is written where the embedding kernel of the next step reads it
+        launch_draw(ctx, temperature, top_p, -1.0f, seed, pen, ctx->d_tokens, hist.p, (int) i);
     }
     HIP_CTX_OK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
     if (tokens_out) HIP_CTX_OK(ctx, hipMemcpyAsync(tokens_out, hist.p, n_tokens * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     if (!fetch_outputs(ctx, nullptr, nullptr)) return false;
     if (elapsed_ms) HIP_CTX_OK(ctx, hipEventElapsedTime(elapsed_ms, ctx->ev0, ctx->ev1));
     return true;
+}
+
+// Samples one token from the logits of the last evaluation on the device (reference: python/sampling.py sample_logits, run there on
+// the host after downloading the logits). u in [0, 1): the caller's uniform random number; u < 0: the context's generator (seed).
+RWKV_API bool rwkv_mi_sample(struct rwkv_context * ctx, float temperature, float top_p, float u, uint64_t seed, uint32_t * token_out) {
+    ctx->last_error = RWKV_ERROR_NONE;
+    RW_NO_PIPELINE(ctx, false);
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, temperature >= 0.0f && top_p >= 0.0f && top_p <= 1.0f && u < 1.0f && token_out, "bad sampling arguments");
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, ctx->model->has_head, "this stage has no head");
+    return sample_once(ctx, temperature, top_p, u, seed, nullptr, token_out);
+}
+
+// rwkv_mi_sample on the adjusted logits (the context's counts and bias); record: the chosen token is counted
+RWKV_API bool rwkv_mi_sample_penalized(struct rwkv_context * ctx, float temperature, float top_p, float u, uint64_t seed,
+                                       float presence, float frequency, uint32_t record, uint32_t * token_out) {
+    if (!penalty_call(ctx)) return false;
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, temperature >= 0.0f && top_p >= 0.0f && top_p <= 1.0f && u < 1.0f && token_out, "bad sampling arguments");
+    if (!check_penalty(ctx, presence, frequency, 0)) return false;
+    const Penalty pen{presence, frequency, record};
+    return sample_once(ctx, temperature, top_p, u, seed, &pen, token_out);
+}
+
+// Feeds first_token, then n_tokens - 1 times a token sampled (temperature, top_p, generator seeded with `seed`) from the previous logits;
+// the draw counter starts from 0.
+RWKV_API bool rwkv_mi_decode_sample(struct rwkv_context * ctx, uint32_t first_token, size_t n_tokens, float temperature, float top_p, uint64_t seed,
+                                    uint32_t * tokens_out, float * elapsed_ms) {
+    ctx->last_error = RWKV_ERROR_NONE;
+    RW_NO_PIPELINE(ctx, false);
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, first_token < (size_t) ctx->model->n_vocab() && n_tokens > 0, "bad arguments");
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, temperature >= 0.0f && top_p >= 0.0f && top_p <= 1.0f, "bad sampling arguments");
+    HIP_CTX_OK(ctx, hipSetDevice(ctx->model->device));
+    if (!upload_tokens(ctx, &first_token, 1) || !ensure_sampler(ctx)) return false;
+    HIP_CTX_OK(ctx, hipMemsetAsync(ctx->d_rng_counter, 0, 8, ctx->stream));
+    return decode_sample_loop(ctx, n_tokens, temperature, top_p, seed, nullptr, tokens_out, elapsed_ms);
+}
+
+// rwkv_mi_decode_sample with the penalised draw, every step recorded. It CONTINUES: neither the counts nor the draw counter are reset.
+RWKV_API bool rwkv_mi_decode_sample_penalized(struct rwkv_context * ctx, uint32_t first_token, size_t n_tokens, float temperature, float top_p, uint64_t seed,
+                                              float presence, float frequency, uint32_t * tokens_out, float * elapsed_ms) {
+    if (!penalty_call(ctx)) return false;
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, first_token < (size_t) ctx->model->n_vocab() && n_tokens > 0, "bad arguments");
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, temperature >= 0.0f && top_p >= 0.0f && top_p <= 1.0f, "bad sampling arguments");
+    if (!check_penalty(ctx, presence, frequency, 0)) return false;
+    HIP_CTX_OK(ctx, hipSetDevice(ctx->model->device));
+    if (!ensure_sampler(ctx) || !ensure_penalty(ctx) || !upload_tokens(ctx, &first_token, 1)) return false;
+    const Penalty pen{presence, frequency, 1u};
+    return decode_sample_loop(ctx, n_tokens, temperature, top_p, seed, &pen, tokens_out, elapsed_ms);
 }
 
 // Eager (graph-free) greedy decode with a HIP-event pair around every launch of the dominant kernel.
@@ -879,39 +884,77 @@ static bool batch_fail_through(rwkv_mi_batch * B) { B->ctx->last_error |= B->run
 #define BATCH_HIP_OK(B, CALL) \
     do { hipError_t e_ = (CALL); RW_CTX_CHECK((B)->ctx, RWKV_ERROR_GRAPH, false, e_ == hipSuccess, "HIP error: %s", hipGetErrorString(e_)); } while (0)
 
-// n, slots and tokens of a call: no slot changes when they are rejected
-static bool batch_check_call(rwkv_mi_batch * B, const uint32_t * slots, const uint32_t * tokens, size_t n) {
+// What a batch call is: a point on three axes. The input -- one token per row, or a segment per row (lens); the draw -- none,
+// the sampler, or the penalised sampler; the repeat -- one pass (batch_pass) or a device loop of n_tokens steps (batch_loop, where no draw
+// means the greedy argmax). Every entry point fills in this description and calls one of the two bodies.
+enum class Draw { none, sample, penalized };
+struct BatchCall {
+    const uint32_t * slots, * tokens;   // row i is slot slots[i] fed tokens[i] ...
+    size_t n;
+    // ... or the next lens[i] of tokens. `ragged` says only that lens is REQUIRED: batch_check_rows picks its NULL-argument message by it and
+    // nothing else reads it -- past that check ragged == (lens != NULL), and everything branches on lens
+    bool ragged = false;
+    const uint32_t * lens = nullptr;
+    Draw draw = Draw::none;
+    const rwkv_mi_sample_params * params = nullptr;        // [n], with a draw
+    const rwkv_mi_penalty_params * penalties = nullptr;    // [n], with the penalised draw
+    // what a single pass reports: the logits of each row's last token; the sampled tokens (with a draw); per-token scores (ragged, no draw)
+    float * logits_out = nullptr;
+    uint32_t * sampled_out = nullptr;
+    const uint32_t * targets = nullptr;
+    float * logprobs_out = nullptr;
+    uint32_t * argmax_out = nullptr;
+};
+
+// n, slots, lens and tokens of a call: no slot changes when they are rejected. Row i feeds lens[i] consecutive tokens to slot slots[i]; the
+// form without lens has every length 1 and checks tokens[i] with its row. *T_out = the tokens of the pass.
+static bool batch_check_rows(rwkv_mi_batch * B, const BatchCall & c, size_t * T_out) {
     rwkv_context * ctx = B->ctx;
-    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, slots != nullptr && tokens != nullptr, "slots or tokens is NULL");
-    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, n > 0 && n <= B->n_slots, "n (%zu) must be in 1 .. %zu", n, B->n_slots);
+    if (c.ragged) RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, c.slots != nullptr && c.lens != nullptr && c.tokens != nullptr, "slots, lens or tokens is NULL");
+    else RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, c.slots != nullptr && c.tokens != nullptr, "slots or tokens is NULL");
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, c.n > 0 && c.n <= B->n_slots, "n (%zu) must be in 1 .. %zu", c.n, B->n_slots);
     const size_t n_vocab = (size_t) ctx->model->n_vocab();
     std::vector<uint8_t> seen(B->n_slots, 0);
-    for (size_t i = 0; i < n; i++) {
-        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, slots[i] < B->n_slots, "slot %" PRIu32 " at index %zu is out of range (0 .. %zu)", slots[i], i, B->n_slots - 1);
-        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, !seen[slots[i]], "slot %" PRIu32 " appears twice", slots[i]);
-        seen[slots[i]] = 1;
-        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, tokens[i] < n_vocab, "Token at index %zu (%" PRIu32 ") is out of range (0 .. %zu)", i, tokens[i], n_vocab - 1);
+    uint64_t T = 0;
+    for (size_t i = 0; i < c.n; i++) {
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, c.slots[i] < B->n_slots, "slot %" PRIu32 " at index %zu is out of range (0 .. %zu)", c.slots[i], i, B->n_slots - 1);
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, !seen[c.slots[i]], "slot %" PRIu32 " appears twice", c.slots[i]);
+        seen[c.slots[i]] = 1;
+        if (!c.lens) {
+            RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, c.tokens[i] < n_vocab, "Token at index %zu (%" PRIu32 ") is out of range (0 .. %zu)", i, c.tokens[i], n_vocab - 1);
+            T++;
+            continue;
+        }
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, c.lens[i] > 0, "lens[%zu] is 0", i);
+        T += c.lens[i];
+        // (token positions are 32-bit words of the segment table)
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, T <= (uint64_t) INT32_MAX, "the lengths add up to more than %d tokens", INT32_MAX);
     }
+    for (size_t t = 0; c.lens && t < (size_t) T; t++)
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, c.tokens[t] < n_vocab, "Token at index %zu (%" PRIu32 ") is out of range (0 .. %zu)", t, c.tokens[t], n_vocab - 1);
+    *T_out = (size_t) T;
     return true;
 }
 
 // row tables of the n named slots (table 0: current -> other buffer, table 1: the reverse) and the tokens into the batch's device words
-static bool batch_upload(rwkv_mi_batch * B, const uint32_t * slots, const uint32_t * tokens, size_t n, int tables) {
+static bool batch_upload(rwkv_mi_batch * B, const BatchCall & c, int tables) {
     rwkv_context * run = B->run;
+    const uint32_t * slots = c.slots;
+    const size_t n = c.n;
     BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));   // (the previous call's copies may still read the staging)
     for (int tb = 0; tb < tables; tb++)
         for (size_t i = 0; i < n; i++) {
             const int p = B->parity[slots[i]] ^ tb;
             B->h_rows[(size_t) tb * B->n_slots + i] = RowState{B->slot_buf(slots[i], p), B->slot_buf(slots[i], p ^ 1)};
         }
-    memcpy(run->h_tokens, tokens, n * sizeof(uint32_t));
+    memcpy(run->h_tokens, c.tokens, n * sizeof(uint32_t));
     for (int tb = 0; tb < tables; tb++)
         BATCH_HIP_OK(B, hipMemcpyAsync(B->d_rows + (size_t) tb * B->n_slots, B->h_rows + (size_t) tb * B->n_slots, n * sizeof(RowState), hipMemcpyHostToDevice, run->stream));
     BATCH_HIP_OK(B, hipMemcpyAsync(run->d_tokens, run->h_tokens, n * sizeof(uint32_t), hipMemcpyHostToDevice, run->stream));
     return true;
 }
 
-// the sampling arguments of a call (checked after batch_check_call, before anything changes)
+// the sampling arguments of a call (checked after batch_check_rows, before anything changes)
 static bool batch_check_params(rwkv_mi_batch * B, const rwkv_mi_sample_params * params, size_t n, bool u_used) {
     rwkv_context * ctx = B->ctx;
     RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, params != nullptr, "params is NULL");
@@ -937,13 +980,14 @@ static bool batch_ensure_sampler(rwkv_mi_batch * B) {
     return true;
 }
 
-// the sampler's row table of the n named slots, one upload per call (after batch_upload: the stream has been drained, the staging is free)
-static bool batch_upload_params(rwkv_mi_batch * B, const uint32_t * slots, const rwkv_mi_sample_params * params, size_t n, bool generator_only) {
-    for (size_t i = 0; i < n; i++) {
-        B->h_srows[i] = SampleRow{params[i], B->d_counters + slots[i]};
-        if (generator_only) B->h_srows[i].p.u = -1.0f;
+// the sampler's row table of the n named slots, one upload per call (after batch_upload*: the stream has been drained, the staging is free).
+// loop: the generator draws
+static bool batch_upload_params(rwkv_mi_batch * B, const BatchCall & c, bool loop) {
+    for (size_t i = 0; i < c.n; i++) {
+        B->h_srows[i] = SampleRow{c.params[i], B->d_counters + c.slots[i]};
+        if (loop) B->h_srows[i].p.u = -1.0f;
     }
-    BATCH_HIP_OK(B, hipMemcpyAsync(B->d_srows, B->h_srows, n * sizeof(SampleRow), hipMemcpyHostToDevice, B->run->stream));
+    BATCH_HIP_OK(B, hipMemcpyAsync(B->d_srows, B->h_srows, c.n * sizeof(SampleRow), hipMemcpyHostToDevice, B->run->stream));
     return true;
 }
 
@@ -975,18 +1019,18 @@ static bool batch_ensure_penalty(rwkv_mi_batch * B) {
     return true;
 }
 
-// the penalised row table of the n named slots (after batch_upload: the stream has been drained, the staging is free). loop: the generator
+// the penalised row table of the n named slots (after batch_upload*: the stream has been drained, the staging is free). loop: the generator
 // draws and every step records
-static bool batch_upload_penalty_rows(rwkv_mi_batch * B, const uint32_t * slots, const rwkv_mi_sample_params * params, const rwkv_mi_penalty_params * penalties,
-                                      size_t n, bool loop) {
+static bool batch_upload_penalty_rows(rwkv_mi_batch * B, const BatchCall & c, bool loop) {
     const size_t V = (size_t) B->ctx->model->n_vocab();
-    for (size_t i = 0; i < n; i++) {
-        const size_t s = slots[i];
-        B->h_prows[i] = PenaltyRow{params[i], B->d_counters + s, penalties[i].presence, penalties[i].frequency, loop ? 1u : penalties[i].record,
+    for (size_t i = 0; i < c.n; i++) {
+        const size_t s = c.slots[i];
+        const rwkv_mi_penalty_params & pen = c.penalties[i];
+        B->h_prows[i] = PenaltyRow{c.params[i], B->d_counters + s, pen.presence, pen.frequency, loop ? 1u : pen.record,
                                    B->d_counts + s * V, B->has_bias[s] ? B->d_bias + s * V : nullptr};
         if (loop) B->h_prows[i].p.u = -1.0f;
     }
-    BATCH_HIP_OK(B, hipMemcpyAsync(B->d_prows, B->h_prows, n * sizeof(PenaltyRow), hipMemcpyHostToDevice, B->run->stream));
+    BATCH_HIP_OK(B, hipMemcpyAsync(B->d_prows, B->h_prows, c.n * sizeof(PenaltyRow), hipMemcpyHostToDevice, B->run->stream));
     return true;
 }
 
@@ -1000,34 +1044,13 @@ static bool batch_slot_call(rwkv_mi_batch * B, size_t slot) {
 
 // ---- ragged passes: row i feeds lens[i] consecutive tokens to slot slots[i] ----
 
-// n, slots, lens and the sum(lens) tokens of a call: no slot changes when they are rejected. *T_out = sum(lens).
-static bool batch_check_ragged(rwkv_mi_batch * B, const uint32_t * slots, const uint32_t * lens, const uint32_t * tokens, size_t n, size_t * T_out) {
-    rwkv_context * ctx = B->ctx;
-    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, slots != nullptr && lens != nullptr && tokens != nullptr, "slots, lens or tokens is NULL");
-    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, n > 0 && n <= B->n_slots, "n (%zu) must be in 1 .. %zu", n, B->n_slots);
-    const size_t n_vocab = (size_t) ctx->model->n_vocab();
-    std::vector<uint8_t> seen(B->n_slots, 0);
-    uint64_t T = 0;
-    for (size_t i = 0; i < n; i++) {
-        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, slots[i] < B->n_slots, "slot %" PRIu32 " at index %zu is out of range (0 .. %zu)", slots[i], i, B->n_slots - 1);
-        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, !seen[slots[i]], "slot %" PRIu32 " appears twice", slots[i]);
-        seen[slots[i]] = 1;
-        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, lens[i] > 0, "lens[%zu] is 0", i);
-        T += lens[i];
-        // (token positions are 32-bit words of the segment table)
-        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, T <= (uint64_t) INT32_MAX, "the lengths add up to more than %d tokens", INT32_MAX);
-    }
-    for (size_t t = 0; t < (size_t) T; t++)
-        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, tokens[t] < n_vocab, "Token at index %zu (%" PRIu32 ") is out of range (0 .. %zu)", t, tokens[t], n_vocab - 1);
-    *T_out = (size_t) T;
-    return true;
-}
-
 // the token words and the tables of a ragged call, grown where needed (new buffers first: a failure leaves the batch as it was), then
 // filled and uploaded: one copy for the tables, one for the tokens
-static bool batch_upload_ragged(rwkv_mi_batch * B, const uint32_t * slots, const uint32_t * lens, const uint32_t * tokens, size_t n, size_t T) {
+static bool batch_upload_ragged(rwkv_mi_batch * B, const BatchCall & c, size_t T) {
     rwkv_context * ctx = B->ctx;
     rwkv_context * run = B->run;
+    const uint32_t * slots = c.slots, * lens = c.lens;
+    const size_t n = c.n;
     const Model & m = *ctx->model;
     BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));   // (the previous call's copies may still read the staging)
     if ((int64_t) T > run->d_tokens_cap) {
@@ -1067,7 +1090,7 @@ static bool batch_upload_ragged(rwkv_mi_batch * B, const uint32_t * slots, const
         last[i] = g.t1 - 1;
         t = g.t1;
     }
-    memcpy(run->h_tokens, tokens, T * sizeof(uint32_t));
+    memcpy(run->h_tokens, c.tokens, T * sizeof(uint32_t));
     BATCH_HIP_OK(B, hipMemcpyAsync(B->d_seg, B->h_seg, bytes, hipMemcpyHostToDevice, run->stream));
     BATCH_HIP_OK(B, hipMemcpyAsync(run->d_tokens, run->h_tokens, T * sizeof(uint32_t), hipMemcpyHostToDevice, run->stream));
     SegPass & ps = B->pass;
@@ -1075,6 +1098,114 @@ static bool batch_upload_ragged(rwkv_mi_batch * B, const uint32_t * slots, const
     ps.d_seg_of = (const int32_t *) (B->d_seg + off_seg_of); ps.d_last = (const int32_t *) (B->d_seg + off_last);
     ps.h_long = B->long_segs.data();
     ps.n = (int64_t) n; ps.n_short = (int64_t) n_short; ps.n_long = (int64_t) B->long_segs.size();
+    return true;
+}
+
+// ---- the two bodies of the batch calls ----
+
+// every argument of a call, nothing changed yet, in the order the entry points report them: rows, targets, params, penalties. u_used: the rows'
+// u is read (a single pass; in a loop the generator draws)
+static bool batch_check_args(rwkv_mi_batch * B, const BatchCall & c, bool u_used, size_t * T_out) {
+    if (!batch_check_rows(B, c, T_out) || !check_targets(B->ctx, c.targets, *T_out, c.logprobs_out)) return false;
+    if (c.draw != Draw::none && !batch_check_params(B, c.params, c.n, u_used)) return false;
+    return c.draw != Draw::penalized || batch_check_penalties(B, c.penalties, c.n);
+}
+
+// the buffers the draw of a call needs: the plain sampler allocates none of the penalty tables
+static bool batch_ensure_draw(rwkv_mi_batch * B, const BatchCall & c) {
+    if (c.draw == Draw::penalized) return batch_ensure_penalty(B);
+    return c.draw == Draw::none || batch_ensure_sampler(B);
+}
+
+// the rows or the segments of a call (that drains the stream first), then its sampler table. loop: both row tables
+static bool batch_upload_call(rwkv_mi_batch * B, const BatchCall & c, size_t T, bool loop) {
+    if (!(c.lens ? batch_upload_ragged(B, c, T) : batch_upload(B, c, loop ? 2 : 1))) return false;
+    if (c.draw == Draw::penalized) return batch_upload_penalty_rows(B, c, loop);
+    return c.draw == Draw::none || batch_upload_params(B, c, loop);
+}
+
+static RowSampler batch_sampler(rwkv_mi_batch * B, const BatchCall & c, uint32_t * hist) {
+    return c.draw == Draw::penalized ? RowSampler{nullptr, B->d_probs, hist, B->d_prows} : RowSampler{B->d_srows, B->d_probs, hist};
+}
+
+// a pass that could not be launched: the stream is drained before the call returns (what it had enqueued reads the staging)
+static bool batch_fail_drained(rwkv_mi_batch * B) { (void) hipStreamSynchronize(B->run->stream); return batch_fail_through(B); }
+
+static void batch_flip(rwkv_mi_batch * B, const BatchCall & c) { for (size_t i = 0; i < c.n; i++) B->parity[c.slots[i]] ^= 1; }
+
+// One pass: every named slot advances by its token or its segment, then what the call asked for goes back to the host.
+static bool batch_pass(rwkv_mi_batch * B, const BatchCall & c) {
+    rwkv_context * ctx = B->ctx;
+    rwkv_context * run = B->run;
+    ctx->last_error = RWKV_ERROR_NONE;
+    size_t T = 0;
+    if (!batch_check_args(B, c, true, &T)) return false;
+    const bool drawn = c.draw != Draw::none, scoring = c.logprobs_out || c.argmax_out;
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, !drawn || c.sampled_out != nullptr, "sampled_out is NULL");
+    run->print_errors = ctx->print_errors;
+    BATCH_HIP_OK(B, hipSetDevice(ctx->model->device));
+    if (!batch_ensure_draw(B, c)) return false;
+    if (scoring && !ensure_score(run, (int64_t) T)) return batch_fail_through(B);
+    if (!batch_upload_call(B, c, T, false)) return false;   // (drains the stream: the staging of the targets is free as well)
+    if (c.logprobs_out) {
+        memcpy(run->h_score_targets, c.targets, T * sizeof(uint32_t));
+        BATCH_HIP_OK(B, hipMemcpyAsync(run->d_score_targets, run->h_score_targets, T * sizeof(uint32_t), hipMemcpyHostToDevice, run->stream));
+    }
+    // Row i's token lands in the batch's token word i (a ragged pass has read all T of them by then): the 4 n bytes that go back to the host.
+    const RowSampler sampler = batch_sampler(B, c, nullptr);
+    // scoring is the ragged pass with the head on every token (engine.hip, ScorePass): T rows of log-probs / argmax in token order
+    ScorePass sp;
+    sp.targets = sp.logprobs = c.logprobs_out != nullptr;
+    sp.argmax = c.argmax_out != nullptr;
+    const bool want_logits = drawn || scoring || c.logits_out;
+    const bool ok = c.lens ? forward_segs(run, B->pass, (int64_t) T, want_logits, drawn ? &sampler : nullptr, scoring ? &sp : nullptr)
+                           : forward_rows(run, B->d_rows, (int64_t) c.n, want_logits, drawn ? &sampler : nullptr);
+    if (!ok) return batch_fail_drained(B);
+    if (drawn) BATCH_HIP_OK(B, hipMemcpyAsync(run->h_tokens, run->d_tokens, c.n * sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream));
+    if (c.logits_out) BATCH_HIP_OK(B, hipMemcpyAsync(c.logits_out, run->d_logits, c.n * (size_t) ctx->model->n_vocab() * sizeof(float), hipMemcpyDeviceToHost, run->stream));
+    if (c.logprobs_out) BATCH_HIP_OK(B, hipMemcpyAsync(c.logprobs_out, run->d_score_logprobs, T * sizeof(float), hipMemcpyDeviceToHost, run->stream));
+    if (c.argmax_out) BATCH_HIP_OK(B, hipMemcpyAsync(c.argmax_out, run->d_score_argmax, T * sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream));
+    BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));
+    if (drawn) memcpy(c.sampled_out, run->h_tokens, c.n * sizeof(uint32_t));
+    batch_flip(B, c);
+    return true;
+}
+
+// The device loop: n_tokens passes of one token per row, each row's next token chosen on the device -- its argmax, or the call's draw.
+// tokens_out: [n][n_tokens]. The plain sampled loop starts the named slots' draw counters from 0. The penalised loop CONTINUES: the named
+// slots' counts and draw counters are where the caller left them, and every step records.
+static bool batch_loop(rwkv_mi_batch * B, const BatchCall & c, size_t n_tokens, uint32_t * tokens_out, float * elapsed_ms) {
+    rwkv_context * ctx = B->ctx;
+    rwkv_context * run = B->run;
+    ctx->last_error = RWKV_ERROR_NONE;
+    size_t T = 0;
+    if (!batch_check_args(B, c, false, &T)) return false;
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, n_tokens > 0, "n_tokens is 0");
+    run->print_errors = ctx->print_errors;
+    const size_t n = c.n;
+    const bool drawn = c.draw != Draw::none;
+    BATCH_HIP_OK(B, hipSetDevice(ctx->model->device));
+    if (!batch_ensure_draw(B, c)) return false;
+    DevBuf<uint32_t> hist;   // [n_tokens][n], freed on every exit
+    BATCH_HIP_OK(B, hist.alloc(n_tokens * n));
+    if (!batch_upload_call(B, c, T, true)) return false;
+    if (c.draw == Draw::sample) launch_sample_seek_rows(B->d_srows, (int64_t) n, 0ull, run->stream);   // the named slots' streams start over
+    BATCH_HIP_OK(B, hipEventRecord(run->ev0, run->stream));
+    for (size_t i = 0; i < n_tokens; i++) {
+        // step i reads the buffers step i - 1 wrote: the two row tables alternate; the token of each row -- sampled inside the pass's chain
+        // bracket, or its argmax after it -- lands where its next embedding lookup reads it
+        const RowSampler sampler = batch_sampler(B, c, hist.p + i * n);
+        if (!forward_rows(run, B->d_rows + (i & 1) * B->n_slots, (int64_t) n, true, drawn ? &sampler : nullptr)) return batch_fail_drained(B);
+        if (!drawn) launch_argmax(run->d_logits, (int64_t) n, ctx->model->n_vocab(), run->d_tokens, hist.p + i * n, run->stream);
+    }
+    BATCH_HIP_OK(B, hipEventRecord(run->ev1, run->stream));
+    std::vector<uint32_t> h(tokens_out ? n_tokens * n : 0);
+    if (tokens_out) BATCH_HIP_OK(B, hipMemcpyAsync(h.data(), hist.p, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream));
+    BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));
+    if (elapsed_ms) BATCH_HIP_OK(B, hipEventElapsedTime(elapsed_ms, run->ev0, run->ev1));
+    for (size_t r = 0; r < n && tokens_out; r++)
+        for (size_t i = 0; i < n_tokens; i++) tokens_out[r * n_tokens + i] = h[i * n + r];
+    if (n_tokens & 1) batch_flip(B, c);
     return true;
 }
 
@@ -1205,175 +1336,51 @@ RWKV_API bool rwkv_mi_batch_state_to_context(struct rwkv_mi_batch * B, size_t sl
 }
 
 RWKV_API bool rwkv_mi_batch_eval(struct rwkv_mi_batch * B, const uint32_t * slots, const uint32_t * tokens, size_t n, float * logits_out) {
-    rwkv_context * ctx = B->ctx;
-    ctx->last_error = RWKV_ERROR_NONE;
-    if (!batch_check_call(B, slots, tokens, n)) return false;
-    rwkv_context * run = B->run;
-    run->print_errors = ctx->print_errors;
-    BATCH_HIP_OK(B, hipSetDevice(ctx->model->device));
-    if (!batch_upload(B, slots, tokens, n, 1)) return false;
-    if (!forward_rows(run, B->d_rows, (int64_t) n, logits_out != nullptr)) return batch_fail_through(B);
-    if (logits_out) BATCH_HIP_OK(B, hipMemcpyAsync(logits_out, run->d_logits, n * (size_t) ctx->model->n_vocab() * sizeof(float), hipMemcpyDeviceToHost, run->stream));
-    BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));
-    for (size_t i = 0; i < n; i++) B->parity[slots[i]] ^= 1;
-    return true;
+    BatchCall c{slots, tokens, n};
+    c.logits_out = logits_out;
+    return batch_pass(B, c);
 }
 
 RWKV_API bool rwkv_mi_batch_decode_greedy(struct rwkv_mi_batch * B, const uint32_t * slots, const uint32_t * first_tokens, size_t n,
                                           size_t n_tokens, uint32_t * tokens_out, float * elapsed_ms) {
-    rwkv_context * ctx = B->ctx;
-    ctx->last_error = RWKV_ERROR_NONE;
-    if (!batch_check_call(B, slots, first_tokens, n)) return false;
-    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, n_tokens > 0, "n_tokens is 0");
-    rwkv_context * run = B->run;
-    run->print_errors = ctx->print_errors;
-    const int64_t n_vocab = ctx->model->n_vocab();
-    BATCH_HIP_OK(B, hipSetDevice(ctx->model->device));
-    struct DevBuf { uint32_t * p = nullptr; ~DevBuf() { if (p) (void) hipFree(p); } } hist;   // [n_tokens][n], freed on every exit
-    BATCH_HIP_OK(B, hipMalloc((void **) &hist.p, n_tokens * n * sizeof(uint32_t)));
-    if (!batch_upload(B, slots, first_tokens, n, 2)) return false;
-    BATCH_HIP_OK(B, hipEventRecord(run->ev0, run->stream));
-    for (size_t i = 0; i < n_tokens; i++) {
-        // step i reads the buffers step i - 1 wrote: the two row tables alternate; the argmax of each row lands where its next embedding reads it
-        if (!forward_rows(run, B->d_rows + (i & 1) * B->n_slots, (int64_t) n, true)) {
-            (void) hipStreamSynchronize(run->stream);
-            return batch_fail_through(B);
-        }
-        launch_argmax(run->d_logits, (int64_t) n, n_vocab, run->d_tokens, hist.p + i * n, run->stream);
-    }
-    BATCH_HIP_OK(B, hipEventRecord(run->ev1, run->stream));
-    std::vector<uint32_t> h(tokens_out ? n_tokens * n : 0);
-    if (tokens_out) BATCH_HIP_OK(B, hipMemcpyAsync(h.data(), hist.p, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream));
-    BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));
-    if (elapsed_ms) BATCH_HIP_OK(B, hipEventElapsedTime(elapsed_ms, run->ev0, run->ev1));
-    for (size_t r = 0; r < n && tokens_out; r++)
-        for (size_t i = 0; i < n_tokens; i++) tokens_out[r * n_tokens + i] = h[i * n + r];
-    if (n_tokens & 1) for (size_t i = 0; i < n; i++) B->parity[slots[i]] ^= 1;
-    return true;
+    return batch_loop(B, BatchCall{slots, first_tokens, n}, n_tokens, tokens_out, elapsed_ms);
 }
 
 RWKV_API bool rwkv_mi_batch_eval_sample(struct rwkv_mi_batch * B, const uint32_t * slots, const uint32_t * tokens, size_t n,
                                         const struct rwkv_mi_sample_params * params, uint32_t * sampled_out, float * logits_out) {
-    rwkv_context * ctx = B->ctx;
-    ctx->last_error = RWKV_ERROR_NONE;
-    if (!batch_check_call(B, slots, tokens, n) || !batch_check_params(B, params, n, true)) return false;
-    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, sampled_out != nullptr, "sampled_out is NULL");
-    rwkv_context * run = B->run;
-    run->print_errors = ctx->print_errors;
-    BATCH_HIP_OK(B, hipSetDevice(ctx->model->device));
-    if (!batch_ensure_sampler(B)) return false;
-    if (!batch_upload(B, slots, tokens, n, 1) || !batch_upload_params(B, slots, params, n, false)) return false;
-    // each row's token lands in the batch's token word of that row: the 4 n bytes that go back to the host
-    const RowSampler sampler{B->d_srows, B->d_probs, nullptr};
-    if (!forward_rows(run, B->d_rows, (int64_t) n, true, &sampler)) { (void) hipStreamSynchronize(run->stream); return batch_fail_through(B); }
-    BATCH_HIP_OK(B, hipMemcpyAsync(run->h_tokens, run->d_tokens, n * sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream));
-    if (logits_out) BATCH_HIP_OK(B, hipMemcpyAsync(logits_out, run->d_logits, n * (size_t) ctx->model->n_vocab() * sizeof(float), hipMemcpyDeviceToHost, run->stream));
-    BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));
-    memcpy(sampled_out, run->h_tokens, n * sizeof(uint32_t));
-    for (size_t i = 0; i < n; i++) B->parity[slots[i]] ^= 1;
-    return true;
+    BatchCall c{slots, tokens, n};
+    c.draw = Draw::sample; c.params = params;
+    c.sampled_out = sampled_out; c.logits_out = logits_out;
+    return batch_pass(B, c);
 }
 
 RWKV_API bool rwkv_mi_batch_eval_ragged(struct rwkv_mi_batch * B, const uint32_t * slots, const uint32_t * lens, const uint32_t * tokens, size_t n,
                                         float * logits_out) {
-    rwkv_context * ctx = B->ctx;
-    ctx->last_error = RWKV_ERROR_NONE;
-    size_t T = 0;
-    if (!batch_check_ragged(B, slots, lens, tokens, n, &T)) return false;
-    rwkv_context * run = B->run;
-    run->print_errors = ctx->print_errors;
-    BATCH_HIP_OK(B, hipSetDevice(ctx->model->device));
-    if (!batch_upload_ragged(B, slots, lens, tokens, n, T)) return false;
-    if (!forward_segs(run, B->pass, (int64_t) T, logits_out != nullptr)) { (void) hipStreamSynchronize(run->stream); return batch_fail_through(B); }
-    if (logits_out) BATCH_HIP_OK(B, hipMemcpyAsync(logits_out, run->d_logits, n * (size_t) ctx->model->n_vocab() * sizeof(float), hipMemcpyDeviceToHost, run->stream));
-    BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));
-    for (size_t i = 0; i < n; i++) B->parity[slots[i]] ^= 1;
-    return true;
+    BatchCall c{slots, tokens, n, true, lens};
+    c.logits_out = logits_out;
+    return batch_pass(B, c);
 }
 
-// The ragged pass with the head on every token (engine.hip, ScorePass): T rows of log-probs / argmax in token order.
 RWKV_API bool rwkv_mi_batch_score_ragged(struct rwkv_mi_batch * B, const uint32_t * slots, const uint32_t * lens, const uint32_t * tokens, const uint32_t * targets,
                                          size_t n, float * logprobs_out, uint32_t * argmax_out) {
-    rwkv_context * ctx = B->ctx;
-    ctx->last_error = RWKV_ERROR_NONE;
-    size_t T = 0;
-    if (!batch_check_ragged(B, slots, lens, tokens, n, &T) || !check_targets(ctx, targets, T, logprobs_out)) return false;
-    rwkv_context * run = B->run;
-    run->print_errors = ctx->print_errors;
-    BATCH_HIP_OK(B, hipSetDevice(ctx->model->device));
-    const bool scoring = logprobs_out || argmax_out;
-    if (scoring && !ensure_score(run, (int64_t) T)) return batch_fail_through(B);
-    if (!batch_upload_ragged(B, slots, lens, tokens, n, T)) return false;   // (drains the stream: the staging of the targets is free as well)
-    if (logprobs_out) {
-        memcpy(run->h_score_targets, targets, T * sizeof(uint32_t));
-        BATCH_HIP_OK(B, hipMemcpyAsync(run->d_score_targets, run->h_score_targets, T * sizeof(uint32_t), hipMemcpyHostToDevice, run->stream));
-    }
-    ScorePass sp;
-    sp.targets = sp.logprobs = logprobs_out != nullptr;
-    sp.argmax = argmax_out != nullptr;
-    if (!forward_segs(run, B->pass, (int64_t) T, scoring, nullptr, scoring ? &sp : nullptr)) { (void) hipStreamSynchronize(run->stream); return batch_fail_through(B); }
-    if (logprobs_out) BATCH_HIP_OK(B, hipMemcpyAsync(logprobs_out, run->d_score_logprobs, T * sizeof(float), hipMemcpyDeviceToHost, run->stream));
-    if (argmax_out) BATCH_HIP_OK(B, hipMemcpyAsync(argmax_out, run->d_score_argmax, T * sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream));
-    BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));
-    for (size_t i = 0; i < n; i++) B->parity[slots[i]] ^= 1;
-    return true;
+    BatchCall c{slots, tokens, n, true, lens};
+    c.targets = targets; c.logprobs_out = logprobs_out; c.argmax_out = argmax_out;
+    return batch_pass(B, c);
 }
 
 RWKV_API bool rwkv_mi_batch_eval_ragged_sample(struct rwkv_mi_batch * B, const uint32_t * slots, const uint32_t * lens, const uint32_t * tokens, size_t n,
                                                const struct rwkv_mi_sample_params * params, uint32_t * sampled_out, float * logits_out) {
-    rwkv_context * ctx = B->ctx;
-    ctx->last_error = RWKV_ERROR_NONE;
-    size_t T = 0;
-    if (!batch_check_ragged(B, slots, lens, tokens, n, &T) || !batch_check_params(B, params, n, true)) return false;
-    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, sampled_out != nullptr, "sampled_out is NULL");
-    rwkv_context * run = B->run;
-    run->print_errors = ctx->print_errors;
-    BATCH_HIP_OK(B, hipSetDevice(ctx->model->device));
-    if (!batch_ensure_sampler(B)) return false;
-    if (!batch_upload_ragged(B, slots, lens, tokens, n, T) || !batch_upload_params(B, slots, params, n, false)) return false;
-    // row i's token lands in the batch's token word i (the pass has read all T of them by then): the 4 n bytes that go back to the host
-    const RowSampler sampler{B->d_srows, B->d_probs, nullptr};
-    if (!forward_segs(run, B->pass, (int64_t) T, true, &sampler)) { (void) hipStreamSynchronize(run->stream); return batch_fail_through(B); }
-    BATCH_HIP_OK(B, hipMemcpyAsync(run->h_tokens, run->d_tokens, n * sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream));
-    if (logits_out) BATCH_HIP_OK(B, hipMemcpyAsync(logits_out, run->d_logits, n * (size_t) ctx->model->n_vocab() * sizeof(float), hipMemcpyDeviceToHost, run->stream));
-    BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));
-    memcpy(sampled_out, run->h_tokens, n * sizeof(uint32_t));
-    for (size_t i = 0; i < n; i++) B->parity[slots[i]] ^= 1;
-    return true;
+    BatchCall c{slots, tokens, n, true, lens};
+    c.draw = Draw::sample; c.params = params;
+    c.sampled_out = sampled_out; c.logits_out = logits_out;
+    return batch_pass(B, c);
 }
 
 RWKV_API bool rwkv_mi_batch_decode_sample(struct rwkv_mi_batch * B, const uint32_t * slots, const uint32_t * first_tokens, size_t n,
                                           size_t n_tokens, const struct rwkv_mi_sample_params * params, uint32_t * tokens_out, float * elapsed_ms) {
-    rwkv_context * ctx = B->ctx;
-    ctx->last_error = RWKV_ERROR_NONE;
-    if (!batch_check_call(B, slots, first_tokens, n) || !batch_check_params(B, params, n, false)) return false;
-    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, n_tokens > 0, "n_tokens is 0");
-    rwkv_context * run = B->run;
-    run->print_errors = ctx->print_errors;
-    BATCH_HIP_OK(B, hipSetDevice(ctx->model->device));
-    if (!batch_ensure_sampler(B)) return false;
-    struct DevBuf { uint32_t * p = nullptr; ~DevBuf() { if (p) (void) hipFree(p); } } hist;   // [n_tokens][n], freed on every exit
-    BATCH_HIP_OK(B, hipMalloc((void **) &hist.p, n_tokens * n * sizeof(uint32_t)));
-    if (!batch_upload(B, slots, first_tokens, n, 2) || !batch_upload_params(B, slots, params, n, true)) return false;
-    launch_sample_seek_rows(B->d_srows, (int64_t) n, 0ull, run->stream);   // the named slots' streams start over
-    BATCH_HIP_OK(B, hipEventRecord(run->ev0, run->stream));
-    for (size_t i = 0; i < n_tokens; i++) {
-        // as the greedy loop: the two row tables alternate; each row's sampled token lands where its next embedding lookup reads it
-        const RowSampler sampler{B->d_srows, B->d_probs, hist.p + i * n};
-        if (!forward_rows(run, B->d_rows + (i & 1) * B->n_slots, (int64_t) n, true, &sampler)) {
-            (void) hipStreamSynchronize(run->stream);
-            return batch_fail_through(B);
-        }
-    }
-    BATCH_HIP_OK(B, hipEventRecord(run->ev1, run->stream));
-    std::vector<uint32_t> h(tokens_out ? n_tokens * n : 0);
-    if (tokens_out) BATCH_HIP_OK(B, hipMemcpyAsync(h.data(), hist.p, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream));
-    BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));
-    if (elapsed_ms) BATCH_HIP_OK(B, hipEventElapsedTime(elapsed_ms, run->ev0, run->ev1));
-    for (size_t r = 0; r < n && tokens_out; r++)
-        for (size_t i = 0; i < n_tokens; i++) tokens_out[r * n_tokens + i] = h[i * n + r];
-    if (n_tokens & 1) for (size_t i = 0; i < n; i++) B->parity[slots[i]] ^= 1;
-    return true;
+    BatchCall c{slots, first_tokens, n};
+    c.draw = Draw::sample; c.params = params;
+    return batch_loop(B, c, n_tokens, tokens_out, elapsed_ms);
 }
 
 RWKV_API bool rwkv_mi_batch_rng_seek(struct rwkv_mi_batch * B, size_t slot, uint64_t counter) {
@@ -1428,80 +1435,27 @@ RWKV_API bool rwkv_mi_batch_logit_bias_set(struct rwkv_mi_batch * B, size_t slot
 RWKV_API bool rwkv_mi_batch_eval_sample_penalized(struct rwkv_mi_batch * B, const uint32_t * slots, const uint32_t * tokens, size_t n,
                                                   const struct rwkv_mi_sample_params * params, const struct rwkv_mi_penalty_params * penalties,
                                                   uint32_t * sampled_out, float * logits_out) {
-    rwkv_context * ctx = B->ctx;
-    ctx->last_error = RWKV_ERROR_NONE;
-    if (!batch_check_call(B, slots, tokens, n) || !batch_check_params(B, params, n, true) || !batch_check_penalties(B, penalties, n)) return false;
-    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, sampled_out != nullptr, "sampled_out is NULL");
-    rwkv_context * run = B->run;
-    run->print_errors = ctx->print_errors;
-    BATCH_HIP_OK(B, hipSetDevice(ctx->model->device));
-    if (!batch_ensure_penalty(B)) return false;
-    if (!batch_upload(B, slots, tokens, n, 1) || !batch_upload_penalty_rows(B, slots, params, penalties, n, false)) return false;
-    const RowSampler sampler{nullptr, B->d_probs, nullptr, B->d_prows};
-    if (!forward_rows(run, B->d_rows, (int64_t) n, true, &sampler)) { (void) hipStreamSynchronize(run->stream); return batch_fail_through(B); }
-    BATCH_HIP_OK(B, hipMemcpyAsync(run->h_tokens, run->d_tokens, n * sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream));
-    if (logits_out) BATCH_HIP_OK(B, hipMemcpyAsync(logits_out, run->d_logits, n * (size_t) ctx->model->n_vocab() * sizeof(float), hipMemcpyDeviceToHost, run->stream));
-    BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));
-    memcpy(sampled_out, run->h_tokens, n * sizeof(uint32_t));
-    for (size_t i = 0; i < n; i++) B->parity[slots[i]] ^= 1;
-    return true;
+    BatchCall c{slots, tokens, n};
+    c.draw = Draw::penalized; c.params = params; c.penalties = penalties;
+    c.sampled_out = sampled_out; c.logits_out = logits_out;
+    return batch_pass(B, c);
 }
 
 RWKV_API bool rwkv_mi_batch_eval_ragged_sample_penalized(struct rwkv_mi_batch * B, const uint32_t * slots, const uint32_t * lens, const uint32_t * tokens,
                                                          size_t n, const struct rwkv_mi_sample_params * params,
                                                          const struct rwkv_mi_penalty_params * penalties, uint32_t * sampled_out, float * logits_out) {
-    rwkv_context * ctx = B->ctx;
-    ctx->last_error = RWKV_ERROR_NONE;
-    size_t T = 0;
-    if (!batch_check_ragged(B, slots, lens, tokens, n, &T) || !batch_check_params(B, params, n, true) || !batch_check_penalties(B, penalties, n)) return false;
-    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, sampled_out != nullptr, "sampled_out is NULL");
-    rwkv_context * run = B->run;
-    run->print_errors = ctx->print_errors;
-    BATCH_HIP_OK(B, hipSetDevice(ctx->model->device));
-    if (!batch_ensure_penalty(B)) return false;
-    if (!batch_upload_ragged(B, slots, lens, tokens, n, T) || !batch_upload_penalty_rows(B, slots, params, penalties, n, false)) return false;
-    const RowSampler sampler{nullptr, B->d_probs, nullptr, B->d_prows};
-    if (!forward_segs(run, B->pass, (int64_t) T, true, &sampler)) { (void) hipStreamSynchronize(run->stream); return batch_fail_through(B); }
-    BATCH_HIP_OK(B, hipMemcpyAsync(run->h_tokens, run->d_tokens, n * sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream));
-    if (logits_out) BATCH_HIP_OK(B, hipMemcpyAsync(logits_out, run->d_logits, n * (size_t) ctx->model->n_vocab() * sizeof(float), hipMemcpyDeviceToHost, run->stream));
-    BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));
-    memcpy(sampled_out, run->h_tokens, n * sizeof(uint32_t));
-    for (size_t i = 0; i < n; i++) B->parity[slots[i]] ^= 1;
-    return true;
+    BatchCall c{slots, tokens, n, true, lens};
+    c.draw = Draw::penalized; c.params = params; c.penalties = penalties;
+    c.sampled_out = sampled_out; c.logits_out = logits_out;
+    return batch_pass(B, c);
 }
 
-// The penalised loop CONTINUES: the named slots' counts and draw counters are where the caller left them, and every step records.
 RWKV_API bool rwkv_mi_batch_decode_sample_penalized(struct rwkv_mi_batch * B, const uint32_t * slots, const uint32_t * first_tokens, size_t n,
                                                     size_t n_tokens, const struct rwkv_mi_sample_params * params,
                                                     const struct rwkv_mi_penalty_params * penalties, uint32_t * tokens_out, float * elapsed_ms) {
-    rwkv_context * ctx = B->ctx;
-    ctx->last_error = RWKV_ERROR_NONE;
-    if (!batch_check_call(B, slots, first_tokens, n) || !batch_check_params(B, params, n, false) || !batch_check_penalties(B, penalties, n)) return false;
-    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, n_tokens > 0, "n_tokens is 0");
-    rwkv_context * run = B->run;
-    run->print_errors = ctx->print_errors;
-    BATCH_HIP_OK(B, hipSetDevice(ctx->model->device));
-    if (!batch_ensure_penalty(B)) return false;
-    struct DevBuf { uint32_t * p = nullptr; ~DevBuf() { if (p) (void) hipFree(p); } } hist;   // [n_tokens][n], freed on every exit
-    BATCH_HIP_OK(B, hipMalloc((void **) &hist.p, n_tokens * n * sizeof(uint32_t)));
-    if (!batch_upload(B, slots, first_tokens, n, 2) || !batch_upload_penalty_rows(B, slots, params, penalties, n, true)) return false;
-    BATCH_HIP_OK(B, hipEventRecord(run->ev0, run->stream));
-    for (size_t i = 0; i < n_tokens; i++) {
-        const RowSampler sampler{nullptr, B->d_probs, hist.p + i * n, B->d_prows};
-        if (!forward_rows(run, B->d_rows + (i & 1) * B->n_slots, (int64_t) n, true, &sampler)) {
-            (void) hipStreamSynchronize(run->stream);
-            return batch_fail_through(B);
-        }
-    }
-    BATCH_HIP_OK(B, hipEventRecord(run->ev1, run->stream));
-    std::vector<uint32_t> h(tokens_out ? n_tokens * n : 0);
-    if (tokens_out) BATCH_HIP_OK(B, hipMemcpyAsync(h.data(), hist.p, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream));
-    BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));
-    if (elapsed_ms) BATCH_HIP_OK(B, hipEventElapsedTime(elapsed_ms, run->ev0, run->ev1));
-    for (size_t r = 0; r < n && tokens_out; r++)
-        for (size_t i = 0; i < n_tokens; i++) tokens_out[r * n_tokens + i] = h[i * n + r];
-    if (n_tokens & 1) for (size_t i = 0; i < n; i++) B->parity[slots[i]] ^= 1;
-    return true;
+    BatchCall c{slots, first_tokens, n};
+    c.draw = Draw::penalized; c.params = params; c.penalties = penalties;
+    return batch_loop(B, c, n_tokens, tokens_out, elapsed_ms);
 }
 
 }  // extern "C"

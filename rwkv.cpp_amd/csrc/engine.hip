@@ -852,6 +852,13 @@ void batch_context_destroy(rwkv_context * c) {
     destroy_context(c);
 }
 
+// The row sampler of a batch pass over the `rows` rows of ctx->d_logits: row r's token goes to ctx->d_tokens[r] (and to s.hist[r] when given).
+static void launch_row_sampler(rwkv_context * ctx, const RowSampler & s, int64_t rows) {
+    const int n_vocab = (int) ctx->model->n_vocab();
+    if (s.ptable) launch_pen_sample_rows(ctx->d_logits, rows, n_vocab, s.ptable, s.probs, ctx->d_tokens, s.hist, ctx->stream);
+    else launch_sample_rows(ctx->d_logits, rows, n_vocab, s.table, s.probs, ctx->d_tokens, s.hist, ctx->stream);
+}
+
 // One pass of T rows, row t = one token (ctx->d_tokens[t]) of the sequence whose state is d_rows[t]. Logits: ctx->d_logits[T][n_vocab].
 // sample: the T sampler workgroups (sampling.hip, k_sample_rows) follow the head INSIDE the chain bracket. Each of them is 1024 threads,
 // a CU's worth of waves, so up to T CUs are taken while they run; the completion event mega_chain_end records is what the device's next
@@ -864,10 +871,7 @@ bool forward_rows(rwkv_context * ctx, const RowState * d_rows, int64_t T, bool w
     r.state.rows = d_rows;
     mega_chain_begin(ctx);
     r.run(want_logits);
-    if (sample && want_logits && !r.failed) {
-        if (sample->ptable) launch_pen_sample_rows(ctx->d_logits, T, (int) m.n_vocab(), sample->ptable, sample->probs, ctx->d_tokens, sample->hist, ctx->stream);
-        else launch_sample_rows(ctx->d_logits, T, (int) m.n_vocab(), sample->table, sample->probs, ctx->d_tokens, sample->hist, ctx->stream);
-    }
+    if (sample && want_logits && !r.failed) launch_row_sampler(ctx, *sample, T);
     mega_chain_end(ctx);
     HIP_CTX_OK(ctx, hipGetLastError());
     RW_CTX_CHECK(ctx, RWKV_ERROR_GRAPH | RWKV_ERROR_ALLOC, false, !r.failed, "a batched product could not be launched (out of device memory for the tile-major weight image?)");
@@ -895,10 +899,7 @@ bool forward_segs(rwkv_context * ctx, const SegPass & p, int64_t T, bool want_lo
     r.state.segs = p.d_segs; r.state.n_segs = p.n; r.state.seg_of = p.d_seg_of;
     mega_chain_begin(ctx);
     r.run(want_logits);
-    if (sample && want_logits && !r.failed) {
-        if (sample->ptable) launch_pen_sample_rows(ctx->d_logits, p.n, (int) m.n_vocab(), sample->ptable, sample->probs, ctx->d_tokens, sample->hist, ctx->stream);
-        else launch_sample_rows(ctx->d_logits, p.n, (int) m.n_vocab(), sample->table, sample->probs, ctx->d_tokens, sample->hist, ctx->stream);
-    }
+    if (sample && want_logits && !r.failed) launch_row_sampler(ctx, *sample, p.n);
     mega_chain_end(ctx);
     HIP_CTX_OK(ctx, hipGetLastError());
     RW_CTX_CHECK(ctx, RWKV_ERROR_GRAPH | RWKV_ERROR_ALLOC, false, !r.failed, "a product of the ragged pass could not be launched (out of device memory for the tile-major weight image?)");

@@ -613,22 +613,6 @@ def _u32(values) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(values, dtype=np.int64).astype(np.uint32))
 
 
-def sample_params(n: int, temperature, top_p, u=-1.0, seed=0):
-    """[n] struct rwkv_mi_sample_params; each argument is a scalar (every row) or a sequence of length n."""
-    def rows(v, what):
-        a = np.asarray(v)
-        if a.ndim == 0:
-            return [a.item()] * n
-        if a.shape != (n,):
-            raise ValueError(f"{what} must be a scalar or a sequence of length {n}")
-        return a.tolist()
-    t, p, us, sd = rows(temperature, "temperature"), rows(top_p, "top_p"), rows(u, "u"), rows(seed, "seed")
-    arr = (SampleParams * n)()
-    for i in range(n):
-        arr[i] = SampleParams(float(t[i]), float(p[i]), float(us[i]), int(sd[i]) & 0xFFFFFFFFFFFFFFFF)
-    return arr
-
-
 def _rows(n: int, v, what: str) -> list:
     a = np.asarray(v)
     if a.ndim == 0:
@@ -636,6 +620,15 @@ def _rows(n: int, v, what: str) -> list:
     if a.shape != (n,):
         raise ValueError(f"{what} must be a scalar or a sequence of length {n}")
     return a.tolist()
+
+
+def sample_params(n: int, temperature, top_p, u=-1.0, seed=0):
+    """[n] struct rwkv_mi_sample_params; each argument is a scalar (every row) or a sequence of length n."""
+    t, p, us, sd = _rows(n, temperature, "temperature"), _rows(n, top_p, "top_p"), _rows(n, u, "u"), _rows(n, seed, "seed")
+    arr = (SampleParams * n)()
+    for i in range(n):
+        arr[i] = SampleParams(float(t[i]), float(p[i]), float(us[i]), int(sd[i]) & 0xFFFFFFFFFFFFFFFF)
+    return arr
 
 
 def penalty_params(n: int, presence, frequency, record=True):
@@ -695,11 +688,33 @@ class RWKVBatch:
         if not self._L.rwkv_mi_batch_state_to_context(self._ptr, slot, model._ctx.ptr):
             self._fail("rwkv_mi_batch_state_to_context")
 
-    def eval(self, slots: List[int], tokens: List[int], want_logits: bool = True) -> Optional[np.ndarray]:
-        """One token per named slot in one pass; logits [n][n_vocab] in call order (None when want_logits is False)."""
+    @staticmethod
+    def _slot_tokens(slots, tokens, what: str):
+        """slots and one token per slot (the argument named `what`) as uint32 arrays of one length"""
         s, t = _u32(slots), _u32(tokens)
         if s.size != t.size:
-            raise ValueError("slots and tokens differ in length")
+            raise ValueError(f"slots and {what} differ in length")
+        return s, t
+
+    def _sampled(self, name: str, n: int, want_logits: bool, *args):
+        """The single pass `name`(batch, *args, sampled_out, logits_out): tokens [n], with the logits [n][n_vocab] when want_logits."""
+        out = np.empty(n, dtype=np.uint32)
+        logits = np.empty((n, self._n_vocab), dtype=np.float32) if want_logits else None
+        if not getattr(self._L, name)(self._ptr, *args, out.ctypes.data_as(P_UINT32), ctypes.cast(_ptr(logits), P_FLOAT)):
+            self._fail(name)
+        return (out, logits) if want_logits else out
+
+    def _loop(self, name: str, n: int, n_tokens: int, *args) -> Tuple[np.ndarray, float]:
+        """The device loop `name`(batch, *args, tokens_out, elapsed_ms): tokens [n][n_tokens], elapsed milliseconds."""
+        out = np.empty((n, n_tokens), dtype=np.uint32)
+        ms = ctypes.c_float(0.0)
+        if not getattr(self._L, name)(self._ptr, *args, ctypes.cast(out.ctypes.data, P_UINT32), ctypes.byref(ms)):
+            self._fail(name)
+        return out, float(ms.value)
+
+    def eval(self, slots: List[int], tokens: List[int], want_logits: bool = True) -> Optional[np.ndarray]:
+        """One token per named slot in one pass; logits [n][n_vocab] in call order (None when want_logits is False)."""
+        s, t = self._slot_tokens(slots, tokens, "tokens")
         out = np.empty((s.size, self._n_vocab), dtype=np.float32) if want_logits else None
         if not self._L.rwkv_mi_batch_eval(self._ptr, s.ctypes.data_as(P_UINT32), t.ctypes.data_as(P_UINT32), s.size, ctypes.cast(_ptr(out), P_FLOAT)):
             self._fail("rwkv_mi_batch_eval")
@@ -707,43 +722,22 @@ class RWKVBatch:
 
     def decode_greedy(self, slots: List[int], first_tokens: List[int], n_tokens: int) -> Tuple[np.ndarray, float]:
         """Greedy loop on the device for every named slot: tokens [n][n_tokens], elapsed milliseconds."""
-        s, t = _u32(slots), _u32(first_tokens)
-        if s.size != t.size:
-            raise ValueError("slots and first_tokens differ in length")
-        out = np.empty((s.size, n_tokens), dtype=np.uint32)
-        ms = ctypes.c_float(0.0)
-        if not self._L.rwkv_mi_batch_decode_greedy(self._ptr, s.ctypes.data_as(P_UINT32), t.ctypes.data_as(P_UINT32), s.size, n_tokens,
-                                                   ctypes.cast(out.ctypes.data, P_UINT32), ctypes.byref(ms)):
-            self._fail("rwkv_mi_batch_decode_greedy")
-        return out, float(ms.value)
+        s, t = self._slot_tokens(slots, first_tokens, "first_tokens")
+        return self._loop("rwkv_mi_batch_decode_greedy", s.size, n_tokens, s.ctypes.data_as(P_UINT32), t.ctypes.data_as(P_UINT32), s.size, n_tokens)
 
     def eval_sample(self, slots: List[int], tokens: List[int], temperature=1.0, top_p=0.8, u=-1.0, seed=0, want_logits: bool = False):
         """One token per named slot in one pass, then one token sampled per row on the device: tokens [n] (and the logits [n][n_vocab]
         when want_logits). temperature, top_p, u, seed: a scalar (every row) or a sequence of length n. u < 0 draws from the slot's
         own stream uniform01(seed, counter of the slot)."""
-        s, t = _u32(slots), _u32(tokens)
-        if s.size != t.size:
-            raise ValueError("slots and tokens differ in length")
-        params = sample_params(s.size, temperature, top_p, u, seed)
-        out = np.empty(s.size, dtype=np.uint32)
-        logits = np.empty((s.size, self._n_vocab), dtype=np.float32) if want_logits else None
-        if not self._L.rwkv_mi_batch_eval_sample(self._ptr, s.ctypes.data_as(P_UINT32), t.ctypes.data_as(P_UINT32), s.size, params,
-                                                 out.ctypes.data_as(P_UINT32), ctypes.cast(_ptr(logits), P_FLOAT)):
-            self._fail("rwkv_mi_batch_eval_sample")
-        return (out, logits) if want_logits else out
+        s, t = self._slot_tokens(slots, tokens, "tokens")
+        return self._sampled("rwkv_mi_batch_eval_sample", s.size, want_logits, s.ctypes.data_as(P_UINT32), t.ctypes.data_as(P_UINT32), s.size,
+                             sample_params(s.size, temperature, top_p, u, seed))
 
     def decode_sample(self, slots: List[int], first_tokens: List[int], n_tokens: int, temperature=1.0, top_p=0.8, seed=0) -> Tuple[np.ndarray, float]:
         """Sampling loop on the device for every named slot (their draw counters start from 0): tokens [n][n_tokens], elapsed milliseconds."""
-        s, t = _u32(slots), _u32(first_tokens)
-        if s.size != t.size:
-            raise ValueError("slots and first_tokens differ in length")
-        params = sample_params(s.size, temperature, top_p, -1.0, seed)
-        out = np.empty((s.size, n_tokens), dtype=np.uint32)
-        ms = ctypes.c_float(0.0)
-        if not self._L.rwkv_mi_batch_decode_sample(self._ptr, s.ctypes.data_as(P_UINT32), t.ctypes.data_as(P_UINT32), s.size, n_tokens, params,
-                                                   ctypes.cast(out.ctypes.data, P_UINT32), ctypes.byref(ms)):
-            self._fail("rwkv_mi_batch_decode_sample")
-        return out, float(ms.value)
+        s, t = self._slot_tokens(slots, first_tokens, "first_tokens")
+        return self._loop("rwkv_mi_batch_decode_sample", s.size, n_tokens, s.ctypes.data_as(P_UINT32), t.ctypes.data_as(P_UINT32), s.size, n_tokens,
+                          sample_params(s.size, temperature, top_p, -1.0, seed))
 
     @staticmethod
     def _ragged(slots, token_lists):
@@ -772,13 +766,8 @@ class RWKVBatch:
         want_logits). The parameters as eval_sample takes them. Every row is sampled: give a non-final prompt chunk temperature 0 (an
         argmax, which leaves the slot's draw counter where it was)."""
         s, lens, toks = self._ragged(slots, token_lists)
-        params = sample_params(s.size, temperature, top_p, u, seed)
-        out = np.empty(s.size, dtype=np.uint32)
-        logits = np.empty((s.size, self._n_vocab), dtype=np.float32) if want_logits else None
-        if not self._L.rwkv_mi_batch_eval_ragged_sample(self._ptr, s.ctypes.data_as(P_UINT32), lens.ctypes.data_as(P_UINT32), toks.ctypes.data_as(P_UINT32),
-                                                        s.size, params, out.ctypes.data_as(P_UINT32), ctypes.cast(_ptr(logits), P_FLOAT)):
-            self._fail("rwkv_mi_batch_eval_ragged_sample")
-        return (out, logits) if want_logits else out
+        return self._sampled("rwkv_mi_batch_eval_ragged_sample", s.size, want_logits, s.ctypes.data_as(P_UINT32), lens.ctypes.data_as(P_UINT32),
+                             toks.ctypes.data_as(P_UINT32), s.size, sample_params(s.size, temperature, top_p, u, seed))
 
     def score_ragged(self, slots: List[int], token_lists: List[List[int]], target_lists: Optional[List[List[int]]] = None, want_argmax: bool = True):
         """token_lists[i] to slot slots[i], all rows in ONE pass (as eval_ragged), with the prediction after EVERY token: (list of logprob
@@ -833,48 +822,26 @@ class RWKVBatch:
                               record=True, want_logits: bool = False):
         """eval_sample with each row's logits less presence + count * frequency of its slot, plus the slot's bias; a row with `record`
         counts its token afterwards. presence, frequency, record: a scalar (every row) or a sequence of length n."""
-        s, t = _u32(slots), _u32(tokens)
-        if s.size != t.size:
-            raise ValueError("slots and tokens differ in length")
-        params = sample_params(s.size, temperature, top_p, u, seed)
-        pens = penalty_params(s.size, presence, frequency, record)
-        out = np.empty(s.size, dtype=np.uint32)
-        logits = np.empty((s.size, self._n_vocab), dtype=np.float32) if want_logits else None
-        if not self._L.rwkv_mi_batch_eval_sample_penalized(self._ptr, s.ctypes.data_as(P_UINT32), t.ctypes.data_as(P_UINT32), s.size, params, pens,
-                                                           out.ctypes.data_as(P_UINT32), ctypes.cast(_ptr(logits), P_FLOAT)):
-            self._fail("rwkv_mi_batch_eval_sample_penalized")
-        return (out, logits) if want_logits else out
+        s, t = self._slot_tokens(slots, tokens, "tokens")
+        return self._sampled("rwkv_mi_batch_eval_sample_penalized", s.size, want_logits, s.ctypes.data_as(P_UINT32), t.ctypes.data_as(P_UINT32), s.size,
+                             sample_params(s.size, temperature, top_p, u, seed), penalty_params(s.size, presence, frequency, record))
 
     def eval_ragged_sample_penalized(self, slots: List[int], token_lists: List[List[int]], temperature=1.0, top_p=0.8, u=-1.0, seed=0, presence=0.2,
                                      frequency=0.2, record=True, want_logits: bool = False):
         """eval_ragged_sample with the penalised draw. Give a non-final prompt chunk temperature 0 AND record False: nothing of the slot's
         draw counter or counts moves then."""
         s, lens, toks = self._ragged(slots, token_lists)
-        params = sample_params(s.size, temperature, top_p, u, seed)
-        pens = penalty_params(s.size, presence, frequency, record)
-        out = np.empty(s.size, dtype=np.uint32)
-        logits = np.empty((s.size, self._n_vocab), dtype=np.float32) if want_logits else None
-        if not self._L.rwkv_mi_batch_eval_ragged_sample_penalized(self._ptr, s.ctypes.data_as(P_UINT32), lens.ctypes.data_as(P_UINT32),
-                                                                  toks.ctypes.data_as(P_UINT32), s.size, params, pens, out.ctypes.data_as(P_UINT32),
-                                                                  ctypes.cast(_ptr(logits), P_FLOAT)):
-            self._fail("rwkv_mi_batch_eval_ragged_sample_penalized")
-        return (out, logits) if want_logits else out
+        return self._sampled("rwkv_mi_batch_eval_ragged_sample_penalized", s.size, want_logits, s.ctypes.data_as(P_UINT32), lens.ctypes.data_as(P_UINT32),
+                             toks.ctypes.data_as(P_UINT32), s.size, sample_params(s.size, temperature, top_p, u, seed),
+                             penalty_params(s.size, presence, frequency, record))
 
     def decode_sample_penalized(self, slots: List[int], first_tokens: List[int], n_tokens: int, temperature=1.0, top_p=0.8, seed=0, presence=0.2,
                                 frequency=0.2) -> Tuple[np.ndarray, float]:
         """decode_sample with the penalised draw, every step recorded: tokens [n][n_tokens], elapsed milliseconds. It continues -- neither
         the counts nor the draw counters are reset; call counts_reset(slot) and rng_seek(slot, 0) for a new request."""
-        s, t = _u32(slots), _u32(first_tokens)
-        if s.size != t.size:
-            raise ValueError("slots and first_tokens differ in length")
-        params = sample_params(s.size, temperature, top_p, -1.0, seed)
-        pens = penalty_params(s.size, presence, frequency, True)
-        out = np.empty((s.size, n_tokens), dtype=np.uint32)
-        ms = ctypes.c_float(0.0)
-        if not self._L.rwkv_mi_batch_decode_sample_penalized(self._ptr, s.ctypes.data_as(P_UINT32), t.ctypes.data_as(P_UINT32), s.size, n_tokens, params,
-                                                             pens, ctypes.cast(out.ctypes.data, P_UINT32), ctypes.byref(ms)):
-            self._fail("rwkv_mi_batch_decode_sample_penalized")
-        return out, float(ms.value)
+        s, t = self._slot_tokens(slots, first_tokens, "first_tokens")
+        return self._loop("rwkv_mi_batch_decode_sample_penalized", s.size, n_tokens, s.ctypes.data_as(P_UINT32), t.ctypes.data_as(P_UINT32), s.size, n_tokens,
+                          sample_params(s.size, temperature, top_p, -1.0, seed), penalty_params(s.size, presence, frequency, True))
 
     def free(self) -> None:
         if self._ptr:

@@ -295,6 +295,46 @@ RWKV_API bool rwkv_mi_sample_penalized(struct rwkv_context * ctx, float temperat
 RWKV_API bool rwkv_mi_decode_sample_penalized(struct rwkv_context * ctx, uint32_t first_token, size_t n_tokens, float temperature, float top_p, uint64_t seed,
                                               float presence, float frequency, uint32_t * tokens_out, float * elapsed_ms);
 
+/* ---- Stop sequences and per-row token budgets in the batch decode loops ----
+ * The three device loops above advance every row by exactly n_tokens passes. A request ends at a step of its own: at end of text, at a stop
+ * string such as the chat program's '\n\n' (chat_with_bot.py:245-276), or at its length limit. rwkv_mi_batch_decode_until is the loop of the
+ * same family -- params == NULL: the greedy loop; params without penalties: rwkv_mi_batch_decode_sample (the named slots' draw counters start
+ * from 0); both: rwkv_mi_batch_decode_sample_penalized (it continues, every step records) -- in which each row ends by itself.
+ * Row r emits tokens as its plain loop does: tokens_out[r][i] is the token chosen after pass i. It RETIRES after the first pass i at which
+ * its emitted tokens tokens_out[r][0..i] end with one of its stop sequences, or i + 1 == stops[r].max_tokens. Then lens_out[r] = i + 1 and
+ * stopped_by_out[r] = the index of the matching sequence among the row's own (the lowest when several match; a match at the budget's last step
+ * reports the match), or RWKV_MI_NO_TOKEN when the budget ended the row. Only tokens emitted by this call are matched: first_tokens[r] is not
+ * part of the window and a sequence cannot straddle two calls. n_seqs == 0: a budget only. A one-token sequence is a stop token ({0}: end of
+ * text). tokens_out[r][j] = RWKV_MI_NO_TOKEN for lens_out[r] <= j < stride.
+ * The rows' sequences are given back to back: seq_lens holds sum(n_seqs) lengths, row 0's first; seq_tokens their sum(seq_lens) tokens.
+ * THE GUARANTEE: after the call everything that belongs to slots[r] -- its state, the batch's parity for it, its draw counter, its occurrence
+ * table and the first lens_out[r] emitted tokens -- is, bit for bit and word for word, what the plain loop of the same family with
+ * n_tokens = lens_out[r] leaves when it runs that slot, whoever else was in the call and however long they ran. The stop token is emitted
+ * (and, penalised, recorded) but not fed: continue a slot by feeding tokens_out[r][lens_out[r] - 1], as after a plain loop. A retired row
+ * draws nothing, records nothing and advances no counter.
+ * The call ends when every row has retired, not at the largest budget: passes are enqueued in blocks of K (16; RWKV_MI_LOOP_BLOCK in
+ * 1 .. 1024 overrides it, read at the call) and the number of live rows of block b - 1 is read after block b has been enqueued, so at most 2 K
+ * passes run past the step at which the last row retired -- invisible in the results, counted by rwkv_mi_batch_last_loop_passes, covered by
+ * elapsed_ms. The buffers are allocated by the first call (RWKV_ERROR_ALLOC when they cannot be) and released by rwkv_mi_batch_free.
+ * Besides what the plain loop of its family rejects, the call returns false with RWKV_ERROR_ARGS and changes no slot, parity, counter, count or
+ * bias when stops or lens_out is NULL, penalties is given without params, a max_tokens is 0, stride is less than the largest max_tokens, an
+ * n_seqs is above RWKV_MI_STOP_MAX_SEQS, seq_lens is NULL with any n_seqs > 0 (or seq_tokens with any sequence), a sequence's length is 0 or
+ * above RWKV_MI_STOP_MAX_LEN, or a sequence token is >= n_vocab. A failure after the first pass leaves the named slots unspecified. */
+#define RWKV_MI_STOP_MAX_SEQS 16          /* stop sequences per row */
+#define RWKV_MI_STOP_MAX_LEN  8           /* tokens per stop sequence */
+#define RWKV_MI_NO_TOKEN      UINT32_MAX
+struct rwkv_mi_stop_params { uint32_t max_tokens; uint32_t n_seqs; };   /* 8 bytes */
+RWKV_API bool rwkv_mi_batch_decode_until(struct rwkv_mi_batch * batch, const uint32_t * slots, const uint32_t * first_tokens, size_t n,
+                                         const struct rwkv_mi_sample_params * params       /* [n], NULL: greedy */,
+                                         const struct rwkv_mi_penalty_params * penalties   /* [n], NULL: the plain draw; needs params */,
+                                         const struct rwkv_mi_stop_params * stops          /* [n] */,
+                                         const uint32_t * seq_lens                         /* the rows' sequences back to back: sum(n_seqs) lengths ... */,
+                                         const uint32_t * seq_tokens                       /* ... and their tokens back to back: sum(seq_lens) words */,
+                                         size_t stride, uint32_t * tokens_out /* [n][stride], may be NULL */, uint32_t * lens_out /* [n] */,
+                                         uint32_t * stopped_by_out /* [n], may be NULL */, float * elapsed_ms /* may be NULL */);
+/* passes the last device loop of the batch enqueued (0 before the first) */
+RWKV_API size_t rwkv_mi_batch_last_loop_passes(const struct rwkv_mi_batch * batch);
+
 #if defined(__cplusplus)
 }
 #endif

@@ -7,6 +7,7 @@ from .rwkv_cpp import (  # noqa: F401
     HOOKS_LIB_PATH,
     LIB_PATH,
     NO_TARGET,
+    NO_TOKEN,
     PenaltyParams,
     RWKVBatch,
     RWKVContext,
@@ -14,8 +15,10 @@ from .rwkv_cpp import (  # noqa: F401
     RWKVSharedLibrary,
     SAMPLE_HOOKS_LIB_PATH,
     SampleParams,
+    StopParams,
     build_library,
     load_rwkv_shared_library,
     penalty_params,
     sample_params,
+    stop_params,
 )

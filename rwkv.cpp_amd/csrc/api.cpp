@@ -874,6 +874,16 @@ struct rwkv_mi_batch {
     size_t seg_cap = 0;
     std::vector<SegState> long_segs;
     SegPass pass;
+    // rwkv_mi_batch_decode_until: the words of a call in one device buffer with its pinned staging, laid out by batch_upload_stops for the call's
+    // n and sequences (capacity: n_slots rows of RWKV_MI_STOP_MAX_SEQS sequences of RWKV_MI_STOP_MAX_LEN tokens); the live count of the last two
+    // blocks in pinned memory, each behind its event -- allocated by the first call of that family
+    uint8_t * d_stop = nullptr;
+    uint8_t * h_stop = nullptr;
+    uint32_t * h_live_count = nullptr;   // [2]
+    hipEvent_t ev_block[2] = {nullptr, nullptr};
+    StopTables stop{};                   // the device pointers of the current call
+    size_t stop_off_lens = 0;            // where lens[n], reasons[n] start in both buffers
+    size_t last_loop_passes = 0;
 
     float * slot_buf(size_t slot, int p) const { return states + ((size_t) p * n_slots + slot) * (size_t) state_len; }
 };
@@ -885,8 +895,9 @@ static bool batch_fail_through(rwkv_mi_batch * B) { B->ctx->last_error |= B->run
     do { hipError_t e_ = (CALL); RW_CTX_CHECK((B)->ctx, RWKV_ERROR_GRAPH, false, e_ == hipSuccess, "HIP error: %s", hipGetErrorString(e_)); } while (0)
 
 // What a batch call is: a point on three axes. The input -- one token per row, or a segment per row (lens); the draw -- none,
-// the sampler, or the penalised sampler; the repeat -- one pass (batch_pass) or a device loop of n_tokens steps (batch_loop, where no draw
-// means the greedy argmax). Every entry point fills in this description and calls one of the two bodies.
+// the sampler, or the penalised sampler; the repeat -- one pass (batch_pass), a device loop of n_tokens steps (batch_loop, where no draw
+// means the greedy argmax), or that loop with every row ending by itself (batch_until). Every entry point fills in this description and calls one
+// of the three bodies.
 enum class Draw { none, sample, penalized };
 struct BatchCall {
     const uint32_t * slots, * tokens;   // row i is slot slots[i] fed tokens[i] ...
@@ -904,6 +915,14 @@ struct BatchCall {
     const uint32_t * targets = nullptr;
     float * logprobs_out = nullptr;
     uint32_t * argmax_out = nullptr;
+    // rwkv_mi_batch_decode_until (until: the call is one; batch_until is its body): a budget and stop sequences per row, the rows' sequences back
+    // to back in seq_lens / seq_tokens; tokens_out is [n][stride]
+    bool until = false;
+    const rwkv_mi_stop_params * stops = nullptr;
+    const uint32_t * seq_lens = nullptr, * seq_tokens = nullptr;
+    size_t stride = 0;
+    uint32_t * lens_out = nullptr;
+    uint32_t * stopped_by_out = nullptr;
 };
 
 // n, slots, lens and tokens of a call: no slot changes when they are rejected. Row i feeds lens[i] consecutive tokens to slot slots[i]; the
@@ -1101,25 +1120,99 @@ static bool batch_upload_ragged(rwkv_mi_batch * B, const BatchCall & c, size_t T
     return true;
 }
 
-// ---- the two bodies of the batch calls ----
+// ---- stop sequences and budgets (rwkv_mi_batch_decode_until) ----
+
+// the stop arguments of a call (checked with the other arguments, before anything changes)
+static bool batch_check_stops(rwkv_mi_batch * B, const BatchCall & c) {
+    rwkv_context * ctx = B->ctx;
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, c.stops != nullptr && c.lens_out != nullptr, "stops or lens_out is NULL");
+    const size_t n_vocab = (size_t) ctx->model->n_vocab();
+    size_t n_seqs = 0, n_toks = 0;
+    for (size_t i = 0; i < c.n; i++) {
+        const rwkv_mi_stop_params & sp = c.stops[i];
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, sp.max_tokens > 0, "max_tokens at index %zu is 0", i);
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, (size_t) sp.max_tokens <= c.stride, "stride (%zu) is less than max_tokens at index %zu (%" PRIu32 ")", c.stride, i, sp.max_tokens);
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, sp.n_seqs <= RWKV_MI_STOP_MAX_SEQS, "n_seqs at index %zu (%" PRIu32 ") is above %d", i, sp.n_seqs, RWKV_MI_STOP_MAX_SEQS);
+        n_seqs += sp.n_seqs;
+    }
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, n_seqs == 0 || c.seq_lens != nullptr, "seq_lens is NULL");
+    for (size_t s = 0; s < n_seqs; s++) {
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, c.seq_lens[s] > 0 && c.seq_lens[s] <= RWKV_MI_STOP_MAX_LEN, "the length of stop sequence %zu (%" PRIu32 ") must be in 1 .. %d",
+                     s, c.seq_lens[s], RWKV_MI_STOP_MAX_LEN);
+        n_toks += c.seq_lens[s];
+    }
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, n_toks == 0 || c.seq_tokens != nullptr, "seq_tokens is NULL");
+    for (size_t t = 0; t < n_toks; t++)
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, c.seq_tokens[t] < n_vocab, "stop token at index %zu (%" PRIu32 ") is out of range (0 .. %zu)", t, c.seq_tokens[t], n_vocab - 1);
+    return true;
+}
+
+// bytes of the stop words of a call of n rows with n_seqs sequences of n_toks tokens in all: rows, live, lens, reasons, live count, lengths, tokens
+static size_t stop_bytes(size_t n, size_t n_seqs, size_t n_toks) { return n * sizeof(StopRow) + (3 * n + 1 + n_seqs + n_toks) * sizeof(uint32_t); }
+
+// the stop buffers and the two block events: on the first call of the family
+static bool batch_ensure_stop(rwkv_mi_batch * B) {
+    rwkv_context * ctx = B->ctx;
+    if (B->d_stop && B->h_stop && B->h_live_count && B->ev_block[0] && B->ev_block[1]) return true;
+    const size_t bytes = stop_bytes(B->n_slots, B->n_slots * RWKV_MI_STOP_MAX_SEQS, B->n_slots * RWKV_MI_STOP_MAX_SEQS * RWKV_MI_STOP_MAX_LEN);
+    hipError_t e = hipSuccess;
+    if (!B->d_stop) e = hipMalloc((void **) &B->d_stop, bytes);
+    if (e == hipSuccess && !B->h_stop) e = hipHostMalloc((void **) &B->h_stop, bytes, hipHostMallocDefault);
+    if (e == hipSuccess && !B->h_live_count) e = hipHostMalloc((void **) &B->h_live_count, 2 * sizeof(uint32_t), hipHostMallocDefault);
+    for (hipEvent_t & ev : B->ev_block) if (e == hipSuccess && !ev) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    if (e != hipSuccess) (void) hipGetLastError();
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the stop tables of %zu slots: %s", B->n_slots, hipGetErrorString(e));
+    return true;
+}
+
+// the stop words of the n rows, one upload per call (after batch_upload: the stream has been drained, the staging is free): every row live,
+// no length, no reason, n rows to go
+static bool batch_upload_stops(rwkv_mi_batch * B, const BatchCall & c) {
+    const size_t n = c.n;
+    size_t n_seqs = 0, n_toks = 0;
+    StopRow * rows = (StopRow *) B->h_stop;
+    for (size_t i = 0; i < n; i++) {
+        rows[i] = StopRow{c.stops[i].max_tokens, c.stops[i].n_seqs, (uint32_t) n_seqs, (uint32_t) n_toks};
+        for (uint32_t s = 0; s < c.stops[i].n_seqs; s++) n_toks += c.seq_lens[n_seqs + s];
+        n_seqs += c.stops[i].n_seqs;
+    }
+    const size_t off_live = n * sizeof(StopRow), off_lens = off_live + n * 4, off_reasons = off_lens + n * 4, off_count = off_reasons + n * 4;
+    const size_t off_sl = off_count + 4, off_st = off_sl + n_seqs * 4, bytes = off_st + n_toks * 4;
+    uint32_t * live = (uint32_t *) (B->h_stop + off_live), * lens = (uint32_t *) (B->h_stop + off_lens), * reasons = (uint32_t *) (B->h_stop + off_reasons);
+    for (size_t i = 0; i < n; i++) { live[i] = 1u; lens[i] = 0u; reasons[i] = RWKV_MI_NO_TOKEN; }
+    *(uint32_t *) (B->h_stop + off_count) = (uint32_t) n;
+    if (n_seqs) memcpy(B->h_stop + off_sl, c.seq_lens, n_seqs * 4);
+    if (n_toks) memcpy(B->h_stop + off_st, c.seq_tokens, n_toks * 4);
+    BATCH_HIP_OK(B, hipMemcpyAsync(B->d_stop, B->h_stop, bytes, hipMemcpyHostToDevice, B->run->stream));
+    uint8_t * d = B->d_stop;
+    B->stop = StopTables{(const StopRow *) d, (const uint32_t *) (d + off_sl), (const uint32_t *) (d + off_st), (uint32_t *) (d + off_live),
+                         (uint32_t *) (d + off_lens), (uint32_t *) (d + off_reasons), (uint32_t *) (d + off_count)};
+    B->stop_off_lens = off_lens;
+    return true;
+}
+
+// ---- the bodies of the batch calls ----
 
 // every argument of a call, nothing changed yet, in the order the entry points report them: rows, targets, params, penalties. u_used: the rows'
 // u is read (a single pass; in a loop the generator draws)
 static bool batch_check_args(rwkv_mi_batch * B, const BatchCall & c, bool u_used, size_t * T_out) {
     if (!batch_check_rows(B, c, T_out) || !check_targets(B->ctx, c.targets, *T_out, c.logprobs_out)) return false;
     if (c.draw != Draw::none && !batch_check_params(B, c.params, c.n, u_used)) return false;
-    return c.draw != Draw::penalized || batch_check_penalties(B, c.penalties, c.n);
+    if (c.draw == Draw::penalized && !batch_check_penalties(B, c.penalties, c.n)) return false;
+    return !c.until || batch_check_stops(B, c);
 }
 
 // the buffers the draw of a call needs: the plain sampler allocates none of the penalty tables
 static bool batch_ensure_draw(rwkv_mi_batch * B, const BatchCall & c) {
+    if (c.until && !batch_ensure_stop(B)) return false;
     if (c.draw == Draw::penalized) return batch_ensure_penalty(B);
     return c.draw == Draw::none || batch_ensure_sampler(B);
 }
 
-// the rows or the segments of a call (that drains the stream first), then its sampler table. loop: both row tables
+// the rows or the segments of a call (that drains the stream first), then its stop words and its sampler table. loop: both row tables
 static bool batch_upload_call(rwkv_mi_batch * B, const BatchCall & c, size_t T, bool loop) {
     if (!(c.lens ? batch_upload_ragged(B, c, T) : batch_upload(B, c, loop ? 2 : 1))) return false;
+    if (c.until && !batch_upload_stops(B, c)) return false;
     if (c.draw == Draw::penalized) return batch_upload_penalty_rows(B, c, loop);
     return c.draw == Draw::none || batch_upload_params(B, c, loop);
 }
@@ -1206,6 +1299,78 @@ static bool batch_loop(rwkv_mi_batch * B, const BatchCall & c, size_t n_tokens, 
     for (size_t r = 0; r < n && tokens_out; r++)
         for (size_t i = 0; i < n_tokens; i++) tokens_out[r * n_tokens + i] = h[i * n + r];
     if (n_tokens & 1) batch_flip(B, c);
+    B->last_loop_passes = n_tokens;
+    return true;
+}
+
+// passes per block of batch_until: 16, or RWKV_MI_LOOP_BLOCK in 1 .. 1024 (read at the call)
+static size_t loop_block() {
+    const char * e = getenv("RWKV_MI_LOOP_BLOCK");
+    if (!e || !e[0]) return 16;
+    char * end = nullptr;
+    const long v = strtol(e, &end, 10);
+    return (*end == 0 && v >= 1 && v <= 1024) ? (size_t) v : 16;
+}
+
+// The device loop in which every row ends by itself (rwkv_mi_batch_decode_until): batch_loop's passes, the draw behind the rows' live words and
+// followed by the stop test (engine.hip launch_row_sampler, sampling.hip k_stop_rows), which retires a row ON THE DEVICE by rewriting its entries
+// of the two row tables -- the model's kernels never learn of it. What the host adds is when to stop enqueuing: passes go out in blocks of K; behind
+// each block the live count is copied to pinned memory and an event recorded; after enqueuing block b the host waits for the event of block
+// b - 1 (which has long passed, or passes while block b runs: the device is never idle for it) and stops when that count is 0. Passes past a
+// row's retirement are dead steps into the row's other buffer: at most 2 K of them run after the last row has retired.
+static bool batch_until(rwkv_mi_batch * B, const BatchCall & c, uint32_t * tokens_out, float * elapsed_ms) {
+    rwkv_context * ctx = B->ctx;
+    rwkv_context * run = B->run;
+    size_t T = 0;
+    if (!batch_check_args(B, c, false, &T)) return false;
+    run->print_errors = ctx->print_errors;
+    const size_t n = c.n, K = loop_block();
+    size_t budget = 0;
+    for (size_t i = 0; i < n; i++) budget = std::max(budget, (size_t) c.stops[i].max_tokens);
+    BATCH_HIP_OK(B, hipSetDevice(ctx->model->device));
+    if (!batch_ensure_draw(B, c)) return false;
+    DevBuf<uint32_t> hist;   // [budget][n], freed on every exit; a word no row wrote stays RWKV_MI_NO_TOKEN
+    hipError_t he = hist.alloc(budget * n);
+    if (he != hipSuccess) (void) hipGetLastError();
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, false, he == hipSuccess, "cannot allocate the history of %zu steps of %zu rows: %s", budget, n, hipGetErrorString(he));
+    if (!batch_upload_call(B, c, T, true)) return false;
+    if (c.draw == Draw::sample) launch_sample_seek_rows(B->d_srows, (int64_t) n, 0ull, run->stream);   // the named slots' streams start over
+    BATCH_HIP_OK(B, hipMemsetAsync(hist.p, 0xFF, budget * n * sizeof(uint32_t), run->stream));
+    BATCH_HIP_OK(B, hipEventRecord(run->ev0, run->stream));
+    size_t passes = 0;
+    for (size_t b = 0; passes < budget; b++) {
+        for (const size_t end = std::min(budget, passes + K); passes < end; passes++) {
+            RowState * used = B->d_rows + (passes & 1) * B->n_slots, * other = B->d_rows + ((passes & 1) ^ 1) * B->n_slots;
+            const RowStop stop{B->stop, (uint32_t) passes, used, other};
+            RowSampler sampler = batch_sampler(B, c, hist.p);
+            if (c.draw == Draw::none) sampler.table = nullptr;   // (no draw: the greedy argmax)
+            sampler.stop = &stop;
+            if (!forward_rows(run, used, (int64_t) n, true, &sampler)) return batch_fail_drained(B);
+        }
+        hipError_t e = hipMemcpyAsync(B->h_live_count + (b & 1), B->stop.live_count, sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream);
+        if (e == hipSuccess) e = hipEventRecord(B->ev_block[b & 1], run->stream);
+        if (e == hipSuccess && b > 0) e = hipEventSynchronize(B->ev_block[(b - 1) & 1]);
+        if (e != hipSuccess) { (void) hipStreamSynchronize(run->stream); BATCH_HIP_OK(B, e); }
+        if (b > 0 && B->h_live_count[(b - 1) & 1] == 0) break;
+    }
+    BATCH_HIP_OK(B, hipEventRecord(run->ev1, run->stream));
+    std::vector<uint32_t> h(tokens_out ? passes * n : 0);
+    uint32_t * h_lens = (uint32_t *) (B->h_stop + B->stop_off_lens);   // lens[n], then reasons[n]
+    if (tokens_out) BATCH_HIP_OK(B, hipMemcpyAsync(h.data(), hist.p, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream));
+    BATCH_HIP_OK(B, hipMemcpyAsync(h_lens, B->stop.lens, 2 * n * sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream));
+    BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));
+    if (elapsed_ms) BATCH_HIP_OK(B, hipEventElapsedTime(elapsed_ms, run->ev0, run->ev1));
+    B->last_loop_passes = passes;
+    // (every budget is at most `budget`, and the loop ends on a live count of 0 or at `budget`: every row has retired)
+    for (size_t r = 0; r < n; r++)
+        RW_CTX_CHECK(ctx, RWKV_ERROR_GRAPH, false, h_lens[r] > 0 && h_lens[r] <= passes, "row %zu did not retire (the device loop failed)", r);
+    for (size_t r = 0; r < n; r++) {
+        const size_t len = h_lens[r];
+        c.lens_out[r] = (uint32_t) len;
+        if (c.stopped_by_out) c.stopped_by_out[r] = h_lens[n + r];
+        for (size_t j = 0; tokens_out && j < c.stride; j++) tokens_out[r * c.stride + j] = j < len ? h[j * n + r] : RWKV_MI_NO_TOKEN;
+        if (len & 1) B->parity[c.slots[r]] ^= 1;
+    }
     return true;
 }
 
@@ -1230,6 +1395,10 @@ RWKV_API void rwkv_mi_batch_free(struct rwkv_mi_batch * B) {
     if (B->h_prows) (void) hipHostFree(B->h_prows);
     if (B->d_seg) (void) hipFree(B->d_seg);
     if (B->h_seg) (void) hipHostFree(B->h_seg);
+    if (B->d_stop) (void) hipFree(B->d_stop);
+    if (B->h_stop) (void) hipHostFree(B->h_stop);
+    if (B->h_live_count) (void) hipHostFree(B->h_live_count);
+    for (hipEvent_t ev : B->ev_block) if (ev) (void) hipEventDestroy(ev);
     batch_context_destroy(B->run);
     delete B;
 }
@@ -1457,5 +1626,21 @@ RWKV_API bool rwkv_mi_batch_decode_sample_penalized(struct rwkv_mi_batch * B, co
     c.draw = Draw::penalized; c.params = params; c.penalties = penalties;
     return batch_loop(B, c, n_tokens, tokens_out, elapsed_ms);
 }
+
+RWKV_API bool rwkv_mi_batch_decode_until(struct rwkv_mi_batch * B, const uint32_t * slots, const uint32_t * first_tokens, size_t n,
+                                         const struct rwkv_mi_sample_params * params, const struct rwkv_mi_penalty_params * penalties,
+                                         const struct rwkv_mi_stop_params * stops, const uint32_t * seq_lens, const uint32_t * seq_tokens,
+                                         size_t stride, uint32_t * tokens_out, uint32_t * lens_out, uint32_t * stopped_by_out, float * elapsed_ms) {
+    B->ctx->last_error = RWKV_ERROR_NONE;
+    RW_CTX_CHECK(B->ctx, RWKV_ERROR_ARGS, false, params != nullptr || penalties == nullptr, "penalties are given without params");
+    BatchCall c{slots, first_tokens, n};
+    c.draw = penalties ? Draw::penalized : params ? Draw::sample : Draw::none;
+    c.params = params; c.penalties = penalties;
+    c.until = true; c.stops = stops; c.seq_lens = seq_lens; c.seq_tokens = seq_tokens;
+    c.stride = stride; c.lens_out = lens_out; c.stopped_by_out = stopped_by_out;
+    return batch_until(B, c, tokens_out, elapsed_ms);
+}
+
+RWKV_API size_t rwkv_mi_batch_last_loop_passes(const struct rwkv_mi_batch * B) { return B ? B->last_loop_passes : 0; }
 
 }  // extern "C"

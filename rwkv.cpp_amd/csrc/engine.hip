@@ -855,6 +855,16 @@ void batch_context_destroy(rwkv_context * c) {
 // The row sampler of a batch pass over the `rows` rows of ctx->d_logits: row r's token goes to ctx->d_tokens[r] (and to s.hist[r] when given).
 static void launch_row_sampler(rwkv_context * ctx, const RowSampler & s, int64_t rows) {
     const int n_vocab = (int) ctx->model->n_vocab();
+    if (s.stop) {
+        // a step of rwkv_mi_batch_decode_until: the draw behind the live words, then the stop test on what it wrote
+        uint32_t * hist = s.hist + (size_t) s.stop->step * (size_t) rows;
+        const uint32_t * live = s.stop->t.live;
+        if (s.ptable) launch_pen_sample_rows_live(ctx->d_logits, rows, n_vocab, s.ptable, s.probs, ctx->d_tokens, hist, live, ctx->stream);
+        else if (s.table) launch_sample_rows_live(ctx->d_logits, rows, n_vocab, s.table, s.probs, ctx->d_tokens, hist, live, ctx->stream);
+        else launch_argmax_live(ctx->d_logits, rows, n_vocab, ctx->d_tokens, hist, live, ctx->stream);
+        launch_stop_rows(s.stop->t, rows, s.hist, s.stop->step, s.stop->used, s.stop->other, ctx->stream);
+        return;
+    }
     if (s.ptable) launch_pen_sample_rows(ctx->d_logits, rows, n_vocab, s.ptable, s.probs, ctx->d_tokens, s.hist, ctx->stream);
     else launch_sample_rows(ctx->d_logits, rows, n_vocab, s.table, s.probs, ctx->d_tokens, s.hist, ctx->stream);
 }

@@ -141,6 +141,8 @@ void launch_fill_state_v4(float * state, int64_t n_layer, int64_t D, hipStream_t
 // argmax of each row of logits[rows][n] -> out[row] (first index of the maximum; NaN never wins), and hist[row] unless hist is nullptr.
 // Feeds the next embedding lookup of the on-device greedy decode loops.
 void launch_argmax(const float * logits, int64_t rows, int64_t n, uint32_t * out, uint32_t * hist, hipStream_t st);
+// the same behind a per-row live word (rwkv_mi_batch_decode_until): a row with live[row] == 0 reads nothing and writes nothing
+void launch_argmax_live(const float * logits, int64_t rows, int64_t n, uint32_t * out, uint32_t * hist, const uint32_t * live, hipStream_t st);
 
 // Scoring (score.hip, k_score_rows): per row of logits[rows][n], argmax[row] by launch_argmax's rule and
 //   logprobs[row] = (float) ((double) l[targets[row]] - (m + log(sum_j exp((double) l[j] - m)))),  m = the row maximum, the sum in float64 in a fixed order;

@@ -1368,7 +1368,7 @@ void launch_fill_state_v4(float * state, int64_t n_layer, int64_t D, hipStream_t
 }
 
 // one workgroup per row of logits[rows][n]
-__global__ __launch_bounds__(1024) void k_argmax(const float * __restrict__ logits_all, int64_t n, uint32_t * __restrict__ out, uint32_t * __restrict__ hist) {
+__device__ __forceinline__ void argmax_row(const float * __restrict__ logits_all, int64_t n, uint32_t * __restrict__ out, uint32_t * __restrict__ hist) {
     __shared__ float l_v[16];
     __shared__ int l_i[16];
     const int64_t row = blockIdx.x;
@@ -1406,8 +1406,20 @@ __global__ __launch_bounds__(1024) void k_argmax(const float * __restrict__ logi
         if (hist) hist[row] = tok;
     }
 }
+__global__ __launch_bounds__(1024) void k_argmax(const float * __restrict__ logits_all, int64_t n, uint32_t * __restrict__ out, uint32_t * __restrict__ hist) {
+    argmax_row(logits_all, n, out, hist);
+}
+// the same row behind its live word (rwkv_mi_batch_decode_until, greedy): a retired row reads no logit and writes no token
+__global__ __launch_bounds__(1024) void k_argmax_live(const float * __restrict__ logits_all, int64_t n, uint32_t * __restrict__ out, uint32_t * __restrict__ hist,
+                                                      const uint32_t * __restrict__ live) {
+    if (!live[blockIdx.x]) return;
+    argmax_row(logits_all, n, out, hist);
+}
 void launch_argmax(const float * logits, int64_t rows, int64_t n, uint32_t * out, uint32_t * hist, hipStream_t st) {
     hipLaunchKernelGGL(k_argmax, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, out, hist);
+}
+void launch_argmax_live(const float * logits, int64_t rows, int64_t n, uint32_t * out, uint32_t * hist, const uint32_t * live, hipStream_t st) {
+    hipLaunchKernelGGL(k_argmax_live, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, out, hist, live);
 }
 
 // load-time transpose of the v6 mix matrix: [5][D][R] (file) -> [5][R][D], so that lanes read consecutive d

@@ -124,6 +124,21 @@ void launch_pen_sample(const float * logits, int n, float temperature, float top
                        float presence, float frequency, uint32_t record, uint32_t * count, const float * bias,
                        float * probs, uint32_t * out_token, uint32_t * hist, int hist_pos, hipStream_t st);
 void launch_pen_sample_rows(const float * logits, int64_t rows, int n, const PenaltyRow * table, float * probs, uint32_t * tokens, uint32_t * hist, hipStream_t st);
+// rwkv_mi_batch_decode_until (sampling.hip): the two row samplers behind a per-row live word -- a row with live[r] == 0 returns before it reads
+// a logit: no draw, no counter advance, no count, no token or history word -- and the stop test that retires rows.
+void launch_sample_rows_live(const float * logits, int64_t rows, int n, const SampleRow * table, float * probs, uint32_t * tokens, uint32_t * hist,
+                             const uint32_t * live, hipStream_t st);
+void launch_pen_sample_rows_live(const float * logits, int64_t rows, int n, const PenaltyRow * table, float * probs, uint32_t * tokens, uint32_t * hist,
+                                 const uint32_t * live, hipStream_t st);
+// A row's stop parameters and where its sequences start in the call's flat tables: its lengths at seq_lens[seq0 ..], its tokens at seq_tokens[tok0 ..].
+struct StopRow { uint32_t max_tokens, n_seqs, seq0, tok0; };
+// The device words of a call: per row its live word (1 until it retires), its length and its reason (the index of the matching sequence, or
+// RWKV_MI_NO_TOKEN for the budget) once it has; live_count: the rows still live.
+struct StopTables { const StopRow * rows; const uint32_t * seq_lens, * seq_tokens; uint32_t * live, * lens, * reasons, * live_count; };
+// After the draw of pass `step` (hist: [step][rows], this call's tokens): retires the live rows whose tokens end with one of their sequences or
+// whose budget is step + 1. A retired row gets {in = what pass `step` wrote, out = its other buffer} in both row tables (used: the table of
+// pass `step`, other: the one of pass step + 1).
+void launch_stop_rows(const StopTables & t, int64_t rows, const uint32_t * hist, uint32_t step, RowState * used, RowState * other, hipStream_t st);
 void launch_count_add(uint32_t * count, const uint32_t * tokens, int64_t n, int n_vocab, hipStream_t st);                        // count[tokens[i]] += 1
 void launch_bias_scatter(float * bias, const uint32_t * ids, const float * values, int64_t n, int n_vocab, hipStream_t st);     // bias[ids[i]] = values[i]
 
@@ -258,7 +273,10 @@ rwkv_context * batch_context_create(Model * m, int64_t max_rows);
 void batch_context_destroy(rwkv_context * c);
 // sample: when given, one sampled token per row from the pass's logits (launch_sample_rows), launched inside the pass's place in the chain
 // (ptable: the penalised row table; when given, launch_pen_sample_rows takes the place of launch_sample_rows and `table` is not read)
-struct RowSampler { const SampleRow * table; float * probs; uint32_t * hist; const PenaltyRow * ptable = nullptr; };
+// stop: the pass is step `step` of rwkv_mi_batch_decode_until -- the draw (with neither table: the greedy argmax) runs behind the live words and
+// launch_stop_rows follows it, both inside the pass's place in the chain; hist is then the WHOLE history [step][T] and step's row is written
+struct RowStop { StopTables t; uint32_t step; RowState * used, * other; };
+struct RowSampler { const SampleRow * table; float * probs; uint32_t * hist; const PenaltyRow * ptable = nullptr; const RowStop * stop = nullptr; };
 bool forward_rows(rwkv_context * ctx, const RowState * d_rows, int64_t T, bool want_logits, const RowSampler * sample = nullptr);
 
 // Ragged batch pass: row i of the call is a SEGMENT, tokens [t0, t1) of the pass, consecutive tokens of one slot's sequence.

@@ -15,6 +15,8 @@
 // (the reference's chat program, chat_with_bot.py:246-247 -- its loop runs over the tokens that have occurred -- then sample_logits'
 // logit_bias, sampling.py:27-36; every operation rounded to f32 in that order) from the sequence's occurrence table count[n] and its
 // optional bias table, and counts the chosen token afterwards.
+// rwkv_mi_batch_decode_until: k_sample_rows_live / k_pen_sample_rows_live are the two row samplers behind a per-row live word, and
+// k_stop_rows retires a row -- stop sequence or budget -- by rewriting its entries of the two row tables on the device.
 // The logits themselves are never written.
 #include "kdev.h"
 #include "model.h"
@@ -214,6 +216,19 @@ __global__ __launch_bounds__(1024) void k_sample_rows(const float * __restrict__
     sample_body([=](int i0) { return PlainLogits{lg + i0}; }, n, p.temperature, p.top_p, p.u, p.seed, table[r].counter, probs + r * stride, tokens + r, hist ? hist + r : nullptr);
 }
 
+// The row form behind its LIVE WORD (rwkv_mi_batch_decode_until), a third entry point over the same body: a row that has retired returns
+// before it reads a logit -- no draw, no counter advance, no token or history word. The whole workgroup takes the branch together: no barrier
+// is left waiting. hist is always given here.
+__global__ __launch_bounds__(1024) void k_sample_rows_live(const float * __restrict__ logits, int n, const SampleRow * __restrict__ table,
+                                                           float * __restrict__ probs, size_t stride, uint32_t * __restrict__ tokens, uint32_t * __restrict__ hist,
+                                                           const uint32_t * __restrict__ live) {
+    const size_t r = blockIdx.x;
+    if (!live[r]) return;
+    const rwkv_mi_sample_params p = table[r].p;
+    const float * lg = logits + r * (size_t) n;
+    sample_body([=](int i0) { return PlainLogits{lg + i0}; }, n, p.temperature, p.top_p, p.u, p.seed, table[r].counter, probs + r * stride, tokens + r, hist + r);
+}
+
 // The penalised entry points: the same body on the adjusted logits, then -- when `record` is set -- the chosen token's count goes up by
 // one (thread 0, after the draw, argmax or not: the draw of step i has seen the counts of the steps before it).
 __global__ __launch_bounds__(1024) void k_pen_sample(const float * __restrict__ logits, int n, float temperature, float top_p, float u_in,
@@ -233,6 +248,49 @@ __global__ __launch_bounds__(1024) void k_pen_sample_rows(const float * __restri
     const int pick = sample_body([=](int i0) { return PenalisedLogits{lg + i0, row.count + i0, row.bias ? row.bias + i0 : nullptr, row.presence, row.frequency}; },
                                  n, row.p.temperature, row.p.top_p, row.p.u, row.p.seed, row.counter, probs + r * stride, tokens + r, hist ? hist + r : nullptr);
     if (threadIdx.x == 0 && row.record) row.count[pick] += 1u;
+}
+
+// ... and behind its live word: a retired row records nothing either
+__global__ __launch_bounds__(1024) void k_pen_sample_rows_live(const float * __restrict__ logits, int n, const PenaltyRow * __restrict__ table,
+                                                               float * __restrict__ probs, size_t stride, uint32_t * __restrict__ tokens, uint32_t * __restrict__ hist,
+                                                               const uint32_t * __restrict__ live) {
+    const size_t r = blockIdx.x;
+    if (!live[r]) return;
+    const PenaltyRow row = table[r];
+    const float * lg = logits + r * (size_t) n;
+    const int pick = sample_body([=](int i0) { return PenalisedLogits{lg + i0, row.count + i0, row.bias ? row.bias + i0 : nullptr, row.presence, row.frequency}; },
+                                 n, row.p.temperature, row.p.top_p, row.p.u, row.p.seed, row.counter, probs + r * stride, tokens + r, hist + r);
+    if (threadIdx.x == 0 && row.record) row.count[pick] += 1u;
+}
+
+// The stop test of rwkv_mi_batch_decode_until, one thread per row, after the draw of pass `step` of the call (hist: [step][n], the tokens this
+// call has emitted). A live row retires when its emitted tokens end with one of its stop sequences (the lowest index wins) or when step + 1
+// is its budget: its length and reason are written, its live word cleared, the live count taken down by one -- and BOTH row tables get the
+// entry {in = F, out = G}, F the buffer pass `step` wrote for the row (`used`, the table of that pass, holds it as .out), G the other one.
+// From the next pass on the row recomputes a dead step from F into G; F, the state of the row's last token, is never written again.
+__global__ __launch_bounds__(64) void k_stop_rows(StopTables t, int n, const uint32_t * __restrict__ hist, uint32_t step, RowState * used, RowState * other) {
+    const int r = blockIdx.x * 64 + threadIdx.x;
+    if (r >= n || !t.live[r]) return;
+    const StopRow sr = t.rows[r];
+    const uint32_t * sl = t.seq_lens + sr.seq0;
+    const uint32_t * tk = t.seq_tokens + sr.tok0;
+    uint32_t reason = RWKV_MI_NO_TOKEN;
+    for (uint32_t s = 0; s < sr.n_seqs && reason == RWKV_MI_NO_TOKEN; s++) {
+        const uint32_t L = sl[s];
+        bool match = L <= step + 1u;   // (the window is this call's tokens only)
+        for (uint32_t k = 0; match && k < L; k++) match = hist[(size_t) (step + 1u - L + k) * (size_t) n + r] == tk[k];
+        if (match) reason = s;
+        tk += L;
+    }
+    if (reason == RWKV_MI_NO_TOKEN && step + 1u != sr.max_tokens) return;
+    t.lens[r] = step + 1u;
+    t.reasons[r] = reason;
+    t.live[r] = 0u;
+    const RowState u = used[r];
+    const RowState dead{u.out, const_cast<float *>(u.in)};
+    used[r] = dead;
+    other[r] = dead;
+    atomicSub(t.live_count, 1u);
 }
 
 // count[tokens[i]] += 1 for a list of tokens (rwkv_mi_*counts_add: a token may come more than once)
@@ -270,6 +328,20 @@ void launch_pen_sample(const float * logits, int n, float temperature, float top
 
 void launch_pen_sample_rows(const float * logits, int64_t rows, int n, const PenaltyRow * table, float * probs, uint32_t * tokens, uint32_t * hist, hipStream_t st) {
     hipLaunchKernelGGL(k_pen_sample_rows, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, table, probs, sample_scratch_floats(n), tokens, hist);
+}
+
+void launch_sample_rows_live(const float * logits, int64_t rows, int n, const SampleRow * table, float * probs, uint32_t * tokens, uint32_t * hist,
+                             const uint32_t * live, hipStream_t st) {
+    hipLaunchKernelGGL(k_sample_rows_live, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, table, probs, sample_scratch_floats(n), tokens, hist, live);
+}
+
+void launch_pen_sample_rows_live(const float * logits, int64_t rows, int n, const PenaltyRow * table, float * probs, uint32_t * tokens, uint32_t * hist,
+                                 const uint32_t * live, hipStream_t st) {
+    hipLaunchKernelGGL(k_pen_sample_rows_live, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, table, probs, sample_scratch_floats(n), tokens, hist, live);
+}
+
+void launch_stop_rows(const StopTables & t, int64_t rows, const uint32_t * hist, uint32_t step, RowState * used, RowState * other, hipStream_t st) {
+    hipLaunchKernelGGL(k_stop_rows, dim3((unsigned) ((rows + 63) / 64)), dim3(64), 0, st, t, (int) rows, hist, step, used, other);
 }
 
 void launch_count_add(uint32_t * count, const uint32_t * tokens, int64_t n, int n_vocab, hipStream_t st) {

@@ -28,7 +28,11 @@ PENALTY_SYMBOLS = ("rwkv_mi_batch_counts_reset", "rwkv_mi_batch_counts_add", "rw
                    "rwkv_mi_counts_reset", "rwkv_mi_counts_add", "rwkv_mi_counts_store", "rwkv_mi_logit_bias_set", "rwkv_mi_rng_seek",
                    "rwkv_mi_sample_penalized", "rwkv_mi_decode_sample_penalized")
 SCORE_SYMBOLS = ("rwkv_mi_score_resident", "rwkv_mi_batch_score_ragged")
+UNTIL_SYMBOLS = ("rwkv_mi_batch_decode_until", "rwkv_mi_batch_last_loop_passes")
 NO_TARGET = 0xFFFFFFFF   # RWKV_MI_NO_TARGET: a position that is not scored (its log-prob is 0)
+NO_TOKEN = 0xFFFFFFFF    # RWKV_MI_NO_TOKEN: no token (past a row's length), no stop sequence (the budget ended the row)
+STOP_MAX_SEQS = 16       # RWKV_MI_STOP_MAX_SEQS
+STOP_MAX_LEN = 8         # RWKV_MI_STOP_MAX_LEN
 P_FLOAT = ctypes.POINTER(ctypes.c_float)
 P_UINT32 = ctypes.POINTER(ctypes.c_uint32)
 
@@ -47,6 +51,14 @@ class PenaltyParams(ctypes.Structure):
 
 
 P_PENALTY_PARAMS = ctypes.POINTER(PenaltyParams)
+
+
+class StopParams(ctypes.Structure):
+    """struct rwkv_mi_stop_params (include/rwkv_mi355x.h): one row's token budget and the number of its stop sequences, 8 bytes."""
+    _fields_ = [("max_tokens", ctypes.c_uint32), ("n_seqs", ctypes.c_uint32)]
+
+
+P_STOP_PARAMS = ctypes.POINTER(StopParams)
 
 
 def build_library(force: bool = False) -> str:
@@ -229,6 +241,13 @@ class RWKVSharedLibrary:
             L.rwkv_mi_batch_score_ragged.argtypes = [c_batch, P_UINT32, P_UINT32, P_UINT32, P_UINT32, ctypes.c_size_t, P_FLOAT, P_UINT32]
             for name in SCORE_SYMBOLS:
                 getattr(L, name).restype = ctypes.c_bool
+        # device loops in which every row ends by itself: stop sequences and per-row budgets
+        if hasattr(L, "rwkv_mi_batch_decode_until"):   # (absent from older A/B builds loaded through RWKV_LIB_DIR)
+            L.rwkv_mi_batch_decode_until.argtypes = [c_batch, P_UINT32, P_UINT32, ctypes.c_size_t, P_SAMPLE_PARAMS, P_PENALTY_PARAMS, P_STOP_PARAMS,
+                                                     P_UINT32, P_UINT32, ctypes.c_size_t, P_UINT32, P_UINT32, P_UINT32, P_FLOAT]
+            L.rwkv_mi_batch_decode_until.restype = ctypes.c_bool
+            L.rwkv_mi_batch_last_loop_passes.argtypes = [c_batch]
+            L.rwkv_mi_batch_last_loop_passes.restype = ctypes.c_size_t
         if hasattr(L, "rwkv_test_score_rows"):   # (librwkv_testhooks_sample.so only)
             L.rwkv_test_score_rows.argtypes = [P_FLOAT, ctypes.c_int64, ctypes.c_int64, P_UINT32, P_FLOAT, P_UINT32]
             L.rwkv_test_score_rows.restype = ctypes.c_bool
@@ -640,6 +659,31 @@ def penalty_params(n: int, presence, frequency, record=True):
     return arr
 
 
+def stop_params(n: int, max_tokens, stop=None):
+    """The stop arguments of RWKVBatch.decode_until for n rows: ([n] struct rwkv_mi_stop_params, seq_lens, seq_tokens), the rows' sequences back
+    to back. max_tokens: a scalar (every row) or one value per row. stop: None, a list of token-id sequences for all rows ([[0], [187, 187]]), or
+    one such list per row ([[[0]], [], [[187, 187], [535]]]: a list whose elements' elements are sequences)."""
+    mt = _rows(n, max_tokens, "max_tokens")
+    if stop is None:
+        per_row = [[] for _ in range(n)]
+    else:
+        stop = [list(s) for s in stop]
+        if any(len(s) and isinstance(s[0], (list, tuple, np.ndarray)) for s in stop) or (len(stop) == n and all(len(s) == 0 for s in stop) and n > 0):
+            if len(stop) != n:
+                raise ValueError(f"stop must be a list of sequences or one such list per row ({n} rows)")
+            per_row = [[list(q) for q in s] for s in stop]
+        else:
+            per_row = [stop] * n
+    arr = (StopParams * n)()
+    lens, toks = [], []
+    for i in range(n):
+        arr[i] = StopParams(int(mt[i]), len(per_row[i]))
+        for q in per_row[i]:
+            lens.append(len(q))
+            toks.extend(int(t) for t in q)
+    return arr, _u32(lens).reshape(-1), _u32(toks).reshape(-1)
+
+
 def _bias_arrays(bias: dict):
     ids = _u32(list(bias.keys())).reshape(-1)
     values = np.ascontiguousarray(np.asarray(list(bias.values()), dtype=np.float64).astype(np.float32)).reshape(-1)
@@ -842,6 +886,37 @@ class RWKVBatch:
         s, t = self._slot_tokens(slots, first_tokens, "first_tokens")
         return self._loop("rwkv_mi_batch_decode_sample_penalized", s.size, n_tokens, s.ctypes.data_as(P_UINT32), t.ctypes.data_as(P_UINT32), s.size, n_tokens,
                           sample_params(s.size, temperature, top_p, -1.0, seed), penalty_params(s.size, presence, frequency, True))
+
+    def decode_until(self, slots: List[int], first_tokens: List[int], max_tokens, stop=None, temperature=None, top_p=0.8, seed=0, presence=None,
+                     frequency=None):
+        """The device loop in which every row ends by itself: at one of its stop sequences (token ids; `stop` as stop_params takes it) or after
+        max_tokens tokens (a scalar or one value per row). temperature None: the greedy loop; a temperature: decode_sample (the slots' draw
+        counters start from 0); with presence or frequency given: decode_sample_penalized (it continues, every step records). Returns (list of
+        n uint32 arrays, each of its row's own length; stopped_by [n]: the index of the row's matching sequence, or NO_TOKEN when the budget
+        ended it; elapsed milliseconds). Each slot is left exactly as the plain loop of its row's length leaves it."""
+        s, t = self._slot_tokens(slots, first_tokens, "first_tokens")
+        n = s.size
+        sp, seq_lens, seq_tokens = stop_params(n, max_tokens, stop)
+        penalised = presence is not None or frequency is not None
+        if penalised and temperature is None:
+            raise ValueError("penalties need a temperature (the greedy loop has no penalised form)")
+        params = None if temperature is None else sample_params(n, temperature, top_p, -1.0, seed)
+        pens = penalty_params(n, 0.0 if presence is None else presence, 0.0 if frequency is None else frequency, True) if penalised else None
+        stride = max([int(r.max_tokens) for r in sp], default=0)
+        out = np.empty((n, stride), dtype=np.uint32)
+        lens = np.zeros(n, dtype=np.uint32)
+        why = np.empty(n, dtype=np.uint32)
+        ms = ctypes.c_float(0.0)
+        if not self._L.rwkv_mi_batch_decode_until(self._ptr, s.ctypes.data_as(P_UINT32), t.ctypes.data_as(P_UINT32), n, params, pens, sp,
+                                                  seq_lens.ctypes.data_as(P_UINT32), seq_tokens.ctypes.data_as(P_UINT32), stride,
+                                                  ctypes.cast(out.ctypes.data, P_UINT32), lens.ctypes.data_as(P_UINT32), why.ctypes.data_as(P_UINT32),
+                                                  ctypes.byref(ms)):
+            self._fail("rwkv_mi_batch_decode_until")
+        return [out[i, : int(lens[i])].copy() for i in range(n)], why, float(ms.value)
+
+    def last_loop_passes(self) -> int:
+        """Passes the batch's last device loop enqueued (decode_until stops at most two blocks after its last row has retired)."""
+        return int(self._L.rwkv_mi_batch_last_loop_passes(self._ptr))
 
     def free(self) -> None:
         if self._ptr:

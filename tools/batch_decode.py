@@ -29,6 +29,14 @@ the smallest of --reps runs after one warm-up run of the same shape, both sides 
                        it, N x (rwkv_mi_eval_resident on a context with its logits, then rwkv_mi_batch_state_from_context)
   mode ragged_join     a 64-row decode step (sampled on the device, temperature 0) that also carries prompt chunks, against the same
                        decode step alone plus the chunks pre-filled on a context and copied in
+
+--until times rwkv_mi_batch_decode_until (sampled family: temperature 1.0, top-p 0.8, seed = row) against the unchanged plain loop in the same
+process, HIP events around each device loop, the smallest of --reps runs, --tokens steps (the budget); records also go to --out:
+  mode until_no_stop      (a) no stop met, every budget = --tokens, for RWKV_MI_LOOP_BLOCK in 4, 16, 64: ms per step against
+                          rwkv_mi_batch_decode_sample's -- the price of the live words, the stop kernel and the block hand-shake
+  mode until_half_retire  (b) every second row retires at a quarter of the budget, against (a) at the default block: what dead rows cost
+  mode until_all_retire   (c) every row retires at a quarter of the budget, against the plain loop of the full budget, with last_loop_passes
+  mode until_eval_sample  the way without either loop: one synchronising rwkv_mi_batch_eval_sample call per token, host clock
 """
 import argparse
 import json
@@ -142,6 +150,65 @@ def ragged(pkg, m, args):
         sink.close()
 
 
+def until(pkg, m, args):
+    V = m.n_vocab
+    sink = open(args.out, "a") if args.out else None
+    steps = args.tokens
+    quarter = max(1, steps // 4)
+
+    def emit(rec):
+        rec.update({"steps": steps, "reps": args.reps, "temperature": 1.0, "top_p": 0.8, "config": args.config, "dtype": args.dtype})
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if sink:
+            sink.write(line + "\n")
+            sink.flush()
+
+    ns = [int(x) for x in args.n.split(",")]
+    b = pkg.RWKVBatch(m, max(ns))
+    for n in ns:
+        slots = list(range(n))
+        first = [(7 * i + 1) % V for i in slots]
+
+        def best(run):
+            out = []
+            for k in range(args.reps + 1):   # (run 0: warm-up -- buffers of the first call, tile-major weight images)
+                for s in slots:
+                    b.state_load(s, None)
+                out.append(run())
+            return min(out[1:])
+
+        plain_ms = best(lambda: b.decode_sample(slots, first, steps, 1.0, 0.8, slots)[1])
+        by_block = {}
+        for block in (4, 16, 64):
+            os.environ["RWKV_MI_LOOP_BLOCK"] = str(block)
+            by_block[block] = best(lambda: b.decode_until(slots, first, steps, None, 1.0, 0.8, slots)[2])
+            emit({"mode": "until_no_stop", "n": n, "block": block, "ms_per_step": round(by_block[block] / steps, 4),
+                  "plain_ms_per_step": round(plain_ms / steps, 4), "until_over_plain": round(by_block[block] / plain_ms, 4), "passes": b.last_loop_passes()})
+        os.environ.pop("RWKV_MI_LOOP_BLOCK", None)
+        half = [quarter if i % 2 else steps for i in slots]
+        half_ms = best(lambda: b.decode_until(slots, first, half, None, 1.0, 0.8, slots)[2])
+        emit({"mode": "until_half_retire", "n": n, "retire_at": quarter, "retiring_rows": sum(1 for i in slots if i % 2), "ms_per_step": round(half_ms / steps, 4),
+              "no_stop_ms_per_step": round(by_block[16] / steps, 4), "half_over_no_stop": round(half_ms / by_block[16], 4), "passes": b.last_loop_passes()})
+        all_ms = best(lambda: b.decode_until(slots, first, quarter, None, 1.0, 0.8, slots)[2])
+        emit({"mode": "until_all_retire", "n": n, "retire_at": quarter, "ms": round(all_ms, 3), "plain_full_budget_ms": round(plain_ms, 3),
+              "plain_over_until": round(plain_ms / all_ms, 2), "passes": b.last_loop_passes()})
+
+        def per_token():
+            toks = list(first)
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                toks = [int(t) for t in b.eval_sample(slots, toks, 1.0, 0.8, -1.0, slots)]
+            return (time.perf_counter() - t0) * 1e3
+
+        call_ms = best(per_token)
+        emit({"mode": "until_eval_sample", "n": n, "ms_per_step": round(call_ms / steps, 4), "until_ms_per_step": round(by_block[16] / steps, 4),
+              "per_token_calls_over_until": round(call_ms / by_block[16], 3)})
+    b.free()
+    if sink:
+        sink.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("model_path")
@@ -153,8 +220,9 @@ def main():
     ap.add_argument("--sample", action="store_true", help="also time the sampling loop: on the device, and through the host")
     ap.add_argument("--penalties", action="store_true", help="with --sample: also time the penalised sampling loop, on the device and through the host")
     ap.add_argument("--ragged", action="store_true", help="time the ragged pass: prompt ingestion and joining a decode step (see above)")
-    ap.add_argument("--reps", type=int, default=3, help="--ragged: timed runs of each shape (the smallest is reported)")
-    ap.add_argument("--out", default=None, help="--ragged, --penalties: also append the records to this file")
+    ap.add_argument("--until", action="store_true", help="time rwkv_mi_batch_decode_until against the plain sampled loop (see above)")
+    ap.add_argument("--reps", type=int, default=3, help="--ragged, --until: timed runs of each shape (the smallest is reported)")
+    ap.add_argument("--out", default=None, help="--ragged, --penalties, --until: also append the records to this file")
     args = ap.parse_args()
 
     import __graft_entry__ as graft
@@ -175,6 +243,10 @@ def main():
     m = pkg.RWKVModel(lib, args.model_path, thread_count=1, gpu_layer_count=99)
     if args.ragged:
         ragged(pkg, m, args)
+        m.free()
+        return
+    if args.until:
+        until(pkg, m, args)
         m.free()
         return
     ns = [int(x) for x in args.n.split(",")]

@@ -259,32 +259,17 @@ struct RawBlk {
 
 // Weight-stream loads. A decode step reads every weight byte exactly once, from one CU: with the non-temporal policy (`nt`) the
 // lines are not kept in L2 / MALL for a re-use that never comes (MI355X_MICROARCH.md, row nt-weights: issued -> landed -18 %,
-// a decode layer -5...10 %). RWKV_NT_WEIGHTS=0 builds the default-policy variant for A/B runs.
-#ifndef RWKV_NT_WEIGHTS
-#define RWKV_NT_WEIGHTS 1
-#endif
+// a decode layer -5...10 %).
 typedef int wv4i __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ int4 ldw16(const void * p) {
-#if RWKV_NT_WEIGHTS
     const wv4i v = __builtin_nontemporal_load(reinterpret_cast<const wv4i *>(p));
     return make_int4(v.x, v.y, v.z, v.w);
-#else
-    return *reinterpret_cast<const int4 *>(p);
-#endif
 }
 __device__ __forceinline__ uint32_t ldw4(const uint32_t * p) {
-#if RWKV_NT_WEIGHTS
     return __builtin_nontemporal_load(p);
-#else
-    return *p;
-#endif
 }
 __device__ __forceinline__ uint32_t ldw2(const uint16_t * p) {
-#if RWKV_NT_WEIGHTS
     return (uint32_t) __builtin_nontemporal_load(p);
-#else
-    return (uint32_t) *p;
-#endif
 }
 
 template <int FMT, bool ONCE = true>   // ONCE = false: weights that many workgroups re-read (token-tiled sequence kernels) keep the default policy

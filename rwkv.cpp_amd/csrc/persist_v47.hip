@@ -30,11 +30,11 @@
 // Hand-overs (DESIGN.md 6.3c has the measurements behind each): a wave that waits WATCHES before it sweeps -- one tag word per group of
 // eight lanes, eight producers' units, four reads in flight on short rows (persist.h watch4) -- and sweeps when all eight have turned;
 // RWKV-4's y is swept and quantised by the eight workers (YPAR); RWKV-7's head workgroups gather lr1 first and r / k / v under their
-// second low-rank stages (P47_HEAD_SPLIT); three of five steps of RWKV-7's value rows wait in LDS from the end of the time mixing
+// second low-rank stages; three of five steps of RWKV-7's value rows wait in LDS from the end of the time mixing
 // (ESTAGE, LDS-DMA); the layer table is read through the scalar cache (KLayer); spare workgroups park a third pass of the head in LDS
-// (PARK). Compile-time switches for same-box A/B builds (tools/build_variant.sh): P47_WATCH (0 none / 1 one read / 2 four deep),
-// P47_WATCH_SPREAD (units watched: 8), P47_HEAD_SPLIT, P47_ESTAGE, P47_E_NOWAIT, P47_YPAR, P47_PARK -- on; P47_EARLY, P47_E_MID,
-// P47_E_WITH_C, P47_PRO2_FIRST -- measured, off. Run time: RWKV_MI_P47_NOFOLD, RWKV_MI_P47_CALM.
+// (PARK). The arms that lost their same-box A/B runs are gone from this file: DESIGN.md Appendix B lists each with its result and the
+// commit that still has it. The only compile-time switch left is P47_ONLY (one instantiation instead of the table: the register-budget
+// builds of tools/check_ring_regs.sh). Run time: RWKV_MI_P47_NOFOLD, RWKV_MI_P47_CALM.
 //
 // Residency and safety as mega_v6.hip: NR (+ H) <= CUs, polls are bounded by the abort word.
 #include "persist.h"
@@ -90,45 +90,11 @@ struct P47 {
     // ln_out + head + argmax inside the launch (last stage, rwkv_graph.inc:704-708): logits != nullptr; every workgroup of the grid takes rows
     float * logits; uint32_t * next_tok; const void * head; long long lnout_w, lnout_b; int V; int u_am; int n_spare;
     int calm;                                        // long waits watch ONE unit before the full-width poll -- bit 0: spare / head workgroups for the last layer
-                                                     // (the polling waves of the layers: P47_WATCH, compile time)
+                                                     // (the polling waves of the layers always watch: K47::watch)
 };
 
-#ifndef P47_WATCH_SL
-#define P47_WATCH_SL 5
-#endif
-#ifndef P47_WATCH_SPREAD
-#define P47_WATCH_SPREAD 8
-#endif
-#ifndef P47_HEAD_SPLIT
-#define P47_HEAD_SPLIT 1
-#endif
-#ifndef P47_PRO2_FIRST
-#define P47_PRO2_FIRST 0
-#endif
-#ifndef P47_E_WITH_C
-#define P47_E_WITH_C 0
-#endif
-#ifndef P47_E_MID
-#define P47_E_MID 0
-#endif
-#ifndef P47_E_NOWAIT
-#define P47_E_NOWAIT 1
-#endif
-#ifndef P47_ESTAGE
-#define P47_ESTAGE 1
-#endif
-#ifndef P47_YPAR
-#define P47_YPAR 1
-#endif
-#ifndef P47_EARLY
-#define P47_EARLY 0
-#endif
-#ifndef P47_PARK
-#define P47_PARK 1
-#endif
-#ifndef P47_WATCH
-#define P47_WATCH 2
-#endif
+constexpr int P47_WATCH_SL = 5;        // watch4: sleep (x 64 clocks) between two reads of a watched unit
+constexpr int P47_WATCH_SPREAD = 8;    // units watched per wave (see far_unit)
 
 enum { S47_A = 0, S47_Y = 1, S47_XATT = 2, S47_KQ = 3, S47_XFFN = 4, S47_AM = 5, S47_IN = 6 };
 
@@ -150,23 +116,12 @@ __device__ __forceinline__ void lf_wait(Poll & pl, const unsigned * f, unsigned 
 }
 
 // acc + f16(w) * x with the f16 operand converted inside the instruction (v_fma_mix_f32: exact conversion, one rounding -- the same value as
-// v_cvt_f32_f16 + v_fma_f32, in half the issue slots; P47_FMA_MIX=0 builds the two-instruction form for A/B runs)
-#ifndef P47_FMA_MIX
-#define P47_FMA_MIX 1
-#endif
+// v_cvt_f32_f16 + v_fma_f32, in half the issue slots)
 __device__ __forceinline__ float fma_h_lo(unsigned wpair, float x, float acc) {
-#if P47_FMA_MIX
     float d; asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(d) : "v"(wpair), "v"(x), "v"(acc)); return d;
-#else
-    return fmaf(h2f_bits((uint16_t) (wpair & 0xFFFFu)), x, acc);
-#endif
 }
 __device__ __forceinline__ float fma_h_hi(unsigned wpair, float x, float acc) {
-#if P47_FMA_MIX
     float d; asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(d) : "v"(wpair), "v"(x), "v"(acc)); return d;
-#else
-    return fmaf(h2f_bits((uint16_t) (wpair >> 16)), x, acc);
-#endif
 }
 
 // R rows row0, row0 + rstride, ... of a quantised matrix with nbk blocks per row: every load of the batch in flight (fused_blocks.h's
@@ -247,21 +202,13 @@ struct K47 {
     static constexpr int DU = (3 * nb + 63) / 64, KQU = (3 * nbF + 63) / 64;
     static constexpr int STEPS = D / 32;
     static constexpr int NIA = V7 ? 6 : 3, NIF = V7 ? 1 : 2;
-    // Short rows (D <= 768: a layer's weights are 66 registers per lane at Q5_1): every batch of weights is issued a whole phase earlier than it
-    // is needed -- behind B1 what the phases after the y hand-over read, behind B4 the value rows and the next layer's r / k / v rows -- so no
-    // read of the workers is in flight in front of a hand-over's sweep on the same CU (the sweeps behind a batch took 1.7 - 2.0 us after the
-    // last store, the one with nothing in front of it 1.06). Long rows keep the late issue: 168 registers hold one phase's batch, not two.
-    static constexpr bool EARLY = P47_EARLY && D <= 768;
     // The value rows' weights (F = 4 D long: 123 KB per workgroup at D = 2560) cannot be issued before the key rows are done -- the registers
     // hold the key rows' -- so the layer's last phase was its weight stream: 19.7 MB behind the kq hand-over, 5.4 us. ESTAGE: NST of a
     // wave's UF steps go global -> LDS (LDS-DMA, no registers) when the time mixing's rows are done, and wait there through the head's phase;
     // behind the key rows only UF - NST steps are left to stream. (Formats with a 4-byte scale pair and 16 code bytes per block.)
-    static constexpr bool ESTAGE = P47_ESTAGE && V7 && GPB == 2 && UF >= 4 && QF<FMT>::HM && QF<FMT>::QS == 16 && nbF % 64 == 0 && l47_nst(D, V7) > 0;
+    static constexpr bool ESTAGE = V7 && GPB == 2 && UF >= 4 && QF<FMT>::HM && QF<FMT>::QS == 16 && nbF % 64 == 0 && l47_nst(D, V7) > 0;
     static constexpr int NST = ESTAGE ? l47_nst(D, V7) : 0, ST_Q = 0, ST_H = NST * GPB * 1024, ST_S = ST_H + NST * GPB * 256, ST_W = NST * GPB * 1536;
-    // short rows: the value rows' weights (12 registers per lane at D = 768) go in flight with the output and key rows', a hand-over earlier --
-    // nothing of the workers is then in front of the kq sweep on the CU
-    static constexpr bool E_WITH_C = P47_E_WITH_C && !EARLY && UF <= 2;
-    static constexpr bool YPAR = P47_YPAR && !V7 && GPB == 1 && (D / 8) % 32 == 0;   // RWKV-4's y hand-over swept and quantised by the eight workers
+    static constexpr bool YPAR = !V7 && GPB == 1 && (D / 8) % 32 == 0;   // RWKV-4's y hand-over swept and quantised by the eight workers
     static_assert(D % 256 == 0 && GK % GPB == 0 && NR * 8 * GPB == D && NBLK <= 256 && NU <= 32 && KQU <= 32, "geometry");
 
     struct Lds {
@@ -287,27 +234,20 @@ struct K47 {
     // lanes (n requests per read), and turns when ALL of them have -- the sweep behind it rarely comes back incomplete (an incomplete sweep
     // costs a memory round trip). 1 -> 8: +6.4 % at 169M, +5.1 % at 2.9B.
     static __device__ __forceinline__ int far_unit() {
-        constexpr int NSP = P47_WATCH_SPREAD < 1 ? 1 : P47_WATCH_SPREAD;
+        constexpr int NSP = P47_WATCH_SPREAD;
         const int k = (int) (threadIdx.x & 63) / (64 / NSP);
         return (((int) blockIdx.x + (2 * k + 1) * NR / (2 * NSP)) % NR) * 8 + (k & 7);
     }
     static __device__ __forceinline__ int far_head() {
-        constexpr int NSP = P47_WATCH_SPREAD < 1 ? 1 : P47_WATCH_SPREAD;
+        constexpr int NSP = P47_WATCH_SPREAD;
         const int k = (int) (threadIdx.x & 63) / (64 / NSP);
         return ((int) blockIdx.x + k * H / NSP) % H;
     }
-    // in front of a hand-over's sweep on a row workgroup's polling wave (P47_WATCH: 0 none, 1 one read at a time, 2 four reads deep);
-    // watch_done(w) behind the sweep
+    // in front of a hand-over's sweep on a row workgroup's polling wave; watch_done(w) behind the sweep
     static __device__ __forceinline__ void watch(Watch4 & w, const P47 & p, Poll & pl, xrsrc xr, int unit, unsigned tag) {
-#if P47_WATCH == 2
         // (four deep where the layer is short: +1.4 % at 169M; at 2.9B, where the weight stream runs through two of the five waits, -0.6 %)
         if constexpr (D <= 768) watch4<P47_WATCH_SL>(w, pl, p.xch, p.xch_bytes, unit, tag);
         else { calm_wait<1>(pl, xr, unit, tag); w.v = 0u; }
-#elif P47_WATCH == 1
-        calm_wait<1>(pl, xr, unit, tag); w.v = 0u;
-#else
-        w.v = 0u;
-#endif
     }
     static __device__ __forceinline__ int row0_of(int u) { return GPB == 1 ? u : (u & 63) + 128 * (u >> 6); }
 
@@ -474,22 +414,6 @@ struct K47 {
     template <int NI, int NQ, bool LR>
     static __device__ __forceinline__ void pro_run(const Lds & l, const Pro<NI> & pr, const ProSrc<NI> & src, float * carry_out, bool write_state, int tid) {
         const float scale = l.sc[0];
-        if constexpr (SL == 2 && P47_PRO2_FIRST) {
-            // (the second slot's parameters go in flight BEFORE the first slot's arithmetic: loaded behind it, waves 0 and 1 finished the
-            //  time-mixing prologue 1.45 us after the others -- a memory round trip -- and B2 waited for them)
-            const int wave0 = __builtin_amdgcn_readfirstlane(tid) & ~63;
-            if (wave0 + 512 < NG4) {           // whole waves (NG4 % 64 == 0)
-                Pro<NI> p2;
-                asm volatile("" : : "v"(pr.cf[NI - 1].w) : "memory");   // (the first slot's parameters have landed HERE: with p2 in flight the compiler's wait for them would be a wait for p2 as well)
-                pro_load<NI>(p2, src, tid + 512);
-                __builtin_amdgcn_sched_barrier(0);
-                pro_group<NI, NQ, LR>(l, pr, scale, carry_out, write_state, tid, true);
-                pro_group<NI, NQ, LR>(l, p2, scale, carry_out, write_state, tid + 512, true);
-            } else {
-                pro_group<NI, NQ, LR>(l, pr, scale, carry_out, write_state, tid < NG4 ? tid : 0, tid < NG4);
-            }
-            return;
-        }
         pro_group<NI, NQ, LR>(l, pr, scale, carry_out, write_state, tid < NG4 ? tid : 0, tid < NG4);
 #pragma unroll
         for (int u = 1; u < SL; u++) {
@@ -751,15 +675,6 @@ struct K47 {
             rows_issue<FMT, GPB, UD>(wA[1], ar.w(KO(L, wk)), has ? e0 : 0, has ? 64 : 0, has ? nb : 1, lane);
             rows_issue<FMT, GPB, UD>(wA[2], ar.w(KO(L, wv)), has ? e0 : 0, has ? 64 : 0, has ? nb : 1, lane);
         };
-        // EARLY: the youngest read of the previous batch as an operand of an (empty) instruction HERE. The compiler counts reads and writes of
-        // vector memory in one counter and, with a write outstanding (a hand-over store, a state row), waits for the counter to reach zero
-        // whatever it needs: a prologue that finds a fresh batch in flight then waits for the whole batch (measured: 1.05 -> 2.7 us). With the
-        // wait taken before the new batch is issued, the phases that follow find their operands landed and wait for nothing.
-        auto landed = [&](auto & bt) {
-            constexpr int UU = (int) (sizeof(bt.raw) / sizeof(bt.raw[0])), RR = (int) (sizeof(bt.raw[0]) / sizeof(bt.raw[0][0]));
-            if constexpr (QF<FMT>::QS == 32) asm volatile("" : : "v"(bt.raw[UU - 1][RR - 1].q[1].w) : "memory");
-            else asm volatile("" : : "v"(bt.raw[UU - 1][RR - 1].q[0].w) : "memory");
-        };
         // the channel-mixing prologue's parameters, the output rows and the key (+ receptance) rows
         auto issue_C = [&](int li) {
             __builtin_amdgcn_sched_barrier(0);
@@ -839,7 +754,6 @@ struct K47 {
 #pragma unroll
                 for (int r = 0; r < GPB; r++) xown[r] = l.hx[e0 + 64 * r];
             }
-            if constexpr (EARLY) { landed(wA[2]); issue_C(li); }
             pro_run<NIA, 3, V7>(l, pa, sa, sout_l + D, blk == 0, opq(tid0));
             T47(2);
             __syncthreads();   // B2
@@ -882,7 +796,7 @@ struct K47 {
                 }
             }
             T47(3);
-            if constexpr (!EARLY) { issue_C(li); stage_E(li); if constexpr (E_WITH_C) issue_E(li); }   // (they stream through the y hand-over)
+            issue_C(li); stage_E(li);   // (they stream through the y hand-over)
             if constexpr (YPAR) {
                 // this wave's eighth of y: elements EPW own .. EPW own + EPW - 1 (units of the same index), a 32-block per half-wave and pass
                 constexpr int EPW = D / 8, NPASS = (EPW + 63) / 64;
@@ -927,7 +841,6 @@ struct K47 {
             T47(5);
             __syncthreads();   // B4
             T47(6);
-            if constexpr (EARLY) { if constexpr (V7) landed(wK[GPB - 1]); else landed(wFr); issue_E(li); issue_A(last ? li : li + 1, !last); }
             pro_run<NIF, NIF, false>(l, pf, sf, sout_l, blk == 0, opq(tid0));
             __syncthreads();   // B5
             T47(7);
@@ -941,19 +854,18 @@ struct K47 {
                     const float v = pick_lane<4>(res, lane);
                     const float t = v > 0.0f ? v : 0.0f;
                     if (lane < 4) l.out[32 * g + 4 * own + lane] = t * t;
-                    if constexpr (ESTAGE && P47_E_MID && GPB == 2) { if (g == 0) issue_E(li); }   // (the first key group's registers are free: the value rows' last steps go in flight under the second)
                 }
                 lf_add(l.fl, 1u);
                 if constexpr (!V7) rows_sum<FMT, GPB, UD>(wFr, nb, lane, qvec_at(l.q[1], D), rgate);
             }
             T47(8);
-            if constexpr (UF >= 4 && !(ESTAGE && P47_E_NOWAIT)) {
+            if constexpr (UF >= 4 && !ESTAGE) {
                 // (long rows: 77 KB per workgroup at 2.9B. Issued before the comm wave has stored this workgroup's key groups they sit in the
                 //  CU's memory pipe in front of that store -- and 159 other workgroups wait for it: measured 1.6 us on the slowest)
                 kq_seen += 1u;
                 lf_wait(plw, l.fl + 1, kq_seen);
             }
-            if constexpr (!EARLY && !E_WITH_C && !(ESTAGE && P47_E_MID && GPB == 2)) issue_E(li);
+            issue_E(li);
             __syncthreads();   // B6: kq
             T47(9);
             unstage_E();
@@ -970,7 +882,7 @@ struct K47 {
                 else x_store(p.u_xffn, tagL + S47_XFFN);        // (the last layer's x goes to every workgroup's ln_out when the head follows in this launch)
             }
             T47(10);
-            if constexpr (!EARLY) issue_A(last ? li : li + 1, !last);
+            issue_A(last ? li : li + 1, !last);
         }
     }
 
@@ -1120,7 +1032,6 @@ struct K47 {
             T47(0);
             stage_state(li);
             float rv, kv0, vv;
-#if P47_HEAD_SPLIT
             // The lr1 vector first (fp16-rounded into LDS: what ggml feeds an F16 matrix): the polling waves of the row workgroups publish it a
             // row phase before r / k / v (their jobs run beside the workers' R / K / V rows), and the second low-rank stages need nothing else
             // -- they run on the eight workers while this wave waits for r, k, v of its channels (one unit per lane). Gathered together the
@@ -1148,25 +1059,6 @@ struct K47 {
                 watch_done(wt);
                 rv = __uint_as_float(dv[0].x); kv0 = __uint_as_float(dv[0].y); vv = __uint_as_float(dv[0].z);
             }
-#else
-            // r, k, v of this lane's channel (one unit) and the lr1 vector (fp16-rounded into LDS: what ggml feeds an F16 matrix)
-            {
-                const int lane = opq(lane0), c = hb * S + lane;
-                int ptr[NL1 + 1]; bool valid[NL1 + 1]; v4u dv[NL1 + 1];
-                ptr[0] = p.u_a + c; valid[0] = true;
-#pragma unroll
-                for (int k = 0; k < NL1; k++) { ptr[k + 1] = p.u_lr1 + lane + 64 * k; valid[k + 1] = lane + 64 * k < KI(L, lr_n); }
-                Watch4 wt;
-                watch(wt, p, pl, xr, p.u_a + hb * S + 32, tagL + S47_A);   // (~30 us per layer: r / k / v of one of the head's channels first, then the sweep)
-                poll_ptrs<NL1 + 1>(pl, xr, ptr, valid, tagL + S47_A, dv);
-                watch_done(wt);
-                rv = __uint_as_float(dv[0].x); kv0 = __uint_as_float(dv[0].y); vv = __uint_as_float(dv[0].z);
-#pragma unroll
-                for (int k = 0; k < NL1; k++) l.lr1[lane + 64 * k] = round_f16(__uint_as_float(dv[k + 1].x));
-            }
-            T47(1);
-            __syncthreads();   // H1
-#endif
             __syncthreads();   // H2: the second stages' results are in l.ch
             T47(2);
             const int lane = opq(lane0), c = hb * S + lane;
@@ -1320,7 +1212,7 @@ struct K47 {
     // the 169M model is 77 MB, the registers of 256 workgroups hold 55 MB of it and the row workgroups can only fill theirs when their last
     // layer is done (measured: their 2 x 12 KB per wave took 8.8 us to ISSUE, 96 CUs pulling 18.8 MB at the pace of their outstanding
     // requests). With 3 passes per spare wave settled before the token is known, a row wave is left with one pass and the tail with ~3 MB.
-    static constexpr bool PARK = P47_PARK && CPP == 1 && NHB == 2 && D <= 768;
+    static constexpr bool PARK = CPP == 1 && NHB == 2 && D <= 768;
     static constexpr int LPW = PARK ? 1 : 0;
     static_assert(CH == (STEPS <= 24 ? 24 : 16) && (!PARK || l47_park_bytes(D) == (size_t) 9 * LPW * CH * 512), "park area");
     static constexpr int HXB = NHB > 2 ? 4 : 8;   // activation reads per pinned batch
@@ -1565,31 +1457,21 @@ __global__ __launch_bounds__(576) void k47_persist(P47 p) {
     typename K::HJ hj;
     const bool fold_head = p.logits != nullptr;
     if ((int) blockIdx.x < K::NR) {
-#ifndef P47_X_NO_ROW_COMM
         if (wave == 8) K::row_comm(p, l, tid & 63, base);
-#endif
-#ifndef P47_X_NO_ROW_WORKER
         if (wave != 8) { K::row_worker(p, l, tid, wave, base); if (fold_head) { K::hj_init(hj, p, wave); K::hj_prefetch(hj, p, tid & 63); } }
-#endif
     } else if ((int) blockIdx.x < K::NBLK) {
         if constexpr (ARCH == 7) {
-#ifndef P47_X_NO_HEAD_COMM
             if (wave == 8) K::head_comm(p, l, tid & 63, base);
-#endif
-#ifndef P47_X_NO_HEAD_WORKER
             if (wave != 8) { K::head_worker(p, l, tid, wave); if (fold_head) { K::hj_init(hj, p, wave); K::hj_prefetch(hj, p, tid & 63); } }
-#endif
         }
     } else {
         // spare workgroup: only rows of the head; its waves that do not poll start their stream now
         if (fold_head && (K::PARK || wave != 8)) { K::hj_init(hj, p, wave); K::hj_park(hj, p, l, wave, tid & 63); K::hj_prefetch(hj, p, tid & 63); }
     }
-#ifndef P47_X_NO_TAIL
     if (fold_head) {
         // (the polling waves issue theirs behind the poll inside tail(): results return in order per wave)
         K::tail(p, l, hj, tid, wave, base);
     }
-#endif
     if (blockIdx.x == 0 && tid == 0) p.ctl[0] = base + (unsigned) (p.l1 - p.l0) * 8u;
 }
 
@@ -1597,9 +1479,7 @@ __global__ __launch_bounds__(576) void k47_persist(P47 p) {
 // host side
 // ---------------------------------------------------------------------------------------------------------------
 
-#ifndef P47_CALM_DEFAULT
-#define P47_CALM_DEFAULT 1
-#endif
+constexpr int P47_CALM_DEFAULT = 1;    // P47::calm without RWKV_MI_P47_CALM
 
 struct P47Handle : PersistentDecoder {
     P47Layer * d_layers = nullptr;

@@ -209,6 +209,7 @@ __global__ __launch_bounds__(MF<FMT>::NT, 2) void k_mmq_mfma(MmqArgs A) {
     typedef MF<FMT> M;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
 #ifdef PF_EXP_STAMP
+    // (the only compile-time switch of this file; tools/mmq_stamps.py builds with it. The other timing-only builds: DESIGN.md Appendix B)
     // timing-only build: workgroup 0's thread 0 overwrites y[0][0 .. 5] with its own timeline in microseconds (100 MHz wall clock):
     // prologue issued, first chunk landed, walk done, epilogue done; y[0][5] = the wall clock at entry (low bits), for launch gaps
     const unsigned long long st_t0 = wall_clock64();
@@ -339,33 +340,18 @@ __global__ __launch_bounds__(MF<FMT>::NT, 2) void k_mmq_mfma(MmqArgs A) {
             // every wave has finished reading the buffer the next chunk goes into (its last reads are two stages back)
             const int k = sg_l / M::CH;
             // chunk k has landed when only the DMAs of the younger chunks k + 1 .. k + NBUF - 2 are outstanding (vmcnt counts this wave's)
-#ifdef PF_EXP_NOSYNC
-            if (false) { } else if (true) { } else
-#endif
             if (M::NBUF > 2 && k + M::NBUF - 2 < n_chunks) {
                 if (NSUB == 1 || sub_w == 0) wait_vm<M::n_dma(0) * (M::NBUF - 2)>(); else wait_vm<M::n_dma(NSUB - 1) * (M::NBUF - 2)>();
             } else {
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             }
-#ifndef PF_EXP_NOSYNC
             __syncthreads();
-#endif
-#ifdef PF_EXP_NODMA
-            if (k + M::NBUF - 1 < n_chunks && k < 1) issue(k + M::NBUF - 1);
-#else
             if (k + M::NBUF - 1 < n_chunks) issue(k + M::NBUF - 1);
-#endif
             to_bnd = k + 1 < n_chunks ? M::CH : 0x40000000;      // (no boundary behind the last chunk)
         }
         to_bnd--;
-#ifdef PF_EXP_NOOPS
-        if (sg_l <= 2)
-#endif
         n_braw = *reinterpret_cast<const int4 *>(lds + (off_l + a_braw));
         n_scw = *reinterpret_cast<const unsigned *>(lds + (off_l + a_scw));
-#ifdef PF_EXP_NOOPS
-        if (sg_l <= 2)
-#endif
         n_aop = *reinterpret_cast<const v4i *>(lds + (off_l + a_aop));
         if constexpr (M::QH) n_qhw = *reinterpret_cast<const unsigned *>(lds + (off_l + a_scw + (M::OFF_WQH - M::OFF_WSC)));
         off_s = off_l;
@@ -410,9 +396,6 @@ __global__ __launch_bounds__(MF<FMT>::NT, 2) void k_mmq_mfma(MmqArgs A) {
     // Tokens of register r: (r & 3) + 8 (r >> 2) + 4 h.
     auto read_scales = [&]() {                   // of the step whose codes load_ops read last
         const unsigned char * S = lds + (off_s + a_xd);
-#ifdef PF_EXP_NODX
-        if (sg_l > 2) return;
-#endif
 #pragma unroll
         for (int g = 0; g < 4; g++) {
             const float4 dx4 = *reinterpret_cast<const float4 *>(S + 32 * g);
@@ -424,7 +407,6 @@ __global__ __launch_bounds__(MF<FMT>::NT, 2) void k_mmq_mfma(MmqArgs A) {
             }
         }
     };
-    [[maybe_unused]] int sigma = 0;          // (read by the timing-only builds)
     // One step: fold block sigma into cur (FIRST: the leaf's first block, cur = fma(.., .., +0)), start block sigma + 1, read block
     // sigma + 2. Every LDS read is issued a stage before its use: the eight waves of the workgroup run in lock-step between the chunk
     // barriers, so a read that is waited for right away queues behind everybody else's (measured: 46 % of the wave cycles in waits).
@@ -444,9 +426,6 @@ __global__ __launch_bounds__(MF<FMT>::NT, 2) void k_mmq_mfma(MmqArgs A) {
         PIN8(sf);
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (M::OVERLAP) launch();
-#ifdef PF_EXP_NOFOLD
-        if (sigma == 0)
-#endif
 #pragma unroll
         for (int j = 0; j < 8; j++) {
             const v2f zero = {0.0f, 0.0f};
@@ -462,7 +441,6 @@ __global__ __launch_bounds__(MF<FMT>::NT, 2) void k_mmq_mfma(MmqArgs A) {
         load_ops();
         __builtin_amdgcn_sched_barrier(0);
 #undef PIN8
-        sigma++;
     };
 #ifdef PF_EXP_STAMP
     st_t1 = wall_clock64();
@@ -497,11 +475,7 @@ __global__ __launch_bounds__(MF<FMT>::NT, 2) void k_mmq_mfma(MmqArgs A) {
                 for (int j = 0; j < 8; j++) cur[j] = (v2f){0.0f, 0.0f};
             }
             // merges after leaf c = 8 a + u: one per trailing one bit of c
-#ifdef PF_EXP_NOMERGE
-            if (u == 7) { for (int j = 0; j < 8; j++) V[j] = s0[j] + cur[j]; } else if (false) {
-#else
             if (u == 1 || u == 5) {
-#endif
 #pragma unroll
                 for (int j = 0; j < 8; j++) s1[j] = s0[j] + cur[j];
             } else if (u == 3) {
@@ -1023,20 +997,8 @@ constexpr int W7_LDS = (2 * W7_CH * (5 * 64 + 16) + 4 * 16 * 64 * 4) * 4;     //
 // The instructions are written out by hand: the compiler's hazard recogniser puts two wait states in front of every DPP instruction
 // whose ANY source was written by the previous VALU instruction; the hardware needs them for the DPP-permuted source only
 // (the products, written long before), not for the accumulator, which is read like any other source 1.
-template <int Q> __device__ __forceinline__ float w7_bc(float p) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(p), 0x150 + Q /* row_newbcast:Q */, 0xF, 0xF, true));
-}
-template <int Q> __device__ __forceinline__ void w7_chain(float & x, float p0, float p1, float p2, float p3) {
-    if constexpr (Q < 16) {
-        x = w7_bc<Q>(p0) + x; x = w7_bc<Q>(p1) + x; x = w7_bc<Q>(p2) + x; x = w7_bc<Q>(p3) + x;
-        w7_chain<Q + 1>(x, p0, p1, p2, p3);
-    }
-}
 __device__ __forceinline__ float w7_row_sum(float p0, float p1, float p2, float p3) {
     float x = 0.0f;
-#ifdef W7_CHAIN_BUILTIN
-    w7_chain<0>(x, p0, p1, p2, p3);
-#else
 #define W7_A(Q) "v_add_f32_dpp %0, %1, %0 row_newbcast:" #Q " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
                 "v_add_f32_dpp %0, %2, %0 row_newbcast:" #Q " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
                 "v_add_f32_dpp %0, %3, %0 row_newbcast:" #Q " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
@@ -1046,7 +1008,6 @@ __device__ __forceinline__ float w7_row_sum(float p0, float p1, float p2, float 
                  W7_A(8) W7_A(9) W7_A(10) W7_A(11) W7_A(12) W7_A(13) W7_A(14) W7_A(15)
                  : "+v"(x) : "v"(p0), "v"(p1), "v"(p2), "v"(p3));
 #undef W7_A
-#endif
     return x;
 }
 

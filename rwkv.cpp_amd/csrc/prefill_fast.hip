@@ -29,11 +29,8 @@ template <int FMT> struct MG {
     typedef MF<FMT> M;                       // the per-step slot layout (128 rows, two token tiles) is the exact kernel's
 // (measured, 1.6B Q4_0, 1024-token pass, same box: two buffers of 8 blocks = 78 KB, two workgroups per CU: 86.1 k tokens/s; three buffers,
 //  one workgroup per CU: 76.0 k -- the second workgroup hides more than the deeper prefetch; the exact kernel: 73.2 k)
-#ifndef PFF_NBUF
-#define PFF_NBUF 2
-#endif
     static constexpr int NT = 256, CH = 8;
-    static constexpr int NBUF = PFF_NBUF * CH * M::SLOT <= 160 * 1024 ? PFF_NBUF : 2;   // chunk buffers: chunk k + NBUF - 1 is issued when chunk k starts (Q8_0: two fit)
+    static constexpr int NBUF = 2;   // chunk buffers: chunk k + NBUF - 1 is issued when chunk k starts (Q8_0: two fit)
     static constexpr int DMA_PER_CHUNK = 2 * M::n_dma(0);                   // DMA instructions of one wave per chunk (its two steps): the vmcnt share
     static constexpr int LDS_BYTES = NBUF * CH * M::SLOT;
     static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");   // (Q4_0 / Q4_1: 78 - 82 KB, two workgroups per CU; Q5 / Q8_0: one)

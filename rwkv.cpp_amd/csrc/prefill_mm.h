@@ -39,21 +39,15 @@ template <int FMT> struct MF {
     static constexpr int  P_TAIL = P_WSC + P_WQH + P_XD + P_XS + P_XO, NTR = (P_TAIL + 63) / 64, NR = NW + 2 + NTR;   // rows per step
     // steps per chunk; stack levels kept in LDS (64 B per thread each) so that two chunks of 8 steps + the levels fit in 160 KiB
     static constexpr bool OVERLAP = !(QH && HM);                // the MFMA of step sigma + 1 runs under the fold of step sigma (Q5_1: no registers for it)
-#ifndef PF_CH
-#define PF_CH 8
-#endif
-#ifndef PF_NBUF
-#define PF_NBUF 2
-#endif
     // NBUF chunk buffers of CH steps: chunk k + NBUF - 1 is issued when chunk k starts, (NBUF - 1) CH steps before its first read; the
     // boundary waits with a counted vmcnt for chunk k only. Measured in round 4 (1.6B Q4_0, average launch of the 1024-token pass,
     // profiles/r04q_mmq_variants.txt): CH 8 x 2 buffers 40.7 us; CH 4 x 2 / 3 / 4 buffers 42.9 / 43.6 / 43.2 us -- the depth of the
-    // prefetch does not matter, the extra barriers cost 6 %. The timing-only builds behind -DPF_EXP_* (results invalid: parts of the
-    // step are skipped) say where the time is NOT: without the fold 38.6 us, without the LDS operand reads 41.4, without the scale
+    // prefetch does not matter, the extra barriers cost 6 %. Timing-only builds that skipped parts of the step (results
+    // invalid) say where the time is NOT: without the fold 38.6 us, without the LDS operand reads 41.4, without the scale
     // reads 41.3, without the merges 39.7, without the DMAs after the first chunks 39.2, without the boundary wait + barrier 38.3,
     // without all of these together 31.8 us. What is left in that last build -- the nibble unpack, the MFMA, the magic subtraction,
     // the walk's control flow and the launch's fixed part -- is 78 % of the kernel: no single resource the profiler names is the bound.
-    static constexpr int CH = PF_CH, NBUF = PF_NBUF, STK_LDS = Q8 ? 1 : 2;
+    static constexpr int CH = 8, NBUF = 2, STK_LDS = Q8 ? 1 : 2;
     static constexpr int LDS_BYTES = NBUF * CH * SLOT + STK_LDS * 64 * NT;
     // DMA instructions one wave issues per chunk (its vmcnt share): rows r = sub, sub + NSUB, ... of its step; a tail row is one DMA per
     // small array that has pieces in it (see `seg` in the kernel)

@@ -206,24 +206,9 @@ __device__ __forceinline__ void rec_wait(RawRec<FMT, R, U> & w) {
         }
 }
 
-// Round 6: 4-bit codes against NIBBLE PLANES of the activations (R6_DOT8; Q4_0 / Q4_1). The row phases are bound by VALU issue,
-// and 12 of a Q4 block's ~26 VALU instructions only unpack its nibbles into bytes for v_dot4. v_dot8_u32_u4 multiplies the packed nibbles as they
-// lie: with b = a + 128 (one xor per activation dword, 1 <= b <= 255) = 16 bh + bl,
-//     sum w a = 16 sum w bh + sum w bl - 128 sum w,
-// three dot8 per code dword (the last against 0x11111111) and no unpacking: 12 + 3 instead of 12 + 8 + 1 instructions per block. The nibble
-// planes are built once per phase and lane, in the order the weight nibbles lie in a code dword (byte t of dword j: low nibble = element 4 j + t,
-// high nibble = element 16 + 4 j + t). Integers are exact in any order: the block sum -- and everything behind it -- is bit for bit the same.
-// Built, bit-identical (parity tests + bench parity green), measured, OFF: 662.0 against 672.5 tokens/s on the 7B (three alternations on one box),
-// 1420.8 against 1432.3 on the 1.6B -- a third fewer VALU instructions per block and 1.5 % SLOWER: v_dot8_u32_u4 does not issue at v_dot4's rate on
-// this part, or the phases are less issue-bound than the per-SIMD record counts suggest; profiles/r06_dot8_ab.txt.
-#ifndef R6_DOT8
-#define R6_DOT8 0
-#endif
-template <int FMT> constexpr bool r6_nib() { return R6_DOT8 != 0 && (FMT == T_Q4_0 || FMT == T_Q4_1); }
 // The activation blocks a lane needs are the same for every record of a phase (block 64 u + lane of the image): read once per phase.
-// (nibble planes: alo[u] = the low nibbles of b, ahi[u] = the high nibbles, one dword per code dword)
 template <int U> struct ActRegs { int4 alo[U], ahi[U]; float dx[U], sx[U]; int asum[U]; };
-template <int FMT, int U>
+template <int U>
 __device__ __forceinline__ void act_load(ActRegs<U> & ar, const QVec & a, int nbk, int lane) {
 #pragma unroll
     for (int u = 0; u < U; u++) {
@@ -231,18 +216,7 @@ __device__ __forceinline__ void act_load(ActRegs<U> & ar, const QVec & a, int nb
         const int b = bb < nbk ? bb : nbk - 1;
         const int4 lo = *reinterpret_cast<const int4 *>(a.q + b * 16);
         const int4 hi = *reinterpret_cast<const int4 *>(a.q + nbk * 16 + b * 16);
-        if constexpr (r6_nib<FMT>()) {
-            const unsigned l4[4] = {(unsigned) lo.x ^ 0x80808080u, (unsigned) lo.y ^ 0x80808080u, (unsigned) lo.z ^ 0x80808080u, (unsigned) lo.w ^ 0x80808080u};
-            const unsigned h4[4] = {(unsigned) hi.x ^ 0x80808080u, (unsigned) hi.y ^ 0x80808080u, (unsigned) hi.z ^ 0x80808080u, (unsigned) hi.w ^ 0x80808080u};
-            unsigned bl[4], bh[4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                bl[j] = (l4[j] & 0x0F0F0F0Fu) | ((h4[j] << 4) & 0xF0F0F0F0u);
-                bh[j] = ((l4[j] >> 4) & 0x0F0F0F0Fu) | (h4[j] & 0xF0F0F0F0u);
-            }
-            ar.alo[u] = make_int4((int) bl[0], (int) bl[1], (int) bl[2], (int) bl[3]);
-            ar.ahi[u] = make_int4((int) bh[0], (int) bh[1], (int) bh[2], (int) bh[3]);
-        } else { ar.alo[u] = lo; ar.ahi[u] = hi; }
+        ar.alo[u] = lo; ar.ahi[u] = hi;
         ar.dx[u] = a.d[b]; ar.sx[u] = a.s[b]; ar.asum[u] = a.isum[b];
     }
 }
@@ -257,53 +231,6 @@ __device__ __forceinline__ void rec_acc(const RawRec<FMT, R, U> & w, const ActRe
     constexpr int GU = (GB / R) < U ? ((GB / R) > 0 ? (GB / R) : 1) : U;
 #pragma unroll
     for (int r = 0; r < R; r++) acc[r] = 0.0f;
-    if constexpr (r6_nib<FMT>()) {
-        // nibble planes (see act_load): three v_dot8_u32_u4 chains per block, breadth first over the GU x R blocks of a group
-#pragma unroll
-        for (int u0 = 0; u0 < U; u0 += GU) {
-            unsigned sl[GU][R], sh[GU][R], sw[GU][R];
-#pragma unroll
-            for (int g = 0; g < GU; g++)
-#pragma unroll
-                for (int r = 0; r < R; r++) { sl[g][r] = 0u; sh[g][r] = 0u; sw[g][r] = 0u; }
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-#pragma unroll
-                for (int g = 0; g < GU; g++) {
-                    if (u0 + g < U) {
-                        const int u = u0 + g;
-                        const unsigned bl = (unsigned) (k == 0 ? ar.alo[u].x : (k == 1 ? ar.alo[u].y : (k == 2 ? ar.alo[u].z : ar.alo[u].w)));
-                        const unsigned bh = (unsigned) (k == 0 ? ar.ahi[u].x : (k == 1 ? ar.ahi[u].y : (k == 2 ? ar.ahi[u].z : ar.ahi[u].w)));
-#pragma unroll
-                        for (int r = 0; r < R; r++) {
-                            const wv4i & q = w.raw[u][r].q[0];
-                            const unsigned c = (unsigned) (k == 0 ? q.x : (k == 1 ? q.y : (k == 2 ? q.z : q.w)));
-                            sl[g][r] = __builtin_amdgcn_udot8(c, bl, sl[g][r], false);
-                            sh[g][r] = __builtin_amdgcn_udot8(c, bh, sh[g][r], false);
-                            sw[g][r] = __builtin_amdgcn_udot8(c, 0x11111111u, sw[g][r], false);
-                        }
-                    }
-                }
-            }
-#pragma unroll
-            for (int g = 0; g < GU; g++) {
-                if (u0 + g < U) {
-                    const int u = u0 + g;
-                    const bool valid = u + 1 < U || u * WAVE + lane < nbk;   // (only the last step of a row can be short)
-#pragma unroll
-                    for (int r = 0; r < R; r++) {
-                        int sv = (int) ((sh[g][r] << 4) + sl[g][r]) - (int) (sw[g][r] << 7);      // sum w a = 16 sum w bh + sum w bl - 128 sum w
-                        if constexpr (QF<FMT>::OFF != 0) sv -= QF<FMT>::OFF * ar.asum[u];
-                        const float wd = h2f_bits((uint16_t) (w.raw[u][r].sc & 0xFFFFu));
-                        const float dd = wd * ar.dx[u];
-                        acc[r] = fmaf(dd, valid ? (float) sv : 0.0f, acc[r]);
-                        if constexpr (QF<FMT>::HM) acc[r] = fmaf(h2f_bits((uint16_t) (w.raw[u][r].sc >> 16)), valid ? ar.sx[u] : 0.0f, acc[r]);
-                    }
-                }
-            }
-        }
-        return;
-    }
 #pragma unroll
     for (int u0 = 0; u0 < U; u0 += GU) {
         WBlk<FMT> wb[GU][R];
@@ -366,13 +293,17 @@ __device__ __forceinline__ void wave_sum_n(float (&v)[N]) {
 // the kernel. EPT = D / 512, NBD = decay rank / 32, UF = 64-block steps of an F-long row, KSL = gather slots per lane for the
 // quantised F-vector. Exactly RG_NBLK workgroups of 512 threads.
 // ---------------------------------------------------------------------------------------------------------------
-#ifndef R6_ROWS_WAIT   /* 1 (debugging aid): every take inside a row phase waits for its LDS reads at once */
+// The compile-time switches of this file -- these three and no others (the arms that lost their A/B runs: DESIGN.md Appendix B):
+//   R6_ROWS_WAIT = 1   hazard-debugging aid: the conditional takes of a row phase (a wave's tail record) wait for their LDS reads at once
+//   R6_RT_STAMPS = 1   every phase stamp from the 100 MHz real-time counter (one clock for all workgroups: tools/trace_ring_cp.py)
+//                      instead of the shader clock
+//   R6_ONLY_FMT = fmt  one variant (that format, the 7B geometry) instead of the table: the register-budget builds of
+//                      tools/check_ring_regs.sh
+// None of them alters a result.
+#ifndef R6_ROWS_WAIT
 #define R6_ROWS_WAIT 0
 #endif
-#ifndef R6_REPOLL_MISSING
-#define R6_REPOLL_MISSING 0
-#endif
-#ifndef R6_RT_STAMPS   /* 1: every phase stamp from the 100 MHz real-time counter (one clock for all workgroups: tools/trace_ring_cp.py) instead of the shader clock */
+#ifndef R6_RT_STAMPS
 #define R6_RT_STAMPS 0
 #endif
 #if R6_RT_STAMPS
@@ -403,19 +334,9 @@ struct R6 {
     static __device__ __forceinline__ RingShape shape(const R6P & p) {
         RingShape s; s.D = D; s.F = p.F; s.R5 = 5 * p.R; s.DR = p.DR;
         s.qs = QF<FMT>::QS; s.scb = QF<FMT>::HM ? 4 : 2; s.qhb = QF<FMT>::QH ? 4 : 0;
-        s.bal = BAL ? 1 : 0;
+        // (s.bal stays 0: this kernel consumes the six-apart deal only. ring_geom.h still describes the balanced one: DESIGN.md Appendix B)
         return s;
     }
-    // two-row sets of C and FK dealt by SIMD share (ring_geom.h, RG_BAL_*): the D = 4096 geometry. Built, bit-identical, measured, OFF:
-    // 649.4 tokens/s against 662.4 for the even deal on one box (profiles/r06_balance_ab.txt). The deal moved nothing where it was aimed --
-    // c4 / c5 finish the r/k/v/g rows at 8100 cycles with four records as with five -- because a SIMD issues one VALU instruction per four
-    // cycles whether one wave or two feed it: the row phases are bound by the CU's 4 x 1 issue slots (32 sets in ~8000 cycles), a wave that
-    // shares its SIMD with an older one simply gets the slots the older one leaves, and the seven-record waves became the new last ones.
-#ifndef R6_BALANCE
-#define R6_BALANCE 0
-#endif
-    static constexpr bool BAL = R6_BALANCE != 0 && EPT == 8;
-    template <int PH> static constexpr bool balph() { return BAL && (PH == RG_C || PH == RG_FK); }
 
     // -----------------------------------------------------------------------------------------------------------
     // cooperative gathers: the NG gathering waves each poll a share of the units and stage it into LDS, then meet on a counter
@@ -454,10 +375,8 @@ struct R6 {
             for (int k = 0; k < XSL; k++) if (i0 + k * NG * 64 < N && !keep) stage(k, v[k]);
             return;
         }
-        // A sweep that comes back incomplete re-reads only what was missing (R6_REPOLL_MISSING): a unit is staged by the sweep that finds it,
-        // and a lane that has its unit of a slot reads the buffer's first unit instead (one address for all of them: one request) -- the
-        // retries of a hand-over's last microsecond cost a few requests, not the vector again. (Unconditional loads with a selected
-        // address: loads under `if (missing)` are conditional redefinitions, around which the allocator copies and spills.)
+        // A unit is staged by the sweep that finds it; a sweep that comes back incomplete is repeated whole. (Unconditional loads: loads
+        // under `if (missing)` are conditional redefinitions, around which the allocator copies and spills.)
         bool have[XSL];
 #pragma unroll
         for (int k = 0; k < XSL; k++) have[k] = i0 + k * NG * 64 >= N;
@@ -465,7 +384,7 @@ struct R6 {
             asm volatile("" ::: "memory");
             v4u v[XSL];
 #pragma unroll
-            for (int k = 0; k < XSL; k++) v[k] = tg_load(xr, (R6_REPOLL_MISSING && have[k]) ? buf : buf + i0 + k * NG * 64);
+            for (int k = 0; k < XSL; k++) v[k] = tg_load(xr, buf + i0 + k * NG * 64);
             bool ok = true;
 #pragma unroll
             for (int k = 0; k < XSL; k++) {
@@ -502,11 +421,11 @@ struct R6 {
         bool have[SL];
 #pragma unroll
         for (int k = 0; k < SL; k++) have[k] = i0 + k * NG * 64 >= n;
-        for (unsigned spin = 0;; spin++) {   // (a retry re-reads only what was missing: see gather_x)
+        for (unsigned spin = 0;; spin++) {   // (a unit is staged once: see gather_x)
             asm volatile("" ::: "memory");
             v4u v[SL];
 #pragma unroll
-            for (int k = 0; k < SL; k++) v[k] = tg_load(xr, (R6_REPOLL_MISSING && have[k]) ? src : src + i0 + k * NG * 64);
+            for (int k = 0; k < SL; k++) v[k] = tg_load(xr, src + i0 + k * NG * 64);
             bool ok = true;
 #pragma unroll
             for (int k = 0; k < SL; k++) {
@@ -525,32 +444,17 @@ struct R6 {
     // another wave of the workgroup has seen its own turn (LDS word); only then the wide sweeps start.
     // idle(): called once per watch round (the consumers use the wait to take their first record of the coming phase out of the ring
     // as soon as it has landed: rows_pre)
-    // The look at a sentinel: the tag word of one unit, the same address on every lane. R6_SWATCH = 1 reads it through the SCALAR memory path
-    // (s_load_dword glc: past the scalar cache, served by the L2 like an sc1 vector load) -- it does not queue in the CU's vector memory pipe
-    // behind the LDS-DMA fills and the sweeps (tools/watch_bench.hip: a chain of idle hand-overs 1.16 us each against 1.62 us).
-#ifndef R6_SWATCH
-#define R6_SWATCH 0
-#endif
-    static __device__ __forceinline__ bool look_turned(const Poll & pl, xrsrc xr, int unit, unsigned tag) {
-#if R6_SWATCH
-        if (!pl.sw) { const v4u v = tg_load(xr, unit); return __builtin_amdgcn_readfirstlane((int) tg_ok(v, tag)) != 0; }   // (R6_SWATCH = 2: the comm wave only)
-        const unsigned off = (unsigned) __builtin_amdgcn_readfirstlane(unit) * 16u + 12u;
-        const unsigned long long a = (unsigned long long) pl.xch;
-        const unsigned long long base = (unsigned long long) (unsigned) __builtin_amdgcn_readfirstlane((int) (unsigned) a) | ((unsigned long long) (unsigned) __builtin_amdgcn_readfirstlane((int) (unsigned) (a >> 32)) << 32);
-        unsigned t;
-        asm volatile("s_load_dword %0, %1, %2 glc\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) : "s"(base), "s"(off) : "memory");
-        return (t & 0xFFFFu) == (tag & 0xFFFFu);
-#else
+    // The look at a sentinel: the tag word of one unit, the same address on every lane.
+    static __device__ __forceinline__ bool look_turned(xrsrc xr, int unit, unsigned tag) {
         const v4u v = tg_load(xr, unit);
         return __builtin_amdgcn_readfirstlane((int) tg_ok(v, tag)) != 0;
-#endif
     }
     template <typename Idle>
     static __device__ __forceinline__ void gather_hint(Poll & pl, xrsrc xr, int unit, unsigned tag, unsigned * go, unsigned gen, int nap, Idle && idle) {
         for (unsigned spin = 0;; spin++) {
             if (fl_ld(go) >= gen || pl.dead) break;
             asm volatile("" ::: "memory");
-            if (look_turned(pl, xr, unit, tag)) { fl_st(go, gen); break; }
+            if (look_turned(xr, unit, tag)) { fl_st(go, gen); break; }
             idle();
             if (poll_backoff(pl, spin)) break;
             for (int i = 0; i < nap; i++) __builtin_amdgcn_s_sleep(1);
@@ -681,7 +585,7 @@ struct R6 {
     // F: LN2 + token shift + the two mixes + quantise -> l.q1 (key input), l.q2 (receptance input)
     static __device__ __forceinline__ void prologue_F(Poll & pl, const Lds & l, const PF & pf, float * sout_l, bool write_state, int c, int lane, unsigned gen, unsigned eg) {
         const float scale = c < 4 ? ln_stats(pl, l, c * 64 + lane, lane, gen + eg) : ln_scale(pl, l, lane, gen + eg);
-        const QVec qk = qvec_at(l.q1, D), qr = qvec_at(l.q2, D);
+        const QVec qk = qvec_at(l.q1, D);
 #pragma unroll
         for (int u = 0; u < SMAX; u++) {
             if (u >= pslots(c)) break;
@@ -707,8 +611,7 @@ struct R6 {
             unsigned packed; float d16, s16; int isum;
             quant_vec4(xk, packed, d16, s16, isum);
             qvec_store4(qk, nb, i, packed, d16, s16, isum);
-            if constexpr (DEFER_XR) *reinterpret_cast<float4 *>(l.x + i) = make_float4(xr[0], xr[1], xr[2], xr[3]);   // (this thread is the only reader of these four elements from here on)
-            else { quant_vec4(xr, packed, d16, s16, isum); qvec_store4(qr, nb, i, packed, d16, s16, isum); }
+            *reinterpret_cast<float4 *>(l.x + i) = make_float4(xr[0], xr[1], xr[2], xr[3]);   // (this thread is the only reader of these four elements from here on)
         }
         fl_add(l.fl + (c < 4 ? FL_PRO : FL_PROX), 1u);
     }
@@ -716,10 +619,6 @@ struct R6 {
     // (their results are used in the value rows' epilogue, a hand-over later). So the prologue leaves the receptance input as floats in
     // l.x (in place of x - mean) and its quantisation -- a third of the prologue's arithmetic -- runs here, behind the wave's key rows,
     // under the kq hand-over. Same statements on the same values: bit-identical.
-#ifndef R6_DEFER_XR
-#define R6_DEFER_XR 1
-#endif
-    static constexpr bool DEFER_XR = R6_DEFER_XR != 0;
     static __device__ __forceinline__ void quant_xr(const Lds & l, int c, int lane) {
         const QVec qr = qvec_at(l.q2, D);
 #pragma unroll
@@ -775,22 +674,12 @@ struct R6 {
     // DMA in flight at the next LDS access; completion is counted by hand.) A wave issues at most one instruction every four cycles, so
     // the loader's instruction count per fill IS its ceiling: 16 instructions per fill (scalar address arithmetic, M0 save / restore per
     // fill) gave 23 GB/s alone in this kernel; this is 2 per fill.
-#ifndef R6_DMA_OFFSET_BOTH
-#define R6_DMA_OFFSET_BOTH 1
-#endif
     template <bool NT>
     static __device__ __forceinline__ void dma_quad(unsigned long long sbase, unsigned voff, unsigned m0dst) {
         unsigned keep;
-#if R6_DMA_OFFSET_BOTH
 #define R6_QUAD(POL) "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t" \
                      "global_load_lds_dwordx4 %1, %2" POL "\n\tglobal_load_lds_dwordx4 %1, %2 offset:1024" POL "\n\t" \
                      "global_load_lds_dwordx4 %1, %2 offset:2048" POL "\n\tglobal_load_lds_dwordx4 %1, %2 offset:3072" POL "\n\ts_mov_b32 m0, %0"
-#else
-#define R6_QUAD(POL) "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t" \
-                     "global_load_lds_dwordx4 %1, %2" POL "\n\ts_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 offset:1024" POL "\n\t" \
-                     "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 offset:2048" POL "\n\t" \
-                     "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 offset:3072" POL "\n\ts_mov_b32 m0, %0"
-#endif
         if constexpr (NT) asm volatile(R6_QUAD(" nt") : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(m0dst) : "memory");
         else asm volatile(R6_QUAD("") : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(m0dst) : "memory");
 #undef R6_QUAD
@@ -942,19 +831,11 @@ struct R6 {
         unsigned cnt;          // records this wave owns in this phase
         unsigned pos, ro;      // stream position / ring offset of the next record to take
         unsigned after;        // where this wave's stream continues behind the phase
-        unsigned base;         // stream position of the phase's record 0
+        unsigned base;         // stream position of the phase's record 0 (read by nothing since the balanced deal went: DESIGN.md Appendix B)
     };
-    // record number of this wave's T-th record of phase PH: six apart, or by the balanced deal (scalar selects on the wave's pair, no table in memory)
+    // record number of this wave's T-th record of phase PH: six apart
     template <int PH, int T>
-    static __device__ __forceinline__ unsigned ownj(const Cons & cs) {
-        if constexpr (balph<PH>()) {
-            constexpr int TT = T < RG_BAL_TMAX ? T : RG_BAL_TMAX - 1;
-            constexpr unsigned a = (unsigned) (PH == RG_C ? RG_BAL_C_J[0][TT] : RG_BAL_K_J[0][TT]), b = (unsigned) (PH == RG_C ? RG_BAL_C_J[1][TT] : RG_BAL_K_J[1][TT]),
-                               d = (unsigned) (PH == RG_C ? RG_BAL_C_J[2][TT] : RG_BAL_K_J[2][TT]);
-            const unsigned pr = (unsigned) cs.c >> 1;
-            return (pr == 0u ? a : (pr == 1u ? b : d)) + ((unsigned) cs.c & 1u);
-        } else return rg_first_j(cs.cu, PH, cs.c) + (unsigned) (NC * T);
-    }
+    static __device__ __forceinline__ unsigned ownj(const Cons & cs) { return rg_first_j(cs.cu, PH, cs.c) + (unsigned) (NC * T); }
     template <int R, int U> static constexpr unsigned recb() { return (unsigned) (U * R * 64) * (QF<FMT>::QS + (QF<FMT>::HM ? 4 : 2) + (QF<FMT>::QH ? 4 : 0)); }
     template <int PH, int R, int U, int NP>
     static __device__ __forceinline__ void pre_begin(const Cons & cs, Pre<PH, R, U, NP> & pre) {
@@ -996,30 +877,20 @@ struct R6 {
         // the reads above are in the LDS queue: the ring may be refilled up to this wave's next record (every lane writes the same word)
         asm volatile("" ::: "memory");
         const bool last = pre.have + 1u >= pre.cnt;
-        // this wave's next record: NC records on, or where the balanced deal puts it (behind the last one: not used)
-        unsigned nxt;
-        if constexpr (balph<PH>()) nxt = pre.base + ownj<PH, T + 1>(cs) * RECB; else nxt = pre.pos + STRIDE;
+        const unsigned nxt = pre.pos + STRIDE;   // this wave's next record: NC records on (behind the last one: not used)
         __hip_atomic_store(l.fl + FL_DONE + 2 + cs.c, last ? pre.after : nxt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         if constexpr (WAIT) rec_wait<FMT, R, U>(pre.w[T % NP]);
         pre.have += 1u;
         // (a wave's records are NC records apart: more than one lap of the ring for the long Q8_0 value rows)
         pre.ro += nxt - pre.pos; pre.pos = nxt;
         pre.ro = pre.ro >= cs.RB ? pre.ro - cs.RB : pre.ro;
-        if constexpr (!balph<PH>() && STRIDE > 32768u) { pre.ro = pre.ro >= cs.RB ? pre.ro - cs.RB : pre.ro; pre.ro = pre.ro >= cs.RB ? pre.ro - cs.RB : pre.ro; }
+        if constexpr (STRIDE > 32768u) { pre.ro = pre.ro >= cs.RB ? pre.ro - cs.RB : pre.ro; pre.ro = pre.ro >= cs.RB ? pre.ro - cs.RB : pre.ro; }
         return true;
     }
-    // which phases take records ahead (1: r/k/v/g, 2: output, 4: ffn key, 8: ffn value), and how many per wave. D = 2048: none -- a layer
-    // block (130 KB per workgroup) nearly fits the ring as it is, and the extra ring checks in the watch loops cost 2.5 %.
-    // + 16: W1 + r/k/v/g records during the x hand-over at the top of the layer, + 32: output records during the act hand-over, + 64: ffn
-    // key records during the yq hand-over (the phase behind the one the hand-over feeds), + 128: ffn receptance records behind those.
-    // (+ 16 only compiles without scratch since the layer loop has no separate first-layer branch: see gather_x)
-#ifndef R6_PRE_MASK
-#define R6_PRE_MASK 255
-#endif
-#ifndef R6_PRE_MASK_SMALL   /* the same for D = 2048: rounds 3 / 4 measured -2.5 % and left it off; on round 6's kernel +0.6 % (1427.6 against 1419.5 tokens/s on the 1.6B, two alternations) */
-#define R6_PRE_MASK_SMALL 255
-#endif
-    static constexpr int PRE_MASK = EPT > 4 ? R6_PRE_MASK : R6_PRE_MASK_SMALL;
+    // Every row phase takes records ahead, in every geometry: W1 + r/k/v/g records during the x hand-over at the top of the layer, output
+    // records during the act hand-over, ffn key records during the yq hand-over (the phase behind the one the hand-over feeds) and ffn
+    // receptance records behind those, ffn value records during the kq hand-over (G_PRE).
+    // (the take at the top of the layer only compiles without scratch since the layer loop has no separate first-layer branch: see gather_x)
     // Stage 1 of a gather (gather_hint) with the wait put to use: until the hand-over's sentinel turns, the wave takes its records of
     // the coming phase as they land -- record 0, then 1, ... up to NP -- and never waits for a record once the hand-over is there.
     // Written as a straight sequence of NP steps (each: spin until "record t has landed" or "the hand-over turned"), not as one loop that
@@ -1056,7 +927,7 @@ struct R6 {
                     // a landed record is taken at once -- except that every `look`-th take in a row is preceded by a look at the sentinel
                     if (landed && (spin > 0u || (unsigned) t % look != 0u)) { here = true; break; }
                     asm volatile("" ::: "memory");
-                    if (look_turned(pl, xr, unit, tag)) { fl_st(go, gen); turned = true; break; }
+                    if (look_turned(xr, unit, tag)) { fl_st(go, gen); turned = true; break; }
                     if (landed) { here = true; break; }
                     if (poll_backoff(pl, spin)) { turned = true; break; }
                     for (int i = 0; i < nap; i++) __builtin_amdgcn_s_sleep(1);
@@ -1075,13 +946,13 @@ struct R6 {
     static __device__ __forceinline__ void hint_take(Cons & cs, Poll & pl, const Lds & l, xrsrc xr, int unit, unsigned tag, unsigned * go, unsigned gen, int nap,
                                                      bool on_a, Pre<PA_, RA, UA, NA> & a, bool on_b, Pre<PB_, RB_, UB_, NB_> & b, bool no_handover = false) {
         Pre<RG_W1, 1, 1, 1> none;
-        none.have = 0u; none.cnt = 0u; none.pos = 0u; none.ro = 0u; none.after = 0u; none.base = 0u;
+        none.have = 0u; none.cnt = 0u; none.pos = 0u; none.ro = 0u; none.after = 0u;
         hint_take(cs, pl, l, xr, unit, tag, go, gen, nap, on_a, a, on_b, b, false, none, no_handover);
     }
     template <int PH, int R, int U, int NP>
     static __device__ __forceinline__ void hint_take(Cons & cs, Poll & pl, const Lds & l, xrsrc xr, int unit, unsigned tag, unsigned * go, unsigned gen, int nap, bool on, Pre<PH, R, U, NP> & pre) {
         Pre<RG_W1, 1, 1, 1> none;
-        none.have = 0u; none.cnt = 0u; none.pos = 0u; none.ro = 0u; none.after = 0u; none.base = 0u;
+        none.have = 0u; none.cnt = 0u; none.pos = 0u; none.ro = 0u; none.after = 0u;
         hint_take(cs, pl, l, xr, unit, tag, go, gen, nap, on, pre, false, none, false, none);
     }
 
@@ -1091,19 +962,18 @@ struct R6 {
     // register. epi(integral_constant<t>, j, res) receives the row sums of the wave's t-th record (record j of the phase).
     // (The first version walked the records in a loop with the cursor in a struct: ~300 overhead instructions per record -- half of
     //  them scalar, forty branches -- around ~140 useful ones; a C phase took 13.7 k cycles for 3.6 k cycles of arithmetic.)
-    // TMIN: every wave that owns any record of the phase owns at least TMIN (= TF when the records are dealt six apart; the smallest share of
-    // a balanced deal). Steps t < TMIN are unconditional code; the others ask `t < cnt` (wave-uniform) -- and where there are several of those
-    // (balanced deal) their takes wait for their LDS reads at once: a buffer with reads in flight must not cross a join of control flow,
-    // where the register allocator may copy it (the copy would carry the old contents). With every step conditional Q8_0 computed garbage.
-    template <int PH, int R, int U, int TF, int NP, int TMIN = TF, typename EpiF>
+    // Steps t < TF are unconditional code; the tail asks `t < cnt` (wave-uniform). A buffer with reads in flight must not cross a join of
+    // control flow, where the register allocator may copy it (the copy would carry the old contents): with every step conditional Q8_0
+    // computed garbage.
+    template <int PH, int R, int U, int TF, int NP, typename EpiF>
     static __device__ __forceinline__ void rows(Cons & cs, Poll & pl, const Lds & l, const QVec & act, int nbk, Pre<PH, R, U, NP> & pre, EpiF && epi) {
-        static_assert(NP >= 1 && NP <= TF + 1 && TMIN <= TF, "rows: buffers");
+        static_assert(NP >= 1 && NP <= TF + 1, "rows: buffers");
         if (pre.cnt == 0u) return;
-        constexpr bool SAFE = TMIN < TF || R6_ROWS_WAIT != 0;       // conditional takes wait at once
-        auto has = [&](int t) { return t < TMIN || (unsigned) t < pre.cnt; };
+        constexpr bool SAFE = R6_ROWS_WAIT != 0;                    // conditional takes wait at once
+        auto has = [&](int t) { return t < TF || (unsigned) t < pre.cnt; };
         const int ln = opq(cs.lane);
         ActRegs<U> ar;
-        act_load<FMT, U>(ar, act, nbk, ln);
+        act_load<U>(ar, act, nbk, ln);
         // per-lane partial sums of every record of the phase; ONE interleaved butterfly over all of them at the end (a butterfly is six
         // dependent cross-lane steps: per record they ran back to back, two chains at a time)
         float part[(TF + 1) * R];
@@ -1128,7 +998,7 @@ struct R6 {
         // what is not in registers yet (blocking), up to NP records; then the arithmetic, and behind record t its buffer takes record t + NP
         Unroll<0, NP>::run([&](auto tc) {
             constexpr int t = decltype(tc)::value;
-            if (has(t) && pre.have <= (unsigned) t) (void) rec_take<t, PH, R, U, NP, (SAFE && t >= TMIN)>(cs, pl, l, pre, true);
+            if (has(t) && pre.have <= (unsigned) t) (void) rec_take<t, PH, R, U, NP, (SAFE && t >= TF)>(cs, pl, l, pre, true);
         });
         // (record t's reads were issued NP - 1 takes ago; the take issued right before this wait -- of record t - 1 + NP, behind the
         //  arithmetic of record t - 1 -- may stay in flight: its LDS latency overlaps the arithmetic instead of preceding it)
@@ -1141,7 +1011,7 @@ struct R6 {
                 finish(tc, pre.w[t % NP]);
                 took = false;
                 if constexpr (t + NP <= TF) {
-                    constexpr bool W = SAFE && t + NP >= TMIN;
+                    constexpr bool W = SAFE && t + NP >= TF;
                     if (has(t + NP)) { (void) rec_take<t + NP, PH, R, U, NP, W>(cs, pl, l, pre, true); took = !W; }
                 }
             }
@@ -1157,51 +1027,24 @@ struct R6 {
             }
         });
     }
-    // a phase without records taken ahead
-    template <int PH, int R, int U, int TF, int NP, typename EpiF>
-    static __device__ __forceinline__ void rows(Cons & cs, Poll & pl, const Lds & l, const QVec & act, int nbk, EpiF && epi) {
-        Pre<PH, R, U, NP> pre;
-        pre_begin<PH>(cs, pre);
-        rows<PH, R, U, TF, NP>(cs, pl, l, act, nbk, pre, epi);
-    }
-
     // buffers per wave and phase = records held in registers at once. r/k/v/g sets (C), output rows (E), ffn key sets (K), ffn receptance
-    // rows (R), ffn value rows (G). With records taken ahead (PRE_MASK): as many as the register file holds without spilling
-    // (tools/check_ring_regs.sh prints the budget of every instantiation); without: the double buffer (one buffer for Q8_0's 36-register
-    // blocks and for the long value rows).
-    // (TFx: a wave owns TFx or TFx + 1 records of the phase -- dealt six apart; with the balanced deal of C and FK: up to TFx + 1)
+    // rows (R), ffn value rows (G): as many as the register file holds without spilling (tools/check_ring_regs.sh prints the budget of
+    // every instantiation).
+    // (TFx: a wave owns TFx or TFx + 1 records of the phase -- dealt six apart)
     static constexpr int KSETS = UF * 64 > NBLK ? 32 : 16 /* two-row key sets of a workgroup that owns any */,
                          KCOMM = (KSETS % NC <= 2) ? KSETS % NC : 0 /* ... of which the comm wave takes the last ones (ring_geom.h, rg_key_comm) */;
-    static constexpr int TFC = BAL ? RG_BAL_C_N[1] - 1 : (D * 4 / NBLK / 2) / NC, TFE = RE / NC, TFK = BAL ? RG_BAL_K_N[1] - 1 : (KSETS - KCOMM) / NC;
-    static constexpr int TMC = BAL ? RG_BAL_C_N[2] : TFC, TMK = BAL ? RG_BAL_K_N[2] : TFK;   // the smallest share of a wave that owns any
-    static_assert(!BAL || (D * 4 / NBLK / 2 == RG_BAL_C_SETS && KSETS - KCOMM == RG_BAL_K_SETS), "balanced deal: geometry");
+    static constexpr int TFC = (D * 4 / NBLK / 2) / NC, TFE = RE / NC, TFK = (KSETS - KCOMM) / NC;
     static constexpr bool Q8 = QF<FMT>::QS == 32, Q5 = QF<FMT>::QH;
     static constexpr int npcap(int want, int tf) { return want < 1 ? 1 : (want > tf + 1 ? tf + 1 : want); }
-#ifndef R6_NPC
-#define R6_NPC (Q8 ? 3 : (Q5 ? 5 : 6))
-#endif
-#ifndef R6_NPE
-#define R6_NPE 3
-#endif
-#ifndef R6_NPK
-#define R6_NPK ((PRE_MASK & 128) ? (Q8 ? 2 : (Q5 ? 4 : 5)) : (Q8 ? 3 : (Q5 ? 5 : 6)))   /* (with the receptance records held as well: one buffer less) */
-#endif
-#ifndef R6_NPG
-#define R6_NPG (Q8 ? 1 : 3)
-#endif
-    static constexpr int NPC = npcap((PRE_MASK & 1) ? R6_NPC : (Q8 ? 1 : 2), TFC);
-    static constexpr int NPE = npcap((PRE_MASK & 2) ? R6_NPE : (Q8 ? 1 : 2), TFE);
-    static constexpr int NPK = npcap((PRE_MASK & 4) ? R6_NPK : (Q8 ? 1 : 2), TFK);
-    static constexpr int NPR = npcap((PRE_MASK & 128) ? 3 : (Q8 ? 1 : 2), TFE);
-    static constexpr int NPG = npcap((PRE_MASK & 8) ? R6_NPG : 1, TFE);
-    // value records are taken ahead where one fits 48 registers (not Q8_0's 63 at F = 14336). Rounds 4 and 5 tested sizeof(RawRec) <= 192 here:
-    // the 16-byte aligned code vectors pad every block to 32 bytes, 7 blocks = 224, and the take was off for EVERY format at the 7B geometry
-    // (tools/trace_ring.py, "records already in registers": G 0.00) -- R6_G_PRE_OLD=1 rebuilds that.
-#ifndef R6_G_PRE_OLD
-#define R6_G_PRE_OLD 0
-#endif
+    static constexpr int NPC = npcap(Q8 ? 3 : (Q5 ? 5 : 6), TFC);
+    static constexpr int NPE = npcap(3, TFE);
+    static constexpr int NPK = npcap(Q8 ? 2 : (Q5 ? 4 : 5), TFK);   // (with the receptance records held as well: one buffer less than NPC)
+    static constexpr int NPR = npcap(3, TFE);
+    static constexpr int NPG = npcap(Q8 ? 1 : 3, TFE);
+    // value records are taken ahead where one fits 48 registers (not Q8_0's 63 at F = 14336), counted in registers: sizeof(RawRec) over-counts,
+    // the 16-byte aligned code vectors pad every block to 32 bytes
     static constexpr int rec_regs(int R, int U) { return U * R * (QF<FMT>::QS / 4 + 1 + (QF<FMT>::QH ? 1 : 0)); }
-    static constexpr bool G_PRE = R6_G_PRE_OLD ? sizeof(RawRec<FMT, 1, UF>) <= 48 * 4 : rec_regs(1, UF) <= 48;
+    static constexpr bool G_PRE = rec_regs(1, UF) <= 48;
 
     static __device__ __forceinline__ void consumer_main(const R6P & p, const Lds & l, int lane, int wave, unsigned base) {
         const int blk = blockIdx.x;
@@ -1210,7 +1053,7 @@ struct R6 {
         // (The prologue parameters are loaded by EVERY consumer wave, also where waves 4, 5 take no part: a load under `if (pro)` is a
         //  conditional definition, and the compiler then waits for it and copies it right where it is issued.)
         const int F = p.F, nbF = F / 32;
-        Poll pl{p.ctl, false, p.xch, R6_SWATCH == 1};
+        Poll pl{p.ctl, false};
         const M6Arena ar{p.arena};
         const xrsrc xr = make_xrsrc(p.xch, p.xch_bytes);
         const RingShape sh = shape(p);
@@ -1231,23 +1074,10 @@ struct R6 {
         const bool emb_in = p.tok != nullptr;          // the launch starts from the token id (wave-uniform)
         const unsigned eg = emb_in ? 1u : 0u;
         if (emb_in && c < 4) embed_ln0(p, pl, l, ar, c * 64 + opq(lane), opq(lane));
-        // Where the prologue parameters are loaded (LayerNorm affine, token-shift source, mix weights: 4 / 5 float4 per slot and thread).
-        // R6_LATE_PARAMS = 0 (round 3): a whole phase ahead -- 48 / 60 registers live across a hand-over wait. 1: at the start of the
-        // prologue, in flight under the LayerNorm statistics (two reduction rounds, ~1 us; the lines are the same for every workgroup:
-        // L2 hits) -- the hand-over waits then hold next to nothing but records taken ahead, which is what the registers are for now.
-        // 2 (default): both when the x hand-over's sentinel has turned -- in flight under the sweep and the statistics, behind the records taken
-        // during the wait (LN1's a phase ahead as in round 3 would be 48 registers live across the loop's back edge and the wait in which the
-        // r/k/v/g records are taken). Measured on the 7B: placement 1 costs 1.5 + 0.6 us per layer in the two prologues (the loads are NOT
-        // covered by the statistics).
-#ifndef R6_LATE_PARAMS
-#define R6_LATE_PARAMS 2
-#endif
-        // (D = 2048 takes no records ahead and holds nothing across the x hand-over: there LN1's parameters go out a phase ahead as in round 3 --
-        //  issued behind the sentinel they cost the 1.6B 1.8 %)
-        constexpr bool PA_EARLY = R6_LATE_PARAMS == 0 || (R6_LATE_PARAMS == 2 && (PRE_MASK & 16) == 0);
-        constexpr bool PF_EARLY = R6_LATE_PARAMS == 0 || (R6_LATE_PARAMS == 2 && (PRE_MASK & 4) == 0);
+        // The prologue parameters (LayerNorm affine, token-shift source, mix weights: 4 / 5 float4 per slot and thread) are loaded when the x
+        // hand-over's sentinel has turned -- in flight under the sweep and the statistics, behind the records taken during the wait, so that
+        // the hand-over waits hold next to nothing but those records.
         PA pa; PF pf;
-        if (PA_EARLY) issue_pa(pa, ar, p.layers[0], p.sin, c, opq(lane));
 
         for (int li = 0; li < p.n_layers; li++) {
             const M6Layer & L = p.layers[li];
@@ -1271,10 +1101,9 @@ struct R6 {
                 // (the first layer of a launch has no hand-over in front of it: its x lies in plain memory; same statements, see gather_x)
                 const bool first = li == 0;
                 watch_begin(l);
-                hint_take(cs, pl, l, xr, p.xffn + ((blk * 37 + c * 211) & 1023), tagL - 8u + SLOT_XFFN, l.fl + FL_HX, 2u * li + 1u, p.nap, (PRE_MASK & 16) != 0 && !first, pw,
-                          (PRE_MASK & 16) != 0 && !first, pc, first);
+                hint_take(cs, pl, l, xr, p.xffn + ((blk * 37 + c * 211) & 1023), tagL - 8u + SLOT_XFFN, l.fl + FL_HX, 2u * li + 1u, p.nap, !first, pw, !first, pc, first);
                 watch_end(l);
-                if (R6_LATE_PARAMS == 2 && !PA_EARLY) { issue_pa(pa, ar, L, sin_l, c, opq(lane)); __builtin_amdgcn_sched_barrier(0); }
+                issue_pa(pa, ar, L, sin_l, c, opq(lane)); __builtin_amdgcn_sched_barrier(0);
                 sweep_begin(l);
                 gather_x(pl, xr, p.xffn, tagL - 8u + SLOT_XFFN, c, opq(lane), l.x, first ? p.x : nullptr, first && emb_in);
             }
@@ -1286,7 +1115,6 @@ struct R6 {
 #pragma unroll
                 for (int t = 0; t < XT; t++) { const int row = c + NC * t; const float v = l.x[blk * RE + (row < RE ? row : 0)]; xown[t] = take ? v : xown[t]; }
             }
-            if (R6_LATE_PARAMS == 1) { issue_pa(pa, ar, L, sin_l, c, opq(lane)); __builtin_amdgcn_sched_barrier(0); }
             if (pro) prologue_A(pl, l, pa, sout_l, blk == 0, c, opq(lane), 2u * li + 1u, eg);
             prologue_wait(pl, l, 2u * li + 1u);
             R6STAMP(2);
@@ -1301,7 +1129,7 @@ struct R6 {
             {
                 const int img = (0x4213 >> (4 * mat)) & 0xF;   // r, k, v, g -> mix image (w, k, v, r, g order)
                 watch_begin(l);
-                hint_take(cs, pl, l, xr, p.act5 + img * p.act_stride + ((blk * 7 + c * 19) & 127), tagL + SLOT_ACT, l.fl + FL_HACT, g1, p.nap, (PRE_MASK & 1) != 0, pc, (PRE_MASK & 32) != 0, pe);
+                hint_take(cs, pl, l, xr, p.act5 + img * p.act_stride + ((blk * 7 + c * 19) & 127), tagL + SLOT_ACT, l.fl + FL_HACT, g1, p.nap, true, pc, true, pe);
                 watch_end(l);
                 sweep_begin(l);
                 gather_qvec<DSL>(pl, xr, p.act5 + img * p.act_stride, D, tagL + SLOT_ACT, c, opq(lane), l.act);
@@ -1320,7 +1148,7 @@ struct R6 {
                 if (p.trace && li == p.trace_layer && lane == 0) p.trace[((long long) blockIdx.x * 8 + wave) * 32 + 20] = (long long) fl_ld(l.fl + FL_LANDED) * 1024ll - (long long) (cs.lbase + cs.cu.off[RG_C]);
                 R6RSTAMP(26);
                 havepk |= pc.have << 4;
-                rows<RG_C, 2, UD, TFC, NPC, TMC>(cs, pl, l, qvec_at(l.act, D), nb, pc, [&](auto tc, int, const float (&res)[2]) {
+                rows<RG_C, 2, UD, TFC, NPC>(cs, pl, l, qvec_at(l.act, D), nb, pc, [&](auto tc, int, const float (&res)[2]) {
                     constexpr int t = decltype(tc)::value;
                     all[2 * t] = res[0]; all[2 * t + 1] = res[1];
                 });
@@ -1329,13 +1157,12 @@ struct R6 {
                 if (mat == 3) v = v / (1.0f + det_expf(-v));     // gate: silu
                 const int v1 = __builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x101, 0xF, 0xF, true);   // lane 2 t collects row 1 (row_shl:1)
                 int j = 0x7fff;   // record number of the set lane ln >> 1 finishes (a select chain over this wave's records)
-                Unroll<0, MAXT>::run([&](auto tc) { constexpr int t = decltype(tc)::value; const int jt = (t < TMC || (unsigned) t < pc.cnt) ? (int) ownj<RG_C, t>(cs) : 0x7fff; j = (ln >> 1) == t ? jt : j; });
+                Unroll<0, MAXT>::run([&](auto tc) { constexpr int t = decltype(tc)::value; const int jt = (t < TFC || (unsigned) t < pc.cnt) ? (int) ownj<RG_C, t>(cs) : 0x7fff; j = (ln >> 1) == t ? jt : j; });
                 if (ln < 2 * MAXT && (ln & 1) == 0 && j < (int) cs.cu.n[RG_C])
                     tg_store(xr, p.rkvg + ((mat * D + cbase + 2 * j) >> 1), __float_as_uint(v), (unsigned) v1, 0u, 0u, tagL + SLOT_RKVG);
             }
             R6STAMP(5); R6RSTAMP(27);
             if (p.trace && li == p.trace_layer && lane == 0) p.trace[((long long) blockIdx.x * 8 + wave) * 32 + 24] = cs.waited;
-            if (PF_EARLY) issue_pf(pf, ar, L, sin_l, c, opq(lane));
             __builtin_amdgcn_sched_barrier(0);
             // ---- E: output projection + residual ----
             Pre<RG_FK, 2, UD, NPK> pk;
@@ -1343,7 +1170,7 @@ struct R6 {
             Pre<RG_FR, 1, UD, NPR> pr;
             pre_begin<RG_FR>(cs, pr);
             watch_begin(l);
-            hint_take(cs, pl, l, xr, p.yq + ((blk * 7 + c * 19) & 127), tagL + SLOT_YQ, l.fl + FL_HYQ, g1, p.nap, (PRE_MASK & 2) != 0, pe, (PRE_MASK & 64) != 0, pk, (PRE_MASK & 128) != 0, pr);
+            hint_take(cs, pl, l, xr, p.yq + ((blk * 7 + c * 19) & 127), tagL + SLOT_YQ, l.fl + FL_HYQ, g1, p.nap, true, pe, true, pk, true, pr);
             watch_end(l);
             sweep_begin(l);
             gather_qvec<DSL>(pl, xr, p.yq, D, tagL + SLOT_YQ, c, opq(lane), l.yq);
@@ -1359,30 +1186,27 @@ struct R6 {
             R6STAMP(7);
             // ---- F: x, LN2 + mixes + quantise, key sets (-> comm quantises them), receptance rows ----
             watch_begin(l);
-            hint_take(cs, pl, l, xr, p.xatt + ((blk * 37 + c * 211) & 1023), tagL + SLOT_XATT, l.fl + FL_HX, 2u * li + 2u, p.nap, (PRE_MASK & 4) != 0, pk, (PRE_MASK & 128) != 0, pr);
+            hint_take(cs, pl, l, xr, p.xatt + ((blk * 37 + c * 211) & 1023), tagL + SLOT_XATT, l.fl + FL_HX, 2u * li + 2u, p.nap, true, pk, true, pr);
             watch_end(l);
-            if (R6_LATE_PARAMS == 2 && !PF_EARLY) { issue_pf(pf, ar, L, sin_l, c, opq(lane)); __builtin_amdgcn_sched_barrier(0); }
+            issue_pf(pf, ar, L, sin_l, c, opq(lane)); __builtin_amdgcn_sched_barrier(0);
             sweep_begin(l);
             gather_x(pl, xr, p.xatt, tagL + SLOT_XATT, c, opq(lane), l.x);
             gather_meet(pl, l.fl + FL_GX, 2u * li + 2u);
             sweep_end(l);
             R6STAMP(8);
-            if (R6_LATE_PARAMS == 1) { issue_pf(pf, ar, L, sin_l, c, opq(lane)); __builtin_amdgcn_sched_barrier(0); }
             if (pro) prologue_F(pl, l, pf, sout_l, blk == 0, c, opq(lane), 2u * li + 2u, eg);
             prologue_wait(pl, l, 2u * li + 2u);
             R6STAMP(9); R6RSTAMP(28);
             if (p.trace && li == p.trace_layer && lane == 0) p.trace[((long long) blockIdx.x * 8 + wave) * 32 + 21] = (long long) fl_ld(l.fl + FL_LANDED) * 1024ll - (long long) (cs.lbase + cs.cu.off[RG_FK]);
             havepk |= (pk.have << 12) | (pr.have << 16);
-            rows<RG_FK, 2, UD, TFK, NPK, TMK>(cs, pl, l, qvec_at(l.q1, D), nb, pk, [&](auto, int j, const float (&res)[2]) {
+            rows<RG_FK, 2, UD, TFK, NPK>(cs, pl, l, qvec_at(l.q1, D), nb, pk, [&](auto, int j, const float (&res)[2]) {
                 const float v = lane == 1 ? res[1] : res[0];
                 const float t = v > 0.0f ? v : 0.0f;
                 if (lane < 2) l.out[2 * j + lane] = t * t;
             });
             fl_add(l.fl + FL_KEYS, 1u);
-            if constexpr (DEFER_XR) {
-                if (pro) quant_xr(l, c, opq(lane));
-                fl_wait(pl, l.fl + FL_XRQ, (unsigned) (SHI > 0 ? NC : 4) * g1);
-            }
+            if (pro) quant_xr(l, c, opq(lane));
+            fl_wait(pl, l.fl + FL_XRQ, (unsigned) (SHI > 0 ? NC : 4) * g1);
             R6STAMP(10);
             rows<RG_FR, 1, UD, RE / NC, NPR>(cs, pl, l, qvec_at(l.q2, D), nb, pr, [&](auto tc, int, const float (&res)[1]) {
                 constexpr int t = decltype(tc)::value;
@@ -1395,7 +1219,7 @@ struct R6 {
             // (registers: not the long Q8_0 rows of the 7B geometry)
             watch_begin(l);
             { const unsigned lk = cs.look; cs.look = (unsigned) __builtin_amdgcn_readfirstlane(p.look_g);
-              hint_take(cs, pl, l, xr, p.kq + ((blk * 5 + c * 173) & 511), tagL + SLOT_KQ, l.fl + FL_HKQ, g1, p.nap, (PRE_MASK & 8) != 0 && G_PRE, pg);
+              hint_take(cs, pl, l, xr, p.kq + ((blk * 5 + c * 173) & 511), tagL + SLOT_KQ, l.fl + FL_HKQ, g1, p.nap, G_PRE, pg);
               cs.look = lk; }
             watch_end(l);
             sweep_begin(l);
@@ -1414,14 +1238,8 @@ struct R6 {
             if (lane == 0) tg_store(xr, p.xffn + blk * NC + c, __float_as_uint(xown[0]), __float_as_uint(xown[XT > 1 ? 1 : 0]), __float_as_uint(xown[XT > 2 ? 2 : 0]), 0u, tagL + SLOT_XFFN);
             R6STAMP(13); R6RSTAMP(14);
             if (p.trace && li == p.trace_layer && lane == 0) { p.trace[((long long) blockIdx.x * 8 + wave) * 32 + 25] = cs.waited; p.trace[((long long) blockIdx.x * 8 + wave) * 32 + 15] = (long long) havepk; }
-            __builtin_amdgcn_sched_barrier(0);   // (the loads below stay behind the value rows: hoisted into them they cost 48 registers at the kernel's peak)
-            if (PA_EARLY) {   // the next layer's prologue parameters: in flight while this wave watches the x hand-over's sentinel (not across G: registers)
-                // (unconditionally -- behind the last layer the same layer's again: under `if (li + 1 < n_layers)` the parameters are
-                //  conditionally redefined, and the old values stay live through the whole layer on the path the compiler cannot rule out)
-                const int nl = li + 1 < p.n_layers ? li + 1 : li;
-                issue_pa(pa, ar, p.layers[nl], p.sin + (long long) nl * p.state_stride, c, opq(lane));
-            }
-            __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_sched_barrier(0);   // (nothing of the next layer moves up into the value rows)
+            __builtin_amdgcn_sched_barrier(0);   // (the second marker of the pair that stood around the retired early parameter loads: DESIGN.md Appendix B)
         }
         if (p.logits) head_phase(p, l, cs, pl, xr, ar, hd, hbase, lane, wave, base, eg);
     }
@@ -1548,7 +1366,7 @@ struct R6 {
         const int g = NC;                              // gather share
         const int F = p.F, DR = p.DR, R = p.R, H = p.H;
         const int nbF = F / 32;
-        Poll pl{p.ctl, false, p.xch, R6_SWATCH != 0};
+        Poll pl{p.ctl, false};
         const M6Arena ar{p.arena};
         const xrsrc xr = make_xrsrc(p.xch, p.xch_bytes);
         const int mat = (blk * (4 * D / NBLK)) / D;
@@ -1676,7 +1494,7 @@ struct R6 {
             if (has_dw1) {
                 const int ln = opq(lane);
                 ActRegs<UD> arw;
-                act_load<FMT, UD>(arw, qvec_at(l.actw, D), nb, ln);
+                act_load<UD>(arw, qvec_at(l.actw, D), nb, ln);
                 float part[1];
                 rec_acc<FMT, 1, UD>(dwr, arw, nb, ln, part);
                 wave_sum_n<1>(part);
@@ -1830,7 +1648,7 @@ struct R6 {
                     prologue_wait(pl, l, 2u * li + 2u);              // l.q1 holds the quantised key input
                     const int lnK = opq(lane);
                     ActRegs<UD> ark;
-                    act_load<FMT, UD>(ark, qvec_at(l.q1, D), nb, lnK);
+                    act_load<UD>(ark, qvec_at(l.q1, D), nb, lnK);
                     float part[2 * KCOMM];
 #pragma unroll
                     for (int q = 0; q < KCOMM; q++) rec_acc<FMT, 2, UD>(kxr[q], ark, nb, lnK, part + 2 * q);
@@ -1937,18 +1755,15 @@ __global__ __launch_bounds__(512) void k6_ring(R6P p) {
     if (tid0 < FL_WORDS) l.fl[tid0] = (tid0 >= FL_DONE + 2 && tid0 < FL_DONE + 2 + RG_NC) ? 0u : (tid0 >= FL_DONE && tid0 < FL_DONE + 8 ? 0xFFFFFFFFu : 0u);
     __syncthreads();   // the only workgroup barrier of the launch
     const unsigned base = p.ctl[0];
-#ifndef R6_ROLES
-#define R6_ROLES 7
-#endif
     if (p.dbg & 8) {   // timing experiment: the loader alone (every other wave releases the whole ring and leaves)
         if (wave == 0) K::loader_main(p, l, lane);
         else fl_st(l.fl + FL_DONE + wave, 0xFFFFFFFFu);
         return;
     }
     if (p.trace && lane == 0) p.trace[((long long) blockIdx.x * 8 + wave) * 32 + 31] = (long long) __builtin_amdgcn_s_getreg(4 | (0 << 6) | (15 << 11));   // HW_ID[15:0]: wave, SIMD, pipe, CU, SH, SE
-    if (wave == 0) { if (R6_ROLES & 1) K::loader_main(p, l, lane); }
-    else if (wave == 1) { if (R6_ROLES & 2) K::comm_main(p, l, lane, base); }
-    else { if (R6_ROLES & 4) K::consumer_main(p, l, lane, wave, base); }
+    if (wave == 0) K::loader_main(p, l, lane);
+    else if (wave == 1) K::comm_main(p, l, lane, base);
+    else K::consumer_main(p, l, lane, wave, base);
     if (blockIdx.x == 0 && tid0 == 64) p.ctl[0] = base + (unsigned) p.n_layers * 8u;
 }
 
@@ -2073,7 +1888,7 @@ static const RingVariant g_ring_variants[] = {
     {FMT, 8, 4, 7, 3, k6_ring<FMT, 8, 4, 7, 3>},   /* D 4096, F 14336 (448 blocks: 7 steps, 1344 units), decay rank 128: RWKV-6 7B */ \
     {FMT, 5, 2, 5, 2, k6_ring<FMT, 5, 2, 5, 2>},   /* D 2560, F 8960 (280 blocks: 5 steps, 840 units), decay rank 64: RWKV-6 3B */ \
     {FMT, 4, 2, 4, 2, k6_ring<FMT, 4, 2, 4, 2>}    /* D 2048, F 7168 (224 blocks: 4 steps, 672 units), decay rank 64: RWKV-6 1.6B */
-#ifdef R6_ONLY_FMT   /* (register-budget experiments: one format, the 7B geometry) */
+#ifdef R6_ONLY_FMT
     {R6_ONLY_FMT, 8, 4, 7, 3, k6_ring<R6_ONLY_FMT, 8, 4, 7, 3>},
 #else
     RING_VARIANTS(T_Q4_0), RING_VARIANTS(T_Q4_1), RING_VARIANTS(T_Q5_0), RING_VARIANTS(T_Q5_1), RING_VARIANTS(T_Q8_0),

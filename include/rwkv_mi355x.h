@@ -335,6 +335,51 @@ RWKV_API bool rwkv_mi_batch_decode_until(struct rwkv_mi_batch * batch, const uin
 /* passes the last device loop of the batch enqueued (0 before the first) */
 RWKV_API size_t rwkv_mi_batch_last_loop_passes(const struct rwkv_mi_batch * batch);
 
+/* ---- The report: log-probs and top-N alternatives of every emitted token ----
+ * What serving APIs call logprobs / top_logprobs. A caller of the device loops could so far learn how likely an emitted token was only by leaving
+ * the loop (n_vocab floats per row and step to the host) or by a second pass with rwkv_mi_batch_score_ragged over what was emitted, and the
+ * alternatives not at all. The REPORT is an opt-in property of a batch, or of a context, beside a call's input, draw and repeat; off by default.
+ * While it is on, every call that EMITS a token -- a draw, or the greedy argmax of a loop -- records, for each emitted token of each row,
+ * from the MODEL'S logits l of that step (the unmodified logits logits_out returns: not the penalised or biased adj, not shaped by temperature
+ * or top_p):
+ *   chosen       = (float) ((double) l[token] - (m + log(S))),  m and S exactly those of the scoring calls above: the value is, bit for bit,
+ *                  the logprob rwkv_mi_batch_score_ragged / rwkv_mi_score_resident gives for the same logits with target = token (the two
+ *                  kernels share one body);
+ *   top_ids[k], top_logprobs[k], k < top_n <= RWKV_MI_TOP_MAX: the top_n logits that are not NaN, by value descending, then by index
+ *                  ascending, each with the same log-prob expression. A NaN never ranks; -inf ranks last among the rest; where fewer than
+ *                  top_n logits rank the remaining entries are RWKV_MI_NO_TOKEN / -INFINITY. Whenever some logit exceeds -inf, top_ids[0] is
+ *                  the token the greedy loops pick. The selection is exact and depends on the row's logits alone -- not on the other rows,
+ *                  the chunking or the run.
+ * A PENALISED OR BIASED ROW REPORTS THE MODEL'S DISTRIBUTION, not the one it was drawn from: its chosen token need not be among the top_n, and
+ * a token a bias forbids may be.
+ * With the report on, the emitted tokens, states, parities, draw counters and occurrence tables are bit for bit those of the same call with it
+ * off; with it off, no launch, allocation or copy is added.
+ * Covered: rwkv_mi_batch_eval_sample, _eval_ragged_sample and their _penalized forms (steps = 1, from each row's last-token logits); the three
+ * device loops, rwkv_mi_batch_decode_greedy included (steps = n_tokens); rwkv_mi_batch_decode_until (steps = the passes it enqueued,
+ * rwkv_mi_batch_last_loop_passes: row r's entries at j >= lens_out[r] are 0.0f / RWKV_MI_NO_TOKEN / -INFINITY; the step at which a row retires IS
+ * reported -- the stop token's log-prob -- and a retired row writes nothing afterwards); on a context rwkv_mi_sample, rwkv_mi_sample_penalized
+ * (rows = steps = 1), rwkv_mi_decode_sample and rwkv_mi_decode_sample_penalized (rows = 1, steps = n_tokens). rwkv_mi_decode_greedy picks its
+ * token inside the persistent launch and is NOT covered: greedy with a report is rwkv_mi_decode_sample at temperature 0.
+ * The report of a call stays readable until the next emitting call, the next set_logprobs, or free; calls that emit nothing (rwkv_mi_batch_eval,
+ * the scoring calls, ...) leave it alone, and so does a call that is rejected for its arguments. The device buffers are allocated by the
+ * first reporting call and grown to the largest since (RWKV_ERROR_ALLOC, nothing changed, when they cannot be); rwkv_mi_batch_free / rwkv_free
+ * release them.
+ * The calls below return false with RWKV_ERROR_ARGS and change nothing when top_n > RWKV_MI_TOP_MAX or top_n > n_vocab, when _shape or _store
+ * runs before any reporting call (or after a set_logprobs), when stride < steps, or when the context is a RWKV_MI_DEVICES chain. */
+#define RWKV_MI_TOP_MAX 20
+/* Turns the report on (with top_n alternatives per token; 0: the chosen token's log-prob only) or off. Ends the current report either way. */
+RWKV_API bool rwkv_mi_batch_set_logprobs(struct rwkv_mi_batch * batch, bool enabled, uint32_t top_n);
+/* The shape of the last reporting call: its rows, its steps, the top_n it ran with. Any pointer may be NULL. */
+RWKV_API bool rwkv_mi_batch_logprobs_shape(struct rwkv_mi_batch * batch, size_t * rows, size_t * steps, uint32_t * top_n);
+/* Copies the report to the host, rows in the last call's order, transposed like the loops' tokens_out. Each output may be NULL. */
+RWKV_API bool rwkv_mi_batch_logprobs_store(struct rwkv_mi_batch * batch, size_t stride, float * chosen_out /* [rows][stride] */,
+                                           uint32_t * top_ids_out /* [rows][stride][top_n] */, float * top_logprobs_out /* [rows][stride][top_n] */);
+/* The single context: the same three (rows = 1). */
+RWKV_API bool rwkv_mi_set_logprobs(struct rwkv_context * ctx, bool enabled, uint32_t top_n);
+RWKV_API bool rwkv_mi_logprobs_shape(struct rwkv_context * ctx, size_t * rows, size_t * steps, uint32_t * top_n);
+RWKV_API bool rwkv_mi_logprobs_store(struct rwkv_context * ctx, size_t stride, float * chosen_out /* [stride] */,
+                                     uint32_t * top_ids_out /* [stride][top_n] */, float * top_logprobs_out /* [stride][top_n] */);
+
 #if defined(__cplusplus)
 }
 #endif

@@ -16,6 +16,7 @@ from .rwkv_cpp import (  # noqa: F401
     SAMPLE_HOOKS_LIB_PATH,
     SampleParams,
     StopParams,
+    TOP_MAX,
     build_library,
     load_rwkv_shared_library,
     penalty_params,

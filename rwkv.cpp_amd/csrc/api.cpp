@@ -397,6 +397,107 @@ static bool ensure_sampler(rwkv_context * ctx) {
     return true;
 }
 
+// ---- the report of the emitted tokens (rwkv_mi_*set_logprobs / _logprobs_shape / _logprobs_store): what contexts and batches share ----
+
+static bool report_set(rwkv_context * ctx, LogprobReport & lp, bool enabled, uint32_t top_n) {
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, top_n <= RWKV_MI_TOP_MAX && (size_t) top_n <= (size_t) ctx->model->n_vocab(),
+                 "top_n (%" PRIu32 ") is above %d or above n_vocab", top_n, RWKV_MI_TOP_MAX);
+    lp.enabled = enabled;
+    lp.top_n = enabled ? top_n : 0;
+    lp.valid = false;
+    return true;
+}
+
+// buffers for `entries` = steps * rows records of the current top_n (new buffers first: a failure leaves the report as it was). The caller
+// has drained the stream the previous report was written on.
+static bool report_ensure(rwkv_context * ctx, LogprobReport & lp, size_t entries) {
+    const size_t top = entries * lp.top_n;
+    float * dc = nullptr, * dv = nullptr;
+    uint32_t * di = nullptr;
+    hipError_t e = hipSuccess;
+    if (entries > lp.cap) e = hipMalloc((void **) &dc, entries * sizeof(float));
+    if (e == hipSuccess && top > lp.cap_top) {
+        e = hipMalloc((void **) &di, top * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMalloc((void **) &dv, top * sizeof(float));
+    }
+    if (e != hipSuccess) { for (void * q : {(void *) dc, (void *) di, (void *) dv}) if (q) (void) hipFree(q); (void) hipGetLastError(); }
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the log-prob report of %zu tokens: %s", entries, hipGetErrorString(e));
+    if (dc) { if (lp.d_chosen) (void) hipFree(lp.d_chosen); lp.d_chosen = dc; lp.cap = entries; lp.valid = false; }
+    if (di) {
+        if (lp.d_ids) (void) hipFree(lp.d_ids);
+        if (lp.d_vals) (void) hipFree(lp.d_vals);
+        lp.d_ids = di; lp.d_vals = dv; lp.cap_top = top; lp.valid = false;
+    }
+    return true;
+}
+
+// what a reporting call that succeeded leaves: its shape and, per row, the steps the row wrote (lens == nullptr: all of them)
+static void report_done(LogprobReport & lp, size_t rows, size_t steps, const uint32_t * lens) {
+    lp.rows = rows; lp.steps = steps; lp.last_top_n = lp.top_n; lp.valid = true;
+    lp.lens.assign(rows, (uint32_t) steps);
+    for (size_t r = 0; lens && r < rows; r++) lp.lens[r] = lens[r];
+}
+
+static bool report_shape(rwkv_context * ctx, const LogprobReport & lp, size_t * rows, size_t * steps, uint32_t * top_n) {
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, lp.valid, "there is no log-prob report (no reporting call yet, or rwkv_mi_*set_logprobs since)");
+    if (rows) *rows = lp.rows;
+    if (steps) *steps = lp.steps;
+    if (top_n) *top_n = lp.last_top_n;
+    return true;
+}
+
+// [steps][rows] on the device -> [rows][stride] on the host, the way the loops' tokens_out is transposed; an entry behind a row's length
+// is 0 / RWKV_MI_NO_TOKEN / -inf
+static bool report_store(rwkv_context * ctx, const LogprobReport & lp, hipStream_t st, size_t stride, float * chosen_out, uint32_t * top_ids_out, float * top_logprobs_out) {
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, lp.valid, "there is no log-prob report (no reporting call yet, or rwkv_mi_*set_logprobs since)");
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, stride >= lp.steps, "stride (%zu) is less than the report's steps (%zu)", stride, lp.steps);
+    const size_t R = lp.rows, S = lp.steps, N = lp.last_top_n, E = R * S;
+    const bool tops = N > 0 && (top_ids_out || top_logprobs_out);
+    std::vector<float> hc(chosen_out ? E : 0), hv(tops && top_logprobs_out ? E * N : 0);
+    std::vector<uint32_t> hi(tops && top_ids_out ? E * N : 0);
+    if (!hc.empty()) HIP_CTX_OK(ctx, hipMemcpyAsync(hc.data(), lp.d_chosen, E * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (!hi.empty()) HIP_CTX_OK(ctx, hipMemcpyAsync(hi.data(), lp.d_ids, E * N * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (!hv.empty()) HIP_CTX_OK(ctx, hipMemcpyAsync(hv.data(), lp.d_vals, E * N * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_CTX_OK(ctx, hipStreamSynchronize(st));
+    for (size_t r = 0; r < R; r++)
+        for (size_t j = 0; j < stride; j++) {
+            const bool in = j < lp.lens[r];
+            const size_t src = j * R + r, dst = r * stride + j;
+            if (chosen_out) chosen_out[dst] = in ? hc[src] : 0.0f;
+            for (size_t k = 0; k < N; k++) {
+                if (top_ids_out) top_ids_out[dst * N + k] = in ? hi[src * N + k] : RWKV_MI_NO_TOKEN;
+                if (top_logprobs_out) top_logprobs_out[dst * N + k] = in ? hv[src * N + k] : -INFINITY;
+            }
+        }
+    return true;
+}
+
+RWKV_API bool rwkv_mi_set_logprobs(struct rwkv_context * ctx, bool enabled, uint32_t top_n) {
+    ctx->last_error = RWKV_ERROR_NONE;
+    RW_NO_PIPELINE(ctx, false);
+    return report_set(ctx, ctx->lp, enabled, top_n);
+}
+
+RWKV_API bool rwkv_mi_logprobs_shape(struct rwkv_context * ctx, size_t * rows, size_t * steps, uint32_t * top_n) {
+    ctx->last_error = RWKV_ERROR_NONE;
+    RW_NO_PIPELINE(ctx, false);
+    return report_shape(ctx, ctx->lp, rows, steps, top_n);
+}
+
+RWKV_API bool rwkv_mi_logprobs_store(struct rwkv_context * ctx, size_t stride, float * chosen_out, uint32_t * top_ids_out, float * top_logprobs_out) {
+    ctx->last_error = RWKV_ERROR_NONE;
+    RW_NO_PIPELINE(ctx, false);
+    HIP_CTX_OK(ctx, hipSetDevice(ctx->model->device));
+    return report_store(ctx, ctx->lp, ctx->stream, stride, chosen_out, top_ids_out, top_logprobs_out);
+}
+
+// the context's report buffers for a call of `steps` draws (nothing when the report is off)
+static bool ensure_report(rwkv_context * ctx, size_t steps) {
+    if (!ctx->lp.enabled) return true;
+    HIP_CTX_OK(ctx, hipStreamSynchronize(ctx->stream));
+    return report_ensure(ctx, ctx->lp, steps);
+}
+
 // ---- penalised sampling (rwkv_mi_*_penalized, rwkv_mi_*counts_*, rwkv_mi_*logit_bias_set): what contexts and batches share ----
 
 // the arguments of counts_add / logit_bias_set / a penalty (checked before anything changes; errors are reported on ctx)
@@ -533,15 +634,21 @@ static void launch_draw(rwkv_context * ctx, float temperature, float top_p, floa
     if (pen) launch_pen_sample(ctx->d_logits, n_vocab, temperature, top_p, u, seed, ctx->d_rng_counter, pen->presence, pen->frequency, pen->record, ctx->d_counts,
                                ctx->has_bias ? ctx->d_bias : nullptr, ctx->d_probs, out, hist, hist_pos, ctx->stream);
     else launch_sample(ctx->d_logits, n_vocab, temperature, top_p, u, seed, ctx->d_rng_counter, ctx->d_probs, out, hist, hist_pos, ctx->stream);
+    // the report of the token just written, slot hist_pos of the context's buffers (ensure_report has sized them)
+    const LogprobReport & lp = ctx->lp;
+    if (lp.enabled) launch_logprob_rows(ctx->d_logits, 1, n_vocab, out, (int) lp.top_n, lp.d_chosen + hist_pos, lp.d_ids + (size_t) hist_pos * lp.top_n,
+                                        lp.d_vals + (size_t) hist_pos * lp.top_n, nullptr, ctx->stream);
 }
 
 // rwkv_mi_sample / rwkv_mi_sample_penalized behind their argument checks
 static bool sample_once(rwkv_context * ctx, float temperature, float top_p, float u, uint64_t seed, const Penalty * pen, uint32_t * token_out) {
     HIP_CTX_OK(ctx, hipSetDevice(ctx->model->device));
-    if (!ensure_sampler(ctx) || (pen && !ensure_penalty(ctx))) return false;
+    if (!ensure_sampler(ctx) || (pen && !ensure_penalty(ctx)) || !ensure_report(ctx, 1)) return false;
+    ctx->lp.valid = false;
     launch_draw(ctx, temperature, top_p, u, seed, pen, ctx->d_next_token, nullptr, 0);
     HIP_CTX_OK(ctx, hipMemcpyAsync(token_out, ctx->d_next_token, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIP_CTX_OK(ctx, hipStreamSynchronize(ctx->stream));
+    if (ctx->lp.enabled) report_done(ctx->lp, 1, 1, nullptr);
     return true;
 }
 
@@ -551,6 +658,8 @@ static bool decode_sample_loop(rwkv_context * ctx, size_t n_tokens, float temper
                                uint32_t * tokens_out, float * elapsed_ms) {
     DevBuf<uint32_t> hist;
     HIP_CTX_OK(ctx, hist.alloc(n_tokens));
+    if (!ensure_report(ctx, n_tokens)) return false;
+    ctx->lp.valid = false;
     HIP_CTX_OK(ctx, hipStreamSynchronize(ctx->stream));
     HIP_CTX_OK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
     for (size_t i = 0; i < n_tokens; i++) {
@@ -562,6 +671,7 @@ static bool decode_sample_loop(rwkv_context * ctx, size_t n_tokens, float temper
     if (tokens_out) HIP_CTX_OK(ctx, hipMemcpyAsync(tokens_out, hist.p, n_tokens * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     if (!fetch_outputs(ctx, nullptr, nullptr)) return false;
     if (elapsed_ms) HIP_CTX_OK(ctx, hipEventElapsedTime(elapsed_ms, ctx->ev0, ctx->ev1));
+    if (ctx->lp.enabled) report_done(ctx->lp, 1, n_tokens, nullptr);
     return true;
 }
 
@@ -884,6 +994,7 @@ struct rwkv_mi_batch {
     StopTables stop{};                   // the device pointers of the current call
     size_t stop_off_lens = 0;            // where lens[n], reasons[n] start in both buffers
     size_t last_loop_passes = 0;
+    LogprobReport lp;                    // the report of the batch's emitting calls (rwkv_mi_batch_set_logprobs)
 
     float * slot_buf(size_t slot, int p) const { return states + ((size_t) p * n_slots + slot) * (size_t) state_len; }
 };
@@ -897,7 +1008,8 @@ static bool batch_fail_through(rwkv_mi_batch * B) { B->ctx->last_error |= B->run
 // What a batch call is: a point on three axes. The input -- one token per row, or a segment per row (lens); the draw -- none,
 // the sampler, or the penalised sampler; the repeat -- one pass (batch_pass), a device loop of n_tokens steps (batch_loop, where no draw
 // means the greedy argmax), or that loop with every row ending by itself (batch_until). Every entry point fills in this description and calls one
-// of the three bodies.
+// of the three bodies. The REPORT is a fourth property, the batch's own: a call that emits tokens -- a draw, or a loop's argmax --
+// records them when B->lp.enabled; the bodies branch on that and on `emits`, never on who called.
 enum class Draw { none, sample, penalized };
 struct BatchCall {
     const uint32_t * slots, * tokens;   // row i is slot slots[i] fed tokens[i] ...
@@ -924,6 +1036,21 @@ struct BatchCall {
     uint32_t * lens_out = nullptr;
     uint32_t * stopped_by_out = nullptr;
 };
+
+// the slot of step `step` of a call of n rows in the batch's report buffers (step 0: the buffers themselves)
+static RowReport batch_report(const rwkv_mi_batch * B, size_t n, size_t step) {
+    const LogprobReport & lp = B->lp;
+    return RowReport{lp.d_chosen + step * n, lp.d_ids + step * n * lp.top_n, lp.d_vals + step * n * lp.top_n, lp.top_n};
+}
+
+// the report buffers of an emitting call of `steps` steps (nothing when the report is off); the previous report ends here
+static bool batch_ensure_report(rwkv_mi_batch * B, size_t n, size_t steps) {
+    if (!B->lp.enabled) return true;
+    BATCH_HIP_OK(B, hipStreamSynchronize(B->run->stream));
+    if (!report_ensure(B->ctx, B->lp, steps * n)) return false;
+    B->lp.valid = false;
+    return true;
+}
 
 // n, slots, lens and tokens of a call: no slot changes when they are rejected. Row i feeds lens[i] consecutive tokens to slot slots[i]; the
 // form without lens has every length 1 and checks tokens[i] with its row. *T_out = the tokens of the pass.
@@ -1239,13 +1366,17 @@ static bool batch_pass(rwkv_mi_batch * B, const BatchCall & c) {
     BATCH_HIP_OK(B, hipSetDevice(ctx->model->device));
     if (!batch_ensure_draw(B, c)) return false;
     if (scoring && !ensure_score(run, (int64_t) T)) return batch_fail_through(B);
+    const bool report = drawn && B->lp.enabled;   // (a pass emits where it draws)
+    if (report && !batch_ensure_report(B, c.n, 1)) return false;
     if (!batch_upload_call(B, c, T, false)) return false;   // (drains the stream: the staging of the targets is free as well)
     if (c.logprobs_out) {
         memcpy(run->h_score_targets, c.targets, T * sizeof(uint32_t));
         BATCH_HIP_OK(B, hipMemcpyAsync(run->d_score_targets, run->h_score_targets, T * sizeof(uint32_t), hipMemcpyHostToDevice, run->stream));
     }
     // Row i's token lands in the batch's token word i (a ragged pass has read all T of them by then): the 4 n bytes that go back to the host.
-    const RowSampler sampler = batch_sampler(B, c, nullptr);
+    RowSampler sampler = batch_sampler(B, c, nullptr);
+    const RowReport rep = report ? batch_report(B, c.n, 0) : RowReport{};
+    if (report) sampler.report = &rep;
     // scoring is the ragged pass with the head on every token (engine.hip, ScorePass): T rows of log-probs / argmax in token order
     ScorePass sp;
     sp.targets = sp.logprobs = c.logprobs_out != nullptr;
@@ -1261,6 +1392,7 @@ static bool batch_pass(rwkv_mi_batch * B, const BatchCall & c) {
     BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));
     if (drawn) memcpy(c.sampled_out, run->h_tokens, c.n * sizeof(uint32_t));
     batch_flip(B, c);
+    if (report) report_done(B->lp, c.n, 1, nullptr);
     return true;
 }
 
@@ -1281,15 +1413,22 @@ static bool batch_loop(rwkv_mi_batch * B, const BatchCall & c, size_t n_tokens, 
     if (!batch_ensure_draw(B, c)) return false;
     DevBuf<uint32_t> hist;   // [n_tokens][n], freed on every exit
     BATCH_HIP_OK(B, hist.alloc(n_tokens * n));
+    const bool report = B->lp.enabled;   // (every step of a loop emits)
+    if (!batch_ensure_report(B, n, n_tokens)) return false;
     if (!batch_upload_call(B, c, T, true)) return false;
     if (c.draw == Draw::sample) launch_sample_seek_rows(B->d_srows, (int64_t) n, 0ull, run->stream);   // the named slots' streams start over
     BATCH_HIP_OK(B, hipEventRecord(run->ev0, run->stream));
     for (size_t i = 0; i < n_tokens; i++) {
         // step i reads the buffers step i - 1 wrote: the two row tables alternate; the token of each row -- sampled inside the pass's chain
         // bracket, or its argmax after it -- lands where its next embedding lookup reads it
-        const RowSampler sampler = batch_sampler(B, c, hist.p + i * n);
+        RowSampler sampler = batch_sampler(B, c, hist.p + i * n);
+        const RowReport rep = report ? batch_report(B, n, i) : RowReport{};
+        if (report) sampler.report = &rep;
         if (!forward_rows(run, B->d_rows + (i & 1) * B->n_slots, (int64_t) n, true, drawn ? &sampler : nullptr)) return batch_fail_drained(B);
-        if (!drawn) launch_argmax(run->d_logits, (int64_t) n, ctx->model->n_vocab(), run->d_tokens, hist.p + i * n, run->stream);
+        if (drawn) continue;
+        // the greedy argmax, and its report directly behind it: the event the device's next persistent launch waits on is recorded after both
+        launch_argmax(run->d_logits, (int64_t) n, ctx->model->n_vocab(), run->d_tokens, hist.p + i * n, run->stream);
+        if (report) launch_logprob_rows(run->d_logits, (int64_t) n, (int) ctx->model->n_vocab(), run->d_tokens, (int) rep.top_n, rep.chosen, rep.ids, rep.vals, nullptr, run->stream);
     }
     BATCH_HIP_OK(B, hipEventRecord(run->ev1, run->stream));
     std::vector<uint32_t> h(tokens_out ? n_tokens * n : 0);
@@ -1300,6 +1439,7 @@ static bool batch_loop(rwkv_mi_batch * B, const BatchCall & c, size_t n_tokens, 
         for (size_t i = 0; i < n_tokens; i++) tokens_out[r * n_tokens + i] = h[i * n + r];
     if (n_tokens & 1) batch_flip(B, c);
     B->last_loop_passes = n_tokens;
+    if (report) report_done(B->lp, n, n_tokens, nullptr);
     return true;
 }
 
@@ -1333,6 +1473,9 @@ static bool batch_until(rwkv_mi_batch * B, const BatchCall & c, uint32_t * token
     hipError_t he = hist.alloc(budget * n);
     if (he != hipSuccess) (void) hipGetLastError();
     RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, false, he == hipSuccess, "cannot allocate the history of %zu steps of %zu rows: %s", budget, n, hipGetErrorString(he));
+    const bool report = B->lp.enabled;   // (every step of a live row emits; a slot no row wrote is never read back: report_store fills behind lens)
+    if (!batch_ensure_report(B, n, budget)) return false;
+    const RowReport rep = report ? batch_report(B, n, 0) : RowReport{};
     if (!batch_upload_call(B, c, T, true)) return false;
     if (c.draw == Draw::sample) launch_sample_seek_rows(B->d_srows, (int64_t) n, 0ull, run->stream);   // the named slots' streams start over
     BATCH_HIP_OK(B, hipMemsetAsync(hist.p, 0xFF, budget * n * sizeof(uint32_t), run->stream));
@@ -1345,6 +1488,7 @@ static bool batch_until(rwkv_mi_batch * B, const BatchCall & c, uint32_t * token
             RowSampler sampler = batch_sampler(B, c, hist.p);
             if (c.draw == Draw::none) sampler.table = nullptr;   // (no draw: the greedy argmax)
             sampler.stop = &stop;
+            if (report) sampler.report = &rep;
             if (!forward_rows(run, used, (int64_t) n, true, &sampler)) return batch_fail_drained(B);
         }
         hipError_t e = hipMemcpyAsync(B->h_live_count + (b & 1), B->stop.live_count, sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream);
@@ -1371,6 +1515,7 @@ static bool batch_until(rwkv_mi_batch * B, const BatchCall & c, uint32_t * token
         for (size_t j = 0; tokens_out && j < c.stride; j++) tokens_out[r * c.stride + j] = j < len ? h[j * n + r] : RWKV_MI_NO_TOKEN;
         if (len & 1) B->parity[c.slots[r]] ^= 1;
     }
+    if (report) report_done(B->lp, n, passes, h_lens);
     return true;
 }
 
@@ -1399,6 +1544,7 @@ RWKV_API void rwkv_mi_batch_free(struct rwkv_mi_batch * B) {
     if (B->h_stop) (void) hipHostFree(B->h_stop);
     if (B->h_live_count) (void) hipHostFree(B->h_live_count);
     for (hipEvent_t ev : B->ev_block) if (ev) (void) hipEventDestroy(ev);
+    B->lp.release();
     batch_context_destroy(B->run);
     delete B;
 }
@@ -1642,5 +1788,21 @@ RWKV_API bool rwkv_mi_batch_decode_until(struct rwkv_mi_batch * B, const uint32_
 }
 
 RWKV_API size_t rwkv_mi_batch_last_loop_passes(const struct rwkv_mi_batch * B) { return B ? B->last_loop_passes : 0; }
+
+RWKV_API bool rwkv_mi_batch_set_logprobs(struct rwkv_mi_batch * B, bool enabled, uint32_t top_n) {
+    B->ctx->last_error = RWKV_ERROR_NONE;
+    return report_set(B->ctx, B->lp, enabled, top_n);
+}
+
+RWKV_API bool rwkv_mi_batch_logprobs_shape(struct rwkv_mi_batch * B, size_t * rows, size_t * steps, uint32_t * top_n) {
+    B->ctx->last_error = RWKV_ERROR_NONE;
+    return report_shape(B->ctx, B->lp, rows, steps, top_n);
+}
+
+RWKV_API bool rwkv_mi_batch_logprobs_store(struct rwkv_mi_batch * B, size_t stride, float * chosen_out, uint32_t * top_ids_out, float * top_logprobs_out) {
+    B->ctx->last_error = RWKV_ERROR_NONE;
+    BATCH_HIP_OK(B, hipSetDevice(B->ctx->model->device));
+    return report_store(B->ctx, B->lp, B->run->stream, stride, chosen_out, top_ids_out, top_logprobs_out);
+}
 
 }  // extern "C"

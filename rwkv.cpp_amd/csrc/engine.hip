@@ -274,6 +274,7 @@ void destroy_context(rwkv_context * ctx) {
     if (ctx->h_score_targets) (void) hipHostFree(ctx->h_score_targets);
     if (ctx->d_score_logprobs) (void) hipFree(ctx->d_score_logprobs);
     if (ctx->d_score_argmax) (void) hipFree(ctx->d_score_argmax);
+    ctx->lp.release();
     if (ctx->h_tokens) (void) hipHostFree(ctx->h_tokens);
     if (ctx->ev0) (void) hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void) hipEventDestroy(ctx->ev1);
@@ -853,6 +854,7 @@ void batch_context_destroy(rwkv_context * c) {
 }
 
 // The row sampler of a batch pass over the `rows` rows of ctx->d_logits: row r's token goes to ctx->d_tokens[r] (and to s.hist[r] when given).
+// Order within a step: the draw (or argmax), then the report of what it wrote (s.report), then the stop test.
 static void launch_row_sampler(rwkv_context * ctx, const RowSampler & s, int64_t rows) {
     const int n_vocab = (int) ctx->model->n_vocab();
     if (s.stop) {
@@ -862,11 +864,17 @@ static void launch_row_sampler(rwkv_context * ctx, const RowSampler & s, int64_t
         if (s.ptable) launch_pen_sample_rows_live(ctx->d_logits, rows, n_vocab, s.ptable, s.probs, ctx->d_tokens, hist, live, ctx->stream);
         else if (s.table) launch_sample_rows_live(ctx->d_logits, rows, n_vocab, s.table, s.probs, ctx->d_tokens, hist, live, ctx->stream);
         else launch_argmax_live(ctx->d_logits, rows, n_vocab, ctx->d_tokens, hist, live, ctx->stream);
+        if (s.report) {
+            const size_t at = (size_t) s.stop->step * (size_t) rows;
+            launch_logprob_rows(ctx->d_logits, rows, n_vocab, ctx->d_tokens, (int) s.report->top_n, s.report->chosen + at, s.report->ids + at * s.report->top_n,
+                                s.report->vals + at * s.report->top_n, live, ctx->stream);
+        }
         launch_stop_rows(s.stop->t, rows, s.hist, s.stop->step, s.stop->used, s.stop->other, ctx->stream);
         return;
     }
     if (s.ptable) launch_pen_sample_rows(ctx->d_logits, rows, n_vocab, s.ptable, s.probs, ctx->d_tokens, s.hist, ctx->stream);
     else launch_sample_rows(ctx->d_logits, rows, n_vocab, s.table, s.probs, ctx->d_tokens, s.hist, ctx->stream);
+    if (s.report) launch_logprob_rows(ctx->d_logits, rows, n_vocab, ctx->d_tokens, (int) s.report->top_n, s.report->chosen, s.report->ids, s.report->vals, nullptr, ctx->stream);
 }
 
 // One pass of T rows, row t = one token (ctx->d_tokens[t]) of the sequence whose state is d_rows[t]. Logits: ctx->d_logits[T][n_vocab].

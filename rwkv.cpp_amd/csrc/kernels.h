@@ -148,6 +148,11 @@ void launch_argmax_live(const float * logits, int64_t rows, int64_t n, uint32_t 
 //   logprobs[row] = (float) ((double) l[targets[row]] - (m + log(sum_j exp((double) l[j] - m)))),  m = the row maximum, the sum in float64 in a fixed order;
 // a row whose target is UINT32_MAX (or >= n) gets 0. targets, logprobs and argmax may each be nullptr (targets == nullptr: every logprob is 0).
 void launch_score_rows(const float * logits, int64_t rows, int n, const uint32_t * targets, float * logprobs, uint32_t * argmax, hipStream_t st);
+// The report of a draw (score.hip, k_logprob_rows): per row of logits[rows][n], chosen[row] = the log-prob above with target tokens[row] (the
+// word the draw has just written) and top_ids / top_lp [row][top_n] = the top_n logits that are not NaN by value descending, then index
+// ascending, with their log-probs (RWKV_MI_NO_TOKEN / -inf where fewer rank). live (may be nullptr): a row with live[row] == 0 writes nothing.
+void launch_logprob_rows(const float * logits, int64_t rows, int n, const uint32_t * tokens, int top_n, float * chosen, uint32_t * top_ids, float * top_lp,
+                         const uint32_t * live, hipStream_t st);
 
 // load-time transpose of att.time_maa_w2: [5][D][R] -> [5][R][D]
 void launch_transpose_w2(const float * src, float * dst, int64_t D, int64_t R, hipStream_t st);

@@ -154,6 +154,28 @@ bool    scan_stage_costs(const char * path, std::vector<uint64_t> & per_layer, u
 // The context (opaque to callers).
 // ---------------------------------------------------------------------------------------------------------------
 
+namespace rwkvmi {
+// The report of a context's or a batch's emitting calls (rwkv_mi_*set_logprobs): whether it is on and with how many alternatives; the device
+// buffers, laid out like the loops' history -- chosen[steps][rows], ids / vals [steps][rows][top_n] -- allocated by the first reporting call
+// and grown to the largest since; and what the last reporting call left in them (valid: there is one). lens[r]: the steps row r wrote.
+struct LogprobReport {
+    bool enabled = false;
+    uint32_t top_n = 0;
+    float * d_chosen = nullptr;
+    uint32_t * d_ids = nullptr;
+    float * d_vals = nullptr;
+    size_t cap = 0, cap_top = 0;   // entries of d_chosen; of d_ids and d_vals
+    bool valid = false;
+    size_t rows = 0, steps = 0;
+    uint32_t last_top_n = 0;
+    std::vector<uint32_t> lens;
+    void release() {
+        for (void * p : {(void *) d_chosen, (void *) d_ids, (void *) d_vals}) if (p) (void) hipFree(p);
+        d_chosen = nullptr; d_ids = nullptr; d_vals = nullptr; cap = cap_top = 0; valid = false;
+    }
+};
+}  // namespace rwkvmi
+
 struct rwkv_context {
     rwkvmi::Model * model = nullptr;
     uint32_t n_threads = 0;
@@ -198,6 +220,7 @@ struct rwkv_context {
     float *    d_score_logprobs = nullptr;
     uint32_t * d_score_argmax = nullptr;
     int64_t    score_cap = 0;
+    rwkvmi::LogprobReport lp;                     // the report of the context's draws (rwkv_mi_set_logprobs)
 
     // pinned host staging for tokens / logits
     uint32_t * h_tokens = nullptr;
@@ -275,8 +298,12 @@ void batch_context_destroy(rwkv_context * c);
 // (ptable: the penalised row table; when given, launch_pen_sample_rows takes the place of launch_sample_rows and `table` is not read)
 // stop: the pass is step `step` of rwkv_mi_batch_decode_until -- the draw (with neither table: the greedy argmax) runs behind the live words and
 // launch_stop_rows follows it, both inside the pass's place in the chain; hist is then the WHOLE history [step][T] and step's row is written
+// report: when given, launch_logprob_rows follows the draw (and precedes the stop test) on the tokens it wrote: the pointers are the step's slot of
+// the report buffers -- with stop, as hist, the WHOLE buffers, and step's slot is written behind the live words
 struct RowStop { StopTables t; uint32_t step; RowState * used, * other; };
-struct RowSampler { const SampleRow * table; float * probs; uint32_t * hist; const PenaltyRow * ptable = nullptr; const RowStop * stop = nullptr; };
+struct RowReport { float * chosen; uint32_t * ids; float * vals; uint32_t top_n; };
+struct RowSampler { const SampleRow * table; float * probs; uint32_t * hist; const PenaltyRow * ptable = nullptr; const RowStop * stop = nullptr;
+                    const RowReport * report = nullptr; };
 bool forward_rows(rwkv_context * ctx, const RowState * d_rows, int64_t T, bool want_logits, const RowSampler * sample = nullptr);
 
 // Ragged batch pass: row i of the call is a SEGMENT, tokens [t0, t1) of the pass, consecutive tokens of one slot's sequence.

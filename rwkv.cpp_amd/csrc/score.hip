@@ -13,21 +13,21 @@
 // registers a 1024-thread workgroup leaves, but only for rows of at most 65536 logits and with the f64 exp's own registers on top; the
 // second read of a 256 KB row comes from L2 / the memory-side cache the head product has just written, and the kernel's time is the
 // rows * n_vocab float64 exps either way (about 1 % of the head product it follows).
+// k_logprob_rows (rwkv_mi_*set_logprobs) is the same reduction for the token a draw has just emitted, plus the row's top-N: see below.
 #include "kdev.h"
 #include "model.h"
 
 namespace rwkvmi {
 
-__global__ __launch_bounds__(1024) void k_score_rows(const float * __restrict__ logits_all, int n, const uint32_t * __restrict__ targets /* may be NULL */,
-                                                     float * __restrict__ logprobs /* may be NULL */, uint32_t * __restrict__ argmax /* may be NULL */) {
+// One body, several entry points (the convention of sampling.hip and kernels.hip): k_score_rows and k_logprob_rows both reduce a row through
+// these two functions, so the log-prob a draw reports for its token is, bit for bit, the one k_score_rows gives that row with that target.
+
+// The row maximum and its first index (k_argmax). Thread 0 returns the index (0x7fffffff when nothing compares greater than -inf) and has
+// written the maximum to *l_m; the other threads read it behind the barrier score_row_lse starts with.
+__device__ __forceinline__ int score_row_max(const float * __restrict__ logits, int n, float * l_m) {
     __shared__ float l_v[16];
     __shared__ int l_i[16];
-    __shared__ double l_s[16];
-    __shared__ float l_m;
-    const int64_t row = blockIdx.x;
-    const float * __restrict__ logits = logits_all + row * (int64_t) n;
     const int NT = blockDim.x;
-    // ---- maximum and its first index (k_argmax) ----
     float best = -INFINITY;
     int bi = 0x7fffffff;
     int i = threadIdx.x;
@@ -54,20 +54,21 @@ __global__ __launch_bounds__(1024) void k_score_rows(const float * __restrict__ 
     if (threadIdx.x == 0) {
         for (int w = 1; w < (NT >> 6); w++)
             if (l_v[w] > best || (l_v[w] == best && l_i[w] < bi)) { best = l_v[w]; bi = l_i[w]; }
-        l_m = best;
-        if (argmax) argmax[row] = bi == 0x7fffffff ? 0u : (uint32_t) bi;
+        *l_m = best;
     }
-    if (!logprobs) return;
-    // ---- log-probability of the target (the branch is uniform over the workgroup) ----
-    const uint32_t target = targets ? targets[row] : UINT32_MAX;
-    if (target >= (uint32_t) n) {   // RWKV_MI_NO_TARGET (an index behind the row is never read)
-        if (threadIdx.x == 0) logprobs[row] = 0.0f;
-        return;
-    }
+    return bi;
+}
+
+// m + log(S), S = sum_j exp((double) l[j] - m) in the fixed order of the file's head; the value is thread 0's (the others return 0).
+// Called by the whole workgroup after score_row_max.
+__device__ __forceinline__ double score_row_lse(const float * __restrict__ logits, int n, const float * l_m) {
+    __shared__ double l_s[16];
+    const int NT = blockDim.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     __syncthreads();
-    const double m = (double) l_m;
+    const double m = (double) *l_m;
     double acc = 0.0;
-    i = threadIdx.x;
+    int i = threadIdx.x;
     for (; i + 3 * NT < n; i += 4 * NT) {   // 4 loads in flight per trip, added in the order of j
         float v[4];
 #pragma unroll
@@ -80,15 +81,114 @@ __global__ __launch_bounds__(1024) void k_score_rows(const float * __restrict__ 
     for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, WAVE);
     if (lane == 0) l_s[wave] = acc;
     __syncthreads();
-    if (threadIdx.x == 0) {
-        double S = 0.0;
-        for (int w = 0; w < (NT >> 6); w++) S += l_s[w];
-        logprobs[row] = (float) ((double) logits[target] - (m + log(S)));
+    if (threadIdx.x != 0) return 0.0;
+    double S = 0.0;
+    for (int w = 0; w < (NT >> 6); w++) S += l_s[w];
+    return m + log(S);
+}
+
+// the log-prob of a logit of the row, rounded to f32 once
+__device__ __forceinline__ float score_logprob(float l, double lse) { return (float) ((double) l - lse); }
+
+__global__ __launch_bounds__(1024) void k_score_rows(const float * __restrict__ logits_all, int n, const uint32_t * __restrict__ targets /* may be NULL */,
+                                                     float * __restrict__ logprobs /* may be NULL */, uint32_t * __restrict__ argmax /* may be NULL */) {
+    __shared__ float l_m;
+    const int64_t row = blockIdx.x;
+    const float * __restrict__ logits = logits_all + row * (int64_t) n;
+    const int bi = score_row_max(logits, n, &l_m);
+    if (threadIdx.x == 0 && argmax) argmax[row] = bi == 0x7fffffff ? 0u : (uint32_t) bi;
+    if (!logprobs) return;
+    // ---- log-probability of the target (the branch is uniform over the workgroup) ----
+    const uint32_t target = targets ? targets[row] : UINT32_MAX;
+    if (target >= (uint32_t) n) {   // RWKV_MI_NO_TARGET (an index behind the row is never read)
+        if (threadIdx.x == 0) logprobs[row] = 0.0f;
+        return;
     }
+    const double lse = score_row_lse(logits, n, &l_m);
+    if (threadIdx.x == 0) logprobs[row] = score_logprob(logits[target], lse);
+}
+
+// ---- the report of a draw (rwkv_mi_*set_logprobs): the log-prob of the token a row has just emitted and the row's top_n alternatives ----
+// Where a logit ranks: by value descending, then by index ascending; a NaN never ranks (key 0), -inf ranks last among the rest, -0 ranks
+// as +0. The key is the logit's bit pattern made monotone in the upper word and the complement of the index in the lower one: the keys
+// of a row are distinct, a larger key ranks earlier, and the largest key of all is the token k_argmax picks.
+__device__ __forceinline__ unsigned long long rank_key(float v, int j) {
+    if (v != v) return 0ull;
+    if (v == 0.0f) v = 0.0f;
+    uint32_t u = __float_as_uint(v);
+    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return ((unsigned long long) u << 32) | (unsigned long long) (0xFFFFFFFFu - (uint32_t) j);
+}
+
+// One body for k_logprob_rows and its live form. chosen = the score of the row's token (the word the draw has just written), by the two
+// functions k_score_rows is made of. Then top_n sweeps over the row: sweep k finds the largest key below the key sweep k - 1 found --
+// per thread over j = i, i + 1024, ..., the 64 lanes by the xor butterfly, the waves through LDS (two buffers in turn: one barrier per
+// sweep). A maximum of distinct integers is the same in any order, so the selection is exact and depends on the row's logits alone; no
+// atomics. A sweep that finds nothing ends the list: the remaining entries are RWKV_MI_NO_TOKEN / -inf.
+// Cost: the row is read 2 + top_n times, from L2 after the first; the float64 exps of the sum are one read's worth of 64 per thread.
+__device__ __forceinline__ void logprob_row_body(const float * __restrict__ logits, int n, uint32_t token, int top_n,
+                                                 float * __restrict__ chosen, uint32_t * __restrict__ top_ids, float * __restrict__ top_lp) {
+    __shared__ float l_m;
+    __shared__ unsigned long long l_k[2][16];
+    (void) score_row_max(logits, n, &l_m);
+    const double lse = score_row_lse(logits, n, &l_m);
+    const int tid = threadIdx.x, NT = blockDim.x;
+    if (tid == 0) *chosen = token < (uint32_t) n ? score_logprob(logits[token], lse) : 0.0f;   // (an index behind the row is never read)
+    unsigned long long bound = ~0ull;
+    int k = 0;
+    for (; k < top_n; k++) {
+        unsigned long long best = 0ull;
+        int i = tid;
+        for (; i + 7 * NT < n; i += 8 * NT) {   // 8 loads in flight per trip
+            float v[8];
+#pragma unroll
+            for (int u = 0; u < 8; u++) v[u] = logits[i + u * NT];
+#pragma unroll
+            for (int u = 0; u < 8; u++) { const unsigned long long key = rank_key(v[u], i + u * NT); if (key < bound && key > best) best = key; }
+        }
+        for (; i < n; i += NT) { const unsigned long long key = rank_key(logits[i], i); if (key < bound && key > best) best = key; }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { const unsigned long long ok = __shfl_xor(best, o, WAVE); if (ok > best) best = ok; }
+        if ((tid & 63) == 0) l_k[k & 1][tid >> 6] = best;
+        __syncthreads();
+        for (int w = 0; w < (NT >> 6); w++) { const unsigned long long wk = l_k[k & 1][w]; if (wk > best) best = wk; }
+        if (best == 0ull) break;   // (uniform: every thread holds the workgroup's maximum)
+        bound = best;
+        if (tid == 0) {
+            const uint32_t id = 0xFFFFFFFFu - (uint32_t) (best & 0xFFFFFFFFull);
+            top_ids[k] = id;
+            top_lp[k] = score_logprob(logits[id], lse);
+        }
+    }
+    if (tid == 0) for (; k < top_n; k++) { top_ids[k] = UINT32_MAX; top_lp[k] = -INFINITY; }
+}
+
+// Row form: grid = rows, one workgroup per row; row r's token is tokens[r], its record goes to chosen[r], top_ids[r][top_n], top_lp[r][top_n].
+__global__ __launch_bounds__(1024) void k_logprob_rows(const float * __restrict__ logits_all, int n, const uint32_t * __restrict__ tokens, int top_n,
+                                                       float * __restrict__ chosen, uint32_t * __restrict__ top_ids, float * __restrict__ top_lp) {
+    const size_t r = blockIdx.x;
+    logprob_row_body(logits_all + r * (size_t) n, n, tokens[r], top_n, chosen + r, top_ids + r * (size_t) top_n, top_lp + r * (size_t) top_n);
+}
+
+// ... and behind the row's LIVE WORD (rwkv_mi_batch_decode_until; the pattern of k_sample_rows_live): a retired row writes nothing. The launch
+// sits between the draw and k_stop_rows, so the step at which a row retires is reported. The whole workgroup takes the branch together.
+__global__ __launch_bounds__(1024) void k_logprob_rows_live(const float * __restrict__ logits_all, int n, const uint32_t * __restrict__ tokens, int top_n,
+                                                            float * __restrict__ chosen, uint32_t * __restrict__ top_ids, float * __restrict__ top_lp,
+                                                            const uint32_t * __restrict__ live) {
+    const size_t r = blockIdx.x;
+    if (!live[r]) return;
+    logprob_row_body(logits_all + r * (size_t) n, n, tokens[r], top_n, chosen + r, top_ids + r * (size_t) top_n, top_lp + r * (size_t) top_n);
 }
 
 void launch_score_rows(const float * logits, int64_t rows, int n, const uint32_t * targets, float * logprobs, uint32_t * argmax, hipStream_t st) {
     if (rows > 0 && (logprobs || argmax)) hipLaunchKernelGGL(k_score_rows, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, targets, logprobs, argmax);
+}
+
+void launch_logprob_rows(const float * logits, int64_t rows, int n, const uint32_t * tokens, int top_n, float * chosen, uint32_t * top_ids, float * top_lp,
+                         const uint32_t * live, hipStream_t st) {
+    if (rows <= 0) return;
+    if (live) hipLaunchKernelGGL(k_logprob_rows_live, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, tokens, top_n, chosen, top_ids, top_lp, live);
+    else hipLaunchKernelGGL(k_logprob_rows, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, tokens, top_n, chosen, top_ids, top_lp);
 }
 
 }  // namespace rwkvmi

@@ -1,10 +1,11 @@
-// testhooks_sample.cpp -- the sampler's entry point for tests/ ONLY (include/rwkv_testhooks_sample.h) and the scoring kernel's
-// (include/rwkv_testhooks_score.h). `make` links it with every product
+// testhooks_sample.cpp -- the sampler's entry point for tests/ ONLY (include/rwkv_testhooks_sample.h), the scoring kernel's
+// (include/rwkv_testhooks_score.h) and the report kernel's (include/rwkv_testhooks_logprobs.h). `make` links it with every product
 // object into a third library, lib/librwkv_testhooks_sample.so; neither librwkv.so nor librwkv_testhooks.so carries it.
 #include "model.h"
 #include "rwkv_mi355x.h"
 #include "rwkv_testhooks_sample.h"
 #include "rwkv_testhooks_score.h"
+#include "rwkv_testhooks_logprobs.h"
 
 #include <vector>
 
@@ -63,6 +64,33 @@ RWKV_API bool rwkv_test_score_rows(const float * logits, int64_t rows, int64_t n
              (!argmax_out || hipMemcpy(argmax_out, d_am, R * 4, hipMemcpyDeviceToHost) == hipSuccess);
     }
     for (void * p : {(void *) d_logits, (void *) d_lp, (void *) d_tgt, (void *) d_am}) if (p) (void) hipFree(p);
+    RW_CHECK(RWKV_ERROR_GRAPH, false, ok, "HIP error: %s", hipGetErrorString(hipGetLastError()));
+    return true;
+}
+
+// Test hook: the report kernel on standalone logits, row r's emitted token tokens[r].
+RWKV_API bool rwkv_test_logprob_rows(const float * logits, int64_t rows, int64_t n_vocab, const uint32_t * tokens, uint32_t top_n,
+                                     float * chosen_out, uint32_t * top_ids_out, float * top_logprobs_out) {
+    g_last_error = RWKV_ERROR_NONE;
+    RW_CHECK(RWKV_ERROR_ARGS, false, logits && tokens && rows > 0 && rows <= 65535 && n_vocab > 0 && n_vocab <= (int64_t) 1 << 24 &&
+             top_n <= RWKV_MI_TOP_MAX && (int64_t) top_n <= n_vocab, "bad arguments");
+    for (int64_t r = 0; r < rows; r++) RW_CHECK(RWKV_ERROR_ARGS, false, (int64_t) tokens[r] < n_vocab, "token %lld is out of range", (long long) r);
+    const size_t R = (size_t) rows, V = (size_t) n_vocab, N = top_n ? top_n : 1;   // (top_n == 0: one unused word per row)
+    float * d_logits = nullptr, * d_ch = nullptr, * d_lp = nullptr;
+    uint32_t * d_tok = nullptr, * d_ids = nullptr;
+    bool ok = hipMalloc((void **) &d_logits, R * V * 4) == hipSuccess && hipMalloc((void **) &d_ch, R * 4) == hipSuccess &&
+              hipMalloc((void **) &d_tok, R * 4) == hipSuccess && hipMalloc((void **) &d_ids, R * N * 4) == hipSuccess &&
+              hipMalloc((void **) &d_lp, R * N * 4) == hipSuccess &&
+              hipMemcpy(d_logits, logits, R * V * 4, hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(d_tok, tokens, R * 4, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok) {
+        launch_logprob_rows(d_logits, rows, (int) n_vocab, d_tok, (int) top_n, d_ch, d_ids, d_lp, nullptr, nullptr);
+        ok = hipDeviceSynchronize() == hipSuccess &&
+             (!chosen_out || hipMemcpy(chosen_out, d_ch, R * 4, hipMemcpyDeviceToHost) == hipSuccess) &&
+             (!top_ids_out || !top_n || hipMemcpy(top_ids_out, d_ids, R * top_n * 4, hipMemcpyDeviceToHost) == hipSuccess) &&
+             (!top_logprobs_out || !top_n || hipMemcpy(top_logprobs_out, d_lp, R * top_n * 4, hipMemcpyDeviceToHost) == hipSuccess);
+    }
+    for (void * p : {(void *) d_logits, (void *) d_ch, (void *) d_tok, (void *) d_ids, (void *) d_lp}) if (p) (void) hipFree(p);
     RW_CHECK(RWKV_ERROR_GRAPH, false, ok, "HIP error: %s", hipGetErrorString(hipGetLastError()));
     return true;
 }

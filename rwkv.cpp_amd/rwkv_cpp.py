@@ -29,6 +29,9 @@ PENALTY_SYMBOLS = ("rwkv_mi_batch_counts_reset", "rwkv_mi_batch_counts_add", "rw
                    "rwkv_mi_sample_penalized", "rwkv_mi_decode_sample_penalized")
 SCORE_SYMBOLS = ("rwkv_mi_score_resident", "rwkv_mi_batch_score_ragged")
 UNTIL_SYMBOLS = ("rwkv_mi_batch_decode_until", "rwkv_mi_batch_last_loop_passes")
+LOGPROBS_SYMBOLS = ("rwkv_mi_batch_set_logprobs", "rwkv_mi_batch_logprobs_shape", "rwkv_mi_batch_logprobs_store",
+                    "rwkv_mi_set_logprobs", "rwkv_mi_logprobs_shape", "rwkv_mi_logprobs_store")
+TOP_MAX = 20             # RWKV_MI_TOP_MAX: the most alternatives a report holds per token
 NO_TARGET = 0xFFFFFFFF   # RWKV_MI_NO_TARGET: a position that is not scored (its log-prob is 0)
 NO_TOKEN = 0xFFFFFFFF    # RWKV_MI_NO_TOKEN: no token (past a row's length), no stop sequence (the budget ended the row)
 STOP_MAX_SEQS = 16       # RWKV_MI_STOP_MAX_SEQS
@@ -248,6 +251,18 @@ class RWKVSharedLibrary:
             L.rwkv_mi_batch_decode_until.restype = ctypes.c_bool
             L.rwkv_mi_batch_last_loop_passes.argtypes = [c_batch]
             L.rwkv_mi_batch_last_loop_passes.restype = ctypes.c_size_t
+        # the report: log-probs and top-N alternatives of every emitted token
+        if hasattr(L, "rwkv_mi_batch_set_logprobs"):   # (absent from older A/B builds loaded through RWKV_LIB_DIR)
+            P_SIZE = ctypes.POINTER(ctypes.c_size_t)
+            for handle, prefix in ((c_batch, "rwkv_mi_batch_"), (c_ctx, "rwkv_mi_")):
+                getattr(L, prefix + "set_logprobs").argtypes = [handle, ctypes.c_bool, ctypes.c_uint32]
+                getattr(L, prefix + "logprobs_shape").argtypes = [handle, P_SIZE, P_SIZE, P_UINT32]
+                getattr(L, prefix + "logprobs_store").argtypes = [handle, ctypes.c_size_t, P_FLOAT, P_UINT32, P_FLOAT]
+            for name in LOGPROBS_SYMBOLS:
+                getattr(L, name).restype = ctypes.c_bool
+        if hasattr(L, "rwkv_test_logprob_rows"):   # (librwkv_testhooks_sample.so only)
+            L.rwkv_test_logprob_rows.argtypes = [P_FLOAT, ctypes.c_int64, ctypes.c_int64, P_UINT32, ctypes.c_uint32, P_FLOAT, P_UINT32, P_FLOAT]
+            L.rwkv_test_logprob_rows.restype = ctypes.c_bool
         if hasattr(L, "rwkv_test_score_rows"):   # (librwkv_testhooks_sample.so only)
             L.rwkv_test_score_rows.argtypes = [P_FLOAT, ctypes.c_int64, ctypes.c_int64, P_UINT32, P_FLOAT, P_UINT32]
             L.rwkv_test_score_rows.restype = ctypes.c_bool
@@ -328,6 +343,22 @@ class RWKVSharedLibrary:
 
 def load_rwkv_shared_library() -> RWKVSharedLibrary:
     return RWKVSharedLibrary(LIB_PATH)
+
+
+def _report(L, prefix: str, handle):
+    """The last report of a batch or a context (rwkv_mi_*logprobs_shape / _store) as (chosen [rows][steps] float32, top_ids [rows][steps][top_n]
+    uint32, top_logprobs [rows][steps][top_n] float32); None when the library refuses (no report yet)."""
+    rows, steps, top_n = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_uint32(0)
+    if not getattr(L, prefix + "logprobs_shape")(handle, ctypes.byref(rows), ctypes.byref(steps), ctypes.byref(top_n)):
+        return None
+    r, s, k = int(rows.value), int(steps.value), int(top_n.value)
+    chosen = np.empty((r, s), dtype=np.float32)
+    ids = np.empty((r, s, k), dtype=np.uint32)
+    vals = np.empty((r, s, k), dtype=np.float32)
+    if not getattr(L, prefix + "logprobs_store")(handle, s, ctypes.cast(_ptr(chosen), P_FLOAT), ctypes.cast(_ptr(ids) if k else 0, P_UINT32),
+                                                 ctypes.cast(_ptr(vals) if k else 0, P_FLOAT)):
+        return None
+    return chosen, ids, vals
 
 
 def _ptr(a: Optional[np.ndarray]) -> int:
@@ -556,6 +587,22 @@ class RWKVModel:
         self._mi("rwkv_mi_decode_sample_penalized", first_token, n_tokens, temperature, top_p, seed, presence, frequency,
                  ctypes.cast(out.ctypes.data, P_UINT32), ctypes.byref(ms))
         return out, float(ms.value)
+
+    # --- the report: log-probs and top-N alternatives of every emitted token (include/rwkv_mi355x.h) ---
+
+    def set_logprobs(self, top_n: int = 0, enabled: bool = True) -> None:
+        """Turns the report of the context's draws (sample, sample_penalized, decode_sample, decode_sample_penalized) on, with top_n <= TOP_MAX
+        alternatives per token, or off. decode_greedy is not covered: greedy with a report is decode_sample at temperature 0."""
+        self._mi("rwkv_mi_set_logprobs", bool(enabled), int(top_n))
+
+    def logprobs(self):
+        """The report of the last draw or loop: (chosen [1][steps], top_ids [1][steps][top_n], top_logprobs [1][steps][top_n]), taken from the
+        model's logits (not the penalised ones); chosen equals score_resident's log-prob of the emitted token, bit for bit."""
+        out = _report(self._library.library, "rwkv_mi_", self._ctx.ptr)
+        if out is None:
+            self.last_error = self._library.rwkv_get_last_error(self._ctx)
+            raise ValueError(f"rwkv_mi_logprobs_store failed (error flags {self.last_error})")
+        return out
 
     def profile_decode(self, first_token: int, n_tokens: int) -> dict:
         out = (ctypes.c_double * 4)()
@@ -913,6 +960,23 @@ class RWKVBatch:
                                                   ctypes.byref(ms)):
             self._fail("rwkv_mi_batch_decode_until")
         return [out[i, : int(lens[i])].copy() for i in range(n)], why, float(ms.value)
+
+    # --- the report: log-probs and top-N alternatives of every emitted token (include/rwkv_mi355x.h) ---
+
+    def set_logprobs(self, top_n: int = 0, enabled: bool = True) -> None:
+        """Turns the report on, with top_n <= TOP_MAX alternatives per token, or off. While it is on, every call that emits tokens (the sampled
+        passes, the device loops -- the greedy one included -- and decode_until) records each emitted token's log-prob and the top_n of its step."""
+        if not self._L.rwkv_mi_batch_set_logprobs(self._ptr, bool(enabled), int(top_n)):
+            self._fail("rwkv_mi_batch_set_logprobs")
+
+    def logprobs(self):
+        """The report of the last emitting call, rows in its order: (chosen [rows][steps], top_ids [rows][steps][top_n], top_logprobs
+        [rows][steps][top_n]), from the MODEL'S logits (a penalised or biased row's token need not be among its top_n). chosen equals
+        score_ragged's log-prob of the emitted token, bit for bit. After decode_until a row's entries behind its length are 0 / NO_TOKEN / -inf."""
+        out = _report(self._L, "rwkv_mi_batch_", self._ptr)
+        if out is None:
+            self._fail("rwkv_mi_batch_logprobs_store")
+        return out
 
     def last_loop_passes(self) -> int:
         """Passes the batch's last device loop enqueued (decode_until stops at most two blocks after its last row has retired)."""

@@ -37,6 +37,13 @@ process, HIP events around each device loop, the smallest of --reps runs, --toke
   mode until_half_retire  (b) every second row retires at a quarter of the budget, against (a) at the default block: what dead rows cost
   mode until_all_retire   (c) every row retires at a quarter of the budget, against the plain loop of the full budget, with last_loop_passes
   mode until_eval_sample  the way without either loop: one synchronising rwkv_mi_batch_eval_sample call per token, host clock
+
+--sample --logprobs N[,N...] times the sampled loop (temperature 1.0, top-p 0.8, seed = row) with and without the report of the emitted tokens
+(rwkv_mi_batch_set_logprobs) in the same process, HIP events around each device loop, the smallest of --reps runs, --tokens steps, for every
+top_n of the list; records also go to --out:
+  mode logprobs_report   ms per step with the report at this top_n, the same run's step without it, and their difference
+  mode logprobs_host     the way without it: RWKVBatch.eval with the logits to the host, then a float64 log-softmax and np.argpartition for
+                         the largest top_n of the list on each row, the token taken as its argmax; host clock around the loop
 """
 import argparse
 import json
@@ -209,6 +216,70 @@ def until(pkg, m, args):
         sink.close()
 
 
+def logprobs(pkg, m, args):
+    import numpy as np
+    V = m.n_vocab
+    sink = open(args.out, "a") if args.out else None
+    steps = args.tokens
+    tops = [int(x) for x in args.logprobs.split(",")]
+
+    def emit(rec):
+        rec.update({"steps": steps, "reps": args.reps, "temperature": 1.0, "top_p": 0.8, "config": args.config, "dtype": args.dtype})
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if sink:
+            sink.write(line + "\n")
+            sink.flush()
+
+    ns = [int(x) for x in args.n.split(",")]
+    b = pkg.RWKVBatch(m, max(ns))
+    for n in ns:
+        slots = list(range(n))
+        first = [(7 * i + 1) % V for i in slots]
+
+        def best(run):
+            out = []
+            for k in range(args.reps + 1):   # (run 0: warm-up -- buffers of the first call, tile-major weight images)
+                for s in slots:
+                    b.state_load(s, None)
+                out.append(run())
+            return min(out[1:])
+
+        b.set_logprobs(enabled=False)
+        plain_ms = best(lambda: b.decode_sample(slots, first, steps, 1.0, 0.8, slots)[1])
+        for top_n in tops:
+            b.set_logprobs(top_n)
+            rep_ms = best(lambda: b.decode_sample(slots, first, steps, 1.0, 0.8, slots)[1])
+            t0 = time.perf_counter()
+            b.logprobs()
+            store_ms = (time.perf_counter() - t0) * 1e3
+            emit({"mode": "logprobs_report", "n": n, "top_n": top_n, "ms_per_step": round(rep_ms / steps, 4), "plain_ms_per_step": round(plain_ms / steps, 4),
+                  "report_ms_per_step": round((rep_ms - plain_ms) / steps, 4), "report_over_plain": round(rep_ms / plain_ms, 4),
+                  "store_ms_per_call": round(store_ms, 3), "report_bytes_per_step": 4 * n * (1 + 2 * top_n)})
+        b.set_logprobs(enabled=False)
+        top = max(tops)
+
+        def host():
+            toks = list(first)
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                lg = b.eval(slots, toks).astype(np.float64)
+                mx = lg.max(axis=1, keepdims=True)
+                lp = lg - (mx + np.log(np.exp(lg - mx).sum(axis=1, keepdims=True)))
+                if top:
+                    part = np.argpartition(-lp, top - 1, axis=1)[:, :top]
+                    np.take_along_axis(lp, part, axis=1)
+                toks = lp.argmax(axis=1).tolist()
+            return (time.perf_counter() - t0) * 1e3
+
+        host_ms = best(host)
+        emit({"mode": "logprobs_host", "n": n, "top_n": top, "ms_per_step": round(host_ms / steps, 4), "plain_ms_per_step": round(plain_ms / steps, 4),
+              "host_over_plain": round(host_ms / plain_ms, 2), "logits_bytes_per_step": 4 * n * V})
+    b.free()
+    if sink:
+        sink.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("model_path")
@@ -221,8 +292,10 @@ def main():
     ap.add_argument("--penalties", action="store_true", help="with --sample: also time the penalised sampling loop, on the device and through the host")
     ap.add_argument("--ragged", action="store_true", help="time the ragged pass: prompt ingestion and joining a decode step (see above)")
     ap.add_argument("--until", action="store_true", help="time rwkv_mi_batch_decode_until against the plain sampled loop (see above)")
-    ap.add_argument("--reps", type=int, default=3, help="--ragged, --until: timed runs of each shape (the smallest is reported)")
-    ap.add_argument("--out", default=None, help="--ragged, --penalties, --until: also append the records to this file")
+    ap.add_argument("--logprobs", default=None, metavar="N[,N...]",
+                    help="with --sample: time the sampled loop with and without the report of the emitted tokens, for each top_n of the list (see above)")
+    ap.add_argument("--reps", type=int, default=3, help="--ragged, --until, --logprobs: timed runs of each shape (the smallest is reported)")
+    ap.add_argument("--out", default=None, help="--ragged, --penalties, --until, --logprobs: also append the records to this file")
     args = ap.parse_args()
 
     import __graft_entry__ as graft
@@ -247,6 +320,12 @@ def main():
         return
     if args.until:
         until(pkg, m, args)
+        m.free()
+        return
+    if args.logprobs is not None:
+        if not args.sample:
+            ap.error("--logprobs times the sampled loop: give --sample with it")
+        logprobs(pkg, m, args)
         m.free()
         return
     ns = [int(x) for x in args.n.split(",")]

@@ -49,6 +49,7 @@ struct R6P {
     int inflight, thin;                                // loader: DMA instructions in flight (normal / while the workgroup gathers)
     int look;                                          // consumers: records taken per look at a hand-over's sentinel (hint_take)
     int look_g;                                        // ... at the kq hand-over (value records; RWKV_MI_RING_LOOKG)
+    int topup;                                         // consumers: landed records taken behind a completed gather (take_landed; RWKV_MI_RING_TOPUP: 1 prologue A, 2 prologue F, 4 kq hand-over)
     int hthin;                                         // ... while a wave of the workgroup watches a hand-over's sentinel (= inflight: no third level)
     int nap;                                           // extra 64-cycle sleeps between two looks at a gather's sentinel unit
     int burst;                                         // loader: fills issued per round (between two looks at the consumers' positions)
@@ -807,6 +808,7 @@ struct R6 {
         int c, lane;
         int dbg;               // RWKV_MI_RING_DBG (bit 5: timing experiment, the records' arithmetic replaced by an xor of what was read)
         unsigned look;         // takes per look at a hand-over's sentinel (hint_take)
+        unsigned topup;        // where landed records are taken behind a completed gather (take_landed; bits of p.topup)
         long long waited;      // (tracing) cycles spent waiting for the loader
     };
     template <int T, int TE> struct Unroll {
@@ -955,6 +957,29 @@ struct R6 {
         none.have = 0u; none.cnt = 0u; none.pos = 0u; none.ro = 0u; none.after = 0u;
         hint_take(cs, pl, l, xr, unit, tag, go, gen, nap, on, pre, false, none, false, none);
     }
+    // Takes stop when the sentinel turns, and the next ones happen inside rows(): whatever landed in between stays in the ring through the
+    // sweep and the prologue behind it (LN + mixes + quantise, 2.4 - 2.7 us in which this workgroup polls nothing), and the loader finds
+    // the ring full for that long. take_landed empties it into the buffers that wait for those records: every record of `a`, then of `b`
+    // (stream order, as in hint_take), that HAS landed -- no look at a sentinel, no wait, so it adds nothing that could fail to end. The
+    // same straight steps as hint_take's, for the same reason; WAIT stays true (a buffer with reads in flight must not cross a join).
+    // Call sites are chosen by the bits of p.topup (RWKV_MI_RING_TOPUP): 1 in front of prologue A, 2 in front of prologue F, 4 in front
+    // of the kq hand-over.
+    template <int PA_, int RA, int UA, int NA, int PB_, int RB_, int UB_, int NB_>
+    static __device__ __forceinline__ void take_landed(Cons & cs, Poll & pl, const Lds & l, Pre<PA_, RA, UA, NA> & a, Pre<PB_, RB_, UB_, NB_> & b) {
+        auto step = [&](auto & pre, auto tc, bool ok) {
+            constexpr int t = decltype(tc)::value;
+            using P = typename std::remove_reference<decltype(pre)>::type;
+            if (ok && pre.have == (unsigned) t && (unsigned) t < pre.cnt) (void) rec_take<t, P::PH_, P::R_, P::U_, P::NP_>(cs, pl, l, pre, false);
+        };
+        Unroll<0, NA>::run([&](auto tc) { step(a, tc, true); });
+        Unroll<0, NB_>::run([&](auto tc) { step(b, tc, a.have >= a.cnt); });
+    }
+    template <int PH, int R, int U, int NP>
+    static __device__ __forceinline__ void take_landed(Cons & cs, Poll & pl, const Lds & l, Pre<PH, R, U, NP> & pre) {
+        Pre<RG_W1, 1, 1, 1> none;
+        none.have = 0u; none.cnt = 0u; none.pos = 0u; none.ro = 0u; none.after = 0u;
+        take_landed(cs, pl, l, pre, none);
+    }
 
     // The records of one phase that belong to this wave: j0, j0 + NC, ...; the first TF exist for every wave that owns any (compile-time),
     // one more ("tail") for some. Statically unrolled: the cursor is scalar arithmetic (stream position and ring offset advance by a
@@ -1058,7 +1083,7 @@ struct R6 {
         const xrsrc xr = make_xrsrc(p.xch, p.xch_bytes);
         const RingShape sh = shape(p);
         Cons cs;
-        cs.cu = rg_cu(sh, blk); cs.lbase = 0; cs.landed = 0; cs.RB = __builtin_amdgcn_readfirstlane(p.ring_bytes); cs.ring_lds = __builtin_amdgcn_readfirstlane((unsigned) (size_t) (__attribute__((address_space(3))) unsigned char *) l.ring); cs.c = c; cs.lane = lane; cs.dbg = __builtin_amdgcn_readfirstlane(p.dbg); cs.look = (unsigned) __builtin_amdgcn_readfirstlane(p.look); cs.waited = 0;
+        cs.cu = rg_cu(sh, blk); cs.lbase = 0; cs.landed = 0; cs.RB = __builtin_amdgcn_readfirstlane(p.ring_bytes); cs.ring_lds = __builtin_amdgcn_readfirstlane((unsigned) (size_t) (__attribute__((address_space(3))) unsigned char *) l.ring); cs.c = c; cs.lane = lane; cs.dbg = __builtin_amdgcn_readfirstlane(p.dbg); cs.look = (unsigned) __builtin_amdgcn_readfirstlane(p.look); cs.topup = (unsigned) __builtin_amdgcn_readfirstlane(p.topup); cs.waited = 0;
         const int mat = (blk * (4 * D / NBLK)) / D;   // which of r, k, v, g this workgroup's sets belong to
         const int cbase = (blk * (4 * D / NBLK)) % D;
         const bool has_dw1 = blk < p.DR;
@@ -1109,6 +1134,7 @@ struct R6 {
             }
             gather_meet(pl, l.fl + FL_GX, 2u * li + 1u);
             sweep_end(l);
+            if (cs.topup & 1u) take_landed(cs, pl, l, pw, pc);
             R6STAMP(1);
             {   // behind an in-launch embedding the residual rows of this wave start from l.x (a select, not a branch: see gather_x)
                 const bool take = li == 0 && emb_in;
@@ -1193,6 +1219,7 @@ struct R6 {
             gather_x(pl, xr, p.xatt, tagL + SLOT_XATT, c, opq(lane), l.x);
             gather_meet(pl, l.fl + FL_GX, 2u * li + 2u);
             sweep_end(l);
+            if (cs.topup & 2u) take_landed(cs, pl, l, pk, pr);
             R6STAMP(8);
             if (pro) prologue_F(pl, l, pf, sout_l, blk == 0, c, opq(lane), 2u * li + 2u, eg);
             prologue_wait(pl, l, 2u * li + 2u);
@@ -1217,6 +1244,7 @@ struct R6 {
             Pre<RG_G, 1, UF, NPG> pg;
             pre_begin<RG_G>(cs, pg);
             // (registers: not the long Q8_0 rows of the 7B geometry)
+            if (G_PRE && (cs.topup & 4u)) take_landed(cs, pl, l, pg);
             watch_begin(l);
             { const unsigned lk = cs.look; cs.look = (unsigned) __builtin_amdgcn_readfirstlane(p.look_g);
               hint_take(cs, pl, l, xr, p.kq + ((blk * 5 + c * 173) & 511), tagL + SLOT_KQ, l.fl + FL_HKQ, g1, p.nap, G_PRE, pg);
@@ -2117,6 +2145,12 @@ PersistentDecoder * ring_v6_create(const Model & m) {
     if (q.look < 1) q.look = 1;
     q.look_g = env_int("RWKV_MI_RING_LOOKG", q.look);
     if (q.look_g < 1) q.look_g = 1;
+    // take_landed's call sites (1: in front of prologue A, 2: prologue F, 4: the kq hand-over). Same-box A/B, DESIGN.md 7.3, 7B: Q4_0 bits
+    // 1 + 2 together +3.5 % (alone +0.3 % and +1.5 %; bit 0 on top -0.8 %), Q5_1 +4.8 % (same with bit 0), Q8_0 bits 0 + 1 +7 % (+3.5 % each;
+    // bit 2 does nothing there: no value records ahead). At D = 2048 nothing pays: bit 0 neutral, bit 1 -0.9 %, bit 2 -2.7 % (a layer
+    // there is all hand-overs). Q4_1 / Q5_0 go with their neighbours; D = 2560: not measured.
+    const int topup_default = D == 4096 ? (g_ring_variants[rs->variant].fmt == T_Q8_0 ? 3 : 6) : 0;
+    q.topup = env_int("RWKV_MI_RING_TOPUP", topup_default) & 7;
     q.nap = env_int("RWKV_MI_RING_NAP", 2);
     q.dbg = env_int("RWKV_MI_RING_DBG", 0);
     q.burst = env_int("RWKV_MI_RING_BURST", 24) / 4;   // in groups of four fills

@@ -333,6 +333,10 @@ void   fused_v4_layer(const Model & m, const LayerW & L, float * x, const float 
 // the persistent decode kernels (persist_host.h), one creator each. nullptr: the model / device does not qualify
 PersistentDecoder * mega_v6_create(const Model & m);   // RWKV-6, register prefetch (mega_v6.hip)
 PersistentDecoder * ring_v6_create(const Model & m);   // RWKV-6, LDS-DMA weight ring (ring_v6.hip)
+// tests/ only (csrc/testhooks_rowsum.cpp): ring_v6.hip's two row-sum reductions on n x 64 device floats, n in 1..16 (false: n out of range);
+// ring_rowsum_lanes(n): the lanes one value occupies in the scattered result (ScatP<n>::W)
+bool launch_ring_rowsum_test(int n, const float * in, float * out_n, float * out_s, hipStream_t st);
+int ring_rowsum_lanes(int n);
 PersistentDecoder * p47_create(const Model & m);       // RWKV-4 / RWKV-7 (persist_v47.hip)
 const char * persist_unavailable_reason(const Model & m);   // nullptr: a persistent kernel exists for this model on this device
 // ---- layer pipeline in one process (pipeline.cpp) ----

@@ -290,6 +290,60 @@ __device__ __forceinline__ void wave_sum_n(float (&v)[N]) {
     for (int i = 0; i < N; i++) v[i] = v[i] + __int_as_float(lane_xor1_i(__float_as_int(v[i])));
 }
 
+// The same N trees as wave_sum_n, every node formed ONCE (a reduce-scatter). A butterfly forms each node of a value's tree in both
+// lanes of a pair -- at the end all 64 lanes hold the same total; the rows need it in one. Here a level halves the registers instead:
+// of a pair of registers (a, b) the lower half of every lane group goes on with a's node and the upper half with b's, each the sum of
+// the two operands wave_sum_n adds at that level (lower lane's first; IEEE addition is commutative, so the node is the same bits in
+// whichever lane of the pair forms it -- only the payload of a NaN that meets another NaN may follow the operand order). Levels 32 and
+// 16 are one permlane swap of the pair and one addition, levels 8 and 4 two DPP moves under a bank mask and one addition; where one
+// register is left the remaining levels are the butterfly's steps on it. N is padded to P = the next power of two with zeros (dead
+// registers, no conditional). Returns one register: value i's total stands in lanes [i * 64 / P, (i + 1) * 64 / P).
+template <int N> struct ScatP { static constexpr int P = N <= 1 ? 1 : (N <= 2 ? 2 : (N <= 4 ? 4 : (N <= 8 ? 8 : 16))), W = 64 / P; };
+template <int N>
+__device__ __forceinline__ float wave_sum_scatter(const float (&v)[N]) {
+    static_assert(N >= 1 && N <= 16, "wave_sum_scatter: at most 16 values (the levels below 4 have one register left)");
+    constexpr int P = ScatP<N>::P;
+    float w[P];
+#pragma unroll
+    for (int i = 0; i < P; i++) w[i] = i < N ? v[i] : 0.0f;
+    // level 32: register i goes on with value i in lanes 0 - 31 and value i + P / 2 in lanes 32 - 63
+    if constexpr (P >= 2) {
+#pragma unroll
+        for (int i = 0; i < P / 2; i++)
+            if (i < N) { const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(w[i]), __float_as_uint(w[i + P / 2]), false, false); w[i] = __uint_as_float(r[0]) + __uint_as_float(r[1]); }
+    } else { const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(w[0]), __float_as_uint(w[0]), false, false); w[0] = __uint_as_float(r[0]) + __uint_as_float(r[1]); }
+    // level 16: the even rows of 16 lanes go on with register i's values, the odd rows with register i + P / 4's
+    if constexpr (P >= 4) {
+#pragma unroll
+        for (int i = 0; i < P / 4; i++)
+            if (i < N) { const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(w[i]), __float_as_uint(w[i + P / 4]), false, false); w[i] = __uint_as_float(r[0]) + __uint_as_float(r[1]); }
+    } else { const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(w[0]), __float_as_uint(w[0]), false, false); w[0] = __uint_as_float(r[0]) + __uint_as_float(r[1]); }
+    // level 8: lanes 0 - 7 of a row go on with a (own + lane l + 8's), lanes 8 - 15 with b (lane l - 8's + own); row_ror:8 reads lane l ^ 8
+    if constexpr (P >= 8) {
+#pragma unroll
+        for (int i = 0; i < P / 8; i++)
+            if (i < N) {
+                const int a = __float_as_int(w[i]), b = __float_as_int(w[i + P / 8]);
+                const int hi = __builtin_amdgcn_update_dpp(b, a, 0x128, 0xF, 0x3, false);     // lanes 0 - 7: a[l + 8]; lanes 8 - 15: b[l]
+                const int lo = __builtin_amdgcn_update_dpp(a, b, 0x128, 0xF, 0xC, false);     // lanes 0 - 7: a[l];     lanes 8 - 15: b[l - 8]
+                w[i] = __int_as_float(lo) + __int_as_float(hi);
+            }
+    } else w[0] = w[0] + __int_as_float(lane_xor8_i(__float_as_int(w[0])));
+    // level 4: banks 0 and 2 (lanes 0 - 3, 8 - 11 of a row) go on with a, banks 1 and 3 with b (row_shl:4 reads lane l + 4, row_shr:4 lane l - 4)
+    if constexpr (P >= 16) {
+        const int a = __float_as_int(w[0]), b = __float_as_int(w[1]);
+        const int hi = __builtin_amdgcn_update_dpp(b, a, 0x104, 0xF, 0x5, false);             // banks 0, 2: a[l + 4]; banks 1, 3: b[l]
+        const int lo = __builtin_amdgcn_update_dpp(a, b, 0x114, 0xF, 0xA, false);             // banks 0, 2: a[l];     banks 1, 3: b[l - 4]
+        w[0] = __int_as_float(lo) + __int_as_float(hi);
+    } else w[0] = w[0] + __int_as_float(lane_xor4_i(__float_as_int(w[0])));
+    w[0] = w[0] + __int_as_float(lane_xor2_i(__float_as_int(w[0])));
+    w[0] = w[0] + __int_as_float(lane_xor1_i(__float_as_int(w[0])));
+    return w[0];
+}
+// value i of wave_sum_scatter<N>'s result, wave-uniform (one v_readlane)
+template <int N, int I>
+__device__ __forceinline__ float scatter_get(float s) { return __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(s), I * ScatP<N>::W)); }
+
 // ---------------------------------------------------------------------------------------------------------------
 // the kernel. EPT = D / 512, NBD = decay rank / 32, UF = 64-block steps of an F-long row, KSL = gather slots per lane for the
 // quantised F-vector. Exactly RG_NBLK workgroups of 512 threads.
@@ -313,6 +367,12 @@ __device__ __forceinline__ void wave_sum_n(float (&v)[N]) {
 #define R6STAMP(K) do { if (p.trace && li == p.trace_layer && lane == 0) p.trace[((long long) blockIdx.x * 8 + wave) * 32 + (K)] = (long long) __builtin_readcyclecounter(); } while (0)
 #endif
 #define R6RSTAMP(K) do { if (p.trace && li == p.trace_layer && lane == 0) p.trace[((long long) blockIdx.x * 8 + wave) * 32 + (K)] = (long long) __builtin_amdgcn_s_memrealtime(); } while (0)
+
+// Assembly comments around one record of a row phase (the wait for its LDS reads, rec_acc, the take issued behind it) and around a
+// phase's tail (the row-sum reduction + the epilogue): tools/ring_slots.py counts the instructions between them. A comment emits
+// no instruction.
+#define R6REC_MARK(PH, T, EDGE) asm volatile("; R6REC %0 %1 " EDGE :: "n"(PH), "n"(T))
+#define R6TAIL_MARK(PH, EDGE) asm volatile("; R6TAIL %0 0 " EDGE :: "n"(PH))
 
 template <int FMT, int EPT, int NBD, int UF, int KSL>
 struct R6 {
@@ -990,7 +1050,12 @@ struct R6 {
     // Steps t < TF are unconditional code; the tail asks `t < cnt` (wave-uniform). A buffer with reads in flight must not cross a join of
     // control flow, where the register allocator may copy it (the copy would carry the old contents): with every step conditional Q8_0
     // computed garbage.
-    template <int PH, int R, int U, int TF, int NP, typename EpiF>
+    // The row sums of the phase are reduced together. SUM_GET: wave_sum_scatter (every node of every tree once), epi receives record t's
+    // sums wave-uniform (one readlane each). SUM_LANES: the same, and epi(s) is called once with the scattered register -- row r of the
+    // wave's t-th record in lanes [(t * R + r) * W, ... + W), W = ScatP<(TF + 1) * R>::W -- and finishes every record in its own lanes.
+    // SUM_N: wave_sum_n, the (TF + 1) * R butterflies (the ffn key rows: see there).
+    enum { SUM_GET = 0, SUM_LANES = 1, SUM_N = 2 };
+    template <int PH, int R, int U, int TF, int NP, int SUM = SUM_GET, typename EpiF>
     static __device__ __forceinline__ void rows(Cons & cs, Poll & pl, const Lds & l, const QVec & act, int nbk, Pre<PH, R, U, NP> & pre, EpiF && epi) {
         static_assert(NP >= 1 && NP <= TF + 1, "rows: buffers");
         if (pre.cnt == 0u) return;
@@ -1031,6 +1096,7 @@ struct R6 {
         Unroll<0, TF + 1>::run([&](auto tc) {
             constexpr int t = decltype(tc)::value;
             if (has(t)) {
+                R6REC_MARK(PH, t, "begin");
                 if (NP >= 2 && took) rec_wait<FMT, R, U, rec_lds_ops<FMT, R, U>()>(pre.w[t % NP]);
                 else rec_wait<FMT, R, U>(pre.w[t % NP]);
                 finish(tc, pre.w[t % NP]);
@@ -1039,18 +1105,36 @@ struct R6 {
                     constexpr bool W = SAFE && t + NP >= TF;
                     if (has(t + NP)) { (void) rec_take<t + NP, PH, R, U, NP, W>(cs, pl, l, pre, true); took = !W; }
                 }
+                R6REC_MARK(PH, t, "end");
             }
         });
-        wave_sum_n<(TF + 1) * R>(part);
-        Unroll<0, TF + 1>::run([&](auto tc) {
-            constexpr int t = decltype(tc)::value;
-            if (has(t)) {
-                float res[R];
+        R6TAIL_MARK(PH, "begin");       // (the caller closes the bracket behind its epilogue)
+        constexpr int NS = (TF + 1) * R;
+        if constexpr (NS == 1 || SUM == SUM_N) {
+            wave_sum_n<NS>(part);
+            Unroll<0, TF + 1>::run([&](auto tc) {
+                constexpr int t = decltype(tc)::value;
+                if (has(t)) {
+                    float res[R];
 #pragma unroll
-                for (int r = 0; r < R; r++) res[r] = part[t * R + r];
-                epi(tc, (int) ownj<PH, t>(cs), res);
-            }
-        });
+                    for (int r = 0; r < R; r++) res[r] = part[t * R + r];
+                    epi(tc, (int) ownj<PH, t>(cs), res);
+                }
+            });
+        } else {
+            const float s = wave_sum_scatter<NS>(part);
+            if constexpr (SUM == SUM_LANES) epi(s);
+            else Unroll<0, TF + 1>::run([&](auto tc) {
+                constexpr int t = decltype(tc)::value;
+                if (has(t)) {
+                    float res[R];
+                    // (into a vector register again: as scalars the sums stay live across the hand-overs behind the phase -- rrow, xown -- and
+                    //  the scalar registers those spill are reloaded in every wait loop)
+                    Unroll<0, R>::run([&](auto rc) { constexpr int r = decltype(rc)::value; float x = scatter_get<NS, t * R + r>(s); asm volatile("" : "+v"(x)); res[r] = x; });
+                    epi(tc, (int) ownj<PH, t>(cs), res);
+                }
+            });
+        }
     }
     // buffers per wave and phase = records held in registers at once. r/k/v/g sets (C), output rows (E), ffn key sets (K), ffn receptance
     // rows (R), ffn value rows (G): as many as the register file holds without spilling (tools/check_ring_regs.sh prints the budget of
@@ -1148,6 +1232,7 @@ struct R6 {
             rows<RG_W1, 1, UD, 0, 1>(cs, pl, l, qvec_at(l.q1, D), nb, pw, [&](auto, int j, const float (&res)[1]) {
                 if (lane == 0) tg_store(xr, p.tl + blk + NBLK * j, __float_as_uint(det_tanhf(res[0])), 0u, 0u, 0u, tagL + SLOT_TL);
             });
+            R6TAIL_MARK(RG_W1, "end");
             R6STAMP(3);
             // ---- C: the mixed inputs (this workgroup's matrix reads ONE of the five), decay row, r/k/v/g sets ----
             Pre<RG_E, 1, UD, NPE> pe;
@@ -1167,25 +1252,22 @@ struct R6 {
             {
                 // all row sums first, then ONE epilogue: lane 2 t + r finishes row r of this wave's t-th set (the gate's silu is a double-
                 // precision exp: once per phase, not once per record) and lanes 0, 2, 4, ... store their set's unit with one instruction
-                constexpr int MAXT = TFC + 1;
-                float all[2 * MAXT];
-#pragma unroll
-                for (int t = 0; t < 2 * MAXT; t++) all[t] = 0.0f;
+                constexpr int MAXT = TFC + 1, W = ScatP<2 * MAXT>::W;    // W lanes per row sum: set t in lanes 2 W t (row 0) and 2 W t + W (row 1)
+                static_assert(W >= 4 && W <= 8, "C epilogue: a set's two sums lie in one row of 16 lanes");
+                float v = 0.0f;
                 if (p.trace && li == p.trace_layer && lane == 0) p.trace[((long long) blockIdx.x * 8 + wave) * 32 + 20] = (long long) fl_ld(l.fl + FL_LANDED) * 1024ll - (long long) (cs.lbase + cs.cu.off[RG_C]);
                 R6RSTAMP(26);
                 havepk |= pc.have << 4;
-                rows<RG_C, 2, UD, TFC, NPC>(cs, pl, l, qvec_at(l.act, D), nb, pc, [&](auto tc, int, const float (&res)[2]) {
-                    constexpr int t = decltype(tc)::value;
-                    all[2 * t] = res[0]; all[2 * t + 1] = res[1];
-                });
+                rows<RG_C, 2, UD, TFC, NPC, SUM_LANES>(cs, pl, l, qvec_at(l.act, D), nb, pc, [&](float s) { v = s; });
                 const int ln = opq(lane);
-                float v = pick_lane<2 * MAXT>(all, ln);
                 if (mat == 3) v = v / (1.0f + det_expf(-v));     // gate: silu
-                const int v1 = __builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x101, 0xF, 0xF, true);   // lane 2 t collects row 1 (row_shl:1)
-                int j = 0x7fff;   // record number of the set lane ln >> 1 finishes (a select chain over this wave's records)
-                Unroll<0, MAXT>::run([&](auto tc) { constexpr int t = decltype(tc)::value; const int jt = (t < TFC || (unsigned) t < pc.cnt) ? (int) ownj<RG_C, t>(cs) : 0x7fff; j = (ln >> 1) == t ? jt : j; });
-                if (ln < 2 * MAXT && (ln & 1) == 0 && j < (int) cs.cu.n[RG_C])
+                const int v1 = __builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x100 + W, 0xF, 0xF, true);   // lane 2 W t collects row 1 (row_shl:W)
+                // record number of the set lane ln finishes: this wave's records are NC apart (ownj)
+                const int t = (int) ((unsigned) ln / (2 * W));
+                const int j = (t < TFC || (unsigned) t < pc.cnt) ? (int) rg_first_j(cs.cu, RG_C, cs.c) + NC * t : 0x7fff;
+                if (ln < 2 * W * MAXT && (ln & (2 * W - 1)) == 0 && j < (int) cs.cu.n[RG_C])
                     tg_store(xr, p.rkvg + ((mat * D + cbase + 2 * j) >> 1), __float_as_uint(v), (unsigned) v1, 0u, 0u, tagL + SLOT_RKVG);
+                R6TAIL_MARK(RG_C, "end");
             }
             R6STAMP(5); R6RSTAMP(27);
             if (p.trace && li == p.trace_layer && lane == 0) p.trace[((long long) blockIdx.x * 8 + wave) * 32 + 24] = cs.waited;
@@ -1208,6 +1290,7 @@ struct R6 {
                 constexpr int t = decltype(tc)::value;
                 xown[t] = xown[t] + res[0];
             });
+            R6TAIL_MARK(RG_E, "end");
             if (lane == 0) tg_store(xr, p.xatt + blk * NC + c, __float_as_uint(xown[0]), __float_as_uint(xown[XT > 1 ? 1 : 0]), __float_as_uint(xown[XT > 2 ? 2 : 0]), 0u, tagL + SLOT_XATT);
             R6STAMP(7);
             // ---- F: x, LN2 + mixes + quantise, key sets (-> comm quantises them), receptance rows ----
@@ -1226,11 +1309,15 @@ struct R6 {
             R6STAMP(9); R6RSTAMP(28);
             if (p.trace && li == p.trace_layer && lane == 0) p.trace[((long long) blockIdx.x * 8 + wave) * 32 + 21] = (long long) fl_ld(l.fl + FL_LANDED) * 1024ll - (long long) (cs.lbase + cs.cu.off[RG_FK]);
             havepk |= (pk.have << 12) | (pr.have << 16);
-            rows<RG_FK, 2, UD, TFK, NPK>(cs, pl, l, qvec_at(l.q1, D), nb, pk, [&](auto, int j, const float (&res)[2]) {
+            // (the butterflies stay here. With these twelve sums through wave_sum_scatter -- either epilogue form -- the 7B Q4_0 kernel came out
+            //  with 5209 instead of 4077 reloads of spilled scalar registers, all over the layer: prologue F 6223 -> 7094 cycles, the loader late
+            //  in the value rows, 598 against 658 tokens/s on one box, although the key rows themselves were 1060 cycles shorter: DESIGN.md 7.3)
+            rows<RG_FK, 2, UD, TFK, NPK, SUM_N>(cs, pl, l, qvec_at(l.q1, D), nb, pk, [&](auto, int j, const float (&res)[2]) {
                 const float v = lane == 1 ? res[1] : res[0];
                 const float t = v > 0.0f ? v : 0.0f;
                 if (lane < 2) l.out[2 * j + lane] = t * t;
             });
+            R6TAIL_MARK(RG_FK, "end");
             fl_add(l.fl + FL_KEYS, 1u);
             if (pro) quant_xr(l, c, opq(lane));
             fl_wait(pl, l.fl + FL_XRQ, (unsigned) (SHI > 0 ? NC : 4) * g1);
@@ -1239,6 +1326,7 @@ struct R6 {
                 constexpr int t = decltype(tc)::value;
                 rrow[t] = res[0];
             });
+            R6TAIL_MARK(RG_FR, "end");
             R6STAMP(11); R6RSTAMP(29);
             // ---- G: value projection, x += sigmoid(r) * (Wv k) ----
             Pre<RG_G, 1, UF, NPG> pg;
@@ -1263,6 +1351,7 @@ struct R6 {
                 xown[t] = xown[t] + gte;
                 if (li == p.n_layers - 1 && lane == 0) p.x_out[blk * RE + j] = xown[t];
             });
+            R6TAIL_MARK(RG_G, "end");
             if (lane == 0) tg_store(xr, p.xffn + blk * NC + c, __float_as_uint(xown[0]), __float_as_uint(xown[XT > 1 ? 1 : 0]), __float_as_uint(xown[XT > 2 ? 2 : 0]), 0u, tagL + SLOT_XFFN);
             R6STAMP(13); R6RSTAMP(14);
             if (p.trace && li == p.trace_layer && lane == 0) { p.trace[((long long) blockIdx.x * 8 + wave) * 32 + 25] = cs.waited; p.trace[((long long) blockIdx.x * 8 + wave) * 32 + 15] = (long long) havepk; }
@@ -1680,10 +1769,10 @@ struct R6 {
                     float part[2 * KCOMM];
 #pragma unroll
                     for (int q = 0; q < KCOMM; q++) rec_acc<FMT, 2, UD>(kxr[q], ark, nb, lnK, part + 2 * q);
-                    wave_sum_n<2 * KCOMM>(part);
-                    const float v = pick_lane<2 * KCOMM>(part, lnK);
+                    constexpr int W = ScatP<2 * KCOMM>::W;              // lane W i holds row sum i
+                    const float v = wave_sum_scatter<2 * KCOMM>(part);
                     const float t = v > 0.0f ? v : 0.0f;
-                    if (lnK < 2 * KCOMM) l.out[2 * (KSETS - KCOMM) + lnK] = t * t;
+                    if ((lnK & (W - 1)) == 0 && lnK / W < 2 * KCOMM) l.out[2 * (KSETS - KCOMM) + lnK / W] = t * t;
                     __builtin_amdgcn_wave_barrier();
                 }
             }
@@ -2175,5 +2264,27 @@ void RingV6::forward_range(float * x, float *, const float * sin, float * sout, 
     const uint64_t bytes = sh->bytes * (uint64_t) (l1 - l0) / (uint64_t) sh->n_layers + (q.logits ? sh->bytes_head : 0) + (q.tok ? sh->bytes_embed : 0);
     launch_profiled(pf, bytes, g_ring_variants[sh->variant].fn, dim3((unsigned) sh->n_blocks), dim3(512), sh->lds, st, q);
 }
+
+// tests/ only (include/rwkv_testhooks_rowsum.h): one wave runs wave_sum_n<N> -- the definition -- and wave_sum_scatter<N> on the same
+// 64 x N inputs (in[i * 64 + lane]) and stores what every lane holds afterwards: out_n[i * 64 + lane], out_s[lane].
+template <int N>
+__global__ __launch_bounds__(64) void k6_rowsum_test(const float * __restrict__ in, float * __restrict__ out_n, float * __restrict__ out_s) {
+    const int lane = threadIdx.x;
+    float a[N], b[N];
+#pragma unroll
+    for (int i = 0; i < N; i++) { a[i] = in[i * 64 + lane]; b[i] = a[i]; }
+    wave_sum_n<N>(a);
+    const float s = wave_sum_scatter<N>(b);
+#pragma unroll
+    for (int i = 0; i < N; i++) out_n[i * 64 + lane] = a[i];
+    out_s[lane] = s;
+}
+template <int N> static bool rowsum_test_n(int n, const float * in, float * out_n, float * out_s, hipStream_t st) {
+    if (n == N) { hipLaunchKernelGGL(k6_rowsum_test<N>, dim3(1), dim3(64), 0, st, in, out_n, out_s); return true; }
+    if constexpr (N > 1) return rowsum_test_n<N - 1>(n, in, out_n, out_s, st);
+    else return false;
+}
+bool launch_ring_rowsum_test(int n, const float * in, float * out_n, float * out_s, hipStream_t st) { return rowsum_test_n<16>(n, in, out_n, out_s, st); }
+int ring_rowsum_lanes(int n) { return n <= 1 ? 64 : (n <= 2 ? 32 : (n <= 4 ? 16 : (n <= 8 ? 8 : 4))); }
 
 }  // namespace rwkvmi

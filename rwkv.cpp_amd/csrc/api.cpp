@@ -14,38 +14,21 @@ using namespace rwkvmi;
 #define HIP_CTX_OK(CTX, CALL) \
     do { hipError_t e_ = (CALL); RW_CTX_CHECK((CTX), RWKV_ERROR_GRAPH, false, e_ == hipSuccess, "HIP error: %s", hipGetErrorString(e_)); } while (0)
 
-// A temporary device buffer of a call, freed on every exit from its scope (after the caller has drained the stream that uses it).
-template <typename T> struct DevBuf {
-    T * p = nullptr;
-    ~DevBuf() { if (p) (void) hipFree(p); }
-    hipError_t alloc(size_t count) { return hipMalloc((void **) &p, count * sizeof(T)); }
-    // host words into the buffer on `st`
-    bool upload(const T * src, size_t count, hipStream_t st) {
-        return alloc(count) == hipSuccess && hipMemcpyAsync(p, src, count * sizeof(T), hipMemcpyHostToDevice, st) == hipSuccess;
-    }
-};
-
 // Sequence calls are cut into pieces of at most this many tokens internally (bounds scratch memory; results do not
 // depend on the cut because every kernel is per-token order-preserving).
 static const size_t k_max_tokens_per_pass = 1024;
 
 static bool upload_tokens(rwkv_context * ctx, const uint32_t * tokens, size_t n) {
-    if ((int64_t) n > ctx->d_tokens_cap) {
+    if (n > ctx->d_tokens.count) {
         HIP_CTX_OK(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->d_tokens) (void) hipFree(ctx->d_tokens);
-        if (ctx->h_tokens) (void) hipHostFree(ctx->h_tokens);
-        ctx->d_tokens = nullptr; ctx->h_tokens = nullptr; ctx->d_tokens_cap = 0;
-        size_t cap = n < 64 ? 64 : n;
-        HIP_CTX_OK(ctx, hipMalloc((void **) &ctx->d_tokens, cap * sizeof(uint32_t)));
-        HIP_CTX_OK(ctx, hipHostMalloc((void **) &ctx->h_tokens, cap * sizeof(uint32_t), hipHostMallocDefault));
-        ctx->d_tokens_cap = (int64_t) cap;
-        // captured graphs hold the old token pointer
-        for (int a = 0; a < 2; a++) for (int b = 0; b < 2; b++) if (ctx->graph_exec[a][b]) { (void) hipGraphExecDestroy(ctx->graph_exec[a][b]); ctx->graph_exec[a][b] = nullptr; }
+        const size_t cap = n < 64 ? 64 : n;
+        HIP_CTX_OK(ctx, grow(want(ctx->d_tokens, cap), want(ctx->h_tokens, cap)));
+        drop_graphs(ctx);   // captured graphs hold the old token pointer
     }
     // the previous pass may still be reading h_tokens through an in-flight copy
     HIP_CTX_OK(ctx, hipStreamSynchronize(ctx->stream));
-    memcpy(ctx->h_tokens, tokens, n * sizeof(uint32_t));
-    HIP_CTX_OK(ctx, hipMemcpyAsync(ctx->d_tokens, ctx->h_tokens, n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    memcpy(ctx->h_tokens.p, tokens, n * sizeof(uint32_t));
+    HIP_CTX_OK(ctx, hipMemcpyAsync(ctx->d_tokens.p, ctx->h_tokens.p, n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
     return true;
 }
 
@@ -75,7 +58,7 @@ static const char * k_abort_msg = "persistent decode kernel timed out waiting fo
 static bool fetch_outputs(rwkv_context * ctx, float * state_out, float * logits_out, bool * aborted = nullptr) {
     if (aborted) *aborted = false;
     if (state_out && !state_to_host(ctx, state_out)) return false;
-    if (logits_out) HIP_CTX_OK(ctx, hipMemcpyAsync(logits_out, ctx->d_logits, (size_t) ctx->model->n_vocab() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    if (logits_out) HIP_CTX_OK(ctx, hipMemcpyAsync(logits_out, ctx->d_logits.p, (size_t) ctx->model->n_vocab() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     // (a control-word copy that could not even be enqueued leaves a stale "not aborted" mirror: treated as an abort)
     const bool ctl_ok = !ctx->mega || ctx->mega->ctl.fetch(ctx->stream);
     HIP_CTX_OK(ctx, hipStreamSynchronize(ctx->stream));
@@ -324,14 +307,14 @@ RWKV_API bool rwkv_mi_score_resident(struct rwkv_context * ctx, const uint32_t *
         const size_t step = (n_tokens - done) < k_max_tokens_per_pass ? (n_tokens - done) : k_max_tokens_per_pass;
         if (!upload_tokens(ctx, tokens + done, step)) return false;   // (drains the stream: the staging of the targets is free as well)
         if (logprobs_out) {
-            memcpy(ctx->h_score_targets, targets + done, step * sizeof(uint32_t));
-            HIP_CTX_OK(ctx, hipMemcpyAsync(ctx->d_score_targets, ctx->h_score_targets, step * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+            memcpy(ctx->h_score_targets.p, targets + done, step * sizeof(uint32_t));
+            HIP_CTX_OK(ctx, hipMemcpyAsync(ctx->d_score_targets.p, ctx->h_score_targets.p, step * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
         }
         if (step == 1) {
             if (!forward_decode(ctx, true)) return false;
-            launch_score_rows(ctx->d_logits, 1, (int) n_vocab, logprobs_out ? ctx->d_score_targets : nullptr, logprobs_out ? ctx->d_score_logprobs : nullptr,
-                              argmax_out ? ctx->d_score_argmax : nullptr, ctx->stream);
-            if (logits_all_out) HIP_CTX_OK(ctx, hipMemcpyAsync(logits_all_out + done * n_vocab, ctx->d_logits, n_vocab * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+            launch_score_rows(ctx->d_logits.p, 1, (int) n_vocab, logprobs_out ? ctx->d_score_targets.p : nullptr, logprobs_out ? ctx->d_score_logprobs.p : nullptr,
+                              argmax_out ? ctx->d_score_argmax.p : nullptr, ctx->stream);
+            if (logits_all_out) HIP_CTX_OK(ctx, hipMemcpyAsync(logits_all_out + done * n_vocab, ctx->d_logits.p, n_vocab * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
         } else {
             ScorePass sp;
             sp.targets = sp.logprobs = logprobs_out != nullptr;
@@ -340,8 +323,8 @@ RWKV_API bool rwkv_mi_score_resident(struct rwkv_context * ctx, const uint32_t *
             sp.keep_last = done + step == n_tokens;
             if (!forward(ctx, (int64_t) step, true, &sp)) return false;
         }
-        if (logprobs_out) HIP_CTX_OK(ctx, hipMemcpyAsync(logprobs_out + done, ctx->d_score_logprobs, step * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-        if (argmax_out) HIP_CTX_OK(ctx, hipMemcpyAsync(argmax_out + done, ctx->d_score_argmax, step * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        if (logprobs_out) HIP_CTX_OK(ctx, hipMemcpyAsync(logprobs_out + done, ctx->d_score_logprobs.p, step * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+        if (argmax_out) HIP_CTX_OK(ctx, hipMemcpyAsync(argmax_out + done, ctx->d_score_argmax.p, step * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
         done += step;
     }
     return fetch_outputs(ctx, nullptr, nullptr);
@@ -360,7 +343,7 @@ RWKV_API bool rwkv_mi_decode_greedy(struct rwkv_context * ctx, uint32_t first_to
     uint32_t * d_hist = hist.p;
     HIP_CTX_OK(ctx, hipStreamSynchronize(ctx->stream));
     // persist_v47.hip: the launch itself picks the token, leaves it where its own embedding lookup reads it and appends it to the history
-    const bool in_launch = folded_argmax_target(ctx) == ctx->d_tokens && ctx->mega->set_history(d_hist, n_tokens, ctx->stream);
+    const bool in_launch = folded_argmax_target(ctx) == ctx->d_tokens.p && ctx->mega->set_history(d_hist, n_tokens, ctx->stream);
     // (every exit from here on takes the history pointer out of the kernel's control words again: d_hist is freed when this function returns)
     struct HistGuard { rwkv_context * c; bool on; ~HistGuard() { if (on && c->mega) (void) c->mega->set_history(nullptr, 0, c->stream); } } hist_guard{ctx, in_launch};
     HIP_CTX_OK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
@@ -370,8 +353,8 @@ RWKV_API bool rwkv_mi_decode_greedy(struct rwkv_context * ctx, uint32_t first_to
         if (!ok) break;
         if (in_launch) continue;
         // next token = argmax(logits), written where the embedding kernel reads it; no host round trip
-        if (folded_argmax_target(ctx) != ctx->d_tokens) launch_argmax(ctx->d_logits, 1, (int64_t) n_vocab, ctx->d_tokens, nullptr, ctx->stream);
-        if (hipMemcpyAsync(d_hist + i, ctx->d_tokens, sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) ok = false;
+        if (folded_argmax_target(ctx) != ctx->d_tokens.p) launch_argmax(ctx->d_logits.p, 1, (int64_t) n_vocab, ctx->d_tokens.p, nullptr, ctx->stream);
+        if (hipMemcpyAsync(d_hist + i, ctx->d_tokens.p, sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) ok = false;
     }
     if (in_launch && ctx->mega) {
         const bool drained = hipEventRecord(ctx->ev1, ctx->stream) == hipSuccess && hipStreamSynchronize(ctx->stream) == hipSuccess;
@@ -389,10 +372,10 @@ RWKV_API bool rwkv_mi_decode_greedy(struct rwkv_context * ctx, uint32_t first_to
 }
 
 static bool ensure_sampler(rwkv_context * ctx) {
-    if (!ctx->d_probs) HIP_CTX_OK(ctx, hipMalloc((void **) &ctx->d_probs, sample_scratch_floats(ctx->model->n_vocab()) * sizeof(float)));
+    if (!ctx->d_probs) HIP_CTX_OK(ctx, ctx->d_probs.alloc(sample_scratch_floats(ctx->model->n_vocab())));
     if (!ctx->d_rng_counter) {
-        HIP_CTX_OK(ctx, hipMalloc((void **) &ctx->d_rng_counter, 64));
-        HIP_CTX_OK(ctx, hipMemsetAsync(ctx->d_rng_counter, 0, 64, ctx->stream));
+        HIP_CTX_OK(ctx, ctx->d_rng_counter.alloc(8));   // (64 bytes)
+        HIP_CTX_OK(ctx, hipMemsetAsync(ctx->d_rng_counter.p, 0, 64, ctx->stream));
     }
     return true;
 }
@@ -408,26 +391,14 @@ static bool report_set(rwkv_context * ctx, LogprobReport & lp, bool enabled, uin
     return true;
 }
 
-// buffers for `entries` = steps * rows records of the current top_n (new buffers first: a failure leaves the report as it was). The caller
+// buffers for `entries` = steps * rows records of the current top_n (grown as one group: a failure leaves the report as it was). The caller
 // has drained the stream the previous report was written on.
 static bool report_ensure(rwkv_context * ctx, LogprobReport & lp, size_t entries) {
     const size_t top = entries * lp.top_n;
-    float * dc = nullptr, * dv = nullptr;
-    uint32_t * di = nullptr;
-    hipError_t e = hipSuccess;
-    if (entries > lp.cap) e = hipMalloc((void **) &dc, entries * sizeof(float));
-    if (e == hipSuccess && top > lp.cap_top) {
-        e = hipMalloc((void **) &di, top * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc((void **) &dv, top * sizeof(float));
-    }
-    if (e != hipSuccess) { for (void * q : {(void *) dc, (void *) di, (void *) dv}) if (q) (void) hipFree(q); (void) hipGetLastError(); }
+    const bool more = entries > lp.d_chosen.count, more_top = top > lp.d_ids.count;
+    const hipError_t e = grow(want(lp.d_chosen, more ? entries : 0), want(lp.d_ids, more_top ? top : 0), want(lp.d_vals, more_top ? top : 0));
     RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the log-prob report of %zu tokens: %s", entries, hipGetErrorString(e));
-    if (dc) { if (lp.d_chosen) (void) hipFree(lp.d_chosen); lp.d_chosen = dc; lp.cap = entries; lp.valid = false; }
-    if (di) {
-        if (lp.d_ids) (void) hipFree(lp.d_ids);
-        if (lp.d_vals) (void) hipFree(lp.d_vals);
-        lp.d_ids = di; lp.d_vals = dv; lp.cap_top = top; lp.valid = false;
-    }
+    if (more || more_top) lp.valid = false;
     return true;
 }
 
@@ -455,9 +426,9 @@ static bool report_store(rwkv_context * ctx, const LogprobReport & lp, hipStream
     const bool tops = N > 0 && (top_ids_out || top_logprobs_out);
     std::vector<float> hc(chosen_out ? E : 0), hv(tops && top_logprobs_out ? E * N : 0);
     std::vector<uint32_t> hi(tops && top_ids_out ? E * N : 0);
-    if (!hc.empty()) HIP_CTX_OK(ctx, hipMemcpyAsync(hc.data(), lp.d_chosen, E * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (!hi.empty()) HIP_CTX_OK(ctx, hipMemcpyAsync(hi.data(), lp.d_ids, E * N * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    if (!hv.empty()) HIP_CTX_OK(ctx, hipMemcpyAsync(hv.data(), lp.d_vals, E * N * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (!hc.empty()) HIP_CTX_OK(ctx, hipMemcpyAsync(hc.data(), lp.d_chosen.p, E * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (!hi.empty()) HIP_CTX_OK(ctx, hipMemcpyAsync(hi.data(), lp.d_ids.p, E * N * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (!hv.empty()) HIP_CTX_OK(ctx, hipMemcpyAsync(hv.data(), lp.d_vals.p, E * N * sizeof(float), hipMemcpyDeviceToHost, st));
     HIP_CTX_OK(ctx, hipStreamSynchronize(st));
     for (size_t r = 0; r < R; r++)
         for (size_t j = 0; j < stride; j++) {
@@ -557,18 +528,17 @@ static bool table_bias_set(rwkv_context * ctx, float * bias, const uint32_t * id
 // the context's occurrence and bias tables: on the first call of the family
 static bool ensure_penalty(rwkv_context * ctx) {
     const size_t V = (size_t) ctx->model->n_vocab();
-    for (void ** t : {(void **) &ctx->d_counts, (void **) &ctx->d_bias}) {
-        if (*t) continue;
-        void * d = nullptr;
-        hipError_t e = hipMalloc(&d, V * 4);
-        if (e != hipSuccess) (void) hipGetLastError();
+    // (both tables are [n_vocab] 32-bit words; a table that could not be zeroed is not kept)
+    auto table = [&](auto & t) {
+        if (t) return true;
+        std::remove_reference_t<decltype(t)> d;
+        const hipError_t e = grow(want(d, V));
         RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the penalty tables: %s", hipGetErrorString(e));
-        e = hipMemsetAsync(d, 0, V * 4, ctx->stream);
-        if (e != hipSuccess) (void) hipFree(d);
-        HIP_CTX_OK(ctx, e);
-        *t = d;
-    }
-    return true;
+        HIP_CTX_OK(ctx, hipMemsetAsync(d.p, 0, V * 4, ctx->stream));
+        t = std::move(d);
+        return true;
+    };
+    return table(ctx->d_counts) && table(ctx->d_bias);
 }
 
 // what every call of the single-context family starts with
@@ -583,7 +553,7 @@ RWKV_API bool rwkv_mi_counts_reset(struct rwkv_context * ctx) {
     if (!penalty_call(ctx)) return false;
     HIP_CTX_OK(ctx, hipSetDevice(ctx->model->device));
     if (!ensure_penalty(ctx)) return false;
-    HIP_CTX_OK(ctx, hipMemsetAsync(ctx->d_counts, 0, (size_t) ctx->model->n_vocab() * sizeof(uint32_t), ctx->stream));
+    HIP_CTX_OK(ctx, hipMemsetAsync(ctx->d_counts.p, 0, (size_t) ctx->model->n_vocab() * sizeof(uint32_t), ctx->stream));
     HIP_CTX_OK(ctx, hipStreamSynchronize(ctx->stream));
     return true;
 }
@@ -592,7 +562,7 @@ RWKV_API bool rwkv_mi_counts_add(struct rwkv_context * ctx, const uint32_t * tok
     if (!penalty_call(ctx) || !check_count_tokens(ctx, tokens, n)) return false;
     HIP_CTX_OK(ctx, hipSetDevice(ctx->model->device));
     if (!ensure_penalty(ctx)) return false;
-    return table_counts_add(ctx, ctx->d_counts, tokens, n, ctx->stream);
+    return table_counts_add(ctx, ctx->d_counts.p, tokens, n, ctx->stream);
 }
 
 RWKV_API bool rwkv_mi_counts_store(struct rwkv_context * ctx, uint32_t * counts_out) {
@@ -600,7 +570,7 @@ RWKV_API bool rwkv_mi_counts_store(struct rwkv_context * ctx, uint32_t * counts_
     RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, counts_out != nullptr, "counts_out is NULL");
     HIP_CTX_OK(ctx, hipSetDevice(ctx->model->device));
     if (!ensure_penalty(ctx)) return false;
-    HIP_CTX_OK(ctx, hipMemcpyAsync(counts_out, ctx->d_counts, (size_t) ctx->model->n_vocab() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_CTX_OK(ctx, hipMemcpyAsync(counts_out, ctx->d_counts.p, (size_t) ctx->model->n_vocab() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIP_CTX_OK(ctx, hipStreamSynchronize(ctx->stream));
     return true;
 }
@@ -611,7 +581,7 @@ RWKV_API bool rwkv_mi_logit_bias_set(struct rwkv_context * ctx, const uint32_t *
     if (!ensure_penalty(ctx)) return false;
     if (n == 0) { HIP_CTX_OK(ctx, hipStreamSynchronize(ctx->stream)); ctx->has_bias = false; return true; }
     ctx->has_bias = true;   // (a failure below leaves a table that is cleared or half written: it is not read as "no bias")
-    return table_bias_set(ctx, ctx->d_bias, ids, values, n, ctx->stream);
+    return table_bias_set(ctx, ctx->d_bias.p, ids, values, n, ctx->stream);
 }
 
 RWKV_API bool rwkv_mi_rng_seek(struct rwkv_context * ctx, uint64_t counter) {
@@ -620,7 +590,7 @@ RWKV_API bool rwkv_mi_rng_seek(struct rwkv_context * ctx, uint64_t counter) {
     HIP_CTX_OK(ctx, hipSetDevice(ctx->model->device));
     if (!ensure_sampler(ctx)) return false;
     const unsigned long long v = counter;
-    HIP_CTX_OK(ctx, hipMemcpyAsync(ctx->d_rng_counter, &v, sizeof(v), hipMemcpyHostToDevice, ctx->stream));
+    HIP_CTX_OK(ctx, hipMemcpyAsync(ctx->d_rng_counter.p, &v, sizeof(v), hipMemcpyHostToDevice, ctx->stream));
     HIP_CTX_OK(ctx, hipStreamSynchronize(ctx->stream));
     return true;
 }
@@ -631,13 +601,13 @@ struct Penalty { float presence, frequency; uint32_t record; };
 // one draw from the context's logits into *out (and hist[hist_pos] when hist is given), on the adjusted logits when pen is given
 static void launch_draw(rwkv_context * ctx, float temperature, float top_p, float u, uint64_t seed, const Penalty * pen, uint32_t * out, uint32_t * hist, int hist_pos) {
     const int n_vocab = (int) ctx->model->n_vocab();
-    if (pen) launch_pen_sample(ctx->d_logits, n_vocab, temperature, top_p, u, seed, ctx->d_rng_counter, pen->presence, pen->frequency, pen->record, ctx->d_counts,
-                               ctx->has_bias ? ctx->d_bias : nullptr, ctx->d_probs, out, hist, hist_pos, ctx->stream);
-    else launch_sample(ctx->d_logits, n_vocab, temperature, top_p, u, seed, ctx->d_rng_counter, ctx->d_probs, out, hist, hist_pos, ctx->stream);
+    if (pen) launch_pen_sample(ctx->d_logits.p, n_vocab, temperature, top_p, u, seed, ctx->d_rng_counter.p, pen->presence, pen->frequency, pen->record, ctx->d_counts.p,
+                               ctx->has_bias ? ctx->d_bias.p : nullptr, ctx->d_probs.p, out, hist, hist_pos, ctx->stream);
+    else launch_sample(ctx->d_logits.p, n_vocab, temperature, top_p, u, seed, ctx->d_rng_counter.p, ctx->d_probs.p, out, hist, hist_pos, ctx->stream);
     // the report of the token just written, slot hist_pos of the context's buffers (ensure_report has sized them)
     const LogprobReport & lp = ctx->lp;
-    if (lp.enabled) launch_logprob_rows(ctx->d_logits, 1, n_vocab, out, (int) lp.top_n, lp.d_chosen + hist_pos, lp.d_ids + (size_t) hist_pos * lp.top_n,
-                                        lp.d_vals + (size_t) hist_pos * lp.top_n, nullptr, ctx->stream);
+    if (lp.enabled) launch_logprob_rows(ctx->d_logits.p, 1, n_vocab, out, (int) lp.top_n, lp.d_chosen.p + hist_pos, lp.d_ids.p + (size_t) hist_pos * lp.top_n,
+                                        lp.d_vals.p + (size_t) hist_pos * lp.top_n, nullptr, ctx->stream);
 }
 
 // rwkv_mi_sample / rwkv_mi_sample_penalized behind their argument checks
@@ -645,8 +615,8 @@ static bool sample_once(rwkv_context * ctx, float temperature, float top_p, floa
     HIP_CTX_OK(ctx, hipSetDevice(ctx->model->device));
     if (!ensure_sampler(ctx) || (pen && !ensure_penalty(ctx)) || !ensure_report(ctx, 1)) return false;
     ctx->lp.valid = false;
-    launch_draw(ctx, temperature, top_p, u, seed, pen, ctx->d_next_token, nullptr, 0);
-    HIP_CTX_OK(ctx, hipMemcpyAsync(token_out, ctx->d_next_token, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    launch_draw(ctx, temperature, top_p, u, seed, pen, ctx->d_next_token.p, nullptr, 0);
+    HIP_CTX_OK(ctx, hipMemcpyAsync(token_out, ctx->d_next_token.p, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIP_CTX_OK(ctx, hipStreamSynchronize(ctx->stream));
     if (ctx->lp.enabled) report_done(ctx->lp, 1, 1, nullptr);
     return true;
@@ -665,7 +635,7 @@ static bool decode_sample_loop(rwkv_context * ctx, size_t n_tokens, float temper
     for (size_t i = 0; i < n_tokens; i++) {
         if (!forward_decode(ctx, true)) return false;
         // the sampled token is written where the embedding kernel of the next step reads it
-        launch_draw(ctx, temperature, top_p, -1.0f, seed, pen, ctx->d_tokens, hist.p, (int) i);
+        launch_draw(ctx, temperature, top_p, -1.0f, seed, pen, ctx->d_tokens.p, hist.p, (int) i);
     }
     HIP_CTX_OK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
     if (tokens_out) HIP_CTX_OK(ctx, hipMemcpyAsync(tokens_out, hist.p, n_tokens * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -705,7 +675,7 @@ RWKV_API bool rwkv_mi_decode_sample(struct rwkv_context * ctx, uint32_t first_to
     RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, temperature >= 0.0f && top_p >= 0.0f && top_p <= 1.0f, "bad sampling arguments");
     HIP_CTX_OK(ctx, hipSetDevice(ctx->model->device));
     if (!upload_tokens(ctx, &first_token, 1) || !ensure_sampler(ctx)) return false;
-    HIP_CTX_OK(ctx, hipMemsetAsync(ctx->d_rng_counter, 0, 8, ctx->stream));
+    HIP_CTX_OK(ctx, hipMemsetAsync(ctx->d_rng_counter.p, 0, 8, ctx->stream));
     return decode_sample_loop(ctx, n_tokens, temperature, top_p, seed, nullptr, tokens_out, elapsed_ms);
 }
 
@@ -740,7 +710,7 @@ RWKV_API bool rwkv_mi_profile_decode(struct rwkv_context * ctx, uint32_t first_t
         const bool ok = forward(ctx, 1, true);
         pf.on = false;
         if (!ok) return false;
-        if (folded_argmax_target(ctx) != ctx->d_tokens) launch_argmax(ctx->d_logits, 1, (int64_t) n_vocab, ctx->d_tokens, nullptr, ctx->stream);
+        if (folded_argmax_target(ctx) != ctx->d_tokens.p) launch_argmax(ctx->d_logits.p, 1, (int64_t) n_vocab, ctx->d_tokens.p, nullptr, ctx->stream);
         HIP_CTX_OK(ctx, hipStreamSynchronize(ctx->stream));
         for (size_t k = 0; k < pf.used; k++) {
             float ms = 0.0f;
@@ -824,7 +794,7 @@ RWKV_API bool rwkv_mi_decode_healthy(struct rwkv_context * ctx) {
     return !(ctx->mega && ctx->mega->ctl.aborted(ctx->stream));
 }
 
-RWKV_API int rwkv_mi_decode_path(const struct rwkv_context * ctx) { return ctx->mega ? 2 : ((ctx->fused_v6 || ctx->fused_v7 || ctx->fused_v4) ? 1 : 0); }
+RWKV_API int rwkv_mi_decode_path(const struct rwkv_context * ctx) { return ctx->mega ? 2 : (ctx->fused != FusedLayer::none ? 1 : 0); }
 // the documented values of rwkv_mi_persist_kind (include/rwkv_mi355x.h) for the kernel a context holds
 static int public_persist_kind(const rwkv_context * c) {
     switch (c->mega ? c->mega->kind() : DecodePath::Unmeasured) {
@@ -871,7 +841,7 @@ RWKV_API bool rwkv_mi_set_stream(struct rwkv_context * ctx, void * hip_stream) {
     RW_NO_PIPELINE(ctx, false);
     HIP_CTX_OK(ctx, hipSetDevice(ctx->model->device));
     HIP_CTX_OK(ctx, hipStreamSynchronize(ctx->stream));
-    for (int a = 0; a < 2; a++) for (int b = 0; b < 2; b++) if (ctx->graph_exec[a][b]) { (void) hipGraphExecDestroy(ctx->graph_exec[a][b]); ctx->graph_exec[a][b] = nullptr; }
+    drop_graphs(ctx);
     if (ctx->owns_stream && ctx->stream) (void) hipStreamDestroy(ctx->stream);
     ctx->stream = (hipStream_t) hip_stream;
     ctx->owns_stream = false;
@@ -896,14 +866,14 @@ RWKV_API bool rwkv_mi_stage_step(struct rwkv_context * ctx, const uint32_t * d_t
     Model & m = *ctx->model;
     HIP_CTX_OK(ctx, hipSetDevice(m.device));
     const size_t D = (size_t) m.n_embed();
-    if (!ctx->d_tokens) {  // first use: allocate the token slot
+    if (!ctx->d_tokens.p) {  // first use: allocate the token slot
         const uint32_t zero = 0;
         if (!upload_tokens(ctx, &zero, 1)) return false;
     }
     if (!ensure_scratch(ctx, 1)) return false;
     if (m.has_embed) {
         RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, d_token != nullptr, "first stage needs a token");
-        HIP_CTX_OK(ctx, hipMemcpyAsync(ctx->d_tokens, d_token, sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
+        HIP_CTX_OK(ctx, hipMemcpyAsync(ctx->d_tokens.p, d_token, sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
     } else {
         RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, x_in != nullptr, "stage needs x_in");
         HIP_CTX_OK(ctx, hipMemcpyAsync(ctx->b.x, x_in, D * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
@@ -915,7 +885,7 @@ RWKV_API bool rwkv_mi_stage_step(struct rwkv_context * ctx, const uint32_t * d_t
         HIP_CTX_OK(ctx, hipMemcpyAsync(x_out, ctx->b.x, D * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
         if (m.arch_major == 7) HIP_CTX_OK(ctx, hipMemcpyAsync(x_out + D, ctx->b.v_first, D * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
     } else if (d_next_token) {
-        launch_argmax(ctx->d_logits, 1, m.n_vocab(), d_next_token, nullptr, ctx->stream);
+        launch_argmax(ctx->d_logits.p, 1, m.n_vocab(), d_next_token, nullptr, ctx->stream);
     }
     return true;
 }
@@ -930,7 +900,7 @@ RWKV_API bool rwkv_mi_logits_store(struct rwkv_context * ctx, float * logits_out
 }
 
 // device pointer of the context's logits buffer (valid after a last-stage step / any eval that produced logits)
-RWKV_API const float * rwkv_mi_logits_device_ptr(const struct rwkv_context * ctx) { return ctx->stages.empty() ? ctx->d_logits : ctx->stages.back()->d_logits; }
+RWKV_API const float * rwkv_mi_logits_device_ptr(const struct rwkv_context * ctx) { return ctx->stages.empty() ? ctx->d_logits.p : ctx->stages.back()->d_logits.p; }
 
 RWKV_API bool rwkv_mi_trace_phases(struct rwkv_context * ctx, uint32_t token, int layer, int n, long long * out) {
     if (!ctx->mega) return false;
@@ -962,41 +932,40 @@ struct rwkv_mi_batch {
     rwkv_context * run = nullptr;      // the batch's own context (stream, scratch, tokens, logits)
     size_t n_slots = 0;
     int64_t state_len = 0;
-    float * states = nullptr;          // [2][n_slots][state_len]
+    DevBuf<float> states;              // [2][n_slots][state_len]
     std::vector<uint8_t> parity;
-    RowState * d_rows = nullptr;       // [2][n_slots]: the row tables of a call (the greedy loop alternates between the two)
-    RowState * h_rows = nullptr;       // pinned staging of the same
-    unsigned long long * d_counters = nullptr;   // [n_slots]: one draw counter per slot (sampling calls), zero at creation
-    SampleRow * d_srows = nullptr;     // [n_slots]: the sampler's row table of a call (parameters + the counter of the row's slot); with its pinned
-    SampleRow * h_srows = nullptr;     // staging and the sampler's scratch ([n_slots] vectors of probabilities) allocated by the first sampling call
-    float * d_probs = nullptr;
+    DevBuf<RowState> d_rows;           // [2][n_slots]: the row tables of a call (the greedy loop alternates between the two)
+    PinBuf<RowState> h_rows;           // pinned staging of the same
+    DevBuf<unsigned long long> d_counters;       // [n_slots]: one draw counter per slot (sampling calls), zero at creation
+    DevBuf<SampleRow> d_srows;         // [n_slots]: the sampler's row table of a call (parameters + the counter of the row's slot); with its pinned
+    PinBuf<SampleRow> h_srows;         // staging and the sampler's scratch ([n_slots] vectors of probabilities) allocated by the first sampling call
+    DevBuf<float> d_probs;
     // penalised sampling (rwkv_mi_batch_*_penalized): one occurrence table and one bias table per slot, [n_slots][n_vocab] each, and the penalised
     // row table of a call with its pinned staging -- allocated by the first call of that family. has_bias[slot]: a bias has been set and not cleared
-    uint32_t * d_counts = nullptr;
-    float * d_bias = nullptr;
+    DevBuf<uint32_t> d_counts;
+    DevBuf<float> d_bias;
     std::vector<uint8_t> has_bias;
-    PenaltyRow * d_prows = nullptr;
-    PenaltyRow * h_prows = nullptr;
+    DevBuf<PenaltyRow> d_prows;
+    PinBuf<PenaltyRow> h_prows;
     // ragged passes (rwkv_mi_batch_eval_ragged*): the tables of a call -- segments, the short ones again, seg_of[T], last[n] -- in one device
     // buffer with its pinned staging, grown to the largest call so far; the long segments stay on the host (each is a launch of its own)
-    uint8_t * d_seg = nullptr;
-    uint8_t * h_seg = nullptr;
-    size_t seg_cap = 0;
+    DevBuf<uint8_t> d_seg;
+    PinBuf<uint8_t> h_seg;
     std::vector<SegState> long_segs;
     SegPass pass;
     // rwkv_mi_batch_decode_until: the words of a call in one device buffer with its pinned staging, laid out by batch_upload_stops for the call's
     // n and sequences (capacity: n_slots rows of RWKV_MI_STOP_MAX_SEQS sequences of RWKV_MI_STOP_MAX_LEN tokens); the live count of the last two
     // blocks in pinned memory, each behind its event -- allocated by the first call of that family
-    uint8_t * d_stop = nullptr;
-    uint8_t * h_stop = nullptr;
-    uint32_t * h_live_count = nullptr;   // [2]
+    DevBuf<uint8_t> d_stop;
+    PinBuf<uint8_t> h_stop;
+    PinBuf<uint32_t> h_live_count;       // [2]
     hipEvent_t ev_block[2] = {nullptr, nullptr};
     StopTables stop{};                   // the device pointers of the current call
     size_t stop_off_lens = 0;            // where lens[n], reasons[n] start in both buffers
     size_t last_loop_passes = 0;
     LogprobReport lp;                    // the report of the batch's emitting calls (rwkv_mi_batch_set_logprobs)
 
-    float * slot_buf(size_t slot, int p) const { return states + ((size_t) p * n_slots + slot) * (size_t) state_len; }
+    float * slot_buf(size_t slot, int p) const { return states.p + ((size_t) p * n_slots + slot) * (size_t) state_len; }
 };
 
 // errors of the batch's own context are reported on the caller's
@@ -1040,7 +1009,7 @@ struct BatchCall {
 // the slot of step `step` of a call of n rows in the batch's report buffers (step 0: the buffers themselves)
 static RowReport batch_report(const rwkv_mi_batch * B, size_t n, size_t step) {
     const LogprobReport & lp = B->lp;
-    return RowReport{lp.d_chosen + step * n, lp.d_ids + step * n * lp.top_n, lp.d_vals + step * n * lp.top_n, lp.top_n};
+    return RowReport{lp.d_chosen.p + step * n, lp.d_ids.p + step * n * lp.top_n, lp.d_vals.p + step * n * lp.top_n, lp.top_n};
 }
 
 // the report buffers of an emitting call of `steps` steps (nothing when the report is off); the previous report ends here
@@ -1091,12 +1060,12 @@ static bool batch_upload(rwkv_mi_batch * B, const BatchCall & c, int tables) {
     for (int tb = 0; tb < tables; tb++)
         for (size_t i = 0; i < n; i++) {
             const int p = B->parity[slots[i]] ^ tb;
-            B->h_rows[(size_t) tb * B->n_slots + i] = RowState{B->slot_buf(slots[i], p), B->slot_buf(slots[i], p ^ 1)};
+            B->h_rows.p[(size_t) tb * B->n_slots + i] = RowState{B->slot_buf(slots[i], p), B->slot_buf(slots[i], p ^ 1)};
         }
-    memcpy(run->h_tokens, c.tokens, n * sizeof(uint32_t));
+    memcpy(run->h_tokens.p, c.tokens, n * sizeof(uint32_t));
     for (int tb = 0; tb < tables; tb++)
-        BATCH_HIP_OK(B, hipMemcpyAsync(B->d_rows + (size_t) tb * B->n_slots, B->h_rows + (size_t) tb * B->n_slots, n * sizeof(RowState), hipMemcpyHostToDevice, run->stream));
-    BATCH_HIP_OK(B, hipMemcpyAsync(run->d_tokens, run->h_tokens, n * sizeof(uint32_t), hipMemcpyHostToDevice, run->stream));
+        BATCH_HIP_OK(B, hipMemcpyAsync(B->d_rows.p + (size_t) tb * B->n_slots, B->h_rows.p + (size_t) tb * B->n_slots, n * sizeof(RowState), hipMemcpyHostToDevice, run->stream));
+    BATCH_HIP_OK(B, hipMemcpyAsync(run->d_tokens.p, run->h_tokens.p, n * sizeof(uint32_t), hipMemcpyHostToDevice, run->stream));
     return true;
 }
 
@@ -1117,11 +1086,7 @@ static bool batch_check_params(rwkv_mi_batch * B, const rwkv_mi_sample_params * 
 static bool batch_ensure_sampler(rwkv_mi_batch * B) {
     rwkv_context * ctx = B->ctx;
     if (B->d_probs && B->d_srows && B->h_srows) return true;
-    hipError_t e = hipSuccess;
-    if (!B->d_probs) e = hipMalloc((void **) &B->d_probs, B->n_slots * sample_scratch_floats(ctx->model->n_vocab()) * sizeof(float));
-    if (e == hipSuccess && !B->d_srows) e = hipMalloc((void **) &B->d_srows, B->n_slots * sizeof(SampleRow));
-    if (e == hipSuccess && !B->h_srows) e = hipHostMalloc((void **) &B->h_srows, B->n_slots * sizeof(SampleRow), hipHostMallocDefault);
-    if (e != hipSuccess) (void) hipGetLastError();
+    const hipError_t e = grow(want(B->d_probs, B->n_slots * sample_scratch_floats(ctx->model->n_vocab())), want(B->d_srows, B->n_slots), want(B->h_srows, B->n_slots));
     RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the sampler's scratch for %zu slots: %s", B->n_slots, hipGetErrorString(e));
     return true;
 }
@@ -1130,10 +1095,10 @@ static bool batch_ensure_sampler(rwkv_mi_batch * B) {
 // loop: the generator draws
 static bool batch_upload_params(rwkv_mi_batch * B, const BatchCall & c, bool loop) {
     for (size_t i = 0; i < c.n; i++) {
-        B->h_srows[i] = SampleRow{c.params[i], B->d_counters + c.slots[i]};
-        if (loop) B->h_srows[i].p.u = -1.0f;
+        B->h_srows.p[i] = SampleRow{c.params[i], B->d_counters.p + c.slots[i]};
+        if (loop) B->h_srows.p[i].p.u = -1.0f;
     }
-    BATCH_HIP_OK(B, hipMemcpyAsync(B->d_srows, B->h_srows, c.n * sizeof(SampleRow), hipMemcpyHostToDevice, B->run->stream));
+    BATCH_HIP_OK(B, hipMemcpyAsync(B->d_srows.p, B->h_srows.p, c.n * sizeof(SampleRow), hipMemcpyHostToDevice, B->run->stream));
     return true;
 }
 
@@ -1148,19 +1113,15 @@ static bool batch_check_penalties(rwkv_mi_batch * B, const rwkv_mi_penalty_param
 static bool batch_ensure_penalty(rwkv_mi_batch * B) {
     rwkv_context * ctx = B->ctx;
     if (!batch_ensure_sampler(B)) return false;
+    if (B->d_counts && B->d_bias && B->d_prows && B->h_prows) return true;
     const size_t words = B->n_slots * (size_t) ctx->model->n_vocab();
-    hipError_t e = hipSuccess;
-    for (void ** t : {(void **) &B->d_counts, (void **) &B->d_bias}) {
-        if (*t || e != hipSuccess) continue;
-        void * d = nullptr;
-        e = hipMalloc(&d, words * 4);
-        if (e != hipSuccess) break;
-        if (hipMemsetAsync(d, 0, words * 4, B->run->stream) != hipSuccess || hipStreamSynchronize(B->run->stream) != hipSuccess) { (void) hipFree(d); e = hipErrorOutOfMemory; break; }
-        *t = d;
-    }
-    if (e == hipSuccess && !B->d_prows) e = hipMalloc((void **) &B->d_prows, B->n_slots * sizeof(PenaltyRow));
-    if (e == hipSuccess && !B->h_prows) e = hipHostMalloc((void **) &B->h_prows, B->n_slots * sizeof(PenaltyRow), hipHostMallocDefault);
-    if (e != hipSuccess) (void) hipGetLastError();
+    DevBuf<uint32_t> counts;
+    DevBuf<float> bias;
+    hipError_t e = grow(want(counts, words), want(bias, words), want(B->d_prows, B->n_slots), want(B->h_prows, B->n_slots));
+    // (a table that could not be zeroed is not kept)
+    if (e == hipSuccess && (hipMemsetAsync(counts.p, 0, words * 4, B->run->stream) != hipSuccess || hipMemsetAsync(bias.p, 0, words * 4, B->run->stream) != hipSuccess ||
+                            hipStreamSynchronize(B->run->stream) != hipSuccess)) { e = hipErrorOutOfMemory; (void) hipGetLastError(); }
+    if (e == hipSuccess) { B->d_counts = std::move(counts); B->d_bias = std::move(bias); }
     RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the penalty tables of %zu slots: %s", B->n_slots, hipGetErrorString(e));
     return true;
 }
@@ -1172,11 +1133,11 @@ static bool batch_upload_penalty_rows(rwkv_mi_batch * B, const BatchCall & c, bo
     for (size_t i = 0; i < c.n; i++) {
         const size_t s = c.slots[i];
         const rwkv_mi_penalty_params & pen = c.penalties[i];
-        B->h_prows[i] = PenaltyRow{c.params[i], B->d_counters + s, pen.presence, pen.frequency, loop ? 1u : pen.record,
-                                   B->d_counts + s * V, B->has_bias[s] ? B->d_bias + s * V : nullptr};
-        if (loop) B->h_prows[i].p.u = -1.0f;
+        B->h_prows.p[i] = PenaltyRow{c.params[i], B->d_counters.p + s, pen.presence, pen.frequency, loop ? 1u : pen.record,
+                                   B->d_counts.p + s * V, B->has_bias[s] ? B->d_bias.p + s * V : nullptr};
+        if (loop) B->h_prows.p[i].p.u = -1.0f;
     }
-    BATCH_HIP_OK(B, hipMemcpyAsync(B->d_prows, B->h_prows, c.n * sizeof(PenaltyRow), hipMemcpyHostToDevice, B->run->stream));
+    BATCH_HIP_OK(B, hipMemcpyAsync(B->d_prows.p, B->h_prows.p, c.n * sizeof(PenaltyRow), hipMemcpyHostToDevice, B->run->stream));
     return true;
 }
 
@@ -1199,31 +1160,20 @@ static bool batch_upload_ragged(rwkv_mi_batch * B, const BatchCall & c, size_t T
     const size_t n = c.n;
     const Model & m = *ctx->model;
     BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));   // (the previous call's copies may still read the staging)
-    if ((int64_t) T > run->d_tokens_cap) {
-        uint32_t * d = nullptr, * h = nullptr;
-        hipError_t e = hipMalloc((void **) &d, T * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipHostMalloc((void **) &h, T * sizeof(uint32_t), hipHostMallocDefault);
-        if (e != hipSuccess) { if (d) (void) hipFree(d); (void) hipGetLastError(); }
+    if (T > run->d_tokens.count) {
+        const hipError_t e = grow(want(run->d_tokens, T), want(run->h_tokens, T));
         RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the token words of %zu tokens: %s", T, hipGetErrorString(e));
-        (void) hipFree(run->d_tokens); (void) hipHostFree(run->h_tokens);
-        run->d_tokens = d; run->h_tokens = h; run->d_tokens_cap = run->h_tokens_cap = (int64_t) T;
     }
     size_t n_short = 0;
     for (size_t i = 0; i < n; i++) if (!seg_takes_seq_kernel(m, lens[i])) n_short++;
     const size_t off_short = n * sizeof(SegState), off_seg_of = off_short + n_short * sizeof(SegState), off_last = off_seg_of + T * sizeof(int32_t);
     const size_t bytes = off_last + n * sizeof(int32_t);
-    if (bytes > B->seg_cap) {
-        uint8_t * d = nullptr, * h = nullptr;
-        hipError_t e = hipMalloc((void **) &d, bytes);
-        if (e == hipSuccess) e = hipHostMalloc((void **) &h, bytes, hipHostMallocDefault);
-        if (e != hipSuccess) { if (d) (void) hipFree(d); (void) hipGetLastError(); }
+    if (bytes > B->d_seg.count) {
+        const hipError_t e = grow(want(B->d_seg, bytes), want(B->h_seg, bytes));
         RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the segment tables of %zu tokens: %s", T, hipGetErrorString(e));
-        if (B->d_seg) (void) hipFree(B->d_seg);
-        if (B->h_seg) (void) hipHostFree(B->h_seg);
-        B->d_seg = d; B->h_seg = h; B->seg_cap = bytes;
     }
-    SegState * segs = (SegState *) B->h_seg, * shorts = (SegState *) (B->h_seg + off_short);
-    int32_t * seg_of = (int32_t *) (B->h_seg + off_seg_of), * last = (int32_t *) (B->h_seg + off_last);
+    SegState * segs = (SegState *) B->h_seg.p, * shorts = (SegState *) (B->h_seg.p + off_short);
+    int32_t * seg_of = (int32_t *) (B->h_seg.p + off_seg_of), * last = (int32_t *) (B->h_seg.p + off_last);
     B->long_segs.clear();
     int32_t t = 0;
     size_t k = 0;
@@ -1236,12 +1186,12 @@ static bool batch_upload_ragged(rwkv_mi_batch * B, const BatchCall & c, size_t T
         last[i] = g.t1 - 1;
         t = g.t1;
     }
-    memcpy(run->h_tokens, c.tokens, T * sizeof(uint32_t));
-    BATCH_HIP_OK(B, hipMemcpyAsync(B->d_seg, B->h_seg, bytes, hipMemcpyHostToDevice, run->stream));
-    BATCH_HIP_OK(B, hipMemcpyAsync(run->d_tokens, run->h_tokens, T * sizeof(uint32_t), hipMemcpyHostToDevice, run->stream));
+    memcpy(run->h_tokens.p, c.tokens, T * sizeof(uint32_t));
+    BATCH_HIP_OK(B, hipMemcpyAsync(B->d_seg.p, B->h_seg.p, bytes, hipMemcpyHostToDevice, run->stream));
+    BATCH_HIP_OK(B, hipMemcpyAsync(run->d_tokens.p, run->h_tokens.p, T * sizeof(uint32_t), hipMemcpyHostToDevice, run->stream));
     SegPass & ps = B->pass;
-    ps.d_segs = (const SegState *) B->d_seg; ps.d_short = (const SegState *) (B->d_seg + off_short);
-    ps.d_seg_of = (const int32_t *) (B->d_seg + off_seg_of); ps.d_last = (const int32_t *) (B->d_seg + off_last);
+    ps.d_segs = (const SegState *) B->d_seg.p; ps.d_short = (const SegState *) (B->d_seg.p + off_short);
+    ps.d_seg_of = (const int32_t *) (B->d_seg.p + off_seg_of); ps.d_last = (const int32_t *) (B->d_seg.p + off_last);
     ps.h_long = B->long_segs.data();
     ps.n = (int64_t) n; ps.n_short = (int64_t) n_short; ps.n_long = (int64_t) B->long_segs.size();
     return true;
@@ -1282,10 +1232,7 @@ static bool batch_ensure_stop(rwkv_mi_batch * B) {
     rwkv_context * ctx = B->ctx;
     if (B->d_stop && B->h_stop && B->h_live_count && B->ev_block[0] && B->ev_block[1]) return true;
     const size_t bytes = stop_bytes(B->n_slots, B->n_slots * RWKV_MI_STOP_MAX_SEQS, B->n_slots * RWKV_MI_STOP_MAX_SEQS * RWKV_MI_STOP_MAX_LEN);
-    hipError_t e = hipSuccess;
-    if (!B->d_stop) e = hipMalloc((void **) &B->d_stop, bytes);
-    if (e == hipSuccess && !B->h_stop) e = hipHostMalloc((void **) &B->h_stop, bytes, hipHostMallocDefault);
-    if (e == hipSuccess && !B->h_live_count) e = hipHostMalloc((void **) &B->h_live_count, 2 * sizeof(uint32_t), hipHostMallocDefault);
+    hipError_t e = grow(want(B->d_stop, B->d_stop ? 0 : bytes), want(B->h_stop, B->h_stop ? 0 : bytes), want(B->h_live_count, B->h_live_count ? 0 : 2));
     for (hipEvent_t & ev : B->ev_block) if (e == hipSuccess && !ev) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
     if (e != hipSuccess) (void) hipGetLastError();
     RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the stop tables of %zu slots: %s", B->n_slots, hipGetErrorString(e));
@@ -1297,7 +1244,7 @@ static bool batch_ensure_stop(rwkv_mi_batch * B) {
 static bool batch_upload_stops(rwkv_mi_batch * B, const BatchCall & c) {
     const size_t n = c.n;
     size_t n_seqs = 0, n_toks = 0;
-    StopRow * rows = (StopRow *) B->h_stop;
+    StopRow * rows = (StopRow *) B->h_stop.p;
     for (size_t i = 0; i < n; i++) {
         rows[i] = StopRow{c.stops[i].max_tokens, c.stops[i].n_seqs, (uint32_t) n_seqs, (uint32_t) n_toks};
         for (uint32_t s = 0; s < c.stops[i].n_seqs; s++) n_toks += c.seq_lens[n_seqs + s];
@@ -1305,13 +1252,13 @@ static bool batch_upload_stops(rwkv_mi_batch * B, const BatchCall & c) {
     }
     const size_t off_live = n * sizeof(StopRow), off_lens = off_live + n * 4, off_reasons = off_lens + n * 4, off_count = off_reasons + n * 4;
     const size_t off_sl = off_count + 4, off_st = off_sl + n_seqs * 4, bytes = off_st + n_toks * 4;
-    uint32_t * live = (uint32_t *) (B->h_stop + off_live), * lens = (uint32_t *) (B->h_stop + off_lens), * reasons = (uint32_t *) (B->h_stop + off_reasons);
+    uint32_t * live = (uint32_t *) (B->h_stop.p + off_live), * lens = (uint32_t *) (B->h_stop.p + off_lens), * reasons = (uint32_t *) (B->h_stop.p + off_reasons);
     for (size_t i = 0; i < n; i++) { live[i] = 1u; lens[i] = 0u; reasons[i] = RWKV_MI_NO_TOKEN; }
-    *(uint32_t *) (B->h_stop + off_count) = (uint32_t) n;
-    if (n_seqs) memcpy(B->h_stop + off_sl, c.seq_lens, n_seqs * 4);
-    if (n_toks) memcpy(B->h_stop + off_st, c.seq_tokens, n_toks * 4);
-    BATCH_HIP_OK(B, hipMemcpyAsync(B->d_stop, B->h_stop, bytes, hipMemcpyHostToDevice, B->run->stream));
-    uint8_t * d = B->d_stop;
+    *(uint32_t *) (B->h_stop.p + off_count) = (uint32_t) n;
+    if (n_seqs) memcpy(B->h_stop.p + off_sl, c.seq_lens, n_seqs * 4);
+    if (n_toks) memcpy(B->h_stop.p + off_st, c.seq_tokens, n_toks * 4);
+    BATCH_HIP_OK(B, hipMemcpyAsync(B->d_stop.p, B->h_stop.p, bytes, hipMemcpyHostToDevice, B->run->stream));
+    uint8_t * d = B->d_stop.p;
     B->stop = StopTables{(const StopRow *) d, (const uint32_t *) (d + off_sl), (const uint32_t *) (d + off_st), (uint32_t *) (d + off_live),
                          (uint32_t *) (d + off_lens), (uint32_t *) (d + off_reasons), (uint32_t *) (d + off_count)};
     B->stop_off_lens = off_lens;
@@ -1345,7 +1292,7 @@ static bool batch_upload_call(rwkv_mi_batch * B, const BatchCall & c, size_t T, 
 }
 
 static RowSampler batch_sampler(rwkv_mi_batch * B, const BatchCall & c, uint32_t * hist) {
-    return c.draw == Draw::penalized ? RowSampler{nullptr, B->d_probs, hist, B->d_prows} : RowSampler{B->d_srows, B->d_probs, hist};
+    return c.draw == Draw::penalized ? RowSampler{nullptr, B->d_probs.p, hist, B->d_prows.p} : RowSampler{B->d_srows.p, B->d_probs.p, hist};
 }
 
 // a pass that could not be launched: the stream is drained before the call returns (what it had enqueued reads the staging)
@@ -1370,8 +1317,8 @@ static bool batch_pass(rwkv_mi_batch * B, const BatchCall & c) {
     if (report && !batch_ensure_report(B, c.n, 1)) return false;
     if (!batch_upload_call(B, c, T, false)) return false;   // (drains the stream: the staging of the targets is free as well)
     if (c.logprobs_out) {
-        memcpy(run->h_score_targets, c.targets, T * sizeof(uint32_t));
-        BATCH_HIP_OK(B, hipMemcpyAsync(run->d_score_targets, run->h_score_targets, T * sizeof(uint32_t), hipMemcpyHostToDevice, run->stream));
+        memcpy(run->h_score_targets.p, c.targets, T * sizeof(uint32_t));
+        BATCH_HIP_OK(B, hipMemcpyAsync(run->d_score_targets.p, run->h_score_targets.p, T * sizeof(uint32_t), hipMemcpyHostToDevice, run->stream));
     }
     // Row i's token lands in the batch's token word i (a ragged pass has read all T of them by then): the 4 n bytes that go back to the host.
     RowSampler sampler = batch_sampler(B, c, nullptr);
@@ -1383,14 +1330,14 @@ static bool batch_pass(rwkv_mi_batch * B, const BatchCall & c) {
     sp.argmax = c.argmax_out != nullptr;
     const bool want_logits = drawn || scoring || c.logits_out;
     const bool ok = c.lens ? forward_segs(run, B->pass, (int64_t) T, want_logits, drawn ? &sampler : nullptr, scoring ? &sp : nullptr)
-                           : forward_rows(run, B->d_rows, (int64_t) c.n, want_logits, drawn ? &sampler : nullptr);
+                           : forward_rows(run, B->d_rows.p, (int64_t) c.n, want_logits, drawn ? &sampler : nullptr);
     if (!ok) return batch_fail_drained(B);
-    if (drawn) BATCH_HIP_OK(B, hipMemcpyAsync(run->h_tokens, run->d_tokens, c.n * sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream));
-    if (c.logits_out) BATCH_HIP_OK(B, hipMemcpyAsync(c.logits_out, run->d_logits, c.n * (size_t) ctx->model->n_vocab() * sizeof(float), hipMemcpyDeviceToHost, run->stream));
-    if (c.logprobs_out) BATCH_HIP_OK(B, hipMemcpyAsync(c.logprobs_out, run->d_score_logprobs, T * sizeof(float), hipMemcpyDeviceToHost, run->stream));
-    if (c.argmax_out) BATCH_HIP_OK(B, hipMemcpyAsync(c.argmax_out, run->d_score_argmax, T * sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream));
+    if (drawn) BATCH_HIP_OK(B, hipMemcpyAsync(run->h_tokens.p, run->d_tokens.p, c.n * sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream));
+    if (c.logits_out) BATCH_HIP_OK(B, hipMemcpyAsync(c.logits_out, run->d_logits.p, c.n * (size_t) ctx->model->n_vocab() * sizeof(float), hipMemcpyDeviceToHost, run->stream));
+    if (c.logprobs_out) BATCH_HIP_OK(B, hipMemcpyAsync(c.logprobs_out, run->d_score_logprobs.p, T * sizeof(float), hipMemcpyDeviceToHost, run->stream));
+    if (c.argmax_out) BATCH_HIP_OK(B, hipMemcpyAsync(c.argmax_out, run->d_score_argmax.p, T * sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream));
     BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));
-    if (drawn) memcpy(c.sampled_out, run->h_tokens, c.n * sizeof(uint32_t));
+    if (drawn) memcpy(c.sampled_out, run->h_tokens.p, c.n * sizeof(uint32_t));
     batch_flip(B, c);
     if (report) report_done(B->lp, c.n, 1, nullptr);
     return true;
@@ -1416,7 +1363,7 @@ static bool batch_loop(rwkv_mi_batch * B, const BatchCall & c, size_t n_tokens, 
     const bool report = B->lp.enabled;   // (every step of a loop emits)
     if (!batch_ensure_report(B, n, n_tokens)) return false;
     if (!batch_upload_call(B, c, T, true)) return false;
-    if (c.draw == Draw::sample) launch_sample_seek_rows(B->d_srows, (int64_t) n, 0ull, run->stream);   // the named slots' streams start over
+    if (c.draw == Draw::sample) launch_sample_seek_rows(B->d_srows.p, (int64_t) n, 0ull, run->stream);   // the named slots' streams start over
     BATCH_HIP_OK(B, hipEventRecord(run->ev0, run->stream));
     for (size_t i = 0; i < n_tokens; i++) {
         // step i reads the buffers step i - 1 wrote: the two row tables alternate; the token of each row -- sampled inside the pass's chain
@@ -1424,11 +1371,11 @@ static bool batch_loop(rwkv_mi_batch * B, const BatchCall & c, size_t n_tokens, 
         RowSampler sampler = batch_sampler(B, c, hist.p + i * n);
         const RowReport rep = report ? batch_report(B, n, i) : RowReport{};
         if (report) sampler.report = &rep;
-        if (!forward_rows(run, B->d_rows + (i & 1) * B->n_slots, (int64_t) n, true, drawn ? &sampler : nullptr)) return batch_fail_drained(B);
+        if (!forward_rows(run, B->d_rows.p + (i & 1) * B->n_slots, (int64_t) n, true, drawn ? &sampler : nullptr)) return batch_fail_drained(B);
         if (drawn) continue;
         // the greedy argmax, and its report directly behind it: the event the device's next persistent launch waits on is recorded after both
-        launch_argmax(run->d_logits, (int64_t) n, ctx->model->n_vocab(), run->d_tokens, hist.p + i * n, run->stream);
-        if (report) launch_logprob_rows(run->d_logits, (int64_t) n, (int) ctx->model->n_vocab(), run->d_tokens, (int) rep.top_n, rep.chosen, rep.ids, rep.vals, nullptr, run->stream);
+        launch_argmax(run->d_logits.p, (int64_t) n, ctx->model->n_vocab(), run->d_tokens.p, hist.p + i * n, run->stream);
+        if (report) launch_logprob_rows(run->d_logits.p, (int64_t) n, (int) ctx->model->n_vocab(), run->d_tokens.p, (int) rep.top_n, rep.chosen, rep.ids, rep.vals, nullptr, run->stream);
     }
     BATCH_HIP_OK(B, hipEventRecord(run->ev1, run->stream));
     std::vector<uint32_t> h(tokens_out ? n_tokens * n : 0);
@@ -1477,13 +1424,13 @@ static bool batch_until(rwkv_mi_batch * B, const BatchCall & c, uint32_t * token
     if (!batch_ensure_report(B, n, budget)) return false;
     const RowReport rep = report ? batch_report(B, n, 0) : RowReport{};
     if (!batch_upload_call(B, c, T, true)) return false;
-    if (c.draw == Draw::sample) launch_sample_seek_rows(B->d_srows, (int64_t) n, 0ull, run->stream);   // the named slots' streams start over
+    if (c.draw == Draw::sample) launch_sample_seek_rows(B->d_srows.p, (int64_t) n, 0ull, run->stream);   // the named slots' streams start over
     BATCH_HIP_OK(B, hipMemsetAsync(hist.p, 0xFF, budget * n * sizeof(uint32_t), run->stream));
     BATCH_HIP_OK(B, hipEventRecord(run->ev0, run->stream));
     size_t passes = 0;
     for (size_t b = 0; passes < budget; b++) {
         for (const size_t end = std::min(budget, passes + K); passes < end; passes++) {
-            RowState * used = B->d_rows + (passes & 1) * B->n_slots, * other = B->d_rows + ((passes & 1) ^ 1) * B->n_slots;
+            RowState * used = B->d_rows.p + (passes & 1) * B->n_slots, * other = B->d_rows.p + ((passes & 1) ^ 1) * B->n_slots;
             const RowStop stop{B->stop, (uint32_t) passes, used, other};
             RowSampler sampler = batch_sampler(B, c, hist.p);
             if (c.draw == Draw::none) sampler.table = nullptr;   // (no draw: the greedy argmax)
@@ -1491,15 +1438,15 @@ static bool batch_until(rwkv_mi_batch * B, const BatchCall & c, uint32_t * token
             if (report) sampler.report = &rep;
             if (!forward_rows(run, used, (int64_t) n, true, &sampler)) return batch_fail_drained(B);
         }
-        hipError_t e = hipMemcpyAsync(B->h_live_count + (b & 1), B->stop.live_count, sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream);
+        hipError_t e = hipMemcpyAsync(B->h_live_count.p + (b & 1), B->stop.live_count, sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream);
         if (e == hipSuccess) e = hipEventRecord(B->ev_block[b & 1], run->stream);
         if (e == hipSuccess && b > 0) e = hipEventSynchronize(B->ev_block[(b - 1) & 1]);
         if (e != hipSuccess) { (void) hipStreamSynchronize(run->stream); BATCH_HIP_OK(B, e); }
-        if (b > 0 && B->h_live_count[(b - 1) & 1] == 0) break;
+        if (b > 0 && B->h_live_count.p[(b - 1) & 1] == 0) break;
     }
     BATCH_HIP_OK(B, hipEventRecord(run->ev1, run->stream));
     std::vector<uint32_t> h(tokens_out ? passes * n : 0);
-    uint32_t * h_lens = (uint32_t *) (B->h_stop + B->stop_off_lens);   // lens[n], then reasons[n]
+    uint32_t * h_lens = (uint32_t *) (B->h_stop.p + B->stop_off_lens);   // lens[n], then reasons[n]
     if (tokens_out) BATCH_HIP_OK(B, hipMemcpyAsync(h.data(), hist.p, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream));
     BATCH_HIP_OK(B, hipMemcpyAsync(h_lens, B->stop.lens, 2 * n * sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream));
     BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));
@@ -1527,26 +1474,10 @@ RWKV_API void rwkv_mi_batch_free(struct rwkv_mi_batch * B) {
         (void) hipSetDevice(B->run->model->device);
         (void) hipStreamSynchronize(B->run->stream);
     }
-    if (B->states) (void) hipFree(B->states);
-    if (B->d_rows) (void) hipFree(B->d_rows);
-    if (B->h_rows) (void) hipHostFree(B->h_rows);
-    if (B->d_counters) (void) hipFree(B->d_counters);
-    if (B->d_srows) (void) hipFree(B->d_srows);
-    if (B->h_srows) (void) hipHostFree(B->h_srows);
-    if (B->d_probs) (void) hipFree(B->d_probs);
-    if (B->d_counts) (void) hipFree(B->d_counts);
-    if (B->d_bias) (void) hipFree(B->d_bias);
-    if (B->d_prows) (void) hipFree(B->d_prows);
-    if (B->h_prows) (void) hipHostFree(B->h_prows);
-    if (B->d_seg) (void) hipFree(B->d_seg);
-    if (B->h_seg) (void) hipHostFree(B->h_seg);
-    if (B->d_stop) (void) hipFree(B->d_stop);
-    if (B->h_stop) (void) hipHostFree(B->h_stop);
-    if (B->h_live_count) (void) hipHostFree(B->h_live_count);
     for (hipEvent_t ev : B->ev_block) if (ev) (void) hipEventDestroy(ev);
-    B->lp.release();
-    batch_context_destroy(B->run);
-    delete B;
+    rwkv_context * run = B->run;
+    delete B;   // its buffers: after the drain above, before the batch's own context gives up its stream and its reference to the model
+    batch_context_destroy(run);
 }
 
 RWKV_API struct rwkv_mi_batch * rwkv_mi_batch_create(struct rwkv_context * ctx, size_t n_slots) {
@@ -1568,15 +1499,15 @@ RWKV_API struct rwkv_mi_batch * rwkv_mi_batch_create(struct rwkv_context * ctx, 
     RW_CTX_CHECK(ctx, RWKV_ERROR_CTX | RWKV_ERROR_ALLOC, nullptr, B->run != nullptr, "cannot create the batch's stream / buffers (device memory?)");
     B->run->print_errors = ctx->print_errors;
     const size_t sbytes = (size_t) B->state_len * sizeof(float);
-    hipError_t e = hipMalloc((void **) &B->states, 2 * n_slots * sbytes);
+    hipError_t e = B->states.alloc(2 * n_slots * (size_t) B->state_len);
     RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, nullptr, e == hipSuccess, "cannot allocate %zu slot states: %s", n_slots, hipGetErrorString(e));
-    e = hipMalloc((void **) &B->d_rows, 2 * n_slots * sizeof(RowState));
+    e = B->d_rows.alloc(2 * n_slots);
     RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, nullptr, e == hipSuccess, "HIP error: %s", hipGetErrorString(e));
-    e = hipHostMalloc((void **) &B->h_rows, 2 * n_slots * sizeof(RowState), hipHostMallocDefault);
+    e = B->h_rows.alloc(2 * n_slots);
     RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, nullptr, e == hipSuccess, "HIP error: %s", hipGetErrorString(e));
-    e = hipMalloc((void **) &B->d_counters, n_slots * sizeof(unsigned long long));
+    e = B->d_counters.alloc(n_slots);
     RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, nullptr, e == hipSuccess, "HIP error: %s", hipGetErrorString(e));
-    e = hipMemsetAsync(B->d_counters, 0, n_slots * sizeof(unsigned long long), B->run->stream);
+    e = hipMemsetAsync(B->d_counters.p, 0, n_slots * sizeof(unsigned long long), B->run->stream);
     RW_CTX_CHECK(ctx, RWKV_ERROR_GRAPH, nullptr, e == hipSuccess, "HIP error: %s", hipGetErrorString(e));
     // every slot starts from the fresh state (both buffers: a slot's first pass reads buffer 0)
     for (size_t s = 0; s < n_slots; s++) {
@@ -1634,7 +1565,7 @@ RWKV_API bool rwkv_mi_batch_state_from_context(struct rwkv_mi_batch * B, size_t 
     BATCH_HIP_OK(B, hipSetDevice(other->model->device));
     BATCH_HIP_OK(B, hipStreamSynchronize(other->stream));     // (the context's last step has written its state)
     hipStream_t st = B->run->stream;
-    BATCH_HIP_OK(B, hipMemcpyAsync(B->slot_buf(slot, B->parity[slot]), other->state[other->cur], (size_t) B->state_len * sizeof(float), hipMemcpyDeviceToDevice, st));
+    BATCH_HIP_OK(B, hipMemcpyAsync(B->slot_buf(slot, B->parity[slot]), other->state[other->cur].p, (size_t) B->state_len * sizeof(float), hipMemcpyDeviceToDevice, st));
     BATCH_HIP_OK(B, hipStreamSynchronize(st));
     return true;
 }
@@ -1645,7 +1576,7 @@ RWKV_API bool rwkv_mi_batch_state_to_context(struct rwkv_mi_batch * B, size_t sl
     BATCH_HIP_OK(B, hipSetDevice(other->model->device));
     hipStream_t st = B->run->stream;
     BATCH_HIP_OK(B, hipStreamSynchronize(st));
-    BATCH_HIP_OK(B, hipMemcpyAsync(other->state[other->cur], B->slot_buf(slot, B->parity[slot]), (size_t) B->state_len * sizeof(float), hipMemcpyDeviceToDevice, other->stream));
+    BATCH_HIP_OK(B, hipMemcpyAsync(other->state[other->cur].p, B->slot_buf(slot, B->parity[slot]), (size_t) B->state_len * sizeof(float), hipMemcpyDeviceToDevice, other->stream));
     BATCH_HIP_OK(B, hipStreamSynchronize(other->stream));
     return true;
 }
@@ -1705,7 +1636,7 @@ RWKV_API bool rwkv_mi_batch_rng_seek(struct rwkv_mi_batch * B, size_t slot, uint
     BATCH_HIP_OK(B, hipSetDevice(ctx->model->device));
     hipStream_t st = B->run->stream;
     const unsigned long long v = counter;
-    BATCH_HIP_OK(B, hipMemcpyAsync(B->d_counters + slot, &v, sizeof(v), hipMemcpyHostToDevice, st));
+    BATCH_HIP_OK(B, hipMemcpyAsync(B->d_counters.p + slot, &v, sizeof(v), hipMemcpyHostToDevice, st));
     BATCH_HIP_OK(B, hipStreamSynchronize(st));
     return true;
 }
@@ -1715,7 +1646,7 @@ RWKV_API bool rwkv_mi_batch_counts_reset(struct rwkv_mi_batch * B, size_t slot) 
     BATCH_HIP_OK(B, hipSetDevice(B->ctx->model->device));
     if (!batch_ensure_penalty(B)) return false;
     const size_t V = (size_t) B->ctx->model->n_vocab();
-    BATCH_HIP_OK(B, hipMemsetAsync(B->d_counts + slot * V, 0, V * sizeof(uint32_t), B->run->stream));
+    BATCH_HIP_OK(B, hipMemsetAsync(B->d_counts.p + slot * V, 0, V * sizeof(uint32_t), B->run->stream));
     BATCH_HIP_OK(B, hipStreamSynchronize(B->run->stream));
     return true;
 }
@@ -1724,7 +1655,7 @@ RWKV_API bool rwkv_mi_batch_counts_add(struct rwkv_mi_batch * B, size_t slot, co
     if (!batch_slot_call(B, slot) || !check_count_tokens(B->ctx, tokens, n)) return false;
     BATCH_HIP_OK(B, hipSetDevice(B->ctx->model->device));
     if (!batch_ensure_penalty(B)) return false;
-    return table_counts_add(B->ctx, B->d_counts + slot * (size_t) B->ctx->model->n_vocab(), tokens, n, B->run->stream);
+    return table_counts_add(B->ctx, B->d_counts.p + slot * (size_t) B->ctx->model->n_vocab(), tokens, n, B->run->stream);
 }
 
 RWKV_API bool rwkv_mi_batch_counts_store(struct rwkv_mi_batch * B, size_t slot, uint32_t * counts_out) {
@@ -1733,7 +1664,7 @@ RWKV_API bool rwkv_mi_batch_counts_store(struct rwkv_mi_batch * B, size_t slot, 
     BATCH_HIP_OK(B, hipSetDevice(B->ctx->model->device));
     if (!batch_ensure_penalty(B)) return false;
     const size_t V = (size_t) B->ctx->model->n_vocab();
-    BATCH_HIP_OK(B, hipMemcpyAsync(counts_out, B->d_counts + slot * V, V * sizeof(uint32_t), hipMemcpyDeviceToHost, B->run->stream));
+    BATCH_HIP_OK(B, hipMemcpyAsync(counts_out, B->d_counts.p + slot * V, V * sizeof(uint32_t), hipMemcpyDeviceToHost, B->run->stream));
     BATCH_HIP_OK(B, hipStreamSynchronize(B->run->stream));
     return true;
 }
@@ -1744,7 +1675,7 @@ RWKV_API bool rwkv_mi_batch_logit_bias_set(struct rwkv_mi_batch * B, size_t slot
     if (!batch_ensure_penalty(B)) return false;
     if (n == 0) { BATCH_HIP_OK(B, hipStreamSynchronize(B->run->stream)); B->has_bias[slot] = 0; return true; }
     B->has_bias[slot] = 1;   // (a failure below leaves a table that is cleared or half written: it is not read as "no bias")
-    return table_bias_set(B->ctx, B->d_bias + slot * (size_t) B->ctx->model->n_vocab(), ids, values, n, B->run->stream);
+    return table_bias_set(B->ctx, B->d_bias.p + slot * (size_t) B->ctx->model->n_vocab(), ids, values, n, B->run->stream);
 }
 
 RWKV_API bool rwkv_mi_batch_eval_sample_penalized(struct rwkv_mi_batch * B, const uint32_t * slots, const uint32_t * tokens, size_t n,

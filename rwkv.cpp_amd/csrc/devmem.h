@@ -1,0 +1,65 @@
+// devmem.h -- who owns device and pinned host memory: a buffer is a member (or a local) of the type below and is released with its owner.
+// Streams, events, graphs and IPC handles are not memory and stay with the code that orders them. Kernel parameter structs take the raw
+// pointer (.p); an owner that is destroyed has drained, in its free function, the stream its buffers were used on.
+#pragma once
+#include <cstddef>
+#include <utility>
+
+#include <hip/hip_runtime.h>
+
+namespace rwkvmi {
+
+// `count` elements of T from hipMalloc (DevBuf) or hipHostMalloc(..., hipHostMallocDefault) (PinBuf); move-only.
+template <typename T, bool Pinned> struct MemBuf {
+    T * p = nullptr;
+    size_t count = 0;
+    MemBuf() = default;
+    MemBuf(const MemBuf &) = delete;
+    MemBuf & operator=(const MemBuf &) = delete;
+    MemBuf(MemBuf && o) noexcept : p(o.p), count(o.count) { o.p = nullptr; o.count = 0; }
+    MemBuf & operator=(MemBuf && o) noexcept {
+        if (this != &o) { reset(); p = o.p; count = o.count; o.p = nullptr; o.count = 0; }
+        return *this;
+    }
+    ~MemBuf() { reset(); }
+    T * get() const { return p; }
+    explicit operator bool() const { return p != nullptr; }
+    void reset() {
+        if (p) (void) (Pinned ? hipHostFree(p) : hipFree(p));
+        p = nullptr; count = 0;
+    }
+    // releases what it holds, then allocates; a failure leaves it empty
+    hipError_t alloc(size_t n) {
+        reset();
+        const hipError_t e = Pinned ? hipHostMalloc((void **) &p, n * sizeof(T), hipHostMallocDefault) : hipMalloc((void **) &p, n * sizeof(T));
+        if (e == hipSuccess) count = n; else p = nullptr;
+        return e;
+    }
+    // a fresh device buffer of host words, copied on `st`
+    bool upload(const T * src, size_t n, hipStream_t st) {
+        static_assert(!Pinned, "upload fills a device buffer");
+        return alloc(n) == hipSuccess && hipMemcpyAsync(p, src, n * sizeof(T), hipMemcpyHostToDevice, st) == hipSuccess;
+    }
+};
+template <typename T> using DevBuf = MemBuf<T, false>;
+template <typename T> using PinBuf = MemBuf<T, true>;
+
+// Growing a group of buffers as ONE decision: every new piece is allocated first, and only when all of them exist are the old ones released
+// and replaced. On a failure the new pieces are freed, the sticky HIP error is cleared and every buffer is what it was.
+//   hipError_t e = grow(want(a, n), want(b, m));        (a count of 0: that buffer stays)
+template <typename Buf> struct GrowReq { Buf & buf; size_t count; Buf fresh; };
+template <typename Buf> GrowReq<Buf> want(Buf & buf, size_t count) { return GrowReq<Buf>{buf, count, Buf()}; }
+
+template <typename... Req> hipError_t grow(Req &&... reqs) {
+    hipError_t e = hipSuccess;
+    ((e = (e == hipSuccess && reqs.count) ? reqs.fresh.alloc(reqs.count) : e), ...);
+    if (e != hipSuccess) {
+        (reqs.fresh.reset(), ...);
+        (void) hipGetLastError();
+        return e;
+    }
+    ((reqs.count ? (void) (reqs.buf = std::move(reqs.fresh)) : (void) 0), ...);
+    return hipSuccess;
+}
+
+}  // namespace rwkvmi

@@ -95,13 +95,12 @@ static void note(rwkv_context * ctx, const char * fmt, ...) {
 static void calibrate_decode_path(rwkv_context * ctx, std::vector<std::unique_ptr<PersistentDecoder>> cand) {
     Model & m = *ctx->model;
     const bool v6 = m.arch_major == 6;
-    uint32_t * tok = nullptr;
-    if (hipMalloc((void **) &tok, 256) != hipSuccess) { ctx->mega = std::move(cand[0]); return; }
+    DevBuf<uint32_t> tok;   // (the calibration's own token words, 256 bytes, in the place of the context's)
+    if (tok.alloc(64) != hipSuccess) { ctx->mega = std::move(cand[0]); return; }
     const size_t sbytes = (size_t) m.state_len() * sizeof(float);
-    bool ok = hipMemsetAsync(tok, 0, 256, ctx->stream) == hipSuccess;
-    for (int i = 0; v6 && i < 2; i++) ok = ok && hipMemsetAsync(ctx->state[i], 0, sbytes, ctx->stream) == hipSuccess;
-    uint32_t * saved_tokens = ctx->d_tokens;
-    ctx->d_tokens = tok;
+    bool ok = hipMemsetAsync(tok.p, 0, 256, ctx->stream) == hipSuccess;
+    for (int i = 0; v6 && i < 2; i++) ok = ok && hipMemsetAsync(ctx->state[i].p, 0, sbytes, ctx->stream) == hipSuccess;
+    std::swap(ctx->d_tokens, tok);
     // (with logits: a kernel that folds ln_out + head runs them inside its launch, the other paths as launches of their own -- part of what is compared)
     auto timed = [&](std::unique_ptr<PersistentDecoder> & h) -> float {
         ctx->mega.swap(h);
@@ -140,10 +139,10 @@ static void calibrate_decode_path(rwkv_context * ctx, std::vector<std::unique_pt
         else { t[best] = p2 < t[best] ? p2 : t[best]; const float f2 = timed(launches); t_fused = f2 < t_fused ? f2 : t_fused; }
     }
     (void) hipStreamSynchronize(ctx->stream);
-    ctx->d_tokens = saved_tokens;
+    std::swap(ctx->d_tokens, tok);
     ctx->cur = 0;
     ctx->last_error = 0;
-    (void) hipFree(tok);
+    tok.reset();
     const bool keep = ok && !bad[best] && !(t_fused < 0.97f * t[best]);
     for (size_t i = 0; i < cand.size(); i++) if (bad[i]) note(ctx, "calibration: the %s kernel timed out (not every workgroup resident)", decode_path_name(cand[i]->kind()));
     if (!bad[best]) note(ctx, "calibration: %s %.3f ms / token against %.3f ms for the per-layer launches: %s", decode_path_name(cand[best]->kind()), t[best] / 6.0f, t_fused / 6.0f, keep ? "kept" : "dropped");
@@ -175,7 +174,7 @@ void recover_from_abort(rwkv_context * ctx) {
     mega_chain_forget(ctx);
     mega_chain_count(ctx, -1);
     ctx->mega.reset();
-    for (int a = 0; a < 2; a++) for (int b = 0; b < 2; b++) if (ctx->graph_exec[a][b]) { (void) hipGraphExecDestroy(ctx->graph_exec[a][b]); ctx->graph_exec[a][b] = nullptr; }
+    drop_graphs(ctx);
 }
 
 rwkv_context * create_context(Model * m, uint32_t n_threads) {
@@ -197,10 +196,9 @@ rwkv_context * create_context(Model * m, uint32_t n_threads) {
     hipError_t e;
     if ((e = hipSetDevice(m->device)) != hipSuccess) return fail(e);
     if ((e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking)) != hipSuccess) return fail(e);
-    const size_t sbytes = (size_t) m->state_len() * sizeof(float);
-    for (int i = 0; i < 2; i++) if ((e = hipMalloc((void **) &ctx->state[i], sbytes)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc((void **) &ctx->d_logits, (size_t) m->n_vocab() * sizeof(float))) != hipSuccess) return fail(e);
-    if ((e = hipMalloc((void **) &ctx->d_next_token, 64)) != hipSuccess) return fail(e);
+    for (int i = 0; i < 2; i++) if ((e = ctx->state[i].alloc((size_t) m->state_len())) != hipSuccess) return fail(e);
+    if ((e = ctx->d_logits.alloc((size_t) m->n_vocab())) != hipSuccess) return fail(e);
+    if ((e = ctx->d_next_token.alloc(16)) != hipSuccess) return fail(e);   // (64 bytes)
     if ((e = hipEventCreate(&ctx->ev0)) != hipSuccess) return fail(e);
     if ((e = hipEventCreate(&ctx->ev1)) != hipSuccess) return fail(e);
     if ((e = hipEventCreateWithFlags(&ctx->mega_done, hipEventDisableTiming)) != hipSuccess) return fail(e);
@@ -208,19 +206,14 @@ rwkv_context * create_context(Model * m, uint32_t n_threads) {
     const char * g = getenv("RWKV_MI_NO_GRAPH");
     ctx->use_graph = !(g && g[0] == '1');
     const char * nf = getenv("RWKV_MI_NO_FUSED");
-    if (!(nf && nf[0] == '1') && fused_v6_supported(*m)) {
-        if ((e = hipMalloc(&ctx->fused_scratch, fused_v6_scratch_bytes(*m))) != hipSuccess) return fail(e);
-        ctx->fused_v6 = true;
+    if (!(nf && nf[0] == '1')) {
+        size_t bytes = 0;
+        if (fused_v6_supported(*m)) { ctx->fused = FusedLayer::v6; bytes = fused_v6_scratch_bytes(*m); }
+        else if (fused_v7_supported(*m)) { ctx->fused = FusedLayer::v7; bytes = fused_v7_scratch_bytes(*m); }
+        else if (fused_v4_supported(*m)) { ctx->fused = FusedLayer::v4; bytes = fused_v4_scratch_bytes(*m); }
+        if (ctx->fused != FusedLayer::none && (e = ctx->fused_scratch.alloc(bytes)) != hipSuccess) return fail(e);
     }
-    if (!(nf && nf[0] == '1') && fused_v7_supported(*m)) {
-        if ((e = hipMalloc(&ctx->fused_scratch, fused_v7_scratch_bytes(*m))) != hipSuccess) return fail(e);
-        ctx->fused_v7 = true;
-    }
-    if (!(nf && nf[0] == '1') && fused_v4_supported(*m)) {
-        if ((e = hipMalloc(&ctx->fused_scratch, fused_v4_scratch_bytes(*m))) != hipSuccess) return fail(e);
-        ctx->fused_v4 = true;
-    }
-    if (ctx->fused_v6 || ctx->fused_v7 || ctx->fused_v4) {
+    if (ctx->fused != FusedLayer::none) {
         // one persistent launch per token where the model and the device have a variant; the fused launches stay as the fall-back
         const char * nm = getenv("RWKV_MI_NO_MEGA"), * na = getenv("RWKV_MI_NO_AUTOTUNE"), * pk = getenv("RWKV_MI_PERSIST");
         const DecodePath known = m->decode_choice.load();      // (what an earlier context of this model measured)
@@ -239,7 +232,7 @@ rwkv_context * create_context(Model * m, uint32_t n_threads) {
             calibrate_decode_path(ctx.get(), std::move(cand));
         } else if (!cand.empty()) ctx->mega = std::move(cand[0]);
     }
-    if (!ctx->fused_v6 && !ctx->fused_v7 && !ctx->fused_v4) { const char * why = persist_unavailable_reason(*m); note(ctx.get(), "%s", (nf && nf[0] == '1') ? "RWKV_MI_NO_FUSED=1" : (why ? why : "no fused layer for this model")); }
+    if (ctx->fused == FusedLayer::none) { const char * why = persist_unavailable_reason(*m); note(ctx.get(), "%s", (nf && nf[0] == '1') ? "RWKV_MI_NO_FUSED=1" : (why ? why : "no fused layer for this model")); }
     // A new context starts from the reference's fresh state (rwkv_eval.inc:224-241), whatever the calibration left behind:
     // rwkv_mi_eval_resident / rwkv_mi_decode_greedy / rwkv_mi_stage_step continue from the resident state without a load.
     ctx->cur = 0;
@@ -248,7 +241,7 @@ rwkv_context * create_context(Model * m, uint32_t n_threads) {
     return ctx.release();
 }
 
-static void drop_graphs(rwkv_context * ctx) {
+void drop_graphs(rwkv_context * ctx) {
     for (int a = 0; a < 2; a++) for (int b = 0; b < 2; b++) if (ctx->graph_exec[a][b]) { (void) hipGraphExecDestroy(ctx->graph_exec[a][b]); ctx->graph_exec[a][b] = nullptr; }
 }
 
@@ -257,31 +250,18 @@ void destroy_context(rwkv_context * ctx) {
     if (ctx->stream) (void) hipStreamSynchronize(ctx->stream);
     if (ctx->abi_streamer) { abi_streamer_free(ctx->abi_streamer); ctx->abi_streamer = nullptr; }
     drop_graphs(ctx);
-    for (int i = 0; i < 2; i++) if (ctx->state[i]) (void) hipFree(ctx->state[i]);
-    if (ctx->scratch) (void) hipFree(ctx->scratch);
-    if (ctx->fused_scratch) (void) hipFree(ctx->fused_scratch);
     if (ctx->mega) { mega_chain_forget(ctx); mega_chain_count(ctx, -1); ctx->mega.reset(); }
     if (ctx->mega_done) (void) hipEventDestroy(ctx->mega_done);
-    if (ctx->d_tokens) (void) hipFree(ctx->d_tokens);
-    if (ctx->d_logits) (void) hipFree(ctx->d_logits);
-    if (ctx->d_next_token) (void) hipFree(ctx->d_next_token);
-    if (ctx->d_probs) (void) hipFree(ctx->d_probs);
-    if (ctx->d_rng_counter) (void) hipFree(ctx->d_rng_counter);
-    if (ctx->d_counts) (void) hipFree(ctx->d_counts);
-    if (ctx->d_bias) (void) hipFree(ctx->d_bias);
-    if (ctx->d_score) (void) hipFree(ctx->d_score);
-    if (ctx->d_score_targets) (void) hipFree(ctx->d_score_targets);
-    if (ctx->h_score_targets) (void) hipHostFree(ctx->h_score_targets);
-    if (ctx->d_score_logprobs) (void) hipFree(ctx->d_score_logprobs);
-    if (ctx->d_score_argmax) (void) hipFree(ctx->d_score_argmax);
-    ctx->lp.release();
-    if (ctx->h_tokens) (void) hipHostFree(ctx->h_tokens);
     if (ctx->ev0) (void) hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void) hipEventDestroy(ctx->ev1);
     for (hipEvent_t e : ctx->prof.events) (void) hipEventDestroy(e);
-    if (ctx->stream && ctx->owns_stream) { matvec_f_release_stream(ctx->stream); (void) hipStreamDestroy(ctx->stream); }
-    release_model(ctx->model);
+    Model * m = ctx->model;
+    hipStream_t st = ctx->owns_stream ? ctx->stream : nullptr;
+    // The context's buffers are its members and go here: after the drain above, before its stream is destroyed and before the model's last
+    // reference can free the arena.
     delete ctx;
+    if (st) { matvec_f_release_stream(st); (void) hipStreamDestroy(st); }
+    release_model(m);
 }
 
 // Scratch for T tokens: one allocation carved into named activations.
@@ -298,11 +278,11 @@ bool ensure_scratch(rwkv_context * ctx, int64_t T) {
     constexpr size_t k_ws_part = (size_t) 16 << 20;   // split-walk partial sums: up to 64 tiles x 8 parts x 32 KiB
     constexpr int    k_ws_counters = 1024;
     if (T >= k_mfma_min_tokens) total += align_up(tile_act_bytes(T, (int64_t) KQ), 256) + 5 * align_up(tile_act_bytes(T, (int64_t) D), 256) + k_ws_part + k_ws_counters * sizeof(int);
-    if (ctx->scratch) { HIP_CTX_OK(ctx, hipStreamSynchronize(ctx->stream)); (void) hipFree(ctx->scratch); ctx->scratch = nullptr; ctx->scratch_T = 0; }
+    // (the old scratch goes BEFORE the new one is allocated, unlike every grow(): it is the context's largest buffer)
+    if (ctx->scratch) { HIP_CTX_OK(ctx, hipStreamSynchronize(ctx->stream)); ctx->scratch.reset(); ctx->scratch_T = 0; }
     drop_graphs(ctx);
-    HIP_CTX_OK(ctx, hipMalloc(&ctx->scratch, total));
-    ctx->scratch_bytes = total;
-    uint8_t * p = (uint8_t *) ctx->scratch;
+    HIP_CTX_OK(ctx, ctx->scratch.alloc(total));
+    uint8_t * p = ctx->scratch.p;
     auto takef = [&](size_t n) { float * r = (float *) p; p += fsz(n); return r; };
     auto & b = ctx->b;
     b.x = takef(D); b.xn = takef(D); b.sx = takef(D);
@@ -332,44 +312,24 @@ bool ensure_scratch(rwkv_context * ctx, int64_t T) {
 // Scoring buffers of a context (model.h, ScorePass): everything new is allocated before anything old is released.
 bool ensure_score(rwkv_context * ctx, int64_t rows) {
     const size_t V = (size_t) ctx->model->n_vocab();
-    float * chunk = nullptr;
     int64_t R = ctx->score_R;
-    hipError_t e = hipSuccess;
-    if (!ctx->d_score) {
+    const bool first = !ctx->d_score;
+    if (first) {
         R = (int64_t) (((size_t) 64 << 20) / (4 * V));
         R = R < 32 ? 32 : (R > 1024 ? 1024 : R);
         // (read here, once per context: tests force many chunks on small models with it)
         if (const char * v = getenv("RWKV_MI_SCORE_ROWS")) { const long long n = atoll(v); if (n >= 1) R = (int64_t) n; }
-        e = hipMalloc((void **) &chunk, (size_t) R * V * sizeof(float));
     }
-    uint32_t * dt = nullptr, * ht = nullptr, * da = nullptr;
-    float * dl = nullptr;
     const int64_t cap = rows < 1024 ? 1024 : rows;
-    const bool grow = rows > ctx->score_cap;
-    if (grow) {
-        if (e == hipSuccess) e = hipMalloc((void **) &dt, (size_t) cap * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipHostMalloc((void **) &ht, (size_t) cap * sizeof(uint32_t), hipHostMallocDefault);
-        if (e == hipSuccess) e = hipMalloc((void **) &dl, (size_t) cap * sizeof(float));
-        if (e == hipSuccess) e = hipMalloc((void **) &da, (size_t) cap * sizeof(uint32_t));
-        if (e == hipSuccess && ctx->score_cap) e = hipStreamSynchronize(ctx->stream);   // (an earlier call's copies may still use the old words)
-    }
-    if (e != hipSuccess) {
-        if (chunk) (void) hipFree(chunk);
-        if (dt) (void) hipFree(dt);
-        if (ht) (void) hipHostFree(ht);
-        if (dl) (void) hipFree(dl);
-        if (da) (void) hipFree(da);
-        (void) hipGetLastError();
-    }
+    const size_t words = rows > ctx->score_cap ? (size_t) cap : 0;
+    hipError_t e = hipSuccess;
+    if (words && ctx->score_cap) e = hipStreamSynchronize(ctx->stream);   // (an earlier call's copies may still use the old words)
+    if (e != hipSuccess) (void) hipGetLastError();
+    else e = grow(want(ctx->d_score, first ? (size_t) R * V : 0), want(ctx->d_score_targets, words), want(ctx->h_score_targets, words),
+                  want(ctx->d_score_logprobs, words), want(ctx->d_score_argmax, words));
     RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the scoring buffers (%lld rows of %zu logits): %s", (long long) R, V, hipGetErrorString(e));
-    if (chunk) { ctx->d_score = chunk; ctx->score_R = R; }
-    if (grow) {
-        if (ctx->d_score_targets) (void) hipFree(ctx->d_score_targets);
-        if (ctx->h_score_targets) (void) hipHostFree(ctx->h_score_targets);
-        if (ctx->d_score_logprobs) (void) hipFree(ctx->d_score_logprobs);
-        if (ctx->d_score_argmax) (void) hipFree(ctx->d_score_argmax);
-        ctx->d_score_targets = dt; ctx->h_score_targets = ht; ctx->d_score_logprobs = dl; ctx->d_score_argmax = da; ctx->score_cap = cap;
-    }
+    if (first) ctx->score_R = R;
+    if (words) ctx->score_cap = cap;
     return true;
 }
 
@@ -379,7 +339,7 @@ bool state_from_host(rwkv_context * ctx, const float * state_in) {
     Model & m = *ctx->model;
     if (g_test_fail_state_init.load(std::memory_order_relaxed) > 0 && g_test_fail_state_init.fetch_sub(1) > 0)
         RW_CTX_CHECK(ctx, RWKV_ERROR_GRAPH, false, false, "state initialisation failed (injected by the test hook)");
-    float * dst = ctx->state[ctx->cur];
+    float * dst = ctx->state[ctx->cur].p;
     if (state_in) {
         HIP_CTX_OK(ctx, hipMemcpyAsync(dst, state_in, (size_t) m.state_len() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     } else if (m.arch_major >= 5) {
@@ -392,7 +352,7 @@ bool state_from_host(rwkv_context * ctx, const float * state_in) {
 
 bool state_to_host(rwkv_context * ctx, float * state_out) {
     Model & m = *ctx->model;
-    HIP_CTX_OK(ctx, hipMemcpyAsync(state_out, ctx->state[ctx->cur], (size_t) m.state_len() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_CTX_OK(ctx, hipMemcpyAsync(state_out, ctx->state[ctx->cur].p, (size_t) m.state_len() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     return true;
 }
 
@@ -700,12 +660,12 @@ struct Runner {
 
     void run_embed() {
         if (!state.rows && !seg && T == 1 && ctx->mega && m.has_embed && ctx->mega->folds_embed()) return;   // inside the persistent launch
-        if (m.has_embed) launch_embed_ln0(*m.emb, ctx->d_tokens, T, D, f(m.ln0_w), f(m.ln0_b), b.x, st);
+        if (m.has_embed) launch_embed_ln0(*m.emb, ctx->d_tokens.p, T, D, f(m.ln0_w), f(m.ln0_b), b.x, st);
     }
     // layers [lb, le) of the stage (absolute layer ids); returns true when the launch also produced the logits (ring kernel, last layers)
     bool run_layers(uint32_t lb, uint32_t le, bool want_logits) {
-        const float * sin = ctx->state[ctx->cur];
-        float * sout = ctx->state[ctx->cur ^ 1];
+        const float * sin = ctx->state[ctx->cur].p;
+        float * sout = ctx->state[ctx->cur ^ 1].p;
         state.in = sin; state.out = sout;
         const int64_t per_layer = m.state_per_layer();
         const bool one = T == 1 && !state.rows && !seg;   // (the single-token paths work on the context's own state)
@@ -715,17 +675,17 @@ struct Runner {
             const float * s0 = sin + (int64_t) m.layer_begin * per_layer;
             float * o0 = sout + (int64_t) m.layer_begin * per_layer;
             // (the launch starts from the token id and ends with the argmax where the stage has embedding / head and the kernel folds them)
-            const uint32_t * tok = (lb == m.layer_begin && m.has_embed && ctx->mega->folds_embed()) ? ctx->d_tokens : nullptr;
-            uint32_t * ntok = ctx->ntok_out ? ctx->ntok_out : (tok ? ctx->d_tokens : ctx->d_next_token);    // the greedy loops read the next token where the embedding reads it
-            ctx->mega->forward_range(b.x, b.v_first, s0, o0, st, whole ? &ctx->prof : nullptr, head_done ? ctx->d_logits : nullptr, (int) (lb - m.layer_begin), (int) (le - m.layer_begin), tok, ntok);
+            const uint32_t * tok = (lb == m.layer_begin && m.has_embed && ctx->mega->folds_embed()) ? ctx->d_tokens.p : nullptr;
+            uint32_t * ntok = ctx->ntok_out ? ctx->ntok_out : (tok ? ctx->d_tokens.p : ctx->d_next_token.p);    // the greedy loops read the next token where the embedding reads it
+            ctx->mega->forward_range(b.x, b.v_first, s0, o0, st, whole ? &ctx->prof : nullptr, head_done ? ctx->d_logits.p : nullptr, (int) (lb - m.layer_begin), (int) (le - m.layer_begin), tok, ntok);
             return head_done;
         }
         for (uint32_t i = lb; i < le; i++) {
             const LayerW & L = m.layers[i];
             const int64_t so = (int64_t) i * per_layer;
-            if (one && ctx->fused_v6) { fused_v6_layer(m, L, b.x, sin + so, sout + so, ctx->fused_scratch, st, &ctx->prof); continue; }
-            if (one && ctx->fused_v4) { fused_v4_layer(m, L, b.x, sin + so, sout + so, ctx->fused_scratch, st, &ctx->prof); continue; }
-            if (one && ctx->fused_v7) { fused_v7_layer(m, L, (int) i, b.x, b.v_first, sin + so, sout + so, ctx->fused_scratch, st, &ctx->prof); continue; }
+            if (one && ctx->fused == FusedLayer::v6) { fused_v6_layer(m, L, b.x, sin + so, sout + so, ctx->fused_scratch.p, st, &ctx->prof); continue; }
+            if (one && ctx->fused == FusedLayer::v4) { fused_v4_layer(m, L, b.x, sin + so, sout + so, ctx->fused_scratch.p, st, &ctx->prof); continue; }
+            if (one && ctx->fused == FusedLayer::v7) { fused_v7_layer(m, L, (int) i, b.x, b.v_first, sin + so, sout + so, ctx->fused_scratch.p, st, &ctx->prof); continue; }
             switch (m.arch_major) {
                 case 4: att_v4(L, so); break;
                 case 5: att_v5(L, so); break;
@@ -747,37 +707,37 @@ struct Runner {
             rows = Tall - r0 < R ? Tall - r0 : R;
             launch_layernorm(b.x + r0 * D, rows, D, f(m.ln_out_w), f(m.ln_out_b), b.xn, st);
             T = rows;
-            mm(m.head, b.xn, ctx->d_score);
+            mm(m.head, b.xn, ctx->d_score.p);
             T = Tall;
-            launch_score_rows(ctx->d_score, rows, (int) V, score->targets ? ctx->d_score_targets + r0 : nullptr,
-                              score->logprobs ? ctx->d_score_logprobs + r0 : nullptr, score->argmax ? ctx->d_score_argmax + r0 : nullptr, st);
+            launch_score_rows(ctx->d_score.p, rows, (int) V, score->targets ? ctx->d_score_targets.p + r0 : nullptr,
+                              score->logprobs ? ctx->d_score_logprobs.p + r0 : nullptr, score->argmax ? ctx->d_score_argmax.p + r0 : nullptr, st);
             if (score->h_logits_all &&
-                hipMemcpyAsync(score->h_logits_all + r0 * V, ctx->d_score, (size_t) (rows * V) * sizeof(float), hipMemcpyDeviceToHost, st) != hipSuccess) copy_failed = true;
+                hipMemcpyAsync(score->h_logits_all + r0 * V, ctx->d_score.p, (size_t) (rows * V) * sizeof(float), hipMemcpyDeviceToHost, st) != hipSuccess) copy_failed = true;
         }
         // the context's own logits are those of the last token, as after a plain pass (the sampler and rwkv_mi_logits_store read them)
         if (score->keep_last &&
-            hipMemcpyAsync(ctx->d_logits, ctx->d_score + (rows - 1) * V, (size_t) V * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) copy_failed = true;
+            hipMemcpyAsync(ctx->d_logits.p, ctx->d_score.p + (rows - 1) * V, (size_t) V * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) copy_failed = true;
     }
     void run_head() {
         if (score) { run_head_score(); return; }
         if (state.rows) {
             // row mode: every row is the last token of its sequence -- ln_out on all rows, one product with T rows into [T][n_vocab]
             launch_layernorm(b.x, T, D, f(m.ln_out_w), f(m.ln_out_b), b.xn, st);
-            mm(m.head, b.xn, ctx->d_logits);
+            mm(m.head, b.xn, ctx->d_logits.p);
             return;
         }
         if (seg) {
             // segment mode: ln_out on the last token of each segment (gathered), one product with seg->n rows into [n][n_vocab]
             launch_layernorm_gather(b.x, seg->d_last, seg->n, D, f(m.ln_out_w), f(m.ln_out_b), b.xn, st);
             const int64_t Tsave = T; T = seg->n;
-            mm(m.head, b.xn, ctx->d_logits);
+            mm(m.head, b.xn, ctx->d_logits.p);
             T = Tsave;
             return;
         }
         // ln_out on the last token only, then the head projection (rwkv_graph.inc:704-708, 851-854)
         launch_layernorm(b.x + (T - 1) * D, 1, D, f(m.ln_out_w), f(m.ln_out_b), b.xlast, st);
         const int64_t Tsave = T; T = 1;
-        mm(m.head, b.xlast, ctx->d_logits);
+        mm(m.head, b.xlast, ctx->d_logits.p);
         T = Tsave;
     }
     void run(bool want_logits) {
@@ -793,13 +753,13 @@ struct Runner {
 // greedy loops then need no argmax launch -- and no copy when that is where their next step reads the token.
 uint32_t * folded_argmax_target(const rwkv_context * ctx) {
     if (!ctx->mega || !ctx->model->has_head || !ctx->mega->folds_argmax()) return nullptr;
-    return (ctx->model->has_embed && ctx->mega->folds_embed()) ? ctx->d_tokens : ctx->d_next_token;
+    return (ctx->model->has_embed && ctx->mega->folds_embed()) ? ctx->d_tokens.p : ctx->d_next_token.p;
 }
 
 int64_t handoff_len(const Model & m) { return m.arch_major == 7 ? 2 * m.n_embed() : m.n_embed(); }
 
 bool forward(rwkv_context * ctx, int64_t T, bool want_logits, const ScorePass * score) {
-    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, !score || (T > 1 && ctx->d_score), "a scoring pass needs its buffers and at least two tokens");
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, !score || (T > 1 && ctx->d_score.p), "a scoring pass needs its buffers and at least two tokens");
     if (!ensure_scratch(ctx, T)) return false;
     Model & m = *ctx->model;
     Runner r{ctx, m, ctx->stream, T, m.n_embed(), m.head_count, m.head_size, ctx->b};
@@ -831,13 +791,11 @@ rwkv_context * batch_context_create(Model * m, int64_t max_rows) {
     c->use_graph = false;
     bool ok = hipSetDevice(m->device) == hipSuccess &&
               hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) == hipSuccess &&
-              hipMalloc((void **) &c->d_logits, (size_t) max_rows * (size_t) m->n_vocab() * sizeof(float)) == hipSuccess &&
-              hipMalloc((void **) &c->d_tokens, (size_t) max_rows * sizeof(uint32_t)) == hipSuccess &&
-              hipHostMalloc((void **) &c->h_tokens, (size_t) max_rows * sizeof(uint32_t), hipHostMallocDefault) == hipSuccess &&
+              c->d_logits.alloc((size_t) max_rows * (size_t) m->n_vocab()) == hipSuccess &&
+              c->d_tokens.alloc((size_t) max_rows) == hipSuccess && c->h_tokens.alloc((size_t) max_rows) == hipSuccess &&
               hipEventCreate(&c->ev0) == hipSuccess && hipEventCreate(&c->ev1) == hipSuccess &&
               hipEventCreateWithFlags(&c->mega_done, hipEventDisableTiming) == hipSuccess;
     if (!ok) { destroy_context(c); return nullptr; }
-    c->d_tokens_cap = c->h_tokens_cap = max_rows;
     prefill_prepare_current_device();
     // (a persistent context already on the device recorded nothing while it was alone: drain it once)
     if (mega_chain_count(c, +1) > 1) (void) hipDeviceSynchronize();
@@ -853,7 +811,7 @@ void batch_context_destroy(rwkv_context * c) {
     destroy_context(c);
 }
 
-// The row sampler of a batch pass over the `rows` rows of ctx->d_logits: row r's token goes to ctx->d_tokens[r] (and to s.hist[r] when given).
+// The row sampler of a batch pass over the `rows` rows of ctx->d_logits.p: row r's token goes to ctx->d_tokens.p[r] (and to s.hist[r] when given).
 // Order within a step: the draw (or argmax), then the report of what it wrote (s.report), then the stop test.
 static void launch_row_sampler(rwkv_context * ctx, const RowSampler & s, int64_t rows) {
     const int n_vocab = (int) ctx->model->n_vocab();
@@ -861,23 +819,23 @@ static void launch_row_sampler(rwkv_context * ctx, const RowSampler & s, int64_t
         // a step of rwkv_mi_batch_decode_until: the draw behind the live words, then the stop test on what it wrote
         uint32_t * hist = s.hist + (size_t) s.stop->step * (size_t) rows;
         const uint32_t * live = s.stop->t.live;
-        if (s.ptable) launch_pen_sample_rows_live(ctx->d_logits, rows, n_vocab, s.ptable, s.probs, ctx->d_tokens, hist, live, ctx->stream);
-        else if (s.table) launch_sample_rows_live(ctx->d_logits, rows, n_vocab, s.table, s.probs, ctx->d_tokens, hist, live, ctx->stream);
-        else launch_argmax_live(ctx->d_logits, rows, n_vocab, ctx->d_tokens, hist, live, ctx->stream);
+        if (s.ptable) launch_pen_sample_rows_live(ctx->d_logits.p, rows, n_vocab, s.ptable, s.probs, ctx->d_tokens.p, hist, live, ctx->stream);
+        else if (s.table) launch_sample_rows_live(ctx->d_logits.p, rows, n_vocab, s.table, s.probs, ctx->d_tokens.p, hist, live, ctx->stream);
+        else launch_argmax_live(ctx->d_logits.p, rows, n_vocab, ctx->d_tokens.p, hist, live, ctx->stream);
         if (s.report) {
             const size_t at = (size_t) s.stop->step * (size_t) rows;
-            launch_logprob_rows(ctx->d_logits, rows, n_vocab, ctx->d_tokens, (int) s.report->top_n, s.report->chosen + at, s.report->ids + at * s.report->top_n,
+            launch_logprob_rows(ctx->d_logits.p, rows, n_vocab, ctx->d_tokens.p, (int) s.report->top_n, s.report->chosen + at, s.report->ids + at * s.report->top_n,
                                 s.report->vals + at * s.report->top_n, live, ctx->stream);
         }
         launch_stop_rows(s.stop->t, rows, s.hist, s.stop->step, s.stop->used, s.stop->other, ctx->stream);
         return;
     }
-    if (s.ptable) launch_pen_sample_rows(ctx->d_logits, rows, n_vocab, s.ptable, s.probs, ctx->d_tokens, s.hist, ctx->stream);
-    else launch_sample_rows(ctx->d_logits, rows, n_vocab, s.table, s.probs, ctx->d_tokens, s.hist, ctx->stream);
-    if (s.report) launch_logprob_rows(ctx->d_logits, rows, n_vocab, ctx->d_tokens, (int) s.report->top_n, s.report->chosen, s.report->ids, s.report->vals, nullptr, ctx->stream);
+    if (s.ptable) launch_pen_sample_rows(ctx->d_logits.p, rows, n_vocab, s.ptable, s.probs, ctx->d_tokens.p, s.hist, ctx->stream);
+    else launch_sample_rows(ctx->d_logits.p, rows, n_vocab, s.table, s.probs, ctx->d_tokens.p, s.hist, ctx->stream);
+    if (s.report) launch_logprob_rows(ctx->d_logits.p, rows, n_vocab, ctx->d_tokens.p, (int) s.report->top_n, s.report->chosen, s.report->ids, s.report->vals, nullptr, ctx->stream);
 }
 
-// One pass of T rows, row t = one token (ctx->d_tokens[t]) of the sequence whose state is d_rows[t]. Logits: ctx->d_logits[T][n_vocab].
+// One pass of T rows, row t = one token (ctx->d_tokens.p[t]) of the sequence whose state is d_rows[t]. Logits: ctx->d_logits.p[T][n_vocab].
 // sample: the T sampler workgroups (sampling.hip, k_sample_rows) follow the head INSIDE the chain bracket. Each of them is 1024 threads,
 // a CU's worth of waves, so up to T CUs are taken while they run; the completion event mega_chain_end records is what the device's next
 // persistent launch waits on, and with the sampler in front of it that launch still finds every CU free ("a batch pass never runs beside
@@ -904,11 +862,11 @@ bool seg_takes_seq_kernel(const Model & m, int64_t len) {
     return !(m.arch_major == 7 && no_seq7);
 }
 
-// One ragged pass of T tokens (ctx->d_tokens) in p.n segments: segment i = tokens [t0, t1) of the sequence whose state goes
-// segs[i].in -> segs[i].out. Logits: ctx->d_logits[n][n_vocab], those of each segment's last token. The pass takes the place in the
+// One ragged pass of T tokens (ctx->d_tokens.p) in p.n segments: segment i = tokens [t0, t1) of the sequence whose state goes
+// segs[i].in -> segs[i].out. Logits: ctx->d_logits.p[n][n_vocab], those of each segment's last token. The pass takes the place in the
 // per-device chain that forward_rows takes, the sampler included.
 bool forward_segs(rwkv_context * ctx, const SegPass & p, int64_t T, bool want_logits, const RowSampler * sample, const ScorePass * score) {
-    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, !score || (!sample && ctx->d_score), "a scoring pass needs its buffers and takes no sampler");
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, !score || (!sample && ctx->d_score.p), "a scoring pass needs its buffers and takes no sampler");
     if (!ensure_scratch(ctx, T)) { (void) hipGetLastError(); ctx->last_error |= RWKV_ERROR_ALLOC; return false; }
     Model & m = *ctx->model;
     Runner r{ctx, m, ctx->stream, T, m.n_embed(), m.head_count, m.head_size, ctx->b};
@@ -1004,7 +962,7 @@ bool forward_streamed_eligible(const rwkv_context * ctx) {
     return (size_t) m.state_len() * sizeof(float) >= ((size_t) 4 << 20);   // small states: the serial copies are already cheap
 }
 
-// One token (already in ctx->d_tokens) from the caller's state_in (nullptr: the fresh state) into the caller's state_out (nullptr: none).
+// One token (already in ctx->d_tokens.p) from the caller's state_in (nullptr: the fresh state) into the caller's state_out (nullptr: none).
 // On return the streams are drained; *aborted reports a poll time-out of the persistent kernel (the caller repeats the step).
 bool forward_streamed(rwkv_context * ctx, bool want_logits, const float * h_in, float * h_out, float * h_logits, bool * aborted) {
     *aborted = false;
@@ -1056,8 +1014,8 @@ bool forward_streamed(rwkv_context * ctx, bool want_logits, const float * h_in, 
     }
     const int G = (int) gsz.size();
     const int64_t per = m.state_per_layer();
-    float * sin = ctx->state[ctx->cur];
-    float * sout = ctx->state[ctx->cur ^ 1];
+    float * sin = ctx->state[ctx->cur].p;
+    float * sout = ctx->state[ctx->cur ^ 1].p;
     // every fallible step of the set-up comes BEFORE the download job is published: a return between arming the worker and the final wait
     // would leave it inside a stale job holding the caller's pointer (it then finished the NEXT call's groups twice, the second time after
     // that call had returned)
@@ -1102,7 +1060,7 @@ bool forward_streamed(rwkv_context * ctx, bool want_logits, const float * h_in, 
     }
     if (chained) mega_chain_end(ctx);
     if (ok && want_logits && !head_done) r.run_head();
-    if (ok && h_logits) ok = hipMemcpyAsync(h_logits, ctx->d_logits, (size_t) m.n_vocab() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
+    if (ok && h_logits) ok = hipMemcpyAsync(h_logits, ctx->d_logits.p, (size_t) m.n_vocab() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
     const bool ctl_ok = !ctx->mega || ctx->mega->ctl.fetch(ctx->stream);
     const bool sync_ok = hipStreamSynchronize(ctx->stream) == hipSuccess;
     {   // the download thread must be done with this call whatever happened above (it holds the caller's pointer)

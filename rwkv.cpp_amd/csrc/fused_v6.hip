@@ -511,7 +511,7 @@ static void fused_v6_layer_t(const Model & m, const LayerW & L, float * x, const
     launch_profiled(pf, L.ffn_value->nbytes + qvec_bytes(F) + D * 12, k6_proj_res<FMT, 4, 4, true>, dim3((unsigned) ((D + 15) / 16)), dim3(256), ((qvec_bytes(F) + 15) / 16) * 16, st, g);
 }
 
-// ---- the projection / channel-mixing launches shared with the other architectures' fused layers (fused_v7.hip, fused_v4.hip) ----
+// ---- the projection / channel-mixing launches shared with the other architectures' fused layers (RWKV-7 and RWKV-4 / RWKV-5, both in fused_v7.hip) ----
 template <int FMT>
 static void fused_proj_res_t(const DevTensor * W, const void * act, float * x, const float * rgate, int64_t N, int64_t K, bool long_rows, hipStream_t st, rwkv_context::Prof * pf) {
     P6E e{planes(W), act, x, rgate, N, K};

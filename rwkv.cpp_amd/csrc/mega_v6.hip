@@ -763,17 +763,17 @@ __global__ void k_block_w2(const float * __restrict__ src, float * __restrict__ 
         dst[o] = src[i];
     }
 }
+void launch_block_w2(const float * src, float * dst, int D, int R) { hipLaunchKernelGGL(k_block_w2, dim3(512), dim3(256), 0, 0, src, dst, D, R); }
 
 struct MegaV6 : PersistentDecoder {
-    float * w2b = nullptr;
-    M6Layer * d_layers = nullptr;
-    void * xch = nullptr;
+    DevBuf<float> w2b;
+    DevBuf<M6Layer> d_layers;
+    DevBuf<uint8_t> xch;
     M6P proto{};
     int variant = -1, n_blocks = 0;
     size_t lds = 0;
     uint64_t algo_bytes = 0;   // algorithmic bytes of one launch: every layer tensor once + the recurrent state read and written
 
-    ~MegaV6() override;
     DecodePath kind() const override { return DecodePath::Regs; }
     uint64_t bytes() const override { return algo_bytes; }
     bool has_range() const override { return false; }   // one launch always covers every layer of the stage; nothing is folded into it
@@ -797,22 +797,12 @@ static const MegaVariant g_variants[] = {
     MEGA_VARIANTS(T_Q4_0), MEGA_VARIANTS(T_Q4_1), MEGA_VARIANTS(T_Q5_0), MEGA_VARIANTS(T_Q5_1), MEGA_VARIANTS(T_Q8_0),
 };
 
-static int mega_variant(const Model & m, int n_cu) {
-    if (m.arch_major != 6 || m.head_size != 64 || m.layer_end <= m.layer_begin) return -1;
-    const int64_t D = m.n_embed(), H = m.head_count;
-    const int fmt = (int) m.header.data_type;
-    const LayerW & L0 = m.layers[m.layer_begin];
-    if (!L0.ffn_key || !L0.att_time_decay_w1 || !L0.att_time_maa_w1) return -1;
-    const int64_t F = L0.ffn_key->ne[1], DR = L0.att_time_decay_w1->ne[1], R5 = L0.att_time_maa_w1->ne[1], R = R5 / 5;
+// the instantiation for a stage v6_stage_shape accepted (-1: none)
+static int mega_variant(const V6Shape & s, int n_cu) {
+    const int64_t D = s.D, F = s.F, DR = s.DR, R = s.R;
+    const int fmt = s.fmt;
     const int64_t NB = 256, NW = NB * 7;   // the kernel is laid out for exactly 256 workgroups (one per CU of an MI355X)
-    if (n_cu != NB || H > NB || F % 32 != 0 || 5 * (D / 64) + R5 + DR > NW || !(R == 32 || R == 64)) return -1;
-    for (uint32_t i = m.layer_begin; i < m.layer_end; i++) {
-        const LayerW & L = m.layers[i];
-        const DevTensor * mats[] = {L.att_receptance, L.att_key, L.att_value, L.att_gate, L.att_output, L.att_time_maa_w1,
-                                    L.att_time_decay_w1, L.att_time_decay_w2, L.ffn_key, L.ffn_value, L.ffn_receptance};
-        for (const DevTensor * t : mats) if (!t || t->type != fmt) return -1;
-        if (L.ffn_key->ne[1] != F || L.att_time_decay_w1->ne[1] != DR || L.att_time_maa_w1->ne[1] != R5) return -1;
-    }
+    if (n_cu != NB || s.H > NB || F % 32 != 0 || 5 * (D / 64) + s.R5 + DR > NW || !(R == 32 || R == 64)) return -1;
     for (size_t v = 0; v < sizeof(g_variants) / sizeof(g_variants[0]); v++) {
         const MegaVariant & mv = g_variants[v];
         if (mv.fmt == fmt && D == mv.ept * 512 && 3 * (F / 32) <= (int64_t) mv.kqu * 64 && DR == mv.nbd * 32 && (F / 32 + NB - 1) / NB == mv.gpb) return (int) v;
@@ -820,90 +810,51 @@ static int mega_variant(const Model & m, int n_cu) {
     return -1;
 }
 
-MegaV6::~MegaV6() {
-    if (d_layers) (void) hipFree(d_layers);
-    if (w2b) (void) hipFree(w2b);
-    if (xch) (void) hipFree(xch);
-}
-
 // Returns nullptr when the model / device does not qualify (the caller keeps the seven-launch path).
 PersistentDecoder * mega_v6_create(const Model & m) {
     hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, m.device) != hipSuccess) return nullptr;
+    V6Shape shape;
+    if (hipGetDeviceProperties(&prop, m.device) != hipSuccess || !v6_stage_shape(m, shape)) return nullptr;
     const int NB = prop.multiProcessorCount;
-    const int v = mega_variant(m, NB);
+    const int v = mega_variant(shape, NB);
     if (v < 0) return nullptr;
-    const LayerW & L0 = m.layers[m.layer_begin];
-    const int64_t D = m.n_embed(), F = L0.ffn_key->ne[1], DR = L0.att_time_decay_w1->ne[1], R = L0.att_time_maa_w1->ne[1] / 5;
-    MegaV6 * mg = new MegaV6();
+    const int64_t D = shape.D, F = shape.F, DR = shape.DR, R = shape.R;
+    std::unique_ptr<MegaV6> mg(new MegaV6());
     mg->variant = v; mg->n_blocks = NB;
     mg->lds = m6_lds((int) D, (int) F).total;
-    if (mg->lds > (size_t) prop.sharedMemPerBlock && hipFuncSetAttribute((const void *) g_variants[v].fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) mg->lds) != hipSuccess) {
-        delete mg; return nullptr;
-    }
+    if (mg->lds > (size_t) prop.sharedMemPerBlock && hipFuncSetAttribute((const void *) g_variants[v].fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) mg->lds) != hipSuccess) return nullptr;
     (void) hipFuncSetAttribute((const void *) g_variants[v].fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) mg->lds);
     const size_t w2_layer = (size_t) 5 * R * D;
-    if (R % 4 != 0 || hipMalloc((void **) &mg->w2b, w2_layer * (m.layer_end - m.layer_begin) * sizeof(float)) != hipSuccess) { delete mg; return nullptr; }
-    std::vector<M6Layer> hl;
-    const unsigned char * abase = (const unsigned char *) m.arena;
-    bool in_arena = true;
-    auto off = [&](const void * ptr) -> long long {
-        const long long o = (const unsigned char *) ptr - abase;
-        if (!ptr || o < 0 || (uint64_t) o >= m.arena_bytes) in_arena = false;
-        return o;
-    };
-    auto f = [&](const DevTensor * t) { return off(t->data); };
-    auto pl3 = [&](const DevTensor * t) { M6Off o; o.qs = off(t->qs); o.qh = t->qh ? off(t->qh) : 0; o.sc = off(t->sc); return o; };
-    uint64_t bytes = 0;
-    for (uint32_t i = m.layer_begin; i < m.layer_end; i++) {
-        const LayerW & L = m.layers[i];
-        M6Layer d{};
-        d.ln1_w = f(L.ln1_w); d.ln1_b = f(L.ln1_b); d.maa_x = f(L.att_time_maa_x);
-        d.maa[0] = f(L.att_time_maa_w); d.maa[1] = f(L.att_time_maa_k); d.maa[2] = f(L.att_time_maa_v); d.maa[3] = f(L.att_time_maa_r); d.maa[4] = f(L.att_time_maa_g);
-        d.w2b = (long long) hl.size() * 5 * R * D; d.time_decay = f(L.att_time_decay); d.faaaa = f(L.att_time_faaaa);
-        d.lnx_w = f(L.att_ln_x_w); d.lnx_b = f(L.att_ln_x_b); d.ln2_w = f(L.ln2_w); d.ln2_b = f(L.ln2_b);
-        d.fmaa_k = f(L.ffn_time_maa_k); d.fmaa_r = f(L.ffn_time_maa_r);
-        d.w1 = pl3(L.att_time_maa_w1);
-        d.rkvg[0] = pl3(L.att_receptance); d.rkvg[1] = pl3(L.att_key); d.rkvg[2] = pl3(L.att_value); d.rkvg[3] = pl3(L.att_gate);
-        d.dw1 = pl3(L.att_time_decay_w1); d.dw2 = pl3(L.att_time_decay_w2); d.wo = pl3(L.att_output);
-        d.fk = pl3(L.ffn_key); d.fr = pl3(L.ffn_receptance); d.fv = pl3(L.ffn_value);
-        hipLaunchKernelGGL(k_block_w2, dim3(512), dim3(256), 0, 0, (const float *) L.att_time_maa_w2->data, mg->w2b + hl.size() * w2_layer, (int) D, (int) R);
-        hl.push_back(d);
-        const DevTensor * all[] = {L.ln1_w, L.ln1_b, L.att_time_maa_x, L.att_time_maa_w, L.att_time_maa_k, L.att_time_maa_v, L.att_time_maa_r, L.att_time_maa_g,
-                                   L.att_time_maa_w1, L.att_time_maa_w2, L.att_time_decay, L.att_time_faaaa, L.att_time_decay_w1, L.att_time_decay_w2,
-                                   L.att_receptance, L.att_key, L.att_value, L.att_gate, L.att_output, L.att_ln_x_w, L.att_ln_x_b, L.ln2_w, L.ln2_b,
-                                   L.ffn_time_maa_k, L.ffn_time_maa_r, L.ffn_key, L.ffn_value, L.ffn_receptance};
-        for (const DevTensor * t : all) if (t) bytes += t->nbytes;
-        bytes += 2 * (uint64_t) m.state_per_layer() * sizeof(float);
-    }
-    mg->algo_bytes = bytes;
-    if (!in_arena) { delete mg; return nullptr; }
+    if (R % 4 != 0 || mg->w2b.alloc(w2_layer * (m.layer_end - m.layer_begin)) != hipSuccess) return nullptr;
+    const V6Table tab = v6_layer_table(m, w2_layer);
+    const std::vector<M6Layer> & hl = tab.layers;
+    mg->algo_bytes = tab.bytes;
+    if (!tab.in_arena) return nullptr;
+    for (size_t i = 0; i < hl.size(); i++)
+        launch_block_w2((const float *) m.layers[m.layer_begin + i].att_time_maa_w2->data, mg->w2b.p + i * w2_layer, (int) D, (int) R);
     const int64_t nbD = D / 32, nbF = F / 32;
     const int64_t PAD = 2048;   // polls read whole 64-lane rounds: keep every buffer readable past its end
     auto up = [](int64_t v) { return (v + 63) / 64 * 64; };
     const int64_t act_stride = up(3 * nbD), xunits = up(256 * 8);
     const int64_t sizes[9] = {up(1280) + PAD, 5 * act_stride + PAD, 2 * D + PAD, 256 + PAD, act_stride + PAD, xunits + PAD, up(3 * nbF) + PAD, xunits + PAD, xunits + PAD};
-    int64_t units = 0;
-    for (int64_t z : sizes) units += z;
-    bool ok = hipMalloc((void **) &mg->d_layers, hl.size() * sizeof(M6Layer)) == hipSuccess
-           && hipMemcpy(mg->d_layers, hl.data(), hl.size() * sizeof(M6Layer), hipMemcpyHostToDevice) == hipSuccess
-           && hipMalloc(&mg->xch, (size_t) units * 16) == hipSuccess && hipMemset(mg->xch, 0, (size_t) units * 16) == hipSuccess
-           && mg->ctl.alloc(8u);
-    if (!ok) { delete mg; return nullptr; }
     M6P & q = mg->proto;
-    q.layers = mg->d_layers; q.n_layers = (int) hl.size();
-    q.arena = abase; q.w2b = mg->w2b;
-    if (hipDeviceSynchronize() != hipSuccess) { delete mg; return nullptr; }
+    int * const slots[9] = {&q.tl, &q.act5, &q.rkvg, &q.dl, &q.yq, &q.xatt, &q.kq, &q.rr, &q.xffn};
+    const int64_t units = carve_exchange(sizes, 9, slots);
+    bool ok = mg->d_layers.alloc(hl.size()) == hipSuccess
+           && hipMemcpy(mg->d_layers.p, hl.data(), hl.size() * sizeof(M6Layer), hipMemcpyHostToDevice) == hipSuccess
+           && mg->xch.alloc((size_t) units * 16) == hipSuccess && hipMemset(mg->xch.p, 0, (size_t) units * 16) == hipSuccess
+           && mg->ctl.alloc(8u);
+    if (!ok) return nullptr;
+    q.layers = mg->d_layers.p; q.n_layers = (int) hl.size();
+    q.arena = (const unsigned char *) m.arena; q.w2b = mg->w2b.p;
+    if (hipDeviceSynchronize() != hipSuccess) return nullptr;
     q.state_stride = m.state_per_layer();
-    q.xch = mg->xch; q.xch_bytes = (unsigned) (units * 16);
-    int u = 0;
-    int * slots[9] = {&q.tl, &q.act5, &q.rkvg, &q.dl, &q.yq, &q.xatt, &q.kq, &q.rr, &q.xffn};
-    for (int i = 0; i < 9; i++) { *slots[i] = u; u += (int) sizes[i]; }
+    q.xch = mg->xch.p; q.xch_bytes = (unsigned) (units * 16);
     q.act_stride = act_stride;
-    q.ctl = mg->ctl.dev;
+    q.ctl = mg->ctl.dev.p;
     q.F = (int) F; q.DR = (int) DR; q.R = (int) R; q.H = (int) m.head_count;
     q.gpb = (int) ((nbF + NB - 1) / NB);
-    return mg;
+    return mg.release();
 }
 
 // sin / sout: state of the stage's FIRST layer. One launch covers every layer of the stage.

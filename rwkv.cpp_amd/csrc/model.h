@@ -7,6 +7,7 @@
 #include <mutex>
 
 #include "common.h"
+#include "devmem.h"
 #include "kernels.h"
 #include "persist_host.h"
 #include "rwkv_mi355x.h"
@@ -155,24 +156,21 @@ bool    scan_stage_costs(const char * path, std::vector<uint64_t> & per_layer, u
 // ---------------------------------------------------------------------------------------------------------------
 
 namespace rwkvmi {
+enum class FusedLayer { none, v4, v6, v7 };   // which fused per-layer decode path a context runs (at most one exists for a model)
+
 // The report of a context's or a batch's emitting calls (rwkv_mi_*set_logprobs): whether it is on and with how many alternatives; the device
 // buffers, laid out like the loops' history -- chosen[steps][rows], ids / vals [steps][rows][top_n] -- allocated by the first reporting call
 // and grown to the largest since; and what the last reporting call left in them (valid: there is one). lens[r]: the steps row r wrote.
 struct LogprobReport {
     bool enabled = false;
     uint32_t top_n = 0;
-    float * d_chosen = nullptr;
-    uint32_t * d_ids = nullptr;
-    float * d_vals = nullptr;
-    size_t cap = 0, cap_top = 0;   // entries of d_chosen; of d_ids and d_vals
+    DevBuf<float> d_chosen;        // .count: the entries the buffers were sized for ...
+    DevBuf<uint32_t> d_ids;        // ... and entries * top_n of d_ids and d_vals
+    DevBuf<float> d_vals;
     bool valid = false;
     size_t rows = 0, steps = 0;
     uint32_t last_top_n = 0;
     std::vector<uint32_t> lens;
-    void release() {
-        for (void * p : {(void *) d_chosen, (void *) d_ids, (void *) d_vals}) if (p) (void) hipFree(p);
-        d_chosen = nullptr; d_ids = nullptr; d_vals = nullptr; cap = cap_top = 0; valid = false;
-    }
 };
 }  // namespace rwkvmi
 
@@ -186,13 +184,12 @@ struct rwkv_context {
     bool owns_stream = true;   // false after rwkv_mi_set_stream (the caller's stream, e.g. torch's current stream)
 
     // Device-resident recurrent state, ping-pong (kernels read [cur], write [cur ^ 1]).
-    float * state[2] = {nullptr, nullptr};
+    rwkvmi::DevBuf<float> state[2];
     int cur = 0;
 
     // Scratch for T tokens (grown on demand).
     int64_t scratch_T = 0;
-    void *  scratch = nullptr;
-    size_t  scratch_bytes = 0;
+    rwkvmi::DevBuf<uint8_t> scratch;   // (.count: its bytes)
     struct Buf {
         float *x, *xn, *sx, *m[6], *r, *k, *v, *g, *w, *a, *t0, *t1, *t2, *out, *ffk, *lr1, *lr2, *v_first, *xlast;
         rwkvmi::QAct qa;
@@ -201,30 +198,26 @@ struct rwkv_context {
         rwkvmi::MmqWs ws;         // workspace of the split walk (prefill.hip)
     } b{};
 
-    uint32_t * d_tokens = nullptr;
-    int64_t    d_tokens_cap = 0;
-    float *    d_logits = nullptr;
-    uint32_t * d_next_token = nullptr;
-    float *    d_probs = nullptr;                 // sampler scratch (sample_scratch_floats(n_vocab) floats), allocated on first use
-    unsigned long long * d_rng_counter = nullptr;
-    uint32_t * d_counts = nullptr;                // penalised sampling (rwkv_mi_*_penalized): the context's occurrence table [n_vocab] and its bias table
-    float *    d_bias = nullptr;                  // [n_vocab], allocated by the first call of that family; has_bias: a bias has been set and not cleared
+    rwkvmi::DevBuf<uint32_t> d_tokens;            // the token words of a pass and their pinned staging, grown together (.count: the capacity)
+    rwkvmi::PinBuf<uint32_t> h_tokens;
+    rwkvmi::DevBuf<float>    d_logits;
+    rwkvmi::DevBuf<uint32_t> d_next_token;
+    rwkvmi::DevBuf<float>    d_probs;             // sampler scratch (sample_scratch_floats(n_vocab) floats), allocated on first use
+    rwkvmi::DevBuf<unsigned long long> d_rng_counter;
+    rwkvmi::DevBuf<uint32_t> d_counts;            // penalised sampling (rwkv_mi_*_penalized): the context's occurrence table [n_vocab] and its bias table
+    rwkvmi::DevBuf<float>    d_bias;              // [n_vocab], allocated by the first call of that family; has_bias: a bias has been set and not cleared
     bool       has_bias = false;
     // scoring (rwkv_mi_score_resident / rwkv_mi_batch_score_ragged; engine.hip ensure_score), allocated by the first scoring call: the chunk
     // of the all-position head, [score_R][n_vocab] logits, and the per-row words of a pass for score_cap rows -- targets in (with their
     // pinned staging), log-probs and argmax out
-    float *    d_score = nullptr;
+    rwkvmi::DevBuf<float>    d_score;
     int64_t    score_R = 0;
-    uint32_t * d_score_targets = nullptr;
-    uint32_t * h_score_targets = nullptr;
-    float *    d_score_logprobs = nullptr;
-    uint32_t * d_score_argmax = nullptr;
+    rwkvmi::DevBuf<uint32_t> d_score_targets;
+    rwkvmi::PinBuf<uint32_t> h_score_targets;
+    rwkvmi::DevBuf<float>    d_score_logprobs;
+    rwkvmi::DevBuf<uint32_t> d_score_argmax;
     int64_t    score_cap = 0;
     rwkvmi::LogprobReport lp;                     // the report of the context's draws (rwkv_mi_set_logprobs)
-
-    // pinned host staging for tokens / logits
-    uint32_t * h_tokens = nullptr;
-    int64_t    h_tokens_cap = 0;
 
     // captured single-token graphs: [cur][with_logits]
     hipGraphExec_t graph_exec[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
@@ -246,11 +239,9 @@ struct rwkv_context {
                                           // persistent launch, the per-device chain does not wait on it a second time
     std::string persist_note;         // why this context runs the single-token path it runs (rwkv_mi_persist_info: chosen kernel, calibration, fall-backs)
 
-    // fused single-token path (fused_v6.hip) when the model qualifies
-    bool  fused_v6 = false;
-    bool  fused_v7 = false;   // fused RWKV-7 layer (fused_v7.hip)
-    bool  fused_v4 = false;   // fused RWKV-4 / RWKV-5 layer (fused_v4.hip)
-    void * fused_scratch = nullptr;
+    // fused single-token layer when the model qualifies: RWKV-6 (fused_v6.hip), RWKV-7 or RWKV-4 / RWKV-5 (both in fused_v7.hip)
+    rwkvmi::FusedLayer fused = rwkvmi::FusedLayer::none;
+    rwkvmi::DevBuf<uint8_t> fused_scratch;
     // persistent whole-stage decode kernel (persist_host.h) when the model and the device qualify; takes precedence
     std::unique_ptr<rwkvmi::PersistentDecoder> mega;
 
@@ -359,6 +350,7 @@ void abi_streamer_free(void * p);
 bool forward_decode(rwkv_context * ctx, bool want_logits);
 bool single_launch_step(const rwkv_context * ctx, bool want_logits);
 hipEvent_t mega_chain_marker(rwkv_context * ctx);   // the event recorded behind ctx's persistent launch if that launch is the latest of its device (else nullptr)   // the step is one directly issued persistent launch (no graph replay)
+void drop_graphs(rwkv_context * ctx);   // the captured single-token graphs hold pointers: dropped when a buffer they name moves
 // grows the per-context activation scratch to hold T tokens
 bool ensure_scratch(rwkv_context * ctx, int64_t T);
 uint32_t * folded_argmax_target(const rwkv_context * ctx);

@@ -16,11 +16,7 @@ typedef volatile __attribute__((address_space(1))) v4u gv4u;
 // generic (FLAT) loads also count on the LDS counter -- every LDS wait would then wait for the weight prefetch in flight;
 // arena (a kernel argument, known global) + offset keeps the weight stream on vmcnt alone. Fields are fetched with
 // scalar loads where they are used, not held across the layer.
-struct M6Off { long long qs, qh, sc; };
-struct M6Layer {
-    long long ln1_w, ln1_b, maa_x, maa[5], w2b /* floats into M6P::w2b */, time_decay, faaaa, lnx_w, lnx_b, ln2_w, ln2_b, fmaa_k, fmaa_r;
-    M6Off w1, rkvg[4], dw1, dw2, wo, fk, fr, fv;
-};
+// (M6Off, M6Layer: persist_host.h, with the host code that fills them)
 struct M6Arena {
     const unsigned char * base;
     __device__ __forceinline__ const float * f(long long off) const { return reinterpret_cast<const float *>(base + off); }

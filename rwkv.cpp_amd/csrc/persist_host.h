@@ -9,6 +9,8 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
+#include "devmem.h"
+
 namespace rwkvmi {
 
 // The single-token path of a stage: what a handle is (Regs / Ring / K47) and what the first context of a model measured as fastest
@@ -51,13 +53,12 @@ static void launch_profiled(DecodeProf * pf, uint64_t bytes, Kern kernel, dim3 g
 // the caller's own stream synchronisation. (A blocking hipMemcpy would go through the legacy null stream and couple every blocking
 // stream of the process.)
 struct PersistCtl {
-    unsigned * dev = nullptr;
-    unsigned * host = nullptr;   // pinned mirror of dev[0..1], refreshed by fetch()
+    DevBuf<unsigned> dev;
+    PinBuf<unsigned> host;       // pinned mirror of dev[0..1], refreshed by fetch()
 
     bool alloc(unsigned generation);   // zeroed words, then {generation, 0} on the device and in the mirror
-    void release();
     bool fetch(hipStream_t st) const;                  // async copy of the control words into the mirror
-    bool aborted_cached() const { return host[1] != 0; }   // the mirror's abort word (valid after the stream was synchronised)
+    bool aborted_cached() const { return host.p[1] != 0; }   // the mirror's abort word (valid after the stream was synchronised)
     bool aborted(hipStream_t st) const;                // fetch + synchronise + check
     unsigned generation(hipStream_t st) const;         // fetch + synchronise; 0 on failure
     // clears the abort word (after the caller has drained the stream), so that the handle -- or the context that drops it -- is usable again
@@ -98,10 +99,51 @@ struct PersistentDecoder {
 
 protected:
     float * x_out = nullptr;
-    long long * trace_buf = nullptr;
+    DevBuf<long long> trace_buf;
     // the body of trace(): a zeroed buffer of n + extra stamps on first use, bound to the kernel's parameter slots; fetch copies the first
     // n out (extra: the ring loader's samples, dumped raw to the file RWKV_MI_RING_LTRACE names)
     bool trace_into(long long *& slot, int & slot_layer, int layer, size_t n, size_t extra, long long * out, bool fetch);
 };
+
+// ---- what the creators of the persistent kernels share (bodies: persist_host.cpp) ----
+
+struct Model;
+
+// The per-layer table of the RWKV-6 kernels (persist.h says why offsets): byte offsets from the parameter arena, three planes per matrix.
+struct M6Off { long long qs, qh, sc; };
+struct M6Layer {
+    long long ln1_w, ln1_b, maa_x, maa[5], w2b /* floats into M6P::w2b */, time_decay, faaaa, lnx_w, lnx_b, ln2_w, ln2_b, fmaa_k, fmaa_r;
+    M6Off w1, rkvg[4], dw1, dw2, wo, fk, fr, fv;
+};
+
+// Offsets of a model's parameters from its arena. in_arena is sticky: false once an address was null or outside the arena (the kernels
+// address every weight as arena + offset, so such a model does not qualify).
+struct ArenaOffsets {
+    const unsigned char * base;
+    uint64_t bytes;
+    bool in_arena = true;
+    explicit ArenaOffsets(const Model & m);
+    long long off(const void * ptr);
+    long long f(const DevTensor * t) { return off(t->data); }                  // a tensor the architecture always has
+    long long f_opt(const DevTensor * t) { return t ? off(t->data) : 0; }      // one a layer may lack (persist_v47.hip): offset 0, no failure
+    M6Off pl3(const DevTensor * t);                                            // the planes of a quantised matrix
+};
+
+// What both RWKV-6 kernels ask of a stage before their own geometry test: RWKV-6 with 64-wide heads, a non-empty layer range, the eleven
+// matrices of every layer present and of the file's one format, F / DR / R5 the same in every layer. false: no persistent RWKV-6 kernel.
+struct V6Shape { int64_t D, F, DR, R5, R, H; int fmt; };
+bool v6_stage_shape(const Model & m, V6Shape & s);
+
+// The layer table of the stage (layer i's blocked W2 at i * w2_layer floats), the algorithmic bytes of one launch over it -- every layer
+// tensor once + the recurrent state read and written -- and whether every address was inside the arena.
+struct V6Table { std::vector<M6Layer> layers; uint64_t bytes = 0; bool in_arena = true; };
+V6Table v6_layer_table(const Model & m, size_t w2_layer);
+
+// W2 ([5][R][D] floats) into the chunk-blocked layout both RWKV-6 kernels read, on the null stream (the kernel: mega_v6.hip, k_block_w2)
+void launch_block_w2(const float * src, float * dst, int D, int R);
+
+// The exchange arena of a kernel: slot i starts at unit *slots[i], the units of sizes[0 .. i) before it; returns the units of all n. The size
+// lists are the kernels' own.
+int64_t carve_exchange(const int64_t * sizes, int n, int * const * slots);
 
 }  // namespace rwkvmi

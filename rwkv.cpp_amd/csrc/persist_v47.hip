@@ -1482,8 +1482,8 @@ __global__ __launch_bounds__(576) void k47_persist(P47 p) {
 constexpr int P47_CALM_DEFAULT = 1;    // P47::calm without RWKV_MI_P47_CALM
 
 struct P47Handle : PersistentDecoder {
-    P47Layer * d_layers = nullptr;
-    void * xch = nullptr;
+    DevBuf<P47Layer> d_layers;
+    DevBuf<uint8_t> xch;
     P47 proto{};
     int variant = -1, n_blocks = 0, n_layers = 0, n_cu = 0;
     size_t lds = 0;
@@ -1491,7 +1491,6 @@ struct P47Handle : PersistentDecoder {
     bool fold_embed = false, fold_head = false;
     uint64_t embed_bytes = 0, head_bytes = 0;
 
-    ~P47Handle() override;
     DecodePath kind() const override { return DecodePath::K47; }
     uint64_t bytes() const override { uint64_t s = embed_bytes + head_bytes; for (uint64_t b : layer_bytes) s += b; return s; }
     bool folds_embed() const override { return fold_embed; }
@@ -1552,11 +1551,6 @@ static int p47_variant(const Model & m, int n_cu) {
     return -1;
 }
 
-P47Handle::~P47Handle() {
-    if (d_layers) (void) hipFree(d_layers);
-    if (xch) (void) hipFree(xch);
-}
-
 // Returns nullptr when the model / device does not qualify (the caller keeps the fused per-layer launches).
 PersistentDecoder * p47_create(const Model & m) {
     hipDeviceProp_t prop;
@@ -1566,20 +1560,14 @@ PersistentDecoder * p47_create(const Model & m) {
     const P47Variant & pv = g_p47[v];
     const int64_t D = m.n_embed(), F = 4 * D;
     const bool v7 = m.arch_major == 7;
-    P47Handle * g = new P47Handle();
+    std::unique_ptr<P47Handle> g(new P47Handle());
     g->variant = v; g->n_blocks = pv.nblk; g->n_cu = prop.multiProcessorCount;
     g->lds = l47_lds((int) D, v7).total;
-    if (hipFuncSetAttribute((const void *) pv.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) g->lds) != hipSuccess) { delete g; return nullptr; }
+    if (hipFuncSetAttribute((const void *) pv.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) g->lds) != hipSuccess) return nullptr;
     std::vector<P47Layer> hl;
-    const unsigned char * abase = (const unsigned char *) m.arena;
-    bool in_arena = true;
-    auto off = [&](const void * ptr) -> long long {
-        const long long o = (const unsigned char *) ptr - abase;
-        if (!ptr || o < 0 || (uint64_t) o >= m.arena_bytes) in_arena = false;
-        return o;
-    };
-    auto f = [&](const DevTensor * t) -> long long { return t ? off(t->data) : 0; };
-    auto pl3 = [&](const DevTensor * t) { M6Off o; o.qs = off(t->qs); o.qh = t->qh ? off(t->qh) : 0; o.sc = off(t->sc); return o; };
+    ArenaOffsets ao(m);
+    auto f = [&](const DevTensor * t) { return ao.f_opt(t); };   // (a tensor a layer lacks -- layer 0's v1, v0 -- is offset 0)
+    auto pl3 = [&](const DevTensor * t) { return ao.pl3(t); };
     for (uint32_t i = m.layer_begin; i < m.layer_end; i++) {
         const LayerW & L = m.layers[i];
         P47Layer d{};
@@ -1605,7 +1593,7 @@ PersistentDecoder * p47_create(const Model & m) {
             for (int k = 0; k < 4; k++) {
                 d.lr1[k] = l1[k] ? f(l1[k]) : f(l1[0]); d.lr2[k] = l2[k] ? f(l2[k]) : f(l2[0]);
                 d.rank[k] = l1[k] ? (int) l1[k]->ne[1] : 0; d.lbase[k] = basev; basev += d.rank[k];
-                if (d.rank[k] % 4 != 0) in_arena = false;
+                if (d.rank[k] % 4 != 0) ao.in_arena = false;
                 if (l1[k]) all.push_back(l1[k]);
                 if (l2[k]) all.push_back(l2[k]);
             }
@@ -1620,28 +1608,25 @@ PersistentDecoder * p47_create(const Model & m) {
         g->layer_bytes.push_back(bytes);
         hl.push_back(d);
     }
-    if (!in_arena) { delete g; return nullptr; }
+    if (!ao.in_arena) return nullptr;
     g->n_layers = (int) hl.size();
     const int64_t nbD = D / 32, nbF = F / 32;
     const int64_t PAD = 2048;   // polls read whole 64-lane rounds: keep every buffer readable past its end
     auto up = [](int64_t x) { return (x + 63) / 64 * 64; };
     const int64_t sizes[7] = {up(D) + PAD, 2048 + PAD, up(3 * nbD > D ? 3 * nbD : D) + PAD, up(D) + PAD, up(3 * nbF) + PAD, up(D) + PAD, 256 + PAD};
-    int64_t units = 0;
-    for (int64_t z : sizes) units += z;
-    bool ok = hipMalloc((void **) &g->d_layers, hl.size() * sizeof(P47Layer)) == hipSuccess
-           && hipMemcpy(g->d_layers, hl.data(), hl.size() * sizeof(P47Layer), hipMemcpyHostToDevice) == hipSuccess
-           && hipMalloc(&g->xch, (size_t) units * 16) == hipSuccess && hipMemset(g->xch, 0, (size_t) units * 16) == hipSuccess
-           && g->ctl.alloc(16u);
-    if (!ok) { delete g; return nullptr; }
     P47 & q = g->proto;
-    q.layers = g->d_layers; q.l0 = 0; q.l1 = g->n_layers;
-    q.arena = abase;
+    int * const slots[7] = {&q.u_a, &q.u_lr1, &q.u_y, &q.u_xatt, &q.u_kq, &q.u_xffn, &q.u_am};
+    const int64_t units = carve_exchange(sizes, 7, slots);
+    bool ok = g->d_layers.alloc(hl.size()) == hipSuccess
+           && hipMemcpy(g->d_layers.p, hl.data(), hl.size() * sizeof(P47Layer), hipMemcpyHostToDevice) == hipSuccess
+           && g->xch.alloc((size_t) units * 16) == hipSuccess && hipMemset(g->xch.p, 0, (size_t) units * 16) == hipSuccess
+           && g->ctl.alloc(16u);
+    if (!ok) return nullptr;
+    q.layers = g->d_layers.p; q.l0 = 0; q.l1 = g->n_layers;
+    q.arena = ao.base;
     q.state_stride = m.state_per_layer();
-    q.xch = g->xch; q.xch_bytes = (unsigned) (units * 16);
-    int u = 0;
-    int * slots[7] = {&q.u_a, &q.u_lr1, &q.u_y, &q.u_xatt, &q.u_kq, &q.u_xffn, &q.u_am};
-    for (int i = 0; i < 7; i++) { *slots[i] = u; u += (int) sizes[i]; }
-    q.ctl = g->ctl.dev;
+    q.xch = g->xch.p; q.xch_bytes = (unsigned) (units * 16);
+    q.ctl = g->ctl.dev.p;
     q.V = (int) m.n_vocab();
     // embedding + ln0 and ln_out + head + argmax inside the launch where the stage has them in a dtype the kernel reads (RWKV_MI_P47_NOFOLD=1: measurement aid)
     const char * nofold = getenv("RWKV_MI_P47_NOFOLD");
@@ -1660,8 +1645,8 @@ PersistentDecoder * p47_create(const Model & m) {
     // long waits (spare and head workgroups) on one unit instead of the full-width poll; RWKV_MI_P47_CALM=0..3 selects which (measurement aid)
     const char * calm = getenv("RWKV_MI_P47_CALM");
     q.calm = calm && calm[0] >= '0' && calm[0] <= '9' ? atoi(calm) : P47_CALM_DEFAULT;
-    if (!in_arena) { delete g; return nullptr; }
-    return g;
+    if (!ao.in_arena) return nullptr;
+    return g.release();
 }
 
 // layers [l0, l1) of the stage (indices into the stage's own layer table); sin / sout: state of the stage's first layer. tok (device): the

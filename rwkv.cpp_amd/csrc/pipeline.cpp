@@ -140,7 +140,7 @@ static bool stage_state_in(rwkv_context * c, const float * state_in) {
     Model & m = *c->model;
     const int64_t per = m.state_per_layer();
     const int64_t off = (int64_t) m.layer_begin * per, cnt = (int64_t) (m.layer_end - m.layer_begin) * per;
-    float * dst = c->state[c->cur] + off;
+    float * dst = c->state[c->cur].p + off;
     if (state_in) {
         HIP_FRONT_OK(c, hipMemcpyAsync(dst, state_in + off, (size_t) cnt * sizeof(float), hipMemcpyHostToDevice, c->stream));
         return true;
@@ -151,7 +151,7 @@ static bool stage_state_out(rwkv_context * c, float * state_out) {
     Model & m = *c->model;
     const int64_t per = m.state_per_layer();
     const int64_t off = (int64_t) m.layer_begin * per, cnt = (int64_t) (m.layer_end - m.layer_begin) * per;
-    HIP_FRONT_OK(c, hipMemcpyAsync(state_out + off, c->state[c->cur] + off, (size_t) cnt * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_FRONT_OK(c, hipMemcpyAsync(state_out + off, c->state[c->cur].p + off, (size_t) cnt * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     return true;
 }
 
@@ -211,7 +211,7 @@ bool pipeline_eval(rwkv_context * front, const uint32_t * tokens, size_t n, size
         if (state_out && !stage_state_out(c, state_out)) return fail(c);
     }
     rwkv_context * tail = st[S - 1];
-    if (logits_out && hipMemcpyAsync(logits_out, tail->d_logits, (size_t) tail->model->n_vocab() * sizeof(float), hipMemcpyDeviceToHost, tail->stream) != hipSuccess) return fail(tail);
+    if (logits_out && hipMemcpyAsync(logits_out, tail->d_logits.p, (size_t) tail->model->n_vocab() * sizeof(float), hipMemcpyDeviceToHost, tail->stream) != hipSuccess) return fail(tail);
     for (rwkv_context * c : st) {
         if (hipSetDevice(c->model->device) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return fail(c);
         if (c->mega && c->mega->ctl.aborted(c->stream)) { recover_from_abort(c); front->last_error |= RWKV_ERROR_GRAPH; return false; }

@@ -1949,15 +1949,6 @@ __global__ void k_ring_pack_head(const unsigned short * __restrict__ head, int n
     }
 }
 
-__global__ void k_block_w2_ring(const float * __restrict__ src, float * __restrict__ dst, int D, int R) {   // (layout: see k_block_w2, mega_v6.hip)
-    const long long n = 5ll * R * D;
-    for (long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long) gridDim.x * blockDim.x) {
-        const int d = (int) (i % D); const long long fm = i / D; const int m = (int) (fm % R), f = (int) (fm / R);
-        const long long o = ((((long long) f * (D / 64) + d / 64) * (R / 4) + m / 4) * 64 + d % 64) * 4 + m % 4;
-        dst[o] = src[i];
-    }
-}
-
 // What a context's ring kernel derives from the WEIGHTS alone -- the per-workgroup streams (3.9 GB + 0.5 GB of head for the 7B Q4_0),
 // the chunk-blocked W2, the layer table -- is built once per Model and shared by every context of it (rwkv_clone_context, the decode
 // streams of a pipeline stage: the reference's clones share their weights too, rwkv.cpp:109-143). Round 3 built it per context:
@@ -1965,10 +1956,10 @@ __global__ void k_block_w2_ring(const float * __restrict__ src, float * __restri
 // pointer (Model::ring_shared, under Model::derived_mu) only while a handle holds it.
 struct RingShared {
     int ref = 0;
-    float * w2b = nullptr;
-    M6Layer * d_layers = nullptr;
-    R6Cu * d_cus = nullptr;
-    unsigned char * stream = nullptr;
+    DevBuf<float> w2b;
+    DevBuf<M6Layer> d_layers;
+    DevBuf<R6Cu> d_cus;
+    DevBuf<unsigned char> stream;
     int variant = -1, n_blocks = 0, n_layers = 0;
     size_t lds = 0, ring = 0, mirror = 0;
     uint64_t bytes = 0;
@@ -1983,7 +1974,7 @@ struct RingShared {
 struct RingV6 : PersistentDecoder {
     const Model * model = nullptr;
     RingShared * sh = nullptr;
-    void * xch = nullptr;
+    DevBuf<uint8_t> xch;
     R6P proto{};
 
     ~RingV6() override;
@@ -2012,23 +2003,13 @@ static const RingVariant g_ring_variants[] = {
 #endif
 };
 
-static int ring_variant(const Model & m, int n_cu) {
-    if (m.arch_major != 6 || m.head_size != 64 || m.layer_end <= m.layer_begin) return -1;
-    const int64_t D = m.n_embed(), H = m.head_count;
-    const int fmt = (int) m.header.data_type;
-    const LayerW & L0 = m.layers[m.layer_begin];
-    if (!L0.ffn_key || !L0.att_time_decay_w1 || !L0.att_time_maa_w1) return -1;
-    const int64_t F = L0.ffn_key->ne[1], DR = L0.att_time_decay_w1->ne[1], R5 = L0.att_time_maa_w1->ne[1], R = R5 / 5;
+// the instantiation for a stage v6_stage_shape accepted (-1: none)
+static int ring_variant(const V6Shape & s, int n_cu) {
+    const int64_t D = s.D, F = s.F, DR = s.DR, R = s.R;
+    const int fmt = s.fmt;
     const int64_t NB = RG_NBLK;
     const int64_t gpb = (F / 32 + NB - 1) / NB;
-    if (n_cu != NB || H > NB || F % 32 != 0 || F % (gpb * 32) != 0 || DR > NB || DR % 32 != 0 || 5 * (D / 64) > NB + NB / 2 || !(R == 32 || R == 64) || gpb * 32 > 64) return -1;
-    for (uint32_t i = m.layer_begin; i < m.layer_end; i++) {
-        const LayerW & L = m.layers[i];
-        const DevTensor * mats[] = {L.att_receptance, L.att_key, L.att_value, L.att_gate, L.att_output, L.att_time_maa_w1,
-                                    L.att_time_decay_w1, L.att_time_decay_w2, L.ffn_key, L.ffn_value, L.ffn_receptance};
-        for (const DevTensor * t : mats) if (!t || t->type != fmt) return -1;
-        if (L.ffn_key->ne[1] != F || L.att_time_decay_w1->ne[1] != DR || L.att_time_maa_w1->ne[1] != R5) return -1;
-    }
+    if (n_cu != NB || s.H > NB || F % 32 != 0 || F % (gpb * 32) != 0 || DR > NB || DR % 32 != 0 || 5 * (D / 64) > NB + NB / 2 || !(R == 32 || R == 64) || gpb * 32 > 64) return -1;
     for (size_t v = 0; v < sizeof(g_ring_variants) / sizeof(g_ring_variants[0]); v++) {
         const RingVariant & rv = g_ring_variants[v];
         const int64_t nbF = F / 32;
@@ -2037,31 +2018,22 @@ static int ring_variant(const Model & m, int n_cu) {
     return -1;
 }
 
-static void ring_shared_free(RingShared * sh) {
-    if (!sh) return;
-    if (sh->d_layers) (void) hipFree(sh->d_layers);
-    if (sh->d_cus) (void) hipFree(sh->d_cus);
-    if (sh->w2b) (void) hipFree(sh->w2b);
-    if (sh->stream) (void) hipFree(sh->stream);
-    delete sh;
-}
-
 static int env_int(const char * name, int dflt) { const char * e = getenv(name); return e && e[0] ? atoi(e) : dflt; }
 
 // builds the shared images of model m on the current device (nullptr: the model / device does not qualify, or out of memory -- said on stderr)
 static RingShared * ring_shared_build(const Model & m) {
     hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, m.device) != hipSuccess) return nullptr;
+    V6Shape shape;
+    if (hipGetDeviceProperties(&prop, m.device) != hipSuccess || !v6_stage_shape(m, shape)) return nullptr;
     const int NB = prop.multiProcessorCount;
-    const int v = ring_variant(m, NB);
+    const int v = ring_variant(shape, NB);
     if (v < 0) return nullptr;
-    const LayerW & L0 = m.layers[m.layer_begin];
-    const int64_t D = m.n_embed(), F = L0.ffn_key->ne[1], DR = L0.att_time_decay_w1->ne[1], R = L0.att_time_maa_w1->ne[1] / 5;
-    const int fmt = (int) m.header.data_type;
+    const int64_t D = shape.D, F = shape.F, DR = shape.DR, R = shape.R;
+    const int fmt = shape.fmt;
     RingShape sh; sh.D = (int) D; sh.F = (int) F; sh.R5 = (int) (5 * R); sh.DR = (int) DR;
     sh.qs = fmt == T_Q8_0 ? 32 : 16; sh.scb = (fmt == T_Q4_1 || fmt == T_Q5_1) ? 4 : 2; sh.qhb = (fmt == T_Q5_0 || fmt == T_Q5_1) ? 4 : 0;
     const int n_layers = (int) (m.layer_end - m.layer_begin);
-    RingShared * rs = new RingShared();
+    std::unique_ptr<RingShared> rs(new RingShared());
     rs->variant = v; rs->n_blocks = NB; rs->n_layers = n_layers;
     rs->D = D; rs->F = F; rs->DR = DR; rs->R = R;
     const R6Lds lo = r6_lds((int) D, (int) F);
@@ -2070,12 +2042,12 @@ static RingShared * ring_shared_build(const Model & m) {
     const size_t max_rec_bytes = rg_rec_bytes(sh, 1, (int) F) > rg_rec_bytes(sh, 2, (int) D) ? rg_rec_bytes(sh, 1, (int) F) : rg_rec_bytes(sh, 2, (int) D);
     const size_t mirror = ((max_rec_bytes > RG_HREC ? max_rec_bytes : RG_HREC) + 4095) / 4096 * 4096;
     size_t ring = (size_t) env_int("RWKV_MI_RING_KB", 1024) * 1024;
-    if (lo.fixed + mirror + 32 * 1024 > lds_max) { delete rs; return nullptr; }
+    if (lo.fixed + mirror + 32 * 1024 > lds_max) return nullptr;
     if (ring > lds_max - lo.fixed - mirror) ring = lds_max - lo.fixed - mirror;
     ring = ring / 4096 * 4096;
     if (ring < 32 * 1024) ring = 32 * 1024;
     rs->lds = lo.fixed + ring + mirror; rs->ring = ring; rs->mirror = mirror;
-    if (hipFuncSetAttribute((const void *) g_ring_variants[v].fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) rs->lds) != hipSuccess) { delete rs; return nullptr; }
+    if (hipFuncSetAttribute((const void *) g_ring_variants[v].fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) rs->lds) != hipSuccess) return nullptr;
     // the head behind the last layer: F16 head.weight of a stage that owns it, rows divisible into 16-row groups per workgroup
     const bool fold_head = m.has_head && m.head && m.head->type == T_F16 && m.head->cols() == D && m.n_vocab() % (RG_NBLK * 16) == 0 && m.ln_out_w && m.ln_out_b
                            && !(getenv("RWKV_MI_RING_NO_HEAD") && getenv("RWKV_MI_RING_NO_HEAD")[0] == '1');
@@ -2089,82 +2061,58 @@ static RingShared * ring_shared_build(const Model & m) {
         int nr = 0; for (int ph = 0; ph < RG_NPHASE; ph++) nr += (int) cu.n[ph];
         max_rec = nr > max_rec ? nr : max_rec;
         const uint64_t bytes = (uint64_t) cu.layer_bytes * n_layers;
-        if (bytes + (1u << 20) > 0xFFFFFFFFull) { delete rs; return nullptr; }   // stream positions are 32-bit
+        if (bytes + (1u << 20) > 0xFFFFFFFFull) return nullptr;   // stream positions are 32-bit
         const uint64_t hbytes = fold_head ? rg_head((int) m.n_vocab(), (int) D).bytes : 0;
-        if (bytes + hbytes + (1u << 20) > 0xFFFFFFFFull) { delete rs; return nullptr; }
+        if (bytes + hbytes + (1u << 20) > 0xFFFFFFFFull) return nullptr;
         hc[b].base = total; hc[b].chunks = (unsigned) ((bytes + 4 * RG_CHUNK - 1) / (4 * RG_CHUNK)) * 4u;
         hc[b].chunks_head = (unsigned) ((bytes + hbytes + 4 * RG_CHUNK - 1) / (4 * RG_CHUNK)) * 4u; hc[b].layer_bytes = cu.layer_bytes; hc[b].pad = 0;
         total += (uint64_t) hc[b].chunks_head * RG_CHUNK;
     }
     const size_t w2_layer = (size_t) 5 * R * D;
-    bool ok = R % 4 == 0 && hipMalloc((void **) &rs->w2b, w2_layer * n_layers * sizeof(float)) == hipSuccess
-           && hipMalloc((void **) &rs->stream, total + 4 * RG_CHUNK) == hipSuccess
-           && hipMalloc((void **) &rs->d_cus, hc.size() * sizeof(R6Cu)) == hipSuccess
-           && hipMemcpy(rs->d_cus, hc.data(), hc.size() * sizeof(R6Cu), hipMemcpyHostToDevice) == hipSuccess;
+    bool ok = R % 4 == 0 && rs->w2b.alloc(w2_layer * n_layers) == hipSuccess
+           && rs->stream.alloc(total + 4 * RG_CHUNK) == hipSuccess
+           && rs->d_cus.alloc(hc.size()) == hipSuccess
+           && hipMemcpy(rs->d_cus.p, hc.data(), hc.size() * sizeof(R6Cu), hipMemcpyHostToDevice) == hipSuccess;
     if (!ok) {
         (void) hipGetLastError();
         fprintf(stderr, "librwkv: no room for the ring kernel's weight streams (%.2f GB): this model continues on the per-layer launches\n", (double) total / 1e9);
-        ring_shared_free(rs);
         return nullptr;
     }
-    std::vector<M6Layer> hl;
+    // the layer table first: a model with a parameter outside the arena is turned away before anything is launched for it
+    const V6Table tab = v6_layer_table(m, w2_layer);
+    const std::vector<M6Layer> & hl = tab.layers;
+    if (!tab.in_arena) return nullptr;
     const unsigned char * abase = (const unsigned char *) m.arena;
-    bool in_arena = true;
-    auto off = [&](const void * ptr) -> long long {
-        const long long o = (const unsigned char *) ptr - abase;
-        if (!ptr || o < 0 || (uint64_t) o >= m.arena_bytes) in_arena = false;
-        return o;
-    };
-    auto f = [&](const DevTensor * t) { return off(t->data); };
-    auto pl3 = [&](const DevTensor * t) { M6Off o; o.qs = off(t->qs); o.qh = t->qh ? off(t->qh) : 0; o.sc = off(t->sc); return o; };
-    uint64_t bytes = 0;
-    for (uint32_t i = m.layer_begin; i < m.layer_end; i++) {
-        const LayerW & L = m.layers[i];
-        M6Layer d{};
-        d.ln1_w = f(L.ln1_w); d.ln1_b = f(L.ln1_b); d.maa_x = f(L.att_time_maa_x);
-        d.maa[0] = f(L.att_time_maa_w); d.maa[1] = f(L.att_time_maa_k); d.maa[2] = f(L.att_time_maa_v); d.maa[3] = f(L.att_time_maa_r); d.maa[4] = f(L.att_time_maa_g);
-        d.w2b = (long long) hl.size() * 5 * R * D; d.time_decay = f(L.att_time_decay); d.faaaa = f(L.att_time_faaaa);
-        d.lnx_w = f(L.att_ln_x_w); d.lnx_b = f(L.att_ln_x_b); d.ln2_w = f(L.ln2_w); d.ln2_b = f(L.ln2_b);
-        d.fmaa_k = f(L.ffn_time_maa_k); d.fmaa_r = f(L.ffn_time_maa_r);
-        d.w1 = pl3(L.att_time_maa_w1);
-        d.rkvg[0] = pl3(L.att_receptance); d.rkvg[1] = pl3(L.att_key); d.rkvg[2] = pl3(L.att_value); d.rkvg[3] = pl3(L.att_gate);
-        d.dw1 = pl3(L.att_time_decay_w1); d.dw2 = pl3(L.att_time_decay_w2); d.wo = pl3(L.att_output);
-        d.fk = pl3(L.ffn_key); d.fr = pl3(L.ffn_receptance); d.fv = pl3(L.ffn_value);
-        if (!in_arena) break;
-        hipLaunchKernelGGL(k_block_w2_ring, dim3(512), dim3(256), 0, 0, (const float *) L.att_time_maa_w2->data, rs->w2b + hl.size() * w2_layer, (int) D, (int) R);
+    for (size_t i = 0; i < hl.size(); i++) {
+        const M6Layer & d = hl[i];
+        launch_block_w2((const float *) m.layers[m.layer_begin + i].att_time_maa_w2->data, rs->w2b.p + i * w2_layer, (int) D, (int) R);
         PackMat pm; pm.w1 = d.w1; pm.dw1 = d.dw1; for (int q = 0; q < 4; q++) pm.rkvg[q] = d.rkvg[q]; pm.wo = d.wo; pm.fk = d.fk; pm.fr = d.fr; pm.fv = d.fv;
-        hipLaunchKernelGGL(k_ring_pack, dim3((unsigned) max_rec, RG_NBLK), dim3(64), 0, 0, abase, pm, sh, rs->d_cus, rs->stream, (int) hl.size(), max_rec);
-        hl.push_back(d);
-        const DevTensor * all[] = {L.ln1_w, L.ln1_b, L.att_time_maa_x, L.att_time_maa_w, L.att_time_maa_k, L.att_time_maa_v, L.att_time_maa_r, L.att_time_maa_g,
-                                   L.att_time_maa_w1, L.att_time_maa_w2, L.att_time_decay, L.att_time_faaaa, L.att_time_decay_w1, L.att_time_decay_w2,
-                                   L.att_receptance, L.att_key, L.att_value, L.att_gate, L.att_output, L.att_ln_x_w, L.att_ln_x_b, L.ln2_w, L.ln2_b,
-                                   L.ffn_time_maa_k, L.ffn_time_maa_r, L.ffn_key, L.ffn_value, L.ffn_receptance};
-        for (const DevTensor * t : all) if (t) bytes += t->nbytes;
-        bytes += 2 * (uint64_t) m.state_per_layer() * sizeof(float);
+        hipLaunchKernelGGL(k_ring_pack, dim3((unsigned) max_rec, RG_NBLK), dim3(64), 0, 0, abase, pm, sh, rs->d_cus.p, rs->stream.p, (int) i, max_rec);
     }
-    rs->bytes = bytes;
+    ArenaOffsets ao(m);   // (ln0, ln_out)
+    rs->bytes = tab.bytes;
     {
         const char * nf = getenv("RWKV_MI_RING_NO_EMBED");   // (measurement aid: the embedding and the argmax as their own launches, as up to round 5)
-        if (!(nf && nf[0] == '1') && m.has_embed && m.emb && m.ln0_w && m.ln0_b && (m.emb->type == T_F16 || m.emb->type == T_F32) && in_arena) {
+        if (!(nf && nf[0] == '1') && m.has_embed && m.emb && m.ln0_w && m.ln0_b && (m.emb->type == T_F16 || m.emb->type == T_F32)) {
             rs->embed = true;
-            rs->ln0w_off = off(m.ln0_w->data); rs->ln0b_off = off(m.ln0_b->data);
+            rs->ln0w_off = ao.off(m.ln0_w->data); rs->ln0b_off = ao.off(m.ln0_b->data);
             rs->bytes_embed = (uint64_t) D * (m.emb->type == T_F16 ? 2 : 4) + m.ln0_w->nbytes + m.ln0_b->nbytes;
-            if (!in_arena) rs->embed = false;
-            in_arena = true;   // (ln0 outside the arena only switches the fold off)
+            if (!ao.in_arena) rs->embed = false;
+            ao.in_arena = true;   // (ln0 outside the arena only switches the fold off)
         }
     }
-    if (fold_head && in_arena) {
-        rs->lnw_off = off(m.ln_out_w->data); rs->lnb_off = off(m.ln_out_b->data);
+    if (fold_head) {
+        rs->lnw_off = ao.off(m.ln_out_w->data); rs->lnb_off = ao.off(m.ln_out_b->data);
         const RingHead hd = rg_head((int) m.n_vocab(), (int) D);
         hipLaunchKernelGGL(k_ring_pack_head, dim3((unsigned) (hd.hg * hd.chunks), RG_NBLK), dim3(64), 0, 0, (const unsigned short *) m.head->data, (int) m.n_vocab(), (int) D,
-                           rs->d_cus, rs->stream, n_layers);
+                           rs->d_cus.p, rs->stream.p, n_layers);
         rs->bytes_head = m.head->nbytes + m.ln_out_w->nbytes + m.ln_out_b->nbytes + (uint64_t) m.n_vocab() * 4;
     }
-    ok = in_arena && hipMalloc((void **) &rs->d_layers, hl.size() * sizeof(M6Layer)) == hipSuccess
-      && hipMemcpy(rs->d_layers, hl.data(), hl.size() * sizeof(M6Layer), hipMemcpyHostToDevice) == hipSuccess
+    ok = ao.in_arena && rs->d_layers.alloc(hl.size()) == hipSuccess
+      && hipMemcpy(rs->d_layers.p, hl.data(), hl.size() * sizeof(M6Layer), hipMemcpyHostToDevice) == hipSuccess
       && hipDeviceSynchronize() == hipSuccess;
-    if (!ok) { ring_shared_free(rs); return nullptr; }
-    return rs;
+    if (!ok) return nullptr;
+    return rs.release();
 }
 
 static RingShared * ring_shared_acquire(const Model & m) {
@@ -2179,13 +2127,10 @@ static void ring_shared_release(const Model & m, RingShared * rs) {
     std::lock_guard<std::mutex> lk(m.derived_mu);
     if (--rs->ref > 0) return;
     if (m.ring_shared == rs) m.ring_shared = nullptr;
-    ring_shared_free(rs);
+    delete rs;
 }
 
-RingV6::~RingV6() {
-    if (xch) (void) hipFree(xch);
-    if (model) ring_shared_release(*model, sh);
-}
+RingV6::~RingV6() { if (model) ring_shared_release(*model, sh); }   // (the ref-count; the exchange arena goes with the members)
 
 // Returns nullptr when the model / device does not qualify (the caller tries the register-prefetch kernel, then the seven launches).
 // Per context: the exchange arena, the control words, the trace buffer. Everything derived from the weights is shared (RingShared).
@@ -2201,22 +2146,19 @@ PersistentDecoder * ring_v6_create(const Model & m) {
     auto up = [](int64_t v) { return (v + 63) / 64 * 64; };
     const int64_t act_stride = up(3 * nbD), xunits = up(RG_NBLK * RG_NC);
     const int64_t sizes[9] = {up(1280) + PAD, 5 * act_stride + PAD, 2 * D + PAD, 256 + PAD, act_stride + PAD, xunits + PAD, up(3 * nbF) + PAD, xunits + PAD, up(RG_NBLK) + PAD};
-    int64_t units = 0;
-    for (int64_t z : sizes) units += z;
-    bool ok = hipMalloc(&rg->xch, (size_t) units * 16) == hipSuccess && hipMemset(rg->xch, 0, (size_t) units * 16) == hipSuccess
+    R6P & q = rg->proto;
+    int * const slots[9] = {&q.tl, &q.act5, &q.rkvg, &q.dl, &q.yq, &q.xatt, &q.kq, &q.xffn, &q.am};
+    const int64_t units = carve_exchange(sizes, 9, slots);
+    bool ok = rg->xch.alloc((size_t) units * 16) == hipSuccess && hipMemset(rg->xch.p, 0, (size_t) units * 16) == hipSuccess
       && rg->ctl.alloc(8u);
     if (!ok || hipDeviceSynchronize() != hipSuccess) { delete rg; return nullptr; }
-    R6P & q = rg->proto;
-    q.layers = rs->d_layers; q.n_layers = rs->n_layers; q.layer0 = 0; q.layers_total = rs->n_layers;
-    q.arena = (const unsigned char *) m.arena; q.w2b = rs->w2b;
+    q.layers = rs->d_layers.p; q.n_layers = rs->n_layers; q.layer0 = 0; q.layers_total = rs->n_layers;
+    q.arena = (const unsigned char *) m.arena; q.w2b = rs->w2b.p;
     q.state_stride = m.state_per_layer();
-    q.xch = rg->xch; q.xch_bytes = (unsigned) (units * 16);
-    int u = 0;
-    int * slots[9] = {&q.tl, &q.act5, &q.rkvg, &q.dl, &q.yq, &q.xatt, &q.kq, &q.xffn, &q.am};
-    for (int i = 0; i < 9; i++) { *slots[i] = u; u += (int) sizes[i]; }
+    q.xch = rg->xch.p; q.xch_bytes = (unsigned) (units * 16);
     q.act_stride = (int) act_stride;
-    q.ctl = rg->ctl.dev;
-    q.stream = rs->stream; q.cus = rs->d_cus;
+    q.ctl = rg->ctl.dev.p;
+    q.stream = rs->stream.p; q.cus = rs->d_cus.p;
     q.F = (int) F; q.DR = (int) rs->DR; q.R = (int) rs->R; q.H = (int) m.head_count;
     q.ring_bytes = (unsigned) rs->ring; q.mirror_bytes = (unsigned) rs->mirror;
     // on the workgroups of the value matrix: their r/k/v/g phase is the shortest (no decay row, 5.0 us against 5.8 - 6.4 us), and the
@@ -2257,7 +2199,7 @@ void RingV6::forward_range(float * x, float *, const float * sin, float * sout, 
     q.x = x;
     q.x_out = (x_out && l1 == sh->n_layers) ? x_out : x;
     q.tok = (sh->embed && l0 == 0) ? tok : nullptr;
-    q.layers = sh->d_layers + l0; q.n_layers = l1 - l0; q.layer0 = l0; q.layers_total = sh->n_layers;
+    q.layers = sh->d_layers.p + l0; q.n_layers = l1 - l0; q.layer0 = l0; q.layers_total = sh->n_layers;
     q.sin = sin + (long long) l0 * q.state_stride; q.sout = sout + (long long) l0 * q.state_stride;
     q.logits = (sh->head && l1 == sh->n_layers) ? logits : nullptr;
     q.next_tok = q.logits ? next_tok : nullptr;

@@ -99,7 +99,7 @@ struct LocalHop : Hop {
         }
         ok = hipSetDevice(ddev) == hipSuccess;
         for (Slot & s : slots) {
-            ok = ok && hipMalloc(&s.box, bytes) == hipSuccess;
+            ok = ok && hipMalloc(&s.box, bytes) == hipSuccess;   // (raw: freed with its two events on the destination device, ~LocalHop)
             ok = ok && hipEventCreateWithFlags(&s.ready, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&s.taken, hipEventDisableTiming) == hipSuccess;
         }
     }
@@ -264,7 +264,7 @@ struct IpcShm { std::atomic<int> ready; int world; IpcBox box[16]; };
 struct IpcWorld {
     std::string name; int rank = 0, world = 0, device = 0;
     IpcShm * shm = nullptr;
-    void * mine = nullptr;                   // this rank's mailbox (device memory)
+    void * mine = nullptr;                   // this rank's mailbox (device memory; raw: exported over IPC, freed after the peers' handles are closed)
     void * peer[16] = {};                    // opened mailboxes of the ranks this one sends to
     uint64_t got[k_ipc_slots] = {};          // messages received per slot of this rank's mailbox
     uint64_t put[16][k_ipc_slots] = {};      // messages sent per (destination, slot)
@@ -345,7 +345,7 @@ bool stage_iteration(StagePart & p, rwkv_context * err, size_t t, int j) {
     auto fail = [&]() { err->last_error |= c->last_error ? c->last_error : (int) RWKV_ERROR_GRAPH; return false; };
     if (hipSetDevice(m.device) != hipSuccess || !ensure_scratch(c, 1)) return fail();
     if (m.has_embed) {
-        if (t > 0 && p.tok_in && !p.tok_in->recv(j, 0, c->d_tokens, sizeof(uint32_t), c->stream)) return fail();
+        if (t > 0 && p.tok_in && !p.tok_in->recv(j, 0, c->d_tokens.p, sizeof(uint32_t), c->stream)) return fail();
     } else {
         if (!p.in || !p.in->recv(j, 0, c->b.x, D * sizeof(float), c->stream)) return fail();
         if (m.arch_major == 7 && !p.in->recv(j, 1, c->b.v_first, D * sizeof(float), c->stream)) return fail();
@@ -365,8 +365,8 @@ bool stage_iteration(StagePart & p, rwkv_context * err, size_t t, int j) {
         if (!p.tok_out->produce_end(j, 0, c->stream, mega_chain_marker(c))) return fail();
     } else if (m.has_head) {
         // the chosen token: where this context's embedding reads it (a one-stage "chain"), else in the slot the feedback hop sends from
-        uint32_t * dst = m.has_embed ? c->d_tokens : c->d_next_token;
-        if (folded_argmax_target(c) != dst) launch_argmax(c->d_logits, 1, m.n_vocab(), dst, nullptr, c->stream);   // (else the persistent launch left it there)
+        uint32_t * dst = m.has_embed ? c->d_tokens.p : c->d_next_token.p;
+        if (folded_argmax_target(c) != dst) launch_argmax(c->d_logits.p, 1, m.n_vocab(), dst, nullptr, c->stream);   // (else the persistent launch left it there)
         const bool in_launch = (size_t) j < p.hist_in_launch.size() && p.hist_in_launch[(size_t) j] && folded_argmax_target(c) == dst;
         if (!in_launch && hipMemcpyAsync(p.d_hist + (size_t) j * p.n_tokens + t, dst, sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream) != hipSuccess) return fail();
         if (p.tok_out && t + 1 < p.n_tokens && !p.tok_out->send(j, 0, dst, sizeof(uint32_t), c->stream)) return fail();
@@ -460,9 +460,10 @@ bool drain(StagePart & p, rwkv_context * err) {
     return ok;
 }
 
+// a token history on device `dev`: that device is made current before the buffer is released
 struct DevMem {
-    void * p = nullptr; int dev = 0;
-    ~DevMem() { if (p) { (void) hipSetDevice(dev); (void) hipFree(p); } }
+    DevBuf<uint32_t> buf; int dev = 0;
+    ~DevMem() { if (buf) (void) hipSetDevice(dev); }
 };
 
 }  // namespace
@@ -511,8 +512,8 @@ bool pipeline_decode_greedy(rwkv_context * const * fronts, size_t n_streams, con
         parts[S - 1].tok_out = h; parts[0].tok_in = h;
     }
     DevMem hist; hist.dev = parts[S - 1].h[0]->model->device;
-    RW_CTX_CHECK(f0, RWKV_ERROR_ALLOC, false, hipSetDevice(hist.dev) == hipSuccess && hipMalloc(&hist.p, n_streams * n_tokens * sizeof(uint32_t)) == hipSuccess, "cannot allocate the token history");
-    parts[S - 1].d_hist = (uint32_t *) hist.p;
+    RW_CTX_CHECK(f0, RWKV_ERROR_ALLOC, false, hipSetDevice(hist.dev) == hipSuccess && hist.buf.alloc(n_streams * n_tokens) == hipSuccess, "cannot allocate the token history");
+    parts[S - 1].d_hist = hist.buf.p;
     if (!seed_tokens(parts[0], f0, first_tokens)) return false;
     // the hops deliver straight into the buffers the receiving stages read (fixed for the length of this call: T stays 1)
     for (size_t s = 0; s < S; s++)
@@ -520,7 +521,7 @@ bool pipeline_decode_greedy(rwkv_context * const * fronts, size_t n_streams, con
             rwkv_context * c = parts[s].h[j];
             if (hipSetDevice(c->model->device) != hipSuccess || !ensure_scratch(c, 1)) { f0->last_error |= c->last_error ? c->last_error : (int) RWKV_ERROR_ALLOC; return false; }
             if (parts[s].in) { (void) parts[s].in->bind((int) j, 0, c->b.x); if (c->model->arch_major == 7) (void) parts[s].in->bind((int) j, 1, c->b.v_first); }
-            if (parts[s].tok_in) (void) parts[s].tok_in->bind((int) j, 0, c->d_tokens);
+            if (parts[s].tok_in) (void) parts[s].tok_in->bind((int) j, 0, c->d_tokens.p);
         }
     for (auto & h : hops) h->set_closed_loop(S > 1);       // (S > 1: the token feedback closes the loop for every decode stream)
     HistScope hist_scope(parts[S - 1]);
@@ -537,7 +538,7 @@ bool pipeline_decode_greedy(rwkv_context * const * fronts, size_t n_streams, con
     RW_CTX_CHECK(f0, RWKV_ERROR_GRAPH, false, ok, "greedy decode through the stage chain failed: %s", hipGetErrorString(hipGetLastError()));
     RW_CTX_CHECK(f0, RWKV_ERROR_GRAPH, false, clean, "the persistent decode kernel of a stage timed out; the stage continues on the per-layer launches");
     if (elapsed_ms) *elapsed_ms = (float) std::chrono::duration<double, std::milli>(t1 - t0).count();
-    if (tokens_out) RUN_OK(f0, hipMemcpy(tokens_out, hist.p, n_streams * n_tokens * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (tokens_out) RUN_OK(f0, hipMemcpy(tokens_out, hist.buf.p, n_streams * n_tokens * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return true;
 }
 
@@ -550,7 +551,7 @@ bool pipeline_state_load(rwkv_context * front, const float * state_in) {
         if (ok && state_in) {
             const int64_t per = m.state_per_layer();
             const int64_t off = (int64_t) m.layer_begin * per, cnt = (int64_t) (m.layer_end - m.layer_begin) * per;
-            ok = hipMemcpyAsync(c->state[c->cur] + off, state_in + off, (size_t) cnt * sizeof(float), hipMemcpyHostToDevice, c->stream) == hipSuccess;
+            ok = hipMemcpyAsync(c->state[c->cur].p + off, state_in + off, (size_t) cnt * sizeof(float), hipMemcpyHostToDevice, c->stream) == hipSuccess;
         } else if (ok) ok = state_from_host(c, nullptr);
         ok = ok && hipStreamSynchronize(c->stream) == hipSuccess;
         if (!ok) { front->last_error |= c->last_error ? c->last_error : (int) RWKV_ERROR_GRAPH; return false; }
@@ -563,7 +564,7 @@ bool pipeline_state_store(rwkv_context * front, float * state_out) {
         const int64_t per = m.state_per_layer();
         const int64_t off = (int64_t) m.layer_begin * per, cnt = (int64_t) (m.layer_end - m.layer_begin) * per;
         const bool ok = hipSetDevice(m.device) == hipSuccess &&
-                        hipMemcpyAsync(state_out + off, c->state[c->cur] + off, (size_t) cnt * sizeof(float), hipMemcpyDeviceToHost, c->stream) == hipSuccess &&
+                        hipMemcpyAsync(state_out + off, c->state[c->cur].p + off, (size_t) cnt * sizeof(float), hipMemcpyDeviceToHost, c->stream) == hipSuccess &&
                         hipStreamSynchronize(c->stream) == hipSuccess;
         if (!ok) { front->last_error |= RWKV_ERROR_GRAPH; return false; }
     }
@@ -685,8 +686,8 @@ RWKV_API bool rwkv_mi_stage_run(struct rwkv_context * const * handles, size_t n_
     RW_CTX_CHECK(c0, RWKV_ERROR_ALLOC, false, ok, "cannot create the streams of the token feedback");
     DevMem hist; hist.dev = m.device;
     if (m.has_head) {
-        RUN_OK(c0, hipMalloc(&hist.p, n_streams * n_tokens * sizeof(uint32_t)));
-        part.d_hist = (uint32_t *) hist.p;
+        RUN_OK(c0, hist.buf.alloc(n_streams * n_tokens));
+        part.d_hist = hist.buf.p;
     }
     if (m.has_embed && !seed_tokens(part, c0, first_tokens)) return false;
     HistScope hist_scope(part);
@@ -700,7 +701,7 @@ RWKV_API bool rwkv_mi_stage_run(struct rwkv_context * const * handles, size_t n_
     RW_CTX_CHECK(c0, RWKV_ERROR_GRAPH, false, ok, "the stage's decode loop failed: %s", hipGetErrorString(hipGetLastError()));
     RW_CTX_CHECK(c0, RWKV_ERROR_GRAPH, false, clean, "the persistent decode kernel timed out; the stage continues on the per-layer launches");
     if (elapsed_ms) *elapsed_ms = (float) std::chrono::duration<double, std::milli>(t1 - t0).count();
-    if (tokens_out && m.has_head) RUN_OK(c0, hipMemcpy(tokens_out, hist.p, n_streams * n_tokens * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (tokens_out && m.has_head) RUN_OK(c0, hipMemcpy(tokens_out, hist.buf.p, n_streams * n_tokens * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return true;
 }
 

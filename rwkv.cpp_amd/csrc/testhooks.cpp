@@ -72,9 +72,11 @@ RWKV_API bool rwkv_mi_test_quantize_act(const float * x, int64_t n, int8_t * q, 
     g_last_error = RWKV_ERROR_NONE;
     RW_CHECK(RWKV_ERROR_ARGS, false, x && q && d && s && isum && n > 0 && n % 32 == 0, "bad arguments");
     const size_t nb = (size_t) n / 32;
-    float * dx = nullptr; uint8_t * dq = nullptr;
-    bool ok = hipMalloc((void **) &dx, (size_t) n * 4) == hipSuccess && hipMalloc((void **) &dq, (size_t) n + 3 * nb * 4 + 1024) == hipSuccess &&
-              hipMemcpy(dx, x, (size_t) n * 4, hipMemcpyHostToDevice) == hipSuccess;
+    DevBuf<float> x_buf;
+    DevBuf<uint8_t> q_buf;
+    bool ok = x_buf.alloc((size_t) n) == hipSuccess && q_buf.alloc((size_t) n + 3 * nb * 4 + 1024) == hipSuccess;
+    float * dx = x_buf.p; uint8_t * dq = q_buf.p;
+    ok = ok && hipMemcpy(dx, x, (size_t) n * 4, hipMemcpyHostToDevice) == hipSuccess;
     if (ok) {
         QAct qa;
         qa.q = (int8_t *) dq;
@@ -86,8 +88,6 @@ RWKV_API bool rwkv_mi_test_quantize_act(const float * x, int64_t n, int8_t * q, 
              hipMemcpy(d, qa.d, nb * 4, hipMemcpyDeviceToHost) == hipSuccess && hipMemcpy(s, qa.s, nb * 4, hipMemcpyDeviceToHost) == hipSuccess &&
              hipMemcpy(isum, qa.isum, nb * 4, hipMemcpyDeviceToHost) == hipSuccess;
     }
-    if (dx) (void) hipFree(dx);
-    if (dq) (void) hipFree(dq);
     RW_CHECK(RWKV_ERROR_GRAPH, false, ok, "HIP error: %s", hipGetErrorString(hipGetLastError()));
     return true;
 }
@@ -96,15 +96,14 @@ RWKV_API bool rwkv_mi_test_quantize_act(const float * x, int64_t n, int8_t * q, 
 RWKV_API bool rwkv_mi_test_unary(int op, const float * x, float * y, int64_t n) {
     g_last_error = RWKV_ERROR_NONE;
     RW_CHECK(RWKV_ERROR_ARGS, false, x && y && n > 0, "bad arguments");
-    float *dx = nullptr, *dy = nullptr;
-    bool ok = hipMalloc((void **) &dx, (size_t) n * 4) == hipSuccess && hipMalloc((void **) &dy, (size_t) n * 4) == hipSuccess &&
-              hipMemcpy(dx, x, (size_t) n * 4, hipMemcpyHostToDevice) == hipSuccess;
+    DevBuf<float> x_buf, y_buf;
+    bool ok = x_buf.alloc((size_t) n) == hipSuccess && y_buf.alloc((size_t) n) == hipSuccess;
+    float * dx = x_buf.p, * dy = y_buf.p;
+    ok = ok && hipMemcpy(dx, x, (size_t) n * 4, hipMemcpyHostToDevice) == hipSuccess;
     if (ok) {
         launch_test_unary(op, dx, dy, n, nullptr);
         ok = hipDeviceSynchronize() == hipSuccess && hipMemcpy(y, dy, (size_t) n * 4, hipMemcpyDeviceToHost) == hipSuccess;
     }
-    if (dx) (void) hipFree(dx);
-    if (dy) (void) hipFree(dy);
     RW_CHECK(RWKV_ERROR_GRAPH, false, ok, "HIP error: %s", hipGetErrorString(hipGetLastError()));
     return true;
 }
@@ -117,16 +116,19 @@ RWKV_API bool rwkv_mi_test_mul_mat(int type, const void * w, int64_t K, int64_t 
     RW_CHECK(RWKV_ERROR_ARGS, false, K % 32 == 0, "K must be a multiple of 32");
     const uint64_t wbytes = tensor_nbytes(type, K, N, 1);
     const int64_t nblk = K * N / 32;
-    void *d_raw = nullptr, *d_x = nullptr, *d_y = nullptr, *d_q = nullptr, *d_planes = nullptr;
+    DevBuf<uint8_t> raw_buf, q_buf, planes_buf, tile_buf, ws_buf;
+    DevBuf<float> x_buf, y_buf;
     bool ok = true;
     auto chk = [&](hipError_t e) { if (e != hipSuccess) { global_fail(RWKV_ERROR_GRAPH, __FILE__, __LINE__, "hip call", "HIP error: %s", hipGetErrorString(e)); ok = false; } return ok; };
     DevTensor W;
     W.type = type; W.ndim = 2; W.ne[0] = K; W.ne[1] = N; W.nbytes = wbytes;
     QAct qa;
     const size_t nbk = (size_t) T * (size_t)(K / 32);
-    if (chk(hipMalloc(&d_raw, wbytes)) && chk(hipMalloc(&d_x, (size_t) T * K * 4)) && chk(hipMalloc(&d_y, (size_t) T * N * 4)) &&
-        chk(hipMalloc(&d_q, (size_t) T * K + 3 * nbk * 4 + 1024)) && chk(hipMalloc(&d_planes, (size_t) nblk * 40 + 1024)) &&
-        chk(hipMemcpy(d_raw, w, wbytes, hipMemcpyHostToDevice)) && chk(hipMemcpy(d_x, x, (size_t) T * K * 4, hipMemcpyHostToDevice))) {
+    if (chk(raw_buf.alloc(wbytes)) && chk(x_buf.alloc((size_t) T * K)) && chk(y_buf.alloc((size_t) T * N)) &&
+        chk(q_buf.alloc((size_t) T * K + 3 * nbk * 4 + 1024)) && chk(planes_buf.alloc((size_t) nblk * 40 + 1024)) &&
+        chk(hipMemcpy(raw_buf.p, w, wbytes, hipMemcpyHostToDevice)) && chk(hipMemcpy(x_buf.p, x, (size_t) T * K * 4, hipMemcpyHostToDevice))) {
+        uint8_t * d_raw = raw_buf.p, * d_q = q_buf.p, * d_planes = planes_buf.p;
+        float * d_x = x_buf.p, * d_y = y_buf.p;
         hipStream_t st = nullptr;
         if (dtype_quantized(type)) {
             W.qs = (uint8_t *) d_planes;
@@ -139,15 +141,14 @@ RWKV_API bool rwkv_mi_test_mul_mat(int type, const void * w, int64_t K, int64_t 
             qa.isum = (int *) (qa.s + nbk);
             if (T >= k_mfma_min_tokens) {
                 // sequence mode: tile-major quantiser + int8 GEMM on the matrix cores (what the engine does for T >= 32)
-                void * d_tile = nullptr;
-                if (chk(hipMalloc(&d_tile, tile_act_bytes(T, K)))) {
-                    const TileAct ta = tile_act_at(d_tile, T, K);
+                if (chk(tile_buf.alloc(tile_act_bytes(T, K)))) {
+                    const TileAct ta = tile_act_at(tile_buf.p, T, K);
                     launch_quantize_act_tiles((const float *) d_x, T, K, type, ta, st);
                     // (with the workspace of the split walk, as the engine runs it: few-tile shapes take that path)
                     MmqWs ws;
-                    void * d_ws = nullptr;
                     const size_t ws_part = (size_t) 16 << 20;
-                    if (chk(hipMalloc(&d_ws, ws_part + 1024 * sizeof(int))) && chk(hipMemsetAsync((uint8_t *) d_ws + ws_part, 0, 1024 * sizeof(int), st))) {
+                    if (chk(ws_buf.alloc(ws_part + 1024 * sizeof(int))) && chk(hipMemsetAsync(ws_buf.p + ws_part, 0, 1024 * sizeof(int), st))) {
+                        uint8_t * d_ws = ws_buf.p;
                         ws.part = (float *) d_ws; ws.part_bytes = ws_part; ws.counters = (int *) ((uint8_t *) d_ws + ws_part); ws.n_counters = 1024;
                     }
                     if (!launch_mmq_mfma(W, ta, T, (float *) d_y, N, Epi(), st, &ws)) ok = false;
@@ -167,8 +168,7 @@ RWKV_API bool rwkv_mi_test_mul_mat(int type, const void * w, int64_t K, int64_t 
                             (void) hipEventDestroy(e0); (void) hipEventDestroy(e1);
                         }
                     }
-                    (void) hipFree(d_tile);
-                    if (d_ws) (void) hipFree(d_ws);
+                    tile_buf.reset(); ws_buf.reset();
                     free_pf(W);
                 }
             } else {
@@ -183,7 +183,6 @@ RWKV_API bool rwkv_mi_test_mul_mat(int type, const void * w, int64_t K, int64_t 
         chk(hipGetLastError());
         if (ok) chk(hipMemcpy(y, d_y, (size_t) T * N * 4, hipMemcpyDeviceToHost));
     }
-    for (void * p : {d_raw, d_x, d_y, d_q, d_planes}) if (p) (void) hipFree(p);
     return ok;
 }
 

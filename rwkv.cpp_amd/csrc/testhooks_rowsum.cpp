@@ -12,15 +12,15 @@ RWKV_API bool rwkv_test_ring_rowsum(int n, const float * values, float * butterf
     g_last_error = RWKV_ERROR_NONE;
     RW_CHECK(RWKV_ERROR_ARGS, false, values && butterfly_out && scatter_out && lanes_per_value && n >= 1 && n <= 16, "bad arguments");
     const size_t bytes = (size_t) n * 64 * 4;
-    float * d_in = nullptr, * d_n = nullptr, * d_s = nullptr;
-    bool ok = hipMalloc((void **) &d_in, bytes) == hipSuccess && hipMalloc((void **) &d_n, bytes) == hipSuccess && hipMalloc((void **) &d_s, 64 * 4) == hipSuccess &&
-              hipMemcpy(d_in, values, bytes, hipMemcpyHostToDevice) == hipSuccess;
+    DevBuf<float> in_buf, n_buf, s_buf;
+    bool ok = in_buf.alloc((size_t) n * 64) == hipSuccess && n_buf.alloc((size_t) n * 64) == hipSuccess && s_buf.alloc(64) == hipSuccess;
+    float * d_in = in_buf.p, * d_n = n_buf.p, * d_s = s_buf.p;
+    ok = ok && hipMemcpy(d_in, values, bytes, hipMemcpyHostToDevice) == hipSuccess;
     if (ok) {
         ok = launch_ring_rowsum_test(n, d_in, d_n, d_s, nullptr) && hipDeviceSynchronize() == hipSuccess &&
              hipMemcpy(butterfly_out, d_n, bytes, hipMemcpyDeviceToHost) == hipSuccess && hipMemcpy(scatter_out, d_s, 64 * 4, hipMemcpyDeviceToHost) == hipSuccess;
         *lanes_per_value = ring_rowsum_lanes(n);
     }
-    for (void * p : {(void *) d_in, (void *) d_n, (void *) d_s}) if (p) (void) hipFree(p);
     RW_CHECK(RWKV_ERROR_GRAPH, false, ok, "HIP error: %s", hipGetErrorString(hipGetLastError()));
     return true;
 }

@@ -19,16 +19,19 @@ RWKV_API bool rwkv_mi_test_sample_rows(const float * logits, int64_t n_rows, int
     g_last_error = RWKV_ERROR_NONE;
     RW_CHECK(RWKV_ERROR_ARGS, false, logits && params && tokens_out && n_rows > 0 && n_rows <= 65535 && n_vocab > 0 && n_vocab <= (int64_t) 1 << 24, "bad arguments");
     const size_t R = (size_t) n_rows, V = (size_t) n_vocab;
-    float *d_logits = nullptr, *d_probs = nullptr;
-    unsigned long long * d_ctr = nullptr;
-    SampleRow * d_table = nullptr;
-    uint32_t * d_tok = nullptr;
+    DevBuf<float> logits_buf, probs_buf;
+    DevBuf<unsigned long long> ctr_buf;
+    DevBuf<SampleRow> table_buf;
+    DevBuf<uint32_t> tok_buf;
     std::vector<SampleRow> table(R);
-    bool ok = hipMalloc((void **) &d_logits, R * V * 4) == hipSuccess && hipMalloc((void **) &d_probs, R * sample_scratch_floats(n_vocab) * 4) == hipSuccess &&
-              hipMalloc((void **) &d_ctr, R * 8) == hipSuccess && hipMalloc((void **) &d_table, R * sizeof(SampleRow)) == hipSuccess &&
-              hipMalloc((void **) &d_tok, R * 4) == hipSuccess &&
-              hipMemcpy(d_logits, logits, R * V * 4, hipMemcpyHostToDevice) == hipSuccess &&
-              (counters ? hipMemcpy(d_ctr, counters, R * 8, hipMemcpyHostToDevice) : hipMemset(d_ctr, 0, R * 8)) == hipSuccess;
+    bool ok = logits_buf.alloc(R * V) == hipSuccess && probs_buf.alloc(R * sample_scratch_floats(n_vocab)) == hipSuccess &&
+              ctr_buf.alloc(R) == hipSuccess && table_buf.alloc(R) == hipSuccess && tok_buf.alloc(R) == hipSuccess;
+    float * d_logits = logits_buf.p, * d_probs = probs_buf.p;
+    unsigned long long * d_ctr = ctr_buf.p;
+    SampleRow * d_table = table_buf.p;
+    uint32_t * d_tok = tok_buf.p;
+    ok = ok && hipMemcpy(d_logits, logits, R * V * 4, hipMemcpyHostToDevice) == hipSuccess &&
+         (counters ? hipMemcpy(d_ctr, counters, R * 8, hipMemcpyHostToDevice) : hipMemset(d_ctr, 0, R * 8)) == hipSuccess;
     if (ok) {
         for (size_t r = 0; r < R; r++) table[r] = SampleRow{params[r], d_ctr + r};
         ok = hipMemcpy(d_table, table.data(), R * sizeof(SampleRow), hipMemcpyHostToDevice) == hipSuccess;
@@ -41,7 +44,6 @@ RWKV_API bool rwkv_mi_test_sample_rows(const float * logits, int64_t n_rows, int
         ok = hipDeviceSynchronize() == hipSuccess && hipMemcpy(tokens_out, d_tok, R * 4, hipMemcpyDeviceToHost) == hipSuccess &&
              (!counters || hipMemcpy(counters, d_ctr, R * 8, hipMemcpyDeviceToHost) == hipSuccess);
     }
-    for (void * p : {(void *) d_logits, (void *) d_probs, (void *) d_ctr, (void *) d_table, (void *) d_tok}) if (p) (void) hipFree(p);
     RW_CHECK(RWKV_ERROR_GRAPH, false, ok, "HIP error: %s", hipGetErrorString(hipGetLastError()));
     return true;
 }
@@ -51,11 +53,12 @@ RWKV_API bool rwkv_test_score_rows(const float * logits, int64_t rows, int64_t n
     g_last_error = RWKV_ERROR_NONE;
     RW_CHECK(RWKV_ERROR_ARGS, false, logits && rows > 0 && rows <= 65535 && n_vocab > 0 && n_vocab <= (int64_t) 1 << 24, "bad arguments");
     const size_t R = (size_t) rows, V = (size_t) n_vocab;
-    float * d_logits = nullptr, * d_lp = nullptr;
-    uint32_t * d_tgt = nullptr, * d_am = nullptr;
-    bool ok = hipMalloc((void **) &d_logits, R * V * 4) == hipSuccess && hipMalloc((void **) &d_lp, R * 4) == hipSuccess &&
-              hipMalloc((void **) &d_tgt, R * 4) == hipSuccess && hipMalloc((void **) &d_am, R * 4) == hipSuccess &&
-              hipMemcpy(d_logits, logits, R * V * 4, hipMemcpyHostToDevice) == hipSuccess &&
+    DevBuf<float> logits_buf, lp_buf;
+    DevBuf<uint32_t> tgt_buf, am_buf;
+    bool ok = logits_buf.alloc(R * V) == hipSuccess && lp_buf.alloc(R) == hipSuccess && tgt_buf.alloc(R) == hipSuccess && am_buf.alloc(R) == hipSuccess;
+    float * d_logits = logits_buf.p, * d_lp = lp_buf.p;
+    uint32_t * d_tgt = tgt_buf.p, * d_am = am_buf.p;
+    ok = ok && hipMemcpy(d_logits, logits, R * V * 4, hipMemcpyHostToDevice) == hipSuccess &&
               (!targets || hipMemcpy(d_tgt, targets, R * 4, hipMemcpyHostToDevice) == hipSuccess);
     if (ok) {
         launch_score_rows(d_logits, rows, (int) n_vocab, targets ? d_tgt : nullptr, logprobs_out ? d_lp : nullptr, argmax_out ? d_am : nullptr, nullptr);
@@ -63,7 +66,6 @@ RWKV_API bool rwkv_test_score_rows(const float * logits, int64_t rows, int64_t n
              (!logprobs_out || hipMemcpy(logprobs_out, d_lp, R * 4, hipMemcpyDeviceToHost) == hipSuccess) &&
              (!argmax_out || hipMemcpy(argmax_out, d_am, R * 4, hipMemcpyDeviceToHost) == hipSuccess);
     }
-    for (void * p : {(void *) d_logits, (void *) d_lp, (void *) d_tgt, (void *) d_am}) if (p) (void) hipFree(p);
     RW_CHECK(RWKV_ERROR_GRAPH, false, ok, "HIP error: %s", hipGetErrorString(hipGetLastError()));
     return true;
 }
@@ -76,12 +78,13 @@ RWKV_API bool rwkv_test_logprob_rows(const float * logits, int64_t rows, int64_t
              top_n <= RWKV_MI_TOP_MAX && (int64_t) top_n <= n_vocab, "bad arguments");
     for (int64_t r = 0; r < rows; r++) RW_CHECK(RWKV_ERROR_ARGS, false, (int64_t) tokens[r] < n_vocab, "token %lld is out of range", (long long) r);
     const size_t R = (size_t) rows, V = (size_t) n_vocab, N = top_n ? top_n : 1;   // (top_n == 0: one unused word per row)
-    float * d_logits = nullptr, * d_ch = nullptr, * d_lp = nullptr;
-    uint32_t * d_tok = nullptr, * d_ids = nullptr;
-    bool ok = hipMalloc((void **) &d_logits, R * V * 4) == hipSuccess && hipMalloc((void **) &d_ch, R * 4) == hipSuccess &&
-              hipMalloc((void **) &d_tok, R * 4) == hipSuccess && hipMalloc((void **) &d_ids, R * N * 4) == hipSuccess &&
-              hipMalloc((void **) &d_lp, R * N * 4) == hipSuccess &&
-              hipMemcpy(d_logits, logits, R * V * 4, hipMemcpyHostToDevice) == hipSuccess &&
+    DevBuf<float> logits_buf, ch_buf, lp_buf;
+    DevBuf<uint32_t> tok_buf, ids_buf;
+    bool ok = logits_buf.alloc(R * V) == hipSuccess && ch_buf.alloc(R) == hipSuccess && tok_buf.alloc(R) == hipSuccess &&
+              ids_buf.alloc(R * N) == hipSuccess && lp_buf.alloc(R * N) == hipSuccess;
+    float * d_logits = logits_buf.p, * d_ch = ch_buf.p, * d_lp = lp_buf.p;
+    uint32_t * d_tok = tok_buf.p, * d_ids = ids_buf.p;
+    ok = ok && hipMemcpy(d_logits, logits, R * V * 4, hipMemcpyHostToDevice) == hipSuccess &&
               hipMemcpy(d_tok, tokens, R * 4, hipMemcpyHostToDevice) == hipSuccess;
     if (ok) {
         launch_logprob_rows(d_logits, rows, (int) n_vocab, d_tok, (int) top_n, d_ch, d_ids, d_lp, nullptr, nullptr);
@@ -90,7 +93,6 @@ RWKV_API bool rwkv_test_logprob_rows(const float * logits, int64_t rows, int64_t
              (!top_ids_out || !top_n || hipMemcpy(top_ids_out, d_ids, R * top_n * 4, hipMemcpyDeviceToHost) == hipSuccess) &&
              (!top_logprobs_out || !top_n || hipMemcpy(top_logprobs_out, d_lp, R * top_n * 4, hipMemcpyDeviceToHost) == hipSuccess);
     }
-    for (void * p : {(void *) d_logits, (void *) d_ch, (void *) d_tok, (void *) d_ids, (void *) d_lp}) if (p) (void) hipFree(p);
     RW_CHECK(RWKV_ERROR_GRAPH, false, ok, "HIP error: %s", hipGetErrorString(hipGetLastError()));
     return true;
 }

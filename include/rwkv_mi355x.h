@@ -335,6 +335,46 @@ RWKV_API bool rwkv_mi_batch_decode_until(struct rwkv_mi_batch * batch, const uin
 /* passes the last device loop of the batch enqueued (0 before the first) */
 RWKV_API size_t rwkv_mi_batch_last_loop_passes(const struct rwkv_mi_batch * batch);
 
+/* ---- Slot-to-slot copy and beam search: sequences that continue ANOTHER slot's state ----
+ * rwkv_mi_batch_state_copy: slot src's state into slot dst, device to device on the batch's stream -- what n parallel samples of one prompt
+ * need (prefill once, copy n - 1 times), and how a beam caller keeps its prompt state. `what` is a bit set: the state is copied always
+ * (RWKV_MI_COPY_STATE names it); _COUNTER adds the slot's draw counter, _COUNTS its occurrence table, _BIAS its bias table and whether a bias
+ * is set (a batch that has never used the penalised family has neither table: every count is 0, no bias is set, and the two bits copy
+ * nothing). dst == src is a no-op that returns true. An out-of-range slot or an unknown bit is RWKV_ERROR_ARGS and changes nothing. */
+#define RWKV_MI_COPY_STATE   1u
+#define RWKV_MI_COPY_COUNTER 2u
+#define RWKV_MI_COPY_COUNTS  4u
+#define RWKV_MI_COPY_BIAS    8u
+RWKV_API bool rwkv_mi_batch_state_copy(struct rwkv_mi_batch * batch, size_t dst_slot, size_t src_slot, uint32_t what);
+
+/* rwkv_mi_batch_decode_beam: beam search on the device. n_groups independent groups of W = params->width hypotheses in n_groups * W rows; row
+ * g * W + j is slot slots[g * W + j] (all distinct). Group g starts from the state of slots[g * W] and from first_tokens[g], which is not yet
+ * evaluated (the convention of rwkv_mi_batch_decode_greedy), with scores {0, -inf, ...}. THE STATE slots[g * W] HELD IS CONSUMED, as are the
+ * other named slots': keep a prompt state with rwkv_mi_batch_state_copy into a slot the call does not name.
+ * One step, after each pass: every unfinished hypothesis offers the W best tokens of its logits -- the report's top-N rule above (value
+ * descending, then index ascending; NaN never ranks) with the report's log-prob expression, bit for bit -- each with the cumulative score
+ * (double) score + (double) logprob, kept as double; not a token whose log-prob is not above -inf. A finished hypothesis offers itself once,
+ * score unchanged. A score of -inf offers nothing. The W best of a group's candidates, by score descending, then parent index ascending, then
+ * rank within the parent ascending -- a total order, so the result depends on the logits alone -- become hypotheses 0 .. W - 1 (0 the best).
+ * A hypothesis finishes when its token is one of end_tokens (at most 8; the end token is part of its text and its score). Where fewer than W
+ * candidates exist (a group whose logits are all NaN) the remaining hypotheses are dead: score -inf, length 0, finished.
+ * The call ends when every hypothesis of every group has finished, or after n_tokens steps; the passes go out in blocks as in
+ * rwkv_mi_batch_decode_until (rwkv_mi_batch_last_loop_passes: the passes enqueued). No state moves during the loop: a step re-parents the rows of
+ * the next pass on the device. Afterwards slots[g * W + j] holds the state of hypothesis j before its last token, if j is unfinished, exactly
+ * as a greedy loop leaves a slot: rwkv_mi_batch_eval of that token continues the text. The state of a finished hypothesis is unspecified.
+ * Slots the call does not name, all draw counters, occurrence and bias tables are untouched. The report (rwkv_mi_batch_set_logprobs) is not
+ * filled: logprobs_out carries the numbers, each equal, bit for bit, to rwkv_mi_batch_score_ragged's for that token.
+ * tokens_out [G][W][n_tokens] (RWKV_MI_NO_TOKEN past a hypothesis' length), lens_out [G][W], scores_out [G][W], logprobs_out [G][W][n_tokens]
+ * (0 past the length), elapsed_ms: each may be NULL. With W = 1 and no end tokens the call is rwkv_mi_batch_decode_greedy.
+ * OUT OF SCOPE: penalties and bias, length normalisation, continuing a beam from given scores.
+ * RWKV_ERROR_ARGS, nothing changed: a slot out of range or named twice; width not in 1 .. RWKV_MI_TOP_MAX or above n_vocab; n_end > 8 or an
+ * end id >= n_vocab; a first token >= n_vocab; n_tokens or n_groups 0; n_groups * width > n_slots. The call's device words are allocated by
+ * the first beam call of a batch (RWKV_ERROR_ALLOC, nothing changed, when they cannot be). */
+struct rwkv_mi_beam_params { uint32_t width; uint32_t n_end; const uint32_t * end_tokens; };   /* 16 bytes */
+RWKV_API bool rwkv_mi_batch_decode_beam(struct rwkv_mi_batch * batch, const uint32_t * slots /* [G][W] */, const uint32_t * first_tokens /* [G] */,
+                                        size_t n_groups, const struct rwkv_mi_beam_params * params, size_t n_tokens, uint32_t * tokens_out,
+                                        uint32_t * lens_out, double * scores_out, float * logprobs_out, float * elapsed_ms);
+
 /* ---- The report: log-probs and top-N alternatives of every emitted token ----
  * What serving APIs call logprobs / top_logprobs. A caller of the device loops could so far learn how likely an emitted token was only by leaving
  * the loop (n_vocab floats per row and step to the host) or by a second pass with rwkv_mi_batch_score_ragged over what was emitted, and the

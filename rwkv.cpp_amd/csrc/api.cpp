@@ -963,7 +963,12 @@ struct rwkv_mi_batch {
     StopTables stop{};                   // the device pointers of the current call
     size_t stop_off_lens = 0;            // where lens[n], reasons[n] start in both buffers
     size_t last_loop_passes = 0;
-    LogprobReport lp;                    // the report of the batch's emitting calls (rwkv_mi_batch_set_logprobs)
+    // rwkv_mi_batch_decode_beam: the per-row words of a call (BeamTables: scores, finished words, lengths, live count, candidates) in one device
+    // buffer for n_slots rows, with the pinned staging of the part a call uploads and reads back -- allocated by the first beam call, as are
+    // h_live_count and ev_block above where decode_until has not
+    DevBuf<uint8_t> d_beam;
+    PinBuf<uint8_t> h_beam;
+    LogprobReport lp;                   // the report of the batch's emitting calls (rwkv_mi_batch_set_logprobs)
 
     float * slot_buf(size_t slot, int p) const { return states.p + ((size_t) p * n_slots + slot) * (size_t) state_len; }
 };
@@ -1466,6 +1471,166 @@ static bool batch_until(rwkv_mi_batch * B, const BatchCall & c, uint32_t * token
     return true;
 }
 
+// ---- beam search (rwkv_mi_batch_decode_beam) ----
+
+// a call of G groups of W hypotheses: row g * W + j is slot slots[g * W + j]
+struct BeamCall {
+    const uint32_t * slots, * first_tokens;
+    size_t G;
+    const rwkv_mi_beam_params * p;
+    size_t n_tokens;
+};
+
+// bytes of the beam words of `rows` rows and where they start: scores (double), finished, lens, the live count (with a pad word) -- the part a
+// call uploads -- then the candidates' ids and log-probs [rows][RWKV_MI_TOP_MAX] and the body's unused word per row
+struct BeamLayout {
+    size_t finished, lens, count, upload, ids, lp, chosen, bytes;
+    explicit BeamLayout(size_t rows) {
+        finished = rows * sizeof(double); lens = finished + rows * 4; count = lens + rows * 4; upload = count + 8;
+        ids = upload; lp = ids + rows * RWKV_MI_TOP_MAX * 4; chosen = lp + rows * RWKV_MI_TOP_MAX * 4; bytes = chosen + rows * 4;
+    }
+};
+
+// every argument of a beam call, nothing changed yet
+static bool batch_check_beam(rwkv_mi_batch * B, const BeamCall & c) {
+    rwkv_context * ctx = B->ctx;
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, c.slots != nullptr && c.first_tokens != nullptr && c.p != nullptr, "slots, first_tokens or params is NULL");
+    const size_t n_vocab = (size_t) ctx->model->n_vocab(), W = c.p->width;
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, W >= 1 && W <= RWKV_MI_TOP_MAX && W <= n_vocab, "width (%zu) must be in 1 .. %d and at most n_vocab", W, RWKV_MI_TOP_MAX);
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, c.G >= 1 && c.G <= B->n_slots && c.G * W <= B->n_slots, "n_groups (%zu) x width (%zu) must be in 1 .. %zu rows", c.G, W, B->n_slots);
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, c.n_tokens > 0, "n_tokens is 0");
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, c.p->n_end <= 8 && (c.p->n_end == 0 || c.p->end_tokens != nullptr), "n_end (%" PRIu32 ") is above 8 or end_tokens is NULL", c.p->n_end);
+    for (uint32_t e = 0; e < c.p->n_end; e++)
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, c.p->end_tokens[e] < n_vocab, "end token at index %" PRIu32 " (%" PRIu32 ") is out of range (0 .. %zu)", e, c.p->end_tokens[e], n_vocab - 1);
+    std::vector<uint8_t> seen(B->n_slots, 0);
+    for (size_t r = 0; r < c.G * W; r++) {
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, c.slots[r] < B->n_slots, "slot %" PRIu32 " at index %zu is out of range (0 .. %zu)", c.slots[r], r, B->n_slots - 1);
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, !seen[c.slots[r]], "slot %" PRIu32 " appears twice", c.slots[r]);
+        seen[c.slots[r]] = 1;
+    }
+    for (size_t g = 0; g < c.G; g++)
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, c.first_tokens[g] < n_vocab, "Token at index %zu (%" PRIu32 ") is out of range (0 .. %zu)", g, c.first_tokens[g], n_vocab - 1);
+    return true;
+}
+
+// the beam words, the live count's pinned words and the two block events: on the first beam call
+static bool batch_ensure_beam(rwkv_mi_batch * B) {
+    rwkv_context * ctx = B->ctx;
+    if (B->d_beam && B->h_beam && B->h_live_count && B->ev_block[0] && B->ev_block[1]) return true;
+    const BeamLayout L(B->n_slots);
+    hipError_t e = grow(want(B->d_beam, B->d_beam ? 0 : L.bytes), want(B->h_beam, B->h_beam ? 0 : L.upload), want(B->h_live_count, B->h_live_count ? 0 : 2));
+    for (hipEvent_t & ev : B->ev_block) if (e == hipSuccess && !ev) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    if (e != hipSuccess) (void) hipGetLastError();
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the beam tables of %zu slots: %s", B->n_slots, hipGetErrorString(e));
+    return true;
+}
+
+// The device loop of a beam search: batch_until's blocks of passes, each pass followed by the two kernels of a step (engine.hip launch_row_sampler,
+// score.hip k_beam_rows / k_beam_select). A step RE-PARENTS instead of copying: the selection writes, into the row table of the next pass, for
+// every row the buffer its parent has just written as .in; .out stays the row's own slot's other buffer. Every read of a pass is of a buffer
+// the pass before wrote (the first: the group's start buffer), every write goes to the other buffer of a named slot -- no pass writes what it
+// or a later row of it reads, and any number of children share a parent. The only states that move are those of the last selection: a
+// hypothesis that ends in another slot's buffer is copied home, device to device, into its slot's idle buffer.
+static bool batch_beam(rwkv_mi_batch * B, const BeamCall & c, uint32_t * tokens_out, uint32_t * lens_out, double * scores_out, float * logprobs_out, float * elapsed_ms) {
+    rwkv_context * ctx = B->ctx;
+    rwkv_context * run = B->run;
+    ctx->last_error = RWKV_ERROR_NONE;
+    if (!batch_check_beam(B, c)) return false;
+    run->print_errors = ctx->print_errors;
+    const size_t W = c.p->width, n = c.G * W, n_tokens = c.n_tokens, K = loop_block();
+    BATCH_HIP_OK(B, hipSetDevice(ctx->model->device));
+    if (!batch_ensure_beam(B)) return false;
+    DevBuf<uint32_t> hist;   // token, parent, log-prob: [3][n_tokens][n], freed on every exit
+    hipError_t he = hist.alloc(3 * n_tokens * n);
+    if (he != hipSuccess) (void) hipGetLastError();
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, false, he == hipSuccess, "cannot allocate the history of %zu steps of %zu rows: %s", n_tokens, n, hipGetErrorString(he));
+    BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));   // (the previous call's copies may still read the staging)
+    // table 0: every row of a group from the group's start buffer into its own slot's other buffer; table 1: .out back into the current one
+    // (its .in is written by the first selection)
+    const BeamLayout L(n);
+    double * h_score = (double *) B->h_beam.p;
+    uint32_t * h_fin = (uint32_t *) (B->h_beam.p + L.finished), * h_len = (uint32_t *) (B->h_beam.p + L.lens);
+    for (size_t r = 0; r < n; r++) {
+        const size_t s0 = c.slots[r - r % W], s = c.slots[r];
+        float * cur = B->slot_buf(s, B->parity[s]), * oth = B->slot_buf(s, B->parity[s] ^ 1);
+        B->h_rows.p[r] = RowState{B->slot_buf(s0, B->parity[s0]), oth};
+        B->h_rows.p[B->n_slots + r] = RowState{oth, cur};
+        run->h_tokens.p[r] = c.first_tokens[r / W];
+        h_score[r] = r % W ? -INFINITY : 0.0;
+        h_fin[r] = 0u; h_len[r] = 0u;
+    }
+    *(uint32_t *) (B->h_beam.p + L.count) = (uint32_t) n;
+    for (int tb = 0; tb < 2; tb++)
+        BATCH_HIP_OK(B, hipMemcpyAsync(B->d_rows.p + (size_t) tb * B->n_slots, B->h_rows.p + (size_t) tb * B->n_slots, n * sizeof(RowState), hipMemcpyHostToDevice, run->stream));
+    BATCH_HIP_OK(B, hipMemcpyAsync(run->d_tokens.p, run->h_tokens.p, n * sizeof(uint32_t), hipMemcpyHostToDevice, run->stream));
+    BATCH_HIP_OK(B, hipMemcpyAsync(B->d_beam.p, B->h_beam.p, L.upload, hipMemcpyHostToDevice, run->stream));
+    uint8_t * d = B->d_beam.p;
+    BeamTables t{(double *) d, (uint32_t *) (d + L.finished), (uint32_t *) (d + L.lens), (uint32_t *) (d + L.ids), (float *) (d + L.lp), (float *) (d + L.chosen),
+                 hist.p, hist.p + n_tokens * n, (float *) (hist.p + 2 * n_tokens * n), (uint32_t *) (d + L.count), (uint32_t) W, c.p->n_end, {}};
+    for (uint32_t e = 0; e < c.p->n_end; e++) t.end_tokens[e] = c.p->end_tokens[e];
+    BATCH_HIP_OK(B, hipEventRecord(run->ev0, run->stream));
+    size_t passes = 0;
+    for (size_t b = 0; passes < n_tokens; b++) {
+        for (const size_t end = std::min(n_tokens, passes + K); passes < end; passes++) {
+            RowState * used = B->d_rows.p + (passes & 1) * B->n_slots, * other = B->d_rows.p + ((passes & 1) ^ 1) * B->n_slots;
+            const RowBeam beam{t, (uint32_t) passes, used, other};
+            RowSampler sampler{nullptr, nullptr, nullptr};
+            sampler.beam = &beam;
+            if (!forward_rows(run, used, (int64_t) n, true, &sampler)) return batch_fail_drained(B);
+        }
+        hipError_t e = hipMemcpyAsync(B->h_live_count.p + (b & 1), t.live_count, sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream);
+        if (e == hipSuccess) e = hipEventRecord(B->ev_block[b & 1], run->stream);
+        if (e == hipSuccess && b > 0) e = hipEventSynchronize(B->ev_block[(b - 1) & 1]);
+        if (e != hipSuccess) { (void) hipStreamSynchronize(run->stream); BATCH_HIP_OK(B, e); }
+        if (b > 0 && B->h_live_count.p[(b - 1) & 1] == 0) break;
+    }
+    BATCH_HIP_OK(B, hipEventRecord(run->ev1, run->stream));
+    std::vector<uint32_t> h(3 * passes * n);
+    for (size_t a = 0; a < 3; a++)
+        BATCH_HIP_OK(B, hipMemcpyAsync(h.data() + a * passes * n, hist.p + a * n_tokens * n, passes * n * sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream));
+    BATCH_HIP_OK(B, hipMemcpyAsync(B->h_beam.p, B->d_beam.p, L.count, hipMemcpyDeviceToHost, run->stream));
+    BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));
+    if (elapsed_ms) BATCH_HIP_OK(B, hipEventElapsedTime(elapsed_ms, run->ev0, run->ev1));
+    B->last_loop_passes = passes;
+    const uint32_t * h_tok = h.data(), * h_par = h.data() + passes * n;
+    const float * h_lp = (const float *) (h.data() + 2 * passes * n);
+    // the backtrace: hypothesis j of the last selection, then its parent's of the step before, ...; a step without a token (the hypothesis
+    // had finished) adds nothing. A dead hypothesis (score -inf) has no text.
+    std::vector<uint32_t> text(passes);
+    std::vector<float> text_lp(passes);
+    for (size_t r = 0; r < n; r++) {
+        size_t len = 0, at = r;
+        for (size_t i = passes; i-- > 0 && h_score[r] > -INFINITY;) {
+            const size_t w = i * n + at;
+            RW_CTX_CHECK(ctx, RWKV_ERROR_GRAPH, false, h_par[w] < W, "the history of row %zu is broken at step %zu (the device loop failed)", r, i);
+            if (h_tok[w] != RWKV_MI_NO_TOKEN) { text[len] = h_tok[w]; text_lp[len] = h_lp[w]; len++; }
+            at = r - r % W + h_par[w];
+        }
+        RW_CTX_CHECK(ctx, RWKV_ERROR_GRAPH, false, len == h_len[r], "row %zu has %zu tokens in the history and a length of %" PRIu32 " (the device loop failed)", r, len, h_len[r]);
+        if (lens_out) lens_out[r] = (uint32_t) len;
+        if (scores_out) scores_out[r] = h_score[r];
+        for (size_t j = 0; j < n_tokens; j++) {
+            if (tokens_out) tokens_out[r * n_tokens + j] = j < len ? text[len - 1 - j] : RWKV_MI_NO_TOKEN;
+            if (logprobs_out) logprobs_out[r * n_tokens + j] = j < len ? text_lp[len - 1 - j] : 0.0f;
+        }
+    }
+    // where the states are: the last pass wrote row x's into slot x's buffer parity ^ (passes & 1). An unfinished hypothesis whose last parent
+    // is another row is copied from that row's buffer into its own slot's other one, which no copy reads; the parities follow
+    const int odd = (int) (passes & 1);
+    std::vector<uint8_t> parity(n);
+    for (size_t r = 0; r < n; r++) {
+        const size_t s = c.slots[r], rp = r - r % W + h_par[(passes - 1) * n + r];
+        parity[r] = B->parity[s] ^ odd;
+        if (h_fin[r] || rp == r) continue;   // (an unfinished row's parent has been checked by its backtrace)
+        const size_t sp = c.slots[rp];
+        parity[r] ^= 1;
+        BATCH_HIP_OK(B, hipMemcpyAsync(B->slot_buf(s, parity[r]), B->slot_buf(sp, B->parity[sp] ^ odd), (size_t) B->state_len * sizeof(float), hipMemcpyDeviceToDevice, run->stream));
+    }
+    for (size_t r = 0; r < n; r++) B->parity[c.slots[r]] = parity[r];
+    BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));
+    return true;
+}
+
 extern "C" {
 
 RWKV_API void rwkv_mi_batch_free(struct rwkv_mi_batch * B) {
@@ -1719,6 +1884,36 @@ RWKV_API bool rwkv_mi_batch_decode_until(struct rwkv_mi_batch * B, const uint32_
 }
 
 RWKV_API size_t rwkv_mi_batch_last_loop_passes(const struct rwkv_mi_batch * B) { return B ? B->last_loop_passes : 0; }
+
+RWKV_API bool rwkv_mi_batch_state_copy(struct rwkv_mi_batch * B, size_t dst_slot, size_t src_slot, uint32_t what) {
+    rwkv_context * ctx = B->ctx;
+    ctx->last_error = RWKV_ERROR_NONE;
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, dst_slot < B->n_slots && src_slot < B->n_slots, "slot %zu or %zu is out of range", dst_slot, src_slot);
+    const uint32_t known = RWKV_MI_COPY_STATE | RWKV_MI_COPY_COUNTER | RWKV_MI_COPY_COUNTS | RWKV_MI_COPY_BIAS;
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, (what & ~known) == 0, "unknown bits in what (0x%" PRIx32 ")", what);
+    if (dst_slot == src_slot) return true;
+    BATCH_HIP_OK(B, hipSetDevice(ctx->model->device));
+    hipStream_t st = B->run->stream;
+    const size_t V = (size_t) ctx->model->n_vocab();
+    BATCH_HIP_OK(B, hipMemcpyAsync(B->slot_buf(dst_slot, B->parity[dst_slot]), B->slot_buf(src_slot, B->parity[src_slot]), (size_t) B->state_len * sizeof(float), hipMemcpyDeviceToDevice, st));
+    if (what & RWKV_MI_COPY_COUNTER)
+        BATCH_HIP_OK(B, hipMemcpyAsync(B->d_counters.p + dst_slot, B->d_counters.p + src_slot, sizeof(unsigned long long), hipMemcpyDeviceToDevice, st));
+    // (a batch without the penalty tables has every count 0 and no bias: there is nothing to copy)
+    if ((what & RWKV_MI_COPY_COUNTS) && B->d_counts)
+        BATCH_HIP_OK(B, hipMemcpyAsync(B->d_counts.p + dst_slot * V, B->d_counts.p + src_slot * V, V * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    if ((what & RWKV_MI_COPY_BIAS) && B->d_bias) {
+        BATCH_HIP_OK(B, hipMemcpyAsync(B->d_bias.p + dst_slot * V, B->d_bias.p + src_slot * V, V * sizeof(float), hipMemcpyDeviceToDevice, st));
+        B->has_bias[dst_slot] = B->has_bias[src_slot];
+    }
+    BATCH_HIP_OK(B, hipStreamSynchronize(st));
+    return true;
+}
+
+RWKV_API bool rwkv_mi_batch_decode_beam(struct rwkv_mi_batch * B, const uint32_t * slots, const uint32_t * first_tokens, size_t n_groups,
+                                        const struct rwkv_mi_beam_params * params, size_t n_tokens, uint32_t * tokens_out, uint32_t * lens_out,
+                                        double * scores_out, float * logprobs_out, float * elapsed_ms) {
+    return batch_beam(B, BeamCall{slots, first_tokens, n_groups, params, n_tokens}, tokens_out, lens_out, scores_out, logprobs_out, elapsed_ms);
+}
 
 RWKV_API bool rwkv_mi_batch_set_logprobs(struct rwkv_mi_batch * B, bool enabled, uint32_t top_n) {
     B->ctx->last_error = RWKV_ERROR_NONE;

@@ -815,6 +815,12 @@ void batch_context_destroy(rwkv_context * c) {
 // Order within a step: the draw (or argmax), then the report of what it wrote (s.report), then the stop test.
 static void launch_row_sampler(rwkv_context * ctx, const RowSampler & s, int64_t rows) {
     const int n_vocab = (int) ctx->model->n_vocab();
+    if (s.beam) {
+        // a step of rwkv_mi_batch_decode_beam: every row's candidates, then each group's selection (which writes the rows' next tokens)
+        launch_beam_rows(ctx->d_logits.p, rows, n_vocab, s.beam->t, ctx->stream);
+        launch_beam_select(s.beam->t, rows / (int64_t) s.beam->t.width, ctx->d_tokens.p, s.beam->step, s.beam->used, s.beam->other, ctx->stream);
+        return;
+    }
     if (s.stop) {
         // a step of rwkv_mi_batch_decode_until: the draw behind the live words, then the stop test on what it wrote
         uint32_t * hist = s.hist + (size_t) s.stop->step * (size_t) rows;

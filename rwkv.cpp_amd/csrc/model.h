@@ -140,6 +140,25 @@ struct StopTables { const StopRow * rows; const uint32_t * seq_lens, * seq_token
 // whose budget is step + 1. A retired row gets {in = what pass `step` wrote, out = its other buffer} in both row tables (used: the table of
 // pass `step`, other: the one of pass step + 1).
 void launch_stop_rows(const StopTables & t, int64_t rows, const uint32_t * hist, uint32_t step, RowState * used, RowState * other, hipStream_t st);
+// rwkv_mi_batch_decode_beam (score.hip): the device words of a call of G groups of `width` hypotheses, row g * width + j = hypothesis j of group g.
+// Per row its cumulative score (double), its finished word, its length; the candidates of the step -- cand_ids / cand_lp [rows][width], the
+// report's top-`width` of the row's logits -- and the word the shared body writes its unused `chosen` to; the history [steps][rows] of emitted
+// token (RWKV_MI_NO_TOKEN: none), parent (the index within the group) and the token's f32 log-prob; live_count (may be NULL): the unfinished
+// hypotheses of all groups; the ids that finish a hypothesis, by value.
+struct BeamTables {
+    double * score; uint32_t * finished, * len;
+    uint32_t * cand_ids; float * cand_lp; float * chosen;
+    uint32_t * hist_tok, * hist_parent; float * hist_lp;
+    uint32_t * live_count;
+    uint32_t width, n_end;
+    uint32_t end_tokens[8];
+};
+// The two kernels of a step, after the head of a pass over `rows` = groups * width rows: the candidates of every row that is unfinished and has a
+// finite score, then per group the selection, which rewrites the rows' words in place, appends row `step` of the history, puts each row's next
+// token into tokens[row] and re-parents the next pass: other[row].in = used[row of its parent].out (used: the row table of this pass, other:
+// the one of the next; both NULL: no table is touched).
+void launch_beam_rows(const float * logits, int64_t rows, int n, const BeamTables & t, hipStream_t st);
+void launch_beam_select(const BeamTables & t, int64_t groups, uint32_t * tokens, uint32_t step, const RowState * used, RowState * other, hipStream_t st);
 void launch_count_add(uint32_t * count, const uint32_t * tokens, int64_t n, int n_vocab, hipStream_t st);                        // count[tokens[i]] += 1
 void launch_bias_scatter(float * bias, const uint32_t * ids, const float * values, int64_t n, int n_vocab, hipStream_t st);     // bias[ids[i]] = values[i]
 
@@ -291,10 +310,13 @@ void batch_context_destroy(rwkv_context * c);
 // launch_stop_rows follows it, both inside the pass's place in the chain; hist is then the WHOLE history [step][T] and step's row is written
 // report: when given, launch_logprob_rows follows the draw (and precedes the stop test) on the tokens it wrote: the pointers are the step's slot of
 // the report buffers -- with stop, as hist, the WHOLE buffers, and step's slot is written behind the live words
+// beam: the pass is step `step` of rwkv_mi_batch_decode_beam -- instead of a draw, launch_beam_rows and launch_beam_select follow the head, both
+// inside the pass's place in the chain; nothing else of the sampler is read
 struct RowStop { StopTables t; uint32_t step; RowState * used, * other; };
 struct RowReport { float * chosen; uint32_t * ids; float * vals; uint32_t top_n; };
+struct RowBeam { BeamTables t; uint32_t step; const RowState * used; RowState * other; };
 struct RowSampler { const SampleRow * table; float * probs; uint32_t * hist; const PenaltyRow * ptable = nullptr; const RowStop * stop = nullptr;
-                    const RowReport * report = nullptr; };
+                    const RowReport * report = nullptr; const RowBeam * beam = nullptr; };
 bool forward_rows(rwkv_context * ctx, const RowState * d_rows, int64_t T, bool want_logits, const RowSampler * sample = nullptr);
 
 // Ragged batch pass: row i of the call is a SEGMENT, tokens [t0, t1) of the pass, consecutive tokens of one slot's sequence.

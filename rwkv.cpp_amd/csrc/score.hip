@@ -180,6 +180,108 @@ __global__ __launch_bounds__(1024) void k_logprob_rows_live(const float * __rest
     logprob_row_body(logits_all + r * (size_t) n, n, tokens[r], top_n, chosen + r, top_ids + r * (size_t) top_n, top_lp + r * (size_t) top_n);
 }
 
+// ---- one step of the beam search (rwkv_mi_batch_decode_beam): the rows' candidates, then the selection of each group ----
+// The candidates of a row are the report's top-N at N = the beam width, through the report's body: ids and f32 log-probs in the report's order,
+// bit for bit what k_logprob_rows gives the row. Behind the row's own words (the pattern of the _live kernels): a finished hypothesis, and one
+// whose score is -inf, offers nothing of its logits and its workgroup returns before it reads one. (The body's `chosen` is asked for no token:
+// it writes the 0 of an index behind the row into a word nobody reads.)
+__global__ __launch_bounds__(1024) void k_beam_rows(const float * __restrict__ logits_all, int n, int width, const double * __restrict__ score,
+                                                    const uint32_t * __restrict__ finished, float * __restrict__ chosen, uint32_t * __restrict__ cand_ids,
+                                                    float * __restrict__ cand_lp) {
+    const size_t r = blockIdx.x;
+    if (finished[r] || !(score[r] > -INFINITY)) return;
+    logprob_row_body(logits_all + r * (size_t) n, n, UINT32_MAX, width, chosen + r, cand_ids + r * (size_t) width, cand_lp + r * (size_t) width);
+}
+
+// The selection, one wave per group of W = t.width hypotheses (rows g W .. g W + W - 1); lane i < W holds hypothesis i.
+// Candidates, numbered c = parent * W + rank: a live parent with a finite score offers its W (id, lp) pairs with the cumulative score
+// (double) score[parent] + (double) lp, kept as double -- not the pairs without a token or whose lp is not above -inf (-inf, or the NaN of a
+// row that holds one); a finished parent with a finite score offers itself once, at rank 0, with its score and no token; a score of -inf
+// offers nothing. The W best by score descending, then c ascending (parent, then rank) -- a total order on distinct c, so the result does not
+// depend on the order of execution: round j finds the best candidate behind the one round j - 1 found, per lane over c = lane, lane + 64, ...,
+// the 64 lanes by the xor butterfly (32, 16, ... 1), and lane j keeps it. Every lane reads what it needs of the group into registers before any
+// lane writes (the words are rewritten in place).
+// Hypothesis j then becomes selection j: its token goes to tokens[row] (where the row's next embedding lookup reads it) and to the history;
+// a finished one is fed the token it was fed before (a dead step) and records no token; one for which no candidate is left is dead: score
+// -inf, parent itself, finished, length 0. other[row].in = used[row of the parent].out re-parents the next pass; other[row].out stays.
+// live_count moves by the change of the group's unfinished hypotheses: an integer sum, the same in any order.
+__global__ __launch_bounds__(64) void k_beam_select(BeamTables t, size_t rows, uint32_t * tokens, uint32_t step, const RowState * used, RowState * other) {
+    constexpr int Q = (RWKV_MI_TOP_MAX * RWKV_MI_TOP_MAX + 63) / 64;   // candidates per lane
+    const int W = (int) t.width, lane = threadIdx.x;
+    const size_t r0 = (size_t) blockIdx.x * (size_t) W;
+    const bool mine = lane < W;
+    double sc = -INFINITY;
+    uint32_t fin = 1u, len = 0u, fed = 0u;
+    if (mine) { sc = t.score[r0 + lane]; fin = t.finished[r0 + lane]; len = t.len[r0 + lane]; fed = tokens[r0 + lane]; }
+    double cs[Q];
+#pragma unroll
+    for (int q = 0; q < Q; q++) {
+        const int c = lane + 64 * q;
+        const bool in = c < W * W;
+        const int p = in ? c / W : 0, k = in ? c % W : 0;
+        const double ps = __shfl(sc, p, WAVE);
+        const uint32_t pf = __shfl(fin, p, WAVE);
+        cs[q] = -INFINITY;
+        if (!in || !(ps > -INFINITY)) continue;
+        if (pf) { if (k == 0) cs[q] = ps; continue; }
+        const size_t at = (r0 + (size_t) p) * (size_t) W + (size_t) k;
+        const float lp = t.cand_lp[at];
+        if (t.cand_ids[at] != UINT32_MAX && lp > -INFINITY) cs[q] = ps + (double) lp;
+    }
+    double prev_s = INFINITY, my_s = -INFINITY;
+    int prev_c = -1, my_c = 0x7fffffff;
+    for (int j = 0; j < W; j++) {
+        double bs = -INFINITY;
+        int bc = 0x7fffffff;
+#pragma unroll
+        for (int q = 0; q < Q; q++) {
+            const int c = lane + 64 * q;
+            const double s = cs[q];
+            if (!(s > -INFINITY) || !(s < prev_s || (s == prev_s && c > prev_c))) continue;
+            if (s > bs || (s == bs && c < bc)) { bs = s; bc = c; }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const double os = __shfl_xor(bs, o, WAVE);
+            const int oc = __shfl_xor(bc, o, WAVE);
+            if (os > bs || (os == bs && oc < bc)) { bs = os; bc = oc; }
+        }
+        if (lane == j) { my_s = bs; my_c = bc; }
+        if (bc == 0x7fffffff) break;   // (uniform: every lane holds the wave's best; nothing is left for the later rounds either)
+        prev_s = bs; prev_c = bc;
+    }
+    const bool dead = my_c == 0x7fffffff;
+    const int parent = dead ? (mine ? lane : 0) : my_c / W;
+    const uint32_t p_fin = __shfl(fin, parent, WAVE), p_len = __shfl(len, parent, WAVE), p_fed = __shfl(fed, parent, WAVE);
+    uint32_t tok = UINT32_MAX, n_fin = 1u, n_len = 0u, n_fed = fed;
+    float lp = 0.0f;
+    if (mine && !dead) {
+        n_fed = p_fed; n_len = p_len;
+        if (!p_fin) {
+            const size_t at = (r0 + (size_t) parent) * (size_t) W + (size_t) (my_c % W);
+            tok = t.cand_ids[at]; lp = t.cand_lp[at];
+            n_fed = tok; n_len = p_len + 1u; n_fin = 0u;
+            for (uint32_t e = 0; e < t.n_end; e++) if (tok == t.end_tokens[e]) n_fin = 1u;
+        }
+    }
+    const int before = __popcll(__ballot(mine && !fin)), after = __popcll(__ballot(mine && !n_fin));
+    if (lane == 0 && t.live_count && after != before) atomicAdd(t.live_count, (uint32_t) (after - before));
+    if (!mine) return;
+    const size_t r = r0 + (size_t) lane, h = (size_t) step * rows + r;
+    t.score[r] = dead ? -INFINITY : my_s; t.finished[r] = n_fin; t.len[r] = n_len;
+    tokens[r] = n_fed;
+    t.hist_tok[h] = tok; t.hist_parent[h] = (uint32_t) parent; t.hist_lp[h] = lp;
+    if (other) other[r].in = used[r0 + (size_t) parent].out;
+}
+
+void launch_beam_rows(const float * logits, int64_t rows, int n, const BeamTables & t, hipStream_t st) {
+    if (rows > 0) hipLaunchKernelGGL(k_beam_rows, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, (int) t.width, t.score, t.finished, t.chosen, t.cand_ids, t.cand_lp);
+}
+
+void launch_beam_select(const BeamTables & t, int64_t groups, uint32_t * tokens, uint32_t step, const RowState * used, RowState * other, hipStream_t st) {
+    if (groups > 0) hipLaunchKernelGGL(k_beam_select, dim3((unsigned) groups), dim3(64), 0, st, t, (size_t) groups * t.width, tokens, step, used, other);
+}
+
 void launch_score_rows(const float * logits, int64_t rows, int n, const uint32_t * targets, float * logprobs, uint32_t * argmax, hipStream_t st) {
     if (rows > 0 && (logprobs || argmax)) hipLaunchKernelGGL(k_score_rows, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, targets, logprobs, argmax);
 }

@@ -1,11 +1,13 @@
 // testhooks_sample.cpp -- the sampler's entry point for tests/ ONLY (include/rwkv_testhooks_sample.h), the scoring kernel's
-// (include/rwkv_testhooks_score.h) and the report kernel's (include/rwkv_testhooks_logprobs.h). `make` links it with every product
+// (include/rwkv_testhooks_score.h), the report kernel's (include/rwkv_testhooks_logprobs.h) and the beam step's
+// (include/rwkv_testhooks_beam.h). `make` links it with every product
 // object into a third library, lib/librwkv_testhooks_sample.so; neither librwkv.so nor librwkv_testhooks.so carries it.
 #include "model.h"
 #include "rwkv_mi355x.h"
 #include "rwkv_testhooks_sample.h"
 #include "rwkv_testhooks_score.h"
 #include "rwkv_testhooks_logprobs.h"
+#include "rwkv_testhooks_beam.h"
 
 #include <vector>
 
@@ -92,6 +94,42 @@ RWKV_API bool rwkv_test_logprob_rows(const float * logits, int64_t rows, int64_t
              (!chosen_out || hipMemcpy(chosen_out, d_ch, R * 4, hipMemcpyDeviceToHost) == hipSuccess) &&
              (!top_ids_out || !top_n || hipMemcpy(top_ids_out, d_ids, R * top_n * 4, hipMemcpyDeviceToHost) == hipSuccess) &&
              (!top_logprobs_out || !top_n || hipMemcpy(top_logprobs_out, d_lp, R * top_n * 4, hipMemcpyDeviceToHost) == hipSuccess);
+    }
+    RW_CHECK(RWKV_ERROR_GRAPH, false, ok, "HIP error: %s", hipGetErrorString(hipGetLastError()));
+    return true;
+}
+
+// Test hook: the two kernels of one beam step on standalone logits, scores and finished words.
+RWKV_API bool rwkv_test_beam_step(const float * logits, int64_t groups, int64_t n_vocab, const double * scores_in, const uint32_t * finished_in,
+                                  uint32_t width, const uint32_t * end_tokens, uint32_t n_end, uint32_t * tokens_out, uint32_t * parents_out,
+                                  float * logprobs_out, double * scores_out, uint32_t * finished_out) {
+    g_last_error = RWKV_ERROR_NONE;
+    RW_CHECK(RWKV_ERROR_ARGS, false, logits && scores_in && finished_in && groups > 0 && n_vocab > 0 && n_vocab <= (int64_t) 1 << 24 &&
+             width >= 1 && width <= RWKV_MI_TOP_MAX && (int64_t) width <= n_vocab && groups * (int64_t) width <= 65535 && n_end <= 8 && (!n_end || end_tokens),
+             "bad arguments");
+    for (uint32_t e = 0; e < n_end; e++) RW_CHECK(RWKV_ERROR_ARGS, false, (int64_t) end_tokens[e] < n_vocab, "end token %u is out of range", e);
+    const size_t R = (size_t) groups * width, V = (size_t) n_vocab;
+    DevBuf<float> logits_buf, lp_buf, ch_buf, hlp_buf;
+    DevBuf<double> score_buf;
+    DevBuf<uint32_t> fin_buf, len_buf, ids_buf, tok_buf, htok_buf, hpar_buf;
+    bool ok = logits_buf.alloc(R * V) == hipSuccess && lp_buf.alloc(R * width) == hipSuccess && ch_buf.alloc(R) == hipSuccess && hlp_buf.alloc(R) == hipSuccess &&
+              score_buf.alloc(R) == hipSuccess && fin_buf.alloc(R) == hipSuccess && len_buf.alloc(R) == hipSuccess && ids_buf.alloc(R * width) == hipSuccess &&
+              tok_buf.alloc(R) == hipSuccess && htok_buf.alloc(R) == hipSuccess && hpar_buf.alloc(R) == hipSuccess;
+    ok = ok && hipMemcpy(logits_buf.p, logits, R * V * 4, hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(score_buf.p, scores_in, R * 8, hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(fin_buf.p, finished_in, R * 4, hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemset(len_buf.p, 0, R * 4) == hipSuccess && hipMemset(tok_buf.p, 0, R * 4) == hipSuccess;
+    if (ok) {
+        BeamTables t{score_buf.p, fin_buf.p, len_buf.p, ids_buf.p, lp_buf.p, ch_buf.p, htok_buf.p, hpar_buf.p, hlp_buf.p, nullptr, width, n_end, {}};
+        for (uint32_t e = 0; e < n_end; e++) t.end_tokens[e] = end_tokens[e];
+        launch_beam_rows(logits_buf.p, (int64_t) R, (int) n_vocab, t, nullptr);
+        launch_beam_select(t, groups, tok_buf.p, 0u, nullptr, nullptr, nullptr);
+        ok = hipDeviceSynchronize() == hipSuccess &&
+             (!tokens_out || hipMemcpy(tokens_out, htok_buf.p, R * 4, hipMemcpyDeviceToHost) == hipSuccess) &&
+             (!parents_out || hipMemcpy(parents_out, hpar_buf.p, R * 4, hipMemcpyDeviceToHost) == hipSuccess) &&
+             (!logprobs_out || hipMemcpy(logprobs_out, hlp_buf.p, R * 4, hipMemcpyDeviceToHost) == hipSuccess) &&
+             (!scores_out || hipMemcpy(scores_out, score_buf.p, R * 8, hipMemcpyDeviceToHost) == hipSuccess) &&
+             (!finished_out || hipMemcpy(finished_out, fin_buf.p, R * 4, hipMemcpyDeviceToHost) == hipSuccess);
     }
     RW_CHECK(RWKV_ERROR_GRAPH, false, ok, "HIP error: %s", hipGetErrorString(hipGetLastError()));
     return true;

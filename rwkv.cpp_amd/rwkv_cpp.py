@@ -31,7 +31,9 @@ SCORE_SYMBOLS = ("rwkv_mi_score_resident", "rwkv_mi_batch_score_ragged")
 UNTIL_SYMBOLS = ("rwkv_mi_batch_decode_until", "rwkv_mi_batch_last_loop_passes")
 LOGPROBS_SYMBOLS = ("rwkv_mi_batch_set_logprobs", "rwkv_mi_batch_logprobs_shape", "rwkv_mi_batch_logprobs_store",
                     "rwkv_mi_set_logprobs", "rwkv_mi_logprobs_shape", "rwkv_mi_logprobs_store")
-TOP_MAX = 20             # RWKV_MI_TOP_MAX: the most alternatives a report holds per token
+BEAM_SYMBOLS = ("rwkv_mi_batch_state_copy", "rwkv_mi_batch_decode_beam")
+COPY_STATE, COPY_COUNTER, COPY_COUNTS, COPY_BIAS = 1, 2, 4, 8   # RWKV_MI_COPY_*: the bits of rwkv_mi_batch_state_copy's `what`
+TOP_MAX = 20             # RWKV_MI_TOP_MAX: the most alternatives a report holds per token, and the widest beam
 NO_TARGET = 0xFFFFFFFF   # RWKV_MI_NO_TARGET: a position that is not scored (its log-prob is 0)
 NO_TOKEN = 0xFFFFFFFF    # RWKV_MI_NO_TOKEN: no token (past a row's length), no stop sequence (the budget ended the row)
 STOP_MAX_SEQS = 16       # RWKV_MI_STOP_MAX_SEQS
@@ -62,6 +64,11 @@ class StopParams(ctypes.Structure):
 
 
 P_STOP_PARAMS = ctypes.POINTER(StopParams)
+
+
+class BeamParams(ctypes.Structure):
+    """struct rwkv_mi_beam_params (include/rwkv_mi355x.h): the beam width and the ids that finish a hypothesis, 16 bytes."""
+    _fields_ = [("width", ctypes.c_uint32), ("n_end", ctypes.c_uint32), ("end_tokens", P_UINT32)]
 
 
 def build_library(force: bool = False) -> str:
@@ -260,6 +267,17 @@ class RWKVSharedLibrary:
                 getattr(L, prefix + "logprobs_store").argtypes = [handle, ctypes.c_size_t, P_FLOAT, P_UINT32, P_FLOAT]
             for name in LOGPROBS_SYMBOLS:
                 getattr(L, name).restype = ctypes.c_bool
+        # slot-to-slot copy and beam search
+        if hasattr(L, "rwkv_mi_batch_decode_beam"):   # (absent from older A/B builds loaded through RWKV_LIB_DIR)
+            L.rwkv_mi_batch_state_copy.argtypes = [c_batch, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint32]
+            L.rwkv_mi_batch_decode_beam.argtypes = [c_batch, P_UINT32, P_UINT32, ctypes.c_size_t, ctypes.POINTER(BeamParams), ctypes.c_size_t, P_UINT32, P_UINT32,
+                                                    ctypes.POINTER(ctypes.c_double), P_FLOAT, P_FLOAT]
+            for name in BEAM_SYMBOLS:
+                getattr(L, name).restype = ctypes.c_bool
+        if hasattr(L, "rwkv_test_beam_step"):   # (librwkv_testhooks_sample.so only)
+            L.rwkv_test_beam_step.argtypes = [P_FLOAT, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_double), P_UINT32, ctypes.c_uint32, P_UINT32,
+                                              ctypes.c_uint32, P_UINT32, P_UINT32, P_FLOAT, ctypes.POINTER(ctypes.c_double), P_UINT32]
+            L.rwkv_test_beam_step.restype = ctypes.c_bool
         if hasattr(L, "rwkv_test_logprob_rows"):   # (librwkv_testhooks_sample.so only)
             L.rwkv_test_logprob_rows.argtypes = [P_FLOAT, ctypes.c_int64, ctypes.c_int64, P_UINT32, ctypes.c_uint32, P_FLOAT, P_UINT32, P_FLOAT]
             L.rwkv_test_logprob_rows.restype = ctypes.c_bool
@@ -960,6 +978,40 @@ class RWKVBatch:
                                                   ctypes.byref(ms)):
             self._fail("rwkv_mi_batch_decode_until")
         return [out[i, : int(lens[i])].copy() for i in range(n)], why, float(ms.value)
+
+    # --- slot-to-slot copy and beam search (include/rwkv_mi355x.h) ---
+
+    def copy_state(self, dst: int, src: int, counter: bool = False, counts: bool = False, bias: bool = False) -> None:
+        """Slot src's state into slot dst, device to device (n samples of one prompt: prefill once, copy n - 1 times); with counter, counts, bias:
+        the slot's draw counter, occurrence table, bias table as well. dst == src does nothing."""
+        what = COPY_STATE | (COPY_COUNTER if counter else 0) | (COPY_COUNTS if counts else 0) | (COPY_BIAS if bias else 0)
+        if not self._L.rwkv_mi_batch_state_copy(self._ptr, dst, src, what):
+            self._fail("rwkv_mi_batch_state_copy")
+
+    def decode_beam(self, slots, first_tokens: List[int], width: int, n_tokens: int, end_tokens=(), want_logprobs: bool = True):
+        """Beam search on the device: G groups of `width` hypotheses. slots: [G][width] distinct slots (a flat list of G * width is taken too);
+        group g starts from the state of slots[g][0] -- which is consumed: keep a prompt with copy_state -- and first_tokens[g]. A hypothesis
+        finishes at one of end_tokens (at most 8 ids). Returns (tokens [G][width][n_tokens] with NO_TOKEN past a hypothesis' length, lens
+        [G][width], scores float64 [G][width], logprobs float32 [G][width][n_tokens] or None, elapsed milliseconds); hypothesis 0 is the best.
+        Afterwards slots[g][j] continues an unfinished hypothesis j as a greedy loop's slot would: eval its last token."""
+        s = _u32(slots).reshape(-1)
+        t = _u32(first_tokens).reshape(-1)
+        width = int(width)
+        if width < 1 or s.size != t.size * width:
+            raise ValueError("slots must hold width slots per first token")
+        G = t.size
+        ends = _u32(list(end_tokens)).reshape(-1)
+        params = BeamParams(width, ends.size, ends.ctypes.data_as(P_UINT32) if ends.size else None)
+        tokens = np.empty((G, width, n_tokens), dtype=np.uint32)
+        lens = np.zeros((G, width), dtype=np.uint32)
+        scores = np.empty((G, width), dtype=np.float64)
+        lps = np.empty((G, width, n_tokens), dtype=np.float32) if want_logprobs else None
+        ms = ctypes.c_float(0.0)
+        if not self._L.rwkv_mi_batch_decode_beam(self._ptr, s.ctypes.data_as(P_UINT32), t.ctypes.data_as(P_UINT32), G, ctypes.byref(params), n_tokens,
+                                                 ctypes.cast(tokens.ctypes.data, P_UINT32), lens.ctypes.data_as(P_UINT32),
+                                                 scores.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.cast(_ptr(lps), P_FLOAT), ctypes.byref(ms)):
+            self._fail("rwkv_mi_batch_decode_beam")
+        return tokens, lens, scores, lps, float(ms.value)
 
     # --- the report: log-probs and top-N alternatives of every emitted token (include/rwkv_mi355x.h) ---
 

@@ -44,6 +44,12 @@ top_n of the list; records also go to --out:
   mode logprobs_report   ms per step with the report at this top_n, the same run's step without it, and their difference
   mode logprobs_host     the way without it: RWKVBatch.eval with the logits to the host, then a float64 log-softmax and np.argpartition for
                          the largest top_n of the list on each row, the token taken as its argmax; host clock around the loop
+
+--beam W[,W...] times rwkv_mi_batch_decode_beam (no end tokens, --tokens steps) for every width of the list, G = rows // W groups at the largest
+row count of --n, HIP events around each device loop, the smallest of --reps runs; records also go to --out:
+  mode beam        ms per step of the beam loop beside the greedy loop's at the same row count from the same run, and their difference
+  mode beam_host   the search driven from the host with the calls that existed before: RWKVBatch.eval with the logits to the host, a float64
+                   log-softmax and the W best of each row, the selection, the states permuted with state_store / state_load; host clock
 """
 import argparse
 import json
@@ -280,6 +286,87 @@ def logprobs(pkg, m, args):
         sink.close()
 
 
+def beam(pkg, m, args):
+    import numpy as np
+    V = m.n_vocab
+    sink = open(args.out, "a") if args.out else None
+    steps = args.tokens
+    widths = [int(x) for x in args.beam.split(",")]
+    rows_wanted = max(int(x) for x in args.n.split(","))
+
+    def emit(rec):
+        rec.update({"steps": steps, "reps": args.reps, "config": args.config, "dtype": args.dtype})
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if sink:
+            sink.write(line + "\n")
+            sink.flush()
+
+    b = pkg.RWKVBatch(m, rows_wanted)
+    for W in widths:
+        G = max(1, rows_wanted // W)
+        n = G * W
+        slots = list(range(n))
+        first = [(7 * g + 1) % V for g in range(G)]
+
+        def best(run):
+            out = []
+            for k in range(args.reps + 1):   # (run 0: warm-up -- buffers of the first call, tile-major weight images)
+                for s in slots:
+                    b.state_load(s, None)
+                out.append(run())
+            return min(out[1:])
+
+        greedy_ms = best(lambda: b.decode_greedy(slots, [first[r // W] for r in range(n)], steps)[1])
+        beam_ms = best(lambda: b.decode_beam(slots, first, W, steps)[4])
+        emit({"mode": "beam", "width": W, "groups": G, "rows": n, "ms_per_step": round(beam_ms / steps, 4), "greedy_ms_per_step": round(greedy_ms / steps, 4),
+              "beam_step_minus_greedy_ms": round((beam_ms - greedy_ms) / steps, 4), "beam_over_greedy": round(beam_ms / greedy_ms, 4), "passes": b.last_loop_passes()})
+
+        def host():
+            # the search driven from the host with calls that existed before: the logits to the host, a float64 log-softmax and the W best
+            # of each row there, the selection, the states permuted with state_store / state_load
+            score = np.where(np.arange(n) % W == 0, 0.0, -np.inf)
+            fed = [first[r // W] for r in range(n)]
+            for s in slots:
+                if s % W:
+                    b.state_load(s, b.state_store(s - s % W))
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                lg = b.eval(slots, fed).astype(np.float64)
+                mx = lg.max(axis=1, keepdims=True)
+                lp = lg - (mx + np.log(np.exp(lg - mx).sum(axis=1, keepdims=True)))
+                top = np.argpartition(-lp, W - 1, axis=1)[:, :W] if W < V else np.tile(np.arange(V), (n, 1))
+                top = np.take_along_axis(top, np.argsort(-np.take_along_axis(lp, top, axis=1), axis=1, kind="stable"), axis=1)
+                cand = score[:, None] + np.take_along_axis(lp, top, axis=1)
+                states = None
+                for g in range(G):
+                    flat = cand[g * W:(g + 1) * W].reshape(-1)
+                    pick = np.argsort(-flat, kind="stable")[:W]
+                    parents = pick // W
+                    if np.any(parents != np.arange(W)):
+                        if states is None:
+                            states = {}
+                        for j in range(W):
+                            p = g * W + int(parents[j])
+                            if p != g * W + j and p not in states:
+                                states[p] = b.state_store(p)
+                        for j in range(W):
+                            p = g * W + int(parents[j])
+                            if p != g * W + j:
+                                b.state_load(g * W + j, states[p])
+                    score[g * W:(g + 1) * W] = flat[pick]
+                    for j in range(W):
+                        fed[g * W + j] = int(top[g * W + int(parents[j]), int(pick[j]) % W])
+            return (time.perf_counter() - t0) * 1e3
+
+        host_ms = best(host)
+        emit({"mode": "beam_host", "width": W, "groups": G, "rows": n, "ms_per_step": round(host_ms / steps, 4), "beam_ms_per_step": round(beam_ms / steps, 4),
+              "host_over_device": round(host_ms / beam_ms, 2), "logits_bytes_per_step": 4 * n * V, "state_bytes": 4 * m.state_len})
+    b.free()
+    if sink:
+        sink.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("model_path")
@@ -294,8 +381,10 @@ def main():
     ap.add_argument("--until", action="store_true", help="time rwkv_mi_batch_decode_until against the plain sampled loop (see above)")
     ap.add_argument("--logprobs", default=None, metavar="N[,N...]",
                     help="with --sample: time the sampled loop with and without the report of the emitted tokens, for each top_n of the list (see above)")
-    ap.add_argument("--reps", type=int, default=3, help="--ragged, --until, --logprobs: timed runs of each shape (the smallest is reported)")
-    ap.add_argument("--out", default=None, help="--ragged, --penalties, --until, --logprobs: also append the records to this file")
+    ap.add_argument("--beam", default=None, metavar="W[,W...]",
+                    help="time rwkv_mi_batch_decode_beam for each width of the list at the largest row count of --n, against the greedy loop and the host-driven search")
+    ap.add_argument("--reps", type=int, default=3, help="--ragged, --until, --logprobs, --beam: timed runs of each shape (the smallest is reported)")
+    ap.add_argument("--out", default=None, help="--ragged, --penalties, --until, --logprobs, --beam: also append the records to this file")
     args = ap.parse_args()
 
     import __graft_entry__ as graft
@@ -320,6 +409,10 @@ def main():
         return
     if args.until:
         until(pkg, m, args)
+        m.free()
+        return
+    if args.beam is not None:
+        beam(pkg, m, args)
         m.free()
         return
     if args.logprobs is not None:

@@ -161,6 +161,46 @@ RG_HD uint32_t rg_next_own_in_layer(const RingCu & c, int cons, int from) {
     return RG_NONE;
 }
 
+// ---- what ONE consumer wave needs of the above, phase by phase ----
+// The geometry is the same for every layer and every launch, so the host evaluates the functions above once per (workgroup, consumer
+// wave, phase) and the kernel reads the entry of the phase it enters -- eight dwords through the scalar cache -- instead of carrying a
+// RingCu through the layer loop (ring_v6.hip, pre_begin). Filled by rg_wave() and by nothing else; only the six-apart deal (bal == 0).
+struct RingWavePhase {
+    uint32_t j0;        // rg_first_j: the wave's first record of the phase (its t-th is j0 + RG_NC * t)
+    uint32_t cnt;       // rg_own_count
+    uint32_t pos;       // offset of record j0 in the layer block: off[phase] + j0 * rec[phase]
+    uint32_t after;     // rg_next_own_in_layer(phase + 1): where the wave's stream continues behind the phase (RG_NONE: in the next block)
+    uint32_t ro;        // pos % ring bytes
+    uint32_t pad[3];
+};
+struct RingWave {
+    RingWavePhase ph[RG_NPHASE];
+    uint32_t layer_bytes;   // of the workgroup's layer block
+    uint32_t layer_ro;      // layer_bytes % ring bytes
+    uint32_t first_own;     // rg_next_own_in_layer(0)
+    uint32_t pad[5];
+};
+static_assert(sizeof(RingWavePhase) == 32 && sizeof(RingWave) == 256, "RingWave: one scalar load per phase");
+RG_HD RingWave rg_wave(const RingCu & c, int cons, uint32_t ring_bytes) {
+    RingWave w;
+    for (int p = 0; p < RG_NPHASE; p++) {
+        RingWavePhase & e = w.ph[p];
+        e.j0 = rg_first_j(c, p, cons);
+        e.cnt = rg_own_count(c, p, cons);
+        e.pos = c.off[p] + e.j0 * c.rec[p];
+        e.after = rg_next_own_in_layer(c, cons, p + 1);
+        e.ro = e.pos % ring_bytes;
+        e.pad[0] = e.pad[1] = e.pad[2] = 0;
+    }
+    w.layer_bytes = c.layer_bytes;
+    w.layer_ro = c.layer_bytes % ring_bytes;
+    w.first_own = rg_next_own_in_layer(c, cons, 0);
+    for (int i = 0; i < 5; i++) w.pad[i] = 0;
+    return w;
+}
+// the table's entry of (workgroup b, consumer wave cons)
+RG_HD int rg_wave_index(int b, int cons) { return b * RG_NC + cons; }
+
 // ---- the head projection behind the last layer (F16 head.weight, ggml's F16 dot order: 32 partial sums k mod 32, four lanes per row) ----
 // Workgroup b owns rows [b * hg * 16, (b + 1) * hg * 16) in hg row groups of 16 rows; a record = 16 rows x RG_HSTEPS steps of 32
 // columns: [step][lane = 4 * row + q] 16 bytes = columns 32 step + 8 q .. + 7 of that row (lane-linear for the consumer, 1 KiB per step).

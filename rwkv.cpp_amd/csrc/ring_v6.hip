@@ -42,13 +42,15 @@ struct R6P {
     int act_stride;                                    // units between the five mix images
     unsigned * ctl;                                    // [0] tag generation, [1] abort
     const unsigned char * stream; const R6Cu * cus;     // the per-workgroup weight streams
+    const RingWave * waves;                            // [workgroup][consumer wave]: its records of every phase (ring_geom.h, rg_wave; for THIS ring size)
     int layer0, layers_total;                          // this launch covers layers [layer0, layer0 + n_layers) of the stage's layers_total (the streamed rwkv_eval cuts a token into groups)
     int F, DR, R, H;
     int head_wg0;                                      // first of the H workgroups whose comm wave runs a WKV head
     unsigned ring_bytes, mirror_bytes;                 // LDS ring (multiple of 4 KiB) and how much of its head is repeated behind its end
     int inflight, thin;                                // loader: DMA instructions in flight (normal / while the workgroup gathers)
-    int look;                                          // consumers: records taken per look at a hand-over's sentinel (hint_take)
-    int look_g;                                        // ... at the kq hand-over (value records; RWKV_MI_RING_LOOKG)
+    unsigned look;                                     // consumers: records taken per look at a hand-over's sentinel (hint_take; RWKV_MI_RING_LOOK), as a
+                                                       // mask the host unpacks once: bit t = "a wave's take t is NOT preceded by a look" = t % look != 0
+    unsigned look_g;                                   // ... at the kq hand-over (value records; RWKV_MI_RING_LOOKG)
     int topup;                                         // consumers: landed records taken behind a completed gather (take_landed; RWKV_MI_RING_TOPUP: 1 prologue A, 2 prologue F, 4 kq hand-over)
     int hthin;                                         // ... while a wave of the workgroup watches a hand-over's sentinel (= inflight: no third level)
     int nap;                                           // extra 64-cycle sleeps between two looks at a gather's sentinel unit
@@ -69,7 +71,8 @@ enum { FL_LANDED = 0, FL_SWB = 1, FL_SWE = 2 /* wide sweeps begun / ended (the l
        FL_PROX = 25 /* consumer waves 4, 5 are done with their share of a prologue's elementwise part */,
        FL_HWB = 26, FL_HWE = 27 /* sentinel watches begun / ended (p.hthin: the loader's depth while a wave of the workgroup watches a hand-over) */,
        FL_XRQ = 28 /* waves done with the deferred quantisation of the ffn receptance input (quant_xr) */,
-       FL_AM = 29 /* consumer waves that have left their argmax candidate in l.bc */, FL_WORDS = 32 };
+       FL_AM = 29 /* consumer waves that have left their argmax candidate in l.bc */,
+       FL_XRD = 30 /* consumer waves 4, 5 have read their residual rows out of l.x (once per launch, behind an in-launch embedding: ln_stats) */, FL_WORDS = 32 };
 
 struct R6Lds { size_t x, q1, q2, u, tl, bc, red, out, dl, misc, fl, ring, fixed; };
 __host__ __device__ inline R6Lds r6_lds(int D, int F) {
@@ -354,7 +357,8 @@ __device__ __forceinline__ float scatter_get(float s) { return __uint_as_float(_
 //                      instead of the shader clock
 //   R6_ONLY_FMT = fmt  one variant (that format, the 7B geometry) instead of the table: the register-budget builds of
 //                      tools/check_ring_regs.sh
-// None of them alters a result.
+// None of them alters a result. (R6_INSTR_TU is no switch: ring_v6_instr.hip sets it to include this file's device half and instantiate the
+// instrumented kernels from it -- see k6_ring_body.)
 #ifndef R6_ROWS_WAIT
 #define R6_ROWS_WAIT 0
 #endif
@@ -362,11 +366,13 @@ __device__ __forceinline__ float scatter_get(float s) { return __uint_as_float(_
 #define R6_RT_STAMPS 0
 #endif
 #if R6_RT_STAMPS
-#define R6STAMP(K) do { if (p.trace && li == p.trace_layer && lane == 0) p.trace[((long long) blockIdx.x * 8 + wave) * 32 + (K)] = (long long) __builtin_amdgcn_s_memrealtime(); } while (0)
+#define R6STAMP(K) do { if constexpr (INS) { if (p->trace && li == p->trace_layer && lane == 0) p->trace[((long long) blockIdx.x * 8 + wave) * 32 + (K)] = (long long) __builtin_amdgcn_s_memrealtime(); } } while (0)
 #else
-#define R6STAMP(K) do { if (p.trace && li == p.trace_layer && lane == 0) p.trace[((long long) blockIdx.x * 8 + wave) * 32 + (K)] = (long long) __builtin_readcyclecounter(); } while (0)
+#define R6STAMP(K) do { if constexpr (INS) { if (p->trace && li == p->trace_layer && lane == 0) p->trace[((long long) blockIdx.x * 8 + wave) * 32 + (K)] = (long long) __builtin_readcyclecounter(); } } while (0)
 #endif
-#define R6RSTAMP(K) do { if (p.trace && li == p.trace_layer && lane == 0) p.trace[((long long) blockIdx.x * 8 + wave) * 32 + (K)] = (long long) __builtin_amdgcn_s_memrealtime(); } while (0)
+#define R6RSTAMP(K) do { if constexpr (INS) { if (p->trace && li == p->trace_layer && lane == 0) p->trace[((long long) blockIdx.x * 8 + wave) * 32 + (K)] = (long long) __builtin_amdgcn_s_memrealtime(); } } while (0)
+// one value into slot K of the traced layer (the instrumented instantiation only; V is not evaluated in the product one)
+#define R6TRACE(K, V) do { if constexpr (INS) { if (p->trace && li == p->trace_layer && lane == 0) p->trace[((long long) blockIdx.x * 8 + wave) * 32 + (K)] = (long long) (V); } } while (0)
 
 // Assembly comments around one record of a row phase (the wait for its LDS reads, rec_acc, the take issued behind it) and around a
 // phase's tail (the row-sum reduction + the epilogue): tools/ring_slots.py counts the instructions between them. A comment emits
@@ -374,7 +380,26 @@ __device__ __forceinline__ float scatter_get(float s) { return __uint_as_float(_
 #define R6REC_MARK(PH, T, EDGE) asm volatile("; R6REC %0 %1 " EDGE :: "n"(PH), "n"(T))
 #define R6TAIL_MARK(PH, EDGE) asm volatile("; R6TAIL %0 0 " EDGE :: "n"(PH))
 
-template <int FMT, int EPT, int NBD, int UF, int KSL>
+// The launch's parameters are read where they are used, not carried: the compiler loads a by-value kernel argument in the entry block, and
+// what is then live across the layer loop -- some sixty scalars against 104 registers -- it can only keep in spill lanes (a v_writelane at
+// entry, a v_readlane, a VALU issue slot, at every use inside the hand-over loops). R6Arg is the kernarg segment itself (the one argument,
+// R6P, at offset 0) behind a pointer the compiler cannot see through: fresh() at a phase boundary ends the life of everything read before
+// it, and the phase reads its own handful through the scalar cache (s_load, one wait). The same trade as the layer table's.
+struct R6Arg {
+    typedef const __attribute__((address_space(4))) R6P * Ptr;
+    Ptr q;
+    __device__ __forceinline__ R6Arg() { fresh(); }
+    __device__ __forceinline__ void fresh() { q = (Ptr) __builtin_amdgcn_kernarg_segment_ptr(); asm volatile("" : "+s"(q)); }
+    __device__ __forceinline__ Ptr operator->() const { return q; }
+};
+
+// r6_pin: a parameter read at the top of a phase is in its register before the phase's records -- the load does not sink into the phase's tail.
+// r6_park: a wave-uniform value that changes once per layer waits in a vector register and comes back with one v_readfirstlane where it is
+// used (Cons::lro, next_block, cpark) -- the allocator would keep it in a spill lane and reload it wherever it likes, the phase tails included.
+template <typename T> __device__ __forceinline__ T r6_pin(T v) { asm volatile("" : "+s"(v)); return v; }
+__device__ __forceinline__ unsigned r6_park(unsigned v) { asm volatile("" : "+v"(v)); return v; }
+
+template <int FMT, int EPT, int NBD, int UF, int KSL, bool INS>
 struct R6 {
     static constexpr int S = 64, NBLK = RG_NBLK, NC = RG_NC, NG = RG_NC + 1;   // NG: waves that gather (consumers + comm)
     static constexpr int D = EPT * 512;
@@ -392,12 +417,11 @@ struct R6 {
         double * red;
         unsigned * fl;
     };
-    static __device__ __forceinline__ RingShape shape(const R6P & p) {
-        RingShape s; s.D = D; s.F = p.F; s.R5 = 5 * p.R; s.DR = p.DR;
-        s.qs = QF<FMT>::QS; s.scb = QF<FMT>::HM ? 4 : 2; s.qhb = QF<FMT>::QH ? 4 : 0;
-        // (s.bal stays 0: this kernel consumes the six-apart deal only. ring_geom.h still describes the balanced one: DESIGN.md Appendix B)
-        return s;
-    }
+    // (No RingShape, no RingCu on the device: what a consumer wave needs of the geometry it reads, phase by phase, from the table the host
+    //  filled with ring_geom.h's functions -- R6P::waves, pre_begin. The six-apart deal only; the balanced one: DESIGN.md Appendix B.)
+    typedef const __attribute__((address_space(4))) RingWave * WavePtr;
+    // (cpark: the consumer index parked in a vector register, see Cons)
+    static __device__ __forceinline__ WavePtr wave_entry(R6Arg p, unsigned cpark) { return (WavePtr) p->waves + rg_wave_index((int) blockIdx.x, __builtin_amdgcn_readfirstlane((int) cpark)); }
 
     // -----------------------------------------------------------------------------------------------------------
     // cooperative gathers: the NG gathering waves each poll a share of the units and stage it into LDS, then meet on a counter
@@ -532,7 +556,7 @@ struct R6 {
     // A wave's wide sweep of a hand-over (after its sentinel turned) until the workgroup's gather is complete: the loader is thinned
     // for exactly that span -- its fills sit in the same memory pipe as the polls (row gather-pass). NOT while a wave merely watches a
     // sentinel: the comm wave reaches most gathers a whole row phase early, and a loader thinned through the row phases streams at half rate.
-    // ... and, as a third level (p.hthin, by default the normal depth), while a wave watches a sentinel: with the records of a phase taken
+    // ... and, as a third level (p->hthin, by default the normal depth), while a wave watches a sentinel: with the records of a phase taken
     // into registers during these waits the loader streams through them, and a poll queues behind whatever the loader has in flight
     static __device__ __forceinline__ void watch_begin(const Lds & l) { fl_add(l.fl + FL_HWB, 1u); }
     static __device__ __forceinline__ void watch_end(const Lds & l) { fl_add(l.fl + FL_HWE, 1u); }
@@ -582,7 +606,9 @@ struct R6 {
     }
     // LayerNorm statistics of the row in l.x: thread pt < 256 owns the partial over elements pt, pt + 256, ...;
     // every wave folds the 256 partials itself (the additions of block_sum_d). Leaves x - mean in l.x. gen = prologues so far.
-    static __device__ __forceinline__ float ln_stats(Poll & pl, const Lds & l, int pt, int lane, unsigned gen) {
+    // rd_wait != 0 (the first LayerNorm behind an in-launch embedding): consumer waves 4, 5 take their residual rows out of l.x and are no part of
+    // the two reduction rounds -- x - mean is written only when rd_wait of them have said (FL_XRD) that they have read.
+    static __device__ __forceinline__ float ln_stats(Poll & pl, const Lds & l, int pt, int lane, unsigned gen, unsigned rd_wait = 0u) {
         constexpr int NP = D / 256;
         float xv[NP];
 #pragma unroll
@@ -595,6 +621,7 @@ struct R6 {
         fl_wait(pl, l.fl + FL_RED1, 4u * gen);
         const double t1 = (l.red[lane] + l.red[lane + 128]) + (l.red[lane + 64] + l.red[lane + 192]);
         const float mean = (float) (wave_sum_d(t1) / (double) D);
+        if (rd_wait) fl_wait(pl, l.fl + FL_XRD, rd_wait);
         double s2 = 0.0;
 #pragma unroll
         for (int j = 0; j < NP; j++) { const float v = xv[j] - mean; l.x[pt + 256 * j] = v; s2 += (double) (v * v); }
@@ -614,8 +641,8 @@ struct R6 {
     }
     // A: LN1 + token shift + maa_x mix + quantise -> l.q1
     // (gen = prologues so far; eg = 1 when an embedding LayerNorm ran in front of them: the reduction counters are one round further)
-    static __device__ __forceinline__ void prologue_A(Poll & pl, const Lds & l, const PA & pa, float * sout_l, bool write_state, int c, int lane, unsigned gen, unsigned eg) {
-        const float scale = c < 4 ? ln_stats(pl, l, c * 64 + lane, lane, gen + eg) : ln_scale(pl, l, lane, gen + eg);
+    static __device__ __forceinline__ void prologue_A(Poll & pl, const Lds & l, const PA & pa, float * sout_l, bool write_state, int c, int lane, unsigned gen, unsigned eg, unsigned rd_wait) {
+        const float scale = c < 4 ? ln_stats(pl, l, c * 64 + lane, lane, gen + eg, rd_wait) : ln_scale(pl, l, lane, gen + eg);
         if (c == 0 && lane == 0) l.misc[0] = scale;
         const QVec lq = qvec_at(l.q1, D);
 #pragma unroll
@@ -703,16 +730,16 @@ struct R6 {
     // embedding row of the token + ln0 -> l.x (rwkv_graph.inc:655-658; the statements of k_embed_ln0 / block_layernorm in kernels.hip: the same
     // 256 partials, the same tree). Consumer waves 0..3, thread pt owns elements pt, pt + 256, ... through all of it: no meeting but the two
     // reduction rounds. The other gathering waves find l.x complete behind the first layer's gather_meet.
-    static __device__ __forceinline__ void embed_ln0(const R6P & p, Poll & pl, const Lds & l, const M6Arena & ar, int pt, int lane) {
+    static __device__ __forceinline__ void embed_ln0(R6Arg p, Poll & pl, const Lds & l, const M6Arena & ar, int pt, int lane) {
         constexpr int NP = D / 256;
-        const unsigned tk = p.tok[0];
-        const long long row = tk < (unsigned) p.n_vocab ? (long long) tk : 0ll;   // (host-side token ids are range-checked by the API; this guards device-side ones)
-        const float * w0 = ar.f(p.ln0_w), * b0 = ar.f(p.ln0_b);
+        const unsigned tk = p->tok[0];
+        const long long row = tk < (unsigned) p->n_vocab ? (long long) tk : 0ll;   // (host-side token ids are range-checked by the API; this guards device-side ones)
+        const float * w0 = ar.f(p->ln0_w), * b0 = ar.f(p->ln0_b);
         float wv[NP], bv[NP];
 #pragma unroll
         for (int j = 0; j < NP; j++) {
             const int e = pt + 256 * j;
-            l.x[e] = p.emb_f16 ? h2f_bits(reinterpret_cast<const uint16_t *>(p.emb)[row * D + e]) : reinterpret_cast<const float *>(p.emb)[row * D + e];
+            l.x[e] = p->emb_f16 ? h2f_bits(reinterpret_cast<const uint16_t *>(p->emb)[row * D + e]) : reinterpret_cast<const float *>(p->emb)[row * D + e];
             wv[j] = w0[e]; bv[j] = b0[e];
         }
         const float scale = ln_stats(pl, l, pt, lane, 1u);
@@ -769,35 +796,40 @@ struct R6 {
     // publishing them to the consumers and looking at their positions in between -- instead of draining the queue.
     // The first `mirror` bytes of the ring are filled twice: once in place, once behind the ring's end (the copy first, so that "the
     // fill has landed" covers it; its source lines stay in L2 for the second read: default policy, everything else is non-temporal).
-    static __device__ __forceinline__ void loader_main(const R6P & p, const Lds & l, int lane) {
+    static __device__ __forceinline__ void loader_main(R6Arg p, const Lds & l, int lane) {
         const int wave = 0;
-        const R6Cu cu = p.cus[blockIdx.x];
+        const R6Cu cu = p->cus[blockIdx.x];
         // fills of this launch (multiple of four): the whole stage's as precomputed, or a layer range's (+ the head's rows behind the last layer)
-        unsigned total_ = p.logits ? cu.chunks_head : cu.chunks;
-        if (p.n_layers != p.layers_total) {
-            const unsigned long long bytes = (unsigned long long) p.n_layers * cu.layer_bytes + (p.logits ? (unsigned long long) rg_head(p.n_vocab, D).bytes : 0ull);
+        unsigned total_ = p->logits ? cu.chunks_head : cu.chunks;
+        if (p->n_layers != p->layers_total) {
+            const unsigned long long bytes = (unsigned long long) p->n_layers * cu.layer_bytes + (p->logits ? (unsigned long long) rg_head(p->n_vocab, D).bytes : 0ull);
             total_ = (unsigned) ((bytes + 4 * RG_CHUNK - 1) / (4 * RG_CHUNK)) * 4u;
         }
         const unsigned total = __builtin_amdgcn_readfirstlane(total_);
-        const unsigned long long src0 = (unsigned long long) p.stream + cu.base + (unsigned long long) p.layer0 * cu.layer_bytes;
-        const unsigned RB = __builtin_amdgcn_readfirstlane(p.ring_bytes), MIR = __builtin_amdgcn_readfirstlane(p.mirror_bytes);
+        const unsigned long long src0 = (unsigned long long) p->stream + cu.base + (unsigned long long) p->layer0 * cu.layer_bytes;
+        const unsigned RB = __builtin_amdgcn_readfirstlane(p->ring_bytes), MIR = __builtin_amdgcn_readfirstlane(p->mirror_bytes);
         const unsigned ring_m0 = __builtin_amdgcn_readfirstlane((unsigned) (size_t) (__attribute__((address_space(3))) unsigned char *) l.ring);
         const unsigned voff = (unsigned) lane * 16u;
-        const int w_norm = __builtin_amdgcn_readfirstlane(p.inflight) & ~3, w_thin = __builtin_amdgcn_readfirstlane(p.thin) & ~3, w_hint = __builtin_amdgcn_readfirstlane(p.hthin) & ~3;
-        Poll pl{p.ctl, false};
+        const int w_norm = __builtin_amdgcn_readfirstlane(p->inflight) & ~3, w_thin = __builtin_amdgcn_readfirstlane(p->thin) & ~3, w_hint = __builtin_amdgcn_readfirstlane(p->hthin) & ~3;
+        Poll pl{p->ctl, false};
         unsigned issued = 0, roff = 0, landed = 0;
         unsigned min_done = 0, thin = 0;
         int level = 0;
-        const unsigned burst = (unsigned) __builtin_amdgcn_readfirstlane(p.burst);
+        const unsigned burst = (unsigned) __builtin_amdgcn_readfirstlane(p->burst);
         const unsigned s_lo = __builtin_amdgcn_readfirstlane((unsigned) src0), s_hi = __builtin_amdgcn_readfirstlane((unsigned) (src0 >> 32));
-        const int li = p.trace_layer;   // (stamps: once per launch)
+        int li = 0;
+        if constexpr (INS) li = p->trace_layer;   // (stamps: once per launch)
         R6STAMP(0);
         unsigned stalls = 0, rounds = 0;
         unsigned long long sb = ((unsigned long long) s_hi << 32) | s_lo;
         unsigned * const fland = l.fl + FL_LANDED;
         // (tracing) workgroups 0 and 131 sample their rounds behind the phase stamps: [2][512][4] after the n_blocks * 8 * 32 stamp slots
-        long long * const lsamp = (p.trace && (blockIdx.x == 0 || blockIdx.x == 131)) ? p.trace + (size_t) gridDim.x * 8 * 32 + (blockIdx.x == 0 ? 0 : 2048) : nullptr;
-        const unsigned samp_lo = (unsigned) p.trace_layer * cu.layer_bytes, samp_hi = samp_lo + cu.layer_bytes;
+        long long * lsamp = nullptr;
+        unsigned samp_lo = 0u, samp_hi = 0u;
+        if constexpr (INS) {
+            lsamp = (p->trace && (blockIdx.x == 0 || blockIdx.x == 131)) ? p->trace + (size_t) gridDim.x * 8 * 32 + (blockIdx.x == 0 ? 0 : 2048) : nullptr;
+            samp_lo = (unsigned) p->trace_layer * cu.layer_bytes; samp_hi = samp_lo + cu.layer_bytes;
+        }
         unsigned nsamp = 0;
         for (unsigned spin = 0; issued < total;) {
             const unsigned lim0 = min_done >= total * 1024u ? total : ((min_done + RB) >> 12) << 2;
@@ -808,8 +840,8 @@ struct R6 {
             const v4u dh = *reinterpret_cast<const v4u *>(l.fl);   // {landed, sweeps begun, sweeps ended, -}
             const uint2 dw = *reinterpret_cast<const uint2 *>(l.fl + FL_HWB);   // {watches begun, ended}
             const int w = thin == 1u ? w_thin : (thin == 2u ? w_hint : w_norm);
-            rounds++;
-            if (lsamp && nsamp < 512u && issued * 1024u + 4096u > samp_lo && landed * 1024u < samp_hi) {   // (tracing: this workgroup's rounds around the traced layer)
+            if constexpr (INS) rounds++;
+            if (INS && lsamp && nsamp < 512u && issued * 1024u + 4096u > samp_lo && landed * 1024u < samp_hi) {   // (tracing: this workgroup's rounds around the traced layer)
                 if (lane == 0) {
                     long long * o = lsamp + (size_t) nsamp * 4;
                     o[0] = (long long) __builtin_amdgcn_s_memrealtime(); o[1] = (long long) issued * 1024 - samp_lo; o[2] = (long long) landed * 1024 - samp_lo;
@@ -830,7 +862,7 @@ struct R6 {
                 issued += 4u * n;
                 if (level > w) { wait_vm(w); level = w; }
             } else {
-                stalls++;
+                if constexpr (INS) stalls++;
                 if (level > 0) { const int x = (level - 1) & ~3; wait_vm(x); level = x; }
                 else if (lds_backoff(pl, spin++)) break;
             }
@@ -849,9 +881,9 @@ struct R6 {
         wait_vm(0);
         fl_st(l.fl + FL_LANDED, total);
         R6STAMP(1);
-        if (p.trace && lane == 0) {
-            p.trace[((long long) blockIdx.x * 8 + wave) * 32 + 2] = (long long) stalls;
-            p.trace[((long long) blockIdx.x * 8 + wave) * 32 + 3] = (long long) rounds;
+        if (INS && p->trace && lane == 0) {
+            p->trace[((long long) blockIdx.x * 8 + wave) * 32 + 2] = (long long) stalls;
+            p->trace[((long long) blockIdx.x * 8 + wave) * 32 + 3] = (long long) rounds;
         }
     }
 
@@ -859,16 +891,17 @@ struct R6 {
     // consumer waves
     // -----------------------------------------------------------------------------------------------------------
     struct Cons {
-        RingCu cu;
         unsigned lbase;        // stream position of the current layer's block
+        unsigned lro;          // ... modulo the ring size (advanced layer by layer: no division)
+                               // (lro and next_block change once per layer and are read once per phase: they wait in a vector register -- r6_park --
+                               //  and come back with one v_readfirstlane where pre_begin uses them, instead of in spill lanes wherever the allocator reloads them)
         unsigned next_block;   // stream position of this wave's first record behind the current layer (next layer, head, or none)
         unsigned RB;
         unsigned ring_lds;     // LDS address of the ring
         unsigned landed;       // chunks known to have landed
         int c, lane;
+        unsigned cpark;        // c for the table lookups, parked like lro
         int dbg;               // RWKV_MI_RING_DBG (bit 5: timing experiment, the records' arithmetic replaced by an xor of what was read)
-        unsigned look;         // takes per look at a hand-over's sentinel (hint_take)
-        unsigned topup;        // where landed records are taken behind a completed gather (take_landed; bits of p.topup)
         long long waited;      // (tracing) cycles spent waiting for the loader
     };
     template <int T, int TE> struct Unroll {
@@ -893,23 +926,26 @@ struct R6 {
         unsigned cnt;          // records this wave owns in this phase
         unsigned pos, ro;      // stream position / ring offset of the next record to take
         unsigned after;        // where this wave's stream continues behind the phase
-        unsigned base;         // stream position of the phase's record 0 (read by nothing since the balanced deal went: DESIGN.md Appendix B)
+        unsigned j0;           // record number of this wave's first record of the phase (its t-th: j0 + NC * t)
+        unsigned base;         // stream position of the phase's record 0 (the instrumented kernel's trace only)
     };
     // record number of this wave's T-th record of phase PH: six apart
-    template <int PH, int T>
-    static __device__ __forceinline__ unsigned ownj(const Cons & cs) { return rg_first_j(cs.cu, PH, cs.c) + (unsigned) (NC * T); }
+    template <int T, typename P>
+    static __device__ __forceinline__ unsigned ownj(const P & pre) { return pre.j0 + (unsigned) (NC * T); }
     template <int R, int U> static constexpr unsigned recb() { return (unsigned) (U * R * 64) * (QF<FMT>::QS + (QF<FMT>::HM ? 4 : 2) + (QF<FMT>::QH ? 4 : 0)); }
     template <int PH, int R, int U, int NP>
-    static __device__ __forceinline__ void pre_begin(const Cons & cs, Pre<PH, R, U, NP> & pre) {
+    static __device__ __forceinline__ void pre_begin(R6Arg p, const Cons & cs, Pre<PH, R, U, NP> & pre) {
         constexpr unsigned RECB = recb<R, U>();
-        const unsigned j0 = rg_first_j(cs.cu, PH, cs.c);
+        const WavePtr wt = wave_entry(p, cs.cpark);
+        const unsigned j0 = wt->ph[PH].j0, cnt = wt->ph[PH].cnt, pos = wt->ph[PH].pos, after = wt->ph[PH].after, ro = wt->ph[PH].ro;   // (one scalar load)
         pre.have = 0;
-        pre.cnt = __builtin_amdgcn_readfirstlane(rg_own_count(cs.cu, PH, cs.c));
-        pre.base = __builtin_amdgcn_readfirstlane(cs.lbase + cs.cu.off[PH]);
-        pre.pos = __builtin_amdgcn_readfirstlane(cs.lbase + cs.cu.off[PH] + j0 * RECB);
-        pre.ro = __builtin_amdgcn_readfirstlane(pre.pos - (pre.pos / cs.RB) * cs.RB);   // (once per phase)
-        const unsigned nxt = rg_next_own_in_layer(cs.cu, cs.c, PH + 1);
-        pre.after = __builtin_amdgcn_readfirstlane(nxt != RG_NONE ? cs.lbase + nxt : cs.next_block);
+        pre.cnt = cnt; pre.j0 = j0;
+        pre.base = 0u;
+        if constexpr (INS) pre.base = cs.lbase + pos - j0 * RECB;
+        pre.pos = cs.lbase + pos;
+        pre.ro = (unsigned) __builtin_amdgcn_readfirstlane(cs.lro) + ro;   // (both below the ring size)
+        pre.ro = pre.ro >= cs.RB ? pre.ro - cs.RB : pre.ro;
+        pre.after = after != RG_NONE ? cs.lbase + after : (unsigned) __builtin_amdgcn_readfirstlane(cs.next_block);
 #pragma unroll
         for (int i = 0; i < NP; i++) rec_reserve<FMT, R, U>(pre.w[i]);
     }
@@ -925,13 +961,14 @@ struct R6 {
             cs.landed = fl_ld(l.fl + FL_LANDED);
             if (cs.landed < need) {
                 if (!block) return false;
-                const long long t0 = (long long) __builtin_readcyclecounter();
+                long long t0 = 0;
+                if constexpr (INS) t0 = (long long) __builtin_readcyclecounter();
                 for (unsigned spin = 0;; spin++) {
                     cs.landed = fl_ld(l.fl + FL_LANDED);
                     if (cs.landed >= need || pl.dead) break;
                     if (lds_backoff(pl, spin)) break;
                 }
-                cs.waited += (long long) __builtin_readcyclecounter() - t0;
+                if constexpr (INS) cs.waited += (long long) __builtin_readcyclecounter() - t0;
             }
         }
         asm volatile("" ::: "memory");
@@ -963,7 +1000,7 @@ struct R6 {
     // has landed. Six takes back to back kept all seven waves of a workgroup away from their sentinels for a microsecond, and the hand-
     // over behind them waited that long (measured: x hand-over + 0.95 us, kq + 1.5 us); a look before EVERY take (1 - 2 us each under
     // the stream) left the ffn key records in the ring through the yq wait -- three output records and one or two key records was all a
-    // wave got to -- and the loader idle for 4 us behind them. `look` takes per look (p.look, RWKV_MI_RING_LOOK); the workgroup's
+    // wave got to -- and the loader idle for 4 us behind them. `look` takes per look (p->look, RWKV_MI_RING_LOOK); the workgroup's
     // "turned" word in LDS is read before every take. Measured on the 7B Q4_0, same box, tokens/s: round-3 kernel 638 - 654, look 1: 639 - 644,
     // 2: 630, 3: 626, 6: 608 -- every record taken sooner costs the hand-overs more than the row phase behind them gains (the stream
     // and the polls share the memory system: DESIGN.md 7.2c). Default 1.
@@ -972,10 +1009,9 @@ struct R6 {
     // 2 - 3 us into every wait -- the records of the NEXT phase sat in it until the next wait; now they leave during this one, and
     // what streams in behind them is two phases ahead.
     template <int PA_, int RA, int UA, int NA, int PB_, int RB_, int UB_, int NB_, int PC_, int RC, int UC, int NC_>
-    static __device__ __forceinline__ void hint_take(Cons & cs, Poll & pl, const Lds & l, xrsrc xr, int unit, unsigned tag, unsigned * go, unsigned gen, int nap,
+    static __device__ __forceinline__ void hint_take(Cons & cs, Poll & pl, const Lds & l, xrsrc xr, int unit, unsigned tag, unsigned * go, unsigned gen, int nap, unsigned look,
                                                      bool on_a, Pre<PA_, RA, UA, NA> & a, bool on_b, Pre<PB_, RB_, UB_, NB_> & b, bool on_c, Pre<PC_, RC, UC, NC_> & c3, bool no_handover = false) {
         bool turned = no_handover;            // (the first layer of a launch: nothing to wait for, nothing taken ahead)
-        const unsigned look = cs.look;
         auto step = [&](auto & pre, auto tc, bool ok) {
             constexpr int t = decltype(tc)::value;
             using P = typename std::remove_reference<decltype(pre)>::type;
@@ -987,7 +1023,7 @@ struct R6 {
                     if (cs.landed < need) cs.landed = fl_ld(l.fl + FL_LANDED);
                     const bool landed = cs.landed >= need;
                     // a landed record is taken at once -- except that every `look`-th take in a row is preceded by a look at the sentinel
-                    if (landed && (spin > 0u || (unsigned) t % look != 0u)) { here = true; break; }
+                    if (landed && (spin > 0u || ((look >> t) & 1u) != 0u)) { here = true; break; }
                     asm volatile("" ::: "memory");
                     if (look_turned(xr, unit, tag)) { fl_st(go, gen); turned = true; break; }
                     if (landed) { here = true; break; }
@@ -997,7 +1033,7 @@ struct R6 {
                 if (here) (void) rec_take<t, P::PH_, P::R_, P::U_, P::NP_>(cs, pl, l, pre, false);
             }
         };
-        if (!(cs.dbg & 64)) {
+        if (!INS || !(cs.dbg & 64)) {
             Unroll<0, NA>::run([&](auto tc) { step(a, tc, on_a); });
             Unroll<0, NB_>::run([&](auto tc) { step(b, tc, on_b && a.have >= a.cnt); });
             Unroll<0, NC_>::run([&](auto tc) { step(c3, tc, on_c && a.have >= a.cnt && b.have >= b.cnt); });
@@ -1005,24 +1041,24 @@ struct R6 {
         if (!turned) gather_hint(pl, xr, unit, tag, go, gen, nap);
     }
     template <int PA_, int RA, int UA, int NA, int PB_, int RB_, int UB_, int NB_>
-    static __device__ __forceinline__ void hint_take(Cons & cs, Poll & pl, const Lds & l, xrsrc xr, int unit, unsigned tag, unsigned * go, unsigned gen, int nap,
+    static __device__ __forceinline__ void hint_take(Cons & cs, Poll & pl, const Lds & l, xrsrc xr, int unit, unsigned tag, unsigned * go, unsigned gen, int nap, unsigned look,
                                                      bool on_a, Pre<PA_, RA, UA, NA> & a, bool on_b, Pre<PB_, RB_, UB_, NB_> & b, bool no_handover = false) {
         Pre<RG_W1, 1, 1, 1> none;
         none.have = 0u; none.cnt = 0u; none.pos = 0u; none.ro = 0u; none.after = 0u;
-        hint_take(cs, pl, l, xr, unit, tag, go, gen, nap, on_a, a, on_b, b, false, none, no_handover);
+        hint_take(cs, pl, l, xr, unit, tag, go, gen, nap, look, on_a, a, on_b, b, false, none, no_handover);
     }
     template <int PH, int R, int U, int NP>
-    static __device__ __forceinline__ void hint_take(Cons & cs, Poll & pl, const Lds & l, xrsrc xr, int unit, unsigned tag, unsigned * go, unsigned gen, int nap, bool on, Pre<PH, R, U, NP> & pre) {
+    static __device__ __forceinline__ void hint_take(Cons & cs, Poll & pl, const Lds & l, xrsrc xr, int unit, unsigned tag, unsigned * go, unsigned gen, int nap, unsigned look, bool on, Pre<PH, R, U, NP> & pre) {
         Pre<RG_W1, 1, 1, 1> none;
         none.have = 0u; none.cnt = 0u; none.pos = 0u; none.ro = 0u; none.after = 0u;
-        hint_take(cs, pl, l, xr, unit, tag, go, gen, nap, on, pre, false, none, false, none);
+        hint_take(cs, pl, l, xr, unit, tag, go, gen, nap, look, on, pre, false, none, false, none);
     }
     // Takes stop when the sentinel turns, and the next ones happen inside rows(): whatever landed in between stays in the ring through the
     // sweep and the prologue behind it (LN + mixes + quantise, 2.4 - 2.7 us in which this workgroup polls nothing), and the loader finds
     // the ring full for that long. take_landed empties it into the buffers that wait for those records: every record of `a`, then of `b`
     // (stream order, as in hint_take), that HAS landed -- no look at a sentinel, no wait, so it adds nothing that could fail to end. The
     // same straight steps as hint_take's, for the same reason; WAIT stays true (a buffer with reads in flight must not cross a join).
-    // Call sites are chosen by the bits of p.topup (RWKV_MI_RING_TOPUP): 1 in front of prologue A, 2 in front of prologue F, 4 in front
+    // Call sites are chosen by the bits of p->topup (RWKV_MI_RING_TOPUP): 1 in front of prologue A, 2 in front of prologue F, 4 in front
     // of the kq hand-over.
     template <int PA_, int RA, int UA, int NA, int PB_, int RB_, int UB_, int NB_>
     static __device__ __forceinline__ void take_landed(Cons & cs, Poll & pl, const Lds & l, Pre<PA_, RA, UA, NA> & a, Pre<PB_, RB_, UB_, NB_> & b) {
@@ -1053,7 +1089,8 @@ struct R6 {
     // The row sums of the phase are reduced together. SUM_GET: wave_sum_scatter (every node of every tree once), epi receives record t's
     // sums wave-uniform (one readlane each). SUM_LANES: the same, and epi(s) is called once with the scattered register -- row r of the
     // wave's t-th record in lanes [(t * R + r) * W, ... + W), W = ScatP<(TF + 1) * R>::W -- and finishes every record in its own lanes.
-    // SUM_N: wave_sum_n, the (TF + 1) * R butterflies (the ffn key rows: see there).
+    // SUM_N: wave_sum_n, the (TF + 1) * R butterflies (the ffn key rows: see there); epi(sums) is called once with all of them, every lane holding every
+    // total -- sums[t * R + r], valid for t < TF or t < pre.cnt.
     enum { SUM_GET = 0, SUM_LANES = 1, SUM_N = 2 };
     template <int PH, int R, int U, int TF, int NP, int SUM = SUM_GET, typename EpiF>
     static __device__ __forceinline__ void rows(Cons & cs, Poll & pl, const Lds & l, const QVec & act, int nbk, Pre<PH, R, U, NP> & pre, EpiF && epi) {
@@ -1071,7 +1108,7 @@ struct R6 {
         for (int i = 0; i < (TF + 1) * R; i++) part[i] = 0.0f;
         auto finish = [&](auto tc, const RawRec<FMT, R, U> & wr) {
             constexpr int t = decltype(tc)::value;
-            if (cs.dbg & 32) {
+            if (INS && (cs.dbg & 32)) {
                 unsigned x = 0;
 #pragma unroll
                 for (int u = 0; u < U; u++)
@@ -1110,7 +1147,10 @@ struct R6 {
         });
         R6TAIL_MARK(PH, "begin");       // (the caller closes the bracket behind its epilogue)
         constexpr int NS = (TF + 1) * R;
-        if constexpr (NS == 1 || SUM == SUM_N) {
+        if constexpr (NS > 1 && SUM == SUM_N) {
+            wave_sum_n<NS>(part);
+            epi(part);
+        } else if constexpr (NS == 1) {
             wave_sum_n<NS>(part);
             Unroll<0, TF + 1>::run([&](auto tc) {
                 constexpr int t = decltype(tc)::value;
@@ -1118,7 +1158,7 @@ struct R6 {
                     float res[R];
 #pragma unroll
                     for (int r = 0; r < R; r++) res[r] = part[t * R + r];
-                    epi(tc, (int) ownj<PH, t>(cs), res);
+                    epi(tc, (int) ownj<t>(pre), res);
                 }
             });
         } else {
@@ -1131,7 +1171,7 @@ struct R6 {
                     // (into a vector register again: as scalars the sums stay live across the hand-overs behind the phase -- rrow, xown -- and
                     //  the scalar registers those spill are reloaded in every wait loop)
                     Unroll<0, R>::run([&](auto rc) { constexpr int r = decltype(rc)::value; float x = scatter_get<NS, t * R + r>(s); asm volatile("" : "+v"(x)); res[r] = x; });
-                    epi(tc, (int) ownj<PH, t>(cs), res);
+                    epi(tc, (int) ownj<t>(pre), res);
                 }
             });
         }
@@ -1155,32 +1195,24 @@ struct R6 {
     static constexpr int rec_regs(int R, int U) { return U * R * (QF<FMT>::QS / 4 + 1 + (QF<FMT>::QH ? 1 : 0)); }
     static constexpr bool G_PRE = rec_regs(1, UF) <= 48;
 
-    static __device__ __forceinline__ void consumer_main(const R6P & p, const Lds & l, int lane, int wave, unsigned base) {
+    static __device__ __forceinline__ void consumer_main(R6Arg p, const Lds & l, int lane, int wave, unsigned base) {
         const int blk = blockIdx.x;
         const int c = wave - 2;                       // consumer index = gather share
         const bool pro = c < 4 || SHI > 0;            // takes part in the prologues' elementwise part
         // (The prologue parameters are loaded by EVERY consumer wave, also where waves 4, 5 take no part: a load under `if (pro)` is a
         //  conditional definition, and the compiler then waits for it and copies it right where it is issued.)
-        const int F = p.F, nbF = F / 32;
-        Poll pl{p.ctl, false};
-        const M6Arena ar{p.arena};
-        const xrsrc xr = make_xrsrc(p.xch, p.xch_bytes);
-        const RingShape sh = shape(p);
+        Poll pl{p->ctl, false};
+        const M6Arena ar{p->arena};
+        const xrsrc xr = make_xrsrc(p->xch, p->xch_bytes);
         Cons cs;
-        cs.cu = rg_cu(sh, blk); cs.lbase = 0; cs.landed = 0; cs.RB = __builtin_amdgcn_readfirstlane(p.ring_bytes); cs.ring_lds = __builtin_amdgcn_readfirstlane((unsigned) (size_t) (__attribute__((address_space(3))) unsigned char *) l.ring); cs.c = c; cs.lane = lane; cs.dbg = __builtin_amdgcn_readfirstlane(p.dbg); cs.look = (unsigned) __builtin_amdgcn_readfirstlane(p.look); cs.topup = (unsigned) __builtin_amdgcn_readfirstlane(p.topup); cs.waited = 0;
+        cs.lbase = 0; cs.lro = 0; cs.landed = 0; cs.RB = __builtin_amdgcn_readfirstlane(p->ring_bytes); cs.ring_lds = __builtin_amdgcn_readfirstlane((unsigned) (size_t) (__attribute__((address_space(3))) unsigned char *) l.ring); cs.c = c; cs.cpark = r6_park((unsigned) c); cs.lane = lane; cs.dbg = 0; if constexpr (INS) cs.dbg = __builtin_amdgcn_readfirstlane(p->dbg); cs.waited = 0;
         const int mat = (blk * (4 * D / NBLK)) / D;   // which of r, k, v, g this workgroup's sets belong to
         const int cbase = (blk * (4 * D / NBLK)) % D;
-        const bool has_dw1 = blk < p.DR;
-
-        // where this wave's stream continues behind a layer: its first record of the next layer, or of the head, or nowhere
-        const unsigned first_own = rg_next_own_in_layer(cs.cu, c, 0);
-        const RingHead hd = rg_head(p.n_vocab, D);
-        const unsigned hbase = (unsigned) p.n_layers * cs.cu.layer_bytes;
-        const unsigned head_first = (p.logits && c < hd.hg) ? hbase + rg_head_off(hd, 0, 0, c) : 0xFFFFFFFFu;
+        const bool has_dw1 = blk < NBD * 32;
         float xown[XT], rrow[XT];
 #pragma unroll
-        for (int t = 0; t < XT; t++) { const int row = c + NC * t; xown[t] = row < RE ? p.x[blk * RE + row] : 0.0f; rrow[t] = 0.0f; }
-        const bool emb_in = p.tok != nullptr;          // the launch starts from the token id (wave-uniform)
+        for (int t = 0; t < XT; t++) { const int row = c + NC * t; xown[t] = row < RE ? p->x[blk * RE + row] : 0.0f; rrow[t] = 0.0f; }
+        const bool emb_in = p->tok != nullptr;          // the launch starts from the token id (wave-uniform)
         const unsigned eg = emb_in ? 1u : 0u;
         if (emb_in && c < 4) embed_ln0(p, pl, l, ar, c * 64 + opq(lane), opq(lane));
         // The prologue parameters (LayerNorm affine, token-shift source, mix weights: 4 / 5 float4 per slot and thread) are loaded when the x
@@ -1188,21 +1220,27 @@ struct R6 {
         // the hand-over waits hold next to nothing but those records.
         PA pa; PF pf;
 
-        for (int li = 0; li < p.n_layers; li++) {
-            const M6Layer & L = p.layers[li];
-            const float * sin_l = p.sin + (long long) li * p.state_stride;
-            float * sout_l = p.sout + (long long) li * p.state_stride;
+        for (int li = 0; li < p->n_layers; li++) {
+            // (the layer's table entry and state rows are addressed anew in each of the two phases that use them: A and F)
             const unsigned tagL = base + (unsigned) li * 8u;
             const unsigned g1 = (unsigned) li + 1u;   // generation of this layer's once-per-layer counters
-            cs.lbase = (unsigned) li * cs.cu.layer_bytes;
-            cs.next_block = li + 1 < p.n_layers ? cs.lbase + cs.cu.layer_bytes + first_own : head_first;
+            p.fresh();
+            {   // where this wave's stream continues behind the layer: its first record of the next layer, or of the head, or nowhere
+                const WavePtr wt = wave_entry(p, cs.cpark);
+                const unsigned lb = wt->layer_bytes, fo = wt->first_own;
+                const unsigned nxt = cs.lbase + lb;              // (cs.lbase / cs.lro: advanced at the bottom of the loop)
+                unsigned nb_;
+                if (li + 1 < p->n_layers) nb_ = nxt + fo;
+                else { const RingHead hd = rg_head(p->n_vocab, D); nb_ = (p->logits && c < hd.hg) ? nxt + rg_head_off(hd, 0, 0, c) : 0xFFFFFFFFu; }
+                cs.next_block = r6_park(nb_);
+            }
             R6STAMP(0);
-            if (p.trace && li == p.trace_layer && lane == 0) p.trace[((long long) blockIdx.x * 8 + wave) * 32 + 23] = cs.waited;
+            R6TRACE(23, cs.waited);
             unsigned havepk = 0u;   // (tracing) records of each row phase already in registers when the phase starts, 4 bits per phase
             Pre<RG_W1, 1, UD, 1> pw;
-            pre_begin<RG_W1>(cs, pw);
+            pre_begin<RG_W1>(p, cs, pw);
             Pre<RG_C, 2, UD, NPC> pc;
-            pre_begin<RG_C>(cs, pc);
+            pre_begin<RG_C>(p, cs, pc);
             // (per-lane offsets are derived from an opaque copy of the lane index in every phase: left alone, the compiler hoists a
             //  hundred loop-invariant address registers of the gathers out of the layer loop and spills them)
             // ---- A: x, LN1 + mix + quantise, W1 rows ----
@@ -1210,41 +1248,48 @@ struct R6 {
                 // (the first layer of a launch has no hand-over in front of it: its x lies in plain memory; same statements, see gather_x)
                 const bool first = li == 0;
                 watch_begin(l);
-                hint_take(cs, pl, l, xr, p.xffn + ((blk * 37 + c * 211) & 1023), tagL - 8u + SLOT_XFFN, l.fl + FL_HX, 2u * li + 1u, p.nap, !first, pw, !first, pc, first);
+                hint_take(cs, pl, l, xr, p->xffn + ((blk * 37 + c * 211) & 1023), tagL - 8u + SLOT_XFFN, l.fl + FL_HX, 2u * li + 1u, p->nap, p->look, !first, pw, !first, pc, first);
                 watch_end(l);
-                issue_pa(pa, ar, L, sin_l, c, opq(lane)); __builtin_amdgcn_sched_barrier(0);
+                issue_pa(pa, ar, p->layers[li], p->sin + (long long) li * p->state_stride, c, opq(lane)); __builtin_amdgcn_sched_barrier(0);
                 sweep_begin(l);
-                gather_x(pl, xr, p.xffn, tagL - 8u + SLOT_XFFN, c, opq(lane), l.x, first ? p.x : nullptr, first && emb_in);
+                gather_x(pl, xr, p->xffn, tagL - 8u + SLOT_XFFN, c, opq(lane), l.x, first ? p->x : nullptr, first && emb_in);
             }
             gather_meet(pl, l.fl + FL_GX, 2u * li + 1u);
             sweep_end(l);
-            if (cs.topup & 1u) take_landed(cs, pl, l, pw, pc);
-            R6STAMP(1);
+            const bool take = li == 0 && emb_in;
             {   // behind an in-launch embedding the residual rows of this wave start from l.x (a select, not a branch: see gather_x)
-                const bool take = li == 0 && emb_in;
+                // Waves 0 - 3 replace x by x - mean in ln_stats once the four of them have met, and waves 4, 5 are no part of that meeting: they
+                // say on FL_XRD that they have read, and ln_stats waits for the two of them before its first write (once per launch). Without it a
+                // late wave 4 or 5 -- late by the takes that stood in front of this read -- found x - mean: behind ln0 a mean of 1e-9, one ulp in one row.
 #pragma unroll
                 for (int t = 0; t < XT; t++) { const int row = c + NC * t; const float v = l.x[blk * RE + (row < RE ? row : 0)]; xown[t] = take ? v : xown[t]; }
+                if (take && c >= 4) fl_add(l.fl + FL_XRD, 1u);   // (LDS operations of a wave execute in order: the reads above are served first)
+                asm volatile("" ::: "memory");
             }
-            if (pro) prologue_A(pl, l, pa, sout_l, blk == 0, c, opq(lane), 2u * li + 1u, eg);
+            if (p->topup & 1u) take_landed(cs, pl, l, pw, pc);
+            R6STAMP(1);
+            if (pro) prologue_A(pl, l, pa, p->sout + (long long) li * p->state_stride, blk == 0, c, opq(lane), 2u * li + 1u, eg, take ? (unsigned) (NC - 4) : 0u);
             prologue_wait(pl, l, 2u * li + 1u);
             R6STAMP(2);
-            havepk |= pw.have;
-            rows<RG_W1, 1, UD, 0, 1>(cs, pl, l, qvec_at(l.q1, D), nb, pw, [&](auto, int j, const float (&res)[1]) {
-                if (lane == 0) tg_store(xr, p.tl + blk + NBLK * j, __float_as_uint(det_tanhf(res[0])), 0u, 0u, 0u, tagL + SLOT_TL);
+            if constexpr (INS) havepk |= pw.have;
+            const int u_tl = r6_pin(p->tl + blk + NBLK * (int) pw.j0), lnw = opq(lane);   // (a wave owns at most one W1 record: j0)
+            rows<RG_W1, 1, UD, 0, 1>(cs, pl, l, qvec_at(l.q1, D), nb, pw, [&](auto, int, const float (&res)[1]) {
+                if (lnw == 0) tg_store(xr, u_tl, __float_as_uint(det_tanhf(res[0])), 0u, 0u, 0u, tagL + SLOT_TL);
             });
             R6TAIL_MARK(RG_W1, "end");
             R6STAMP(3);
             // ---- C: the mixed inputs (this workgroup's matrix reads ONE of the five), decay row, r/k/v/g sets ----
+            p.fresh();
             Pre<RG_E, 1, UD, NPE> pe;
-            pre_begin<RG_E>(cs, pe);
+            pre_begin<RG_E>(p, cs, pe);
             {
                 const int img = (0x4213 >> (4 * mat)) & 0xF;   // r, k, v, g -> mix image (w, k, v, r, g order)
                 watch_begin(l);
-                hint_take(cs, pl, l, xr, p.act5 + img * p.act_stride + ((blk * 7 + c * 19) & 127), tagL + SLOT_ACT, l.fl + FL_HACT, g1, p.nap, true, pc, true, pe);
+                hint_take(cs, pl, l, xr, p->act5 + img * p->act_stride + ((blk * 7 + c * 19) & 127), tagL + SLOT_ACT, l.fl + FL_HACT, g1, p->nap, p->look, true, pc, true, pe);
                 watch_end(l);
                 sweep_begin(l);
-                gather_qvec<DSL>(pl, xr, p.act5 + img * p.act_stride, D, tagL + SLOT_ACT, c, opq(lane), l.act);
-                if (has_dw1) gather_qvec<DSL>(pl, xr, p.act5, D, tagL + SLOT_ACT, c, opq(lane), l.actw);
+                gather_qvec<DSL>(pl, xr, p->act5 + img * p->act_stride, D, tagL + SLOT_ACT, c, opq(lane), l.act);
+                if (has_dw1) gather_qvec<DSL>(pl, xr, p->act5, D, tagL + SLOT_ACT, c, opq(lane), l.actw);
                 gather_meet(pl, l.fl + FL_GACT, g1);
                 sweep_end(l);
             }
@@ -1255,67 +1300,79 @@ struct R6 {
                 constexpr int MAXT = TFC + 1, W = ScatP<2 * MAXT>::W;    // W lanes per row sum: set t in lanes 2 W t (row 0) and 2 W t + W (row 1)
                 static_assert(W >= 4 && W <= 8, "C epilogue: a set's two sums lie in one row of 16 lanes");
                 float v = 0.0f;
-                if (p.trace && li == p.trace_layer && lane == 0) p.trace[((long long) blockIdx.x * 8 + wave) * 32 + 20] = (long long) fl_ld(l.fl + FL_LANDED) * 1024ll - (long long) (cs.lbase + cs.cu.off[RG_C]);
+                R6TRACE(20, (long long) fl_ld(l.fl + FL_LANDED) * 1024ll - (long long) pc.base);
                 R6RSTAMP(26);
-                havepk |= pc.have << 4;
+                if constexpr (INS) havepk |= pc.have << 4;
                 rows<RG_C, 2, UD, TFC, NPC, SUM_LANES>(cs, pl, l, qvec_at(l.act, D), nb, pc, [&](float s) { v = s; });
                 const int ln = opq(lane);
                 if (mat == 3) v = v / (1.0f + det_expf(-v));     // gate: silu
                 const int v1 = __builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x100 + W, 0xF, 0xF, true);   // lane 2 W t collects row 1 (row_shl:W)
                 // record number of the set lane ln finishes: this wave's records are NC apart (ownj)
                 const int t = (int) ((unsigned) ln / (2 * W));
-                const int j = (t < TFC || (unsigned) t < pc.cnt) ? (int) rg_first_j(cs.cu, RG_C, cs.c) + NC * t : 0x7fff;
-                if (ln < 2 * W * MAXT && (ln & (2 * W - 1)) == 0 && j < (int) cs.cu.n[RG_C])
-                    tg_store(xr, p.rkvg + ((mat * D + cbase + 2 * j) >> 1), __float_as_uint(v), (unsigned) v1, 0u, 0u, tagL + SLOT_RKVG);
+                const int j = (t < TFC || (unsigned) t < pc.cnt) ? (int) pc.j0 + NC * t : 0x7fff;
+                if (ln < 2 * W * MAXT && (ln & (2 * W - 1)) == 0 && j < D * 4 / NBLK / 2 /* two-row sets of a workgroup: ring_geom.h, n[RG_C] */)
+                    tg_store(xr, p->rkvg + ((mat * D + cbase + 2 * j) >> 1), __float_as_uint(v), (unsigned) v1, 0u, 0u, tagL + SLOT_RKVG);
                 R6TAIL_MARK(RG_C, "end");
             }
             R6STAMP(5); R6RSTAMP(27);
-            if (p.trace && li == p.trace_layer && lane == 0) p.trace[((long long) blockIdx.x * 8 + wave) * 32 + 24] = cs.waited;
+            R6TRACE(24, cs.waited);
             __builtin_amdgcn_sched_barrier(0);
             // ---- E: output projection + residual ----
+            p.fresh();
             Pre<RG_FK, 2, UD, NPK> pk;
-            pre_begin<RG_FK>(cs, pk);
+            pre_begin<RG_FK>(p, cs, pk);
             Pre<RG_FR, 1, UD, NPR> pr;
-            pre_begin<RG_FR>(cs, pr);
+            pre_begin<RG_FR>(p, cs, pr);
             watch_begin(l);
-            hint_take(cs, pl, l, xr, p.yq + ((blk * 7 + c * 19) & 127), tagL + SLOT_YQ, l.fl + FL_HYQ, g1, p.nap, true, pe, true, pk, true, pr);
+            hint_take(cs, pl, l, xr, p->yq + ((blk * 7 + c * 19) & 127), tagL + SLOT_YQ, l.fl + FL_HYQ, g1, p->nap, p->look, true, pe, true, pk, true, pr);
             watch_end(l);
             sweep_begin(l);
-            gather_qvec<DSL>(pl, xr, p.yq, D, tagL + SLOT_YQ, c, opq(lane), l.yq);
+            gather_qvec<DSL>(pl, xr, p->yq, D, tagL + SLOT_YQ, c, opq(lane), l.yq);
             gather_meet(pl, l.fl + FL_GYQ, g1);
             sweep_end(l);
             R6STAMP(6);
-            havepk |= pe.have << 8;
+            if constexpr (INS) havepk |= pe.have << 8;
             rows<RG_E, 1, UD, RE / NC, NPE>(cs, pl, l, qvec_at(l.yq, D), nb, pe, [&](auto tc, int, const float (&res)[1]) {
                 constexpr int t = decltype(tc)::value;
                 xown[t] = xown[t] + res[0];
             });
             R6TAIL_MARK(RG_E, "end");
-            if (lane == 0) tg_store(xr, p.xatt + blk * NC + c, __float_as_uint(xown[0]), __float_as_uint(xown[XT > 1 ? 1 : 0]), __float_as_uint(xown[XT > 2 ? 2 : 0]), 0u, tagL + SLOT_XATT);
+            if (lane == 0) tg_store(xr, p->xatt + blk * NC + c, __float_as_uint(xown[0]), __float_as_uint(xown[XT > 1 ? 1 : 0]), __float_as_uint(xown[XT > 2 ? 2 : 0]), 0u, tagL + SLOT_XATT);
             R6STAMP(7);
             // ---- F: x, LN2 + mixes + quantise, key sets (-> comm quantises them), receptance rows ----
+            p.fresh();
             watch_begin(l);
-            hint_take(cs, pl, l, xr, p.xatt + ((blk * 37 + c * 211) & 1023), tagL + SLOT_XATT, l.fl + FL_HX, 2u * li + 2u, p.nap, true, pk, true, pr);
+            hint_take(cs, pl, l, xr, p->xatt + ((blk * 37 + c * 211) & 1023), tagL + SLOT_XATT, l.fl + FL_HX, 2u * li + 2u, p->nap, p->look, true, pk, true, pr);
             watch_end(l);
-            issue_pf(pf, ar, L, sin_l, c, opq(lane)); __builtin_amdgcn_sched_barrier(0);
+            issue_pf(pf, ar, p->layers[li], p->sin + (long long) li * p->state_stride, c, opq(lane)); __builtin_amdgcn_sched_barrier(0);
             sweep_begin(l);
-            gather_x(pl, xr, p.xatt, tagL + SLOT_XATT, c, opq(lane), l.x);
+            gather_x(pl, xr, p->xatt, tagL + SLOT_XATT, c, opq(lane), l.x);
             gather_meet(pl, l.fl + FL_GX, 2u * li + 2u);
             sweep_end(l);
-            if (cs.topup & 2u) take_landed(cs, pl, l, pk, pr);
+            if (p->topup & 2u) take_landed(cs, pl, l, pk, pr);
             R6STAMP(8);
-            if (pro) prologue_F(pl, l, pf, sout_l, blk == 0, c, opq(lane), 2u * li + 2u, eg);
+            if (pro) prologue_F(pl, l, pf, p->sout + (long long) li * p->state_stride, blk == 0, c, opq(lane), 2u * li + 2u, eg);
             prologue_wait(pl, l, 2u * li + 2u);
             R6STAMP(9); R6RSTAMP(28);
-            if (p.trace && li == p.trace_layer && lane == 0) p.trace[((long long) blockIdx.x * 8 + wave) * 32 + 21] = (long long) fl_ld(l.fl + FL_LANDED) * 1024ll - (long long) (cs.lbase + cs.cu.off[RG_FK]);
-            havepk |= (pk.have << 12) | (pr.have << 16);
-            // (the butterflies stay here. With these twelve sums through wave_sum_scatter -- either epilogue form -- the 7B Q4_0 kernel came out
-            //  with 5209 instead of 4077 reloads of spilled scalar registers, all over the layer: prologue F 6223 -> 7094 cycles, the loader late
-            //  in the value rows, 598 against 658 tokens/s on one box, although the key rows themselves were 1060 cycles shorter: DESIGN.md 7.3)
-            rows<RG_FK, 2, UD, TFK, NPK, SUM_N>(cs, pl, l, qvec_at(l.q1, D), nb, pk, [&](auto, int j, const float (&res)[2]) {
-                const float v = lane == 1 ? res[1] : res[0];
-                const float t = v > 0.0f ? v : 0.0f;
-                if (lane < 2) l.out[2 * j + lane] = t * t;
+            R6TRACE(21, (long long) fl_ld(l.fl + FL_LANDED) * 1024ll - (long long) pk.base);
+            if constexpr (INS) havepk |= (pk.have << 12) | (pr.have << 16);
+            // (the butterflies are still here, untried on this kernel. When these twelve sums last went through wave_sum_scatter the kernel spilled
+            //  four hundred scalars and the allocator re-dealt them -- 5209 instead of 4077 reloads, 598 against 658 tokens/s although the key rows
+            //  were 1060 cycles shorter. That obstacle is gone (R6Arg, RingWave); the tail is the next thing to try: DESIGN.md 7.3, 9 (a))
+            // (lanes 0 and 1 store row 0 and row 1 of every set: l.out[2 j + lane], j = j0 + NC t -- one address per phase, an immediate offset per record)
+            const int lnk = opq(lane);
+            typedef __attribute__((address_space(3))) float * LdsF;
+            LdsF okp = (LdsF) (l.out + 2 * (int) pk.j0 + lnk);
+            asm volatile("" : "+v"(okp));
+            rows<RG_FK, 2, UD, TFK, NPK, SUM_N>(cs, pl, l, qvec_at(l.q1, D), nb, pk, [&](const float (&sum)[2 * (TFK + 1)]) {
+                if (lnk < 2) Unroll<0, TFK + 1>::run([&](auto tc) {          // (the two storing lanes are masked in once, not once per record)
+                    constexpr int t = decltype(tc)::value;
+                    if (t < TFK || (unsigned) t < pk.cnt) {
+                        const float v = lnk == 1 ? sum[2 * t + 1] : sum[2 * t];
+                        const float r = v > 0.0f ? v : 0.0f;
+                        okp[2 * NC * t] = r * r;
+                    }
+                });
             });
             R6TAIL_MARK(RG_FK, "end");
             fl_add(l.fl + FL_KEYS, 1u);
@@ -1327,38 +1384,49 @@ struct R6 {
                 rrow[t] = res[0];
             });
             R6TAIL_MARK(RG_FR, "end");
+            __builtin_amdgcn_sched_barrier(0);   // (the value phase's cursor arithmetic stays behind the receptance rows' tail)
             R6STAMP(11); R6RSTAMP(29);
             // ---- G: value projection, x += sigmoid(r) * (Wv k) ----
+            p.fresh();
+            const int F = p->F, nbF = F / 32;
             Pre<RG_G, 1, UF, NPG> pg;
-            pre_begin<RG_G>(cs, pg);
+            pre_begin<RG_G>(p, cs, pg);
             // (registers: not the long Q8_0 rows of the 7B geometry)
-            if (G_PRE && (cs.topup & 4u)) take_landed(cs, pl, l, pg);
+            if (G_PRE && (p->topup & 4u)) take_landed(cs, pl, l, pg);
             watch_begin(l);
-            { const unsigned lk = cs.look; cs.look = (unsigned) __builtin_amdgcn_readfirstlane(p.look_g);
-              hint_take(cs, pl, l, xr, p.kq + ((blk * 5 + c * 173) & 511), tagL + SLOT_KQ, l.fl + FL_HKQ, g1, p.nap, G_PRE, pg);
-              cs.look = lk; }
+            hint_take(cs, pl, l, xr, p->kq + ((blk * 5 + c * 173) & 511), tagL + SLOT_KQ, l.fl + FL_HKQ, g1, p->nap, p->look_g, G_PRE, pg);
             watch_end(l);
             sweep_begin(l);
-            gather_qvec<KSL>(pl, xr, p.kq, F, tagL + SLOT_KQ, c, opq(lane), l.kq);
+            gather_qvec<KSL>(pl, xr, p->kq, F, tagL + SLOT_KQ, c, opq(lane), l.kq);
             gather_meet(pl, l.fl + FL_GKQ, g1);
             sweep_end(l);
             R6STAMP(12); R6RSTAMP(30);
-            if (p.trace && li == p.trace_layer && lane == 0) p.trace[((long long) blockIdx.x * 8 + wave) * 32 + 22] = (long long) fl_ld(l.fl + FL_LANDED) * 1024ll - (long long) (cs.lbase + cs.cu.off[RG_G]);
-            havepk |= pg.have << 20;
-            rows<RG_G, 1, UF, RE / NC, NPG>(cs, pl, l, qvec_at(l.kq, F), nbF, pg, [&](auto tc, int j, const float (&res)[1]) {
+            R6TRACE(22, (long long) fl_ld(l.fl + FL_LANDED) * 1024ll - (long long) pg.base);
+            if constexpr (INS) havepk |= pg.have << 20;
+            const bool last = r6_pin(p->n_layers) - 1 == li;
+            float * const xo = r6_pin(p->x_out + blk * RE + (int) pg.j0);   // row of this wave's record 0 (its t-th: NC rows on)
+            const int lng = opq(lane);
+            rows<RG_G, 1, UF, RE / NC, NPG>(cs, pl, l, qvec_at(l.kq, F), nbF, pg, [&](auto tc, int, const float (&res)[1]) {
                 constexpr int t = decltype(tc)::value;
                 const float gte = sigmoid_f(rrow[t]) * res[0];
                 xown[t] = xown[t] + gte;
-                if (li == p.n_layers - 1 && lane == 0) p.x_out[blk * RE + j] = xown[t];
+                if (last && lng == 0) xo[NC * t] = xown[t];
             });
             R6TAIL_MARK(RG_G, "end");
-            if (lane == 0) tg_store(xr, p.xffn + blk * NC + c, __float_as_uint(xown[0]), __float_as_uint(xown[XT > 1 ? 1 : 0]), __float_as_uint(xown[XT > 2 ? 2 : 0]), 0u, tagL + SLOT_XFFN);
+            if (lane == 0) tg_store(xr, p->xffn + blk * NC + c, __float_as_uint(xown[0]), __float_as_uint(xown[XT > 1 ? 1 : 0]), __float_as_uint(xown[XT > 2 ? 2 : 0]), 0u, tagL + SLOT_XFFN);
             R6STAMP(13); R6RSTAMP(14);
-            if (p.trace && li == p.trace_layer && lane == 0) { p.trace[((long long) blockIdx.x * 8 + wave) * 32 + 25] = cs.waited; p.trace[((long long) blockIdx.x * 8 + wave) * 32 + 15] = (long long) havepk; }
+            R6TRACE(25, cs.waited); R6TRACE(15, havepk);
             __builtin_amdgcn_sched_barrier(0);   // (nothing of the next layer moves up into the value rows)
             __builtin_amdgcn_sched_barrier(0);   // (the second marker of the pair that stood around the retired early parameter loads: DESIGN.md Appendix B)
+            {   // the next layer's block
+                const WavePtr wt = wave_entry(p, cs.cpark);
+                cs.lbase += wt->layer_bytes;
+                unsigned lro = (unsigned) __builtin_amdgcn_readfirstlane(cs.lro) + wt->layer_ro;
+                cs.lro = r6_park(lro >= cs.RB ? lro - cs.RB : lro);
+            }
         }
-        if (p.logits) head_phase(p, l, cs, pl, xr, ar, hd, hbase, lane, wave, base, eg);
+        p.fresh();
+        if (p->logits) head_phase(p, l, cs, pl, xr, ar, lane, wave, base, eg);
     }
 
     // -----------------------------------------------------------------------------------------------------------
@@ -1366,24 +1434,26 @@ struct R6 {
     // (rwkv_graph.inc:704-708; ggml's F16 dot: activations rounded to fp16, 32 partial sums k mod 32 accumulated with fma in increasing k,
     // folded 16 / 8 / 4, (p0 + p1) + (p2 + p3) -- the order of k_mvf in kernels.hip: four lanes per row, lane q holds partials 8 q .. 8 q + 7)
     // -----------------------------------------------------------------------------------------------------------
-    static __device__ __forceinline__ void head_phase(const R6P & p, const Lds & l, Cons & cs, Poll & pl, xrsrc xr, const M6Arena & ar, const RingHead & hd,
-                                                      unsigned hbase, int lane, int wave, unsigned base, unsigned eg) {
-        const int blk = blockIdx.x, c = cs.c, li = p.n_layers;       // (li: the layer index the stamps and generations continue with)
+    static __device__ __forceinline__ void head_phase(R6Arg p, const Lds & l, Cons & cs, Poll & pl, xrsrc xr, const M6Arena & ar,
+                                                      int lane, int wave, unsigned base, unsigned eg) {
+        const int blk = blockIdx.x, c = cs.c, li = p->n_layers;       // (li: the layer index the stamps and generations continue with)
+        const RingHead hd = rg_head(p->n_vocab, D);
+        const unsigned hbase = cs.lbase;                              // (behind the last layer's block)
         const unsigned tagL = base + (unsigned) li * 8u;
         const int pt = c * 64 + lane;
         R6STAMP(0); R6RSTAMP(16);
         // x after the last layer
         watch_begin(l);
-        gather_hint(pl, xr, p.xffn + ((blk * 37 + c * 211) & 1023), tagL - 8u + SLOT_XFFN, l.fl + FL_HX, 2u * li + 1u, p.nap);
+        gather_hint(pl, xr, p->xffn + ((blk * 37 + c * 211) & 1023), tagL - 8u + SLOT_XFFN, l.fl + FL_HX, 2u * li + 1u, p->nap);
         watch_end(l);
         sweep_begin(l);
-        gather_x(pl, xr, p.xffn, tagL - 8u + SLOT_XFFN, c, opq(lane), l.x);
+        gather_x(pl, xr, p->xffn, tagL - 8u + SLOT_XFFN, c, opq(lane), l.x);
         gather_meet(pl, l.fl + FL_GX, 2u * li + 1u);
         sweep_end(l);
         R6STAMP(1);
         if (c < 4) {
             const float scale = ln_stats(pl, l, pt, lane, 2u * li + 1u + eg);
-            const float * lw = ar.f(p.lnout_w), * lb = ar.f(p.lnout_b);
+            const float * lw = ar.f(p->lnout_w), * lb = ar.f(p->lnout_b);
 #pragma unroll
             for (int u = 0; u < (D + 1023) / 1024; u++) {
                 const int i = pt * 4 + u * 1024;
@@ -1400,7 +1470,7 @@ struct R6 {
         }
         fl_wait(pl, l.fl + FL_PRO, 4u * (2u * li + 1u));
         R6STAMP(2);
-        if (p.trace && li == p.trace_layer && lane == 0) p.trace[((long long) blockIdx.x * 8 + wave) * 32 + 20] = (long long) fl_ld(l.fl + FL_LANDED) * 1024ll - (long long) hbase;
+        R6TRACE(20, (long long) fl_ld(l.fl + FL_LANDED) * 1024ll - (long long) hbase);
         long long waited = 0;
         // row groups of this wave
         unsigned * const dn = l.fl + FL_DONE + 2 + c;
@@ -1422,13 +1492,13 @@ struct R6 {
             for (int k = 0; k < CHK; k++) {
                 const unsigned need = (pos + RG_HREC + 1023u) >> 10;
                 if (cs.landed < need) {
-                    const long long t0 = p.trace ? (long long) __builtin_readcyclecounter() : 0;
+                    const long long t0 = (INS && p->trace) ? (long long) __builtin_readcyclecounter() : 0;
                     for (unsigned spin = 0;; spin++) {
                         cs.landed = fl_ld(l.fl + FL_LANDED);
                         if (cs.landed >= need || pl.dead) break;
                         if (lds_backoff(pl, spin)) break;
                     }
-                    if (p.trace) waited += (long long) __builtin_readcyclecounter() - t0;
+                    if (INS && p->trace) waited += (long long) __builtin_readcyclecounter() - t0;
                 }
                 asm volatile("" ::: "memory");
                 const int4 * wp = reinterpret_cast<const int4 *>(l.ring + ro) + ln;
@@ -1463,7 +1533,7 @@ struct R6 {
             for (int e = 0; e < 4; e++) ps8[e] += ps8[e + 4];
             const float r = (ps8[0] + ps8[1]) + (ps8[2] + ps8[3]);
             const int vrow = blk * hd.hg * 16 + g * 16 + (ln >> 2);
-            if (q == 0) { p.logits[vrow] = r; if (r > am_best) { am_best = r; am_i = vrow; } }   // (rows come in increasing order per lane: ties keep the smaller index)
+            if (q == 0) { p->logits[vrow] = r; if (r > am_best) { am_best = r; am_i = vrow; } }   // (rows come in increasing order per lane: ties keep the smaller index)
             if (ps < 4) R6STAMP(3 + ps);
         }
         // this wave's candidate -> l.bc[c]; the comm wave merges the six and publishes the workgroup's (tail_argmax)
@@ -1471,25 +1541,25 @@ struct R6 {
         if (ln == 0) { l.bc[2 * c] = am_best; l.bc[2 * c + 1] = __int_as_float(am_i); }
         fl_add(l.fl + FL_AM, 1u);
         R6STAMP(7); R6RSTAMP(17);
-        if (p.trace && li == p.trace_layer && lane == 0) p.trace[((long long) blockIdx.x * 8 + wave) * 32 + 21] = waited;
+        R6TRACE(21, waited);
     }
 
     // -----------------------------------------------------------------------------------------------------------
     // comm wave
     // -----------------------------------------------------------------------------------------------------------
-    static __device__ __forceinline__ void comm_main(const R6P & p, const Lds & l, int lane, unsigned base) {
+    static __device__ __forceinline__ void comm_main(R6Arg p, const Lds & l, int lane, unsigned base) {
         const int wave = 1;
         const int blk = blockIdx.x;
         const int g = NC;                              // gather share
-        const int F = p.F, DR = p.DR, R = p.R, H = p.H;
+        const int F = p->F, DR = NBD * 32, R = p->R, H = D / S;   // (decay rank and head count: fixed by the instantiation, see ring_variant)
         const int nbF = F / 32;
-        Poll pl{p.ctl, false};
-        const M6Arena ar{p.arena};
-        const xrsrc xr = make_xrsrc(p.xch, p.xch_bytes);
+        Poll pl{p->ctl, false};
+        const M6Arena ar{p->arena};
+        const xrsrc xr = make_xrsrc(p->xch, p->xch_bytes);
         const int mat = (blk * (4 * D / NBLK)) / D;
         const bool has_dw1 = blk < DR;
         // the WKV heads run on workgroups hw0 .. hw0 + H - 1
-        const int hw0 = __builtin_amdgcn_readfirstlane(p.head_wg0);
+        const int hw0 = __builtin_amdgcn_readfirstlane(p->head_wg0);
         const bool d_has = blk >= hw0 && blk < hw0 + H;
         const int d_head = blk - hw0;
         const int gpb = (nbF + NBLK - 1) / NBLK;
@@ -1499,10 +1569,10 @@ struct R6 {
         const int b_extra = NCH - NBLK;
         const int b_chunk2 = (b_extra > 0 && blk >= NBLK / 4 && blk < NBLK / 4 + b_extra) ? NBLK + (blk - NBLK / 4) : -1;
 
-        for (int li = 0; li < p.n_layers; li++) {
-            const M6Layer & L = p.layers[li];
-            const float * sin_l = p.sin + (long long) li * p.state_stride;
-            float * sout_l = p.sout + (long long) li * p.state_stride;
+        for (int li = 0; li < p->n_layers; li++) {
+            const M6Layer & L = p->layers[li];
+            const float * sin_l = p->sin + (long long) li * p->state_stride;
+            float * sout_l = p->sout + (long long) li * p->state_stride;
             const unsigned tagL = base + (unsigned) li * 8u;
             const unsigned g1 = (unsigned) li + 1u;
             R6STAMP(0);
@@ -1510,10 +1580,10 @@ struct R6 {
             {
                 const bool first = li == 0;
                 watch_begin(l);
-                if (!first) gather_hint(pl, xr, p.xffn + ((blk * 37 + g * 211) & 1023), tagL - 8u + SLOT_XFFN, l.fl + FL_HX, 2u * li + 1u, p.nap);
+                if (!first) gather_hint(pl, xr, p->xffn + ((blk * 37 + g * 211) & 1023), tagL - 8u + SLOT_XFFN, l.fl + FL_HX, 2u * li + 1u, p->nap);
                 watch_end(l);
                 sweep_begin(l);
-                gather_x(pl, xr, p.xffn, tagL - 8u + SLOT_XFFN, g, opq(lane), l.x, first ? p.x : nullptr, first && p.tok != nullptr);
+                gather_x(pl, xr, p->xffn, tagL - 8u + SLOT_XFFN, g, opq(lane), l.x, first ? p->x : nullptr, first && p->tok != nullptr);
             }
             gather_meet(pl, l.fl + FL_GX, 2u * li + 1u);
             sweep_end(l);
@@ -1528,7 +1598,7 @@ struct R6 {
                 const int ch = q == 0 ? (blk < NCH ? blk : 0) : (b_chunk2 >= 0 ? b_chunk2 : 0);
                 bf[q] = ch / (D / 64);
                 bd[q] = (ch % (D / 64)) * 64 + lnA;
-                const float4 * cbp = reinterpret_cast<const float4 *>(p.w2b + L.w2b + (long long) ch * R * 64);
+                const float4 * cbp = reinterpret_cast<const float4 *>(p->w2b + L.w2b + (long long) ch * R * 64);
 #pragma unroll
                 for (int m4 = 0; m4 < 16; m4++) { const int4 t = ldw16(cbp + (m4 < R / 4 ? m4 : R / 4 - 1) * 64 + lnA); wB4[q][m4] = make_float4(__int_as_float(t.x), __int_as_float(t.y), __int_as_float(t.z), __int_as_float(t.w)); }
                 wBmaa[q] = ar.f(L.maa[bf[q]])[bd[q]];
@@ -1558,8 +1628,8 @@ struct R6 {
                     csx[q] = cpv[q] - cxn[q];
                 }
                 watch_begin(l);
-                if (!(p.dbg & 128)) gather_hint(pl, xr, p.tl + ((blk * 7) & 127), tagL + SLOT_TL, l.fl + FL_HTL, g1, p.nap);   // (one unit first, then the sweep; RWKV_MI_RING_DBG bit 7: the sweep at once -- one wave per workgroup, 5 KB per attempt)
-                poll_units<5, 64>(pl, xr, p.tl, 5 * R, tagL + SLOT_TL, ln, [&](int i, const v4u & v) { l.tl[i] = __uint_as_float(v.x); });
+                if (!INS || !(p->dbg & 128)) gather_hint(pl, xr, p->tl + ((blk * 7) & 127), tagL + SLOT_TL, l.fl + FL_HTL, g1, p->nap);   // (one unit first, then the sweep; RWKV_MI_RING_DBG bit 7: the sweep at once -- one wave per workgroup, 5 KB per attempt)
+                poll_units<5, 64>(pl, xr, p->tl, 5 * R, tagL + SLOT_TL, ln, [&](int i, const v4u & v) { l.tl[i] = __uint_as_float(v.x); });
                 watch_end(l);
                 __builtin_amdgcn_wave_barrier();
                 R6STAMP(3); R6RSTAMP(18);
@@ -1589,7 +1659,7 @@ struct R6 {
                         const float o = mm + cxn[q];
                         int qi, isum; float d16, s16;
                         quant_block32(o, qi, d16, s16, isum);
-                        if (has) tq_store_block(xr, p.act5 + bf[q] * p.act_stride, bd[q] >> 5, ln & 31, qi, d16, s16, isum, tagL + SLOT_ACT);
+                        if (has) tq_store_block(xr, p->act5 + bf[q] * p->act_stride, bd[q] >> 5, ln & 31, qi, d16, s16, isum, tagL + SLOT_ACT);
                     }
                 }
             }
@@ -1598,11 +1668,11 @@ struct R6 {
             {
                 const int img = (0x4213 >> (4 * mat)) & 0xF;
                 watch_begin(l);
-                gather_hint(pl, xr, p.act5 + img * p.act_stride + ((blk * 7 + g * 19) & 127), tagL + SLOT_ACT, l.fl + FL_HACT, g1, p.nap);
+                gather_hint(pl, xr, p->act5 + img * p->act_stride + ((blk * 7 + g * 19) & 127), tagL + SLOT_ACT, l.fl + FL_HACT, g1, p->nap);
                 watch_end(l);
                 sweep_begin(l);
-                gather_qvec<DSL>(pl, xr, p.act5 + img * p.act_stride, D, tagL + SLOT_ACT, g, opq(lane), l.act);
-                if (has_dw1) gather_qvec<DSL>(pl, xr, p.act5, D, tagL + SLOT_ACT, g, opq(lane), l.actw);
+                gather_qvec<DSL>(pl, xr, p->act5 + img * p->act_stride, D, tagL + SLOT_ACT, g, opq(lane), l.act);
+                if (has_dw1) gather_qvec<DSL>(pl, xr, p->act5, D, tagL + SLOT_ACT, g, opq(lane), l.actw);
                 gather_meet(pl, l.fl + FL_GACT, g1);
                 sweep_end(l);
             }
@@ -1615,7 +1685,7 @@ struct R6 {
                 float part[1];
                 rec_acc<FMT, 1, UD>(dwr, arw, nb, ln, part);
                 wave_sum_n<1>(part);
-                if (ln == 0) tg_store(xr, p.dl + blk, __float_as_uint(det_tanhf(part[0])), 0u, 0u, 0u, tagL + SLOT_RKVG);
+                if (ln == 0) tg_store(xr, p->dl + blk, __float_as_uint(det_tanhf(part[0])), 0u, 0u, 0u, tagL + SLOT_RKVG);
             }
             // ---- D: WKV head of this workgroup ----
             if (d_has) {
@@ -1634,7 +1704,7 @@ struct R6 {
                 unsigned dq[6];
                 watch_begin(l);
                 {
-                    const int ptr[2] = {p.dl + ln, p.dl + (NBD > 2 ? 64 + ln : ln)};
+                    const int ptr[2] = {p->dl + ln, p->dl + (NBD > 2 ? 64 + ln : ln)};
                     const bool valid[2] = {true, NBD > 2};
                     v4u dv[2];
                     poll_ptrs<2>(pl, xr, ptr, valid, tagL + SLOT_RKVG, dv);
@@ -1643,8 +1713,8 @@ struct R6 {
                 v4u early[4];
                 {
                     asm volatile("" ::: "memory");
-                    early[0] = tg_load(xr, p.rkvg + (c >> 1)); early[1] = tg_load(xr, p.rkvg + ((D + c) >> 1));
-                    early[2] = tg_load(xr, p.rkvg + ((2 * D + c) >> 1)); early[3] = tg_load(xr, p.rkvg + ((3 * D + c) >> 1));
+                    early[0] = tg_load(xr, p->rkvg + (c >> 1)); early[1] = tg_load(xr, p->rkvg + ((D + c) >> 1));
+                    early[2] = tg_load(xr, p->rkvg + ((2 * D + c) >> 1)); early[3] = tg_load(xr, p->rkvg + ((3 * D + c) >> 1));
                 }
                 // 1. quantise dl (DR = 32 NBD elements) into LDS: half-wave = block
                 const QVec ldl = qvec_at(l.dl, NBD * 32);
@@ -1674,7 +1744,7 @@ struct R6 {
                 const float wdec = det_expf(-det_expf(P[0] + td));
                 // r, k, v, g of channel c: one unit per 2-row set (first read issued above, before the decay was computed)
                 {
-                    const int ptr[4] = {p.rkvg + (c >> 1), p.rkvg + ((D + c) >> 1), p.rkvg + ((2 * D + c) >> 1), p.rkvg + ((3 * D + c) >> 1)};
+                    const int ptr[4] = {p->rkvg + (c >> 1), p->rkvg + ((D + c) >> 1), p->rkvg + ((2 * D + c) >> 1), p->rkvg + ((3 * D + c) >> 1)};
                     const bool valid[4] = {true, true, true, true};
                     v4u dv[4] = {early[0], early[1], early[2], early[3]};
                     bool ok = true;
@@ -1718,15 +1788,15 @@ struct R6 {
                 y *= __uint_as_float(dq[3]);
                 int qi, isum; float d16, s16;
                 quant_block32(y, qi, d16, s16, isum);
-                tq_store_block(xr, p.yq, 2 * d_head + (ln >> 5), ln & 31, qi, d16, s16, isum, tagL + SLOT_YQ);
+                tq_store_block(xr, p->yq, 2 * d_head + (ln >> 5), ln & 31, qi, d16, s16, isum, tagL + SLOT_YQ);
             }
             R6STAMP(6); R6RSTAMP(21);
             // ---- E ----
             watch_begin(l);
-            gather_hint(pl, xr, p.yq + ((blk * 7 + g * 19) & 127), tagL + SLOT_YQ, l.fl + FL_HYQ, g1, p.nap);
+            gather_hint(pl, xr, p->yq + ((blk * 7 + g * 19) & 127), tagL + SLOT_YQ, l.fl + FL_HYQ, g1, p->nap);
             watch_end(l);
             sweep_begin(l);
-            gather_qvec<DSL>(pl, xr, p.yq, D, tagL + SLOT_YQ, g, opq(lane), l.yq);
+            gather_qvec<DSL>(pl, xr, p->yq, D, tagL + SLOT_YQ, g, opq(lane), l.yq);
             gather_meet(pl, l.fl + FL_GYQ, g1);
             sweep_end(l);
             R6STAMP(7); R6RSTAMP(22);
@@ -1753,10 +1823,10 @@ struct R6 {
                 __builtin_amdgcn_sched_barrier(0);
             }
             watch_begin(l);
-            gather_hint(pl, xr, p.xatt + ((blk * 37 + g * 211) & 1023), tagL + SLOT_XATT, l.fl + FL_HX, 2u * li + 2u, p.nap);
+            gather_hint(pl, xr, p->xatt + ((blk * 37 + g * 211) & 1023), tagL + SLOT_XATT, l.fl + FL_HX, 2u * li + 2u, p->nap);
             watch_end(l);
             sweep_begin(l);
-            gather_x(pl, xr, p.xatt, tagL + SLOT_XATT, g, opq(lane), l.x);
+            gather_x(pl, xr, p->xatt, tagL + SLOT_XATT, g, opq(lane), l.x);
             gather_meet(pl, l.fl + FL_GX, 2u * li + 2u);
             sweep_end(l);
             R6STAMP(8); R6RSTAMP(23);
@@ -1781,6 +1851,7 @@ struct R6 {
             {
                 // quantise this workgroup's key groups (relu^2 outputs): half-wave = group
                 const int ln = opq(lane);
+                const int nbF = r6_pin(p->F / 32), gpb = (nbF + NBLK - 1) / NBLK;   // (read here: not carried through the layer into this loop)
                 for (int g2 = 0; g2 < (gpb + 1) / 2; g2++) {
                     const int gi = g2 * 2 + (ln >> 5);
                     const int gg = blk * gpb + gi;
@@ -1788,28 +1859,28 @@ struct R6 {
                     const float v = valid ? l.out[gi * 32 + (ln & 31)] : 0.0f;
                     int qi, isum; float d16, s16;
                     quant_block32(v, qi, d16, s16, isum);
-                    tq_store_block(xr, p.kq, valid ? gg : 0, ln & 31, qi, d16, s16, isum, tagL + SLOT_KQ, valid);
+                    tq_store_block(xr, p->kq, valid ? gg : 0, ln & 31, qi, d16, s16, isum, tagL + SLOT_KQ, valid);
                 }
             }
             R6STAMP(10); R6RSTAMP(24);
             // ---- G ----
             watch_begin(l);
-            gather_hint(pl, xr, p.kq + ((blk * 5 + g * 173) & 511), tagL + SLOT_KQ, l.fl + FL_HKQ, g1, p.nap);
+            gather_hint(pl, xr, p->kq + ((blk * 5 + g * 173) & 511), tagL + SLOT_KQ, l.fl + FL_HKQ, g1, p->nap);
             watch_end(l);
             sweep_begin(l);
-            gather_qvec<KSL>(pl, xr, p.kq, F, tagL + SLOT_KQ, g, opq(lane), l.kq);
+            gather_qvec<KSL>(pl, xr, p->kq, F, tagL + SLOT_KQ, g, opq(lane), l.kq);
             gather_meet(pl, l.fl + FL_GKQ, g1);
             sweep_end(l);
             R6STAMP(11); R6RSTAMP(25);
         }
-        if (p.logits) {   // the head: this wave's share of the last x hand-over (the consumers do the rest)
-            const int li = p.n_layers;
+        if (p->logits) {   // the head: this wave's share of the last x hand-over (the consumers do the rest)
+            const int li = p->n_layers;
             const unsigned tagL = base + (unsigned) li * 8u;
             watch_begin(l);
-            gather_hint(pl, xr, p.xffn + ((blk * 37 + g * 211) & 1023), tagL - 8u + SLOT_XFFN, l.fl + FL_HX, 2u * li + 1u, p.nap);
+            gather_hint(pl, xr, p->xffn + ((blk * 37 + g * 211) & 1023), tagL - 8u + SLOT_XFFN, l.fl + FL_HX, 2u * li + 1u, p->nap);
             watch_end(l);
             sweep_begin(l);
-            gather_x(pl, xr, p.xffn, tagL - 8u + SLOT_XFFN, g, opq(lane), l.x);
+            gather_x(pl, xr, p->xffn, tagL - 8u + SLOT_XFFN, g, opq(lane), l.x);
             gather_meet(pl, l.fl + FL_GX, 2u * li + 1u);
             sweep_end(l);
         }
@@ -1821,20 +1892,20 @@ struct R6 {
     // 256 units and writes the token where the next launch's embedding reads it (and into the greedy loops' history: ctl[2..6]).
     // EVERY launch publishes its units (without logits: an empty candidate), so the stale content of the buffer is always the previous
     // launch's -- a launch 65536 / (8 layers) tokens back would carry the same 16-bit tag.
-    static __device__ __forceinline__ void tail_argmax(const R6P & p, const Lds & l, Poll & pl, xrsrc xr, int lane, unsigned base) {
+    static __device__ __forceinline__ void tail_argmax(R6Arg p, const Lds & l, Poll & pl, xrsrc xr, int lane, unsigned base) {
         const int blk = blockIdx.x;
-        const unsigned tagA = base + (unsigned) (p.n_layers - 1) * 8u + 7u;
+        const unsigned tagA = base + (unsigned) (p->n_layers - 1) * 8u + 7u;
         float b = -INFINITY; int bi = 0x7fffffff;
-        if (p.logits) {
+        if (p->logits) {
             fl_wait(pl, l.fl + FL_AM, (unsigned) NC);
             if (lane < NC) { b = l.bc[2 * lane]; bi = __float_as_int(l.bc[2 * lane + 1]); }
             am_wave(b, bi);
         }
-        if (lane == 0) tg_store(xr, p.am + blk, __float_as_uint(b), (unsigned) bi, 0u, 0u, tagA);
-        if (!p.logits || !p.next_tok || blk != 0) return;
+        if (lane == 0) tg_store(xr, p->am + blk, __float_as_uint(b), (unsigned) bi, 0u, 0u, tagA);
+        if (!p->logits || !p->next_tok || blk != 0) return;
         int ptr[NBLK / 64]; bool valid[NBLK / 64]; v4u dv[NBLK / 64];
 #pragma unroll
-        for (int k = 0; k < NBLK / 64; k++) { ptr[k] = p.am + lane + 64 * k; valid[k] = true; }
+        for (int k = 0; k < NBLK / 64; k++) { ptr[k] = p->am + lane + 64 * k; valid[k] = true; }
         poll_ptrs<NBLK / 64>(pl, xr, ptr, valid, tagA, dv);
         float b3 = -INFINITY; int i3 = 0x7fffffff;
 #pragma unroll
@@ -1843,25 +1914,28 @@ struct R6 {
         if (lane == 0) {
             // (no element compared greater than -inf: every logit is NaN or -inf -- the token feeds the next embedding lookup and must stay a row of the table)
             const unsigned tokn = i3 == 0x7fffffff ? 0u : (unsigned) i3;
-            p.next_tok[0] = tokn;
-            if (p.ctl[2] != 0u) {   // greedy loops: history pointer ctl[4..5], position ctl[3], capacity ctl[6]
-                unsigned * hist = reinterpret_cast<unsigned *>((unsigned long long) p.ctl[4] | ((unsigned long long) p.ctl[5] << 32));
-                const unsigned pos = p.ctl[3];
-                if (pos < p.ctl[6]) hist[pos] = tokn;
-                p.ctl[3] = pos + 1u;
+            p->next_tok[0] = tokn;
+            if (p->ctl[2] != 0u) {   // greedy loops: history pointer ctl[4..5], position ctl[3], capacity ctl[6]
+                unsigned * hist = reinterpret_cast<unsigned *>((unsigned long long) p->ctl[4] | ((unsigned long long) p->ctl[5] << 32));
+                const unsigned pos = p->ctl[3];
+                if (pos < p->ctl[6]) hist[pos] = tokn;
+                p->ctl[3] = pos + 1u;
             }
         }
     }
 };
 
-template <int FMT, int EPT, int NBD, int UF, int KSL>
-__global__ __launch_bounds__(512) void k6_ring(R6P p) {
+// INS = false: the product kernel -- no stamp, no trace store, no RWKV_MI_RING_DBG branch is compiled, and p->trace, p->trace_layer and p->dbg are
+// read nowhere. INS = true: the instrumented one (ring_v6_instr.hip), launched exactly when a trace slot is bound or RWKV_MI_RING_DBG is set.
+template <int FMT, int EPT, int NBD, int UF, int KSL, bool INS>
+__device__ __forceinline__ void k6_ring_body() {
+    R6Arg p;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    typedef R6<FMT, EPT, NBD, UF, KSL> K;
+    typedef R6<FMT, EPT, NBD, UF, KSL, INS> K;
     const int tid0 = threadIdx.x;
     const int lane = tid0 & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid0 >> 6);
-    const R6Lds lo = r6_lds(K::D, p.F);
+    const R6Lds lo = r6_lds(K::D, p->F);
     typename K::Lds l;
     l.x = reinterpret_cast<float *>(smem + lo.x); l.q1 = smem + lo.q1; l.q2 = smem + lo.q2;
     const size_t qd = (qvec_bytes(K::D) + 15) / 16 * 16;
@@ -1871,18 +1945,43 @@ __global__ __launch_bounds__(512) void k6_ring(R6P p) {
     l.fl = reinterpret_cast<unsigned *>(smem + lo.fl); l.ring = smem + lo.ring;
     if (tid0 < FL_WORDS) l.fl[tid0] = (tid0 >= FL_DONE + 2 && tid0 < FL_DONE + 2 + RG_NC) ? 0u : (tid0 >= FL_DONE && tid0 < FL_DONE + 8 ? 0xFFFFFFFFu : 0u);
     __syncthreads();   // the only workgroup barrier of the launch
-    const unsigned base = p.ctl[0];
-    if (p.dbg & 8) {   // timing experiment: the loader alone (every other wave releases the whole ring and leaves)
+    const unsigned base = p->ctl[0];
+    if (INS && (p->dbg & 8)) {   // timing experiment: the loader alone (every other wave releases the whole ring and leaves)
         if (wave == 0) K::loader_main(p, l, lane);
         else fl_st(l.fl + FL_DONE + wave, 0xFFFFFFFFu);
         return;
     }
-    if (p.trace && lane == 0) p.trace[((long long) blockIdx.x * 8 + wave) * 32 + 31] = (long long) __builtin_amdgcn_s_getreg(4 | (0 << 6) | (15 << 11));   // HW_ID[15:0]: wave, SIMD, pipe, CU, SH, SE
+    if (INS && p->trace && lane == 0) p->trace[((long long) blockIdx.x * 8 + wave) * 32 + 31] = (long long) __builtin_amdgcn_s_getreg(4 | (0 << 6) | (15 << 11));   // HW_ID[15:0]: wave, SIMD, pipe, CU, SH, SE
     if (wave == 0) K::loader_main(p, l, lane);
     else if (wave == 1) K::comm_main(p, l, lane, base);
     else K::consumer_main(p, l, lane, wave, base);
-    if (blockIdx.x == 0 && tid0 == 64) p.ctl[0] = base + (unsigned) p.n_layers * 8u;
+    if (blockIdx.x == 0 && tid0 == 64) p->ctl[0] = base + (unsigned) p->n_layers * 8u;
 }
+template <int FMT, int EPT, int NBD, int UF, int KSL>
+__global__ __launch_bounds__(512) void k6_ring(R6P) { k6_ring_body<FMT, EPT, NBD, UF, KSL, false>(); }
+template <int FMT, int EPT, int NBD, int UF, int KSL>
+__global__ __launch_bounds__(512) void k6_ring_ins(R6P) { k6_ring_body<FMT, EPT, NBD, UF, KSL, true>(); }
+
+// The instantiations: this file defines the product kernels, ring_v6_instr.hip (which includes this file up to here) the instrumented ones
+// -- two translation units, so that the two halves compile side by side. Same order in both tables: an index into one is an index into the other.
+typedef void (*RingKernel)(R6P);
+struct RingVariant { int fmt, ept, nbd, uf, ksl; RingKernel fn; };
+#define RING_VARIANTS(KERN, FMT) \
+    {FMT, 8, 4, 7, 3, KERN<FMT, 8, 4, 7, 3>},   /* D 4096, F 14336 (448 blocks: 7 steps, 1344 units), decay rank 128: RWKV-6 7B */ \
+    {FMT, 5, 2, 5, 2, KERN<FMT, 5, 2, 5, 2>},   /* D 2560, F 8960 (280 blocks: 5 steps, 840 units), decay rank 64: RWKV-6 3B */ \
+    {FMT, 4, 2, 4, 2, KERN<FMT, 4, 2, 4, 2>}    /* D 2048, F 7168 (224 blocks: 4 steps, 672 units), decay rank 64: RWKV-6 1.6B */
+#ifdef R6_ONLY_FMT
+#define RING_TABLE(KERN) {R6_ONLY_FMT, 8, 4, 7, 3, KERN<R6_ONLY_FMT, 8, 4, 7, 3>},
+#else
+#define RING_TABLE(KERN) RING_VARIANTS(KERN, T_Q4_0), RING_VARIANTS(KERN, T_Q4_1), RING_VARIANTS(KERN, T_Q5_0), RING_VARIANTS(KERN, T_Q5_1), RING_VARIANTS(KERN, T_Q8_0),
+#endif
+
+#ifdef R6_INSTR_TU
+extern const RingVariant g_ring_variants_ins[];
+const RingVariant g_ring_variants_ins[] = { RING_TABLE(k6_ring_ins) };
+}  // namespace rwkvmi
+#else
+extern const RingVariant g_ring_variants_ins[];   // ring_v6_instr.hip
 
 // ---------------------------------------------------------------------------------------------------------------
 // host side
@@ -1959,6 +2058,7 @@ struct RingShared {
     DevBuf<float> w2b;
     DevBuf<M6Layer> d_layers;
     DevBuf<R6Cu> d_cus;
+    DevBuf<RingWave> d_waves;     // every consumer wave's records, phase by phase (ring_geom.h, rg_wave), for this ring size
     DevBuf<unsigned char> stream;
     int variant = -1, n_blocks = 0, n_layers = 0;
     size_t lds = 0, ring = 0, mirror = 0;
@@ -1986,22 +2086,15 @@ struct RingV6 : PersistentDecoder {
     void forward_range(float * x, float * v_first, const float * sin, float * sout, hipStream_t st, DecodeProf * pf, float * logits, int l0, int l1,
                        const uint32_t * tok, uint32_t * next_tok) override;
     // cycle stamps of one layer (16 per wave), n_blocks * 8 * 32 values (+ the loader's round samples of two workgroups)
-    bool trace(int layer, long long * out, bool fetch) override { return trace_into(proto.trace, proto.trace_layer, layer, (size_t) sh->n_blocks * 8 * 32, 2 * 512 * 4, out, fetch); }
+    // (the slot is bound from the arming call to the fetch: the launches in between are the instrumented kernel's, every other one the product kernel's)
+    bool trace(int layer, long long * out, bool fetch) override {
+        const bool ok = trace_into(proto.trace, proto.trace_layer, layer, (size_t) sh->n_blocks * 8 * 32, 2 * 512 * 4, out, fetch);
+        if (fetch) proto.trace = nullptr;
+        return ok;
+    }
 };
 
-typedef void (*RingKernel)(R6P);
-struct RingVariant { int fmt, ept, nbd, uf, ksl; RingKernel fn; };
-static const RingVariant g_ring_variants[] = {
-#define RING_VARIANTS(FMT) \
-    {FMT, 8, 4, 7, 3, k6_ring<FMT, 8, 4, 7, 3>},   /* D 4096, F 14336 (448 blocks: 7 steps, 1344 units), decay rank 128: RWKV-6 7B */ \
-    {FMT, 5, 2, 5, 2, k6_ring<FMT, 5, 2, 5, 2>},   /* D 2560, F 8960 (280 blocks: 5 steps, 840 units), decay rank 64: RWKV-6 3B */ \
-    {FMT, 4, 2, 4, 2, k6_ring<FMT, 4, 2, 4, 2>}    /* D 2048, F 7168 (224 blocks: 4 steps, 672 units), decay rank 64: RWKV-6 1.6B */
-#ifdef R6_ONLY_FMT
-    {R6_ONLY_FMT, 8, 4, 7, 3, k6_ring<R6_ONLY_FMT, 8, 4, 7, 3>},
-#else
-    RING_VARIANTS(T_Q4_0), RING_VARIANTS(T_Q4_1), RING_VARIANTS(T_Q5_0), RING_VARIANTS(T_Q5_1), RING_VARIANTS(T_Q8_0),
-#endif
-};
+static const RingVariant g_ring_variants[] = { RING_TABLE(k6_ring) };
 
 // the instantiation for a stage v6_stage_shape accepted (-1: none)
 static int ring_variant(const V6Shape & s, int n_cu) {
@@ -2009,7 +2102,7 @@ static int ring_variant(const V6Shape & s, int n_cu) {
     const int fmt = s.fmt;
     const int64_t NB = RG_NBLK;
     const int64_t gpb = (F / 32 + NB - 1) / NB;
-    if (n_cu != NB || s.H > NB || F % 32 != 0 || F % (gpb * 32) != 0 || DR > NB || DR % 32 != 0 || 5 * (D / 64) > NB + NB / 2 || !(R == 32 || R == 64) || gpb * 32 > 64) return -1;
+    if (n_cu != NB || s.H > NB || s.H * 64 != D /* the kernel takes the head count from D */ || F % 32 != 0 || F % (gpb * 32) != 0 || DR > NB || DR % 32 != 0 || 5 * (D / 64) > NB + NB / 2 || !(R == 32 || R == 64) || gpb * 32 > 64) return -1;
     for (size_t v = 0; v < sizeof(g_ring_variants) / sizeof(g_ring_variants[0]); v++) {
         const RingVariant & rv = g_ring_variants[v];
         const int64_t nbF = F / 32;
@@ -2048,6 +2141,7 @@ static RingShared * ring_shared_build(const Model & m) {
     if (ring < 32 * 1024) ring = 32 * 1024;
     rs->lds = lo.fixed + ring + mirror; rs->ring = ring; rs->mirror = mirror;
     if (hipFuncSetAttribute((const void *) g_ring_variants[v].fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) rs->lds) != hipSuccess) return nullptr;
+    if (hipFuncSetAttribute((const void *) g_ring_variants_ins[v].fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) rs->lds) != hipSuccess) return nullptr;
     // the head behind the last layer: F16 head.weight of a stage that owns it, rows divisible into 16-row groups per workgroup
     const bool fold_head = m.has_head && m.head && m.head->type == T_F16 && m.head->cols() == D && m.n_vocab() % (RG_NBLK * 16) == 0 && m.ln_out_w && m.ln_out_b
                            && !(getenv("RWKV_MI_RING_NO_HEAD") && getenv("RWKV_MI_RING_NO_HEAD")[0] == '1');
@@ -2068,11 +2162,19 @@ static RingShared * ring_shared_build(const Model & m) {
         hc[b].chunks_head = (unsigned) ((bytes + hbytes + 4 * RG_CHUNK - 1) / (4 * RG_CHUNK)) * 4u; hc[b].layer_bytes = cu.layer_bytes; hc[b].pad = 0;
         total += (uint64_t) hc[b].chunks_head * RG_CHUNK;
     }
+    // ... and what each consumer wave takes out of them: the kernel reads this where it used to evaluate rg_cu() and its accessors
+    std::vector<RingWave> hw((size_t) RG_NBLK * RG_NC);
+    for (int b = 0; b < RG_NBLK; b++) {
+        const RingCu cu = rg_cu(sh, b);
+        for (int c = 0; c < RG_NC; c++) hw[(size_t) rg_wave_index(b, c)] = rg_wave(cu, c, (uint32_t) ring);
+    }
     const size_t w2_layer = (size_t) 5 * R * D;
     bool ok = R % 4 == 0 && rs->w2b.alloc(w2_layer * n_layers) == hipSuccess
            && rs->stream.alloc(total + 4 * RG_CHUNK) == hipSuccess
            && rs->d_cus.alloc(hc.size()) == hipSuccess
-           && hipMemcpy(rs->d_cus.p, hc.data(), hc.size() * sizeof(R6Cu), hipMemcpyHostToDevice) == hipSuccess;
+           && hipMemcpy(rs->d_cus.p, hc.data(), hc.size() * sizeof(R6Cu), hipMemcpyHostToDevice) == hipSuccess
+           && rs->d_waves.alloc(hw.size()) == hipSuccess
+           && hipMemcpy(rs->d_waves.p, hw.data(), hw.size() * sizeof(RingWave), hipMemcpyHostToDevice) == hipSuccess;
     if (!ok) {
         (void) hipGetLastError();
         fprintf(stderr, "librwkv: no room for the ring kernel's weight streams (%.2f GB): this model continues on the per-layer launches\n", (double) total / 1e9);
@@ -2158,7 +2260,7 @@ PersistentDecoder * ring_v6_create(const Model & m) {
     q.xch = rg->xch.p; q.xch_bytes = (unsigned) (units * 16);
     q.act_stride = (int) act_stride;
     q.ctl = rg->ctl.dev.p;
-    q.stream = rs->stream.p; q.cus = rs->d_cus.p;
+    q.stream = rs->stream.p; q.cus = rs->d_cus.p; q.waves = rs->d_waves.p;
     q.F = (int) F; q.DR = (int) rs->DR; q.R = (int) rs->R; q.H = (int) m.head_count;
     q.ring_bytes = (unsigned) rs->ring; q.mirror_bytes = (unsigned) rs->mirror;
     // on the workgroups of the value matrix: their r/k/v/g phase is the shortest (no decay row, 5.0 us against 5.8 - 6.4 us), and the
@@ -2172,10 +2274,12 @@ PersistentDecoder * ring_v6_create(const Model & m) {
     q.inflight = snap(env_int("RWKV_MI_RING_INFLIGHT", 48));
     q.thin = snap(env_int("RWKV_MI_RING_THIN", 16));
     q.hthin = snap(env_int("RWKV_MI_RING_HTHIN", q.inflight));
-    q.look = env_int("RWKV_MI_RING_LOOK", 1);
-    if (q.look < 1) q.look = 1;
-    q.look_g = env_int("RWKV_MI_RING_LOOKG", q.look);
-    if (q.look_g < 1) q.look_g = 1;
+    int look = env_int("RWKV_MI_RING_LOOK", 1);
+    if (look < 1) look = 1;
+    int look_g = env_int("RWKV_MI_RING_LOOKG", look);
+    if (look_g < 1) look_g = 1;
+    auto look_mask = [](int n) { unsigned m = 0u; for (int t = 0; t < 32; t++) if (t % n != 0) m |= 1u << t; return m; };   // (a wave holds at most six records of a phase)
+    q.look = look_mask(look); q.look_g = look_mask(look_g);
     // take_landed's call sites (1: in front of prologue A, 2: prologue F, 4: the kq hand-over). Same-box A/B, DESIGN.md 7.3, 7B: Q4_0 bits
     // 1 + 2 together +3.5 % (alone +0.3 % and +1.5 %; bit 0 on top -0.8 %), Q5_1 +4.8 % (same with bit 0), Q8_0 bits 0 + 1 +7 % (+3.5 % each;
     // bit 2 does nothing there: no value records ahead). At D = 2048 nothing pays: bit 0 neutral, bit 1 -0.9 %, bit 2 -2.7 % (a layer
@@ -2204,7 +2308,9 @@ void RingV6::forward_range(float * x, float *, const float * sin, float * sout, 
     q.logits = (sh->head && l1 == sh->n_layers) ? logits : nullptr;
     q.next_tok = q.logits ? next_tok : nullptr;
     const uint64_t bytes = sh->bytes * (uint64_t) (l1 - l0) / (uint64_t) sh->n_layers + (q.logits ? sh->bytes_head : 0) + (q.tok ? sh->bytes_embed : 0);
-    launch_profiled(pf, bytes, g_ring_variants[sh->variant].fn, dim3((unsigned) sh->n_blocks), dim3(512), sh->lds, st, q);
+    // the instrumented instantiation exactly when there is something for it to do: a bound trace slot, or a RWKV_MI_RING_DBG experiment
+    const RingKernel fn = (q.trace != nullptr || q.dbg != 0) ? g_ring_variants_ins[sh->variant].fn : g_ring_variants[sh->variant].fn;
+    launch_profiled(pf, bytes, fn, dim3((unsigned) sh->n_blocks), dim3(512), sh->lds, st, q);
 }
 
 // tests/ only (include/rwkv_testhooks_rowsum.h): one wave runs wave_sum_n<N> -- the definition -- and wave_sum_scatter<N> on the same
@@ -2230,3 +2336,4 @@ bool launch_ring_rowsum_test(int n, const float * in, float * out_n, float * out
 int ring_rowsum_lanes(int n) { return n <= 1 ? 64 : (n <= 2 ? 32 : (n <= 4 ? 16 : (n <= 8 ? 8 : 4))); }
 
 }  // namespace rwkvmi
+#endif  // R6_INSTR_TU

@@ -12,3 +12,10 @@ for m in re.finditer(r'\.name:\s+(_Z\S*k6_ring\S*)\n(.*?)\.wavefront_size', t, r
     args=re.search(r'k6_ringILi(\d+)ELi(\d+)', nm)
     print(f"fmt {args.group(1)} ept {args.group(2)}: vgpr {g('vgpr_count')} sgpr {g('sgpr_count')} spill_v {g('vgpr_spill_count')} spill_s {g('sgpr_spill_count')} scratch {g('private_segment_fixed_size')}")
 PY
+# scalar registers kept in spill lanes: saves / reloads by the loop depth of their block, and the code length (tools/ring_slots.py)
+python3 - $OUT "$(dirname "$0")" <<'PY'
+import sys
+sys.path.insert(0, sys.argv[2])
+import ring_slots
+sys.stdout.write(ring_slots.spill_table(ring_slots.spills(open(sys.argv[1]).read())))
+PY

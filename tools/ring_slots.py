@@ -105,6 +105,66 @@ def count(text):
     return out
 
 
+BLOCK = re.compile(r"^\.LBB\d+_\d+:")
+DEPTH = re.compile(r"^\s*;.*\bDepth=(\d+)")
+LANE = re.compile(r"^\s+v_(writelane|readlane)_b32\s+(\w+),\s*(\w+)")
+META = re.compile(r"\.name:\s+(_Z\w*k6_ring\w*)\n(.*?)\.wavefront_size", re.S)
+
+
+def spills(text):
+    """[(format, geometry, {"sgpr_spill": .sgpr_spill_count, "bytes": code length, "reload": {depth: n}, "save": {depth: n}})] in the order the
+    kernels appear. A spill lane is a VGPR that some v_writelane_b32 of the kernel writes; a save is a v_writelane_b32, a reload a v_readlane_b32
+    out of a spill lane (the row sums' own readlanes read other registers). depth = the compiler's `Depth=N` annotation of the block (0: none)."""
+    meta = {m.group(1): m.group(2) for m in META.finditer(text)}
+    out, name, rows = [], None, []
+    for line in text.splitlines():
+        f = FUNC.match(line)
+        if f:
+            name, key, depth, rows, hdr = f.group(1), (FORMATS.get(int(f.group(2)), f.group(2)), GEOMS.get(int(f.group(3)), f.group(3))), 0, [], False
+            continue
+        if name is None:
+            continue
+        if line.startswith(".Lfunc_end"):
+            lanes = {dst for kind, dst, src, d in rows if kind == "writelane"}
+            rec = {"reload": collections.Counter(), "save": collections.Counter()}
+            for kind, dst, src, d in rows:
+                if kind == "writelane": rec["save"][d] += 1
+                elif src in lanes: rec["reload"][d] += 1
+            body = meta.get(name, "")
+            g = re.search(r"\.sgpr_spill_count:\s+(\d+)", body)
+            rec["sgpr_spill"] = int(g.group(1)) if g else None
+            g = re.search(r"; codeLenInByte = (\d+)", text[text.index(name + ":"):])
+            rec["bytes"] = int(g.group(1)) if g else None
+            out.append(key + (rec,))
+            name = None
+            continue
+        if BLOCK.match(line):
+            depth, hdr = 0, True          # (the annotations follow the label; a block without one lies in no loop)
+            d = DEPTH.match(line.split(":", 1)[1]) if ";" in line else None
+            if d: depth = int(d.group(1))
+            continue
+        d = DEPTH.match(line)
+        if d and hdr:
+            depth = max(depth, int(d.group(1)))
+            continue
+        m = LANE.match(line)
+        if m:
+            rows.append((m.group(1), m.group(2), m.group(3), depth))
+        if INSN.match(line):
+            hdr = False
+    return out
+
+
+def spill_table(sp):
+    lines = []
+    for fmt, geom, r in sp:
+        rl, sv = r["reload"], r["save"]
+        deep = lambda c: sum(n for d, n in c.items() if d >= 2)
+        lines.append("%-4s %-4s sgpr_spill_count %4s  code %7s bytes  reloads depth 0 / 1 / >= 2: %4d / %4d / %4d  saves: %4d / %4d / %4d"
+                     % (geom, fmt, r["sgpr_spill"], r["bytes"], rl[0], rl[1], deep(rl), sv[0], sv[1], deep(sv)))
+    return "\n".join(lines) + "\n"
+
+
 def table(counts, which=DEFAULT):
     lines = []
     for inst in sorted(counts):
@@ -143,6 +203,7 @@ def main():
             compile_asm(os.path.join(d, "ring.s"))
             text = open(os.path.join(d, "ring.s")).read()
     sys.stdout.write(table(count(text), which))
+    sys.stdout.write("== scalar registers kept in spill lanes\n" + spill_table(spills(text)))
 
 
 if __name__ == "__main__":

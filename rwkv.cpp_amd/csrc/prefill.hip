@@ -360,6 +360,8 @@ __global__ __launch_bounds__(MF<FMT>::NT, 2) void k_mmq_mfma(MmqArgs A) {
     };
     // The MFMA accumulates onto the bit pattern of 1.5 * 2^23: for |sum| < 2^22 the result, read as a float, IS 12582912 + sum exactly,
     // and one packed subtraction per register pair (exact) replaces two v_cvt_f32_i32. |sum| <= 32 * 128 * 127 < 2^19 for every format.
+    // (The largest sum of every format is reached in tests/test_gpu_block_extremes.py test_products_on_hand_built_blocks, T >= 32: codes -128 /
+    //  all-min / all-max against activation codes of +-127; that they are reached is asserted in tests/test_cpu_block_extremes.py.)
     constexpr int   MAGIC_I = 0x4B400000;
     constexpr float MAGIC_F = 12582912.0f;
     v16i magic;
@@ -375,6 +377,7 @@ __global__ __launch_bounds__(MF<FMT>::NT, 2) void k_mmq_mfma(MmqArgs A) {
             bop[0] = raw[0]; bop[1] = raw[1]; bop[2] = raw[2]; bop[3] = raw[3];
         } else if constexpr (FMT == T_Q4_0) {
             // signed (q - 8) placed in the HIGH nibble: the MFMA returns 16 x the block sum, the token scales carry 1/16
+            // (16 x 32 x 8 x 127 = 520192 < 2^19, and d_x / 16 of an fp16-subnormal d_x is exact in f32: both ends in test_products_on_hand_built_blocks)
 #pragma unroll
             for (int i = 0; i < 4; i++) { const int t = raw[i] << nib_sh; bop[i] = (t & (int) 0xF0F0F0F0) ^ (int) 0x80808080; }
         } else if constexpr (FMT == T_Q4_1) {
@@ -416,7 +419,7 @@ __global__ __launch_bounds__(MF<FMT>::NT, 2) void k_mmq_mfma(MmqArgs A) {
 #pragma unroll
         for (int j = 0; j < 8; j++) {
             sf[j] = (v2f){__int_as_float(acc[2 * j]), __int_as_float(acc[2 * j + 1])} - (v2f){MAGIC_F, MAGIC_F};
-            if constexpr (M::XO) sf[j] = sf[j] - aux[j];            // exact: integers below 2^24
+            if constexpr (M::XO) sf[j] = sf[j] - aux[j];            // exact: integers below 2^24 (|16 sum q_x| <= 65024, |sum| <= 125984: reached in test_products_on_hand_built_blocks, Q5_0)
         }
         const float mw_c = mw_l, dw_c = dw_l;
         // (opaque uses pin the order: the sums leave `acc` before the next MFMA is issued into the same registers, and the fold

@@ -215,7 +215,7 @@ __global__ __launch_bounds__(256, 2) void k_mmq_fast(FastArgs A) {
 #pragma unroll
         for (int i = 0; i < 2; i++) {
             const v2f dw2 = {q.dw[i], q.dw[i]};
-            const float cdw = -MAGIC_F * q.dw[i];                    // exact: an fp16 value times 1.5 * 2^23
+            const float cdw = -MAGIC_F * q.dw[i];                    // exact: an fp16 value times 1.5 * 2^23 (d_w = +-65504, +-2^-24, 0: tests/test_gpu_block_extremes.py test_plain_order_arm_on_hand_built_blocks)
             const v2f cdw2 = {cdw, cdw};
 #pragma unroll
             for (int j = 0; j < 8; j++) {

@@ -371,15 +371,6 @@ RWKV_API bool rwkv_mi_decode_greedy(struct rwkv_context * ctx, uint32_t first_to
     return fetch_outputs(ctx, nullptr, nullptr);   // drains the stream; a poll time-out invalidates the whole run (state included)
 }
 
-static bool ensure_sampler(rwkv_context * ctx) {
-    if (!ctx->d_probs) HIP_CTX_OK(ctx, ctx->d_probs.alloc(sample_scratch_floats(ctx->model->n_vocab())));
-    if (!ctx->d_rng_counter) {
-        HIP_CTX_OK(ctx, ctx->d_rng_counter.alloc(8));   // (64 bytes)
-        HIP_CTX_OK(ctx, hipMemsetAsync(ctx->d_rng_counter.p, 0, 64, ctx->stream));
-    }
-    return true;
-}
-
 // ---- the report of the emitted tokens (rwkv_mi_*set_logprobs / _logprobs_shape / _logprobs_store): what contexts and batches share ----
 
 static bool report_set(rwkv_context * ctx, LogprobReport & lp, bool enabled, uint32_t top_n) {
@@ -500,46 +491,93 @@ static bool check_penalty(rwkv_context * ctx, float presence, float frequency, s
     return true;
 }
 
-// count[tokens[i]] += 1 on the device (arguments checked); drains st
-static bool table_counts_add(rwkv_context * ctx, uint32_t * count, const uint32_t * tokens, size_t n, hipStream_t st) {
+// ---- the draw state of a context's sequence or of a batch's slots (model.h, DrawState) ----
+
+bool DrawState::ensure_counters(rwkv_context * ctx, hipStream_t st) {
+    if (counters) return true;
+    DevBuf<unsigned long long> fresh;
+    const hipError_t e = grow(want(fresh, slots));
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the draw counters of %zu slots: %s", slots, hipGetErrorString(e));
+    HIP_CTX_OK(ctx, hipMemsetAsync(fresh.p, 0, slots * sizeof(unsigned long long), st));
+    counters = std::move(fresh);
+    return true;
+}
+
+bool DrawState::ensure_sampler(rwkv_context * ctx, hipStream_t st) {
+    if (!ensure_counters(ctx, st)) return false;
+    if (probs) return true;
+    const hipError_t e = grow(want(probs, slots * sample_scratch_floats((int64_t) n_vocab)));
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the sampler's scratch for %zu slots: %s", slots, hipGetErrorString(e));
+    return true;
+}
+
+bool DrawState::ensure_penalty(rwkv_context * ctx, hipStream_t st) {
+    if (counts && bias) return true;
+    const size_t words = slots * n_vocab;   // (both tables are 32-bit words)
+    DevBuf<uint32_t> c;
+    DevBuf<float> b;
+    const hipError_t e = grow(want(c, words), want(b, words));
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the penalty tables of %zu slots: %s", slots, hipGetErrorString(e));
+    // (a table that could not be zeroed is not kept)
+    HIP_CTX_OK(ctx, hipMemsetAsync(c.p, 0, words * 4, st));
+    HIP_CTX_OK(ctx, hipMemsetAsync(b.p, 0, words * 4, st));
+    HIP_CTX_OK(ctx, hipStreamSynchronize(st));
+    counts = std::move(c);
+    bias = std::move(b);
+    return true;
+}
+
+bool DrawState::seek(rwkv_context * ctx, size_t slot, unsigned long long value, hipStream_t st) {
+    if (!ensure_counters(ctx, st)) return false;
+    HIP_CTX_OK(ctx, hipMemcpyAsync(counter(slot), &value, sizeof(value), hipMemcpyHostToDevice, st));
+    HIP_CTX_OK(ctx, hipStreamSynchronize(st));
+    return true;
+}
+
+bool DrawState::counts_reset(rwkv_context * ctx, size_t slot, hipStream_t st) {
+    if (!ensure_penalty(ctx, st)) return false;
+    HIP_CTX_OK(ctx, hipMemsetAsync(counts_of(slot), 0, n_vocab * sizeof(uint32_t), st));
+    HIP_CTX_OK(ctx, hipStreamSynchronize(st));
+    return true;
+}
+
+// count[tokens[i]] += 1 on the device
+bool DrawState::counts_add(rwkv_context * ctx, size_t slot, const uint32_t * tokens, size_t n, hipStream_t st) {
+    if (!ensure_penalty(ctx, st)) return false;
     if (n == 0) return true;
     DevBuf<uint32_t> d;
     bool ok = d.upload(tokens, n, st);
-    if (ok) launch_count_add(count, d.p, (int64_t) n, (int) ctx->model->n_vocab(), st);
+    if (ok) launch_count_add(counts_of(slot), d.p, (int64_t) n, (int) n_vocab, st);
     ok = ok && hipGetLastError() == hipSuccess;
     ok = hipStreamSynchronize(st) == hipSuccess && ok;
     RW_CTX_CHECK(ctx, RWKV_ERROR_GRAPH, false, ok, "HIP error: %s", hipGetErrorString(hipGetLastError()));
     return true;
 }
 
-// bias = 0, then bias[ids[i]] = values[i] on the device (arguments checked, n > 0); drains st
-static bool table_bias_set(rwkv_context * ctx, float * bias, const uint32_t * ids, const float * values, size_t n, hipStream_t st) {
-    const int64_t n_vocab = ctx->model->n_vocab();
+bool DrawState::counts_store(rwkv_context * ctx, size_t slot, uint32_t * counts_out, hipStream_t st) {
+    if (!ensure_penalty(ctx, st)) return false;
+    HIP_CTX_OK(ctx, hipMemcpyAsync(counts_out, counts_of(slot), n_vocab * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_CTX_OK(ctx, hipStreamSynchronize(st));
+    return true;
+}
+
+// bias = 0, then bias[ids[i]] = values[i] on the device
+bool DrawState::bias_set(rwkv_context * ctx, size_t slot, const uint32_t * ids, const float * values, size_t n, hipStream_t st) {
+    if (!ensure_penalty(ctx, st)) return false;
+    if (n == 0) { HIP_CTX_OK(ctx, hipStreamSynchronize(st)); has_bias[slot] = 0; return true; }
+    has_bias[slot] = 1;   // (a failure below leaves a table that is cleared or half written: it is not read as "no bias")
+    float * table = bias.p + slot * n_vocab;
     DevBuf<uint32_t> di;
     DevBuf<float> dv;
-    bool ok = di.upload(ids, n, st) && dv.upload(values, n, st) && hipMemsetAsync(bias, 0, (size_t) n_vocab * sizeof(float), st) == hipSuccess;
-    if (ok) launch_bias_scatter(bias, di.p, dv.p, (int64_t) n, (int) n_vocab, st);
+    bool ok = di.upload(ids, n, st) && dv.upload(values, n, st) && hipMemsetAsync(table, 0, n_vocab * sizeof(float), st) == hipSuccess;
+    if (ok) launch_bias_scatter(table, di.p, dv.p, (int64_t) n, (int) n_vocab, st);
     ok = ok && hipGetLastError() == hipSuccess;
     ok = hipStreamSynchronize(st) == hipSuccess && ok;
     RW_CTX_CHECK(ctx, RWKV_ERROR_GRAPH, false, ok, "HIP error: %s", hipGetErrorString(hipGetLastError()));
     return true;
 }
 
-// the context's occurrence and bias tables: on the first call of the family
-static bool ensure_penalty(rwkv_context * ctx) {
-    const size_t V = (size_t) ctx->model->n_vocab();
-    // (both tables are [n_vocab] 32-bit words; a table that could not be zeroed is not kept)
-    auto table = [&](auto & t) {
-        if (t) return true;
-        std::remove_reference_t<decltype(t)> d;
-        const hipError_t e = grow(want(d, V));
-        RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the penalty tables: %s", hipGetErrorString(e));
-        HIP_CTX_OK(ctx, hipMemsetAsync(d.p, 0, V * 4, ctx->stream));
-        t = std::move(d);
-        return true;
-    };
-    return table(ctx->d_counts) && table(ctx->d_bias);
-}
+static bool on_device(rwkv_context * ctx) { HIP_CTX_OK(ctx, hipSetDevice(ctx->model->device)); return true; }
 
 // what every call of the single-context family starts with
 static bool penalty_call(rwkv_context * ctx) {
@@ -550,49 +588,27 @@ static bool penalty_call(rwkv_context * ctx) {
 }
 
 RWKV_API bool rwkv_mi_counts_reset(struct rwkv_context * ctx) {
-    if (!penalty_call(ctx)) return false;
-    HIP_CTX_OK(ctx, hipSetDevice(ctx->model->device));
-    if (!ensure_penalty(ctx)) return false;
-    HIP_CTX_OK(ctx, hipMemsetAsync(ctx->d_counts.p, 0, (size_t) ctx->model->n_vocab() * sizeof(uint32_t), ctx->stream));
-    HIP_CTX_OK(ctx, hipStreamSynchronize(ctx->stream));
-    return true;
+    return penalty_call(ctx) && on_device(ctx) && ctx->draw.counts_reset(ctx, 0, ctx->stream);
 }
 
 RWKV_API bool rwkv_mi_counts_add(struct rwkv_context * ctx, const uint32_t * tokens, size_t n) {
-    if (!penalty_call(ctx) || !check_count_tokens(ctx, tokens, n)) return false;
-    HIP_CTX_OK(ctx, hipSetDevice(ctx->model->device));
-    if (!ensure_penalty(ctx)) return false;
-    return table_counts_add(ctx, ctx->d_counts.p, tokens, n, ctx->stream);
+    return penalty_call(ctx) && check_count_tokens(ctx, tokens, n) && on_device(ctx) && ctx->draw.counts_add(ctx, 0, tokens, n, ctx->stream);
 }
 
 RWKV_API bool rwkv_mi_counts_store(struct rwkv_context * ctx, uint32_t * counts_out) {
     if (!penalty_call(ctx)) return false;
     RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, counts_out != nullptr, "counts_out is NULL");
-    HIP_CTX_OK(ctx, hipSetDevice(ctx->model->device));
-    if (!ensure_penalty(ctx)) return false;
-    HIP_CTX_OK(ctx, hipMemcpyAsync(counts_out, ctx->d_counts.p, (size_t) ctx->model->n_vocab() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_CTX_OK(ctx, hipStreamSynchronize(ctx->stream));
-    return true;
+    return on_device(ctx) && ctx->draw.counts_store(ctx, 0, counts_out, ctx->stream);
 }
 
 RWKV_API bool rwkv_mi_logit_bias_set(struct rwkv_context * ctx, const uint32_t * ids, const float * values, size_t n) {
-    if (!penalty_call(ctx) || !check_bias(ctx, ids, values, n)) return false;
-    HIP_CTX_OK(ctx, hipSetDevice(ctx->model->device));
-    if (!ensure_penalty(ctx)) return false;
-    if (n == 0) { HIP_CTX_OK(ctx, hipStreamSynchronize(ctx->stream)); ctx->has_bias = false; return true; }
-    ctx->has_bias = true;   // (a failure below leaves a table that is cleared or half written: it is not read as "no bias")
-    return table_bias_set(ctx, ctx->d_bias.p, ids, values, n, ctx->stream);
+    return penalty_call(ctx) && check_bias(ctx, ids, values, n) && on_device(ctx) && ctx->draw.bias_set(ctx, 0, ids, values, n, ctx->stream);
 }
 
 RWKV_API bool rwkv_mi_rng_seek(struct rwkv_context * ctx, uint64_t counter) {
     ctx->last_error = RWKV_ERROR_NONE;
     RW_NO_PIPELINE(ctx, false);
-    HIP_CTX_OK(ctx, hipSetDevice(ctx->model->device));
-    if (!ensure_sampler(ctx)) return false;
-    const unsigned long long v = counter;
-    HIP_CTX_OK(ctx, hipMemcpyAsync(ctx->d_rng_counter.p, &v, sizeof(v), hipMemcpyHostToDevice, ctx->stream));
-    HIP_CTX_OK(ctx, hipStreamSynchronize(ctx->stream));
-    return true;
+    return on_device(ctx) && ctx->draw.seek(ctx, 0, counter, ctx->stream);
 }
 
 // the penalty of a single-context draw: the context's counts and bias enter the logits; record: the chosen token is counted
@@ -601,9 +617,10 @@ struct Penalty { float presence, frequency; uint32_t record; };
 // one draw from the context's logits into *out (and hist[hist_pos] when hist is given), on the adjusted logits when pen is given
 static void launch_draw(rwkv_context * ctx, float temperature, float top_p, float u, uint64_t seed, const Penalty * pen, uint32_t * out, uint32_t * hist, int hist_pos) {
     const int n_vocab = (int) ctx->model->n_vocab();
-    if (pen) launch_pen_sample(ctx->d_logits.p, n_vocab, temperature, top_p, u, seed, ctx->d_rng_counter.p, pen->presence, pen->frequency, pen->record, ctx->d_counts.p,
-                               ctx->has_bias ? ctx->d_bias.p : nullptr, ctx->d_probs.p, out, hist, hist_pos, ctx->stream);
-    else launch_sample(ctx->d_logits.p, n_vocab, temperature, top_p, u, seed, ctx->d_rng_counter.p, ctx->d_probs.p, out, hist, hist_pos, ctx->stream);
+    const DrawState & d = ctx->draw;
+    if (pen) launch_pen_sample(ctx->d_logits.p, n_vocab, temperature, top_p, u, seed, d.counter(0), pen->presence, pen->frequency, pen->record, d.counts_of(0),
+                               d.bias_of(0), d.probs.p, out, hist, hist_pos, ctx->stream);
+    else launch_sample(ctx->d_logits.p, n_vocab, temperature, top_p, u, seed, d.counter(0), d.probs.p, out, hist, hist_pos, ctx->stream);
     // the report of the token just written, slot hist_pos of the context's buffers (ensure_report has sized them)
     const LogprobReport & lp = ctx->lp;
     if (lp.enabled) launch_logprob_rows(ctx->d_logits.p, 1, n_vocab, out, (int) lp.top_n, lp.d_chosen.p + hist_pos, lp.d_ids.p + (size_t) hist_pos * lp.top_n,
@@ -613,7 +630,7 @@ static void launch_draw(rwkv_context * ctx, float temperature, float top_p, floa
 // rwkv_mi_sample / rwkv_mi_sample_penalized behind their argument checks
 static bool sample_once(rwkv_context * ctx, float temperature, float top_p, float u, uint64_t seed, const Penalty * pen, uint32_t * token_out) {
     HIP_CTX_OK(ctx, hipSetDevice(ctx->model->device));
-    if (!ensure_sampler(ctx) || (pen && !ensure_penalty(ctx)) || !ensure_report(ctx, 1)) return false;
+    if (!ctx->draw.ensure_sampler(ctx, ctx->stream) || (pen && !ctx->draw.ensure_penalty(ctx, ctx->stream)) || !ensure_report(ctx, 1)) return false;
     ctx->lp.valid = false;
     launch_draw(ctx, temperature, top_p, u, seed, pen, ctx->d_next_token.p, nullptr, 0);
     HIP_CTX_OK(ctx, hipMemcpyAsync(token_out, ctx->d_next_token.p, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -674,8 +691,8 @@ RWKV_API bool rwkv_mi_decode_sample(struct rwkv_context * ctx, uint32_t first_to
     RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, first_token < (size_t) ctx->model->n_vocab() && n_tokens > 0, "bad arguments");
     RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, temperature >= 0.0f && top_p >= 0.0f && top_p <= 1.0f, "bad sampling arguments");
     HIP_CTX_OK(ctx, hipSetDevice(ctx->model->device));
-    if (!upload_tokens(ctx, &first_token, 1) || !ensure_sampler(ctx)) return false;
-    HIP_CTX_OK(ctx, hipMemsetAsync(ctx->d_rng_counter.p, 0, 8, ctx->stream));
+    if (!upload_tokens(ctx, &first_token, 1) || !ctx->draw.ensure_sampler(ctx, ctx->stream)) return false;
+    HIP_CTX_OK(ctx, hipMemsetAsync(ctx->draw.counter(0), 0, 8, ctx->stream));
     return decode_sample_loop(ctx, n_tokens, temperature, top_p, seed, nullptr, tokens_out, elapsed_ms);
 }
 
@@ -687,7 +704,7 @@ RWKV_API bool rwkv_mi_decode_sample_penalized(struct rwkv_context * ctx, uint32_
     RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, temperature >= 0.0f && top_p >= 0.0f && top_p <= 1.0f, "bad sampling arguments");
     if (!check_penalty(ctx, presence, frequency, 0)) return false;
     HIP_CTX_OK(ctx, hipSetDevice(ctx->model->device));
-    if (!ensure_sampler(ctx) || !ensure_penalty(ctx) || !upload_tokens(ctx, &first_token, 1)) return false;
+    if (!ctx->draw.ensure_sampler(ctx, ctx->stream) || !ctx->draw.ensure_penalty(ctx, ctx->stream) || !upload_tokens(ctx, &first_token, 1)) return false;
     const Penalty pen{presence, frequency, 1u};
     return decode_sample_loop(ctx, n_tokens, temperature, top_p, seed, &pen, tokens_out, elapsed_ms);
 }
@@ -936,16 +953,10 @@ struct rwkv_mi_batch {
     std::vector<uint8_t> parity;
     DevBuf<RowState> d_rows;           // [2][n_slots]: the row tables of a call (the greedy loop alternates between the two)
     PinBuf<RowState> h_rows;           // pinned staging of the same
-    DevBuf<unsigned long long> d_counters;       // [n_slots]: one draw counter per slot (sampling calls), zero at creation
-    DevBuf<SampleRow> d_srows;         // [n_slots]: the sampler's row table of a call (parameters + the counter of the row's slot); with its pinned
-    PinBuf<SampleRow> h_srows;         // staging and the sampler's scratch ([n_slots] vectors of probabilities) allocated by the first sampling call
-    DevBuf<float> d_probs;
-    // penalised sampling (rwkv_mi_batch_*_penalized): one occurrence table and one bias table per slot, [n_slots][n_vocab] each, and the penalised
-    // row table of a call with its pinned staging -- allocated by the first call of that family. has_bias[slot]: a bias has been set and not cleared
-    DevBuf<uint32_t> d_counts;
-    DevBuf<float> d_bias;
-    std::vector<uint8_t> has_bias;
-    DevBuf<PenaltyRow> d_prows;
+    DrawState draw;                    // the slots' draw state: counters (zero at creation), sampler scratch, occurrence and bias tables
+    DevBuf<SampleRow> d_srows;         // [n_slots]: the sampler's row table of a call (parameters + the counter of the row's slot) with its pinned
+    PinBuf<SampleRow> h_srows;         // staging, allocated by the first sampling call
+    DevBuf<PenaltyRow> d_prows;        // the penalised row table of a call with its pinned staging, allocated by the first call of that family
     PinBuf<PenaltyRow> h_prows;
     // ragged passes (rwkv_mi_batch_eval_ragged*): the tables of a call -- segments, the short ones again, seg_of[T], last[n] -- in one device
     // buffer with its pinned staging, grown to the largest call so far; the long segments stay on the host (each is a launch of its own)
@@ -984,7 +995,6 @@ static bool batch_fail_through(rwkv_mi_batch * B) { B->ctx->last_error |= B->run
 // means the greedy argmax), or that loop with every row ending by itself (batch_until). Every entry point fills in this description and calls one
 // of the three bodies. The REPORT is a fourth property, the batch's own: a call that emits tokens -- a draw, or a loop's argmax --
 // records them when B->lp.enabled; the bodies branch on that and on `emits`, never on who called.
-enum class Draw { none, sample, penalized };
 struct BatchCall {
     const uint32_t * slots, * tokens;   // row i is slot slots[i] fed tokens[i] ...
     size_t n;
@@ -1011,11 +1021,8 @@ struct BatchCall {
     uint32_t * stopped_by_out = nullptr;
 };
 
-// the slot of step `step` of a call of n rows in the batch's report buffers (step 0: the buffers themselves)
-static RowReport batch_report(const rwkv_mi_batch * B, size_t n, size_t step) {
-    const LogprobReport & lp = B->lp;
-    return RowReport{lp.d_chosen.p + step * n, lp.d_ids.p + step * n * lp.top_n, lp.d_vals.p + step * n * lp.top_n, lp.top_n};
-}
+// the batch's report buffers (batch_ensure_report has sized them for the call)
+static RowReport batch_report(const rwkv_mi_batch * B) { return RowReport{B->lp.d_chosen.p, B->lp.d_ids.p, B->lp.d_vals.p, B->lp.top_n}; }
 
 // the report buffers of an emitting call of `steps` steps (nothing when the report is off); the previous report ends here
 static bool batch_ensure_report(rwkv_mi_batch * B, size_t n, size_t steps) {
@@ -1087,20 +1094,22 @@ static bool batch_check_params(rwkv_mi_batch * B, const rwkv_mi_sample_params * 
     return true;
 }
 
-// scratch and row table of the sampler: on the first sampling call of the batch
-static bool batch_ensure_sampler(rwkv_mi_batch * B) {
+// the row tables of a call's draw with their pinned staging, then the slots' own buffers (B->draw): on the first call of the family. The plain
+// sampler allocates none of the penalty tables
+static bool batch_ensure_draw_tables(rwkv_mi_batch * B, bool penalized) {
     rwkv_context * ctx = B->ctx;
-    if (B->d_probs && B->d_srows && B->h_srows) return true;
-    const hipError_t e = grow(want(B->d_probs, B->n_slots * sample_scratch_floats(ctx->model->n_vocab())), want(B->d_srows, B->n_slots), want(B->h_srows, B->n_slots));
-    RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the sampler's scratch for %zu slots: %s", B->n_slots, hipGetErrorString(e));
-    return true;
+    const size_t n = B->n_slots;
+    const hipError_t e = grow(want(B->d_srows, B->d_srows ? 0 : n), want(B->h_srows, B->h_srows ? 0 : n),
+                              want(B->d_prows, !penalized || B->d_prows ? 0 : n), want(B->h_prows, !penalized || B->h_prows ? 0 : n));
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the sampler's row tables for %zu slots: %s", n, hipGetErrorString(e));
+    return B->draw.ensure_sampler(ctx, B->run->stream) && (!penalized || B->draw.ensure_penalty(ctx, B->run->stream));
 }
 
 // the sampler's row table of the n named slots, one upload per call (after batch_upload*: the stream has been drained, the staging is free).
 // loop: the generator draws
 static bool batch_upload_params(rwkv_mi_batch * B, const BatchCall & c, bool loop) {
     for (size_t i = 0; i < c.n; i++) {
-        B->h_srows.p[i] = SampleRow{c.params[i], B->d_counters.p + c.slots[i]};
+        B->h_srows.p[i] = SampleRow{c.params[i], B->draw.counter(c.slots[i])};
         if (loop) B->h_srows.p[i].p.u = -1.0f;
     }
     BATCH_HIP_OK(B, hipMemcpyAsync(B->d_srows.p, B->h_srows.p, c.n * sizeof(SampleRow), hipMemcpyHostToDevice, B->run->stream));
@@ -1114,39 +1123,21 @@ static bool batch_check_penalties(rwkv_mi_batch * B, const rwkv_mi_penalty_param
     return true;
 }
 
-// the slots' occurrence and bias tables (zeroed), the penalised row table and the sampler's scratch: on the first call of the family
-static bool batch_ensure_penalty(rwkv_mi_batch * B) {
-    rwkv_context * ctx = B->ctx;
-    if (!batch_ensure_sampler(B)) return false;
-    if (B->d_counts && B->d_bias && B->d_prows && B->h_prows) return true;
-    const size_t words = B->n_slots * (size_t) ctx->model->n_vocab();
-    DevBuf<uint32_t> counts;
-    DevBuf<float> bias;
-    hipError_t e = grow(want(counts, words), want(bias, words), want(B->d_prows, B->n_slots), want(B->h_prows, B->n_slots));
-    // (a table that could not be zeroed is not kept)
-    if (e == hipSuccess && (hipMemsetAsync(counts.p, 0, words * 4, B->run->stream) != hipSuccess || hipMemsetAsync(bias.p, 0, words * 4, B->run->stream) != hipSuccess ||
-                            hipStreamSynchronize(B->run->stream) != hipSuccess)) { e = hipErrorOutOfMemory; (void) hipGetLastError(); }
-    if (e == hipSuccess) { B->d_counts = std::move(counts); B->d_bias = std::move(bias); }
-    RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the penalty tables of %zu slots: %s", B->n_slots, hipGetErrorString(e));
-    return true;
-}
-
 // the penalised row table of the n named slots (after batch_upload*: the stream has been drained, the staging is free). loop: the generator
 // draws and every step records
 static bool batch_upload_penalty_rows(rwkv_mi_batch * B, const BatchCall & c, bool loop) {
-    const size_t V = (size_t) B->ctx->model->n_vocab();
+    const DrawState & d = B->draw;
     for (size_t i = 0; i < c.n; i++) {
         const size_t s = c.slots[i];
         const rwkv_mi_penalty_params & pen = c.penalties[i];
-        B->h_prows.p[i] = PenaltyRow{c.params[i], B->d_counters.p + s, pen.presence, pen.frequency, loop ? 1u : pen.record,
-                                   B->d_counts.p + s * V, B->has_bias[s] ? B->d_bias.p + s * V : nullptr};
+        B->h_prows.p[i] = PenaltyRow{c.params[i], d.counter(s), pen.presence, pen.frequency, loop ? 1u : pen.record, d.counts_of(s), d.bias_of(s)};
         if (loop) B->h_prows.p[i].p.u = -1.0f;
     }
     BATCH_HIP_OK(B, hipMemcpyAsync(B->d_prows.p, B->h_prows.p, c.n * sizeof(PenaltyRow), hipMemcpyHostToDevice, B->run->stream));
     return true;
 }
 
-// what the calls on one slot's tables start with
+// what the calls on one slot's draw state start with
 static bool batch_slot_call(rwkv_mi_batch * B, size_t slot) {
     rwkv_context * ctx = B->ctx;
     ctx->last_error = RWKV_ERROR_NONE;
@@ -1281,11 +1272,10 @@ static bool batch_check_args(rwkv_mi_batch * B, const BatchCall & c, bool u_used
     return !c.until || batch_check_stops(B, c);
 }
 
-// the buffers the draw of a call needs: the plain sampler allocates none of the penalty tables
+// the buffers the draw of a call needs
 static bool batch_ensure_draw(rwkv_mi_batch * B, const BatchCall & c) {
     if (c.until && !batch_ensure_stop(B)) return false;
-    if (c.draw == Draw::penalized) return batch_ensure_penalty(B);
-    return c.draw == Draw::none || batch_ensure_sampler(B);
+    return c.draw == Draw::none || batch_ensure_draw_tables(B, c.draw == Draw::penalized);
 }
 
 // the rows or the segments of a call (that drains the stream first), then its stop words and its sampler table. loop: both row tables
@@ -1296,8 +1286,13 @@ static bool batch_upload_call(rwkv_mi_batch * B, const BatchCall & c, size_t T, 
     return c.draw == Draw::none || batch_upload_params(B, c, loop);
 }
 
-static RowSampler batch_sampler(rwkv_mi_batch * B, const BatchCall & c, uint32_t * hist) {
-    return c.draw == Draw::penalized ? RowSampler{nullptr, B->d_probs.p, hist, B->d_prows.p} : RowSampler{B->d_srows.p, B->d_probs.p, hist};
+// what follows the head of the call's passes (model.h, RowSampler): its draw, the call's whole history and, when it reports, report buffers;
+// a loop sets the step
+static RowSampler batch_sampler(rwkv_mi_batch * B, const BatchCall & c, uint32_t * hist, const RowReport * report) {
+    RowSampler s;
+    s.draw = c.draw; s.srows = B->d_srows.p; s.prows = B->d_prows.p; s.probs = B->draw.probs.p;
+    s.hist = hist; s.report = report;
+    return s;
 }
 
 // a pass that could not be launched: the stream is drained before the call returns (what it had enqueued reads the staging)
@@ -1326,9 +1321,8 @@ static bool batch_pass(rwkv_mi_batch * B, const BatchCall & c) {
         BATCH_HIP_OK(B, hipMemcpyAsync(run->d_score_targets.p, run->h_score_targets.p, T * sizeof(uint32_t), hipMemcpyHostToDevice, run->stream));
     }
     // Row i's token lands in the batch's token word i (a ragged pass has read all T of them by then): the 4 n bytes that go back to the host.
-    RowSampler sampler = batch_sampler(B, c, nullptr);
-    const RowReport rep = report ? batch_report(B, c.n, 0) : RowReport{};
-    if (report) sampler.report = &rep;
+    const RowReport rep = batch_report(B);
+    const RowSampler sampler = batch_sampler(B, c, nullptr, report ? &rep : nullptr);
     // scoring is the ragged pass with the head on every token (engine.hip, ScorePass): T rows of log-probs / argmax in token order
     ScorePass sp;
     sp.targets = sp.logprobs = c.logprobs_out != nullptr;
@@ -1370,17 +1364,15 @@ static bool batch_loop(rwkv_mi_batch * B, const BatchCall & c, size_t n_tokens, 
     if (!batch_upload_call(B, c, T, true)) return false;
     if (c.draw == Draw::sample) launch_sample_seek_rows(B->d_srows.p, (int64_t) n, 0ull, run->stream);   // the named slots' streams start over
     BATCH_HIP_OK(B, hipEventRecord(run->ev0, run->stream));
+    const RowReport rep = batch_report(B);
+    RowSampler sampler = batch_sampler(B, c, hist.p, report ? &rep : nullptr);
     for (size_t i = 0; i < n_tokens; i++) {
         // step i reads the buffers step i - 1 wrote: the two row tables alternate; the token of each row -- sampled inside the pass's chain
         // bracket, or its argmax after it -- lands where its next embedding lookup reads it
-        RowSampler sampler = batch_sampler(B, c, hist.p + i * n);
-        const RowReport rep = report ? batch_report(B, n, i) : RowReport{};
-        if (report) sampler.report = &rep;
+        sampler.step = (uint32_t) i;
         if (!forward_rows(run, B->d_rows.p + (i & 1) * B->n_slots, (int64_t) n, true, drawn ? &sampler : nullptr)) return batch_fail_drained(B);
-        if (drawn) continue;
         // the greedy argmax, and its report directly behind it: the event the device's next persistent launch waits on is recorded after both
-        launch_argmax(run->d_logits.p, (int64_t) n, ctx->model->n_vocab(), run->d_tokens.p, hist.p + i * n, run->stream);
-        if (report) launch_logprob_rows(run->d_logits.p, (int64_t) n, (int) ctx->model->n_vocab(), run->d_tokens.p, (int) rep.top_n, rep.chosen, rep.ids, rep.vals, nullptr, run->stream);
+        if (!drawn) launch_row_sampler(run, sampler, (int64_t) n);
     }
     BATCH_HIP_OK(B, hipEventRecord(run->ev1, run->stream));
     std::vector<uint32_t> h(tokens_out ? n_tokens * n : 0);
@@ -1427,21 +1419,20 @@ static bool batch_until(rwkv_mi_batch * B, const BatchCall & c, uint32_t * token
     RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, false, he == hipSuccess, "cannot allocate the history of %zu steps of %zu rows: %s", budget, n, hipGetErrorString(he));
     const bool report = B->lp.enabled;   // (every step of a live row emits; a slot no row wrote is never read back: report_store fills behind lens)
     if (!batch_ensure_report(B, n, budget)) return false;
-    const RowReport rep = report ? batch_report(B, n, 0) : RowReport{};
     if (!batch_upload_call(B, c, T, true)) return false;
     if (c.draw == Draw::sample) launch_sample_seek_rows(B->d_srows.p, (int64_t) n, 0ull, run->stream);   // the named slots' streams start over
     BATCH_HIP_OK(B, hipMemsetAsync(hist.p, 0xFF, budget * n * sizeof(uint32_t), run->stream));
     BATCH_HIP_OK(B, hipEventRecord(run->ev0, run->stream));
+    const RowReport rep = batch_report(B);
+    RowSampler sampler = batch_sampler(B, c, hist.p, report ? &rep : nullptr);
+    RowStop stop{B->stop, nullptr, nullptr};
+    sampler.stop = &stop;
     size_t passes = 0;
     for (size_t b = 0; passes < budget; b++) {
         for (const size_t end = std::min(budget, passes + K); passes < end; passes++) {
-            RowState * used = B->d_rows.p + (passes & 1) * B->n_slots, * other = B->d_rows.p + ((passes & 1) ^ 1) * B->n_slots;
-            const RowStop stop{B->stop, (uint32_t) passes, used, other};
-            RowSampler sampler = batch_sampler(B, c, hist.p);
-            if (c.draw == Draw::none) sampler.table = nullptr;   // (no draw: the greedy argmax)
-            sampler.stop = &stop;
-            if (report) sampler.report = &rep;
-            if (!forward_rows(run, used, (int64_t) n, true, &sampler)) return batch_fail_drained(B);
+            stop.used = B->d_rows.p + (passes & 1) * B->n_slots; stop.other = B->d_rows.p + ((passes & 1) ^ 1) * B->n_slots;
+            sampler.step = (uint32_t) passes;
+            if (!forward_rows(run, stop.used, (int64_t) n, true, &sampler)) return batch_fail_drained(B);
         }
         hipError_t e = hipMemcpyAsync(B->h_live_count.p + (b & 1), B->stop.live_count, sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream);
         if (e == hipSuccess) e = hipEventRecord(B->ev_block[b & 1], run->stream);
@@ -1573,9 +1564,9 @@ static bool batch_beam(rwkv_mi_batch * B, const BeamCall & c, uint32_t * tokens_
     for (size_t b = 0; passes < n_tokens; b++) {
         for (const size_t end = std::min(n_tokens, passes + K); passes < end; passes++) {
             RowState * used = B->d_rows.p + (passes & 1) * B->n_slots, * other = B->d_rows.p + ((passes & 1) ^ 1) * B->n_slots;
-            const RowBeam beam{t, (uint32_t) passes, used, other};
-            RowSampler sampler{nullptr, nullptr, nullptr};
-            sampler.beam = &beam;
+            const RowBeam beam{t, used, other};
+            RowSampler sampler;
+            sampler.beam = &beam; sampler.step = (uint32_t) passes;
             if (!forward_rows(run, used, (int64_t) n, true, &sampler)) return batch_fail_drained(B);
         }
         hipError_t e = hipMemcpyAsync(B->h_live_count.p + (b & 1), t.live_count, sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream);
@@ -1658,7 +1649,7 @@ RWKV_API struct rwkv_mi_batch * rwkv_mi_batch_create(struct rwkv_context * ctx, 
     B->n_slots = n_slots;
     B->state_len = m.state_len();
     B->parity.assign(n_slots, 0);
-    B->has_bias.assign(n_slots, 0);
+    B->draw.init(n_slots, (size_t) m.n_vocab());
     RW_CTX_CHECK(ctx, RWKV_ERROR_GRAPH, nullptr, hipSetDevice(m.device) == hipSuccess, "hipSetDevice failed");
     B->run = batch_context_create(&m, (int64_t) n_slots);
     RW_CTX_CHECK(ctx, RWKV_ERROR_CTX | RWKV_ERROR_ALLOC, nullptr, B->run != nullptr, "cannot create the batch's stream / buffers (device memory?)");
@@ -1670,10 +1661,7 @@ RWKV_API struct rwkv_mi_batch * rwkv_mi_batch_create(struct rwkv_context * ctx, 
     RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, nullptr, e == hipSuccess, "HIP error: %s", hipGetErrorString(e));
     e = B->h_rows.alloc(2 * n_slots);
     RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, nullptr, e == hipSuccess, "HIP error: %s", hipGetErrorString(e));
-    e = B->d_counters.alloc(n_slots);
-    RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, nullptr, e == hipSuccess, "HIP error: %s", hipGetErrorString(e));
-    e = hipMemsetAsync(B->d_counters.p, 0, n_slots * sizeof(unsigned long long), B->run->stream);
-    RW_CTX_CHECK(ctx, RWKV_ERROR_GRAPH, nullptr, e == hipSuccess, "HIP error: %s", hipGetErrorString(e));
+    if (!B->draw.ensure_counters(ctx, B->run->stream)) return nullptr;
     // every slot starts from the fresh state (both buffers: a slot's first pass reads buffer 0)
     for (size_t s = 0; s < n_slots; s++) {
         float * dst = B->slot_buf(s, 0);
@@ -1795,52 +1783,25 @@ RWKV_API bool rwkv_mi_batch_decode_sample(struct rwkv_mi_batch * B, const uint32
 }
 
 RWKV_API bool rwkv_mi_batch_rng_seek(struct rwkv_mi_batch * B, size_t slot, uint64_t counter) {
-    rwkv_context * ctx = B->ctx;
-    ctx->last_error = RWKV_ERROR_NONE;
-    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, slot < B->n_slots, "slot %zu is out of range", slot);
-    BATCH_HIP_OK(B, hipSetDevice(ctx->model->device));
-    hipStream_t st = B->run->stream;
-    const unsigned long long v = counter;
-    BATCH_HIP_OK(B, hipMemcpyAsync(B->d_counters.p + slot, &v, sizeof(v), hipMemcpyHostToDevice, st));
-    BATCH_HIP_OK(B, hipStreamSynchronize(st));
-    return true;
+    return batch_slot_call(B, slot) && on_device(B->ctx) && B->draw.seek(B->ctx, slot, counter, B->run->stream);
 }
 
 RWKV_API bool rwkv_mi_batch_counts_reset(struct rwkv_mi_batch * B, size_t slot) {
-    if (!batch_slot_call(B, slot)) return false;
-    BATCH_HIP_OK(B, hipSetDevice(B->ctx->model->device));
-    if (!batch_ensure_penalty(B)) return false;
-    const size_t V = (size_t) B->ctx->model->n_vocab();
-    BATCH_HIP_OK(B, hipMemsetAsync(B->d_counts.p + slot * V, 0, V * sizeof(uint32_t), B->run->stream));
-    BATCH_HIP_OK(B, hipStreamSynchronize(B->run->stream));
-    return true;
+    return batch_slot_call(B, slot) && on_device(B->ctx) && B->draw.counts_reset(B->ctx, slot, B->run->stream);
 }
 
 RWKV_API bool rwkv_mi_batch_counts_add(struct rwkv_mi_batch * B, size_t slot, const uint32_t * tokens, size_t n) {
-    if (!batch_slot_call(B, slot) || !check_count_tokens(B->ctx, tokens, n)) return false;
-    BATCH_HIP_OK(B, hipSetDevice(B->ctx->model->device));
-    if (!batch_ensure_penalty(B)) return false;
-    return table_counts_add(B->ctx, B->d_counts.p + slot * (size_t) B->ctx->model->n_vocab(), tokens, n, B->run->stream);
+    return batch_slot_call(B, slot) && check_count_tokens(B->ctx, tokens, n) && on_device(B->ctx) && B->draw.counts_add(B->ctx, slot, tokens, n, B->run->stream);
 }
 
 RWKV_API bool rwkv_mi_batch_counts_store(struct rwkv_mi_batch * B, size_t slot, uint32_t * counts_out) {
     if (!batch_slot_call(B, slot)) return false;
     RW_CTX_CHECK(B->ctx, RWKV_ERROR_ARGS, false, counts_out != nullptr, "counts_out is NULL");
-    BATCH_HIP_OK(B, hipSetDevice(B->ctx->model->device));
-    if (!batch_ensure_penalty(B)) return false;
-    const size_t V = (size_t) B->ctx->model->n_vocab();
-    BATCH_HIP_OK(B, hipMemcpyAsync(counts_out, B->d_counts.p + slot * V, V * sizeof(uint32_t), hipMemcpyDeviceToHost, B->run->stream));
-    BATCH_HIP_OK(B, hipStreamSynchronize(B->run->stream));
-    return true;
+    return on_device(B->ctx) && B->draw.counts_store(B->ctx, slot, counts_out, B->run->stream);
 }
 
 RWKV_API bool rwkv_mi_batch_logit_bias_set(struct rwkv_mi_batch * B, size_t slot, const uint32_t * ids, const float * values, size_t n) {
-    if (!batch_slot_call(B, slot) || !check_bias(B->ctx, ids, values, n)) return false;
-    BATCH_HIP_OK(B, hipSetDevice(B->ctx->model->device));
-    if (!batch_ensure_penalty(B)) return false;
-    if (n == 0) { BATCH_HIP_OK(B, hipStreamSynchronize(B->run->stream)); B->has_bias[slot] = 0; return true; }
-    B->has_bias[slot] = 1;   // (a failure below leaves a table that is cleared or half written: it is not read as "no bias")
-    return table_bias_set(B->ctx, B->d_bias.p + slot * (size_t) B->ctx->model->n_vocab(), ids, values, n, B->run->stream);
+    return batch_slot_call(B, slot) && check_bias(B->ctx, ids, values, n) && on_device(B->ctx) && B->draw.bias_set(B->ctx, slot, ids, values, n, B->run->stream);
 }
 
 RWKV_API bool rwkv_mi_batch_eval_sample_penalized(struct rwkv_mi_batch * B, const uint32_t * slots, const uint32_t * tokens, size_t n,
@@ -1894,16 +1855,16 @@ RWKV_API bool rwkv_mi_batch_state_copy(struct rwkv_mi_batch * B, size_t dst_slot
     if (dst_slot == src_slot) return true;
     BATCH_HIP_OK(B, hipSetDevice(ctx->model->device));
     hipStream_t st = B->run->stream;
-    const size_t V = (size_t) ctx->model->n_vocab();
+    DrawState & d = B->draw;
     BATCH_HIP_OK(B, hipMemcpyAsync(B->slot_buf(dst_slot, B->parity[dst_slot]), B->slot_buf(src_slot, B->parity[src_slot]), (size_t) B->state_len * sizeof(float), hipMemcpyDeviceToDevice, st));
     if (what & RWKV_MI_COPY_COUNTER)
-        BATCH_HIP_OK(B, hipMemcpyAsync(B->d_counters.p + dst_slot, B->d_counters.p + src_slot, sizeof(unsigned long long), hipMemcpyDeviceToDevice, st));
+        BATCH_HIP_OK(B, hipMemcpyAsync(d.counter(dst_slot), d.counter(src_slot), sizeof(unsigned long long), hipMemcpyDeviceToDevice, st));
     // (a batch without the penalty tables has every count 0 and no bias: there is nothing to copy)
-    if ((what & RWKV_MI_COPY_COUNTS) && B->d_counts)
-        BATCH_HIP_OK(B, hipMemcpyAsync(B->d_counts.p + dst_slot * V, B->d_counts.p + src_slot * V, V * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-    if ((what & RWKV_MI_COPY_BIAS) && B->d_bias) {
-        BATCH_HIP_OK(B, hipMemcpyAsync(B->d_bias.p + dst_slot * V, B->d_bias.p + src_slot * V, V * sizeof(float), hipMemcpyDeviceToDevice, st));
-        B->has_bias[dst_slot] = B->has_bias[src_slot];
+    if ((what & RWKV_MI_COPY_COUNTS) && d.counts)
+        BATCH_HIP_OK(B, hipMemcpyAsync(d.counts_of(dst_slot), d.counts_of(src_slot), d.n_vocab * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    if ((what & RWKV_MI_COPY_BIAS) && d.bias) {
+        BATCH_HIP_OK(B, hipMemcpyAsync(d.bias.p + dst_slot * d.n_vocab, d.bias.p + src_slot * d.n_vocab, d.n_vocab * sizeof(float), hipMemcpyDeviceToDevice, st));
+        d.has_bias[dst_slot] = d.has_bias[src_slot];
     }
     BATCH_HIP_OK(B, hipStreamSynchronize(st));
     return true;

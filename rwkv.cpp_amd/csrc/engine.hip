@@ -187,6 +187,7 @@ rwkv_context * create_context(Model * m, uint32_t n_threads) {
     }
     ctx->model = m;
     ctx->n_threads = n_threads;
+    ctx->draw.init(1, (size_t) m->n_vocab());
     m->refcount++;
     auto fail = [&](hipError_t e) {
         global_fail(RWKV_ERROR_CTX | RWKV_ERROR_ALLOC, __FILE__, __LINE__, "hip allocation", "HIP error: %s", hipGetErrorString(e));
@@ -811,41 +812,40 @@ void batch_context_destroy(rwkv_context * c) {
     destroy_context(c);
 }
 
-// The row sampler of a batch pass over the `rows` rows of ctx->d_logits.p: row r's token goes to ctx->d_tokens.p[r] (and to s.hist[r] when given).
-// Order within a step: the draw (or argmax), then the report of what it wrote (s.report), then the stop test.
-static void launch_row_sampler(rwkv_context * ctx, const RowSampler & s, int64_t rows) {
+// What follows the head of a batch pass over the `rows` rows of ctx->d_logits.p (model.h, RowSampler): row r's token goes to ctx->d_tokens.p[r]
+// and, with a history, into the step's row of it. Order within a step: the choice, then the report of what it wrote, then the stop test.
+void launch_row_sampler(rwkv_context * ctx, const RowSampler & s, int64_t rows) {
     const int n_vocab = (int) ctx->model->n_vocab();
+    const float * logits = ctx->d_logits.p;
+    uint32_t * tokens = ctx->d_tokens.p;
     if (s.beam) {
         // a step of rwkv_mi_batch_decode_beam: every row's candidates, then each group's selection (which writes the rows' next tokens)
-        launch_beam_rows(ctx->d_logits.p, rows, n_vocab, s.beam->t, ctx->stream);
-        launch_beam_select(s.beam->t, rows / (int64_t) s.beam->t.width, ctx->d_tokens.p, s.beam->step, s.beam->used, s.beam->other, ctx->stream);
+        launch_beam_rows(logits, rows, n_vocab, s.beam->t, ctx->stream);
+        launch_beam_select(s.beam->t, rows / (int64_t) s.beam->t.width, tokens, s.step, s.beam->used, s.beam->other, ctx->stream);
         return;
     }
-    if (s.stop) {
-        // a step of rwkv_mi_batch_decode_until: the draw behind the live words, then the stop test on what it wrote
-        uint32_t * hist = s.hist + (size_t) s.stop->step * (size_t) rows;
-        const uint32_t * live = s.stop->t.live;
-        if (s.ptable) launch_pen_sample_rows_live(ctx->d_logits.p, rows, n_vocab, s.ptable, s.probs, ctx->d_tokens.p, hist, live, ctx->stream);
-        else if (s.table) launch_sample_rows_live(ctx->d_logits.p, rows, n_vocab, s.table, s.probs, ctx->d_tokens.p, hist, live, ctx->stream);
-        else launch_argmax_live(ctx->d_logits.p, rows, n_vocab, ctx->d_tokens.p, hist, live, ctx->stream);
-        if (s.report) {
-            const size_t at = (size_t) s.stop->step * (size_t) rows;
-            launch_logprob_rows(ctx->d_logits.p, rows, n_vocab, ctx->d_tokens.p, (int) s.report->top_n, s.report->chosen + at, s.report->ids + at * s.report->top_n,
-                                s.report->vals + at * s.report->top_n, live, ctx->stream);
-        }
-        launch_stop_rows(s.stop->t, rows, s.hist, s.stop->step, s.stop->used, s.stop->other, ctx->stream);
-        return;
+    const size_t at = (size_t) s.step * (size_t) rows;   // the step's slot of the call's history and report buffers
+    uint32_t * hist = s.hist ? s.hist + at : nullptr;
+    const uint32_t * live = s.stop ? s.stop->t.live : nullptr;   // (rwkv_mi_batch_decode_until: everything but the stop test runs behind the live words)
+    switch (s.draw) {
+        case Draw::penalized: launch_pen_sample_rows(logits, rows, n_vocab, s.prows, s.probs, tokens, hist, live, ctx->stream); break;
+        case Draw::sample:    launch_sample_rows(logits, rows, n_vocab, s.srows, s.probs, tokens, hist, live, ctx->stream); break;
+        case Draw::none:
+            if (live) launch_argmax_live(logits, rows, n_vocab, tokens, hist, live, ctx->stream);
+            else launch_argmax(logits, rows, n_vocab, tokens, hist, ctx->stream);
+            break;
     }
-    if (s.ptable) launch_pen_sample_rows(ctx->d_logits.p, rows, n_vocab, s.ptable, s.probs, ctx->d_tokens.p, s.hist, ctx->stream);
-    else launch_sample_rows(ctx->d_logits.p, rows, n_vocab, s.table, s.probs, ctx->d_tokens.p, s.hist, ctx->stream);
-    if (s.report) launch_logprob_rows(ctx->d_logits.p, rows, n_vocab, ctx->d_tokens.p, (int) s.report->top_n, s.report->chosen, s.report->ids, s.report->vals, nullptr, ctx->stream);
+    if (const RowReport * rp = s.report)
+        launch_logprob_rows(logits, rows, n_vocab, tokens, (int) rp->top_n, rp->chosen + at, rp->ids + at * rp->top_n, rp->vals + at * rp->top_n, live, ctx->stream);
+    if (s.stop) launch_stop_rows(s.stop->t, rows, s.hist, s.step, s.stop->used, s.stop->other, ctx->stream);
 }
 
 // One pass of T rows, row t = one token (ctx->d_tokens.p[t]) of the sequence whose state is d_rows[t]. Logits: ctx->d_logits.p[T][n_vocab].
 // sample: the T sampler workgroups (sampling.hip, k_sample_rows) follow the head INSIDE the chain bracket. Each of them is 1024 threads,
 // a CU's worth of waves, so up to T CUs are taken while they run; the completion event mega_chain_end records is what the device's next
 // persistent launch waits on, and with the sampler in front of it that launch still finds every CU free ("a batch pass never runs beside
-// a persistent kernel" holds for the sampler too). The greedy loop's argmax stays where it was, after the bracket.
+// a persistent kernel" holds for the sampler too). The greedy loop's argmax stays where it was, after the bracket: batch_loop (api.cpp) calls
+// launch_row_sampler itself behind the pass for that family.
 bool forward_rows(rwkv_context * ctx, const RowState * d_rows, int64_t T, bool want_logits, const RowSampler * sample) {
     if (!ensure_scratch(ctx, T)) return false;
     Model & m = *ctx->model;

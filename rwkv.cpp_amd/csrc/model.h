@@ -12,6 +12,8 @@
 #include "persist_host.h"
 #include "rwkv_mi355x.h"
 
+struct rwkv_context;
+
 namespace rwkvmi {
 
 // Parameter slots of one layer; names follow the reference's key table (rwkv_model_loading.inc:132-282).
@@ -115,7 +117,10 @@ inline size_t sample_scratch_floats(int64_t n) { return (size_t) ((n + 1023) / 1
 // of the row's SLOT). probs: [rows][sample_scratch_floats(n)] scratch. Row r's token goes to tokens[r] (the word its next embedding lookup
 // reads) and, when hist is given, to hist[r].
 struct SampleRow { rwkv_mi_sample_params p; unsigned long long * counter; };
-void launch_sample_rows(const float * logits, int64_t rows, int n, const SampleRow * table, float * probs, uint32_t * tokens, uint32_t * hist, hipStream_t st);
+// live (here and in the penalised form; NULL: every row draws): rwkv_mi_batch_decode_until's per-row live words -- a row with live[r] == 0 returns
+// before it reads a logit: no draw, no counter advance, no count, no token or history word.
+void launch_sample_rows(const float * logits, int64_t rows, int n, const SampleRow * table, float * probs, uint32_t * tokens, uint32_t * hist,
+                        const uint32_t * live, hipStream_t st);
 void launch_sample_seek_rows(const SampleRow * table, int64_t rows, unsigned long long value, hipStream_t st);   // *table[r].counter = value
 // The penalised forms (rwkv_mi_*_penalized): the same draw on adj[j] = (logits[j] - (presence + (float) count[j] * frequency)) + bias[j]
 // (the penalty where count[j] > 0 only; bias == NULL: no bias), then count[token] += 1 when record is set. count: the sequence's occurrence table ([n] words), bias: its bias
@@ -124,13 +129,8 @@ struct PenaltyRow { rwkv_mi_sample_params p; unsigned long long * counter; float
 void launch_pen_sample(const float * logits, int n, float temperature, float top_p, float u, unsigned long long seed, unsigned long long * counter,
                        float presence, float frequency, uint32_t record, uint32_t * count, const float * bias,
                        float * probs, uint32_t * out_token, uint32_t * hist, int hist_pos, hipStream_t st);
-void launch_pen_sample_rows(const float * logits, int64_t rows, int n, const PenaltyRow * table, float * probs, uint32_t * tokens, uint32_t * hist, hipStream_t st);
-// rwkv_mi_batch_decode_until (sampling.hip): the two row samplers behind a per-row live word -- a row with live[r] == 0 returns before it reads
-// a logit: no draw, no counter advance, no count, no token or history word -- and the stop test that retires rows.
-void launch_sample_rows_live(const float * logits, int64_t rows, int n, const SampleRow * table, float * probs, uint32_t * tokens, uint32_t * hist,
-                             const uint32_t * live, hipStream_t st);
-void launch_pen_sample_rows_live(const float * logits, int64_t rows, int n, const PenaltyRow * table, float * probs, uint32_t * tokens, uint32_t * hist,
-                                 const uint32_t * live, hipStream_t st);
+void launch_pen_sample_rows(const float * logits, int64_t rows, int n, const PenaltyRow * table, float * probs, uint32_t * tokens, uint32_t * hist,
+                            const uint32_t * live, hipStream_t st);
 // A row's stop parameters and where its sequences start in the call's flat tables: its lengths at seq_lens[seq0 ..], its tokens at seq_tokens[tok0 ..].
 struct StopRow { uint32_t max_tokens, n_seqs, seq0, tok0; };
 // The device words of a call: per row its live word (1 until it retires), its length and its reason (the index of the matching sequence, or
@@ -161,6 +161,37 @@ void launch_beam_rows(const float * logits, int64_t rows, int n, const BeamTable
 void launch_beam_select(const BeamTables & t, int64_t groups, uint32_t * tokens, uint32_t step, const RowState * used, RowState * other, hipStream_t st);
 void launch_count_add(uint32_t * count, const uint32_t * tokens, int64_t n, int n_vocab, hipStream_t st);                        // count[tokens[i]] += 1
 void launch_bias_scatter(float * bias, const uint32_t * ids, const float * values, int64_t n, int n_vocab, hipStream_t st);     // bias[ids[i]] = values[i]
+
+// The draw state of `slots` sequences of a model, owned in one place (api.cpp): per slot the draw counter, the sampler's scratch vector, the
+// occurrence table and the bias table of the penalised draw, and whether a bias is set. A context holds one of 1 slot, a batch one of n_slots.
+// Nothing is allocated by init(): the counters come with ensure_counters (a batch calls it when it is created, so its counters exist and are
+// zero from then on; a context gets its counter with its first draw or seek), the scratch with ensure_sampler, the two tables -- zeroed; a
+// table that could not be zeroed is not kept -- with the first call of the penalised family. Every growth is one grow(want(...)) decision: a
+// call that fails leaves every buffer as it was. No stream is kept (rwkv_mi_set_stream can change a context's): each operation takes the
+// stream it works on and the context its errors are reported on -- RWKV_ERROR_ALLOC for memory, RWKV_ERROR_GRAPH for any other HIP error.
+// The operations on a slot's tables drain the stream before they return.
+struct DrawState {
+    size_t slots = 0, n_vocab = 0;
+    DevBuf<unsigned long long> counters;   // [slots]
+    DevBuf<float>    probs;                // [slots][sample_scratch_floats(n_vocab)]
+    DevBuf<uint32_t> counts;               // [slots][n_vocab]
+    DevBuf<float>    bias;                 // [slots][n_vocab]
+    std::vector<uint8_t> has_bias;         // [slots]: a bias has been set and not cleared
+
+    void init(size_t n_slots, size_t vocab) { slots = n_slots; n_vocab = vocab; has_bias.assign(n_slots, 0); }
+    unsigned long long * counter(size_t slot) const { return counters.p + slot; }
+    uint32_t * counts_of(size_t slot) const { return counts.p + slot * n_vocab; }
+    const float * bias_of(size_t slot) const { return has_bias[slot] ? bias.p + slot * n_vocab : nullptr; }   // NULL: none is set
+
+    bool ensure_counters(rwkv_context * ctx, hipStream_t st);
+    bool ensure_sampler(rwkv_context * ctx, hipStream_t st);   // the counters and the scratch
+    bool ensure_penalty(rwkv_context * ctx, hipStream_t st);   // the two tables
+    bool seek(rwkv_context * ctx, size_t slot, unsigned long long value, hipStream_t st);
+    bool counts_reset(rwkv_context * ctx, size_t slot, hipStream_t st);
+    bool counts_add(rwkv_context * ctx, size_t slot, const uint32_t * tokens, size_t n, hipStream_t st);   // (arguments checked: check_count_tokens)
+    bool counts_store(rwkv_context * ctx, size_t slot, uint32_t * counts_out, hipStream_t st);
+    bool bias_set(rwkv_context * ctx, size_t slot, const uint32_t * ids, const float * values, size_t n, hipStream_t st);   // n == 0: cleared (check_bias)
+};
 
 // Loads [layer_begin, layer_end) of the file (layer_end == UINT32_MAX: all layers) onto the current HIP device.
 // Returns nullptr with the thread-local error set, like the reference loader (rwkv_model_loading.inc:288-419).
@@ -221,11 +252,7 @@ struct rwkv_context {
     rwkvmi::PinBuf<uint32_t> h_tokens;
     rwkvmi::DevBuf<float>    d_logits;
     rwkvmi::DevBuf<uint32_t> d_next_token;
-    rwkvmi::DevBuf<float>    d_probs;             // sampler scratch (sample_scratch_floats(n_vocab) floats), allocated on first use
-    rwkvmi::DevBuf<unsigned long long> d_rng_counter;
-    rwkvmi::DevBuf<uint32_t> d_counts;            // penalised sampling (rwkv_mi_*_penalized): the context's occurrence table [n_vocab] and its bias table
-    rwkvmi::DevBuf<float>    d_bias;              // [n_vocab], allocated by the first call of that family; has_bias: a bias has been set and not cleared
-    bool       has_bias = false;
+    rwkvmi::DrawState draw;                       // the context's draw state, 1 slot: counter, sampler scratch, occurrence and bias table
     // scoring (rwkv_mi_score_resident / rwkv_mi_batch_score_ragged; engine.hip ensure_score), allocated by the first scoring call: the chunk
     // of the all-position head, [score_R][n_vocab] logits, and the per-row words of a pass for score_cap rows -- targets in (with their
     // pinned staging), log-probs and argmax out
@@ -304,19 +331,32 @@ bool ensure_score(rwkv_context * ctx, int64_t rows);
 // chain of persistent launches) and one pass of T rows, row t from state d_rows[t].in into d_rows[t].out
 rwkv_context * batch_context_create(Model * m, int64_t max_rows);
 void batch_context_destroy(rwkv_context * c);
-// sample: when given, one sampled token per row from the pass's logits (launch_sample_rows), launched inside the pass's place in the chain
-// (ptable: the penalised row table; when given, launch_pen_sample_rows takes the place of launch_sample_rows and `table` is not read)
-// stop: the pass is step `step` of rwkv_mi_batch_decode_until -- the draw (with neither table: the greedy argmax) runs behind the live words and
-// launch_stop_rows follows it, both inside the pass's place in the chain; hist is then the WHOLE history [step][T] and step's row is written
-// report: when given, launch_logprob_rows follows the draw (and precedes the stop test) on the tokens it wrote: the pointers are the step's slot of
-// the report buffers -- with stop, as hist, the WHOLE buffers, and step's slot is written behind the live words
-// beam: the pass is step `step` of rwkv_mi_batch_decode_beam -- instead of a draw, launch_beam_rows and launch_beam_select follow the head, both
-// inside the pass's place in the chain; nothing else of the sampler is read
-struct RowStop { StopTables t; uint32_t step; RowState * used, * other; };
+// What follows the head of a batch pass over `rows` rows (launch_row_sampler), described once: row r's token goes to ctx->d_tokens.p[r].
+//   draw    which choice is made: the greedy argmax (none), the sampler (sample: srows, launch_sample_rows) or the penalised sampler
+//           (penalized: prows, launch_pen_sample_rows); probs: the samplers' scratch
+//   hist, report, step   the call's WHOLE history [steps][rows] and report buffers (chosen [steps][rows], ids / vals [steps][rows][top_n]), either
+//           may be NULL, and the step of the call this pass is: the step's slot of each is written. A single pass is step 0
+//   stop    the pass is a step of rwkv_mi_batch_decode_until: the choice and the report run behind the live words and launch_stop_rows follows them
+//   beam    the pass is a step of rwkv_mi_batch_decode_beam: instead of a choice, launch_beam_rows and launch_beam_select follow the head;
+//           of the rest only `step` is read
+// Order within a step: the choice, then the report of what it wrote, then the stop test.
+enum class Draw { none, sample, penalized };
+struct RowStop { StopTables t; RowState * used, * other; };
 struct RowReport { float * chosen; uint32_t * ids; float * vals; uint32_t top_n; };
-struct RowBeam { BeamTables t; uint32_t step; const RowState * used; RowState * other; };
-struct RowSampler { const SampleRow * table; float * probs; uint32_t * hist; const PenaltyRow * ptable = nullptr; const RowStop * stop = nullptr;
-                    const RowReport * report = nullptr; const RowBeam * beam = nullptr; };
+struct RowBeam { BeamTables t; const RowState * used; RowState * other; };
+struct RowSampler {
+    Draw draw = Draw::none;
+    const SampleRow * srows = nullptr;
+    const PenaltyRow * prows = nullptr;
+    float * probs = nullptr;
+    uint32_t * hist = nullptr;
+    const RowReport * report = nullptr;
+    uint32_t step = 0;
+    const RowStop * stop = nullptr;
+    const RowBeam * beam = nullptr;
+};
+void launch_row_sampler(rwkv_context * ctx, const RowSampler & s, int64_t rows);
+// sample: when given, launch_row_sampler follows the head inside the pass's place in the chain
 bool forward_rows(rwkv_context * ctx, const RowState * d_rows, int64_t T, bool want_logits, const RowSampler * sample = nullptr);
 
 // Ragged batch pass: row i of the call is a SEGMENT, tokens [t0, t1) of the pass, consecutive tokens of one slot's sequence.

@@ -15,8 +15,8 @@
 // (the reference's chat program, chat_with_bot.py:246-247 -- its loop runs over the tokens that have occurred -- then sample_logits'
 // logit_bias, sampling.py:27-36; every operation rounded to f32 in that order) from the sequence's occurrence table count[n] and its
 // optional bias table, and counts the chosen token afterwards.
-// rwkv_mi_batch_decode_until: k_sample_rows_live / k_pen_sample_rows_live are the two row samplers behind a per-row live word, and
-// k_stop_rows retires a row -- stop sequence or budget -- by rewriting its entries of the two row tables on the device.
+// rwkv_mi_batch_decode_until: the two row samplers take a per-row live word (live; NULL everywhere else), and k_stop_rows retires a
+// row -- stop sequence or budget -- by rewriting its entries of the two row tables on the device.
 // The logits themselves are never written.
 #include "kdev.h"
 #include "model.h"
@@ -208,25 +208,16 @@ __global__ __launch_bounds__(1024) void k_sample(const float * __restrict__ logi
 }
 
 // Row form: grid = rows, one workgroup per row; row r's probabilities in its own stretch of the scratch (stride floats apart, the batch owns it).
+// live (rwkv_mi_batch_decode_until; NULL: every row draws): a row whose LIVE WORD is 0 has retired and returns before it reads a logit -- no
+// draw, no counter advance, no token or history word. The whole workgroup takes the branch together: no barrier is left waiting.
 __global__ __launch_bounds__(1024) void k_sample_rows(const float * __restrict__ logits, int n, const SampleRow * __restrict__ table,
-                                                      float * __restrict__ probs, size_t stride, uint32_t * __restrict__ tokens, uint32_t * __restrict__ hist) {
+                                                      float * __restrict__ probs, size_t stride, uint32_t * __restrict__ tokens, uint32_t * __restrict__ hist,
+                                                      const uint32_t * __restrict__ live) {
     const size_t r = blockIdx.x;
+    if (live && !live[r]) return;
     const rwkv_mi_sample_params p = table[r].p;
     const float * lg = logits + r * (size_t) n;
     sample_body([=](int i0) { return PlainLogits{lg + i0}; }, n, p.temperature, p.top_p, p.u, p.seed, table[r].counter, probs + r * stride, tokens + r, hist ? hist + r : nullptr);
-}
-
-// The row form behind its LIVE WORD (rwkv_mi_batch_decode_until), a third entry point over the same body: a row that has retired returns
-// before it reads a logit -- no draw, no counter advance, no token or history word. The whole workgroup takes the branch together: no barrier
-// is left waiting. hist is always given here.
-__global__ __launch_bounds__(1024) void k_sample_rows_live(const float * __restrict__ logits, int n, const SampleRow * __restrict__ table,
-                                                           float * __restrict__ probs, size_t stride, uint32_t * __restrict__ tokens, uint32_t * __restrict__ hist,
-                                                           const uint32_t * __restrict__ live) {
-    const size_t r = blockIdx.x;
-    if (!live[r]) return;
-    const rwkv_mi_sample_params p = table[r].p;
-    const float * lg = logits + r * (size_t) n;
-    sample_body([=](int i0) { return PlainLogits{lg + i0}; }, n, p.temperature, p.top_p, p.u, p.seed, table[r].counter, probs + r * stride, tokens + r, hist + r);
 }
 
 // The penalised entry points: the same body on the adjusted logits, then -- when `record` is set -- the chosen token's count goes up by
@@ -240,26 +231,16 @@ __global__ __launch_bounds__(1024) void k_pen_sample(const float * __restrict__ 
     if (threadIdx.x == 0 && record) count[pick] += 1u;
 }
 
+// (live: as k_sample_rows -- a retired row records nothing either)
 __global__ __launch_bounds__(1024) void k_pen_sample_rows(const float * __restrict__ logits, int n, const PenaltyRow * __restrict__ table,
-                                                          float * __restrict__ probs, size_t stride, uint32_t * __restrict__ tokens, uint32_t * __restrict__ hist) {
+                                                          float * __restrict__ probs, size_t stride, uint32_t * __restrict__ tokens, uint32_t * __restrict__ hist,
+                                                          const uint32_t * __restrict__ live) {
     const size_t r = blockIdx.x;
+    if (live && !live[r]) return;
     const PenaltyRow row = table[r];
     const float * lg = logits + r * (size_t) n;
     const int pick = sample_body([=](int i0) { return PenalisedLogits{lg + i0, row.count + i0, row.bias ? row.bias + i0 : nullptr, row.presence, row.frequency}; },
                                  n, row.p.temperature, row.p.top_p, row.p.u, row.p.seed, row.counter, probs + r * stride, tokens + r, hist ? hist + r : nullptr);
-    if (threadIdx.x == 0 && row.record) row.count[pick] += 1u;
-}
-
-// ... and behind its live word: a retired row records nothing either
-__global__ __launch_bounds__(1024) void k_pen_sample_rows_live(const float * __restrict__ logits, int n, const PenaltyRow * __restrict__ table,
-                                                               float * __restrict__ probs, size_t stride, uint32_t * __restrict__ tokens, uint32_t * __restrict__ hist,
-                                                               const uint32_t * __restrict__ live) {
-    const size_t r = blockIdx.x;
-    if (!live[r]) return;
-    const PenaltyRow row = table[r];
-    const float * lg = logits + r * (size_t) n;
-    const int pick = sample_body([=](int i0) { return PenalisedLogits{lg + i0, row.count + i0, row.bias ? row.bias + i0 : nullptr, row.presence, row.frequency}; },
-                                 n, row.p.temperature, row.p.top_p, row.p.u, row.p.seed, row.counter, probs + r * stride, tokens + r, hist + r);
     if (threadIdx.x == 0 && row.record) row.count[pick] += 1u;
 }
 
@@ -315,8 +296,9 @@ void launch_sample(const float * logits, int n, float temperature, float top_p, 
     hipLaunchKernelGGL(k_sample, dim3(1), dim3(1024), 0, st, logits, n, temperature, top_p, u, seed, counter, probs, out_token, hist, hist_pos);
 }
 
-void launch_sample_rows(const float * logits, int64_t rows, int n, const SampleRow * table, float * probs, uint32_t * tokens, uint32_t * hist, hipStream_t st) {
-    hipLaunchKernelGGL(k_sample_rows, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, table, probs, sample_scratch_floats(n), tokens, hist);
+void launch_sample_rows(const float * logits, int64_t rows, int n, const SampleRow * table, float * probs, uint32_t * tokens, uint32_t * hist,
+                        const uint32_t * live, hipStream_t st) {
+    hipLaunchKernelGGL(k_sample_rows, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, table, probs, sample_scratch_floats(n), tokens, hist, live);
 }
 
 void launch_pen_sample(const float * logits, int n, float temperature, float top_p, float u, unsigned long long seed, unsigned long long * counter,
@@ -326,18 +308,9 @@ void launch_pen_sample(const float * logits, int n, float temperature, float top
                        probs, out_token, hist, hist_pos);
 }
 
-void launch_pen_sample_rows(const float * logits, int64_t rows, int n, const PenaltyRow * table, float * probs, uint32_t * tokens, uint32_t * hist, hipStream_t st) {
-    hipLaunchKernelGGL(k_pen_sample_rows, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, table, probs, sample_scratch_floats(n), tokens, hist);
-}
-
-void launch_sample_rows_live(const float * logits, int64_t rows, int n, const SampleRow * table, float * probs, uint32_t * tokens, uint32_t * hist,
-                             const uint32_t * live, hipStream_t st) {
-    hipLaunchKernelGGL(k_sample_rows_live, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, table, probs, sample_scratch_floats(n), tokens, hist, live);
-}
-
-void launch_pen_sample_rows_live(const float * logits, int64_t rows, int n, const PenaltyRow * table, float * probs, uint32_t * tokens, uint32_t * hist,
-                                 const uint32_t * live, hipStream_t st) {
-    hipLaunchKernelGGL(k_pen_sample_rows_live, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, table, probs, sample_scratch_floats(n), tokens, hist, live);
+void launch_pen_sample_rows(const float * logits, int64_t rows, int n, const PenaltyRow * table, float * probs, uint32_t * tokens, uint32_t * hist,
+                            const uint32_t * live, hipStream_t st) {
+    hipLaunchKernelGGL(k_pen_sample_rows, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, table, probs, sample_scratch_floats(n), tokens, hist, live);
 }
 
 void launch_stop_rows(const StopTables & t, int64_t rows, const uint32_t * hist, uint32_t step, RowState * used, RowState * other, hipStream_t st) {

@@ -170,7 +170,7 @@ __global__ __launch_bounds__(1024) void k_logprob_rows(const float * __restrict_
     logprob_row_body(logits_all + r * (size_t) n, n, tokens[r], top_n, chosen + r, top_ids + r * (size_t) top_n, top_lp + r * (size_t) top_n);
 }
 
-// ... and behind the row's LIVE WORD (rwkv_mi_batch_decode_until; the pattern of k_sample_rows_live): a retired row writes nothing. The launch
+// ... and behind the row's LIVE WORD (rwkv_mi_batch_decode_until; as the row samplers' live argument): a retired row writes nothing. The launch
 // sits between the draw and k_stop_rows, so the step at which a row retires is reported. The whole workgroup takes the branch together.
 __global__ __launch_bounds__(1024) void k_logprob_rows_live(const float * __restrict__ logits_all, int n, const uint32_t * __restrict__ tokens, int top_n,
                                                             float * __restrict__ chosen, uint32_t * __restrict__ top_ids, float * __restrict__ top_lp,

@@ -1,7 +1,8 @@
 """Stop sequences and per-row token budgets in the batch decode loops (rwkv_mi_batch_decode_until), without a GPU: the libraries export the
 two entry points, the header and the binding declare them, struct rwkv_mi_stop_params is laid out as the C header has it, decode_until's
-arguments are shaped as documented, and the sampler's new entry points (csrc/sampling.hip: k_sample_rows_live, k_pen_sample_rows_live, and
-the stop test k_stop_rows) keep within the budget of a 1024-thread workgroup while the four existing entry points keep the registers they had.
+arguments are shaped as documented, and csrc/sampling.hip has exactly its four draw entry points and the stop test k_stop_rows: all five keep
+within the budget of a 1024-thread workgroup, and the four draw entry points -- the two row forms now take the live words of decode_until as
+a last argument that may be NULL -- keep the registers they had before that argument.
 
 stop_rule() below is the stop rule of include/rwkv_mi355x.h restated in Python; tests/test_gpu_batch_until.py imports it as its matcher."""
 import ctypes
@@ -16,9 +17,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = "/opt/rocm/bin/hipcc"
 SYMBOLS = ("rwkv_mi_batch_decode_until", "rwkv_mi_batch_last_loop_passes")
 NO_TOKEN = 0xFFFFFFFF
-# (sgpr_count, vgpr_count) of the four existing entry points as the commit before this feature compiles them for gfx950: they must not move
+# (sgpr_count, vgpr_count) of the four draw entry points as the commit before decode_until compiled them for gfx950: they must not move
 PARENT_REGS = {"k_sample": (48, 39), "k_sample_rows": (52, 39), "k_pen_sample": (50, 39), "k_pen_sample_rows": (54, 39)}
-NEW_KERNELS = ("k_sample_rows_live", "k_pen_sample_rows_live", "k_stop_rows")
+NEW_KERNELS = ("k_stop_rows",)
 
 
 def stop_rule(tokens, max_tokens, seqs):
@@ -121,7 +122,7 @@ def test_stop_rule_hand_written_cases():
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
-def test_live_entry_points_keep_the_budget_and_the_existing_four_their_registers(tmp_path):
+def test_draw_entry_points_and_stop_test_keep_the_budget_and_the_four_their_registers(tmp_path):
     src = os.path.join(ROOT, "rwkv.cpp_amd", "csrc", "sampling.hip")
     out = str(tmp_path / "sampling.s")
     cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-DRWKV_SHARED", "-DRWKV_BUILD",

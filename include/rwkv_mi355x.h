@@ -420,6 +420,51 @@ RWKV_API bool rwkv_mi_logprobs_shape(struct rwkv_context * ctx, size_t * rows, s
 RWKV_API bool rwkv_mi_logprobs_store(struct rwkv_context * ctx, size_t stride, float * chosen_out /* [stride] */,
                                      uint32_t * top_ids_out /* [stride][top_n] */, float * top_logprobs_out /* [stride][top_n] */);
 
+/* ---- Guided decoding: token automata that mask the device sampler per slot ----
+ * What serving APIs call JSON mode, a regex, a choice among fixed answers, a tool-call grammar: constraining WHICH tokens a row may emit. A GUIDE
+ * is a deterministic automaton over token ids: n_states states and a transition next(state, token) that is a state or DEAD. A batch holds up
+ * to RWKV_MI_GUIDE_MAX guides, shared by its slots (one schema serves many requests); each slot may have one attached, with a current state.
+ * Compiling a regex or a schema into such an automaton is the caller's business.
+ * THE SEMANTICS, one statement: a row whose slot has a guide attached, in state s, reads instead of its logit for token j
+ *     the value its draw would read anyway -- l[j] for the plain sampler, adj[j] for the penalised one -- where next(s, j) is a state,
+ *     -inf                                                                                               where next(s, j) is dead;
+ * everything after that is the sampler unchanged: softmax, top-p cut-off, temperature power, draw, the draw-counter rule, temperature == 0 ->
+ * argmax. After the draw the slot's state becomes next(s, token). If the picked token is dead -- possible only with all-NaN logits, or when
+ * the caller's own -inf bias removes every allowed token -- the state stays s and the slot's MISS COUNTER goes up by one.
+ * The logits are never written, and the report keeps reporting the model's logits, as it does under penalties.
+ * HONOURED by the sampled and penalised batch calls, for whatever is attached to the slots they name: rwkv_mi_batch_eval_sample,
+ * _eval_ragged_sample, _decode_sample, their _penalized forms, and rwkv_mi_batch_decode_until with params. The loops CONTINUE a guide as the
+ * penalised loops continue their counts: nothing resets a guide state except rwkv_mi_batch_guide_attach. In a ragged pass EVERY row draws and
+ * so advances its guide: a caller that feeds non-final prompt chunks attaches the guide before the pass whose draw is the first constrained
+ * token, not earlier. A retired row of rwkv_mi_batch_decode_until does not advance its guide, and THE GUARANTEE of that call extends to the
+ * guide words: afterwards a slot's guide state and miss counter are those of the plain loop of lens_out[r] steps.
+ * An unguided slot in a call that also names guided ones draws, bit for bit, what it draws in a call without any; a call that names no guided
+ * slot performs no launch, allocation or copy it did not perform before, and a batch that never creates a guide allocates nothing.
+ * REJECTED with RWKV_ERROR_ARGS, nothing changed, when a named slot has a guide attached: rwkv_mi_batch_decode_greedy, rwkv_mi_batch_decode_until
+ * with params == NULL and rwkv_mi_batch_decode_beam -- the greedy family has no sampler to mask; guided greedy is temperature == 0 on the
+ * sampled family. rwkv_mi_batch_eval, rwkv_mi_batch_score_ragged and rwkv_mi_batch_state_copy (no copy bit names them) leave guide words alone.
+ * ON THE DEVICE a guide is the dense table uint16_t next[n_states][n_vocab], 0xFFFF for dead: 2 n_vocab bytes per state (128 KiB at 65 536
+ * tokens). The edges cross to the device in the CSR form below and are expanded there.
+ * rwkv_mi_batch_guide_create: the edges of state s are edge_tokens / edge_next [edge_begin[s] .. edge_begin[s + 1]), tokens strictly ascending.
+ * *guide_out is the new guide's id (0 .. RWKV_MI_GUIDE_MAX - 1). False with RWKV_ERROR_ARGS, nothing changed, when a pointer is NULL, n_states is 0
+ * or above RWKV_MI_GUIDE_MAX_STATES, RWKV_MI_GUIDE_MAX guides exist, edge_begin does not start at 0 or decreases, a state has no edge (every state
+ * allows at least one token: a mask is never empty), a token is >= n_vocab, a state's tokens are not strictly ascending, or a next is >=
+ * n_states; with RWKV_ERROR_ALLOC, nothing changed, when the table cannot be allocated.
+ * rwkv_mi_batch_guide_free: RWKV_ERROR_ARGS, nothing changed, for an id that names no guide and for a guide still attached to a slot.
+ * rwkv_mi_batch_guide_attach: attaches `guide` to the slot in `state` and sets the slot's miss counter to 0; RWKV_MI_NO_GUIDE detaches (state is
+ * ignored). RWKV_ERROR_ARGS, nothing changed, for a slot out of range, an id that names no guide, a state >= the guide's n_states. The slots'
+ * guide words are allocated by the first attach (RWKV_ERROR_ALLOC, nothing changed, when they cannot be).
+ * rwkv_mi_batch_guide_state: the slot's guide (RWKV_MI_NO_GUIDE, state 0, misses 0 for a slot without one), its current state and its miss
+ * counter; each output may be NULL. rwkv_mi_batch_free releases the guides and the guide words. */
+#define RWKV_MI_GUIDE_MAX        16        /* guides per batch */
+#define RWKV_MI_GUIDE_MAX_STATES 65535     /* states per guide (0xFFFF is the dead word) */
+#define RWKV_MI_NO_GUIDE         UINT32_MAX
+RWKV_API bool rwkv_mi_batch_guide_create(struct rwkv_mi_batch * batch, uint32_t n_states, const uint32_t * edge_begin /* [n_states + 1] */,
+                                         const uint32_t * edge_tokens, const uint32_t * edge_next, uint32_t * guide_out);
+RWKV_API bool rwkv_mi_batch_guide_free(struct rwkv_mi_batch * batch, uint32_t guide);
+RWKV_API bool rwkv_mi_batch_guide_attach(struct rwkv_mi_batch * batch, size_t slot, uint32_t guide /* RWKV_MI_NO_GUIDE: detach */, uint32_t state);
+RWKV_API bool rwkv_mi_batch_guide_state(struct rwkv_mi_batch * batch, size_t slot, uint32_t * guide_out, uint32_t * state_out, uint32_t * misses_out);
+
 #if defined(__cplusplus)
 }
 #endif

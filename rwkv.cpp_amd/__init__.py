@@ -5,8 +5,12 @@ repo root to sys.path and use `importlib.import_module("rwkv.cpp_amd")` is NOT p
 """
 from .rwkv_cpp import (  # noqa: F401
     BeamParams,
+    GUIDE_HOOKS_LIB_PATH,
+    GUIDE_MAX,
+    GUIDE_MAX_STATES,
     HOOKS_LIB_PATH,
     LIB_PATH,
+    NO_GUIDE,
     NO_TARGET,
     NO_TOKEN,
     PenaltyParams,
@@ -19,6 +23,7 @@ from .rwkv_cpp import (  # noqa: F401
     StopParams,
     TOP_MAX,
     build_library,
+    guide_edges,
     load_rwkv_shared_library,
     penalty_params,
     sample_params,

@@ -577,6 +577,44 @@ bool DrawState::bias_set(rwkv_context * ctx, size_t slot, const uint32_t * ids, 
     return true;
 }
 
+bool DrawState::ensure_guides(rwkv_context * ctx, hipStream_t st) {
+    if (guide_state && guide_misses) return true;
+    DevBuf<uint32_t> s, m;
+    const hipError_t e = grow(want(s, slots), want(m, slots));
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the guide words of %zu slots: %s", slots, hipGetErrorString(e));
+    // (words that could not be zeroed are not kept)
+    HIP_CTX_OK(ctx, hipMemsetAsync(s.p, 0, slots * sizeof(uint32_t), st));
+    HIP_CTX_OK(ctx, hipMemsetAsync(m.p, 0, slots * sizeof(uint32_t), st));
+    HIP_CTX_OK(ctx, hipStreamSynchronize(st));
+    guide_state = std::move(s);
+    guide_misses = std::move(m);
+    return true;
+}
+
+bool DrawState::guide_attach(rwkv_context * ctx, size_t slot, uint32_t guide, uint32_t state, hipStream_t st) {
+    const bool detach = guide == RWKV_MI_NO_GUIDE;
+    if (detach && !guide_state) { HIP_CTX_OK(ctx, hipStreamSynchronize(st)); guide_of[slot] = guide; return true; }   // (never attached: no words exist)
+    if (!ensure_guides(ctx, st)) return false;
+    const uint32_t words[2] = {detach ? 0u : state, 0u};
+    HIP_CTX_OK(ctx, hipMemcpyAsync(guide_state.p + slot, &words[0], sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIP_CTX_OK(ctx, hipMemcpyAsync(guide_misses.p + slot, &words[1], sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIP_CTX_OK(ctx, hipStreamSynchronize(st));
+    guide_of[slot] = guide;
+    return true;
+}
+
+bool DrawState::guide_words(rwkv_context * ctx, size_t slot, uint32_t * state_out, uint32_t * misses_out, hipStream_t st) {
+    uint32_t words[2] = {0u, 0u};
+    if (guide_of[slot] != RWKV_MI_NO_GUIDE) {
+        HIP_CTX_OK(ctx, hipMemcpyAsync(&words[0], guide_state.p + slot, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_CTX_OK(ctx, hipMemcpyAsync(&words[1], guide_misses.p + slot, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_CTX_OK(ctx, hipStreamSynchronize(st));
+    }
+    if (state_out) *state_out = words[0];
+    if (misses_out) *misses_out = words[1];
+    return true;
+}
+
 static bool on_device(rwkv_context * ctx) { HIP_CTX_OK(ctx, hipSetDevice(ctx->model->device)); return true; }
 
 // what every call of the single-context family starts with
@@ -939,6 +977,47 @@ RWKV_API uint32_t rwkv_mi_decode_generation(struct rwkv_context * ctx) {
 
 }  // extern "C"
 
+// ---- a guide's edges and its table on the device (rwkv_mi_batch_guide_create; model.h) ----
+namespace rwkvmi {
+
+const char * guide_edges_fault(size_t n_vocab, uint32_t n_states, const uint32_t * edge_begin, const uint32_t * edge_tokens, const uint32_t * edge_next) {
+    if (!edge_begin || !edge_tokens || !edge_next) return "edge_begin, edge_tokens or edge_next is NULL";
+    if (n_states == 0 || n_states > RWKV_MI_GUIDE_MAX_STATES) return "n_states is 0 or above RWKV_MI_GUIDE_MAX_STATES";
+    if (edge_begin[0] != 0) return "edge_begin does not start at 0";
+    for (uint32_t s = 0; s < n_states; s++) {
+        if (edge_begin[s + 1] < edge_begin[s]) return "edge_begin decreases";
+        if (edge_begin[s + 1] == edge_begin[s]) return "a state has no edge";
+    }
+    for (uint32_t s = 0; s < n_states; s++)
+        for (size_t e = edge_begin[s]; e < edge_begin[s + 1]; e++) {
+            if (edge_tokens[e] >= n_vocab) return "an edge's token is out of range";
+            if (e > edge_begin[s] && edge_tokens[e] <= edge_tokens[e - 1]) return "a state's tokens are not strictly ascending";
+            if (edge_next[e] >= n_states) return "an edge's next state is out of range";
+        }
+    return nullptr;
+}
+
+hipError_t guide_table_build(DevBuf<uint16_t> & table, size_t n_vocab, uint32_t n_states, const uint32_t * edge_begin, const uint32_t * edge_tokens,
+                             const uint32_t * edge_next, hipStream_t st, bool * alloc_failed) {
+    const size_t n_edges = edge_begin[n_states];
+    DevBuf<uint16_t> fresh;
+    DevBuf<uint32_t> d_begin, d_tokens, d_next;
+    *alloc_failed = true;
+    hipError_t e = grow(want(fresh, (size_t) n_states * n_vocab), want(d_begin, (size_t) n_states + 1), want(d_tokens, n_edges), want(d_next, n_edges));
+    if (e != hipSuccess) return e;
+    *alloc_failed = false;
+    e = hipMemcpyAsync(d_begin.p, edge_begin, ((size_t) n_states + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_tokens.p, edge_tokens, n_edges * sizeof(uint32_t), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_next.p, edge_next, n_edges * sizeof(uint32_t), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) { launch_guide_expand(fresh.p, n_states, (int) n_vocab, d_begin.p, d_tokens.p, d_next.p, st); e = hipGetLastError(); }
+    const hipError_t es = hipStreamSynchronize(st);   // (the edges are read until here, also after a failure)
+    if (e == hipSuccess) e = es;
+    if (e == hipSuccess) table = std::move(fresh);
+    return e;
+}
+
+}  // namespace rwkvmi
+
 // ---------------------------------------------------------------------------------------------------------------
 // Batched decode (rwkv_mi_batch_*): n sequences per pass over the weights. The slots' states are [2][n_slots][state_len] in HBM with a
 // parity per slot; a pass reads slot s at buffer parity[s] and writes buffer parity[s] ^ 1 through a row table ({in, out} per row,
@@ -958,6 +1037,13 @@ struct rwkv_mi_batch {
     PinBuf<SampleRow> h_srows;         // staging, allocated by the first sampling call
     DevBuf<PenaltyRow> d_prows;        // the penalised row table of a call with its pinned staging, allocated by the first call of that family
     PinBuf<PenaltyRow> h_prows;
+    // guided decoding (rwkv_mi_batch_guide_*): the guides' dense tables next[n_states][n_vocab], shared by the slots (which guide a slot has, and
+    // its state and miss words, are the draw state's); the guide rows of a call with their pinned staging, allocated by the first call that names
+    // a guided slot
+    DevBuf<uint16_t> guides[RWKV_MI_GUIDE_MAX];
+    uint32_t guide_states[RWKV_MI_GUIDE_MAX] = {};   // n_states of each (0: the id is free)
+    DevBuf<GuideRow> d_grows;
+    PinBuf<GuideRow> h_grows;
     // ragged passes (rwkv_mi_batch_eval_ragged*): the tables of a call -- segments, the short ones again, seg_of[T], last[n] -- in one device
     // buffer with its pinned staging, grown to the largest call so far; the long segments stay on the host (each is a launch of its own)
     DevBuf<uint8_t> d_seg;
@@ -1137,6 +1223,34 @@ static bool batch_upload_penalty_rows(rwkv_mi_batch * B, const BatchCall & c, bo
     return true;
 }
 
+// ---- guided decoding: which calls see a guide (rwkv_mi_batch_guide_*) ----
+
+// whether a call names a slot with a guide attached (its slots have been checked)
+static bool batch_names_guided(const rwkv_mi_batch * B, const uint32_t * slots, size_t n) {
+    for (size_t i = 0; i < n; i++) if (B->draw.guide_of[slots[i]] != RWKV_MI_NO_GUIDE) return true;
+    return false;
+}
+
+// the greedy family has no sampler to mask: a call of it that names a guided slot is rejected with its other arguments
+static bool batch_check_unguided(rwkv_mi_batch * B, const uint32_t * slots, size_t n, const char * call) {
+    RW_CTX_CHECK(B->ctx, RWKV_ERROR_ARGS, false, !batch_names_guided(B, slots, n),
+                 "%s takes no slot with a guide attached (guided greedy is temperature 0 of the sampled calls)", call);
+    return true;
+}
+
+// the guide rows of the n named slots (after batch_upload*: the stream has been drained, the staging is free): the table of the slot's guide, or
+// NULL for a slot without one, and the slot's two words
+static bool batch_upload_guide_rows(rwkv_mi_batch * B, const BatchCall & c) {
+    const DrawState & d = B->draw;
+    for (size_t i = 0; i < c.n; i++) {
+        const size_t s = c.slots[i];
+        const uint32_t g = d.guide_of[s];
+        B->h_grows.p[i] = GuideRow{g == RWKV_MI_NO_GUIDE ? nullptr : B->guides[g].p, d.guide_state.p + s, d.guide_misses.p + s};
+    }
+    BATCH_HIP_OK(B, hipMemcpyAsync(B->d_grows.p, B->h_grows.p, c.n * sizeof(GuideRow), hipMemcpyHostToDevice, B->run->stream));
+    return true;
+}
+
 // what the calls on one slot's draw state start with
 static bool batch_slot_call(rwkv_mi_batch * B, size_t slot) {
     rwkv_context * ctx = B->ctx;
@@ -1275,15 +1389,21 @@ static bool batch_check_args(rwkv_mi_batch * B, const BatchCall & c, bool u_used
 // the buffers the draw of a call needs
 static bool batch_ensure_draw(rwkv_mi_batch * B, const BatchCall & c) {
     if (c.until && !batch_ensure_stop(B)) return false;
-    return c.draw == Draw::none || batch_ensure_draw_tables(B, c.draw == Draw::penalized);
+    if (c.draw == Draw::none) return true;
+    if (batch_names_guided(B, c.slots, c.n) && !B->d_grows) {   // the guide rows with their pinned staging: on the first guided call
+        const hipError_t e = grow(want(B->d_grows, B->n_slots), want(B->h_grows, B->n_slots));
+        RW_CTX_CHECK(B->ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the guide rows of %zu slots: %s", B->n_slots, hipGetErrorString(e));
+    }
+    return batch_ensure_draw_tables(B, c.draw == Draw::penalized);
 }
 
 // the rows or the segments of a call (that drains the stream first), then its stop words and its sampler table. loop: both row tables
 static bool batch_upload_call(rwkv_mi_batch * B, const BatchCall & c, size_t T, bool loop) {
     if (!(c.lens ? batch_upload_ragged(B, c, T) : batch_upload(B, c, loop ? 2 : 1))) return false;
     if (c.until && !batch_upload_stops(B, c)) return false;
-    if (c.draw == Draw::penalized) return batch_upload_penalty_rows(B, c, loop);
-    return c.draw == Draw::none || batch_upload_params(B, c, loop);
+    if (c.draw == Draw::none) return true;
+    if (batch_names_guided(B, c.slots, c.n) && !batch_upload_guide_rows(B, c)) return false;
+    return c.draw == Draw::penalized ? batch_upload_penalty_rows(B, c, loop) : batch_upload_params(B, c, loop);
 }
 
 // what follows the head of the call's passes (model.h, RowSampler): its draw, the call's whole history and, when it reports, report buffers;
@@ -1291,6 +1411,7 @@ static bool batch_upload_call(rwkv_mi_batch * B, const BatchCall & c, size_t T, 
 static RowSampler batch_sampler(rwkv_mi_batch * B, const BatchCall & c, uint32_t * hist, const RowReport * report) {
     RowSampler s;
     s.draw = c.draw; s.srows = B->d_srows.p; s.prows = B->d_prows.p; s.probs = B->draw.probs.p;
+    if (c.draw != Draw::none && batch_names_guided(B, c.slots, c.n)) s.grows = B->d_grows.p;
     s.hist = hist; s.report = report;
     return s;
 }
@@ -1351,6 +1472,7 @@ static bool batch_loop(rwkv_mi_batch * B, const BatchCall & c, size_t n_tokens, 
     ctx->last_error = RWKV_ERROR_NONE;
     size_t T = 0;
     if (!batch_check_args(B, c, false, &T)) return false;
+    if (c.draw == Draw::none && !batch_check_unguided(B, c.slots, c.n, "the greedy loop")) return false;
     RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, n_tokens > 0, "n_tokens is 0");
     run->print_errors = ctx->print_errors;
     const size_t n = c.n;
@@ -1407,6 +1529,7 @@ static bool batch_until(rwkv_mi_batch * B, const BatchCall & c, uint32_t * token
     rwkv_context * run = B->run;
     size_t T = 0;
     if (!batch_check_args(B, c, false, &T)) return false;
+    if (c.draw == Draw::none && !batch_check_unguided(B, c.slots, c.n, "the greedy loop")) return false;
     run->print_errors = ctx->print_errors;
     const size_t n = c.n, K = loop_block();
     size_t budget = 0;
@@ -1501,7 +1624,7 @@ static bool batch_check_beam(rwkv_mi_batch * B, const BeamCall & c) {
     }
     for (size_t g = 0; g < c.G; g++)
         RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, c.first_tokens[g] < n_vocab, "Token at index %zu (%" PRIu32 ") is out of range (0 .. %zu)", g, c.first_tokens[g], n_vocab - 1);
-    return true;
+    return batch_check_unguided(B, c.slots, c.G * W, "beam search");
 }
 
 // the beam words, the live count's pinned words and the two block events: on the first beam call
@@ -1890,6 +2013,60 @@ RWKV_API bool rwkv_mi_batch_logprobs_store(struct rwkv_mi_batch * B, size_t stri
     B->ctx->last_error = RWKV_ERROR_NONE;
     BATCH_HIP_OK(B, hipSetDevice(B->ctx->model->device));
     return report_store(B->ctx, B->lp, B->run->stream, stride, chosen_out, top_ids_out, top_logprobs_out);
+}
+
+// ---- guided decoding (include/rwkv_mi355x.h): the guides of a batch and the guide words of its slots ----
+
+RWKV_API bool rwkv_mi_batch_guide_create(struct rwkv_mi_batch * B, uint32_t n_states, const uint32_t * edge_begin, const uint32_t * edge_tokens,
+                                         const uint32_t * edge_next, uint32_t * guide_out) {
+    rwkv_context * ctx = B->ctx;
+    ctx->last_error = RWKV_ERROR_NONE;
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, guide_out != nullptr, "guide_out is NULL");
+    const size_t n_vocab = (size_t) ctx->model->n_vocab();
+    const char * fault = guide_edges_fault(n_vocab, n_states, edge_begin, edge_tokens, edge_next);
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, fault == nullptr, "bad guide: %s", fault);
+    uint32_t id = 0;
+    while (id < RWKV_MI_GUIDE_MAX && B->guide_states[id]) id++;
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, id < RWKV_MI_GUIDE_MAX, "the batch already holds %d guides", RWKV_MI_GUIDE_MAX);
+    BATCH_HIP_OK(B, hipSetDevice(ctx->model->device));
+    bool alloc_failed = false;
+    const hipError_t e = guide_table_build(B->guides[id], n_vocab, n_states, edge_begin, edge_tokens, edge_next, B->run->stream, &alloc_failed);
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, false, !alloc_failed, "cannot allocate the table of a guide of %" PRIu32 " states (%zu bytes): %s", n_states,
+                 (size_t) n_states * n_vocab * sizeof(uint16_t), hipGetErrorString(e));
+    BATCH_HIP_OK(B, e);
+    B->guide_states[id] = n_states;
+    *guide_out = id;
+    return true;
+}
+
+RWKV_API bool rwkv_mi_batch_guide_free(struct rwkv_mi_batch * B, uint32_t guide) {
+    rwkv_context * ctx = B->ctx;
+    ctx->last_error = RWKV_ERROR_NONE;
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, guide < RWKV_MI_GUIDE_MAX && B->guide_states[guide], "%" PRIu32 " names no guide", guide);
+    for (size_t s = 0; s < B->n_slots; s++)
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, B->draw.guide_of[s] != guide, "guide %" PRIu32 " is still attached to slot %zu", guide, s);
+    BATCH_HIP_OK(B, hipSetDevice(ctx->model->device));
+    BATCH_HIP_OK(B, hipStreamSynchronize(B->run->stream));
+    B->guides[guide].reset();
+    B->guide_states[guide] = 0;
+    return true;
+}
+
+RWKV_API bool rwkv_mi_batch_guide_attach(struct rwkv_mi_batch * B, size_t slot, uint32_t guide, uint32_t state) {
+    if (!batch_slot_call(B, slot)) return false;
+    rwkv_context * ctx = B->ctx;
+    if (guide != RWKV_MI_NO_GUIDE) {
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, guide < RWKV_MI_GUIDE_MAX && B->guide_states[guide], "%" PRIu32 " names no guide", guide);
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, state < B->guide_states[guide], "state %" PRIu32 " is out of range (guide %" PRIu32 " has %" PRIu32 " states)", state, guide,
+                     B->guide_states[guide]);
+    }
+    return on_device(ctx) && B->draw.guide_attach(ctx, slot, guide, state, B->run->stream);
+}
+
+RWKV_API bool rwkv_mi_batch_guide_state(struct rwkv_mi_batch * B, size_t slot, uint32_t * guide_out, uint32_t * state_out, uint32_t * misses_out) {
+    if (!batch_slot_call(B, slot)) return false;
+    if (guide_out) *guide_out = B->draw.guide_of[slot];
+    return on_device(B->ctx) && B->draw.guide_words(B->ctx, slot, state_out, misses_out, B->run->stream);
 }
 
 }  // extern "C"

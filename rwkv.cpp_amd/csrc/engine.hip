@@ -828,8 +828,14 @@ void launch_row_sampler(rwkv_context * ctx, const RowSampler & s, int64_t rows) 
     uint32_t * hist = s.hist ? s.hist + at : nullptr;
     const uint32_t * live = s.stop ? s.stop->t.live : nullptr;   // (rwkv_mi_batch_decode_until: everything but the stop test runs behind the live words)
     switch (s.draw) {
-        case Draw::penalized: launch_pen_sample_rows(logits, rows, n_vocab, s.prows, s.probs, tokens, hist, live, ctx->stream); break;
-        case Draw::sample:    launch_sample_rows(logits, rows, n_vocab, s.srows, s.probs, tokens, hist, live, ctx->stream); break;
+        case Draw::penalized:
+            if (s.grows) launch_guided_pen_sample_rows(logits, rows, n_vocab, s.prows, s.grows, s.probs, tokens, hist, live, ctx->stream);
+            else launch_pen_sample_rows(logits, rows, n_vocab, s.prows, s.probs, tokens, hist, live, ctx->stream);
+            break;
+        case Draw::sample:
+            if (s.grows) launch_guided_sample_rows(logits, rows, n_vocab, s.srows, s.grows, s.probs, tokens, hist, live, ctx->stream);
+            else launch_sample_rows(logits, rows, n_vocab, s.srows, s.probs, tokens, hist, live, ctx->stream);
+            break;
         case Draw::none:
             if (live) launch_argmax_live(logits, rows, n_vocab, tokens, hist, live, ctx->stream);
             else launch_argmax(logits, rows, n_vocab, tokens, hist, ctx->stream);

@@ -131,6 +131,24 @@ void launch_pen_sample(const float * logits, int n, float temperature, float top
                        float * probs, uint32_t * out_token, uint32_t * hist, int hist_pos, hipStream_t st);
 void launch_pen_sample_rows(const float * logits, int64_t rows, int n, const PenaltyRow * table, float * probs, uint32_t * tokens, uint32_t * hist,
                             const uint32_t * live, hipStream_t st);
+// The guided forms (rwkv_mi_batch_guide_*): a parallel table gives row r the dense table of its guide -- next[n_states][n], GUIDE_DEAD where
+// the transition is dead; NULL: the row has no guide and draws as the unguided kernel does -- and its slot's state and miss words. A guided
+// row in state s reads -inf for token j where next[s][j] is dead, the value of its draw elsewhere; thread 0 then moves the state to
+// next[s][token], or counts a miss when that is dead.
+constexpr uint16_t GUIDE_DEAD = 0xFFFF;
+struct GuideRow { const uint16_t * next; uint32_t * state; uint32_t * misses; };
+void launch_guided_sample_rows(const float * logits, int64_t rows, int n, const SampleRow * table, const GuideRow * guides, float * probs, uint32_t * tokens,
+                               uint32_t * hist, const uint32_t * live, hipStream_t st);
+void launch_guided_pen_sample_rows(const float * logits, int64_t rows, int n, const PenaltyRow * table, const GuideRow * guides, float * probs, uint32_t * tokens,
+                                   uint32_t * hist, const uint32_t * live, hipStream_t st);
+// next[n_states][n_vocab] from the edges in CSR form on the device (checked by the caller: tokens < n_vocab and distinct per state, next < n_states)
+void launch_guide_expand(uint16_t * next, uint32_t n_states, int n_vocab, const uint32_t * edge_begin, const uint32_t * edge_tokens, const uint32_t * edge_next,
+                         hipStream_t st);
+// api.cpp: the rules of rwkv_mi_batch_guide_create on a guide's edges (nullptr: they hold; else which one does not), and the table built on
+// the device from edges that passed: allocated, expanded, the stream drained. A failure leaves `table` as it was
+const char * guide_edges_fault(size_t n_vocab, uint32_t n_states, const uint32_t * edge_begin, const uint32_t * edge_tokens, const uint32_t * edge_next);
+hipError_t guide_table_build(DevBuf<uint16_t> & table, size_t n_vocab, uint32_t n_states, const uint32_t * edge_begin, const uint32_t * edge_tokens,
+                             const uint32_t * edge_next, hipStream_t st, bool * alloc_failed);
 // A row's stop parameters and where its sequences start in the call's flat tables: its lengths at seq_lens[seq0 ..], its tokens at seq_tokens[tok0 ..].
 struct StopRow { uint32_t max_tokens, n_seqs, seq0, tok0; };
 // The device words of a call: per row its live word (1 until it retires), its length and its reason (the index of the matching sequence, or
@@ -166,7 +184,7 @@ void launch_bias_scatter(float * bias, const uint32_t * ids, const float * value
 // occurrence table and the bias table of the penalised draw, and whether a bias is set. A context holds one of 1 slot, a batch one of n_slots.
 // Nothing is allocated by init(): the counters come with ensure_counters (a batch calls it when it is created, so its counters exist and are
 // zero from then on; a context gets its counter with its first draw or seek), the scratch with ensure_sampler, the two tables -- zeroed; a
-// table that could not be zeroed is not kept -- with the first call of the penalised family. Every growth is one grow(want(...)) decision: a
+// table that could not be zeroed is not kept -- with the first call of the penalised family, the guide words with the first attach. Every growth is one grow(want(...)) decision: a
 // call that fails leaves every buffer as it was. No stream is kept (rwkv_mi_set_stream can change a context's): each operation takes the
 // stream it works on and the context its errors are reported on -- RWKV_ERROR_ALLOC for memory, RWKV_ERROR_GRAPH for any other HIP error.
 // The operations on a slot's tables drain the stream before they return.
@@ -177,8 +195,13 @@ struct DrawState {
     DevBuf<uint32_t> counts;               // [slots][n_vocab]
     DevBuf<float>    bias;                 // [slots][n_vocab]
     std::vector<uint8_t> has_bias;         // [slots]: a bias has been set and not cleared
+    // the guide words (rwkv_mi_batch_guide_*): the guide attached to each slot (the host's: RWKV_MI_NO_GUIDE for none) and, on the device, the
+    // slot's current state and miss counter -- zeroed, allocated by the first attach
+    std::vector<uint32_t> guide_of;        // [slots]
+    DevBuf<uint32_t> guide_state;          // [slots]
+    DevBuf<uint32_t> guide_misses;         // [slots]
 
-    void init(size_t n_slots, size_t vocab) { slots = n_slots; n_vocab = vocab; has_bias.assign(n_slots, 0); }
+    void init(size_t n_slots, size_t vocab) { slots = n_slots; n_vocab = vocab; has_bias.assign(n_slots, 0); guide_of.assign(n_slots, RWKV_MI_NO_GUIDE); }
     unsigned long long * counter(size_t slot) const { return counters.p + slot; }
     uint32_t * counts_of(size_t slot) const { return counts.p + slot * n_vocab; }
     const float * bias_of(size_t slot) const { return has_bias[slot] ? bias.p + slot * n_vocab : nullptr; }   // NULL: none is set
@@ -191,6 +214,10 @@ struct DrawState {
     bool counts_add(rwkv_context * ctx, size_t slot, const uint32_t * tokens, size_t n, hipStream_t st);   // (arguments checked: check_count_tokens)
     bool counts_store(rwkv_context * ctx, size_t slot, uint32_t * counts_out, hipStream_t st);
     bool bias_set(rwkv_context * ctx, size_t slot, const uint32_t * ids, const float * values, size_t n, hipStream_t st);   // n == 0: cleared (check_bias)
+    bool ensure_guides(rwkv_context * ctx, hipStream_t st);    // the two guide words per slot
+    // attaches `guide` in `state` (checked by the caller) or, with RWKV_MI_NO_GUIDE, detaches; the slot's miss counter starts from 0 either way
+    bool guide_attach(rwkv_context * ctx, size_t slot, uint32_t guide, uint32_t state, hipStream_t st);
+    bool guide_words(rwkv_context * ctx, size_t slot, uint32_t * state_out, uint32_t * misses_out, hipStream_t st);   // (0, 0 without a guide)
 };
 
 // Loads [layer_begin, layer_end) of the file (layer_end == UINT32_MAX: all layers) onto the current HIP device.
@@ -333,7 +360,8 @@ rwkv_context * batch_context_create(Model * m, int64_t max_rows);
 void batch_context_destroy(rwkv_context * c);
 // What follows the head of a batch pass over `rows` rows (launch_row_sampler), described once: row r's token goes to ctx->d_tokens.p[r].
 //   draw    which choice is made: the greedy argmax (none), the sampler (sample: srows, launch_sample_rows) or the penalised sampler
-//           (penalized: prows, launch_pen_sample_rows); probs: the samplers' scratch
+//           (penalized: prows, launch_pen_sample_rows); probs: the samplers' scratch; grows (NULL: no named slot has a guide): the guide rows,
+//           with which the guided form of either sampler is launched instead
 //   hist, report, step   the call's WHOLE history [steps][rows] and report buffers (chosen [steps][rows], ids / vals [steps][rows][top_n]), either
 //           may be NULL, and the step of the call this pass is: the step's slot of each is written. A single pass is step 0
 //   stop    the pass is a step of rwkv_mi_batch_decode_until: the choice and the report run behind the live words and launch_stop_rows follows them
@@ -348,6 +376,7 @@ struct RowSampler {
     Draw draw = Draw::none;
     const SampleRow * srows = nullptr;
     const PenaltyRow * prows = nullptr;
+    const GuideRow * grows = nullptr;   // the call names a guided slot: the guided form of the sampler runs on this parallel table
     float * probs = nullptr;
     uint32_t * hist = nullptr;
     const RowReport * report = nullptr;

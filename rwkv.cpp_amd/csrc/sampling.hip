@@ -17,6 +17,8 @@
 // optional bias table, and counts the chosen token afterwards.
 // rwkv_mi_batch_decode_until: the two row samplers take a per-row live word (live; NULL everywhere else), and k_stop_rows retires a
 // row -- stop sequence or budget -- by rewriting its entries of the two row tables on the device.
+// Guided draws (k_guided_sample_rows / k_guided_pen_sample_rows, rwkv_mi_batch_guide_*): a row whose slot has a guide attached, in state s,
+// reads -inf instead of the value above wherever the guide's next(s, j) is dead, and moves its state to next(s, token) afterwards.
 // The logits themselves are never written.
 #include "kdev.h"
 #include "model.h"
@@ -77,6 +79,30 @@ struct PenalisedLogits {
     }
     __device__ __forceinline__ float again(int j, const ProbVec & pr) const { return pr.get(j); }
 };
+
+// The guided source (k_guided_sample_rows / k_guided_pen_sample_rows): the value the row's draw would read anyway -- Inner is PlainLogits or
+// PenalisedLogits -- with the mask applied LAST: -inf where the guide's transition from the row's state is dead. nx: the thread's chunk of
+// the state's row of the dense table, contiguous like its chunk of the count table; NULL: the row has no guide and reads what Inner reads.
+// first() stashes the value as the penalised source does, so again() neither reads the table a second time nor derives the value again.
+template <class Inner>
+struct GuidedLogits {
+    Inner in; const uint16_t * nx /* may be NULL */;
+    __device__ __forceinline__ float first(int j, const ProbVec & pr) const {
+        float a = in.first(j, pr);
+        if (nx && nx[j] == GUIDE_DEAD) a = -INFINITY;
+        pr.set(j, a);
+        return a;
+    }
+    __device__ __forceinline__ float again(int j, const ProbVec & pr) const { return pr.get(j); }
+};
+
+// What thread 0 does to a guided row's words after the draw (where the penalised rows count the token): the state moves along the picked
+// token's transition; a dead pick -- all-NaN logits, or a caller's -inf bias on every allowed token -- leaves it and counts a miss. The
+// state word is only ever written from the table (or by rwkv_mi_batch_guide_attach, which checks it), so it always indexes inside it.
+__device__ __forceinline__ void guide_advance(const GuideRow & g, const uint16_t * state_row, int pick) {
+    const uint16_t to = state_row[pick];
+    if (to != GUIDE_DEAD) *g.state = to; else *g.misses += 1u;
+}
 
 // One body, two entry points (the convention of the recurrence kernels and their row forms): k_sample hands it its arguments,
 // k_sample_rows the pointers and parameters of row blockIdx.x. Everything the workgroup does -- chunks, summation order, bisection, scan,
@@ -244,6 +270,54 @@ __global__ __launch_bounds__(1024) void k_pen_sample_rows(const float * __restri
     if (threadIdx.x == 0 && row.record) row.count[pick] += 1u;
 }
 
+// The guided entry points (rwkv_mi_batch_guide_*): the two row forms above with a parallel table of guide rows. Row r with a guide reads
+// its slot's state word s -- every thread, before the body's first barrier; thread 0 writes it after the last -- and draws through
+// GuidedLogits on row s of the guide's table; a row without one (next == NULL) picks, bit for bit, what the unguided kernel picks.
+// live: as k_sample_rows -- a retired row does not advance its guide either.
+__global__ __launch_bounds__(1024) void k_guided_sample_rows(const float * __restrict__ logits, int n, const SampleRow * __restrict__ table,
+                                                             const GuideRow * __restrict__ guides, float * __restrict__ probs, size_t stride,
+                                                             uint32_t * __restrict__ tokens, uint32_t * __restrict__ hist, const uint32_t * __restrict__ live) {
+    const size_t r = blockIdx.x;
+    if (live && !live[r]) return;
+    const rwkv_mi_sample_params p = table[r].p;
+    const GuideRow g = guides[r];
+    const uint16_t * srow = g.next ? g.next + (size_t) *g.state * (size_t) n : nullptr;
+    const float * lg = logits + r * (size_t) n;
+    const int pick = sample_body([=](int i0) { return GuidedLogits<PlainLogits>{PlainLogits{lg + i0}, srow ? srow + i0 : nullptr}; },
+                                 n, p.temperature, p.top_p, p.u, p.seed, table[r].counter, probs + r * stride, tokens + r, hist ? hist + r : nullptr);
+    if (threadIdx.x == 0 && srow) guide_advance(g, srow, pick);
+}
+
+__global__ __launch_bounds__(1024) void k_guided_pen_sample_rows(const float * __restrict__ logits, int n, const PenaltyRow * __restrict__ table,
+                                                                 const GuideRow * __restrict__ guides, float * __restrict__ probs, size_t stride,
+                                                                 uint32_t * __restrict__ tokens, uint32_t * __restrict__ hist, const uint32_t * __restrict__ live) {
+    const size_t r = blockIdx.x;
+    if (live && !live[r]) return;
+    const PenaltyRow row = table[r];
+    const GuideRow g = guides[r];
+    const uint16_t * srow = g.next ? g.next + (size_t) *g.state * (size_t) n : nullptr;
+    const float * lg = logits + r * (size_t) n;
+    const int pick = sample_body([=](int i0) {
+                                     return GuidedLogits<PenalisedLogits>{PenalisedLogits{lg + i0, row.count + i0, row.bias ? row.bias + i0 : nullptr, row.presence, row.frequency},
+                                                                          srow ? srow + i0 : nullptr};
+                                 },
+                                 n, row.p.temperature, row.p.top_p, row.p.u, row.p.seed, row.counter, probs + r * stride, tokens + r, hist ? hist + r : nullptr);
+    if (threadIdx.x == 0 && row.record) row.count[pick] += 1u;
+    if (threadIdx.x == 0 && srow) guide_advance(g, srow, pick);
+}
+
+// rwkv_mi_batch_guide_create: the dense table next[n_states][n_vocab] from the CSR edges, one workgroup per state: the dead fill of the
+// state's row, then -- behind a barrier -- one 2-byte store per edge. A state's tokens are distinct, so no two stores meet.
+__global__ __launch_bounds__(256) void k_guide_expand(uint16_t * __restrict__ next, int n_vocab, const uint32_t * __restrict__ edge_begin,
+                                                      const uint32_t * __restrict__ edge_tokens, const uint32_t * __restrict__ edge_next) {
+    uint16_t * row = next + (size_t) blockIdx.x * (size_t) n_vocab;
+    for (int j = threadIdx.x; j < n_vocab; j += 256) row[j] = GUIDE_DEAD;
+    __syncthreads();
+    const uint32_t e1 = edge_begin[blockIdx.x + 1];
+    for (size_t e = (size_t) edge_begin[blockIdx.x] + threadIdx.x; e < e1; e += 256)
+        if (edge_tokens[e] < (uint32_t) n_vocab) row[edge_tokens[e]] = (uint16_t) edge_next[e];
+}
+
 // The stop test of rwkv_mi_batch_decode_until, one thread per row, after the draw of pass `step` of the call (hist: [step][n], the tokens this
 // call has emitted). A live row retires when its emitted tokens end with one of its stop sequences (the lowest index wins) or when step + 1
 // is its budget: its length and reason are written, its live word cleared, the live count taken down by one -- and BOTH row tables get the
@@ -311,6 +385,21 @@ void launch_pen_sample(const float * logits, int n, float temperature, float top
 void launch_pen_sample_rows(const float * logits, int64_t rows, int n, const PenaltyRow * table, float * probs, uint32_t * tokens, uint32_t * hist,
                             const uint32_t * live, hipStream_t st) {
     hipLaunchKernelGGL(k_pen_sample_rows, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, table, probs, sample_scratch_floats(n), tokens, hist, live);
+}
+
+void launch_guided_sample_rows(const float * logits, int64_t rows, int n, const SampleRow * table, const GuideRow * guides, float * probs, uint32_t * tokens,
+                               uint32_t * hist, const uint32_t * live, hipStream_t st) {
+    hipLaunchKernelGGL(k_guided_sample_rows, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, table, guides, probs, sample_scratch_floats(n), tokens, hist, live);
+}
+
+void launch_guided_pen_sample_rows(const float * logits, int64_t rows, int n, const PenaltyRow * table, const GuideRow * guides, float * probs, uint32_t * tokens,
+                                   uint32_t * hist, const uint32_t * live, hipStream_t st) {
+    hipLaunchKernelGGL(k_guided_pen_sample_rows, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, table, guides, probs, sample_scratch_floats(n), tokens, hist, live);
+}
+
+void launch_guide_expand(uint16_t * next, uint32_t n_states, int n_vocab, const uint32_t * edge_begin, const uint32_t * edge_tokens, const uint32_t * edge_next,
+                         hipStream_t st) {
+    hipLaunchKernelGGL(k_guide_expand, dim3(n_states), dim3(256), 0, st, next, n_vocab, edge_begin, edge_tokens, edge_next);
 }
 
 void launch_stop_rows(const StopTables & t, int64_t rows, const uint32_t * hist, uint32_t step, RowState * used, RowState * other, hipStream_t st) {

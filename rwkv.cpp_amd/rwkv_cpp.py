@@ -21,8 +21,10 @@ LIB_PATH = os.path.join(PKG_DIR, os.environ.get("RWKV_LIB_DIR", "lib"), "librwkv
 HOOKS_LIB_PATH = os.path.join(PKG_DIR, os.environ.get("RWKV_LIB_DIR", "lib"), "librwkv_testhooks.so")
 # tests/ only: the same objects + csrc/testhooks_sample.cpp (include/rwkv_testhooks_sample.h): the sampler kernel on caller-supplied logits
 SAMPLE_HOOKS_LIB_PATH = os.path.join(PKG_DIR, os.environ.get("RWKV_LIB_DIR", "lib"), "librwkv_testhooks_sample.so")
+# tests/ only: the same objects + csrc/testhooks_guide.cpp (include/rwkv_testhooks_guide.h): the guided sampler kernels on caller-supplied logits
+GUIDE_HOOKS_LIB_PATH = os.path.join(PKG_DIR, os.environ.get("RWKV_LIB_DIR", "lib"), "librwkv_testhooks_guide.so")
 
-QUANTIZED_FORMAT_NAMES = ("Q4_0", "Q4_1", "Q5_0", "Q5_1", "Q8_0")
+QUANTIZED_FORMAT_NAMES =("Q4_0", "Q4_1", "Q5_0", "Q5_1", "Q8_0")
 PENALTY_SYMBOLS = ("rwkv_mi_batch_counts_reset", "rwkv_mi_batch_counts_add", "rwkv_mi_batch_counts_store", "rwkv_mi_batch_logit_bias_set",
                    "rwkv_mi_batch_eval_sample_penalized", "rwkv_mi_batch_eval_ragged_sample_penalized", "rwkv_mi_batch_decode_sample_penalized",
                    "rwkv_mi_counts_reset", "rwkv_mi_counts_add", "rwkv_mi_counts_store", "rwkv_mi_logit_bias_set", "rwkv_mi_rng_seek",
@@ -32,7 +34,11 @@ UNTIL_SYMBOLS = ("rwkv_mi_batch_decode_until", "rwkv_mi_batch_last_loop_passes")
 LOGPROBS_SYMBOLS = ("rwkv_mi_batch_set_logprobs", "rwkv_mi_batch_logprobs_shape", "rwkv_mi_batch_logprobs_store",
                     "rwkv_mi_set_logprobs", "rwkv_mi_logprobs_shape", "rwkv_mi_logprobs_store")
 BEAM_SYMBOLS = ("rwkv_mi_batch_state_copy", "rwkv_mi_batch_decode_beam")
-COPY_STATE, COPY_COUNTER, COPY_COUNTS, COPY_BIAS = 1, 2, 4, 8   # RWKV_MI_COPY_*: the bits of rwkv_mi_batch_state_copy's `what`
+GUIDE_SYMBOLS = ("rwkv_mi_batch_guide_create", "rwkv_mi_batch_guide_free", "rwkv_mi_batch_guide_attach", "rwkv_mi_batch_guide_state")
+GUIDE_MAX = 16              # RWKV_MI_GUIDE_MAX: guides per batch
+GUIDE_MAX_STATES = 65535    # RWKV_MI_GUIDE_MAX_STATES: states per guide
+NO_GUIDE = 0xFFFFFFFF       # RWKV_MI_NO_GUIDE: a slot without a guide
+COPY_STATE, COPY_COUNTER, COPY_COUNTS, COPY_BIAS = 1, 2, 4, 8  # RWKV_MI_COPY_*: the bits of rwkv_mi_batch_state_copy's `what`
 TOP_MAX = 20             # RWKV_MI_TOP_MAX: the most alternatives a report holds per token, and the widest beam
 NO_TARGET = 0xFFFFFFFF   # RWKV_MI_NO_TARGET: a position that is not scored (its log-prob is 0)
 NO_TOKEN = 0xFFFFFFFF    # RWKV_MI_NO_TOKEN: no token (past a row's length), no stop sequence (the budget ended the row)
@@ -274,6 +280,18 @@ class RWKVSharedLibrary:
                                                     ctypes.POINTER(ctypes.c_double), P_FLOAT, P_FLOAT]
             for name in BEAM_SYMBOLS:
                 getattr(L, name).restype = ctypes.c_bool
+        # guided decoding: token automata that mask the device sampler per slot
+        if hasattr(L, "rwkv_mi_batch_guide_create"):   # (absent from older A/B builds loaded through RWKV_LIB_DIR)
+            L.rwkv_mi_batch_guide_create.argtypes = [c_batch, ctypes.c_uint32, P_UINT32, P_UINT32, P_UINT32, P_UINT32]
+            L.rwkv_mi_batch_guide_free.argtypes = [c_batch, ctypes.c_uint32]
+            L.rwkv_mi_batch_guide_attach.argtypes = [c_batch, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32]
+            L.rwkv_mi_batch_guide_state.argtypes = [c_batch, ctypes.c_size_t, P_UINT32, P_UINT32, P_UINT32]
+            for name in GUIDE_SYMBOLS:
+                getattr(L, name).restype = ctypes.c_bool
+        if hasattr(L, "rwkv_mi_test_guided_rows"):   # (librwkv_testhooks_guide.so only)
+            L.rwkv_mi_test_guided_rows.argtypes = [P_FLOAT, ctypes.c_int64, ctypes.c_int64, ctypes.c_uint32, P_UINT32, P_UINT32, P_UINT32, P_UINT32, P_UINT32, P_UINT32,
+                                                   P_SAMPLE_PARAMS, P_PENALTY_PARAMS, P_UINT32, P_FLOAT, ctypes.POINTER(ctypes.c_uint64), P_UINT32, P_UINT32, P_UINT32]
+            L.rwkv_mi_test_guided_rows.restype = ctypes.c_bool
         if hasattr(L, "rwkv_test_beam_step"):   # (librwkv_testhooks_sample.so only)
             L.rwkv_test_beam_step.argtypes = [P_FLOAT, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_double), P_UINT32, ctypes.c_uint32, P_UINT32,
                                               ctypes.c_uint32, P_UINT32, P_UINT32, P_FLOAT, ctypes.POINTER(ctypes.c_double), P_UINT32]
@@ -749,6 +767,18 @@ def stop_params(n: int, max_tokens, stop=None):
     return arr, _u32(lens).reshape(-1), _u32(toks).reshape(-1)
 
 
+def guide_edges(edges):
+    """A guide in the CSR form of rwkv_mi_batch_guide_create from one {token: next_state} dict per state: (edge_begin [n_states + 1],
+    edge_tokens, edge_next), each state's tokens ascending."""
+    begin, toks, nxt = [0], [], []
+    for e in edges:
+        for t in sorted(int(k) for k in e):
+            toks.append(t)
+            nxt.append(int(e[t]))
+        begin.append(len(toks))
+    return _u32(begin).reshape(-1), _u32(toks).reshape(-1), _u32(nxt).reshape(-1)
+
+
 def _bias_arrays(bias: dict):
     ids = _u32(list(bias.keys())).reshape(-1)
     values = np.ascontiguousarray(np.asarray(list(bias.values()), dtype=np.float64).astype(np.float32)).reshape(-1)
@@ -1012,6 +1042,41 @@ class RWKVBatch:
                                                  scores.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.cast(_ptr(lps), P_FLOAT), ctypes.byref(ms)):
             self._fail("rwkv_mi_batch_decode_beam")
         return tokens, lens, scores, lps, float(ms.value)
+
+    # --- guided decoding: token automata that mask the device sampler per slot (include/rwkv_mi355x.h) ---
+
+    def create_guide(self, edges) -> int:
+        """A guide from one {token: next_state} dict per state (every state allows at least one token): its id. The batch holds up to GUIDE_MAX
+        guides, shared by its slots."""
+        begin, toks, nxt = guide_edges(edges)
+        out = ctypes.c_uint32(NO_GUIDE)
+        if not self._L.rwkv_mi_batch_guide_create(self._ptr, begin.size - 1, begin.ctypes.data_as(P_UINT32), toks.ctypes.data_as(P_UINT32),
+                                                  nxt.ctypes.data_as(P_UINT32), ctypes.byref(out)):
+            self._fail("rwkv_mi_batch_guide_create")
+        return int(out.value)
+
+    def free_guide(self, guide: int) -> None:
+        """Releases a guide that no slot has attached."""
+        if not self._L.rwkv_mi_batch_guide_free(self._ptr, guide):
+            self._fail("rwkv_mi_batch_guide_free")
+
+    def attach_guide(self, slot: int, guide: int, state: int = 0) -> None:
+        """From now on the sampled and penalised calls draw the slot's tokens under `guide`, starting in `state`; the slot's miss counter
+        starts from 0. The greedy loops and decode_beam reject a slot with a guide."""
+        if not self._L.rwkv_mi_batch_guide_attach(self._ptr, slot, guide, state):
+            self._fail("rwkv_mi_batch_guide_attach")
+
+    def detach_guide(self, slot: int) -> None:
+        if not self._L.rwkv_mi_batch_guide_attach(self._ptr, slot, NO_GUIDE, 0):
+            self._fail("rwkv_mi_batch_guide_attach")
+
+    def guide_state(self, slot: int) -> Tuple[int, int, int]:
+        """(guide, state, misses) of a slot; guide is NO_GUIDE for a slot without one. misses: the draws whose token the guide did not allow
+        (all-NaN logits, or a bias of -inf on every allowed token)."""
+        g, s, m = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_uint32(0)
+        if not self._L.rwkv_mi_batch_guide_state(self._ptr, slot, ctypes.byref(g), ctypes.byref(s), ctypes.byref(m)):
+            self._fail("rwkv_mi_batch_guide_state")
+        return int(g.value), int(s.value), int(m.value)
 
     # --- the report: log-probs and top-N alternatives of every emitted token (include/rwkv_mi355x.h) ---
 

@@ -45,6 +45,15 @@ top_n of the list; records also go to --out:
   mode logprobs_host     the way without it: RWKVBatch.eval with the logits to the host, then a float64 log-softmax and np.argpartition for
                          the largest top_n of the list on each row, the token taken as its argmax; host clock around the loop
 
+--sample --guide times the sampled loop (temperature 1.0, top-p 0.8, seed = row) three ways in the same process, --tokens steps, the smallest of
+--reps runs (the plain loop also with its largest run: the run-to-run spread of the box), under a guide of 4 states that each allow a random half
+of the vocabulary; records also go to --out:
+  mode guide_plain    (a) rwkv_mi_batch_decode_sample with no guide attached, HIP events around the device loop -- the only arm when the library
+                      loaded through RWKV_LIB_DIR is a build without guides
+  mode guide_device   (b) the same loop with the guide attached to every row; guide_ms_per_step is its step minus (a)'s
+  mode guide_host     (c) the way without guides: per token and row rwkv_mi_batch_logit_bias_set with -inf on every forbidden id, one
+                      rwkv_mi_batch_eval_sample_penalized pass, the token read back, the automaton stepped on the host; host clock
+
 --beam W[,W...] times rwkv_mi_batch_decode_beam (no end tokens, --tokens steps) for every width of the list, G = rows // W groups at the largest
 row count of --n, HIP events around each device loop, the smallest of --reps runs; records also go to --out:
   mode beam        ms per step of the beam loop beside the greedy loop's at the same row count from the same run, and their difference
@@ -367,6 +376,93 @@ def beam(pkg, m, args):
         sink.close()
 
 
+def guide(pkg, m, args):
+    import ctypes
+
+    import numpy as np
+    V = m.n_vocab
+    L = m._library.library
+    sink = open(args.out, "a") if args.out else None
+    steps = args.tokens
+    have_guides = hasattr(L, "rwkv_mi_batch_guide_create")   # (an older build loaded through RWKV_LIB_DIR: the plain loop only)
+    n_states = 4
+
+    def emit(rec):
+        rec.update({"steps": steps, "reps": args.reps, "temperature": 1.0, "top_p": 0.8, "config": args.config, "dtype": args.dtype})
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if sink:
+            sink.write(line + "\n")
+            sink.flush()
+
+    # a guide of a few states, each allowing a random half of the vocabulary; for the host-driven loop, per state, the ids it forbids with
+    # their -inf values as rwkv_mi_batch_logit_bias_set takes them, and the dense transition table to step on the host
+    rng = np.random.default_rng(7)
+    allowed = [np.flatnonzero(rng.random(V) < 0.5) for _ in range(n_states)]
+    nxt = np.full((n_states, V), 0xFFFF, dtype=np.uint16)
+    for s, a in enumerate(allowed):
+        nxt[s, a] = rng.integers(0, n_states, size=a.size)
+    off_ids = [np.ascontiguousarray(np.flatnonzero(nxt[s] == 0xFFFF).astype(np.uint32)) for s in range(n_states)]
+    off_vals = [np.full(ids.size, -np.inf, dtype=np.float32) for ids in off_ids]
+    P_U32, P_F32 = ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_float)
+
+    ns = [int(x) for x in args.n.split(",")]
+    b = pkg.RWKVBatch(m, max(ns))
+    gid = b.create_guide([{int(t): int(nxt[s, t]) for t in a} for s, a in enumerate(allowed)]) if have_guides else None
+    for n in ns:
+        slots = list(range(n))
+        first = [(7 * i + 1) % V for i in slots]
+
+        def runs(run, guided):
+            out = []
+            for k in range(args.reps + 1):   # (run 0: warm-up -- buffers of the first call, tile-major weight images)
+                for s in slots:
+                    b.state_load(s, None)
+                    if have_guides:
+                        b.attach_guide(s, gid if guided else pkg.NO_GUIDE, s % n_states if guided else 0)
+                out.append(run())
+            return out[1:]
+
+        plain = runs(lambda: b.decode_sample(slots, first, steps, 1.0, 0.8, slots)[1], False)
+        plain_ms = min(plain)
+        emit({"mode": "guide_plain", "n": n, "ms_per_step": round(plain_ms / steps, 4), "ms_per_step_max": round(max(plain) / steps, 4),
+              "spread": round(max(plain) / plain_ms - 1.0, 4), "guides_in_library": have_guides})
+        if not have_guides:
+            continue
+        dev_ms = min(runs(lambda: b.decode_sample(slots, first, steps, 1.0, 0.8, slots)[1], True))
+        assert all(b.guide_state(s)[2] == 0 for s in slots), "a guided row missed"
+        emit({"mode": "guide_device", "n": n, "ms_per_step": round(dev_ms / steps, 4), "plain_ms_per_step": round(plain_ms / steps, 4),
+              "guide_ms_per_step": round((dev_ms - plain_ms) / steps, 4), "guided_over_plain": round(dev_ms / plain_ms, 4), "states": n_states,
+              "table_bytes": int(nxt.nbytes)})
+
+        def host():
+            # the way without guides: before every token each row's mask goes up as a bias of -inf, one synchronising pass samples, the token
+            # comes back and the automaton steps on the host
+            state = [s % n_states for s in slots]
+            toks = list(first)
+            for s in slots:
+                b.rng_seek(s, 0)
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                for i, s in enumerate(slots):
+                    ids, vals = off_ids[state[i]], off_vals[state[i]]
+                    if not L.rwkv_mi_batch_logit_bias_set(b._ptr, s, ids.ctypes.data_as(P_U32), vals.ctypes.data_as(P_F32), ids.size):
+                        raise RuntimeError("rwkv_mi_batch_logit_bias_set failed")
+                toks = [int(t) for t in b.eval_sample_penalized(slots, toks, 1.0, 0.8, -1.0, slots, 0.0, 0.0, False)]
+                state = [int(nxt[state[i], toks[i]]) for i in range(n)]
+            ms = (time.perf_counter() - t0) * 1e3
+            for s in slots:
+                b.set_logit_bias(s, {})
+            return ms
+
+        host_ms = min(runs(host, False))
+        emit({"mode": "guide_host", "n": n, "ms_per_step": round(host_ms / steps, 4), "device_ms_per_step": round(dev_ms / steps, 4),
+              "host_over_device": round(host_ms / dev_ms, 2), "bias_entries_per_row_and_step": int(np.mean([ids.size for ids in off_ids]))})
+    b.free()
+    if sink:
+        sink.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("model_path")
@@ -383,8 +479,10 @@ def main():
                     help="with --sample: time the sampled loop with and without the report of the emitted tokens, for each top_n of the list (see above)")
     ap.add_argument("--beam", default=None, metavar="W[,W...]",
                     help="time rwkv_mi_batch_decode_beam for each width of the list at the largest row count of --n, against the greedy loop and the host-driven search")
-    ap.add_argument("--reps", type=int, default=3, help="--ragged, --until, --logprobs, --beam: timed runs of each shape (the smallest is reported)")
-    ap.add_argument("--out", default=None, help="--ragged, --penalties, --until, --logprobs, --beam: also append the records to this file")
+    ap.add_argument("--guide", action="store_true",
+                    help="with --sample: time the sampled loop plain, guided on the device, and masked from the host before every token (see above)")
+    ap.add_argument("--reps", type=int, default=3, help="--ragged, --until, --logprobs, --beam, --guide: timed runs of each shape (the smallest is reported)")
+    ap.add_argument("--out", default=None, help="--ragged, --penalties, --until, --logprobs, --beam, --guide: also append the records to this file")
     args = ap.parse_args()
 
     import __graft_entry__ as graft
@@ -413,6 +511,12 @@ def main():
         return
     if args.beam is not None:
         beam(pkg, m, args)
+        m.free()
+        return
+    if args.guide:
+        if not args.sample:
+            ap.error("--guide times the sampled loop: give --sample with it")
+        guide(pkg, m, args)
         m.free()
         return
     if args.logprobs is not None:

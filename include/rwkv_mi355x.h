@@ -465,6 +465,50 @@ RWKV_API bool rwkv_mi_batch_guide_free(struct rwkv_mi_batch * batch, uint32_t gu
 RWKV_API bool rwkv_mi_batch_guide_attach(struct rwkv_mi_batch * batch, size_t slot, uint32_t guide /* RWKV_MI_NO_GUIDE: detach */, uint32_t state);
 RWKV_API bool rwkv_mi_batch_guide_state(struct rwkv_mi_batch * batch, size_t slot, uint32_t * guide_out, uint32_t * state_out, uint32_t * misses_out);
 
+/* ---- Speculative decoding: verify a draft in one pass, keep its prefix ----
+ * A decode pass is bound by the walk over the weights, not by arithmetic: a pass that feeds a row 5 tokens walks them once, as a pass that feeds
+ * it 1 does. Where a cheap drafter (prompt lookup, an n-gram table, a small model in another context) guesses a row's next few tokens, one pass
+ * can therefore emit several. What a recurrent model adds to the problem: THE STATE CANNOT BE TRUNCATED. After a pass over x0 d1 .. dk the slot
+ * holds the state after dk, which is useless when only d1 .. da were right. This call verifies and repairs in ONE walk over the weights: the pass
+ * stashes the inputs of its recurrences per token, the device decides how much of each draft stands, and the recurrences of the rows whose
+ * draft did not stand in full are replayed over what did.
+ * Row r names slot slots[r] and feeds it x0 -- the token not yet fed, by the convention of the device loops -- followed by a draft d1 .. dk,
+ * k = lens[r] - 1, 0 <= k <= RWKV_MI_DRAFT_MAX; tokens holds the rows back to back, T = sum(lens) words.
+ * THE SEMANTICS. Let e0, e1, ... be the tokens the PLAIN LOOP OF THE SAME FAMILY would emit for that slot from its current state, draw counter
+ * and occurrence table:
+ *     params == NULL              greedy      rwkv_mi_batch_decode_greedy
+ *     params given                sampled     successive rwkv_mi_batch_eval_sample steps with u < 0 (the generator draws), the slot's draw
+ *                                             counter CONTINUING, not reset
+ *     params and penalties given  penalised   rwkv_mi_batch_decode_sample_penalized: it continues and every step records
+ * (params[r].u and penalties[r].record are not read.) The number of accepted draft tokens a is the largest a <= k with e0 .. e(a-1) == d1 .. da.
+ * The call emits lens_out[r] = a + 1 and tokens_out[r][0 .. a] = e0 .. ea -- the accepted draft, then the correction or bonus token -- and
+ * tokens_out[r][j] = RWKV_MI_NO_TOKEN for a < j < stride.
+ * THE GUARANTEE: speculation never changes what is emitted, only how many passes it takes. After the call everything that belongs to slots[r]
+ * -- its state as rwkv_mi_batch_state_store shows it, its draw counter (advanced once per draw that is not an argmax: a + 1 times at a
+ * temperature > 0), its occurrence table (a + 1 tokens recorded in the penalised family) -- is, bit for bit and word for word, what that plain
+ * loop with n_tokens = a + 1 leaves, whoever else is in the call and whatever their drafts were. ea is emitted (and, penalised, recorded) but
+ * not fed: the next call feeds it as its x0. logits_out[r] holds the model's logits from which ea was chosen. A row with lens[r] == 1 is a
+ * plain step. Slots not named are untouched.
+ * The guarantee holds on the default arms; under the opt-in arms RWKV_MI_SEQ_Q=fast and RWKV_MI_SEQ_F16=mfma a pass of T >= 32 tokens has the
+ * stated tolerance of sequence mode instead, as the ragged calls have.
+ * OUT OF SCOPE: the report -- like beam search the call does not fill it and leaves the current one alone; slots with a guide attached, which
+ * are rejected; a device loop with a drafter on the device; stochastic acceptance against a draft distribution, which would change the
+ * emitted stream, and this call must not.
+ * Besides what rwkv_mi_batch_eval_ragged rejects, the call returns false with RWKV_ERROR_ARGS and changes no slot, parity, counter or count
+ * when a lens[r] is above 1 + RWKV_MI_DRAFT_MAX, tokens_out or lens_out is NULL, stride is less than the largest lens[r], penalties is given
+ * without params, params or penalties hold what the sampled and penalised calls reject, or a named slot has a guide attached.
+ * The call's buffers -- the logits of all T tokens, and per layer and token the inputs of the recurrences: (5, 5, 6, 8) x n_embed floats for
+ * RWKV-4, 5, 6, 7, plus one plane the replay writes -- are allocated by the first call and grown to the largest since (RWKV_ERROR_ALLOC,
+ * nothing changed, when they cannot be); rwkv_mi_batch_free releases them. Every other call performs no launch, allocation or copy it did not
+ * perform before. */
+#define RWKV_MI_DRAFT_MAX 8      /* draft tokens per row */
+RWKV_API bool rwkv_mi_batch_eval_draft(struct rwkv_mi_batch * batch, const uint32_t * slots, const uint32_t * lens /* [n]: 1 + the row's draft length */,
+                                       const uint32_t * tokens /* T = sum(lens): per row x0, d1 .. dk */, size_t n,
+                                       const struct rwkv_mi_sample_params * params      /* [n], NULL: greedy */,
+                                       const struct rwkv_mi_penalty_params * penalties  /* [n], NULL: the plain draw; needs params */,
+                                       size_t stride, uint32_t * tokens_out /* [n][stride] */, uint32_t * lens_out /* [n] */,
+                                       float * logits_out /* [n][n_vocab], may be NULL */);
+
 #if defined(__cplusplus)
 }
 #endif

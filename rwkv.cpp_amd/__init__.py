@@ -5,6 +5,7 @@ repo root to sys.path and use `importlib.import_module("rwkv.cpp_amd")` is NOT p
 """
 from .rwkv_cpp import (  # noqa: F401
     BeamParams,
+    DRAFT_MAX,
     GUIDE_HOOKS_LIB_PATH,
     GUIDE_MAX,
     GUIDE_MAX_STATES,
@@ -25,6 +26,7 @@ from .rwkv_cpp import (  # noqa: F401
     build_library,
     guide_edges,
     load_rwkv_shared_library,
+    lookup_draft,
     penalty_params,
     sample_params,
     stop_params,

@@ -1065,6 +1065,14 @@ struct rwkv_mi_batch {
     // h_live_count and ev_block above where decode_until has not
     DevBuf<uint8_t> d_beam;
     PinBuf<uint8_t> h_beam;
+    // rwkv_mi_batch_eval_draft: the logits of every token of a pass [T][n_vocab] and the stash of its recurrences' inputs (kernels.h, DraftStash),
+    // both grown to the largest call so far; the layers' vectors, keep[n_slots] and the emitted tokens [n_slots][1 + RWKV_MI_DRAFT_MAX] with
+    // their pinned staging (keep first) -- allocated by the first draft call
+    DevBuf<float> d_draft_logits;
+    DevBuf<float> d_draft_stash;
+    DevBuf<DraftLayer> d_draft_layers;
+    DevBuf<uint32_t> d_draft_words;
+    PinBuf<uint32_t> h_draft_words;
     LogprobReport lp;                   // the report of the batch's emitting calls (rwkv_mi_batch_set_logprobs)
 
     float * slot_buf(size_t slot, int p) const { return states.p + ((size_t) p * n_slots + slot) * (size_t) state_len; }
@@ -1460,6 +1468,82 @@ static bool batch_pass(rwkv_mi_batch * B, const BatchCall & c) {
     if (drawn) memcpy(c.sampled_out, run->h_tokens.p, c.n * sizeof(uint32_t));
     batch_flip(B, c);
     if (report) report_done(B->lp, c.n, 1, nullptr);
+    return true;
+}
+
+// ---- speculative decoding (rwkv_mi_batch_eval_draft) ----
+
+// what the call checks beyond the rows, params and penalties of its family (nothing changed yet)
+static bool batch_check_draft(rwkv_mi_batch * B, const BatchCall & c, const uint32_t * tokens_out) {
+    rwkv_context * ctx = B->ctx;
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, tokens_out != nullptr && c.lens_out != nullptr, "tokens_out or lens_out is NULL");
+    for (size_t i = 0; i < c.n; i++) {
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, c.lens[i] <= 1u + RWKV_MI_DRAFT_MAX, "lens[%zu] (%" PRIu32 ") is above 1 + RWKV_MI_DRAFT_MAX (%d)", i, c.lens[i], 1 + RWKV_MI_DRAFT_MAX);
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, (size_t) c.lens[i] <= c.stride, "stride (%zu) is less than lens[%zu] (%" PRIu32 ")", c.stride, i, c.lens[i]);
+    }
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, !batch_names_guided(B, c.slots, c.n), "rwkv_mi_batch_eval_draft takes no slot with a guide attached");
+    return true;
+}
+
+// the call's buffers for a pass of T tokens: one decision, a failure leaves every buffer as it was. The layers' vectors are uploaded with the
+// first allocation (the stream is drained by the upload that follows)
+static bool batch_ensure_draft(rwkv_mi_batch * B, size_t T) {
+    rwkv_context * ctx = B->ctx;
+    const Model & m = *ctx->model;
+    const size_t V = (size_t) m.n_vocab(), D = (size_t) m.n_embed(), L = (size_t) (m.layer_end - m.layer_begin);
+    const size_t logits = T * V, stash = L * (size_t) (draft_stash_inputs(m) + 3) * T * D, words = B->n_slots * (2 + RWKV_MI_DRAFT_MAX);
+    const bool first = !B->d_draft_layers;
+    if (logits > B->d_draft_logits.count || stash > B->d_draft_stash.count) BATCH_HIP_OK(B, hipStreamSynchronize(B->run->stream));   // (an earlier call may still read the old ones)
+    const hipError_t e = grow(want(B->d_draft_logits, logits > B->d_draft_logits.count ? logits : 0), want(B->d_draft_stash, stash > B->d_draft_stash.count ? stash : 0),
+                              want(B->d_draft_layers, first ? L : 0), want(B->d_draft_words, first ? words : 0), want(B->h_draft_words, first ? words : 0));
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the draft buffers of %zu tokens: %s", T, hipGetErrorString(e));
+    if (first) {
+        std::vector<DraftLayer> lw(L);
+        auto f = [](const DevTensor * t) { return t ? (const float *) t->data : nullptr; };
+        for (size_t i = 0; i < L; i++) {
+            const LayerW & w = m.layers[m.layer_begin + i];
+            const bool faaaa = m.arch_major == 6 || (m.arch_major == 5 && m.arch_minor >= 2);
+            lw[i] = DraftLayer{m.arch_major == 7 ? nullptr : f(faaaa ? w.att_time_faaaa : w.att_time_first), m.arch_major >= 6 ? nullptr : f(w.att_time_decay)};
+        }
+        const hipError_t eu = hipMemcpy(B->d_draft_layers.p, lw.data(), L * sizeof(DraftLayer), hipMemcpyHostToDevice);
+        if (eu != hipSuccess) { B->d_draft_layers.reset(); B->d_draft_words.reset(); B->h_draft_words.reset(); }
+        BATCH_HIP_OK(B, eu);
+    }
+    return true;
+}
+
+// One draft pass (engine.hip forward_draft): every named slot is fed x0 and its draft in one walk over the weights; the device then decides how
+// much of each draft the plain loop of the call's family would have emitted, and puts the slots whose draft did not stand in full back to the
+// state after what did. The host learns lens_out and tokens_out after one synchronisation; `keep` never leaves the device in between.
+static bool batch_draft(rwkv_mi_batch * B, const BatchCall & c, uint32_t * tokens_out) {
+    rwkv_context * ctx = B->ctx;
+    rwkv_context * run = B->run;
+    ctx->last_error = RWKV_ERROR_NONE;
+    size_t T = 0;
+    if (!batch_check_args(B, c, false, &T) || !batch_check_draft(B, c, tokens_out)) return false;
+    run->print_errors = ctx->print_errors;
+    BATCH_HIP_OK(B, hipSetDevice(ctx->model->device));
+    if (!batch_ensure_draw(B, c) || !batch_ensure_draft(B, T)) return false;
+    if (!batch_upload_call(B, c, T, true)) return false;   // (loop: the generator draws, every step records)
+    const Model & m = *ctx->model;
+    const int W = 1 + RWKV_MI_DRAFT_MAX;
+    DraftPass d;
+    d.stash.base = B->d_draft_stash.p; d.stash.n_in = draft_stash_inputs(m); d.stash.plane = (int64_t) T * m.n_embed();
+    d.stash.layer0 = m.layer_begin; d.stash.per_layer = m.state_per_layer();
+    d.lw = B->d_draft_layers.p; d.logits_all = B->d_draft_logits.p;
+    d.draw = c.draw; d.srows = B->d_srows.p; d.prows = B->d_prows.p; d.probs = B->draw.probs.p;
+    d.keep = B->d_draft_words.p; d.out = B->d_draft_words.p + B->n_slots; d.out_stride = W;
+    if (!forward_draft(run, B->pass, (int64_t) T, d)) return batch_fail_drained(B);
+    BATCH_HIP_OK(B, hipMemcpyAsync(B->h_draft_words.p, B->d_draft_words.p, c.n * sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream));
+    BATCH_HIP_OK(B, hipMemcpyAsync(B->h_draft_words.p + B->n_slots, d.out, c.n * (size_t) W * sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream));
+    if (c.logits_out) BATCH_HIP_OK(B, hipMemcpyAsync(c.logits_out, run->d_logits.p, c.n * (size_t) m.n_vocab() * sizeof(float), hipMemcpyDeviceToHost, run->stream));
+    BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));
+    for (size_t r = 0; r < c.n; r++) {
+        c.lens_out[r] = B->h_draft_words.p[r];
+        const uint32_t * e = B->h_draft_words.p + B->n_slots + r * (size_t) W;
+        for (size_t j = 0; j < c.stride; j++) tokens_out[r * c.stride + j] = j < (size_t) W ? e[j] : RWKV_MI_NO_TOKEN;
+    }
+    batch_flip(B, c);
     return true;
 }
 
@@ -1968,6 +2052,19 @@ RWKV_API bool rwkv_mi_batch_decode_until(struct rwkv_mi_batch * B, const uint32_
 }
 
 RWKV_API size_t rwkv_mi_batch_last_loop_passes(const struct rwkv_mi_batch * B) { return B ? B->last_loop_passes : 0; }
+
+RWKV_API bool rwkv_mi_batch_eval_draft(struct rwkv_mi_batch * B, const uint32_t * slots, const uint32_t * lens, const uint32_t * tokens, size_t n,
+                                       const struct rwkv_mi_sample_params * params, const struct rwkv_mi_penalty_params * penalties,
+                                       size_t stride, uint32_t * tokens_out, uint32_t * lens_out, float * logits_out) {
+    B->ctx->last_error = RWKV_ERROR_NONE;
+    RW_CTX_CHECK(B->ctx, RWKV_ERROR_ARGS, false, params != nullptr || penalties == nullptr, "penalties are given without params");
+    BatchCall c{slots, tokens, n};
+    c.ragged = true; c.lens = lens;
+    c.draw = penalties ? Draw::penalized : params ? Draw::sample : Draw::none;
+    c.params = params; c.penalties = penalties;
+    c.stride = stride; c.lens_out = lens_out; c.logits_out = logits_out;
+    return batch_draft(B, c, tokens_out);
+}
 
 RWKV_API bool rwkv_mi_batch_state_copy(struct rwkv_mi_batch * B, size_t dst_slot, size_t src_slot, uint32_t what) {
     rwkv_context * ctx = B->ctx;

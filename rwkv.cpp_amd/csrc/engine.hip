@@ -381,6 +381,31 @@ struct Runner {
     StateRef state;
     const SegPass * seg = nullptr;
     const ScorePass * score = nullptr;   // score mode: the head runs on every row of the pass (run_head_score)
+    // draft mode (segment mode only; rwkv_mi_batch_eval_draft): every layer stashes the inputs of its recurrences, the head runs on every row
+    // into draft->logits_all. Without it no launch of a pass changes.
+    const DraftPass * draft = nullptr;
+    float * stash_plane(uint32_t layer, int i) const {
+        const DraftStash & d = draft->stash;
+        return d.base + ((int64_t) (layer - m.layer_begin) * d.planes() + i) * d.plane;
+    }
+    // after a layer's time mixing, before its channel mixing overwrites b.xn and b.r: the WKV body's inputs in the order of its arguments, then
+    // the input of the att token-shift mix
+    void stash_att(uint32_t layer) {
+        DraftStashSrc s;
+        switch (m.arch_major) {
+            case 4: s.src[0] = b.k; s.src[1] = b.v; s.src[2] = b.r; s.n = 3; break;
+            case 5: s.src[0] = b.r; s.src[1] = b.k; s.src[2] = b.v; s.n = 3; break;
+            case 6: s.src[0] = b.r; s.src[1] = b.k; s.src[2] = b.v; s.src[3] = b.w; s.n = 4; break;
+            default: s.src[0] = b.r; s.src[1] = b.w; s.src[2] = b.t0; s.src[3] = b.v; s.src[4] = b.t1; s.src[5] = b.t2; s.n = 6; break;
+        }
+        s.src[s.n++] = b.xn;
+        launch_draft_stash(s, stash_plane(layer, 0), draft->stash.plane, st);
+    }
+    // after the channel mixing: the input of its token-shift mix
+    void stash_ffn(uint32_t layer) {
+        DraftStashSrc s; s.src[0] = b.xn; s.n = 1;
+        launch_draft_stash(s, stash_plane(layer, draft->stash.n_in + 1), draft->stash.plane, st);
+    }
     // the WKV state of the segments the _segs kernels run (seg->d_short), at offset so
     StateRef seg_short(int64_t so) const { StateRef s = state.at(so); s.segs = seg->d_short; s.n_segs = seg->n_short; return s; }
 
@@ -694,7 +719,9 @@ struct Runner {
                 case 7: att_v7(L, (int) i, so); break;
                 default: break;
             }
+            if (draft) stash_att(i);
             ffn(L, so);
+            if (draft) stash_ffn(i);
         }
         return false;
     }
@@ -721,6 +748,13 @@ struct Runner {
     }
     void run_head() {
         if (score) { run_head_score(); return; }
+        if (draft) {
+            // draft mode: ln_out on all T rows, one product with T rows into [T][n_vocab] (per row what row mode's head computes)
+            drop_pre();
+            launch_layernorm(b.x, T, D, f(m.ln_out_w), f(m.ln_out_b), b.xn, st);
+            mm(m.head, b.xn, draft->logits_all);
+            return;
+        }
         if (state.rows) {
             // row mode: every row is the last token of its sequence -- ln_out on all rows, one product with T rows into [T][n_vocab]
             launch_layernorm(b.x, T, D, f(m.ln_out_w), f(m.ln_out_b), b.xn, st);
@@ -892,6 +926,30 @@ bool forward_segs(rwkv_context * ctx, const SegPass & p, int64_t T, bool want_lo
     HIP_CTX_OK(ctx, hipGetLastError());
     RW_CTX_CHECK(ctx, RWKV_ERROR_GRAPH | RWKV_ERROR_ALLOC, false, !r.failed, "a product of the ragged pass could not be launched (out of device memory for the tile-major weight image?)");
     RW_CTX_CHECK(ctx, RWKV_ERROR_GRAPH, false, !r.copy_failed, "a copy of the scoring pass's logits could not be enqueued");
+    return true;
+}
+
+// One draft pass (model.h, DraftPass): the ragged pass of forward_segs with the stash and the head on every token, then -- inside the pass's
+// place in the per-device chain, as the samplers are -- the choice and the replay.
+bool forward_draft(rwkv_context * ctx, const SegPass & p, int64_t T, const DraftPass & d) {
+    Model & m = *ctx->model;
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, p.n_long == 0 && p.n_short == p.n && d.stash.base && d.logits_all, "a draft pass takes short segments and needs its buffers");
+    if (!ensure_scratch(ctx, T)) { (void) hipGetLastError(); ctx->last_error |= RWKV_ERROR_ALLOC; return false; }
+    Runner r{ctx, m, ctx->stream, T, m.n_embed(), m.head_count, m.head_size, ctx->b};
+    r.seg = &p;
+    r.draft = &d;
+    r.state.segs = p.d_segs; r.state.n_segs = p.n; r.state.seg_of = p.d_seg_of;
+    mega_chain_begin(ctx);
+    r.run(true);
+    if (!r.failed) {
+        launch_draft_accept_rows(d.logits_all, p.n, (int) m.n_vocab(), p.d_segs, ctx->d_tokens.p, d.draw, d.srows, d.prows, d.probs, d.out, d.out_stride, d.keep,
+                                 ctx->d_logits.p, ctx->stream);
+        launch_draft_replay(d.stash, d.lw, m.arch_major, m.arch_minor, p.d_segs, p.n, d.keep, (int64_t) (m.layer_end - m.layer_begin), m.n_embed(), m.head_count, m.head_size,
+                            ctx->stream);
+    }
+    mega_chain_end(ctx);
+    HIP_CTX_OK(ctx, hipGetLastError());
+    RW_CTX_CHECK(ctx, RWKV_ERROR_GRAPH | RWKV_ERROR_ALLOC, false, !r.failed, "a product of the draft pass could not be launched (out of device memory for the tile-major weight image?)");
     return true;
 }
 

@@ -120,6 +120,30 @@ void launch_wkv7(const float * r, const float * w, const float * k, const float 
 bool launch_wkv7_seq(const float * r, const float * w, const float * k, const float * v, const float * a, const float * b,
                      const float * state_in, float * state_out, float * out, int64_t T, int64_t H, hipStream_t st);
 
+// Speculative decoding (rwkv_mi_batch_eval_draft): the stash of a pass and the replay of its recurrences (kernels.hip, "Replay").
+// The stash of a pass of T tokens is [layers][planes()][T][D] floats; per layer, plane i < n_in is input i of the layer's WKV body in the order
+// of its arguments (v4: k, v, r; v5: r, k, v; v6: r, k, v, w; v7: r, w, k', v, -kk, kk*a), plane n_in the input of the att token-shift mix,
+// plane n_in + 1 that of the ffn mix (what k_mix_segs leaves in the carry at a segment's last token), plane n_in + 2 where a replay's body
+// writes the per-token output nobody reads. layer0 / per_layer: the first layer of the stash and the floats of a layer in a state buffer.
+struct DraftStash {
+    float * base = nullptr;
+    int n_in = 0;
+    int64_t plane = 0;   // T * D
+    int64_t layer0 = 0, per_layer = 0;
+    __host__ __device__ int64_t planes() const { return n_in + 3; }
+};
+struct DraftStashSrc { const float * src[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; int n = 0; };
+// dst[i][0 .. plane) = src[i][0 .. plane), i < s.n
+void launch_draft_stash(const DraftStashSrc & s, float * dst, int64_t plane, hipStream_t st);
+// the vectors of a layer a body reads beside its per-token inputs: v4 time_first / time_decay, v5 time_first or time_faaaa / time_decay, v6
+// time_faaaa / unused, v7 none
+struct DraftLayer { const float * u; const float * w; };
+// For every layer of the stash and every segment i with keep[i] < t1 - t0: the layer's WKV body over tokens [t0, t0 + keep[i]) from segs[i].in
+// into segs[i].out on the stashed inputs, and the two token-shift carries of token t0 + keep[i] - 1 into segs[i].out. A segment with
+// keep[i] == t1 - t0 is left alone. keep is read on the device. lw: [n_layers] on the device (v7: may be nullptr).
+void launch_draft_replay(const DraftStash & d, const DraftLayer * lw, int arch_major, int arch_minor, const SegState * segs, int64_t n_segs,
+                         const uint32_t * keep, int64_t n_layers, int64_t D, int64_t H, int64_t S, hipStream_t st);
+
 // Per-head group norm * ln_x.w + ln_x.b, optional v7 bonus (+ v * sum_head(k*r*r_k)), optional gate multiply
 // (rwkv_graph.inc:280-289, 375-382, 465-479). In place on x[T][H*S].
 void launch_groupnorm(float * x, const float * lw, const float * lb, float eps, const float * gate,

@@ -914,10 +914,12 @@ void launch_v6_mix2(const V6Mix2Args & a, int64_t T, int64_t D, int64_t R, hipSt
 
 // ---------------------------------------------------------------------------------------------------------------
 // WKV recurrences. Sequential in t inside the kernel; the state stays in registers across the tokens of a call.
-// Each recurrence is one __device__ body over tokens [t0, t1) from state_in to state_out, with three entry points:
+// Each recurrence is one __device__ body over tokens [t0, t1) from state_in to state_out, with four entry points:
 //   k_wkvX       (grid H, or channel blocks for RWKV-4): one sequence, body(state_in, state_out, 0, T);
 //   k_wkvX_rows  (grid (H, T)): row t is its own sequence (batched decode), body(rows[t].in + so, rows[t].out + so, t, t + 1);
-//   k_wkvX_segs  (grid (H, n_segs)): segment i is tokens [t0, t1) of its own sequence (ragged pass), body(segs[i].in + so, segs[i].out + so, t0, t1).
+//   k_wkvX_segs  (grid (H, n_segs)): segment i is tokens [t0, t1) of its own sequence (ragged pass), body(segs[i].in + so, segs[i].out + so, t0, t1);
+//   k_wkvX_replay (grid (H, n_segs, layers), rwkv_mi_batch_eval_draft): every layer of segment i again over its first keep[i] tokens, on the
+//                inputs the pass stashed, body(segs[i].in + so, segs[i].out + so, t0, t0 + keep[i]) -- see "Replay" below.
 // A row therefore performs exactly the statements of one single-token step, in the same order. The bodies' pointers are plain: the
 // entry points' parameters carry __restrict__ (on the row forms' slot pointers it raised k_wkv7_rows<64> from 86 to 126 VGPRs).
 // ---------------------------------------------------------------------------------------------------------------
@@ -1260,6 +1262,128 @@ void launch_wkv7(const float * r, const float * w, const float * k, const float 
         case 32: go(k_wkv7<32>, k_wkv7_rows<32>, 64); break;
         default: go(k_wkv7_generic, k_wkv7_rows_generic, 256, S); break;
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Replay (rwkv_mi_batch_eval_draft). A recurrent state cannot be cut back: after a ragged pass over x0 d1 .. dk a slot's other buffer holds
+// the state after dk, and when only keep < 1 + k of those tokens stand it is of no use. The pass therefore stashes, per layer and token, what
+// its recurrences read (DraftStash: the inputs of the layer's WKV body and the two token-shift inputs), and once keep[i] is known on the
+// device the fourth entry point of each body runs segment i's first keep[i] tokens again from the slot's CURRENT buffer, which the pass has
+// not touched, into the other one: exactly the statements of a ragged pass over those tokens. A segment whose whole draft stands returns at
+// once -- the pass has left the right state. The bodies' per-token output goes to a plane of the stash nobody reads.
+// ---------------------------------------------------------------------------------------------------------------
+
+// src[i][0 .. plane) -> dst + i * plane, i < n: the planes of a layer the pass is about to overwrite
+__global__ __launch_bounds__(256) void k_draft_stash(DraftStashSrc s, float * __restrict__ dst, int64_t plane) {
+    for (int64_t idx = (int64_t) blockIdx.x * 256 + threadIdx.x; idx < plane; idx += (int64_t) gridDim.x * 256)
+        for (int i = 0; i < s.n; i++) dst[(int64_t) i * plane + idx] = s.src[i][idx];
+}
+
+void launch_draft_stash(const DraftStashSrc & s, float * dst, int64_t plane, hipStream_t st) {
+    const unsigned grid = (unsigned) ((plane + 255) / 256 < 4096 ? (plane + 255) / 256 : 4096);
+    hipLaunchKernelGGL(k_draft_stash, dim3(grid), dim3(256), 0, st, s, dst, plane);
+}
+
+// what a replay block works on: its segment, how much of it stands (0: nothing to do), its layer's planes
+struct ReplayBlock { SegState seg; int64_t t1; const float * in; float * sink; int64_t so; };
+__device__ __forceinline__ ReplayBlock replay_block(const DraftStash & d, const SegState * __restrict__ segs, const uint32_t * __restrict__ keep) {
+    ReplayBlock b;
+    b.seg = segs[blockIdx.y];
+    const int64_t kp = keep[blockIdx.y];
+    b.t1 = kp < (int64_t) (b.seg.t1 - b.seg.t0) ? b.seg.t0 + kp : 0;   // (the whole workgroup takes the same way: no barrier is left waiting)
+    b.in = d.base + (int64_t) blockIdx.z * d.planes() * d.plane;
+    b.sink = const_cast<float *>(b.in) + (int64_t) (d.n_in + 2) * d.plane;
+    b.so = (d.layer0 + (int64_t) blockIdx.z) * d.per_layer;
+    return b;
+}
+
+__global__ __launch_bounds__(256) void k_wkv4_replay(DraftStash d, const DraftLayer * __restrict__ lw, const SegState * __restrict__ segs,
+                                                     const uint32_t * __restrict__ keep, int64_t D) {
+    const ReplayBlock b = replay_block(d, segs, keep);
+    if (!b.t1) return;
+    const DraftLayer w = lw[blockIdx.z];
+    wkv4_body(b.in, b.in + d.plane, b.in + 2 * d.plane, w.u, w.w, b.seg.in + b.so + 2 * D, b.seg.out + b.so + 2 * D, b.sink, b.seg.t0, b.t1, D);
+}
+
+// RWKV-5: r, k, v stashed, u and w the layer's vectors (w_mode < 2); RWKV-6: w stashed as the fourth plane (w_mode 2)
+template <int S>
+__global__ __launch_bounds__(64) void k_wkv6_replay(DraftStash d, const DraftLayer * __restrict__ lw, int u_per_chan, int w_mode,
+                                                    const SegState * __restrict__ segs, const uint32_t * __restrict__ keep, int64_t H) {
+    const ReplayBlock b = replay_block(d, segs, keep);
+    if (!b.t1) return;
+    const DraftLayer w = lw[blockIdx.z];
+    const int64_t so = b.so + 2 * H * S;
+    wkv6_body<S>(b.in, b.in + d.plane, b.in + 2 * d.plane, w.u, u_per_chan, w_mode == 2 ? b.in + 3 * d.plane : w.w, w_mode,
+                 b.seg.in + so, b.seg.out + so, b.sink, b.seg.t0, b.t1, H);
+}
+
+__global__ __launch_bounds__(256) void k_wkv6_replay_generic(DraftStash d, const DraftLayer * __restrict__ lw, int u_per_chan, int w_mode,
+                                                             const SegState * __restrict__ segs, const uint32_t * __restrict__ keep, int64_t H, int64_t S) {
+    const ReplayBlock b = replay_block(d, segs, keep);
+    if (!b.t1) return;
+    const DraftLayer w = lw[blockIdx.z];
+    const int64_t so = b.so + 2 * H * S;
+    wkv6_body_generic(b.in, b.in + d.plane, b.in + 2 * d.plane, w.u, u_per_chan, w_mode == 2 ? b.in + 3 * d.plane : w.w, w_mode,
+                      b.seg.in + so, b.seg.out + so, b.sink, b.seg.t0, b.t1, H, S);
+}
+
+template <int S>
+__global__ __launch_bounds__(64) void k_wkv7_replay(DraftStash d, const SegState * __restrict__ segs, const uint32_t * __restrict__ keep, int64_t H) {
+    const ReplayBlock b = replay_block(d, segs, keep);
+    if (!b.t1) return;
+    const int64_t so = b.so + 2 * H * S;
+    wkv7_body<S>(b.in, b.in + d.plane, b.in + 2 * d.plane, b.in + 3 * d.plane, b.in + 4 * d.plane, b.in + 5 * d.plane,
+                 b.seg.in + so, b.seg.out + so, b.sink, b.seg.t0, b.t1, H);
+}
+
+__global__ __launch_bounds__(256) void k_wkv7_replay_generic(DraftStash d, const SegState * __restrict__ segs, const uint32_t * __restrict__ keep,
+                                                             int64_t H, int64_t S) {
+    const ReplayBlock b = replay_block(d, segs, keep);
+    if (!b.t1) return;
+    const int64_t so = b.so + 2 * H * S;
+    wkv7_body_generic(b.in, b.in + d.plane, b.in + 2 * d.plane, b.in + 3 * d.plane, b.in + 4 * d.plane, b.in + 5 * d.plane,
+                      b.seg.in + so, b.seg.out + so, b.sink, b.seg.t0, b.t1, H, S);
+}
+
+// the two token-shift carries of a replayed segment: what k_mix_segs leaves at a segment's last token, for token t0 + keep - 1 -- the ffn
+// mix's input at so, the att mix's at so + D
+__global__ __launch_bounds__(256) void k_draft_carry(DraftStash d, const SegState * __restrict__ segs, const uint32_t * __restrict__ keep, int64_t D) {
+    const ReplayBlock b = replay_block(d, segs, keep);
+    const int64_t i = (int64_t) blockIdx.x * 256 + threadIdx.x;
+    if (!b.t1 || i >= D) return;
+    const int64_t at = (b.t1 - 1) * D + i;
+    b.seg.out[b.so + i] = b.in[(int64_t) (d.n_in + 1) * d.plane + at];
+    b.seg.out[b.so + D + i] = b.in[(int64_t) d.n_in * d.plane + at];
+}
+
+void launch_draft_replay(const DraftStash & d, const DraftLayer * lw, int arch_major, int arch_minor, const SegState * segs, int64_t n_segs,
+                         const uint32_t * keep, int64_t n_layers, int64_t D, int64_t H, int64_t S, hipStream_t st) {
+    const unsigned n = (unsigned) n_segs, L = (unsigned) n_layers;
+    if (arch_major == 4) {
+        hipLaunchKernelGGL(k_wkv4_replay, dim3((unsigned) ((D + 255) / 256), n, L), dim3(256), 0, st, d, lw, segs, keep, D);
+    } else if (arch_major <= 6) {
+        const int u_per_chan = (arch_major == 6 || arch_minor >= 2) ? 1 : 0, w_mode = arch_major == 6 ? 2 : u_per_chan;
+        const dim3 grid((unsigned) H, n, L);
+        auto go = [&](auto kern, unsigned block, auto... generic_s) {
+            hipLaunchKernelGGL(kern, grid, dim3(block), 0, st, d, lw, u_per_chan, w_mode, segs, keep, H, generic_s...);
+        };
+        switch (S) {
+            case 64: go(k_wkv6_replay<64>, 64); break;
+            case 32: go(k_wkv6_replay<32>, 64); break;
+            case 16: go(k_wkv6_replay<16>, 64); break;
+            case 8:  go(k_wkv6_replay<8>, 64); break;
+            default: go(k_wkv6_replay_generic, 256, S); break;
+        }
+    } else {
+        const dim3 grid((unsigned) H, n, L);
+        auto go = [&](auto kern, unsigned block, auto... generic_s) { hipLaunchKernelGGL(kern, grid, dim3(block), 0, st, d, segs, keep, H, generic_s...); };
+        switch (S) {
+            case 64: go(k_wkv7_replay<64>, 64); break;
+            case 32: go(k_wkv7_replay<32>, 64); break;
+            default: go(k_wkv7_replay_generic, 256, S); break;
+        }
+    }
+    hipLaunchKernelGGL(k_draft_carry, dim3((unsigned) ((D + 255) / 256), n, L), dim3(256), 0, st, d, segs, keep, D);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -400,6 +400,33 @@ struct SegPass {
 bool seg_takes_seq_kernel(const Model & m, int64_t len);
 bool forward_segs(rwkv_context * ctx, const SegPass & p, int64_t T, bool want_logits, const RowSampler * sample = nullptr, const ScorePass * score = nullptr);
 
+// Speculative decoding (rwkv_mi_batch_eval_draft): a ragged pass whose n segments are x0 d1 .. dk of at most 1 + RWKV_MI_DRAFT_MAX tokens each
+// (all of them on the _segs recurrences), with three additions that run in this call only:
+//   the stash    every layer copies the inputs of its recurrences into `stash` (kernels.h, DraftStash) while the pass runs;
+//   the head     on ALL T tokens into logits_all[T][n_vocab], addressable together: a row's positions are read in sequence;
+//   the choice   k_draft_accept_rows (sampling.hip) walks each row's positions with the draw of the call's family -- draw / srows / prows /
+//                probs as in RowSampler -- and leaves out[n][out_stride] (the emitted tokens, RWKV_MI_NO_TOKEN behind them), keep[n] (their
+//                number) and, in ctx->d_logits row r, the logits the row's last emitted token was chosen from;
+//   the replay   launch_draft_replay re-runs the recurrences of every row whose draft did not stand in full over its first keep tokens.
+// keep never leaves the device in between. lw: the layers' vectors on the device (kernels.h, DraftLayer).
+struct DraftPass {
+    DraftStash stash;
+    const DraftLayer * lw = nullptr;
+    float * logits_all = nullptr;
+    Draw draw = Draw::none;
+    const SampleRow * srows = nullptr;
+    const PenaltyRow * prows = nullptr;
+    float * probs = nullptr;
+    uint32_t * out = nullptr;
+    int out_stride = 0;
+    uint32_t * keep = nullptr;
+};
+void launch_draft_accept_rows(const float * logits, int64_t rows, int n, const SegState * segs, const uint32_t * tokens, Draw draw, const SampleRow * srows,
+                              const PenaltyRow * prows, float * probs, uint32_t * out, int out_stride, uint32_t * keep, float * logits_row, hipStream_t st);
+// inputs of a layer's WKV body a pass stashes (DraftStash::n_in): 3, 3, 4, 6 for RWKV-4, 5, 6, 7
+inline int draft_stash_inputs(const Model & m) { return m.arch_major == 7 ? 6 : (m.arch_major == 6 ? 4 : 3); }
+bool forward_draft(rwkv_context * ctx, const SegPass & p, int64_t T, const DraftPass & d);
+
 // fused RWKV-6 decode layer (fused_v6.hip)
 bool   fused_v6_supported(const Model & m);
 size_t fused_v6_scratch_bytes(const Model & m);

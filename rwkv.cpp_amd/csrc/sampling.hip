@@ -306,6 +306,74 @@ __global__ __launch_bounds__(1024) void k_guided_pen_sample_rows(const float * _
     if (threadIdx.x == 0 && srow) guide_advance(g, srow, pick);
 }
 
+// The greedy loops' choice for one row by the whole workgroup, returned to every thread: the largest logit, the lowest index among equals; a
+// NaN never wins, and where nothing compares greater than -inf the token is 0 -- the rule of k_argmax / k_argmax_live and of the scoring kernel.
+__device__ __forceinline__ int draft_argmax(const float * lg, int n) {
+    __shared__ float l_v[16];
+    __shared__ int l_i[16], l_res;
+    float best = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) { const float v = lg[i]; if (v > best) { best = v; bi = i; } }
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(best, o, WAVE); const int oi = __shfl_xor(bi, o, WAVE);
+        if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+    }
+    if ((threadIdx.x & 63) == 0) { l_v[threadIdx.x >> 6] = best; l_i[threadIdx.x >> 6] = bi; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < (int) (blockDim.x >> 6); w++) if (l_v[w] > best || (l_v[w] == best && l_i[w] < bi)) { best = l_v[w]; bi = l_i[w]; }
+        l_res = bi == 0x7fffffff ? 0 : bi;
+    }
+    __syncthreads();
+    return l_res;
+}
+
+// rwkv_mi_batch_eval_draft: which tokens of a row's draft stand. One workgroup per row r = segment segs[r] of the pass, whose tokens
+// [t0, t1) are x0 d1 .. dk and whose logits (of EVERY token: logits[T][n]) are in HBM. Position j = 0 .. k chooses e_j from the logits after
+// token t0 + j exactly as the plain loop of the family chooses it -- FAMILY 0: the greedy argmax; 1: sample_body on PlainLogits with the row of
+// k_sample_rows; 2: sample_body on PenalisedLogits with the row of k_pen_sample_rows, thread 0 counting the pick -- and writes it to
+// out[r][j]; the walk ends after the first j with j == k or e_j != d(j+1). Then keep[r] = j + 1, out[r][j + 1 .. out_stride) = RWKV_MI_NO_TOKEN
+// and the logits of position j go to row r of logits_row. The draw counter and the counts advance once per position walked, so they end where
+// the plain loop of keep[r] steps leaves them. The pick comes back to every thread: the whole workgroup leaves the walk together. Between two
+// positions a fence and a barrier: the next one reads the counter and the count thread 0 has just written, and reuses the body's LDS words.
+template <int FAMILY>
+__global__ __launch_bounds__(1024) void k_draft_accept_rows(const float * __restrict__ logits, int n, const SegState * __restrict__ segs,
+                                                            const uint32_t * __restrict__ tokens, const SampleRow * __restrict__ srows,
+                                                            const PenaltyRow * __restrict__ prows, float * __restrict__ probs, size_t stride,
+                                                            uint32_t * __restrict__ out, int out_stride, uint32_t * __restrict__ keep,
+                                                            float * __restrict__ logits_row) {
+    const size_t r = blockIdx.x;
+    const SegState seg = segs[r];
+    const int k = seg.t1 - seg.t0 - 1;
+    uint32_t * o = out + r * (size_t) out_stride;
+    int j = 0;
+    for (;;) {
+        const float * lg = logits + (size_t) (seg.t0 + j) * (size_t) n;
+        int pick;
+        if (FAMILY == 0) {
+            pick = draft_argmax(lg, n);
+            if (threadIdx.x == 0) o[j] = (uint32_t) pick;
+        } else if (FAMILY == 1) {
+            const rwkv_mi_sample_params p = srows[r].p;
+            pick = sample_body([=](int i0) { return PlainLogits{lg + i0}; }, n, p.temperature, p.top_p, p.u, p.seed, srows[r].counter, probs + r * stride, o + j, nullptr);
+        } else {
+            const PenaltyRow row = prows[r];
+            pick = sample_body([=](int i0) { return PenalisedLogits{lg + i0, row.count + i0, row.bias ? row.bias + i0 : nullptr, row.presence, row.frequency}; },
+                               n, row.p.temperature, row.p.top_p, row.p.u, row.p.seed, row.counter, probs + r * stride, o + j, nullptr);
+            if (threadIdx.x == 0) row.count[pick] += 1u;
+        }
+        if (j == k || (uint32_t) pick != tokens[seg.t0 + j + 1]) break;
+        j++;
+        __threadfence_block();
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) keep[r] = (uint32_t) (j + 1);
+    for (int i = j + 1 + (int) threadIdx.x; i < out_stride; i += blockDim.x) o[i] = RWKV_MI_NO_TOKEN;
+    const float * src = logits + (size_t) (seg.t0 + j) * (size_t) n;
+    float * dst = logits_row + r * (size_t) n;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) dst[i] = src[i];
+}
+
 // rwkv_mi_batch_guide_create: the dense table next[n_states][n_vocab] from the CSR edges, one workgroup per state: the dead fill of the
 // state's row, then -- behind a barrier -- one 2-byte store per edge. A state's tokens are distinct, so no two stores meet.
 __global__ __launch_bounds__(256) void k_guide_expand(uint16_t * __restrict__ next, int n_vocab, const uint32_t * __restrict__ edge_begin,
@@ -395,6 +463,19 @@ void launch_guided_sample_rows(const float * logits, int64_t rows, int n, const 
 void launch_guided_pen_sample_rows(const float * logits, int64_t rows, int n, const PenaltyRow * table, const GuideRow * guides, float * probs, uint32_t * tokens,
                                    uint32_t * hist, const uint32_t * live, hipStream_t st) {
     hipLaunchKernelGGL(k_guided_pen_sample_rows, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, table, guides, probs, sample_scratch_floats(n), tokens, hist, live);
+}
+
+void launch_draft_accept_rows(const float * logits, int64_t rows, int n, const SegState * segs, const uint32_t * tokens, Draw draw, const SampleRow * srows,
+                              const PenaltyRow * prows, float * probs, uint32_t * out, int out_stride, uint32_t * keep, float * logits_row, hipStream_t st) {
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, segs, tokens, srows, prows, probs, sample_scratch_floats(n), out, out_stride,
+                           keep, logits_row);
+    };
+    switch (draw) {
+        case Draw::none: go(k_draft_accept_rows<0>); break;
+        case Draw::sample: go(k_draft_accept_rows<1>); break;
+        case Draw::penalized: go(k_draft_accept_rows<2>); break;
+    }
 }
 
 void launch_guide_expand(uint16_t * next, uint32_t n_states, int n_vocab, const uint32_t * edge_begin, const uint32_t * edge_tokens, const uint32_t * edge_next,

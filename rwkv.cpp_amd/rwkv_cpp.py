@@ -38,6 +38,8 @@ GUIDE_SYMBOLS = ("rwkv_mi_batch_guide_create", "rwkv_mi_batch_guide_free", "rwkv
 GUIDE_MAX = 16              # RWKV_MI_GUIDE_MAX: guides per batch
 GUIDE_MAX_STATES = 65535    # RWKV_MI_GUIDE_MAX_STATES: states per guide
 NO_GUIDE = 0xFFFFFFFF       # RWKV_MI_NO_GUIDE: a slot without a guide
+DRAFT_SYMBOLS = ("rwkv_mi_batch_eval_draft",)
+DRAFT_MAX = 8               # RWKV_MI_DRAFT_MAX: draft tokens per row of RWKVBatch.eval_draft
 COPY_STATE, COPY_COUNTER, COPY_COUNTS, COPY_BIAS = 1, 2, 4, 8  # RWKV_MI_COPY_*: the bits of rwkv_mi_batch_state_copy's `what`
 TOP_MAX = 20             # RWKV_MI_TOP_MAX: the most alternatives a report holds per token, and the widest beam
 NO_TARGET = 0xFFFFFFFF   # RWKV_MI_NO_TARGET: a position that is not scored (its log-prob is 0)
@@ -287,6 +289,12 @@ class RWKVSharedLibrary:
             L.rwkv_mi_batch_guide_attach.argtypes = [c_batch, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32]
             L.rwkv_mi_batch_guide_state.argtypes = [c_batch, ctypes.c_size_t, P_UINT32, P_UINT32, P_UINT32]
             for name in GUIDE_SYMBOLS:
+                getattr(L, name).restype = ctypes.c_bool
+        # speculative decoding: verify a draft in one pass, keep its prefix
+        if hasattr(L, "rwkv_mi_batch_eval_draft"):   # (absent from older A/B builds loaded through RWKV_LIB_DIR)
+            L.rwkv_mi_batch_eval_draft.argtypes = [c_batch, P_UINT32, P_UINT32, P_UINT32, ctypes.c_size_t, P_SAMPLE_PARAMS, P_PENALTY_PARAMS, ctypes.c_size_t,
+                                                   P_UINT32, P_UINT32, P_FLOAT]
+            for name in DRAFT_SYMBOLS:
                 getattr(L, name).restype = ctypes.c_bool
         if hasattr(L, "rwkv_mi_test_guided_rows"):   # (librwkv_testhooks_guide.so only)
             L.rwkv_mi_test_guided_rows.argtypes = [P_FLOAT, ctypes.c_int64, ctypes.c_int64, ctypes.c_uint32, P_UINT32, P_UINT32, P_UINT32, P_UINT32, P_UINT32, P_UINT32,
@@ -779,6 +787,20 @@ def guide_edges(edges):
     return _u32(begin).reshape(-1), _u32(toks).reshape(-1), _u32(nxt).reshape(-1)
 
 
+def lookup_draft(history, k: int, ngram: int = 3) -> List[int]:
+    """Prompt-lookup drafting: the (at most k) tokens that followed the most recent EARLIER occurrence of the last `ngram` tokens of
+    `history`; fewer where the history ends first, none where there is no such occurrence or the history is shorter than ngram + 1."""
+    h = [int(t) for t in history]
+    k, ngram = int(k), int(ngram)
+    if k <= 0 or ngram <= 0 or len(h) <= ngram:
+        return []
+    tail = h[-ngram:]
+    for start in range(len(h) - ngram - 1, -1, -1):   # (the occurrence that is the tail itself is not an earlier one)
+        if h[start:start + ngram] == tail:
+            return h[start + ngram:start + ngram + k]
+    return []
+
+
 def _bias_arrays(bias: dict):
     ids = _u32(list(bias.keys())).reshape(-1)
     values = np.ascontiguousarray(np.asarray(list(bias.values()), dtype=np.float64).astype(np.float32)).reshape(-1)
@@ -1008,6 +1030,28 @@ class RWKVBatch:
                                                   ctypes.byref(ms)):
             self._fail("rwkv_mi_batch_decode_until")
         return [out[i, : int(lens[i])].copy() for i in range(n)], why, float(ms.value)
+
+    # --- speculative decoding (include/rwkv_mi355x.h) ---
+
+    def eval_draft(self, slots: List[int], rows: List[List[int]], params=None, penalties=None, want_logits: bool = False):
+        """rows[i] = [x0, d1 .. dk] (k <= DRAFT_MAX) to slot slots[i], all rows in ONE pass: x0 is the token not yet fed, d1 .. dk a draft of what
+        follows. Returns (emitted: one list per row -- the accepted draft tokens, then the correction or bonus token --, lens uint32 [n]), with
+        the logits [n][n_vocab] each row's last token was chosen from as a third element when want_logits. params None: greedy; sample_params(..):
+        sampled, the slots' draw counters continuing; with penalty_params(..) as well: penalised, every emitted token recorded. What is emitted,
+        and every slot's state, draw counter and counts, are those of the plain loop of len(emitted[i]) steps: continue by feeding
+        emitted[i][-1] as the next x0."""
+        s, lens, toks = self._ragged(slots, rows)
+        n = s.size
+        stride = max(int(lens.max()) if n else 0, 1)
+        out = np.empty((n, stride), dtype=np.uint32)
+        kept = np.zeros(n, dtype=np.uint32)
+        logits = np.empty((n, self._n_vocab), dtype=np.float32) if want_logits else None
+        if not self._L.rwkv_mi_batch_eval_draft(self._ptr, s.ctypes.data_as(P_UINT32), lens.ctypes.data_as(P_UINT32), toks.ctypes.data_as(P_UINT32), n,
+                                                params, penalties, stride, ctypes.cast(out.ctypes.data, P_UINT32), kept.ctypes.data_as(P_UINT32),
+                                                ctypes.cast(_ptr(logits), P_FLOAT)):
+            self._fail("rwkv_mi_batch_eval_draft")
+        emitted = [out[i, : int(kept[i])].tolist() for i in range(n)]
+        return (emitted, kept, logits) if want_logits else (emitted, kept)
 
     # --- slot-to-slot copy and beam search (include/rwkv_mi355x.h) ---
 

@@ -59,6 +59,17 @@ row count of --n, HIP events around each device loop, the smallest of --reps run
   mode beam        ms per step of the beam loop beside the greedy loop's at the same row count from the same run, and their difference
   mode beam_host   the search driven from the host with the calls that existed before: RWKVBatch.eval with the logits to the host, a float64
                    log-softmax and the W best of each row, the selection, the states permuted with state_store / state_load; host clock
+
+--draft K[,K...] times rwkv_mi_batch_eval_draft for every draft length of the list and every n, greedy and sampled (temperature 1.0, top-p 0.8,
+seed = row), host clock around complete calls (each ends with its stream drained), the smallest of --reps runs after a warm-up run, everything
+in this process and run; records also go to --out. Drafts are cut from the true continuation, computed ahead with the plain loop, and corrupted
+so that exactly a tokens per row stand -- synthetic weights give no meaningful natural acceptance rate:
+  mode draft_plain      the plain device loops of the same n (HIP events): what the draft call has to beat
+  mode draft_overhead   one call of n rows of 1 + K tokens, every draft standing (nothing replayed) and none standing (every row replayed),
+                        against rwkv_mi_batch_eval_ragged_sample of the same shape -- the only arm when the library loaded through RWKV_LIB_DIR
+                        is a build without the call: the difference is the stash, the head on every token, the choice and the replay
+  mode draft_accept     --tokens successive calls with a in 0, 1, 2, 4, 8 (a <= K) tokens standing per row: tokens/s against the plain loop's,
+                        and break_even_a = call time / plain step time - 1, the acceptance from which the call wins
 """
 import argparse
 import json
@@ -463,6 +474,105 @@ def guide(pkg, m, args):
         sink.close()
 
 
+def draft(pkg, m, args):
+    import numpy as np
+    V = m.n_vocab
+    L = m._library.library
+    have_draft = hasattr(L, "rwkv_mi_batch_eval_draft")   # (an older build loaded through RWKV_LIB_DIR: the ragged pass and the plain loops only)
+    sink = open(args.out, "a") if args.out else None
+    ks = [int(x) for x in args.draft.split(",")]
+    ns = [int(x) for x in args.n.split(",")]
+    passes = args.tokens
+    accepts = (0, 1, 2, 4, 8)
+
+    def emit(rec):
+        rec.update({"reps": args.reps, "temperature": 1.0, "top_p": 0.8, "config": args.config, "dtype": args.dtype, "draft_in_library": have_draft})
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if sink:
+            sink.write(line + "\n")
+            sink.flush()
+
+    def corrupt(true_row, k, a):
+        d = [int(t) for t in true_row[:k]]
+        if a < k:
+            d[a] = (d[a] + 1) % V
+        return d
+
+    b = pkg.RWKVBatch(m, max(ns))
+    for n in ns:
+        slots = list(range(n))
+        first = [(7 * i + 1) % V for i in slots]
+
+        def fresh():
+            for s in slots:
+                b.state_load(s, None)
+                b.rng_seek(s, 0)
+
+        def best(run):
+            out = []
+            for _ in range(args.reps + 1):   # (run 0: warm-up -- buffers of the first call, tile-major weight images)
+                fresh()
+                out.append(run())
+            return min(out[1:])
+
+        def clocked(call):
+            def run():
+                t0 = time.perf_counter()
+                call()
+                return (time.perf_counter() - t0) * 1e3
+            return run
+
+        need = passes * (max(accepts) + 1) + max(ks) + 1
+        plain = {"greedy": best(lambda: b.decode_greedy(slots, first, 32)[1]) / 32,
+                 "sampled": best(lambda: b.decode_sample(slots, first, 32, 1.0, 0.8, slots)[1]) / 32}
+        emit({"mode": "draft_plain", "n": n, "greedy_ms_per_step": round(plain["greedy"], 4), "sampled_ms_per_step": round(plain["sampled"], 4), "steps": 32})
+        for family in ("greedy", "sampled"):
+            fresh()
+            true = (b.decode_greedy(slots, first, need) if family == "greedy" else b.decode_sample(slots, first, need, 1.0, 0.8, slots))[0]
+            params = None if family == "greedy" else pkg.sample_params(n, 1.0, 0.8, -1.0, slots)
+            temperature = 0.0 if family == "greedy" else 1.0
+            for k in ks:
+                # 1. the call's overhead: one call of n rows of 1 + k tokens against the ragged pass of the same shape that samples each row's last
+                # token -- what is added is the stash, the head on every token, the sequential choice and (where a draft falls) the replay
+                rows_all = [[first[i]] + corrupt(true[i], k, k) for i in slots]
+                rows_none = [[first[i]] + corrupt(true[i], k, 0) for i in slots]
+                ragged_ms = best(clocked(lambda: b.eval_ragged_sample(slots, rows_all, temperature, 0.8, -1.0, slots)))
+                rec = {"mode": "draft_overhead", "family": family, "n": n, "k": k, "T": n * (k + 1), "ragged_sample_ms": round(ragged_ms, 4)}
+                if have_draft:
+                    all_ms = best(clocked(lambda: b.eval_draft(slots, rows_all, params=params)))
+                    none_ms = best(clocked(lambda: b.eval_draft(slots, rows_none, params=params)))
+                    rec.update({"draft_all_accepted_ms": round(all_ms, 4), "draft_none_accepted_ms": round(none_ms, 4),
+                                "overhead_all_accepted_ms": round(all_ms - ragged_ms, 4), "overhead_none_accepted_ms": round(none_ms - ragged_ms, 4)})
+                emit(rec)
+                if not have_draft:
+                    continue
+                # 2. tokens/s as a function of acceptance: `passes` successive calls whose drafts are cut from the true continuation and corrupted
+                # so that exactly a tokens per row stand, the rows built ahead of the clock; each call emits a + 1 tokens per row
+                for a in [x for x in accepts if x <= k]:
+                    calls, pos, x0 = [], 0, list(first)
+                    for _ in range(passes):
+                        calls.append([[x0[i]] + corrupt(true[i][pos:], k, a) for i in slots])
+                        pos += a + 1
+                        x0 = [int(true[i][pos - 1]) for i in slots]
+
+                    def run():
+                        t0 = time.perf_counter()
+                        for rows in calls:
+                            _, lens = b.eval_draft(slots, rows, params=params)
+                            assert (lens == a + 1).all(), (a, lens)
+                        return (time.perf_counter() - t0) * 1e3
+                    call_ms = best(run) / passes
+                    plain_ms = plain[family]
+                    emit({"mode": "draft_accept", "family": family, "n": n, "k": k, "a": a, "passes": passes, "ms_per_call": round(call_ms, 4),
+                          "tokens_per_s": round(n * (a + 1) / (call_ms / 1e3), 1), "plain_ms_per_step": round(plain_ms, 4),
+                          "plain_tokens_per_s": round(n / (plain_ms / 1e3), 1), "speedup": round((a + 1) * plain_ms / call_ms, 3),
+                          "break_even_a": round(call_ms / plain_ms - 1.0, 3)})
+    b.free()
+    if sink:
+        sink.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("model_path")
@@ -481,8 +591,10 @@ def main():
                     help="time rwkv_mi_batch_decode_beam for each width of the list at the largest row count of --n, against the greedy loop and the host-driven search")
     ap.add_argument("--guide", action="store_true",
                     help="with --sample: time the sampled loop plain, guided on the device, and masked from the host before every token (see above)")
-    ap.add_argument("--reps", type=int, default=3, help="--ragged, --until, --logprobs, --beam, --guide: timed runs of each shape (the smallest is reported)")
-    ap.add_argument("--out", default=None, help="--ragged, --penalties, --until, --logprobs, --beam, --guide: also append the records to this file")
+    ap.add_argument("--draft", default=None, metavar="K[,K...]",
+                    help="time rwkv_mi_batch_eval_draft for each draft length of the list: its overhead over the ragged pass, tokens/s by acceptance (see above)")
+    ap.add_argument("--reps", type=int, default=3, help="--draft, --ragged, --until, --logprobs, --beam, --guide: timed runs of each shape (the smallest is reported)")
+    ap.add_argument("--out", default=None, help="--draft, --ragged, --penalties, --until, --logprobs, --beam, --guide: also append the records to this file")
     args = ap.parse_args()
 
     import __graft_entry__ as graft
@@ -511,6 +623,10 @@ def main():
         return
     if args.beam is not None:
         beam(pkg, m, args)
+        m.free()
+        return
+    if args.draft is not None:
+        draft(pkg, m, args)
         m.free()
         return
     if args.guide:

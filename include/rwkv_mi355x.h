@@ -33,7 +33,8 @@ RWKV_API bool rwkv_mi_decode_greedy(struct rwkv_context * ctx, uint32_t first_to
 
 /* Temperature / top-p sampling ON THE DEVICE from the logits of the last evaluation (the reference samples on the host:
  * python/sampling.py:10-52 -- same statements: softmax, top-p cut-off, p^(1/temperature), renormalise, draw). temperature == 0: argmax;
- * top_p == 0 means 1. u in [0, 1): the caller's uniform random number; u < 0: the context's counter-based generator with `seed`. */
+ * top_p == 0 means 1. u in [0, 1): the caller's uniform random number; u < 0: the context's counter-based generator with `seed`.
+ * top-k and min-p are not arguments but a setting of the sequence (rwkv_mi_truncation_set, below): every draw reads it. */
 RWKV_API bool rwkv_mi_sample(struct rwkv_context * ctx, float temperature, float top_p, float u, uint64_t seed, uint32_t * token_out);
 /* Sampling decode loop entirely on the device (like rwkv_mi_decode_greedy, the sampled token feeds the next embedding lookup). */
 RWKV_API bool rwkv_mi_decode_sample(struct rwkv_context * ctx, uint32_t first_token, size_t n_tokens, float temperature, float top_p, uint64_t seed,
@@ -164,7 +165,8 @@ RWKV_API bool rwkv_mi_batch_decode_greedy(struct rwkv_mi_batch * batch, const ui
                                           size_t n_tokens, uint32_t * tokens_out, float * elapsed_ms);
 
 /* Sampling in the batch, on the device: one row of parameters per row of the call, with the meaning of rwkv_mi_sample's arguments
- * (temperature == 0: argmax; top_p == 0 means 1; u in [0, 1): the caller's uniform number; u < 0: the generator uniform01(seed, counter)).
+ * (temperature == 0: argmax; top_p == 0 means 1; u in [0, 1): the caller's uniform number; u < 0: the generator uniform01(seed, counter));
+ * top-k and min-p are a setting of the slot (rwkv_mi_batch_truncation_set, below).
  * The batch owns ONE DRAW COUNTER PER SLOT (zero at rwkv_mi_batch_create): a row's draw reads and advances the counter of its slot, not of
  * its position in the call, by one per draw that is not an argmax -- a sequence's random stream does not depend on who else is in the pass
  * or in which order the slots are named. rwkv_mi_batch_eval and rwkv_mi_batch_decode_greedy never touch the counters.
@@ -340,7 +342,8 @@ RWKV_API size_t rwkv_mi_batch_last_loop_passes(const struct rwkv_mi_batch * batc
  * need (prefill once, copy n - 1 times), and how a beam caller keeps its prompt state. `what` is a bit set: the state is copied always
  * (RWKV_MI_COPY_STATE names it); _COUNTER adds the slot's draw counter, _COUNTS its occurrence table, _BIAS its bias table and whether a bias
  * is set (a batch that has never used the penalised family has neither table: every count is 0, no bias is set, and the two bits copy
- * nothing). dst == src is a no-op that returns true. An out-of-range slot or an unknown bit is RWKV_ERROR_ARGS and changes nothing. */
+ * nothing). dst == src is a no-op that returns true. An out-of-range slot or an unknown bit is RWKV_ERROR_ARGS and changes nothing.
+ * There is no bit for the truncation setting (rwkv_mi_batch_truncation_set): it is two words the caller holds, and sets on dst themselves. */
 #define RWKV_MI_COPY_STATE   1u
 #define RWKV_MI_COPY_COUNTER 2u
 #define RWKV_MI_COPY_COUNTS  4u
@@ -508,6 +511,37 @@ RWKV_API bool rwkv_mi_batch_eval_draft(struct rwkv_mi_batch * batch, const uint3
                                        const struct rwkv_mi_penalty_params * penalties  /* [n], NULL: the plain draw; needs params */,
                                        size_t stride, uint32_t * tokens_out /* [n][stride] */, uint32_t * lens_out /* [n] */,
                                        float * logits_out /* [n][n_vocab], may be NULL */);
+
+/* ---- Top-k and min-p in the device sampler: per-sequence truncation settings ----
+ * A sequence -- a slot of a batch, or a context -- carries an optional TRUNCATION SETTING {top_k, min_p}. It is kept like the slot's bias
+ * table and its guide: it stays until it is changed, and EVERY draw of that sequence reads it -- rwkv_mi_sample, rwkv_mi_decode_sample and
+ * their _penalized forms on a context; rwkv_mi_batch_eval_sample, _eval_ragged_sample, the three _penalized forms, _decode_sample, the
+ * sampled and penalised families of _decode_until and of _eval_draft (which emits what the plain loop with the same setting would), on
+ * guided slots as on others. top_k == 0 or top_k >= n_vocab: no top-k; min_p == 0: no min-p; {0, 0} is "none", the state at creation (a
+ * context made by rwkv_clone_context starts with none as well).
+ * THE ORDER: mask -> softmax -> top-p and min-p, intersected -> temperature.
+ *   top-k is a MASK on the values the draw reads. Let a[j] be what the row's draw reads today: the logit l[j]; penalised, the adjusted
+ *   adj[j]; guided, either with the guide's -inf applied. The tokens are ranked by (a descending, index ascending) -- the total order of the
+ *   report's top-N; a NaN never ranks, -inf ranks last -- and every token outside the first top_k of that order reads -inf. The sampler then
+ *   runs unchanged on these values: softmax, the top-p cut-off, the temperature power, the scan, the draw. top-p is therefore taken on the
+ *   distribution of the k survivors (the order of llama.cpp, vLLM and HF; RWKV's own pipeline cuts top-p on the FULL distribution and
+ *   applies top-k afterwards, which keeps fewer tokens). By construction the token is, bit for bit, what the sampler without a setting
+ *   picks from logits the caller had masked to -inf themselves.
+ *   min-p runs on the sampler's f32 probabilities p, beside the top-p cut-off: a token survives where p[j] >= min_p * p_max (the product
+ *   rounded to f32, p_max the largest p) AND it passes the top-p cut-off as before. Both thresholds are taken on the same distribution:
+ *   the surviving set is their intersection.
+ *   A row with temperature == 0 is an argmax; the maximum at its lowest index survives both truncations, so the setting changes nothing
+ *   there. The draw counter's rule is unchanged: one advance per draw that is not an argmax.
+ * With the setting "none" a draw is exactly the draw described above -- token, counter, counts, guide state -- and no call performs a launch,
+ * allocation or copy it did not perform before. The logits are never written; the report (rwkv_mi_*set_logprobs) still reads the model's
+ * logits; the greedy loops and beam search do not read the setting. rwkv_mi_batch_state_copy has no bit for it.
+ * set returns false with RWKV_ERROR_ARGS and changes nothing when the slot is out of range, when min_p is NaN, below 0 or above 1, or (the
+ * context forms, as the penalised context calls) on a RWKV_MI_DEVICES chain. get: either pointer may be NULL.
+ * OUT OF SCOPE: penalty decay (a float occurrence table and a new store call), typical-p and tail-free sampling. */
+RWKV_API bool rwkv_mi_batch_truncation_set(struct rwkv_mi_batch * batch, size_t slot, uint32_t top_k, float min_p);
+RWKV_API bool rwkv_mi_batch_truncation_get(struct rwkv_mi_batch * batch, size_t slot, uint32_t * top_k_out, float * min_p_out);
+RWKV_API bool rwkv_mi_truncation_set(struct rwkv_context * ctx, uint32_t top_k, float min_p);
+RWKV_API bool rwkv_mi_truncation_get(struct rwkv_context * ctx, uint32_t * top_k_out, float * min_p_out);
 
 #if defined(__cplusplus)
 }

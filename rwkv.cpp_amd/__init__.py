@@ -5,6 +5,8 @@ repo root to sys.path and use `importlib.import_module("rwkv.cpp_amd")` is NOT p
 """
 from .rwkv_cpp import (  # noqa: F401
     BeamParams,
+    CUT_HOOKS_LIB_PATH,
+    CutParams,
     DRAFT_MAX,
     GUIDE_HOOKS_LIB_PATH,
     GUIDE_MAX,

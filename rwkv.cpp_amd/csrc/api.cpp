@@ -615,6 +615,14 @@ bool DrawState::guide_words(rwkv_context * ctx, size_t slot, uint32_t * state_ou
     return true;
 }
 
+// the truncation setting of a slot: host words, read by every draw of the slot from the next call on
+bool DrawState::cut_set(rwkv_context * ctx, size_t slot, uint32_t top_k, float min_p) {
+    // (written so that a NaN fails the comparison)
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, min_p >= 0.0f && min_p <= 1.0f, "min_p (%g) must be in 0 .. 1", (double) min_p);
+    cuts[slot] = CutRow{top_k, min_p};
+    return true;
+}
+
 static bool on_device(rwkv_context * ctx) { HIP_CTX_OK(ctx, hipSetDevice(ctx->model->device)); return true; }
 
 // what every call of the single-context family starts with
@@ -649,6 +657,20 @@ RWKV_API bool rwkv_mi_rng_seek(struct rwkv_context * ctx, uint64_t counter) {
     return on_device(ctx) && ctx->draw.seek(ctx, 0, counter, ctx->stream);
 }
 
+RWKV_API bool rwkv_mi_truncation_set(struct rwkv_context * ctx, uint32_t top_k, float min_p) {
+    ctx->last_error = RWKV_ERROR_NONE;
+    RW_NO_PIPELINE(ctx, false);
+    return ctx->draw.cut_set(ctx, 0, top_k, min_p);
+}
+
+RWKV_API bool rwkv_mi_truncation_get(struct rwkv_context * ctx, uint32_t * top_k_out, float * min_p_out) {
+    ctx->last_error = RWKV_ERROR_NONE;
+    RW_NO_PIPELINE(ctx, false);
+    if (top_k_out) *top_k_out = ctx->draw.cuts[0].top_k;
+    if (min_p_out) *min_p_out = ctx->draw.cuts[0].min_p;
+    return true;
+}
+
 // the penalty of a single-context draw: the context's counts and bias enter the logits; record: the chosen token is counted
 struct Penalty { float presence, frequency; uint32_t record; };
 
@@ -657,8 +679,8 @@ static void launch_draw(rwkv_context * ctx, float temperature, float top_p, floa
     const int n_vocab = (int) ctx->model->n_vocab();
     const DrawState & d = ctx->draw;
     if (pen) launch_pen_sample(ctx->d_logits.p, n_vocab, temperature, top_p, u, seed, d.counter(0), pen->presence, pen->frequency, pen->record, d.counts_of(0),
-                               d.bias_of(0), d.probs.p, out, hist, hist_pos, ctx->stream);
-    else launch_sample(ctx->d_logits.p, n_vocab, temperature, top_p, u, seed, d.counter(0), d.probs.p, out, hist, hist_pos, ctx->stream);
+                               d.bias_of(0), d.cuts[0], d.probs.p, out, hist, hist_pos, ctx->stream);
+    else launch_sample(ctx->d_logits.p, n_vocab, temperature, top_p, u, seed, d.counter(0), d.cuts[0], d.probs.p, out, hist, hist_pos, ctx->stream);
     // the report of the token just written, slot hist_pos of the context's buffers (ensure_report has sized them)
     const LogprobReport & lp = ctx->lp;
     if (lp.enabled) launch_logprob_rows(ctx->d_logits.p, 1, n_vocab, out, (int) lp.top_n, lp.d_chosen.p + hist_pos, lp.d_ids.p + (size_t) hist_pos * lp.top_n,
@@ -1044,6 +1066,10 @@ struct rwkv_mi_batch {
     uint32_t guide_states[RWKV_MI_GUIDE_MAX] = {};   // n_states of each (0: the id is free)
     DevBuf<GuideRow> d_grows;
     PinBuf<GuideRow> h_grows;
+    // the truncation rows of a call (rwkv_mi_batch_truncation_set; the settings themselves are the draw state's host words) with their pinned
+    // staging, allocated by the first call that names a slot with a setting
+    DevBuf<CutRow> d_crows;
+    PinBuf<CutRow> h_crows;
     // ragged passes (rwkv_mi_batch_eval_ragged*): the tables of a call -- segments, the short ones again, seg_of[T], last[n] -- in one device
     // buffer with its pinned staging, grown to the largest call so far; the long segments stay on the host (each is a launch of its own)
     DevBuf<uint8_t> d_seg;
@@ -1259,6 +1285,21 @@ static bool batch_upload_guide_rows(rwkv_mi_batch * B, const BatchCall & c) {
     return true;
 }
 
+// ---- truncation settings: which calls see one (rwkv_mi_*truncation_set) ----
+
+// whether a call names a slot whose setting truncates anything (its slots have been checked)
+static bool batch_names_cut(const rwkv_mi_batch * B, const uint32_t * slots, size_t n) {
+    for (size_t i = 0; i < n; i++) if (B->draw.has_cut(slots[i])) return true;
+    return false;
+}
+
+// the truncation rows of the n named slots (after batch_upload*: the stream has been drained, the staging is free)
+static bool batch_upload_cut_rows(rwkv_mi_batch * B, const BatchCall & c) {
+    for (size_t i = 0; i < c.n; i++) B->h_crows.p[i] = B->draw.cuts[c.slots[i]];
+    BATCH_HIP_OK(B, hipMemcpyAsync(B->d_crows.p, B->h_crows.p, c.n * sizeof(CutRow), hipMemcpyHostToDevice, B->run->stream));
+    return true;
+}
+
 // what the calls on one slot's draw state start with
 static bool batch_slot_call(rwkv_mi_batch * B, size_t slot) {
     rwkv_context * ctx = B->ctx;
@@ -1402,6 +1443,10 @@ static bool batch_ensure_draw(rwkv_mi_batch * B, const BatchCall & c) {
         const hipError_t e = grow(want(B->d_grows, B->n_slots), want(B->h_grows, B->n_slots));
         RW_CTX_CHECK(B->ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the guide rows of %zu slots: %s", B->n_slots, hipGetErrorString(e));
     }
+    if (batch_names_cut(B, c.slots, c.n) && !B->d_crows) {   // the truncation rows with their pinned staging: on the first call that names a setting
+        const hipError_t e = grow(want(B->d_crows, B->n_slots), want(B->h_crows, B->n_slots));
+        RW_CTX_CHECK(B->ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the truncation rows of %zu slots: %s", B->n_slots, hipGetErrorString(e));
+    }
     return batch_ensure_draw_tables(B, c.draw == Draw::penalized);
 }
 
@@ -1411,6 +1456,7 @@ static bool batch_upload_call(rwkv_mi_batch * B, const BatchCall & c, size_t T, 
     if (c.until && !batch_upload_stops(B, c)) return false;
     if (c.draw == Draw::none) return true;
     if (batch_names_guided(B, c.slots, c.n) && !batch_upload_guide_rows(B, c)) return false;
+    if (batch_names_cut(B, c.slots, c.n) && !batch_upload_cut_rows(B, c)) return false;
     return c.draw == Draw::penalized ? batch_upload_penalty_rows(B, c, loop) : batch_upload_params(B, c, loop);
 }
 
@@ -1420,6 +1466,7 @@ static RowSampler batch_sampler(rwkv_mi_batch * B, const BatchCall & c, uint32_t
     RowSampler s;
     s.draw = c.draw; s.srows = B->d_srows.p; s.prows = B->d_prows.p; s.probs = B->draw.probs.p;
     if (c.draw != Draw::none && batch_names_guided(B, c.slots, c.n)) s.grows = B->d_grows.p;
+    if (c.draw != Draw::none && batch_names_cut(B, c.slots, c.n)) s.crows = B->d_crows.p;
     s.hist = hist; s.report = report;
     return s;
 }
@@ -1532,6 +1579,7 @@ static bool batch_draft(rwkv_mi_batch * B, const BatchCall & c, uint32_t * token
     d.stash.layer0 = m.layer_begin; d.stash.per_layer = m.state_per_layer();
     d.lw = B->d_draft_layers.p; d.logits_all = B->d_draft_logits.p;
     d.draw = c.draw; d.srows = B->d_srows.p; d.prows = B->d_prows.p; d.probs = B->draw.probs.p;
+    if (c.draw != Draw::none && batch_names_cut(B, c.slots, c.n)) d.crows = B->d_crows.p;
     d.keep = B->d_draft_words.p; d.out = B->d_draft_words.p + B->n_slots; d.out_stride = W;
     if (!forward_draft(run, B->pass, (int64_t) T, d)) return batch_fail_drained(B);
     BATCH_HIP_OK(B, hipMemcpyAsync(B->h_draft_words.p, B->d_draft_words.p, c.n * sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream));
@@ -1993,6 +2041,17 @@ RWKV_API bool rwkv_mi_batch_rng_seek(struct rwkv_mi_batch * B, size_t slot, uint
     return batch_slot_call(B, slot) && on_device(B->ctx) && B->draw.seek(B->ctx, slot, counter, B->run->stream);
 }
 
+RWKV_API bool rwkv_mi_batch_truncation_set(struct rwkv_mi_batch * B, size_t slot, uint32_t top_k, float min_p) {
+    return batch_slot_call(B, slot) && B->draw.cut_set(B->ctx, slot, top_k, min_p);
+}
+
+RWKV_API bool rwkv_mi_batch_truncation_get(struct rwkv_mi_batch * B, size_t slot, uint32_t * top_k_out, float * min_p_out) {
+    if (!batch_slot_call(B, slot)) return false;
+    if (top_k_out) *top_k_out = B->draw.cuts[slot].top_k;
+    if (min_p_out) *min_p_out = B->draw.cuts[slot].min_p;
+    return true;
+}
+
 RWKV_API bool rwkv_mi_batch_counts_reset(struct rwkv_mi_batch * B, size_t slot) {
     return batch_slot_call(B, slot) && on_device(B->ctx) && B->draw.counts_reset(B->ctx, slot, B->run->stream);
 }
@@ -2070,6 +2129,7 @@ RWKV_API bool rwkv_mi_batch_state_copy(struct rwkv_mi_batch * B, size_t dst_slot
     rwkv_context * ctx = B->ctx;
     ctx->last_error = RWKV_ERROR_NONE;
     RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, dst_slot < B->n_slots && src_slot < B->n_slots, "slot %zu or %zu is out of range", dst_slot, src_slot);
+    // (no bit for the truncation setting: it is two host words the caller sets on the destination slot themselves)
     const uint32_t known = RWKV_MI_COPY_STATE | RWKV_MI_COPY_COUNTER | RWKV_MI_COPY_COUNTS | RWKV_MI_COPY_BIAS;
     RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, (what & ~known) == 0, "unknown bits in what (0x%" PRIx32 ")", what);
     if (dst_slot == src_slot) return true;

@@ -109,38 +109,46 @@ constexpr int64_t k_mfma_min_tokens = 32;   // sequence calls of at least this m
 
 // temperature / top-p sampling on the logits in HBM (sampling.hip). u < 0: draw from the counter-based generator (seed, *counter; the
 // counter is advanced on the device). The token is written to out_token (and to hist[hist_pos] when hist is given).
+// cut: the sequence's truncation setting (CutRow below; {0, 0}: none -- the draw is the one described above).
+struct CutRow;
 void launch_sample(const float * logits, int n, float temperature, float top_p, float u, unsigned long long seed, unsigned long long * counter,
-                   float * probs, uint32_t * out_token, uint32_t * hist, int hist_pos, hipStream_t st);
+                   const CutRow & cut, float * probs, uint32_t * out_token, uint32_t * hist, int hist_pos, hipStream_t st);
 // probs: scratch of sample_scratch_floats(n) floats (the vocabulary rounded up to whole chunks of the 1024 threads: the kernel keeps it transposed).
 inline size_t sample_scratch_floats(int64_t n) { return (size_t) ((n + 1023) / 1024) * 1024; }
 // The row form (batched decode): one workgroup per row of logits[rows][n], row r with table[r]'s parameters and draw counter (the counter
 // of the row's SLOT). probs: [rows][sample_scratch_floats(n)] scratch. Row r's token goes to tokens[r] (the word its next embedding lookup
 // reads) and, when hist is given, to hist[r].
 struct SampleRow { rwkv_mi_sample_params p; unsigned long long * counter; };
+// The truncation setting of a row's sequence (rwkv_mi_*truncation_set), a table parallel to the row table as the guide rows are; a NULL table:
+// no row has one. top_k (0 or >= n: off): of the values the draw would read -- logits, adjusted logits, a guide's mask applied -- the first
+// top_k in the order (value descending, index ascending; a NaN never ranks) are read as they are, every other one as -inf. min_p (0: off):
+// of the probabilities the body computes from these, those below (float) (min_p * the largest) are cut, beside the top-p cut-off. A row
+// with temperature 0 is an argmax, which survives both: it ignores the setting.
+struct CutRow { uint32_t top_k; float min_p; };
 // live (here and in the penalised form; NULL: every row draws): rwkv_mi_batch_decode_until's per-row live words -- a row with live[r] == 0 returns
 // before it reads a logit: no draw, no counter advance, no count, no token or history word.
-void launch_sample_rows(const float * logits, int64_t rows, int n, const SampleRow * table, float * probs, uint32_t * tokens, uint32_t * hist,
-                        const uint32_t * live, hipStream_t st);
+void launch_sample_rows(const float * logits, int64_t rows, int n, const SampleRow * table, const CutRow * cuts, float * probs, uint32_t * tokens,
+                        uint32_t * hist, const uint32_t * live, hipStream_t st);
 void launch_sample_seek_rows(const SampleRow * table, int64_t rows, unsigned long long value, hipStream_t st);   // *table[r].counter = value
 // The penalised forms (rwkv_mi_*_penalized): the same draw on adj[j] = (logits[j] - (presence + (float) count[j] * frequency)) + bias[j]
 // (the penalty where count[j] > 0 only; bias == NULL: no bias), then count[token] += 1 when record is set. count: the sequence's occurrence table ([n] words), bias: its bias
 // table ([n] floats). The row table carries them per row, beside the sampler's parameters and the draw counter of the row's slot.
 struct PenaltyRow { rwkv_mi_sample_params p; unsigned long long * counter; float presence; float frequency; uint32_t record; uint32_t * count; const float * bias; };
 void launch_pen_sample(const float * logits, int n, float temperature, float top_p, float u, unsigned long long seed, unsigned long long * counter,
-                       float presence, float frequency, uint32_t record, uint32_t * count, const float * bias,
+                       float presence, float frequency, uint32_t record, uint32_t * count, const float * bias, const CutRow & cut,
                        float * probs, uint32_t * out_token, uint32_t * hist, int hist_pos, hipStream_t st);
-void launch_pen_sample_rows(const float * logits, int64_t rows, int n, const PenaltyRow * table, float * probs, uint32_t * tokens, uint32_t * hist,
-                            const uint32_t * live, hipStream_t st);
+void launch_pen_sample_rows(const float * logits, int64_t rows, int n, const PenaltyRow * table, const CutRow * cuts, float * probs, uint32_t * tokens,
+                            uint32_t * hist, const uint32_t * live, hipStream_t st);
 // The guided forms (rwkv_mi_batch_guide_*): a parallel table gives row r the dense table of its guide -- next[n_states][n], GUIDE_DEAD where
 // the transition is dead; NULL: the row has no guide and draws as the unguided kernel does -- and its slot's state and miss words. A guided
 // row in state s reads -inf for token j where next[s][j] is dead, the value of its draw elsewhere; thread 0 then moves the state to
 // next[s][token], or counts a miss when that is dead.
 constexpr uint16_t GUIDE_DEAD = 0xFFFF;
 struct GuideRow { const uint16_t * next; uint32_t * state; uint32_t * misses; };
-void launch_guided_sample_rows(const float * logits, int64_t rows, int n, const SampleRow * table, const GuideRow * guides, float * probs, uint32_t * tokens,
-                               uint32_t * hist, const uint32_t * live, hipStream_t st);
-void launch_guided_pen_sample_rows(const float * logits, int64_t rows, int n, const PenaltyRow * table, const GuideRow * guides, float * probs, uint32_t * tokens,
-                                   uint32_t * hist, const uint32_t * live, hipStream_t st);
+void launch_guided_sample_rows(const float * logits, int64_t rows, int n, const SampleRow * table, const GuideRow * guides, const CutRow * cuts, float * probs,
+                               uint32_t * tokens, uint32_t * hist, const uint32_t * live, hipStream_t st);
+void launch_guided_pen_sample_rows(const float * logits, int64_t rows, int n, const PenaltyRow * table, const GuideRow * guides, const CutRow * cuts, float * probs,
+                                   uint32_t * tokens, uint32_t * hist, const uint32_t * live, hipStream_t st);
 // next[n_states][n_vocab] from the edges in CSR form on the device (checked by the caller: tokens < n_vocab and distinct per state, next < n_states)
 void launch_guide_expand(uint16_t * next, uint32_t n_states, int n_vocab, const uint32_t * edge_begin, const uint32_t * edge_tokens, const uint32_t * edge_next,
                          hipStream_t st);
@@ -200,11 +208,17 @@ struct DrawState {
     std::vector<uint32_t> guide_of;        // [slots]
     DevBuf<uint32_t> guide_state;          // [slots]
     DevBuf<uint32_t> guide_misses;         // [slots]
+    // the truncation settings (rwkv_mi_*truncation_set): host words only, {0, 0} -- none -- from init() on; every draw of the slot reads them
+    std::vector<CutRow> cuts;              // [slots]
 
-    void init(size_t n_slots, size_t vocab) { slots = n_slots; n_vocab = vocab; has_bias.assign(n_slots, 0); guide_of.assign(n_slots, RWKV_MI_NO_GUIDE); }
+    void init(size_t n_slots, size_t vocab) {
+        slots = n_slots; n_vocab = vocab; has_bias.assign(n_slots, 0); guide_of.assign(n_slots, RWKV_MI_NO_GUIDE); cuts.assign(n_slots, CutRow{0u, 0.0f});
+    }
     unsigned long long * counter(size_t slot) const { return counters.p + slot; }
     uint32_t * counts_of(size_t slot) const { return counts.p + slot * n_vocab; }
     const float * bias_of(size_t slot) const { return has_bias[slot] ? bias.p + slot * n_vocab : nullptr; }   // NULL: none is set
+    // whether the slot's setting truncates anything (top_k == 0 or >= n_vocab: no top-k; min_p == 0: no min-p)
+    bool has_cut(size_t slot) const { return (cuts[slot].top_k != 0u && cuts[slot].top_k < n_vocab) || cuts[slot].min_p != 0.0f; }
 
     bool ensure_counters(rwkv_context * ctx, hipStream_t st);
     bool ensure_sampler(rwkv_context * ctx, hipStream_t st);   // the counters and the scratch
@@ -218,6 +232,7 @@ struct DrawState {
     // attaches `guide` in `state` (checked by the caller) or, with RWKV_MI_NO_GUIDE, detaches; the slot's miss counter starts from 0 either way
     bool guide_attach(rwkv_context * ctx, size_t slot, uint32_t guide, uint32_t state, hipStream_t st);
     bool guide_words(rwkv_context * ctx, size_t slot, uint32_t * state_out, uint32_t * misses_out, hipStream_t st);   // (0, 0 without a guide)
+    bool cut_set(rwkv_context * ctx, size_t slot, uint32_t top_k, float min_p);   // min_p in [0, 1], or RWKV_ERROR_ARGS and nothing changed
 };
 
 // Loads [layer_begin, layer_end) of the file (layer_end == UINT32_MAX: all layers) onto the current HIP device.
@@ -361,7 +376,8 @@ void batch_context_destroy(rwkv_context * c);
 // What follows the head of a batch pass over `rows` rows (launch_row_sampler), described once: row r's token goes to ctx->d_tokens.p[r].
 //   draw    which choice is made: the greedy argmax (none), the sampler (sample: srows, launch_sample_rows) or the penalised sampler
 //           (penalized: prows, launch_pen_sample_rows); probs: the samplers' scratch; grows (NULL: no named slot has a guide): the guide rows,
-//           with which the guided form of either sampler is launched instead
+//           with which the guided form of either sampler is launched instead; crows (NULL: no named slot has a truncation setting): the
+//           settings of the rows, which every form of the sampler takes
 //   hist, report, step   the call's WHOLE history [steps][rows] and report buffers (chosen [steps][rows], ids / vals [steps][rows][top_n]), either
 //           may be NULL, and the step of the call this pass is: the step's slot of each is written. A single pass is step 0
 //   stop    the pass is a step of rwkv_mi_batch_decode_until: the choice and the report run behind the live words and launch_stop_rows follows them
@@ -377,6 +393,7 @@ struct RowSampler {
     const SampleRow * srows = nullptr;
     const PenaltyRow * prows = nullptr;
     const GuideRow * grows = nullptr;   // the call names a guided slot: the guided form of the sampler runs on this parallel table
+    const CutRow * crows = nullptr;     // the call names a slot with a truncation setting: the rows' settings, parallel to the row table
     float * probs = nullptr;
     uint32_t * hist = nullptr;
     const RowReport * report = nullptr;
@@ -416,13 +433,15 @@ struct DraftPass {
     Draw draw = Draw::none;
     const SampleRow * srows = nullptr;
     const PenaltyRow * prows = nullptr;
+    const CutRow * crows = nullptr;     // the rows' truncation settings as in RowSampler (NULL: none), read at every position walked
     float * probs = nullptr;
     uint32_t * out = nullptr;
     int out_stride = 0;
     uint32_t * keep = nullptr;
 };
 void launch_draft_accept_rows(const float * logits, int64_t rows, int n, const SegState * segs, const uint32_t * tokens, Draw draw, const SampleRow * srows,
-                              const PenaltyRow * prows, float * probs, uint32_t * out, int out_stride, uint32_t * keep, float * logits_row, hipStream_t st);
+                              const PenaltyRow * prows, const CutRow * cuts, float * probs, uint32_t * out, int out_stride, uint32_t * keep, float * logits_row,
+                              hipStream_t st);
 // inputs of a layer's WKV body a pass stashes (DraftStash::n_in): 3, 3, 4, 6 for RWKV-4, 5, 6, 7
 inline int draft_stash_inputs(const Model & m) { return m.arch_major == 7 ? 6 : (m.arch_major == 6 ? 4 : 3); }
 bool forward_draft(rwkv_context * ctx, const SegPass & p, int64_t T, const DraftPass & d);

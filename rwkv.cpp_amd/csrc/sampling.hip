@@ -1,5 +1,5 @@
-// sampling.hip -- temperature / top-p sampling on the device (the reference samples on the host from downloaded logits,
-// python/sampling.py:10-52): softmax, nucleus cut-off, p^(1/temperature), renormalise, draw -- one launch of one workgroup on the
+// sampling.hip -- temperature / top-k / top-p / min-p sampling on the device (the reference samples on the host from downloaded logits,
+// python/sampling.py:10-52): [top-k mask,] softmax, nucleus cut-off [and min-p], p^(1/temperature), renormalise, draw -- one launch of one workgroup on the
 // logits that are already in HBM; the chosen token lands where the next embedding lookup reads it, so a sampling decode loop
 // never leaves the device (rwkv_mi_decode_sample). Semantics follow sample_probs() statement by statement:
 //   probs = softmax(logits);  top_p == 0 -> 1;  temperature == 0 -> argmax;
@@ -19,6 +19,11 @@
 // row -- stop sequence or budget -- by rewriting its entries of the two row tables on the device.
 // Guided draws (k_guided_sample_rows / k_guided_pen_sample_rows, rwkv_mi_batch_guide_*): a row whose slot has a guide attached, in state s,
 // reads -inf instead of the value above wherever the guide's next(s, j) is dead, and moves its state to next(s, token) afterwards.
+// Truncation settings (rwkv_mi_*truncation_set; the k_cut_* forms of the four entry points above, the guided forms and the draft walk take the
+// row's CutRow {top_k, min_p}, by value or from a table parallel to the row table; a call that names no setting launches what it launched before): mask -> softmax -> top-p and min-p, intersected -> temperature. A row with top-k on runs
+// select_stage in front of the body -- of the values above, all but the first top_k in the order (value descending, index ascending) read
+// -inf -- and the body on the stash; min-p is one more threshold of the body, p >= (float) (min_p * p_max), combined with the top-p
+// cut-off as the larger bit pattern. {0, 0}: the draw above, statement for statement.
 // The logits themselves are never written.
 #include "kdev.h"
 #include "model.h"
@@ -59,6 +64,7 @@ struct ProbVec {
 // Where sample_body takes the logit of element j of the thread's chunk from: first() in the pass that finds the maximum, again() in the
 // pass that exponentiates. The plain source loads the logit both times.
 struct PlainLogits {
+    static constexpr bool stashes = false;   // (whether first() leaves the value in the scratch vector: the select stage stores it where not)
     const float * lg;
     __device__ __forceinline__ float first(int j, const ProbVec &) const { return lg[j]; }
     __device__ __forceinline__ float again(int j, const ProbVec &) const { return lg[j]; }
@@ -68,6 +74,7 @@ struct PlainLogits {
 // the three tables, so the 64 lanes of a load touch 64 cache lines each time, while the scratch is laid out for the passes -- the stash
 // costs one coalesced store and load per element and saves three such loads; the arithmetic is the same either way.
 struct PenalisedLogits {
+    static constexpr bool stashes = true;
     const float * lg; const uint32_t * count; const float * bias /* may be NULL */; float presence, frequency;
     __device__ __forceinline__ float first(int j, const ProbVec & pr) const {
         float a = lg[j];
@@ -86,6 +93,7 @@ struct PenalisedLogits {
 // first() stashes the value as the penalised source does, so again() neither reads the table a second time nor derives the value again.
 template <class Inner>
 struct GuidedLogits {
+    static constexpr bool stashes = true;
     Inner in; const uint16_t * nx /* may be NULL */;
     __device__ __forceinline__ float first(int j, const ProbVec & pr) const {
         float a = in.first(j, pr);
@@ -95,6 +103,87 @@ struct GuidedLogits {
     }
     __device__ __forceinline__ float again(int j, const ProbVec & pr) const { return pr.get(j); }
 };
+
+// What sample_body reads behind the select stage: the scratch vector in both passes (the stage has left the masked values there).
+struct StashedLogits {
+    __device__ __forceinline__ float first(int j, const ProbVec & pr) const { return pr.get(j); }
+    __device__ __forceinline__ float again(int j, const ProbVec & pr) const { return pr.get(j); }
+};
+
+// The order of top-k as an unsigned key: a larger value has a larger key, equal values (+0 and -0 among them) the same one, -inf the
+// smallest key a number has, and a NaN -- which never ranks -- 0, below all of them.
+__device__ __forceinline__ uint32_t rank_key(float a) {
+    if (a != a) return 0u;
+    if (a == 0.0f) return 0x80000000u;
+    const uint32_t b = __float_as_uint(a);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+// The select stage of a row with top-k on (0 < k < n), in front of sample_body: the values the draw would read -- src.first() over the
+// thread's chunk, stashed in the scratch vector -- are ranked by (value descending, index ascending), and every one outside the first k is
+// overwritten with -inf. The k-th largest key is found exactly by a byte-radix select, most significant byte first: a 256-bin histogram in
+// LDS of the keys that share the prefix found so far (integer atomics: the counts do not depend on the order of arrival), from which wave
+// 0 takes the bin that holds the k-th largest and the number of keys above it. The keys above the k-th largest number k - need, so `need`
+// of the tied class survive: its members get ranks by index -- a thread's chunk is a contiguous ascending range, so a per-thread count, an
+// exclusive scan over the threads and a walk of the chunk give them -- unless the whole class survives, when no rank is needed. A NaN is
+// always dropped. Every thread takes the same branches (k and the LDS words are uniform); the stage ends behind a barrier, so its LDS
+// words are fenced from the body's.
+template <class Src>
+__device__ __forceinline__ void select_stage(const Src & src, int cnt, uint32_t k, const ProbVec & pr) {
+    __shared__ uint32_t c_hist[256];
+    __shared__ uint32_t c_wave[16];
+    __shared__ uint32_t c_digit, c_above, c_class;
+    const int tid = threadIdx.x;
+    for_chunk(cnt, [&](int j) { const float a = src.first(j, pr); if (!Src::stashes) pr.set(j, a); });
+    uint32_t kth = 0u, need = k, tied = 0u;   // kth: the prefix of the k-th largest key; need: how many of the keys with that prefix survive
+    for (int shift = 24; shift >= 0; shift -= 8) {
+        if (tid < 256) c_hist[tid] = 0u;
+        __syncthreads();
+        const uint32_t above_mask = shift == 24 ? 0u : 0xFFFFFFFFu << (shift + 8);
+        for_chunk(cnt, [&](int j) {
+            const uint32_t key = rank_key(pr.get(j));
+            if ((key & above_mask) == kth) atomicAdd(&c_hist[(key >> shift) & 255u], 1u);
+        });
+        __syncthreads();
+        if (tid < 64) {
+            // lane l holds bins 4 l .. 4 l + 3; suf: the keys in the bins of the lanes from l on, above: in those of the lanes behind l
+            uint32_t h[4];
+            for (int b = 0; b < 4; b++) h[b] = c_hist[4 * tid + b];
+            const uint32_t own = h[0] + h[1] + h[2] + h[3];
+            uint32_t suf = own;
+            for (int o = 1; o < 64; o <<= 1) { const uint32_t v = __shfl_down(suf, o, WAVE); if (tid + o < 64) suf += v; }
+            uint32_t above = suf - own;
+            if (above < need && suf >= need) {   // (exactly one lane: the keys with the prefix number at least need >= 1)
+                int b = 3;
+                while (b > 0 && above + h[b] < need) { above += h[b]; b--; }
+                c_digit = (uint32_t) (4 * tid + b); c_above = above; c_class = h[b];
+            }
+        }
+        __syncthreads();
+        kth |= c_digit << shift;
+        need -= c_above;
+        tied = c_class;
+    }
+    // need of the `tied` keys equal to kth survive, the lowest indices first
+    uint32_t rank = 0u;
+    if (tied != need) {
+        uint32_t mine = 0u;
+        for_chunk(cnt, [&](int j) { mine += rank_key(pr.get(j)) == kth ? 1u : 0u; });
+        uint32_t inc = mine;
+        for (int o = 1; o < 64; o <<= 1) { const uint32_t v = __shfl_up(inc, o, WAVE); if ((tid & 63) >= o) inc += v; }
+        if ((tid & 63) == 63) c_wave[tid >> 6] = inc;
+        __syncthreads();
+        rank = inc - mine;
+        for (int w = 0; w < (tid >> 6); w++) rank += c_wave[w];
+    }
+    for_chunk(cnt, [&](int j) {
+        const uint32_t key = rank_key(pr.get(j));
+        bool keep = key > kth;
+        if (key == kth) { keep = rank < need; rank++; }
+        if (!keep || key == 0u) pr.set(j, -INFINITY);
+    });
+    __syncthreads();
+}
 
 // What thread 0 does to a guided row's words after the draw (where the penalised rows count the token): the state moves along the picked
 // token's transition; a dead pick -- all-NaN logits, or a caller's -inf bias on every allowed token -- leaves it and counts a miss. The
@@ -111,7 +200,7 @@ __device__ __forceinline__ void guide_advance(const GuideRow & g, const uint16_t
 // of a load touch two cache lines instead of 64 (a thread's chunk is contiguous in the logits; ~35 passes run over the probabilities).
 // make_src(i0): the logit source of the thread whose chunk starts at token i0 (PlainLogits or PenalisedLogits).
 template <class MakeSrc>
-__device__ __forceinline__ int sample_body(MakeSrc && make_src, int n, float temperature, float top_p, float u_in,
+__device__ __forceinline__ int sample_body(MakeSrc && make_src, int n, float temperature, float top_p, float min_p /* 0: none */, float u_in,
                                            unsigned long long seed, unsigned long long * counter /* read and advanced by thread 0; may be NULL */,
                                            float * __restrict__ probs /* scratch of C * 1024 >= n floats, C = ceil(n / 1024) */,
                                            uint32_t * __restrict__ out_token, uint32_t * __restrict__ hist_word /* may be NULL */) {
@@ -176,6 +265,19 @@ __device__ __forceinline__ int sample_body(MakeSrc && make_src, int n, float tem
             }
             cutoff_bits = none ? __float_as_uint(1.0f * inv) : T;
         }
+        if (min_p != 0.0f) {
+            // min-p, on the same distribution as the top-p cut-off: p survives where p >= (float) (min_p * p_max) as well -- the larger of
+            // the two thresholds' bit patterns (non-negative floats: bit order = value order) in front of the pass below
+            float pm = 0.0f;
+            for_chunk(cnt, [&](int j) { pm = fmaxf(pm, pr.get(j)); });
+            for (int o = 32; o > 0; o >>= 1) pm = fmaxf(pm, __shfl_xor(pm, o, WAVE));
+            __syncthreads();
+            if ((tid & 63) == 0) red[tid >> 6] = pm;
+            __syncthreads();
+            for (int w = 0; w < (NT >> 6); w++) pm = fmaxf(pm, red[w]);
+            const unsigned floor_bits = __float_as_uint(min_p * pm);
+            if (floor_bits > cutoff_bits) cutoff_bits = floor_bits;
+        }
         const float it = 1.0f / temperature;
         part = 0.0f;
         for_chunk(cnt, [&](int j) {
@@ -227,10 +329,38 @@ __device__ __forceinline__ int sample_body(MakeSrc && make_src, int n, float tem
     return pick;
 }
 
+// The draw of a sequence with the truncation setting `cut` (model.h, CutRow): a row with top-k on runs the select stage on its source and
+// then the body on the stash; every other row runs the body on its source, exactly as before there were settings -- {0, 0} is that draw,
+// statement for statement. min-p is the body's. A row with temperature 0 is an argmax, which both truncations keep: it skips the stage
+// (and never reaches the body's min-p). The setting is the row's, so the whole workgroup takes one branch.
+template <class MakeSrc>
+__device__ __forceinline__ int cut_sample(MakeSrc && make_src, const CutRow & cut, int n, float temperature, float top_p, float u_in,
+                                          unsigned long long seed, unsigned long long * counter, float * __restrict__ probs,
+                                          uint32_t * __restrict__ out_token, uint32_t * __restrict__ hist_word) {
+    if (cut.top_k == 0u || cut.top_k >= (uint32_t) n || temperature == 0.0f)
+        return sample_body(make_src, n, temperature, top_p, cut.min_p, u_in, seed, counter, probs, out_token, hist_word);
+    const int tid = threadIdx.x, NT = blockDim.x;
+    const int C = (n + NT - 1) / NT;   // (the body's chunks)
+    const int i0 = tid * C, i1 = i0 + C < n ? i0 + C : n;
+    select_stage(make_src(i0), i1 - i0, cut.top_k, ProbVec{probs + tid, NT});
+    return sample_body([](int) { return StashedLogits{}; }, n, temperature, top_p, cut.min_p, u_in, seed, counter, probs, out_token, hist_word);
+}
+
 __global__ __launch_bounds__(1024) void k_sample(const float * __restrict__ logits, int n, float temperature, float top_p, float u_in,
                                                  unsigned long long seed, unsigned long long * counter,
                                                  float * __restrict__ probs, uint32_t * __restrict__ out_token, uint32_t * __restrict__ hist, int hist_pos) {
-    sample_body([=](int i0) { return PlainLogits{logits + i0}; }, n, temperature, top_p, u_in, seed, counter, probs, out_token, hist ? hist + hist_pos : nullptr);
+    sample_body([=](int i0) { return PlainLogits{logits + i0}; }, n, temperature, top_p, 0.0f, u_in, seed, counter, probs, out_token, hist ? hist + hist_pos : nullptr);
+}
+
+// The truncating forms of the four draw entry points (k_cut_*): the entry point above or below with the sequence's setting -- by value for a
+// context, whose setting is host words; from a table parallel to the row table for the row forms. They are entry points of their own, not an
+// argument of the old ones: a call that names no setting launches the kernel it launched before there were settings, registers and all
+// (tests/test_cpu_batch_until.py pins the four's register counts). The guided forms and the draft walk, younger and unpinned, take the
+// table as an argument that may be NULL.
+__global__ __launch_bounds__(1024) void k_cut_sample(const float * __restrict__ logits, int n, float temperature, float top_p, float u_in,
+                                                     unsigned long long seed, unsigned long long * counter, CutRow cut,
+                                                     float * __restrict__ probs, uint32_t * __restrict__ out_token, uint32_t * __restrict__ hist, int hist_pos) {
+    cut_sample([=](int i0) { return PlainLogits{logits + i0}; }, cut, n, temperature, top_p, u_in, seed, counter, probs, out_token, hist ? hist + hist_pos : nullptr);
 }
 
 // Row form: grid = rows, one workgroup per row; row r's probabilities in its own stretch of the scratch (stride floats apart, the batch owns it).
@@ -243,7 +373,19 @@ __global__ __launch_bounds__(1024) void k_sample_rows(const float * __restrict__
     if (live && !live[r]) return;
     const rwkv_mi_sample_params p = table[r].p;
     const float * lg = logits + r * (size_t) n;
-    sample_body([=](int i0) { return PlainLogits{lg + i0}; }, n, p.temperature, p.top_p, p.u, p.seed, table[r].counter, probs + r * stride, tokens + r, hist ? hist + r : nullptr);
+    sample_body([=](int i0) { return PlainLogits{lg + i0}; }, n, p.temperature, p.top_p, 0.0f, p.u, p.seed, table[r].counter, probs + r * stride, tokens + r, hist ? hist + r : nullptr);
+}
+
+__global__ __launch_bounds__(1024) void k_cut_sample_rows(const float * __restrict__ logits, int n, const SampleRow * __restrict__ table,
+                                                          const CutRow * __restrict__ cuts, float * __restrict__ probs, size_t stride,
+                                                          uint32_t * __restrict__ tokens, uint32_t * __restrict__ hist, const uint32_t * __restrict__ live) {
+    const size_t r = blockIdx.x;
+    if (live && !live[r]) return;
+    const rwkv_mi_sample_params p = table[r].p;
+    const float * lg = logits + r * (size_t) n;
+    const CutRow cut = cuts[r];
+    cut_sample([=](int i0) { return PlainLogits{lg + i0}; }, cut, n, p.temperature, p.top_p, p.u, p.seed, table[r].counter, probs + r * stride, tokens + r,
+               hist ? hist + r : nullptr);
 }
 
 // The penalised entry points: the same body on the adjusted logits, then -- when `record` is set -- the chosen token's count goes up by
@@ -253,7 +395,16 @@ __global__ __launch_bounds__(1024) void k_pen_sample(const float * __restrict__ 
                                                      uint32_t * count, const float * __restrict__ bias,
                                                      float * __restrict__ probs, uint32_t * __restrict__ out_token, uint32_t * __restrict__ hist, int hist_pos) {
     const int pick = sample_body([=](int i0) { return PenalisedLogits{logits + i0, count + i0, bias ? bias + i0 : nullptr, presence, frequency}; },
-                                 n, temperature, top_p, u_in, seed, counter, probs, out_token, hist ? hist + hist_pos : nullptr);
+                                 n, temperature, top_p, 0.0f, u_in, seed, counter, probs, out_token, hist ? hist + hist_pos : nullptr);
+    if (threadIdx.x == 0 && record) count[pick] += 1u;
+}
+
+__global__ __launch_bounds__(1024) void k_cut_pen_sample(const float * __restrict__ logits, int n, float temperature, float top_p, float u_in,
+                                                         unsigned long long seed, unsigned long long * counter, float presence, float frequency, uint32_t record,
+                                                         uint32_t * count, const float * __restrict__ bias, CutRow cut,
+                                                         float * __restrict__ probs, uint32_t * __restrict__ out_token, uint32_t * __restrict__ hist, int hist_pos) {
+    const int pick = cut_sample([=](int i0) { return PenalisedLogits{logits + i0, count + i0, bias ? bias + i0 : nullptr, presence, frequency}; },
+                                cut, n, temperature, top_p, u_in, seed, counter, probs, out_token, hist ? hist + hist_pos : nullptr);
     if (threadIdx.x == 0 && record) count[pick] += 1u;
 }
 
@@ -266,7 +417,20 @@ __global__ __launch_bounds__(1024) void k_pen_sample_rows(const float * __restri
     const PenaltyRow row = table[r];
     const float * lg = logits + r * (size_t) n;
     const int pick = sample_body([=](int i0) { return PenalisedLogits{lg + i0, row.count + i0, row.bias ? row.bias + i0 : nullptr, row.presence, row.frequency}; },
-                                 n, row.p.temperature, row.p.top_p, row.p.u, row.p.seed, row.counter, probs + r * stride, tokens + r, hist ? hist + r : nullptr);
+                                 n, row.p.temperature, row.p.top_p, 0.0f, row.p.u, row.p.seed, row.counter, probs + r * stride, tokens + r, hist ? hist + r : nullptr);
+    if (threadIdx.x == 0 && row.record) row.count[pick] += 1u;
+}
+
+__global__ __launch_bounds__(1024) void k_cut_pen_sample_rows(const float * __restrict__ logits, int n, const PenaltyRow * __restrict__ table,
+                                                              const CutRow * __restrict__ cuts, float * __restrict__ probs, size_t stride,
+                                                              uint32_t * __restrict__ tokens, uint32_t * __restrict__ hist, const uint32_t * __restrict__ live) {
+    const size_t r = blockIdx.x;
+    if (live && !live[r]) return;
+    const PenaltyRow row = table[r];
+    const CutRow cut = cuts[r];
+    const float * lg = logits + r * (size_t) n;
+    const int pick = cut_sample([=](int i0) { return PenalisedLogits{lg + i0, row.count + i0, row.bias ? row.bias + i0 : nullptr, row.presence, row.frequency}; },
+                                cut, n, row.p.temperature, row.p.top_p, row.p.u, row.p.seed, row.counter, probs + r * stride, tokens + r, hist ? hist + r : nullptr);
     if (threadIdx.x == 0 && row.record) row.count[pick] += 1u;
 }
 
@@ -275,33 +439,37 @@ __global__ __launch_bounds__(1024) void k_pen_sample_rows(const float * __restri
 // GuidedLogits on row s of the guide's table; a row without one (next == NULL) picks, bit for bit, what the unguided kernel picks.
 // live: as k_sample_rows -- a retired row does not advance its guide either.
 __global__ __launch_bounds__(1024) void k_guided_sample_rows(const float * __restrict__ logits, int n, const SampleRow * __restrict__ table,
-                                                             const GuideRow * __restrict__ guides, float * __restrict__ probs, size_t stride,
+                                                             const GuideRow * __restrict__ guides, const CutRow * __restrict__ cuts /* may be NULL */,
+                                                             float * __restrict__ probs, size_t stride,
                                                              uint32_t * __restrict__ tokens, uint32_t * __restrict__ hist, const uint32_t * __restrict__ live) {
     const size_t r = blockIdx.x;
     if (live && !live[r]) return;
     const rwkv_mi_sample_params p = table[r].p;
     const GuideRow g = guides[r];
+    const CutRow cut = cuts ? cuts[r] : CutRow{0u, 0.0f};
     const uint16_t * srow = g.next ? g.next + (size_t) *g.state * (size_t) n : nullptr;
     const float * lg = logits + r * (size_t) n;
-    const int pick = sample_body([=](int i0) { return GuidedLogits<PlainLogits>{PlainLogits{lg + i0}, srow ? srow + i0 : nullptr}; },
-                                 n, p.temperature, p.top_p, p.u, p.seed, table[r].counter, probs + r * stride, tokens + r, hist ? hist + r : nullptr);
+    const int pick = cut_sample([=](int i0) { return GuidedLogits<PlainLogits>{PlainLogits{lg + i0}, srow ? srow + i0 : nullptr}; },
+                                cut, n, p.temperature, p.top_p, p.u, p.seed, table[r].counter, probs + r * stride, tokens + r, hist ? hist + r : nullptr);
     if (threadIdx.x == 0 && srow) guide_advance(g, srow, pick);
 }
 
 __global__ __launch_bounds__(1024) void k_guided_pen_sample_rows(const float * __restrict__ logits, int n, const PenaltyRow * __restrict__ table,
-                                                                 const GuideRow * __restrict__ guides, float * __restrict__ probs, size_t stride,
+                                                                 const GuideRow * __restrict__ guides, const CutRow * __restrict__ cuts /* may be NULL */,
+                                                                 float * __restrict__ probs, size_t stride,
                                                                  uint32_t * __restrict__ tokens, uint32_t * __restrict__ hist, const uint32_t * __restrict__ live) {
     const size_t r = blockIdx.x;
     if (live && !live[r]) return;
     const PenaltyRow row = table[r];
     const GuideRow g = guides[r];
+    const CutRow cut = cuts ? cuts[r] : CutRow{0u, 0.0f};
     const uint16_t * srow = g.next ? g.next + (size_t) *g.state * (size_t) n : nullptr;
     const float * lg = logits + r * (size_t) n;
-    const int pick = sample_body([=](int i0) {
-                                     return GuidedLogits<PenalisedLogits>{PenalisedLogits{lg + i0, row.count + i0, row.bias ? row.bias + i0 : nullptr, row.presence, row.frequency},
-                                                                          srow ? srow + i0 : nullptr};
-                                 },
-                                 n, row.p.temperature, row.p.top_p, row.p.u, row.p.seed, row.counter, probs + r * stride, tokens + r, hist ? hist + r : nullptr);
+    const int pick = cut_sample([=](int i0) {
+                                    return GuidedLogits<PenalisedLogits>{PenalisedLogits{lg + i0, row.count + i0, row.bias ? row.bias + i0 : nullptr, row.presence, row.frequency},
+                                                                         srow ? srow + i0 : nullptr};
+                                },
+                                cut, n, row.p.temperature, row.p.top_p, row.p.u, row.p.seed, row.counter, probs + r * stride, tokens + r, hist ? hist + r : nullptr);
     if (threadIdx.x == 0 && row.record) row.count[pick] += 1u;
     if (threadIdx.x == 0 && srow) guide_advance(g, srow, pick);
 }
@@ -339,11 +507,13 @@ __device__ __forceinline__ int draft_argmax(const float * lg, int n) {
 template <int FAMILY>
 __global__ __launch_bounds__(1024) void k_draft_accept_rows(const float * __restrict__ logits, int n, const SegState * __restrict__ segs,
                                                             const uint32_t * __restrict__ tokens, const SampleRow * __restrict__ srows,
-                                                            const PenaltyRow * __restrict__ prows, float * __restrict__ probs, size_t stride,
+                                                            const PenaltyRow * __restrict__ prows, const CutRow * __restrict__ cuts /* may be NULL */,
+                                                            float * __restrict__ probs, size_t stride,
                                                             uint32_t * __restrict__ out, int out_stride, uint32_t * __restrict__ keep,
                                                             float * __restrict__ logits_row) {
     const size_t r = blockIdx.x;
     const SegState seg = segs[r];
+    const CutRow cut = FAMILY != 0 && cuts ? cuts[r] : CutRow{0u, 0.0f};
     const int k = seg.t1 - seg.t0 - 1;
     uint32_t * o = out + r * (size_t) out_stride;
     int j = 0;
@@ -355,11 +525,11 @@ __global__ __launch_bounds__(1024) void k_draft_accept_rows(const float * __rest
             if (threadIdx.x == 0) o[j] = (uint32_t) pick;
         } else if (FAMILY == 1) {
             const rwkv_mi_sample_params p = srows[r].p;
-            pick = sample_body([=](int i0) { return PlainLogits{lg + i0}; }, n, p.temperature, p.top_p, p.u, p.seed, srows[r].counter, probs + r * stride, o + j, nullptr);
+            pick = cut_sample([=](int i0) { return PlainLogits{lg + i0}; }, cut, n, p.temperature, p.top_p, p.u, p.seed, srows[r].counter, probs + r * stride, o + j, nullptr);
         } else {
             const PenaltyRow row = prows[r];
-            pick = sample_body([=](int i0) { return PenalisedLogits{lg + i0, row.count + i0, row.bias ? row.bias + i0 : nullptr, row.presence, row.frequency}; },
-                               n, row.p.temperature, row.p.top_p, row.p.u, row.p.seed, row.counter, probs + r * stride, o + j, nullptr);
+            pick = cut_sample([=](int i0) { return PenalisedLogits{lg + i0, row.count + i0, row.bias ? row.bias + i0 : nullptr, row.presence, row.frequency}; },
+                              cut, n, row.p.temperature, row.p.top_p, row.p.u, row.p.seed, row.counter, probs + r * stride, o + j, nullptr);
             if (threadIdx.x == 0) row.count[pick] += 1u;
         }
         if (j == k || (uint32_t) pick != tokens[seg.t0 + j + 1]) break;
@@ -434,41 +604,49 @@ __global__ __launch_bounds__(64) void k_sample_seek_rows(const SampleRow * __res
 }
 
 void launch_sample(const float * logits, int n, float temperature, float top_p, float u, unsigned long long seed, unsigned long long * counter,
-                   float * probs, uint32_t * out_token, uint32_t * hist, int hist_pos, hipStream_t st) {
-    hipLaunchKernelGGL(k_sample, dim3(1), dim3(1024), 0, st, logits, n, temperature, top_p, u, seed, counter, probs, out_token, hist, hist_pos);
+                   const CutRow & cut, float * probs, uint32_t * out_token, uint32_t * hist, int hist_pos, hipStream_t st) {
+    if (cut.top_k == 0u && cut.min_p == 0.0f) hipLaunchKernelGGL(k_sample, dim3(1), dim3(1024), 0, st, logits, n, temperature, top_p, u, seed, counter, probs, out_token, hist, hist_pos);
+    else hipLaunchKernelGGL(k_cut_sample, dim3(1), dim3(1024), 0, st, logits, n, temperature, top_p, u, seed, counter, cut, probs, out_token, hist, hist_pos);
 }
 
-void launch_sample_rows(const float * logits, int64_t rows, int n, const SampleRow * table, float * probs, uint32_t * tokens, uint32_t * hist,
-                        const uint32_t * live, hipStream_t st) {
-    hipLaunchKernelGGL(k_sample_rows, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, table, probs, sample_scratch_floats(n), tokens, hist, live);
+void launch_sample_rows(const float * logits, int64_t rows, int n, const SampleRow * table, const CutRow * cuts, float * probs, uint32_t * tokens,
+                        uint32_t * hist, const uint32_t * live, hipStream_t st) {
+    if (!cuts) hipLaunchKernelGGL(k_sample_rows, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, table, probs, sample_scratch_floats(n), tokens, hist, live);
+    else hipLaunchKernelGGL(k_cut_sample_rows, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, table, cuts, probs, sample_scratch_floats(n), tokens, hist, live);
 }
 
 void launch_pen_sample(const float * logits, int n, float temperature, float top_p, float u, unsigned long long seed, unsigned long long * counter,
-                       float presence, float frequency, uint32_t record, uint32_t * count, const float * bias,
+                       float presence, float frequency, uint32_t record, uint32_t * count, const float * bias, const CutRow & cut,
                        float * probs, uint32_t * out_token, uint32_t * hist, int hist_pos, hipStream_t st) {
-    hipLaunchKernelGGL(k_pen_sample, dim3(1), dim3(1024), 0, st, logits, n, temperature, top_p, u, seed, counter, presence, frequency, record, count, bias,
-                       probs, out_token, hist, hist_pos);
+    if (cut.top_k == 0u && cut.min_p == 0.0f)
+        hipLaunchKernelGGL(k_pen_sample, dim3(1), dim3(1024), 0, st, logits, n, temperature, top_p, u, seed, counter, presence, frequency, record, count, bias,
+                           probs, out_token, hist, hist_pos);
+    else
+        hipLaunchKernelGGL(k_cut_pen_sample, dim3(1), dim3(1024), 0, st, logits, n, temperature, top_p, u, seed, counter, presence, frequency, record, count, bias, cut,
+                           probs, out_token, hist, hist_pos);
 }
 
-void launch_pen_sample_rows(const float * logits, int64_t rows, int n, const PenaltyRow * table, float * probs, uint32_t * tokens, uint32_t * hist,
-                            const uint32_t * live, hipStream_t st) {
-    hipLaunchKernelGGL(k_pen_sample_rows, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, table, probs, sample_scratch_floats(n), tokens, hist, live);
+void launch_pen_sample_rows(const float * logits, int64_t rows, int n, const PenaltyRow * table, const CutRow * cuts, float * probs, uint32_t * tokens,
+                            uint32_t * hist, const uint32_t * live, hipStream_t st) {
+    if (!cuts) hipLaunchKernelGGL(k_pen_sample_rows, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, table, probs, sample_scratch_floats(n), tokens, hist, live);
+    else hipLaunchKernelGGL(k_cut_pen_sample_rows, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, table, cuts, probs, sample_scratch_floats(n), tokens, hist, live);
 }
 
-void launch_guided_sample_rows(const float * logits, int64_t rows, int n, const SampleRow * table, const GuideRow * guides, float * probs, uint32_t * tokens,
-                               uint32_t * hist, const uint32_t * live, hipStream_t st) {
-    hipLaunchKernelGGL(k_guided_sample_rows, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, table, guides, probs, sample_scratch_floats(n), tokens, hist, live);
+void launch_guided_sample_rows(const float * logits, int64_t rows, int n, const SampleRow * table, const GuideRow * guides, const CutRow * cuts, float * probs,
+                               uint32_t * tokens, uint32_t * hist, const uint32_t * live, hipStream_t st) {
+    hipLaunchKernelGGL(k_guided_sample_rows, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, table, guides, cuts, probs, sample_scratch_floats(n), tokens, hist, live);
 }
 
-void launch_guided_pen_sample_rows(const float * logits, int64_t rows, int n, const PenaltyRow * table, const GuideRow * guides, float * probs, uint32_t * tokens,
-                                   uint32_t * hist, const uint32_t * live, hipStream_t st) {
-    hipLaunchKernelGGL(k_guided_pen_sample_rows, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, table, guides, probs, sample_scratch_floats(n), tokens, hist, live);
+void launch_guided_pen_sample_rows(const float * logits, int64_t rows, int n, const PenaltyRow * table, const GuideRow * guides, const CutRow * cuts, float * probs,
+                                   uint32_t * tokens, uint32_t * hist, const uint32_t * live, hipStream_t st) {
+    hipLaunchKernelGGL(k_guided_pen_sample_rows, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, table, guides, cuts, probs, sample_scratch_floats(n), tokens, hist, live);
 }
 
 void launch_draft_accept_rows(const float * logits, int64_t rows, int n, const SegState * segs, const uint32_t * tokens, Draw draw, const SampleRow * srows,
-                              const PenaltyRow * prows, float * probs, uint32_t * out, int out_stride, uint32_t * keep, float * logits_row, hipStream_t st) {
+                              const PenaltyRow * prows, const CutRow * cuts, float * probs, uint32_t * out, int out_stride, uint32_t * keep, float * logits_row,
+                              hipStream_t st) {
     auto go = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, segs, tokens, srows, prows, probs, sample_scratch_floats(n), out, out_stride,
+        hipLaunchKernelGGL(kern, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, segs, tokens, srows, prows, cuts, probs, sample_scratch_floats(n), out, out_stride,
                            keep, logits_row);
     };
     switch (draw) {

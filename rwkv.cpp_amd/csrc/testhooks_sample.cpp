@@ -39,10 +39,10 @@ RWKV_API bool rwkv_mi_test_sample_rows(const float * logits, int64_t n_rows, int
         ok = hipMemcpy(d_table, table.data(), R * sizeof(SampleRow), hipMemcpyHostToDevice) == hipSuccess;
     }
     if (ok) {
-        if (rows_kernel) launch_sample_rows(d_logits, n_rows, (int) n_vocab, d_table, d_probs, d_tok, nullptr, nullptr, nullptr);
+        if (rows_kernel) launch_sample_rows(d_logits, n_rows, (int) n_vocab, d_table, nullptr, d_probs, d_tok, nullptr, nullptr, nullptr);
         else for (size_t r = 0; r < R; r++)
             launch_sample(d_logits + r * V, (int) n_vocab, params[r].temperature, params[r].top_p, params[r].u, params[r].seed, d_ctr + r,
-                          d_probs, d_tok + r, nullptr, 0, nullptr);
+                          CutRow{0u, 0.0f}, d_probs, d_tok + r, nullptr, 0, nullptr);
         ok = hipDeviceSynchronize() == hipSuccess && hipMemcpy(tokens_out, d_tok, R * 4, hipMemcpyDeviceToHost) == hipSuccess &&
              (!counters || hipMemcpy(counters, d_ctr, R * 8, hipMemcpyDeviceToHost) == hipSuccess);
     }

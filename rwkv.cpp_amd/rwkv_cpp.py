@@ -23,6 +23,8 @@ HOOKS_LIB_PATH = os.path.join(PKG_DIR, os.environ.get("RWKV_LIB_DIR", "lib"), "l
 SAMPLE_HOOKS_LIB_PATH = os.path.join(PKG_DIR, os.environ.get("RWKV_LIB_DIR", "lib"), "librwkv_testhooks_sample.so")
 # tests/ only: the same objects + csrc/testhooks_guide.cpp (include/rwkv_testhooks_guide.h): the guided sampler kernels on caller-supplied logits
 GUIDE_HOOKS_LIB_PATH = os.path.join(PKG_DIR, os.environ.get("RWKV_LIB_DIR", "lib"), "librwkv_testhooks_guide.so")
+# tests/ only: the same objects + csrc/testhooks_cut.cpp (include/rwkv_testhooks_cut.h): the plain sampler with a truncation setting per row
+CUT_HOOKS_LIB_PATH = os.path.join(PKG_DIR, os.environ.get("RWKV_LIB_DIR", "lib"), "librwkv_testhooks_cut.so")
 
 QUANTIZED_FORMAT_NAMES =("Q4_0", "Q4_1", "Q5_0", "Q5_1", "Q8_0")
 PENALTY_SYMBOLS = ("rwkv_mi_batch_counts_reset", "rwkv_mi_batch_counts_add", "rwkv_mi_batch_counts_store", "rwkv_mi_batch_logit_bias_set",
@@ -39,6 +41,7 @@ GUIDE_MAX = 16              # RWKV_MI_GUIDE_MAX: guides per batch
 GUIDE_MAX_STATES = 65535    # RWKV_MI_GUIDE_MAX_STATES: states per guide
 NO_GUIDE = 0xFFFFFFFF       # RWKV_MI_NO_GUIDE: a slot without a guide
 DRAFT_SYMBOLS = ("rwkv_mi_batch_eval_draft",)
+TRUNCATION_SYMBOLS = ("rwkv_mi_batch_truncation_set", "rwkv_mi_batch_truncation_get", "rwkv_mi_truncation_set", "rwkv_mi_truncation_get")
 DRAFT_MAX = 8               # RWKV_MI_DRAFT_MAX: draft tokens per row of RWKVBatch.eval_draft
 COPY_STATE, COPY_COUNTER, COPY_COUNTS, COPY_BIAS = 1, 2, 4, 8  # RWKV_MI_COPY_*: the bits of rwkv_mi_batch_state_copy's `what`
 TOP_MAX = 20             # RWKV_MI_TOP_MAX: the most alternatives a report holds per token, and the widest beam
@@ -72,6 +75,11 @@ class StopParams(ctypes.Structure):
 
 
 P_STOP_PARAMS = ctypes.POINTER(StopParams)
+
+
+class CutParams(ctypes.Structure):
+    """struct rwkv_mi_test_cut (include/rwkv_testhooks_cut.h): one row's truncation setting as the test hook takes it, 8 bytes."""
+    _fields_ = [("top_k", ctypes.c_uint32), ("min_p", ctypes.c_float)]
 
 
 class BeamParams(ctypes.Structure):
@@ -296,6 +304,18 @@ class RWKVSharedLibrary:
                                                    P_UINT32, P_UINT32, P_FLOAT]
             for name in DRAFT_SYMBOLS:
                 getattr(L, name).restype = ctypes.c_bool
+        # top-k and min-p: per-sequence truncation settings of the device sampler
+        if hasattr(L, "rwkv_mi_batch_truncation_set"):   # (absent from older A/B builds loaded through RWKV_LIB_DIR)
+            L.rwkv_mi_batch_truncation_set.argtypes = [c_batch, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_float]
+            L.rwkv_mi_batch_truncation_get.argtypes = [c_batch, ctypes.c_size_t, P_UINT32, P_FLOAT]
+            L.rwkv_mi_truncation_set.argtypes = [c_ctx, ctypes.c_uint32, ctypes.c_float]
+            L.rwkv_mi_truncation_get.argtypes = [c_ctx, P_UINT32, P_FLOAT]
+            for name in TRUNCATION_SYMBOLS:
+                getattr(L, name).restype = ctypes.c_bool
+        if hasattr(L, "rwkv_mi_test_cut_rows"):   # (librwkv_testhooks_cut.so only)
+            L.rwkv_mi_test_cut_rows.argtypes = [P_FLOAT, ctypes.c_int64, ctypes.c_int64, P_SAMPLE_PARAMS, ctypes.POINTER(CutParams), ctypes.POINTER(ctypes.c_uint64),
+                                                ctypes.c_int, P_UINT32, P_FLOAT]
+            L.rwkv_mi_test_cut_rows.restype = ctypes.c_bool
         if hasattr(L, "rwkv_mi_test_guided_rows"):   # (librwkv_testhooks_guide.so only)
             L.rwkv_mi_test_guided_rows.argtypes = [P_FLOAT, ctypes.c_int64, ctypes.c_int64, ctypes.c_uint32, P_UINT32, P_UINT32, P_UINT32, P_UINT32, P_UINT32, P_UINT32,
                                                    P_SAMPLE_PARAMS, P_PENALTY_PARAMS, P_UINT32, P_FLOAT, ctypes.POINTER(ctypes.c_uint64), P_UINT32, P_UINT32, P_UINT32]
@@ -615,6 +635,17 @@ class RWKVModel:
     def rng_seek(self, counter: int) -> None:
         """Sets the context's draw counter (0 for a new request)."""
         self._mi("rwkv_mi_rng_seek", counter)
+
+    def set_truncation(self, top_k: int = 0, min_p: float = 0.0) -> None:
+        """The context's truncation setting, read by every draw from now on: top_k (0: off) masks all but the top_k largest values the draw
+        reads to -inf before the softmax; min_p (0: off) cuts the probabilities below min_p * the largest, beside top-p. (0, 0) clears."""
+        self._mi("rwkv_mi_truncation_set", int(top_k), float(min_p))
+
+    def truncation(self) -> Tuple[int, float]:
+        """The context's truncation setting (top_k, min_p); (0, 0.0) is none."""
+        k, p = ctypes.c_uint32(0), ctypes.c_float(0.0)
+        self._mi("rwkv_mi_truncation_get", ctypes.byref(k), ctypes.byref(p))
+        return int(k.value), float(p.value)
 
     def sample_penalized(self, temperature: float = 1.0, top_p: float = 0.8, u: float = -1.0, seed: int = 0, presence: float = 0.2,
                          frequency: float = 0.2, record: bool = True) -> int:
@@ -953,6 +984,21 @@ class RWKVBatch:
         """Sets a slot's draw counter (0 for a new request in a reused slot)."""
         if not self._L.rwkv_mi_batch_rng_seek(self._ptr, slot, counter):
             self._fail("rwkv_mi_batch_rng_seek")
+
+    def set_truncation(self, slot: int, top_k: int = 0, min_p: float = 0.0) -> None:
+        """The slot's truncation setting, read by every draw of the slot from now on (eval_sample, the ragged and penalised forms, the
+        loops, decode_until, eval_draft; guided or not): top_k (0: off) masks all but the top_k largest values the draw reads to -inf before
+        the softmax; min_p (0: off) cuts the probabilities below min_p * the largest, beside top-p. (0, 0) clears. copy_state does not
+        carry it: set it on the destination slot."""
+        if not self._L.rwkv_mi_batch_truncation_set(self._ptr, slot, int(top_k), float(min_p)):
+            self._fail("rwkv_mi_batch_truncation_set")
+
+    def truncation(self, slot: int) -> Tuple[int, float]:
+        """The slot's truncation setting (top_k, min_p); (0, 0.0) is none."""
+        k, p = ctypes.c_uint32(0), ctypes.c_float(0.0)
+        if not self._L.rwkv_mi_batch_truncation_get(self._ptr, slot, ctypes.byref(k), ctypes.byref(p)):
+            self._fail("rwkv_mi_batch_truncation_get")
+        return int(k.value), float(p.value)
 
     # --- penalised sampling: one occurrence table and one bias table per slot (include/rwkv_mi355x.h) ---
 

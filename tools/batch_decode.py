@@ -54,6 +54,16 @@ of the vocabulary; records also go to --out:
   mode guide_host     (c) the way without guides: per token and row rwkv_mi_batch_logit_bias_set with -inf on every forbidden id, one
                       rwkv_mi_batch_eval_sample_penalized pass, the token read back, the automaton stepped on the host; host clock
 
+--sample --cut K[,K...] times the sampled loop (temperature 1.0, top-p 0.8, seed = row) under truncation settings (rwkv_mi_batch_truncation_set)
+in the same process, --tokens steps, HIP events around each device loop, the smallest of --reps runs (the loop without a setting also with its
+largest run: the run-to-run spread of the box); sampler_ms_per_step is a loop's step minus the greedy loop's of the same n and run; records
+also go to --out:
+  mode cut_plain    rwkv_mi_batch_decode_sample with no setting on any slot -- the only arm when the library loaded through RWKV_LIB_DIR is a
+                    build without the settings
+  mode cut_device   the same loop with every slot set to {K, 0} for each K of the list, to {0, 0.05}, and to {the first K, 0.05}
+  mode cut_host     the host path doing the same job: RWKVBatch.eval with the logits to the host, then in NumPy the top-k mask (argpartition),
+                    softmax, the top-p cut-off intersected with min-p, the draw; host clock around the loop
+
 --beam W[,W...] times rwkv_mi_batch_decode_beam (no end tokens, --tokens steps) for every width of the list, G = rows // W groups at the largest
 row count of --n, HIP events around each device loop, the smallest of --reps runs; records also go to --out:
   mode beam        ms per step of the beam loop beside the greedy loop's at the same row count from the same run, and their difference
@@ -387,6 +397,94 @@ def beam(pkg, m, args):
         sink.close()
 
 
+def host_sample_cut(logits, temperature, top_p, top_k, min_p, rng):
+    """host_sample with the two truncations in the device's order: mask -> softmax -> top-p and min-p, intersected -> temperature."""
+    import numpy as np
+    x = logits.copy()
+    if 0 < top_k < x.size:
+        x[np.argpartition(x, x.size - top_k)[:x.size - top_k]] = -np.inf
+    x -= x.max()
+    probs = np.exp(x)
+    probs /= probs.sum()
+    cutoff = 0.0
+    if 0.0 < top_p < 1.0:
+        sorted_probs = np.sort(probs)[::-1]
+        cutoff = float(sorted_probs[np.argmax(np.cumsum(sorted_probs) > top_p)])
+    if min_p:
+        cutoff = max(cutoff, min_p * float(probs.max()))
+    probs[probs < cutoff] = 0
+    if temperature != 1.0:
+        probs = np.power(probs, 1.0 / temperature)
+    probs = probs / probs.sum()
+    return int(rng.choice(a=len(probs), p=probs))
+
+
+def cut(pkg, m, args):
+    import numpy as np
+    V = m.n_vocab
+    L = m._library.library
+    sink = open(args.out, "a") if args.out else None
+    steps = args.tokens
+    have_cut = hasattr(L, "rwkv_mi_batch_truncation_set")   # (an older build loaded through RWKV_LIB_DIR: the plain loop only)
+    ks = [int(x) for x in args.cut.split(",")]
+    settings = [(k, 0.0) for k in ks] + [(0, 0.05), (ks[0], 0.05)]
+
+    def emit(rec):
+        rec.update({"steps": steps, "reps": args.reps, "temperature": 1.0, "top_p": 0.8, "config": args.config, "dtype": args.dtype,
+                    "truncation_in_library": have_cut})
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if sink:
+            sink.write(line + "\n")
+            sink.flush()
+
+    ns = [int(x) for x in args.n.split(",")]
+    b = pkg.RWKVBatch(m, max(ns))
+    for n in ns:
+        slots = list(range(n))
+        first = [(7 * i + 1) % V for i in slots]
+
+        def runs(run, setting):
+            out = []
+            for k in range(args.reps + 1):   # (run 0: warm-up -- buffers of the first call, tile-major weight images)
+                for s in slots:
+                    b.state_load(s, None)
+                    if have_cut:
+                        b.set_truncation(s, *setting)
+                out.append(run())
+            return out[1:]
+
+        greedy_ms = min(runs(lambda: b.decode_greedy(slots, first, steps)[1], (0, 0.0)))
+        plain = runs(lambda: b.decode_sample(slots, first, steps, 1.0, 0.8, slots)[1], (0, 0.0))
+        plain_ms = min(plain)
+        emit({"mode": "cut_plain", "n": n, "ms_per_step": round(plain_ms / steps, 4), "ms_per_step_max": round(max(plain) / steps, 4),
+              "spread": round(max(plain) / plain_ms - 1.0, 4), "greedy_ms_per_step": round(greedy_ms / steps, 4),
+              "sampler_ms_per_step": round((plain_ms - greedy_ms) / steps, 4)})
+        if not have_cut:
+            continue
+        for top_k, min_p in settings:
+            dev_ms = min(runs(lambda: b.decode_sample(slots, first, steps, 1.0, 0.8, slots)[1], (top_k, min_p)))
+            emit({"mode": "cut_device", "n": n, "top_k": top_k, "min_p": min_p, "ms_per_step": round(dev_ms / steps, 4),
+                  "plain_ms_per_step": round(plain_ms / steps, 4), "sampler_ms_per_step": round((dev_ms - greedy_ms) / steps, 4),
+                  "cut_ms_per_step": round((dev_ms - plain_ms) / steps, 4), "cut_over_plain": round(dev_ms / plain_ms, 4)})
+        top_k, min_p = settings[-1]
+        rngs = [np.random.default_rng(i) for i in range(n)]
+
+        def host():
+            toks = list(first)
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                lg = b.eval(slots, toks)
+                toks = [host_sample_cut(lg[i], 1.0, 0.8, top_k, min_p, rngs[i]) for i in range(n)]
+            return (time.perf_counter() - t0) * 1e3
+
+        host_ms = min(runs(host, (0, 0.0)))
+        emit({"mode": "cut_host", "n": n, "top_k": top_k, "min_p": min_p, "ms_per_step": round(host_ms / steps, 4), "logits_bytes_per_step": 4 * n * V})
+    b.free()
+    if sink:
+        sink.close()
+
+
 def guide(pkg, m, args):
     import ctypes
 
@@ -591,10 +689,12 @@ def main():
                     help="time rwkv_mi_batch_decode_beam for each width of the list at the largest row count of --n, against the greedy loop and the host-driven search")
     ap.add_argument("--guide", action="store_true",
                     help="with --sample: time the sampled loop plain, guided on the device, and masked from the host before every token (see above)")
+    ap.add_argument("--cut", default=None, metavar="K[,K...]",
+                    help="with --sample: time the sampled loop with no truncation setting, with top_k = each K, with min_p = 0.05, and with both (see above)")
     ap.add_argument("--draft", default=None, metavar="K[,K...]",
                     help="time rwkv_mi_batch_eval_draft for each draft length of the list: its overhead over the ragged pass, tokens/s by acceptance (see above)")
-    ap.add_argument("--reps", type=int, default=3, help="--draft, --ragged, --until, --logprobs, --beam, --guide: timed runs of each shape (the smallest is reported)")
-    ap.add_argument("--out", default=None, help="--draft, --ragged, --penalties, --until, --logprobs, --beam, --guide: also append the records to this file")
+    ap.add_argument("--reps", type=int, default=3, help="--draft, --ragged, --until, --logprobs, --beam, --guide, --cut: timed runs of each shape (the smallest is reported)")
+    ap.add_argument("--out", default=None, help="--draft, --ragged, --penalties, --until, --logprobs, --beam, --guide, --cut: also append the records to this file")
     args = ap.parse_args()
 
     import __graft_entry__ as graft
@@ -633,6 +733,12 @@ def main():
         if not args.sample:
             ap.error("--guide times the sampled loop: give --sample with it")
         guide(pkg, m, args)
+        m.free()
+        return
+    if args.cut is not None:
+        if not args.sample:
+            ap.error("--cut times the sampled loop: give --sample with it")
+        cut(pkg, m, args)
         m.free()
         return
     if args.logprobs is not None:

@@ -537,11 +537,57 @@ RWKV_API bool rwkv_mi_batch_eval_draft(struct rwkv_mi_batch * batch, const uint3
  * logits; the greedy loops and beam search do not read the setting. rwkv_mi_batch_state_copy has no bit for it.
  * set returns false with RWKV_ERROR_ARGS and changes nothing when the slot is out of range, when min_p is NaN, below 0 or above 1, or (the
  * context forms, as the penalised context calls) on a RWKV_MI_DEVICES chain. get: either pointer may be NULL.
- * OUT OF SCOPE: penalty decay (a float occurrence table and a new store call), typical-p and tail-free sampling. */
+ * OUT OF SCOPE: typical-p and tail-free sampling. */
 RWKV_API bool rwkv_mi_batch_truncation_set(struct rwkv_mi_batch * batch, size_t slot, uint32_t top_k, float min_p);
 RWKV_API bool rwkv_mi_batch_truncation_get(struct rwkv_mi_batch * batch, size_t slot, uint32_t * top_k_out, float * min_p_out);
 RWKV_API bool rwkv_mi_truncation_set(struct rwkv_context * ctx, uint32_t top_k, float min_p);
 RWKV_API bool rwkv_mi_truncation_get(struct rwkv_context * ctx, uint32_t * top_k_out, float * min_p_out);
+
+/* ---- Penalty decay and repetition penalty in the device sampler: per-sequence repetition settings ----
+ * A sequence -- a slot of a batch, or a context -- carries an optional REPETITION SETTING {decay, repetition}. It is kept like the truncation
+ * setting: it stays until it is changed, a context made by rwkv_clone_context starts with none, and EVERY PENALISED DRAW of that sequence reads
+ * it -- rwkv_mi_sample_penalized and rwkv_mi_decode_sample_penalized on a context; rwkv_mi_batch_eval_sample_penalized,
+ * _eval_ragged_sample_penalized, _decode_sample_penalized, the penalised families of _decode_until and of _eval_draft, on guided slots and on
+ * slots with a truncation setting as on others. {1, 1} is "none", the state at creation.
+ *   repetition  the multiplicative penalty of HF, vLLM and llama.cpp on the tokens that have occurred.
+ *   decay       RWKV's own recipe: the occurrence table decays before the new token is counted (the demos' alpha_decay, 0.996), so the
+ *               frequency penalty of a long answer stays bounded. A sequence with decay != 1 is DECAYING: the 4-byte words of its occurrence
+ *               row hold float instead of uint32.
+ * THE ARITHMETIC. With o[j] the row's occurrence entry -- the float, or (float) count[j] on a sequence that is not decaying -- a penalised draw
+ * reads, every operation rounded to f32 in this order, no contraction, IEEE division:
+ *     a = l[j]
+ *     if (o[j] > 0) { a = a > 0 ? a / repetition : a * repetition;       (HF's rule: 0, -0, NaN and -inf take the multiply)
+ *                     a = a - (presence + o[j] * frequency); }
+ *     if (bias)       a = a + bias[j]
+ * With the setting none this is adj[j] above, statement for statement. Everything after that is the sampler, with the guide's mask and the
+ * truncation setting applied to these values as they are to adj[j].
+ * After the draw, where the row records (its record is non-zero; in rwkv_mi_batch_decode_until, the row is live; every position walked by
+ * rwkv_mi_batch_eval_draft), a decaying sequence does, in this order,
+ *     for every j:  o[j] = o[j] * decay           (f32, subnormals kept)
+ *     o[token] = o[token] + 1.0f
+ * and a sequence that is not decaying count[token] += 1 as before. A row that does not record neither decays nor counts. The draw of step i
+ * sees the table of the steps before it. An entry that has underflowed to 0 is a token that has not occurred.
+ * On a decaying sequence rwkv_mi_*counts_add applies the two statements once per token, in the order given (resuming a recorded response leaves
+ * the table the draws would have left); counts_reset zeroes the row; counts_store (uint32) returns false with RWKV_ERROR_ARGS and writes
+ * nothing; counts_store_f32 works on both kinds of sequence (the counts of one that is not decaying are exact as floats below 2^24).
+ * A set that changes WHETHER the sequence is decaying zeroes its occurrence row (a new request calls counts_reset anyway; a caller resuming a
+ * response calls counts_add afterwards); a set that does not leaves the row alone.
+ * rwkv_mi_batch_state_copy with RWKV_MI_COPY_COUNTS copies the row as it is between two slots of one kind; between a decaying slot and one that
+ * is not it returns false with RWKV_ERROR_ARGS and changes nothing. It has no bit for the setting itself.
+ * With the setting none a penalised draw is exactly the draw described above, and no call performs a launch, allocation or copy it did not
+ * perform before. A pass that names slots with and without a setting draws them all with the kernels of this section; a row with {1, 1} then
+ * reads uint32 counts and picks what it always picked. The plain sampled calls, the greedy loops, beam search and the report never read or
+ * touch the setting.
+ * set returns false with RWKV_ERROR_ARGS and changes nothing when the slot is out of range, when decay is NaN, below 0 or above 1, when
+ * repetition is NaN, infinite or not above 0, or (the context forms, as the penalised context calls) on a RWKV_MI_DEVICES chain. get: either
+ * pointer may be NULL.
+ * OUT OF SCOPE: per-token count weights (the demos' zero weight for digits and punctuation), a last-n window for the repetition penalty. */
+RWKV_API bool rwkv_mi_batch_repetition_set(struct rwkv_mi_batch * batch, size_t slot, float decay, float repetition);
+RWKV_API bool rwkv_mi_batch_repetition_get(struct rwkv_mi_batch * batch, size_t slot, float * decay_out, float * repetition_out);
+RWKV_API bool rwkv_mi_batch_counts_store_f32(struct rwkv_mi_batch * batch, size_t slot, float * out /* [n_vocab] */);
+RWKV_API bool rwkv_mi_repetition_set(struct rwkv_context * ctx, float decay, float repetition);
+RWKV_API bool rwkv_mi_repetition_get(struct rwkv_context * ctx, float * decay_out, float * repetition_out);
+RWKV_API bool rwkv_mi_counts_store_f32(struct rwkv_context * ctx, float * out /* [n_vocab] */);
 
 #if defined(__cplusplus)
 }

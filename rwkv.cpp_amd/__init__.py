@@ -7,6 +7,7 @@ from .rwkv_cpp import (  # noqa: F401
     BeamParams,
     CUT_HOOKS_LIB_PATH,
     CutParams,
+    DECAY_HOOKS_LIB_PATH,
     DRAFT_MAX,
     GUIDE_HOOKS_LIB_PATH,
     GUIDE_MAX,
@@ -17,6 +18,7 @@ from .rwkv_cpp import (  # noqa: F401
     NO_TARGET,
     NO_TOKEN,
     PenaltyParams,
+    RepParams,
     RWKVBatch,
     RWKVContext,
     RWKVModel,

@@ -547,7 +547,9 @@ bool DrawState::counts_add(rwkv_context * ctx, size_t slot, const uint32_t * tok
     if (n == 0) return true;
     DevBuf<uint32_t> d;
     bool ok = d.upload(tokens, n, st);
-    if (ok) launch_count_add(counts_of(slot), d.p, (int64_t) n, (int) n_vocab, st);
+    // (a decaying slot's row holds floats: every token of the list decays the row and counts, in the list's order)
+    if (ok && decaying(slot)) launch_count_add_decay((float *) counts_of(slot), d.p, (int64_t) n, (int) n_vocab, reps[slot].decay, st);
+    else if (ok) launch_count_add(counts_of(slot), d.p, (int64_t) n, (int) n_vocab, st);
     ok = ok && hipGetLastError() == hipSuccess;
     ok = hipStreamSynchronize(st) == hipSuccess && ok;
     RW_CTX_CHECK(ctx, RWKV_ERROR_GRAPH, false, ok, "HIP error: %s", hipGetErrorString(hipGetLastError()));
@@ -555,9 +557,20 @@ bool DrawState::counts_add(rwkv_context * ctx, size_t slot, const uint32_t * tok
 }
 
 bool DrawState::counts_store(rwkv_context * ctx, size_t slot, uint32_t * counts_out, hipStream_t st) {
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, !decaying(slot), "the slot is decaying: its occurrence row holds floats (counts_store_f32 reads it)");
     if (!ensure_penalty(ctx, st)) return false;
     HIP_CTX_OK(ctx, hipMemcpyAsync(counts_out, counts_of(slot), n_vocab * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIP_CTX_OK(ctx, hipStreamSynchronize(st));
+    return true;
+}
+
+// the row as floats: a decaying slot's words as they are, the counts of any other converted (exact below 2^24)
+bool DrawState::counts_store_f32(rwkv_context * ctx, size_t slot, float * out, hipStream_t st) {
+    if (!ensure_penalty(ctx, st)) return false;
+    HIP_CTX_OK(ctx, hipMemcpyAsync(out, counts_of(slot), n_vocab * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_CTX_OK(ctx, hipStreamSynchronize(st));
+    if (!decaying(slot))
+        for (size_t j = 0; j < n_vocab; j++) { uint32_t c; memcpy(&c, out + j, sizeof(c)); out[j] = (float) c; }
     return true;
 }
 
@@ -623,6 +636,20 @@ bool DrawState::cut_set(rwkv_context * ctx, size_t slot, uint32_t top_k, float m
     return true;
 }
 
+// the repetition setting of a slot: host words, read by every penalised draw of the slot from the next call on. The words of the slot's
+// occurrence row are floats exactly while decay != 1: a set that changes that zeroes the row (a table not yet allocated is zero already)
+bool DrawState::rep_set(rwkv_context * ctx, size_t slot, float decay, float repetition, hipStream_t st) {
+    // (written so that a NaN fails the comparison)
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, decay >= 0.0f && decay <= 1.0f, "decay (%g) must be in 0 .. 1", (double) decay);
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, repetition > 0.0f && repetition < INFINITY, "repetition (%g) must be finite and above 0", (double) repetition);
+    if ((decay != 1.0f) != decaying(slot) && counts) {
+        HIP_CTX_OK(ctx, hipMemsetAsync(counts_of(slot), 0, n_vocab * sizeof(uint32_t), st));
+        HIP_CTX_OK(ctx, hipStreamSynchronize(st));
+    }
+    reps[slot] = RepRow{decay, repetition};
+    return true;
+}
+
 static bool on_device(rwkv_context * ctx) { HIP_CTX_OK(ctx, hipSetDevice(ctx->model->device)); return true; }
 
 // what every call of the single-context family starts with
@@ -645,6 +672,26 @@ RWKV_API bool rwkv_mi_counts_store(struct rwkv_context * ctx, uint32_t * counts_
     if (!penalty_call(ctx)) return false;
     RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, counts_out != nullptr, "counts_out is NULL");
     return on_device(ctx) && ctx->draw.counts_store(ctx, 0, counts_out, ctx->stream);
+}
+
+RWKV_API bool rwkv_mi_counts_store_f32(struct rwkv_context * ctx, float * out) {
+    if (!penalty_call(ctx)) return false;
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, out != nullptr, "out is NULL");
+    return on_device(ctx) && ctx->draw.counts_store_f32(ctx, 0, out, ctx->stream);
+}
+
+RWKV_API bool rwkv_mi_repetition_set(struct rwkv_context * ctx, float decay, float repetition) {
+    ctx->last_error = RWKV_ERROR_NONE;
+    RW_NO_PIPELINE(ctx, false);
+    return on_device(ctx) && ctx->draw.rep_set(ctx, 0, decay, repetition, ctx->stream);
+}
+
+RWKV_API bool rwkv_mi_repetition_get(struct rwkv_context * ctx, float * decay_out, float * repetition_out) {
+    ctx->last_error = RWKV_ERROR_NONE;
+    RW_NO_PIPELINE(ctx, false);
+    if (decay_out) *decay_out = ctx->draw.reps[0].decay;
+    if (repetition_out) *repetition_out = ctx->draw.reps[0].repetition;
+    return true;
 }
 
 RWKV_API bool rwkv_mi_logit_bias_set(struct rwkv_context * ctx, const uint32_t * ids, const float * values, size_t n) {
@@ -679,7 +726,7 @@ static void launch_draw(rwkv_context * ctx, float temperature, float top_p, floa
     const int n_vocab = (int) ctx->model->n_vocab();
     const DrawState & d = ctx->draw;
     if (pen) launch_pen_sample(ctx->d_logits.p, n_vocab, temperature, top_p, u, seed, d.counter(0), pen->presence, pen->frequency, pen->record, d.counts_of(0),
-                               d.bias_of(0), d.cuts[0], d.probs.p, out, hist, hist_pos, ctx->stream);
+                               d.bias_of(0), d.cuts[0], d.reps[0], d.probs.p, out, hist, hist_pos, ctx->stream);
     else launch_sample(ctx->d_logits.p, n_vocab, temperature, top_p, u, seed, d.counter(0), d.cuts[0], d.probs.p, out, hist, hist_pos, ctx->stream);
     // the report of the token just written, slot hist_pos of the context's buffers (ensure_report has sized them)
     const LogprobReport & lp = ctx->lp;
@@ -1070,6 +1117,10 @@ struct rwkv_mi_batch {
     // staging, allocated by the first call that names a slot with a setting
     DevBuf<CutRow> d_crows;
     PinBuf<CutRow> h_crows;
+    // the repetition rows of a penalised call (rwkv_mi_batch_repetition_set; the settings are the draw state's host words) with their pinned
+    // staging, allocated by the first penalised call that names a slot with a setting
+    DevBuf<RepRow> d_rrows;
+    PinBuf<RepRow> h_rrows;
     // ragged passes (rwkv_mi_batch_eval_ragged*): the tables of a call -- segments, the short ones again, seg_of[T], last[n] -- in one device
     // buffer with its pinned staging, grown to the largest call so far; the long segments stay on the host (each is a launch of its own)
     DevBuf<uint8_t> d_seg;
@@ -1300,6 +1351,22 @@ static bool batch_upload_cut_rows(rwkv_mi_batch * B, const BatchCall & c) {
     return true;
 }
 
+// ---- repetition settings: which calls see one (rwkv_mi_*repetition_set) ----
+
+// whether a call draws penalised and names a slot with a repetition setting (its slots have been checked): the other draws never read one
+static bool batch_names_rep(const rwkv_mi_batch * B, const BatchCall & c) {
+    if (c.draw != Draw::penalized) return false;
+    for (size_t i = 0; i < c.n; i++) if (B->draw.has_rep(c.slots[i])) return true;
+    return false;
+}
+
+// the repetition rows of the n named slots (after batch_upload*: the stream has been drained, the staging is free)
+static bool batch_upload_rep_rows(rwkv_mi_batch * B, const BatchCall & c) {
+    for (size_t i = 0; i < c.n; i++) B->h_rrows.p[i] = B->draw.reps[c.slots[i]];
+    BATCH_HIP_OK(B, hipMemcpyAsync(B->d_rrows.p, B->h_rrows.p, c.n * sizeof(RepRow), hipMemcpyHostToDevice, B->run->stream));
+    return true;
+}
+
 // what the calls on one slot's draw state start with
 static bool batch_slot_call(rwkv_mi_batch * B, size_t slot) {
     rwkv_context * ctx = B->ctx;
@@ -1447,6 +1514,10 @@ static bool batch_ensure_draw(rwkv_mi_batch * B, const BatchCall & c) {
         const hipError_t e = grow(want(B->d_crows, B->n_slots), want(B->h_crows, B->n_slots));
         RW_CTX_CHECK(B->ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the truncation rows of %zu slots: %s", B->n_slots, hipGetErrorString(e));
     }
+    if (batch_names_rep(B, c) && !B->d_rrows) {   // the repetition rows with their pinned staging: on the first penalised call that names a setting
+        const hipError_t e = grow(want(B->d_rrows, B->n_slots), want(B->h_rrows, B->n_slots));
+        RW_CTX_CHECK(B->ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the repetition rows of %zu slots: %s", B->n_slots, hipGetErrorString(e));
+    }
     return batch_ensure_draw_tables(B, c.draw == Draw::penalized);
 }
 
@@ -1457,6 +1528,7 @@ static bool batch_upload_call(rwkv_mi_batch * B, const BatchCall & c, size_t T, 
     if (c.draw == Draw::none) return true;
     if (batch_names_guided(B, c.slots, c.n) && !batch_upload_guide_rows(B, c)) return false;
     if (batch_names_cut(B, c.slots, c.n) && !batch_upload_cut_rows(B, c)) return false;
+    if (batch_names_rep(B, c) && !batch_upload_rep_rows(B, c)) return false;
     return c.draw == Draw::penalized ? batch_upload_penalty_rows(B, c, loop) : batch_upload_params(B, c, loop);
 }
 
@@ -1467,6 +1539,7 @@ static RowSampler batch_sampler(rwkv_mi_batch * B, const BatchCall & c, uint32_t
     s.draw = c.draw; s.srows = B->d_srows.p; s.prows = B->d_prows.p; s.probs = B->draw.probs.p;
     if (c.draw != Draw::none && batch_names_guided(B, c.slots, c.n)) s.grows = B->d_grows.p;
     if (c.draw != Draw::none && batch_names_cut(B, c.slots, c.n)) s.crows = B->d_crows.p;
+    if (batch_names_rep(B, c)) s.rrows = B->d_rrows.p;
     s.hist = hist; s.report = report;
     return s;
 }
@@ -1580,6 +1653,7 @@ static bool batch_draft(rwkv_mi_batch * B, const BatchCall & c, uint32_t * token
     d.lw = B->d_draft_layers.p; d.logits_all = B->d_draft_logits.p;
     d.draw = c.draw; d.srows = B->d_srows.p; d.prows = B->d_prows.p; d.probs = B->draw.probs.p;
     if (c.draw != Draw::none && batch_names_cut(B, c.slots, c.n)) d.crows = B->d_crows.p;
+    if (batch_names_rep(B, c)) d.rrows = B->d_rrows.p;
     d.keep = B->d_draft_words.p; d.out = B->d_draft_words.p + B->n_slots; d.out_stride = W;
     if (!forward_draft(run, B->pass, (int64_t) T, d)) return batch_fail_drained(B);
     BATCH_HIP_OK(B, hipMemcpyAsync(B->h_draft_words.p, B->d_draft_words.p, c.n * sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream));
@@ -2052,6 +2126,23 @@ RWKV_API bool rwkv_mi_batch_truncation_get(struct rwkv_mi_batch * B, size_t slot
     return true;
 }
 
+RWKV_API bool rwkv_mi_batch_repetition_set(struct rwkv_mi_batch * B, size_t slot, float decay, float repetition) {
+    return batch_slot_call(B, slot) && on_device(B->ctx) && B->draw.rep_set(B->ctx, slot, decay, repetition, B->run->stream);
+}
+
+RWKV_API bool rwkv_mi_batch_repetition_get(struct rwkv_mi_batch * B, size_t slot, float * decay_out, float * repetition_out) {
+    if (!batch_slot_call(B, slot)) return false;
+    if (decay_out) *decay_out = B->draw.reps[slot].decay;
+    if (repetition_out) *repetition_out = B->draw.reps[slot].repetition;
+    return true;
+}
+
+RWKV_API bool rwkv_mi_batch_counts_store_f32(struct rwkv_mi_batch * B, size_t slot, float * out) {
+    if (!batch_slot_call(B, slot)) return false;
+    RW_CTX_CHECK(B->ctx, RWKV_ERROR_ARGS, false, out != nullptr, "out is NULL");
+    return on_device(B->ctx) && B->draw.counts_store_f32(B->ctx, slot, out, B->run->stream);
+}
+
 RWKV_API bool rwkv_mi_batch_counts_reset(struct rwkv_mi_batch * B, size_t slot) {
     return batch_slot_call(B, slot) && on_device(B->ctx) && B->draw.counts_reset(B->ctx, slot, B->run->stream);
 }
@@ -2132,6 +2223,9 @@ RWKV_API bool rwkv_mi_batch_state_copy(struct rwkv_mi_batch * B, size_t dst_slot
     // (no bit for the truncation setting: it is two host words the caller sets on the destination slot themselves)
     const uint32_t known = RWKV_MI_COPY_STATE | RWKV_MI_COPY_COUNTER | RWKV_MI_COPY_COUNTS | RWKV_MI_COPY_BIAS;
     RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, (what & ~known) == 0, "unknown bits in what (0x%" PRIx32 ")", what);
+    // (nor one for the repetition setting; but a row of floats is not a row of counts: the copy is between slots of one kind)
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, !(what & RWKV_MI_COPY_COUNTS) || B->draw.decaying(dst_slot) == B->draw.decaying(src_slot),
+                 "RWKV_MI_COPY_COUNTS between a decaying slot and one that is not (%zu, %zu)", dst_slot, src_slot);
     if (dst_slot == src_slot) return true;
     BATCH_HIP_OK(B, hipSetDevice(ctx->model->device));
     hipStream_t st = B->run->stream;

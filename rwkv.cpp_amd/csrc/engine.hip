@@ -863,8 +863,8 @@ void launch_row_sampler(rwkv_context * ctx, const RowSampler & s, int64_t rows) 
     const uint32_t * live = s.stop ? s.stop->t.live : nullptr;   // (rwkv_mi_batch_decode_until: everything but the stop test runs behind the live words)
     switch (s.draw) {
         case Draw::penalized:
-            if (s.grows) launch_guided_pen_sample_rows(logits, rows, n_vocab, s.prows, s.grows, s.crows, s.probs, tokens, hist, live, ctx->stream);
-            else launch_pen_sample_rows(logits, rows, n_vocab, s.prows, s.crows, s.probs, tokens, hist, live, ctx->stream);
+            if (s.grows) launch_guided_pen_sample_rows(logits, rows, n_vocab, s.prows, s.grows, s.crows, s.rrows, s.probs, tokens, hist, live, ctx->stream);
+            else launch_pen_sample_rows(logits, rows, n_vocab, s.prows, s.crows, s.rrows, s.probs, tokens, hist, live, ctx->stream);
             break;
         case Draw::sample:
             if (s.grows) launch_guided_sample_rows(logits, rows, n_vocab, s.srows, s.grows, s.crows, s.probs, tokens, hist, live, ctx->stream);
@@ -942,7 +942,7 @@ bool forward_draft(rwkv_context * ctx, const SegPass & p, int64_t T, const Draft
     mega_chain_begin(ctx);
     r.run(true);
     if (!r.failed) {
-        launch_draft_accept_rows(d.logits_all, p.n, (int) m.n_vocab(), p.d_segs, ctx->d_tokens.p, d.draw, d.srows, d.prows, d.crows, d.probs, d.out, d.out_stride,
+        launch_draft_accept_rows(d.logits_all, p.n, (int) m.n_vocab(), p.d_segs, ctx->d_tokens.p, d.draw, d.srows, d.prows, d.crows, d.rrows, d.probs, d.out, d.out_stride,
                                  d.keep, ctx->d_logits.p, ctx->stream);
         launch_draft_replay(d.stash, d.lw, m.arch_major, m.arch_minor, p.d_segs, p.n, d.keep, (int64_t) (m.layer_end - m.layer_begin), m.n_embed(), m.head_count, m.head_size,
                             ctx->stream);

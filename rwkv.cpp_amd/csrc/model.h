@@ -134,11 +134,17 @@ void launch_sample_seek_rows(const SampleRow * table, int64_t rows, unsigned lon
 // (the penalty where count[j] > 0 only; bias == NULL: no bias), then count[token] += 1 when record is set. count: the sequence's occurrence table ([n] words), bias: its bias
 // table ([n] floats). The row table carries them per row, beside the sampler's parameters and the draw counter of the row's slot.
 struct PenaltyRow { rwkv_mi_sample_params p; unsigned long long * counter; float presence; float frequency; uint32_t record; uint32_t * count; const float * bias; };
+// The repetition setting of a row's sequence (rwkv_mi_*repetition_set), a table parallel to the row table as the truncation rows are; a NULL
+// table: no row of the call has one, and the kernels of before run. repetition (1: off): where the token has occurred, the logit is divided
+// by it when positive and multiplied by it otherwise, in front of the penalty. decay (1: off): the sequence is DECAYING -- the words of its
+// occurrence row (PenaltyRow::count) hold floats, and a draw that records multiplies every one of them by decay before it adds 1.0f to the
+// pick's. The arithmetic is spelled out in include/rwkv_mi355x.h. A row with {1, 1} in a table reads uint32 counts and draws as it always did.
+struct RepRow { float decay; float repetition; };
 void launch_pen_sample(const float * logits, int n, float temperature, float top_p, float u, unsigned long long seed, unsigned long long * counter,
-                       float presence, float frequency, uint32_t record, uint32_t * count, const float * bias, const CutRow & cut,
+                       float presence, float frequency, uint32_t record, uint32_t * count, const float * bias, const CutRow & cut, const RepRow & rep,
                        float * probs, uint32_t * out_token, uint32_t * hist, int hist_pos, hipStream_t st);
-void launch_pen_sample_rows(const float * logits, int64_t rows, int n, const PenaltyRow * table, const CutRow * cuts, float * probs, uint32_t * tokens,
-                            uint32_t * hist, const uint32_t * live, hipStream_t st);
+void launch_pen_sample_rows(const float * logits, int64_t rows, int n, const PenaltyRow * table, const CutRow * cuts, const RepRow * reps, float * probs,
+                            uint32_t * tokens, uint32_t * hist, const uint32_t * live, hipStream_t st);
 // The guided forms (rwkv_mi_batch_guide_*): a parallel table gives row r the dense table of its guide -- next[n_states][n], GUIDE_DEAD where
 // the transition is dead; NULL: the row has no guide and draws as the unguided kernel does -- and its slot's state and miss words. A guided
 // row in state s reads -inf for token j where next[s][j] is dead, the value of its draw elsewhere; thread 0 then moves the state to
@@ -147,8 +153,8 @@ constexpr uint16_t GUIDE_DEAD = 0xFFFF;
 struct GuideRow { const uint16_t * next; uint32_t * state; uint32_t * misses; };
 void launch_guided_sample_rows(const float * logits, int64_t rows, int n, const SampleRow * table, const GuideRow * guides, const CutRow * cuts, float * probs,
                                uint32_t * tokens, uint32_t * hist, const uint32_t * live, hipStream_t st);
-void launch_guided_pen_sample_rows(const float * logits, int64_t rows, int n, const PenaltyRow * table, const GuideRow * guides, const CutRow * cuts, float * probs,
-                                   uint32_t * tokens, uint32_t * hist, const uint32_t * live, hipStream_t st);
+void launch_guided_pen_sample_rows(const float * logits, int64_t rows, int n, const PenaltyRow * table, const GuideRow * guides, const CutRow * cuts,
+                                   const RepRow * reps, float * probs, uint32_t * tokens, uint32_t * hist, const uint32_t * live, hipStream_t st);
 // next[n_states][n_vocab] from the edges in CSR form on the device (checked by the caller: tokens < n_vocab and distinct per state, next < n_states)
 void launch_guide_expand(uint16_t * next, uint32_t n_states, int n_vocab, const uint32_t * edge_begin, const uint32_t * edge_tokens, const uint32_t * edge_next,
                          hipStream_t st);
@@ -186,6 +192,8 @@ struct BeamTables {
 void launch_beam_rows(const float * logits, int64_t rows, int n, const BeamTables & t, hipStream_t st);
 void launch_beam_select(const BeamTables & t, int64_t groups, uint32_t * tokens, uint32_t step, const RowState * used, RowState * other, hipStream_t st);
 void launch_count_add(uint32_t * count, const uint32_t * tokens, int64_t n, int n_vocab, hipStream_t st);                        // count[tokens[i]] += 1
+// the same on a decaying sequence's row: per token of the list, in its order, every entry * decay, then the token's entry + 1.0f
+void launch_count_add_decay(float * occ, const uint32_t * tokens, int64_t n, int n_vocab, float decay, hipStream_t st);
 void launch_bias_scatter(float * bias, const uint32_t * ids, const float * values, int64_t n, int n_vocab, hipStream_t st);     // bias[ids[i]] = values[i]
 
 // The draw state of `slots` sequences of a model, owned in one place (api.cpp): per slot the draw counter, the sampler's scratch vector, the
@@ -210,15 +218,21 @@ struct DrawState {
     DevBuf<uint32_t> guide_misses;         // [slots]
     // the truncation settings (rwkv_mi_*truncation_set): host words only, {0, 0} -- none -- from init() on; every draw of the slot reads them
     std::vector<CutRow> cuts;              // [slots]
+    // the repetition settings (rwkv_mi_*repetition_set): host words only, {1, 1} -- none -- from init() on; every PENALISED draw of the slot reads
+    // them. A slot with decay != 1 is decaying: the words of its row of `counts` are floats (the row is zeroed when a set changes that)
+    std::vector<RepRow> reps;              // [slots]
 
     void init(size_t n_slots, size_t vocab) {
         slots = n_slots; n_vocab = vocab; has_bias.assign(n_slots, 0); guide_of.assign(n_slots, RWKV_MI_NO_GUIDE); cuts.assign(n_slots, CutRow{0u, 0.0f});
+        reps.assign(n_slots, RepRow{1.0f, 1.0f});
     }
     unsigned long long * counter(size_t slot) const { return counters.p + slot; }
     uint32_t * counts_of(size_t slot) const { return counts.p + slot * n_vocab; }
     const float * bias_of(size_t slot) const { return has_bias[slot] ? bias.p + slot * n_vocab : nullptr; }   // NULL: none is set
     // whether the slot's setting truncates anything (top_k == 0 or >= n_vocab: no top-k; min_p == 0: no min-p)
     bool has_cut(size_t slot) const { return (cuts[slot].top_k != 0u && cuts[slot].top_k < n_vocab) || cuts[slot].min_p != 0.0f; }
+    bool decaying(size_t slot) const { return reps[slot].decay != 1.0f; }
+    bool has_rep(size_t slot) const { return decaying(slot) || reps[slot].repetition != 1.0f; }
 
     bool ensure_counters(rwkv_context * ctx, hipStream_t st);
     bool ensure_sampler(rwkv_context * ctx, hipStream_t st);   // the counters and the scratch
@@ -226,13 +240,16 @@ struct DrawState {
     bool seek(rwkv_context * ctx, size_t slot, unsigned long long value, hipStream_t st);
     bool counts_reset(rwkv_context * ctx, size_t slot, hipStream_t st);
     bool counts_add(rwkv_context * ctx, size_t slot, const uint32_t * tokens, size_t n, hipStream_t st);   // (arguments checked: check_count_tokens)
-    bool counts_store(rwkv_context * ctx, size_t slot, uint32_t * counts_out, hipStream_t st);
+    bool counts_store(rwkv_context * ctx, size_t slot, uint32_t * counts_out, hipStream_t st);   // RWKV_ERROR_ARGS on a decaying slot
     bool bias_set(rwkv_context * ctx, size_t slot, const uint32_t * ids, const float * values, size_t n, hipStream_t st);   // n == 0: cleared (check_bias)
     bool ensure_guides(rwkv_context * ctx, hipStream_t st);    // the two guide words per slot
     // attaches `guide` in `state` (checked by the caller) or, with RWKV_MI_NO_GUIDE, detaches; the slot's miss counter starts from 0 either way
     bool guide_attach(rwkv_context * ctx, size_t slot, uint32_t guide, uint32_t state, hipStream_t st);
     bool guide_words(rwkv_context * ctx, size_t slot, uint32_t * state_out, uint32_t * misses_out, hipStream_t st);   // (0, 0 without a guide)
     bool cut_set(rwkv_context * ctx, size_t slot, uint32_t top_k, float min_p);   // min_p in [0, 1], or RWKV_ERROR_ARGS and nothing changed
+    // decay in [0, 1], repetition finite and > 0, or RWKV_ERROR_ARGS and nothing changed; a set that changes whether the slot is decaying zeroes its row
+    bool rep_set(rwkv_context * ctx, size_t slot, float decay, float repetition, hipStream_t st);
+    bool counts_store_f32(rwkv_context * ctx, size_t slot, float * out, hipStream_t st);   // either kind of row, as floats
 };
 
 // Loads [layer_begin, layer_end) of the file (layer_end == UINT32_MAX: all layers) onto the current HIP device.
@@ -377,7 +394,8 @@ void batch_context_destroy(rwkv_context * c);
 //   draw    which choice is made: the greedy argmax (none), the sampler (sample: srows, launch_sample_rows) or the penalised sampler
 //           (penalized: prows, launch_pen_sample_rows); probs: the samplers' scratch; grows (NULL: no named slot has a guide): the guide rows,
 //           with which the guided form of either sampler is launched instead; crows (NULL: no named slot has a truncation setting): the
-//           settings of the rows, which every form of the sampler takes
+//           settings of the rows, which every form of the sampler takes; rrows (NULL: the call is not penalised, or no named slot has a
+//           repetition setting): the rows' repetition settings, with which the k_rep_* form of the penalised sampler is launched
 //   hist, report, step   the call's WHOLE history [steps][rows] and report buffers (chosen [steps][rows], ids / vals [steps][rows][top_n]), either
 //           may be NULL, and the step of the call this pass is: the step's slot of each is written. A single pass is step 0
 //   stop    the pass is a step of rwkv_mi_batch_decode_until: the choice and the report run behind the live words and launch_stop_rows follows them
@@ -394,6 +412,7 @@ struct RowSampler {
     const PenaltyRow * prows = nullptr;
     const GuideRow * grows = nullptr;   // the call names a guided slot: the guided form of the sampler runs on this parallel table
     const CutRow * crows = nullptr;     // the call names a slot with a truncation setting: the rows' settings, parallel to the row table
+    const RepRow * rrows = nullptr;     // the penalised call names a slot with a repetition setting: the rows' settings, parallel to the row table
     float * probs = nullptr;
     uint32_t * hist = nullptr;
     const RowReport * report = nullptr;
@@ -434,14 +453,15 @@ struct DraftPass {
     const SampleRow * srows = nullptr;
     const PenaltyRow * prows = nullptr;
     const CutRow * crows = nullptr;     // the rows' truncation settings as in RowSampler (NULL: none), read at every position walked
+    const RepRow * rrows = nullptr;     // the rows' repetition settings as in RowSampler (NULL: none; the penalised family only)
     float * probs = nullptr;
     uint32_t * out = nullptr;
     int out_stride = 0;
     uint32_t * keep = nullptr;
 };
 void launch_draft_accept_rows(const float * logits, int64_t rows, int n, const SegState * segs, const uint32_t * tokens, Draw draw, const SampleRow * srows,
-                              const PenaltyRow * prows, const CutRow * cuts, float * probs, uint32_t * out, int out_stride, uint32_t * keep, float * logits_row,
-                              hipStream_t st);
+                              const PenaltyRow * prows, const CutRow * cuts, const RepRow * reps, float * probs, uint32_t * out, int out_stride, uint32_t * keep,
+                              float * logits_row, hipStream_t st);
 // inputs of a layer's WKV body a pass stashes (DraftStash::n_in): 3, 3, 4, 6 for RWKV-4, 5, 6, 7
 inline int draft_stash_inputs(const Model & m) { return m.arch_major == 7 ? 6 : (m.arch_major == 6 ? 4 : 3); }
 bool forward_draft(rwkv_context * ctx, const SegPass & p, int64_t T, const DraftPass & d);

@@ -24,6 +24,9 @@
 // select_stage in front of the body -- of the values above, all but the first top_k in the order (value descending, index ascending) read
 // -inf -- and the body on the stash; min-p is one more threshold of the body, p >= (float) (min_p * p_max), combined with the top-p
 // cut-off as the larger bit pattern. {0, 0}: the draw above, statement for statement.
+// Repetition settings (rwkv_mi_*repetition_set; RepetitionLogits and the k_rep_* entry points): a penalised draw of a sequence with the setting
+// {decay, repetition} divides or multiplies the logit of an occurred token by `repetition` in front of the penalty, and a sequence with decay != 1
+// keeps its occurrence row as floats that every recorded draw multiplies by decay before it counts the pick. {1, 1}: the penalised draw above.
 // The logits themselves are never written.
 #include "kdev.h"
 #include "model.h"
@@ -86,6 +89,49 @@ struct PenalisedLogits {
     }
     __device__ __forceinline__ float again(int j, const ProbVec & pr) const { return pr.get(j); }
 };
+
+// The penalised source of a sequence with a repetition setting (rwkv_mi_*repetition_set; model.h, RepRow): the row's occurrence word o[j] is a
+// float where the sequence is decaying (is_float), else (float) count[j], and the value is, every operation rounded to f32 in this order,
+//   a = l[j];   o[j] > 0:  a = a > 0 ? a / repetition : a * repetition;  a = a - (presence + o[j] * frequency);      bias:  a = a + bias[j]
+// ({1, 1}: the penalised source's adj[j], statement for statement). It stashes like the penalised source, so the guided source and the select
+// stage take it unchanged. It only reads the row: what a recorded draw does to it follows the draw (rep_record).
+struct RepetitionLogits {
+    static constexpr bool stashes = true;
+    const float * lg; const uint32_t * occ; const float * bias /* may be NULL */; float presence, frequency, repetition; bool is_float;
+    __device__ __forceinline__ float first(int j, const ProbVec & pr) const {
+        float a = lg[j];
+        const uint32_t w = occ[j];
+        const float o = is_float ? __uint_as_float(w) : (float) w;
+        if (o > 0.0f) {
+            a = a > 0.0f ? a / repetition : a * repetition;   // (0, -0, NaN and -inf take the multiply)
+            a = a - (presence + o * frequency);
+        }
+        if (bias) a = a + bias[j];
+        pr.set(j, a);
+        return a;
+    }
+    __device__ __forceinline__ float again(int j, const ProbVec & pr) const { return pr.get(j); }
+};
+
+// make_src of a row with the setting `rep`: occ is the row's table
+__device__ __forceinline__ auto rep_source(const float * lg, const uint32_t * occ, const float * bias, float presence, float frequency, const RepRow & rep) {
+    const bool is_float = rep.decay != 1.0f;
+    const float repetition = rep.repetition;
+    return [=](int i0) { return RepetitionLogits{lg + i0, occ + i0, bias ? bias + i0 : nullptr, presence, frequency, repetition, is_float}; };
+}
+
+// What follows the draw of such a row when it records (every thread calls it: record is the row's). A decaying row is swept by the whole
+// workgroup, o[j] = o[j] * decay in a pass of its own over the row in index order -- consecutive lanes, consecutive words, where the draw's
+// reads of the table are a chunk per thread: riding the sweep on those reads cost 0.06-0.08 ms a step on the 7B, this pass DESIGN 6.14's
+// figure -- and behind a barrier thread 0 adds 1.0f to the pick's entry; any other row counts + 1u. The body's barriers lie between the last
+// read of the row in first() and the sweep.
+__device__ __forceinline__ void rep_record(uint32_t * occ, int n, const RepRow & rep, uint32_t record, int pick) {
+    if (!record) return;
+    if (rep.decay == 1.0f) { if (threadIdx.x == 0) occ[pick] += 1u; return; }
+    for (int j = threadIdx.x; j < n; j += blockDim.x) occ[j] = __float_as_uint(__uint_as_float(occ[j]) * rep.decay);
+    __syncthreads();
+    if (threadIdx.x == 0) occ[pick] = __float_as_uint(__uint_as_float(occ[pick]) + 1.0f);
+}
 
 // The guided source (k_guided_sample_rows / k_guided_pen_sample_rows): the value the row's draw would read anyway -- Inner is PlainLogits or
 // PenalisedLogits -- with the mask applied LAST: -inf where the guide's transition from the row's state is dead. nx: the thread's chunk of
@@ -474,6 +520,52 @@ __global__ __launch_bounds__(1024) void k_guided_pen_sample_rows(const float * _
     if (threadIdx.x == 0 && srow) guide_advance(g, srow, pick);
 }
 
+// The entry points of a penalised draw with a repetition setting (k_rep_*; launched only where a row of the call has one: a call without
+// launches what it launched before): the single-context form with the settings by value, the row form and the guided row form with the
+// table `reps` parallel to the row table (cuts may be NULL; a row with {1, 1} reads uint32 counts and draws as k_pen_sample_rows does), and --
+// below -- the draft walk. The draw is cut_sample on RepetitionLogits, so a truncation setting and a guide compose with it as with the
+// penalised source; a retired row (live) returns before it reads or sweeps anything.
+__global__ __launch_bounds__(1024) void k_rep_pen_sample(const float * __restrict__ logits, int n, float temperature, float top_p, float u_in,
+                                                         unsigned long long seed, unsigned long long * counter, float presence, float frequency, uint32_t record,
+                                                         uint32_t * count, const float * __restrict__ bias, CutRow cut, RepRow rep,
+                                                         float * __restrict__ probs, uint32_t * __restrict__ out_token, uint32_t * __restrict__ hist, int hist_pos) {
+    const int pick = cut_sample(rep_source(logits, count, bias, presence, frequency, rep), cut, n, temperature, top_p, u_in, seed, counter, probs, out_token,
+                                hist ? hist + hist_pos : nullptr);
+    rep_record(count, n, rep, record, pick);
+}
+
+__global__ __launch_bounds__(1024) void k_rep_pen_sample_rows(const float * __restrict__ logits, int n, const PenaltyRow * __restrict__ table,
+                                                              const CutRow * __restrict__ cuts /* may be NULL */, const RepRow * __restrict__ reps,
+                                                              float * __restrict__ probs, size_t stride,
+                                                              uint32_t * __restrict__ tokens, uint32_t * __restrict__ hist, const uint32_t * __restrict__ live) {
+    const size_t r = blockIdx.x;
+    if (live && !live[r]) return;
+    const PenaltyRow row = table[r];
+    const CutRow cut = cuts ? cuts[r] : CutRow{0u, 0.0f};
+    const RepRow rep = reps[r];
+    const int pick = cut_sample(rep_source(logits + r * (size_t) n, row.count, row.bias, row.presence, row.frequency, rep),
+                                cut, n, row.p.temperature, row.p.top_p, row.p.u, row.p.seed, row.counter, probs + r * stride, tokens + r, hist ? hist + r : nullptr);
+    rep_record(row.count, n, rep, row.record, pick);
+}
+
+__global__ __launch_bounds__(1024) void k_guided_rep_pen_sample_rows(const float * __restrict__ logits, int n, const PenaltyRow * __restrict__ table,
+                                                                     const GuideRow * __restrict__ guides, const CutRow * __restrict__ cuts /* may be NULL */,
+                                                                     const RepRow * __restrict__ reps, float * __restrict__ probs, size_t stride,
+                                                                     uint32_t * __restrict__ tokens, uint32_t * __restrict__ hist, const uint32_t * __restrict__ live) {
+    const size_t r = blockIdx.x;
+    if (live && !live[r]) return;
+    const PenaltyRow row = table[r];
+    const GuideRow g = guides[r];
+    const CutRow cut = cuts ? cuts[r] : CutRow{0u, 0.0f};
+    const RepRow rep = reps[r];
+    const uint16_t * srow = g.next ? g.next + (size_t) *g.state * (size_t) n : nullptr;
+    const auto inner = rep_source(logits + r * (size_t) n, row.count, row.bias, row.presence, row.frequency, rep);
+    const int pick = cut_sample([=](int i0) { return GuidedLogits<RepetitionLogits>{inner(i0), srow ? srow + i0 : nullptr}; },
+                                cut, n, row.p.temperature, row.p.top_p, row.p.u, row.p.seed, row.counter, probs + r * stride, tokens + r, hist ? hist + r : nullptr);
+    rep_record(row.count, n, rep, row.record, pick);
+    if (threadIdx.x == 0 && srow) guide_advance(g, srow, pick);
+}
+
 // The greedy loops' choice for one row by the whole workgroup, returned to every thread: the largest logit, the lowest index among equals; a
 // NaN never wins, and where nothing compares greater than -inf the token is 0 -- the rule of k_argmax / k_argmax_live and of the scoring kernel.
 __device__ __forceinline__ int draft_argmax(const float * lg, int n) {
@@ -544,6 +636,41 @@ __global__ __launch_bounds__(1024) void k_draft_accept_rows(const float * __rest
     for (int i = threadIdx.x; i < n; i += blockDim.x) dst[i] = src[i];
 }
 
+// The walk's fourth family: family 2 on RepetitionLogits with the row's setting reps[r]. An entry point of its own with the walk written out
+// again, not a fourth value of FAMILY: the three instantiations above compile as they did before there were repetition settings (sharing the
+// walk through a device function moved the registers of the greedy one). Every position walked records, so a decaying row sweeps and counts
+// once per position walked and its table ends where the plain loop of keep[r] steps leaves it: nothing is rolled back.
+__global__ __launch_bounds__(1024) void k_rep_draft_accept_rows(const float * __restrict__ logits, int n, const SegState * __restrict__ segs,
+                                                                const uint32_t * __restrict__ tokens, const PenaltyRow * __restrict__ prows,
+                                                                const CutRow * __restrict__ cuts /* may be NULL */, const RepRow * __restrict__ reps,
+                                                                float * __restrict__ probs, size_t stride,
+                                                                uint32_t * __restrict__ out, int out_stride, uint32_t * __restrict__ keep,
+                                                                float * __restrict__ logits_row) {
+    const size_t r = blockIdx.x;
+    const SegState seg = segs[r];
+    const CutRow cut = cuts ? cuts[r] : CutRow{0u, 0.0f};
+    const RepRow rep = reps[r];
+    const int k = seg.t1 - seg.t0 - 1;
+    uint32_t * o = out + r * (size_t) out_stride;
+    int j = 0;
+    for (;;) {
+        const float * lg = logits + (size_t) (seg.t0 + j) * (size_t) n;
+        const PenaltyRow row = prows[r];
+        const int pick = cut_sample(rep_source(lg, row.count, row.bias, row.presence, row.frequency, rep),
+                                    cut, n, row.p.temperature, row.p.top_p, row.p.u, row.p.seed, row.counter, probs + r * stride, o + j, nullptr);
+        rep_record(row.count, n, rep, 1u, pick);
+        if (j == k || (uint32_t) pick != tokens[seg.t0 + j + 1]) break;
+        j++;
+        __threadfence_block();
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) keep[r] = (uint32_t) (j + 1);
+    for (int i = j + 1 + (int) threadIdx.x; i < out_stride; i += blockDim.x) o[i] = RWKV_MI_NO_TOKEN;
+    const float * src = logits + (size_t) (seg.t0 + j) * (size_t) n;
+    float * dst = logits_row + r * (size_t) n;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) dst[i] = src[i];
+}
+
 // rwkv_mi_batch_guide_create: the dense table next[n_states][n_vocab] from the CSR edges, one workgroup per state: the dead fill of the
 // state's row, then -- behind a barrier -- one 2-byte store per edge. A state's tokens are distinct, so no two stores meet.
 __global__ __launch_bounds__(256) void k_guide_expand(uint16_t * __restrict__ next, int n_vocab, const uint32_t * __restrict__ edge_begin,
@@ -592,6 +719,21 @@ __global__ __launch_bounds__(256) void k_count_add(uint32_t * __restrict__ count
     if (i < n && tokens[i] < (uint32_t) n_vocab) atomicAdd(count + tokens[i], 1u);
 }
 
+// The same on the table of a decaying sequence: for every token of the list, in its order, every entry is multiplied by decay and the token's
+// entry goes up by 1.0f -- what the draws that recorded these tokens would have left. One thread owns entry j from the first token to the last
+// (the list is read by every thread at the same index), so the n products are rounded one after the other as the plain loop rounds them; the
+// closed form decay^n is not bit-equal to that.
+__global__ __launch_bounds__(256) void k_count_add_decay(float * __restrict__ occ, const uint32_t * __restrict__ tokens, int64_t n, int n_vocab, float decay) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= n_vocab) return;
+    float o = occ[j];
+    for (int64_t i = 0; i < n; i++) {
+        o = o * decay;
+        if (tokens[i] == (uint32_t) j) o = o + 1.0f;
+    }
+    occ[j] = o;
+}
+
 // bias[ids[i]] = values[i] (rwkv_mi_*logit_bias_set, into a table the caller has cleared; the ids are distinct)
 __global__ __launch_bounds__(256) void k_bias_scatter(float * __restrict__ bias, const uint32_t * __restrict__ ids, const float * __restrict__ values, int64_t n, int n_vocab) {
     const int64_t i = (int64_t) blockIdx.x * 256 + threadIdx.x;
@@ -616,9 +758,12 @@ void launch_sample_rows(const float * logits, int64_t rows, int n, const SampleR
 }
 
 void launch_pen_sample(const float * logits, int n, float temperature, float top_p, float u, unsigned long long seed, unsigned long long * counter,
-                       float presence, float frequency, uint32_t record, uint32_t * count, const float * bias, const CutRow & cut,
+                       float presence, float frequency, uint32_t record, uint32_t * count, const float * bias, const CutRow & cut, const RepRow & rep,
                        float * probs, uint32_t * out_token, uint32_t * hist, int hist_pos, hipStream_t st) {
-    if (cut.top_k == 0u && cut.min_p == 0.0f)
+    if (rep.decay != 1.0f || rep.repetition != 1.0f)
+        hipLaunchKernelGGL(k_rep_pen_sample, dim3(1), dim3(1024), 0, st, logits, n, temperature, top_p, u, seed, counter, presence, frequency, record, count, bias, cut, rep,
+                           probs, out_token, hist, hist_pos);
+    else if (cut.top_k == 0u && cut.min_p == 0.0f)
         hipLaunchKernelGGL(k_pen_sample, dim3(1), dim3(1024), 0, st, logits, n, temperature, top_p, u, seed, counter, presence, frequency, record, count, bias,
                            probs, out_token, hist, hist_pos);
     else
@@ -626,9 +771,10 @@ void launch_pen_sample(const float * logits, int n, float temperature, float top
                            probs, out_token, hist, hist_pos);
 }
 
-void launch_pen_sample_rows(const float * logits, int64_t rows, int n, const PenaltyRow * table, const CutRow * cuts, float * probs, uint32_t * tokens,
-                            uint32_t * hist, const uint32_t * live, hipStream_t st) {
-    if (!cuts) hipLaunchKernelGGL(k_pen_sample_rows, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, table, probs, sample_scratch_floats(n), tokens, hist, live);
+void launch_pen_sample_rows(const float * logits, int64_t rows, int n, const PenaltyRow * table, const CutRow * cuts, const RepRow * reps, float * probs,
+                            uint32_t * tokens, uint32_t * hist, const uint32_t * live, hipStream_t st) {
+    if (reps) hipLaunchKernelGGL(k_rep_pen_sample_rows, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, table, cuts, reps, probs, sample_scratch_floats(n), tokens, hist, live);
+    else if (!cuts) hipLaunchKernelGGL(k_pen_sample_rows, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, table, probs, sample_scratch_floats(n), tokens, hist, live);
     else hipLaunchKernelGGL(k_cut_pen_sample_rows, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, table, cuts, probs, sample_scratch_floats(n), tokens, hist, live);
 }
 
@@ -637,14 +783,21 @@ void launch_guided_sample_rows(const float * logits, int64_t rows, int n, const 
     hipLaunchKernelGGL(k_guided_sample_rows, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, table, guides, cuts, probs, sample_scratch_floats(n), tokens, hist, live);
 }
 
-void launch_guided_pen_sample_rows(const float * logits, int64_t rows, int n, const PenaltyRow * table, const GuideRow * guides, const CutRow * cuts, float * probs,
-                                   uint32_t * tokens, uint32_t * hist, const uint32_t * live, hipStream_t st) {
-    hipLaunchKernelGGL(k_guided_pen_sample_rows, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, table, guides, cuts, probs, sample_scratch_floats(n), tokens, hist, live);
+void launch_guided_pen_sample_rows(const float * logits, int64_t rows, int n, const PenaltyRow * table, const GuideRow * guides, const CutRow * cuts,
+                                   const RepRow * reps, float * probs, uint32_t * tokens, uint32_t * hist, const uint32_t * live, hipStream_t st) {
+    if (reps) hipLaunchKernelGGL(k_guided_rep_pen_sample_rows, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, table, guides, cuts, reps, probs, sample_scratch_floats(n),
+                                 tokens, hist, live);
+    else hipLaunchKernelGGL(k_guided_pen_sample_rows, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, table, guides, cuts, probs, sample_scratch_floats(n), tokens, hist, live);
 }
 
 void launch_draft_accept_rows(const float * logits, int64_t rows, int n, const SegState * segs, const uint32_t * tokens, Draw draw, const SampleRow * srows,
-                              const PenaltyRow * prows, const CutRow * cuts, float * probs, uint32_t * out, int out_stride, uint32_t * keep, float * logits_row,
-                              hipStream_t st) {
+                              const PenaltyRow * prows, const CutRow * cuts, const RepRow * reps, float * probs, uint32_t * out, int out_stride, uint32_t * keep,
+                              float * logits_row, hipStream_t st) {
+    if (draw == Draw::penalized && reps) {
+        hipLaunchKernelGGL(k_rep_draft_accept_rows, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, segs, tokens, prows, cuts, reps, probs, sample_scratch_floats(n), out,
+                           out_stride, keep, logits_row);
+        return;
+    }
     auto go = [&](auto kern) {
         hipLaunchKernelGGL(kern, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, segs, tokens, srows, prows, cuts, probs, sample_scratch_floats(n), out, out_stride,
                            keep, logits_row);
@@ -667,6 +820,10 @@ void launch_stop_rows(const StopTables & t, int64_t rows, const uint32_t * hist,
 
 void launch_count_add(uint32_t * count, const uint32_t * tokens, int64_t n, int n_vocab, hipStream_t st) {
     if (n > 0) hipLaunchKernelGGL(k_count_add, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, st, count, tokens, n, n_vocab);
+}
+
+void launch_count_add_decay(float * occ, const uint32_t * tokens, int64_t n, int n_vocab, float decay, hipStream_t st) {
+    if (n > 0) hipLaunchKernelGGL(k_count_add_decay, dim3((unsigned) ((n_vocab + 255) / 256)), dim3(256), 0, st, occ, tokens, n, n_vocab, decay);
 }
 
 void launch_bias_scatter(float * bias, const uint32_t * ids, const float * values, int64_t n, int n_vocab, hipStream_t st) {

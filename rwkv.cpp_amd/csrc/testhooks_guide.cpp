@@ -69,7 +69,7 @@ RWKV_API bool rwkv_mi_test_guided_rows(const float * logits, int64_t n_rows, int
              hipMemcpy(grow_buf.p, grows.data(), R * sizeof(GuideRow), hipMemcpyHostToDevice) == hipSuccess;
     }
     if (ok) {
-        if (penalties) launch_guided_pen_sample_rows(logits_buf.p, n_rows, (int) n_vocab, prow_buf.p, grow_buf.p, nullptr, probs_buf.p, tok_buf.p, nullptr, nullptr, nullptr);
+        if (penalties) launch_guided_pen_sample_rows(logits_buf.p, n_rows, (int) n_vocab, prow_buf.p, grow_buf.p, nullptr, nullptr, probs_buf.p, tok_buf.p, nullptr, nullptr, nullptr);
         else launch_guided_sample_rows(logits_buf.p, n_rows, (int) n_vocab, srow_buf.p, grow_buf.p, nullptr, probs_buf.p, tok_buf.p, nullptr, nullptr, nullptr);
         ok = hipDeviceSynchronize() == hipSuccess && hipMemcpy(tokens_out, tok_buf.p, R * 4, hipMemcpyDeviceToHost) == hipSuccess &&
              hipMemcpy(states_out, state_buf.p, R * 4, hipMemcpyDeviceToHost) == hipSuccess &&

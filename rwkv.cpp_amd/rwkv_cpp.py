@@ -26,6 +26,9 @@ GUIDE_HOOKS_LIB_PATH = os.path.join(PKG_DIR, os.environ.get("RWKV_LIB_DIR", "lib
 # tests/ only: the same objects + csrc/testhooks_cut.cpp (include/rwkv_testhooks_cut.h): the plain sampler with a truncation setting per row
 CUT_HOOKS_LIB_PATH = os.path.join(PKG_DIR, os.environ.get("RWKV_LIB_DIR", "lib"), "librwkv_testhooks_cut.so")
 
+# tests/ only: the same objects + csrc/testhooks_decay.cpp (include/rwkv_testhooks_decay.h): the penalised sampler with a repetition setting per row
+DECAY_HOOKS_LIB_PATH = os.path.join(PKG_DIR, os.environ.get("RWKV_LIB_DIR", "lib"), "librwkv_testhooks_decay.so")
+
 QUANTIZED_FORMAT_NAMES =("Q4_0", "Q4_1", "Q5_0", "Q5_1", "Q8_0")
 PENALTY_SYMBOLS = ("rwkv_mi_batch_counts_reset", "rwkv_mi_batch_counts_add", "rwkv_mi_batch_counts_store", "rwkv_mi_batch_logit_bias_set",
                    "rwkv_mi_batch_eval_sample_penalized", "rwkv_mi_batch_eval_ragged_sample_penalized", "rwkv_mi_batch_decode_sample_penalized",
@@ -42,6 +45,8 @@ GUIDE_MAX_STATES = 65535    # RWKV_MI_GUIDE_MAX_STATES: states per guide
 NO_GUIDE = 0xFFFFFFFF       # RWKV_MI_NO_GUIDE: a slot without a guide
 DRAFT_SYMBOLS = ("rwkv_mi_batch_eval_draft",)
 TRUNCATION_SYMBOLS = ("rwkv_mi_batch_truncation_set", "rwkv_mi_batch_truncation_get", "rwkv_mi_truncation_set", "rwkv_mi_truncation_get")
+REPETITION_SYMBOLS = ("rwkv_mi_batch_repetition_set", "rwkv_mi_batch_repetition_get", "rwkv_mi_batch_counts_store_f32",
+                      "rwkv_mi_repetition_set", "rwkv_mi_repetition_get", "rwkv_mi_counts_store_f32")
 DRAFT_MAX = 8               # RWKV_MI_DRAFT_MAX: draft tokens per row of RWKVBatch.eval_draft
 COPY_STATE, COPY_COUNTER, COPY_COUNTS, COPY_BIAS = 1, 2, 4, 8  # RWKV_MI_COPY_*: the bits of rwkv_mi_batch_state_copy's `what`
 TOP_MAX = 20             # RWKV_MI_TOP_MAX: the most alternatives a report holds per token, and the widest beam
@@ -80,6 +85,11 @@ P_STOP_PARAMS = ctypes.POINTER(StopParams)
 class CutParams(ctypes.Structure):
     """struct rwkv_mi_test_cut (include/rwkv_testhooks_cut.h): one row's truncation setting as the test hook takes it, 8 bytes."""
     _fields_ = [("top_k", ctypes.c_uint32), ("min_p", ctypes.c_float)]
+
+
+class RepParams(ctypes.Structure):
+    """struct rwkv_mi_test_rep (include/rwkv_testhooks_decay.h): one row's repetition setting as the test hook takes it, 8 bytes."""
+    _fields_ = [("decay", ctypes.c_float), ("repetition", ctypes.c_float)]
 
 
 class BeamParams(ctypes.Structure):
@@ -312,6 +322,22 @@ class RWKVSharedLibrary:
             L.rwkv_mi_truncation_get.argtypes = [c_ctx, P_UINT32, P_FLOAT]
             for name in TRUNCATION_SYMBOLS:
                 getattr(L, name).restype = ctypes.c_bool
+        # penalty decay and repetition penalty: per-sequence repetition settings of the penalised draws
+        if hasattr(L, "rwkv_mi_batch_repetition_set"):   # (absent from older A/B builds loaded through RWKV_LIB_DIR)
+            L.rwkv_mi_batch_repetition_set.argtypes = [c_batch, ctypes.c_size_t, ctypes.c_float, ctypes.c_float]
+            L.rwkv_mi_batch_repetition_get.argtypes = [c_batch, ctypes.c_size_t, P_FLOAT, P_FLOAT]
+            L.rwkv_mi_batch_counts_store_f32.argtypes = [c_batch, ctypes.c_size_t, P_FLOAT]
+            L.rwkv_mi_repetition_set.argtypes = [c_ctx, ctypes.c_float, ctypes.c_float]
+            L.rwkv_mi_repetition_get.argtypes = [c_ctx, P_FLOAT, P_FLOAT]
+            L.rwkv_mi_counts_store_f32.argtypes = [c_ctx, P_FLOAT]
+            for name in REPETITION_SYMBOLS:
+                getattr(L, name).restype = ctypes.c_bool
+        if hasattr(L, "rwkv_mi_test_decay_rows"):   # (librwkv_testhooks_decay.so only)
+            L.rwkv_mi_test_decay_rows.argtypes = [P_FLOAT, ctypes.c_int64, ctypes.c_int64, P_SAMPLE_PARAMS, P_PENALTY_PARAMS, ctypes.POINTER(RepParams), P_UINT32,
+                                                  P_FLOAT, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int, P_UINT32]
+            L.rwkv_mi_test_decay_rows.restype = ctypes.c_bool
+            L.rwkv_mi_test_decay_counts_add.argtypes = [P_FLOAT, ctypes.c_int64, P_UINT32, ctypes.c_int64, ctypes.c_float]
+            L.rwkv_mi_test_decay_counts_add.restype = ctypes.c_bool
         if hasattr(L, "rwkv_mi_test_cut_rows"):   # (librwkv_testhooks_cut.so only)
             L.rwkv_mi_test_cut_rows.argtypes = [P_FLOAT, ctypes.c_int64, ctypes.c_int64, P_SAMPLE_PARAMS, ctypes.POINTER(CutParams), ctypes.POINTER(ctypes.c_uint64),
                                                 ctypes.c_int, P_UINT32, P_FLOAT]
@@ -646,6 +672,24 @@ class RWKVModel:
         k, p = ctypes.c_uint32(0), ctypes.c_float(0.0)
         self._mi("rwkv_mi_truncation_get", ctypes.byref(k), ctypes.byref(p))
         return int(k.value), float(p.value)
+
+    def set_repetition(self, decay: float = 1.0, repetition: float = 1.0) -> None:
+        """The context's repetition setting, read by every PENALISED draw from now on: repetition (1: off) divides the positive and multiplies
+        the other logits of the tokens that have occurred; decay (1: off) makes the occurrence table a float table that every recorded draw
+        multiplies by decay before it counts its token. (1, 1) clears. A set that turns decay on or off zeroes the table."""
+        self._mi("rwkv_mi_repetition_set", float(decay), float(repetition))
+
+    def repetition(self) -> Tuple[float, float]:
+        """The context's repetition setting (decay, repetition); (1.0, 1.0) is none."""
+        d, r = ctypes.c_float(0.0), ctypes.c_float(0.0)
+        self._mi("rwkv_mi_repetition_get", ctypes.byref(d), ctypes.byref(r))
+        return float(d.value), float(r.value)
+
+    def counts_f32(self) -> np.ndarray:
+        """The context's occurrence table as float32 [n_vocab]: the decayed occurrences of a decaying context, the counts of any other."""
+        out = np.empty(self.n_vocab, dtype=np.float32)
+        self._mi("rwkv_mi_counts_store_f32", out.ctypes.data_as(P_FLOAT))
+        return out
 
     def sample_penalized(self, temperature: float = 1.0, top_p: float = 0.8, u: float = -1.0, seed: int = 0, presence: float = 0.2,
                          frequency: float = 0.2, record: bool = True) -> int:
@@ -999,6 +1043,29 @@ class RWKVBatch:
         if not self._L.rwkv_mi_batch_truncation_get(self._ptr, slot, ctypes.byref(k), ctypes.byref(p)):
             self._fail("rwkv_mi_batch_truncation_get")
         return int(k.value), float(p.value)
+
+    def set_repetition(self, slot: int, decay: float = 1.0, repetition: float = 1.0) -> None:
+        """The slot's repetition setting, read by every PENALISED draw of the slot from now on (eval_sample_penalized, the ragged form, the
+        penalised loop, decode_until and eval_draft with penalties; guided or truncating or not): repetition (1: off) divides the positive and
+        multiplies the other logits of the tokens that have occurred; decay (1: off) makes the slot's occurrence row a float row that every
+        recorded draw multiplies by decay before it counts its token. (1, 1) clears. A set that turns decay on or off zeroes the row.
+        copy_state does not carry the setting: set it on the destination slot."""
+        if not self._L.rwkv_mi_batch_repetition_set(self._ptr, slot, float(decay), float(repetition)):
+            self._fail("rwkv_mi_batch_repetition_set")
+
+    def repetition(self, slot: int) -> Tuple[float, float]:
+        """The slot's repetition setting (decay, repetition); (1.0, 1.0) is none."""
+        d, r = ctypes.c_float(0.0), ctypes.c_float(0.0)
+        if not self._L.rwkv_mi_batch_repetition_get(self._ptr, slot, ctypes.byref(d), ctypes.byref(r)):
+            self._fail("rwkv_mi_batch_repetition_get")
+        return float(d.value), float(r.value)
+
+    def counts_f32(self, slot: int) -> np.ndarray:
+        """The slot's occurrence row as float32 [n_vocab]: the decayed occurrences of a decaying slot, the counts of any other."""
+        out = np.empty(self._n_vocab, dtype=np.float32)
+        if not self._L.rwkv_mi_batch_counts_store_f32(self._ptr, slot, out.ctypes.data_as(P_FLOAT)):
+            self._fail("rwkv_mi_batch_counts_store_f32")
+        return out
 
     # --- penalised sampling: one occurrence table and one bias table per slot (include/rwkv_mi355x.h) ---
 

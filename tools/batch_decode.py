@@ -64,6 +64,17 @@ also go to --out:
   mode cut_host     the host path doing the same job: RWKVBatch.eval with the logits to the host, then in NumPy the top-k mask (argpartition),
                     softmax, the top-p cut-off intersected with min-p, the draw; host clock around the loop
 
+--sample --penalties --decay D[,D...] [--repetition R] times the penalised loop (temperature 1.0, top-p 0.8, seed = row, presence 0.2, frequency
+0.2, every step recorded) under repetition settings (rwkv_mi_batch_repetition_set) in the same process, --tokens steps, HIP events around each
+device loop, the smallest of --reps runs (the loop without a setting also with its largest run: the run-to-run spread of the box); records also
+go to --out:
+  mode decay_plain    rwkv_mi_batch_decode_sample_penalized with no setting on any slot -- the only arm when the library loaded through
+                      RWKV_LIB_DIR is a build without the settings
+  mode decay_device   the same loop with every slot set to {D, 1} for each D of the list, to {1, R}, and to {the first D, R}; setting_ms_per_step
+                      is its step minus decay_plain's
+  mode decay_host     the host path doing the same job: RWKVBatch.eval with the logits to the host, then in NumPy the decayed float table, the
+                      repetition and presence / frequency penalty on it, sample_probs; host clock around the loop
+
 --beam W[,W...] times rwkv_mi_batch_decode_beam (no end tokens, --tokens steps) for every width of the list, G = rows // W groups at the largest
 row count of --n, HIP events around each device loop, the smallest of --reps runs; records also go to --out:
   mode beam        ms per step of the beam loop beside the greedy loop's at the same row count from the same run, and their difference
@@ -572,6 +583,85 @@ def guide(pkg, m, args):
         sink.close()
 
 
+def decay(pkg, m, args):
+    import numpy as np
+    V = m.n_vocab
+    have = hasattr(m._library.library, "rwkv_mi_batch_repetition_set")   # (an older build loaded through RWKV_LIB_DIR: the plain arm only)
+    sink = open(args.out, "a") if args.out else None
+    ns = [int(x) for x in args.n.split(",")]
+    decays = [float(x) for x in args.decay.split(",")]
+    steps, presence, frequency = args.tokens, 0.2, 0.2
+
+    def emit(rec):
+        rec.update({"steps": steps, "reps": args.reps, "presence": presence, "frequency": frequency, "temperature": 1.0, "top_p": 0.8,
+                    "config": args.config, "dtype": args.dtype, "settings_in_library": have})
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if sink:
+            sink.write(line + "\n")
+            sink.flush()
+
+    b = pkg.RWKVBatch(m, max(ns))
+    for n in ns:
+        slots = list(range(n))
+        first = [(7 * i + 1) % V for i in slots]
+
+        def device(setting):
+            out = []
+            for r in range(args.reps + 1):   # (run 0: warm-up -- tables, rows and tile-major weight images of the first call)
+                for s in slots:
+                    b.state_load(s, None)
+                    if have:
+                        b.set_repetition(s, *setting)
+                    b.counts_reset(s)
+                    b.rng_seek(s, 0)
+                out.append(b.decode_sample_penalized(slots, first, args.warmup if r == 0 else steps, 1.0, 0.8, slots, presence, frequency)[1])
+            return out[1:]
+
+        plain = device((1.0, 1.0))
+        plain_ms = min(plain)
+        emit({"mode": "decay_plain", "n": n, "ms_per_step": round(plain_ms / steps, 4), "ms_per_step_max": round(max(plain) / steps, 4),
+              "spread": round(max(plain) / plain_ms - 1.0, 4)})
+        if not have:
+            continue
+        for setting in [(d, 1.0) for d in decays] + [(1.0, args.repetition), (decays[0], args.repetition)]:
+            ms = min(device(setting))
+            emit({"mode": "decay_device", "n": n, "decay": setting[0], "repetition": setting[1], "ms_per_step": round(ms / steps, 4),
+                  "plain_ms_per_step": round(plain_ms / steps, 4), "setting_ms_per_step": round((ms - plain_ms) / steps, 4),
+                  "table_store_bytes_per_step": 4 * V * n if setting[0] != 1.0 else 0})
+        for s in slots:
+            b.set_repetition(s, 1.0, 1.0)
+        # the way without the settings: per token the logits to the host, the demos' recipe on a float table in NumPy, sample_probs
+        d32, r32, p32, f32 = np.float32(decays[0]), np.float32(args.repetition), np.float32(presence), np.float32(frequency)
+        rngs = [np.random.default_rng(i) for i in range(n)]
+        for s in slots:
+            b.state_load(s, None)
+        toks = list(first)
+        for timed in (False, True):
+            occ = np.zeros((n, V), dtype=np.float32)
+            t0 = time.perf_counter()
+            for _ in range(steps if timed else args.warmup):
+                lg = b.eval(slots, toks)
+                for i in range(n):
+                    row, o = lg[i], occ[i]
+                    at = np.flatnonzero(o > 0)
+                    v = row[at]
+                    v = np.where(v > 0, v / r32, v * r32)
+                    row[at] = v - (p32 + o[at] * f32)
+                    toks[i] = host_sample(row, 1.0, 0.8, rngs[i])
+                    o *= d32
+                    o[toks[i]] += np.float32(1.0)
+            host_ms = (time.perf_counter() - t0) * 1e3 / steps
+        dev_ms = min(device((decays[0], args.repetition))) / steps
+        emit({"mode": "decay_host", "n": n, "decay": decays[0], "repetition": args.repetition, "ms_per_step": round(host_ms, 4),
+              "device_ms_per_step": round(dev_ms, 4), "host_over_device": round(host_ms / dev_ms, 2), "logits_bytes_per_step": 4 * n * V})
+        for s in slots:
+            b.set_repetition(s, 1.0, 1.0)
+    b.free()
+    if sink:
+        sink.close()
+
+
 def draft(pkg, m, args):
     import numpy as np
     V = m.n_vocab
@@ -691,10 +781,13 @@ def main():
                     help="with --sample: time the sampled loop plain, guided on the device, and masked from the host before every token (see above)")
     ap.add_argument("--cut", default=None, metavar="K[,K...]",
                     help="with --sample: time the sampled loop with no truncation setting, with top_k = each K, with min_p = 0.05, and with both (see above)")
+    ap.add_argument("--decay", default=None, metavar="D[,D...]",
+                    help="with --sample --penalties: time the penalised loop with no repetition setting, with decay = each D, with --repetition, and with both (see above)")
+    ap.add_argument("--repetition", type=float, default=1.1, help="--decay: the repetition penalty of the arms that have one")
     ap.add_argument("--draft", default=None, metavar="K[,K...]",
                     help="time rwkv_mi_batch_eval_draft for each draft length of the list: its overhead over the ragged pass, tokens/s by acceptance (see above)")
-    ap.add_argument("--reps", type=int, default=3, help="--draft, --ragged, --until, --logprobs, --beam, --guide, --cut: timed runs of each shape (the smallest is reported)")
-    ap.add_argument("--out", default=None, help="--draft, --ragged, --penalties, --until, --logprobs, --beam, --guide, --cut: also append the records to this file")
+    ap.add_argument("--reps", type=int, default=3, help="--draft, --ragged, --until, --logprobs, --beam, --guide, --cut, --decay: timed runs of each shape (the smallest is reported)")
+    ap.add_argument("--out", default=None, help="--draft, --ragged, --penalties, --until, --logprobs, --beam, --guide, --cut, --decay: also append the records to this file")
     args = ap.parse_args()
 
     import __graft_entry__ as graft
@@ -739,6 +832,12 @@ def main():
         if not args.sample:
             ap.error("--cut times the sampled loop: give --sample with it")
         cut(pkg, m, args)
+        m.free()
+        return
+    if args.decay is not None:
+        if not (args.sample and args.penalties):
+            ap.error("--decay times the penalised sampled loop: give --sample --penalties with it")
+        decay(pkg, m, args)
         m.free()
         return
     if args.logprobs is not None:

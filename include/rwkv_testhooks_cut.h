@@ -15,8 +15,8 @@ extern "C" {
 struct rwkv_mi_test_cut { uint32_t top_k; float min_p; };
 
 /* Test hook (used by tests/ only): the plain sampler with a truncation setting per row on caller-supplied logits [n_rows][n_vocab]. Row r
- * draws with params[r], cuts[r] and counters[r] ([n_rows] in / out; NULL: zero, not returned). rows_kernel != 0: k_cut_sample_rows in ONE launch
- * with the settings as its row table; 0: row after row, each with its setting by value (k_cut_sample; k_sample where it is {0, 0}). tokens_out: [n_rows]. weights_out
+ * draws with params[r], cuts[r] and counters[r] ([n_rows] in / out; NULL: zero, not returned). rows_kernel != 0: k_draw_rows<plain, 1, 0> in ONE launch
+ * with the settings as its row table; 0: row after row, each with its setting by value (k_draw<plain, 1>; k_draw<plain, 0> where it is {0, 0}). tokens_out: [n_rows]. weights_out
  * ([n_rows][n_vocab], or NULL): the vector the draw ran over -- the body's scratch after the draw, copied out in TOKEN order (the kernel keeps
  * it transposed): the unnormalised weight of every token, 0 where a truncation cut it. */
 RWKV_API bool rwkv_mi_test_cut_rows(const float * logits, int64_t n_rows, int64_t n_vocab, const struct rwkv_mi_sample_params * params,

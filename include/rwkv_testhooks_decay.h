@@ -17,8 +17,8 @@ struct rwkv_mi_test_rep { float decay; float repetition; };
 /* Test hook (used by tests/ only): the penalised sampler with a repetition setting per row on caller-supplied logits [n_rows][n_vocab]. Row r
  * draws with params[r], penalties[r] (record included), reps[r] and counters[r] ([n_rows] in / out; NULL: zero, not returned) on the occurrence
  * row occ[r] ([n_rows][n_vocab] 4-byte words in / out: floats where reps[r].decay != 1, uint32 counts elsewhere) and bias[r] ([n_rows][n_vocab];
- * NULL: no row has a bias). rows_kernel != 0: k_rep_pen_sample_rows in ONE launch with the settings as its table, a row with {1, 1} included;
- * 0: row after row, each with its setting by value (k_rep_pen_sample; k_pen_sample where it is {1, 1}). tokens_out: [n_rows]. */
+ * NULL: no row has a bias). rows_kernel != 0: k_draw_rows<rep, 1, 0> in ONE launch with the settings as its table, a row with {1, 1} included;
+ * 0: row after row, each with its setting by value (k_draw<rep, 1>; k_draw<pen, 0> where it is {1, 1}). tokens_out: [n_rows]. */
 RWKV_API bool rwkv_mi_test_decay_rows(const float * logits, int64_t n_rows, int64_t n_vocab, const struct rwkv_mi_sample_params * params,
                                       const struct rwkv_mi_penalty_params * penalties, const struct rwkv_mi_test_rep * reps, uint32_t * occ,
                                       const float * bias, uint64_t * counters, int rows_kernel, uint32_t * tokens_out);

@@ -11,7 +11,7 @@
 extern "C" {
 #endif
 
-/* Test hook (used by tests/ only): k_guided_sample_rows (penalties == NULL) or k_guided_pen_sample_rows in ONE launch on caller-supplied logits
+/* Test hook (used by tests/ only): k_draw_rows<plain, 1, 1> (penalties == NULL) or k_draw_rows<pen, 1, 1> in ONE launch on caller-supplied logits
  * [n_rows][n_vocab], after k_guide_expand has built the tables of n_guides guides. Guide g has n_states[g] states; the guides' edges are given
  * back to back in the CSR form of rwkv_mi_batch_guide_create: edge_begin holds sum(n_states[g] + 1) words, each guide's own run starting at 0,
  * edge_tokens / edge_next the edges of guide 0, then guide 1, ... . Row r draws with params[r] and counters[r] ([n_rows] in / out; NULL: zero,

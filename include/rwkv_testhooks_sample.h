@@ -11,7 +11,7 @@
 extern "C" {
 #endif
 
-/* Test hook (used by tests/ only): k_sample_rows in one launch (rows_kernel != 0), or k_sample row after row (rows_kernel == 0), on
+/* Test hook (used by tests/ only): k_draw_rows<plain, 0, 0> in one launch (rows_kernel != 0), or k_draw<plain, 0> row after row (rows_kernel == 0), on
  * caller-supplied logits [n_rows][n_vocab]; counters: [n_rows] in / out (NULL: zero, not returned). */
 RWKV_API bool rwkv_mi_test_sample_rows(const float * logits, int64_t n_rows, int64_t n_vocab, const struct rwkv_mi_sample_params * params,
                                        uint64_t * counters, int rows_kernel, uint32_t * tokens_out);

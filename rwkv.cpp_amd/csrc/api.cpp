@@ -719,15 +719,13 @@ RWKV_API bool rwkv_mi_truncation_get(struct rwkv_context * ctx, uint32_t * top_k
 }
 
 // the penalty of a single-context draw: the context's counts and bias enter the logits; record: the chosen token is counted
-struct Penalty { float presence, frequency; uint32_t record; };
+using Penalty = rwkv_mi_penalty_params;
 
 // one draw from the context's logits into *out (and hist[hist_pos] when hist is given), on the adjusted logits when pen is given
 static void launch_draw(rwkv_context * ctx, float temperature, float top_p, float u, uint64_t seed, const Penalty * pen, uint32_t * out, uint32_t * hist, int hist_pos) {
     const int n_vocab = (int) ctx->model->n_vocab();
-    const DrawState & d = ctx->draw;
-    if (pen) launch_pen_sample(ctx->d_logits.p, n_vocab, temperature, top_p, u, seed, d.counter(0), pen->presence, pen->frequency, pen->record, d.counts_of(0),
-                               d.bias_of(0), d.cuts[0], d.reps[0], d.probs.p, out, hist, hist_pos, ctx->stream);
-    else launch_sample(ctx->d_logits.p, n_vocab, temperature, top_p, u, seed, d.counter(0), d.cuts[0], d.probs.p, out, hist, hist_pos, ctx->stream);
+    const DrawRow row = ctx->draw.row(0, rwkv_mi_sample_params{temperature, top_p, u, seed}, pen, pen ? pen->record : 0u);
+    launch_draw(ctx->d_logits.p, n_vocab, row, DrawForm::of_row(pen ? Draw::penalized : Draw::sample, row), ctx->draw.probs.p, out, hist, hist_pos, ctx->stream);
     // the report of the token just written, slot hist_pos of the context's buffers (ensure_report has sized them)
     const LogprobReport & lp = ctx->lp;
     if (lp.enabled) launch_logprob_rows(ctx->d_logits.p, 1, n_vocab, out, (int) lp.top_n, lp.d_chosen.p + hist_pos, lp.d_ids.p + (size_t) hist_pos * lp.top_n,
@@ -1102,25 +1100,15 @@ struct rwkv_mi_batch {
     DevBuf<RowState> d_rows;           // [2][n_slots]: the row tables of a call (the greedy loop alternates between the two)
     PinBuf<RowState> h_rows;           // pinned staging of the same
     DrawState draw;                    // the slots' draw state: counters (zero at creation), sampler scratch, occurrence and bias tables
-    DevBuf<SampleRow> d_srows;         // [n_slots]: the sampler's row table of a call (parameters + the counter of the row's slot) with its pinned
-    PinBuf<SampleRow> h_srows;         // staging, allocated by the first sampling call
-    DevBuf<PenaltyRow> d_prows;        // the penalised row table of a call with its pinned staging, allocated by the first call of that family
-    PinBuf<PenaltyRow> h_prows;
+    // the row table of a drawing call, [n_slots] (model.h, DrawRow: filled by DrawState::row), with its pinned staging -- allocated with the
+    // sampler's buffers by the first drawing call -- and the form of the current call's kernel
+    DevBuf<DrawRow> d_draw_rows;
+    PinBuf<DrawRow> h_draw_rows;
+    DrawForm form;
     // guided decoding (rwkv_mi_batch_guide_*): the guides' dense tables next[n_states][n_vocab], shared by the slots (which guide a slot has, and
-    // its state and miss words, are the draw state's); the guide rows of a call with their pinned staging, allocated by the first call that names
-    // a guided slot
+    // its state and miss words, are the draw state's)
     DevBuf<uint16_t> guides[RWKV_MI_GUIDE_MAX];
     uint32_t guide_states[RWKV_MI_GUIDE_MAX] = {};   // n_states of each (0: the id is free)
-    DevBuf<GuideRow> d_grows;
-    PinBuf<GuideRow> h_grows;
-    // the truncation rows of a call (rwkv_mi_batch_truncation_set; the settings themselves are the draw state's host words) with their pinned
-    // staging, allocated by the first call that names a slot with a setting
-    DevBuf<CutRow> d_crows;
-    PinBuf<CutRow> h_crows;
-    // the repetition rows of a penalised call (rwkv_mi_batch_repetition_set; the settings are the draw state's host words) with their pinned
-    // staging, allocated by the first penalised call that names a slot with a setting
-    DevBuf<RepRow> d_rrows;
-    PinBuf<RepRow> h_rrows;
     // ragged passes (rwkv_mi_batch_eval_ragged*): the tables of a call -- segments, the short ones again, seg_of[T], last[n] -- in one device
     // buffer with its pinned staging, grown to the largest call so far; the long segments stay on the host (each is a launch of its own)
     DevBuf<uint8_t> d_seg;
@@ -1265,46 +1253,10 @@ static bool batch_check_params(rwkv_mi_batch * B, const rwkv_mi_sample_params * 
     return true;
 }
 
-// the row tables of a call's draw with their pinned staging, then the slots' own buffers (B->draw): on the first call of the family. The plain
-// sampler allocates none of the penalty tables
-static bool batch_ensure_draw_tables(rwkv_mi_batch * B, bool penalized) {
-    rwkv_context * ctx = B->ctx;
-    const size_t n = B->n_slots;
-    const hipError_t e = grow(want(B->d_srows, B->d_srows ? 0 : n), want(B->h_srows, B->h_srows ? 0 : n),
-                              want(B->d_prows, !penalized || B->d_prows ? 0 : n), want(B->h_prows, !penalized || B->h_prows ? 0 : n));
-    RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the sampler's row tables for %zu slots: %s", n, hipGetErrorString(e));
-    return B->draw.ensure_sampler(ctx, B->run->stream) && (!penalized || B->draw.ensure_penalty(ctx, B->run->stream));
-}
-
-// the sampler's row table of the n named slots, one upload per call (after batch_upload*: the stream has been drained, the staging is free).
-// loop: the generator draws
-static bool batch_upload_params(rwkv_mi_batch * B, const BatchCall & c, bool loop) {
-    for (size_t i = 0; i < c.n; i++) {
-        B->h_srows.p[i] = SampleRow{c.params[i], B->draw.counter(c.slots[i])};
-        if (loop) B->h_srows.p[i].p.u = -1.0f;
-    }
-    BATCH_HIP_OK(B, hipMemcpyAsync(B->d_srows.p, B->h_srows.p, c.n * sizeof(SampleRow), hipMemcpyHostToDevice, B->run->stream));
-    return true;
-}
-
 // the penalties of a call (checked with the other arguments, before anything changes)
 static bool batch_check_penalties(rwkv_mi_batch * B, const rwkv_mi_penalty_params * penalties, size_t n) {
     RW_CTX_CHECK(B->ctx, RWKV_ERROR_ARGS, false, penalties != nullptr, "penalties is NULL");
     for (size_t i = 0; i < n; i++) if (!check_penalty(B->ctx, penalties[i].presence, penalties[i].frequency, i)) return false;
-    return true;
-}
-
-// the penalised row table of the n named slots (after batch_upload*: the stream has been drained, the staging is free). loop: the generator
-// draws and every step records
-static bool batch_upload_penalty_rows(rwkv_mi_batch * B, const BatchCall & c, bool loop) {
-    const DrawState & d = B->draw;
-    for (size_t i = 0; i < c.n; i++) {
-        const size_t s = c.slots[i];
-        const rwkv_mi_penalty_params & pen = c.penalties[i];
-        B->h_prows.p[i] = PenaltyRow{c.params[i], d.counter(s), pen.presence, pen.frequency, loop ? 1u : pen.record, d.counts_of(s), d.bias_of(s)};
-        if (loop) B->h_prows.p[i].p.u = -1.0f;
-    }
-    BATCH_HIP_OK(B, hipMemcpyAsync(B->d_prows.p, B->h_prows.p, c.n * sizeof(PenaltyRow), hipMemcpyHostToDevice, B->run->stream));
     return true;
 }
 
@@ -1320,50 +1272,6 @@ static bool batch_names_guided(const rwkv_mi_batch * B, const uint32_t * slots, 
 static bool batch_check_unguided(rwkv_mi_batch * B, const uint32_t * slots, size_t n, const char * call) {
     RW_CTX_CHECK(B->ctx, RWKV_ERROR_ARGS, false, !batch_names_guided(B, slots, n),
                  "%s takes no slot with a guide attached (guided greedy is temperature 0 of the sampled calls)", call);
-    return true;
-}
-
-// the guide rows of the n named slots (after batch_upload*: the stream has been drained, the staging is free): the table of the slot's guide, or
-// NULL for a slot without one, and the slot's two words
-static bool batch_upload_guide_rows(rwkv_mi_batch * B, const BatchCall & c) {
-    const DrawState & d = B->draw;
-    for (size_t i = 0; i < c.n; i++) {
-        const size_t s = c.slots[i];
-        const uint32_t g = d.guide_of[s];
-        B->h_grows.p[i] = GuideRow{g == RWKV_MI_NO_GUIDE ? nullptr : B->guides[g].p, d.guide_state.p + s, d.guide_misses.p + s};
-    }
-    BATCH_HIP_OK(B, hipMemcpyAsync(B->d_grows.p, B->h_grows.p, c.n * sizeof(GuideRow), hipMemcpyHostToDevice, B->run->stream));
-    return true;
-}
-
-// ---- truncation settings: which calls see one (rwkv_mi_*truncation_set) ----
-
-// whether a call names a slot whose setting truncates anything (its slots have been checked)
-static bool batch_names_cut(const rwkv_mi_batch * B, const uint32_t * slots, size_t n) {
-    for (size_t i = 0; i < n; i++) if (B->draw.has_cut(slots[i])) return true;
-    return false;
-}
-
-// the truncation rows of the n named slots (after batch_upload*: the stream has been drained, the staging is free)
-static bool batch_upload_cut_rows(rwkv_mi_batch * B, const BatchCall & c) {
-    for (size_t i = 0; i < c.n; i++) B->h_crows.p[i] = B->draw.cuts[c.slots[i]];
-    BATCH_HIP_OK(B, hipMemcpyAsync(B->d_crows.p, B->h_crows.p, c.n * sizeof(CutRow), hipMemcpyHostToDevice, B->run->stream));
-    return true;
-}
-
-// ---- repetition settings: which calls see one (rwkv_mi_*repetition_set) ----
-
-// whether a call draws penalised and names a slot with a repetition setting (its slots have been checked): the other draws never read one
-static bool batch_names_rep(const rwkv_mi_batch * B, const BatchCall & c) {
-    if (c.draw != Draw::penalized) return false;
-    for (size_t i = 0; i < c.n; i++) if (B->draw.has_rep(c.slots[i])) return true;
-    return false;
-}
-
-// the repetition rows of the n named slots (after batch_upload*: the stream has been drained, the staging is free)
-static bool batch_upload_rep_rows(rwkv_mi_batch * B, const BatchCall & c) {
-    for (size_t i = 0; i < c.n; i++) B->h_rrows.p[i] = B->draw.reps[c.slots[i]];
-    BATCH_HIP_OK(B, hipMemcpyAsync(B->d_rrows.p, B->h_rrows.p, c.n * sizeof(RepRow), hipMemcpyHostToDevice, B->run->stream));
     return true;
 }
 
@@ -1502,44 +1410,44 @@ static bool batch_check_args(rwkv_mi_batch * B, const BatchCall & c, bool u_used
     return !c.until || batch_check_stops(B, c);
 }
 
-// the buffers the draw of a call needs
+// the form of the call's draw kernel -- decided here, once, from the slots the call names; everything after reads B->form -- and the buffers
+// the call needs: the stop tables; for a drawing call the row table with its pinned staging, on the first one, then the slots' own buffers
+// (B->draw; the plain sampler allocates none of the penalty tables)
 static bool batch_ensure_draw(rwkv_mi_batch * B, const BatchCall & c) {
+    B->form = B->draw.form(c.draw, c.slots, c.n);
     if (c.until && !batch_ensure_stop(B)) return false;
     if (c.draw == Draw::none) return true;
-    if (batch_names_guided(B, c.slots, c.n) && !B->d_grows) {   // the guide rows with their pinned staging: on the first guided call
-        const hipError_t e = grow(want(B->d_grows, B->n_slots), want(B->h_grows, B->n_slots));
-        RW_CTX_CHECK(B->ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the guide rows of %zu slots: %s", B->n_slots, hipGetErrorString(e));
+    const size_t n = B->n_slots;
+    const hipError_t e = grow(want(B->d_draw_rows, B->d_draw_rows ? 0 : n), want(B->h_draw_rows, B->h_draw_rows ? 0 : n));
+    RW_CTX_CHECK(B->ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the sampler's row tables for %zu slots: %s", n, hipGetErrorString(e));
+    return B->draw.ensure_sampler(B->ctx, B->run->stream) && (c.draw != Draw::penalized || B->draw.ensure_penalty(B->ctx, B->run->stream));
+}
+
+// the row table of the n named slots, one upload per call (after batch_upload*: the stream has been drained, the staging is free). loop: the
+// generator draws and every step records
+static bool batch_upload_draw_rows(rwkv_mi_batch * B, const BatchCall & c, bool loop) {
+    const bool pen = c.draw == Draw::penalized;
+    for (size_t i = 0; i < c.n; i++) {
+        DrawRow & r = B->h_draw_rows.p[i];
+        r = B->draw.row(c.slots[i], c.params[i], pen ? &c.penalties[i] : nullptr, loop ? 1u : pen ? c.penalties[i].record : 0u, B->guides);
+        if (loop) r.p.u = -1.0f;
     }
-    if (batch_names_cut(B, c.slots, c.n) && !B->d_crows) {   // the truncation rows with their pinned staging: on the first call that names a setting
-        const hipError_t e = grow(want(B->d_crows, B->n_slots), want(B->h_crows, B->n_slots));
-        RW_CTX_CHECK(B->ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the truncation rows of %zu slots: %s", B->n_slots, hipGetErrorString(e));
-    }
-    if (batch_names_rep(B, c) && !B->d_rrows) {   // the repetition rows with their pinned staging: on the first penalised call that names a setting
-        const hipError_t e = grow(want(B->d_rrows, B->n_slots), want(B->h_rrows, B->n_slots));
-        RW_CTX_CHECK(B->ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the repetition rows of %zu slots: %s", B->n_slots, hipGetErrorString(e));
-    }
-    return batch_ensure_draw_tables(B, c.draw == Draw::penalized);
+    BATCH_HIP_OK(B, hipMemcpyAsync(B->d_draw_rows.p, B->h_draw_rows.p, c.n * sizeof(DrawRow), hipMemcpyHostToDevice, B->run->stream));
+    return true;
 }
 
 // the rows or the segments of a call (that drains the stream first), then its stop words and its sampler table. loop: both row tables
 static bool batch_upload_call(rwkv_mi_batch * B, const BatchCall & c, size_t T, bool loop) {
     if (!(c.lens ? batch_upload_ragged(B, c, T) : batch_upload(B, c, loop ? 2 : 1))) return false;
     if (c.until && !batch_upload_stops(B, c)) return false;
-    if (c.draw == Draw::none) return true;
-    if (batch_names_guided(B, c.slots, c.n) && !batch_upload_guide_rows(B, c)) return false;
-    if (batch_names_cut(B, c.slots, c.n) && !batch_upload_cut_rows(B, c)) return false;
-    if (batch_names_rep(B, c) && !batch_upload_rep_rows(B, c)) return false;
-    return c.draw == Draw::penalized ? batch_upload_penalty_rows(B, c, loop) : batch_upload_params(B, c, loop);
+    return c.draw == Draw::none || batch_upload_draw_rows(B, c, loop);
 }
 
 // what follows the head of the call's passes (model.h, RowSampler): its draw, the call's whole history and, when it reports, report buffers;
 // a loop sets the step
-static RowSampler batch_sampler(rwkv_mi_batch * B, const BatchCall & c, uint32_t * hist, const RowReport * report) {
+static RowSampler batch_sampler(rwkv_mi_batch * B, uint32_t * hist, const RowReport * report) {
     RowSampler s;
-    s.draw = c.draw; s.srows = B->d_srows.p; s.prows = B->d_prows.p; s.probs = B->draw.probs.p;
-    if (c.draw != Draw::none && batch_names_guided(B, c.slots, c.n)) s.grows = B->d_grows.p;
-    if (c.draw != Draw::none && batch_names_cut(B, c.slots, c.n)) s.crows = B->d_crows.p;
-    if (batch_names_rep(B, c)) s.rrows = B->d_rrows.p;
+    s.form = B->form; s.rows = B->d_draw_rows.p; s.probs = B->draw.probs.p;
     s.hist = hist; s.report = report;
     return s;
 }
@@ -1571,7 +1479,7 @@ static bool batch_pass(rwkv_mi_batch * B, const BatchCall & c) {
     }
     // Row i's token lands in the batch's token word i (a ragged pass has read all T of them by then): the 4 n bytes that go back to the host.
     const RowReport rep = batch_report(B);
-    const RowSampler sampler = batch_sampler(B, c, nullptr, report ? &rep : nullptr);
+    const RowSampler sampler = batch_sampler(B, nullptr, report ? &rep : nullptr);
     // scoring is the ragged pass with the head on every token (engine.hip, ScorePass): T rows of log-probs / argmax in token order
     ScorePass sp;
     sp.targets = sp.logprobs = c.logprobs_out != nullptr;
@@ -1651,9 +1559,7 @@ static bool batch_draft(rwkv_mi_batch * B, const BatchCall & c, uint32_t * token
     d.stash.base = B->d_draft_stash.p; d.stash.n_in = draft_stash_inputs(m); d.stash.plane = (int64_t) T * m.n_embed();
     d.stash.layer0 = m.layer_begin; d.stash.per_layer = m.state_per_layer();
     d.lw = B->d_draft_layers.p; d.logits_all = B->d_draft_logits.p;
-    d.draw = c.draw; d.srows = B->d_srows.p; d.prows = B->d_prows.p; d.probs = B->draw.probs.p;
-    if (c.draw != Draw::none && batch_names_cut(B, c.slots, c.n)) d.crows = B->d_crows.p;
-    if (batch_names_rep(B, c)) d.rrows = B->d_rrows.p;
+    d.form = B->form; d.rows = B->d_draw_rows.p; d.probs = B->draw.probs.p;
     d.keep = B->d_draft_words.p; d.out = B->d_draft_words.p + B->n_slots; d.out_stride = W;
     if (!forward_draft(run, B->pass, (int64_t) T, d)) return batch_fail_drained(B);
     BATCH_HIP_OK(B, hipMemcpyAsync(B->h_draft_words.p, B->d_draft_words.p, c.n * sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream));
@@ -1690,10 +1596,10 @@ static bool batch_loop(rwkv_mi_batch * B, const BatchCall & c, size_t n_tokens, 
     const bool report = B->lp.enabled;   // (every step of a loop emits)
     if (!batch_ensure_report(B, n, n_tokens)) return false;
     if (!batch_upload_call(B, c, T, true)) return false;
-    if (c.draw == Draw::sample) launch_sample_seek_rows(B->d_srows.p, (int64_t) n, 0ull, run->stream);   // the named slots' streams start over
+    if (c.draw == Draw::sample) launch_sample_seek_rows(B->d_draw_rows.p, (int64_t) n, 0ull, run->stream);   // the named slots' streams start over
     BATCH_HIP_OK(B, hipEventRecord(run->ev0, run->stream));
     const RowReport rep = batch_report(B);
-    RowSampler sampler = batch_sampler(B, c, hist.p, report ? &rep : nullptr);
+    RowSampler sampler = batch_sampler(B, hist.p, report ? &rep : nullptr);
     for (size_t i = 0; i < n_tokens; i++) {
         // step i reads the buffers step i - 1 wrote: the two row tables alternate; the token of each row -- sampled inside the pass's chain
         // bracket, or its argmax after it -- lands where its next embedding lookup reads it
@@ -1749,11 +1655,11 @@ static bool batch_until(rwkv_mi_batch * B, const BatchCall & c, uint32_t * token
     const bool report = B->lp.enabled;   // (every step of a live row emits; a slot no row wrote is never read back: report_store fills behind lens)
     if (!batch_ensure_report(B, n, budget)) return false;
     if (!batch_upload_call(B, c, T, true)) return false;
-    if (c.draw == Draw::sample) launch_sample_seek_rows(B->d_srows.p, (int64_t) n, 0ull, run->stream);   // the named slots' streams start over
+    if (c.draw == Draw::sample) launch_sample_seek_rows(B->d_draw_rows.p, (int64_t) n, 0ull, run->stream);   // the named slots' streams start over
     BATCH_HIP_OK(B, hipMemsetAsync(hist.p, 0xFF, budget * n * sizeof(uint32_t), run->stream));
     BATCH_HIP_OK(B, hipEventRecord(run->ev0, run->stream));
     const RowReport rep = batch_report(B);
-    RowSampler sampler = batch_sampler(B, c, hist.p, report ? &rep : nullptr);
+    RowSampler sampler = batch_sampler(B, hist.p, report ? &rep : nullptr);
     RowStop stop{B->stop, nullptr, nullptr};
     sampler.stop = &stop;
     size_t passes = 0;

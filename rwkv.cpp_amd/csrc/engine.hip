@@ -861,27 +861,16 @@ void launch_row_sampler(rwkv_context * ctx, const RowSampler & s, int64_t rows) 
     const size_t at = (size_t) s.step * (size_t) rows;   // the step's slot of the call's history and report buffers
     uint32_t * hist = s.hist ? s.hist + at : nullptr;
     const uint32_t * live = s.stop ? s.stop->t.live : nullptr;   // (rwkv_mi_batch_decode_until: everything but the stop test runs behind the live words)
-    switch (s.draw) {
-        case Draw::penalized:
-            if (s.grows) launch_guided_pen_sample_rows(logits, rows, n_vocab, s.prows, s.grows, s.crows, s.rrows, s.probs, tokens, hist, live, ctx->stream);
-            else launch_pen_sample_rows(logits, rows, n_vocab, s.prows, s.crows, s.rrows, s.probs, tokens, hist, live, ctx->stream);
-            break;
-        case Draw::sample:
-            if (s.grows) launch_guided_sample_rows(logits, rows, n_vocab, s.srows, s.grows, s.crows, s.probs, tokens, hist, live, ctx->stream);
-            else launch_sample_rows(logits, rows, n_vocab, s.srows, s.crows, s.probs, tokens, hist, live, ctx->stream);
-            break;
-        case Draw::none:
-            if (live) launch_argmax_live(logits, rows, n_vocab, tokens, hist, live, ctx->stream);
-            else launch_argmax(logits, rows, n_vocab, tokens, hist, ctx->stream);
-            break;
-    }
+    if (s.form.draw != Draw::none) launch_draw_rows(logits, rows, n_vocab, s.rows, s.form, s.probs, tokens, hist, live, ctx->stream);
+    else if (live) launch_argmax_live(logits, rows, n_vocab, tokens, hist, live, ctx->stream);
+    else launch_argmax(logits, rows, n_vocab, tokens, hist, ctx->stream);
     if (const RowReport * rp = s.report)
         launch_logprob_rows(logits, rows, n_vocab, tokens, (int) rp->top_n, rp->chosen + at, rp->ids + at * rp->top_n, rp->vals + at * rp->top_n, live, ctx->stream);
     if (s.stop) launch_stop_rows(s.stop->t, rows, s.hist, s.step, s.stop->used, s.stop->other, ctx->stream);
 }
 
 // One pass of T rows, row t = one token (ctx->d_tokens.p[t]) of the sequence whose state is d_rows[t]. Logits: ctx->d_logits.p[T][n_vocab].
-// sample: the T sampler workgroups (sampling.hip, k_sample_rows) follow the head INSIDE the chain bracket. Each of them is 1024 threads,
+// sample: the T sampler workgroups (sampling.hip, k_draw_rows) follow the head INSIDE the chain bracket. Each of them is 1024 threads,
 // a CU's worth of waves, so up to T CUs are taken while they run; the completion event mega_chain_end records is what the device's next
 // persistent launch waits on, and with the sampler in front of it that launch still finds every CU free ("a batch pass never runs beside
 // a persistent kernel" holds for the sampler too). The greedy loop's argmax stays where it was, after the bracket: batch_loop (api.cpp) calls
@@ -942,8 +931,8 @@ bool forward_draft(rwkv_context * ctx, const SegPass & p, int64_t T, const Draft
     mega_chain_begin(ctx);
     r.run(true);
     if (!r.failed) {
-        launch_draft_accept_rows(d.logits_all, p.n, (int) m.n_vocab(), p.d_segs, ctx->d_tokens.p, d.draw, d.srows, d.prows, d.crows, d.rrows, d.probs, d.out, d.out_stride,
-                                 d.keep, ctx->d_logits.p, ctx->stream);
+        launch_draft_accept_rows(d.logits_all, p.n, (int) m.n_vocab(), p.d_segs, ctx->d_tokens.p, d.rows, d.form, d.probs, d.out, d.out_stride, d.keep, ctx->d_logits.p,
+                                 ctx->stream);
         launch_draft_replay(d.stash, d.lw, m.arch_major, m.arch_minor, p.d_segs, p.n, d.keep, (int64_t) (m.layer_end - m.layer_begin), m.n_embed(), m.head_count, m.head_size,
                             ctx->stream);
     }

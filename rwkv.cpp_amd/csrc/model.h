@@ -107,54 +107,70 @@ bool launch_wkv6_seq(const float * r, const float * k, const float * v, const fl
                      const float * state_in, float * state_out, float * out, int64_t T, int64_t H, hipStream_t st);
 constexpr int64_t k_mfma_min_tokens = 32;   // sequence calls of at least this many tokens per pass take the GEMM path
 
-// temperature / top-p sampling on the logits in HBM (sampling.hip). u < 0: draw from the counter-based generator (seed, *counter; the
-// counter is advanced on the device). The token is written to out_token (and to hist[hist_pos] when hist is given).
-// cut: the sequence's truncation setting (CutRow below; {0, 0}: none -- the draw is the one described above).
-struct CutRow;
-void launch_sample(const float * logits, int n, float temperature, float top_p, float u, unsigned long long seed, unsigned long long * counter,
-                   const CutRow & cut, float * probs, uint32_t * out_token, uint32_t * hist, int hist_pos, hipStream_t st);
+// ---- the device sampler (sampling.hip): temperature / top-k / top-p / min-p draws on logits in HBM ----
+// Everything the draw of one row can read, in one struct: a context's draw builds one on the host, a batch call uploads one table of them.
+//   p, counter   the sampler's parameters and the draw counter of the row's sequence. p.u < 0: the draw comes from the counter-based generator
+//                (p.seed, *counter), and thread 0 advances the counter on the device
+//   presence, frequency, record, count, bias   the penalised draw (rwkv_mi_*_penalized) reads, instead of the logit,
+//                adj[j] = (logits[j] - (presence + (float) count[j] * frequency)) + bias[j]   (the penalty where count[j] > 0 only; bias == NULL:
+//                no bias) and, when record is set, counts the token: count[token] += 1. count: the sequence's occurrence table ([n] words),
+//                bias: its bias table ([n] floats)
+//   next, state, misses   the guide of the row's slot (rwkv_mi_batch_guide_*): its dense table next[n_states][n], GUIDE_DEAD where the transition
+//                is dead -- NULL: the row has no guide and draws as the unguided kernel does -- and the slot's state and miss words. A guided
+//                row in state s reads -inf for token j where next[s][j] is dead, the value of its draw elsewhere; thread 0 then moves the state
+//                to next[s][token], or counts a miss when that is dead
+//   top_k, min_p   the truncation setting of the row's sequence (rwkv_mi_*truncation_set; {0, 0}: none). top_k (0 or >= n: off): of the values
+//                the draw would read -- logits, adjusted logits, a guide's mask applied -- the first top_k in the order (value descending, index
+//                ascending; a NaN never ranks) are read as they are, every other one as -inf. min_p (0: off): of the probabilities the body
+//                computes from these, those below (float) (min_p * the largest) are cut, beside the top-p cut-off. A row with temperature 0
+//                is an argmax, which survives both: it ignores the setting
+//   decay, repetition   the repetition setting of the row's sequence (rwkv_mi_*repetition_set; {1, 1}: none), read by the penalised draw.
+//                repetition: where the token has occurred, the logit is divided by it when positive and multiplied by it otherwise, in front
+//                of the penalty. decay != 1: the sequence is DECAYING -- the words of `count` hold floats, and a draw that records multiplies
+//                every one of them by decay before it adds 1.0f to the pick's. The arithmetic is spelled out in include/rwkv_mi355x.h
+constexpr uint16_t GUIDE_DEAD = 0xFFFF;
+struct DrawRow {
+    rwkv_mi_sample_params p; unsigned long long * counter;
+    float presence; float frequency; uint32_t record;
+    uint32_t * count; const float * bias;
+    const uint16_t * next; uint32_t * state; uint32_t * misses;
+    uint32_t top_k; float min_p;
+    float decay; float repetition;
+};
+// the two settings as a sequence keeps them (DrawState's host words)
+struct CutRow { uint32_t top_k; float min_p; };
+struct RepRow { float decay; float repetition; };
+// What the kernel of a call is specialised on, decided ONCE per call from the sequences it names (DrawState::form): which choice is made --
+// the greedy argmax (none: no draw kernel runs), the sampler or the penalised sampler -- and which of the row's optional fields its kernel
+// reads. A call that uses none of a feature launches the kernel of before that feature:
+//   guided   a named sequence has a guide;   rep   the call is penalised and a named sequence has a repetition setting;
+//   cut      a named sequence has a truncation setting -- or guided, or rep: those kernels exist in the truncating form only.
+enum class Draw { none, sample, penalized };
+enum : int { SRC_PLAIN = 0, SRC_PEN = 1, SRC_REP = 2 };   // what a draw kernel reads (sampling.hip): logits, penalised, penalised with repetition
+struct DrawForm {
+    Draw draw = Draw::none; bool cut = false, guided = false, rep = false;
+    static DrawForm of(Draw draw, bool has_cut, bool has_guide, bool has_rep) {
+        DrawForm f;
+        f.draw = draw; f.guided = draw != Draw::none && has_guide; f.rep = draw == Draw::penalized && has_rep; f.cut = draw != Draw::none && (has_cut || f.guided || f.rep);
+        return f;
+    }
+    // the form of a context's draw of `row`: its truncating kernel runs whenever a word of the setting is set (top_k >= n too, which truncates nothing)
+    static DrawForm of_row(Draw draw, const DrawRow & row) {
+        return of(draw, row.top_k != 0u || row.min_p != 0.0f, false, row.decay != 1.0f || row.repetition != 1.0f);
+    }
+};
 // probs: scratch of sample_scratch_floats(n) floats (the vocabulary rounded up to whole chunks of the 1024 threads: the kernel keeps it transposed).
 inline size_t sample_scratch_floats(int64_t n) { return (size_t) ((n + 1023) / 1024) * 1024; }
-// The row form (batched decode): one workgroup per row of logits[rows][n], row r with table[r]'s parameters and draw counter (the counter
-// of the row's SLOT). probs: [rows][sample_scratch_floats(n)] scratch. Row r's token goes to tokens[r] (the word its next embedding lookup
-// reads) and, when hist is given, to hist[r].
-struct SampleRow { rwkv_mi_sample_params p; unsigned long long * counter; };
-// The truncation setting of a row's sequence (rwkv_mi_*truncation_set), a table parallel to the row table as the guide rows are; a NULL table:
-// no row has one. top_k (0 or >= n: off): of the values the draw would read -- logits, adjusted logits, a guide's mask applied -- the first
-// top_k in the order (value descending, index ascending; a NaN never ranks) are read as they are, every other one as -inf. min_p (0: off):
-// of the probabilities the body computes from these, those below (float) (min_p * the largest) are cut, beside the top-p cut-off. A row
-// with temperature 0 is an argmax, which survives both: it ignores the setting.
-struct CutRow { uint32_t top_k; float min_p; };
-// live (here and in the penalised form; NULL: every row draws): rwkv_mi_batch_decode_until's per-row live words -- a row with live[r] == 0 returns
-// before it reads a logit: no draw, no counter advance, no count, no token or history word.
-void launch_sample_rows(const float * logits, int64_t rows, int n, const SampleRow * table, const CutRow * cuts, float * probs, uint32_t * tokens,
-                        uint32_t * hist, const uint32_t * live, hipStream_t st);
-void launch_sample_seek_rows(const SampleRow * table, int64_t rows, unsigned long long value, hipStream_t st);   // *table[r].counter = value
-// The penalised forms (rwkv_mi_*_penalized): the same draw on adj[j] = (logits[j] - (presence + (float) count[j] * frequency)) + bias[j]
-// (the penalty where count[j] > 0 only; bias == NULL: no bias), then count[token] += 1 when record is set. count: the sequence's occurrence table ([n] words), bias: its bias
-// table ([n] floats). The row table carries them per row, beside the sampler's parameters and the draw counter of the row's slot.
-struct PenaltyRow { rwkv_mi_sample_params p; unsigned long long * counter; float presence; float frequency; uint32_t record; uint32_t * count; const float * bias; };
-// The repetition setting of a row's sequence (rwkv_mi_*repetition_set), a table parallel to the row table as the truncation rows are; a NULL
-// table: no row of the call has one, and the kernels of before run. repetition (1: off): where the token has occurred, the logit is divided
-// by it when positive and multiplied by it otherwise, in front of the penalty. decay (1: off): the sequence is DECAYING -- the words of its
-// occurrence row (PenaltyRow::count) hold floats, and a draw that records multiplies every one of them by decay before it adds 1.0f to the
-// pick's. The arithmetic is spelled out in include/rwkv_mi355x.h. A row with {1, 1} in a table reads uint32 counts and draws as it always did.
-struct RepRow { float decay; float repetition; };
-void launch_pen_sample(const float * logits, int n, float temperature, float top_p, float u, unsigned long long seed, unsigned long long * counter,
-                       float presence, float frequency, uint32_t record, uint32_t * count, const float * bias, const CutRow & cut, const RepRow & rep,
-                       float * probs, uint32_t * out_token, uint32_t * hist, int hist_pos, hipStream_t st);
-void launch_pen_sample_rows(const float * logits, int64_t rows, int n, const PenaltyRow * table, const CutRow * cuts, const RepRow * reps, float * probs,
-                            uint32_t * tokens, uint32_t * hist, const uint32_t * live, hipStream_t st);
-// The guided forms (rwkv_mi_batch_guide_*): a parallel table gives row r the dense table of its guide -- next[n_states][n], GUIDE_DEAD where
-// the transition is dead; NULL: the row has no guide and draws as the unguided kernel does -- and its slot's state and miss words. A guided
-// row in state s reads -inf for token j where next[s][j] is dead, the value of its draw elsewhere; thread 0 then moves the state to
-// next[s][token], or counts a miss when that is dead.
-constexpr uint16_t GUIDE_DEAD = 0xFFFF;
-struct GuideRow { const uint16_t * next; uint32_t * state; uint32_t * misses; };
-void launch_guided_sample_rows(const float * logits, int64_t rows, int n, const SampleRow * table, const GuideRow * guides, const CutRow * cuts, float * probs,
-                               uint32_t * tokens, uint32_t * hist, const uint32_t * live, hipStream_t st);
-void launch_guided_pen_sample_rows(const float * logits, int64_t rows, int n, const PenaltyRow * table, const GuideRow * guides, const CutRow * cuts,
-                                   const RepRow * reps, float * probs, uint32_t * tokens, uint32_t * hist, const uint32_t * live, hipStream_t st);
+// One draw of a context: one workgroup on logits[n] with `row`. The token is written to out_token (and to hist[hist_pos] when hist is given).
+void launch_draw(const float * logits, int n, const DrawRow & row, const DrawForm & form, float * probs, uint32_t * out_token, uint32_t * hist, int hist_pos,
+                 hipStream_t st);
+// The row form (batched decode): one workgroup per row of logits[rows][n], row r with table[r]. probs: [rows][sample_scratch_floats(n)] scratch.
+// Row r's token goes to tokens[r] (the word its next embedding lookup reads) and, when hist is given, to hist[r].
+// live (NULL: every row draws): rwkv_mi_batch_decode_until's per-row live words -- a row with live[r] == 0 returns before it reads anything: no
+// draw, no counter advance, no count, no guide step, no token or history word.
+void launch_draw_rows(const float * logits, int64_t rows, int n, const DrawRow * table, const DrawForm & form, float * probs, uint32_t * tokens, uint32_t * hist,
+                      const uint32_t * live, hipStream_t st);
+void launch_sample_seek_rows(const DrawRow * table, int64_t rows, unsigned long long value, hipStream_t st);   // *table[r].counter = value
 // next[n_states][n_vocab] from the edges in CSR form on the device (checked by the caller: tokens < n_vocab and distinct per state, next < n_states)
 void launch_guide_expand(uint16_t * next, uint32_t n_states, int n_vocab, const uint32_t * edge_begin, const uint32_t * edge_tokens, const uint32_t * edge_next,
                          hipStream_t st);
@@ -233,6 +249,22 @@ struct DrawState {
     bool has_cut(size_t slot) const { return (cuts[slot].top_k != 0u && cuts[slot].top_k < n_vocab) || cuts[slot].min_p != 0.0f; }
     bool decaying(size_t slot) const { return reps[slot].decay != 1.0f; }
     bool has_rep(size_t slot) const { return decaying(slot) || reps[slot].repetition != 1.0f; }
+    // The row of a draw of `slot` -- the one place that knows where a sequence's counter, tables, guide words and settings live. pen (NULL: the
+    // plain draw, which reads neither table) with `record` in place of its own; guides (NULL: a context, which has none): the batch's tables,
+    // indexed by guide_of
+    DrawRow row(size_t slot, const rwkv_mi_sample_params & p, const rwkv_mi_penalty_params * pen, uint32_t record, const DevBuf<uint16_t> * guides = nullptr) const {
+        const uint32_t g = guide_of[slot];
+        const bool guided = guides && g != RWKV_MI_NO_GUIDE;
+        return DrawRow{p, counter(slot), pen ? pen->presence : 0.0f, pen ? pen->frequency : 0.0f, pen ? record : 0u, pen ? counts_of(slot) : nullptr,
+                       pen ? bias_of(slot) : nullptr, guided ? guides[g].p : nullptr, guided ? guide_state.p + slot : nullptr,
+                       guided ? guide_misses.p + slot : nullptr, cuts[slot].top_k, cuts[slot].min_p, reps[slot].decay, reps[slot].repetition};
+    }
+    // the form of a call that draws for the n named slots
+    DrawForm form(Draw draw, const uint32_t * named, size_t n) const {
+        bool cut = false, guided = false, rep = false;
+        for (size_t i = 0; i < n; i++) { cut |= has_cut(named[i]); guided |= guide_of[named[i]] != RWKV_MI_NO_GUIDE; rep |= has_rep(named[i]); }
+        return DrawForm::of(draw, cut, guided, rep);
+    }
 
     bool ensure_counters(rwkv_context * ctx, hipStream_t st);
     bool ensure_sampler(rwkv_context * ctx, hipStream_t st);   // the counters and the scratch
@@ -391,28 +423,20 @@ bool ensure_score(rwkv_context * ctx, int64_t rows);
 rwkv_context * batch_context_create(Model * m, int64_t max_rows);
 void batch_context_destroy(rwkv_context * c);
 // What follows the head of a batch pass over `rows` rows (launch_row_sampler), described once: row r's token goes to ctx->d_tokens.p[r].
-//   draw    which choice is made: the greedy argmax (none), the sampler (sample: srows, launch_sample_rows) or the penalised sampler
-//           (penalized: prows, launch_pen_sample_rows); probs: the samplers' scratch; grows (NULL: no named slot has a guide): the guide rows,
-//           with which the guided form of either sampler is launched instead; crows (NULL: no named slot has a truncation setting): the
-//           settings of the rows, which every form of the sampler takes; rrows (NULL: the call is not penalised, or no named slot has a
-//           repetition setting): the rows' repetition settings, with which the k_rep_* form of the penalised sampler is launched
+//   form, rows, probs   which choice is made -- the greedy argmax (Draw::none) or launch_draw_rows in the call's form -- on the call's row table
+//           (one DrawRow per row of the pass) with the samplers' scratch
 //   hist, report, step   the call's WHOLE history [steps][rows] and report buffers (chosen [steps][rows], ids / vals [steps][rows][top_n]), either
 //           may be NULL, and the step of the call this pass is: the step's slot of each is written. A single pass is step 0
 //   stop    the pass is a step of rwkv_mi_batch_decode_until: the choice and the report run behind the live words and launch_stop_rows follows them
 //   beam    the pass is a step of rwkv_mi_batch_decode_beam: instead of a choice, launch_beam_rows and launch_beam_select follow the head;
 //           of the rest only `step` is read
 // Order within a step: the choice, then the report of what it wrote, then the stop test.
-enum class Draw { none, sample, penalized };
 struct RowStop { StopTables t; RowState * used, * other; };
 struct RowReport { float * chosen; uint32_t * ids; float * vals; uint32_t top_n; };
 struct RowBeam { BeamTables t; const RowState * used; RowState * other; };
 struct RowSampler {
-    Draw draw = Draw::none;
-    const SampleRow * srows = nullptr;
-    const PenaltyRow * prows = nullptr;
-    const GuideRow * grows = nullptr;   // the call names a guided slot: the guided form of the sampler runs on this parallel table
-    const CutRow * crows = nullptr;     // the call names a slot with a truncation setting: the rows' settings, parallel to the row table
-    const RepRow * rrows = nullptr;     // the penalised call names a slot with a repetition setting: the rows' settings, parallel to the row table
+    DrawForm form;
+    const DrawRow * rows = nullptr;
     float * probs = nullptr;
     uint32_t * hist = nullptr;
     const RowReport * report = nullptr;
@@ -440,8 +464,8 @@ bool forward_segs(rwkv_context * ctx, const SegPass & p, int64_t T, bool want_lo
 // (all of them on the _segs recurrences), with three additions that run in this call only:
 //   the stash    every layer copies the inputs of its recurrences into `stash` (kernels.h, DraftStash) while the pass runs;
 //   the head     on ALL T tokens into logits_all[T][n_vocab], addressable together: a row's positions are read in sequence;
-//   the choice   k_draft_accept_rows (sampling.hip) walks each row's positions with the draw of the call's family -- draw / srows / prows /
-//                probs as in RowSampler -- and leaves out[n][out_stride] (the emitted tokens, RWKV_MI_NO_TOKEN behind them), keep[n] (their
+//   the choice   k_draft_accept_rows (sampling.hip) walks each row's positions with the draw of the call's family -- form / rows / probs as
+//                in RowSampler -- and leaves out[n][out_stride] (the emitted tokens, RWKV_MI_NO_TOKEN behind them), keep[n] (their
 //                number) and, in ctx->d_logits row r, the logits the row's last emitted token was chosen from;
 //   the replay   launch_draft_replay re-runs the recurrences of every row whose draft did not stand in full over its first keep tokens.
 // keep never leaves the device in between. lw: the layers' vectors on the device (kernels.h, DraftLayer).
@@ -449,19 +473,15 @@ struct DraftPass {
     DraftStash stash;
     const DraftLayer * lw = nullptr;
     float * logits_all = nullptr;
-    Draw draw = Draw::none;
-    const SampleRow * srows = nullptr;
-    const PenaltyRow * prows = nullptr;
-    const CutRow * crows = nullptr;     // the rows' truncation settings as in RowSampler (NULL: none), read at every position walked
-    const RepRow * rrows = nullptr;     // the rows' repetition settings as in RowSampler (NULL: none; the penalised family only)
+    DrawForm form;                      // as in RowSampler; a row's settings are read at every position walked
+    const DrawRow * rows = nullptr;
     float * probs = nullptr;
     uint32_t * out = nullptr;
     int out_stride = 0;
     uint32_t * keep = nullptr;
 };
-void launch_draft_accept_rows(const float * logits, int64_t rows, int n, const SegState * segs, const uint32_t * tokens, Draw draw, const SampleRow * srows,
-                              const PenaltyRow * prows, const CutRow * cuts, const RepRow * reps, float * probs, uint32_t * out, int out_stride, uint32_t * keep,
-                              float * logits_row, hipStream_t st);
+void launch_draft_accept_rows(const float * logits, int64_t rows, int n, const SegState * segs, const uint32_t * tokens, const DrawRow * table, const DrawForm & form,
+                              float * probs, uint32_t * out, int out_stride, uint32_t * keep, float * logits_row, hipStream_t st);
 // inputs of a layer's WKV body a pass stashes (DraftStash::n_in): 3, 3, 4, 6 for RWKV-4, 5, 6, 7
 inline int draft_stash_inputs(const Model & m) { return m.arch_major == 7 ? 6 : (m.arch_major == 6 ? 4 : 3); }
 bool forward_draft(rwkv_context * ctx, const SegPass & p, int64_t T, const DraftPass & d);

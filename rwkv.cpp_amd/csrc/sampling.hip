@@ -8,26 +8,30 @@
 // The cut-off is found without sorting: the largest threshold t (bisection over the float bit pattern, 31 reductions) with
 // sum{p >= t} > top_p is exactly that probability. Sums are f32 in a fixed order (per-thread contiguous chunks, then a tree): runs
 // are reproducible; against numpy's sequential cumsum the result can differ only when u or top_p falls within rounding of a boundary.
-// Batched decode samples every row of a pass in one launch of k_sample_rows: one workgroup per row, per-row parameters and the draw
-// counter of the row's slot from a device table (rwkv_mi_batch_eval_sample / _decode_sample).
-// Penalised draws (k_pen_sample / k_pen_sample_rows, rwkv_mi_*_penalized): the same body reads, instead of the logit l[j],
-//   adj[j] = (l[j] - (presence + (float) count[j] * frequency)) + bias[j]      where count[j] > 0;      l[j] + bias[j] elsewhere
-// (the reference's chat program, chat_with_bot.py:246-247 -- its loop runs over the tokens that have occurred -- then sample_logits'
-// logit_bias, sampling.py:27-36; every operation rounded to f32 in that order) from the sequence's occurrence table count[n] and its
-// optional bias table, and counts the chosen token afterwards.
-// rwkv_mi_batch_decode_until: the two row samplers take a per-row live word (live; NULL everywhere else), and k_stop_rows retires a
-// row -- stop sequence or budget -- by rewriting its entries of the two row tables on the device.
-// Guided draws (k_guided_sample_rows / k_guided_pen_sample_rows, rwkv_mi_batch_guide_*): a row whose slot has a guide attached, in state s,
-// reads -inf instead of the value above wherever the guide's next(s, j) is dead, and moves its state to next(s, token) afterwards.
-// Truncation settings (rwkv_mi_*truncation_set; the k_cut_* forms of the four entry points above, the guided forms and the draft walk take the
-// row's CutRow {top_k, min_p}, by value or from a table parallel to the row table; a call that names no setting launches what it launched before): mask -> softmax -> top-p and min-p, intersected -> temperature. A row with top-k on runs
-// select_stage in front of the body -- of the values above, all but the first top_k in the order (value descending, index ascending) read
-// -inf -- and the body on the stash; min-p is one more threshold of the body, p >= (float) (min_p * p_max), combined with the top-p
-// cut-off as the larger bit pattern. {0, 0}: the draw above, statement for statement.
-// Repetition settings (rwkv_mi_*repetition_set; RepetitionLogits and the k_rep_* entry points): a penalised draw of a sequence with the setting
-// {decay, repetition} divides or multiplies the logit of an occurred token by `repetition` in front of the penalty, and a sequence with decay != 1
-// keeps its occurrence row as floats that every recorded draw multiplies by decay before it counts the pick. {1, 1}: the penalised draw above.
-// The logits themselves are never written.
+// Every draw is ONE body, draw_row, on ONE description of a row, DrawRow (model.h): the sampler's parameters, the draw counter of the row's
+// sequence, its penalty and tables, its guide, its truncation and repetition settings. The body has three compile-time axes, and an entry
+// point is an instantiation of them -- a call launches the one its DrawForm (model.h) names, so a call that uses none of a feature runs the
+// code of before that feature, registers and all (tests/test_cpu_batch_until.py pins the four unset forms; DESIGN.md 6.15 has the table):
+//   SRC     what the draw reads instead of the logit l[j]. PLAIN: l[j]. PEN (rwkv_mi_*_penalized):
+//             adj[j] = (l[j] - (presence + (float) count[j] * frequency)) + bias[j]      where count[j] > 0;      l[j] + bias[j] elsewhere
+//           (the reference's chat program, chat_with_bot.py:246-247 -- its loop runs over the tokens that have occurred -- then sample_logits'
+//           logit_bias, sampling.py:27-36; every operation rounded to f32 in that order) from the sequence's occurrence table count[n] and its
+//           optional bias table; a draw that records counts the chosen token afterwards. REP (rwkv_mi_*repetition_set; RepetitionLogits): the
+//           penalised draw of a call that names a sequence with a setting {decay, repetition} -- the logit of an occurred token is divided or
+//           multiplied by `repetition` in front of the penalty, and a sequence with decay != 1 keeps its occurrence row as floats that every
+//           recorded draw multiplies by decay before it counts the pick. A row with {1, 1} draws as PEN does.
+//   CUT     the row's truncation setting {top_k, min_p} is read (rwkv_mi_*truncation_set; cut_sample): mask -> softmax -> top-p and min-p,
+//           intersected -> temperature. A row with top-k on runs select_stage in front of the body -- of the values above, all but the first
+//           top_k in the order (value descending, index ascending) read -inf -- and the body on the stash; min-p is one more threshold of the
+//           body, p >= (float) (min_p * p_max), combined with the top-p cut-off as the larger bit pattern. A row with {0, 0} draws as the form
+//           without CUT does, statement for statement. The REP and GUIDED forms exist with CUT only.
+//   GUIDED  (the row form only; rwkv_mi_batch_guide_*) a row whose slot has a guide attached, in state s, reads -inf instead of the value
+//           above wherever the guide's next(s, j) is dead, and moves its state to next(s, token) afterwards; a row without one draws as the
+//           unguided form does.
+// The entry points: k_draw<SRC, CUT>, one workgroup on a context's logits; k_draw_rows<SRC, CUT, GUIDED>, one workgroup per row of a batch
+// pass (rwkv_mi_batch_eval_sample / _decode_sample and their kin), behind the row's live word in rwkv_mi_batch_decode_until, whose k_stop_rows
+// retires a row -- stop sequence or budget -- by rewriting its entries of the two row tables on the device; k_draft_accept_rows<FAMILY>, the
+// walk of rwkv_mi_batch_eval_draft, which draws once per position. The logits themselves are never written.
 #include "kdev.h"
 #include "model.h"
 
@@ -90,7 +94,7 @@ struct PenalisedLogits {
     __device__ __forceinline__ float again(int j, const ProbVec & pr) const { return pr.get(j); }
 };
 
-// The penalised source of a sequence with a repetition setting (rwkv_mi_*repetition_set; model.h, RepRow): the row's occurrence word o[j] is a
+// The penalised source of a sequence with a repetition setting (rwkv_mi_*repetition_set; model.h, DrawRow): the row's occurrence word o[j] is a
 // float where the sequence is decaying (is_float), else (float) count[j], and the value is, every operation rounded to f32 in this order,
 //   a = l[j];   o[j] > 0:  a = a > 0 ? a / repetition : a * repetition;  a = a - (presence + o[j] * frequency);      bias:  a = a + bias[j]
 // ({1, 1}: the penalised source's adj[j], statement for statement). It stashes like the penalised source, so the guided source and the select
@@ -133,8 +137,8 @@ __device__ __forceinline__ void rep_record(uint32_t * occ, int n, const RepRow &
     if (threadIdx.x == 0) occ[pick] = __float_as_uint(__uint_as_float(occ[pick]) + 1.0f);
 }
 
-// The guided source (k_guided_sample_rows / k_guided_pen_sample_rows): the value the row's draw would read anyway -- Inner is PlainLogits or
-// PenalisedLogits -- with the mask applied LAST: -inf where the guide's transition from the row's state is dead. nx: the thread's chunk of
+// The guided source (the GUIDED forms of k_draw_rows): the value the row's draw would read anyway -- Inner is any of the three sources
+// above -- with the mask applied LAST: -inf where the guide's transition from the row's state is dead. nx: the thread's chunk of
 // the state's row of the dense table, contiguous like its chunk of the count table; NULL: the row has no guide and reads what Inner reads.
 // first() stashes the value as the penalised source does, so again() neither reads the table a second time nor derives the value again.
 template <class Inner>
@@ -234,14 +238,14 @@ __device__ __forceinline__ void select_stage(const Src & src, int cnt, uint32_t 
 // What thread 0 does to a guided row's words after the draw (where the penalised rows count the token): the state moves along the picked
 // token's transition; a dead pick -- all-NaN logits, or a caller's -inf bias on every allowed token -- leaves it and counts a miss. The
 // state word is only ever written from the table (or by rwkv_mi_batch_guide_attach, which checks it), so it always indexes inside it.
-__device__ __forceinline__ void guide_advance(const GuideRow & g, const uint16_t * state_row, int pick) {
+__device__ __forceinline__ void guide_advance(const DrawRow & g, const uint16_t * state_row, int pick) {
     const uint16_t to = state_row[pick];
     if (to != GUIDE_DEAD) *g.state = to; else *g.misses += 1u;
 }
 
-// One body, two entry points (the convention of the recurrence kernels and their row forms): k_sample hands it its arguments,
-// k_sample_rows the pointers and parameters of row blockIdx.x. Everything the workgroup does -- chunks, summation order, bisection, scan,
-// draw -- is this function, so a row of the batch picks bit for bit the token the single-context sampler picks from the same logits.
+// The sampler proper, shared by every entry point (the convention of the recurrence kernels and their row forms): k_draw hands it a context's
+// row, k_draw_rows the row of blockIdx.x. Everything the workgroup does -- chunks, summation order, bisection, scan, draw -- is this
+// function, so a row of the batch picks bit for bit the token the single-context sampler picks from the same logits.
 // The scratch vector is laid out for the passes, not for the reader: token i0 + j of thread tid lives at probs[j * 1024 + tid], so the 64 lanes
 // of a load touch two cache lines instead of 64 (a thread's chunk is contiguous in the logits; ~35 passes run over the probabilities).
 // make_src(i0): the logit source of the thread whose chunk starts at token i0 (PlainLogits or PenalisedLogits).
@@ -375,7 +379,7 @@ __device__ __forceinline__ int sample_body(MakeSrc && make_src, int n, float tem
     return pick;
 }
 
-// The draw of a sequence with the truncation setting `cut` (model.h, CutRow): a row with top-k on runs the select stage on its source and
+// The draw of a sequence with the truncation setting `cut` (model.h, DrawRow): a row with top-k on runs the select stage on its source and
 // then the body on the stash; every other row runs the body on its source, exactly as before there were settings -- {0, 0} is that draw,
 // statement for statement. min-p is the body's. A row with temperature 0 is an argmax, which both truncations keep: it skips the stage
 // (and never reaches the body's min-p). The setting is the row's, so the whole workgroup takes one branch.
@@ -392,178 +396,64 @@ __device__ __forceinline__ int cut_sample(MakeSrc && make_src, const CutRow & cu
     return sample_body([](int) { return StashedLogits{}; }, n, temperature, top_p, cut.min_p, u_in, seed, counter, probs, out_token, hist_word);
 }
 
-__global__ __launch_bounds__(1024) void k_sample(const float * __restrict__ logits, int n, float temperature, float top_p, float u_in,
-                                                 unsigned long long seed, unsigned long long * counter,
-                                                 float * __restrict__ probs, uint32_t * __restrict__ out_token, uint32_t * __restrict__ hist, int hist_pos) {
-    sample_body([=](int i0) { return PlainLogits{logits + i0}; }, n, temperature, top_p, 0.0f, u_in, seed, counter, probs, out_token, hist ? hist + hist_pos : nullptr);
+// The draw of one row by its workgroup, the pick returned to every thread: the source of SRC on the row's tables -- behind the guide's mask
+// when GUIDED: the row reads its slot's state word s, every thread, before the body's first barrier, and draws through GuidedLogits on row s
+// of the guide's table (next == NULL: no guide, and the pick of the unguided form, bit for bit) -- then cut_sample with the row's setting
+// when CUT, else the body itself with no min-p; then what follows a draw: with `record` the pick is counted (thread 0, argmax or not: the
+// draw of step i has seen the counts of the steps before it; rep_record for SRC_REP), and thread 0 moves the guide, after the last barrier.
+// Only the fields the instantiation names are read: a form without a feature compiles to the code it was before the row had the field.
+template <int SRC, bool CUT, bool GUIDED>
+__device__ __forceinline__ int draw_row(const float * lg, int n, const DrawRow & row, uint32_t record, float * __restrict__ probs,
+                                        uint32_t * __restrict__ out_token, uint32_t * __restrict__ hist_word) {
+    static_assert(CUT || (SRC != SRC_REP && !GUIDED), "the repetition and guided forms go through cut_sample");
+    const uint16_t * srow = nullptr;
+    if constexpr (GUIDED) srow = row.next ? row.next + (size_t) *row.state * (size_t) n : nullptr;
+    const auto inner = [&] {
+        if constexpr (SRC == SRC_PLAIN) return [=](int i0) { return PlainLogits{lg + i0}; };
+        else if constexpr (SRC == SRC_PEN) {
+            uint32_t * count = row.count; const float * bias = row.bias; const float presence = row.presence, frequency = row.frequency;
+            return [=](int i0) { return PenalisedLogits{lg + i0, count + i0, bias ? bias + i0 : nullptr, presence, frequency}; };
+        } else return rep_source(lg, row.count, row.bias, row.presence, row.frequency, RepRow{row.decay, row.repetition});
+    }();
+    const auto make_src = [=](int i0) {
+        if constexpr (GUIDED) return GuidedLogits<decltype(inner(0))>{inner(i0), srow ? srow + i0 : nullptr};
+        else return inner(i0);
+    };
+    const rwkv_mi_sample_params & p = row.p;
+    int pick;
+    if constexpr (CUT) pick = cut_sample(make_src, CutRow{row.top_k, row.min_p}, n, p.temperature, p.top_p, p.u, p.seed, row.counter, probs, out_token, hist_word);
+    else pick = sample_body(make_src, n, p.temperature, p.top_p, 0.0f, p.u, p.seed, row.counter, probs, out_token, hist_word);
+    if constexpr (SRC == SRC_PEN) { if (threadIdx.x == 0 && record) row.count[pick] += 1u; }
+    if constexpr (SRC == SRC_REP) rep_record(row.count, n, RepRow{row.decay, row.repetition}, record, pick);
+    if constexpr (GUIDED) { if (threadIdx.x == 0 && srow) guide_advance(row, srow, pick); }
+    return pick;
 }
 
-// The truncating forms of the four draw entry points (k_cut_*): the entry point above or below with the sequence's setting -- by value for a
-// context, whose setting is host words; from a table parallel to the row table for the row forms. They are entry points of their own, not an
-// argument of the old ones: a call that names no setting launches the kernel it launched before there were settings, registers and all
-// (tests/test_cpu_batch_until.py pins the four's register counts). The guided forms and the draft walk, younger and unpinned, take the
-// table as an argument that may be NULL.
-__global__ __launch_bounds__(1024) void k_cut_sample(const float * __restrict__ logits, int n, float temperature, float top_p, float u_in,
-                                                     unsigned long long seed, unsigned long long * counter, CutRow cut,
-                                                     float * __restrict__ probs, uint32_t * __restrict__ out_token, uint32_t * __restrict__ hist, int hist_pos) {
-    cut_sample([=](int i0) { return PlainLogits{logits + i0}; }, cut, n, temperature, top_p, u_in, seed, counter, probs, out_token, hist ? hist + hist_pos : nullptr);
+// The single-context entry: the row of a context is host words, so it arrives as SCALAR kernel arguments and is assembled here (a DrawRow by
+// value costs the two unset forms 4 SGPRs over their pinned counts; an argument an instantiation does not read costs it nothing).
+template <int SRC, bool CUT>
+__global__ __launch_bounds__(1024) void k_draw(const float * __restrict__ logits, int n, float temperature, float top_p, float u_in, unsigned long long seed,
+                                               unsigned long long * counter, float presence, float frequency, uint32_t record, uint32_t * count,
+                                               const float * __restrict__ bias, CutRow cut, RepRow rep, float * __restrict__ probs,
+                                               uint32_t * __restrict__ out_token, uint32_t * __restrict__ hist, int hist_pos) {
+    const DrawRow row{{temperature, top_p, u_in, seed}, counter, presence, frequency, record, count, bias, nullptr, nullptr, nullptr, cut.top_k, cut.min_p,
+                      rep.decay, rep.repetition};
+    draw_row<SRC, CUT, false>(logits, n, row, record, probs, out_token, hist ? hist + hist_pos : nullptr);
 }
 
-// Row form: grid = rows, one workgroup per row; row r's probabilities in its own stretch of the scratch (stride floats apart, the batch owns it).
-// live (rwkv_mi_batch_decode_until; NULL: every row draws): a row whose LIVE WORD is 0 has retired and returns before it reads a logit -- no
-// draw, no counter advance, no token or history word. The whole workgroup takes the branch together: no barrier is left waiting.
-__global__ __launch_bounds__(1024) void k_sample_rows(const float * __restrict__ logits, int n, const SampleRow * __restrict__ table,
-                                                      float * __restrict__ probs, size_t stride, uint32_t * __restrict__ tokens, uint32_t * __restrict__ hist,
-                                                      const uint32_t * __restrict__ live) {
+// The row entry: grid = rows, one workgroup per row of logits[rows][n] with table[r]; row r's probabilities in its own stretch of the scratch
+// (stride floats apart, the batch owns it), its token in tokens[r] and, with a history, hist[r].
+// live (rwkv_mi_batch_decode_until; NULL: every row draws): a row whose LIVE WORD is 0 has retired and returns before it reads anything -- no
+// draw, no counter advance, no count or sweep, no guide step, no token or history word. The whole workgroup takes the branch together: no
+// barrier is left waiting.
+template <int SRC, bool CUT, bool GUIDED>
+__global__ __launch_bounds__(1024) void k_draw_rows(const float * __restrict__ logits, int n, const DrawRow * __restrict__ table, float * __restrict__ probs,
+                                                    size_t stride, uint32_t * __restrict__ tokens, uint32_t * __restrict__ hist,
+                                                    const uint32_t * __restrict__ live) {
     const size_t r = blockIdx.x;
     if (live && !live[r]) return;
-    const rwkv_mi_sample_params p = table[r].p;
-    const float * lg = logits + r * (size_t) n;
-    sample_body([=](int i0) { return PlainLogits{lg + i0}; }, n, p.temperature, p.top_p, 0.0f, p.u, p.seed, table[r].counter, probs + r * stride, tokens + r, hist ? hist + r : nullptr);
-}
-
-__global__ __launch_bounds__(1024) void k_cut_sample_rows(const float * __restrict__ logits, int n, const SampleRow * __restrict__ table,
-                                                          const CutRow * __restrict__ cuts, float * __restrict__ probs, size_t stride,
-                                                          uint32_t * __restrict__ tokens, uint32_t * __restrict__ hist, const uint32_t * __restrict__ live) {
-    const size_t r = blockIdx.x;
-    if (live && !live[r]) return;
-    const rwkv_mi_sample_params p = table[r].p;
-    const float * lg = logits + r * (size_t) n;
-    const CutRow cut = cuts[r];
-    cut_sample([=](int i0) { return PlainLogits{lg + i0}; }, cut, n, p.temperature, p.top_p, p.u, p.seed, table[r].counter, probs + r * stride, tokens + r,
-               hist ? hist + r : nullptr);
-}
-
-// The penalised entry points: the same body on the adjusted logits, then -- when `record` is set -- the chosen token's count goes up by
-// one (thread 0, after the draw, argmax or not: the draw of step i has seen the counts of the steps before it).
-__global__ __launch_bounds__(1024) void k_pen_sample(const float * __restrict__ logits, int n, float temperature, float top_p, float u_in,
-                                                     unsigned long long seed, unsigned long long * counter, float presence, float frequency, uint32_t record,
-                                                     uint32_t * count, const float * __restrict__ bias,
-                                                     float * __restrict__ probs, uint32_t * __restrict__ out_token, uint32_t * __restrict__ hist, int hist_pos) {
-    const int pick = sample_body([=](int i0) { return PenalisedLogits{logits + i0, count + i0, bias ? bias + i0 : nullptr, presence, frequency}; },
-                                 n, temperature, top_p, 0.0f, u_in, seed, counter, probs, out_token, hist ? hist + hist_pos : nullptr);
-    if (threadIdx.x == 0 && record) count[pick] += 1u;
-}
-
-__global__ __launch_bounds__(1024) void k_cut_pen_sample(const float * __restrict__ logits, int n, float temperature, float top_p, float u_in,
-                                                         unsigned long long seed, unsigned long long * counter, float presence, float frequency, uint32_t record,
-                                                         uint32_t * count, const float * __restrict__ bias, CutRow cut,
-                                                         float * __restrict__ probs, uint32_t * __restrict__ out_token, uint32_t * __restrict__ hist, int hist_pos) {
-    const int pick = cut_sample([=](int i0) { return PenalisedLogits{logits + i0, count + i0, bias ? bias + i0 : nullptr, presence, frequency}; },
-                                cut, n, temperature, top_p, u_in, seed, counter, probs, out_token, hist ? hist + hist_pos : nullptr);
-    if (threadIdx.x == 0 && record) count[pick] += 1u;
-}
-
-// (live: as k_sample_rows -- a retired row records nothing either)
-__global__ __launch_bounds__(1024) void k_pen_sample_rows(const float * __restrict__ logits, int n, const PenaltyRow * __restrict__ table,
-                                                          float * __restrict__ probs, size_t stride, uint32_t * __restrict__ tokens, uint32_t * __restrict__ hist,
-                                                          const uint32_t * __restrict__ live) {
-    const size_t r = blockIdx.x;
-    if (live && !live[r]) return;
-    const PenaltyRow row = table[r];
-    const float * lg = logits + r * (size_t) n;
-    const int pick = sample_body([=](int i0) { return PenalisedLogits{lg + i0, row.count + i0, row.bias ? row.bias + i0 : nullptr, row.presence, row.frequency}; },
-                                 n, row.p.temperature, row.p.top_p, 0.0f, row.p.u, row.p.seed, row.counter, probs + r * stride, tokens + r, hist ? hist + r : nullptr);
-    if (threadIdx.x == 0 && row.record) row.count[pick] += 1u;
-}
-
-__global__ __launch_bounds__(1024) void k_cut_pen_sample_rows(const float * __restrict__ logits, int n, const PenaltyRow * __restrict__ table,
-                                                              const CutRow * __restrict__ cuts, float * __restrict__ probs, size_t stride,
-                                                              uint32_t * __restrict__ tokens, uint32_t * __restrict__ hist, const uint32_t * __restrict__ live) {
-    const size_t r = blockIdx.x;
-    if (live && !live[r]) return;
-    const PenaltyRow row = table[r];
-    const CutRow cut = cuts[r];
-    const float * lg = logits + r * (size_t) n;
-    const int pick = cut_sample([=](int i0) { return PenalisedLogits{lg + i0, row.count + i0, row.bias ? row.bias + i0 : nullptr, row.presence, row.frequency}; },
-                                cut, n, row.p.temperature, row.p.top_p, row.p.u, row.p.seed, row.counter, probs + r * stride, tokens + r, hist ? hist + r : nullptr);
-    if (threadIdx.x == 0 && row.record) row.count[pick] += 1u;
-}
-
-// The guided entry points (rwkv_mi_batch_guide_*): the two row forms above with a parallel table of guide rows. Row r with a guide reads
-// its slot's state word s -- every thread, before the body's first barrier; thread 0 writes it after the last -- and draws through
-// GuidedLogits on row s of the guide's table; a row without one (next == NULL) picks, bit for bit, what the unguided kernel picks.
-// live: as k_sample_rows -- a retired row does not advance its guide either.
-__global__ __launch_bounds__(1024) void k_guided_sample_rows(const float * __restrict__ logits, int n, const SampleRow * __restrict__ table,
-                                                             const GuideRow * __restrict__ guides, const CutRow * __restrict__ cuts /* may be NULL */,
-                                                             float * __restrict__ probs, size_t stride,
-                                                             uint32_t * __restrict__ tokens, uint32_t * __restrict__ hist, const uint32_t * __restrict__ live) {
-    const size_t r = blockIdx.x;
-    if (live && !live[r]) return;
-    const rwkv_mi_sample_params p = table[r].p;
-    const GuideRow g = guides[r];
-    const CutRow cut = cuts ? cuts[r] : CutRow{0u, 0.0f};
-    const uint16_t * srow = g.next ? g.next + (size_t) *g.state * (size_t) n : nullptr;
-    const float * lg = logits + r * (size_t) n;
-    const int pick = cut_sample([=](int i0) { return GuidedLogits<PlainLogits>{PlainLogits{lg + i0}, srow ? srow + i0 : nullptr}; },
-                                cut, n, p.temperature, p.top_p, p.u, p.seed, table[r].counter, probs + r * stride, tokens + r, hist ? hist + r : nullptr);
-    if (threadIdx.x == 0 && srow) guide_advance(g, srow, pick);
-}
-
-__global__ __launch_bounds__(1024) void k_guided_pen_sample_rows(const float * __restrict__ logits, int n, const PenaltyRow * __restrict__ table,
-                                                                 const GuideRow * __restrict__ guides, const CutRow * __restrict__ cuts /* may be NULL */,
-                                                                 float * __restrict__ probs, size_t stride,
-                                                                 uint32_t * __restrict__ tokens, uint32_t * __restrict__ hist, const uint32_t * __restrict__ live) {
-    const size_t r = blockIdx.x;
-    if (live && !live[r]) return;
-    const PenaltyRow row = table[r];
-    const GuideRow g = guides[r];
-    const CutRow cut = cuts ? cuts[r] : CutRow{0u, 0.0f};
-    const uint16_t * srow = g.next ? g.next + (size_t) *g.state * (size_t) n : nullptr;
-    const float * lg = logits + r * (size_t) n;
-    const int pick = cut_sample([=](int i0) {
-                                    return GuidedLogits<PenalisedLogits>{PenalisedLogits{lg + i0, row.count + i0, row.bias ? row.bias + i0 : nullptr, row.presence, row.frequency},
-                                                                         srow ? srow + i0 : nullptr};
-                                },
-                                cut, n, row.p.temperature, row.p.top_p, row.p.u, row.p.seed, row.counter, probs + r * stride, tokens + r, hist ? hist + r : nullptr);
-    if (threadIdx.x == 0 && row.record) row.count[pick] += 1u;
-    if (threadIdx.x == 0 && srow) guide_advance(g, srow, pick);
-}
-
-// The entry points of a penalised draw with a repetition setting (k_rep_*; launched only where a row of the call has one: a call without
-// launches what it launched before): the single-context form with the settings by value, the row form and the guided row form with the
-// table `reps` parallel to the row table (cuts may be NULL; a row with {1, 1} reads uint32 counts and draws as k_pen_sample_rows does), and --
-// below -- the draft walk. The draw is cut_sample on RepetitionLogits, so a truncation setting and a guide compose with it as with the
-// penalised source; a retired row (live) returns before it reads or sweeps anything.
-__global__ __launch_bounds__(1024) void k_rep_pen_sample(const float * __restrict__ logits, int n, float temperature, float top_p, float u_in,
-                                                         unsigned long long seed, unsigned long long * counter, float presence, float frequency, uint32_t record,
-                                                         uint32_t * count, const float * __restrict__ bias, CutRow cut, RepRow rep,
-                                                         float * __restrict__ probs, uint32_t * __restrict__ out_token, uint32_t * __restrict__ hist, int hist_pos) {
-    const int pick = cut_sample(rep_source(logits, count, bias, presence, frequency, rep), cut, n, temperature, top_p, u_in, seed, counter, probs, out_token,
-                                hist ? hist + hist_pos : nullptr);
-    rep_record(count, n, rep, record, pick);
-}
-
-__global__ __launch_bounds__(1024) void k_rep_pen_sample_rows(const float * __restrict__ logits, int n, const PenaltyRow * __restrict__ table,
-                                                              const CutRow * __restrict__ cuts /* may be NULL */, const RepRow * __restrict__ reps,
-                                                              float * __restrict__ probs, size_t stride,
-                                                              uint32_t * __restrict__ tokens, uint32_t * __restrict__ hist, const uint32_t * __restrict__ live) {
-    const size_t r = blockIdx.x;
-    if (live && !live[r]) return;
-    const PenaltyRow row = table[r];
-    const CutRow cut = cuts ? cuts[r] : CutRow{0u, 0.0f};
-    const RepRow rep = reps[r];
-    const int pick = cut_sample(rep_source(logits + r * (size_t) n, row.count, row.bias, row.presence, row.frequency, rep),
-                                cut, n, row.p.temperature, row.p.top_p, row.p.u, row.p.seed, row.counter, probs + r * stride, tokens + r, hist ? hist + r : nullptr);
-    rep_record(row.count, n, rep, row.record, pick);
-}
-
-__global__ __launch_bounds__(1024) void k_guided_rep_pen_sample_rows(const float * __restrict__ logits, int n, const PenaltyRow * __restrict__ table,
-                                                                     const GuideRow * __restrict__ guides, const CutRow * __restrict__ cuts /* may be NULL */,
-                                                                     const RepRow * __restrict__ reps, float * __restrict__ probs, size_t stride,
-                                                                     uint32_t * __restrict__ tokens, uint32_t * __restrict__ hist, const uint32_t * __restrict__ live) {
-    const size_t r = blockIdx.x;
-    if (live && !live[r]) return;
-    const PenaltyRow row = table[r];
-    const GuideRow g = guides[r];
-    const CutRow cut = cuts ? cuts[r] : CutRow{0u, 0.0f};
-    const RepRow rep = reps[r];
-    const uint16_t * srow = g.next ? g.next + (size_t) *g.state * (size_t) n : nullptr;
-    const auto inner = rep_source(logits + r * (size_t) n, row.count, row.bias, row.presence, row.frequency, rep);
-    const int pick = cut_sample([=](int i0) { return GuidedLogits<RepetitionLogits>{inner(i0), srow ? srow + i0 : nullptr}; },
-                                cut, n, row.p.temperature, row.p.top_p, row.p.u, row.p.seed, row.counter, probs + r * stride, tokens + r, hist ? hist + r : nullptr);
-    rep_record(row.count, n, rep, row.record, pick);
-    if (threadIdx.x == 0 && srow) guide_advance(g, srow, pick);
+    const DrawRow row = table[r];
+    draw_row<SRC, CUT, GUIDED>(logits + r * (size_t) n, n, row, row.record, probs + r * stride, tokens + r, hist ? hist + r : nullptr);
 }
 
 // The greedy loops' choice for one row by the whole workgroup, returned to every thread: the largest logit, the lowest index among equals; a
@@ -590,75 +480,33 @@ __device__ __forceinline__ int draft_argmax(const float * lg, int n) {
 
 // rwkv_mi_batch_eval_draft: which tokens of a row's draft stand. One workgroup per row r = segment segs[r] of the pass, whose tokens
 // [t0, t1) are x0 d1 .. dk and whose logits (of EVERY token: logits[T][n]) are in HBM. Position j = 0 .. k chooses e_j from the logits after
-// token t0 + j exactly as the plain loop of the family chooses it -- FAMILY 0: the greedy argmax; 1: sample_body on PlainLogits with the row of
-// k_sample_rows; 2: sample_body on PenalisedLogits with the row of k_pen_sample_rows, thread 0 counting the pick -- and writes it to
-// out[r][j]; the walk ends after the first j with j == k or e_j != d(j+1). Then keep[r] = j + 1, out[r][j + 1 .. out_stride) = RWKV_MI_NO_TOKEN
-// and the logits of position j go to row r of logits_row. The draw counter and the counts advance once per position walked, so they end where
-// the plain loop of keep[r] steps leaves them. The pick comes back to every thread: the whole workgroup leaves the walk together. Between two
-// positions a fence and a barrier: the next one reads the counter and the count thread 0 has just written, and reuses the body's LDS words.
+// token t0 + j exactly as the plain loop of the family chooses it -- FAMILY 0: the greedy argmax; 1 + SRC: draw_row<SRC, true, false> on
+// table[r], recording (a row without a truncation setting carries {0, 0}) -- and writes it to out[r][j]; the walk ends after the first j with
+// j == k or e_j != d(j+1). Then keep[r] = j + 1, out[r][j + 1 .. out_stride) = RWKV_MI_NO_TOKEN and the logits of position j go to row r of
+// logits_row. The draw counter and the occurrence row advance once per position walked -- a decaying row sweeps and counts each time -- so they
+// end where the plain loop of keep[r] steps leaves them: nothing is rolled back. The pick comes back to every thread: the whole workgroup
+// leaves the walk together. Between two positions a fence and a barrier: the next one reads the counter and the count thread 0 has just
+// written, and reuses the body's LDS words.
 template <int FAMILY>
 __global__ __launch_bounds__(1024) void k_draft_accept_rows(const float * __restrict__ logits, int n, const SegState * __restrict__ segs,
-                                                            const uint32_t * __restrict__ tokens, const SampleRow * __restrict__ srows,
-                                                            const PenaltyRow * __restrict__ prows, const CutRow * __restrict__ cuts /* may be NULL */,
-                                                            float * __restrict__ probs, size_t stride,
-                                                            uint32_t * __restrict__ out, int out_stride, uint32_t * __restrict__ keep,
-                                                            float * __restrict__ logits_row) {
+                                                            const uint32_t * __restrict__ tokens, const DrawRow * __restrict__ table /* FAMILY 0: unread */,
+                                                            float * __restrict__ probs, size_t stride, uint32_t * __restrict__ out, int out_stride,
+                                                            uint32_t * __restrict__ keep, float * __restrict__ logits_row) {
     const size_t r = blockIdx.x;
     const SegState seg = segs[r];
-    const CutRow cut = FAMILY != 0 && cuts ? cuts[r] : CutRow{0u, 0.0f};
     const int k = seg.t1 - seg.t0 - 1;
     uint32_t * o = out + r * (size_t) out_stride;
     int j = 0;
     for (;;) {
         const float * lg = logits + (size_t) (seg.t0 + j) * (size_t) n;
         int pick;
-        if (FAMILY == 0) {
+        if constexpr (FAMILY == 0) {
             pick = draft_argmax(lg, n);
             if (threadIdx.x == 0) o[j] = (uint32_t) pick;
-        } else if (FAMILY == 1) {
-            const rwkv_mi_sample_params p = srows[r].p;
-            pick = cut_sample([=](int i0) { return PlainLogits{lg + i0}; }, cut, n, p.temperature, p.top_p, p.u, p.seed, srows[r].counter, probs + r * stride, o + j, nullptr);
         } else {
-            const PenaltyRow row = prows[r];
-            pick = cut_sample([=](int i0) { return PenalisedLogits{lg + i0, row.count + i0, row.bias ? row.bias + i0 : nullptr, row.presence, row.frequency}; },
-                              cut, n, row.p.temperature, row.p.top_p, row.p.u, row.p.seed, row.counter, probs + r * stride, o + j, nullptr);
-            if (threadIdx.x == 0) row.count[pick] += 1u;
+            const DrawRow row = table[r];
+            pick = draw_row<FAMILY - 1, true, false>(lg, n, row, 1u, probs + r * stride, o + j, nullptr);
         }
-        if (j == k || (uint32_t) pick != tokens[seg.t0 + j + 1]) break;
-        j++;
-        __threadfence_block();
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) keep[r] = (uint32_t) (j + 1);
-    for (int i = j + 1 + (int) threadIdx.x; i < out_stride; i += blockDim.x) o[i] = RWKV_MI_NO_TOKEN;
-    const float * src = logits + (size_t) (seg.t0 + j) * (size_t) n;
-    float * dst = logits_row + r * (size_t) n;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) dst[i] = src[i];
-}
-
-// The walk's fourth family: family 2 on RepetitionLogits with the row's setting reps[r]. An entry point of its own with the walk written out
-// again, not a fourth value of FAMILY: the three instantiations above compile as they did before there were repetition settings (sharing the
-// walk through a device function moved the registers of the greedy one). Every position walked records, so a decaying row sweeps and counts
-// once per position walked and its table ends where the plain loop of keep[r] steps leaves it: nothing is rolled back.
-__global__ __launch_bounds__(1024) void k_rep_draft_accept_rows(const float * __restrict__ logits, int n, const SegState * __restrict__ segs,
-                                                                const uint32_t * __restrict__ tokens, const PenaltyRow * __restrict__ prows,
-                                                                const CutRow * __restrict__ cuts /* may be NULL */, const RepRow * __restrict__ reps,
-                                                                float * __restrict__ probs, size_t stride,
-                                                                uint32_t * __restrict__ out, int out_stride, uint32_t * __restrict__ keep,
-                                                                float * __restrict__ logits_row) {
-    const size_t r = blockIdx.x;
-    const SegState seg = segs[r];
-    const CutRow cut = cuts ? cuts[r] : CutRow{0u, 0.0f};
-    const RepRow rep = reps[r];
-    const int k = seg.t1 - seg.t0 - 1;
-    uint32_t * o = out + r * (size_t) out_stride;
-    int j = 0;
-    for (;;) {
-        const float * lg = logits + (size_t) (seg.t0 + j) * (size_t) n;
-        const PenaltyRow row = prows[r];
-        const int pick = cut_sample(rep_source(lg, row.count, row.bias, row.presence, row.frequency, rep),
-                                    cut, n, row.p.temperature, row.p.top_p, row.p.u, row.p.seed, row.counter, probs + r * stride, o + j, nullptr);
-        rep_record(row.count, n, rep, 1u, pick);
         if (j == k || (uint32_t) pick != tokens[seg.t0 + j + 1]) break;
         j++;
         __threadfence_block();
@@ -740,72 +588,65 @@ __global__ __launch_bounds__(256) void k_bias_scatter(float * __restrict__ bias,
     if (i < n && ids[i] < (uint32_t) n_vocab) bias[ids[i]] = values[i];
 }
 
-__global__ __launch_bounds__(64) void k_sample_seek_rows(const SampleRow * __restrict__ table, int rows, unsigned long long value) {
+__global__ __launch_bounds__(64) void k_sample_seek_rows(const DrawRow * __restrict__ table, int rows, unsigned long long value) {
     const int r = blockIdx.x * 64 + threadIdx.x;
     if (r < rows) *table[r].counter = value;
 }
 
-void launch_sample(const float * logits, int n, float temperature, float top_p, float u, unsigned long long seed, unsigned long long * counter,
-                   const CutRow & cut, float * probs, uint32_t * out_token, uint32_t * hist, int hist_pos, hipStream_t st) {
-    if (cut.top_k == 0u && cut.min_p == 0.0f) hipLaunchKernelGGL(k_sample, dim3(1), dim3(1024), 0, st, logits, n, temperature, top_p, u, seed, counter, probs, out_token, hist, hist_pos);
-    else hipLaunchKernelGGL(k_cut_sample, dim3(1), dim3(1024), 0, st, logits, n, temperature, top_p, u, seed, counter, cut, probs, out_token, hist, hist_pos);
+// From a call's form to the instantiation it launches: the one switch of each launcher is over this number. Exactly the forms listed are
+// compiled (tests/test_cpu_draw_forms.py holds the file to the list); DrawForm::of makes no other, and one that arrives anyway is a bug of the
+// caller's that ends the process rather than draw with another kernel.
+constexpr int form_id(int src, bool cut, bool guided) { return src * 4 + (cut ? 2 : 0) + (guided ? 1 : 0); }
+static int form_id(const DrawForm & f) { return form_id(f.rep ? SRC_REP : f.draw == Draw::penalized ? SRC_PEN : SRC_PLAIN, f.cut, f.guided); }
+[[noreturn]] static void no_such_form(const DrawForm & f) {
+    fprintf(stderr, "sampling.hip: no draw kernel of the form {draw %d, cut %d, guided %d, rep %d}\n", (int) f.draw, (int) f.cut, (int) f.guided, (int) f.rep);
+    abort();
 }
 
-void launch_sample_rows(const float * logits, int64_t rows, int n, const SampleRow * table, const CutRow * cuts, float * probs, uint32_t * tokens,
-                        uint32_t * hist, const uint32_t * live, hipStream_t st) {
-    if (!cuts) hipLaunchKernelGGL(k_sample_rows, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, table, probs, sample_scratch_floats(n), tokens, hist, live);
-    else hipLaunchKernelGGL(k_cut_sample_rows, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, table, cuts, probs, sample_scratch_floats(n), tokens, hist, live);
-}
-
-void launch_pen_sample(const float * logits, int n, float temperature, float top_p, float u, unsigned long long seed, unsigned long long * counter,
-                       float presence, float frequency, uint32_t record, uint32_t * count, const float * bias, const CutRow & cut, const RepRow & rep,
-                       float * probs, uint32_t * out_token, uint32_t * hist, int hist_pos, hipStream_t st) {
-    if (rep.decay != 1.0f || rep.repetition != 1.0f)
-        hipLaunchKernelGGL(k_rep_pen_sample, dim3(1), dim3(1024), 0, st, logits, n, temperature, top_p, u, seed, counter, presence, frequency, record, count, bias, cut, rep,
-                           probs, out_token, hist, hist_pos);
-    else if (cut.top_k == 0u && cut.min_p == 0.0f)
-        hipLaunchKernelGGL(k_pen_sample, dim3(1), dim3(1024), 0, st, logits, n, temperature, top_p, u, seed, counter, presence, frequency, record, count, bias,
-                           probs, out_token, hist, hist_pos);
-    else
-        hipLaunchKernelGGL(k_cut_pen_sample, dim3(1), dim3(1024), 0, st, logits, n, temperature, top_p, u, seed, counter, presence, frequency, record, count, bias, cut,
-                           probs, out_token, hist, hist_pos);
-}
-
-void launch_pen_sample_rows(const float * logits, int64_t rows, int n, const PenaltyRow * table, const CutRow * cuts, const RepRow * reps, float * probs,
-                            uint32_t * tokens, uint32_t * hist, const uint32_t * live, hipStream_t st) {
-    if (reps) hipLaunchKernelGGL(k_rep_pen_sample_rows, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, table, cuts, reps, probs, sample_scratch_floats(n), tokens, hist, live);
-    else if (!cuts) hipLaunchKernelGGL(k_pen_sample_rows, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, table, probs, sample_scratch_floats(n), tokens, hist, live);
-    else hipLaunchKernelGGL(k_cut_pen_sample_rows, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, table, cuts, probs, sample_scratch_floats(n), tokens, hist, live);
-}
-
-void launch_guided_sample_rows(const float * logits, int64_t rows, int n, const SampleRow * table, const GuideRow * guides, const CutRow * cuts, float * probs,
-                               uint32_t * tokens, uint32_t * hist, const uint32_t * live, hipStream_t st) {
-    hipLaunchKernelGGL(k_guided_sample_rows, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, table, guides, cuts, probs, sample_scratch_floats(n), tokens, hist, live);
-}
-
-void launch_guided_pen_sample_rows(const float * logits, int64_t rows, int n, const PenaltyRow * table, const GuideRow * guides, const CutRow * cuts,
-                                   const RepRow * reps, float * probs, uint32_t * tokens, uint32_t * hist, const uint32_t * live, hipStream_t st) {
-    if (reps) hipLaunchKernelGGL(k_guided_rep_pen_sample_rows, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, table, guides, cuts, reps, probs, sample_scratch_floats(n),
-                                 tokens, hist, live);
-    else hipLaunchKernelGGL(k_guided_pen_sample_rows, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, table, guides, cuts, probs, sample_scratch_floats(n), tokens, hist, live);
-}
-
-void launch_draft_accept_rows(const float * logits, int64_t rows, int n, const SegState * segs, const uint32_t * tokens, Draw draw, const SampleRow * srows,
-                              const PenaltyRow * prows, const CutRow * cuts, const RepRow * reps, float * probs, uint32_t * out, int out_stride, uint32_t * keep,
-                              float * logits_row, hipStream_t st) {
-    if (draw == Draw::penalized && reps) {
-        hipLaunchKernelGGL(k_rep_draft_accept_rows, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, segs, tokens, prows, cuts, reps, probs, sample_scratch_floats(n), out,
-                           out_stride, keep, logits_row);
-        return;
-    }
+void launch_draw(const float * logits, int n, const DrawRow & row, const DrawForm & form, float * probs, uint32_t * out_token, uint32_t * hist, int hist_pos,
+                 hipStream_t st) {
     auto go = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, segs, tokens, srows, prows, cuts, probs, sample_scratch_floats(n), out, out_stride,
-                           keep, logits_row);
+        hipLaunchKernelGGL(kern, dim3(1), dim3(1024), 0, st, logits, n, row.p.temperature, row.p.top_p, row.p.u, (unsigned long long) row.p.seed, row.counter, row.presence,
+                           row.frequency, row.record, row.count, row.bias, CutRow{row.top_k, row.min_p}, RepRow{row.decay, row.repetition}, probs, out_token, hist, hist_pos);
     };
-    switch (draw) {
-        case Draw::none: go(k_draft_accept_rows<0>); break;
-        case Draw::sample: go(k_draft_accept_rows<1>); break;
-        case Draw::penalized: go(k_draft_accept_rows<2>); break;
+    switch (form_id(form)) {
+        case form_id(SRC_PLAIN, false, false): go(k_draw<SRC_PLAIN, false>); break;
+        case form_id(SRC_PLAIN, true, false):  go(k_draw<SRC_PLAIN, true>); break;
+        case form_id(SRC_PEN, false, false):   go(k_draw<SRC_PEN, false>); break;
+        case form_id(SRC_PEN, true, false):    go(k_draw<SRC_PEN, true>); break;
+        case form_id(SRC_REP, true, false):    go(k_draw<SRC_REP, true>); break;
+        default: no_such_form(form);
+    }
+}
+
+void launch_draw_rows(const float * logits, int64_t rows, int n, const DrawRow * table, const DrawForm & form, float * probs, uint32_t * tokens, uint32_t * hist,
+                      const uint32_t * live, hipStream_t st) {
+    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, table, probs, sample_scratch_floats(n), tokens, hist, live); };
+    switch (form_id(form)) {
+        case form_id(SRC_PLAIN, false, false): go(k_draw_rows<SRC_PLAIN, false, false>); break;
+        case form_id(SRC_PLAIN, true, false):  go(k_draw_rows<SRC_PLAIN, true, false>); break;
+        case form_id(SRC_PLAIN, true, true):   go(k_draw_rows<SRC_PLAIN, true, true>); break;
+        case form_id(SRC_PEN, false, false):   go(k_draw_rows<SRC_PEN, false, false>); break;
+        case form_id(SRC_PEN, true, false):    go(k_draw_rows<SRC_PEN, true, false>); break;
+        case form_id(SRC_PEN, true, true):     go(k_draw_rows<SRC_PEN, true, true>); break;
+        case form_id(SRC_REP, true, false):    go(k_draw_rows<SRC_REP, true, false>); break;
+        case form_id(SRC_REP, true, true):     go(k_draw_rows<SRC_REP, true, true>); break;
+        default: no_such_form(form);
+    }
+}
+
+// (the walk reads every row's truncation setting whatever form.cut says, and takes no guide: rwkv_mi_batch_eval_draft rejects a guided slot)
+void launch_draft_accept_rows(const float * logits, int64_t rows, int n, const SegState * segs, const uint32_t * tokens, const DrawRow * table, const DrawForm & form,
+                              float * probs, uint32_t * out, int out_stride, uint32_t * keep, float * logits_row, hipStream_t st) {
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, segs, tokens, table, probs, sample_scratch_floats(n), out, out_stride, keep, logits_row);
+    };
+    if (form.guided) no_such_form(form);
+    if (form.draw == Draw::none) go(k_draft_accept_rows<0>);
+    else switch (form_id(form) / 4) {
+        case SRC_PLAIN: go(k_draft_accept_rows<1 + SRC_PLAIN>); break;
+        case SRC_PEN:   go(k_draft_accept_rows<1 + SRC_PEN>); break;
+        case SRC_REP:   go(k_draft_accept_rows<1 + SRC_REP>); break;
     }
 }
 
@@ -830,7 +671,7 @@ void launch_bias_scatter(float * bias, const uint32_t * ids, const float * value
     if (n > 0) hipLaunchKernelGGL(k_bias_scatter, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, st, bias, ids, values, n, n_vocab);
 }
 
-void launch_sample_seek_rows(const SampleRow * table, int64_t rows, unsigned long long value, hipStream_t st) {
+void launch_sample_seek_rows(const DrawRow * table, int64_t rows, unsigned long long value, hipStream_t st) {
     hipLaunchKernelGGL(k_sample_seek_rows, dim3((unsigned) ((rows + 63) / 64)), dim3(64), 0, st, table, (int) rows, value);
 }
 

@@ -1,6 +1,6 @@
 // testhooks_guide.cpp -- the guided sampler's entry point for tests/ ONLY (include/rwkv_testhooks_guide.h). `make` links it with every product
 // object into a library of its own, lib/librwkv_testhooks_guide.so; no other library carries it.
-#include "model.h"
+#include "testhooks_draw.h"
 #include "rwkv_mi355x.h"
 #include "rwkv_testhooks_guide.h"
 
@@ -35,48 +35,23 @@ RWKV_API bool rwkv_mi_test_guided_rows(const float * logits, int64_t n_rows, int
         RW_CHECK(RWKV_ERROR_ARGS, false, row_guide[r] == RWKV_MI_NO_GUIDE || (row_guide[r] < n_guides && row_state[r] < n_states[row_guide[r]]),
                  "bad guide or state of row %zu", r);
     std::vector<DevBuf<uint16_t>> tables(n_guides);
-    DevBuf<float> logits_buf, probs_buf, bias_buf;
-    DevBuf<unsigned long long> ctr_buf;
-    DevBuf<SampleRow> srow_buf;
-    DevBuf<PenaltyRow> prow_buf;
-    DevBuf<GuideRow> grow_buf;
-    DevBuf<uint32_t> tok_buf, state_buf, miss_buf, count_buf;
-    bool ok = logits_buf.alloc(R * V) == hipSuccess && probs_buf.alloc(R * sample_scratch_floats(n_vocab)) == hipSuccess && ctr_buf.alloc(R) == hipSuccess &&
-              srow_buf.alloc(R) == hipSuccess && prow_buf.alloc(R) == hipSuccess && grow_buf.alloc(R) == hipSuccess && tok_buf.alloc(R) == hipSuccess &&
-              state_buf.alloc(R) == hipSuccess && miss_buf.alloc(R) == hipSuccess && (!penalties || count_buf.alloc(R * V) == hipSuccess) &&
-              (!penalties || !bias || bias_buf.alloc(R * V) == hipSuccess);
+    DevBuf<uint32_t> state_buf, miss_buf;
+    DrawHook h;
+    bool ok = h.init(logits, n_rows, n_vocab, params, counters, penalties ? counts : nullptr, penalties ? bias : nullptr) && state_buf.alloc(R) == hipSuccess &&
+              miss_buf.alloc(R) == hipSuccess;
     for (uint32_t g = 0; ok && g < n_guides; g++) {
         bool alloc_failed = false;
         ok = guide_table_build(tables[g], V, n_states[g], edge_begin + begin_at[g], edge_tokens + edge_at[g], edge_next + edge_at[g], nullptr, &alloc_failed) == hipSuccess;
     }
-    ok = ok && hipMemcpy(logits_buf.p, logits, R * V * 4, hipMemcpyHostToDevice) == hipSuccess &&
-         (counters ? hipMemcpy(ctr_buf.p, counters, R * 8, hipMemcpyHostToDevice) : hipMemset(ctr_buf.p, 0, R * 8)) == hipSuccess &&
-         hipMemcpy(state_buf.p, row_state, R * 4, hipMemcpyHostToDevice) == hipSuccess && hipMemset(miss_buf.p, 0, R * 4) == hipSuccess &&
-         (!penalties || hipMemcpy(count_buf.p, counts, R * V * 4, hipMemcpyHostToDevice) == hipSuccess) &&
-         (!bias_buf || hipMemcpy(bias_buf.p, bias, R * V * 4, hipMemcpyHostToDevice) == hipSuccess);
-    if (ok) {
-        std::vector<SampleRow> srows(R);
-        std::vector<PenaltyRow> prows(R);
-        std::vector<GuideRow> grows(R);
-        for (size_t r = 0; r < R; r++) {
-            srows[r] = SampleRow{params[r], ctr_buf.p + r};
-            if (penalties) prows[r] = PenaltyRow{params[r], ctr_buf.p + r, penalties[r].presence, penalties[r].frequency, penalties[r].record, count_buf.p + r * V,
-                                                 bias_buf ? bias_buf.p + r * V : nullptr};
-            grows[r] = GuideRow{row_guide[r] == RWKV_MI_NO_GUIDE ? nullptr : tables[row_guide[r]].p, state_buf.p + r, miss_buf.p + r};
-        }
-        ok = hipMemcpy(srow_buf.p, srows.data(), R * sizeof(SampleRow), hipMemcpyHostToDevice) == hipSuccess &&
-             (!penalties || hipMemcpy(prow_buf.p, prows.data(), R * sizeof(PenaltyRow), hipMemcpyHostToDevice) == hipSuccess) &&
-             hipMemcpy(grow_buf.p, grows.data(), R * sizeof(GuideRow), hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && hipMemcpy(state_buf.p, row_state, R * 4, hipMemcpyHostToDevice) == hipSuccess && hipMemset(miss_buf.p, 0, R * 4) == hipSuccess;
+    for (size_t r = 0; ok && r < R; r++) {
+        if (penalties) h.penalise(r, penalties[r]);
+        h.rows[r].next = row_guide[r] == RWKV_MI_NO_GUIDE ? nullptr : tables[row_guide[r]].p;
+        h.rows[r].state = state_buf.p + r; h.rows[r].misses = miss_buf.p + r;
     }
-    if (ok) {
-        if (penalties) launch_guided_pen_sample_rows(logits_buf.p, n_rows, (int) n_vocab, prow_buf.p, grow_buf.p, nullptr, nullptr, probs_buf.p, tok_buf.p, nullptr, nullptr, nullptr);
-        else launch_guided_sample_rows(logits_buf.p, n_rows, (int) n_vocab, srow_buf.p, grow_buf.p, nullptr, probs_buf.p, tok_buf.p, nullptr, nullptr, nullptr);
-        ok = hipDeviceSynchronize() == hipSuccess && hipMemcpy(tokens_out, tok_buf.p, R * 4, hipMemcpyDeviceToHost) == hipSuccess &&
-             hipMemcpy(states_out, state_buf.p, R * 4, hipMemcpyDeviceToHost) == hipSuccess &&
-             hipMemcpy(misses_out, miss_buf.p, R * 4, hipMemcpyDeviceToHost) == hipSuccess &&
-             (!counters || hipMemcpy(counters, ctr_buf.p, R * 8, hipMemcpyDeviceToHost) == hipSuccess) &&
-             (!penalties || hipMemcpy(counts, count_buf.p, R * V * 4, hipMemcpyDeviceToHost) == hipSuccess);
-    }
+    // (the row kernel in its guided form whatever the rows' guides)
+    ok = ok && h.run(DrawForm::of(penalties ? Draw::penalized : Draw::sample, false, true, false), true, tokens_out, counters, penalties ? counts : nullptr) &&
+         hipMemcpy(states_out, state_buf.p, R * 4, hipMemcpyDeviceToHost) == hipSuccess && hipMemcpy(misses_out, miss_buf.p, R * 4, hipMemcpyDeviceToHost) == hipSuccess;
     RW_CHECK(RWKV_ERROR_GRAPH, false, ok, "HIP error: %s", hipGetErrorString(hipGetLastError()));
     return true;
 }

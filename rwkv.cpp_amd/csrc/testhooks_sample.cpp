@@ -2,7 +2,7 @@
 // (include/rwkv_testhooks_score.h), the report kernel's (include/rwkv_testhooks_logprobs.h) and the beam step's
 // (include/rwkv_testhooks_beam.h). `make` links it with every product
 // object into a third library, lib/librwkv_testhooks_sample.so; neither librwkv.so nor librwkv_testhooks.so carries it.
-#include "model.h"
+#include "testhooks_draw.h"
 #include "rwkv_mi355x.h"
 #include "rwkv_testhooks_sample.h"
 #include "rwkv_testhooks_score.h"
@@ -20,32 +20,9 @@ RWKV_API bool rwkv_mi_test_sample_rows(const float * logits, int64_t n_rows, int
                                        uint64_t * counters, int rows_kernel, uint32_t * tokens_out) {
     g_last_error = RWKV_ERROR_NONE;
     RW_CHECK(RWKV_ERROR_ARGS, false, logits && params && tokens_out && n_rows > 0 && n_rows <= 65535 && n_vocab > 0 && n_vocab <= (int64_t) 1 << 24, "bad arguments");
-    const size_t R = (size_t) n_rows, V = (size_t) n_vocab;
-    DevBuf<float> logits_buf, probs_buf;
-    DevBuf<unsigned long long> ctr_buf;
-    DevBuf<SampleRow> table_buf;
-    DevBuf<uint32_t> tok_buf;
-    std::vector<SampleRow> table(R);
-    bool ok = logits_buf.alloc(R * V) == hipSuccess && probs_buf.alloc(R * sample_scratch_floats(n_vocab)) == hipSuccess &&
-              ctr_buf.alloc(R) == hipSuccess && table_buf.alloc(R) == hipSuccess && tok_buf.alloc(R) == hipSuccess;
-    float * d_logits = logits_buf.p, * d_probs = probs_buf.p;
-    unsigned long long * d_ctr = ctr_buf.p;
-    SampleRow * d_table = table_buf.p;
-    uint32_t * d_tok = tok_buf.p;
-    ok = ok && hipMemcpy(d_logits, logits, R * V * 4, hipMemcpyHostToDevice) == hipSuccess &&
-         (counters ? hipMemcpy(d_ctr, counters, R * 8, hipMemcpyHostToDevice) : hipMemset(d_ctr, 0, R * 8)) == hipSuccess;
-    if (ok) {
-        for (size_t r = 0; r < R; r++) table[r] = SampleRow{params[r], d_ctr + r};
-        ok = hipMemcpy(d_table, table.data(), R * sizeof(SampleRow), hipMemcpyHostToDevice) == hipSuccess;
-    }
-    if (ok) {
-        if (rows_kernel) launch_sample_rows(d_logits, n_rows, (int) n_vocab, d_table, nullptr, d_probs, d_tok, nullptr, nullptr, nullptr);
-        else for (size_t r = 0; r < R; r++)
-            launch_sample(d_logits + r * V, (int) n_vocab, params[r].temperature, params[r].top_p, params[r].u, params[r].seed, d_ctr + r,
-                          CutRow{0u, 0.0f}, d_probs, d_tok + r, nullptr, 0, nullptr);
-        ok = hipDeviceSynchronize() == hipSuccess && hipMemcpy(tokens_out, d_tok, R * 4, hipMemcpyDeviceToHost) == hipSuccess &&
-             (!counters || hipMemcpy(counters, d_ctr, R * 8, hipMemcpyDeviceToHost) == hipSuccess);
-    }
+    DrawHook h;
+    const bool ok = h.init(logits, n_rows, n_vocab, params, counters, nullptr, nullptr) &&
+                    h.run(DrawForm::of(Draw::sample, false, false, false), rows_kernel != 0, tokens_out, counters, nullptr);
     RW_CHECK(RWKV_ERROR_GRAPH, false, ok, "HIP error: %s", hipGetErrorString(hipGetLastError()));
     return true;
 }

@@ -1,21 +1,23 @@
 """Presence / frequency penalties and logit bias in the device sampler, without a GPU: the libraries export the entry points of
 include/rwkv_mi355x.h's penalty family, the Python binding declares them (and lays struct rwkv_mi_penalty_params out as the C header does),
-and the four entry points of the sampler kernel (csrc/sampling.hip: k_sample, k_sample_rows and the penalised k_pen_sample,
-k_pen_sample_rows) keep within the budget of a 1024-thread workgroup: 128 registers per thread, no private segment, no spills."""
+and the four entry points of the sampler kernel (csrc/sampling.hip: k_draw<plain, 0>, k_draw_rows<plain, 0, 0> and the penalised k_draw<pen, 0>,
+k_draw_rows<pen, 0, 0>) keep within the budget of a 1024-thread workgroup: 128 registers per thread, no private segment, no spills."""
 import ctypes
 import os
 import re
-import subprocess
 
 import pytest
 
+import kernel_meta
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
 SYMBOLS = ("rwkv_mi_batch_counts_reset", "rwkv_mi_batch_counts_add", "rwkv_mi_batch_counts_store", "rwkv_mi_batch_logit_bias_set",
            "rwkv_mi_batch_eval_sample_penalized", "rwkv_mi_batch_eval_ragged_sample_penalized", "rwkv_mi_batch_decode_sample_penalized",
            "rwkv_mi_counts_reset", "rwkv_mi_counts_add", "rwkv_mi_counts_store", "rwkv_mi_logit_bias_set", "rwkv_mi_rng_seek",
            "rwkv_mi_sample_penalized", "rwkv_mi_decode_sample_penalized")
-KERNELS = ("k_sample", "k_sample_rows", "k_pen_sample", "k_pen_sample_rows")
+# k_draw<SRC, CUT> and k_draw_rows<SRC, CUT, GUIDED> on the plain (0) and the penalised (1) source, no other axis set: what k_sample,
+# k_sample_rows, k_pen_sample and k_pen_sample_rows were
+KERNELS = (("k_draw", (0, 0)), ("k_draw_rows", (0, 0, 0)), ("k_draw", (1, 0)), ("k_draw_rows", (1, 0, 0)))
 
 
 def _pkg():
@@ -68,22 +70,6 @@ def test_penalty_rows_take_scalars_or_sequences():
         pkg.penalty_params(3, 0.25, 0.5, record=[True, False])
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
-def test_penalised_and_plain_entry_points_keep_the_budget(tmp_path):
-    src = os.path.join(ROOT, "rwkv.cpp_amd", "csrc", "sampling.hip")
-    out = str(tmp_path / "sampling.s")
-    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-DRWKV_SHARED", "-DRWKV_BUILD",
-           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "rwkv.cpp_amd", "csrc"), "-S", "--cuda-device-only", src, "-o", out]
-    subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    text = open(out).read()
-    meta = text[text.index("amdhsa.kernels"):]
-    seen = {}
-    for m in re.finditer(r"\.name:\s+(\S+).*?\.private_segment_fixed_size:\s+(\d+).*?\.vgpr_count:\s+(\d+).*?\.vgpr_spill_count:\s+(\d+)", meta, re.S):
-        name, private, vgprs, spills = m.group(1), int(m.group(2)), int(m.group(3)), int(m.group(4))
-        for k in KERNELS:
-            if re.search(r"\d" + k + r"E[Pv]", name):   # (mangled: ...8k_sampleEPKf..., ...17k_pen_sample_rowsEPKf...: the length digits end before the name)
-                seen[k] = name
-                assert private == 0 and spills == 0, (name, private, vgprs, spills)
-                assert vgprs <= 128, (name, vgprs, "1024 threads per workgroup leave 128 registers per thread")
-    assert set(seen) == set(KERNELS), seen
-    assert len(set(seen.values())) == len(KERNELS), seen
+@pytest.mark.skipif(not kernel_meta.have_hipcc(), reason="needs hipcc")
+def test_penalised_and_plain_entry_points_keep_the_budget():
+    kernel_meta.budget("sampling.hip", KERNELS)

@@ -1,18 +1,18 @@
 """Sampling in batched decode without a GPU: the libraries export the entry points and the test hook, the Python binding declares them
-(and lays the parameter struct out as the C header does), and neither entry point of the sampler kernel (csrc/sampling.hip: k_sample,
-k_sample_rows) uses a private segment or spills.
+(and lays the parameter struct out as the C header does), and neither entry point of the sampler kernel (csrc/sampling.hip: k_draw<plain, 0>,
+k_draw_rows<plain, 0, 0>) uses a private segment or spills.
 
 The test hook lives in lib/librwkv_testhooks_sample.so (include/rwkv_testhooks_sample.h), not in librwkv_testhooks.so: the surface of that
 library is pinned to the nine entry points of include/rwkv_testhooks.h by tests/test_cpu_library.py."""
 import ctypes
 import os
 import re
-import subprocess
 
 import pytest
 
+import kernel_meta
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
 SYMBOLS = ("rwkv_mi_batch_eval_sample", "rwkv_mi_batch_decode_sample", "rwkv_mi_batch_rng_seek")
 HOOK = "rwkv_mi_test_sample_rows"
 
@@ -65,22 +65,7 @@ def test_parameter_rows_take_scalars_or_sequences():
         pkg.sample_params(3, [0.7, 0.8], 0.5)
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
-def test_sampler_entry_points_have_no_private_segment(tmp_path):
-    src = os.path.join(ROOT, "rwkv.cpp_amd", "csrc", "sampling.hip")
-    out = str(tmp_path / "sampling.s")
-    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-DRWKV_SHARED", "-DRWKV_BUILD",
-           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "rwkv.cpp_amd", "csrc"), "-S", "--cuda-device-only", src, "-o", out]
-    subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    text = open(out).read()
-    meta = text[text.index("amdhsa.kernels"):]
-    seen = {}
-    for m in re.finditer(r"\.name:\s+(\S+).*?\.private_segment_fixed_size:\s+(\d+).*?\.vgpr_count:\s+(\d+).*?\.vgpr_spill_count:\s+(\d+)", meta, re.S):
-        name, private, vgprs, spills = m.group(1), int(m.group(2)), int(m.group(3)), int(m.group(4))
-        for k in ("k_sample_rows", "k_sample"):
-            if re.search(k + r"E?[Pv]", name) or name.endswith(k):   # (mangled: ...8k_sampleEPKf..., ...13k_sample_rowsEPKf...)
-                seen[k] = name
-                assert private == 0 and spills == 0, (name, private, vgprs, spills)
-                assert vgprs <= 128, (name, vgprs, "1024 threads per workgroup leave 128 registers per thread")
-                break
-    assert set(seen) == {"k_sample", "k_sample_rows"}, seen
+@pytest.mark.skipif(not kernel_meta.have_hipcc(), reason="needs hipcc")
+def test_sampler_entry_points_have_no_private_segment():
+    # the two entry points of the plain draw with no other axis set: k_sample and k_sample_rows before the draws had one body
+    kernel_meta.budget("sampling.hip", (("k_draw", (0, 0)), ("k_draw_rows", (0, 0, 0))))

@@ -8,17 +8,19 @@ stop_rule() below is the stop rule of include/rwkv_mi355x.h restated in Python; 
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import kernel_meta
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
 SYMBOLS = ("rwkv_mi_batch_decode_until", "rwkv_mi_batch_last_loop_passes")
 NO_TOKEN = 0xFFFFFFFF
-# (sgpr_count, vgpr_count) of the four draw entry points as the commit before decode_until compiled them for gfx950: they must not move
-PARENT_REGS = {"k_sample": (48, 39), "k_sample_rows": (52, 39), "k_pen_sample": (50, 39), "k_pen_sample_rows": (54, 39)}
+# (sgpr_count, vgpr_count) of the four draw entry points as the commit before decode_until compiled them for gfx950: they must not move. They
+# were k_sample, k_sample_rows, k_pen_sample, k_pen_sample_rows then; now the plain and the penalised source of k_draw<SRC, CUT> and
+# k_draw_rows<SRC, CUT, GUIDED> with no other axis set
+PARENT_REGS = {("k_draw", (0, 0)): (48, 39), ("k_draw_rows", (0, 0, 0)): (52, 39), ("k_draw", (1, 0)): (50, 39), ("k_draw_rows", (1, 0, 0)): (54, 39)}
 NEW_KERNELS = ("k_stop_rows",)
 
 
@@ -121,26 +123,9 @@ def test_stop_rule_hand_written_cases():
     assert stop_rule([c, a, b, c, a], 5, [[a, b, c]]) == (4, 0)
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
-def test_draw_entry_points_and_stop_test_keep_the_budget_and_the_four_their_registers(tmp_path):
-    src = os.path.join(ROOT, "rwkv.cpp_amd", "csrc", "sampling.hip")
-    out = str(tmp_path / "sampling.s")
-    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-DRWKV_SHARED", "-DRWKV_BUILD",
-           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "rwkv.cpp_amd", "csrc"), "-S", "--cuda-device-only", src, "-o", out]
-    subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    text = open(out).read()
-    meta = text[text.index("amdhsa.kernels"):]
-    seen = {}
-    for m in re.finditer(r"\.name:\s+(\S+).*?\.private_segment_fixed_size:\s+(\d+).*?\.sgpr_count:\s+(\d+).*?\.vgpr_count:\s+(\d+).*?\.vgpr_spill_count:\s+(\d+)", meta, re.S):
-        name = m.group(1)
-        private, sgprs, vgprs, spills = (int(m.group(i)) for i in (2, 3, 4, 5))
-        for k in tuple(PARENT_REGS) + NEW_KERNELS:
-            if not re.search(r"\d" + k + r"E[PNv]", name):   # (mangled: the length digits end before the name, the argument list starts after E)
-                continue
-            seen[k] = name
-            assert private == 0 and spills == 0, (name, private, vgprs, spills)
-            assert vgprs <= 128, (name, vgprs, "1024 threads per workgroup leave 128 registers per thread")
-            if k in PARENT_REGS:
-                assert (sgprs, vgprs) == PARENT_REGS[k], (name, sgprs, vgprs, PARENT_REGS[k])
-    assert set(seen) == set(PARENT_REGS) | set(NEW_KERNELS), seen
-    assert len(set(seen.values())) == len(seen), seen
+@pytest.mark.skipif(not kernel_meta.have_hipcc(), reason="needs hipcc")
+def test_draw_entry_points_and_stop_test_keep_the_budget_and_the_four_their_registers():
+    drawn = kernel_meta.budget("sampling.hip", tuple(PARENT_REGS))
+    kernel_meta.budget("sampling.hip", NEW_KERNELS, wg=64)
+    for key, k in drawn.items():
+        assert (k.sgprs, k.vgprs) == PARENT_REGS[key], (key, k, PARENT_REGS[key])

@@ -10,14 +10,17 @@ import subprocess
 import numpy as np
 import pytest
 
+import kernel_meta
+
 import decay_ref as D
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
 SYMBOLS = {"rwkv_mi_batch_repetition_set": 4, "rwkv_mi_batch_repetition_get": 4, "rwkv_mi_batch_counts_store_f32": 3,
            "rwkv_mi_repetition_set": 3, "rwkv_mi_repetition_get": 3, "rwkv_mi_counts_store_f32": 2}
 HOOKS = {"rwkv_mi_test_decay_rows": 11, "rwkv_mi_test_decay_counts_add": 5}
-KERNELS = ("k_rep_pen_sample", "k_rep_pen_sample_rows", "k_guided_rep_pen_sample_rows", "k_rep_draft_accept_rows")
+# the repetition source (SRC = 2) of k_draw<SRC, CUT>, k_draw_rows<SRC, CUT, GUIDED> and the draft walk (FAMILY = 1 + SRC): what k_rep_pen_sample,
+# k_rep_pen_sample_rows, k_guided_rep_pen_sample_rows and k_rep_draft_accept_rows were
+KERNELS = (("k_draw", (2, 1)), ("k_draw_rows", (2, 1, 0)), ("k_draw_rows", (2, 1, 1)), ("k_draft_accept_rows", (3,)))
 F = np.float32
 
 
@@ -134,26 +137,8 @@ def test_decay_ref_table_rules():
     assert row[5] == F(0.0) and row[0] > F(1.99)
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
-def test_new_entry_points_keep_the_budget(tmp_path):
-    src = os.path.join(ROOT, "rwkv.cpp_amd", "csrc", "sampling.hip")
-    out = str(tmp_path / "sampling.s")
-    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-DRWKV_SHARED", "-DRWKV_BUILD",
-           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "rwkv.cpp_amd", "csrc"), "-S", "--cuda-device-only", src, "-o", out]
-    subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    text = open(out).read()
-    meta = text[text.index("amdhsa.kernels"):]
-    seen = {}
-    for m in re.finditer(r"\.max_flat_workgroup_size:\s+(\d+).*?\.name:\s+(\S+).*?\.private_segment_fixed_size:\s+(\d+).*?\.vgpr_count:\s+(\d+).*?\.vgpr_spill_count:\s+(\d+)",
-                         meta, re.S):
-        wg, name, private, vgprs, spills = int(m.group(1)), m.group(2), int(m.group(3)), int(m.group(4)), int(m.group(5))
-        for k in KERNELS:
-            if re.search(r"\d" + k + r"E[Pv]", name):   # (mangled: ...16k_rep_pen_sampleEPKf...: the length digits end before the name)
-                seen.setdefault(k, []).append(name)
-                print(name, wg, private, vgprs, spills)
-                assert private == 0 and spills == 0, (name, private, vgprs, spills)
-                assert vgprs <= 128, (name, vgprs, "1024 threads per workgroup leave 128 registers per thread")
-                assert wg == 1024, (name, wg)
-    assert set(seen) == set(KERNELS) and all(len(v) == 1 for v in seen.values()), seen
+@pytest.mark.skipif(not kernel_meta.have_hipcc(), reason="needs hipcc")
+def test_new_entry_points_keep_the_budget():
+    kernel_meta.budget("sampling.hip", KERNELS)
     # the decaying count kernel: one thread per entry
-    assert re.search(r"\.name:\s+\S*\d+k_count_add_decayEPf", meta)
+    assert re.search(r"\dk_count_add_decayEPf", kernel_meta.kernels("sampling.hip")["k_count_add_decay"].name)

@@ -5,12 +5,12 @@ every replay kernel without a private segment or spills, the accept kernel withi
 import ctypes
 import os
 import re
-import subprocess
 
 import pytest
 
+import kernel_meta
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
 SYMBOL, N_ARGS = "rwkv_mi_batch_eval_draft", 11
 ACCEPT = "k_draft_accept_rows"
 REPLAY = ("k_wkv4_replay", "k_wkv6_replay", "k_wkv6_replay_generic", "k_wkv7_replay", "k_wkv7_replay_generic", "k_draft_carry", "k_draft_stash")
@@ -80,46 +80,22 @@ def test_lookup_draft_on_hand_written_histories():
     assert d == [4] and type(d[0]) is int
 
 
-def _kernel_meta(src_name, tmp_path):
-    src = os.path.join(ROOT, "rwkv.cpp_amd", "csrc", src_name)
-    out = str(tmp_path / (src_name + ".s"))
-    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-DRWKV_SHARED", "-DRWKV_BUILD",
-           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "rwkv.cpp_amd", "csrc"), "-S", "--cuda-device-only", src, "-o", out]
-    subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    text = open(out).read()
-    meta = text[text.index("amdhsa.kernels"):]
-    rows = []
-    for m in re.finditer(r"\.max_flat_workgroup_size:\s+(\d+).*?\.name:\s+(\S+).*?\.private_segment_fixed_size:\s+(\d+).*?\.vgpr_count:\s+(\d+).*?\.vgpr_spill_count:\s+(\d+)",
-                         meta, re.S):
-        rows.append((m.group(2), int(m.group(1)), int(m.group(3)), int(m.group(4)), int(m.group(5))))
-    return rows
+@pytest.mark.skipif(not kernel_meta.have_hipcc(), reason="needs hipcc")
+def test_accept_kernel_keeps_the_budget():
+    """the families of k_draft_accept_rows -- greedy, sampled, penalised and (the fourth, k_rep_draft_accept_rows before the walk was one
+    template) penalised with a repetition setting: 1024 threads, so 128 registers per thread, no spills, no private segment"""
+    families = kernel_meta.named("sampling.hip", ACCEPT)
+    assert set(families) == {(0,), (1,), (2,), (3,)}, families
+    kernel_meta.budget("sampling.hip", tuple((ACCEPT, f) for f in families))
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
-def test_accept_kernel_keeps_the_budget(tmp_path):
-    """the three families of k_draft_accept_rows: 1024 threads, so 128 registers per thread, no spills, no private segment"""
-    seen = set()
-    for name, wg, private, vgprs, spills in _kernel_meta("sampling.hip", tmp_path):
-        m = re.search(r"\d" + ACCEPT + r"ILi(\d)EEEv", name)
-        if not m:
-            continue
-        seen.add(int(m.group(1)))
-        print(name, wg, private, vgprs, spills)
-        assert private == 0 and spills == 0, (name, private, vgprs, spills)
-        assert vgprs <= 128, (name, vgprs, "1024 threads per workgroup leave 128 registers per thread")
-        assert wg == 1024, (name, wg)
-    assert seen == {0, 1, 2}, seen
-
-
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
-def test_replay_kernels_have_no_private_segment_and_no_spills(tmp_path):
+@pytest.mark.skipif(not kernel_meta.have_hipcc(), reason="needs hipcc")
+def test_replay_kernels_have_no_private_segment_and_no_spills():
     """every entry point of the replay -- the fourth over each WKV body, templated and generic -- and the two copy kernels beside them"""
-    seen = {}
-    for name, wg, private, vgprs, spills in _kernel_meta("kernels.hip", tmp_path):
-        for k in REPLAY:
-            if re.search(r"\d" + k + r"(ILi\d+EEEv|E[Pv]|ENS_)", name):
-                seen.setdefault(k, []).append(name)
-                print(name, wg, private, vgprs, spills)
-                assert private == 0 and spills == 0, (name, private, vgprs, spills)
-    assert set(seen) == set(REPLAY), seen
+    seen = {k: kernel_meta.named("kernels.hip", k) for k in REPLAY}
+    for k, forms in seen.items():
+        assert forms, (k, seen)
+        for kern in forms.values():
+            print(kern)
+            assert kern.private == 0 and kern.spills == 0, kern
     assert len(seen["k_wkv6_replay"]) == 4 and len(seen["k_wkv7_replay"]) == 2, seen   # head sizes 64, 32, 16, 8 and 64, 32

@@ -10,13 +10,16 @@ import subprocess
 import numpy as np
 import pytest
 
+import kernel_meta
+
 import guide_ref as G
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
 SYMBOLS = {"rwkv_mi_batch_guide_create": 6, "rwkv_mi_batch_guide_free": 2, "rwkv_mi_batch_guide_attach": 4, "rwkv_mi_batch_guide_state": 5}
 HOOK = "rwkv_mi_test_guided_rows"
-KERNELS = ("k_guided_sample_rows", "k_guided_pen_sample_rows", "k_guide_expand")
+# the guided forms of k_draw_rows<SRC, CUT, GUIDED> on the plain (0) and the penalised (1) source: what k_guided_sample_rows and
+# k_guided_pen_sample_rows were
+KERNELS = (("k_draw_rows", (0, 1, 1)), ("k_draw_rows", (1, 1, 1)))
 
 
 def _pkg():
@@ -155,23 +158,7 @@ def test_bad_guides_fail_the_check():
         G.Guide([{1: 1}], 10)              # a next state out of range
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
-def test_guided_entry_points_keep_the_budget(tmp_path):
-    src = os.path.join(ROOT, "rwkv.cpp_amd", "csrc", "sampling.hip")
-    out = str(tmp_path / "sampling.s")
-    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-DRWKV_SHARED", "-DRWKV_BUILD",
-           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "rwkv.cpp_amd", "csrc"), "-S", "--cuda-device-only", src, "-o", out]
-    subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    text = open(out).read()
-    meta = text[text.index("amdhsa.kernels"):]
-    seen = {}
-    for m in re.finditer(r"\.max_flat_workgroup_size:\s+(\d+).*?\.name:\s+(\S+).*?\.private_segment_fixed_size:\s+(\d+).*?\.vgpr_count:\s+(\d+).*?\.vgpr_spill_count:\s+(\d+)",
-                         meta, re.S):
-        wg, name, private, vgprs, spills = int(m.group(1)), m.group(2), int(m.group(3)), int(m.group(4)), int(m.group(5))
-        for k in KERNELS:
-            if re.search(r"\d" + k + r"E[Pv]", name):
-                seen[k] = name
-                assert private == 0 and spills == 0, (name, private, vgprs, spills)
-                assert vgprs <= 128, (name, vgprs, "1024 threads per workgroup leave 128 registers per thread")
-                assert wg == (256 if k == "k_guide_expand" else 1024), (name, wg)
-    assert set(seen) == set(KERNELS), seen
+@pytest.mark.skipif(not kernel_meta.have_hipcc(), reason="needs hipcc")
+def test_guided_entry_points_keep_the_budget():
+    kernel_meta.budget("sampling.hip", KERNELS)
+    kernel_meta.budget("sampling.hip", ("k_guide_expand",), wg=256)

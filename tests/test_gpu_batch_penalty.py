@@ -1,5 +1,5 @@
-"""Presence / frequency penalties and logit bias in the device sampler (rwkv_mi_*_penalized, csrc/sampling.hip k_pen_sample /
-k_pen_sample_rows). The penalised draw is pinned three ways: bit for bit to the existing sampler fed the adjusted logits computed on the
+"""Presence / frequency penalties and logit bias in the device sampler (rwkv_mi_*_penalized, csrc/sampling.hip k_draw<pen, 0> /
+k_draw_rows<pen, 0, 0>). The penalised draw is pinned three ways: bit for bit to the existing sampler fed the adjusted logits computed on the
 host in float32 (the statement of include/rwkv_mi355x.h, operation by operation); to the existing calls when the penalties are zero; and
 to the reference's own statement (chat_with_bot.py:246-247, then sampling.py's sample_probs restated in float64). Loops, single steps and
 bursts are compared with each other, rows with contexts that run that sequence alone. Tokens, states, counts and draw counters are
@@ -69,7 +69,7 @@ def _counts_of(V, tokens):
 
 
 def _oracle_draw(adj_rows, T, P, U, seeds, counters):
-    """The existing sampler (plain k_sample_rows through its test hook) on the adjusted logits: tokens and the counters afterwards."""
+    """The existing sampler (plain k_draw_rows<plain, 0, 0> through its test hook) on the adjusted logits: tokens and the counters afterwards."""
     n = len(adj_rows)
     table = pkg.sample_params(n, T, P, U, seeds)
     return _sample_rows(np.stack(adj_rows), table, np.asarray(counters, dtype=np.uint64), 1)

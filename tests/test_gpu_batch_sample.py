@@ -1,4 +1,4 @@
-"""Sampling in batched decode (rwkv_mi_batch_eval_sample / _decode_sample / _rng_seek, csrc/sampling.hip k_sample_rows): every row is pinned
+"""Sampling in batched decode (rwkv_mi_batch_eval_sample / _decode_sample / _rng_seek, csrc/sampling.hip k_draw_rows<plain, 0, 0>): every row is pinned
 to the single-context sampler (rwkv_mi_sample / rwkv_mi_decode_sample on a context that steps that sequence alone), and both entry points of
 the kernel to the float64 restatement of the reference's sample_probs (test_gpu_sampling.ref_distribution). Tokens, states and draw counters
 are compared exactly."""

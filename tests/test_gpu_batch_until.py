@@ -1,5 +1,5 @@
-"""Stop sequences and per-row token budgets in the batch decode loops (rwkv_mi_batch_decode_until; csrc/sampling.hip k_sample_rows and
-k_pen_sample_rows behind their live words, k_stop_rows; csrc/kernels.hip k_argmax_live). The oracle is the unchanged plain loop of the same family plus matching
+"""Stop sequences and per-row token budgets in the batch decode loops (rwkv_mi_batch_decode_until; csrc/sampling.hip k_draw_rows<plain, 0, 0> and
+k_draw_rows<pen, 0, 0> behind their live words, k_stop_rows; csrc/kernels.hip k_argmax_live). The oracle is the unchanged plain loop of the same family plus matching
 on the host: the plain loop runs on a twin batch for the full budget, each row's expected length and reason are computed from its tokens by
 test_cpu_batch_until.stop_rule, and the plain loop runs again on fresh twins with n_tokens = len[r] for what the slot must hold. Every
 comparison is exact.

@@ -1,4 +1,4 @@
-"""Penalty decay and repetition penalty in the device sampler (rwkv_mi_*repetition_set, csrc/sampling.hip RepetitionLogits / k_rep_*): the
+"""Penalty decay and repetition penalty in the device sampler (rwkv_mi_*repetition_set, csrc/sampling.hip RepetitionLogits / the SRC_REP forms of k_draw, k_draw_rows and the draft walk): the
 draw is held, bit for bit, to the existing sampler on logits adjusted on the host by tests/decay_ref.py, the occurrence row to decay_ref's as
 uint32 bit patterns; "none" to the calls without a setting; every device loop to the host-driven loop of single steps; every caller to the
 plain loop. No tolerance anywhere: the new draw is the existing sampler on adjusted values."""

@@ -1,4 +1,4 @@
-"""Guided decoding (rwkv_mi_batch_guide_*; csrc/sampling.hip k_guided_sample_rows, k_guided_pen_sample_rows, k_guide_expand). Everything is
+"""Guided decoding (rwkv_mi_batch_guide_*; csrc/sampling.hip k_draw_rows<plain, 1, 1>, k_draw_rows<pen, 1, 1>, k_guide_expand). Everything is
 bit for bit. At the kernel level the oracle is the EXISTING sampler (rwkv_mi_test_sample_rows) on the same logits -- for the penalised entry
 the adjusted logits of tests/test_gpu_batch_penalty.py -- with -inf written at the positions the guide forbids. At the model level it is
 the host-driven loop a caller had to write before: per step, rwkv_mi_batch_logit_bias_set with -inf off the mask, one

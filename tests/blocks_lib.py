@@ -10,6 +10,9 @@ scale 2^-24 vanishes in f32 rounding, and a kernel that mishandles it would stil
   weight rows      code family x scale class of d (x scale class of m): weight_rows
   activation rows  one per family: activation_rows; token_operands rotates them over the tokens of a T-token operand
   model files      rewrite_quantised_blocks(path, model_palette(seed)): per block a seeded draw of a family (model_palette)
+  F16 matrices     rewrite_f16_matrices(path, f16_palette(seed)): per ELEMENT a seeded draw (emb, head, RWKV-7's low-rank stages; every matrix
+                   of an FP16 file). The kernel-level families of the unquantised products (F16 / F32 weight rows, f32 activation rows at the
+                   edges of binary16 and binary32) are in tests/fx_lib.py, held by tests/test_{cpu,gpu}_fx_extremes.py.
 
 No scale is inf or NaN (such a file is corrupt). Outside what is held (numerics): activations with amax / 127 > 65504, same-sign
 blocks whose fp16 block sum s_x overflows under Q4_1 / Q5_1 (constant 2000 is the largest constant row: s_x = 64000), and the CODES of
@@ -355,4 +358,110 @@ def write_palette_model(synth, path, name, fmt, seed):
         if "key-rows-zero" in c:
             assert c["key-rows-zero"] == 64 * synth.CONFIGS[name].n_embed // 32, (tensor, c)
     assert sum("key-rows-zero" in c for c in counts.values()) == 2, (name, fmt)
+    return counts
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# model files: the F16 matrices (every matrix of an FP16 file; emb, head and RWKV-7's low-rank stages of a quantised one)
+# ---------------------------------------------------------------------------------------------------------------------------------------
+
+def f16_matrices(path):
+    """[(name, dims, byte offset of the payload, payload bytes)] of the F16 2-D tensors of a model file."""
+    with open(path, "rb") as f:
+        blob = f.read()
+    out, p = [], 24
+    while p < len(blob):
+        nd, kl, ty = struct.unpack_from("<3I", blob, p)
+        p += 12
+        dims = struct.unpack_from(f"<{nd}I", blob, p)
+        p += 4 * nd
+        name = blob[p:p + kl].decode()
+        p += kl
+        n = int(np.prod(dims))
+        nbytes = n * 4 if ty == F.F32 else n * 2 if ty == F.F16 else (n // 32) * F.BLOCK_BYTES[ty]
+        if ty == F.F16 and nd == 2:
+            out.append((name, tuple(dims), p, nbytes))
+        p += nbytes
+    return out
+
+
+def rewrite_f16_matrices(path, fn):
+    """The counterpart of rewrite_quantised_blocks for the F16 2-D tensors of a written model file: for each,
+    fn(name, dims, w float16 (N, K)) -> float16 (N, K), or None (left alone), written over the old payload in place (a (K, N) tensor is N
+    rows of K elements). Returns {name: per-family element counts} for the tensors rewritten, as fn.counts[name] gives them."""
+    with open(path, "rb") as f:
+        blob = bytearray(f.read())
+    done = {}
+    for name, dims, at, nbytes in f16_matrices(path):
+        w = np.frombuffer(bytes(blob[at:at + nbytes]), dtype=np.float16).reshape(dims[1], dims[0])
+        new = fn(name, dims, w)
+        if new is None:
+            continue
+        assert new.dtype == np.float16 and new.shape == w.shape, (name, new.dtype, new.shape)
+        blob[at:at + nbytes] = np.ascontiguousarray(new).tobytes()
+        done[name] = dict(getattr(fn, "counts", {}).get(name, {}))
+    with open(path, "wb") as f:
+        f.write(blob)
+    return done
+
+
+F16_PALETTE = ("keep", "neg", "zero", "subnormal", "minnorm", "lowbits")
+
+
+def f16_palette(seed):
+    """The fn of rewrite_f16_matrices used at model level. Per ELEMENT, by a draw u ~ U(0, 1) seeded by (seed, tensor name):
+
+      u < .60   keep
+      u < .70   neg        w -> -w
+      u < .78   zero       +0 or -0
+      u < .88   subnormal  +-j 2^-24, j uniform in 1 .. 1023
+      u < .92   minnorm    2^-14, the smallest normal
+      rest      lowbits    +-s (1 + j 2^-10), j uniform in 0 .. 1023: every mantissa bit in use; s the largest power of two with 2 s <= the
+                           tensor's largest magnitude (tests/fx_lib.py has the family at s = 1; here no value may leave the tensor's range)
+    No value is inf or NaN or larger than the tensor's own largest magnitude, and no row is entirely zero (both asserted): logits stay finite.
+    fn.counts[name] holds the elements of every family of a tensor."""
+    def fn(name, dims, w):
+        rng = _rng(seed, "f16-palette", name)
+        shape, n = w.shape, w.size
+        w = w.reshape(n).copy()
+        top = float(np.abs(w.astype(np.float64)).max())
+        assert np.isfinite(top) and top >= 2.0 ** -13, (name, top)
+        u, neg, j = rng.random(n), rng.random(n) < 0.5, rng.integers(0, 1024, size=n)
+        sgn = np.where(neg, -1.0, 1.0)
+        fam = np.zeros(n, dtype=np.uint8)                               # index into F16_PALETTE
+        s = (u >= 0.60) & (u < 0.70)
+        fam[s] = 1
+        w[s] = -w[s]
+        s = (u >= 0.70) & (u < 0.78)
+        fam[s] = 2
+        w[s] = (0.0 * sgn[s]).astype(np.float16)
+        s = (u >= 0.78) & (u < 0.88)
+        fam[s] = 3
+        w[s] = (sgn[s] * np.maximum(j[s], 1) * SUB).astype(np.float16)
+        s = (u >= 0.88) & (u < 0.92)
+        fam[s] = 4
+        w[s] = np.float16(2.0 ** -14)
+        s = u >= 0.92
+        fam[s] = 5
+        scale = 2.0 ** (np.floor(np.log2(top)) - 1)
+        w[s] = (sgn[s] * scale * (1.0 + j[s] * 2.0 ** -10)).astype(np.float16)
+        w64 = w.astype(np.float64)
+        assert np.isfinite(w64).all() and np.abs(w64).max() <= top, (name, float(np.abs(w64).max()), top)
+        assert np.abs(w64.reshape(shape)).max(axis=1).min() > 0, (name, "a row is entirely zero")
+        fn.counts[name] = dict(zip(F16_PALETTE, (int(c) for c in np.bincount(fam, minlength=len(F16_PALETTE)))))
+        return w.reshape(shape)
+    fn.counts = {}
+    return fn
+
+
+def write_f16_palette_model(synth, path, name, fmt, seed):
+    """Writes synth.CONFIGS[name] as `fmt` and redraws its F16 matrices with f16_palette(seed); the quantised blocks (and the f32 tensors)
+    stay as synth wrote them, so a failure points at F16. Every family must occur in every rewritten tensor (asserted). Returns
+    {tensor: counts}."""
+    synth.write_model(path, synth.CONFIGS[name], fmt, seed=seed)
+    want = [t[0] for t in f16_matrices(path)]
+    counts = rewrite_f16_matrices(path, f16_palette(seed))
+    assert {"emb.weight", "head.weight"} <= set(want) and list(counts) == want, (name, fmt, want, list(counts))
+    for tensor, c in counts.items():
+        assert set(c) == set(F16_PALETTE) and min(c.values()) >= 1, (name, fmt, tensor, c)
     return counts

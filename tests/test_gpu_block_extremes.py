@@ -219,7 +219,7 @@ def test_probe_matrix_reads_back_the_activation_codes(T):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
-# model level
+# model level (the four _check_* bodies and _Reference also serve tests/test_gpu_fx_extremes.py, on files whose F16 matrices are redrawn)
 # ---------------------------------------------------------------------------------------------------------------------------------------
 
 N_SEQ, CHUNK, N_ABI, N_GREEDY, FIRST = 40, 33, 4, 6, 5
@@ -288,7 +288,10 @@ def files(tmp_path_factory):
 
 @pytest.mark.parametrize("key,paths", CASES, ids=IDS)
 def test_eval_on_palette_blocks_on_every_path(files, key, paths):
-    path, ref = files(key)
+    _check_eval_on_every_path(*files(key), key, paths)
+
+
+def _check_eval_on_every_path(path, ref, key, paths):
     for label, *_ in paths:
         m = _open(path, paths, label)
         st = None
@@ -302,7 +305,10 @@ def test_eval_on_palette_blocks_on_every_path(files, key, paths):
 
 @pytest.mark.parametrize("key,paths", CASES, ids=IDS)
 def test_decode_greedy_on_palette_blocks_on_every_path(files, key, paths):
-    path, ref = files(key)
+    _check_decode_greedy_on_every_path(*files(key), key, paths)
+
+
+def _check_decode_greedy_on_every_path(path, ref, key, paths):
     for label, *_ in paths:
         m = _open(path, paths, label)
         want, ost = ref.greedy
@@ -316,7 +322,10 @@ def test_decode_greedy_on_palette_blocks_on_every_path(files, key, paths):
 
 @pytest.mark.parametrize("key,paths", CASES, ids=IDS)
 def test_sequence_kernels_on_palette_blocks(files, key, paths):
-    path, ref = files(key)
+    _check_sequence_kernels(*files(key), key, paths)
+
+
+def _check_sequence_kernels(path, ref, key, paths):
     m = _open(path, paths, "top")
     ol, ost = ref.seq
     for what, (lg, st) in (("eval_sequence", m.eval_sequence(ref.tokens, None)),
@@ -328,7 +337,10 @@ def test_sequence_kernels_on_palette_blocks(files, key, paths):
 
 @pytest.mark.parametrize("key,paths", CASES, ids=IDS)
 def test_rows_and_segments_on_palette_blocks(files, key, paths):
-    path, ref = files(key)
+    _check_rows_and_segments(*files(key), key, paths)
+
+
+def _check_rows_and_segments(path, ref, key, paths):
     m = _open(path, paths, "top")
     V, slots = ref.V, list(range(len(SEG_LENS)))
     b = pkg.RWKVBatch(m, len(slots))

@@ -589,6 +589,59 @@ RWKV_API bool rwkv_mi_repetition_set(struct rwkv_context * ctx, float decay, flo
 RWKV_API bool rwkv_mi_repetition_get(struct rwkv_context * ctx, float * decay_out, float * repetition_out);
 RWKV_API bool rwkv_mi_counts_store_f32(struct rwkv_context * ctx, float * out /* [n_vocab] */);
 
+/* ---- Continuous batching: a queue of requests behind the lanes of one device loop ----
+ * rwkv_mi_batch_decode_until runs n rows until the slowest has ended; a row that has retired recomputes a dead step on every pass.
+ * rwkv_mi_batch_serve takes n LANES (distinct slots of the batch) and a queue of n_requests >= n REQUESTS, all known at the call; when the
+ * request of a lane retires, the next request not yet taken has the lane from the next pass on, decided on the device.
+ * A request q carries: its prompt, prompt_len >= 1 tokens, the requests' prompts back to back in prompt_tokens; from_slot, a slot of the batch
+ * that is NOT a lane of the call, whose current state the request starts from (RWKV_MI_NO_SLOT: the fresh state; from_slot is only read: many
+ * requests may share a system prompt evaluated once); its draw settings -- `sample` (family sample and penalised; u is not read: the
+ * generator draws), `penalty` (penalised; record is not read: every draw records), top_k / min_p (rwkv_mi_batch_truncation_set's, {0, 0}:
+ * none) and decay / repetition (rwkv_mi_batch_repetition_set's, read by the penalised family, {1, 1}: none); its budget and stop sequences,
+ * `stop`, the requests' sequences back to back in seq_lens / seq_tokens as for rwkv_mi_batch_decode_until. The family is the call's.
+ * SCHEDULE: lane r starts with request r. A lane whose request retires after pass i serves the next request not yet taken from pass i + 1 on;
+ * lanes that retire in the same pass take requests in ascending lane order. The assignment is a function of the requests' lengths alone. A
+ * lane feeds its prompt one token per pass and draws nothing until the pass that fed the last prompt token; from then on it is a row of
+ * rwkv_mi_batch_decode_until. Prompt tokens are not counted in the occurrence table. At an admission the lane's draw counter becomes 0 and its
+ * occurrence row zero. With the queue empty a retiring lane goes dead; the call ends when no lane has work (blocks of RWKV_MI_LOOP_BLOCK
+ * passes, as rwkv_mi_batch_decode_until), and never enqueues more than sum(prompt_len - 1 + max_tokens) passes.
+ * THE GUARANTEE: for every request q, tokens_out[q][0 .. lens_out[q]), lens_out[q] and stopped_by_out[q] are, bit for bit, what these calls
+ * give on a batch of one slot: load the fresh state or from_slot's; rwkv_mi_batch_rng_seek 0 and _counts_reset; set the request's truncation and
+ * repetition settings; rwkv_mi_batch_eval of prompt[0 .. prompt_len - 1); rwkv_mi_batch_decode_until of the family with first_token =
+ * prompt[prompt_len - 1] and the request's parameters -- whoever else was in the queue. After the call lane r holds, bit for bit, what those
+ * calls leave for request last_request_out[r]: state (and the batch's parity for it), draw counter and occurrence row. The lane slots' own
+ * truncation / repetition settings are neither read nor changed: to continue a request on its lane, set them to the request's (a lane slot
+ * that is to continue a decaying request must have been decaying before the call: a set that changes that zeroes the row).
+ * Outputs: tokens_out [n_requests][stride] (RWKV_MI_NO_TOKEN past a request's length), lens_out, stopped_by_out (as rwkv_mi_batch_decode_until),
+ * lane_out[q] the lane (index into lanes) that served q, start_pass_out[q] the pass that fed its first prompt token, last_request_out[r] the
+ * last request lane r was given; rwkv_mi_batch_last_loop_passes: the passes enqueued.
+ * REJECTED with RWKV_ERROR_ARGS, nothing changed: lanes, requests, prompt_tokens or lens_out NULL; n not in 1 .. n_slots, a lane out of range
+ * or named twice; n_requests < n; an unknown family; a prompt_len of 0; a prompt token >= n_vocab; a from_slot that is a lane or out of
+ * range; a lane with a guide attached or a bias set; a batch with the log-prob report on; and everything rwkv_mi_batch_decode_until,
+ * rwkv_mi_batch_truncation_set and rwkv_mi_batch_repetition_set reject for the same fields. The buffers are allocated by the first call
+ * (RWKV_ERROR_ALLOC when they cannot be) and released by rwkv_mi_batch_free. A failure after the first pass leaves the lanes unspecified.
+ * OUT OF SCOPE: guides, bias and the report for served requests; chunked prompt ingestion inside the loop (take a long prompt in with
+ * rwkv_mi_batch_eval_ragged into a from_slot); requests that arrive during the call; compacting dead lanes. */
+#define RWKV_MI_NO_SLOT          UINT32_MAX
+#define RWKV_MI_SERVE_GREEDY     0
+#define RWKV_MI_SERVE_SAMPLE     1
+#define RWKV_MI_SERVE_PENALIZED  2
+struct rwkv_mi_serve_request {            /* 72 bytes */
+    uint32_t prompt_len; uint32_t from_slot;
+    struct rwkv_mi_sample_params sample;
+    struct rwkv_mi_penalty_params penalty;
+    uint32_t top_k; float min_p; float decay; float repetition;
+    struct rwkv_mi_stop_params stop;
+    uint32_t reserved;                    /* 0 */
+};
+RWKV_API bool rwkv_mi_batch_serve(struct rwkv_mi_batch * batch, const uint32_t * lanes /* [n] slots */, size_t n, int family,
+                                  const struct rwkv_mi_serve_request * requests /* [n_requests] */, size_t n_requests,
+                                  const uint32_t * prompt_tokens /* sum(prompt_len) words */, const uint32_t * seq_lens, const uint32_t * seq_tokens,
+                                  size_t stride, uint32_t * tokens_out /* [n_requests][stride], may be NULL */, uint32_t * lens_out /* [n_requests] */,
+                                  uint32_t * stopped_by_out /* [n_requests], may be NULL */, uint32_t * lane_out /* [n_requests], may be NULL */,
+                                  uint32_t * start_pass_out /* [n_requests], may be NULL */, uint32_t * last_request_out /* [n], may be NULL */,
+                                  float * elapsed_ms /* may be NULL */);
+
 #if defined(__cplusplus)
 }
 #endif

@@ -1138,6 +1138,12 @@ struct rwkv_mi_batch {
     DevBuf<DraftLayer> d_draft_layers;
     DevBuf<uint32_t> d_draft_words;
     PinBuf<uint32_t> h_draft_words;
+    // rwkv_mi_batch_serve: the words of a call -- the request table, prompts, stop sequences, lane and request words, the emitted tokens -- in
+    // one device buffer with its pinned staging, laid out by ServeLayout and grown to the largest call so far; the fresh state every request
+    // without a from_slot starts from, filled once -- allocated by the first call, as are h_live_count and ev_block above where no other loop has
+    DevBuf<uint8_t> d_serve;
+    PinBuf<uint8_t> h_serve;
+    DevBuf<float> serve_fresh;          // [state_len]
     LogprobReport lp;                   // the report of the batch's emitting calls (rwkv_mi_batch_set_logprobs)
 
     float * slot_buf(size_t slot, int p) const { return states.p + ((size_t) p * n_slots + slot) * (size_t) state_len; }
@@ -1178,6 +1184,12 @@ struct BatchCall {
     size_t stride = 0;
     uint32_t * lens_out = nullptr;
     uint32_t * stopped_by_out = nullptr;
+    // rwkv_mi_batch_serve (batch_serve is its body): slots are the call's lanes, tokens is unused; the queue of n_requests requests with their
+    // prompts back to back, their sequences in seq_lens / seq_tokens; tokens_out, lens_out and stopped_by_out are per request
+    const rwkv_mi_serve_request * requests = nullptr;
+    size_t n_requests = 0;
+    const uint32_t * prompts = nullptr;
+    uint32_t * lane_out = nullptr, * start_pass_out = nullptr, * last_request_out = nullptr;
 };
 
 // the batch's report buffers (batch_ensure_report has sized them for the call)
@@ -1697,6 +1709,220 @@ static bool batch_until(rwkv_mi_batch * B, const BatchCall & c, uint32_t * token
     return true;
 }
 
+// ---- continuous batching (rwkv_mi_batch_serve) ----
+
+// Where the words of a call of n lanes and R requests lie in the serve buffer (byte offsets). What goes up: the request table, the prompts and
+// the sequences, the lane words in their start values, the head of the queue and the work count. From `down` on, what comes back as well: the
+// lanes' last requests, the requests' lengths, reasons, lanes and start passes, and their emitted tokens out[R][stride] (filled on the device).
+struct ServeLayout {
+    size_t reqs, prompts, seq_lens, seq_tokens, lane_slot, req, pos, draw, admit, next, work, down, last, lens, reasons, lane, start, out, bytes;
+    ServeLayout(size_t n, size_t R, size_t n_prompt, size_t n_seqs, size_t n_toks, size_t stride) {
+        size_t o = 0;
+        auto take = [&o](size_t b) { const size_t at = o; o += b; return at; };
+        reqs = take(R * sizeof(ServeReq));
+        prompts = take(n_prompt * 4); seq_lens = take(n_seqs * 4); seq_tokens = take(n_toks * 4);
+        lane_slot = take(n * 4); req = take(n * 4); pos = take(n * 4); draw = take(n * 4); admit = take(n * 4);
+        next = take(4); work = take(4);
+        down = o;
+        last = take(n * 4); lens = take(R * 4); reasons = take(R * 4); lane = take(R * 4); start = take(R * 4);
+        out = take(R * stride * 4);
+        bytes = o;
+    }
+};
+
+// every argument of a serve call, nothing changed yet. *n_prompt_out = the prompt tokens of the queue
+static bool batch_check_serve(rwkv_mi_batch * B, const BatchCall & c, size_t * n_prompt_out) {
+    rwkv_context * ctx = B->ctx;
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, c.slots != nullptr && c.requests != nullptr && c.prompts != nullptr && c.lens_out != nullptr,
+                 "lanes, requests, prompt_tokens or lens_out is NULL");
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, c.n > 0 && c.n <= B->n_slots, "n (%zu) must be in 1 .. %zu", c.n, B->n_slots);
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, c.n_requests >= c.n && c.n_requests < (size_t) SERVE_FREE, "n_requests (%zu) is below the %zu lanes (or above 2^32 - 3)", c.n_requests, c.n);
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, !B->lp.enabled, "rwkv_mi_batch_serve takes no batch with the log-prob report on");
+    std::vector<uint8_t> is_lane(B->n_slots, 0);
+    for (size_t i = 0; i < c.n; i++) {
+        const uint32_t s = c.slots[i];
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, s < B->n_slots, "lane slot %" PRIu32 " at index %zu is out of range (0 .. %zu)", s, i, B->n_slots - 1);
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, !is_lane[s], "lane slot %" PRIu32 " appears twice", s);
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, B->draw.guide_of[s] == RWKV_MI_NO_GUIDE && !B->draw.has_bias[s], "lane slot %" PRIu32 " has a guide attached or a bias set", s);
+        is_lane[s] = 1;
+    }
+    const size_t R = c.n_requests, n_vocab = (size_t) ctx->model->n_vocab();
+    std::vector<rwkv_mi_sample_params> sp(R);
+    std::vector<rwkv_mi_penalty_params> pp(R);
+    std::vector<rwkv_mi_stop_params> st(R);
+    uint64_t P = 0;
+    for (size_t q = 0; q < R; q++) {
+        const rwkv_mi_serve_request & rq = c.requests[q];
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, rq.prompt_len > 0, "the prompt of request %zu is empty", q);
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, rq.from_slot == RWKV_MI_NO_SLOT || (rq.from_slot < B->n_slots && !is_lane[rq.from_slot]),
+                     "from_slot of request %zu (%" PRIu32 ") is a lane of the call or out of range", q, rq.from_slot);
+        P += rq.prompt_len;
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, P <= (uint64_t) INT32_MAX, "the prompts add up to more than %d tokens", INT32_MAX);
+        // (the rules of DrawState::cut_set and rep_set, written so that a NaN fails each comparison)
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, rq.min_p >= 0.0f && rq.min_p <= 1.0f, "min_p of request %zu (%g) must be in 0 .. 1", q, (double) rq.min_p);
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, rq.decay >= 0.0f && rq.decay <= 1.0f, "decay of request %zu (%g) must be in 0 .. 1", q, (double) rq.decay);
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, rq.repetition > 0.0f && rq.repetition < INFINITY, "repetition of request %zu (%g) must be finite and above 0", q, (double) rq.repetition);
+        sp[q] = rq.sample; pp[q] = rq.penalty; st[q] = rq.stop;
+    }
+    for (size_t t = 0; t < (size_t) P; t++)
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, c.prompts[t] < n_vocab, "Prompt token at index %zu (%" PRIu32 ") is out of range (0 .. %zu)", t, c.prompts[t], n_vocab - 1);
+    if (c.draw != Draw::none && !batch_check_params(B, sp.data(), R, false)) return false;
+    if (c.draw == Draw::penalized && !batch_check_penalties(B, pp.data(), R)) return false;
+    BatchCall s = c;   // the requests' budgets and sequences, by the rules of rwkv_mi_batch_decode_until
+    s.n = R; s.stops = st.data();
+    if (!batch_check_stops(B, s)) return false;
+    *n_prompt_out = (size_t) P;
+    return true;
+}
+
+// the serve buffer for `bytes`, and on the first call the fresh state and the two block events with their pinned counts: one decision
+static bool batch_ensure_serve(rwkv_mi_batch * B, size_t bytes) {
+    rwkv_context * ctx = B->ctx;
+    const Model & m = *ctx->model;
+    hipStream_t st = B->run->stream;
+    const bool more = bytes > B->d_serve.count, first = !B->serve_fresh;
+    if (more) BATCH_HIP_OK(B, hipStreamSynchronize(st));   // (an earlier call may still read the old one)
+    hipError_t e = grow(want(B->d_serve, more ? bytes : 0), want(B->h_serve, more ? bytes : 0), want(B->serve_fresh, first ? (size_t) B->state_len : 0),
+                        want(B->h_live_count, B->h_live_count ? 0 : 2));
+    for (hipEvent_t & ev : B->ev_block) if (e == hipSuccess && !ev) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    if (e != hipSuccess) (void) hipGetLastError();
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the serve tables (%zu bytes): %s", bytes, hipGetErrorString(e));
+    if (first) {
+        if (m.arch_major >= 5) e = hipMemsetAsync(B->serve_fresh.p, 0, (size_t) B->state_len * sizeof(float), st);
+        else { launch_fill_state_v4(B->serve_fresh.p, m.n_layer(), m.n_embed(), st); e = hipGetLastError(); }
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) B->serve_fresh.reset();   // (a fresh state that could not be filled is not kept)
+        BATCH_HIP_OK(B, e);
+    }
+    return true;
+}
+
+// workgroups per lane of k_serve_reset: one per 128 KiB of state, at most 256
+static unsigned serve_chunks(int64_t state_len) {
+    const int64_t c = (state_len * (int64_t) sizeof(float) + (128 << 10) - 1) / (128 << 10);
+    return (unsigned) std::min<int64_t>(std::max<int64_t>(c, 1), 256);
+}
+
+// The device loop with a queue behind it (rwkv_mi_batch_serve): batch_until's passes and blocks, the draw behind the lanes' DRAW words and
+// followed by the scheduler (engine.hip launch_row_sampler; sampling.hip k_serve_rows, k_serve_reset), which emits, feeds prompts, retires and
+// admits ON THE DEVICE: between two passes it rewrites a lane's token word, draw row and words and has the request's start state copied into
+// the buffer the lane's next pass reads. The model's kernels never learn of it. The admission in front of pass 0 is the same two kernels.
+// The host polls the number of lanes with work as batch_until polls its live rows, and never enqueues more passes than the queue can need.
+static bool batch_serve(rwkv_mi_batch * B, const BatchCall & c, uint32_t * tokens_out, float * elapsed_ms) {
+    rwkv_context * ctx = B->ctx;
+    rwkv_context * run = B->run;
+    size_t n_prompt = 0;
+    if (!batch_check_serve(B, c, &n_prompt)) return false;
+    run->print_errors = ctx->print_errors;
+    const Model & m = *ctx->model;
+    const size_t n = c.n, R = c.n_requests, K = loop_block(), n_vocab = (size_t) m.n_vocab();
+    const bool pen = c.draw == Draw::penalized;
+    size_t n_seqs = 0, n_toks = 0, bound = 0;
+    bool any_cut = false, any_rep = false;
+    for (size_t q = 0; q < R; q++) {
+        const rwkv_mi_serve_request & rq = c.requests[q];
+        n_seqs += rq.stop.n_seqs;
+        bound += (size_t) rq.prompt_len - 1 + rq.stop.max_tokens;   // (a lane with work advances its request by one pass: no schedule needs more)
+        any_cut |= (rq.top_k != 0u && rq.top_k < n_vocab) || rq.min_p != 0.0f;
+        any_rep |= rq.decay != 1.0f || rq.repetition != 1.0f;
+    }
+    for (size_t s = 0; s < n_seqs; s++) n_toks += c.seq_lens[s];
+    BATCH_HIP_OK(B, hipSetDevice(m.device));
+    BatchCall lanes{c.slots, nullptr, n};
+    lanes.draw = c.draw;
+    if (!batch_ensure_draw(B, lanes)) return false;   // (the draw buffers of the family; the form it derives from the lanes' own settings ...)
+    B->form = DrawForm::of(c.draw, any_cut, false, any_rep);   // (... is not the call's: the requests carry theirs)
+    const ServeLayout L(n, R, n_prompt, n_seqs, n_toks, c.stride);
+    if (!batch_ensure_serve(B, L.bytes)) return false;
+    BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));   // (the previous call's copies may still read the staging)
+    uint8_t * h = B->h_serve.p, * d = B->d_serve.p;
+    auto hw = [h](size_t off) { return (uint32_t *) (h + off); };
+    auto dw = [d](size_t off) { return (uint32_t *) (d + off); };
+    ServeReq * reqs = (ServeReq *) (h + L.reqs);
+    size_t p0 = 0, s0 = 0, t0 = 0;
+    for (size_t q = 0; q < R; q++) {
+        const rwkv_mi_serve_request & rq = c.requests[q];
+        // (the row of DrawState::row for a loop: the generator draws, every penalised draw records; the counter and the occurrence row are the
+        //  lane's, which the scheduler fills in)
+        DrawRow row{};
+        row.p = rq.sample; row.p.u = -1.0f;
+        row.presence = pen ? rq.penalty.presence : 0.0f; row.frequency = pen ? rq.penalty.frequency : 0.0f; row.record = pen ? 1u : 0u;
+        row.top_k = rq.top_k; row.min_p = rq.min_p; row.decay = rq.decay; row.repetition = rq.repetition;
+        const float * start = rq.from_slot == RWKV_MI_NO_SLOT ? B->serve_fresh.p : B->slot_buf(rq.from_slot, B->parity[rq.from_slot]);
+        reqs[q] = ServeReq{row, StopRow{rq.stop.max_tokens, rq.stop.n_seqs, (uint32_t) s0, (uint32_t) t0}, rq.prompt_len, (uint32_t) p0, start};
+        p0 += rq.prompt_len;
+        for (uint32_t s = 0; s < rq.stop.n_seqs; s++) t0 += c.seq_lens[s0 + s];
+        s0 += rq.stop.n_seqs;
+    }
+    memcpy(h + L.prompts, c.prompts, n_prompt * 4);
+    if (n_seqs) memcpy(h + L.seq_lens, c.seq_lens, n_seqs * 4);
+    if (n_toks) memcpy(h + L.seq_tokens, c.seq_tokens, n_toks * 4);
+    for (size_t r = 0; r < n; r++) {
+        hw(L.lane_slot)[r] = c.slots[r]; hw(L.req)[r] = SERVE_FREE; hw(L.pos)[r] = 0u; hw(L.draw)[r] = 0u; hw(L.admit)[r] = 0u; hw(L.last)[r] = RWKV_MI_NO_TOKEN;
+        for (int tb = 0; tb < 2; tb++) {
+            const int p = B->parity[c.slots[r]] ^ tb;
+            B->h_rows.p[(size_t) tb * B->n_slots + r] = RowState{B->slot_buf(c.slots[r], p), B->slot_buf(c.slots[r], p ^ 1)};
+        }
+    }
+    *hw(L.next) = 0u; *hw(L.work) = (uint32_t) n;
+    for (size_t q = 0; q < R; q++) { hw(L.lens)[q] = 0u; hw(L.reasons)[q] = RWKV_MI_NO_TOKEN; hw(L.lane)[q] = RWKV_MI_NO_TOKEN; hw(L.start)[q] = RWKV_MI_NO_TOKEN; }
+    BATCH_HIP_OK(B, hipMemcpyAsync(d, h, L.out, hipMemcpyHostToDevice, run->stream));
+    BATCH_HIP_OK(B, hipMemsetAsync(d + L.out, 0xFF, R * c.stride * 4, run->stream));
+    for (int tb = 0; tb < 2; tb++)
+        BATCH_HIP_OK(B, hipMemcpyAsync(B->d_rows.p + (size_t) tb * B->n_slots, B->h_rows.p + (size_t) tb * B->n_slots, n * sizeof(RowState), hipMemcpyHostToDevice, run->stream));
+    RowServe serve{};
+    serve.t = ServeTables{(const ServeReq *) (d + L.reqs), dw(L.prompts), dw(L.seq_lens), dw(L.seq_tokens), dw(L.out), (uint32_t) c.stride,
+                          dw(L.lens), dw(L.reasons), dw(L.lane), dw(L.start), dw(L.req), dw(L.pos), dw(L.draw), dw(L.admit), dw(L.last), dw(L.lane_slot),
+                          c.draw != Draw::none ? B->d_draw_rows.p : nullptr, B->draw.counters.p, B->draw.counts.p, dw(L.next), dw(L.work),
+                          (uint32_t) R, (uint32_t) n_vocab};
+    serve.state_len = B->state_len; serve.chunks = serve_chunks(B->state_len);
+    RowState * const table[2] = {B->d_rows.p, B->d_rows.p + B->n_slots};
+    BATCH_HIP_OK(B, hipEventRecord(run->ev0, run->stream));
+    // lane r takes request r: the admission in front of pass 0 copies into what table[1] writes, which is what pass 0 reads
+    launch_serve_rows(serve.t, (int64_t) n, run->d_tokens.p, UINT32_MAX, table[1], table[0], run->stream);
+    launch_serve_reset(serve.t, (int64_t) n, serve.chunks, table[1], serve.state_len, run->stream);
+    RowSampler sampler = batch_sampler(B, nullptr, nullptr);
+    sampler.serve = &serve;
+    size_t passes = 0;
+    for (size_t b = 0; passes < bound; b++) {
+        for (const size_t end = std::min(bound, passes + K); passes < end; passes++) {
+            serve.used = table[passes & 1]; serve.other = table[(passes & 1) ^ 1];
+            sampler.step = (uint32_t) passes;
+            if (!forward_rows(run, serve.used, (int64_t) n, true, &sampler)) return batch_fail_drained(B);
+        }
+        hipError_t e = hipMemcpyAsync(B->h_live_count.p + (b & 1), serve.t.work, sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream);
+        if (e == hipSuccess) e = hipEventRecord(B->ev_block[b & 1], run->stream);
+        if (e == hipSuccess && b > 0) e = hipEventSynchronize(B->ev_block[(b - 1) & 1]);
+        if (e != hipSuccess) { (void) hipStreamSynchronize(run->stream); BATCH_HIP_OK(B, e); }
+        if (b > 0 && B->h_live_count.p[(b - 1) & 1] == 0) break;
+    }
+    BATCH_HIP_OK(B, hipEventRecord(run->ev1, run->stream));
+    BATCH_HIP_OK(B, hipMemcpyAsync(h + L.down, d + L.down, L.bytes - L.down, hipMemcpyDeviceToHost, run->stream));
+    BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));
+    if (elapsed_ms) BATCH_HIP_OK(B, hipEventElapsedTime(elapsed_ms, run->ev0, run->ev1));
+    B->last_loop_passes = passes;
+    const uint32_t * lens = hw(L.lens), * reasons = hw(L.reasons), * lane = hw(L.lane), * start = hw(L.start), * last = hw(L.last), * out = hw(L.out);
+    // (the queue's work fits the bound, and the loop ends on a work count of 0 or at the bound: every request has been served to its end)
+    for (size_t q = 0; q < R; q++)
+        RW_CTX_CHECK(ctx, RWKV_ERROR_GRAPH, false, lane[q] < n && lens[q] > 0 && lens[q] <= c.requests[q].stop.max_tokens &&
+                     (reasons[q] != RWKV_MI_NO_TOKEN || lens[q] == c.requests[q].stop.max_tokens), "request %zu did not end (the device loop failed)", q);
+    for (size_t r = 0; r < n; r++) RW_CTX_CHECK(ctx, RWKV_ERROR_GRAPH, false, last[r] < R, "lane %zu served no request (the device loop failed)", r);
+    for (size_t q = 0; q < R; q++) {
+        c.lens_out[q] = lens[q];
+        if (c.stopped_by_out) c.stopped_by_out[q] = reasons[q];
+        if (c.lane_out) c.lane_out[q] = lane[q];
+        if (c.start_pass_out) c.start_pass_out[q] = start[q];
+        if (tokens_out) memcpy(tokens_out + q * c.stride, out + q * c.stride, c.stride * 4);
+    }
+    for (size_t r = 0; r < n; r++) {
+        // the lane ran one pass after the other from pass 0 to the last one of its last request: that many times its buffers changed places
+        const size_t q = last[r], ran = (size_t) start[q] + c.requests[q].prompt_len - 1 + lens[q];
+        if (c.last_request_out) c.last_request_out[r] = (uint32_t) q;
+        if (ran & 1) B->parity[c.slots[r]] ^= 1;
+    }
+    return true;
+}
+
 // ---- beam search (rwkv_mi_batch_decode_beam) ----
 
 // a call of G groups of W hypotheses: row g * W + j is slot slots[g * W + j]
@@ -2108,6 +2334,23 @@ RWKV_API bool rwkv_mi_batch_decode_until(struct rwkv_mi_batch * B, const uint32_
 }
 
 RWKV_API size_t rwkv_mi_batch_last_loop_passes(const struct rwkv_mi_batch * B) { return B ? B->last_loop_passes : 0; }
+
+RWKV_API bool rwkv_mi_batch_serve(struct rwkv_mi_batch * B, const uint32_t * lanes, size_t n, int family, const struct rwkv_mi_serve_request * requests,
+                                  size_t n_requests, const uint32_t * prompt_tokens, const uint32_t * seq_lens, const uint32_t * seq_tokens, size_t stride,
+                                  uint32_t * tokens_out, uint32_t * lens_out, uint32_t * stopped_by_out, uint32_t * lane_out, uint32_t * start_pass_out,
+                                  uint32_t * last_request_out, float * elapsed_ms) {
+    B->ctx->last_error = RWKV_ERROR_NONE;
+    RW_NO_PIPELINE(B->ctx, false);
+    RW_CTX_CHECK(B->ctx, RWKV_ERROR_ARGS, false, family == RWKV_MI_SERVE_GREEDY || family == RWKV_MI_SERVE_SAMPLE || family == RWKV_MI_SERVE_PENALIZED,
+                 "unknown family (%d)", family);
+    BatchCall c{lanes, nullptr, n};
+    c.draw = family == RWKV_MI_SERVE_PENALIZED ? Draw::penalized : family == RWKV_MI_SERVE_SAMPLE ? Draw::sample : Draw::none;
+    c.requests = requests; c.n_requests = n_requests; c.prompts = prompt_tokens;
+    c.seq_lens = seq_lens; c.seq_tokens = seq_tokens;
+    c.stride = stride; c.lens_out = lens_out; c.stopped_by_out = stopped_by_out;
+    c.lane_out = lane_out; c.start_pass_out = start_pass_out; c.last_request_out = last_request_out;
+    return batch_serve(B, c, tokens_out, elapsed_ms);
+}
 
 RWKV_API bool rwkv_mi_batch_eval_draft(struct rwkv_mi_batch * B, const uint32_t * slots, const uint32_t * lens, const uint32_t * tokens, size_t n,
                                        const struct rwkv_mi_sample_params * params, const struct rwkv_mi_penalty_params * penalties,

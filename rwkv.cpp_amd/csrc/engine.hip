@@ -858,6 +858,15 @@ void launch_row_sampler(rwkv_context * ctx, const RowSampler & s, int64_t rows) 
         launch_beam_select(s.beam->t, rows / (int64_t) s.beam->t.width, tokens, s.step, s.beam->used, s.beam->other, ctx->stream);
         return;
     }
+    if (const RowServe * sv = s.serve) {
+        // a step of rwkv_mi_batch_serve: the family's choice behind the lanes' draw words (no history: the scheduler appends the token to its
+        // request's row), then the scheduler, then the admissions it decided
+        if (s.form.draw != Draw::none) launch_draw_rows(logits, rows, n_vocab, s.rows, s.form, s.probs, tokens, nullptr, sv->t.draw, ctx->stream);
+        else launch_argmax_live(logits, rows, n_vocab, tokens, nullptr, sv->t.draw, ctx->stream);
+        launch_serve_rows(sv->t, rows, tokens, s.step, sv->used, sv->other, ctx->stream);
+        launch_serve_reset(sv->t, rows, sv->chunks, sv->used, sv->state_len, ctx->stream);
+        return;
+    }
     const size_t at = (size_t) s.step * (size_t) rows;   // the step's slot of the call's history and report buffers
     uint32_t * hist = s.hist ? s.hist + at : nullptr;
     const uint32_t * live = s.stop ? s.stop->t.live : nullptr;   // (rwkv_mi_batch_decode_until: everything but the stop test runs behind the live words)

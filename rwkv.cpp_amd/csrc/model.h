@@ -188,6 +188,34 @@ struct StopTables { const StopRow * rows; const uint32_t * seq_lens, * seq_token
 // whose budget is step + 1. A retired row gets {in = what pass `step` wrote, out = its other buffer} in both row tables (used: the table of
 // pass `step`, other: the one of pass step + 1).
 void launch_stop_rows(const StopTables & t, int64_t rows, const uint32_t * hist, uint32_t step, RowState * used, RowState * other, hipStream_t st);
+// rwkv_mi_batch_serve (sampling.hip, k_serve_rows / k_serve_reset): a queue of requests behind the n lanes of a call. A request as the device
+// reads it: its draw row -- the request's settings; the counter and the occurrence row are the LANE's, patched in at admission -- its stop row,
+// its prompt (prompt_len tokens at prompts[prompt0 ..]) and the buffer its start state is copied from.
+struct ServeReq { DrawRow row; StopRow stop; uint32_t prompt_len, prompt0; const float * start; };
+// The device words of a call. Per request: its emitted tokens out[q][stride], its length (it grows with every token), its reason, its lane and
+// the pass that fed its first prompt token. Per lane: the request it serves (SERVE_FREE: it waits for one -- only between the two halves of
+// k_serve_rows, and before the first pass; RWKV_MI_NO_TOKEN: dead), the prompt tokens it has been fed, its DRAW WORD (1: the logits of the
+// coming pass are drawn from -- the `live` argument of the draw kernels), its admit word (1: k_serve_reset has a state to copy), the last
+// request it was given, and its slot. rows: the draw table of the lanes (NULL: the greedy family); counters / counts: the batch's, indexed by
+// slot (counts NULL: the batch has no occurrence tables). next_request: the head of the queue, written by k_serve_rows alone; work: the lanes
+// that are not dead, which the host polls.
+constexpr uint32_t SERVE_FREE = 0xFFFFFFFEu;
+struct ServeTables {
+    const ServeReq * reqs; const uint32_t * prompts, * seq_lens, * seq_tokens;
+    uint32_t * out; uint32_t stride;
+    uint32_t * lens, * reasons, * lane, * start_pass;
+    uint32_t * req, * pos, * draw, * admit, * last; const uint32_t * lane_slot;
+    DrawRow * rows; unsigned long long * counters; uint32_t * counts;
+    uint32_t * next_request, * work;
+    uint32_t n_requests, n_vocab;
+};
+// After the draw of pass `step` over the n lanes (tokens: the lanes' token words; used: the row table of that pass, other: the one of pass
+// step + 1): every lane emits, advances its prompt, retires, admits or goes dead. step == UINT32_MAX with used = the table of pass 1: the
+// admission in front of pass 0.
+void launch_serve_rows(const ServeTables & t, int64_t n, uint32_t * tokens, uint32_t step, RowState * used, RowState * other, hipStream_t st);
+// Behind it: lanes x chunks workgroups; those of an admitted lane copy the request's start state into used[lane].out -- the buffer the lane's
+// next pass reads -- and zero its occurrence row
+void launch_serve_reset(const ServeTables & t, int64_t n, unsigned chunks, const RowState * used, int64_t state_len, hipStream_t st);
 // rwkv_mi_batch_decode_beam (score.hip): the device words of a call of G groups of `width` hypotheses, row g * width + j = hypothesis j of group g.
 // Per row its cumulative score (double), its finished word, its length; the candidates of the step -- cand_ids / cand_lp [rows][width], the
 // report's top-`width` of the row's logits -- and the word the shared body writes its unused `chosen` to; the history [steps][rows] of emitted
@@ -434,6 +462,9 @@ void batch_context_destroy(rwkv_context * c);
 struct RowStop { StopTables t; RowState * used, * other; };
 struct RowReport { float * chosen; uint32_t * ids; float * vals; uint32_t top_n; };
 struct RowBeam { BeamTables t; const RowState * used; RowState * other; };
+//   serve   the pass is a step of rwkv_mi_batch_serve: the choice runs behind the lanes' draw words and writes no history; launch_serve_rows and
+//           launch_serve_reset (`chunks` workgroups per lane over state_len floats) follow it
+struct RowServe { ServeTables t; RowState * used, * other; int64_t state_len; unsigned chunks; };
 struct RowSampler {
     DrawForm form;
     const DrawRow * rows = nullptr;
@@ -443,6 +474,7 @@ struct RowSampler {
     uint32_t step = 0;
     const RowStop * stop = nullptr;
     const RowBeam * beam = nullptr;
+    const RowServe * serve = nullptr;
 };
 void launch_row_sampler(rwkv_context * ctx, const RowSampler & s, int64_t rows);
 // sample: when given, launch_row_sampler follows the head inside the pass's place in the chain

@@ -31,7 +31,9 @@
 // The entry points: k_draw<SRC, CUT>, one workgroup on a context's logits; k_draw_rows<SRC, CUT, GUIDED>, one workgroup per row of a batch
 // pass (rwkv_mi_batch_eval_sample / _decode_sample and their kin), behind the row's live word in rwkv_mi_batch_decode_until, whose k_stop_rows
 // retires a row -- stop sequence or budget -- by rewriting its entries of the two row tables on the device; k_draft_accept_rows<FAMILY>, the
-// walk of rwkv_mi_batch_eval_draft, which draws once per position. The logits themselves are never written.
+// walk of rwkv_mi_batch_eval_draft, which draws once per position. The logits themselves are never written. rwkv_mi_batch_serve puts a queue
+// of requests behind the rows: k_serve_rows<DRAWS>, the scheduler that follows each pass's draw (the rows' live words are its draw words), and
+// k_serve_reset<VEC>, which copies an admitted request's start state in; neither draws.
 #include "kdev.h"
 #include "model.h"
 
@@ -561,6 +563,130 @@ __global__ __launch_bounds__(64) void k_stop_rows(StopTables t, int n, const uin
     atomicSub(t.live_count, 1u);
 }
 
+// The scheduler of rwkv_mi_batch_serve (model.h, ServeTables), ONE workgroup, thread tid on lane base + tid, after the draw of pass `step`:
+//   decode   (the lane's draw word is 1: the pass drew tokens[r]) the token is appended to the request's row out[q] and the stop test runs on
+//            that row -- k_stop_rows' rule on a contiguous window: the lowest matching sequence, else the budget. A request that ends leaves
+//            its length and reason and its lane FREE;
+//   prompt   (the draw word is 0) the lane's token word gets the next prompt token; with the last one the draw word goes up;
+//   free     the free lanes of the chunk are ranked in lane order -- a ballot per wave, the waves' counts through LDS -- and lane r takes
+//            request next + rank(r) while the queue lasts: its words, its token word, its draw row (the request's, with the lane's counter,
+//            set to 0, and the lane's occurrence row) and its admit word, for k_serve_reset. A lane the queue has nothing for goes dead as a
+//            row of k_stop_rows does: {in = F, out = G} in both row tables, for good.
+// Who gets what follows from the words alone: next_request is read and written by this workgroup only, no atomic decides anything. Thread 0
+// leaves the new head of the queue and the number of lanes that are not dead. DRAWS: the family has a draw table (the greedy one has none).
+template <bool DRAWS>
+__global__ __launch_bounds__(1024) void k_serve_rows(ServeTables t, int n, uint32_t * __restrict__ tokens, uint32_t step, RowState * used, RowState * other) {
+    __shared__ uint32_t l_free[16], l_work[16];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, waves = blockDim.x >> 6;
+    uint32_t next = *t.next_request, work = 0u;
+    for (int base = 0; base < n; base += blockDim.x) {
+        const int r = base + tid;
+        uint32_t q = r < n ? t.req[r] : RWKV_MI_NO_TOKEN;
+        bool is_free = q == SERVE_FREE;
+        if (q < SERVE_FREE) {
+            const ServeReq & rq = t.reqs[q];
+            if (t.draw[r]) {
+                uint32_t len = t.lens[q];
+                uint32_t * o = t.out + (size_t) q * t.stride;
+                if (len < t.stride) o[len] = tokens[r];
+                len++;
+                const uint32_t * sl = t.seq_lens + rq.stop.seq0;
+                const uint32_t * tk = t.seq_tokens + rq.stop.tok0;
+                uint32_t reason = RWKV_MI_NO_TOKEN;
+                for (uint32_t s = 0; s < rq.stop.n_seqs && reason == RWKV_MI_NO_TOKEN; s++) {
+                    const uint32_t L = sl[s];
+                    bool match = L <= len;   // (the window is the request's own tokens only)
+                    for (uint32_t k = 0; match && k < L; k++) match = o[len - L + k] == tk[k];
+                    if (match) reason = s;
+                    tk += L;
+                }
+                t.lens[q] = len;
+                if (reason != RWKV_MI_NO_TOKEN || len >= rq.stop.max_tokens) { t.reasons[q] = reason; is_free = true; }
+            } else {
+                const uint32_t pos = t.pos[r];
+                tokens[r] = t.prompts[rq.prompt0 + pos];
+                t.pos[r] = pos + 1u;
+                if (pos + 1u == rq.prompt_len) t.draw[r] = 1u;
+            }
+        }
+        const unsigned long long m = __ballot(is_free);
+        uint32_t rank = (uint32_t) __popcll(m & ((1ull << lane) - 1ull));
+        __syncthreads();   // (the chunk before has read the words)
+        if (lane == 0) l_free[wave] = (uint32_t) __popcll(m);
+        __syncthreads();
+        uint32_t total = 0u;
+        for (int w = 0; w < waves; w++) { if (w < wave) rank += l_free[w]; total += l_free[w]; }
+        bool alive = q < SERVE_FREE && !is_free;
+        if (r < n) t.admit[r] = 0u;
+        if (is_free) {
+            const uint32_t qn = next + rank;
+            if (qn < t.n_requests) {
+                const ServeReq & rq = t.reqs[qn];
+                const uint32_t slot = t.lane_slot[r];
+                t.req[r] = qn; t.last[r] = qn; t.pos[r] = 1u;
+                tokens[r] = t.prompts[rq.prompt0];
+                t.draw[r] = rq.prompt_len == 1u ? 1u : 0u;
+                t.lane[qn] = (uint32_t) r; t.start_pass[qn] = step + 1u;
+                t.counters[slot] = 0ull;
+                if constexpr (DRAWS) {
+                    DrawRow * row = t.rows + r;   // (the request's row, then the two words that are the lane's)
+                    *row = rq.row;
+                    row->counter = t.counters + slot;
+                    if (rq.row.record) row->count = t.counts + (size_t) slot * t.n_vocab;
+                }
+                t.admit[r] = 1u;
+                alive = true;
+            } else {
+                t.req[r] = RWKV_MI_NO_TOKEN; t.draw[r] = 0u;
+                const RowState u = used[r];
+                const RowState dead{u.out, const_cast<float *>(u.in)};
+                used[r] = dead;
+                other[r] = dead;
+            }
+        }
+        next = next + total < t.n_requests ? next + total : t.n_requests;
+        work += (uint32_t) __popcll(__ballot(alive));
+    }
+    if (lane == 0) l_work[wave] = work;
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t w_all = 0u;
+        for (int w = 0; w < waves; w++) w_all += l_work[w];
+        *t.next_request = next;
+        *t.work = w_all;
+    }
+}
+
+// The admissions of the pass, grid = lanes x chunks: a workgroup whose lane's admit word is 0 returns at once, all of it together. The others
+// stream the request's start state -- a from_slot's current buffer or the batch's fresh state: one path -- into used[r].out, the buffer the
+// lane's next pass reads (a live lane's two row tables mirror each other) and zero the lane's occurrence row. VEC: 16 bytes per load and
+// store -- the launcher has checked that the state length and the vocabulary are multiples of four words, so every buffer and row is aligned;
+// the other form moves words.
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_serve_reset(ServeTables t, const RowState * __restrict__ used, int64_t state_len) {
+    const int r = blockIdx.x;
+    if (!t.admit[r]) return;
+    const float * __restrict__ src = t.reqs[t.req[r]].start;
+    float * __restrict__ dst = used[r].out;
+    const int64_t i0 = (int64_t) blockIdx.y * 256 + threadIdx.x, hop = (int64_t) gridDim.y * 256;
+    if constexpr (VEC) {
+        const float4 * __restrict__ s4 = (const float4 *) src;
+        float4 * __restrict__ d4 = (float4 *) dst;
+#pragma unroll 4
+        for (int64_t i = i0; i < state_len / 4; i += hop) d4[i] = s4[i];
+    } else {
+        for (int64_t i = i0; i < state_len; i += hop) dst[i] = src[i];
+    }
+    if (!t.counts) return;
+    uint32_t * c = t.counts + (size_t) t.lane_slot[r] * t.n_vocab;
+    if constexpr (VEC) {
+        uint4 * c4 = (uint4 *) c;
+        for (int64_t i = i0; i < (int64_t) (t.n_vocab / 4); i += hop) c4[i] = make_uint4(0u, 0u, 0u, 0u);
+    } else {
+        for (int64_t i = i0; i < (int64_t) t.n_vocab; i += hop) c[i] = 0u;
+    }
+}
+
 // count[tokens[i]] += 1 for a list of tokens (rwkv_mi_*counts_add: a token may come more than once)
 __global__ __launch_bounds__(256) void k_count_add(uint32_t * __restrict__ count, const uint32_t * __restrict__ tokens, int64_t n, int n_vocab) {
     const int64_t i = (int64_t) blockIdx.x * 256 + threadIdx.x;
@@ -657,6 +783,19 @@ void launch_guide_expand(uint16_t * next, uint32_t n_states, int n_vocab, const 
 
 void launch_stop_rows(const StopTables & t, int64_t rows, const uint32_t * hist, uint32_t step, RowState * used, RowState * other, hipStream_t st) {
     hipLaunchKernelGGL(k_stop_rows, dim3((unsigned) ((rows + 63) / 64)), dim3(64), 0, st, t, (int) rows, hist, step, used, other);
+}
+
+void launch_serve_rows(const ServeTables & t, int64_t n, uint32_t * tokens, uint32_t step, RowState * used, RowState * other, hipStream_t st) {
+    const unsigned threads = n >= 1024 ? 1024u : (unsigned) ((n + 63) / 64) * 64u;
+    if (t.rows) hipLaunchKernelGGL(k_serve_rows<true>, dim3(1), dim3(threads), 0, st, t, (int) n, tokens, step, used, other);
+    else hipLaunchKernelGGL(k_serve_rows<false>, dim3(1), dim3(threads), 0, st, t, (int) n, tokens, step, used, other);
+}
+
+void launch_serve_reset(const ServeTables & t, int64_t n, unsigned chunks, const RowState * used, int64_t state_len, hipStream_t st) {
+    // (hipMalloc aligns the buffers themselves: a slot's state and its occurrence row are 16-byte aligned when their lengths are whole float4s)
+    const bool vec = (state_len & 3) == 0 && (!t.counts || (t.n_vocab & 3u) == 0);
+    if (vec) hipLaunchKernelGGL(k_serve_reset<true>, dim3((unsigned) n, chunks), dim3(256), 0, st, t, used, state_len);
+    else hipLaunchKernelGGL(k_serve_reset<false>, dim3((unsigned) n, chunks), dim3(256), 0, st, t, used, state_len);
 }
 
 void launch_count_add(uint32_t * count, const uint32_t * tokens, int64_t n, int n_vocab, hipStream_t st) {

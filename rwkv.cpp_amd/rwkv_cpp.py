@@ -36,6 +36,7 @@ PENALTY_SYMBOLS = ("rwkv_mi_batch_counts_reset", "rwkv_mi_batch_counts_add", "rw
                    "rwkv_mi_sample_penalized", "rwkv_mi_decode_sample_penalized")
 SCORE_SYMBOLS = ("rwkv_mi_score_resident", "rwkv_mi_batch_score_ragged")
 UNTIL_SYMBOLS = ("rwkv_mi_batch_decode_until", "rwkv_mi_batch_last_loop_passes")
+SERVE_SYMBOLS = ("rwkv_mi_batch_serve",)
 LOGPROBS_SYMBOLS = ("rwkv_mi_batch_set_logprobs", "rwkv_mi_batch_logprobs_shape", "rwkv_mi_batch_logprobs_store",
                     "rwkv_mi_set_logprobs", "rwkv_mi_logprobs_shape", "rwkv_mi_logprobs_store")
 BEAM_SYMBOLS = ("rwkv_mi_batch_state_copy", "rwkv_mi_batch_decode_beam")
@@ -54,6 +55,8 @@ NO_TARGET = 0xFFFFFFFF   # RWKV_MI_NO_TARGET: a position that is not scored (its
 NO_TOKEN = 0xFFFFFFFF    # RWKV_MI_NO_TOKEN: no token (past a row's length), no stop sequence (the budget ended the row)
 STOP_MAX_SEQS = 16       # RWKV_MI_STOP_MAX_SEQS
 STOP_MAX_LEN = 8         # RWKV_MI_STOP_MAX_LEN
+NO_SLOT = 0xFFFFFFFF     # RWKV_MI_NO_SLOT
+SERVE_GREEDY, SERVE_SAMPLE, SERVE_PENALIZED = 0, 1, 2   # RWKV_MI_SERVE_*
 P_FLOAT = ctypes.POINTER(ctypes.c_float)
 P_UINT32 = ctypes.POINTER(ctypes.c_uint32)
 
@@ -80,6 +83,17 @@ class StopParams(ctypes.Structure):
 
 
 P_STOP_PARAMS = ctypes.POINTER(StopParams)
+
+
+class ServeRequest(ctypes.Structure):
+    """struct rwkv_mi_serve_request (include/rwkv_mi355x.h): one request of RWKVBatch.serve -- prompt length, start slot, draw settings, budget and
+    number of stop sequences -- 72 bytes."""
+    _fields_ = [("prompt_len", ctypes.c_uint32), ("from_slot", ctypes.c_uint32), ("sample", SampleParams), ("penalty", PenaltyParams),
+                ("top_k", ctypes.c_uint32), ("min_p", ctypes.c_float), ("decay", ctypes.c_float), ("repetition", ctypes.c_float),
+                ("stop", StopParams), ("reserved", ctypes.c_uint32)]
+
+
+P_SERVE_REQUEST = ctypes.POINTER(ServeRequest)
 
 
 class CutParams(ctypes.Structure):
@@ -284,6 +298,11 @@ class RWKVSharedLibrary:
             L.rwkv_mi_batch_decode_until.restype = ctypes.c_bool
             L.rwkv_mi_batch_last_loop_passes.argtypes = [c_batch]
             L.rwkv_mi_batch_last_loop_passes.restype = ctypes.c_size_t
+        # continuous batching: a queue of requests behind the lanes of one device loop
+        if hasattr(L, "rwkv_mi_batch_serve"):   # (absent from older A/B builds loaded through RWKV_LIB_DIR)
+            L.rwkv_mi_batch_serve.argtypes = [c_batch, P_UINT32, ctypes.c_size_t, ctypes.c_int, P_SERVE_REQUEST, ctypes.c_size_t, P_UINT32, P_UINT32, P_UINT32,
+                                              ctypes.c_size_t, P_UINT32, P_UINT32, P_UINT32, P_UINT32, P_UINT32, P_UINT32, P_FLOAT]
+            L.rwkv_mi_batch_serve.restype = ctypes.c_bool
         # the report: log-probs and top-N alternatives of every emitted token
         if hasattr(L, "rwkv_mi_batch_set_logprobs"):   # (absent from older A/B builds loaded through RWKV_LIB_DIR)
             P_SIZE = ctypes.POINTER(ctypes.c_size_t)
@@ -850,6 +869,35 @@ def stop_params(n: int, max_tokens, stop=None):
     return arr, _u32(lens).reshape(-1), _u32(toks).reshape(-1)
 
 
+def serve_requests(requests):
+    """The request table of RWKVBatch.serve from one dict per request: ([R] struct rwkv_mi_serve_request, prompt_tokens, seq_lens, seq_tokens), the
+    requests' prompts and stop sequences back to back. Keys: prompt (token ids, at least one), max_tokens; optional from_slot (None: the fresh
+    state), stop (a list of token-id sequences), temperature (1.0), top_p (0.8), seed (0), presence (0.0), frequency (0.0), top_k (0), min_p (0.0),
+    decay (1.0), repetition (1.0)."""
+    requests = list(requests)
+    arr = (ServeRequest * len(requests))()
+    prompts, lens, toks = [], [], []
+    for i, rq in enumerate(requests):
+        unknown = set(rq) - {"prompt", "max_tokens", "from_slot", "stop", "temperature", "top_p", "seed", "presence", "frequency", "top_k", "min_p", "decay", "repetition"}
+        if unknown:
+            raise ValueError(f"request {i}: unknown keys {sorted(unknown)}")
+        prompt = [int(t) for t in rq["prompt"]]
+        if not prompt:
+            raise ValueError(f"request {i}: the prompt is empty")
+        stop = [[int(t) for t in q] for q in rq.get("stop") or []]
+        from_slot = rq.get("from_slot")
+        arr[i] = ServeRequest(len(prompt), NO_SLOT if from_slot is None else int(from_slot),
+                              SampleParams(float(rq.get("temperature", 1.0)), float(rq.get("top_p", 0.8)), -1.0, int(rq.get("seed", 0)) & 0xFFFFFFFFFFFFFFFF),
+                              PenaltyParams(float(rq.get("presence", 0.0)), float(rq.get("frequency", 0.0)), 1),
+                              int(rq.get("top_k", 0)), float(rq.get("min_p", 0.0)), float(rq.get("decay", 1.0)), float(rq.get("repetition", 1.0)),
+                              StopParams(int(rq["max_tokens"]), len(stop)), 0)
+        prompts.extend(prompt)
+        for q in stop:
+            lens.append(len(q))
+            toks.extend(q)
+    return arr, _u32(prompts).reshape(-1), _u32(lens).reshape(-1), _u32(toks).reshape(-1)
+
+
 def guide_edges(edges):
     """A guide in the CSR form of rwkv_mi_batch_guide_create from one {token: next_state} dict per state: (edge_begin [n_states + 1],
     edge_tokens, edge_next), each state's tokens ascending."""
@@ -1143,6 +1191,30 @@ class RWKVBatch:
                                                   ctypes.byref(ms)):
             self._fail("rwkv_mi_batch_decode_until")
         return [out[i, : int(lens[i])].copy() for i in range(n)], why, float(ms.value)
+
+    def serve(self, lanes: List[int], requests, family: int = SERVE_GREEDY):
+        """Continuous batching: the slots `lanes` serve the queue `requests` (dicts, as serve_requests takes them; at least as many as lanes) in
+        one device loop -- lane r starts with request r, and a lane whose request has ended takes the next one not yet taken on the following
+        pass, in lane order. A request starts from the fresh state or from its from_slot's (never a lane), is fed its prompt one token a pass and
+        then decodes as a row of decode_until with its own settings; family: SERVE_GREEDY, SERVE_SAMPLE or SERVE_PENALIZED, the call's. Returns
+        a dict: tokens (one uint32 array per request, of its own length), stopped_by [R], lane [R] (index into lanes), start_pass [R],
+        last_request [n] (the request whose end state each lane holds), elapsed_ms. Every request's tokens are what it gives alone."""
+        s = _u32(lanes).reshape(-1)
+        arr, prompts, seq_lens, seq_tokens = serve_requests(requests)
+        n, R = s.size, len(arr)
+        stride = max([int(r.stop.max_tokens) for r in arr], default=0)
+        out = np.empty((R, stride), dtype=np.uint32)
+        lens = np.zeros(R, dtype=np.uint32)
+        why, lane, start = (np.empty(R, dtype=np.uint32) for _ in range(3))
+        last = np.empty(n, dtype=np.uint32)
+        ms = ctypes.c_float(0.0)
+        if not self._L.rwkv_mi_batch_serve(self._ptr, s.ctypes.data_as(P_UINT32), n, int(family), arr, R, prompts.ctypes.data_as(P_UINT32),
+                                           seq_lens.ctypes.data_as(P_UINT32), seq_tokens.ctypes.data_as(P_UINT32), stride,
+                                           ctypes.cast(out.ctypes.data, P_UINT32), lens.ctypes.data_as(P_UINT32), why.ctypes.data_as(P_UINT32),
+                                           lane.ctypes.data_as(P_UINT32), start.ctypes.data_as(P_UINT32), last.ctypes.data_as(P_UINT32), ctypes.byref(ms)):
+            self._fail("rwkv_mi_batch_serve")
+        return {"tokens": [out[q, : int(lens[q])].copy() for q in range(R)], "stopped_by": why, "lane": lane, "start_pass": start,
+                "last_request": last, "elapsed_ms": float(ms.value)}
 
     # --- speculative decoding (include/rwkv_mi355x.h) ---
 

@@ -38,6 +38,15 @@ process, HIP events around each device loop, the smallest of --reps runs, --toke
   mode until_all_retire   (c) every row retires at a quarter of the budget, against the plain loop of the full budget, with last_loop_passes
   mode until_eval_sample  the way without either loop: one synchronising rwkv_mi_batch_eval_sample call per token, host clock
 
+--serve times rwkv_mi_batch_serve (sampled family: temperature 1.0, top-p 0.8, seed = request) on a fixed, seeded queue of 4 n requests with
+budgets spread over 16 .. 256 and prompts of 1 .. 32 tokens, for every n of --n (give --n 8,64), the smallest of --reps runs after a warm-up
+run, everything in this process and run; records also go to --out:
+  mode serve            the queue on n lanes: host clock around the call (and the HIP events' figure), useful tokens/s, passes enqueued
+  mode serve_waves      the same queue statically batched, n requests at a time: rwkv_mi_batch_eval_ragged of the prompts but their last
+                        tokens, then rwkv_mi_batch_decode_until until the slowest has ended; host clock around those calls
+  mode serve_admission  the mean time of a pass that admits (every lane, every pass: one prompt token, a budget of one) against one that
+                        does not (n requests of the same number of passes), and the difference per admission
+
 --sample --logprobs N[,N...] times the sampled loop (temperature 1.0, top-p 0.8, seed = row) with and without the report of the emitted tokens
 (rwkv_mi_batch_set_logprobs) in the same process, HIP events around each device loop, the smallest of --reps runs, --tokens steps, for every
 top_n of the list; records also go to --out:
@@ -259,6 +268,89 @@ def until(pkg, m, args):
         emit({"mode": "until_eval_sample", "n": n, "ms_per_step": round(call_ms / steps, 4), "until_ms_per_step": round(by_block[16] / steps, 4),
               "per_token_calls_over_until": round(call_ms / by_block[16], 3)})
     b.free()
+    if sink:
+        sink.close()
+
+
+def serve(pkg, m, args):
+    import numpy as np
+    V = m.n_vocab
+    sink = open(args.out, "a") if args.out else None
+
+    def emit(rec):
+        rec.update({"reps": args.reps, "temperature": 1.0, "top_p": 0.8, "config": args.config, "dtype": args.dtype})
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if sink:
+            sink.write(line + "\n")
+            sink.flush()
+
+    def best(run):
+        out = [run() for _ in range(args.reps + 1)]   # (run 0: warm-up -- buffers of the first call, tile-major weight images)
+        return min(out[1:], key=lambda r: r[0])
+
+    for n in [int(x) for x in args.n.split(",")]:
+        R = 4 * n
+        rng = np.random.default_rng(1000 + n)   # the queue is fixed by n
+        budgets = [int(v) for v in rng.integers(16, 257, R)]
+        prompts = [[int(t) for t in rng.integers(0, V, int(L))] for L in rng.integers(1, 33, R)]
+        reqs = [dict(prompt=prompts[q], max_tokens=budgets[q], temperature=1.0, top_p=0.8, seed=q) for q in range(R)]
+        useful = sum(budgets)   # (no stop sequences: every request runs to its budget, in both arms)
+        lanes = list(range(n))
+        b = pkg.RWKVBatch(m, n)
+
+        def served():
+            t0 = time.perf_counter()
+            got = b.serve(lanes, reqs, pkg.SERVE_SAMPLE)
+            host = (time.perf_counter() - t0) * 1e3
+            assert [len(t) for t in got["tokens"]] == budgets
+            return host, got["elapsed_ms"], b.last_loop_passes(), got["tokens"]
+
+        def waves():
+            # the same queue statically batched: n requests at a time, prompts in one ragged pass, then the loop until the slowest has ended
+            host, passes, toks = 0.0, 0, []
+            for w in range(0, R, n):
+                for s in lanes:
+                    b.state_load(s, None)
+                t0 = time.perf_counter()
+                long = [s for s in lanes if len(prompts[w + s]) > 1]
+                if long:
+                    b.eval_ragged(long, [prompts[w + s][:-1] for s in long], want_logits=False)
+                    passes += 1
+                out, _, _ = b.decode_until(lanes, [prompts[w + s][-1] for s in lanes], budgets[w: w + n], None, 1.0, 0.8, list(range(w, w + n)))
+                host += (time.perf_counter() - t0) * 1e3
+                passes += b.last_loop_passes()
+                toks.extend(out)
+            return host, passes, toks
+
+        s_host, s_dev, s_passes, s_toks = best(served)
+        w_host, w_passes, w_toks = best(waves)
+        same = all(np.array_equal(a, c) for a, c in zip(s_toks, w_toks))
+        emit({"mode": "serve", "n": n, "requests": R, "useful_tokens": useful, "total_ms": round(s_host, 3), "device_ms": round(s_dev, 3), "passes": s_passes,
+              "useful_tokens_per_s": round(useful / s_host * 1e3, 1), "ms_per_pass": round(s_dev / s_passes, 4)})
+        emit({"mode": "serve_waves", "n": n, "requests": R, "useful_tokens": useful, "total_ms": round(w_host, 3), "passes": w_passes,
+              "useful_tokens_per_s": round(useful / w_host * 1e3, 1), "waves_over_serve": round(w_host / s_host, 3), "same_tokens_as_serve": bool(same)})
+
+        # what an admission costs: a queue in which EVERY pass admits all n lanes (one prompt token, one token) against a call of n requests
+        # that admits none after the first pass. Both retire their last request after pass steps - 1, so both enqueue the same passes (the dead
+        # ones behind the last retirement included, which cost what a pass without an admission costs): the difference is the admissions'
+        steps = 32
+        churn = [dict(prompt=[(7 * q + 1) % V], max_tokens=1, temperature=1.0, top_p=0.8, seed=q) for q in range(steps * n)]
+        steady = [dict(prompt=[(7 * q + 1) % V], max_tokens=steps, temperature=1.0, top_p=0.8, seed=q) for q in range(n)]
+
+        def timed(queue):
+            def run():
+                got = b.serve(lanes, queue, pkg.SERVE_SAMPLE)
+                return got["elapsed_ms"], b.last_loop_passes()
+            return best(run)
+
+        (admit_ms, admit_passes), (plain_ms, plain_passes) = timed(churn), timed(steady)
+        assert admit_passes == plain_passes, (admit_passes, plain_passes)
+        plain_pass = plain_ms / plain_passes
+        emit({"mode": "serve_admission", "n": n, "admitting_passes": steps, "passes": plain_passes, "plain_pass_ms": round(plain_pass, 4),
+              "admitting_pass_ms": round(plain_pass + (admit_ms - plain_ms) / steps, 4), "ms_per_admission": round((admit_ms - plain_ms) / (steps * n), 5),
+              "state_mb": round(m.state_len * 4 / 1e6, 2)})
+        b.free()
     if sink:
         sink.close()
 
@@ -773,6 +865,7 @@ def main():
     ap.add_argument("--penalties", action="store_true", help="with --sample: also time the penalised sampling loop, on the device and through the host")
     ap.add_argument("--ragged", action="store_true", help="time the ragged pass: prompt ingestion and joining a decode step (see above)")
     ap.add_argument("--until", action="store_true", help="time rwkv_mi_batch_decode_until against the plain sampled loop (see above)")
+    ap.add_argument("--serve", action="store_true", help="time rwkv_mi_batch_serve on a fixed queue of 4 n requests against the same queue in waves of decode_until (see above)")
     ap.add_argument("--logprobs", default=None, metavar="N[,N...]",
                     help="with --sample: time the sampled loop with and without the report of the emitted tokens, for each top_n of the list (see above)")
     ap.add_argument("--beam", default=None, metavar="W[,W...]",
@@ -812,6 +905,10 @@ def main():
         return
     if args.until:
         until(pkg, m, args)
+        m.free()
+        return
+    if args.serve:
+        serve(pkg, m, args)
         m.free()
         return
     if args.beam is not None:

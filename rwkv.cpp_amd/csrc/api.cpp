@@ -1090,6 +1090,23 @@ hipError_t guide_table_build(DevBuf<uint16_t> & table, size_t n_vocab, uint32_t 
 // parity per slot; a pass reads slot s at buffer parity[s] and writes buffer parity[s] ^ 1 through a row table ({in, out} per row,
 // uploaded through pinned staging). The pass itself is the per-op Runner in row mode on the batch's own context (engine.hip forward_rows).
 // ---------------------------------------------------------------------------------------------------------------
+
+// What the host of a polled device loop reads between two blocks of passes (batch_run_passes): the polled word of the last two blocks in
+// pinned memory, each behind its event. Created by the first polled loop of a batch, whichever it is; destroyed with the batch, whose free
+// function has drained the stream and made the device current.
+struct BlockPoll {
+    PinBuf<uint32_t> count;   // [2]
+    hipEvent_t ev[2] = {nullptr, nullptr};   // (not copyable: `count` is not)
+    ~BlockPoll() { for (hipEvent_t e : ev) if (e) (void) hipEventDestroy(e); }
+    // a failure leaves what exists as it was and clears the sticky HIP error
+    hipError_t ensure() {
+        hipError_t e = count ? hipSuccess : count.alloc(2);
+        for (hipEvent_t & v : ev) if (e == hipSuccess && !v) e = hipEventCreateWithFlags(&v, hipEventDisableTiming);
+        if (e != hipSuccess) (void) hipGetLastError();
+        return e;
+    }
+};
+
 struct rwkv_mi_batch {
     rwkv_context * ctx = nullptr;      // the caller's context: model, device, error word
     rwkv_context * run = nullptr;      // the batch's own context (stream, scratch, tokens, logits)
@@ -1097,7 +1114,7 @@ struct rwkv_mi_batch {
     int64_t state_len = 0;
     DevBuf<float> states;              // [2][n_slots][state_len]
     std::vector<uint8_t> parity;
-    DevBuf<RowState> d_rows;           // [2][n_slots]: the row tables of a call (the greedy loop alternates between the two)
+    DevBuf<RowState> d_rows;           // [2][n_slots]: the row tables of a call (a device loop alternates between the two)
     PinBuf<RowState> h_rows;           // pinned staging of the same
     DrawState draw;                    // the slots' draw state: counters (zero at creation), sampler scratch, occurrence and bias tables
     // the row table of a drawing call, [n_slots] (model.h, DrawRow: filled by DrawState::row), with its pinned staging -- allocated with the
@@ -1115,19 +1132,18 @@ struct rwkv_mi_batch {
     PinBuf<uint8_t> h_seg;
     std::vector<SegState> long_segs;
     SegPass pass;
-    // rwkv_mi_batch_decode_until: the words of a call in one device buffer with its pinned staging, laid out by batch_upload_stops for the call's
-    // n and sequences (capacity: n_slots rows of RWKV_MI_STOP_MAX_SEQS sequences of RWKV_MI_STOP_MAX_LEN tokens); the live count of the last two
-    // blocks in pinned memory, each behind its event -- allocated by the first call of that family
+    // the device loops (batch_run_passes): what the polled ones read between blocks -- allocated by the first of them -- and the passes the
+    // last loop enqueued
+    BlockPoll poll;
+    size_t last_loop_passes = 0;
+    // rwkv_mi_batch_decode_until: the words of a call in one device buffer with its pinned staging, laid out by StopLayout for the call's n and
+    // sequences (capacity: n_slots rows of RWKV_MI_STOP_MAX_SEQS sequences of RWKV_MI_STOP_MAX_LEN tokens) -- allocated by the first call
     DevBuf<uint8_t> d_stop;
     PinBuf<uint8_t> h_stop;
-    PinBuf<uint32_t> h_live_count;       // [2]
-    hipEvent_t ev_block[2] = {nullptr, nullptr};
     StopTables stop{};                   // the device pointers of the current call
     size_t stop_off_lens = 0;            // where lens[n], reasons[n] start in both buffers
-    size_t last_loop_passes = 0;
     // rwkv_mi_batch_decode_beam: the per-row words of a call (BeamTables: scores, finished words, lengths, live count, candidates) in one device
-    // buffer for n_slots rows, with the pinned staging of the part a call uploads and reads back -- allocated by the first beam call, as are
-    // h_live_count and ev_block above where decode_until has not
+    // buffer for n_slots rows, with the pinned staging of the part a call uploads and reads back -- allocated by the first beam call
     DevBuf<uint8_t> d_beam;
     PinBuf<uint8_t> h_beam;
     // rwkv_mi_batch_eval_draft: the logits of every token of a pass [T][n_vocab] and the stash of its recurrences' inputs (kernels.h, DraftStash),
@@ -1140,7 +1156,7 @@ struct rwkv_mi_batch {
     PinBuf<uint32_t> h_draft_words;
     // rwkv_mi_batch_serve: the words of a call -- the request table, prompts, stop sequences, lane and request words, the emitted tokens -- in
     // one device buffer with its pinned staging, laid out by ServeLayout and grown to the largest call so far; the fresh state every request
-    // without a from_slot starts from, filled once -- allocated by the first call, as are h_live_count and ev_block above where no other loop has
+    // without a from_slot starts from, filled once -- allocated by the first call
     DevBuf<uint8_t> d_serve;
     PinBuf<uint8_t> h_serve;
     DevBuf<float> serve_fresh;          // [state_len]
@@ -1155,11 +1171,22 @@ static bool batch_fail_through(rwkv_mi_batch * B) { B->ctx->last_error |= B->run
 #define BATCH_HIP_OK(B, CALL) \
     do { hipError_t e_ = (CALL); RW_CTX_CHECK((B)->ctx, RWKV_ERROR_GRAPH, false, e_ == hipSuccess, "HIP error: %s", hipGetErrorString(e_)); } while (0)
 
+// what every body starts with, before it looks at an argument: no error yet, the batch's own context prints as the caller's does, the
+// batch's device is current
+static bool batch_begin(rwkv_mi_batch * B) {
+    B->ctx->last_error = RWKV_ERROR_NONE;
+    B->run->print_errors = B->ctx->print_errors;
+    BATCH_HIP_OK(B, hipSetDevice(B->ctx->model->device));
+    return true;
+}
+
 // What a batch call is: a point on three axes. The input -- one token per row, or a segment per row (lens); the draw -- none,
-// the sampler, or the penalised sampler; the repeat -- one pass (batch_pass), a device loop of n_tokens steps (batch_loop, where no draw
-// means the greedy argmax), or that loop with every row ending by itself (batch_until). Every entry point fills in this description and calls one
-// of the three bodies. The REPORT is a fourth property, the batch's own: a call that emits tokens -- a draw, or a loop's argmax --
-// records them when B->lp.enabled; the bodies branch on that and on `emits`, never on who called.
+// the sampler, or the penalised sampler; the repeat -- one pass (batch_pass, batch_draft) or a device loop. The loops are one driver
+// (batch_run_passes: the passes, their blocks, the poll that ends them) and what each body adds to it: batch_loop n_tokens steps (no draw
+// means the greedy argmax), batch_until every row ending by itself, batch_serve a queue of requests behind the rows, batch_beam (its own
+// description, BeamCall) a selection behind every pass. Every entry point fills in this description and calls one body. The REPORT
+//  is a fourth property, the batch's own: a call that emits tokens -- a draw, or a loop's argmax -- records them when
+// B->lp.enabled; the bodies branch on that and on `emits`, never on who called.
 struct BatchCall {
     const uint32_t * slots, * tokens;   // row i is slot slots[i] fed tokens[i] ...
     size_t n;
@@ -1234,21 +1261,31 @@ static bool batch_check_rows(rwkv_mi_batch * B, const BatchCall & c, size_t * T_
     return true;
 }
 
-// row tables of the n named slots (table 0: current -> other buffer, table 1: the reverse) and the tokens into the batch's device words
-static bool batch_upload(rwkv_mi_batch * B, const BatchCall & c, int tables) {
-    rwkv_context * run = B->run;
-    const uint32_t * slots = c.slots;
-    const size_t n = c.n;
-    BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));   // (the previous call's copies may still read the staging)
+// row tables of the n named slots into the staging (the stream has been drained): table 0 takes a slot from its current buffer into the
+// other one, table 1 -- what the odd passes of a loop run on -- is the reverse
+static void batch_stage_rows(rwkv_mi_batch * B, const uint32_t * slots, size_t n, int tables) {
     for (int tb = 0; tb < tables; tb++)
         for (size_t i = 0; i < n; i++) {
             const int p = B->parity[slots[i]] ^ tb;
             B->h_rows.p[(size_t) tb * B->n_slots + i] = RowState{B->slot_buf(slots[i], p), B->slot_buf(slots[i], p ^ 1)};
         }
-    memcpy(run->h_tokens.p, c.tokens, n * sizeof(uint32_t));
+}
+
+// the first n rows of the staged tables, whoever staged them, to the device
+static bool batch_upload_rows(rwkv_mi_batch * B, size_t n, int tables) {
     for (int tb = 0; tb < tables; tb++)
-        BATCH_HIP_OK(B, hipMemcpyAsync(B->d_rows.p + (size_t) tb * B->n_slots, B->h_rows.p + (size_t) tb * B->n_slots, n * sizeof(RowState), hipMemcpyHostToDevice, run->stream));
-    BATCH_HIP_OK(B, hipMemcpyAsync(run->d_tokens.p, run->h_tokens.p, n * sizeof(uint32_t), hipMemcpyHostToDevice, run->stream));
+        BATCH_HIP_OK(B, hipMemcpyAsync(B->d_rows.p + (size_t) tb * B->n_slots, B->h_rows.p + (size_t) tb * B->n_slots, n * sizeof(RowState), hipMemcpyHostToDevice, B->run->stream));
+    return true;
+}
+
+// row tables of the n named slots and the tokens into the batch's device words
+static bool batch_upload(rwkv_mi_batch * B, const BatchCall & c, int tables) {
+    rwkv_context * run = B->run;
+    BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));   // (the previous call's copies may still read the staging)
+    batch_stage_rows(B, c.slots, c.n, tables);
+    memcpy(run->h_tokens.p, c.tokens, c.n * sizeof(uint32_t));
+    if (!batch_upload_rows(B, c.n, tables)) return false;
+    BATCH_HIP_OK(B, hipMemcpyAsync(run->d_tokens.p, run->h_tokens.p, c.n * sizeof(uint32_t), hipMemcpyHostToDevice, run->stream));
     return true;
 }
 
@@ -1345,43 +1382,60 @@ static bool batch_upload_ragged(rwkv_mi_batch * B, const BatchCall & c, size_t T
 
 // ---- stop sequences and budgets (rwkv_mi_batch_decode_until) ----
 
-// the stop arguments of a call (checked with the other arguments, before anything changes)
-static bool batch_check_stops(rwkv_mi_batch * B, const BatchCall & c) {
+// the budgets and stop sequences of `n` rows (or requests), checked with the other arguments, before anything changes
+static bool batch_check_stops(rwkv_mi_batch * B, const rwkv_mi_stop_params * stops, size_t n, const uint32_t * seq_lens, const uint32_t * seq_tokens, size_t stride,
+                              const uint32_t * lens_out) {
     rwkv_context * ctx = B->ctx;
-    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, c.stops != nullptr && c.lens_out != nullptr, "stops or lens_out is NULL");
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, stops != nullptr && lens_out != nullptr, "stops or lens_out is NULL");
     const size_t n_vocab = (size_t) ctx->model->n_vocab();
     size_t n_seqs = 0, n_toks = 0;
-    for (size_t i = 0; i < c.n; i++) {
-        const rwkv_mi_stop_params & sp = c.stops[i];
+    for (size_t i = 0; i < n; i++) {
+        const rwkv_mi_stop_params & sp = stops[i];
         RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, sp.max_tokens > 0, "max_tokens at index %zu is 0", i);
-        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, (size_t) sp.max_tokens <= c.stride, "stride (%zu) is less than max_tokens at index %zu (%" PRIu32 ")", c.stride, i, sp.max_tokens);
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, (size_t) sp.max_tokens <= stride, "stride (%zu) is less than max_tokens at index %zu (%" PRIu32 ")", stride, i, sp.max_tokens);
         RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, sp.n_seqs <= RWKV_MI_STOP_MAX_SEQS, "n_seqs at index %zu (%" PRIu32 ") is above %d", i, sp.n_seqs, RWKV_MI_STOP_MAX_SEQS);
         n_seqs += sp.n_seqs;
     }
-    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, n_seqs == 0 || c.seq_lens != nullptr, "seq_lens is NULL");
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, n_seqs == 0 || seq_lens != nullptr, "seq_lens is NULL");
     for (size_t s = 0; s < n_seqs; s++) {
-        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, c.seq_lens[s] > 0 && c.seq_lens[s] <= RWKV_MI_STOP_MAX_LEN, "the length of stop sequence %zu (%" PRIu32 ") must be in 1 .. %d",
-                     s, c.seq_lens[s], RWKV_MI_STOP_MAX_LEN);
-        n_toks += c.seq_lens[s];
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, seq_lens[s] > 0 && seq_lens[s] <= RWKV_MI_STOP_MAX_LEN, "the length of stop sequence %zu (%" PRIu32 ") must be in 1 .. %d",
+                     s, seq_lens[s], RWKV_MI_STOP_MAX_LEN);
+        n_toks += seq_lens[s];
     }
-    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, n_toks == 0 || c.seq_tokens != nullptr, "seq_tokens is NULL");
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, n_toks == 0 || seq_tokens != nullptr, "seq_tokens is NULL");
     for (size_t t = 0; t < n_toks; t++)
-        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, c.seq_tokens[t] < n_vocab, "stop token at index %zu (%" PRIu32 ") is out of range (0 .. %zu)", t, c.seq_tokens[t], n_vocab - 1);
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, seq_tokens[t] < n_vocab, "stop token at index %zu (%" PRIu32 ") is out of range (0 .. %zu)", t, seq_tokens[t], n_vocab - 1);
     return true;
 }
 
-// bytes of the stop words of a call of n rows with n_seqs sequences of n_toks tokens in all: rows, live, lens, reasons, live count, lengths, tokens
-static size_t stop_bytes(size_t n, size_t n_seqs, size_t n_toks) { return n * sizeof(StopRow) + (3 * n + 1 + n_seqs + n_toks) * sizeof(uint32_t); }
+// The next row of a call's StopRow table: its parameters and where its sequences start in the flat tables. *n_seqs and *n_toks are the
+// sequences and tokens of the rows before it on entry, with it on return (after the last row: the call's totals).
+static StopRow stop_row(const rwkv_mi_stop_params & sp, const uint32_t * seq_lens, size_t * n_seqs, size_t * n_toks) {
+    const StopRow row{sp.max_tokens, sp.n_seqs, (uint32_t) *n_seqs, (uint32_t) *n_toks};
+    for (uint32_t s = 0; s < sp.n_seqs; s++) *n_toks += seq_lens[*n_seqs + s];
+    *n_seqs += sp.n_seqs;
+    return row;
+}
 
-// the stop buffers and the two block events: on the first call of the family
+// Where the stop words of a call of n rows with n_seqs sequences of n_toks tokens in all lie in the stop buffer (byte offsets): the rows, their
+// live words, lengths and reasons, the live count, the sequences' lengths and tokens.
+struct StopLayout {
+    size_t rows, live, lens, reasons, count, seq_lens, seq_tokens, bytes;
+    StopLayout(size_t n, size_t n_seqs, size_t n_toks) {
+        size_t o = 0;
+        auto take = [&o](size_t b) { const size_t at = o; o += b; return at; };
+        rows = take(n * sizeof(StopRow)); live = take(n * 4); lens = take(n * 4); reasons = take(n * 4); count = take(4);
+        seq_lens = take(n_seqs * 4); seq_tokens = take(n_toks * 4);
+        bytes = o;
+    }
+};
+
+// the poll words of the batch and the stop buffers: on the first call of the family
 static bool batch_ensure_stop(rwkv_mi_batch * B) {
-    rwkv_context * ctx = B->ctx;
-    if (B->d_stop && B->h_stop && B->h_live_count && B->ev_block[0] && B->ev_block[1]) return true;
-    const size_t bytes = stop_bytes(B->n_slots, B->n_slots * RWKV_MI_STOP_MAX_SEQS, B->n_slots * RWKV_MI_STOP_MAX_SEQS * RWKV_MI_STOP_MAX_LEN);
-    hipError_t e = grow(want(B->d_stop, B->d_stop ? 0 : bytes), want(B->h_stop, B->h_stop ? 0 : bytes), want(B->h_live_count, B->h_live_count ? 0 : 2));
-    for (hipEvent_t & ev : B->ev_block) if (e == hipSuccess && !ev) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-    if (e != hipSuccess) (void) hipGetLastError();
-    RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the stop tables of %zu slots: %s", B->n_slots, hipGetErrorString(e));
+    const size_t bytes = StopLayout(B->n_slots, B->n_slots * RWKV_MI_STOP_MAX_SEQS, B->n_slots * RWKV_MI_STOP_MAX_SEQS * RWKV_MI_STOP_MAX_LEN).bytes;
+    hipError_t e = B->poll.ensure();
+    if (e == hipSuccess && !B->d_stop) e = grow(want(B->d_stop, bytes), want(B->h_stop, bytes));   // (one decision: both or neither)
+    RW_CTX_CHECK(B->ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the stop tables of %zu slots: %s", B->n_slots, hipGetErrorString(e));
     return true;
 }
 
@@ -1390,24 +1444,19 @@ static bool batch_ensure_stop(rwkv_mi_batch * B) {
 static bool batch_upload_stops(rwkv_mi_batch * B, const BatchCall & c) {
     const size_t n = c.n;
     size_t n_seqs = 0, n_toks = 0;
-    StopRow * rows = (StopRow *) B->h_stop.p;
-    for (size_t i = 0; i < n; i++) {
-        rows[i] = StopRow{c.stops[i].max_tokens, c.stops[i].n_seqs, (uint32_t) n_seqs, (uint32_t) n_toks};
-        for (uint32_t s = 0; s < c.stops[i].n_seqs; s++) n_toks += c.seq_lens[n_seqs + s];
-        n_seqs += c.stops[i].n_seqs;
-    }
-    const size_t off_live = n * sizeof(StopRow), off_lens = off_live + n * 4, off_reasons = off_lens + n * 4, off_count = off_reasons + n * 4;
-    const size_t off_sl = off_count + 4, off_st = off_sl + n_seqs * 4, bytes = off_st + n_toks * 4;
-    uint32_t * live = (uint32_t *) (B->h_stop.p + off_live), * lens = (uint32_t *) (B->h_stop.p + off_lens), * reasons = (uint32_t *) (B->h_stop.p + off_reasons);
-    for (size_t i = 0; i < n; i++) { live[i] = 1u; lens[i] = 0u; reasons[i] = RWKV_MI_NO_TOKEN; }
-    *(uint32_t *) (B->h_stop.p + off_count) = (uint32_t) n;
-    if (n_seqs) memcpy(B->h_stop.p + off_sl, c.seq_lens, n_seqs * 4);
-    if (n_toks) memcpy(B->h_stop.p + off_st, c.seq_tokens, n_toks * 4);
-    BATCH_HIP_OK(B, hipMemcpyAsync(B->d_stop.p, B->h_stop.p, bytes, hipMemcpyHostToDevice, B->run->stream));
-    uint8_t * d = B->d_stop.p;
-    B->stop = StopTables{(const StopRow *) d, (const uint32_t *) (d + off_sl), (const uint32_t *) (d + off_st), (uint32_t *) (d + off_live),
-                         (uint32_t *) (d + off_lens), (uint32_t *) (d + off_reasons), (uint32_t *) (d + off_count)};
-    B->stop_off_lens = off_lens;
+    StopRow * rows = (StopRow *) B->h_stop.p;   // (StopLayout::rows is 0)
+    for (size_t i = 0; i < n; i++) rows[i] = stop_row(c.stops[i], c.seq_lens, &n_seqs, &n_toks);
+    const StopLayout L(n, n_seqs, n_toks);
+    uint8_t * h = B->h_stop.p, * d = B->d_stop.p;
+    auto hw = [h](size_t off) { return (uint32_t *) (h + off); };
+    auto dw = [d](size_t off) { return (uint32_t *) (d + off); };
+    for (size_t i = 0; i < n; i++) { hw(L.live)[i] = 1u; hw(L.lens)[i] = 0u; hw(L.reasons)[i] = RWKV_MI_NO_TOKEN; }
+    *hw(L.count) = (uint32_t) n;
+    if (n_seqs) memcpy(h + L.seq_lens, c.seq_lens, n_seqs * 4);
+    if (n_toks) memcpy(h + L.seq_tokens, c.seq_tokens, n_toks * 4);
+    BATCH_HIP_OK(B, hipMemcpyAsync(d, h, L.bytes, hipMemcpyHostToDevice, B->run->stream));
+    B->stop = StopTables{(const StopRow *) (d + L.rows), dw(L.seq_lens), dw(L.seq_tokens), dw(L.live), dw(L.lens), dw(L.reasons), dw(L.count)};
+    B->stop_off_lens = L.lens;
     return true;
 }
 
@@ -1419,7 +1468,7 @@ static bool batch_check_args(rwkv_mi_batch * B, const BatchCall & c, bool u_used
     if (!batch_check_rows(B, c, T_out) || !check_targets(B->ctx, c.targets, *T_out, c.logprobs_out)) return false;
     if (c.draw != Draw::none && !batch_check_params(B, c.params, c.n, u_used)) return false;
     if (c.draw == Draw::penalized && !batch_check_penalties(B, c.penalties, c.n)) return false;
-    return !c.until || batch_check_stops(B, c);
+    return !c.until || batch_check_stops(B, c.stops, c.n, c.seq_lens, c.seq_tokens, c.stride, c.lens_out);
 }
 
 // the form of the call's draw kernel -- decided here, once, from the slots the call names; everything after reads B->form -- and the buffers
@@ -1473,13 +1522,10 @@ static void batch_flip(rwkv_mi_batch * B, const BatchCall & c) { for (size_t i =
 static bool batch_pass(rwkv_mi_batch * B, const BatchCall & c) {
     rwkv_context * ctx = B->ctx;
     rwkv_context * run = B->run;
-    ctx->last_error = RWKV_ERROR_NONE;
     size_t T = 0;
-    if (!batch_check_args(B, c, true, &T)) return false;
+    if (!batch_begin(B) || !batch_check_args(B, c, true, &T)) return false;
     const bool drawn = c.draw != Draw::none, scoring = c.logprobs_out || c.argmax_out;
     RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, !drawn || c.sampled_out != nullptr, "sampled_out is NULL");
-    run->print_errors = ctx->print_errors;
-    BATCH_HIP_OK(B, hipSetDevice(ctx->model->device));
     if (!batch_ensure_draw(B, c)) return false;
     if (scoring && !ensure_score(run, (int64_t) T)) return batch_fail_through(B);
     const bool report = drawn && B->lp.enabled;   // (a pass emits where it draws)
@@ -1558,11 +1604,8 @@ static bool batch_ensure_draft(rwkv_mi_batch * B, size_t T) {
 static bool batch_draft(rwkv_mi_batch * B, const BatchCall & c, uint32_t * tokens_out) {
     rwkv_context * ctx = B->ctx;
     rwkv_context * run = B->run;
-    ctx->last_error = RWKV_ERROR_NONE;
     size_t T = 0;
-    if (!batch_check_args(B, c, false, &T) || !batch_check_draft(B, c, tokens_out)) return false;
-    run->print_errors = ctx->print_errors;
-    BATCH_HIP_OK(B, hipSetDevice(ctx->model->device));
+    if (!batch_begin(B) || !batch_check_args(B, c, false, &T) || !batch_check_draft(B, c, tokens_out)) return false;
     if (!batch_ensure_draw(B, c) || !batch_ensure_draft(B, T)) return false;
     if (!batch_upload_call(B, c, T, true)) return false;   // (loop: the generator draws, every step records)
     const Model & m = *ctx->model;
@@ -1587,53 +1630,7 @@ static bool batch_draft(rwkv_mi_batch * B, const BatchCall & c, uint32_t * token
     return true;
 }
 
-// The device loop: n_tokens passes of one token per row, each row's next token chosen on the device -- its argmax, or the call's draw.
-// tokens_out: [n][n_tokens]. The plain sampled loop starts the named slots' draw counters from 0. The penalised loop CONTINUES: the named
-// slots' counts and draw counters are where the caller left them, and every step records.
-static bool batch_loop(rwkv_mi_batch * B, const BatchCall & c, size_t n_tokens, uint32_t * tokens_out, float * elapsed_ms) {
-    rwkv_context * ctx = B->ctx;
-    rwkv_context * run = B->run;
-    ctx->last_error = RWKV_ERROR_NONE;
-    size_t T = 0;
-    if (!batch_check_args(B, c, false, &T)) return false;
-    if (c.draw == Draw::none && !batch_check_unguided(B, c.slots, c.n, "the greedy loop")) return false;
-    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, n_tokens > 0, "n_tokens is 0");
-    run->print_errors = ctx->print_errors;
-    const size_t n = c.n;
-    const bool drawn = c.draw != Draw::none;
-    BATCH_HIP_OK(B, hipSetDevice(ctx->model->device));
-    if (!batch_ensure_draw(B, c)) return false;
-    DevBuf<uint32_t> hist;   // [n_tokens][n], freed on every exit
-    BATCH_HIP_OK(B, hist.alloc(n_tokens * n));
-    const bool report = B->lp.enabled;   // (every step of a loop emits)
-    if (!batch_ensure_report(B, n, n_tokens)) return false;
-    if (!batch_upload_call(B, c, T, true)) return false;
-    if (c.draw == Draw::sample) launch_sample_seek_rows(B->d_draw_rows.p, (int64_t) n, 0ull, run->stream);   // the named slots' streams start over
-    BATCH_HIP_OK(B, hipEventRecord(run->ev0, run->stream));
-    const RowReport rep = batch_report(B);
-    RowSampler sampler = batch_sampler(B, hist.p, report ? &rep : nullptr);
-    for (size_t i = 0; i < n_tokens; i++) {
-        // step i reads the buffers step i - 1 wrote: the two row tables alternate; the token of each row -- sampled inside the pass's chain
-        // bracket, or its argmax after it -- lands where its next embedding lookup reads it
-        sampler.step = (uint32_t) i;
-        if (!forward_rows(run, B->d_rows.p + (i & 1) * B->n_slots, (int64_t) n, true, drawn ? &sampler : nullptr)) return batch_fail_drained(B);
-        // the greedy argmax, and its report directly behind it: the event the device's next persistent launch waits on is recorded after both
-        if (!drawn) launch_row_sampler(run, sampler, (int64_t) n);
-    }
-    BATCH_HIP_OK(B, hipEventRecord(run->ev1, run->stream));
-    std::vector<uint32_t> h(tokens_out ? n_tokens * n : 0);
-    if (tokens_out) BATCH_HIP_OK(B, hipMemcpyAsync(h.data(), hist.p, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream));
-    BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));
-    if (elapsed_ms) BATCH_HIP_OK(B, hipEventElapsedTime(elapsed_ms, run->ev0, run->ev1));
-    for (size_t r = 0; r < n && tokens_out; r++)
-        for (size_t i = 0; i < n_tokens; i++) tokens_out[r * n_tokens + i] = h[i * n + r];
-    if (n_tokens & 1) batch_flip(B, c);
-    B->last_loop_passes = n_tokens;
-    if (report) report_done(B->lp, n, n_tokens, nullptr);
-    return true;
-}
-
-// passes per block of batch_until: 16, or RWKV_MI_LOOP_BLOCK in 1 .. 1024 (read at the call)
+// passes per block of a polled device loop: 16, or RWKV_MI_LOOP_BLOCK in 1 .. 1024 (read at the call)
 static size_t loop_block() {
     const char * e = getenv("RWKV_MI_LOOP_BLOCK");
     if (!e || !e[0]) return 16;
@@ -1642,23 +1639,99 @@ static size_t loop_block() {
     return (*end == 0 && v >= 1 && v <= 1024) ? (size_t) v : 16;
 }
 
+// The passes of a device loop, between the two events its time is taken from. Pass i runs on row table i & 1 and reads the buffers pass i - 1
+// wrote; the driver gives the sampler the pass's step and tables (used: this pass's, other: the next one's -- what the loop's kernels rewrite
+// to retire, admit or re-parent a row) and `step` enqueues the pass. With a poll_word -- a device word that is 0 once no row has anything
+// left to do -- the host decides when to stop enqueuing: passes go out in blocks of K; behind each block the word is copied to pinned memory
+// and an event recorded; after enqueuing block b the host waits for the event of block b - 1 (which has long passed, or passes while block b
+// runs: the device is never idle for it) and stops when that count is 0. Passes past the end of the work are dead steps, at most 2 K of
+// them. Without one, all max_passes passes are enqueued and nothing waits. A pass that could not be launched, or a failed poll, drains the
+// stream before the call returns (what has been enqueued reads the staging). B->last_loop_passes: the passes enqueued. A step may enqueue
+// more than its pass: what it puts in front of pass 0 (batch_serve's first admission) lies behind ev0, inside the time the loop reports.
+template <typename Step>
+static bool batch_run_passes(rwkv_mi_batch * B, size_t max_passes, const uint32_t * poll_word, RowSampler & sampler, Step step) {
+    rwkv_context * run = B->run;
+    const size_t K = poll_word ? loop_block() : max_passes;
+    BATCH_HIP_OK(B, hipEventRecord(run->ev0, run->stream));
+    size_t passes = 0;
+    for (size_t b = 0; passes < max_passes; b++) {
+        for (const size_t end = std::min(max_passes, passes + K); passes < end; passes++) {
+            sampler.step = (uint32_t) passes;
+            sampler.used = B->d_rows.p + (passes & 1) * B->n_slots; sampler.other = B->d_rows.p + ((passes & 1) ^ 1) * B->n_slots;
+            if (!step(sampler)) return batch_fail_drained(B);
+        }
+        if (!poll_word) break;
+        hipError_t e = hipMemcpyAsync(B->poll.count.p + (b & 1), poll_word, sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream);
+        if (e == hipSuccess) e = hipEventRecord(B->poll.ev[b & 1], run->stream);
+        if (e == hipSuccess && b > 0) e = hipEventSynchronize(B->poll.ev[(b - 1) & 1]);
+        if (e != hipSuccess) { (void) hipStreamSynchronize(run->stream); BATCH_HIP_OK(B, e); }
+        if (b > 0 && B->poll.count.p[(b - 1) & 1] == 0) break;
+    }
+    BATCH_HIP_OK(B, hipEventRecord(run->ev1, run->stream));
+    B->last_loop_passes = passes;
+    return true;
+}
+
+// what ends every loop, behind the copies of its results: the stream drained, the time between the driver's two events
+static bool batch_passes_done(rwkv_mi_batch * B, float * elapsed_ms) {
+    rwkv_context * run = B->run;
+    BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));
+    if (elapsed_ms) BATCH_HIP_OK(B, hipEventElapsedTime(elapsed_ms, run->ev0, run->ev1));
+    return true;
+}
+
+// The device loop: n_tokens passes of one token per row, each row's next token chosen on the device -- its argmax, or the call's draw.
+// tokens_out: [n][n_tokens]. The plain sampled loop starts the named slots' draw counters from 0. The penalised loop CONTINUES: the named
+// slots' counts and draw counters are where the caller left them, and every step records.
+static bool batch_loop(rwkv_mi_batch * B, const BatchCall & c, size_t n_tokens, uint32_t * tokens_out, float * elapsed_ms) {
+    rwkv_context * ctx = B->ctx;
+    rwkv_context * run = B->run;
+    size_t T = 0;
+    if (!batch_begin(B) || !batch_check_args(B, c, false, &T)) return false;
+    if (c.draw == Draw::none && !batch_check_unguided(B, c.slots, c.n, "the greedy loop")) return false;
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, n_tokens > 0, "n_tokens is 0");
+    const size_t n = c.n;
+    const bool drawn = c.draw != Draw::none;
+    if (!batch_ensure_draw(B, c)) return false;
+    DevBuf<uint32_t> hist;   // [n_tokens][n], freed on every exit
+    BATCH_HIP_OK(B, hist.alloc(n_tokens * n));
+    const bool report = B->lp.enabled;   // (every step of a loop emits)
+    if (!batch_ensure_report(B, n, n_tokens)) return false;
+    if (!batch_upload_call(B, c, T, true)) return false;
+    if (c.draw == Draw::sample) launch_sample_seek_rows(B->d_draw_rows.p, (int64_t) n, 0ull, run->stream);   // the named slots' streams start over
+    const RowReport rep = batch_report(B);
+    RowSampler sampler = batch_sampler(B, hist.p, report ? &rep : nullptr);
+    // the token of each row lands where its next embedding lookup reads it: sampled inside the pass's chain bracket, or -- the greedy argmax,
+    // its report directly behind it -- after the bracket: the event the device's next persistent launch waits on is recorded after both
+    const auto step = [&](const RowSampler & s) {
+        if (!forward_rows(run, s.used, (int64_t) n, true, drawn ? &s : nullptr)) return false;
+        if (!drawn) launch_row_sampler(run, s, (int64_t) n);
+        return true;
+    };
+    if (!batch_run_passes(B, n_tokens, nullptr, sampler, step)) return false;
+    std::vector<uint32_t> h(tokens_out ? n_tokens * n : 0);
+    if (tokens_out) BATCH_HIP_OK(B, hipMemcpyAsync(h.data(), hist.p, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream));
+    if (!batch_passes_done(B, elapsed_ms)) return false;
+    for (size_t r = 0; r < n && tokens_out; r++)
+        for (size_t i = 0; i < n_tokens; i++) tokens_out[r * n_tokens + i] = h[i * n + r];
+    if (n_tokens & 1) batch_flip(B, c);
+    if (report) report_done(B->lp, n, n_tokens, nullptr);
+    return true;
+}
+
 // The device loop in which every row ends by itself (rwkv_mi_batch_decode_until): batch_loop's passes, the draw behind the rows' live words and
 // followed by the stop test (engine.hip launch_row_sampler, sampling.hip k_stop_rows), which retires a row ON THE DEVICE by rewriting its entries
-// of the two row tables -- the model's kernels never learn of it. What the host adds is when to stop enqueuing: passes go out in blocks of K; behind
-// each block the live count is copied to pinned memory and an event recorded; after enqueuing block b the host waits for the event of block
-// b - 1 (which has long passed, or passes while block b runs: the device is never idle for it) and stops when that count is 0. Passes past a
-// row's retirement are dead steps into the row's other buffer: at most 2 K of them run after the last row has retired.
+// of the two row tables -- the model's kernels never learn of it. The driver polls the live count. Passes past a row's retirement are dead
+// steps into the row's other buffer.
 static bool batch_until(rwkv_mi_batch * B, const BatchCall & c, uint32_t * tokens_out, float * elapsed_ms) {
     rwkv_context * ctx = B->ctx;
     rwkv_context * run = B->run;
     size_t T = 0;
-    if (!batch_check_args(B, c, false, &T)) return false;
+    if (!batch_begin(B) || !batch_check_args(B, c, false, &T)) return false;
     if (c.draw == Draw::none && !batch_check_unguided(B, c.slots, c.n, "the greedy loop")) return false;
-    run->print_errors = ctx->print_errors;
-    const size_t n = c.n, K = loop_block();
+    const size_t n = c.n;
     size_t budget = 0;
     for (size_t i = 0; i < n; i++) budget = std::max(budget, (size_t) c.stops[i].max_tokens);
-    BATCH_HIP_OK(B, hipSetDevice(ctx->model->device));
     if (!batch_ensure_draw(B, c)) return false;
     DevBuf<uint32_t> hist;   // [budget][n], freed on every exit; a word no row wrote stays RWKV_MI_NO_TOKEN
     hipError_t he = hist.alloc(budget * n);
@@ -1669,32 +1742,16 @@ static bool batch_until(rwkv_mi_batch * B, const BatchCall & c, uint32_t * token
     if (!batch_upload_call(B, c, T, true)) return false;
     if (c.draw == Draw::sample) launch_sample_seek_rows(B->d_draw_rows.p, (int64_t) n, 0ull, run->stream);   // the named slots' streams start over
     BATCH_HIP_OK(B, hipMemsetAsync(hist.p, 0xFF, budget * n * sizeof(uint32_t), run->stream));
-    BATCH_HIP_OK(B, hipEventRecord(run->ev0, run->stream));
     const RowReport rep = batch_report(B);
     RowSampler sampler = batch_sampler(B, hist.p, report ? &rep : nullptr);
-    RowStop stop{B->stop, nullptr, nullptr};
-    sampler.stop = &stop;
-    size_t passes = 0;
-    for (size_t b = 0; passes < budget; b++) {
-        for (const size_t end = std::min(budget, passes + K); passes < end; passes++) {
-            stop.used = B->d_rows.p + (passes & 1) * B->n_slots; stop.other = B->d_rows.p + ((passes & 1) ^ 1) * B->n_slots;
-            sampler.step = (uint32_t) passes;
-            if (!forward_rows(run, stop.used, (int64_t) n, true, &sampler)) return batch_fail_drained(B);
-        }
-        hipError_t e = hipMemcpyAsync(B->h_live_count.p + (b & 1), B->stop.live_count, sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream);
-        if (e == hipSuccess) e = hipEventRecord(B->ev_block[b & 1], run->stream);
-        if (e == hipSuccess && b > 0) e = hipEventSynchronize(B->ev_block[(b - 1) & 1]);
-        if (e != hipSuccess) { (void) hipStreamSynchronize(run->stream); BATCH_HIP_OK(B, e); }
-        if (b > 0 && B->h_live_count.p[(b - 1) & 1] == 0) break;
-    }
-    BATCH_HIP_OK(B, hipEventRecord(run->ev1, run->stream));
+    sampler.stop = &B->stop;
+    if (!batch_run_passes(B, budget, B->stop.live_count, sampler, [&](const RowSampler & s) { return forward_rows(run, s.used, (int64_t) n, true, &s); })) return false;
+    const size_t passes = B->last_loop_passes;
     std::vector<uint32_t> h(tokens_out ? passes * n : 0);
     uint32_t * h_lens = (uint32_t *) (B->h_stop.p + B->stop_off_lens);   // lens[n], then reasons[n]
     if (tokens_out) BATCH_HIP_OK(B, hipMemcpyAsync(h.data(), hist.p, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream));
     BATCH_HIP_OK(B, hipMemcpyAsync(h_lens, B->stop.lens, 2 * n * sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream));
-    BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));
-    if (elapsed_ms) BATCH_HIP_OK(B, hipEventElapsedTime(elapsed_ms, run->ev0, run->ev1));
-    B->last_loop_passes = passes;
+    if (!batch_passes_done(B, elapsed_ms)) return false;
     // (every budget is at most `budget`, and the loop ends on a live count of 0 or at `budget`: every row has retired)
     for (size_t r = 0; r < n; r++)
         RW_CTX_CHECK(ctx, RWKV_ERROR_GRAPH, false, h_lens[r] > 0 && h_lens[r] <= passes, "row %zu did not retire (the device loop failed)", r);
@@ -1768,24 +1825,21 @@ static bool batch_check_serve(rwkv_mi_batch * B, const BatchCall & c, size_t * n
         RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, c.prompts[t] < n_vocab, "Prompt token at index %zu (%" PRIu32 ") is out of range (0 .. %zu)", t, c.prompts[t], n_vocab - 1);
     if (c.draw != Draw::none && !batch_check_params(B, sp.data(), R, false)) return false;
     if (c.draw == Draw::penalized && !batch_check_penalties(B, pp.data(), R)) return false;
-    BatchCall s = c;   // the requests' budgets and sequences, by the rules of rwkv_mi_batch_decode_until
-    s.n = R; s.stops = st.data();
-    if (!batch_check_stops(B, s)) return false;
+    // the requests' budgets and sequences, by the rules of rwkv_mi_batch_decode_until
+    if (!batch_check_stops(B, st.data(), R, c.seq_lens, c.seq_tokens, c.stride, c.lens_out)) return false;
     *n_prompt_out = (size_t) P;
     return true;
 }
 
-// the serve buffer for `bytes`, and on the first call the fresh state and the two block events with their pinned counts: one decision
+// the poll words of the batch; the serve buffer for `bytes` and, on the first call, the fresh state: one decision
 static bool batch_ensure_serve(rwkv_mi_batch * B, size_t bytes) {
     rwkv_context * ctx = B->ctx;
     const Model & m = *ctx->model;
     hipStream_t st = B->run->stream;
     const bool more = bytes > B->d_serve.count, first = !B->serve_fresh;
     if (more) BATCH_HIP_OK(B, hipStreamSynchronize(st));   // (an earlier call may still read the old one)
-    hipError_t e = grow(want(B->d_serve, more ? bytes : 0), want(B->h_serve, more ? bytes : 0), want(B->serve_fresh, first ? (size_t) B->state_len : 0),
-                        want(B->h_live_count, B->h_live_count ? 0 : 2));
-    for (hipEvent_t & ev : B->ev_block) if (e == hipSuccess && !ev) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-    if (e != hipSuccess) (void) hipGetLastError();
+    hipError_t e = B->poll.ensure();
+    if (e == hipSuccess) e = grow(want(B->d_serve, more ? bytes : 0), want(B->h_serve, more ? bytes : 0), want(B->serve_fresh, first ? (size_t) B->state_len : 0));
     RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the serve tables (%zu bytes): %s", bytes, hipGetErrorString(e));
     if (first) {
         if (m.arch_major >= 5) e = hipMemsetAsync(B->serve_fresh.p, 0, (size_t) B->state_len * sizeof(float), st);
@@ -1803,31 +1857,29 @@ static unsigned serve_chunks(int64_t state_len) {
     return (unsigned) std::min<int64_t>(std::max<int64_t>(c, 1), 256);
 }
 
-// The device loop with a queue behind it (rwkv_mi_batch_serve): batch_until's passes and blocks, the draw behind the lanes' DRAW words and
+// The device loop with a queue behind it (rwkv_mi_batch_serve): the driver's passes, the draw behind the lanes' DRAW words and
 // followed by the scheduler (engine.hip launch_row_sampler; sampling.hip k_serve_rows, k_serve_reset), which emits, feeds prompts, retires and
 // admits ON THE DEVICE: between two passes it rewrites a lane's token word, draw row and words and has the request's start state copied into
 // the buffer the lane's next pass reads. The model's kernels never learn of it. The admission in front of pass 0 is the same two kernels.
-// The host polls the number of lanes with work as batch_until polls its live rows, and never enqueues more passes than the queue can need.
+// The driver polls the number of lanes with work, and never enqueues more passes than the queue can need.
 static bool batch_serve(rwkv_mi_batch * B, const BatchCall & c, uint32_t * tokens_out, float * elapsed_ms) {
     rwkv_context * ctx = B->ctx;
     rwkv_context * run = B->run;
     size_t n_prompt = 0;
-    if (!batch_check_serve(B, c, &n_prompt)) return false;
-    run->print_errors = ctx->print_errors;
+    if (!batch_begin(B) || !batch_check_serve(B, c, &n_prompt)) return false;
     const Model & m = *ctx->model;
-    const size_t n = c.n, R = c.n_requests, K = loop_block(), n_vocab = (size_t) m.n_vocab();
+    const size_t n = c.n, R = c.n_requests, n_vocab = (size_t) m.n_vocab();
     const bool pen = c.draw == Draw::penalized;
     size_t n_seqs = 0, n_toks = 0, bound = 0;
     bool any_cut = false, any_rep = false;
+    std::vector<StopRow> stop_rows(R);
     for (size_t q = 0; q < R; q++) {
         const rwkv_mi_serve_request & rq = c.requests[q];
-        n_seqs += rq.stop.n_seqs;
+        stop_rows[q] = stop_row(rq.stop, c.seq_lens, &n_seqs, &n_toks);
         bound += (size_t) rq.prompt_len - 1 + rq.stop.max_tokens;   // (a lane with work advances its request by one pass: no schedule needs more)
         any_cut |= (rq.top_k != 0u && rq.top_k < n_vocab) || rq.min_p != 0.0f;
         any_rep |= rq.decay != 1.0f || rq.repetition != 1.0f;
     }
-    for (size_t s = 0; s < n_seqs; s++) n_toks += c.seq_lens[s];
-    BATCH_HIP_OK(B, hipSetDevice(m.device));
     BatchCall lanes{c.slots, nullptr, n};
     lanes.draw = c.draw;
     if (!batch_ensure_draw(B, lanes)) return false;   // (the draw buffers of the family; the form it derives from the lanes' own settings ...)
@@ -1839,7 +1891,7 @@ static bool batch_serve(rwkv_mi_batch * B, const BatchCall & c, uint32_t * token
     auto hw = [h](size_t off) { return (uint32_t *) (h + off); };
     auto dw = [d](size_t off) { return (uint32_t *) (d + off); };
     ServeReq * reqs = (ServeReq *) (h + L.reqs);
-    size_t p0 = 0, s0 = 0, t0 = 0;
+    size_t p0 = 0;
     for (size_t q = 0; q < R; q++) {
         const rwkv_mi_serve_request & rq = c.requests[q];
         // (the row of DrawState::row for a loop: the generator draws, every penalised draw records; the counter and the occurrence row are the
@@ -1849,58 +1901,38 @@ static bool batch_serve(rwkv_mi_batch * B, const BatchCall & c, uint32_t * token
         row.presence = pen ? rq.penalty.presence : 0.0f; row.frequency = pen ? rq.penalty.frequency : 0.0f; row.record = pen ? 1u : 0u;
         row.top_k = rq.top_k; row.min_p = rq.min_p; row.decay = rq.decay; row.repetition = rq.repetition;
         const float * start = rq.from_slot == RWKV_MI_NO_SLOT ? B->serve_fresh.p : B->slot_buf(rq.from_slot, B->parity[rq.from_slot]);
-        reqs[q] = ServeReq{row, StopRow{rq.stop.max_tokens, rq.stop.n_seqs, (uint32_t) s0, (uint32_t) t0}, rq.prompt_len, (uint32_t) p0, start};
+        reqs[q] = ServeReq{row, stop_rows[q], rq.prompt_len, (uint32_t) p0, start};
         p0 += rq.prompt_len;
-        for (uint32_t s = 0; s < rq.stop.n_seqs; s++) t0 += c.seq_lens[s0 + s];
-        s0 += rq.stop.n_seqs;
     }
     memcpy(h + L.prompts, c.prompts, n_prompt * 4);
     if (n_seqs) memcpy(h + L.seq_lens, c.seq_lens, n_seqs * 4);
     if (n_toks) memcpy(h + L.seq_tokens, c.seq_tokens, n_toks * 4);
-    for (size_t r = 0; r < n; r++) {
-        hw(L.lane_slot)[r] = c.slots[r]; hw(L.req)[r] = SERVE_FREE; hw(L.pos)[r] = 0u; hw(L.draw)[r] = 0u; hw(L.admit)[r] = 0u; hw(L.last)[r] = RWKV_MI_NO_TOKEN;
-        for (int tb = 0; tb < 2; tb++) {
-            const int p = B->parity[c.slots[r]] ^ tb;
-            B->h_rows.p[(size_t) tb * B->n_slots + r] = RowState{B->slot_buf(c.slots[r], p), B->slot_buf(c.slots[r], p ^ 1)};
-        }
-    }
+    for (size_t r = 0; r < n; r++) { hw(L.lane_slot)[r] = c.slots[r]; hw(L.req)[r] = SERVE_FREE; hw(L.pos)[r] = 0u; hw(L.draw)[r] = 0u; hw(L.admit)[r] = 0u; hw(L.last)[r] = RWKV_MI_NO_TOKEN; }
+    batch_stage_rows(B, c.slots, n, 2);
     *hw(L.next) = 0u; *hw(L.work) = (uint32_t) n;
     for (size_t q = 0; q < R; q++) { hw(L.lens)[q] = 0u; hw(L.reasons)[q] = RWKV_MI_NO_TOKEN; hw(L.lane)[q] = RWKV_MI_NO_TOKEN; hw(L.start)[q] = RWKV_MI_NO_TOKEN; }
     BATCH_HIP_OK(B, hipMemcpyAsync(d, h, L.out, hipMemcpyHostToDevice, run->stream));
     BATCH_HIP_OK(B, hipMemsetAsync(d + L.out, 0xFF, R * c.stride * 4, run->stream));
-    for (int tb = 0; tb < 2; tb++)
-        BATCH_HIP_OK(B, hipMemcpyAsync(B->d_rows.p + (size_t) tb * B->n_slots, B->h_rows.p + (size_t) tb * B->n_slots, n * sizeof(RowState), hipMemcpyHostToDevice, run->stream));
+    if (!batch_upload_rows(B, n, 2)) return false;
     RowServe serve{};
     serve.t = ServeTables{(const ServeReq *) (d + L.reqs), dw(L.prompts), dw(L.seq_lens), dw(L.seq_tokens), dw(L.out), (uint32_t) c.stride,
                           dw(L.lens), dw(L.reasons), dw(L.lane), dw(L.start), dw(L.req), dw(L.pos), dw(L.draw), dw(L.admit), dw(L.last), dw(L.lane_slot),
                           c.draw != Draw::none ? B->d_draw_rows.p : nullptr, B->draw.counters.p, B->draw.counts.p, dw(L.next), dw(L.work),
                           (uint32_t) R, (uint32_t) n_vocab};
     serve.state_len = B->state_len; serve.chunks = serve_chunks(B->state_len);
-    RowState * const table[2] = {B->d_rows.p, B->d_rows.p + B->n_slots};
-    BATCH_HIP_OK(B, hipEventRecord(run->ev0, run->stream));
-    // lane r takes request r: the admission in front of pass 0 copies into what table[1] writes, which is what pass 0 reads
-    launch_serve_rows(serve.t, (int64_t) n, run->d_tokens.p, UINT32_MAX, table[1], table[0], run->stream);
-    launch_serve_reset(serve.t, (int64_t) n, serve.chunks, table[1], serve.state_len, run->stream);
     RowSampler sampler = batch_sampler(B, nullptr, nullptr);
     sampler.serve = &serve;
-    size_t passes = 0;
-    for (size_t b = 0; passes < bound; b++) {
-        for (const size_t end = std::min(bound, passes + K); passes < end; passes++) {
-            serve.used = table[passes & 1]; serve.other = table[(passes & 1) ^ 1];
-            sampler.step = (uint32_t) passes;
-            if (!forward_rows(run, serve.used, (int64_t) n, true, &sampler)) return batch_fail_drained(B);
+    const auto step = [&](const RowSampler & s) {
+        if (s.step == 0) {
+            // lane r takes request r: the admission in front of pass 0 copies into what the table of pass 1 writes, which is what pass 0 reads
+            launch_serve_rows(serve.t, (int64_t) n, run->d_tokens.p, UINT32_MAX, s.other, s.used, run->stream);
+            launch_serve_reset(serve.t, (int64_t) n, serve.chunks, s.other, serve.state_len, run->stream);
         }
-        hipError_t e = hipMemcpyAsync(B->h_live_count.p + (b & 1), serve.t.work, sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream);
-        if (e == hipSuccess) e = hipEventRecord(B->ev_block[b & 1], run->stream);
-        if (e == hipSuccess && b > 0) e = hipEventSynchronize(B->ev_block[(b - 1) & 1]);
-        if (e != hipSuccess) { (void) hipStreamSynchronize(run->stream); BATCH_HIP_OK(B, e); }
-        if (b > 0 && B->h_live_count.p[(b - 1) & 1] == 0) break;
-    }
-    BATCH_HIP_OK(B, hipEventRecord(run->ev1, run->stream));
+        return forward_rows(run, s.used, (int64_t) n, true, &s);
+    };
+    if (!batch_run_passes(B, bound, serve.t.work, sampler, step)) return false;
     BATCH_HIP_OK(B, hipMemcpyAsync(h + L.down, d + L.down, L.bytes - L.down, hipMemcpyDeviceToHost, run->stream));
-    BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));
-    if (elapsed_ms) BATCH_HIP_OK(B, hipEventElapsedTime(elapsed_ms, run->ev0, run->ev1));
-    B->last_loop_passes = passes;
+    if (!batch_passes_done(B, elapsed_ms)) return false;
     const uint32_t * lens = hw(L.lens), * reasons = hw(L.reasons), * lane = hw(L.lane), * start = hw(L.start), * last = hw(L.last), * out = hw(L.out);
     // (the queue's work fits the bound, and the loop ends on a work count of 0 or at the bound: every request has been served to its end)
     for (size_t q = 0; q < R; q++)
@@ -1965,19 +1997,16 @@ static bool batch_check_beam(rwkv_mi_batch * B, const BeamCall & c) {
     return batch_check_unguided(B, c.slots, c.G * W, "beam search");
 }
 
-// the beam words, the live count's pinned words and the two block events: on the first beam call
+// the poll words of the batch and the beam words: on the first beam call
 static bool batch_ensure_beam(rwkv_mi_batch * B) {
-    rwkv_context * ctx = B->ctx;
-    if (B->d_beam && B->h_beam && B->h_live_count && B->ev_block[0] && B->ev_block[1]) return true;
     const BeamLayout L(B->n_slots);
-    hipError_t e = grow(want(B->d_beam, B->d_beam ? 0 : L.bytes), want(B->h_beam, B->h_beam ? 0 : L.upload), want(B->h_live_count, B->h_live_count ? 0 : 2));
-    for (hipEvent_t & ev : B->ev_block) if (e == hipSuccess && !ev) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-    if (e != hipSuccess) (void) hipGetLastError();
-    RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the beam tables of %zu slots: %s", B->n_slots, hipGetErrorString(e));
+    hipError_t e = B->poll.ensure();
+    if (e == hipSuccess && !B->d_beam) e = grow(want(B->d_beam, L.bytes), want(B->h_beam, L.upload));   // (one decision: both or neither)
+    RW_CTX_CHECK(B->ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the beam tables of %zu slots: %s", B->n_slots, hipGetErrorString(e));
     return true;
 }
 
-// The device loop of a beam search: batch_until's blocks of passes, each pass followed by the two kernels of a step (engine.hip launch_row_sampler,
+// The device loop of a beam search: the driver's passes, polled on the unfinished hypotheses, each pass followed by the two kernels of a step (engine.hip launch_row_sampler,
 // score.hip k_beam_rows / k_beam_select). A step RE-PARENTS instead of copying: the selection writes, into the row table of the next pass, for
 // every row the buffer its parent has just written as .in; .out stays the row's own slot's other buffer. Every read of a pass is of a buffer
 // the pass before wrote (the first: the group's start buffer), every write goes to the other buffer of a named slot -- no pass writes what it
@@ -1986,11 +2015,8 @@ static bool batch_ensure_beam(rwkv_mi_batch * B) {
 static bool batch_beam(rwkv_mi_batch * B, const BeamCall & c, uint32_t * tokens_out, uint32_t * lens_out, double * scores_out, float * logprobs_out, float * elapsed_ms) {
     rwkv_context * ctx = B->ctx;
     rwkv_context * run = B->run;
-    ctx->last_error = RWKV_ERROR_NONE;
-    if (!batch_check_beam(B, c)) return false;
-    run->print_errors = ctx->print_errors;
-    const size_t W = c.p->width, n = c.G * W, n_tokens = c.n_tokens, K = loop_block();
-    BATCH_HIP_OK(B, hipSetDevice(ctx->model->device));
+    if (!batch_begin(B) || !batch_check_beam(B, c)) return false;
+    const size_t W = c.p->width, n = c.G * W, n_tokens = c.n_tokens;
     if (!batch_ensure_beam(B)) return false;
     DevBuf<uint32_t> hist;   // token, parent, log-prob: [3][n_tokens][n], freed on every exit
     hipError_t he = hist.alloc(3 * n_tokens * n);
@@ -2012,38 +2038,22 @@ static bool batch_beam(rwkv_mi_batch * B, const BeamCall & c, uint32_t * tokens_
         h_fin[r] = 0u; h_len[r] = 0u;
     }
     *(uint32_t *) (B->h_beam.p + L.count) = (uint32_t) n;
-    for (int tb = 0; tb < 2; tb++)
-        BATCH_HIP_OK(B, hipMemcpyAsync(B->d_rows.p + (size_t) tb * B->n_slots, B->h_rows.p + (size_t) tb * B->n_slots, n * sizeof(RowState), hipMemcpyHostToDevice, run->stream));
+    if (!batch_upload_rows(B, n, 2)) return false;
     BATCH_HIP_OK(B, hipMemcpyAsync(run->d_tokens.p, run->h_tokens.p, n * sizeof(uint32_t), hipMemcpyHostToDevice, run->stream));
     BATCH_HIP_OK(B, hipMemcpyAsync(B->d_beam.p, B->h_beam.p, L.upload, hipMemcpyHostToDevice, run->stream));
     uint8_t * d = B->d_beam.p;
     BeamTables t{(double *) d, (uint32_t *) (d + L.finished), (uint32_t *) (d + L.lens), (uint32_t *) (d + L.ids), (float *) (d + L.lp), (float *) (d + L.chosen),
                  hist.p, hist.p + n_tokens * n, (float *) (hist.p + 2 * n_tokens * n), (uint32_t *) (d + L.count), (uint32_t) W, c.p->n_end, {}};
     for (uint32_t e = 0; e < c.p->n_end; e++) t.end_tokens[e] = c.p->end_tokens[e];
-    BATCH_HIP_OK(B, hipEventRecord(run->ev0, run->stream));
-    size_t passes = 0;
-    for (size_t b = 0; passes < n_tokens; b++) {
-        for (const size_t end = std::min(n_tokens, passes + K); passes < end; passes++) {
-            RowState * used = B->d_rows.p + (passes & 1) * B->n_slots, * other = B->d_rows.p + ((passes & 1) ^ 1) * B->n_slots;
-            const RowBeam beam{t, used, other};
-            RowSampler sampler;
-            sampler.beam = &beam; sampler.step = (uint32_t) passes;
-            if (!forward_rows(run, used, (int64_t) n, true, &sampler)) return batch_fail_drained(B);
-        }
-        hipError_t e = hipMemcpyAsync(B->h_live_count.p + (b & 1), t.live_count, sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream);
-        if (e == hipSuccess) e = hipEventRecord(B->ev_block[b & 1], run->stream);
-        if (e == hipSuccess && b > 0) e = hipEventSynchronize(B->ev_block[(b - 1) & 1]);
-        if (e != hipSuccess) { (void) hipStreamSynchronize(run->stream); BATCH_HIP_OK(B, e); }
-        if (b > 0 && B->h_live_count.p[(b - 1) & 1] == 0) break;
-    }
-    BATCH_HIP_OK(B, hipEventRecord(run->ev1, run->stream));
+    RowSampler sampler;
+    sampler.beam = &t;
+    if (!batch_run_passes(B, n_tokens, t.live_count, sampler, [&](const RowSampler & s) { return forward_rows(run, s.used, (int64_t) n, true, &s); })) return false;
+    const size_t passes = B->last_loop_passes;
     std::vector<uint32_t> h(3 * passes * n);
     for (size_t a = 0; a < 3; a++)
         BATCH_HIP_OK(B, hipMemcpyAsync(h.data() + a * passes * n, hist.p + a * n_tokens * n, passes * n * sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream));
     BATCH_HIP_OK(B, hipMemcpyAsync(B->h_beam.p, B->d_beam.p, L.count, hipMemcpyDeviceToHost, run->stream));
-    BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));
-    if (elapsed_ms) BATCH_HIP_OK(B, hipEventElapsedTime(elapsed_ms, run->ev0, run->ev1));
-    B->last_loop_passes = passes;
+    if (!batch_passes_done(B, elapsed_ms)) return false;
     const uint32_t * h_tok = h.data(), * h_par = h.data() + passes * n;
     const float * h_lp = (const float *) (h.data() + 2 * passes * n);
     // the backtrace: hypothesis j of the last selection, then its parent's of the step before, ...; a step without a token (the hypothesis
@@ -2091,9 +2101,8 @@ RWKV_API void rwkv_mi_batch_free(struct rwkv_mi_batch * B) {
         (void) hipSetDevice(B->run->model->device);
         (void) hipStreamSynchronize(B->run->stream);
     }
-    for (hipEvent_t ev : B->ev_block) if (ev) (void) hipEventDestroy(ev);
     rwkv_context * run = B->run;
-    delete B;   // its buffers: after the drain above, before the batch's own context gives up its stream and its reference to the model
+    delete B;   // its buffers and block events: after the drain above, before the batch's own context gives up its stream and its reference to the model
     batch_context_destroy(run);
 }
 

@@ -854,8 +854,8 @@ void launch_row_sampler(rwkv_context * ctx, const RowSampler & s, int64_t rows) 
     uint32_t * tokens = ctx->d_tokens.p;
     if (s.beam) {
         // a step of rwkv_mi_batch_decode_beam: every row's candidates, then each group's selection (which writes the rows' next tokens)
-        launch_beam_rows(logits, rows, n_vocab, s.beam->t, ctx->stream);
-        launch_beam_select(s.beam->t, rows / (int64_t) s.beam->t.width, tokens, s.step, s.beam->used, s.beam->other, ctx->stream);
+        launch_beam_rows(logits, rows, n_vocab, *s.beam, ctx->stream);
+        launch_beam_select(*s.beam, rows / (int64_t) s.beam->width, tokens, s.step, s.used, s.other, ctx->stream);
         return;
     }
     if (const RowServe * sv = s.serve) {
@@ -863,19 +863,19 @@ void launch_row_sampler(rwkv_context * ctx, const RowSampler & s, int64_t rows) 
         // request's row), then the scheduler, then the admissions it decided
         if (s.form.draw != Draw::none) launch_draw_rows(logits, rows, n_vocab, s.rows, s.form, s.probs, tokens, nullptr, sv->t.draw, ctx->stream);
         else launch_argmax_live(logits, rows, n_vocab, tokens, nullptr, sv->t.draw, ctx->stream);
-        launch_serve_rows(sv->t, rows, tokens, s.step, sv->used, sv->other, ctx->stream);
-        launch_serve_reset(sv->t, rows, sv->chunks, sv->used, sv->state_len, ctx->stream);
+        launch_serve_rows(sv->t, rows, tokens, s.step, s.used, s.other, ctx->stream);
+        launch_serve_reset(sv->t, rows, sv->chunks, s.used, sv->state_len, ctx->stream);
         return;
     }
     const size_t at = (size_t) s.step * (size_t) rows;   // the step's slot of the call's history and report buffers
     uint32_t * hist = s.hist ? s.hist + at : nullptr;
-    const uint32_t * live = s.stop ? s.stop->t.live : nullptr;   // (rwkv_mi_batch_decode_until: everything but the stop test runs behind the live words)
+    const uint32_t * live = s.stop ? s.stop->live : nullptr;   // (rwkv_mi_batch_decode_until: everything but the stop test runs behind the live words)
     if (s.form.draw != Draw::none) launch_draw_rows(logits, rows, n_vocab, s.rows, s.form, s.probs, tokens, hist, live, ctx->stream);
     else if (live) launch_argmax_live(logits, rows, n_vocab, tokens, hist, live, ctx->stream);
     else launch_argmax(logits, rows, n_vocab, tokens, hist, ctx->stream);
     if (const RowReport * rp = s.report)
         launch_logprob_rows(logits, rows, n_vocab, tokens, (int) rp->top_n, rp->chosen + at, rp->ids + at * rp->top_n, rp->vals + at * rp->top_n, live, ctx->stream);
-    if (s.stop) launch_stop_rows(s.stop->t, rows, s.hist, s.step, s.stop->used, s.stop->other, ctx->stream);
+    if (s.stop) launch_stop_rows(*s.stop, rows, s.hist, s.step, s.used, s.other, ctx->stream);
 }
 
 // One pass of T rows, row t = one token (ctx->d_tokens.p[t]) of the sequence whose state is d_rows[t]. Logits: ctx->d_logits.p[T][n_vocab].

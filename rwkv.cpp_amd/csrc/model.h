@@ -455,16 +455,15 @@ void batch_context_destroy(rwkv_context * c);
 //           (one DrawRow per row of the pass) with the samplers' scratch
 //   hist, report, step   the call's WHOLE history [steps][rows] and report buffers (chosen [steps][rows], ids / vals [steps][rows][top_n]), either
 //           may be NULL, and the step of the call this pass is: the step's slot of each is written. A single pass is step 0
+//   used, other   in a device loop, whose kernels rewrite the row tables between two passes: the row table of this pass and the one of the next
 //   stop    the pass is a step of rwkv_mi_batch_decode_until: the choice and the report run behind the live words and launch_stop_rows follows them
 //   beam    the pass is a step of rwkv_mi_batch_decode_beam: instead of a choice, launch_beam_rows and launch_beam_select follow the head;
-//           of the rest only `step` is read
-// Order within a step: the choice, then the report of what it wrote, then the stop test.
-struct RowStop { StopTables t; RowState * used, * other; };
-struct RowReport { float * chosen; uint32_t * ids; float * vals; uint32_t top_n; };
-struct RowBeam { BeamTables t; const RowState * used; RowState * other; };
+//           of the rest only `step`, `used` and `other` are read
 //   serve   the pass is a step of rwkv_mi_batch_serve: the choice runs behind the lanes' draw words and writes no history; launch_serve_rows and
 //           launch_serve_reset (`chunks` workgroups per lane over state_len floats) follow it
-struct RowServe { ServeTables t; RowState * used, * other; int64_t state_len; unsigned chunks; };
+// Order within a step: the choice, then the report of what it wrote, then the stop test.
+struct RowReport { float * chosen; uint32_t * ids; float * vals; uint32_t top_n; };
+struct RowServe { ServeTables t; int64_t state_len; unsigned chunks; };
 struct RowSampler {
     DrawForm form;
     const DrawRow * rows = nullptr;
@@ -472,8 +471,9 @@ struct RowSampler {
     uint32_t * hist = nullptr;
     const RowReport * report = nullptr;
     uint32_t step = 0;
-    const RowStop * stop = nullptr;
-    const RowBeam * beam = nullptr;
+    RowState * used = nullptr, * other = nullptr;
+    const StopTables * stop = nullptr;
+    const BeamTables * beam = nullptr;
     const RowServe * serve = nullptr;
 };
 void launch_row_sampler(rwkv_context * ctx, const RowSampler & s, int64_t rows);

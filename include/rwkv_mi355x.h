@@ -620,8 +620,9 @@ RWKV_API bool rwkv_mi_counts_store_f32(struct rwkv_context * ctx, float * out /*
  * range; a lane with a guide attached or a bias set; a batch with the log-prob report on; and everything rwkv_mi_batch_decode_until,
  * rwkv_mi_batch_truncation_set and rwkv_mi_batch_repetition_set reject for the same fields. The buffers are allocated by the first call
  * (RWKV_ERROR_ALLOC when they cannot be) and released by rwkv_mi_batch_free. A failure after the first pass leaves the lanes unspecified.
- * OUT OF SCOPE: guides, bias and the report for served requests; chunked prompt ingestion inside the loop (take a long prompt in with
- * rwkv_mi_batch_eval_ragged into a from_slot); requests that arrive during the call; compacting dead lanes. */
+ * Guides, bias and the report for served requests are rwkv_mi_batch_serve_ex's, below.
+ * OUT OF SCOPE: chunked prompt ingestion inside the loop (take a long prompt in with rwkv_mi_batch_eval_ragged into a from_slot); requests
+ * that arrive during the call; compacting dead lanes. */
 #define RWKV_MI_NO_SLOT          UINT32_MAX
 #define RWKV_MI_SERVE_GREEDY     0
 #define RWKV_MI_SERVE_SAMPLE     1
@@ -641,6 +642,50 @@ RWKV_API bool rwkv_mi_batch_serve(struct rwkv_mi_batch * batch, const uint32_t *
                                   uint32_t * stopped_by_out /* [n_requests], may be NULL */, uint32_t * lane_out /* [n_requests], may be NULL */,
                                   uint32_t * start_pass_out /* [n_requests], may be NULL */, uint32_t * last_request_out /* [n], may be NULL */,
                                   float * elapsed_ms /* may be NULL */);
+
+/* ---- Served requests with a guide, a logit bias and the log-prob report ----
+ * rwkv_mi_batch_serve_ex is rwkv_mi_batch_serve -- its 17 arguments, its schedule, its outputs -- with what belongs to a REQUEST rather than to
+ * a lane: two requests that follow each other on a lane may have different schemas, different biases, or one of them none.
+ * extras[q] (extras NULL: no request has any):
+ *   guide, guide_state   the request's draws are masked by `guide` (a guide of the batch; RWKV_MI_NO_GUIDE: none) from guide_state on, as after
+ *       rwkv_mi_batch_guide_attach(guide, guide_state): the state moves along every token the request draws, prompt tokens do not move it, a
+ *       dead pick counts a miss. The state and miss words are the CALL's, one pair per lane, set at every admission: the lane slots' own guide
+ *       words are neither read nor written. guide_state_out[q] / guide_misses_out[q]: the request's final state and miss count (0 and 0 for
+ *       an unguided request). One guided request puts the whole call on the guided draw kernel; an unguided request draws unmasked on it.
+ *       rwkv_mi_batch_guide_free is not guarded against a running call; the call drains before it returns.
+ *   bias_slot   the request reads the bias table of this slot of the batch (RWKV_MI_NO_SLOT: none), set beforehand with
+ *       rwkv_mi_batch_logit_bias_set. Like from_slot it is only read: many requests may share one table, none is copied. The penalised
+ *       family reads the bias; the plain sampler never does.
+ * THE REPORT: on a batch with the report on (rwkv_mi_batch_set_logprobs) the call fills it per request, every family: rows = n_requests, steps =
+ * stride, so rwkv_mi_batch_logprobs_shape / _store read [n_requests][stride]. The entry at position j of request q is what
+ * rwkv_mi_batch_decode_until reports for that step -- from the model's logits, `chosen` equal to rwkv_mi_batch_score_ragged on the emitted
+ * text bit for bit, an exact top-N of the batch's top_n; entries at j >= lens_out[q] are 0.0f / RWKV_MI_NO_TOKEN / -inf.
+ * THE GUARANTEE extends rwkv_mi_batch_serve's: tokens, length, reason, guide state, miss count and report rows of request q are, bit for bit, what
+ * a batch of one slot gives after: the state load; rwkv_mi_batch_rng_seek 0 and _counts_reset; the two settings;
+ * rwkv_mi_batch_guide_attach(guide, guide_state); rwkv_mi_batch_logit_bias_set of the same ids and values; rwkv_mi_batch_set_logprobs(top_n);
+ * rwkv_mi_batch_eval of prompt[0 .. prompt_len - 1); rwkv_mi_batch_decode_until from prompt[prompt_len - 1] -- whoever else is in the queue and
+ * whatever the lane served before. An unguided, unbiased request draws what it draws through rwkv_mi_batch_serve. With extras NULL and the
+ * report off the call performs the launches, allocations and copies of rwkv_mi_batch_serve and returns the same outputs. The schedule is
+ * still a function of the requests' lengths alone.
+ * REJECTED with RWKV_ERROR_ARGS, nothing changed: everything rwkv_mi_batch_serve rejects except a reporting batch (a lane whose SLOT has a guide
+ * attached or a bias set is still rejected: settings come with requests); a guide that names no guide; a guide_state >= its n_states; a
+ * bias_slot out of range, one that is a lane, or one with no bias set; a guided request in the greedy family (guided greedy is temperature 0
+ * of the sampled family); a bias_slot in a family other than the penalised one; reserved != 0; the report on with a stride of 0.
+ * OUT OF SCOPE: as rwkv_mi_batch_serve; guided greedy; a top_n per request (it is the batch's). */
+struct rwkv_mi_serve_extra {              /* 16 bytes */
+    uint32_t guide;                       /* a guide of the batch; RWKV_MI_NO_GUIDE: none */
+    uint32_t guide_state;                 /* the state the request's first draw is masked from */
+    uint32_t bias_slot;                   /* a slot of the batch whose bias table the request reads; RWKV_MI_NO_SLOT: none */
+    uint32_t reserved;                    /* 0 */
+};
+RWKV_API bool rwkv_mi_batch_serve_ex(struct rwkv_mi_batch * batch, const uint32_t * lanes /* [n] slots */, size_t n, int family,
+                                     const struct rwkv_mi_serve_request * requests /* [n_requests] */, size_t n_requests,
+                                     const uint32_t * prompt_tokens /* sum(prompt_len) words */, const uint32_t * seq_lens, const uint32_t * seq_tokens,
+                                     size_t stride, uint32_t * tokens_out /* [n_requests][stride], may be NULL */, uint32_t * lens_out /* [n_requests] */,
+                                     uint32_t * stopped_by_out /* [n_requests], may be NULL */, uint32_t * lane_out /* [n_requests], may be NULL */,
+                                     uint32_t * start_pass_out /* [n_requests], may be NULL */, uint32_t * last_request_out /* [n], may be NULL */,
+                                     float * elapsed_ms /* may be NULL */, const struct rwkv_mi_serve_extra * extras /* [n_requests], may be NULL */,
+                                     uint32_t * guide_state_out /* [n_requests], may be NULL */, uint32_t * guide_misses_out /* [n_requests], may be NULL */);
 
 #if defined(__cplusplus)
 }

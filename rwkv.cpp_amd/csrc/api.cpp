@@ -1217,6 +1217,11 @@ struct BatchCall {
     size_t n_requests = 0;
     const uint32_t * prompts = nullptr;
     uint32_t * lane_out = nullptr, * start_pass_out = nullptr, * last_request_out = nullptr;
+    // rwkv_mi_batch_serve_ex (serve_ex: the call is one; the same body): what a request carries beyond its struct -- a guide with its start
+    // state, the slot whose bias table it reads -- and its final guide words back; on a reporting batch the call fills the report
+    bool serve_ex = false;
+    const rwkv_mi_serve_extra * extras = nullptr;
+    uint32_t * guide_state_out = nullptr, * guide_misses_out = nullptr;
 };
 
 // the batch's report buffers (batch_ensure_report has sized them for the call)
@@ -1771,17 +1776,23 @@ static bool batch_until(rwkv_mi_batch * B, const BatchCall & c, uint32_t * token
 // Where the words of a call of n lanes and R requests lie in the serve buffer (byte offsets). What goes up: the request table, the prompts and
 // the sequences, the lane words in their start values, the head of the queue and the work count. From `down` on, what comes back as well: the
 // lanes' last requests, the requests' lengths, reasons, lanes and start passes, and their emitted tokens out[R][stride] (filled on the device).
+// guided (a call of rwkv_mi_batch_serve_ex with a guided request; no bytes otherwise): the lanes' guide state and miss words go up, the
+// requests' -- the start state and 0 on the way up, the final words on the way back -- do both.
 struct ServeLayout {
-    size_t reqs, prompts, seq_lens, seq_tokens, lane_slot, req, pos, draw, admit, next, work, down, last, lens, reasons, lane, start, out, bytes;
-    ServeLayout(size_t n, size_t R, size_t n_prompt, size_t n_seqs, size_t n_toks, size_t stride) {
+    size_t reqs, prompts, seq_lens, seq_tokens, lane_slot, req, pos, draw, admit, g_state, g_misses, next, work, down, last, lens, reasons, lane, start,
+           req_g_state, req_g_misses, out, bytes;
+    ServeLayout(size_t n, size_t R, size_t n_prompt, size_t n_seqs, size_t n_toks, size_t stride, bool guided) {
         size_t o = 0;
         auto take = [&o](size_t b) { const size_t at = o; o += b; return at; };
+        const size_t g = guided ? 4 : 0;
         reqs = take(R * sizeof(ServeReq));
         prompts = take(n_prompt * 4); seq_lens = take(n_seqs * 4); seq_tokens = take(n_toks * 4);
         lane_slot = take(n * 4); req = take(n * 4); pos = take(n * 4); draw = take(n * 4); admit = take(n * 4);
+        g_state = take(n * g); g_misses = take(n * g);
         next = take(4); work = take(4);
         down = o;
         last = take(n * 4); lens = take(R * 4); reasons = take(R * 4); lane = take(R * 4); start = take(R * 4);
+        req_g_state = take(R * g); req_g_misses = take(R * g);
         out = take(R * stride * 4);
         bytes = o;
     }
@@ -1794,7 +1805,8 @@ static bool batch_check_serve(rwkv_mi_batch * B, const BatchCall & c, size_t * n
                  "lanes, requests, prompt_tokens or lens_out is NULL");
     RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, c.n > 0 && c.n <= B->n_slots, "n (%zu) must be in 1 .. %zu", c.n, B->n_slots);
     RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, c.n_requests >= c.n && c.n_requests < (size_t) SERVE_FREE, "n_requests (%zu) is below the %zu lanes (or above 2^32 - 3)", c.n_requests, c.n);
-    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, !B->lp.enabled, "rwkv_mi_batch_serve takes no batch with the log-prob report on");
+    if (!c.serve_ex) RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, !B->lp.enabled, "rwkv_mi_batch_serve takes no batch with the log-prob report on");
+    else RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, !B->lp.enabled || c.stride > 0, "the log-prob report is on and stride is 0");
     std::vector<uint8_t> is_lane(B->n_slots, 0);
     for (size_t i = 0; i < c.n; i++) {
         const uint32_t s = c.slots[i];
@@ -1820,6 +1832,21 @@ static bool batch_check_serve(rwkv_mi_batch * B, const BatchCall & c, size_t * n
         RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, rq.decay >= 0.0f && rq.decay <= 1.0f, "decay of request %zu (%g) must be in 0 .. 1", q, (double) rq.decay);
         RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, rq.repetition > 0.0f && rq.repetition < INFINITY, "repetition of request %zu (%g) must be finite and above 0", q, (double) rq.repetition);
         sp[q] = rq.sample; pp[q] = rq.penalty; st[q] = rq.stop;
+        if (!c.extras) continue;
+        // what the request carries beyond its struct: settings come with requests, by the rules of rwkv_mi_batch_guide_attach and _logit_bias_set
+        const rwkv_mi_serve_extra & ex = c.extras[q];
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, ex.reserved == 0, "reserved of the extra of request %zu is not 0", q);
+        if (ex.guide != RWKV_MI_NO_GUIDE) {
+            RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, ex.guide < RWKV_MI_GUIDE_MAX && B->guide_states[ex.guide], "guide of request %zu (%" PRIu32 ") names no guide", q, ex.guide);
+            RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, ex.guide_state < B->guide_states[ex.guide], "guide_state of request %zu (%" PRIu32 ") is out of range (guide %" PRIu32
+                         " has %" PRIu32 " states)", q, ex.guide_state, ex.guide, B->guide_states[ex.guide]);
+            RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, c.draw != Draw::none, "request %zu has a guide in the greedy family (guided greedy is temperature 0 of the sampled one)", q);
+        }
+        if (ex.bias_slot != RWKV_MI_NO_SLOT) {
+            RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, ex.bias_slot < B->n_slots && !is_lane[ex.bias_slot] && B->draw.has_bias[ex.bias_slot],
+                         "bias_slot of request %zu (%" PRIu32 ") is a lane of the call, out of range or has no bias set", q, ex.bias_slot);
+            RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, c.draw == Draw::penalized, "request %zu has a bias_slot in a family that reads no bias (the penalised one does)", q);
+        }
     }
     for (size_t t = 0; t < (size_t) P; t++)
         RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, c.prompts[t] < n_vocab, "Prompt token at index %zu (%" PRIu32 ") is out of range (0 .. %zu)", t, c.prompts[t], n_vocab - 1);
@@ -1862,6 +1889,9 @@ static unsigned serve_chunks(int64_t state_len) {
 // admits ON THE DEVICE: between two passes it rewrites a lane's token word, draw row and words and has the request's start state copied into
 // the buffer the lane's next pass reads. The model's kernels never learn of it. The admission in front of pass 0 is the same two kernels.
 // The driver polls the number of lanes with work, and never enqueues more passes than the queue can need.
+// rwkv_mi_batch_serve_ex is the same body: a request's guide table and bias table go into its draw row here, the guide words of the lanes and
+// of the requests travel in the serve buffer when a request is guided, and on a reporting batch every pass reports between its choice and
+// the scheduler, at (position, request). Without extras and report nothing of that exists: no byte, no launch, no copy more.
 static bool batch_serve(rwkv_mi_batch * B, const BatchCall & c, uint32_t * tokens_out, float * elapsed_ms) {
     rwkv_context * ctx = B->ctx;
     rwkv_context * run = B->run;
@@ -1871,7 +1901,7 @@ static bool batch_serve(rwkv_mi_batch * B, const BatchCall & c, uint32_t * token
     const size_t n = c.n, R = c.n_requests, n_vocab = (size_t) m.n_vocab();
     const bool pen = c.draw == Draw::penalized;
     size_t n_seqs = 0, n_toks = 0, bound = 0;
-    bool any_cut = false, any_rep = false;
+    bool any_cut = false, any_rep = false, any_guided = false;
     std::vector<StopRow> stop_rows(R);
     for (size_t q = 0; q < R; q++) {
         const rwkv_mi_serve_request & rq = c.requests[q];
@@ -1879,13 +1909,17 @@ static bool batch_serve(rwkv_mi_batch * B, const BatchCall & c, uint32_t * token
         bound += (size_t) rq.prompt_len - 1 + rq.stop.max_tokens;   // (a lane with work advances its request by one pass: no schedule needs more)
         any_cut |= (rq.top_k != 0u && rq.top_k < n_vocab) || rq.min_p != 0.0f;
         any_rep |= rq.decay != 1.0f || rq.repetition != 1.0f;
+        any_guided |= c.extras && c.extras[q].guide != RWKV_MI_NO_GUIDE;
     }
     BatchCall lanes{c.slots, nullptr, n};
     lanes.draw = c.draw;
     if (!batch_ensure_draw(B, lanes)) return false;   // (the draw buffers of the family; the form it derives from the lanes' own settings ...)
-    B->form = DrawForm::of(c.draw, any_cut, false, any_rep);   // (... is not the call's: the requests carry theirs)
-    const ServeLayout L(n, R, n_prompt, n_seqs, n_toks, c.stride);
+    B->form = DrawForm::of(c.draw, any_cut, any_guided, any_rep);   // (... is not the call's: the requests carry theirs)
+    const ServeLayout L(n, R, n_prompt, n_seqs, n_toks, c.stride, any_guided);
     if (!batch_ensure_serve(B, L.bytes)) return false;
+    // (the entry point that reports, on a batch that does: entry (j, q) is position j of request q -- rows = R, steps = stride)
+    const bool report = c.serve_ex && B->lp.enabled;
+    if (report && !batch_ensure_report(B, R, c.stride)) return false;
     BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));   // (the previous call's copies may still read the staging)
     uint8_t * h = B->h_serve.p, * d = B->d_serve.p;
     auto hw = [h](size_t off) { return (uint32_t *) (h + off); };
@@ -1900,10 +1934,16 @@ static bool batch_serve(rwkv_mi_batch * B, const BatchCall & c, uint32_t * token
         row.p = rq.sample; row.p.u = -1.0f;
         row.presence = pen ? rq.penalty.presence : 0.0f; row.frequency = pen ? rq.penalty.frequency : 0.0f; row.record = pen ? 1u : 0u;
         row.top_k = rq.top_k; row.min_p = rq.min_p; row.decay = rq.decay; row.repetition = rq.repetition;
+        // (its guide's table and its bias slot's, both only read; the guide words are the lane's, which the scheduler fills in as well)
+        const rwkv_mi_serve_extra ex = c.extras ? c.extras[q] : rwkv_mi_serve_extra{RWKV_MI_NO_GUIDE, 0u, RWKV_MI_NO_SLOT, 0u};
+        if (ex.guide != RWKV_MI_NO_GUIDE) row.next = B->guides[ex.guide].p;
+        if (pen && ex.bias_slot != RWKV_MI_NO_SLOT) row.bias = B->draw.bias_of(ex.bias_slot);
+        if (any_guided) { hw(L.req_g_state)[q] = ex.guide != RWKV_MI_NO_GUIDE ? ex.guide_state : 0u; hw(L.req_g_misses)[q] = 0u; }
         const float * start = rq.from_slot == RWKV_MI_NO_SLOT ? B->serve_fresh.p : B->slot_buf(rq.from_slot, B->parity[rq.from_slot]);
         reqs[q] = ServeReq{row, stop_rows[q], rq.prompt_len, (uint32_t) p0, start};
         p0 += rq.prompt_len;
     }
+    for (size_t r = 0; any_guided && r < n; r++) { hw(L.g_state)[r] = 0u; hw(L.g_misses)[r] = 0u; }
     memcpy(h + L.prompts, c.prompts, n_prompt * 4);
     if (n_seqs) memcpy(h + L.seq_lens, c.seq_lens, n_seqs * 4);
     if (n_toks) memcpy(h + L.seq_tokens, c.seq_tokens, n_toks * 4);
@@ -1918,9 +1958,12 @@ static bool batch_serve(rwkv_mi_batch * B, const BatchCall & c, uint32_t * token
     serve.t = ServeTables{(const ServeReq *) (d + L.reqs), dw(L.prompts), dw(L.seq_lens), dw(L.seq_tokens), dw(L.out), (uint32_t) c.stride,
                           dw(L.lens), dw(L.reasons), dw(L.lane), dw(L.start), dw(L.req), dw(L.pos), dw(L.draw), dw(L.admit), dw(L.last), dw(L.lane_slot),
                           c.draw != Draw::none ? B->d_draw_rows.p : nullptr, B->draw.counters.p, B->draw.counts.p, dw(L.next), dw(L.work),
-                          (uint32_t) R, (uint32_t) n_vocab};
+                          (uint32_t) R, (uint32_t) n_vocab,
+                          any_guided ? dw(L.g_state) : nullptr, any_guided ? dw(L.g_misses) : nullptr,
+                          any_guided ? dw(L.req_g_state) : nullptr, any_guided ? dw(L.req_g_misses) : nullptr};
     serve.state_len = B->state_len; serve.chunks = serve_chunks(B->state_len);
-    RowSampler sampler = batch_sampler(B, nullptr, nullptr);
+    const RowReport rep = batch_report(B);
+    RowSampler sampler = batch_sampler(B, nullptr, report ? &rep : nullptr);
     sampler.serve = &serve;
     const auto step = [&](const RowSampler & s) {
         if (s.step == 0) {
@@ -1945,6 +1988,9 @@ static bool batch_serve(rwkv_mi_batch * B, const BatchCall & c, uint32_t * token
         if (c.lane_out) c.lane_out[q] = lane[q];
         if (c.start_pass_out) c.start_pass_out[q] = start[q];
         if (tokens_out) memcpy(tokens_out + q * c.stride, out + q * c.stride, c.stride * 4);
+        // (an unguided request's words are 0 and 0)
+        if (c.guide_state_out) c.guide_state_out[q] = any_guided ? hw(L.req_g_state)[q] : 0u;
+        if (c.guide_misses_out) c.guide_misses_out[q] = any_guided ? hw(L.req_g_misses)[q] : 0u;
     }
     for (size_t r = 0; r < n; r++) {
         // the lane ran one pass after the other from pass 0 to the last one of its last request: that many times its buffers changed places
@@ -1952,6 +1998,7 @@ static bool batch_serve(rwkv_mi_batch * B, const BatchCall & c, uint32_t * token
         if (c.last_request_out) c.last_request_out[r] = (uint32_t) q;
         if (ran & 1) B->parity[c.slots[r]] ^= 1;
     }
+    if (report) report_done(B->lp, R, c.stride, lens);
     return true;
 }
 
@@ -2344,10 +2391,11 @@ RWKV_API bool rwkv_mi_batch_decode_until(struct rwkv_mi_batch * B, const uint32_
 
 RWKV_API size_t rwkv_mi_batch_last_loop_passes(const struct rwkv_mi_batch * B) { return B ? B->last_loop_passes : 0; }
 
-RWKV_API bool rwkv_mi_batch_serve(struct rwkv_mi_batch * B, const uint32_t * lanes, size_t n, int family, const struct rwkv_mi_serve_request * requests,
-                                  size_t n_requests, const uint32_t * prompt_tokens, const uint32_t * seq_lens, const uint32_t * seq_tokens, size_t stride,
-                                  uint32_t * tokens_out, uint32_t * lens_out, uint32_t * stopped_by_out, uint32_t * lane_out, uint32_t * start_pass_out,
-                                  uint32_t * last_request_out, float * elapsed_ms) {
+// both entry points of the queue: the description they share -- `ex`: the call is rwkv_mi_batch_serve_ex, which takes what follows it -- and the body
+static bool serve_entry(rwkv_mi_batch * B, const uint32_t * lanes, size_t n, int family, const rwkv_mi_serve_request * requests, size_t n_requests,
+                        const uint32_t * prompt_tokens, const uint32_t * seq_lens, const uint32_t * seq_tokens, size_t stride, uint32_t * tokens_out, uint32_t * lens_out,
+                        uint32_t * stopped_by_out, uint32_t * lane_out, uint32_t * start_pass_out, uint32_t * last_request_out, float * elapsed_ms, bool ex,
+                        const rwkv_mi_serve_extra * extras, uint32_t * guide_state_out, uint32_t * guide_misses_out) {
     B->ctx->last_error = RWKV_ERROR_NONE;
     RW_NO_PIPELINE(B->ctx, false);
     RW_CTX_CHECK(B->ctx, RWKV_ERROR_ARGS, false, family == RWKV_MI_SERVE_GREEDY || family == RWKV_MI_SERVE_SAMPLE || family == RWKV_MI_SERVE_PENALIZED,
@@ -2358,7 +2406,25 @@ RWKV_API bool rwkv_mi_batch_serve(struct rwkv_mi_batch * B, const uint32_t * lan
     c.seq_lens = seq_lens; c.seq_tokens = seq_tokens;
     c.stride = stride; c.lens_out = lens_out; c.stopped_by_out = stopped_by_out;
     c.lane_out = lane_out; c.start_pass_out = start_pass_out; c.last_request_out = last_request_out;
+    c.serve_ex = ex; c.extras = extras; c.guide_state_out = guide_state_out; c.guide_misses_out = guide_misses_out;
     return batch_serve(B, c, tokens_out, elapsed_ms);
+}
+
+RWKV_API bool rwkv_mi_batch_serve(struct rwkv_mi_batch * B, const uint32_t * lanes, size_t n, int family, const struct rwkv_mi_serve_request * requests,
+                                  size_t n_requests, const uint32_t * prompt_tokens, const uint32_t * seq_lens, const uint32_t * seq_tokens, size_t stride,
+                                  uint32_t * tokens_out, uint32_t * lens_out, uint32_t * stopped_by_out, uint32_t * lane_out, uint32_t * start_pass_out,
+                                  uint32_t * last_request_out, float * elapsed_ms) {
+    return serve_entry(B, lanes, n, family, requests, n_requests, prompt_tokens, seq_lens, seq_tokens, stride, tokens_out, lens_out, stopped_by_out, lane_out,
+                       start_pass_out, last_request_out, elapsed_ms, false, nullptr, nullptr, nullptr);
+}
+
+RWKV_API bool rwkv_mi_batch_serve_ex(struct rwkv_mi_batch * B, const uint32_t * lanes, size_t n, int family, const struct rwkv_mi_serve_request * requests,
+                                     size_t n_requests, const uint32_t * prompt_tokens, const uint32_t * seq_lens, const uint32_t * seq_tokens, size_t stride,
+                                     uint32_t * tokens_out, uint32_t * lens_out, uint32_t * stopped_by_out, uint32_t * lane_out, uint32_t * start_pass_out,
+                                     uint32_t * last_request_out, float * elapsed_ms, const struct rwkv_mi_serve_extra * extras, uint32_t * guide_state_out,
+                                     uint32_t * guide_misses_out) {
+    return serve_entry(B, lanes, n, family, requests, n_requests, prompt_tokens, seq_lens, seq_tokens, stride, tokens_out, lens_out, stopped_by_out, lane_out,
+                       start_pass_out, last_request_out, elapsed_ms, true, extras, guide_state_out, guide_misses_out);
 }
 
 RWKV_API bool rwkv_mi_batch_eval_draft(struct rwkv_mi_batch * B, const uint32_t * slots, const uint32_t * lens, const uint32_t * tokens, size_t n,

@@ -860,9 +860,13 @@ void launch_row_sampler(rwkv_context * ctx, const RowSampler & s, int64_t rows) 
     }
     if (const RowServe * sv = s.serve) {
         // a step of rwkv_mi_batch_serve: the family's choice behind the lanes' draw words (no history: the scheduler appends the token to its
-        // request's row), then the scheduler, then the admissions it decided
+        // request's row), then -- rwkv_mi_batch_serve_ex on a reporting batch -- the report of what it wrote, at the request's position (the
+        // scheduler is what advances it), then the scheduler, then the admissions it decided
         if (s.form.draw != Draw::none) launch_draw_rows(logits, rows, n_vocab, s.rows, s.form, s.probs, tokens, nullptr, sv->t.draw, ctx->stream);
         else launch_argmax_live(logits, rows, n_vocab, tokens, nullptr, sv->t.draw, ctx->stream);
+        if (const RowReport * rp = s.report)
+            launch_logprob_rows_serve(logits, rows, n_vocab, tokens, (int) rp->top_n, rp->chosen, rp->ids, rp->vals, sv->t.draw, sv->t.req, sv->t.lens, sv->t.stride,
+                                      sv->t.n_requests, ctx->stream);
         launch_serve_rows(sv->t, rows, tokens, s.step, s.used, s.other, ctx->stream);
         launch_serve_reset(sv->t, rows, sv->chunks, s.used, sv->state_len, ctx->stream);
         return;

@@ -177,6 +177,11 @@ void launch_score_rows(const float * logits, int64_t rows, int n, const uint32_t
 // ascending, with their log-probs (RWKV_MI_NO_TOKEN / -inf where fewer rank). live (may be nullptr): a row with live[row] == 0 writes nothing.
 void launch_logprob_rows(const float * logits, int64_t rows, int n, const uint32_t * tokens, int top_n, float * chosen, uint32_t * top_ids, float * top_lp,
                          const uint32_t * live, hipStream_t st);
+// The same for a step of rwkv_mi_batch_serve_ex (k_logprob_rows_serve), between the choice and the scheduler: lane r, when its draw word is
+// set, serves request q = req[r], which has emitted j = lens[q] tokens before this one -- its record goes to entry j * n_requests + q of the
+// buffers ([position][request]); nothing when j >= stride.
+void launch_logprob_rows_serve(const float * logits, int64_t lanes, int n, const uint32_t * tokens, int top_n, float * chosen, uint32_t * top_ids, float * top_lp,
+                               const uint32_t * draw, const uint32_t * req, const uint32_t * lens, uint32_t stride, uint32_t n_requests, hipStream_t st);
 
 // load-time transpose of att.time_maa_w2: [5][D][R] -> [5][R][D]
 void launch_transpose_w2(const float * src, float * dst, int64_t D, int64_t R, hipStream_t st);

@@ -189,8 +189,9 @@ struct StopTables { const StopRow * rows; const uint32_t * seq_lens, * seq_token
 // pass `step`, other: the one of pass step + 1).
 void launch_stop_rows(const StopTables & t, int64_t rows, const uint32_t * hist, uint32_t step, RowState * used, RowState * other, hipStream_t st);
 // rwkv_mi_batch_serve (sampling.hip, k_serve_rows / k_serve_reset): a queue of requests behind the n lanes of a call. A request as the device
-// reads it: its draw row -- the request's settings; the counter and the occurrence row are the LANE's, patched in at admission -- its stop row,
-// its prompt (prompt_len tokens at prompts[prompt0 ..]) and the buffer its start state is copied from.
+// reads it: its draw row -- the request's settings, with (rwkv_mi_batch_serve_ex) its guide's table and its bias slot's table, both only read;
+// the counter, the occurrence row and the guide words are the LANE's, patched in at admission -- its stop row, its prompt (prompt_len tokens at
+// prompts[prompt0 ..]) and the buffer its start state is copied from.
 struct ServeReq { DrawRow row; StopRow stop; uint32_t prompt_len, prompt0; const float * start; };
 // The device words of a call. Per request: its emitted tokens out[q][stride], its length (it grows with every token), its reason, its lane and
 // the pass that fed its first prompt token. Per lane: the request it serves (SERVE_FREE: it waits for one -- only between the two halves of
@@ -198,7 +199,10 @@ struct ServeReq { DrawRow row; StopRow stop; uint32_t prompt_len, prompt0; const
 // coming pass are drawn from -- the `live` argument of the draw kernels), its admit word (1: k_serve_reset has a state to copy), the last
 // request it was given, and its slot. rows: the draw table of the lanes (NULL: the greedy family); counters / counts: the batch's, indexed by
 // slot (counts NULL: the batch has no occurrence tables). next_request: the head of the queue, written by k_serve_rows alone; work: the lanes
-// that are not dead, which the host polls.
+// that are not dead, which the host polls. A call with guided requests (rwkv_mi_batch_serve_ex; NULL otherwise, all four): guide_state /
+// guide_misses, one pair of guide words per LANE -- the call's own, not the lane slots' -- which a guided request's draw row points at from
+// its admission on, and req_guide_state / req_guide_misses per REQUEST: the host leaves the request's start state and 0 there, the scheduler
+// the lane's two words when the request retires. A request is guided when its row has a table (row.next).
 constexpr uint32_t SERVE_FREE = 0xFFFFFFFEu;
 struct ServeTables {
     const ServeReq * reqs; const uint32_t * prompts, * seq_lens, * seq_tokens;
@@ -208,6 +212,7 @@ struct ServeTables {
     DrawRow * rows; unsigned long long * counters; uint32_t * counts;
     uint32_t * next_request, * work;
     uint32_t n_requests, n_vocab;
+    uint32_t * guide_state, * guide_misses, * req_guide_state, * req_guide_misses;
 };
 // After the draw of pass `step` over the n lanes (tokens: the lanes' token words; used: the row table of that pass, other: the one of pass
 // step + 1): every lane emits, advances its prompt, retires, admits or goes dead. step == UINT32_MAX with used = the table of pass 1: the

@@ -572,6 +572,9 @@ __global__ __launch_bounds__(64) void k_stop_rows(StopTables t, int n, const uin
 //            request next + rank(r) while the queue lasts: its words, its token word, its draw row (the request's, with the lane's counter,
 //            set to 0, and the lane's occurrence row) and its admit word, for k_serve_reset. A lane the queue has nothing for goes dead as a
 //            row of k_stop_rows does: {in = F, out = G} in both row tables, for good.
+//   guides   (rwkv_mi_batch_serve_ex; t.guide_state NULL: the call has none, and none of this runs) a request whose row has a table is
+//            guided: at its admission the row gets the LANE's guide words, set to the request's start state and no miss; at its retirement
+//            the two words are left as the request's. An unguided request's row has no table, so it draws unmasked whatever its lane served.
 // Who gets what follows from the words alone: next_request is read and written by this workgroup only, no atomic decides anything. Thread 0
 // leaves the new head of the queue and the number of lanes that are not dead. DRAWS: the family has a draw table (the greedy one has none).
 template <bool DRAWS>
@@ -601,7 +604,13 @@ __global__ __launch_bounds__(1024) void k_serve_rows(ServeTables t, int n, uint3
                     tk += L;
                 }
                 t.lens[q] = len;
-                if (reason != RWKV_MI_NO_TOKEN || len >= rq.stop.max_tokens) { t.reasons[q] = reason; is_free = true; }
+                if (reason != RWKV_MI_NO_TOKEN || len >= rq.stop.max_tokens) {
+                    t.reasons[q] = reason; is_free = true;
+                    if constexpr (DRAWS) {
+                        // (a guided request leaves the lane's guide words, which its draws have moved, as its own)
+                        if (t.guide_state && rq.row.next) { t.req_guide_state[q] = t.guide_state[r]; t.req_guide_misses[q] = t.guide_misses[r]; }
+                    }
+                }
             } else {
                 const uint32_t pos = t.pos[r];
                 tokens[r] = t.prompts[rq.prompt0 + pos];
@@ -633,6 +642,12 @@ __global__ __launch_bounds__(1024) void k_serve_rows(ServeTables t, int n, uint3
                     *row = rq.row;
                     row->counter = t.counters + slot;
                     if (rq.row.record) row->count = t.counts + (size_t) slot * t.n_vocab;
+                    // (a guided request: the lane's guide words, from the request's start state and no miss; any other has no table and
+                    //  no words, whatever the lane served before)
+                    if (t.guide_state && rq.row.next) {
+                        row->state = t.guide_state + r; row->misses = t.guide_misses + r;
+                        t.guide_state[r] = t.req_guide_state[qn]; t.guide_misses[r] = 0u;
+                    }
                 }
                 t.admit[r] = 1u;
                 alive = true;

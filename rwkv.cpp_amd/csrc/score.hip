@@ -180,6 +180,25 @@ __global__ __launch_bounds__(1024) void k_logprob_rows_live(const float * __rest
     logprob_row_body(logits_all + r * (size_t) n, n, tokens[r], top_n, chosen + r, top_ids + r * (size_t) top_n, top_lp + r * (size_t) top_n);
 }
 
+// ... and behind a LANE of rwkv_mi_batch_serve_ex (model.h, ServeTables), between the choice and the scheduler: a lane whose draw word is 0 --
+// it is fed a prompt token, or is dead -- writes nothing. The others serve request q = req[r], which has emitted j = lens[q] tokens before
+// this one (the scheduler behind this launch is what advances lens): the record goes to entry (j, q) of buffers laid out [position][request],
+// so the requests that follow each other on a lane never meet. A position the request's token row does not hold (j >= stride) is not
+// reported. The whole workgroup takes each branch together.
+__global__ __launch_bounds__(1024) void k_logprob_rows_serve(const float * __restrict__ logits_all, int n, const uint32_t * __restrict__ tokens, int top_n,
+                                                             float * __restrict__ chosen, uint32_t * __restrict__ top_ids, float * __restrict__ top_lp,
+                                                             const uint32_t * __restrict__ draw, const uint32_t * __restrict__ req,
+                                                             const uint32_t * __restrict__ lens, uint32_t stride, uint32_t n_requests) {
+    const size_t r = blockIdx.x;
+    if (!draw[r]) return;
+    const uint32_t q = req[r];
+    if (q >= n_requests) return;   // (a lane that draws has a request; a word that names none is never used as an index)
+    const uint32_t j = lens[q];
+    if (j >= stride) return;
+    const size_t at = (size_t) j * n_requests + q;
+    logprob_row_body(logits_all + r * (size_t) n, n, tokens[r], top_n, chosen + at, top_ids + at * (size_t) top_n, top_lp + at * (size_t) top_n);
+}
+
 // ---- one step of the beam search (rwkv_mi_batch_decode_beam): the rows' candidates, then the selection of each group ----
 // The candidates of a row are the report's top-N at N = the beam width, through the report's body: ids and f32 log-probs in the report's order,
 // bit for bit what k_logprob_rows gives the row. Behind the row's own words (the pattern of the _live kernels): a finished hypothesis, and one
@@ -291,6 +310,13 @@ void launch_logprob_rows(const float * logits, int64_t rows, int n, const uint32
     if (rows <= 0) return;
     if (live) hipLaunchKernelGGL(k_logprob_rows_live, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, tokens, top_n, chosen, top_ids, top_lp, live);
     else hipLaunchKernelGGL(k_logprob_rows, dim3((unsigned) rows), dim3(1024), 0, st, logits, n, tokens, top_n, chosen, top_ids, top_lp);
+}
+
+void launch_logprob_rows_serve(const float * logits, int64_t lanes, int n, const uint32_t * tokens, int top_n, float * chosen, uint32_t * top_ids, float * top_lp,
+                               const uint32_t * draw, const uint32_t * req, const uint32_t * lens, uint32_t stride, uint32_t n_requests, hipStream_t st) {
+    if (lanes <= 0) return;
+    hipLaunchKernelGGL(k_logprob_rows_serve, dim3((unsigned) lanes), dim3(1024), 0, st, logits, n, tokens, top_n, chosen, top_ids, top_lp, draw, req, lens, stride,
+                       n_requests);
 }
 
 }  // namespace rwkvmi

@@ -36,7 +36,7 @@ PENALTY_SYMBOLS = ("rwkv_mi_batch_counts_reset", "rwkv_mi_batch_counts_add", "rw
                    "rwkv_mi_sample_penalized", "rwkv_mi_decode_sample_penalized")
 SCORE_SYMBOLS = ("rwkv_mi_score_resident", "rwkv_mi_batch_score_ragged")
 UNTIL_SYMBOLS = ("rwkv_mi_batch_decode_until", "rwkv_mi_batch_last_loop_passes")
-SERVE_SYMBOLS = ("rwkv_mi_batch_serve",)
+SERVE_SYMBOLS = ("rwkv_mi_batch_serve", "rwkv_mi_batch_serve_ex")
 LOGPROBS_SYMBOLS = ("rwkv_mi_batch_set_logprobs", "rwkv_mi_batch_logprobs_shape", "rwkv_mi_batch_logprobs_store",
                     "rwkv_mi_set_logprobs", "rwkv_mi_logprobs_shape", "rwkv_mi_logprobs_store")
 BEAM_SYMBOLS = ("rwkv_mi_batch_state_copy", "rwkv_mi_batch_decode_beam")
@@ -57,6 +57,7 @@ STOP_MAX_SEQS = 16       # RWKV_MI_STOP_MAX_SEQS
 STOP_MAX_LEN = 8         # RWKV_MI_STOP_MAX_LEN
 NO_SLOT = 0xFFFFFFFF     # RWKV_MI_NO_SLOT
 SERVE_GREEDY, SERVE_SAMPLE, SERVE_PENALIZED = 0, 1, 2   # RWKV_MI_SERVE_*
+SERVE_EXTRA_KEYS = ("guide", "guide_state", "bias_slot")   # the keys of a request dict that serve_extras reads (struct rwkv_mi_serve_extra)
 P_FLOAT = ctypes.POINTER(ctypes.c_float)
 P_UINT32 = ctypes.POINTER(ctypes.c_uint32)
 
@@ -94,6 +95,15 @@ class ServeRequest(ctypes.Structure):
 
 
 P_SERVE_REQUEST = ctypes.POINTER(ServeRequest)
+
+
+class ServeExtra(ctypes.Structure):
+    """struct rwkv_mi_serve_extra (include/rwkv_mi355x.h): what a request of RWKVBatch.serve carries beyond its ServeRequest -- its guide and the
+    state it enters it in, the slot whose bias table it reads -- 16 bytes."""
+    _fields_ = [("guide", ctypes.c_uint32), ("guide_state", ctypes.c_uint32), ("bias_slot", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+P_SERVE_EXTRA = ctypes.POINTER(ServeExtra)
 
 
 class CutParams(ctypes.Structure):
@@ -303,6 +313,10 @@ class RWKVSharedLibrary:
             L.rwkv_mi_batch_serve.argtypes = [c_batch, P_UINT32, ctypes.c_size_t, ctypes.c_int, P_SERVE_REQUEST, ctypes.c_size_t, P_UINT32, P_UINT32, P_UINT32,
                                               ctypes.c_size_t, P_UINT32, P_UINT32, P_UINT32, P_UINT32, P_UINT32, P_UINT32, P_FLOAT]
             L.rwkv_mi_batch_serve.restype = ctypes.c_bool
+        # ... whose requests carry a guide and a bias, and which fills the report
+        if hasattr(L, "rwkv_mi_batch_serve_ex"):   # (absent from older A/B builds loaded through RWKV_LIB_DIR)
+            L.rwkv_mi_batch_serve_ex.argtypes = list(L.rwkv_mi_batch_serve.argtypes) + [P_SERVE_EXTRA, P_UINT32, P_UINT32]
+            L.rwkv_mi_batch_serve_ex.restype = ctypes.c_bool
         # the report: log-probs and top-N alternatives of every emitted token
         if hasattr(L, "rwkv_mi_batch_set_logprobs"):   # (absent from older A/B builds loaded through RWKV_LIB_DIR)
             P_SIZE = ctypes.POINTER(ctypes.c_size_t)
@@ -873,12 +887,13 @@ def serve_requests(requests):
     """The request table of RWKVBatch.serve from one dict per request: ([R] struct rwkv_mi_serve_request, prompt_tokens, seq_lens, seq_tokens), the
     requests' prompts and stop sequences back to back. Keys: prompt (token ids, at least one), max_tokens; optional from_slot (None: the fresh
     state), stop (a list of token-id sequences), temperature (1.0), top_p (0.8), seed (0), presence (0.0), frequency (0.0), top_k (0), min_p (0.0),
-    decay (1.0), repetition (1.0)."""
+    decay (1.0), repetition (1.0). The keys of serve_extras -- guide, guide_state, bias_slot -- are accepted and not read here."""
     requests = list(requests)
     arr = (ServeRequest * len(requests))()
     prompts, lens, toks = [], [], []
     for i, rq in enumerate(requests):
         unknown = set(rq) - {"prompt", "max_tokens", "from_slot", "stop", "temperature", "top_p", "seed", "presence", "frequency", "top_k", "min_p", "decay", "repetition"}
+        unknown -= set(SERVE_EXTRA_KEYS)
         if unknown:
             raise ValueError(f"request {i}: unknown keys {sorted(unknown)}")
         prompt = [int(t) for t in rq["prompt"]]
@@ -896,6 +911,20 @@ def serve_requests(requests):
             lens.append(len(q))
             toks.extend(q)
     return arr, _u32(prompts).reshape(-1), _u32(lens).reshape(-1), _u32(toks).reshape(-1)
+
+
+def serve_extras(requests):
+    """The extras table of RWKVBatch.serve ([R] struct rwkv_mi_serve_extra) from the same dicts serve_requests takes, or None when no request
+    names one of the optional keys guide (a guide id; None: NO_GUIDE), guide_state (0), bias_slot (a slot whose bias table the request reads;
+    None: NO_SLOT)."""
+    requests = list(requests)
+    if not any(k in rq for rq in requests for k in SERVE_EXTRA_KEYS):
+        return None
+    arr = (ServeExtra * len(requests))()
+    for i, rq in enumerate(requests):
+        guide, bias_slot = rq.get("guide"), rq.get("bias_slot")
+        arr[i] = ServeExtra(NO_GUIDE if guide is None else int(guide), int(rq.get("guide_state", 0)), NO_SLOT if bias_slot is None else int(bias_slot), 0)
+    return arr
 
 
 def guide_edges(edges):
@@ -1192,29 +1221,40 @@ class RWKVBatch:
             self._fail("rwkv_mi_batch_decode_until")
         return [out[i, : int(lens[i])].copy() for i in range(n)], why, float(ms.value)
 
-    def serve(self, lanes: List[int], requests, family: int = SERVE_GREEDY):
+    def serve(self, lanes: List[int], requests, family: int = SERVE_GREEDY, report: bool = False):
         """Continuous batching: the slots `lanes` serve the queue `requests` (dicts, as serve_requests takes them; at least as many as lanes) in
         one device loop -- lane r starts with request r, and a lane whose request has ended takes the next one not yet taken on the following
         pass, in lane order. A request starts from the fresh state or from its from_slot's (never a lane), is fed its prompt one token a pass and
         then decodes as a row of decode_until with its own settings; family: SERVE_GREEDY, SERVE_SAMPLE or SERVE_PENALIZED, the call's. Returns
         a dict: tokens (one uint32 array per request, of its own length), stopped_by [R], lane [R] (index into lanes), start_pass [R],
-        last_request [n] (the request whose end state each lane holds), elapsed_ms. Every request's tokens are what it gives alone."""
+        last_request [n] (the request whose end state each lane holds), elapsed_ms, guide_state [R] and guide_misses [R] (0 for a request
+        without a guide). Every request's tokens are what it gives alone.
+        A request may carry a guide (keys guide, guide_state) and, in the penalised family, the slot whose bias table it reads (bias_slot; set
+        it with set_logit_bias first; never a lane). report: the batch has the report on (set_logprobs) and the call fills it per request --
+        read it with logprobs(), [R][stride]. Either goes through rwkv_mi_batch_serve_ex; a queue with neither through rwkv_mi_batch_serve."""
+        requests = list(requests)
         s = _u32(lanes).reshape(-1)
         arr, prompts, seq_lens, seq_tokens = serve_requests(requests)
+        extras = serve_extras(requests)
         n, R = s.size, len(arr)
         stride = max([int(r.stop.max_tokens) for r in arr], default=0)
         out = np.empty((R, stride), dtype=np.uint32)
         lens = np.zeros(R, dtype=np.uint32)
         why, lane, start = (np.empty(R, dtype=np.uint32) for _ in range(3))
         last = np.empty(n, dtype=np.uint32)
+        g_state, g_misses = np.zeros(R, dtype=np.uint32), np.zeros(R, dtype=np.uint32)
         ms = ctypes.c_float(0.0)
-        if not self._L.rwkv_mi_batch_serve(self._ptr, s.ctypes.data_as(P_UINT32), n, int(family), arr, R, prompts.ctypes.data_as(P_UINT32),
-                                           seq_lens.ctypes.data_as(P_UINT32), seq_tokens.ctypes.data_as(P_UINT32), stride,
-                                           ctypes.cast(out.ctypes.data, P_UINT32), lens.ctypes.data_as(P_UINT32), why.ctypes.data_as(P_UINT32),
-                                           lane.ctypes.data_as(P_UINT32), start.ctypes.data_as(P_UINT32), last.ctypes.data_as(P_UINT32), ctypes.byref(ms)):
+        args = (self._ptr, s.ctypes.data_as(P_UINT32), n, int(family), arr, R, prompts.ctypes.data_as(P_UINT32),
+                seq_lens.ctypes.data_as(P_UINT32), seq_tokens.ctypes.data_as(P_UINT32), stride,
+                ctypes.cast(out.ctypes.data, P_UINT32), lens.ctypes.data_as(P_UINT32), why.ctypes.data_as(P_UINT32),
+                lane.ctypes.data_as(P_UINT32), start.ctypes.data_as(P_UINT32), last.ctypes.data_as(P_UINT32), ctypes.byref(ms))
+        if extras is not None or report:
+            if not self._L.rwkv_mi_batch_serve_ex(*args, extras, g_state.ctypes.data_as(P_UINT32), g_misses.ctypes.data_as(P_UINT32)):
+                self._fail("rwkv_mi_batch_serve_ex")
+        elif not self._L.rwkv_mi_batch_serve(*args):
             self._fail("rwkv_mi_batch_serve")
         return {"tokens": [out[q, : int(lens[q])].copy() for q in range(R)], "stopped_by": why, "lane": lane, "start_pass": start,
-                "last_request": last, "elapsed_ms": float(ms.value)}
+                "last_request": last, "elapsed_ms": float(ms.value), "guide_state": g_state, "guide_misses": g_misses}
 
     # --- speculative decoding (include/rwkv_mi355x.h) ---
 

@@ -46,6 +46,11 @@ run, everything in this process and run; records also go to --out:
                         tokens, then rwkv_mi_batch_decode_until until the slowest has ended; host clock around those calls
   mode serve_admission  the mean time of a pass that admits (every lane, every pass: one prompt token, a budget of one) against one that
                         does not (n requests of the same number of passes), and the difference per admission
+--serve --guide and --serve --logprobs N time rwkv_mi_batch_serve_ex on the same queue -- every request under a guide of four states, each
+allowing a random half of the vocabulary, or the batch's report on at top_n N (both flags: both) -- against the same waves with the guide
+attached to the lanes or the report on, the only way to either before that call; no admission record:
+  mode serve_guide / serve_logprobs [/ serve_guide_logprobs]   as mode serve
+  mode ..._waves        as mode serve_waves, with same_tokens_as_serve and, with the report, same_chosen_as_serve (the log-probs, bit for bit)
 
 --sample --logprobs N[,N...] times the sampled loop (temperature 1.0, top-p 0.8, seed = row) with and without the report of the emitted tokens
 (rwkv_mi_batch_set_logprobs) in the same process, HIP events around each device loop, the smallest of --reps runs, --tokens steps, for every
@@ -289,6 +294,16 @@ def serve(pkg, m, args):
         out = [run() for _ in range(args.reps + 1)]   # (run 0: warm-up -- buffers of the first call, tile-major weight images)
         return min(out[1:], key=lambda r: r[0])
 
+    # the arm: the plain queue, or -- what only waves of decode_until gave before rwkv_mi_batch_serve_ex -- every request under a guide
+    # (--guide: a few states, each allowing a random half of the vocabulary, as --sample --guide builds it) or the batch's report on
+    # (--logprobs N)
+    guided = bool(args.guide)
+    top_n = int(args.logprobs.split(",")[0]) if args.logprobs else None
+    arm = "serve" + ("_guide" if guided else "") + ("_logprobs" if top_n is not None else "")
+    n_states = 4
+    grng = np.random.default_rng(7)
+    edges = [{int(t): int(grng.integers(0, n_states)) for t in np.flatnonzero(grng.random(V) < 0.5)} for _ in range(n_states)] if guided else None
+
     for n in [int(x) for x in args.n.split(",")]:
         R = 4 * n
         rng = np.random.default_rng(1000 + n)   # the queue is fixed by n
@@ -298,20 +313,32 @@ def serve(pkg, m, args):
         useful = sum(budgets)   # (no stop sequences: every request runs to its budget, in both arms)
         lanes = list(range(n))
         b = pkg.RWKVBatch(m, n)
+        if guided:
+            gid = b.create_guide(edges)
+            for q in range(R):
+                reqs[q].update(guide=gid, guide_state=q % n_states)
+        if top_n is not None:
+            b.set_logprobs(top_n)
 
         def served():
+            for s in lanes:
+                if guided:
+                    b.detach_guide(s)   # (the waves attach: a lane brings no guide of its own)
             t0 = time.perf_counter()
-            got = b.serve(lanes, reqs, pkg.SERVE_SAMPLE)
+            got = b.serve(lanes, reqs, pkg.SERVE_SAMPLE, report=top_n is not None)
             host = (time.perf_counter() - t0) * 1e3
             assert [len(t) for t in got["tokens"]] == budgets
-            return host, got["elapsed_ms"], b.last_loop_passes(), got["tokens"]
+            chosen = [row[:budgets[q]] for q, row in enumerate(b.logprobs()[0])] if top_n is not None else []
+            return host, got["elapsed_ms"], b.last_loop_passes(), got["tokens"], chosen
 
         def waves():
             # the same queue statically batched: n requests at a time, prompts in one ragged pass, then the loop until the slowest has ended
-            host, passes, toks = 0.0, 0, []
+            host, passes, toks, chosen = 0.0, 0, [], []
             for w in range(0, R, n):
                 for s in lanes:
                     b.state_load(s, None)
+                    if guided:
+                        b.attach_guide(s, gid, (w + s) % n_states)
                 t0 = time.perf_counter()
                 long = [s for s in lanes if len(prompts[w + s]) > 1]
                 if long:
@@ -321,15 +348,23 @@ def serve(pkg, m, args):
                 host += (time.perf_counter() - t0) * 1e3
                 passes += b.last_loop_passes()
                 toks.extend(out)
-            return host, passes, toks
+                if top_n is not None:
+                    chosen.extend(row[:budgets[w + s]] for s, row in enumerate(b.logprobs()[0]))
+            return host, passes, toks, chosen
 
-        s_host, s_dev, s_passes, s_toks = best(served)
-        w_host, w_passes, w_toks = best(waves)
+        s_host, s_dev, s_passes, s_toks, s_chosen = best(served)
+        w_host, w_passes, w_toks, w_chosen = best(waves)
         same = all(np.array_equal(a, c) for a, c in zip(s_toks, w_toks))
-        emit({"mode": "serve", "n": n, "requests": R, "useful_tokens": useful, "total_ms": round(s_host, 3), "device_ms": round(s_dev, 3), "passes": s_passes,
+        extra = {}
+        if top_n is not None:
+            extra = {"top_n": top_n, "same_chosen_as_serve": bool(all(np.array_equal(a.view(np.uint32), c.view(np.uint32)) for a, c in zip(s_chosen, w_chosen)))}
+        emit({"mode": arm, "n": n, "requests": R, "useful_tokens": useful, "total_ms": round(s_host, 3), "device_ms": round(s_dev, 3), "passes": s_passes,
               "useful_tokens_per_s": round(useful / s_host * 1e3, 1), "ms_per_pass": round(s_dev / s_passes, 4)})
-        emit({"mode": "serve_waves", "n": n, "requests": R, "useful_tokens": useful, "total_ms": round(w_host, 3), "passes": w_passes,
-              "useful_tokens_per_s": round(useful / w_host * 1e3, 1), "waves_over_serve": round(w_host / s_host, 3), "same_tokens_as_serve": bool(same)})
+        emit({"mode": arm + "_waves", "n": n, "requests": R, "useful_tokens": useful, "total_ms": round(w_host, 3), "passes": w_passes,
+              "useful_tokens_per_s": round(useful / w_host * 1e3, 1), "waves_over_serve": round(w_host / s_host, 3), "same_tokens_as_serve": bool(same), **extra})
+        if arm != "serve":
+            b.free()
+            continue
 
         # what an admission costs: a queue in which EVERY pass admits all n lanes (one prompt token, one token) against a call of n requests
         # that admits none after the first pass. Both retire their last request after pass steps - 1, so both enqueue the same passes (the dead
@@ -865,7 +900,7 @@ def main():
     ap.add_argument("--penalties", action="store_true", help="with --sample: also time the penalised sampling loop, on the device and through the host")
     ap.add_argument("--ragged", action="store_true", help="time the ragged pass: prompt ingestion and joining a decode step (see above)")
     ap.add_argument("--until", action="store_true", help="time rwkv_mi_batch_decode_until against the plain sampled loop (see above)")
-    ap.add_argument("--serve", action="store_true", help="time rwkv_mi_batch_serve on a fixed queue of 4 n requests against the same queue in waves of decode_until (see above)")
+    ap.add_argument("--serve", action="store_true", help="time rwkv_mi_batch_serve on a fixed queue of 4 n requests against the same queue in waves of decode_until; with --guide and / or --logprobs N: rwkv_mi_batch_serve_ex with every request guided, the report on (see above)")
     ap.add_argument("--logprobs", default=None, metavar="N[,N...]",
                     help="with --sample: time the sampled loop with and without the report of the emitted tokens, for each top_n of the list (see above)")
     ap.add_argument("--beam", default=None, metavar="W[,W...]",

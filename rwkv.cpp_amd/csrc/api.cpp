@@ -2,6 +2,7 @@
 // re-implemented on the device-resident engine, plus the opt-in rwkv_mi_* extensions (include/rwkv_mi355x.h).
 #include "model.h"
 #include "rwkv_mi355x.h"
+#include "call_layout.h"
 
 #include <cinttypes>
 #include <cmath>
@@ -1114,51 +1115,42 @@ struct rwkv_mi_batch {
     int64_t state_len = 0;
     DevBuf<float> states;              // [2][n_slots][state_len]
     std::vector<uint8_t> parity;
-    DevBuf<RowState> d_rows;           // [2][n_slots]: the row tables of a call (a device loop alternates between the two)
-    PinBuf<RowState> h_rows;           // pinned staging of the same
+    // The words of a call travel in staged tables (devmem.h, Staged): one device buffer with its pinned staging, the five
+    // untyped ones laid out by call_layout.h. Who allocates each, and when it grows, is said where it is done (batch_ensure_*).
+    StagedRows<RowState> rows;         // [2][n_slots]: the row tables of a call (a device loop alternates between the two)
     DrawState draw;                    // the slots' draw state: counters (zero at creation), sampler scratch, occurrence and bias tables
-    // the row table of a drawing call, [n_slots] (model.h, DrawRow: filled by DrawState::row), with its pinned staging -- allocated with the
-    // sampler's buffers by the first drawing call -- and the form of the current call's kernel
-    DevBuf<DrawRow> d_draw_rows;
-    PinBuf<DrawRow> h_draw_rows;
+    // the row table of a drawing call, [n_slots] (rows.h, DrawRow: filled by DrawState::row) -- allocated with the sampler's buffers by the
+    // first drawing call -- and the form of the current call's kernel
+    StagedRows<DrawRow> draw_rows;
     DrawForm form;
     // guided decoding (rwkv_mi_batch_guide_*): the guides' dense tables next[n_states][n_vocab], shared by the slots (which guide a slot has, and
     // its state and miss words, are the draw state's)
     DevBuf<uint16_t> guides[RWKV_MI_GUIDE_MAX];
     uint32_t guide_states[RWKV_MI_GUIDE_MAX] = {};   // n_states of each (0: the id is free)
-    // ragged passes (rwkv_mi_batch_eval_ragged*): the tables of a call -- segments, the short ones again, seg_of[T], last[n] -- in one device
-    // buffer with its pinned staging, grown to the largest call so far; the long segments stay on the host (each is a launch of its own)
-    DevBuf<uint8_t> d_seg;
-    PinBuf<uint8_t> h_seg;
+    // ragged passes (rwkv_mi_batch_eval_ragged*): the tables of a call (SegLayout); the long segments stay on the host
+    Staged seg;
     std::vector<SegState> long_segs;
     SegPass pass;
     // the device loops (batch_run_passes): what the polled ones read between blocks -- allocated by the first of them -- and the passes the
     // last loop enqueued
     BlockPoll poll;
     size_t last_loop_passes = 0;
-    // rwkv_mi_batch_decode_until: the words of a call in one device buffer with its pinned staging, laid out by StopLayout for the call's n and
-    // sequences (capacity: n_slots rows of RWKV_MI_STOP_MAX_SEQS sequences of RWKV_MI_STOP_MAX_LEN tokens) -- allocated by the first call
-    DevBuf<uint8_t> d_stop;
-    PinBuf<uint8_t> h_stop;
-    StopTables stop{};                   // the device pointers of the current call
-    size_t stop_off_lens = 0;            // where lens[n], reasons[n] start in both buffers
-    // rwkv_mi_batch_decode_beam: the per-row words of a call (BeamTables: scores, finished words, lengths, live count, candidates) in one device
-    // buffer for n_slots rows, with the pinned staging of the part a call uploads and reads back -- allocated by the first beam call
-    DevBuf<uint8_t> d_beam;
-    PinBuf<uint8_t> h_beam;
+    // rwkv_mi_batch_decode_until: the stop words of a call (StopLayout), the device pointers of the current call and where its lengths and
+    // reasons, which come back, lie
+    Staged stop_words;
+    StopTables stop{};
+    Field<uint32_t> stop_lens, stop_reasons;
+    // rwkv_mi_batch_decode_beam: the per-row words of a call (BeamLayout)
+    Staged beam;
     // rwkv_mi_batch_eval_draft: the logits of every token of a pass [T][n_vocab] and the stash of its recurrences' inputs (kernels.h, DraftStash),
-    // both grown to the largest call so far; the layers' vectors, keep[n_slots] and the emitted tokens [n_slots][1 + RWKV_MI_DRAFT_MAX] with
-    // their pinned staging (keep first) -- allocated by the first draft call
+    // both grown to the largest call so far; the layers' vectors and the words a pass leaves (DraftLayout) -- allocated by the first draft call
     DevBuf<float> d_draft_logits;
     DevBuf<float> d_draft_stash;
     DevBuf<DraftLayer> d_draft_layers;
-    DevBuf<uint32_t> d_draft_words;
-    PinBuf<uint32_t> h_draft_words;
-    // rwkv_mi_batch_serve: the words of a call -- the request table, prompts, stop sequences, lane and request words, the emitted tokens -- in
-    // one device buffer with its pinned staging, laid out by ServeLayout and grown to the largest call so far; the fresh state every request
-    // without a from_slot starts from, filled once -- allocated by the first call
-    DevBuf<uint8_t> d_serve;
-    PinBuf<uint8_t> h_serve;
+    Staged draft_words;
+    // rwkv_mi_batch_serve: the words of a call (ServeLayout); the fresh state every request without a from_slot starts from, filled once --
+    // allocated by the first call
+    Staged serve;
     DevBuf<float> serve_fresh;          // [state_len]
     LogprobReport lp;                   // the report of the batch's emitting calls (rwkv_mi_batch_set_logprobs)
 
@@ -1272,14 +1264,14 @@ static void batch_stage_rows(rwkv_mi_batch * B, const uint32_t * slots, size_t n
     for (int tb = 0; tb < tables; tb++)
         for (size_t i = 0; i < n; i++) {
             const int p = B->parity[slots[i]] ^ tb;
-            B->h_rows.p[(size_t) tb * B->n_slots + i] = RowState{B->slot_buf(slots[i], p), B->slot_buf(slots[i], p ^ 1)};
+            B->rows.h()[(size_t) tb * B->n_slots + i] = RowState{B->slot_buf(slots[i], p), B->slot_buf(slots[i], p ^ 1)};
         }
 }
 
 // the first n rows of the staged tables, whoever staged them, to the device
 static bool batch_upload_rows(rwkv_mi_batch * B, size_t n, int tables) {
     for (int tb = 0; tb < tables; tb++)
-        BATCH_HIP_OK(B, hipMemcpyAsync(B->d_rows.p + (size_t) tb * B->n_slots, B->h_rows.p + (size_t) tb * B->n_slots, n * sizeof(RowState), hipMemcpyHostToDevice, B->run->stream));
+        BATCH_HIP_OK(B, B->rows.upload_rows((size_t) tb * B->n_slots, (size_t) tb * B->n_slots + n, B->run->stream));
     return true;
 }
 
@@ -1354,14 +1346,13 @@ static bool batch_upload_ragged(rwkv_mi_batch * B, const BatchCall & c, size_t T
     }
     size_t n_short = 0;
     for (size_t i = 0; i < n; i++) if (!seg_takes_seq_kernel(m, lens[i])) n_short++;
-    const size_t off_short = n * sizeof(SegState), off_seg_of = off_short + n_short * sizeof(SegState), off_last = off_seg_of + T * sizeof(int32_t);
-    const size_t bytes = off_last + n * sizeof(int32_t);
-    if (bytes > B->d_seg.count) {
-        const hipError_t e = grow(want(B->d_seg, bytes), want(B->h_seg, bytes));
+    const SegLayout L(n, n_short, T);
+    if (L.bytes > B->seg.bytes()) {   // (grown to the largest call so far)
+        const hipError_t e = grow(want(B->seg, L.bytes));
         RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the segment tables of %zu tokens: %s", T, hipGetErrorString(e));
     }
-    SegState * segs = (SegState *) B->h_seg.p, * shorts = (SegState *) (B->h_seg.p + off_short);
-    int32_t * seg_of = (int32_t *) (B->h_seg.p + off_seg_of), * last = (int32_t *) (B->h_seg.p + off_last);
+    SegState * segs = B->seg.h(L.segs), * shorts = B->seg.h(L.shorts);
+    int32_t * seg_of = B->seg.h(L.seg_of), * last = B->seg.h(L.last);
     B->long_segs.clear();
     int32_t t = 0;
     size_t k = 0;
@@ -1375,11 +1366,11 @@ static bool batch_upload_ragged(rwkv_mi_batch * B, const BatchCall & c, size_t T
         t = g.t1;
     }
     memcpy(run->h_tokens.p, c.tokens, T * sizeof(uint32_t));
-    BATCH_HIP_OK(B, hipMemcpyAsync(B->d_seg.p, B->h_seg.p, bytes, hipMemcpyHostToDevice, run->stream));
+    BATCH_HIP_OK(B, B->seg.upload(0, L.bytes, run->stream));
     BATCH_HIP_OK(B, hipMemcpyAsync(run->d_tokens.p, run->h_tokens.p, T * sizeof(uint32_t), hipMemcpyHostToDevice, run->stream));
     SegPass & ps = B->pass;
-    ps.d_segs = (const SegState *) B->d_seg.p; ps.d_short = (const SegState *) (B->d_seg.p + off_short);
-    ps.d_seg_of = (const int32_t *) (B->d_seg.p + off_seg_of); ps.d_last = (const int32_t *) (B->d_seg.p + off_last);
+    ps.d_segs = B->seg.d(L.segs); ps.d_short = B->seg.d(L.shorts);
+    ps.d_seg_of = B->seg.d(L.seg_of); ps.d_last = B->seg.d(L.last);
     ps.h_long = B->long_segs.data();
     ps.n = (int64_t) n; ps.n_short = (int64_t) n_short; ps.n_long = (int64_t) B->long_segs.size();
     return true;
@@ -1422,24 +1413,12 @@ static StopRow stop_row(const rwkv_mi_stop_params & sp, const uint32_t * seq_len
     return row;
 }
 
-// Where the stop words of a call of n rows with n_seqs sequences of n_toks tokens in all lie in the stop buffer (byte offsets): the rows, their
-// live words, lengths and reasons, the live count, the sequences' lengths and tokens.
-struct StopLayout {
-    size_t rows, live, lens, reasons, count, seq_lens, seq_tokens, bytes;
-    StopLayout(size_t n, size_t n_seqs, size_t n_toks) {
-        size_t o = 0;
-        auto take = [&o](size_t b) { const size_t at = o; o += b; return at; };
-        rows = take(n * sizeof(StopRow)); live = take(n * 4); lens = take(n * 4); reasons = take(n * 4); count = take(4);
-        seq_lens = take(n_seqs * 4); seq_tokens = take(n_toks * 4);
-        bytes = o;
-    }
-};
-
-// the poll words of the batch and the stop buffers: on the first call of the family
+// the poll words of the batch and the stop words: on the first call of the family, for the largest call there is (n_slots rows of
+// RWKV_MI_STOP_MAX_SEQS sequences of RWKV_MI_STOP_MAX_LEN tokens)
 static bool batch_ensure_stop(rwkv_mi_batch * B) {
     const size_t bytes = StopLayout(B->n_slots, B->n_slots * RWKV_MI_STOP_MAX_SEQS, B->n_slots * RWKV_MI_STOP_MAX_SEQS * RWKV_MI_STOP_MAX_LEN).bytes;
     hipError_t e = B->poll.ensure();
-    if (e == hipSuccess && !B->d_stop) e = grow(want(B->d_stop, bytes), want(B->h_stop, bytes));   // (one decision: both or neither)
+    if (e == hipSuccess && !B->stop_words) e = grow(want(B->stop_words, bytes));
     RW_CTX_CHECK(B->ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the stop tables of %zu slots: %s", B->n_slots, hipGetErrorString(e));
     return true;
 }
@@ -1449,19 +1428,18 @@ static bool batch_ensure_stop(rwkv_mi_batch * B) {
 static bool batch_upload_stops(rwkv_mi_batch * B, const BatchCall & c) {
     const size_t n = c.n;
     size_t n_seqs = 0, n_toks = 0;
-    StopRow * rows = (StopRow *) B->h_stop.p;   // (StopLayout::rows is 0)
-    for (size_t i = 0; i < n; i++) rows[i] = stop_row(c.stops[i], c.seq_lens, &n_seqs, &n_toks);
+    const Staged & w = B->stop_words;
+    for (size_t i = 0; i < n; i++) (void) stop_row(c.stops[i], c.seq_lens, &n_seqs, &n_toks);   // (the call's totals: the layout needs them)
     const StopLayout L(n, n_seqs, n_toks);
-    uint8_t * h = B->h_stop.p, * d = B->d_stop.p;
-    auto hw = [h](size_t off) { return (uint32_t *) (h + off); };
-    auto dw = [d](size_t off) { return (uint32_t *) (d + off); };
-    for (size_t i = 0; i < n; i++) { hw(L.live)[i] = 1u; hw(L.lens)[i] = 0u; hw(L.reasons)[i] = RWKV_MI_NO_TOKEN; }
-    *hw(L.count) = (uint32_t) n;
-    if (n_seqs) memcpy(h + L.seq_lens, c.seq_lens, n_seqs * 4);
-    if (n_toks) memcpy(h + L.seq_tokens, c.seq_tokens, n_toks * 4);
-    BATCH_HIP_OK(B, hipMemcpyAsync(d, h, L.bytes, hipMemcpyHostToDevice, B->run->stream));
-    B->stop = StopTables{(const StopRow *) (d + L.rows), dw(L.seq_lens), dw(L.seq_tokens), dw(L.live), dw(L.lens), dw(L.reasons), dw(L.count)};
-    B->stop_off_lens = L.lens;
+    size_t seq0 = 0, tok0 = 0;
+    for (size_t i = 0; i < n; i++) w.h(L.rows)[i] = stop_row(c.stops[i], c.seq_lens, &seq0, &tok0);
+    for (size_t i = 0; i < n; i++) { w.h(L.live)[i] = 1u; w.h(L.lens)[i] = 0u; w.h(L.reasons)[i] = RWKV_MI_NO_TOKEN; }
+    *w.h(L.count) = (uint32_t) n;
+    if (n_seqs) memcpy(w.h(L.seq_lens), c.seq_lens, L.seq_lens.bytes());
+    if (n_toks) memcpy(w.h(L.seq_tokens), c.seq_tokens, L.seq_tokens.bytes());
+    BATCH_HIP_OK(B, w.upload(0, L.bytes, B->run->stream));
+    B->stop = StopTables{w.d(L.rows), w.d(L.seq_lens), w.d(L.seq_tokens), w.d(L.live), w.d(L.lens), w.d(L.reasons), w.d(L.count)};
+    B->stop_lens = L.lens; B->stop_reasons = L.reasons;
     return true;
 }
 
@@ -1484,7 +1462,7 @@ static bool batch_ensure_draw(rwkv_mi_batch * B, const BatchCall & c) {
     if (c.until && !batch_ensure_stop(B)) return false;
     if (c.draw == Draw::none) return true;
     const size_t n = B->n_slots;
-    const hipError_t e = grow(want(B->d_draw_rows, B->d_draw_rows ? 0 : n), want(B->h_draw_rows, B->h_draw_rows ? 0 : n));
+    const hipError_t e = grow(want(B->draw_rows, B->draw_rows ? 0 : n));
     RW_CTX_CHECK(B->ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the sampler's row tables for %zu slots: %s", n, hipGetErrorString(e));
     return B->draw.ensure_sampler(B->ctx, B->run->stream) && (c.draw != Draw::penalized || B->draw.ensure_penalty(B->ctx, B->run->stream));
 }
@@ -1494,11 +1472,11 @@ static bool batch_ensure_draw(rwkv_mi_batch * B, const BatchCall & c) {
 static bool batch_upload_draw_rows(rwkv_mi_batch * B, const BatchCall & c, bool loop) {
     const bool pen = c.draw == Draw::penalized;
     for (size_t i = 0; i < c.n; i++) {
-        DrawRow & r = B->h_draw_rows.p[i];
+        DrawRow & r = B->draw_rows.h()[i];
         r = B->draw.row(c.slots[i], c.params[i], pen ? &c.penalties[i] : nullptr, loop ? 1u : pen ? c.penalties[i].record : 0u, B->guides);
         if (loop) r.p.u = -1.0f;
     }
-    BATCH_HIP_OK(B, hipMemcpyAsync(B->d_draw_rows.p, B->h_draw_rows.p, c.n * sizeof(DrawRow), hipMemcpyHostToDevice, B->run->stream));
+    BATCH_HIP_OK(B, B->draw_rows.upload_rows(0, c.n, B->run->stream));
     return true;
 }
 
@@ -1513,7 +1491,7 @@ static bool batch_upload_call(rwkv_mi_batch * B, const BatchCall & c, size_t T, 
 // a loop sets the step
 static RowSampler batch_sampler(rwkv_mi_batch * B, uint32_t * hist, const RowReport * report) {
     RowSampler s;
-    s.form = B->form; s.rows = B->d_draw_rows.p; s.probs = B->draw.probs.p;
+    s.form = B->form; s.rows = B->draw_rows.d(); s.probs = B->draw.probs.p;
     s.hist = hist; s.report = report;
     return s;
 }
@@ -1549,7 +1527,7 @@ static bool batch_pass(rwkv_mi_batch * B, const BatchCall & c) {
     sp.argmax = c.argmax_out != nullptr;
     const bool want_logits = drawn || scoring || c.logits_out;
     const bool ok = c.lens ? forward_segs(run, B->pass, (int64_t) T, want_logits, drawn ? &sampler : nullptr, scoring ? &sp : nullptr)
-                           : forward_rows(run, B->d_rows.p, (int64_t) c.n, want_logits, drawn ? &sampler : nullptr);
+                           : forward_rows(run, B->rows.d(), (int64_t) c.n, want_logits, drawn ? &sampler : nullptr);
     if (!ok) return batch_fail_drained(B);
     if (drawn) BATCH_HIP_OK(B, hipMemcpyAsync(run->h_tokens.p, run->d_tokens.p, c.n * sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream));
     if (c.logits_out) BATCH_HIP_OK(B, hipMemcpyAsync(c.logits_out, run->d_logits.p, c.n * (size_t) ctx->model->n_vocab() * sizeof(float), hipMemcpyDeviceToHost, run->stream));
@@ -1582,11 +1560,11 @@ static bool batch_ensure_draft(rwkv_mi_batch * B, size_t T) {
     rwkv_context * ctx = B->ctx;
     const Model & m = *ctx->model;
     const size_t V = (size_t) m.n_vocab(), D = (size_t) m.n_embed(), L = (size_t) (m.layer_end - m.layer_begin);
-    const size_t logits = T * V, stash = L * (size_t) (draft_stash_inputs(m) + 3) * T * D, words = B->n_slots * (2 + RWKV_MI_DRAFT_MAX);
+    const size_t logits = T * V, stash = L * (size_t) (draft_stash_inputs(m) + 3) * T * D, words = DraftLayout(B->n_slots).bytes;
     const bool first = !B->d_draft_layers;
     if (logits > B->d_draft_logits.count || stash > B->d_draft_stash.count) BATCH_HIP_OK(B, hipStreamSynchronize(B->run->stream));   // (an earlier call may still read the old ones)
     const hipError_t e = grow(want(B->d_draft_logits, logits > B->d_draft_logits.count ? logits : 0), want(B->d_draft_stash, stash > B->d_draft_stash.count ? stash : 0),
-                              want(B->d_draft_layers, first ? L : 0), want(B->d_draft_words, first ? words : 0), want(B->h_draft_words, first ? words : 0));
+                              want(B->d_draft_layers, first ? L : 0), want(B->draft_words, first ? words : 0));
     RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the draft buffers of %zu tokens: %s", T, hipGetErrorString(e));
     if (first) {
         std::vector<DraftLayer> lw(L);
@@ -1597,7 +1575,7 @@ static bool batch_ensure_draft(rwkv_mi_batch * B, size_t T) {
             lw[i] = DraftLayer{m.arch_major == 7 ? nullptr : f(faaaa ? w.att_time_faaaa : w.att_time_first), m.arch_major >= 6 ? nullptr : f(w.att_time_decay)};
         }
         const hipError_t eu = hipMemcpy(B->d_draft_layers.p, lw.data(), L * sizeof(DraftLayer), hipMemcpyHostToDevice);
-        if (eu != hipSuccess) { B->d_draft_layers.reset(); B->d_draft_words.reset(); B->h_draft_words.reset(); }
+        if (eu != hipSuccess) { B->d_draft_layers.reset(); B->draft_words.reset(); }
         BATCH_HIP_OK(B, eu);
     }
     return true;
@@ -1615,20 +1593,23 @@ static bool batch_draft(rwkv_mi_batch * B, const BatchCall & c, uint32_t * token
     if (!batch_upload_call(B, c, T, true)) return false;   // (loop: the generator draws, every step records)
     const Model & m = *ctx->model;
     const int W = 1 + RWKV_MI_DRAFT_MAX;
+    const DraftLayout DL(B->n_slots);
+    const Staged & w = B->draft_words;
     DraftPass d;
     d.stash.base = B->d_draft_stash.p; d.stash.n_in = draft_stash_inputs(m); d.stash.plane = (int64_t) T * m.n_embed();
     d.stash.layer0 = m.layer_begin; d.stash.per_layer = m.state_per_layer();
     d.lw = B->d_draft_layers.p; d.logits_all = B->d_draft_logits.p;
-    d.form = B->form; d.rows = B->d_draw_rows.p; d.probs = B->draw.probs.p;
-    d.keep = B->d_draft_words.p; d.out = B->d_draft_words.p + B->n_slots; d.out_stride = W;
+    d.form = B->form; d.rows = B->draw_rows.d(); d.probs = B->draw.probs.p;
+    d.keep = w.d(DL.keep); d.out = w.d(DL.out); d.out_stride = W;
     if (!forward_draft(run, B->pass, (int64_t) T, d)) return batch_fail_drained(B);
-    BATCH_HIP_OK(B, hipMemcpyAsync(B->h_draft_words.p, B->d_draft_words.p, c.n * sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream));
-    BATCH_HIP_OK(B, hipMemcpyAsync(B->h_draft_words.p + B->n_slots, d.out, c.n * (size_t) W * sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream));
+    const Field<uint32_t> keep = DL.keep.first(c.n), out = DL.out.first(c.n * (size_t) W);   // (the call's c.n rows of both)
+    BATCH_HIP_OK(B, w.fetch(keep.off, keep.end(), run->stream));
+    BATCH_HIP_OK(B, w.fetch(out.off, out.end(), run->stream));
     if (c.logits_out) BATCH_HIP_OK(B, hipMemcpyAsync(c.logits_out, run->d_logits.p, c.n * (size_t) m.n_vocab() * sizeof(float), hipMemcpyDeviceToHost, run->stream));
     BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));
     for (size_t r = 0; r < c.n; r++) {
-        c.lens_out[r] = B->h_draft_words.p[r];
-        const uint32_t * e = B->h_draft_words.p + B->n_slots + r * (size_t) W;
+        c.lens_out[r] = w.h(DL.keep)[r];
+        const uint32_t * e = w.h(DL.out) + r * (size_t) W;
         for (size_t j = 0; j < c.stride; j++) tokens_out[r * c.stride + j] = j < (size_t) W ? e[j] : RWKV_MI_NO_TOKEN;
     }
     batch_flip(B, c);
@@ -1662,7 +1643,7 @@ static bool batch_run_passes(rwkv_mi_batch * B, size_t max_passes, const uint32_
     for (size_t b = 0; passes < max_passes; b++) {
         for (const size_t end = std::min(max_passes, passes + K); passes < end; passes++) {
             sampler.step = (uint32_t) passes;
-            sampler.used = B->d_rows.p + (passes & 1) * B->n_slots; sampler.other = B->d_rows.p + ((passes & 1) ^ 1) * B->n_slots;
+            sampler.used = B->rows.d() + (passes & 1) * B->n_slots; sampler.other = B->rows.d() + ((passes & 1) ^ 1) * B->n_slots;
             if (!step(sampler)) return batch_fail_drained(B);
         }
         if (!poll_word) break;
@@ -1703,7 +1684,7 @@ static bool batch_loop(rwkv_mi_batch * B, const BatchCall & c, size_t n_tokens, 
     const bool report = B->lp.enabled;   // (every step of a loop emits)
     if (!batch_ensure_report(B, n, n_tokens)) return false;
     if (!batch_upload_call(B, c, T, true)) return false;
-    if (c.draw == Draw::sample) launch_sample_seek_rows(B->d_draw_rows.p, (int64_t) n, 0ull, run->stream);   // the named slots' streams start over
+    if (c.draw == Draw::sample) launch_sample_seek_rows(B->draw_rows.d(), (int64_t) n, 0ull, run->stream);   // the named slots' streams start over
     const RowReport rep = batch_report(B);
     RowSampler sampler = batch_sampler(B, hist.p, report ? &rep : nullptr);
     // the token of each row lands where its next embedding lookup reads it: sampled inside the pass's chain bracket, or -- the greedy argmax,
@@ -1745,7 +1726,7 @@ static bool batch_until(rwkv_mi_batch * B, const BatchCall & c, uint32_t * token
     const bool report = B->lp.enabled;   // (every step of a live row emits; a slot no row wrote is never read back: report_store fills behind lens)
     if (!batch_ensure_report(B, n, budget)) return false;
     if (!batch_upload_call(B, c, T, true)) return false;
-    if (c.draw == Draw::sample) launch_sample_seek_rows(B->d_draw_rows.p, (int64_t) n, 0ull, run->stream);   // the named slots' streams start over
+    if (c.draw == Draw::sample) launch_sample_seek_rows(B->draw_rows.d(), (int64_t) n, 0ull, run->stream);   // the named slots' streams start over
     BATCH_HIP_OK(B, hipMemsetAsync(hist.p, 0xFF, budget * n * sizeof(uint32_t), run->stream));
     const RowReport rep = batch_report(B);
     RowSampler sampler = batch_sampler(B, hist.p, report ? &rep : nullptr);
@@ -1753,9 +1734,9 @@ static bool batch_until(rwkv_mi_batch * B, const BatchCall & c, uint32_t * token
     if (!batch_run_passes(B, budget, B->stop.live_count, sampler, [&](const RowSampler & s) { return forward_rows(run, s.used, (int64_t) n, true, &s); })) return false;
     const size_t passes = B->last_loop_passes;
     std::vector<uint32_t> h(tokens_out ? passes * n : 0);
-    uint32_t * h_lens = (uint32_t *) (B->h_stop.p + B->stop_off_lens);   // lens[n], then reasons[n]
+    const uint32_t * h_lens = B->stop_words.h(B->stop_lens), * h_reasons = B->stop_words.h(B->stop_reasons);   // (adjacent: one copy)
     if (tokens_out) BATCH_HIP_OK(B, hipMemcpyAsync(h.data(), hist.p, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream));
-    BATCH_HIP_OK(B, hipMemcpyAsync(h_lens, B->stop.lens, 2 * n * sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream));
+    BATCH_HIP_OK(B, B->stop_words.fetch(B->stop_lens.off, B->stop_reasons.end(), run->stream));
     if (!batch_passes_done(B, elapsed_ms)) return false;
     // (every budget is at most `budget`, and the loop ends on a live count of 0 or at `budget`: every row has retired)
     for (size_t r = 0; r < n; r++)
@@ -1763,7 +1744,7 @@ static bool batch_until(rwkv_mi_batch * B, const BatchCall & c, uint32_t * token
     for (size_t r = 0; r < n; r++) {
         const size_t len = h_lens[r];
         c.lens_out[r] = (uint32_t) len;
-        if (c.stopped_by_out) c.stopped_by_out[r] = h_lens[n + r];
+        if (c.stopped_by_out) c.stopped_by_out[r] = h_reasons[r];
         for (size_t j = 0; tokens_out && j < c.stride; j++) tokens_out[r * c.stride + j] = j < len ? h[j * n + r] : RWKV_MI_NO_TOKEN;
         if (len & 1) B->parity[c.slots[r]] ^= 1;
     }
@@ -1772,31 +1753,6 @@ static bool batch_until(rwkv_mi_batch * B, const BatchCall & c, uint32_t * token
 }
 
 // ---- continuous batching (rwkv_mi_batch_serve) ----
-
-// Where the words of a call of n lanes and R requests lie in the serve buffer (byte offsets). What goes up: the request table, the prompts and
-// the sequences, the lane words in their start values, the head of the queue and the work count. From `down` on, what comes back as well: the
-// lanes' last requests, the requests' lengths, reasons, lanes and start passes, and their emitted tokens out[R][stride] (filled on the device).
-// guided (a call of rwkv_mi_batch_serve_ex with a guided request; no bytes otherwise): the lanes' guide state and miss words go up, the
-// requests' -- the start state and 0 on the way up, the final words on the way back -- do both.
-struct ServeLayout {
-    size_t reqs, prompts, seq_lens, seq_tokens, lane_slot, req, pos, draw, admit, g_state, g_misses, next, work, down, last, lens, reasons, lane, start,
-           req_g_state, req_g_misses, out, bytes;
-    ServeLayout(size_t n, size_t R, size_t n_prompt, size_t n_seqs, size_t n_toks, size_t stride, bool guided) {
-        size_t o = 0;
-        auto take = [&o](size_t b) { const size_t at = o; o += b; return at; };
-        const size_t g = guided ? 4 : 0;
-        reqs = take(R * sizeof(ServeReq));
-        prompts = take(n_prompt * 4); seq_lens = take(n_seqs * 4); seq_tokens = take(n_toks * 4);
-        lane_slot = take(n * 4); req = take(n * 4); pos = take(n * 4); draw = take(n * 4); admit = take(n * 4);
-        g_state = take(n * g); g_misses = take(n * g);
-        next = take(4); work = take(4);
-        down = o;
-        last = take(n * 4); lens = take(R * 4); reasons = take(R * 4); lane = take(R * 4); start = take(R * 4);
-        req_g_state = take(R * g); req_g_misses = take(R * g);
-        out = take(R * stride * 4);
-        bytes = o;
-    }
-};
 
 // every argument of a serve call, nothing changed yet. *n_prompt_out = the prompt tokens of the queue
 static bool batch_check_serve(rwkv_mi_batch * B, const BatchCall & c, size_t * n_prompt_out) {
@@ -1863,10 +1819,10 @@ static bool batch_ensure_serve(rwkv_mi_batch * B, size_t bytes) {
     rwkv_context * ctx = B->ctx;
     const Model & m = *ctx->model;
     hipStream_t st = B->run->stream;
-    const bool more = bytes > B->d_serve.count, first = !B->serve_fresh;
+    const bool more = bytes > B->serve.bytes(), first = !B->serve_fresh;   // (grown to the largest call so far)
     if (more) BATCH_HIP_OK(B, hipStreamSynchronize(st));   // (an earlier call may still read the old one)
     hipError_t e = B->poll.ensure();
-    if (e == hipSuccess) e = grow(want(B->d_serve, more ? bytes : 0), want(B->h_serve, more ? bytes : 0), want(B->serve_fresh, first ? (size_t) B->state_len : 0));
+    if (e == hipSuccess) e = grow(want(B->serve, more ? bytes : 0), want(B->serve_fresh, first ? (size_t) B->state_len : 0));
     RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the serve tables (%zu bytes): %s", bytes, hipGetErrorString(e));
     if (first) {
         if (m.arch_major >= 5) e = hipMemsetAsync(B->serve_fresh.p, 0, (size_t) B->state_len * sizeof(float), st);
@@ -1921,10 +1877,8 @@ static bool batch_serve(rwkv_mi_batch * B, const BatchCall & c, uint32_t * token
     const bool report = c.serve_ex && B->lp.enabled;
     if (report && !batch_ensure_report(B, R, c.stride)) return false;
     BATCH_HIP_OK(B, hipStreamSynchronize(run->stream));   // (the previous call's copies may still read the staging)
-    uint8_t * h = B->h_serve.p, * d = B->d_serve.p;
-    auto hw = [h](size_t off) { return (uint32_t *) (h + off); };
-    auto dw = [d](size_t off) { return (uint32_t *) (d + off); };
-    ServeReq * reqs = (ServeReq *) (h + L.reqs);
+    const Staged & w = B->serve;
+    ServeReq * reqs = w.h(L.reqs);
     size_t p0 = 0;
     for (size_t q = 0; q < R; q++) {
         const rwkv_mi_serve_request & rq = c.requests[q];
@@ -1938,29 +1892,29 @@ static bool batch_serve(rwkv_mi_batch * B, const BatchCall & c, uint32_t * token
         const rwkv_mi_serve_extra ex = c.extras ? c.extras[q] : rwkv_mi_serve_extra{RWKV_MI_NO_GUIDE, 0u, RWKV_MI_NO_SLOT, 0u};
         if (ex.guide != RWKV_MI_NO_GUIDE) row.next = B->guides[ex.guide].p;
         if (pen && ex.bias_slot != RWKV_MI_NO_SLOT) row.bias = B->draw.bias_of(ex.bias_slot);
-        if (any_guided) { hw(L.req_g_state)[q] = ex.guide != RWKV_MI_NO_GUIDE ? ex.guide_state : 0u; hw(L.req_g_misses)[q] = 0u; }
+        if (any_guided) { w.h(L.req_g_state)[q] = ex.guide != RWKV_MI_NO_GUIDE ? ex.guide_state : 0u; w.h(L.req_g_misses)[q] = 0u; }
         const float * start = rq.from_slot == RWKV_MI_NO_SLOT ? B->serve_fresh.p : B->slot_buf(rq.from_slot, B->parity[rq.from_slot]);
         reqs[q] = ServeReq{row, stop_rows[q], rq.prompt_len, (uint32_t) p0, start};
         p0 += rq.prompt_len;
     }
-    for (size_t r = 0; any_guided && r < n; r++) { hw(L.g_state)[r] = 0u; hw(L.g_misses)[r] = 0u; }
-    memcpy(h + L.prompts, c.prompts, n_prompt * 4);
-    if (n_seqs) memcpy(h + L.seq_lens, c.seq_lens, n_seqs * 4);
-    if (n_toks) memcpy(h + L.seq_tokens, c.seq_tokens, n_toks * 4);
-    for (size_t r = 0; r < n; r++) { hw(L.lane_slot)[r] = c.slots[r]; hw(L.req)[r] = SERVE_FREE; hw(L.pos)[r] = 0u; hw(L.draw)[r] = 0u; hw(L.admit)[r] = 0u; hw(L.last)[r] = RWKV_MI_NO_TOKEN; }
+    for (size_t r = 0; any_guided && r < n; r++) { w.h(L.g_state)[r] = 0u; w.h(L.g_misses)[r] = 0u; }
+    memcpy(w.h(L.prompts), c.prompts, L.prompts.bytes());
+    if (n_seqs) memcpy(w.h(L.seq_lens), c.seq_lens, L.seq_lens.bytes());
+    if (n_toks) memcpy(w.h(L.seq_tokens), c.seq_tokens, L.seq_tokens.bytes());
+    for (size_t r = 0; r < n; r++) { w.h(L.lane_slot)[r] = c.slots[r]; w.h(L.req)[r] = SERVE_FREE; w.h(L.pos)[r] = 0u; w.h(L.draw)[r] = 0u; w.h(L.admit)[r] = 0u; w.h(L.last)[r] = RWKV_MI_NO_TOKEN; }
     batch_stage_rows(B, c.slots, n, 2);
-    *hw(L.next) = 0u; *hw(L.work) = (uint32_t) n;
-    for (size_t q = 0; q < R; q++) { hw(L.lens)[q] = 0u; hw(L.reasons)[q] = RWKV_MI_NO_TOKEN; hw(L.lane)[q] = RWKV_MI_NO_TOKEN; hw(L.start)[q] = RWKV_MI_NO_TOKEN; }
-    BATCH_HIP_OK(B, hipMemcpyAsync(d, h, L.out, hipMemcpyHostToDevice, run->stream));
-    BATCH_HIP_OK(B, hipMemsetAsync(d + L.out, 0xFF, R * c.stride * 4, run->stream));
+    *w.h(L.next) = 0u; *w.h(L.work) = (uint32_t) n;
+    for (size_t q = 0; q < R; q++) { w.h(L.lens)[q] = 0u; w.h(L.reasons)[q] = RWKV_MI_NO_TOKEN; w.h(L.lane)[q] = RWKV_MI_NO_TOKEN; w.h(L.start)[q] = RWKV_MI_NO_TOKEN; }
+    BATCH_HIP_OK(B, w.upload(0, L.out.off, run->stream));
+    BATCH_HIP_OK(B, hipMemsetAsync(w.d(L.out), 0xFF, L.out.bytes(), run->stream));
     if (!batch_upload_rows(B, n, 2)) return false;
     RowServe serve{};
-    serve.t = ServeTables{(const ServeReq *) (d + L.reqs), dw(L.prompts), dw(L.seq_lens), dw(L.seq_tokens), dw(L.out), (uint32_t) c.stride,
-                          dw(L.lens), dw(L.reasons), dw(L.lane), dw(L.start), dw(L.req), dw(L.pos), dw(L.draw), dw(L.admit), dw(L.last), dw(L.lane_slot),
-                          c.draw != Draw::none ? B->d_draw_rows.p : nullptr, B->draw.counters.p, B->draw.counts.p, dw(L.next), dw(L.work),
+    serve.t = ServeTables{w.d(L.reqs), w.d(L.prompts), w.d(L.seq_lens), w.d(L.seq_tokens), w.d(L.out), (uint32_t) c.stride,
+                          w.d(L.lens), w.d(L.reasons), w.d(L.lane), w.d(L.start), w.d(L.req), w.d(L.pos), w.d(L.draw), w.d(L.admit), w.d(L.last), w.d(L.lane_slot),
+                          c.draw != Draw::none ? B->draw_rows.d() : nullptr, B->draw.counters.p, B->draw.counts.p, w.d(L.next), w.d(L.work),
                           (uint32_t) R, (uint32_t) n_vocab,
-                          any_guided ? dw(L.g_state) : nullptr, any_guided ? dw(L.g_misses) : nullptr,
-                          any_guided ? dw(L.req_g_state) : nullptr, any_guided ? dw(L.req_g_misses) : nullptr};
+                          any_guided ? w.d(L.g_state) : nullptr, any_guided ? w.d(L.g_misses) : nullptr,
+                          any_guided ? w.d(L.req_g_state) : nullptr, any_guided ? w.d(L.req_g_misses) : nullptr};
     serve.state_len = B->state_len; serve.chunks = serve_chunks(B->state_len);
     const RowReport rep = batch_report(B);
     RowSampler sampler = batch_sampler(B, nullptr, report ? &rep : nullptr);
@@ -1974,9 +1928,9 @@ static bool batch_serve(rwkv_mi_batch * B, const BatchCall & c, uint32_t * token
         return forward_rows(run, s.used, (int64_t) n, true, &s);
     };
     if (!batch_run_passes(B, bound, serve.t.work, sampler, step)) return false;
-    BATCH_HIP_OK(B, hipMemcpyAsync(h + L.down, d + L.down, L.bytes - L.down, hipMemcpyDeviceToHost, run->stream));
+    BATCH_HIP_OK(B, w.fetch(L.down, L.bytes, run->stream));
     if (!batch_passes_done(B, elapsed_ms)) return false;
-    const uint32_t * lens = hw(L.lens), * reasons = hw(L.reasons), * lane = hw(L.lane), * start = hw(L.start), * last = hw(L.last), * out = hw(L.out);
+    const uint32_t * lens = w.h(L.lens), * reasons = w.h(L.reasons), * lane = w.h(L.lane), * start = w.h(L.start), * last = w.h(L.last), * out = w.h(L.out);
     // (the queue's work fits the bound, and the loop ends on a work count of 0 or at the bound: every request has been served to its end)
     for (size_t q = 0; q < R; q++)
         RW_CTX_CHECK(ctx, RWKV_ERROR_GRAPH, false, lane[q] < n && lens[q] > 0 && lens[q] <= c.requests[q].stop.max_tokens &&
@@ -1989,8 +1943,8 @@ static bool batch_serve(rwkv_mi_batch * B, const BatchCall & c, uint32_t * token
         if (c.start_pass_out) c.start_pass_out[q] = start[q];
         if (tokens_out) memcpy(tokens_out + q * c.stride, out + q * c.stride, c.stride * 4);
         // (an unguided request's words are 0 and 0)
-        if (c.guide_state_out) c.guide_state_out[q] = any_guided ? hw(L.req_g_state)[q] : 0u;
-        if (c.guide_misses_out) c.guide_misses_out[q] = any_guided ? hw(L.req_g_misses)[q] : 0u;
+        if (c.guide_state_out) c.guide_state_out[q] = any_guided ? w.h(L.req_g_state)[q] : 0u;
+        if (c.guide_misses_out) c.guide_misses_out[q] = any_guided ? w.h(L.req_g_misses)[q] : 0u;
     }
     for (size_t r = 0; r < n; r++) {
         // the lane ran one pass after the other from pass 0 to the last one of its last request: that many times its buffers changed places
@@ -2010,16 +1964,6 @@ struct BeamCall {
     size_t G;
     const rwkv_mi_beam_params * p;
     size_t n_tokens;
-};
-
-// bytes of the beam words of `rows` rows and where they start: scores (double), finished, lens, the live count (with a pad word) -- the part a
-// call uploads -- then the candidates' ids and log-probs [rows][RWKV_MI_TOP_MAX] and the body's unused word per row
-struct BeamLayout {
-    size_t finished, lens, count, upload, ids, lp, chosen, bytes;
-    explicit BeamLayout(size_t rows) {
-        finished = rows * sizeof(double); lens = finished + rows * 4; count = lens + rows * 4; upload = count + 8;
-        ids = upload; lp = ids + rows * RWKV_MI_TOP_MAX * 4; chosen = lp + rows * RWKV_MI_TOP_MAX * 4; bytes = chosen + rows * 4;
-    }
 };
 
 // every argument of a beam call, nothing changed yet
@@ -2044,11 +1988,11 @@ static bool batch_check_beam(rwkv_mi_batch * B, const BeamCall & c) {
     return batch_check_unguided(B, c.slots, c.G * W, "beam search");
 }
 
-// the poll words of the batch and the beam words: on the first beam call
+// the poll words of the batch and the beam words: on the first beam call, for n_slots rows
 static bool batch_ensure_beam(rwkv_mi_batch * B) {
     const BeamLayout L(B->n_slots);
     hipError_t e = B->poll.ensure();
-    if (e == hipSuccess && !B->d_beam) e = grow(want(B->d_beam, L.bytes), want(B->h_beam, L.upload));   // (one decision: both or neither)
+    if (e == hipSuccess && !B->beam) e = grow(want(B->beam, L.bytes));
     RW_CTX_CHECK(B->ctx, RWKV_ERROR_ALLOC, false, e == hipSuccess, "cannot allocate the beam tables of %zu slots: %s", B->n_slots, hipGetErrorString(e));
     return true;
 }
@@ -2073,24 +2017,24 @@ static bool batch_beam(rwkv_mi_batch * B, const BeamCall & c, uint32_t * tokens_
     // table 0: every row of a group from the group's start buffer into its own slot's other buffer; table 1: .out back into the current one
     // (its .in is written by the first selection)
     const BeamLayout L(n);
-    double * h_score = (double *) B->h_beam.p;
-    uint32_t * h_fin = (uint32_t *) (B->h_beam.p + L.finished), * h_len = (uint32_t *) (B->h_beam.p + L.lens);
+    const Staged & w = B->beam;
+    double * h_score = w.h(L.score);
+    uint32_t * h_fin = w.h(L.finished), * h_len = w.h(L.lens);
     for (size_t r = 0; r < n; r++) {
         const size_t s0 = c.slots[r - r % W], s = c.slots[r];
         float * cur = B->slot_buf(s, B->parity[s]), * oth = B->slot_buf(s, B->parity[s] ^ 1);
-        B->h_rows.p[r] = RowState{B->slot_buf(s0, B->parity[s0]), oth};
-        B->h_rows.p[B->n_slots + r] = RowState{oth, cur};
+        B->rows.h()[r] = RowState{B->slot_buf(s0, B->parity[s0]), oth};
+        B->rows.h()[B->n_slots + r] = RowState{oth, cur};
         run->h_tokens.p[r] = c.first_tokens[r / W];
         h_score[r] = r % W ? -INFINITY : 0.0;
         h_fin[r] = 0u; h_len[r] = 0u;
     }
-    *(uint32_t *) (B->h_beam.p + L.count) = (uint32_t) n;
+    *w.h(L.count) = (uint32_t) n;
     if (!batch_upload_rows(B, n, 2)) return false;
     BATCH_HIP_OK(B, hipMemcpyAsync(run->d_tokens.p, run->h_tokens.p, n * sizeof(uint32_t), hipMemcpyHostToDevice, run->stream));
-    BATCH_HIP_OK(B, hipMemcpyAsync(B->d_beam.p, B->h_beam.p, L.upload, hipMemcpyHostToDevice, run->stream));
-    uint8_t * d = B->d_beam.p;
-    BeamTables t{(double *) d, (uint32_t *) (d + L.finished), (uint32_t *) (d + L.lens), (uint32_t *) (d + L.ids), (float *) (d + L.lp), (float *) (d + L.chosen),
-                 hist.p, hist.p + n_tokens * n, (float *) (hist.p + 2 * n_tokens * n), (uint32_t *) (d + L.count), (uint32_t) W, c.p->n_end, {}};
+    BATCH_HIP_OK(B, w.upload(0, L.upload, run->stream));
+    BeamTables t{w.d(L.score), w.d(L.finished), w.d(L.lens), w.d(L.ids), w.d(L.lp), w.d(L.chosen),
+                 hist.p, hist.p + n_tokens * n, (float *) (hist.p + 2 * n_tokens * n), w.d(L.count), (uint32_t) W, c.p->n_end, {}};
     for (uint32_t e = 0; e < c.p->n_end; e++) t.end_tokens[e] = c.p->end_tokens[e];
     RowSampler sampler;
     sampler.beam = &t;
@@ -2099,7 +2043,7 @@ static bool batch_beam(rwkv_mi_batch * B, const BeamCall & c, uint32_t * tokens_
     std::vector<uint32_t> h(3 * passes * n);
     for (size_t a = 0; a < 3; a++)
         BATCH_HIP_OK(B, hipMemcpyAsync(h.data() + a * passes * n, hist.p + a * n_tokens * n, passes * n * sizeof(uint32_t), hipMemcpyDeviceToHost, run->stream));
-    BATCH_HIP_OK(B, hipMemcpyAsync(B->h_beam.p, B->d_beam.p, L.count, hipMemcpyDeviceToHost, run->stream));
+    BATCH_HIP_OK(B, w.fetch(0, L.count.off, run->stream));
     if (!batch_passes_done(B, elapsed_ms)) return false;
     const uint32_t * h_tok = h.data(), * h_par = h.data() + passes * n;
     const float * h_lp = (const float *) (h.data() + 2 * passes * n);
@@ -2174,9 +2118,7 @@ RWKV_API struct rwkv_mi_batch * rwkv_mi_batch_create(struct rwkv_context * ctx, 
     const size_t sbytes = (size_t) B->state_len * sizeof(float);
     hipError_t e = B->states.alloc(2 * n_slots * (size_t) B->state_len);
     RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, nullptr, e == hipSuccess, "cannot allocate %zu slot states: %s", n_slots, hipGetErrorString(e));
-    e = B->d_rows.alloc(2 * n_slots);
-    RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, nullptr, e == hipSuccess, "HIP error: %s", hipGetErrorString(e));
-    e = B->h_rows.alloc(2 * n_slots);
+    e = B->rows.alloc(2 * n_slots);
     RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, nullptr, e == hipSuccess, "HIP error: %s", hipGetErrorString(e));
     if (!B->draw.ensure_counters(ctx, B->run->stream)) return nullptr;
     // every slot starts from the fresh state (both buffers: a slot's first pass reads buffer 0)

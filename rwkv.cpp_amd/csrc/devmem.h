@@ -62,4 +62,35 @@ template <typename... Req> hipError_t grow(Req &&... reqs) {
     return hipSuccess;
 }
 
+// A staged table: a device buffer and pinned staging of the same size and layout, as one owner -- the words of a call, which the host fills
+// or reads in the staging, at the Fields of the call's layout (call_layout.h). grow(want(...)) takes it like a MemBuf. The copies are
+// asynchronous on `st`: the caller keeps the staging untouched until the stream has passed them.
+template <typename T> struct Field;
+struct Staged {
+    DevBuf<uint8_t> dev;
+    PinBuf<uint8_t> pin;
+    explicit operator bool() const { return dev.p != nullptr; }
+    size_t bytes() const { return dev.count; }
+    void reset() { dev.reset(); pin.reset(); }
+    // both or neither; a failure leaves it empty
+    hipError_t alloc(size_t n) {
+        hipError_t e = dev.alloc(n);
+        if (e == hipSuccess) e = pin.alloc(n);
+        if (e != hipSuccess) reset();
+        return e;
+    }
+    template <typename T> T * h(const Field<T> & f) const { return (T *) (pin.p + f.off); }
+    template <typename T> T * d(const Field<T> & f) const { return (T *) (dev.p + f.off); }
+    // the bytes [from, to) of the staging to the device, or back
+    hipError_t upload(size_t from, size_t to, hipStream_t st) const { return hipMemcpyAsync(dev.p + from, pin.p + from, to - from, hipMemcpyHostToDevice, st); }
+    hipError_t fetch(size_t from, size_t to, hipStream_t st) const { return hipMemcpyAsync(pin.p + from, dev.p + from, to - from, hipMemcpyDeviceToHost, st); }
+};
+// a staged table of one field: `n` rows of T
+template <typename T> struct StagedRows : Staged {
+    hipError_t alloc(size_t n) { return Staged::alloc(n * sizeof(T)); }
+    T * h() const { return (T *) pin.p; }
+    T * d() const { return (T *) dev.p; }
+    hipError_t upload_rows(size_t from, size_t to, hipStream_t st) const { return Staged::upload(from * sizeof(T), to * sizeof(T), st); }   // rows [from, to)
+};
+
 }  // namespace rwkvmi

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <atomic>
 #include "common.h"
+#include "rows.h"
 
 namespace rwkvmi {
 
@@ -61,8 +62,7 @@ void launch_layernorm_gather(const float * x, const int32_t * idx, int64_t n, in
 //   rows (batched decode): row t is its own sequence; its state goes rows[t].in -> rows[t].out, a device table of the rows' slots;
 //   segments (ragged batch pass): tokens [t0, t1) of the pass are consecutive tokens of one sequence whose state goes segs[i].in ->
 //   segs[i].out; seg_of[t] names the segment of token t (the token-shift mixes are launched over tokens, the WKV forms over segments).
-struct RowState { const float * in; float * out; };
-struct SegState { const float * in; float * out; int32_t t0, t1; };
+// (RowState and SegState: rows.h)
 struct StateRef {
     const float * in = nullptr;
     float * out = nullptr;

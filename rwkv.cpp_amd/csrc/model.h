@@ -9,6 +9,7 @@
 #include "common.h"
 #include "devmem.h"
 #include "kernels.h"
+#include "rows.h"
 #include "persist_host.h"
 #include "rwkv_mi355x.h"
 
@@ -108,35 +109,8 @@ bool launch_wkv6_seq(const float * r, const float * k, const float * v, const fl
 constexpr int64_t k_mfma_min_tokens = 32;   // sequence calls of at least this many tokens per pass take the GEMM path
 
 // ---- the device sampler (sampling.hip): temperature / top-k / top-p / min-p draws on logits in HBM ----
-// Everything the draw of one row can read, in one struct: a context's draw builds one on the host, a batch call uploads one table of them.
-//   p, counter   the sampler's parameters and the draw counter of the row's sequence. p.u < 0: the draw comes from the counter-based generator
-//                (p.seed, *counter), and thread 0 advances the counter on the device
-//   presence, frequency, record, count, bias   the penalised draw (rwkv_mi_*_penalized) reads, instead of the logit,
-//                adj[j] = (logits[j] - (presence + (float) count[j] * frequency)) + bias[j]   (the penalty where count[j] > 0 only; bias == NULL:
-//                no bias) and, when record is set, counts the token: count[token] += 1. count: the sequence's occurrence table ([n] words),
-//                bias: its bias table ([n] floats)
-//   next, state, misses   the guide of the row's slot (rwkv_mi_batch_guide_*): its dense table next[n_states][n], GUIDE_DEAD where the transition
-//                is dead -- NULL: the row has no guide and draws as the unguided kernel does -- and the slot's state and miss words. A guided
-//                row in state s reads -inf for token j where next[s][j] is dead, the value of its draw elsewhere; thread 0 then moves the state
-//                to next[s][token], or counts a miss when that is dead
-//   top_k, min_p   the truncation setting of the row's sequence (rwkv_mi_*truncation_set; {0, 0}: none). top_k (0 or >= n: off): of the values
-//                the draw would read -- logits, adjusted logits, a guide's mask applied -- the first top_k in the order (value descending, index
-//                ascending; a NaN never ranks) are read as they are, every other one as -inf. min_p (0: off): of the probabilities the body
-//                computes from these, those below (float) (min_p * the largest) are cut, beside the top-p cut-off. A row with temperature 0
-//                is an argmax, which survives both: it ignores the setting
-//   decay, repetition   the repetition setting of the row's sequence (rwkv_mi_*repetition_set; {1, 1}: none), read by the penalised draw.
-//                repetition: where the token has occurred, the logit is divided by it when positive and multiplied by it otherwise, in front
-//                of the penalty. decay != 1: the sequence is DECAYING -- the words of `count` hold floats, and a draw that records multiplies
-//                every one of them by decay before it adds 1.0f to the pick's. The arithmetic is spelled out in include/rwkv_mi355x.h
-constexpr uint16_t GUIDE_DEAD = 0xFFFF;
-struct DrawRow {
-    rwkv_mi_sample_params p; unsigned long long * counter;
-    float presence; float frequency; uint32_t record;
-    uint32_t * count; const float * bias;
-    const uint16_t * next; uint32_t * state; uint32_t * misses;
-    uint32_t top_k; float min_p;
-    float decay; float repetition;
-};
+// (rows.h, DrawRow: everything the draw of one row can read)
+constexpr uint16_t GUIDE_DEAD = 0xFFFF;   // a dead transition of a guide's table
 // the two settings as a sequence keeps them (DrawState's host words)
 struct CutRow { uint32_t top_k; float min_p; };
 struct RepRow { float decay; float repetition; };
@@ -179,21 +153,15 @@ void launch_guide_expand(uint16_t * next, uint32_t n_states, int n_vocab, const 
 const char * guide_edges_fault(size_t n_vocab, uint32_t n_states, const uint32_t * edge_begin, const uint32_t * edge_tokens, const uint32_t * edge_next);
 hipError_t guide_table_build(DevBuf<uint16_t> & table, size_t n_vocab, uint32_t n_states, const uint32_t * edge_begin, const uint32_t * edge_tokens,
                              const uint32_t * edge_next, hipStream_t st, bool * alloc_failed);
-// A row's stop parameters and where its sequences start in the call's flat tables: its lengths at seq_lens[seq0 ..], its tokens at seq_tokens[tok0 ..].
-struct StopRow { uint32_t max_tokens, n_seqs, seq0, tok0; };
-// The device words of a call: per row its live word (1 until it retires), its length and its reason (the index of the matching sequence, or
+// The device words of a call (rows.h, StopRow: a row's parameters): per row its live word (1 until it retires), its length and its reason (the index of the matching sequence, or
 // RWKV_MI_NO_TOKEN for the budget) once it has; live_count: the rows still live.
 struct StopTables { const StopRow * rows; const uint32_t * seq_lens, * seq_tokens; uint32_t * live, * lens, * reasons, * live_count; };
 // After the draw of pass `step` (hist: [step][rows], this call's tokens): retires the live rows whose tokens end with one of their sequences or
 // whose budget is step + 1. A retired row gets {in = what pass `step` wrote, out = its other buffer} in both row tables (used: the table of
 // pass `step`, other: the one of pass step + 1).
 void launch_stop_rows(const StopTables & t, int64_t rows, const uint32_t * hist, uint32_t step, RowState * used, RowState * other, hipStream_t st);
-// rwkv_mi_batch_serve (sampling.hip, k_serve_rows / k_serve_reset): a queue of requests behind the n lanes of a call. A request as the device
-// reads it: its draw row -- the request's settings, with (rwkv_mi_batch_serve_ex) its guide's table and its bias slot's table, both only read;
-// the counter, the occurrence row and the guide words are the LANE's, patched in at admission -- its stop row, its prompt (prompt_len tokens at
-// prompts[prompt0 ..]) and the buffer its start state is copied from.
-struct ServeReq { DrawRow row; StopRow stop; uint32_t prompt_len, prompt0; const float * start; };
-// The device words of a call. Per request: its emitted tokens out[q][stride], its length (it grows with every token), its reason, its lane and
+// rwkv_mi_batch_serve (sampling.hip, k_serve_rows / k_serve_reset): a queue of requests behind the n lanes of a call (rows.h, ServeReq: a
+// request as the device reads it). The device words of a call. Per request: its emitted tokens out[q][stride], its length (it grows with every token), its reason, its lane and
 // the pass that fed its first prompt token. Per lane: the request it serves (SERVE_FREE: it waits for one -- only between the two halves of
 // k_serve_rows, and before the first pass; RWKV_MI_NO_TOKEN: dead), the prompt tokens it has been fed, its DRAW WORD (1: the logits of the
 // coming pass are drawn from -- the `live` argument of the draw kernels), its admit word (1: k_serve_reset has a state to copy), the last

@@ -6,16 +6,25 @@ check_rows) and tests/test_gpu_logprobs.py (check_against_f64). Nothing is compa
 Files: the RWKV-4 FP16 and the RWKV-6 Q5_1 tiny models of tests/golden. Sizes: a batch's token words start at n_slots (4) and its segment
 tables at nothing, so passes of 3, 70 (one segment of 33: a sequence kernel's), 3 and 150 tokens grow both, reuse them and grow them again;
 the report buffers grow with steps * rows * top_n (2 steps, 40 steps, then top_n 2 -> 5), the scoring words past their first 1024 rows never
-in a test this small -- what grows there is the token words under them (5, then 100 positions)."""
+in a test this small -- what grows there is the token words under them (5, then 100 positions). The staged tables of the queue, the stop
+words, the beam words and the draft words (csrc/call_layout.h) on one batch, one call after the other: a queue of 4 requests with 4 tokens
+a request, one of 12 with 16 (the table grows), a rejected one, the first again (the table is reused), one with a guided request (the guide
+fields appear), then decode_until, decode_beam, eval_draft and a ragged pass of 70 tokens. The requests are held against the oracle's
+greedy walk under tests/test_cpu_batch_until.py's stop rule and tests/guide_ref.py's masks, the schedule against
+tests/test_cpu_batch_serve.py's model of it, the beam against tests/test_gpu_beam.py's host-driven search run on the oracle."""
 import ctypes
 
 import numpy as np
 import pytest
 
+import guide_ref as G
 import oracle_lib as O
 import reference_constants as R
 from gpu_lib import model, pkg
 from logprobs_ref import f64_logprobs, top_ids
+from test_cpu_batch_serve import serve_rule
+from test_cpu_batch_until import NO_TOKEN, stop_rule
+from test_gpu_beam import bits32, bits64, host_search
 from test_gpu_logprobs import check_against_f64
 from test_gpu_score import check_rows
 
@@ -244,4 +253,120 @@ def test_a_rejected_call_leaves_the_buffers_as_they_were(golden_dir, version, fm
             with pytest.raises(ValueError):
                 b.set_logprobs(pkg.TOP_MAX + 1)
             assert b.last_error & ARGS
+    b.free(); m.free()
+
+
+def _oracle_request(om, state, prompt, max_tokens, stop=(), guide=None, g_state=0):
+    """(tokens, stopped_by, state after, guide state, misses) of a request alone: the prompt fed from `state`, then every step's argmax -- under
+    `guide`, of the tokens it allows (guide_ref) -- fed in turn, ended by stop_rule. The last token is not fed: the state is that of the plain
+    loop of the request's length. A row of decode_until is the request whose prompt is the row's first token, from the slot's state."""
+    for t in prompt:
+        lg, state = om.eval(t, state)
+    toks, states, words = [], [], [(g_state, 0)]
+    for _ in range(max_tokens):
+        tok = int(np.argmax(lg if guide is None else np.where(guide.mask(words[-1][0]), lg, -np.inf)))
+        if guide is not None:
+            nxt, miss = guide.step(words[-1][0], tok)
+            words.append((nxt, words[-1][1] + miss))
+        toks.append(tok); states.append(state)
+        lg, state = om.eval(tok, state)
+    n, why = stop_rule(toks, max_tokens, stop)
+    return np.asarray(toks[:n], dtype=np.uint32), why, states[n - 1], words[n if guide is not None else 0]
+
+
+def _serve(b, om, ost, lanes, reqs, what, family=pkg.SERVE_GREEDY, guides=None):
+    """one serve call: every request against the request alone from the fresh state, the lanes and start passes against serve_rule, the guide
+    words against the guide's walk, and every slot's state -- a lane holds the end state of its last request, no other slot changes"""
+    got = b.serve(lanes, reqs, family=family)
+    want = [_oracle_request(om, om.init_state(), rq["prompt"], rq["max_tokens"], rq.get("stop") or [],
+                            None if rq.get("guide") is None else guides[rq["guide"]], rq.get("guide_state", 0)) for rq in reqs]
+    lane, start, _ = serve_rule([len(rq["prompt"]) for rq in reqs], [len(w[0]) for w in want], len(lanes))
+    for q, w in enumerate(want):
+        assert np.array_equal(got["tokens"][q], w[0]), (what, "tokens of request", q)
+    assert np.array_equal(got["stopped_by"], [w[1] for w in want]), (what, "reasons")
+    assert np.array_equal(got["lane"], lane) and np.array_equal(got["start_pass"], start), (what, "lanes and start passes")
+    assert np.array_equal(got["guide_state"], [w[3][0] for w in want]) and np.array_equal(got["guide_misses"], [w[3][1] for w in want]), (what, "guide words")
+    last = [max(q for q in range(len(reqs)) if lane[q] == r) for r in range(len(lanes))]
+    assert np.array_equal(got["last_request"], last), (what, "last requests")
+    for r, s in enumerate(lanes):
+        ost[s] = want[last[r]][2]
+    _same_states(b, ost, what)
+
+
+class _OracleSlots:
+    """the slots of a batch on the CPU oracle: what host_search (tests/test_gpu_beam.py) drives in place of a second batch"""
+
+    def __init__(self, om, ost):
+        self.om, self.ost = om, ost
+
+    def state_store(self, s):
+        return self.ost[s].copy()
+
+    def state_load(self, s, st):
+        self.ost[s] = np.array(st, dtype=np.float32)
+
+    def eval(self, slots, tokens):
+        out = []
+        for s, t in zip(slots, tokens):
+            lg, self.ost[s] = self.om.eval(t, self.ost[s])
+            out.append(lg)
+        return np.stack(out)
+
+
+@pytest.mark.parametrize("version,fmt", FILES)
+def test_staged_tables_grow_are_reused_and_outlive_a_rejected_call(golden_dir, version, fmt):
+    m, om = _open(golden_dir, version, fmt)
+    b = pkg.RWKVBatch(m, N_SLOTS)
+    ost = _fresh(om)
+    V = om.n_vocab
+    small = [{"prompt": _tokens(1, q, 1 + q % 2, V), "max_tokens": 2 + q % 3} for q in range(4)]            # at most 4 tokens: stride 4
+    big = [{"prompt": _tokens(2, q, 1 + q % 3, V), "max_tokens": 1 + 5 * q % 16} for q in range(12)]         # request 3 has 16: stride 16
+    stream = _oracle_request(om, om.init_state(), big[4]["prompt"], big[4]["max_tokens"])[0]
+    big[4]["stop"] = [[int(stream[1]), int(stream[2])]]                                                     # (its own second and third token)
+    # 1, 2: the table of the first call, then a larger one
+    _serve(b, om, ost, [2, 0], small, (version, fmt, "4 requests"))
+    _serve(b, om, ost, [1, 3, 0], big, (version, fmt, "12 requests"))
+    # 3: a lane named twice is rejected and changes nothing; 4: the first queue again, in the table the second one left
+    with pytest.raises(ValueError):
+        b.serve([1, 1], small)
+    assert b.last_error & ARGS
+    _same_states(b, ost, (version, fmt, "after the rejected queue"))
+    _serve(b, om, ost, [2, 0], small, (version, fmt, "4 requests again"))
+    # 5: a guided request among plain ones (guided greedy is temperature 0 of the sampled family): the guide fields of the table appear
+    guide = G.random_guide(V, 3, seed=5)
+    gid = b.create_guide(guide.edges)
+    guided = [dict(rq, temperature=0.0) for rq in small]
+    guided[1].update(guide=gid, guide_state=2)
+    _serve(b, om, ost, [2, 0], guided, (version, fmt, "a guided request"), family=pkg.SERVE_SAMPLE, guides={gid: guide})
+    # 6: decode_until: slot 1 ends at its own third token, slot 3 at its budget
+    first, budgets = [34, 105], [6, 5]
+    third = int(_oracle_request(om, ost[1], [first[0]], budgets[0])[0][2])
+    stops = [[[third]], []]
+    out, why, _ = b.decode_until([1, 3], first, budgets, stop=stops)
+    for r, s in enumerate([1, 3]):
+        toks, reason, ost[s], _ = _oracle_request(om, ost[s], [first[r]], budgets[r], stops[r])
+        assert np.array_equal(out[r], toks) and int(why[r]) == reason, (version, fmt, "until, slot", s)
+    assert int(why[0]) == 0 and int(why[1]) == NO_TOKEN and len(out[0]) <= 3 and len(out[1]) == 5, (version, fmt, "until", why)
+    _same_states(b, ost, (version, fmt, "until"))
+    # 7: decode_beam, one group of width 2 from slot 2's state, against the host-driven search on the oracle (which leaves ost where the call
+    # leaves the slots: without end tokens every hypothesis is unfinished)
+    tokens, lens, scores, lps, _ = b.decode_beam([[2, 0]], [110], 2, 4)
+    wt, wl, ws, wlp, wfin = host_search(_OracleSlots(om, ost), [[2, 0]], [110], 2, 4, [])
+    assert np.array_equal(tokens, wt) and np.array_equal(lens, wl), (version, fmt, "beam", tokens.tolist(), wt.tolist())
+    assert np.array_equal(bits32(lps), bits32(wlp)) and np.array_equal(bits64(scores), bits64(ws)), (version, fmt, "beam scores")
+    assert not wfin.any()
+    _same_states(b, ost, (version, fmt, "beam"))
+    # 8: eval_draft, a draft of 2 per row: slot 1's second draft token is wrong (one stands), slot 3's both stand
+    rows = []
+    for s, x0, wrong in ((1, 34, True), (3, 105, False)):
+        true = _oracle_greedy(om, ost[s], x0, 3)[0]
+        rows.append((s, x0, wrong, true))
+    emitted, kept = b.eval_draft([1, 3], [[x0, int(true[0]), (int(true[1]) + (1 if wrong else 0)) % V] for _, x0, wrong, true in rows])
+    for r, (s, x0, wrong, true) in enumerate(rows):
+        n = 2 if wrong else 3
+        assert int(kept[r]) == n and np.array_equal(emitted[r], true[:n]), (version, fmt, "draft, slot", s)
+        ost[s] = _oracle_greedy(om, ost[s], x0, n)[2]
+    _same_states(b, ost, (version, fmt, "draft"))
+    # 9: a ragged pass of 70 tokens after all of them
+    _ragged_pass(b, om, ost, 9, (33, 30, 5, 2), (version, fmt, "ragged pass of 70"))
     b.free(); m.free()

@@ -14,6 +14,7 @@ from rwkv_cpp_amd import synth  # noqa: E402,F401
 
 _lib = None
 _hooks = None
+_recur_hooks = None
 
 
 def _torch_first():
@@ -53,6 +54,35 @@ def hooks_library():
         L.rwkv_mi_test_unary.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]
         L.rwkv_mi_test_unary.restype = ctypes.c_bool
     return _hooks
+
+
+class RecurStates(ctypes.Structure):
+    """struct rwkv_mi_test_recur_states (include/rwkv_testhooks_recur.h)"""
+    _fields_ = [("state_in", ctypes.c_void_p), ("state_out", ctypes.c_void_p), ("n_slots", ctypes.c_int64), ("form", ctypes.c_int), ("n", ctypes.c_int64),
+                ("slots", ctypes.c_void_p), ("t0", ctypes.c_void_p), ("t1", ctypes.c_void_p)]
+
+
+RECUR_HOOKS_LIB_PATH = os.path.join(os.path.dirname(pkg.LIB_PATH), "librwkv_testhooks_recur.so")
+
+
+def recur_hooks_library():
+    """lib/librwkv_testhooks_recur.so: the same objects + the entry points of include/rwkv_testhooks_recur.h (the launchers of the RWKV-5 / 6 / 7
+    recurrences, the group norm and the RWKV-7 key preparation on caller-supplied arrays). Tests only."""
+    global _recur_hooks
+    if _recur_hooks is None:
+        _torch_first()
+        pkg.build_library()
+        _recur_hooks = pkg.RWKVSharedLibrary(RECUR_HOOKS_LIB_PATH)
+        L, P, I64 = _recur_hooks.library, ctypes.c_void_p, ctypes.c_int64
+        for name, args in (("rwkv_mi_test_wkv6", [P, P, P, P, ctypes.c_int, P, ctypes.c_int, ctypes.POINTER(RecurStates), P, I64, I64, I64]),
+                           ("rwkv_mi_test_wkv7", [P] * 6 + [ctypes.POINTER(RecurStates), P, I64, I64, I64]),
+                           ("rwkv_mi_test_wkv6_seq", [P, P, P, P, ctypes.c_int, P, ctypes.c_int, P, P, P, I64, I64, I64]),
+                           ("rwkv_mi_test_wkv7_seq", [P] * 9 + [I64, I64, I64]),
+                           ("rwkv_mi_test_groupnorm", [P, P, P, ctypes.c_float] + [P] * 5 + [I64, I64, I64]),
+                           ("rwkv_mi_test_v7_kprep", [P] * 7 + [I64, I64, I64])):
+            getattr(L, name).argtypes = args
+            getattr(L, name).restype = ctypes.c_bool
+    return _recur_hooks
 
 
 def model(path, hooks=False, **kw):

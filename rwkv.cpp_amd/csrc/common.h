@@ -32,6 +32,8 @@ void ctx_fail(struct ::rwkv_context * ctx, int flags, const char * file, int lin
 // Per-context (eval) check.
 #define RW_CTX_CHECK(CTX, FLAGS, RET, COND, ...) \
     do { if (!(COND)) { ::rwkvmi::ctx_fail((CTX), (FLAGS), __FILE__, __LINE__, #COND, __VA_ARGS__); return RET; } } while (0)
+#define HIP_CTX_OK(CTX, CALL) \
+    do { hipError_t e_ = (CALL); RW_CTX_CHECK((CTX), RWKV_ERROR_GRAPH, false, e_ == hipSuccess, "HIP error: %s", hipGetErrorString(e_)); } while (0)
 
 namespace rwkvmi {
 

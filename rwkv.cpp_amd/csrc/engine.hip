@@ -11,9 +11,6 @@
 
 namespace rwkvmi {
 
-#define HIP_CTX_OK(CTX, CALL) \
-    do { hipError_t e_ = (CALL); RW_CTX_CHECK((CTX), RWKV_ERROR_GRAPH, false, e_ == hipSuccess, "HIP error: %s", hipGetErrorString(e_)); } while (0)
-
 void ctx_fail(struct ::rwkv_context * ctx, int flags, const char * file, int line, const char * expr, const char * fmt, ...) {
     ctx->last_error |= flags;
     if (!ctx->print_errors) return;
@@ -811,7 +808,7 @@ bool forward(rwkv_context * ctx, int64_t T, bool want_logits, const ScorePass * 
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Batched decode (api.cpp, rwkv_mi_batch_*). The batch runs on a context of its own (batch_context_create): the model, a stream, scratch,
+// Batched decode (batch.cpp, rwkv_mi_batch_*). The batch runs on a context of its own (batch_context_create): the model, a stream, scratch,
 // token words and a [rows][n_vocab] logits buffer -- no state, no persistent kernel, no fused layers, no graphs. Growing its scratch
 // therefore never drops the captured graphs of the caller's context.
 // Ordering: the batch takes part in the per-device chain of persistent launches (engine.hip top). It counts as one more member, so a
@@ -886,7 +883,7 @@ void launch_row_sampler(rwkv_context * ctx, const RowSampler & s, int64_t rows) 
 // sample: the T sampler workgroups (sampling.hip, k_draw_rows) follow the head INSIDE the chain bracket. Each of them is 1024 threads,
 // a CU's worth of waves, so up to T CUs are taken while they run; the completion event mega_chain_end records is what the device's next
 // persistent launch waits on, and with the sampler in front of it that launch still finds every CU free ("a batch pass never runs beside
-// a persistent kernel" holds for the sampler too). The greedy loop's argmax stays where it was, after the bracket: batch_loop (api.cpp) calls
+// a persistent kernel" holds for the sampler too). The greedy loop's argmax stays where it was, after the bracket: batch_loop (batch.cpp) calls
 // launch_row_sampler itself behind the pass for that family.
 bool forward_rows(rwkv_context * ctx, const RowState * d_rows, int64_t T, bool want_logits, const RowSampler * sample) {
     if (!ensure_scratch(ctx, T)) return false;

@@ -148,7 +148,7 @@ void launch_sample_seek_rows(const DrawRow * table, int64_t rows, unsigned long 
 // next[n_states][n_vocab] from the edges in CSR form on the device (checked by the caller: tokens < n_vocab and distinct per state, next < n_states)
 void launch_guide_expand(uint16_t * next, uint32_t n_states, int n_vocab, const uint32_t * edge_begin, const uint32_t * edge_tokens, const uint32_t * edge_next,
                          hipStream_t st);
-// api.cpp: the rules of rwkv_mi_batch_guide_create on a guide's edges (nullptr: they hold; else which one does not), and the table built on
+// draw_state.cpp: the rules of rwkv_mi_batch_guide_create on a guide's edges (nullptr: they hold; else which one does not), and the table built on
 // the device from edges that passed: allocated, expanded, the stream drained. A failure leaves `table` as it was
 const char * guide_edges_fault(size_t n_vocab, uint32_t n_states, const uint32_t * edge_begin, const uint32_t * edge_tokens, const uint32_t * edge_next);
 hipError_t guide_table_build(DevBuf<uint16_t> & table, size_t n_vocab, uint32_t n_states, const uint32_t * edge_begin, const uint32_t * edge_tokens,
@@ -213,7 +213,7 @@ void launch_count_add(uint32_t * count, const uint32_t * tokens, int64_t n, int 
 void launch_count_add_decay(float * occ, const uint32_t * tokens, int64_t n, int n_vocab, float decay, hipStream_t st);
 void launch_bias_scatter(float * bias, const uint32_t * ids, const float * values, int64_t n, int n_vocab, hipStream_t st);     // bias[ids[i]] = values[i]
 
-// The draw state of `slots` sequences of a model, owned in one place (api.cpp): per slot the draw counter, the sampler's scratch vector, the
+// The draw state of `slots` sequences of a model, owned in one place (draw_state.cpp): per slot the draw counter, the sampler's scratch vector, the
 // occurrence table and the bias table of the penalised draw, and whether a bias is set. A context holds one of 1 slot, a batch one of n_slots.
 // Nothing is allocated by init(): the counters come with ensure_counters (a batch calls it when it is created, so its counters exist and are
 // zero from then on; a context gets its counter with its first draw or seek), the scratch with ensure_sampler, the two tables -- zeroed; a
@@ -284,6 +284,10 @@ struct DrawState {
     bool rep_set(rwkv_context * ctx, size_t slot, float decay, float repetition, hipStream_t st);
     bool counts_store_f32(rwkv_context * ctx, size_t slot, float * out, hipStream_t st);   // either kind of row, as floats
 };
+// the arguments of counts_add / logit_bias_set / a penalty (checked before anything changes; errors are reported on ctx)
+bool check_count_tokens(rwkv_context * ctx, const uint32_t * tokens, size_t n);
+bool check_bias(rwkv_context * ctx, const uint32_t * ids, const float * values, size_t n);
+bool check_penalty(rwkv_context * ctx, float presence, float frequency, size_t index);
 
 // Loads [layer_begin, layer_end) of the file (layer_end == UINT32_MAX: all layers) onto the current HIP device.
 // Returns nullptr with the thread-local error set, like the reference loader (rwkv_model_loading.inc:288-419).
@@ -303,6 +307,9 @@ enum class FusedLayer { none, v4, v6, v7 };   // which fused per-layer decode pa
 // The report of a context's or a batch's emitting calls (rwkv_mi_*set_logprobs): whether it is on and with how many alternatives; the device
 // buffers, laid out like the loops' history -- chosen[steps][rows], ids / vals [steps][rows][top_n] -- allocated by the first reporting call
 // and grown to the largest since; and what the last reporting call left in them (valid: there is one). lens[r]: the steps row r wrote.
+// `valid` implies `enabled`: set() alone changes `enabled` and clears `valid`; done() alone sets `valid`, for an enabled report. The
+// operations (logprob_report.cpp) take the context their errors go to, and the stream where they use one.
+struct RowReport { float * chosen; uint32_t * ids; float * vals; uint32_t top_n; };   // the buffers as a pass writes them (RowSampler, below)
 struct LogprobReport {
     bool enabled = false;
     uint32_t top_n = 0;
@@ -313,6 +320,16 @@ struct LogprobReport {
     size_t rows = 0, steps = 0;
     uint32_t last_top_n = 0;
     std::vector<uint32_t> lens;
+
+    RowReport buffers() const { return RowReport{d_chosen.p, d_ids.p, d_vals.p, top_n}; }   // (begin has sized them for the call)
+    bool set(rwkv_context * ctx, bool enabled, uint32_t top_n);
+    bool ensure(rwkv_context * ctx, size_t entries);
+    // what every emitting call of `entries` = steps * rows records starts with (nothing when the report is off): the stream drained, the
+    // buffers sized, the previous report ended
+    bool begin(rwkv_context * ctx, hipStream_t st, size_t entries);
+    void done(size_t rows, size_t steps, const uint32_t * lens);
+    bool shape(rwkv_context * ctx, size_t * rows, size_t * steps, uint32_t * top_n) const;
+    bool store(rwkv_context * ctx, hipStream_t st, size_t stride, float * chosen_out, uint32_t * top_ids_out, float * top_logprobs_out) const;
 };
 }  // namespace rwkvmi
 
@@ -387,7 +404,12 @@ struct rwkv_context {
     Prof prof;
 };
 
+#define RW_NO_PIPELINE(CTX, RET) RW_CTX_CHECK((CTX), RWKV_ERROR_ARGS | RWKV_ERROR_UNSUPPORTED, RET, (CTX)->stages.empty(), \
+    "this rwkv_mi_* extension works on a single-device context; with RWKV_MI_DEVICES use the rwkv.h entry points")
+
 namespace rwkvmi {
+
+inline bool on_device(rwkv_context * ctx) { HIP_CTX_OK(ctx, hipSetDevice(ctx->model->device)); return true; }
 
 rwkv_context * create_context(Model * m, uint32_t n_threads);
 void destroy_context(rwkv_context * ctx);
@@ -418,6 +440,8 @@ struct ScorePass {
 // the chunk buffer (first call: score_R = clamp(64 MiB / (4 n_vocab), 32, 1024) rows, or RWKV_MI_SCORE_ROWS >= 1) and per-row words for
 // `rows` rows; false with RWKV_ERROR_ALLOC, nothing changed, when they cannot be allocated
 bool ensure_score(rwkv_context * ctx, int64_t rows);
+// api.cpp: the targets of a scoring call (checked with the other arguments, before anything changes)
+bool check_targets(rwkv_context * ctx, const uint32_t * targets, size_t n, const float * logprobs_out);
 
 // batched decode (engine.hip): the batch's own context (model, stream, scratch, tokens, [max_rows][n_vocab] logits; a member of the per-device
 // chain of persistent launches) and one pass of T rows, row t from state d_rows[t].in into d_rows[t].out
@@ -435,7 +459,6 @@ void batch_context_destroy(rwkv_context * c);
 //   serve   the pass is a step of rwkv_mi_batch_serve: the choice runs behind the lanes' draw words and writes no history; launch_serve_rows and
 //           launch_serve_reset (`chunks` workgroups per lane over state_len floats) follow it
 // Order within a step: the choice, then the report of what it wrote, then the stop test.
-struct RowReport { float * chosen; uint32_t * ids; float * vals; uint32_t top_n; };
 struct RowServe { ServeTables t; int64_t state_len; unsigned chunks; };
 struct RowSampler {
     DrawForm form;
@@ -513,7 +536,7 @@ int ring_rowsum_lanes(int n);
 PersistentDecoder * p47_create(const Model & m);       // RWKV-4 / RWKV-7 (persist_v47.hip)
 const char * persist_unavailable_reason(const Model & m);   // nullptr: a persistent kernel exists for this model on this device
 // ---- layer pipeline in one process (pipeline.cpp) ----
-bool upload_tokens_for(rwkv_context * ctx, const uint32_t * tokens, size_t n);   // api.cpp: pinned staging + async copy into ctx->d_tokens
+bool upload_tokens(rwkv_context * ctx, const uint32_t * tokens, size_t n);   // api.cpp: pinned staging + async copy into ctx->d_tokens
 rwkv_context * pipeline_create(const char * path, uint32_t n_threads, const char * devices);
 void pipeline_destroy(rwkv_context * front);
 bool pipeline_eval(rwkv_context * front, const uint32_t * tokens, size_t n, size_t chunk, const float * state_in, float * state_out, float * logits_out);

@@ -180,7 +180,7 @@ bool pipeline_eval(rwkv_context * front, const uint32_t * tokens, size_t n, size
             const size_t D = (size_t) m.n_embed();
             if (hipSetDevice(m.device) != hipSuccess) return fail(c);
             if (s == 0) {
-                if (!upload_tokens_for(c, tokens + done, T)) return fail(c);
+                if (!upload_tokens(c, tokens + done, T)) return fail(c);
             } else {
                 rwkv_context * p = st[s - 1];
                 // the previous stage's residual stream (its scratch x, [T][D]) -> this stage's, device to device, on the PRODUCER's stream

@@ -444,7 +444,7 @@ struct XDirectScope {
 bool seed_tokens(StagePart & p, rwkv_context * err, const uint32_t * first_tokens) {
     for (size_t j = 0; j < p.h.size(); j++) {
         rwkv_context * c = p.h[j];
-        if (hipSetDevice(c->model->device) != hipSuccess || !upload_tokens_for(c, first_tokens + j, 1)) { err->last_error |= c->last_error ? c->last_error : (int) RWKV_ERROR_GRAPH; return false; }
+        if (hipSetDevice(c->model->device) != hipSuccess || !upload_tokens(c, first_tokens + j, 1)) { err->last_error |= c->last_error ? c->last_error : (int) RWKV_ERROR_GRAPH; return false; }
     }
     return true;
 }

@@ -14,6 +14,6 @@ for s in $SRCS; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 "$@" -O3 -std=c++17 -ffp-contract=off -fPIC -DRWKV_SHARED -DRWKV_BUILD -fvisibility=hidden -I../include -Icsrc -Wall -Wno-unused-function -Wno-unused-variable -c csrc/$s.hip -o build_$D/$s.o &
 done
 wait
-OBJS=$(for o in pipeline runner format quantize api kernels model engine fused_v6 mega_v6 ring_v6 ring_v6_instr persist_v47 persist_host prefill prefill_fast fused_v7 sampling score; do case " $SRCS " in *" $o "*) echo build_$D/$o.o;; *) echo build/$o.o;; esac; done)
+OBJS=$(for o in $(sed -n 's/^SRCS = //p' Makefile); do case " $SRCS " in *" $o "*) echo build_$D/$o.o;; *) echo build/$o.o;; esac; done)
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -Wl,--version-script=csrc/rwkv.map -o $D/librwkv.so $OBJS -ldl
 ls -la $D/librwkv.so

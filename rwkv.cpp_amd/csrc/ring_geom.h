@@ -79,6 +79,34 @@ RG_HD int rg_key_sets(const RingShape & s, int b) {
 }
 RG_HD int rg_key_comm(const RingShape & s, int b) { const int n = rg_key_sets(s, b); return (n >= RG_NC && n % RG_NC <= 2) ? n % RG_NC : 0; }
 
+// ---- which shapes the ring kernel takes ----
+// An instantiation of k6_ring (ring_v6.hip, RING_VARIANTS: one per key and format) is keyed by
+//     ept  D / 512               nbd  decay rank / 32
+//     uf   rg_steps(F)           ksl  ceil(3 F / 32 / 448): gather slots per lane for the 3 F / 32 units of the quantised F-vector
+// and the stream layout above adds its own conditions: at most two 32-row key groups per workgroup, all of them whole (F a multiple of
+// 32 gpb), the decay rows and the 5 D / 64 time-mix units inside the grid, a mix rank of 32 or 64. rg_variant_key is that arithmetic and
+// nothing else -- device, head count and format are ring_variant's -- so that the host-side checkers (tests/cpp/ring_*_check.cpp) sweep
+// exactly the shapes the device admits.
+struct RingKey { int ept, nbd, uf, ksl; };
+constexpr RingKey RG_KEYS[] = {
+    {8, 4, 7, 3},   // D 4096, F 12352 .. 14336 in steps of 64 (386 .. 448 blocks: 7 steps, up to 1344 units), decay rank 128: RWKV-6 7B
+    {5, 2, 5, 2},   // D 2560, F 8256 .. 9536 in steps of 64 (258 .. 298 blocks: 5 steps, up to 894 units), decay rank 64: RWKV-6 3B
+    {4, 2, 4, 2},   // D 2048, F 6176 .. 8192 in steps of 32 (193 .. 256 blocks: 4 steps, up to 768 units), decay rank 64: RWKV-6 1.6B
+};
+constexpr int RG_NKEYS = (int) (sizeof(RG_KEYS) / sizeof(RG_KEYS[0]));
+// the entry of RG_KEYS that takes a stage of n_embed D, ffn size F, decay rank DR and mix rank R (-1: none does)
+inline int rg_variant_key(int64_t D, int64_t F, int64_t DR, int64_t R) {
+    const int64_t NB = RG_NBLK;
+    const int64_t gpb = (F / 32 + NB - 1) / NB;
+    if (F <= 0 || F % 32 != 0 || F % (gpb * 32) != 0 || DR > NB || DR % 32 != 0 || 5 * (D / 64) > NB + NB / 2 || !(R == 32 || R == 64) || gpb * 32 > 64) return -1;
+    const int64_t nbF = F / 32;
+    for (int k = 0; k < RG_NKEYS; k++) {
+        const RingKey & rk = RG_KEYS[k];
+        if (D == rk.ept * 512 && DR == rk.nbd * 32 && (nbF + 63) / 64 == rk.uf && (3 * nbF + 7 * 64 - 1) / (7 * 64) == rk.ksl) return k;
+    }
+    return -1;
+}
+
 // rows of a record: phase-specific matrix (RG_C: the matrix index 0..3 = r, k, v, g), first row, rows per record, row length
 struct RingRec { int mat, row0, R, K; };
 

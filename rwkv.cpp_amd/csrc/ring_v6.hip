@@ -1966,12 +1966,12 @@ __global__ __launch_bounds__(512) void k6_ring_ins(R6P) { k6_ring_body<FMT, EPT,
 // -- two translation units, so that the two halves compile side by side. Same order in both tables: an index into one is an index into the other.
 typedef void (*RingKernel)(R6P);
 struct RingVariant { int fmt, ept, nbd, uf, ksl; RingKernel fn; };
-#define RING_VARIANTS(KERN, FMT) \
-    {FMT, 8, 4, 7, 3, KERN<FMT, 8, 4, 7, 3>},   /* D 4096, F 14336 (448 blocks: 7 steps, 1344 units), decay rank 128: RWKV-6 7B */ \
-    {FMT, 5, 2, 5, 2, KERN<FMT, 5, 2, 5, 2>},   /* D 2560, F 8960 (280 blocks: 5 steps, 840 units), decay rank 64: RWKV-6 3B */ \
-    {FMT, 4, 2, 4, 2, KERN<FMT, 4, 2, 4, 2>}    /* D 2048, F 7168 (224 blocks: 4 steps, 672 units), decay rank 64: RWKV-6 1.6B */
+// one row per key of ring_geom.h (RG_KEYS: the shapes each key takes are listed there; rg_variant_key finds a stage's key, ring_variant its row)
+#define RING_ROW(KERN, FMT, I) {FMT, RG_KEYS[I].ept, RG_KEYS[I].nbd, RG_KEYS[I].uf, RG_KEYS[I].ksl, KERN<FMT, RG_KEYS[I].ept, RG_KEYS[I].nbd, RG_KEYS[I].uf, RG_KEYS[I].ksl>}
+#define RING_VARIANTS(KERN, FMT) RING_ROW(KERN, FMT, 0), RING_ROW(KERN, FMT, 1), RING_ROW(KERN, FMT, 2)
+static_assert(RG_NKEYS == 3, "RING_VARIANTS: one row per key");
 #ifdef R6_ONLY_FMT
-#define RING_TABLE(KERN) {R6_ONLY_FMT, 8, 4, 7, 3, KERN<R6_ONLY_FMT, 8, 4, 7, 3>},
+#define RING_TABLE(KERN) RING_ROW(KERN, R6_ONLY_FMT, 0),
 #else
 #define RING_TABLE(KERN) RING_VARIANTS(KERN, T_Q4_0), RING_VARIANTS(KERN, T_Q4_1), RING_VARIANTS(KERN, T_Q5_0), RING_VARIANTS(KERN, T_Q5_1), RING_VARIANTS(KERN, T_Q8_0),
 #endif
@@ -2098,15 +2098,13 @@ static const RingVariant g_ring_variants[] = { RING_TABLE(k6_ring) };
 
 // the instantiation for a stage v6_stage_shape accepted (-1: none)
 static int ring_variant(const V6Shape & s, int n_cu) {
-    const int64_t D = s.D, F = s.F, DR = s.DR, R = s.R;
-    const int fmt = s.fmt;
-    const int64_t NB = RG_NBLK;
-    const int64_t gpb = (F / 32 + NB - 1) / NB;
-    if (n_cu != NB || s.H > NB || s.H * 64 != D /* the kernel takes the head count from D */ || F % 32 != 0 || F % (gpb * 32) != 0 || DR > NB || DR % 32 != 0 || 5 * (D / 64) > NB + NB / 2 || !(R == 32 || R == 64) || gpb * 32 > 64) return -1;
+    if (n_cu != RG_NBLK || s.H > RG_NBLK || s.H * 64 != s.D /* the kernel takes the head count from D */) return -1;
+    const int k = rg_variant_key(s.D, s.F, s.DR, s.R);   // (the arithmetic on D, F and the two ranks: ring_geom.h)
+    if (k < 0) return -1;
+    const RingKey & rk = RG_KEYS[k];
     for (size_t v = 0; v < sizeof(g_ring_variants) / sizeof(g_ring_variants[0]); v++) {
         const RingVariant & rv = g_ring_variants[v];
-        const int64_t nbF = F / 32;
-        if (rv.fmt == fmt && D == rv.ept * 512 && DR == rv.nbd * 32 && (nbF + 63) / 64 == rv.uf && (3 * nbF + 7 * 64 - 1) / (7 * 64) == rv.ksl) return (int) v;
+        if (rv.fmt == s.fmt && rv.ept == rk.ept && rv.nbd == rk.nbd && rv.uf == rk.uf && rv.ksl == rk.ksl) return (int) v;
     }
     return -1;
 }

@@ -1,7 +1,9 @@
 // Host-side check of the per-workgroup weight stream layout (rwkv.cpp_amd/csrc/ring_geom.h), compiled and run by tests/test_ring_geom.py:
 // every row of every matrix of a layer lands in exactly one record of exactly one workgroup, records tile the layer block without gaps,
 // every record has exactly one consumer wave, a wave's "next own record" walks its records in stream order, and the head geometry
-// covers every vocabulary row once. No GPU, no HIP headers.
+// covers every vocabulary row once -- on every shape the device admits: F = 32 .. 20000 in steps of 32 for each D and both mix ranks,
+// through rg_variant_key, the arithmetic ring_variant (ring_v6.hip) itself calls; the admitted set is asserted to be the 117 (D, F) pairs
+// of the variant table (64 at D 2048, 21 at D 2560, 32 at D 4096). No GPU, no HIP headers.
 #include "ring_geom.h"
 
 #include <cstdio>
@@ -108,19 +110,48 @@ static void check_head(int n_vocab, int K) {
     CHECK(offs.size() * (size_t) RG_HREC == h.bytes, "head: records do not tile the head block");
 }
 
+// what rg_variant_key admits, written out by hand: 64 + 21 + 32 = 117 (D, F) pairs, each at its one decay rank and at both mix ranks
+static bool expected(int D, int F, int DR, int R) {
+    if (!(R == 32 || R == 64) || F % 32 != 0) return false;
+    if (D == 2048) return DR == 64 && F >= 6176 && F <= 8192;
+    if (D == 2560) return DR == 64 && F >= 8256 && F <= 9536 && F % 64 == 0;
+    if (D == 4096) return DR == 128 && F >= 12352 && F <= 14336 && F % 64 == 0;
+    return false;
+}
+
 int main() {
     struct Fmt { const char * name; int qs, scb, qhb; } fmts[] = {{"Q4_0", 16, 2, 0}, {"Q4_1", 16, 4, 0}, {"Q5_0", 16, 2, 4}, {"Q5_1", 16, 4, 4}, {"Q8_0", 32, 2, 0}};
-    struct Geo { int D, F, R5, DR; } geos[] = {{2048, 7168, 160, 64}, {4096, 14336, 320, 128}, {4096, 14336, 160, 64}, {2560, 8960, 160, 64}};
+    // every shape the device admits (ring_v6.hip, ring_variant -> rg_variant_key), in every format; the set itself is the hand-written one
+    std::set<std::pair<int, int>> pairs;
+    int per_d[3] = {0, 0, 0}, shapes = 0;
+    const int Ds[] = {2048, 2560, 4096, 1024, 1536, 3072, 3584, 5120}, DRs[] = {32, 64, 96, 128, 256}, Rs[] = {32, 48, 64, 96};
+    for (int D : Ds) for (int DR : DRs) for (int R : Rs)
+        for (int F = 32; F <= 20000; F += 32) {
+            const int k = rg_variant_key(D, F, DR, R);
+            CHECK((k >= 0) == expected(D, F, DR, R), "D %d F %d DR %d R %d: key %d", D, F, DR, R, k);
+            if (k < 0) continue;
+            CHECK(k < RG_NKEYS && RG_KEYS[k].ept * 512 == D && RG_KEYS[k].nbd * 32 == DR && RG_KEYS[k].uf == rg_steps(F) && 3 * (F / 32) <= RG_KEYS[k].ksl * 448 && 3 * (F / 32) > (RG_KEYS[k].ksl - 1) * 448,
+                  "D %d F %d: key %d does not describe the shape", D, F, k);
+            if (pairs.insert({D, F}).second) per_d[D == 2048 ? 0 : (D == 2560 ? 1 : 2)]++;
+            for (const Fmt & f : fmts)
+                for (int bal = 0; bal <= (D == 4096 ? 1 : 0); bal++) {
+                    RingShape s; s.D = D; s.F = F; s.R5 = 5 * R; s.DR = DR; s.qs = f.qs; s.scb = f.scb; s.qhb = f.qhb; s.bal = bal;
+                    char name[64]; snprintf(name, sizeof name, "%s D=%d F=%d R=%d bal=%d", f.name, D, F, R, bal);
+                    check_shape(s, name);
+                    shapes++;
+                }
+        }
+    CHECK(pairs.size() == 117 && per_d[0] == 64 && per_d[1] == 21 && per_d[2] == 32, "admitted (D, F) pairs: %zu = %d + %d + %d, expected 117 = 64 + 21 + 32", pairs.size(), per_d[0], per_d[1], per_d[2]);
+    CHECK(rg_variant_key(2048, 0, 64, 32) < 0 && rg_variant_key(2048, 7168 + 16, 64, 32) < 0, "F = 0 or no multiple of 32 admitted");
+    // (a layout the device declines, kept from before the sweep: D = 4096 at the ranks of the 1.6B model)
     for (const Fmt & f : fmts)
-        for (const Geo & g : geos) {
-            for (int bal = 0; bal <= (g.D == 4096 ? 1 : 0); bal++) {
-                RingShape s; s.D = g.D; s.F = g.F; s.R5 = g.R5; s.DR = g.DR; s.qs = f.qs; s.scb = f.scb; s.qhb = f.qhb; s.bal = bal;
-                char name[64]; snprintf(name, sizeof name, "%s D=%d bal=%d", f.name, g.D, bal);
-                check_shape(s, name);
-            }
+        for (int bal = 0; bal <= 1; bal++) {
+            RingShape s; s.D = 4096; s.F = 14336; s.R5 = 160; s.DR = 64; s.qs = f.qs; s.scb = f.scb; s.qhb = f.qhb; s.bal = bal;
+            char name[64]; snprintf(name, sizeof name, "%s D=4096 DR=64 bal=%d", f.name, bal);
+            check_shape(s, name);
         }
     for (int v : {4096, 8192, 32768, 65536}) for (int K : {2048, 2560, 4096}) check_head(v, K);
     if (fails) { fprintf(stderr, "%d checks failed\n", fails); return 1; }
-    printf("ring geometry OK\n");
+    printf("ring geometry OK (%zu admitted (D, F) pairs, %d shapes)\n", pairs.size(), shapes);
     return 0;
 }

@@ -6,6 +6,7 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <initializer_list>
 
 using namespace rwkvmi;
 
@@ -49,16 +50,30 @@ static void check_shape(const RingShape & s, uint32_t ring, int n_layers, const 
 
 int main() {
     struct Fmt { const char * name; int qs, scb, qhb; } fmts[] = {{"Q4_0", 16, 2, 0}, {"Q4_1", 16, 4, 0}, {"Q5_0", 16, 2, 4}, {"Q5_1", 16, 4, 4}, {"Q8_0", 32, 2, 0}};
-    struct Geo { int D, F, R5, DR; } geos[] = {{2048, 7168, 160, 64}, {2560, 8960, 160, 64}, {4096, 14336, 320, 128}};
     const uint32_t rings[] = {32 * 1024, 76 * 1024, 100 * 1024, 116 * 1024};   // multiples of 4 KiB, as the host sizes the ring
-    for (const Fmt & f : fmts)
-        for (const Geo & g : geos)
-            for (uint32_t ring : rings) {
-                RingShape s; s.D = g.D; s.F = g.F; s.R5 = g.R5; s.DR = g.DR; s.qs = f.qs; s.scb = f.scb; s.qhb = f.qhb;
-                char name[64]; snprintf(name, sizeof name, "%s D=%d ring=%u", f.name, g.D, ring);
-                check_shape(s, ring, 32, name);
-            }
+    // every shape the device admits (ring_v6.hip, ring_variant -> rg_variant_key): 64 + 21 + 32 (D, F) pairs, both mix ranks
+    const struct { int D, DR, want; } geos[] = {{2048, 64, 64}, {2560, 64, 21}, {4096, 128, 32}};
+    int pairs = 0;
+    for (const auto & g : geos) {
+        int n = 0;
+        for (int F = 32; F <= 20000; F += 32) {
+            const bool in32 = rg_variant_key(g.D, F, g.DR, 32) >= 0, in64 = rg_variant_key(g.D, F, g.DR, 64) >= 0;
+            CHECK(in32 == in64, "D %d F %d: the mix rank decides", g.D, F);
+            if (!in32) continue;
+            n++;
+            for (int R : {32, 64})
+                for (const Fmt & f : fmts)
+                    for (uint32_t ring : rings) {
+                        RingShape s; s.D = g.D; s.F = F; s.R5 = 5 * R; s.DR = g.DR; s.qs = f.qs; s.scb = f.scb; s.qhb = f.qhb;
+                        char name[64]; snprintf(name, sizeof name, "%s D=%d F=%d R=%d ring=%u", f.name, g.D, F, R, ring);
+                        check_shape(s, ring, 32, name);
+                    }
+        }
+        CHECK(n == g.want, "D %d: %d admitted F, expected %d", g.D, n, g.want);
+        pairs += n;
+    }
+    CHECK(pairs == 117, "%d admitted (D, F) pairs, expected 117", pairs);
     if (fails) { fprintf(stderr, "%d checks failed\n", fails); return 1; }
-    printf("ring wave table OK\n");
+    printf("ring wave table OK (%d admitted (D, F) pairs)\n", pairs);
     return 0;
 }

@@ -108,7 +108,7 @@ def expected_names(arch, n_layer):
     return {f"blocks.{i}.{k}" for i in range(n_layer) for k in keys}
 
 
-def state_families(om, seed):
+def state_families(om, seed, long_run=True):
     """{family: float32 state in the oracle's layout} for the file `om` (an oracle_lib.OracleModel) has loaded. All values are finite.
 
       normal      N(0, 1) everywhere
@@ -117,7 +117,8 @@ def state_families(om, seed):
       long-run    the oracle's own state after PROMPT_LEN tokens of lcg_tokens
       half-fresh  RWKV-4 only: even channels as in init_state() (aa = bb = 0, pp = -1e30, shifts 0), odd channels as in `normal`
       pp-high     RWKV-4 only: `normal` with pp ~ U(40, 80)
-    RWKV-4 (per layer: ffn shift, att shift, aa, bb, pp): in every drawn family bb = |drawn| + 0.5 (`tiny`: + 1e-40) and pp ~ U(-60, 60)."""
+    RWKV-4 (per layer: ffn shift, att shift, aa, bb, pp): in every drawn family bb = |drawn| + 0.5 (`tiny`: + 1e-40) and pp ~ U(-60, 60).
+    long_run=False leaves `long-run` out (300 oracle tokens: seconds at D = 4096); the drawn families are the same values either way."""
     rng = np.random.default_rng([int(seed), om.arch_major, om.arch_minor, om.n_embed])
     n, v4 = om.state_len, om.arch_major == 4
     out = {}
@@ -128,7 +129,8 @@ def state_families(om, seed):
             v[:, 3] = (np.abs(v[:, 3].astype(np.float64)) + floor).astype(np.float32)
             v[:, 4] = rng.uniform(-60.0, 60.0, v[:, 4].shape).astype(np.float32)
         out[family] = s
-    _, out["long-run"] = om.eval_sequence(lcg_tokens(om.n_vocab, PROMPT_LEN), om.init_state(), want_logits=False)
+    if long_run:
+        _, out["long-run"] = om.eval_sequence(lcg_tokens(om.n_vocab, PROMPT_LEN), om.init_state(), want_logits=False)
     if v4:
         s = out["normal"].copy()
         s.reshape(om.n_layer, 5, om.n_embed)[:, :, 0::2] = om.init_state().reshape(om.n_layer, 5, om.n_embed)[:, :, 0::2]

@@ -20,26 +20,33 @@ pytestmark = pytest.mark.gpu
 TOKENS = [1, 2, 3, 400, 5, 77, 300, 9, 11, 12]
 
 
-def _check(tmp_path, name, fmt, seed, want_path, env_off, env_on=None):
+def _open(p, env):
+    """A context of the file created under `env` (a variable set to "1", a dict of variables, or None)."""
+    env = {} if env is None else ({env: "1"} if isinstance(env, str) else dict(env))
+    prev = {k: os.environ.get(k) for k in env}
+    os.environ.update(env)
+    try:
+        return model(p)
+    finally:
+        for k, v in prev.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+def _check(tmp_path, name, fmt, seed, want_path, env_off, env_on=None, spec=None, n_seq=97, more=None):
+    """spec: a ModelSpec in place of synth.CONFIGS[name]; env_off None: no second context on another path; more(m, g, om, spec): further
+    checks on the same contexts before they are freed (tests/test_gpu_admitted_geometry.py)."""
     library()
     p = str(tmp_path / "m.bin")
-    spec = synth.CONFIGS[name]
+    spec = synth.CONFIGS[name] if spec is None else spec
     synth.write_model(p, spec, fmt, seed=seed)
     om = O.OracleModel(p)
-    if env_on:
-        os.environ[env_on] = "1"
-    try:
-        m = model(p)
-    finally:
-        if env_on:
-            del os.environ[env_on]
+    m = _open(p, env_on)
     assert m.decode_path() == want_path, (name, m.decode_path())
-    os.environ[env_off] = "1"
-    try:
-        g = model(p)
-    finally:
-        del os.environ[env_off]
-    assert g.decode_path() != want_path
+    g = _open(p, env_off) if env_off is not None else m
+    assert g is m or g.decode_path() != want_path
     ost, st, gst = om.init_state(), None, None
     for i, t in enumerate(TOKENS):
         ol, ost = om.eval(t, ost)
@@ -58,7 +65,7 @@ def _check(tmp_path, name, fmt, seed, want_path, env_off, env_on=None):
     assert list(toks) == ref
     assert np.array_equal(m.state_store(), os2)
     # a 97-token sequence pass (GEMM path for the quantised matrices, token tiles for the F16 ones) and its chunked form
-    seq = [int((1103515245 * i + 12345) % spec.n_vocab) for i in range(97)]
+    seq = [int((1103515245 * i + 12345) % spec.n_vocab) for i in range(n_seq)]
     ol, ost = om.eval_sequence(seq, om.init_state())
     gl, gst = m.eval_sequence(seq, None)
     assert np.array_equal(gl, ol), (name, fmt, "sequence", float(np.abs(gl - ol).max()))
@@ -79,7 +86,12 @@ def _check(tmp_path, name, fmt, seed, want_path, env_off, env_on=None):
     for got, want, what in ((fl, ol, "logits"), (fst, ost, "state")):
         err, tol = float(np.abs(got - want).max()), FAST_ARM_REL_TOL * (1.0 + float(np.abs(want).max()))
         assert np.isfinite(got).all() and err <= tol, (name, fmt, "fast arms", what, err, tol)
-    m.free(); g.free(); om.free()
+    if more is not None:
+        more(m, g, om, spec)
+    m.free()
+    if g is not m:
+        g.free()
+    om.free()
 
 
 @pytest.mark.parametrize("fmt", ["Q5_1", "Q4_0"])

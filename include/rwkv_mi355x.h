@@ -687,6 +687,88 @@ RWKV_API bool rwkv_mi_batch_serve_ex(struct rwkv_mi_batch * batch, const uint32_
                                      float * elapsed_ms /* may be NULL */, const struct rwkv_mi_serve_extra * extras /* [n_requests], may be NULL */,
                                      uint32_t * guide_state_out /* [n_requests], may be NULL */, uint32_t * guide_misses_out /* [n_requests], may be NULL */);
 
+/* ---- Serve sessions: submit, stream and cancel requests while the loop runs ----
+ * rwkv_mi_batch_serve blocks until the last request of a queue that was complete at the call has ended. A SESSION is the same device loop cut
+ * at its block boundaries (RWKV_MI_LOOP_BLOCK passes, read at open) and owned by a handle: between two blocks the host adds requests to the
+ * queue, takes the tokens emitted so far and drops requests. No kernel ever waits for the host.
+ * THE GUARANTEE is rwkv_mi_batch_serve_ex's, whenever a request was submitted: its tokens, length, stop reason and guide words are, bit for
+ * bit, what it gives alone on a batch of one slot. A cancelled request gives a prefix of those tokens.
+ * rwkv_mi_batch_serve_open(batch, lanes, n, family, limits): one session per batch at a time; nothing is enqueued. limits:
+ *   capacity        the entries of the request ring, >= 1 (it may be below n). Request id q lives in entry q % capacity, and an entry is free
+ *                   again once its request's `finished` event has been delivered: at most `capacity` requests are in flight, and a
+ *                   request that outlives capacity - 1 younger ones holds the ring until its end is delivered;
+ *   max_prompt, stride, max_seqs, max_seq_tokens   per request: prompt_len <= max_prompt, stop.max_tokens <= stride, stop.n_seqs <= max_seqs,
+ *                   the tokens of its sequences <= max_seq_tokens -- a ring entry has a fixed size;
+ *   features        RWKV_MI_SERVE_CUT | _REP | _GUIDED: what a request may ask for (top_k / min_p; decay / repetition; a guide). It fixes
+ *                   the draw kernel for the life of the session (_GUIDED and _REP bring _CUT with them, as the draw kernels do); a request
+ *                   with no setting draws the same tokens on the wider kernels;
+ *   reserved        0.
+ * rwkv_mi_batch_serve_submit(session, request, prompt_tokens, seq_lens, seq_tokens, extra, id_out): one request, by the rules of
+ *   rwkv_mi_batch_serve_ex for one request; ids count up from 0 in submit order. from_slot and bias_slot must not be lanes, and their
+ *   contents must stay untouched until the request's end has been delivered (not checked). A rejected submit changes nothing.
+ * rwkv_mi_batch_serve_cancel(session, id): true for a request in flight (submitted, its end not yet delivered); false, nothing changed, for
+ *   an id never issued or one whose end has been delivered. The request retires at the scheduler step after the first pass of the next
+ *   block enqueued -- a token drawn in that pass is still appended, and an end it brings about by itself wins -- with stopped_by
+ *   RWKV_MI_STOP_CANCELLED; in its prompt phase with length 0. A request cancelled while queued is admitted and retires after one pass.
+ *   True says that the request was in flight, not that the cancel decides its end: a request that has ended by itself on the device,
+ *   its end not yet delivered, still reports its own stopped_by.
+ * rwkv_mi_batch_serve_poll(session, flags, events_out, max_events, tokens_out, max_tokens, n_events, n_tokens): in this order,
+ *   1. if the session is BUSY and the last block read left work -- a lane with a request, or a queue head below the number submitted
+ *      (before any block has been read: if anything has been submitted): uploads what was submitted and cancelled since the last block and enqueues one block of passes, an
+ *      admission in front of its first pass (idle lanes take what has arrived at that pass), the fetch of the session's words and an
+ *      event behind it;
+ *   2. waits for the event of every enqueued block but the newest (RWKV_MI_POLL_DRAIN, or a poll that enqueued nothing: the newest too)
+ *      and reads their words;
+ *   3. delivers: one event per request with new tokens or a newly known end, oldest request first, the events' new tokens back to back
+ *      in tokens_out. What does not fit max_events / max_tokens is delivered by the next poll; no token is delivered twice.
+ *   BUSY: a block is enqueued and unread, or the last block read left a lane with a request, or its queue head is below the number
+ *   submitted. A poll of a session that is not busy enqueues nothing and returns at once. When the last block read left no work, a block
+ *   still unread was enqueued with nothing to do: the poll reads it and enqueues no other, so a caller that polls in a loop, with or
+ *   without RWKV_MI_POLL_DRAIN, comes to rest (rwkv_mi_batch_serve_stats stops moving) with at most two blocks of dead passes behind the
+ *   end of the work. What the session does is a function of the sequence of calls, never of timing.
+ *   An event: id; first, the position of its first token; n_new; finished; stopped_by (valid when finished: the sequence index,
+ *   RWKV_MI_NO_TOKEN for the budget, RWKV_MI_STOP_CANCELLED); lane, start_pass (the pass, counted from open, that fed the first prompt
+ *   token); guide_state, guide_misses (valid when finished; 0 and 0 for an unguided request).
+ * rwkv_mi_batch_serve_stats: passes and blocks enqueued so far, requests in flight, submits the ring has room for.
+ * rwkv_mi_batch_serve_close(session, last_request_out): cancels what is in flight, drains, sets each lane slot's parity from the passes its
+ *   requests ran and frees the session; last_request_out[r]: the id lane r served last (RWKV_MI_NO_TOKEN: none -- the slot is as it was). A
+ *   lane holds what its last request left, as after rwkv_mi_batch_serve. rwkv_mi_batch_free closes an open session first.
+ * WHILE A SESSION IS OPEN every batch call that runs a pass (eval*, decode*, score*, serve*), rwkv_mi_batch_set_logprobs and a second open are
+ * rejected with RWKV_ERROR_ARGS, nothing changed. Calls that run no pass stay legal on slots that are not lanes: state_load / _store / _copy,
+ * logit_bias_set, guide_create.
+ * REJECTED with RWKV_ERROR_ARGS, nothing changed -- open: what rwkv_mi_batch_serve rejects for lanes and family (a lane with a guide attached
+ * or a bias set, a RWKV_MI_DEVICES chain); a batch with the log-prob report on; limits NULL, capacity or max_prompt or stride 0, max_seqs
+ * above RWKV_MI_STOP_MAX_SEQS, unknown feature bits, RWKV_MI_SERVE_GUIDED in the greedy family, reserved != 0; an open session. submit: what
+ * rwkv_mi_batch_serve_ex rejects for one request; a request over a limit; one that needs a feature the session did not declare; a full
+ * ring (the message says "full"). poll: events_out or tokens_out NULL with a non-zero maximum.
+ * OUT OF SCOPE: the log-prob report inside a session; chunked prompt ingestion (a long prompt goes in through a from_slot prepared before
+ * open, or one pass per token); priorities or reordering of the queue; compacting idle lanes. */
+#define RWKV_MI_STOP_CANCELLED   (UINT32_MAX - 1u)
+#define RWKV_MI_SERVE_CUT        1u
+#define RWKV_MI_SERVE_REP        2u
+#define RWKV_MI_SERVE_GUIDED     4u
+#define RWKV_MI_POLL_DRAIN       1u
+struct rwkv_mi_serve_limits {             /* 28 bytes */
+    uint32_t capacity; uint32_t max_prompt; uint32_t stride; uint32_t max_seqs; uint32_t max_seq_tokens;
+    uint32_t features;                    /* RWKV_MI_SERVE_CUT | _REP | _GUIDED */
+    uint32_t reserved;                    /* 0 */
+};
+struct rwkv_mi_serve_event {              /* 36 bytes */
+    uint32_t id; uint32_t first; uint32_t n_new; uint32_t finished; uint32_t stopped_by;
+    uint32_t lane; uint32_t start_pass; uint32_t guide_state; uint32_t guide_misses;
+};
+struct rwkv_mi_serve_session;
+RWKV_API struct rwkv_mi_serve_session * rwkv_mi_batch_serve_open(struct rwkv_mi_batch * batch, const uint32_t * lanes /* [n] slots */, size_t n, int family,
+                                                                 const struct rwkv_mi_serve_limits * limits);
+RWKV_API bool rwkv_mi_batch_serve_submit(struct rwkv_mi_serve_session * session, const struct rwkv_mi_serve_request * request,
+                                         const uint32_t * prompt_tokens /* [prompt_len] */, const uint32_t * seq_lens, const uint32_t * seq_tokens,
+                                         const struct rwkv_mi_serve_extra * extra /* may be NULL */, uint32_t * id_out);
+RWKV_API bool rwkv_mi_batch_serve_cancel(struct rwkv_mi_serve_session * session, uint32_t id);
+RWKV_API bool rwkv_mi_batch_serve_poll(struct rwkv_mi_serve_session * session, uint32_t flags, struct rwkv_mi_serve_event * events_out, size_t max_events,
+                                       uint32_t * tokens_out, size_t max_tokens, size_t * n_events, size_t * n_tokens);
+RWKV_API bool rwkv_mi_batch_serve_stats(struct rwkv_mi_serve_session * session, uint64_t * passes, uint64_t * blocks, uint32_t * in_flight, uint32_t * room);
+RWKV_API bool rwkv_mi_batch_serve_close(struct rwkv_mi_serve_session * session, uint32_t * last_request_out /* [n], may be NULL */);
+
 #if defined(__cplusplus)
 }
 #endif

@@ -4,6 +4,7 @@
 #include "model.h"
 #include "rwkv_mi355x.h"
 #include "call_layout.h"
+#include "session_book.h"
 
 #include <cinttypes>
 #include <cmath>
@@ -78,9 +79,14 @@ struct rwkv_mi_batch {
     Staged serve;
     DevBuf<float> serve_fresh;          // [state_len]
     LogprobReport lp;                   // the report of the batch's emitting calls (rwkv_mi_batch_set_logprobs)
+    // the serve session open on the batch (rwkv_mi_batch_serve_open; owned by its handle until close, or closed by rwkv_mi_batch_free):
+    // while there is one, batch_begin rejects every call that runs a pass
+    rwkv_mi_serve_session * session = nullptr;
 
     float * slot_buf(size_t slot, int p) const { return states.p + ((size_t) p * n_slots + slot) * (size_t) state_len; }
 };
+
+struct rwkv_mi_serve_session;
 
 // errors of the batch's own context are reported on the caller's
 static bool batch_fail_through(rwkv_mi_batch * B) { B->ctx->last_error |= B->run->last_error; B->run->last_error = 0; return false; }
@@ -92,6 +98,7 @@ static bool batch_fail_through(rwkv_mi_batch * B) { B->ctx->last_error |= B->run
 // batch's device is current
 static bool batch_begin(rwkv_mi_batch * B) {
     B->ctx->last_error = RWKV_ERROR_NONE;
+    RW_CTX_CHECK(B->ctx, RWKV_ERROR_ARGS, false, B->session == nullptr, "a serve session is open on this batch (rwkv_mi_batch_serve_close ends it)");
     B->run->print_errors = B->ctx->print_errors;
     BATCH_HIP_OK(B, hipSetDevice(B->ctx->model->device));
     return true;
@@ -869,6 +876,298 @@ static bool batch_serve(rwkv_mi_batch * B, const BatchCall & c, uint32_t * token
     return true;
 }
 
+// ---- serve sessions (rwkv_mi_batch_serve_open ..) ----
+
+// The device loop of batch_serve cut at its block boundaries and owned by a handle. The words live in one staged table (SessionLayout): a
+// submit writes its ring entry into the staging, the next block carries it up; what a block brings back goes into staging of its own, one
+// half per block parity, because the fetch of block b runs while the host reads what block b - 1 left. Every decision is the book's
+// (session_book.h); this code enqueues, copies and waits for events.
+struct rwkv_mi_serve_session {
+    rwkv_mi_batch * B = nullptr;
+    std::vector<uint32_t> lanes;
+    std::vector<uint8_t> is_lane;           // [n_slots]
+    Draw draw = Draw::none;
+    DrawForm form;
+    rwkv_mi_serve_limits lim{};
+    SessionLayout L;
+    Staged words;
+    PinBuf<uint8_t> down;                   // [2][L.bytes - L.down]
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    SessionBook book;
+    RowSession dev{};
+    bool failed = false;                    // a block could not be enqueued or read: only close is left
+    ~rwkv_mi_serve_session() { for (hipEvent_t e : ev) if (e) (void) hipEventDestroy(e); }
+};
+
+// what every session call starts with: batch_begin without its session check
+static bool session_begin(rwkv_mi_serve_session * S) {
+    rwkv_mi_batch * B = S->B;
+    B->ctx->last_error = RWKV_ERROR_NONE;
+    B->run->print_errors = B->ctx->print_errors;
+    BATCH_HIP_OK(B, hipSetDevice(B->ctx->model->device));
+    RW_CTX_CHECK(B->ctx, RWKV_ERROR_GRAPH, false, !S->failed, "the session has failed (rwkv_mi_batch_serve_close frees it)");
+    return true;
+}
+
+// One block: what was submitted and cancelled since the last one goes up, the admission in front of the first pass, K passes, the fetch of
+// the words that come back and the block's event.
+static bool session_enqueue(rwkv_mi_serve_session * S) {
+    rwkv_mi_batch * B = S->B;
+    rwkv_context * run = B->run;
+    hipStream_t st = run->stream;
+    const SessionLayout & L = S->L;
+    const Staged & w = S->words;
+    const size_t n = S->lanes.size();
+    const SessionBook::Block b = S->book.begin_block();
+    const size_t half = (size_t) (b.index & 1);
+    S->failed = true;   // (until everything below has been enqueued)
+    for (uint32_t id = b.upload_from; id != b.upload_to;) {
+        const size_t e0 = L.entry_of(id), count = std::min<size_t>(b.upload_to - id, L.capacity - e0);
+        size_t from = 0, to = 0;
+        L.reqs_range(e0, e0 + count, &from, &to);
+        BATCH_HIP_OK(B, w.upload(from, to, st));
+        L.words_range(e0, e0 + count, &from, &to);
+        BATCH_HIP_OK(B, w.upload(from, to, st));
+        id += (uint32_t) count;
+    }
+    const Field<uint32_t> ch = L.cancel_half(half);   // (block b - 2, which read this half, has been consumed)
+    memcpy(w.h(ch), S->book.cancel.data(), ch.bytes());
+    BATCH_HIP_OK(B, w.upload(ch.off, ch.end(), st));
+    RowSession & d = S->dev;
+    d.s.tail = b.tail; d.s.cancel = w.d(ch);
+    RowSampler sampler = batch_sampler(B, nullptr, nullptr);
+    sampler.form = S->form; sampler.session = &d;
+    const auto table = [&](uint32_t pass) { return B->rows.d() + (size_t) (pass & 1u) * B->n_slots; };
+    // idle lanes take what has arrived at the block's first pass: the scheduler step "after pass first_pass - 1", admissions only
+    d.s.admit_only = 1u;
+    launch_session_rows(d.s, (int64_t) n, run->d_tokens.p, b.first_pass - 1u, table(b.first_pass + 1u), table(b.first_pass), st);
+    launch_serve_reset(d.s.t, (int64_t) n, d.chunks, table(b.first_pass + 1u), d.state_len, st);
+    d.s.admit_only = 0u;
+    for (size_t i = 0; i < S->book.K; i++) {
+        const uint32_t pass = b.first_pass + (uint32_t) i;
+        sampler.step = pass; sampler.used = table(pass); sampler.other = table(pass + 1u);
+        if (!forward_rows(run, sampler.used, (int64_t) n, true, &sampler)) return batch_fail_drained(B);
+    }
+    const size_t down_bytes = L.bytes - L.down;
+    hipError_t e = hipMemcpyAsync(S->down.p + half * down_bytes, w.dev.p + L.down, down_bytes, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipEventRecord(S->ev[half], st);
+    if (e != hipSuccess) { (void) hipStreamSynchronize(st); BATCH_HIP_OK(B, e); }
+    S->failed = false;
+    return true;
+}
+
+// reads the words of the enqueued blocks below `upto`, oldest first, each behind its event
+static bool session_consume(rwkv_mi_serve_session * S, uint64_t upto) {
+    rwkv_mi_batch * B = S->B;
+    const SessionLayout & L = S->L;
+    const size_t down_bytes = L.bytes - L.down;
+    while (S->book.consumed < upto) {
+        const size_t half = (size_t) (S->book.consumed & 1);
+        const hipError_t e = hipEventSynchronize(S->ev[half]);
+        if (e != hipSuccess) { S->failed = true; (void) hipStreamSynchronize(B->run->stream); BATCH_HIP_OK(B, e); }
+        const uint8_t * base = S->down.p + half * down_bytes;
+        const auto at = [base, &L](const Field<uint32_t> & f) { return (const uint32_t *) (base + (f.off - L.down)); };
+        const bool g = L.req_g_state.count != 0;
+        S->book.consume(SessionWords{at(L.next), at(L.work), at(L.ids), at(L.done), at(L.lens), at(L.reasons), at(L.lane), at(L.start), at(L.end), at(L.revived),
+                                     g ? at(L.req_g_state) : nullptr, g ? at(L.req_g_misses) : nullptr, at(L.out)});
+    }
+    return true;
+}
+
+// everything rwkv_mi_batch_serve_ex checks for one request, the session's limits and its features; nothing changed
+static bool session_check_request(rwkv_mi_serve_session * S, const rwkv_mi_serve_request & rq, const uint32_t * prompt, const uint32_t * seq_lens,
+                                  const uint32_t * seq_tokens, const rwkv_mi_serve_extra * ex) {
+    rwkv_mi_batch * B = S->B;
+    rwkv_context * ctx = B->ctx;
+    const rwkv_mi_serve_limits & lim = S->lim;
+    const size_t n_vocab = (size_t) ctx->model->n_vocab();
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, rq.prompt_len > 0, "the prompt of the request is empty");
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, rq.prompt_len <= lim.max_prompt, "prompt_len (%" PRIu32 ") is above the session's max_prompt (%" PRIu32 ")", rq.prompt_len, lim.max_prompt);
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, rq.from_slot == RWKV_MI_NO_SLOT || (rq.from_slot < B->n_slots && !S->is_lane[rq.from_slot]),
+                 "from_slot of the request (%" PRIu32 ") is a lane of the session or out of range", rq.from_slot);
+    for (uint32_t t = 0; t < rq.prompt_len; t++)
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, prompt[t] < n_vocab, "Prompt token at index %" PRIu32 " (%" PRIu32 ") is out of range (0 .. %zu)", t, prompt[t], n_vocab - 1);
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, rq.min_p >= 0.0f && rq.min_p <= 1.0f, "min_p of the request (%g) must be in 0 .. 1", (double) rq.min_p);
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, rq.decay >= 0.0f && rq.decay <= 1.0f, "decay of the request (%g) must be in 0 .. 1", (double) rq.decay);
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, rq.repetition > 0.0f && rq.repetition < INFINITY, "repetition of the request (%g) must be finite and above 0", (double) rq.repetition);
+    bool guided = false;
+    if (ex) {
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, ex->reserved == 0, "reserved of the extra of the request is not 0");
+        if (ex->guide != RWKV_MI_NO_GUIDE) {
+            RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, ex->guide < RWKV_MI_GUIDE_MAX && B->guide_states[ex->guide], "guide of the request (%" PRIu32 ") names no guide", ex->guide);
+            RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, ex->guide_state < B->guide_states[ex->guide], "guide_state of the request (%" PRIu32 ") is out of range", ex->guide_state);
+            RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, S->draw != Draw::none, "the request has a guide in the greedy family (guided greedy is temperature 0 of the sampled one)");
+            guided = true;
+        }
+        if (ex->bias_slot != RWKV_MI_NO_SLOT) {
+            RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, ex->bias_slot < B->n_slots && !S->is_lane[ex->bias_slot] && B->draw.has_bias[ex->bias_slot],
+                         "bias_slot of the request (%" PRIu32 ") is a lane of the session, out of range or has no bias set", ex->bias_slot);
+            RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, S->draw == Draw::penalized, "the request has a bias_slot in a family that reads no bias (the penalised one does)");
+        }
+    }
+    if (S->draw != Draw::none && !batch_check_params(B, &rq.sample, 1, false)) return false;
+    if (S->draw == Draw::penalized && !batch_check_penalties(B, &rq.penalty, 1)) return false;
+    uint32_t lens_dummy = 0;
+    if (!batch_check_stops(B, &rq.stop, 1, seq_lens, seq_tokens, lim.stride, &lens_dummy)) return false;
+    size_t n_toks = 0;
+    for (uint32_t q = 0; q < rq.stop.n_seqs; q++) n_toks += seq_lens[q];
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, rq.stop.n_seqs <= lim.max_seqs && n_toks <= lim.max_seq_tokens,
+                 "the request's %" PRIu32 " stop sequences of %zu tokens are above the session's limits (%" PRIu32 ", %" PRIu32 ")", rq.stop.n_seqs, n_toks, lim.max_seqs, lim.max_seq_tokens);
+    // what the request needs of the draw kernel, as batch_serve derives it from its queue
+    const bool cut = S->draw != Draw::none && ((rq.top_k != 0u && rq.top_k < n_vocab) || rq.min_p != 0.0f);
+    const bool rep = S->draw == Draw::penalized && (rq.decay != 1.0f || rq.repetition != 1.0f);
+    // (against the session's kernel, which the features fixed: RWKV_MI_SERVE_GUIDED and _REP bring the truncating form with them)
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, (!cut || S->form.cut) && (!rep || S->form.rep) && (!guided || S->form.guided), "the request needs a feature the session did not declare (cut %d, rep %d, guided %d; features 0x%" PRIx32 ")",
+                 (int) cut, (int) rep, (int) guided, lim.features);
+    return true;
+}
+
+// the session's lanes, checked by batch_check_serve's rules
+static bool session_check_lanes(rwkv_mi_batch * B, const uint32_t * lanes, size_t n, std::vector<uint8_t> * is_lane) {
+    rwkv_context * ctx = B->ctx;
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, lanes != nullptr, "lanes is NULL");
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, n > 0 && n <= B->n_slots, "n (%zu) must be in 1 .. %zu", n, B->n_slots);
+    is_lane->assign(B->n_slots, 0);
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t s = lanes[i];
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, s < B->n_slots, "lane slot %" PRIu32 " at index %zu is out of range (0 .. %zu)", s, i, B->n_slots - 1);
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, !(*is_lane)[s], "lane slot %" PRIu32 " appears twice", s);
+        RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, B->draw.guide_of[s] == RWKV_MI_NO_GUIDE && !B->draw.has_bias[s], "lane slot %" PRIu32 " has a guide attached or a bias set", s);
+        (*is_lane)[s] = 1;
+    }
+    return true;
+}
+
+static rwkv_mi_serve_session * session_open(rwkv_mi_batch * B, const uint32_t * lanes, size_t n, int family, const rwkv_mi_serve_limits * lim) {
+    rwkv_context * ctx = B->ctx;
+    rwkv_context * run = B->run;
+    ctx->last_error = RWKV_ERROR_NONE;
+    RW_NO_PIPELINE(ctx, nullptr);
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, nullptr, family == RWKV_MI_SERVE_GREEDY || family == RWKV_MI_SERVE_SAMPLE || family == RWKV_MI_SERVE_PENALIZED,
+                 "unknown family (%d)", family);
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, nullptr, B->session == nullptr, "a serve session is already open on this batch");
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, nullptr, !B->lp.enabled, "a serve session takes no batch with the log-prob report on");
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, nullptr, lim != nullptr, "limits is NULL");
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, nullptr, lim->reserved == 0, "reserved of the limits is not 0");
+    const uint32_t known = RWKV_MI_SERVE_CUT | RWKV_MI_SERVE_REP | RWKV_MI_SERVE_GUIDED;
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, nullptr, (lim->features & ~known) == 0, "unknown bits in features (0x%" PRIx32 ")", lim->features);
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, nullptr, lim->capacity >= 1 && lim->max_prompt >= 1 && lim->stride >= 1, "capacity, max_prompt and stride must be at least 1");
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, nullptr, lim->max_seqs <= RWKV_MI_STOP_MAX_SEQS && lim->max_seq_tokens <= RWKV_MI_STOP_MAX_SEQS * RWKV_MI_STOP_MAX_LEN,
+                 "max_seqs (%" PRIu32 ") or max_seq_tokens (%" PRIu32 ") is above what a request may carry (%d, %d)", lim->max_seqs, lim->max_seq_tokens, RWKV_MI_STOP_MAX_SEQS,
+                 RWKV_MI_STOP_MAX_SEQS * RWKV_MI_STOP_MAX_LEN);
+    const Draw draw = family == RWKV_MI_SERVE_PENALIZED ? Draw::penalized : family == RWKV_MI_SERVE_SAMPLE ? Draw::sample : Draw::none;
+    const bool guided = (lim->features & RWKV_MI_SERVE_GUIDED) != 0;
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, nullptr, !guided || draw != Draw::none, "RWKV_MI_SERVE_GUIDED in the greedy family (guided greedy is temperature 0 of the sampled one)");
+    std::unique_ptr<rwkv_mi_serve_session> S(new (std::nothrow) rwkv_mi_serve_session());
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, nullptr, S != nullptr, "out of memory");
+    if (!session_check_lanes(B, lanes, n, &S->is_lane)) return nullptr;
+    const SessionLayout L(n, lim->capacity, lim->max_prompt, lim->max_seqs, lim->max_seq_tokens, lim->stride, guided);
+    // (a ring entry's words are addressed by 32-bit word offsets)
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, nullptr, (uint64_t) lim->capacity * lim->stride < (1ull << 28) && L.bytes < (1ull << 31), "the session's tables are too large (%zu bytes)", L.bytes);
+    run->print_errors = ctx->print_errors;
+    if (hipSetDevice(ctx->model->device) != hipSuccess) { RW_CTX_CHECK(ctx, RWKV_ERROR_GRAPH, nullptr, false, "hipSetDevice failed"); }
+    BatchCall lane_call{lanes, nullptr, n};
+    lane_call.draw = draw;
+    if (!batch_ensure_draw(B, lane_call) || !batch_ensure_serve(B, 0)) return nullptr;   // (the family's draw buffers; the fresh state)
+    S->B = B; S->lanes.assign(lanes, lanes + n); S->draw = draw; S->lim = *lim; S->L = L;
+    S->form = DrawForm::of(draw, (lim->features & RWKV_MI_SERVE_CUT) != 0, guided, (lim->features & RWKV_MI_SERVE_REP) != 0);
+    B->form = S->form;
+    hipError_t e = grow(want(S->words, L.bytes), want(S->down, 2 * (L.bytes - L.down)));
+    for (hipEvent_t & v : S->ev) if (e == hipSuccess) e = hipEventCreateWithFlags(&v, hipEventDisableTiming);
+    if (e != hipSuccess) (void) hipGetLastError();
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ALLOC, nullptr, e == hipSuccess, "cannot allocate the session's tables (%zu bytes): %s", L.bytes, hipGetErrorString(e));
+    S->book.init(lim->capacity, n, lim->stride, loop_block());
+    // the start values: every lane idle on {in = its slot's current buffer, out = the other one} in BOTH row tables -- an idle lane's dead
+    // passes leave the slot's state alone --, a valid token word per lane, no entry admitted, an empty queue
+    hipStream_t st = run->stream;
+    if (hipStreamSynchronize(st) != hipSuccess) { RW_CTX_CHECK(ctx, RWKV_ERROR_GRAPH, nullptr, false, "HIP error at the session's start"); }
+    const Staged & w = S->words;
+    memset(w.pin.p, 0, L.bytes);
+    for (size_t r = 0; r < n; r++) { w.h(L.lane_slot)[r] = lanes[r]; w.h(L.req)[r] = SESSION_IDLE; w.h(L.last)[r] = RWKV_MI_NO_TOKEN; }
+    for (size_t i = 0; i < L.capacity; i++) { w.h(L.ids)[i] = RWKV_MI_NO_TOKEN; w.h(L.reasons)[i] = RWKV_MI_NO_TOKEN; }
+    for (int tb = 0; tb < 2; tb++)
+        for (size_t r = 0; r < n; r++) {
+            const int p = B->parity[lanes[r]];
+            B->rows.h()[(size_t) tb * B->n_slots + r] = RowState{B->slot_buf(lanes[r], p), B->slot_buf(lanes[r], p ^ 1)};
+        }
+    e = w.upload(0, L.bytes, st);
+    if (e == hipSuccess) e = hipMemsetAsync(run->d_tokens.p, 0, n * sizeof(uint32_t), st);
+    for (int tb = 0; tb < 2 && e == hipSuccess; tb++) e = B->rows.upload_rows((size_t) tb * B->n_slots, (size_t) tb * B->n_slots + n, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    RW_CTX_CHECK(ctx, RWKV_ERROR_GRAPH, nullptr, e == hipSuccess, "HIP error: %s", hipGetErrorString(e));
+    RowSession & d = S->dev;
+    uint32_t * ring = w.d(L.ring);
+    d.s.t = ServeTables{w.d(L.reqs), ring, ring, ring, w.d(L.out), lim->stride,
+                        w.d(L.lens), w.d(L.reasons), w.d(L.lane), w.d(L.start), w.d(L.req), w.d(L.pos), w.d(L.draw), w.d(L.admit), w.d(L.last), w.d(L.lane_slot),
+                        draw != Draw::none ? B->draw_rows.d() : nullptr, B->draw.counters.p, B->draw.counts.p, w.d(L.next), w.d(L.work),
+                        0u, (uint32_t) ctx->model->n_vocab(),
+                        guided ? w.d(L.g_state) : nullptr, guided ? w.d(L.g_misses) : nullptr, guided ? w.d(L.req_g_state) : nullptr, guided ? w.d(L.req_g_misses) : nullptr};
+    d.s.capacity = lim->capacity; d.s.tail = 0u; d.s.cancel = w.d(L.cancel_half(0));
+    d.s.ids = w.d(L.ids); d.s.done = w.d(L.done); d.s.end_pass = w.d(L.end); d.s.revived = w.d(L.revived);
+    d.s.entry_words = (uint32_t) L.entry_words; d.s.guide_word = (uint32_t) L.w_guide; d.s.admit_only = 0u;
+    d.state_len = B->state_len; d.chunks = serve_chunks(B->state_len);
+    B->session = S.get();
+    return S.release();
+}
+
+// the request's ring entry into the staging: the row batch_serve builds, its words behind it
+static void session_stage(rwkv_mi_serve_session * S, uint32_t id, const rwkv_mi_serve_request & rq, const uint32_t * prompt, const uint32_t * seq_lens,
+                          const uint32_t * seq_tokens, const rwkv_mi_serve_extra * extra) {
+    rwkv_mi_batch * B = S->B;
+    const SessionLayout & L = S->L;
+    const size_t e = L.entry_of(id);
+    const bool pen = S->draw == Draw::penalized;
+    uint32_t * ew = S->words.h(L.ring) + L.word(e, 0);
+    DrawRow row{};
+    row.p = rq.sample; row.p.u = -1.0f;
+    row.presence = pen ? rq.penalty.presence : 0.0f; row.frequency = pen ? rq.penalty.frequency : 0.0f; row.record = pen ? 1u : 0u;
+    row.top_k = rq.top_k; row.min_p = rq.min_p; row.decay = rq.decay; row.repetition = rq.repetition;
+    const rwkv_mi_serve_extra ex = extra ? *extra : rwkv_mi_serve_extra{RWKV_MI_NO_GUIDE, 0u, RWKV_MI_NO_SLOT, 0u};
+    if (ex.guide != RWKV_MI_NO_GUIDE) row.next = B->guides[ex.guide].p;
+    if (pen && ex.bias_slot != RWKV_MI_NO_SLOT) row.bias = B->draw.bias_of(ex.bias_slot);
+    const float * start = rq.from_slot == RWKV_MI_NO_SLOT ? B->serve_fresh.p : B->slot_buf(rq.from_slot, B->parity[rq.from_slot]);
+    const StopRow stop{rq.stop.max_tokens, rq.stop.n_seqs, (uint32_t) L.word(e, L.w_seq_lens), (uint32_t) L.word(e, L.w_seq_tokens)};
+    S->words.h(L.reqs)[e] = ServeReq{row, stop, rq.prompt_len, (uint32_t) L.word(e, L.w_prompt), start};
+    memcpy(ew + L.w_prompt, prompt, (size_t) rq.prompt_len * sizeof(uint32_t));
+    size_t n_toks = 0;
+    for (uint32_t q = 0; q < rq.stop.n_seqs; q++) { ew[L.w_seq_lens + q] = seq_lens[q]; n_toks += seq_lens[q]; }
+    if (n_toks) memcpy(ew + L.w_seq_tokens, seq_tokens, n_toks * sizeof(uint32_t));
+    ew[L.w_guide] = ex.guide != RWKV_MI_NO_GUIDE ? ex.guide_state : 0u;
+}
+
+// Cancels what is in flight, drains, sets the lanes' parities and frees the session. Every request still in flight retires within one block of
+// its cancel word (a queued one after one pass on a lane), so the number of blocks is bounded; a session that is still busy after them has failed.
+static bool session_close(rwkv_mi_serve_session * S, uint32_t * last_request_out) {
+    rwkv_mi_batch * B = S->B;
+    std::unique_ptr<rwkv_mi_serve_session> owner(S);
+    SessionBook & book = S->book;
+    B->ctx->last_error = RWKV_ERROR_NONE;
+    B->run->print_errors = B->ctx->print_errors;
+    (void) hipSetDevice(B->ctx->model->device);
+    bool ok = !S->failed;
+    for (uint32_t id = book.oldest; id != book.submitted; id++) (void) book.cancel_request(id);
+    std::vector<rwkv_mi_serve_event> ev(book.capacity);
+    std::vector<uint32_t> toks(book.capacity * book.stride);
+    size_t ne = 0, nt = 0;
+    if (ok) ok = session_consume(S, book.enqueued);   // (what is still unread first: the blocks below are enqueued on what the device has really done)
+    for (size_t blocks = 0; ok && book.busy() && blocks < book.capacity + 4; blocks++) {
+        ok = session_enqueue(S) && session_consume(S, book.enqueued);
+        if (ok) book.deliver(ev.data(), ev.size(), toks.data(), toks.size(), &ne, &nt);
+    }
+    if (ok) book.deliver(ev.data(), ev.size(), toks.data(), toks.size(), &ne, &nt);
+    (void) hipStreamSynchronize(B->run->stream);   // (whatever happened: nothing of the session's is read after this)
+    B->session = nullptr;
+    if (ok && (book.busy() || book.in_flight != 0)) {
+        ok = false;
+        ctx_fail(B->ctx, RWKV_ERROR_GRAPH, __FILE__, __LINE__, "session drained", "the session did not drain (%" PRIu32 " requests in flight): the device loop failed", book.in_flight);
+    }
+    for (size_t r = 0; r < S->lanes.size(); r++) {
+        if (ok && book.parity_flip(r)) B->parity[S->lanes[r]] ^= 1;
+        if (last_request_out) last_request_out[r] = book.lane_last[r];
+    }
+    return ok;
+}
+
 // ---- beam search (rwkv_mi_batch_decode_beam) ----
 
 // a call of G groups of W hypotheses: row g * W + j is slot slots[g * W + j]
@@ -1001,6 +1300,7 @@ extern "C" {
 
 RWKV_API void rwkv_mi_batch_free(struct rwkv_mi_batch * B) {
     if (!B) return;
+    if (B->session) (void) session_close(B->session, nullptr);
     if (B->run) {
         (void) hipSetDevice(B->run->model->device);
         (void) hipStreamSynchronize(B->run->stream);
@@ -1282,6 +1582,64 @@ RWKV_API bool rwkv_mi_batch_serve_ex(struct rwkv_mi_batch * B, const uint32_t * 
                        start_pass_out, last_request_out, elapsed_ms, true, extras, guide_state_out, guide_misses_out);
 }
 
+// ---- serve sessions (include/rwkv_mi355x.h) ----
+
+RWKV_API struct rwkv_mi_serve_session * rwkv_mi_batch_serve_open(struct rwkv_mi_batch * B, const uint32_t * lanes, size_t n, int family,
+                                                                 const struct rwkv_mi_serve_limits * limits) {
+    return B ? session_open(B, lanes, n, family, limits) : nullptr;
+}
+
+RWKV_API bool rwkv_mi_batch_serve_submit(struct rwkv_mi_serve_session * S, const struct rwkv_mi_serve_request * request, const uint32_t * prompt_tokens,
+                                         const uint32_t * seq_lens, const uint32_t * seq_tokens, const struct rwkv_mi_serve_extra * extra, uint32_t * id_out) {
+    if (!S || !session_begin(S)) return false;
+    rwkv_context * ctx = S->B->ctx;
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, request != nullptr && prompt_tokens != nullptr && id_out != nullptr, "request, prompt_tokens or id_out is NULL");
+    if (!session_check_request(S, *request, prompt_tokens, seq_lens, seq_tokens, extra)) return false;
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, S->book.room() > 0 && S->book.submitted < SERVE_FREE - 1u,
+                 "the request ring is full (%" PRIu32 " requests in flight, capacity %" PRIu32 "): poll until an end has been delivered", S->book.in_flight, S->lim.capacity);
+    const uint32_t id = S->book.submit();
+    session_stage(S, id, *request, prompt_tokens, seq_lens, seq_tokens, extra);
+    *id_out = id;
+    return true;
+}
+
+RWKV_API bool rwkv_mi_batch_serve_cancel(struct rwkv_mi_serve_session * S, uint32_t id) {
+    if (!S) return false;
+    S->B->ctx->last_error = RWKV_ERROR_NONE;
+    return S->book.cancel_request(id);
+}
+
+RWKV_API bool rwkv_mi_batch_serve_poll(struct rwkv_mi_serve_session * S, uint32_t flags, struct rwkv_mi_serve_event * events_out, size_t max_events,
+                                       uint32_t * tokens_out, size_t max_tokens, size_t * n_events, size_t * n_tokens) {
+    if (!S || !session_begin(S)) return false;
+    rwkv_context * ctx = S->B->ctx;
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, (flags & ~RWKV_MI_POLL_DRAIN) == 0, "unknown bits in flags (0x%" PRIx32 ")", flags);
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, n_events != nullptr && n_tokens != nullptr && (events_out != nullptr || max_events == 0) && (tokens_out != nullptr || max_tokens == 0),
+                 "n_events or n_tokens is NULL, or events_out / tokens_out is NULL with a maximum above 0");
+    SessionBook & book = S->book;
+    // (a busy session whose last block read left no work and no queue has a block of dead passes unread: it is read, not followed by another)
+    const bool enqueue = book.busy() && book.wants_block();
+    if (enqueue && !session_enqueue(S)) return false;
+    const uint64_t upto = ((flags & RWKV_MI_POLL_DRAIN) || !enqueue) ? book.enqueued : book.enqueued - 1;
+    if (!session_consume(S, upto)) return false;
+    book.deliver(events_out, max_events, tokens_out, max_tokens, n_events, n_tokens);
+    return true;
+}
+
+RWKV_API bool rwkv_mi_batch_serve_stats(struct rwkv_mi_serve_session * S, uint64_t * passes, uint64_t * blocks, uint32_t * in_flight, uint32_t * room) {
+    if (!S) return false;
+    S->B->ctx->last_error = RWKV_ERROR_NONE;
+    if (passes) *passes = S->book.passes;
+    if (blocks) *blocks = S->book.enqueued;
+    if (in_flight) *in_flight = S->book.in_flight;
+    if (room) *room = S->book.room();
+    return true;
+}
+
+RWKV_API bool rwkv_mi_batch_serve_close(struct rwkv_mi_serve_session * S, uint32_t * last_request_out) {
+    return S ? session_close(S, last_request_out) : false;
+}
+
 RWKV_API bool rwkv_mi_batch_eval_draft(struct rwkv_mi_batch * B, const uint32_t * slots, const uint32_t * lens, const uint32_t * tokens, size_t n,
                                        const struct rwkv_mi_sample_params * params, const struct rwkv_mi_penalty_params * penalties,
                                        size_t stride, uint32_t * tokens_out, uint32_t * lens_out, float * logits_out) {
@@ -1331,6 +1689,7 @@ RWKV_API bool rwkv_mi_batch_decode_beam(struct rwkv_mi_batch * B, const uint32_t
 
 RWKV_API bool rwkv_mi_batch_set_logprobs(struct rwkv_mi_batch * B, bool enabled, uint32_t top_n) {
     B->ctx->last_error = RWKV_ERROR_NONE;
+    RW_CTX_CHECK(B->ctx, RWKV_ERROR_ARGS, false, B->session == nullptr, "a serve session is open on this batch (it takes no log-prob report)");
     return B->lp.set(B->ctx, enabled, top_n);
 }
 

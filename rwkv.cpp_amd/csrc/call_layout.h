@@ -84,6 +84,51 @@ struct ServeLayout {
     }
 };
 
+// The words of a serve session of n lanes over a ring of `capacity` requests (rwkv_mi_batch_serve_open ..). A RING ENTRY has a fixed size:
+// the request's ServeReq in the dense table reqs[capacity] (k_serve_reset indexes it as it does a call's), and entry_words words in `ring`
+// -- max_prompt prompt tokens, max_seqs sequence lengths, max_seq_tokens sequence tokens, the start state of its guide. Request id q lives
+// in entry q % capacity, and a submit goes up as the bytes of its entry alone, one copy for each of the two tables (reqs_range,
+// words_range). word(e, w) is word w of entry e as a word of the ring, which is what a ServeReq's prompt0, stop.seq0 and stop.tok0 hold.
+// Behind the ring: the cancel words, TWICE -- block b uploads and reads half b & 1, so a copy that is still pending never sees the next
+// block's words -- and the lane words in their start values, which go up once, at open. From `down` on, what a block fetches (all of it,
+// one copy, into the half b & 1 of pinned staging of its own): the queue's head and the work count, the lanes' last ids, then per entry the
+// id it was admitted for, done, length, reason, lane, start pass, end pass, revived, the two guide words (guided sessions) and the emitted
+// tokens out[capacity][stride].
+struct SessionLayout {
+    size_t capacity = 0, entry_words = 0;
+    size_t w_prompt = 0, w_seq_lens = 0, w_seq_tokens = 0, w_guide = 0;   // words of an entry, from its start
+    Field<ServeReq> reqs;
+    Field<uint32_t> ring, cancel, lane_slot, req, pos, draw, admit, g_state, g_misses;
+    size_t down = 0;
+    Field<uint32_t> next, work, last, ids, done, lens, reasons, lane, start, end, revived, req_g_state, req_g_misses, out;
+    size_t bytes = 0;
+    SessionLayout() = default;
+    SessionLayout(size_t n, size_t capacity_, size_t max_prompt, size_t max_seqs, size_t max_seq_tokens, size_t stride, bool guided) : capacity(capacity_) {
+        w_prompt = 0; w_seq_lens = max_prompt; w_seq_tokens = w_seq_lens + max_seqs; w_guide = w_seq_tokens + max_seq_tokens;
+        entry_words = w_guide + 1;
+        LayoutCursor c;
+        const auto words = [&c](size_t count) { return c.take<uint32_t>(count); };
+        const size_t g = guided ? 1 : 0, C = capacity;
+        reqs = c.take<ServeReq>(C);
+        ring = words(C * entry_words);
+        cancel = words(2 * C);
+        lane_slot = words(n); req = words(n); pos = words(n); draw = words(n); admit = words(n);
+        g_state = words(n * g); g_misses = words(n * g);
+        down = c.bytes();
+        next = words(1); work = words(1); last = words(n);
+        ids = words(C); done = words(C); lens = words(C); reasons = words(C); lane = words(C); start = words(C); end = words(C); revived = words(C);
+        req_g_state = words(C * g); req_g_misses = words(C * g);
+        out = words(C * stride);
+        bytes = c.bytes();
+    }
+    size_t entry_of(uint32_t id) const { return (size_t) id % capacity; }
+    size_t word(size_t e, size_t w) const { return e * entry_words + w; }                       // words, of the ring
+    // the bytes the entries [e0, e1) go up as: their ServeReqs, their words; and half `half` of the cancel words
+    void reqs_range(size_t e0, size_t e1, size_t * from, size_t * to) const { *from = reqs.off + e0 * sizeof(ServeReq); *to = reqs.off + e1 * sizeof(ServeReq); }
+    void words_range(size_t e0, size_t e1, size_t * from, size_t * to) const { *from = ring.off + word(e0, 0) * sizeof(uint32_t); *to = ring.off + word(e1, 0) * sizeof(uint32_t); }
+    Field<uint32_t> cancel_half(size_t half) const { return Field<uint32_t>{cancel.off + half * capacity * sizeof(uint32_t), capacity}; }
+};
+
 // The beam words of `rows` rows (rwkv_mi_batch_decode_beam): scores, finished words, lengths, the live count with its pad word -- up to
 // `upload`, the part a call uploads; what lies in front of count comes back -- then the candidates' ids and log-probs
 // [rows][RWKV_MI_TOP_MAX] and the body's unused word per row, which never leave the device.

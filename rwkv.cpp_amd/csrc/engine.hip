@@ -868,6 +868,15 @@ void launch_row_sampler(rwkv_context * ctx, const RowSampler & s, int64_t rows) 
         launch_serve_reset(sv->t, rows, sv->chunks, s.used, sv->state_len, ctx->stream);
         return;
     }
+    if (const RowSession * ss = s.session) {
+        // a step of a serve session: the family's choice behind the lanes' draw words, the session's scheduler, the admissions it decided
+        const ServeTables & t = ss->s.t;
+        if (s.form.draw != Draw::none) launch_draw_rows(logits, rows, n_vocab, s.rows, s.form, s.probs, tokens, nullptr, t.draw, ctx->stream);
+        else launch_argmax_live(logits, rows, n_vocab, tokens, nullptr, t.draw, ctx->stream);
+        launch_session_rows(ss->s, rows, tokens, s.step, s.used, s.other, ctx->stream);
+        launch_serve_reset(t, rows, ss->chunks, s.used, ss->state_len, ctx->stream);
+        return;
+    }
     const size_t at = (size_t) s.step * (size_t) rows;   // the step's slot of the call's history and report buffers
     uint32_t * hist = s.hist ? s.hist + at : nullptr;
     const uint32_t * live = s.stop ? s.stop->live : nullptr;   // (rwkv_mi_batch_decode_until: everything but the stop test runs behind the live words)

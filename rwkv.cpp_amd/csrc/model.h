@@ -189,6 +189,26 @@ void launch_serve_rows(const ServeTables & t, int64_t n, uint32_t * tokens, uint
 // Behind it: lanes x chunks workgroups; those of an admitted lane copy the request's start state into used[lane].out -- the buffer the lane's
 // next pass reads -- and zero its occurrence row
 void launch_serve_reset(const ServeTables & t, int64_t n, unsigned chunks, const RowState * used, int64_t state_len, hipStream_t st);
+// A serve session (rwkv_mi_batch_serve_open ..; sampling.hip, k_session_rows): the same tables with the queue a RING of `capacity` entries
+// (call_layout.h, SessionLayout). Request id q lives in entry q % capacity; t.req[r] holds the lane's ENTRY (SESSION_IDLE: the lane has no
+// request and waits for one), t.last[r] the ID of the last request it was given; the per-request words of t are indexed by entry, and
+// t.prompts == t.seq_lens == t.seq_tokens is the ring as words (a ServeReq's prompt0 / seq0 / tok0 are word offsets into it). tail: the ids
+// below it have been uploaded -- a kernel argument, so a request is visible from the block whose launches carry it. cancel[entry]: the
+// request is to retire (the half of the cancel words this block's upload wrote). Per entry, beside t's: the id the entry was admitted for
+// (the host trusts an entry's words when it is the id it submitted there), done (1 from its retirement on), the pass after which it
+// retired, and revived (1: its lane was idle when it took it). entry_words / guide_word: the words of a ring entry and where a guided
+// request's start state lies in it. admit_only: the launch stands in front of a block's first pass and only hands requests to idle lanes.
+constexpr uint32_t SESSION_IDLE = 0xFFFFFFFFu;
+struct SessionTables {
+    ServeTables t;
+    uint32_t capacity, tail;
+    const uint32_t * cancel;
+    uint32_t * ids, * done, * end_pass, * revived;
+    uint32_t entry_words, guide_word;
+    uint32_t admit_only;
+};
+// As launch_serve_rows; launch_serve_reset follows it unchanged (t.reqs[t.req[r]] is the ring entry).
+void launch_session_rows(const SessionTables & s, int64_t n, uint32_t * tokens, uint32_t step, RowState * used, RowState * other, hipStream_t st);
 // rwkv_mi_batch_decode_beam (score.hip): the device words of a call of G groups of `width` hypotheses, row g * width + j = hypothesis j of group g.
 // Per row its cumulative score (double), its finished word, its length; the candidates of the step -- cand_ids / cand_lp [rows][width], the
 // report's top-`width` of the row's logits -- and the word the shared body writes its unused `chosen` to; the history [steps][rows] of emitted
@@ -458,8 +478,10 @@ void batch_context_destroy(rwkv_context * c);
 //           of the rest only `step`, `used` and `other` are read
 //   serve   the pass is a step of rwkv_mi_batch_serve: the choice runs behind the lanes' draw words and writes no history; launch_serve_rows and
 //           launch_serve_reset (`chunks` workgroups per lane over state_len floats) follow it
+//   session the pass is a step of a serve session: as serve, without a report, launch_session_rows in the scheduler's place
 // Order within a step: the choice, then the report of what it wrote, then the stop test.
 struct RowServe { ServeTables t; int64_t state_len; unsigned chunks; };
+struct RowSession { SessionTables s; int64_t state_len; unsigned chunks; };
 struct RowSampler {
     DrawForm form;
     const DrawRow * rows = nullptr;
@@ -471,6 +493,7 @@ struct RowSampler {
     const StopTables * stop = nullptr;
     const BeamTables * beam = nullptr;
     const RowServe * serve = nullptr;
+    const RowSession * session = nullptr;
 };
 void launch_row_sampler(rwkv_context * ctx, const RowSampler & s, int64_t rows);
 // sample: when given, launch_row_sampler follows the head inside the pass's place in the chain

@@ -672,6 +672,130 @@ __global__ __launch_bounds__(1024) void k_serve_rows(ServeTables t, int n, uint3
     }
 }
 
+// The scheduler of a serve session (model.h, SessionTables): k_serve_rows with the queue a ring that the host keeps filling, ONE workgroup,
+// thread tid on lane base + tid, after the draw of pass `step`. What differs:
+//   the ring   the lane's word t.req[r] is the ENTRY of its request, id % capacity, and every per-request word is indexed by it; ids are
+//              handed out from next_request while they are below `tail`, the kernel argument that says how far the host has uploaded;
+//   idle       a lane the queue has nothing for is IDLE, not dead: its two row-table entries become {in = F, out = G} ONCE, when its request
+//              retires with nothing to take, and it stays a candidate of every later step. An admission to an idle lane restores the
+//              mirror (other[r] = {G, F}); k_serve_reset then copies the start state into used[r].out = G, which the next pass reads;
+//   cancel     a request whose cancel word is set retires with RWKV_MI_STOP_CANCELLED at the step after any of its passes, unless that
+//              pass drew a token that ends it by itself (the token is appended and the natural end tested first); in its prompt phase it
+//              retires with length 0;
+//   admit_only the launch in front of a block's first pass: lanes that have a request are not looked at, idle ones take what has arrived.
+// A retirement leaves done = 1 and the pass; an admission the id, done = 0, length 0, lane, start pass and whether the lane was idle. Thread 0
+// leaves the new head of the queue and the number of lanes that have a request, with ordinary stores.
+template <bool DRAWS>
+__global__ __launch_bounds__(1024) void k_session_rows(SessionTables s, int n, uint32_t * __restrict__ tokens, uint32_t step, RowState * used, RowState * other) {
+    __shared__ uint32_t l_free[16], l_work[16];
+    const ServeTables & t = s.t;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, waves = blockDim.x >> 6;
+    uint32_t next = *t.next_request, work = 0u;
+    for (int base = 0; base < n; base += blockDim.x) {
+        const int r = base + tid;
+        const bool in = r < n;
+        const uint32_t e = in ? t.req[r] : SESSION_IDLE;
+        const bool had = e != SESSION_IDLE;
+        bool retired = false;
+        if (had && !s.admit_only) {
+            const ServeReq & rq = t.reqs[e];
+            const bool cancelled = s.cancel[e] != 0u;
+            bool ended = false;
+            if (t.draw[r]) {
+                uint32_t len = t.lens[e];
+                uint32_t * o = t.out + (size_t) e * t.stride;
+                if (len < t.stride) o[len] = tokens[r];
+                len++;
+                const uint32_t * sl = t.seq_lens + rq.stop.seq0;
+                const uint32_t * tk = t.seq_tokens + rq.stop.tok0;
+                uint32_t reason = RWKV_MI_NO_TOKEN;
+                for (uint32_t q = 0; q < rq.stop.n_seqs && reason == RWKV_MI_NO_TOKEN; q++) {
+                    const uint32_t L = sl[q];
+                    bool match = L <= len;   // (the window is the request's own tokens only)
+                    for (uint32_t k = 0; match && k < L; k++) match = o[len - L + k] == tk[k];
+                    if (match) reason = q;
+                    tk += L;
+                }
+                t.lens[e] = len;
+                if (reason != RWKV_MI_NO_TOKEN || len >= rq.stop.max_tokens) { t.reasons[e] = reason; ended = true; }
+            } else if (!cancelled) {
+                const uint32_t pos = t.pos[r];
+                tokens[r] = t.prompts[rq.prompt0 + pos];
+                t.pos[r] = pos + 1u;
+                if (pos + 1u == rq.prompt_len) t.draw[r] = 1u;
+            }
+            if (!ended && cancelled) { t.reasons[e] = RWKV_MI_STOP_CANCELLED; ended = true; }
+            if (ended) {
+                if constexpr (DRAWS) {
+                    if (t.guide_state && rq.row.next) { t.req_guide_state[e] = t.guide_state[r]; t.req_guide_misses[e] = t.guide_misses[r]; }
+                }
+                s.end_pass[e] = step; s.done[e] = 1u;
+                retired = true;
+            }
+        }
+        const bool is_free = in && (!had || retired);
+        const unsigned long long m = __ballot(is_free);
+        uint32_t rank = (uint32_t) __popcll(m & ((1ull << lane) - 1ull));
+        __syncthreads();   // (the chunk before has read the words)
+        if (lane == 0) l_free[wave] = (uint32_t) __popcll(m);
+        __syncthreads();
+        uint32_t total = 0u;
+        for (int w = 0; w < waves; w++) { if (w < wave) rank += l_free[w]; total += l_free[w]; }
+        bool alive = had && !retired;
+        if (in) t.admit[r] = 0u;
+        if (is_free) {
+            const uint32_t qn = next + rank;
+            if (qn < s.tail) {
+                const uint32_t en = qn % s.capacity;
+                const ServeReq & rq = t.reqs[en];
+                const uint32_t slot = t.lane_slot[r];
+                t.req[r] = en; t.last[r] = qn; t.pos[r] = 1u;
+                tokens[r] = t.prompts[rq.prompt0];
+                t.draw[r] = rq.prompt_len == 1u ? 1u : 0u;
+                t.lane[en] = (uint32_t) r; t.start_pass[en] = step + 1u;
+                t.lens[en] = 0u; t.reasons[en] = RWKV_MI_NO_TOKEN;
+                s.ids[en] = qn; s.done[en] = 0u; s.revived[en] = had ? 0u : 1u;
+                t.counters[slot] = 0ull;
+                if constexpr (DRAWS) {
+                    DrawRow * row = t.rows + r;   // (the request's row, then the words that are the lane's: k_serve_rows' admission)
+                    *row = rq.row;
+                    row->counter = t.counters + slot;
+                    if (rq.row.record) row->count = t.counts + (size_t) slot * t.n_vocab;
+                    if (t.guide_state) {   // (the entry's words back are an unguided request's 0 and 0 until a guided one retires)
+                        t.req_guide_state[en] = 0u; t.req_guide_misses[en] = 0u;
+                        if (rq.row.next) {
+                            row->state = t.guide_state + r; row->misses = t.guide_misses + r;
+                            t.guide_state[r] = t.prompts[(size_t) en * s.entry_words + s.guide_word]; t.guide_misses[r] = 0u;
+                        }
+                    }
+                }
+                if (!had) {   // (idle: both entries are {F, G}; the pass that follows runs on `other` and has to read G)
+                    const RowState u = used[r];
+                    other[r] = RowState{u.out, const_cast<float *>(u.in)};
+                }
+                t.admit[r] = 1u;
+                alive = true;
+            } else if (had) {
+                t.req[r] = SESSION_IDLE; t.draw[r] = 0u;
+                const RowState u = used[r];
+                const RowState idle{u.out, const_cast<float *>(u.in)};
+                used[r] = idle;
+                other[r] = idle;
+            }
+        }
+        next = next + total < s.tail ? next + total : s.tail;
+        work += (uint32_t) __popcll(__ballot(alive));
+    }
+    if (lane == 0) l_work[wave] = work;
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t w_all = 0u;
+        for (int w = 0; w < waves; w++) w_all += l_work[w];
+        *t.next_request = next;
+        *t.work = w_all;
+    }
+}
+
 // The admissions of the pass, grid = lanes x chunks: a workgroup whose lane's admit word is 0 returns at once, all of it together. The others
 // stream the request's start state -- a from_slot's current buffer or the batch's fresh state: one path -- into used[r].out, the buffer the
 // lane's next pass reads (a live lane's two row tables mirror each other) and zero the lane's occurrence row. VEC: 16 bytes per load and
@@ -804,6 +928,12 @@ void launch_serve_rows(const ServeTables & t, int64_t n, uint32_t * tokens, uint
     const unsigned threads = n >= 1024 ? 1024u : (unsigned) ((n + 63) / 64) * 64u;
     if (t.rows) hipLaunchKernelGGL(k_serve_rows<true>, dim3(1), dim3(threads), 0, st, t, (int) n, tokens, step, used, other);
     else hipLaunchKernelGGL(k_serve_rows<false>, dim3(1), dim3(threads), 0, st, t, (int) n, tokens, step, used, other);
+}
+
+void launch_session_rows(const SessionTables & s, int64_t n, uint32_t * tokens, uint32_t step, RowState * used, RowState * other, hipStream_t st) {
+    const unsigned threads = n >= 1024 ? 1024u : (unsigned) ((n + 63) / 64) * 64u;
+    if (s.t.rows) hipLaunchKernelGGL(k_session_rows<true>, dim3(1), dim3(threads), 0, st, s, (int) n, tokens, step, used, other);
+    else hipLaunchKernelGGL(k_session_rows<false>, dim3(1), dim3(threads), 0, st, s, (int) n, tokens, step, used, other);
 }
 
 void launch_serve_reset(const ServeTables & t, int64_t n, unsigned chunks, const RowState * used, int64_t state_len, hipStream_t st) {

@@ -105,6 +105,25 @@ class ServeExtra(ctypes.Structure):
 
 P_SERVE_EXTRA = ctypes.POINTER(ServeExtra)
 
+SESSION_SYMBOLS = ("rwkv_mi_batch_serve_open", "rwkv_mi_batch_serve_submit", "rwkv_mi_batch_serve_cancel", "rwkv_mi_batch_serve_poll",
+                   "rwkv_mi_batch_serve_stats", "rwkv_mi_batch_serve_close")
+STOP_CANCELLED = 0xFFFFFFFE                            # RWKV_MI_STOP_CANCELLED: stopped_by of a request that was cancelled
+SERVE_CUT, SERVE_REP, SERVE_GUIDED = 1, 2, 4           # RWKV_MI_SERVE_*: the features of a serve session
+POLL_DRAIN = 1                                         # RWKV_MI_POLL_DRAIN
+
+
+class ServeLimits(ctypes.Structure):
+    """struct rwkv_mi_serve_limits (include/rwkv_mi355x.h): the ring and the per-request limits of a serve session, 28 bytes."""
+    _fields_ = [("capacity", ctypes.c_uint32), ("max_prompt", ctypes.c_uint32), ("stride", ctypes.c_uint32), ("max_seqs", ctypes.c_uint32),
+                ("max_seq_tokens", ctypes.c_uint32), ("features", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class ServeEvent(ctypes.Structure):
+    """struct rwkv_mi_serve_event (include/rwkv_mi355x.h): what a poll of a serve session delivers for one request, 36 bytes."""
+    _fields_ = [("id", ctypes.c_uint32), ("first", ctypes.c_uint32), ("n_new", ctypes.c_uint32), ("finished", ctypes.c_uint32),
+                ("stopped_by", ctypes.c_uint32), ("lane", ctypes.c_uint32), ("start_pass", ctypes.c_uint32), ("guide_state", ctypes.c_uint32),
+                ("guide_misses", ctypes.c_uint32)]
+
 
 class CutParams(ctypes.Structure):
     """struct rwkv_mi_test_cut (include/rwkv_testhooks_cut.h): one row's truncation setting as the test hook takes it, 8 bytes."""
@@ -317,6 +336,19 @@ class RWKVSharedLibrary:
         if hasattr(L, "rwkv_mi_batch_serve_ex"):   # (absent from older A/B builds loaded through RWKV_LIB_DIR)
             L.rwkv_mi_batch_serve_ex.argtypes = list(L.rwkv_mi_batch_serve.argtypes) + [P_SERVE_EXTRA, P_UINT32, P_UINT32]
             L.rwkv_mi_batch_serve_ex.restype = ctypes.c_bool
+        # serve sessions: the same loop kept open between host calls
+        if hasattr(L, "rwkv_mi_batch_serve_open"):   # (absent from older A/B builds loaded through RWKV_LIB_DIR)
+            c_session = ctypes.c_void_p
+            P_SIZE_T = ctypes.POINTER(ctypes.c_size_t)
+            L.rwkv_mi_batch_serve_open.argtypes = [c_batch, P_UINT32, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(ServeLimits)]
+            L.rwkv_mi_batch_serve_open.restype = c_session
+            L.rwkv_mi_batch_serve_submit.argtypes = [c_session, P_SERVE_REQUEST, P_UINT32, P_UINT32, P_UINT32, P_SERVE_EXTRA, P_UINT32]
+            L.rwkv_mi_batch_serve_cancel.argtypes = [c_session, ctypes.c_uint32]
+            L.rwkv_mi_batch_serve_poll.argtypes = [c_session, ctypes.c_uint32, ctypes.POINTER(ServeEvent), ctypes.c_size_t, P_UINT32, ctypes.c_size_t, P_SIZE_T, P_SIZE_T]
+            L.rwkv_mi_batch_serve_stats.argtypes = [c_session, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), P_UINT32, P_UINT32]
+            L.rwkv_mi_batch_serve_close.argtypes = [c_session, P_UINT32]
+            for name in SESSION_SYMBOLS[1:]:
+                getattr(L, name).restype = ctypes.c_bool
         # the report: log-probs and top-N alternatives of every emitted token
         if hasattr(L, "rwkv_mi_batch_set_logprobs"):   # (absent from older A/B builds loaded through RWKV_LIB_DIR)
             P_SIZE = ctypes.POINTER(ctypes.c_size_t)
@@ -959,6 +991,95 @@ def _bias_arrays(bias: dict):
     return ids, values
 
 
+class ServeSession:
+    """A serve session of a RWKVBatch (rwkv_mi_batch_serve_open ..; RWKVBatch.serve_open creates it). submit(**request) takes the keys of
+    serve_requests and serve_extras and returns the request's id; poll() enqueues one block of passes when there is work and returns what
+    the blocks before it emitted; cancel(id) drops a request; close() cancels what is in flight and hands the batch back. Every request's
+    tokens are what it gives alone, whenever it was submitted."""
+
+    def __init__(self, batch: "RWKVBatch", lanes: List[int], family: int, limits: ServeLimits) -> None:
+        self._batch = batch
+        self._L = batch._L
+        self._ptr = None
+        s = _u32(lanes).reshape(-1)
+        self.n_lanes = int(s.size)
+        self.limits = limits
+        ptr = self._L.rwkv_mi_batch_serve_open(batch._ptr, s.ctypes.data_as(P_UINT32), s.size, int(family), ctypes.byref(limits))
+        if not ptr:
+            batch._fail("rwkv_mi_batch_serve_open")
+        self._ptr = ptr
+        batch._session = self
+        self.last_request = None
+        self._events = (ServeEvent * max(int(limits.capacity), 1))()
+        self._tokens = np.empty(max(int(limits.capacity) * int(limits.stride), 1), dtype=np.uint32)
+
+    def _open(self):
+        if not self._ptr:
+            raise ValueError("the session is closed")
+
+    def submit(self, **request) -> int:
+        """One request (prompt, max_tokens, and the optional keys of serve_requests / serve_extras); a misspelt key raises. Returns its id."""
+        self._open()
+        arr, prompts, seq_lens, seq_tokens = serve_requests([request])
+        extras = serve_extras([request])
+        rid = ctypes.c_uint32(0)
+        if not self._L.rwkv_mi_batch_serve_submit(self._ptr, arr, prompts.ctypes.data_as(P_UINT32), seq_lens.ctypes.data_as(P_UINT32),
+                                                  seq_tokens.ctypes.data_as(P_UINT32), extras, ctypes.byref(rid)):
+            self._batch._fail("rwkv_mi_batch_serve_submit")
+        return int(rid.value)
+
+    def cancel(self, rid: int) -> bool:
+        self._open()
+        return bool(self._L.rwkv_mi_batch_serve_cancel(self._ptr, int(rid)))
+
+    def poll(self, drain: bool = False, max_events: Optional[int] = None, max_tokens: Optional[int] = None):
+        """One poll: a list of dict(id, first, tokens, finished, stopped_by, lane, start_pass, guide_state, guide_misses), one per request with
+        new tokens or a newly known end. drain: the block this poll enqueued is waited for as well. max_events / max_tokens bound what one
+        call delivers (the rest comes with the next)."""
+        self._open()
+        me = len(self._events) if max_events is None else min(int(max_events), len(self._events))
+        mt = self._tokens.size if max_tokens is None else min(int(max_tokens), self._tokens.size)
+        ne, nt = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        if not self._L.rwkv_mi_batch_serve_poll(self._ptr, POLL_DRAIN if drain else 0, self._events, me, self._tokens.ctypes.data_as(P_UINT32), mt,
+                                                ctypes.byref(ne), ctypes.byref(nt)):
+            self._batch._fail("rwkv_mi_batch_serve_poll")
+        out, at = [], 0
+        for i in range(ne.value):
+            e = self._events[i]
+            out.append(dict(id=int(e.id), first=int(e.first), tokens=self._tokens[at: at + e.n_new].copy(), finished=bool(e.finished), stopped_by=int(e.stopped_by),
+                            lane=int(e.lane), start_pass=int(e.start_pass), guide_state=int(e.guide_state), guide_misses=int(e.guide_misses)))
+            at += e.n_new
+        return out
+
+    def stats(self):
+        """dict(passes, blocks, in_flight, room): passes and blocks enqueued so far, requests in flight, submits the ring has room for."""
+        self._open()
+        passes, blocks, in_flight, room = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint32(0), ctypes.c_uint32(0)
+        self._L.rwkv_mi_batch_serve_stats(self._ptr, ctypes.byref(passes), ctypes.byref(blocks), ctypes.byref(in_flight), ctypes.byref(room))
+        return dict(passes=int(passes.value), blocks=int(blocks.value), in_flight=int(in_flight.value), room=int(room.value))
+
+    def close(self):
+        """Cancels what is in flight, drains and frees the session; the batch is usable as before. Returns last_request [n_lanes]: the id each
+        lane served last (NO_TOKEN: none)."""
+        if not self._ptr:
+            return self.last_request
+        last = np.empty(self.n_lanes, dtype=np.uint32)
+        ptr, self._ptr = self._ptr, None
+        self._batch._session = None
+        ok = self._L.rwkv_mi_batch_serve_close(ptr, last.ctypes.data_as(P_UINT32))
+        self.last_request = last
+        if not ok:
+            self._batch._fail("rwkv_mi_batch_serve_close")
+        return last
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
 class RWKVBatch:
     """n_slots device-resident sequences of one model advanced together, one pass over the weights per step (rwkv_mi_batch_*).
 
@@ -1256,6 +1377,14 @@ class RWKVBatch:
         return {"tokens": [out[q, : int(lens[q])].copy() for q in range(R)], "stopped_by": why, "lane": lane, "start_pass": start,
                 "last_request": last, "elapsed_ms": float(ms.value), "guide_state": g_state, "guide_misses": g_misses}
 
+    def serve_open(self, lanes: List[int], family: int = SERVE_GREEDY, capacity: int = 16, max_prompt: int = 64, stride: int = 64,
+                   max_seqs: int = STOP_MAX_SEQS, max_seq_tokens: int = STOP_MAX_SEQS * STOP_MAX_LEN, features: int = 0) -> "ServeSession":
+        """A serve session on the slots `lanes`: serve()'s device loop kept open between host calls -- submit requests, poll their tokens as
+        they are emitted, cancel them. capacity: the entries of the request ring (requests in flight); max_prompt, stride (every max_tokens
+        <= stride), max_seqs, max_seq_tokens: per request; features: SERVE_CUT | SERVE_REP | SERVE_GUIDED, what a request may ask for. While
+        the session is open the batch runs no other pass. Use it as a context manager, or close() it."""
+        return ServeSession(self, lanes, family, ServeLimits(int(capacity), int(max_prompt), int(stride), int(max_seqs), int(max_seq_tokens), int(features), 0))
+
     # --- speculative decoding (include/rwkv_mi355x.h) ---
 
     def eval_draft(self, slots: List[int], rows: List[List[int]], params=None, penalties=None, want_logits: bool = False):
@@ -1370,6 +1499,10 @@ class RWKVBatch:
 
     def free(self) -> None:
         if self._ptr:
+            session = getattr(self, "_session", None)
+            if session is not None:
+                session._ptr = None   # (rwkv_mi_batch_free closes it)
+                self._session = None
             self._L.rwkv_mi_batch_free(self._ptr)
             self._ptr = None
 

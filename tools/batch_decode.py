@@ -46,6 +46,10 @@ run, everything in this process and run; records also go to --out:
                         tokens, then rwkv_mi_batch_decode_until until the slowest has ended; host clock around those calls
   mode serve_admission  the mean time of a pass that admits (every lane, every pass: one prompt token, a budget of one) against one that
                         does not (n requests of the same number of passes), and the difference per admission
+--session times the serve session (rwkv_mi_batch_serve_open ..) on the same queue: the whole queue submitted before the first poll against
+serve (modes serve, session_upfront), and the queue revealed in groups of n -- group g + 1 at the poll that delivers the end of half of
+group g -- against one closed serve call per group (modes closed_groups, session_arrivals); both arms emit the same tokens
+(same_tokens_as_serve), and every record of a session carries the bytes it fetches per block and the median host time of a poll.
 --serve --guide and --serve --logprobs N time rwkv_mi_batch_serve_ex on the same queue -- every request under a guide of four states, each
 allowing a random half of the vocabulary, or the batch's report on at top_n N (both flags: both) -- against the same waves with the guide
 attached to the lanes or the report on, the only way to either before that call; no admission record:
@@ -385,6 +389,107 @@ def serve(pkg, m, args):
         emit({"mode": "serve_admission", "n": n, "admitting_passes": steps, "passes": plain_passes, "plain_pass_ms": round(plain_pass, 4),
               "admitting_pass_ms": round(plain_pass + (admit_ms - plain_ms) / steps, 4), "ms_per_admission": round((admit_ms - plain_ms) / (steps * n), 5),
               "state_mb": round(m.state_len * 4 / 1e6, 2)})
+        b.free()
+    if sink:
+        sink.close()
+
+
+def session(pkg, m, args):
+    """--session: the serve session (rwkv_mi_batch_serve_open ..) on the queue of --serve, two arms per n. `session_upfront`: the whole queue
+    submitted before the first poll, against `serve` on the same queue. `session_arrivals`: the queue revealed in groups of n, group g + 1
+    submitted at the poll that delivers the end of half of group g, against one closed `serve` call per group, each after the one before
+    has returned (`closed_groups`). Passes from submit to first token: the pass that draws a request's first token minus the passes
+    enqueued when it was submitted (closed arm: when half of the group before had ended)."""
+    import numpy as np
+    V = m.n_vocab
+    sink = open(args.out, "a") if args.out else None
+
+    def emit(rec):
+        rec.update({"reps": args.reps, "temperature": 1.0, "top_p": 0.8, "config": args.config, "dtype": args.dtype, "loop_block": int(os.environ.get("RWKV_MI_LOOP_BLOCK", 16))})
+        if args.run:
+            rec["run"] = args.run
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if sink:
+            sink.write(line + "\n")
+            sink.flush()
+
+    def best(run):
+        out = [run() for _ in range(args.reps + 1)]   # (run 0: warm-up)
+        return min(out[1:], key=lambda r: r[0])
+
+    for n in [int(x) for x in args.n.split(",")]:
+        R = 4 * n
+        rng = np.random.default_rng(1000 + n)   # the queue of --serve
+        budgets = [int(v) for v in rng.integers(16, 257, R)]
+        prompts = [[int(t) for t in rng.integers(0, V, int(L))] for L in rng.integers(1, 33, R)]
+        reqs = [dict(prompt=prompts[q], max_tokens=budgets[q], temperature=1.0, top_p=0.8, seed=q) for q in range(R)]
+        useful = sum(budgets)
+        lanes = list(range(n))
+        b = pkg.RWKVBatch(m, n)
+        limits = dict(capacity=R, max_prompt=32, stride=256, max_seqs=0, max_seq_tokens=0, features=0)
+        fetch_bytes = 4 * (2 + n + R * (8 + 256))
+
+        def in_session(groups):
+            """groups: lists of request numbers; group g + 1 is submitted at the poll that delivers the end of half of group g"""
+            toks, first_at, submit_at, ended, poll_ms = {}, {}, {}, set(), []
+            t0 = time.perf_counter()
+            with b.serve_open(lanes, pkg.SERVE_SAMPLE, **limits) as s:
+                nxt = 0
+                while len(ended) < R:
+                    while nxt < len(groups) and (nxt == 0 or 2 * len(ended & set(groups[nxt - 1])) >= len(groups[nxt - 1])):
+                        at = s.stats()["passes"]
+                        for q in groups[nxt]:
+                            assert s.submit(**reqs[q]) == len(submit_at)
+                            submit_at[q] = at
+                        nxt += 1
+                    order = [q for g in groups[:nxt] for q in g]   # (id -> request number)
+                    p0 = time.perf_counter()
+                    events = s.poll()
+                    poll_ms.append((time.perf_counter() - p0) * 1e3)
+                    for e in events:
+                        q = order[e["id"]]
+                        toks.setdefault(q, []).extend(e["tokens"].tolist())
+                        first_at.setdefault(q, e["start_pass"] + len(prompts[q]) - 1)
+                        if e["finished"]:
+                            ended.add(q)
+                passes = s.stats()["passes"]
+            host = (time.perf_counter() - t0) * 1e3
+            assert [len(toks[q]) for q in range(R)] == budgets
+            wait = float(np.mean([first_at[q] - submit_at[q] + 1 for q in range(R)]))
+            return host, passes, [toks[q] for q in range(R)], wait, float(np.median(poll_ms)), len(poll_ms)
+
+        def closed(groups):
+            host, base, toks, first_at, submit_at, half = 0.0, 0, {}, {}, {}, 0
+            for g in groups:
+                t0 = time.perf_counter()
+                got = b.serve(lanes, [reqs[q] for q in g], pkg.SERVE_SAMPLE)
+                host += (time.perf_counter() - t0) * 1e3
+                ends = []
+                for i, q in enumerate(g):
+                    toks[q] = got["tokens"][i].tolist()
+                    submit_at[q] = half
+                    first_at[q] = base + int(got["start_pass"][i]) + len(prompts[q]) - 1
+                    ends.append(base + int(got["start_pass"][i]) + len(prompts[q]) - 1 + len(toks[q]))
+                half = sorted(ends)[(len(g) + 1) // 2 - 1]   # the passes enqueued when half of this group had ended: the next group exists from then on
+                base += b.last_loop_passes()
+            wait = float(np.mean([first_at[q] - submit_at[q] + 1 for q in range(R)]))
+            return host, base, [toks[q] for q in range(R)], wait
+
+        whole, groups = [list(range(R))], [list(range(g, g + n)) for g in range(0, R, n)]
+        s_host, s_passes, s_toks, s_wait = best(lambda: closed(whole))
+        u_host, u_passes, u_toks, u_wait, u_poll, u_polls = best(lambda: in_session(whole))
+        emit({"mode": "serve", "n": n, "requests": R, "useful_tokens": useful, "total_ms": round(s_host, 3), "passes": s_passes, "useful_tokens_per_s": round(useful / s_host * 1e3, 1)})
+        emit({"mode": "session_upfront", "n": n, "requests": R, "useful_tokens": useful, "total_ms": round(u_host, 3), "passes": u_passes,
+              "useful_tokens_per_s": round(useful / u_host * 1e3, 1), "session_over_serve": round(u_host / s_host, 4), "same_tokens_as_serve": bool(u_toks == s_toks),
+              "fetch_bytes_per_block": fetch_bytes, "poll_ms_median": round(u_poll, 4), "polls": u_polls})
+        c_host, c_passes, c_toks, c_wait = best(lambda: closed(groups))
+        a_host, a_passes, a_toks, a_wait, a_poll, a_polls = best(lambda: in_session(groups))
+        emit({"mode": "closed_groups", "n": n, "requests": R, "groups": len(groups), "useful_tokens": useful, "total_ms": round(c_host, 3), "passes": c_passes,
+              "useful_tokens_per_s": round(useful / c_host * 1e3, 1), "passes_to_first_token": round(c_wait, 2), "same_tokens_as_serve": bool(c_toks == s_toks)})
+        emit({"mode": "session_arrivals", "n": n, "requests": R, "groups": len(groups), "useful_tokens": useful, "total_ms": round(a_host, 3), "passes": a_passes,
+              "useful_tokens_per_s": round(useful / a_host * 1e3, 1), "passes_to_first_token": round(a_wait, 2), "same_tokens_as_serve": bool(a_toks == s_toks),
+              "closed_over_session": round(c_host / a_host, 3), "fetch_bytes_per_block": fetch_bytes, "poll_ms_median": round(a_poll, 4), "polls": a_polls})
         b.free()
     if sink:
         sink.close()
@@ -901,6 +1006,8 @@ def main():
     ap.add_argument("--ragged", action="store_true", help="time the ragged pass: prompt ingestion and joining a decode step (see above)")
     ap.add_argument("--until", action="store_true", help="time rwkv_mi_batch_decode_until against the plain sampled loop (see above)")
     ap.add_argument("--serve", action="store_true", help="time rwkv_mi_batch_serve on a fixed queue of 4 n requests against the same queue in waves of decode_until; with --guide and / or --logprobs N: rwkv_mi_batch_serve_ex with every request guided, the report on (see above)")
+    ap.add_argument("--session", action="store_true", help="time the serve session on the queue of --serve: the whole queue up front against serve, and arrivals in groups of n against one closed serve call per group")
+    ap.add_argument("--run", default=None, help="--session: an identifier of this process run, written into every record")
     ap.add_argument("--logprobs", default=None, metavar="N[,N...]",
                     help="with --sample: time the sampled loop with and without the report of the emitted tokens, for each top_n of the list (see above)")
     ap.add_argument("--beam", default=None, metavar="W[,W...]",
@@ -940,6 +1047,10 @@ def main():
         return
     if args.until:
         until(pkg, m, args)
+        m.free()
+        return
+    if args.session:
+        session(pkg, m, args)
         m.free()
         return
     if args.serve:

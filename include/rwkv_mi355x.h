@@ -143,7 +143,9 @@ RWKV_API uint32_t rwkv_mi_decode_generation(struct rwkv_context * ctx);
  * Each row of a call is bit-identical to rwkv_eval of that sequence alone. A call reads each named slot's current buffer, writes the
  * other one and flips the slot's parity only when the pass succeeded; slots not named are untouched. A call returns false with
  * RWKV_ERROR_ARGS and changes no slot when n == 0, n > n_slots, a slot index is out of range or repeated, or a token is >= n_vocab.
- * On a device that also runs a persistent decode kernel, batch passes and persistent launches are ordered on the device, never concurrent. */
+ * On a device that also runs a persistent decode kernel, batch passes and persistent launches are ordered on the device, never concurrent.
+ * Passes of 2 .. 31 rows run their quantised products on the matrix cores (k_mmq_rows, csrc/rows_mm.hip), the same bits as before;
+ * RWKV_MI_ROWS_MM=tn (read once per process) keeps them on the token-tiled VALU kernel, for A/B timing. */
 struct rwkv_mi_batch;
 RWKV_API struct rwkv_mi_batch * rwkv_mi_batch_create(struct rwkv_context * ctx, size_t n_slots);
 RWKV_API void rwkv_mi_batch_free(struct rwkv_mi_batch * batch);

@@ -273,6 +273,8 @@ bool ensure_scratch(rwkv_context * ctx, int64_t T) {
     const size_t n_D = 3 + 6 + 6 + 3 + 1 + 1;  // x xn sx | m[6] | r k v g w a | t0 t1 t2 | out | v_first
     size_t total = n_D * fsz(D) + fsz(F) + 2 * fsz(LR) + align_up(D * sizeof(float), 256);
     total += align_up((size_t) T * KQ, 256) + 3 * align_up((size_t) T * (KQ / 32) * 4, 256);
+    const size_t TR = (size_t) (T < k_mfma_min_tokens ? T : k_mfma_min_tokens - 1);   // qa_more: only passes below k_mfma_min_tokens tokens use it
+    total += 3 * (align_up(TR * D, 256) + 3 * align_up(TR * (D / 32) * 4, 256));
     constexpr size_t k_ws_part = (size_t) 16 << 20;   // split-walk partial sums: up to 64 tiles x 8 parts x 32 KiB
     constexpr int    k_ws_counters = 1024;
     if (T >= k_mfma_min_tokens) total += align_up(tile_act_bytes(T, (int64_t) KQ), 256) + 5 * align_up(tile_act_bytes(T, (int64_t) D), 256) + k_ws_part + k_ws_counters * sizeof(int);
@@ -293,6 +295,12 @@ bool ensure_scratch(rwkv_context * ctx, int64_t T) {
     b.qa.d = (float *) p; p += align_up((size_t) T * (KQ / 32) * 4, 256);
     b.qa.s = (float *) p; p += align_up((size_t) T * (KQ / 32) * 4, 256);
     b.qa.isum = (int *) p; p += align_up((size_t) T * (KQ / 32) * 4, 256);
+    for (QAct & q : b.qa_more) {
+        q.q = (int8_t *) p; p += align_up(TR * D, 256);
+        q.d = (float *) p; p += align_up(TR * (D / 32) * 4, 256);
+        q.s = (float *) p; p += align_up(TR * (D / 32) * 4, 256);
+        q.isum = (int *) p; p += align_up(TR * (D / 32) * 4, 256);
+    }
     b.tile = nullptr;
     b.ws = MmqWs();
     for (int i = 0; i < 5; i++) b.tiles[i] = nullptr;
@@ -440,6 +448,15 @@ struct Runner {
             if (!ta || Ws[i]->type != Ws[0]->type || Ws[i]->rows() != Ws[0]->rows() || Ws[i]->cols() != Ws[0]->cols()) batched = false; else tas[i] = *ta;
         }
         if (batched && launch_mmq_mfma_batched(n, Ws, tas, ys, epis, T, Ws[0]->rows(), &b.ws, st)) return;
+        // 2 .. 31 tokens (batched decode): the inputs are quantised one by one into their own regions, the products are one k_mmq_rows launch
+        bool rows = n <= ROWS_MM_BATCH && mmq_rows_admits(Ws[0]->type, T, Ws[0]->cols()) && Ws[0]->cols() == D && !ctx->prof.on;
+        for (int i = 1; i < n && rows; i++) rows = Ws[i]->type == Ws[0]->type && Ws[i]->rows() == Ws[0]->rows() && Ws[i]->cols() == Ws[0]->cols();
+        if (rows) {
+            QAct qs[ROWS_MM_BATCH];
+            for (int i = 0; i < n; i++) { qs[i] = i == 0 ? b.qa : b.qa_more[i - 1]; launch_quantize_act(xs[i], T, D, qs[i], st); }
+            launch_mmq_rows(n, Ws, qs, ys, epis, T, Ws[0]->rows(), st);
+            return;
+        }
         for (int i = 0; i < n; i++) mm(Ws[i], xs[i], ys[i], epis[i]);
     }
 

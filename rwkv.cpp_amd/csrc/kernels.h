@@ -47,6 +47,13 @@ extern std::atomic<unsigned long long> g_mmfx_launches;    // launches of the ex
 extern std::atomic<unsigned long long> g_mmf16_launches;   // launches of the F16 matrix-core sequence kernel so far (test hook reads it)
 void matvec_f_release_stream(hipStream_t st);   // frees the split-K workspace kept for this stream (a context's own stream, at its destruction)
 
+// rows_mm.hip, k_mmq_rows: the same product for 2 <= T < k_mfma_min_tokens on the matrix cores, bit-identical to the single-token kernel per token; up
+// to ROWS_MM_BATCH products of one shape and type per launch. launch_matvec_q takes it when mmq_rows_admits says so (RWKV_MI_ROWS_MM=tn: never).
+constexpr int ROWS_MM_BATCH = 4;
+bool mmq_rows_admits(int wtype, int64_t T, int64_t K);
+void launch_mmq_rows(int n, const DevTensor * const * Ws, const QAct * xs, float * const * ys, const Epi * epis, int64_t T, int64_t ldy, hipStream_t st);
+extern std::atomic<unsigned long long> g_mmq_rows_launches;   // launches of k_mmq_rows so far (test hook reads it)
+
 // x[T][K] f32 -> QAct
 void launch_quantize_act(const float * x, int64_t T, int64_t K, const QAct & out, hipStream_t st);
 

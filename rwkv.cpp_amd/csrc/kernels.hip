@@ -77,7 +77,8 @@ __global__ __launch_bounds__(256) void k_mvq_t1(const uint8_t * __restrict__ qs,
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Projection, quantised weights, token tile (sequence mode). Each weight block is unpacked once and used for TT tokens;
+// Projection, quantised weights, token tile. Since k_mmq_rows (rows_mm.hip) takes every quantised product of 2 .. 31 tokens, this kernel
+// runs only under RWKV_MI_ROWS_MM=tn (A/B, tests). Each weight block is unpacked once and used for TT tokens;
 // the activation tile of the current K-step (64 blocks x TT tokens) is staged in LDS in a lane-linear, conflict-free
 // image [tt][half][lane][16 B]. Per (row, token) the accumulation order equals k_mvq_t1's.
 // ---------------------------------------------------------------------------------------------------------------
@@ -165,6 +166,11 @@ static void launch_mvq_fmt(const DevTensor & W, const QAct & x, int64_t T, float
 }
 
 void launch_matvec_q(const DevTensor & W, const QAct & x, int64_t T, float * y, int64_t ldy, const Epi & epi, hipStream_t st) {
+    if (mmq_rows_admits(W.type, T, W.cols())) {     // 2 .. 31 tokens: k_mmq_rows (rows_mm.hip), the same bits on the matrix cores
+        const DevTensor * w = &W;
+        launch_mmq_rows(1, &w, &x, &y, &epi, T, ldy, st);
+        return;
+    }
     switch (W.type) {
         case T_Q4_0: launch_mvq_fmt<T_Q4_0>(W, x, T, y, ldy, epi, st); break;
         case T_Q4_1: launch_mvq_fmt<T_Q4_1>(W, x, T, y, ldy, epi, st); break;

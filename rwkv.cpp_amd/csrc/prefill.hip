@@ -21,6 +21,8 @@
 // needs a stack of only six partial sums per output (plus the running leaf): after leaf number c, as many merges as c has
 // trailing one bits. Every output element therefore sees exactly the additions of the single-token kernel, in the same order.
 // Leaves without blocks (l >= K/32) are +0.0 there (acc + 0 is the identity on these values) and +0.0 here.
+// (Below k_mfma_min_tokens = 32 tokens the same tree is kept another way: k_mmq_rows, rows_mm.hip, gives each of four waves the subtree
+// l & 3 == wave as 16 accumulators and walks K in plain order on the decode layout.)
 //
 // Memory. A depth-first walk touches blocks 0, 64, ..., 32, 96, ...: in the row-major planes of the decode path that is one
 // 16-byte piece per 128-byte line and eight fetches of every line. The GEMM reads a second image of the matrix instead

@@ -145,7 +145,10 @@ RWKV_API uint32_t rwkv_mi_decode_generation(struct rwkv_context * ctx);
  * RWKV_ERROR_ARGS and changes no slot when n == 0, n > n_slots, a slot index is out of range or repeated, or a token is >= n_vocab.
  * On a device that also runs a persistent decode kernel, batch passes and persistent launches are ordered on the device, never concurrent.
  * Passes of 2 .. 31 rows run their quantised products on the matrix cores (k_mmq_rows, csrc/rows_mm.hip), the same bits as before;
- * RWKV_MI_ROWS_MM=tn (read once per process) keeps them on the token-tiled VALU kernel, for A/B timing. */
+ * RWKV_MI_ROWS_MM=tn (read once per process) keeps them on the token-tiled VALU kernel, for A/B timing.
+ * Passes of 5 .. 31 rows run their F16 / F32 products (the head, every matrix of an FP16 / FP32 file, RWKV-7's low-rank stages) on the matrix
+ * cores too, one pass over the weights (k_mmf_rows, csrc/rows_mf.hip), the same bits as before; RWKV_MI_ROWS_MF=valu (read once per process)
+ * keeps them on k_mvf's token tiles of four, for A/B timing. */
 struct rwkv_mi_batch;
 RWKV_API struct rwkv_mi_batch * rwkv_mi_batch_create(struct rwkv_context * ctx, size_t n_slots);
 RWKV_API void rwkv_mi_batch_free(struct rwkv_mi_batch * batch);

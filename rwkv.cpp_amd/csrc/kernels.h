@@ -54,6 +54,12 @@ bool mmq_rows_admits(int wtype, int64_t T, int64_t K);
 void launch_mmq_rows(int n, const DevTensor * const * Ws, const QAct * xs, float * const * ys, const Epi * epis, int64_t T, int64_t ldy, hipStream_t st);
 extern std::atomic<unsigned long long> g_mmq_rows_launches;   // launches of k_mmq_rows so far (test hook reads it)
 
+// rows_mf.hip, k_mmf_rows: the F16 / F32 product for 4 < T < k_mfma_min_tokens on the matrix cores, one pass over the weights, bit-identical to k_mvf
+// per token. launch_matvec_f takes it when mmf_rows_admits says so (RWKV_MI_ROWS_MF=valu: never).
+bool mmf_rows_admits(int wtype, int64_t T, int64_t K, int64_t ldx);
+void launch_mmf_rows(const DevTensor & W, const float * x, int64_t ldx, int64_t T, float * y, int64_t ldy, const Epi & epi, hipStream_t st);
+extern std::atomic<unsigned long long> g_mmf_rows_launches;   // launches of k_mmf_rows so far (test hook reads it)
+
 // x[T][K] f32 -> QAct
 void launch_quantize_act(const float * x, int64_t T, int64_t K, const QAct & out, hipStream_t st);
 

@@ -714,6 +714,10 @@ void launch_matvec_f(const DevTensor & W, const float * x, int64_t ldx, int64_t 
         else launch_mmfx_t<false, 1, 2>(W, x, ldx, T, y, ldy, epi, st);
         return;
     }
+    if (mmf_rows_admits(W.type, T, W.cols(), ldx)) {     // 5 .. 31 tokens: k_mmf_rows (rows_mf.hip), one pass over the weights, the same bits
+        launch_mmf_rows(W, x, ldx, T, y, ldy, epi, st);
+        return;
+    }
     if (W.type == T_F16) launch_mvf_t<true>(W, x, ldx, T, y, ldy, epi, st);
     else launch_mvf_t<false>(W, x, ldx, T, y, ldy, epi, st);
 }

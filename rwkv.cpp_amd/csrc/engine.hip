@@ -381,7 +381,7 @@ struct Runner {
     // state.rows, where row t is its own sequence. Row mode never takes the single-token paths (persistent / fused), T == 1 included.
     // Segment mode (ragged batch pass, seg != nullptr): state.segs / state.seg_of, the T tokens are seg->n runs of consecutive tokens, each
     // run on its own slot. Everything between the recurrences is per token and runs over all T tokens as in sequence mode (the product
-    // path is chosen on T); the token-shift mixes take the carry per segment (k_mix_segs), the WKV recurrences run per segment. No
+    // path is chosen on T); the token-shift mixes take the carry per segment (k_mix, FORM_SEGS), the WKV recurrences run per segment. No
     // single-token path here either.
     StateRef state;
     const SegPass * seg = nullptr;
@@ -431,8 +431,8 @@ struct Runner {
     // tile images for n outputs of a fused mix (sequence mode, all consumers quantised with `wtype`): registered like prequant's
     // carries: the kernel that would write them takes x_prev from the row above (k_mix_seq_q) -- it has no segment form
     bool fused_outs(int n, float * const * keys, int wtype, TileAct * tas, bool carries = true) {
-        if (state.rows) return false;   // (row mode: the quantising mixes carry across rows; k_mix_rows + prequant instead)
-        if (state.segs && carries) return false;   // (segment mode: k_mix_segs + prequant; the per-token quantising kernels stay)
+        if (state.rows) return false;   // (row mode: the quantising mixes carry across rows; k_mix, FORM_ROWS + prequant instead)
+        if (state.segs && carries) return false;   // (segment mode: k_mix, FORM_SEGS + prequant; the per-token quantising kernels stay)
         if (!(dtype_quantized(wtype) && T >= k_mfma_min_tokens && b.tiles[0] && D % 256 == 0 && n <= 5)) return false;
         for (auto & e : pre) e = Pre();
         for (int i = 0; i < n; i++) { tas[i] = tile_act_at(b.tiles[i], T, D); pre[i].x = keys[i]; pre[i].wtype = wtype; pre[i].K = D; pre[i].ta = tas[i]; }

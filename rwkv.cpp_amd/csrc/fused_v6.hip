@@ -9,7 +9,7 @@
 //   G  k6_ffn_v      value projection, x += sigmoid(r) * (Wv k)                                     (:513-531, :672)
 //
 // Every launch boundary is a real all-to-all dependency (a full-vector LayerNorm or a projection that consumes a whole
-// vector). Arithmetic and reduction orders are exactly those of the per-op kernels in kernels.hip,
+// vector). Arithmetic and reduction orders are exactly those of the per-op kernels in kernels.hip, matvec.hip and recur.hip,
 // so this path is bit-identical to the generic path and to the CPU oracle; tests/test_gpu_* run through it.
 //
 // Quantised activations travel between these kernels in the "lohi" image: for a vector of nb blocks, bytes

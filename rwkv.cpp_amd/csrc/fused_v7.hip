@@ -10,7 +10,7 @@
 //   E  k6_proj_res  value projection + residual add
 //
 // Every launch boundary is an all-to-all dependency (a full-vector LayerNorm, or a projection consuming a whole vector). Arithmetic
-// and reduction orders are those of the per-op kernels (kernels.hip) and of the CPU oracle: bit-identical.
+// and reduction orders are those of the per-op kernels (kernels.hip, matvec.hip, recur.hip) and of the CPU oracle: bit-identical.
 // The low-rank matrices stay in their file dtype (F16 in a quantised checkpoint, F32 when quantised from an FP32 file): their rows
 // run in ggml's 32-partial AVX2 dot order like k_mvf (4 lanes per row), activations rounded to fp16 first for F16 weights.
 #include "fused_blocks.h"

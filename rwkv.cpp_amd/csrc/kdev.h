@@ -5,6 +5,9 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 
+#include <type_traits>
+#include <utility>
+
 #include "kernels.h"
 
 namespace rwkvmi {
@@ -14,6 +17,10 @@ namespace rwkvmi {
 // ---------------------------------------------------------------------------------------------------------------
 // small device helpers
 // ---------------------------------------------------------------------------------------------------------------
+
+// f(integral_constant<int, 0>) .. f(integral_constant<int, N - 1>): an unroll whose index is a compile-time constant inside f
+template <class F, int... I> __device__ __forceinline__ void static_for(F && f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
+template <int N, class F> __device__ __forceinline__ void static_for(F && f) { static_for(f, std::make_integer_sequence<int, N>{}); }
 
 // ---------------------------------------------------------------------------------------------------------------
 // Cross-lane primitives. __shfl_xor lowers to ds_bpermute (LDS crossbar, ~100+ cycles per dependent step); the

@@ -1,4 +1,5 @@
-// kernels.h -- host-callable launchers of the gfx950 kernels (kernels.hip). All launches are asynchronous on `st`.
+// kernels.h -- host-callable launchers of the gfx950 kernels of matvec.hip, recur.hip and kernels.hip (and, where a comment names the file, of
+// rows_mm.hip, rows_mf.hip, prefill.hip and score.hip). All launches are asynchronous on `st`.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -38,6 +39,8 @@ struct Epi {
     const float * aux = nullptr;   // [T][ldy]
 };
 
+// ---- matvec.hip: the products, their dispatch, the activation quantiser ----
+
 // y[t*ldy + n] = epi( W[n,:] . x[t,:] ),  W quantised (planes), x pre-quantised.
 void launch_matvec_q(const DevTensor & W, const QAct & x, int64_t T, float * y, int64_t ldy, const Epi & epi, hipStream_t st);
 // Same for F32 / F16 weights with f32 activations x[t*ldx + k] (F16 weights: activations rounded to fp16 on load).
@@ -60,8 +63,10 @@ bool mmf_rows_admits(int wtype, int64_t T, int64_t K, int64_t ldx);
 void launch_mmf_rows(const DevTensor & W, const float * x, int64_t ldx, int64_t T, float * y, int64_t ldy, const Epi & epi, hipStream_t st);
 extern std::atomic<unsigned long long> g_mmf_rows_launches;   // launches of k_mmf_rows so far (test hook reads it)
 
-// x[T][K] f32 -> QAct
+// matvec.hip: x[T][K] f32 -> QAct
 void launch_quantize_act(const float * x, int64_t T, int64_t K, const QAct & out, hipStream_t st);
+
+// ---- kernels.hip: embedding + ln0, layer norms (elementwise helpers, argmax and the load-time kernels: further down) ----
 
 // Embedding gather (+ convert) + LayerNorm(ln0): x[t,:] = LN(emb[tokens[t], :]) * w + b     (rwkv_graph.inc:655-658)
 void launch_embed_ln0(const DevTensor & emb, const uint32_t * tokens, int64_t T, int64_t D, const float * w, const float * b, float * x, hipStream_t st);
@@ -69,6 +74,8 @@ void launch_embed_ln0(const DevTensor & emb, const uint32_t * tokens, int64_t T,
 void launch_layernorm(const float * x, int64_t T, int64_t D, const float * w, const float * b, float * y, hipStream_t st);
 // the same on n gathered rows: y[i,:] = norm(x[idx[i],:], 1e-5) * w + b   (ragged pass: the last token of each segment, in front of the head)
 void launch_layernorm_gather(const float * x, const int32_t * idx, int64_t n, int64_t D, const float * w, const float * b, float * y, hipStream_t st);
+
+// ---- recur.hip: token-shift mixes, WKV recurrences and their replay, group norm, RWKV-7 key preparation and value mix ----
 
 // Where a recurrence (token-shift carry, WKV state) reads and writes its state component, at offset `off` of the state buffers:
 //   a sequence (rows == nullptr, segs == nullptr): token t continues from token t-1; the state goes in -> out;
@@ -91,6 +98,7 @@ struct StateRef {
 // x_prev[t] = t ? xn[t-1] : carry_in.   mode 0: out_f = xn*c_f + (x_prev - x_prev*c_f)   (v4, v5)
 //                                       mode 1: out_f = (x_prev - xn)*c_f + xn           (v6 xxx / ffn, v7)
 // Also writes carry_out = xn[T-1] and (optionally) sx = x_prev - xn.
+// (carry_in / carry_out: read by the quantising sequence mix of prefill.hip only, k_mix_seq_q; launch_mix takes the carry from its StateRef)
 struct MixArgs {
     const float * xn = nullptr;
     const float * carry_in = nullptr;
@@ -101,7 +109,7 @@ struct MixArgs {
     float * sx = nullptr;
     int mode = 0;
 };
-// the carry is that of `s`: a.carry_in / a.carry_out are set from it (rows: x_prev = rows[t].in[off + d], rows[t].out[off + d] = xn[t][d];
+// the carry is that of `s`, whatever a.carry_in / a.carry_out say (a sequence: s.in[off + d] and s.out[off + d]; rows: x_prev = rows[t].in[off + d], rows[t].out[off + d] = xn[t][d];
 // segments: x_prev = t == seg.t0 ? seg.in[off + d] : xn[t-1][d], and seg.out[off + d] = xn[t][d] at t == seg.t1 - 1, seg = segs[seg_of[t]])
 void launch_mix(MixArgs a, const StateRef & s, int64_t T, int64_t D, hipStream_t st);
 
@@ -133,10 +141,10 @@ void launch_wkv7(const float * r, const float * w, const float * k, const float 
 bool launch_wkv7_seq(const float * r, const float * w, const float * k, const float * v, const float * a, const float * b,
                      const float * state_in, float * state_out, float * out, int64_t T, int64_t H, hipStream_t st);
 
-// Speculative decoding (rwkv_mi_batch_eval_draft): the stash of a pass and the replay of its recurrences (kernels.hip, "Replay").
+// Speculative decoding (rwkv_mi_batch_eval_draft): the stash of a pass and the replay of its recurrences (recur.hip, "Replay").
 // The stash of a pass of T tokens is [layers][planes()][T][D] floats; per layer, plane i < n_in is input i of the layer's WKV body in the order
 // of its arguments (v4: k, v, r; v5: r, k, v; v6: r, k, v, w; v7: r, w, k', v, -kk, kk*a), plane n_in the input of the att token-shift mix,
-// plane n_in + 1 that of the ffn mix (what k_mix_segs leaves in the carry at a segment's last token), plane n_in + 2 where a replay's body
+// plane n_in + 1 that of the ffn mix (what the segment form of k_mix leaves in the carry at a segment's last token), plane n_in + 2 where a replay's body
 // writes the per-token output nobody reads. layer0 / per_layer: the first layer of the stash and the floats of a layer in a state buffer.
 struct DraftStash {
     float * base = nullptr;
@@ -170,7 +178,7 @@ void launch_v7_kprep(const float * k, const float * a, const float * k_k, const 
 // v7 value residual (rwkv_graph.inc:439-453): v = v + (v_first - v) * gate   (gate already sigmoid'ed)
 void launch_v7_vmix(float * v, const float * v_first, const float * gate, int64_t n, hipStream_t st);
 
-// Plain elementwise helpers
+// ---- kernels.hip again: plain elementwise helpers, argmax ----
 void launch_mul(float * y, const float * a, const float * b, int64_t n, hipStream_t st);   // y = a * b
 void launch_copy_f32(float * dst, const float * src, int64_t n, hipStream_t st);
 void launch_fill_state_v4(float * state, int64_t n_layer, int64_t D, hipStream_t st);      // zeros + pp = -1e30
@@ -196,7 +204,7 @@ void launch_logprob_rows(const float * logits, int64_t rows, int n, const uint32
 void launch_logprob_rows_serve(const float * logits, int64_t lanes, int n, const uint32_t * tokens, int top_n, float * chosen, uint32_t * top_ids, float * top_lp,
                                const uint32_t * draw, const uint32_t * req, const uint32_t * lens, uint32_t stride, uint32_t n_requests, hipStream_t st);
 
-// load-time transpose of att.time_maa_w2: [5][D][R] -> [5][R][D]
+// kernels.hip: load-time transpose of att.time_maa_w2: [5][D][R] -> [5][R][D]
 void launch_transpose_w2(const float * src, float * dst, int64_t D, int64_t R, hipStream_t st);
 
 // load-time re-pack of quantised blocks (file layout) into planes; see DevTensor

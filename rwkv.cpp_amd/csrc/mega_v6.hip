@@ -14,7 +14,7 @@
 // workgroup barrier and their own loads. A grid-wide barrier costs 3.2-3.9 us on this part, a tagged hand-over of a
 // 4096-float vector to all 256 workgroups 3.5 us, of a small vector 1.5-2.2 us (tools/barrier_bench.hip, xchg_bench.hip).
 //
-// Arithmetic, reduction orders and epilogues are those of fused_v6.hip / kernels.hip: the results are
+// Arithmetic, reduction orders and epilogues are those of fused_v6.hip / the per-op kernels: the results are
 // bit-identical to the seven-launch path and to the CPU oracle; only the distribution of rows over waves differs.
 //
 // Residency: the grid is one workgroup per CU (512 threads, ~105 KB LDS) and all of them must be resident at once, i.e. the

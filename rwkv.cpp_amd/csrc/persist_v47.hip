@@ -22,7 +22,7 @@
 // workgroup's share of the first low-rank stages. RWKV-7's heads run on H further workgroups that own no rows: their comm wave polls
 // lr1, then r / k / v, and runs the recurrence of kdev's k7_head statement for statement, their eight workers the second stages.
 // Weights go global -> registers one phase ahead (no ring: a workgroup's share of a 169M layer is 55 KB, of a 2.9B layer 412 KB in four
-// phases). Arithmetic and reduction orders are those of fused_v7.hip / kernels.hip and of the CPU oracle: bit-identical.
+// phases). Arithmetic and reduction orders are those of fused_v7.hip / the per-op kernels and of the CPU oracle: bit-identical.
 //
 // Embedding + ln0 (first stage) and ln_out + head + argmax (last stage; every workgroup of the grid, the CUs the layers do not use
 // included) run inside the launch: a token is one graph node. Layer ranges serve pipeline stages and the streamed rwkv_eval.

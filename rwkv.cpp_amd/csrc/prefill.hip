@@ -14,7 +14,7 @@
 //                      columns in packed-f32 registers instead of one wave per head).
 //
 // Bit-exactness with the single-token path (the reference guarantees serial == sequence and tests it with memcmp,
-// tests/test_eval_sequence_in_chunks.c:54; here it holds for every format). A row sum of k_mvq_t1 is a fixed expression:
+// tests/test_eval_sequence_in_chunks.c:54; here it holds for every format). A row sum of k_mvq_t1 (matvec.hip) is a fixed expression:
 // 64 partials P[l], l = b mod 64, each a chain over its blocks in increasing b, then the xor-butterfly 32, 16, 8, 4, 2, 1 --
 // a binary tree whose root splits the leaves by bit 0 of l, the next level by bit 1, ... A depth-first walk of that tree
 // visits the leaves in bit-reversed order l = 0, 32, 16, 48, 8, ..., so the GEMM walks the K dimension in that order and

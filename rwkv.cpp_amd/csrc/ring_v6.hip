@@ -1432,7 +1432,7 @@ struct R6 {
     // -----------------------------------------------------------------------------------------------------------
     // the head behind the last layer: ln_out on the gathered residual stream, logits = head.weight (F16) . fp16(ln_out(x))
     // (rwkv_graph.inc:704-708; ggml's F16 dot: activations rounded to fp16, 32 partial sums k mod 32 accumulated with fma in increasing k,
-    // folded 16 / 8 / 4, (p0 + p1) + (p2 + p3) -- the order of k_mvf in kernels.hip: four lanes per row, lane q holds partials 8 q .. 8 q + 7)
+    // folded 16 / 8 / 4, (p0 + p1) + (p2 + p3) -- the order of k_mvf in matvec.hip: four lanes per row, lane q holds partials 8 q .. 8 q + 7)
     // -----------------------------------------------------------------------------------------------------------
     static __device__ __forceinline__ void head_phase(R6Arg p, const Lds & l, Cons & cs, Poll & pl, xrsrc xr, const M6Arena & ar,
                                                       int lane, int wave, unsigned base, unsigned eg) {

@@ -3,7 +3,7 @@
 // model, every matrix of an FP16 / FP32 file, the low-rank stages of RWKV-7. Every weight byte leaves HBM once per product (k_mvf's token tiles
 // of four walk the matrix ceil(T / 4) times).
 //
-// Numerics: bit-identical to k_mvf on each token alone (kernels.hip, "Projection, F32 / F16 weights"). ggml's vec_dot order: 32 partials,
+// Numerics: bit-identical to k_mvf on each token alone (matvec.hip, "Projection, F32 / F16 weights"). ggml's vec_dot order: 32 partials,
 // partial p the chain fmaf(w[k], x[k], .) over k = p, p + 32, p + 64, ... in increasing k; then ps[i] += ps[i + 16], += ps[i + 8], += ps[i + 4],
 // (ps0 + ps1) + (ps2 + ps3). v_mfma_f32_16x16x4_f32 adds its four k slices onto the accumulator as a chain of single fused multiply-adds in k
 // order (tools/mfma_f32_chain.hip), so ONE instruction with the slices p, p + 32, p + 64, p + 96 of a 128-element step is four links of partial
@@ -55,10 +55,6 @@ template <bool F16, int NT> struct MfrCfg {
     static constexpr int O_W = 0, O_X = MF_R * MF_PITCH, BUF = O_X + TP * MF_PITCH, BYTES = 2 * BUF;
     static_assert(BYTES <= 64 * 1024 && BYTES >= 2 * 8 * NT * 64 * 16, "LDS budget; the waves' exchange at the end reuses the buffers");
 };
-
-// f(integral_constant<int, 0>) .. f(integral_constant<int, N - 1>): the register stage of a chunk is a compile-time index
-template <class F, int... I> __device__ __forceinline__ void mfr_static_for(F && f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, class F> __device__ __forceinline__ void mfr_static_for(F && f) { mfr_static_for(f, std::make_integer_sequence<int, N>{}); }
 
 template <bool F16, int NT>
 __global__ __launch_bounds__(256) void k_mmf_rows(const void * __restrict__ W, int64_t N, int64_t K, const float * __restrict__ x, int64_t ldx,
@@ -167,12 +163,12 @@ __global__ __launch_bounds__(256) void k_mmf_rows(const void * __restrict__ W, i
     //      and chunk q + 1 + PF is requested into the registers that this frees ----
     fetch(stage[0], 0);
     stash(stage[0], 0);
-    mfr_static_for<PF>([&](auto s) { constexpr int S = decltype(s)::value; if (S >= 1 && S < nq) fetch(stage[S], S); });
+    static_for<PF>([&](auto s) { constexpr int S = decltype(s)::value; if (S >= 1 && S < nq) fetch(stage[S], S); });
     if (PF < nq) fetch(stage[0], PF);
     __syncthreads();
 #pragma unroll 1
     for (int q0 = 0; q0 < nq; q0 += PF) {
-        mfr_static_for<PF>([&](auto s) {
+        static_for<PF>([&](auto s) {
             constexpr int S = decltype(s)::value, NX = (S + 1) % PF;
             const int q = q0 + S;
             if (q < nq) {                                                     // (workgroup-uniform)

@@ -2,7 +2,7 @@
 // the product of batched decode (rwkv_mi_batch_*, serve, beam, draft passes) and of short sequence / ragged passes. It reads the DECODE
 // layout (the row-major planes W.qs / W.qh / W.sc) and the plain QAct of launch_quantize_act; every weight byte leaves HBM once per product.
 //
-// Numerics: bit-identical to k_mvq_t1 on each token alone (kernels.hip header). 64 partials P[l], l = b mod 64, each the chain of blk_fma
+// Numerics: bit-identical to k_mvq_t1 on each token alone (matvec.hip). 64 partials P[l], l = b mod 64, each the chain of blk_fma
 // (kdev.h) over its blocks in increasing b, then the xor butterfly 32, 16, 8, 4, 2, 1; leaves without blocks are +0.0. The tree's last two
 // levels pair the leaves by l & 3: root = (s0 + s2) + (s1 + s3), s_w = the sum of the subtree l & 3 == w. Wave w of the workgroup owns that
 // subtree: its 16 leaves l = w + 4 m are 16 accumulators per output, so K is walked in PLAIN order (block b goes to wave b & 3, accumulator
@@ -238,10 +238,7 @@ __global__ __launch_bounds__(RM_NTH) void k_mmq_rows(RowsMmArgs A) {
     };
 #pragma unroll 1
     for (int q0 = 0; q0 < nq; q0 += 4) {
-        round(q0, std::integral_constant<int, 0>{});
-        round(q0 + 1, std::integral_constant<int, 1>{});
-        round(q0 + 2, std::integral_constant<int, 2>{});
-        round(q0 + 3, std::integral_constant<int, 3>{});
+        static_for<RM_PF>([&](auto sub_tag) { round(q0 + decltype(sub_tag)::value, sub_tag); });
     }
 
     // ---- the wave's subtree: leaves l and l ^ 32 (m, m + 8), then ^ 16, ^ 8, ^ 4; the four subtrees meet in LDS as (s0 + s2) + (s1 + s3) ----

@@ -19,7 +19,7 @@
 
 namespace rwkvmi {
 
-// One body, several entry points (the convention of sampling.hip and kernels.hip): k_score_rows and k_logprob_rows both reduce a row through
+// One body, several entry points (the convention of sampling.hip and recur.hip): k_score_rows and k_logprob_rows both reduce a row through
 // these two functions, so the log-prob a draw reports for its token is, bit for bit, the one k_score_rows gives that row with that target.
 
 // The row maximum and its first index (k_argmax). Thread 0 returns the index (0x7fffffff when nothing compares greater than -inf) and has

@@ -1,5 +1,5 @@
 """Hand-built operands of the UNQUANTISED products (F16 / F32 matrices): weight rows and activation rows that reach every end of binary16 and
-binary32, the counterpart of tests/blocks_lib.py for k_mvf, k_mmfx_seq and k_mmf16_seq (csrc/kernels.hip). TEST INFRASTRUCTURE ONLY
+binary32, the counterpart of tests/blocks_lib.py for k_mvf, k_mmfx_seq and k_mmf16_seq (csrc/matvec.hip). TEST INFRASTRUCTURE ONLY
 (tests/test_cpu_fx_extremes.py holds the oracle to an exact emulation on everything made here, tests/test_gpu_fx_extremes.py holds the GPU
 products to the oracle; the model-level palette of F16 elements is blocks_lib.f16_palette).
 

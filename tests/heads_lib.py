@@ -3,7 +3,7 @@ float64 on every file made here, tests/test_gpu_head_sizes.py holds every recurr
 
 synth.CONFIGS has head size 64 only and the tiny golden files have (H, S) = (8, 8), (16, 8) and (1, 64). The loader takes head_size =
 n_embed / head_count from the shape of att.time_decay or att.r_k, so a file of any S that divides D loads; ROWS are the shapes that reach
-the S = 32 and S = 16 instantiations of the recurrence kernels and their generic forms (csrc/kernels.hip: launch_wkv6, launch_wkv7,
+the S = 32 and S = 16 instantiations of the recurrence kernels and their generic forms (csrc/recur.hip: launch_wkv6, launch_wkv7,
 launch_draft_replay):
 
   arch  D     S    H   what it reaches

@@ -70,9 +70,9 @@ def named(src_name, name):
     return out
 
 
-def budget(src_name, keys, wg=1024):
-    """{key: Kernel} of the listed kernels, each of which exists (once: kernels() has one entry per key) and keeps within the budget of a
-    1024-thread workgroup -- no private segment, no spills, at most 128 registers per thread -- at the workgroup size wg"""
+def no_scratch(src_name, keys):
+    """{key: Kernel} of the listed kernels, each of which exists (once: kernels() has one entry per key) and has no private segment and no
+    spills. A missing instantiation fails by its key."""
     found = kernels(src_name)
     missing = [key for key in keys if key not in found]
     assert not missing, (missing, sorted(found, key=str))
@@ -80,10 +80,30 @@ def budget(src_name, keys, wg=1024):
         k = found[key]
         print(key, k)
         assert k.private == 0 and k.spills == 0, (key, k)
-        assert k.vgprs <= 128, (key, k, "1024 threads per workgroup leave 128 registers per thread")
-        assert k.wg == wg, (key, k)
     assert len({found[key].name for key in keys}) == len(keys), keys
     return {key: found[key] for key in keys}
+
+
+def budget(src_name, keys, wg=1024):
+    """no_scratch, and each kernel keeps within the budget of a 1024-thread workgroup -- at most 128 registers per thread -- at the
+    workgroup size wg"""
+    found = no_scratch(src_name, keys)
+    for key, k in found.items():
+        assert k.vgprs <= 128, (key, k, "1024 threads per workgroup leave 128 registers per thread")
+        assert k.wg == wg, (key, k)
+    return found
+
+
+# csrc/recur.hip: the form of an entry point is its last template argument -- but for RWKV-5 / 6, whose body has a kernel of its own per form
+FORM_SEQ, FORM_ROWS, FORM_SEGS = 0, 1, 2
+
+
+def recurrence_entry_points(form):
+    """the keys of the entry points of csrc/recur.hip at one form: the token-shift mix, RWKV-4, RWKV-5 / 6 at head sizes 64 / 32 / 16 / 8 and
+    generic, RWKV-7 at 64 / 32 and generic"""
+    wkv6 = "k_wkv6" + ("", "_rows", "_segs")[form]
+    return (("k_mix", (form,)), ("k_wkv4", (form,)), *((wkv6, (S,)) for S in (64, 32, 16, 8)), wkv6 + "_generic",
+            *(("k_wkv7", (S, form)) for S in (64, 32)), ("k_wkv7_generic", (form,)))
 
 
 if __name__ == "__main__":

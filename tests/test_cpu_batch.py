@@ -1,14 +1,13 @@
 """Batched decode without a GPU: the library exports the rwkv_mi_batch_* entry points, the Python binding declares them, and no row kernel
-of csrc/kernels.hip uses scratch memory (the same metadata read as test_cpu_kernel_budget.py)."""
+of csrc/recur.hip uses scratch memory (the same metadata read as test_cpu_kernel_budget.py)."""
 import ctypes
 import os
-import re
-import subprocess
 
 import pytest
 
+import kernel_meta
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
 SYMBOLS = ("rwkv_mi_batch_create", "rwkv_mi_batch_free", "rwkv_mi_batch_state_load", "rwkv_mi_batch_state_store",
            "rwkv_mi_batch_state_from_context", "rwkv_mi_batch_state_to_context", "rwkv_mi_batch_eval", "rwkv_mi_batch_decode_greedy")
 
@@ -41,22 +40,8 @@ def test_binding_declares_batch_symbols():
         assert callable(getattr(pkg.RWKVBatch, meth)), meth
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
-def test_row_entry_points_have_no_private_segment(tmp_path):
-    src = os.path.join(ROOT, "rwkv.cpp_amd", "csrc", "kernels.hip")
-    out = str(tmp_path / "kernels.s")
-    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-DRWKV_SHARED", "-DRWKV_BUILD",
-           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "rwkv.cpp_amd", "csrc"), "-S", "--cuda-device-only", src, "-o", out]
-    subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    text = open(out).read()
-    meta = text[text.index("amdhsa.kernels"):]
-    seen = set()
-    for m in re.finditer(r"\.name:\s+(\S+).*?\.private_segment_fixed_size:\s+(\d+).*?\.vgpr_count:\s+(\d+).*?\.vgpr_spill_count:\s+(\d+)", meta, re.S):
-        name, private, vgprs, spills = m.group(1), int(m.group(2)), int(m.group(3)), int(m.group(4))
-        if "_rows" in name or "k_argmax" in name:
-            seen.add(name)
-            assert private == 0 and spills == 0, (name, private, vgprs, spills)
-    # k_mix_rows, k_wkv4_rows, k_wkv6_rows<64/32/16/8> + generic, k_wkv7_rows<64/32> + generic, k_argmax (one workgroup per row)
-    assert len(seen) >= 11, sorted(seen)
-    for k in ("k_mix_rows", "k_wkv4_rows", "k_wkv6_rows", "k_wkv7_rows", "k_argmax", "k_wkv6_rows_generic", "k_wkv7_rows_generic"):
-        assert any(k in n for n in seen), k
+@pytest.mark.skipif(not kernel_meta.have_hipcc(), reason="needs hipcc")
+def test_row_entry_points_have_no_private_segment():
+    """the ROWS form of every recurrence, and the argmax kernels of the greedy loops (one workgroup per row)"""
+    kernel_meta.no_scratch("recur.hip", kernel_meta.recurrence_entry_points(kernel_meta.FORM_ROWS))
+    kernel_meta.no_scratch("kernels.hip", ("k_argmax", "k_argmax_live"))

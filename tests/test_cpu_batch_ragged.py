@@ -1,14 +1,14 @@
 """Ragged batch passes without a GPU: the library exports the two entry points, the Python binding declares them, RWKVBatch has the two
-methods, and no segment kernel of csrc/kernels.hip uses scratch memory (the same metadata read as test_cpu_batch.py)."""
+methods, and no segment kernel of csrc/recur.hip uses scratch memory (the same metadata read as test_cpu_batch.py)."""
 import ctypes
 import os
 import re
-import subprocess
 
 import pytest
 
+import kernel_meta
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
 SYMBOLS = ("rwkv_mi_batch_eval_ragged", "rwkv_mi_batch_eval_ragged_sample")
 
 
@@ -48,22 +48,8 @@ def test_header_declares_ragged_calls():
         assert re.search(r"RWKV_API bool " + name + r"\(", text), name
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
-def test_segment_entry_points_have_no_private_segment(tmp_path):
-    src = os.path.join(ROOT, "rwkv.cpp_amd", "csrc", "kernels.hip")
-    out = str(tmp_path / "kernels.s")
-    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-DRWKV_SHARED", "-DRWKV_BUILD",
-           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "rwkv.cpp_amd", "csrc"), "-S", "--cuda-device-only", src, "-o", out]
-    subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    text = open(out).read()
-    meta = text[text.index("amdhsa.kernels"):]
-    seen = set()
-    for m in re.finditer(r"\.name:\s+(\S+).*?\.private_segment_fixed_size:\s+(\d+).*?\.vgpr_count:\s+(\d+).*?\.vgpr_spill_count:\s+(\d+)", meta, re.S):
-        name, private, vgprs, spills = m.group(1), int(m.group(2)), int(m.group(3)), int(m.group(4))
-        if "_segs" in name or "k_layernorm_gather" in name:
-            seen.add(name)
-            assert private == 0 and spills == 0, (name, private, vgprs, spills)
-    # k_mix_segs, k_wkv4_segs, k_wkv6_segs<64/32/16/8> + generic, k_wkv7_segs<64/32> + generic, k_layernorm_gather (the head's rows)
-    assert len(seen) >= 11, sorted(seen)
-    for k in ("k_mix_segs", "k_wkv4_segs", "k_wkv6_segs", "k_wkv7_segs", "k_wkv6_segs_generic", "k_wkv7_segs_generic", "k_layernorm_gather"):
-        assert any(k in n for n in seen), k
+@pytest.mark.skipif(not kernel_meta.have_hipcc(), reason="needs hipcc")
+def test_segment_entry_points_have_no_private_segment():
+    """the SEGS form of every recurrence, and the gathered layer norm in front of the head (the segments' last rows)"""
+    kernel_meta.no_scratch("recur.hip", kernel_meta.recurrence_entry_points(kernel_meta.FORM_SEGS))
+    kernel_meta.no_scratch("kernels.hip", ("k_layernorm_gather",))

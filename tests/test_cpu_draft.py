@@ -1,6 +1,6 @@
 """Speculative decoding (rwkv_mi_batch_eval_draft), without a GPU: the header declares the entry point and its limit, all four libraries export
 it, the binding declares it with the header's argument count, lookup_draft -- the prompt-lookup drafter the binding offers callers -- does what
-its statement says on hand-written histories, and the device-only compile of csrc/sampling.hip and csrc/kernels.hip shows the accept kernel and
+its statement says on hand-written histories, and the device-only compile of csrc/sampling.hip and csrc/recur.hip shows the accept kernel and
 every replay kernel without a private segment or spills, the accept kernel within a 1024-thread workgroup's 128 registers."""
 import ctypes
 import os
@@ -92,7 +92,7 @@ def test_accept_kernel_keeps_the_budget():
 @pytest.mark.skipif(not kernel_meta.have_hipcc(), reason="needs hipcc")
 def test_replay_kernels_have_no_private_segment_and_no_spills():
     """every entry point of the replay -- the fourth over each WKV body, templated and generic -- and the two copy kernels beside them"""
-    seen = {k: kernel_meta.named("kernels.hip", k) for k in REPLAY}
+    seen = {k: kernel_meta.named("recur.hip", k) for k in REPLAY}
     for k, forms in seen.items():
         assert forms, (k, seen)
         for kern in forms.values():

@@ -1,4 +1,4 @@
-"""Speculative decoding in the batch (rwkv_mi_batch_eval_draft; csrc/sampling.hip k_draft_accept_rows, csrc/kernels.hip k_wkvX_replay). The
+"""Speculative decoding in the batch (rwkv_mi_batch_eval_draft; csrc/sampling.hip k_draft_accept_rows, csrc/recur.hip k_wkvX_replay). The
 guarantee is that speculation never changes what is emitted, only how many passes it takes, so everything here is bit for bit: the emitted
 tokens, lens_out, the slot's state as the bytes of state_store, its occurrence table, and -- a draw counter cannot be read back -- the token
 one further generator draw gives, against the PLAIN loop of the same family run for lens_out steps from the same start:

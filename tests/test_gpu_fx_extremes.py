@@ -25,7 +25,7 @@ eval_sequence of 40 and in chunks of 33, three batch slots: two passes, then eva
 The predicted signed zero (F32 weights 1e-30 against activations -1e-30: every product underflows to -0, the oracle returns 0x80000000 at
 every K). CONFIRMED AND FIXED. Device bits of k_mmfx_seq (N = 37, T = 65, every output alike) at K = 32 / 128 / 160 / 2112:
   absent slices fed as fma(+0, +0, a)   0x00000000 / 0x80000000 / 0x00000000 / 0x00000000   (K = 128 has no tail; k_mvf: 0x80000000 everywhere)
-  absent slices fed as fma(+0, -0, a)   0x80000000 / 0x80000000 / 0x80000000 / 0x80000000   (csrc/kernels.hip, fetch; the matrix core honours it)
+  absent slices fed as fma(+0, -0, a)   0x80000000 / 0x80000000 / 0x80000000 / 0x80000000   (csrc/matvec.hip, fetch; the matrix core honours it)
 Nothing else differed on the exact arms: v_mfma_f32_16x16x4_f32 keeps f32 denormals and the converted binary16 subnormals, gives the
 infinities and NaN positions of the fmaf chain, and round_f16 / h2f_bits meet every edge; the private F16 loops of the persistent kernels
 (in-launch head of k6_ring / k47, low-rank stages of k47 and fused_v7.hip) equal the oracle on the redrawn files.
@@ -35,7 +35,7 @@ were run on every build: failures here / in those three):
   (a) h2f_bits (kdev.h) returns 0 for a subnormal half        64 here (the 20 FP16 products -- every shape and T --, all 44 model cases) / 79 in
                                                                those three: N(0, 0.05^2) weights hold a subnormal by chance, one element in 1000
   (b) round_f16 (kdev.h) truncates (__float2half_rz)          66 here (the 20 FP16 products, both FP16 probes, all 44 model cases) / 169
-  (c) the -0 padding of fetch (kernels.hip) reverted to +0    9 here (the FP32 products with T >= 32 at K = 32, 160, 2112; the signed-zero test at
+  (c) the -0 padding of fetch (matvec.hip) reverted to +0    9 here (the FP32 products with T >= 32 at K = 32, 160, 2112; the signed-zero test at
                                                                the same K) / 0: the other three files pass
   (d) in-launch head of persist_v47.hip takes |w| (hj_consume_pass)   8 here (eval and decode_greedy of the four k47 cases) / 6, the decode check of
                                                                test_gpu_seq_f16.py::test_sequence_pass_on_the_matrix_cores on its RWKV-7 Q5_1 files
@@ -215,7 +215,7 @@ def test_opt_in_matrix_core_arm_on_hand_built_operands(K, N, T):
     beside a = 2^-9 made of normal halves (2^-4 x 2^-5) b arrives exactly down to s = 28, the smallest tried; beside the same a made of
     2^15 x the subnormal 2^-24 (nominal 2^1), in either operand, b arrives down to s = 23 and is dropped whole from s = 24 on. The kernel now
     stores a subnormal activation m 2^-24 as the normal half m and adds those elements on a second accumulator, joined times 2^-24 at the
-    end (csrc/kernels.hip, k_mmf16_seq): ramp is at 0.07 of the project's bound and below at every K. Subnormal WEIGHTS still enter the
+    end (csrc/matvec.hip, k_mmf16_seq): ramp is at 0.07 of the project's bound and below at every K. Subnormal WEIGHTS still enter the
     instruction as they are: that is what +sub and -sub show, inside the any-order bound at these shapes.
     """
     t = X.F16

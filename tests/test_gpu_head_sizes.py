@@ -17,18 +17,18 @@ state index at the first token, a fresh one only later:
   f  the fast quantised sequence arm (RWKV_MI_SEQ_Q=force, T = 97) on the S = 96 row of RWKV-6 and RWKV-7, Q5_1: held to float64 with the
      criterion and the constant of tests/test_gpu_f64_reference.py, the launch counter showing that the arm ran
 
-Which kernel of csrc/kernels.hip each case launches (seq: a, b; rows: c; segs: d; replay: e -- b with 40 tokens is also the T >= 32 sequence
+Which kernel of csrc/recur.hip each case launches (seq: a, b; rows: c; segs: d; replay: e -- b with 40 tokens is also the T >= 32 sequence
 pass that skips the lane-pipelined launch_wkv6_seq / launch_wkv7_seq, d the ragged pass that keeps every segment in the short launch, and
 every case the group norm without its quantising sequence form):
   k_wkv6<32> / _rows / _segs / _replay               v5.1-D256-S32 (u and w per head), v6-D256-S32 (w per token)
   k_wkv6<16> / _rows / _segs / _replay               v5.2-D256-S16 (u and w per channel)
   k_wkv6_generic / _rows_ / _segs_ / _replay_generic v6-D768-S96, v6-D256-S128; v6-D1024-S512 (seq and rows; the 256-thread loop twice)
-  k_wkv7<32> / _rows / _segs / _replay               v7-D256-S32
-  k_wkv7_generic / _rows_ / _segs_ / _replay_generic v7-D256-S16, v7-D768-S96, v7-D256-S128; v7-D1024-S512 (seq and rows)
+  k_wkv7<32, FORM> / k_wkv7_replay<32>               v7-D256-S32
+  k_wkv7_generic<FORM> / k_wkv7_replay_generic     v7-D256-S16, v7-D768-S96, v7-D256-S128; v7-D1024-S512 (seq and rows)
   k_groupnorm, k_v7_kprep off one element per lane   S = 16, 32 (idle lanes), 96 (uneven), 128 (two), 512 (eight), every case of the row
 tests/test_gpu_recur_kernels.py runs the same kernels on caller-supplied arrays at the head sizes no file can have.
 
-What the two files see that the suite before them does not (one-line mutations of csrc/kernels.hip on a side build, the whole GPU suite run
+What the two files see that the suite before them does not (one-line mutations of csrc/recur.hip on a side build, the whole GPU suite run
 once on each; "before": the 1357 GPU tests that existed before these two files, of which 1353 pass and 4 skip on the unmutated build):
   wkv6_body_generic reads sin[h S S + j S + i]        61 tests here and in test_gpu_recur_kernels.py fail: every form of the ten generic
   for sin[h S S + i S + j]                            RWKV-6 cases (plain ABI 10, sequence 10, rows 10, segments 8, replay 8), the fast arm of

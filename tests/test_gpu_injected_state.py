@@ -21,7 +21,7 @@ ragged form to that scorer bit for bit): |dev - float32(ref)| <= ulp32(ref) + 2^
 
 What the file sees that the fresh-state suite does not (one-line mutations of one copy of a recurrence each, on a side build; the suite
 without this file passed on both):
-  wkv4_body (kernels.hip), e1 taken as 0 when pp - qq < -10     18 tests here fail, every RWKV-4 case: plain ABI (5), resident loops (4),
+  wkv4_body (recur.hip)  , e1 taken as 0 when pp - qq < -10     18 tests here fail, every RWKV-4 case: plain ABI (5), resident loops (4),
                                                                 sequence (4), rows and segments (5)
   k6_ring (ring_v6.hip), the decay clamped to >= 1e-6           3 fail: plain ABI, resident loops and the eval after a sequence, ring case
 Thresholds much further out are not mutations in f32 and no finite state of these families shows them: e1 < exp(-20) changes a = e1 aa + e2 v

@@ -1,4 +1,4 @@
-"""The recurrence kernels of csrc/kernels.hip and csrc/prefill.hip on caller-supplied arrays (lib/librwkv_testhooks_recur.so,
+"""The recurrence kernels of csrc/recur.hip and csrc/prefill.hip on caller-supplied arrays (lib/librwkv_testhooks_recur.so,
 include/rwkv_testhooks_recur.h), at head sizes no model file can have, against the float32 rendering of the oracle's statements
 (tests/recur_ref.py; tests/test_cpu_recur_ref.py holds that rendering to float64): np.array_equal on the outputs and on the whole out-state.
 The out-buffers go in filled with a sentinel, so a slot no row or segment names, and a token no segment covers, must come back as they went in.
@@ -6,9 +6,9 @@ The out-buffers go in filled with a sentinel, so a slot no row or segment names,
   launch_wkv6 / launch_wkv7   S in {8, 16, 20, 32, 40, 64, 96, 100, 128, 256, 320} (20, 100: no multiple of 8; 40, 96, 100: no power of two; 320:
                               the 256-thread loop of the generic bodies taken twice), H in {1, 3}; RWKV-5 / 6: (u_per_chan, w_mode) in
                               {(0, 0), (1, 1), (1, 2)}
-     sequence                 T in {1, 2, 5}                                                                  k_wkvX<S>, k_wkvX_generic
-     rows                     4 rows over 6 slots in a permuted order, two slots unused                       k_wkvX_rows<S>, k_wkvX_rows_generic
-     segments                 9 tokens; segments of 1, 4 and 2 tokens that start at 2, 5 and 3, on slots 4, 0, 2  k_wkvX_segs<S>, k_wkvX_segs_generic
+     sequence                 T in {1, 2, 5}                                                                  k_wkv6<S>, k_wkv6_generic; k_wkv7<S, 0>, k_wkv7_generic<0>
+     rows                     4 rows over 6 slots in a permuted order, two slots unused                       k_wkv6_rows<S>, k_wkv6_rows_generic; k_wkv7<S, 1>, k_wkv7_generic<1>
+     segments                 9 tokens; segments of 1, 4 and 2 tokens that start at 2, 5 and 3, on slots 4, 0, 2  k_wkv6_segs<S>, k_wkv6_segs_generic; k_wkv7<S, 2>, k_wkv7_generic<2>
                               (templated: wkv6 S = 8, 16, 32, 64; wkv7 S = 32, 64; every other S generic)
   launch_wkvX_seq             S = 64, T in {32, 33, 64, 65, 97}, H in {1, 2, 5}: against the rendering and against launch_wkvX on the same input
   launch_groupnorm            the same S, T * H in {1, 5, 9} (a partial last workgroup of four waves), with and without the gate and the RWKV-7

@@ -1,4 +1,4 @@
-"""Sequence mode on F16 matrices on the matrix cores (k_mmf16_seq, csrc/kernels.hip): FP16 model files and the F16 low-rank stages of
+"""Sequence mode on F16 matrices on the matrix cores (k_mmf16_seq, csrc/matvec.hip): FP16 model files and the F16 low-rank stages of
 RWKV-7 (rwkv_graph.inc:416-447) / the F16 emb of a quantised checkpoint, T >= 32 tokens per pass.
 
 Contract (BASELINE north star; reference tests/test_eval_sequence_in_chunks.c:54, tests/test_tiny_rwkv.c:38-54): bit-exactness with the

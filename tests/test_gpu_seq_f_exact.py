@@ -1,4 +1,4 @@
-"""Sequence mode of F16 / F32 matrices on the matrix cores in ggml's own addition order (k_mmfx_seq, csrc/kernels.hip; round 6): FP16 / FP32
+"""Sequence mode of F16 / F32 matrices on the matrix cores in ggml's own addition order (k_mmfx_seq, csrc/matvec.hip; round 6): FP16 / FP32
 model files and the F16 low-rank stages of RWKV-7 (rwkv_graph.inc:416-447, :744-866), T >= 32 tokens per pass.
 
 v_mfma_f32_16x16x4_f32 adds its four k slices onto the accumulator as a chain of single fused multiply-adds (tools/mfma_f32_chain.hip), so

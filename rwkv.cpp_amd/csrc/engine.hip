@@ -274,7 +274,7 @@ bool ensure_scratch(rwkv_context * ctx, int64_t T) {
     size_t total = n_D * fsz(D) + fsz(F) + 2 * fsz(LR) + align_up(D * sizeof(float), 256);
     total += align_up((size_t) T * KQ, 256) + 3 * align_up((size_t) T * (KQ / 32) * 4, 256);
     const size_t TR = (size_t) (T < k_mfma_min_tokens ? T : k_mfma_min_tokens - 1);   // qa_more: only passes below k_mfma_min_tokens tokens use it
-    total += 3 * (align_up(TR * D, 256) + 3 * align_up(TR * (D / 32) * 4, 256));
+    total += (3 + ROWS_Q_BATCH) * (align_up(TR * D, 256) + 3 * align_up(TR * (D / 32) * 4, 256));   // qa_more and qa_pre
     constexpr size_t k_ws_part = (size_t) 16 << 20;   // split-walk partial sums: up to 64 tiles x 8 parts x 32 KiB
     constexpr int    k_ws_counters = 1024;
     if (T >= k_mfma_min_tokens) total += align_up(tile_act_bytes(T, (int64_t) KQ), 256) + 5 * align_up(tile_act_bytes(T, (int64_t) D), 256) + k_ws_part + k_ws_counters * sizeof(int);
@@ -295,12 +295,14 @@ bool ensure_scratch(rwkv_context * ctx, int64_t T) {
     b.qa.d = (float *) p; p += align_up((size_t) T * (KQ / 32) * 4, 256);
     b.qa.s = (float *) p; p += align_up((size_t) T * (KQ / 32) * 4, 256);
     b.qa.isum = (int *) p; p += align_up((size_t) T * (KQ / 32) * 4, 256);
-    for (QAct & q : b.qa_more) {
+    auto take_rows_q = [&](QAct & q) {
         q.q = (int8_t *) p; p += align_up(TR * D, 256);
         q.d = (float *) p; p += align_up(TR * (D / 32) * 4, 256);
         q.s = (float *) p; p += align_up(TR * (D / 32) * 4, 256);
         q.isum = (int *) p; p += align_up(TR * (D / 32) * 4, 256);
-    }
+    };
+    for (QAct & q : b.qa_more) take_rows_q(q);
+    for (QAct & q : b.qa_pre) take_rows_q(q);
     b.tile = nullptr;
     b.ws = MmqWs();
     for (int i = 0; i < 5; i++) b.tiles[i] = nullptr;
@@ -427,12 +429,29 @@ struct Runner {
         for (auto & e : pre) if (e.x == x && e.K == K && e.wtype == wtype) return &e.ta;
         return nullptr;
     }
-    void drop_pre() { for (auto & e : pre) e = Pre(); }
+    void drop_pre() { for (auto & e : pre) e = Pre(); for (auto & e : preq) e = PreQ(); }
+    // The same registration for the plain QActs of row and segment mode (rows_q.hip): source pointer -> the region of b.qa_pre that a quantising
+    // producer wrote in its place. The f32 vector behind the pointer is NOT written; its only readers are the products that find it here.
+    struct PreQ { const float * x = nullptr; int64_t K = 0; QAct qa; } preq[ROWS_Q_BATCH];
+    // regions for the n outputs `keys` of a producer whose consumers are Ws (row length D each), when rows_q_admits says so. A draft pass is
+    // admitted: what it stashes are the recurrences' inputs and the mixes' input b.xn, never a vector these producers leave unwritten.
+    bool rows_q_outs(int n, float * const * keys, const DevTensor * const * Ws, QAct * qs) {
+        int wt[ROWS_Q_BATCH];
+        for (int i = 0; i < n && i < ROWS_Q_BATCH; i++) { wt[i] = Ws[i]->type; if (Ws[i]->cols() != D) return false; }
+        if (!rows_q_admits(n, wt, T, D, state.rows || state.segs, ctx->prof.on)) return false;
+        drop_pre();
+        for (int i = 0; i < n; i++) { qs[i] = b.qa_pre[i]; preq[i].x = keys[i]; preq[i].K = D; preq[i].qa = qs[i]; }
+        return true;
+    }
+    const QAct * find_preq(const float * x, int64_t K) const {
+        for (auto & e : preq) if (e.x && e.x == x && e.K == K) return &e.qa;
+        return nullptr;
+    }
     // tile images for n outputs of a fused mix (sequence mode, all consumers quantised with `wtype`): registered like prequant's
     // carries: the kernel that would write them takes x_prev from the row above (k_mix_seq_q) -- it has no segment form
     bool fused_outs(int n, float * const * keys, int wtype, TileAct * tas, bool carries = true) {
-        if (state.rows) return false;   // (row mode: the quantising mixes carry across rows; k_mix, FORM_ROWS + prequant instead)
-        if (state.segs && carries) return false;   // (segment mode: k_mix, FORM_SEGS + prequant; the per-token quantising kernels stay)
+        if (state.rows) return false;   // (row mode: the quantising mixes carry across rows; below k_mfma_min_tokens rows_q_outs, else k_mix, FORM_ROWS + prequant)
+        if (state.segs && carries) return false;   // (segment mode: likewise, FORM_SEGS; from k_mfma_min_tokens on the per-token quantising kernels stay)
         if (!(dtype_quantized(wtype) && T >= k_mfma_min_tokens && b.tiles[0] && D % 256 == 0 && n <= 5)) return false;
         for (auto & e : pre) e = Pre();
         for (int i = 0; i < n; i++) { tas[i] = tile_act_at(b.tiles[i], T, D); pre[i].x = keys[i]; pre[i].wtype = wtype; pre[i].K = D; pre[i].ta = tas[i]; }
@@ -448,12 +467,16 @@ struct Runner {
             if (!ta || Ws[i]->type != Ws[0]->type || Ws[i]->rows() != Ws[0]->rows() || Ws[i]->cols() != Ws[0]->cols()) batched = false; else tas[i] = *ta;
         }
         if (batched && launch_mmq_mfma_batched(n, Ws, tas, ys, epis, T, Ws[0]->rows(), &b.ws, st)) return;
-        // 2 .. 31 tokens (batched decode): the inputs are quantised one by one into their own regions, the products are one k_mmq_rows launch
+        // 2 .. 31 tokens (batched decode): the inputs are quantised one by one into their own regions -- or were written there by their producer
+        // (find_preq) --, the products are one k_mmq_rows launch
         bool rows = n <= ROWS_MM_BATCH && mmq_rows_admits(Ws[0]->type, T, Ws[0]->cols()) && Ws[0]->cols() == D && !ctx->prof.on;
         for (int i = 1; i < n && rows; i++) rows = Ws[i]->type == Ws[0]->type && Ws[i]->rows() == Ws[0]->rows() && Ws[i]->cols() == Ws[0]->cols();
         if (rows) {
             QAct qs[ROWS_MM_BATCH];
-            for (int i = 0; i < n; i++) { qs[i] = i == 0 ? b.qa : b.qa_more[i - 1]; launch_quantize_act(xs[i], T, D, qs[i], st); }
+            for (int i = 0; i < n; i++) {
+                if (const QAct * p = find_preq(xs[i], D)) { qs[i] = *p; continue; }   // (its producer wrote it: rows_q.hip)
+                qs[i] = i == 0 ? b.qa : b.qa_more[i - 1]; launch_quantize_act(xs[i], T, D, qs[i], st);
+            }
             launch_mmq_rows(n, Ws, qs, ys, epis, T, Ws[0]->rows(), st);
             return;
         }
@@ -485,7 +508,8 @@ struct Runner {
             if (!launch_mmq_mfma(*W, ta, T, y, N, epi, st, &b.ws)) { ctx->last_error |= RWKV_ERROR_GRAPH | RWKV_ERROR_ALLOC; failed = true; }
             if (pf.on) { (void) hipEventRecord(pf.events[pf.used * 2 + 1], st); pf.used++; }
         } else if (dtype_quantized(W->type)) {
-            launch_quantize_act(x, T, K, b.qa, st);
+            const QAct * xq = find_preq(x, K);   // (row / segment mode: the producer wrote the QAct itself, rows_q.hip)
+            if (!xq) { launch_quantize_act(x, T, K, b.qa, st); xq = &b.qa; }
             auto & pf = ctx->prof;
             const bool timed = pf.on && T == 1 && W->type == (int) m.header.data_type;
             if (timed) {
@@ -498,7 +522,7 @@ struct Runner {
                 pf.bytes[pf.used] = W->nbytes + (uint64_t) K + (uint64_t)(K / 32) * 12 + (uint64_t) N * 4;
                 (void) hipEventRecord(pf.events[pf.used * 2], st);
             }
-            launch_matvec_q(*W, b.qa, T, y, N, epi, st);
+            launch_matvec_q(*W, *xq, T, y, N, epi, st);
             if (timed) { (void) hipEventRecord(pf.events[pf.used * 2 + 1], st); pf.used++; }
         } else {
             launch_matvec_f(*W, x, K, T, y, N, epi, st);
@@ -508,8 +532,12 @@ struct Runner {
     // input image itself (k_groupnorm_seq_q), the f32 values never leave the chip
     void gn_out(const LayerW & L, float eps, const float * gate) {
         TileAct ta[1]; float * keys[1] = {b.out};
+        QAct q[1];
         if (fused_outs(1, keys, L.att_output->type, ta, false) && !ctx->prof.on &&
             launch_groupnorm_seq_q(b.out, f(L.att_ln_x_w), f(L.att_ln_x_b), eps, gate, T, H, S, ta[0], L.att_output->type, st)) {}
+        // row / segment mode: the norm writes the projection's plain QAct (k_groupnorm_rows_q)
+        else if (rows_q_outs(1, keys, &L.att_output, q) &&
+                 launch_groupnorm_rows_q(b.out, f(L.att_ln_x_w), f(L.att_ln_x_b), eps, gate, T, H, S, q[0], rows_q_is_q81(L.att_output->type), st)) {}
         else { drop_pre(); launch_groupnorm(b.out, f(L.att_ln_x_w), f(L.att_ln_x_b), eps, gate, nullptr, nullptr, nullptr, nullptr, T, H, S, st); }
         mm(L.att_output, b.out, b.x, epi(EPI_ADD_RES, nullptr, b.x));
         drop_pre();
@@ -534,6 +562,13 @@ struct Runner {
     }
     // token-shift mix whose carry sits at offset co of a state buffer
     void mix(const MixArgs & a, int64_t co) { launch_mix(a, state.at(co), T, D, st); }
+    // the att mix of RWKV-4 / 5, outputs k, v, r (, g): in row / segment mode as the plain QActs of their four products (k_mix_rows_q)
+    void mix_att(const MixArgs & a, int64_t co, const LayerW & L, int n) {
+        const DevTensor * Ws[4] = {L.att_key, L.att_value, L.att_receptance, L.att_gate};
+        QAct qs[ROWS_Q_BATCH];
+        if (rows_q_outs(n, a.out, Ws, qs)) launch_mix_rows_q(a, state.at(co), T, D, qs, rows_q_is_q81(L.att_key->type), st);
+        else mix(a, co);
+    }
     static const float * f(const DevTensor * t) { return (const float *) t->data; }
     static Epi epi(int op, const float * bias = nullptr, const float * res = nullptr, const float * aux = nullptr) {
         Epi e; e.op = op; e.bias = bias; e.res = res; e.aux = aux; return e;
@@ -548,10 +583,14 @@ struct Runner {
         else { a.mode = 1; a.n_out = 1; a.coef[0] = f(L.ffn_x_k); }
         a.out[0] = b.m[0]; a.out[1] = b.m[1];
         TileAct tas[5];
+        QAct qs[ROWS_Q_BATCH];
         if ((m.arch_major == 7 || L.ffn_receptance->type == L.ffn_key->type) && L.ffn_key->cols() == D && fused_outs(a.n_out, a.out, L.ffn_key->type, tas)) {
             // sequence mode: the mix writes its outputs (RWKV-7: its one output) as quantised tile images (their only consumers are the products below)
             a.out[0] = nullptr; a.out[1] = nullptr; a.carry_in = state.in + so; a.carry_out = state.out + so;
             launch_mix_seq_q(a, T, D, st, tas, L.ffn_key->type);
+        } else if (const DevTensor * Ws[2] = {L.ffn_key, L.ffn_receptance}; rows_q_outs(a.n_out, a.out, Ws, qs)) {
+            // row / segment mode: the mix writes its outputs as the plain QActs of the products below (k_mix_rows_q)
+            launch_mix_rows_q(a, state.at(so), T, D, qs, rows_q_is_q81(L.ffn_key->type), st);
         } else {
             mix(a, so);
             if (m.arch_major != 7) { const float * xs[2] = {b.m[0], b.m[1]}; prequant(2, xs, D, L.ffn_key->type); }
@@ -583,10 +622,11 @@ struct Runner {
         MixArgs a; a.xn = b.xn; a.mode = 0; a.n_out = 3;
         a.coef[0] = f(L.att_time_mix_k); a.coef[1] = f(L.att_time_mix_v); a.coef[2] = f(L.att_time_mix_r);
         a.out[0] = b.m[0]; a.out[1] = b.m[1]; a.out[2] = b.m[2];
-        mix(a, so + D);
+        mix_att(a, so + D, L, 3);
         mm(L.att_receptance, b.m[2], b.r, epi(EPI_SIGMOID));
         mm(L.att_key, b.m[0], b.k);
         mm(L.att_value, b.m[1], b.v);
+        drop_pre();
         launch_wkv4(b.k, b.v, b.r, f(L.att_time_first), f(L.att_time_decay), seg ? seg_short(so + 2 * D) : state.at(so + 2 * D), b.out, T, D, st);
         mm(L.att_output, b.out, b.x, epi(EPI_ADD_RES, nullptr, b.x));
     }
@@ -599,11 +639,12 @@ struct Runner {
         a.coef[0] = f(L.att_time_mix_k); a.coef[1] = f(L.att_time_mix_v); a.coef[2] = f(L.att_time_mix_r);
         if (v52) a.coef[3] = f(L.att_time_mix_g);
         for (int i = 0; i < 4; i++) a.out[i] = b.m[i];
-        mix(a, so + D);
+        mix_att(a, so + D, L, a.n_out);
         mm(L.att_receptance, b.m[2], b.r);
         mm(L.att_key, b.m[0], b.k);
         mm(L.att_value, b.m[1], b.v);
         if (v52) mm(L.att_gate, b.m[3], b.g, epi(EPI_SILU));
+        drop_pre();
         wkv6(b.r, b.k, b.v, v52 ? f(L.att_time_faaaa) : f(L.att_time_first), v52 ? 1 : 0, f(L.att_time_decay), v52 ? 1 : 0,
              so + 2 * D, b.out);
         gn_out(L, 1e-5f, v52 ? b.g : nullptr);
@@ -621,6 +662,9 @@ struct Runner {
             if (fused_outs(1, a.out, L.att_time_maa_w1->type, ta) && getenv("RWKV_MI_NO_MIX_QUANT") == nullptr) {
                 MixArgs q = a; q.out[0] = nullptr; q.carry_in = state.in + so + D; q.carry_out = state.out + so + D;
                 if (!launch_mix_seq_q(q, T, D, st, ta, L.att_time_maa_w1->type)) { drop_pre(); mix(a, so + D); }
+            } else if (QAct q[1]; rows_q_outs(1, a.out, &L.att_time_maa_w1, q)) {
+                // row / segment mode: the same with the plain QAct (k_mix_rows_q; it writes sx and the carry as k_mix does)
+                launch_mix_rows_q(a, state.at(so + D), T, D, q, rows_q_is_q81(L.att_time_maa_w1->type), st);
             } else { drop_pre(); mix(a, so + D); }
         }
         const int64_t R5 = L.att_time_maa_w1->ne[1], R = R5 / 5;
@@ -641,6 +685,12 @@ struct Runner {
                 fused_q = launch_v6_mix2_seq(v, T, D, R, st, tas, wt);
                 if (!fused_q) { drop_pre(); for (int i = 0; i < 5; i++) v.out[i] = b.m[i]; }
             }
+        }
+        if (!fused_q) {
+            // row / segment mode: the five mixed inputs leave the kernel as plain QActs (k_v6_mix2_rows_q), in v.out's order
+            const DevTensor * Ws[5] = {L.att_time_decay_w1, L.att_key, L.att_value, L.att_receptance, L.att_gate};
+            QAct qs[ROWS_Q_BATCH];
+            if (rows_q_outs(5, v.out, Ws, qs)) { launch_v6_mix2_rows_q(v, T, D, R, qs, rows_q_is_q81(Ws[0]->type), st); fused_q = true; }
         }
         if (!fused_q && !(T >= k_mfma_min_tokens && launch_v6_mix2_seq(v, T, D, R, st))) launch_v6_mix2(v, T, D, R, st);
         {

@@ -154,6 +154,30 @@ __device__ __forceinline__ float round_f16(float x) {
     return __half2float(__float2half_rn(x));
 }
 
+// the forms of a recurrence (recur.hip, "The forms of a recurrence")
+enum : int { FORM_SEQ = 0, FORM_ROWS = 1, FORM_SEGS = 2 };
+
+// The per-element statements of the token-shift mixes, one rounding per statement (kernels.h, MixArgs). k_mix (recur.hip) and its quantising
+// row forms (rows_q.hip) go through these.
+__device__ __forceinline__ float mix_lerp_v4(float x, float xp, float c) { const float xc = x * c, pc = xp * c; return xc + (xp - pc); }   // mode 0
+__device__ __forceinline__ float mix_lerp_v6(float x, float sx, float c) { const float sc = sx * c; return sc + x; }                       // mode 1, sx = xp - x
+// element (t, f, d) of the RWKV-6 data-dependent mix (kernels.h, V6Mix2Args): k_v6_mix2 (recur.hip) and its quantising row form (rows_q.hip)
+__device__ __forceinline__ float v6_mix2_elem(const V6Mix2Args & a, int64_t t, int64_t f, int64_t d, int64_t D, int64_t R) {
+    const float * col = a.w2 + f * R * D + d;  // W2 is stored transposed at load: [5][R][D]
+    const float * tl = a.tl + t * 5 * R + f * R;
+    float acc = 0.0f;
+    for (int64_t m = 0; m < R; m++) acc += col[m * D] * tl[m];
+    const int64_t o = t * D + d;
+    const float mm = (acc + a.maa[f][d]) * a.sx[o];
+    return mm + a.xn[o];
+}
+// the group norm's element behind its head's statistics (k_groupnorm without the RWKV-7 bonus)
+__device__ __forceinline__ float groupnorm_elem(float x, float mean, float scale, float w, float b) {
+    float y = (x - mean) * scale;
+    y = y * w;
+    return y + b;
+}
+
 // LayerNorm partials of thread t < 256: elements t, t + 256, ... of a row in LDS, accumulated in that order (DESIGN.md
 // section 4). The LDS reads go out eight at a time: as a plain loop every iteration waits for its own read.
 __device__ __forceinline__ double ln_partial_sum(const float * l_row, int64_t D) {

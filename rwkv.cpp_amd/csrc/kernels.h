@@ -1,5 +1,5 @@
 // kernels.h -- host-callable launchers of the gfx950 kernels of matvec.hip, recur.hip and kernels.hip (and, where a comment names the file, of
-// rows_mm.hip, rows_mf.hip, prefill.hip and score.hip). All launches are asynchronous on `st`.
+// rows_mm.hip, rows_mf.hip, rows_q.hip, prefill.hip and score.hip). All launches are asynchronous on `st`.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -65,6 +65,7 @@ extern std::atomic<unsigned long long> g_mmf_rows_launches;   // launches of k_m
 
 // matvec.hip: x[T][K] f32 -> QAct
 void launch_quantize_act(const float * x, int64_t T, int64_t K, const QAct & out, hipStream_t st);
+extern std::atomic<unsigned long long> g_quant_act_launches;   // launch_quantize_act calls so far (test hook reads it)
 
 // ---- kernels.hip: embedding + ln0, layer norms (elementwise helpers, argmax and the load-time kernels: further down) ----
 
@@ -164,6 +165,20 @@ struct DraftLayer { const float * u; const float * w; };
 // keep[i] == t1 - t0 is left alone. keep is read on the device. lw: [n_layers] on the device (v7: may be nullptr).
 void launch_draft_replay(const DraftStash & d, const DraftLayer * lw, int arch_major, int arch_minor, const SegState * segs, int64_t n_segs,
                          const uint32_t * keep, int64_t n_layers, int64_t D, int64_t H, int64_t S, hipStream_t st);
+
+// rows_q.hip: the quantising row / segment forms of launch_mix, launch_v6_mix2 and launch_groupnorm (no RWKV-7 bonus) for passes of rows or
+// segments below k_mfma_min_tokens tokens: the same f32 values, written only as the plain QAct launch_quantize_act would make of them (outs[f]
+// for output f; q81: the consumers read s). The mix still writes the carry of `s` and a.sx; a.out / x are not written. rows_q_admits is the
+// gate (RWKV_MI_ROWS_Q=plain: never; =nomix2: never for the five outputs of launch_v6_mix2): n consumers of row length K with weights of wtypes[], every one quantised and of one activation kind.
+constexpr int ROWS_Q_BATCH = 5;
+inline bool rows_q_is_q81(int wtype) { return wtype == T_Q4_1 || wtype == T_Q5_1; }
+bool rows_q_admits(int n, const int * wtypes, int64_t T, int64_t K, bool rows_or_segs, bool prof_on);
+void launch_mix_rows_q(const MixArgs & a, const StateRef & s, int64_t T, int64_t D, const QAct * outs, bool q81, hipStream_t st);   // a.n_out <= ROWS_Q_BATCH
+void launch_v6_mix2_rows_q(const V6Mix2Args & a, int64_t T, int64_t D, int64_t R, const QAct * outs, bool q81, hipStream_t st);
+// false (nothing launched): a head size that is no multiple of the 32-element block
+bool launch_groupnorm_rows_q(const float * x, const float * lw, const float * lb, float eps, const float * gate, int64_t T, int64_t H, int64_t S,
+                             const QAct & out, bool q81, hipStream_t st);
+extern std::atomic<unsigned long long> g_rows_q_launches;   // launches of the three kernels so far (test hook reads it)
 
 // Per-head group norm * ln_x.w + ln_x.b, optional v7 bonus (+ v * sum_head(k*r*r_k)), optional gate multiply
 // (rwkv_graph.inc:280-289, 375-382, 465-479). In place on x[T][H*S].

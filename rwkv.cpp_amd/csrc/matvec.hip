@@ -715,8 +715,11 @@ __global__ __launch_bounds__(256) void k_quant_act(const float * __restrict__ x,
     }
 }
 
+std::atomic<unsigned long long> g_quant_act_launches{0};
+
 void launch_quantize_act(const float * x, int64_t T, int64_t K, const QAct & out, hipStream_t st) {
     const int64_t n_blocks = T * K / 32;
+    g_quant_act_launches.fetch_add(1, std::memory_order_relaxed);
     const unsigned grid = (unsigned)((n_blocks * 32 + 255) / 256);
     hipLaunchKernelGGL(k_quant_act, dim3(grid), dim3(256), 0, st, x, n_blocks, out.q, out.d, out.s, out.isum);
 }

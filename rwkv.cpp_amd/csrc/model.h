@@ -373,6 +373,7 @@ struct rwkv_context {
         float *x, *xn, *sx, *m[6], *r, *k, *v, *g, *w, *a, *t0, *t1, *t2, *out, *ffk, *lr1, *lr2, *v_first, *xlast;
         rwkvmi::QAct qa;
         rwkvmi::QAct qa_more[3];   // rows of length D: with qa, the inputs of up to four products that go out as one k_mmq_rows launch (mm_batch)
+        rwkvmi::QAct qa_pre[rwkvmi::ROWS_Q_BATCH];   // rows of length D: what the quantising row producers write (rows_q.hip; Runner::preq names their owners)
         void * tile = nullptr;   // tile-major quantised activations (T >= k_mfma_min_tokens)
         void * tiles[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // the same for inputs quantised ahead, several per launch (row length D)
         rwkvmi::MmqWs ws;         // workspace of the split walk (prefill.hip)

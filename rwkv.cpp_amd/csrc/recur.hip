@@ -13,7 +13,7 @@ namespace rwkvmi {
 // The StateRef is the LAST kernel argument: what a form reads together (out and H; off and rows or segs) then lies together in the argument
 // block and comes in as many scalar loads as a kernel of that form alone would need.
 // ---------------------------------------------------------------------------------------------------------------
-enum : int { FORM_SEQ = 0, FORM_ROWS = 1, FORM_SEGS = 2 };
+// (the enum itself: kdev.h, the quantising row forms of rows_q.hip take the same parameter)
 
 struct FormSpan { const float * in; float * out; int64_t t0, t1; };
 template <int FORM> __device__ __forceinline__ FormSpan form_span(const StateRef & s, int64_t T) {
@@ -43,11 +43,11 @@ static unsigned form_grid_y(const StateRef & s, int64_t T) { return s.segs ? (un
 // the lerps of element idx (channel d) given x and x_prev; the forms of k_mix differ only in where x_prev comes from and the carry goes
 __device__ __forceinline__ void mix_elem(const MixArgs & a, int64_t idx, int64_t d, float x, float xp) {
     if (a.mode == 0) {
-        for (int f = 0; f < a.n_out; f++) { const float c = a.coef[f][d]; const float xc = x * c, pc = xp * c; a.out[f][idx] = xc + (xp - pc); }
+        for (int f = 0; f < a.n_out; f++) a.out[f][idx] = mix_lerp_v4(x, xp, a.coef[f][d]);
     } else {
         const float sx = xp - x;
         if (a.sx) a.sx[idx] = sx;
-        for (int f = 0; f < a.n_out; f++) { const float sc = sx * a.coef[f][d]; a.out[f][idx] = sc + x; }
+        for (int f = 0; f < a.n_out; f++) a.out[f][idx] = mix_lerp_v6(x, sx, a.coef[f][d]);
     }
 }
 
@@ -86,13 +86,7 @@ __global__ __launch_bounds__(256) void k_v6_mix2(V6Mix2Args a, int64_t T, int64_
         const int64_t d = idx % D;
         const int64_t f = (idx / D) % 5;
         const int64_t t = idx / (5 * D);
-        const float * col = a.w2 + f * R * D + d;  // W2 is stored transposed at load: [5][R][D]
-        const float * tl = a.tl + t * 5 * R + f * R;
-        float acc = 0.0f;
-        for (int64_t m = 0; m < R; m++) acc += col[m * D] * tl[m];
-        const int64_t o = t * D + d;
-        const float mm = (acc + a.maa[f][d]) * a.sx[o];
-        a.out[f][o] = mm + a.xn[o];
+        a.out[f][t * D + d] = v6_mix2_elem(a, t, f, d, D, R);
     }
 }
 
@@ -553,9 +547,7 @@ __global__ __launch_bounds__(256) void k_groupnorm(float * __restrict__ x, const
         bonus = wave_sum_f(p);
     }
     for (int64_t j = lane; j < S; j += WAVE) {
-        float y = (x[base + j] - mean) * scale;
-        y = y * lw[h * S + j];
-        y = y + lb[h * S + j];
+        float y = groupnorm_elem(x[base + j], mean, scale, lw[h * S + j], lb[h * S + j]);
         if (v7_k) y += v7_v[base + j] * bonus;
         if (gate) y *= gate[base + j];
         x[base + j] = y;

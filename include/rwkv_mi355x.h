@@ -542,11 +542,49 @@ RWKV_API bool rwkv_mi_batch_eval_draft(struct rwkv_mi_batch * batch, const uint3
  * logits; the greedy loops and beam search do not read the setting. rwkv_mi_batch_state_copy has no bit for it.
  * set returns false with RWKV_ERROR_ARGS and changes nothing when the slot is out of range, when min_p is NaN, below 0 or above 1, or (the
  * context forms, as the penalised context calls) on a RWKV_MI_DEVICES chain. get: either pointer may be NULL.
- * OUT OF SCOPE: typical-p and tail-free sampling. */
+ * OUT OF SCOPE: tail-free sampling (typical-p and top-n-sigma: the shaping setting, below). */
 RWKV_API bool rwkv_mi_batch_truncation_set(struct rwkv_mi_batch * batch, size_t slot, uint32_t top_k, float min_p);
 RWKV_API bool rwkv_mi_batch_truncation_get(struct rwkv_mi_batch * batch, size_t slot, uint32_t * top_k_out, float * min_p_out);
 RWKV_API bool rwkv_mi_truncation_set(struct rwkv_context * ctx, uint32_t top_k, float min_p);
 RWKV_API bool rwkv_mi_truncation_get(struct rwkv_context * ctx, uint32_t * top_k_out, float * min_p_out);
+
+/* ---- Typical-p and top-n-sigma in the device sampler: per-sequence shaping settings ----
+ * A sequence -- a slot of a batch, or a context -- carries an optional SHAPING SETTING {typical_p, n_sigma}. It is kept like the truncation
+ * setting and read by exactly the draws that read that one (the list above: the single and ragged sampled passes and their penalised forms,
+ * the sampled and penalised loops, rwkv_mi_batch_decode_until, the walk of rwkv_mi_batch_eval_draft, guided slots, the context calls).
+ * n_sigma == 0: no floor; typical_p == 0 or typical_p == 1: no typical-p; {0, 0} is "none", the state at creation (a context made by
+ * rwkv_clone_context starts with none as well).
+ * THE ORDER of a draw (llama.cpp's chain):
+ *     the values the draw reads (logits / adjusted / with repetition; the guide's mask applied)
+ *       -> n-sigma floor -> top-k -> typical-p -> softmax -> top-p and min-p, intersected -> temperature
+ *   n-sigma (n_sigma > 0). Over the values v[j] the draw reads that are FINITE -- a NaN and +-inf enter no statistic -- let
+ *       M = max v,   mu = mean v,   sigma = sqrt(mean((v - mu)^2))
+ *   (the sums in double precision). A value below (float) (M - n_sigma * sigma) reads -inf, and so does a NaN, which is never kept. The
+ *   statistics are taken from the values BEFORE top-k, so the floor and top-k commute. When no value is finite nothing is cut.
+ *   typical-p (0 < typical_p < 1). Over the values w[j] that survive the floor and top-k (a NaN reads -inf), with m = max w, d = w - m,
+ *       e = exp(d),  Z = sum e,  p = e / Z,  H = -sum p ln p   (0 ln 0 = 0; the sums in f32, in the sampler's fixed order)
+ *       s[j] = |-ln p[j] - H| = |d[j] - (sum e d) / Z|
+ *   S* is the smallest key with sum{p[j] : s[j] <= S*} > typical_p, and every token with s[j] > S* reads -inf. All tokens AT the key S* are
+ *   kept; at least one token always survives. The masses are added as integers, (uint64) (p * 2^40) against (uint64) (typical_p * 2^40), so
+ *   S* does not depend on the order of the additions; when not even the whole mass exceeds the target (rounding, typical_p next to 1)
+ *   nothing is cut. A row of equal values has one key and is never cut.
+ *   The sampler then runs unchanged on these values: by construction the token is, bit for bit, what the sampler with the same truncation
+ *   setting picks from logits the caller had masked to -inf themselves.
+ *   A row with temperature == 0 is an argmax, which both cuts keep: it skips the two stages exactly as it skips top-k.
+ * With the setting "none" a draw is exactly the draw described above -- token, counter, counts, guide state -- and no call performs a launch,
+ * allocation or copy it did not perform before; with one, the call launches the truncating form of its draw kernel (as a truncation setting
+ * does) and nothing else. The logits are never written; the report still reads the model's logits; the greedy loops and beam search do not
+ * read the setting. It is stateless: rwkv_mi_batch_state_copy has no bit for it, and nothing of it lives on the device.
+ * rwkv_mi_batch_serve, _serve_ex and serve sessions do NOT read it: a request carries its own draw settings, which replace the slot's, and
+ * struct rwkv_mi_serve_request has no shaping words -- per-request shaping is out of scope.
+ * set returns false with RWKV_ERROR_ARGS and changes nothing when the slot is out of range, when typical_p is NaN, below 0 or above 1, when
+ * n_sigma is NaN, negative or infinite, (the batch form) while a serve session is open on the batch, or (the context forms, as the
+ * penalised context calls) on a RWKV_MI_DEVICES chain. get: either pointer may be NULL.
+ * OUT OF SCOPE: tail-free sampling (it needs the sorted order's second differences, and llama.cpp has dropped it); shaping per serve request. */
+RWKV_API bool rwkv_mi_batch_shaping_set(struct rwkv_mi_batch * batch, size_t slot, float typical_p, float n_sigma);
+RWKV_API bool rwkv_mi_batch_shaping_get(struct rwkv_mi_batch * batch, size_t slot, float * typical_p_out, float * n_sigma_out);
+RWKV_API bool rwkv_mi_shaping_set(struct rwkv_context * ctx, float typical_p, float n_sigma);
+RWKV_API bool rwkv_mi_shaping_get(struct rwkv_context * ctx, float * typical_p_out, float * n_sigma_out);
 
 /* ---- Penalty decay and repetition penalty in the device sampler: per-sequence repetition settings ----
  * A sequence -- a slot of a batch, or a context -- carries an optional REPETITION SETTING {decay, repetition}. It is kept like the truncation

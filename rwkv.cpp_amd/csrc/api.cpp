@@ -448,6 +448,20 @@ RWKV_API bool rwkv_mi_truncation_get(struct rwkv_context * ctx, uint32_t * top_k
     return true;
 }
 
+RWKV_API bool rwkv_mi_shaping_set(struct rwkv_context * ctx, float typical_p, float n_sigma) {
+    ctx->last_error = RWKV_ERROR_NONE;
+    RW_NO_PIPELINE(ctx, false);
+    return ctx->draw.shape_set(ctx, 0, typical_p, n_sigma);
+}
+
+RWKV_API bool rwkv_mi_shaping_get(struct rwkv_context * ctx, float * typical_p_out, float * n_sigma_out) {
+    ctx->last_error = RWKV_ERROR_NONE;
+    RW_NO_PIPELINE(ctx, false);
+    if (typical_p_out) *typical_p_out = ctx->draw.shapes[0].typical_p;
+    if (n_sigma_out) *n_sigma_out = ctx->draw.shapes[0].n_sigma;
+    return true;
+}
+
 // the penalty of a single-context draw: the context's counts and bias enter the logits; record: the chosen token is counted
 using Penalty = rwkv_mi_penalty_params;
 

@@ -1469,6 +1469,21 @@ RWKV_API bool rwkv_mi_batch_truncation_get(struct rwkv_mi_batch * B, size_t slot
     return true;
 }
 
+// (a set while a serve session is open is rejected: a session's lanes draw with their requests' settings, and the slot's would be read again
+//  only by calls the session rejects)
+RWKV_API bool rwkv_mi_batch_shaping_set(struct rwkv_mi_batch * B, size_t slot, float typical_p, float n_sigma) {
+    if (!batch_slot_call(B, slot)) return false;
+    RW_CTX_CHECK(B->ctx, RWKV_ERROR_ARGS, false, B->session == nullptr, "a serve session is open on this batch (rwkv_mi_batch_serve_close ends it)");
+    return B->draw.shape_set(B->ctx, slot, typical_p, n_sigma);
+}
+
+RWKV_API bool rwkv_mi_batch_shaping_get(struct rwkv_mi_batch * B, size_t slot, float * typical_p_out, float * n_sigma_out) {
+    if (!batch_slot_call(B, slot)) return false;
+    if (typical_p_out) *typical_p_out = B->draw.shapes[slot].typical_p;
+    if (n_sigma_out) *n_sigma_out = B->draw.shapes[slot].n_sigma;
+    return true;
+}
+
 RWKV_API bool rwkv_mi_batch_repetition_set(struct rwkv_mi_batch * B, size_t slot, float decay, float repetition) {
     return batch_slot_call(B, slot) && on_device(B->ctx) && B->draw.rep_set(B->ctx, slot, decay, repetition, B->run->stream);
 }

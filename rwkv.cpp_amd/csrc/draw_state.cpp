@@ -185,6 +185,15 @@ bool DrawState::cut_set(rwkv_context * ctx, size_t slot, uint32_t top_k, float m
     return true;
 }
 
+// the shaping setting of a slot: host words, read by every draw of the slot from the next call on
+bool DrawState::shape_set(rwkv_context * ctx, size_t slot, float typical_p, float n_sigma) {
+    // (written so that a NaN fails the comparison)
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, typical_p >= 0.0f && typical_p <= 1.0f, "typical_p (%g) must be in 0 .. 1", (double) typical_p);
+    RW_CTX_CHECK(ctx, RWKV_ERROR_ARGS, false, n_sigma >= 0.0f && n_sigma < INFINITY, "n_sigma (%g) must be finite and not below 0", (double) n_sigma);
+    shapes[slot] = ShapeRow{typical_p, n_sigma};
+    return true;
+}
+
 // the repetition setting of a slot: host words, read by every penalised draw of the slot from the next call on. The words of the slot's
 // occurrence row are floats exactly while decay != 1: a set that changes that zeroes the row (a table not yet allocated is zero already)
 bool DrawState::rep_set(rwkv_context * ctx, size_t slot, float decay, float repetition, hipStream_t st) {

@@ -111,14 +111,15 @@ constexpr int64_t k_mfma_min_tokens = 32;   // sequence calls of at least this m
 // ---- the device sampler (sampling.hip): temperature / top-k / top-p / min-p draws on logits in HBM ----
 // (rows.h, DrawRow: everything the draw of one row can read)
 constexpr uint16_t GUIDE_DEAD = 0xFFFF;   // a dead transition of a guide's table
-// the two settings as a sequence keeps them (DrawState's host words)
+// the three settings as a sequence keeps them (DrawState's host words)
 struct CutRow { uint32_t top_k; float min_p; };
 struct RepRow { float decay; float repetition; };
+struct ShapeRow { float typical_p; float n_sigma; };
 // What the kernel of a call is specialised on, decided ONCE per call from the sequences it names (DrawState::form): which choice is made --
 // the greedy argmax (none: no draw kernel runs), the sampler or the penalised sampler -- and which of the row's optional fields its kernel
 // reads. A call that uses none of a feature launches the kernel of before that feature:
 //   guided   a named sequence has a guide;   rep   the call is penalised and a named sequence has a repetition setting;
-//   cut      a named sequence has a truncation setting -- or guided, or rep: those kernels exist in the truncating form only.
+//   cut      a named sequence has a truncation or a shaping setting -- or guided, or rep: those kernels exist in the truncating form only.
 enum class Draw { none, sample, penalized };
 enum : int { SRC_PLAIN = 0, SRC_PEN = 1, SRC_REP = 2 };   // what a draw kernel reads (sampling.hip): logits, penalised, penalised with repetition
 struct DrawForm {
@@ -130,7 +131,7 @@ struct DrawForm {
     }
     // the form of a context's draw of `row`: its truncating kernel runs whenever a word of the setting is set (top_k >= n too, which truncates nothing)
     static DrawForm of_row(Draw draw, const DrawRow & row) {
-        return of(draw, row.top_k != 0u || row.min_p != 0.0f, false, row.decay != 1.0f || row.repetition != 1.0f);
+        return of(draw, row.top_k != 0u || row.min_p != 0.0f || row.typical_p != 0.0f || row.n_sigma != 0.0f, false, row.decay != 1.0f || row.repetition != 1.0f);
     }
 };
 // probs: scratch of sample_scratch_floats(n) floats (the vocabulary rounded up to whole chunks of the 1024 threads: the kernel keeps it transposed).
@@ -258,16 +259,20 @@ struct DrawState {
     // the repetition settings (rwkv_mi_*repetition_set): host words only, {1, 1} -- none -- from init() on; every PENALISED draw of the slot reads
     // them. A slot with decay != 1 is decaying: the words of its row of `counts` are floats (the row is zeroed when a set changes that)
     std::vector<RepRow> reps;              // [slots]
+    // the shaping settings (rwkv_mi_*shaping_set): host words only, {0, 0} -- none -- from init() on; every draw that reads `cuts` reads them
+    std::vector<ShapeRow> shapes;          // [slots]
 
     void init(size_t n_slots, size_t vocab) {
         slots = n_slots; n_vocab = vocab; has_bias.assign(n_slots, 0); guide_of.assign(n_slots, RWKV_MI_NO_GUIDE); cuts.assign(n_slots, CutRow{0u, 0.0f});
-        reps.assign(n_slots, RepRow{1.0f, 1.0f});
+        reps.assign(n_slots, RepRow{1.0f, 1.0f}); shapes.assign(n_slots, ShapeRow{0.0f, 0.0f});
     }
     unsigned long long * counter(size_t slot) const { return counters.p + slot; }
     uint32_t * counts_of(size_t slot) const { return counts.p + slot * n_vocab; }
     const float * bias_of(size_t slot) const { return has_bias[slot] ? bias.p + slot * n_vocab : nullptr; }   // NULL: none is set
     // whether the slot's setting truncates anything (top_k == 0 or >= n_vocab: no top-k; min_p == 0: no min-p)
     bool has_cut(size_t slot) const { return (cuts[slot].top_k != 0u && cuts[slot].top_k < n_vocab) || cuts[slot].min_p != 0.0f; }
+    // whether the slot's shaping setting cuts anything (typical_p == 0 or 1: no typical-p; n_sigma == 0: no floor)
+    bool has_shape(size_t slot) const { return (shapes[slot].typical_p > 0.0f && shapes[slot].typical_p < 1.0f) || shapes[slot].n_sigma > 0.0f; }
     bool decaying(size_t slot) const { return reps[slot].decay != 1.0f; }
     bool has_rep(size_t slot) const { return decaying(slot) || reps[slot].repetition != 1.0f; }
     // The row of a draw of `slot` -- the one place that knows where a sequence's counter, tables, guide words and settings live. pen (NULL: the
@@ -278,12 +283,13 @@ struct DrawState {
         const bool guided = guides && g != RWKV_MI_NO_GUIDE;
         return DrawRow{p, counter(slot), pen ? pen->presence : 0.0f, pen ? pen->frequency : 0.0f, pen ? record : 0u, pen ? counts_of(slot) : nullptr,
                        pen ? bias_of(slot) : nullptr, guided ? guides[g].p : nullptr, guided ? guide_state.p + slot : nullptr,
-                       guided ? guide_misses.p + slot : nullptr, cuts[slot].top_k, cuts[slot].min_p, reps[slot].decay, reps[slot].repetition};
+                       guided ? guide_misses.p + slot : nullptr, cuts[slot].top_k, cuts[slot].min_p, reps[slot].decay, reps[slot].repetition,
+                       shapes[slot].typical_p, shapes[slot].n_sigma};
     }
     // the form of a call that draws for the n named slots
     DrawForm form(Draw draw, const uint32_t * named, size_t n) const {
         bool cut = false, guided = false, rep = false;
-        for (size_t i = 0; i < n; i++) { cut |= has_cut(named[i]); guided |= guide_of[named[i]] != RWKV_MI_NO_GUIDE; rep |= has_rep(named[i]); }
+        for (size_t i = 0; i < n; i++) { cut |= has_cut(named[i]) || has_shape(named[i]); guided |= guide_of[named[i]] != RWKV_MI_NO_GUIDE; rep |= has_rep(named[i]); }
         return DrawForm::of(draw, cut, guided, rep);
     }
 
@@ -300,6 +306,7 @@ struct DrawState {
     bool guide_attach(rwkv_context * ctx, size_t slot, uint32_t guide, uint32_t state, hipStream_t st);
     bool guide_words(rwkv_context * ctx, size_t slot, uint32_t * state_out, uint32_t * misses_out, hipStream_t st);   // (0, 0 without a guide)
     bool cut_set(rwkv_context * ctx, size_t slot, uint32_t top_k, float min_p);   // min_p in [0, 1], or RWKV_ERROR_ARGS and nothing changed
+    bool shape_set(rwkv_context * ctx, size_t slot, float typical_p, float n_sigma);   // typical_p in [0, 1], n_sigma finite and >= 0, or likewise
     // decay in [0, 1], repetition finite and > 0, or RWKV_ERROR_ARGS and nothing changed; a set that changes whether the slot is decaying zeroes its row
     bool rep_set(rwkv_context * ctx, size_t slot, float decay, float repetition, hipStream_t st);
     bool counts_store_f32(rwkv_context * ctx, size_t slot, float * out, hipStream_t st);   // either kind of row, as floats

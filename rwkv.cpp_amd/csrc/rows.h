@@ -31,6 +31,10 @@ struct SegState { const float * in; float * out; int32_t t0, t1; };
 //                repetition: where the token has occurred, the logit is divided by it when positive and multiplied by it otherwise, in front
 //                of the penalty. decay != 1: the sequence is DECAYING -- the words of `count` hold floats, and a draw that records multiplies
 //                every one of them by decay before it adds 1.0f to the pick's. The arithmetic is spelled out in include/rwkv_mi355x.h
+//   typical_p, n_sigma   the shaping setting of the row's sequence (rwkv_mi_*shaping_set; {0, 0}: none), read where top_k is. n_sigma (0: off):
+//                of the values the draw would read, those below max - n_sigma * the standard deviation of the finite ones read -inf, in front
+//                of top-k. typical_p (0 or 1: off): of the values that survive that and top-k, those whose surprise -ln p lies further from
+//                the entropy than the key at which the mass of the nearer ones first exceeds typical_p read -inf, in front of the body
 struct DrawRow {
     rwkv_mi_sample_params p; unsigned long long * counter;
     float presence; float frequency; uint32_t record;
@@ -38,6 +42,7 @@ struct DrawRow {
     const uint16_t * next; uint32_t * state; uint32_t * misses;
     uint32_t top_k; float min_p;
     float decay; float repetition;
+    float typical_p; float n_sigma;
 };
 // A row's stop parameters and where its sequences start in the call's flat tables: its lengths at seq_lens[seq0 ..], its tokens at seq_tokens[tok0 ..].
 struct StopRow { uint32_t max_tokens, n_seqs, seq0, tok0; };

@@ -158,6 +158,7 @@ struct GuidedLogits {
 
 // What sample_body reads behind the select stage: the scratch vector in both passes (the stage has left the masked values there).
 struct StashedLogits {
+    static constexpr bool stashes = true;
     __device__ __forceinline__ float first(int j, const ProbVec & pr) const { return pr.get(j); }
     __device__ __forceinline__ float again(int j, const ProbVec & pr) const { return pr.get(j); }
 };
@@ -235,6 +236,171 @@ __device__ __forceinline__ void select_stage(const Src & src, int cnt, uint32_t 
         if (!keep || key == 0u) pr.set(j, -INFINITY);
     });
     __syncthreads();
+}
+
+// The n-sigma floor of a row with n_sigma > 0, in front of everything else that cuts: over the values the draw would read -- src.first() over
+// the thread's chunk, stashed in the scratch vector -- the maximum M, the count and the sums of v and v * v of the FINITE ones, each in one
+// pass; a NaN or an infinity enters none of them. The sums are doubles (a float squares exactly into one; 65 536 of them leave the mean and
+// the variance good to 1e-12, so sigma^2 = mean(v^2) - mean(v)^2 loses nothing to cancellation) in the file's fixed order: the thread's chunk,
+// the wave by butterfly, the 16 waves in index order. The floor is (float) (M - n_sigma * sigma); -inf when nothing is finite. LDS: 384 bytes.
+template <class Src>
+__device__ __forceinline__ float sigma_floor(const Src & src, int cnt, float n_sigma, const ProbVec & pr) {
+    __shared__ double f_sum[16], f_sq[16];
+    __shared__ float f_max[16];
+    __shared__ uint32_t f_cnt[16];
+    const int tid = threadIdx.x, waves = blockDim.x >> 6;
+    float mx = -INFINITY;
+    double sum = 0.0, sq = 0.0;
+    uint32_t fin = 0u;
+    for_chunk(cnt, [&](int j) {
+        const float a = src.first(j, pr);
+        if (!Src::stashes) pr.set(j, a);
+        if (fabsf(a) < INFINITY) { const double d = (double) a; mx = fmaxf(mx, a); sum += d; sq += d * d; fin++; }   // (a NaN fails the comparison)
+    });
+    for (int o = 32; o > 0; o >>= 1) {
+        mx = fmaxf(mx, __shfl_xor(mx, o, WAVE));
+        sum += __shfl_xor(sum, o, WAVE);
+        sq += __shfl_xor(sq, o, WAVE);
+        fin += __shfl_xor(fin, o, WAVE);
+    }
+    if ((tid & 63) == 0) { f_max[tid >> 6] = mx; f_sum[tid >> 6] = sum; f_sq[tid >> 6] = sq; f_cnt[tid >> 6] = fin; }
+    __syncthreads();
+    mx = -INFINITY; sum = 0.0; sq = 0.0; fin = 0u;
+    for (int w = 0; w < waves; w++) { mx = fmaxf(mx, f_max[w]); sum += f_sum[w]; sq += f_sq[w]; fin += f_cnt[w]; }
+    __syncthreads();   // (the words are free for the row's next draw: the draft walk calls again)
+    if (fin == 0u) return -INFINITY;
+    const double mean = sum / (double) fin;
+    const double var = sq / (double) fin - mean * mean;
+    return (float) ((double) mx - (double) n_sigma * sqrt(var > 0.0 ? var : 0.0));
+}
+
+// What everything behind sigma_floor reads -- the select stage, the typical stage or the body itself: the stashed value, -inf where it lies
+// below the floor or is a NaN (which is never kept). The element is rewritten where it changes, so again() finds the masked value and no
+// sweep of its own applies the floor.
+struct FlooredLogits {
+    static constexpr bool stashes = true;
+    float floor;
+    __device__ __forceinline__ float first(int j, const ProbVec & pr) const {
+        float a = pr.get(j);
+        if (!(a >= floor)) { a = -INFINITY; pr.set(j, a); }
+        return a;
+    }
+    __device__ __forceinline__ float again(int j, const ProbVec & pr) const { return pr.get(j); }
+};
+
+// lane l's value from lane l - o of its wave (o <= l), in halves: the 64-bit running masses of the typical stage
+__device__ __forceinline__ unsigned long long shfl_up_u64(unsigned long long v, int o) {
+    const uint32_t lo = __shfl_up((uint32_t) v, o, WAVE), hi = __shfl_up((uint32_t) (v >> 32), o, WAVE);
+    return ((unsigned long long) hi << 32) | lo;
+}
+
+// The typical stage of a row with 0 < typical_p < 1, in front of sample_body and behind the floor and the select stage: of the values w the
+// draw would read -- src.first() over the thread's chunk, stashed; a NaN reads -inf -- with p = softmax(w), H = -sum p ln p and the key
+//   s[j] = |-ln p[j] - H|,
+// every token whose key lies above S* is overwritten with -inf, S* the smallest key with sum{p[j] : s[j] <= S*} > typical_p. The whole class
+// at S* stays; when no prefix exceeds typical_p -- rounding of the masses near typical_p = 1 -- nothing is cut.
+//   statistics  the maximum m, then Z = sum e and A = sum e * d in one pass, e = det_expf(d), d = w - m (a token with e == 0 adds nothing:
+//               0 ln 0 = 0), f32 in the body's order. With a = A / Z the key needs neither logarithm nor exponential:
+//               -ln p - H = (ln Z - d) - (ln Z - a) = a - d, so s = |d - a|, a non-negative float whose bit order is its value order.
+//   selection   a byte-radix select on the key's bits, most significant byte first, as in select_stage, but the histogram holds MASS, and
+//               the prefix grows towards the SMALLEST key whose running mass exceeds the target. A token's mass is the integer
+//               q = (uint64) (p * 2^40), p = e * (1 / Z): integer addition is associative, so S* does not depend on the order in which the
+//               atomics arrive, and the host can restate it exactly; 65 536 tokens stay below 2^57. The target is (uint64) (typical_p * 2^40).
+//   contention  the top byte of the key puts nearly every token in two or three bins, so each of the 16 waves has a histogram of its own and
+//               a thread folds the run of equal bins of its chunk in registers before it touches LDS; a token without mass adds nothing.
+//               The 16 histograms are summed by 256 threads in wave order, and wave 0 scans the 256 bins: lane l holds bins 4 l .. 4 l + 3
+//               and an inclusive scan over the lanes finds the one lane in which the running mass first exceeds the target.
+//   data        every pass re-reads the stash and recomputes p -- one det_expf per token per pass, 5 in all; no second vector is kept. A last
+//               pass writes -inf where s > S*.
+// LDS: 16 x 256 x 8 = 32 768 bytes of histograms, 128 of reduction words, 64 of the first pass and 16 of results -- 32 976 in all, beside
+// the three bodies' 4 368 each (l_scan and their words, one set per source type), select_stage's 1 104 and the floor's 384: a CUT kernel has
+// 48 664 bytes, of the 64 KB a workgroup may have. Every thread takes the same branches (the LDS words are uniform); the stage ends behind a
+// barrier.
+// (the part of the stage behind its first pass -- the row's values are in the stash, their maximum is m: one function whatever the source
+//  was, so the stage's LDS exists once in a kernel)
+__device__ __forceinline__ void typical_select(int cnt, float m, float typical_p, const ProbVec & pr) {
+    __shared__ unsigned long long t_hist[16][256];
+    __shared__ float t_red[32];
+    __shared__ unsigned long long t_below;
+    __shared__ uint32_t t_digit, t_found;
+    const int tid = threadIdx.x, wave = tid >> 6;
+    float z = 0.0f, ad = 0.0f;
+    for_chunk(cnt, [&](int j) { const float d = pr.get(j) - m, e = det_expf(d); if (e > 0.0f) { z += e; ad += e * d; } });
+    const float Z = block_sum_f(z, t_red);
+    const float A = block_sum_f(ad, t_red);
+    // (nothing finite, or a +inf: there is no distribution to shape, and the body sees the values as they are)
+    if (Z > 0.0f && Z < INFINITY) {
+        const float inv = 1.0f / Z, a = A / Z;
+        const unsigned long long target = (unsigned long long) ((double) typical_p * 1099511627776.0);
+        auto key_of = [&](float d) { return __float_as_uint(fabsf(d - a)); };
+        auto mass_of = [&](float d) { return (unsigned long long) ((det_expf(d) * inv) * 1099511627776.0f); };
+        uint32_t kth = 0u;                  // the prefix of S*
+        unsigned long long below = 0ull;    // the mass of the keys under that prefix
+        bool cuts = true;
+        for (int shift = 24; shift >= 0 && cuts; shift -= 8) {
+            for (int i = tid; i < 16 * 256; i += blockDim.x) (&t_hist[0][0])[i] = 0ull;
+            __syncthreads();
+            const uint32_t above_mask = shift == 24 ? 0u : 0xFFFFFFFFu << (shift + 8);
+            uint32_t run_bin = 0u;
+            unsigned long long run = 0ull;
+            for_chunk(cnt, [&](int j) {
+                const float d = pr.get(j) - m;
+                const uint32_t key = key_of(d);
+                if ((key & above_mask) != kth) return;
+                const unsigned long long q = mass_of(d);
+                if (q == 0ull) return;
+                const uint32_t bin = (key >> shift) & 255u;
+                if (bin != run_bin && run) { atomicAdd(&t_hist[wave][run_bin], run); run = 0ull; }
+                run_bin = bin; run += q;
+            });
+            if (run) atomicAdd(&t_hist[wave][run_bin], run);
+            __syncthreads();
+            if (tid < 256) {
+                unsigned long long all = 0ull;
+                for (int w = 0; w < 16; w++) all += t_hist[w][tid];
+                t_hist[0][tid] = all;
+            }
+            if (tid == 0) t_found = 0u;
+            __syncthreads();
+            if (tid < 64) {
+                unsigned long long h[4];
+                for (int b = 0; b < 4; b++) h[b] = t_hist[0][4 * tid + b];
+                const unsigned long long own = h[0] + h[1] + h[2] + h[3];
+                unsigned long long inc = own;
+                for (int o = 1; o < 64; o <<= 1) { const unsigned long long v = shfl_up_u64(inc, o); if (tid >= o) inc += v; }
+                unsigned long long under = below + (inc - own);
+                if (under <= target && under + own > target) {   // (at most one lane)
+                    int b = 0;
+                    while (b < 3 && under + h[b] <= target) { under += h[b]; b++; }
+                    t_digit = (uint32_t) (4 * tid + b); t_below = under; t_found = 1u;
+                }
+            }
+            __syncthreads();
+            cuts = t_found != 0u;   // (the first pass alone can miss: the mass of a found bin is the sum of its sub-bins, exactly)
+            if (cuts) { kth |= t_digit << shift; below = t_below; }
+        }
+        if (cuts) for_chunk(cnt, [&](int j) { if (key_of(pr.get(j) - m) > kth) pr.set(j, -INFINITY); });
+    }
+    __syncthreads();
+}
+
+template <class Src>
+__device__ __forceinline__ void typical_stage(const Src & src, int cnt, float typical_p, const ProbVec & pr) {
+    __shared__ float t_max[16];
+    const int tid = threadIdx.x;
+    float m = -INFINITY;
+    for_chunk(cnt, [&](int j) {
+        float w = src.first(j, pr);
+        const bool drop = w != w;
+        if (drop) w = -INFINITY;
+        if (drop || !Src::stashes) pr.set(j, w);
+        m = fmaxf(m, w);
+    });
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, WAVE));
+    if ((tid & 63) == 0) t_max[tid >> 6] = m;
+    __syncthreads();
+    for (int w = 0; w < (int) (blockDim.x >> 6); w++) m = fmaxf(m, t_max[w]);
+    typical_select(cnt, m, typical_p, pr);   // (ends behind a barrier: t_max is free for the row's next draw)
 }
 
 // What thread 0 does to a guided row's words after the draw (where the penalised rows count the token): the state moves along the picked
@@ -381,20 +547,40 @@ __device__ __forceinline__ int sample_body(MakeSrc && make_src, int n, float tem
     return pick;
 }
 
-// The draw of a sequence with the truncation setting `cut` (model.h, DrawRow): a row with top-k on runs the select stage on its source and
-// then the body on the stash; every other row runs the body on its source, exactly as before there were settings -- {0, 0} is that draw,
-// statement for statement. min-p is the body's. A row with temperature 0 is an argmax, which both truncations keep: it skips the stage
-// (and never reaches the body's min-p). The setting is the row's, so the whole workgroup takes one branch.
+// The draw of a sequence with the truncation setting `cut` and the shaping setting `shape` (model.h, DrawRow). The stages a row has on run in
+// the order n-sigma floor -> top-k -> typical-p, each on what the one before left, and then the body on the stash:
+//   floor     sigma_floor takes the statistics of the row's source, and everything behind it reads through FlooredLogits -- the select stage,
+//             the typical stage, or, where neither is on, the body itself;
+//   top-k     select_stage, on the source or on the floored stash;
+//   typical   typical_stage, on the source, the floored stash or what the select stage left.
+// A row with none of them on runs the body on its source, exactly as before there were settings -- {0, 0} and {0, 0} is that draw, statement
+// for statement. min-p is the body's. A row with temperature 0 is an argmax, which every cut keeps: it skips the stages (and never reaches
+// the body's min-p). The settings are the row's, so the whole workgroup takes one branch at each step.
 template <class MakeSrc>
-__device__ __forceinline__ int cut_sample(MakeSrc && make_src, const CutRow & cut, int n, float temperature, float top_p, float u_in,
+__device__ __forceinline__ int cut_sample(MakeSrc && make_src, const CutRow & cut, const ShapeRow & shape, int n, float temperature, float top_p, float u_in,
                                           unsigned long long seed, unsigned long long * counter, float * __restrict__ probs,
                                           uint32_t * __restrict__ out_token, uint32_t * __restrict__ hist_word) {
-    if (cut.top_k == 0u || cut.top_k >= (uint32_t) n || temperature == 0.0f)
+    const bool draws = temperature != 0.0f;
+    const bool top_k = draws && cut.top_k != 0u && cut.top_k < (uint32_t) n;
+    const bool sigma = draws && shape.n_sigma > 0.0f;
+    const bool typical = draws && shape.typical_p > 0.0f && shape.typical_p < 1.0f;
+    if (!top_k && !sigma && !typical)
         return sample_body(make_src, n, temperature, top_p, cut.min_p, u_in, seed, counter, probs, out_token, hist_word);
     const int tid = threadIdx.x, NT = blockDim.x;
     const int C = (n + NT - 1) / NT;   // (the body's chunks)
     const int i0 = tid * C, i1 = i0 + C < n ? i0 + C : n;
-    select_stage(make_src(i0), i1 - i0, cut.top_k, ProbVec{probs + tid, NT});
+    const int cnt = i1 - i0;
+    const ProbVec pr{probs + tid, NT};
+    if (sigma) {
+        const FlooredLogits fl{sigma_floor(make_src(i0), cnt, shape.n_sigma, pr)};
+        if (top_k) select_stage(fl, cnt, cut.top_k, pr);
+        else if (typical) typical_stage(fl, cnt, shape.typical_p, pr);
+        else return sample_body([=](int) { return fl; }, n, temperature, top_p, cut.min_p, u_in, seed, counter, probs, out_token, hist_word);
+        if (top_k && typical) typical_stage(StashedLogits{}, cnt, shape.typical_p, pr);
+    } else if (top_k) {
+        select_stage(make_src(i0), cnt, cut.top_k, pr);
+        if (typical) typical_stage(StashedLogits{}, cnt, shape.typical_p, pr);
+    } else typical_stage(make_src(i0), cnt, shape.typical_p, pr);
     return sample_body([](int) { return StashedLogits{}; }, n, temperature, top_p, cut.min_p, u_in, seed, counter, probs, out_token, hist_word);
 }
 
@@ -423,7 +609,7 @@ __device__ __forceinline__ int draw_row(const float * lg, int n, const DrawRow &
     };
     const rwkv_mi_sample_params & p = row.p;
     int pick;
-    if constexpr (CUT) pick = cut_sample(make_src, CutRow{row.top_k, row.min_p}, n, p.temperature, p.top_p, p.u, p.seed, row.counter, probs, out_token, hist_word);
+    if constexpr (CUT) pick = cut_sample(make_src, CutRow{row.top_k, row.min_p}, ShapeRow{row.typical_p, row.n_sigma}, n, p.temperature, p.top_p, p.u, p.seed, row.counter, probs, out_token, hist_word);
     else pick = sample_body(make_src, n, p.temperature, p.top_p, 0.0f, p.u, p.seed, row.counter, probs, out_token, hist_word);
     if constexpr (SRC == SRC_PEN) { if (threadIdx.x == 0 && record) row.count[pick] += 1u; }
     if constexpr (SRC == SRC_REP) rep_record(row.count, n, RepRow{row.decay, row.repetition}, record, pick);
@@ -436,10 +622,10 @@ __device__ __forceinline__ int draw_row(const float * lg, int n, const DrawRow &
 template <int SRC, bool CUT>
 __global__ __launch_bounds__(1024) void k_draw(const float * __restrict__ logits, int n, float temperature, float top_p, float u_in, unsigned long long seed,
                                                unsigned long long * counter, float presence, float frequency, uint32_t record, uint32_t * count,
-                                               const float * __restrict__ bias, CutRow cut, RepRow rep, float * __restrict__ probs,
+                                               const float * __restrict__ bias, CutRow cut, RepRow rep, ShapeRow shape, float * __restrict__ probs,
                                                uint32_t * __restrict__ out_token, uint32_t * __restrict__ hist, int hist_pos) {
     const DrawRow row{{temperature, top_p, u_in, seed}, counter, presence, frequency, record, count, bias, nullptr, nullptr, nullptr, cut.top_k, cut.min_p,
-                      rep.decay, rep.repetition};
+                      rep.decay, rep.repetition, shape.typical_p, shape.n_sigma};
     draw_row<SRC, CUT, false>(logits, n, row, record, probs, out_token, hist ? hist + hist_pos : nullptr);
 }
 
@@ -872,7 +1058,8 @@ void launch_draw(const float * logits, int n, const DrawRow & row, const DrawFor
                  hipStream_t st) {
     auto go = [&](auto kern) {
         hipLaunchKernelGGL(kern, dim3(1), dim3(1024), 0, st, logits, n, row.p.temperature, row.p.top_p, row.p.u, (unsigned long long) row.p.seed, row.counter, row.presence,
-                           row.frequency, row.record, row.count, row.bias, CutRow{row.top_k, row.min_p}, RepRow{row.decay, row.repetition}, probs, out_token, hist, hist_pos);
+                           row.frequency, row.record, row.count, row.bias, CutRow{row.top_k, row.min_p}, RepRow{row.decay, row.repetition},
+                           ShapeRow{row.typical_p, row.n_sigma}, probs, out_token, hist, hist_pos);
     };
     switch (form_id(form)) {
         case form_id(SRC_PLAIN, false, false): go(k_draw<SRC_PLAIN, false>); break;

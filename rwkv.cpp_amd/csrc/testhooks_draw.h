@@ -28,7 +28,7 @@ struct DrawHook {
              (!h_bias || hipMemcpy(bias.p, h_bias, R * V * 4, hipMemcpyHostToDevice) == hipSuccess);
         rows.resize(R);
         for (size_t r = 0; ok && r < R; r++)
-            rows[r] = DrawRow{params[r], ctr.p + r, 0.0f, 0.0f, 0u, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, 0.0f, 1.0f, 1.0f};
+            rows[r] = DrawRow{params[r], ctr.p + r, 0.0f, 0.0f, 0u, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, 0.0f, 1.0f, 1.0f, 0.0f, 0.0f};
         return ok;
     }
     // row r draws penalised from its occurrence row and, where there is one, its bias row

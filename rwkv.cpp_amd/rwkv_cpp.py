@@ -25,6 +25,8 @@ SAMPLE_HOOKS_LIB_PATH = os.path.join(PKG_DIR, os.environ.get("RWKV_LIB_DIR", "li
 GUIDE_HOOKS_LIB_PATH = os.path.join(PKG_DIR, os.environ.get("RWKV_LIB_DIR", "lib"), "librwkv_testhooks_guide.so")
 # tests/ only: the same objects + csrc/testhooks_cut.cpp (include/rwkv_testhooks_cut.h): the plain sampler with a truncation setting per row
 CUT_HOOKS_LIB_PATH = os.path.join(PKG_DIR, os.environ.get("RWKV_LIB_DIR", "lib"), "librwkv_testhooks_cut.so")
+# tests/ only: the same objects + csrc/testhooks_shape.cpp (include/rwkv_testhooks_shape.h): the plain sampler with a truncation and a shaping setting per row
+SHAPE_HOOKS_LIB_PATH = os.path.join(PKG_DIR, os.environ.get("RWKV_LIB_DIR", "lib"), "librwkv_testhooks_shape.so")
 
 # tests/ only: the same objects + csrc/testhooks_decay.cpp (include/rwkv_testhooks_decay.h): the penalised sampler with a repetition setting per row
 DECAY_HOOKS_LIB_PATH = os.path.join(PKG_DIR, os.environ.get("RWKV_LIB_DIR", "lib"), "librwkv_testhooks_decay.so")
@@ -46,6 +48,7 @@ GUIDE_MAX_STATES = 65535    # RWKV_MI_GUIDE_MAX_STATES: states per guide
 NO_GUIDE = 0xFFFFFFFF       # RWKV_MI_NO_GUIDE: a slot without a guide
 DRAFT_SYMBOLS = ("rwkv_mi_batch_eval_draft",)
 TRUNCATION_SYMBOLS = ("rwkv_mi_batch_truncation_set", "rwkv_mi_batch_truncation_get", "rwkv_mi_truncation_set", "rwkv_mi_truncation_get")
+SHAPING_SYMBOLS = ("rwkv_mi_batch_shaping_set", "rwkv_mi_batch_shaping_get", "rwkv_mi_shaping_set", "rwkv_mi_shaping_get")
 REPETITION_SYMBOLS = ("rwkv_mi_batch_repetition_set", "rwkv_mi_batch_repetition_get", "rwkv_mi_batch_counts_store_f32",
                       "rwkv_mi_repetition_set", "rwkv_mi_repetition_get", "rwkv_mi_counts_store_f32")
 DRAFT_MAX = 8               # RWKV_MI_DRAFT_MAX: draft tokens per row of RWKVBatch.eval_draft
@@ -128,6 +131,11 @@ class ServeEvent(ctypes.Structure):
 class CutParams(ctypes.Structure):
     """struct rwkv_mi_test_cut (include/rwkv_testhooks_cut.h): one row's truncation setting as the test hook takes it, 8 bytes."""
     _fields_ = [("top_k", ctypes.c_uint32), ("min_p", ctypes.c_float)]
+
+
+class ShapeParams(ctypes.Structure):
+    """struct rwkv_mi_test_shape (include/rwkv_testhooks_shape.h): one row's truncation and shaping settings as the test hook takes them, 16 bytes."""
+    _fields_ = [("top_k", ctypes.c_uint32), ("min_p", ctypes.c_float), ("typical_p", ctypes.c_float), ("n_sigma", ctypes.c_float)]
 
 
 class RepParams(ctypes.Structure):
@@ -387,6 +395,14 @@ class RWKVSharedLibrary:
             L.rwkv_mi_truncation_get.argtypes = [c_ctx, P_UINT32, P_FLOAT]
             for name in TRUNCATION_SYMBOLS:
                 getattr(L, name).restype = ctypes.c_bool
+        # typical-p and top-n-sigma: per-sequence shaping settings of the device sampler
+        if hasattr(L, "rwkv_mi_batch_shaping_set"):   # (absent from older A/B builds loaded through RWKV_LIB_DIR)
+            L.rwkv_mi_batch_shaping_set.argtypes = [c_batch, ctypes.c_size_t, ctypes.c_float, ctypes.c_float]
+            L.rwkv_mi_batch_shaping_get.argtypes = [c_batch, ctypes.c_size_t, P_FLOAT, P_FLOAT]
+            L.rwkv_mi_shaping_set.argtypes = [c_ctx, ctypes.c_float, ctypes.c_float]
+            L.rwkv_mi_shaping_get.argtypes = [c_ctx, P_FLOAT, P_FLOAT]
+            for name in SHAPING_SYMBOLS:
+                getattr(L, name).restype = ctypes.c_bool
         # penalty decay and repetition penalty: per-sequence repetition settings of the penalised draws
         if hasattr(L, "rwkv_mi_batch_repetition_set"):   # (absent from older A/B builds loaded through RWKV_LIB_DIR)
             L.rwkv_mi_batch_repetition_set.argtypes = [c_batch, ctypes.c_size_t, ctypes.c_float, ctypes.c_float]
@@ -407,6 +423,10 @@ class RWKVSharedLibrary:
             L.rwkv_mi_test_cut_rows.argtypes = [P_FLOAT, ctypes.c_int64, ctypes.c_int64, P_SAMPLE_PARAMS, ctypes.POINTER(CutParams), ctypes.POINTER(ctypes.c_uint64),
                                                 ctypes.c_int, P_UINT32, P_FLOAT]
             L.rwkv_mi_test_cut_rows.restype = ctypes.c_bool
+        if hasattr(L, "rwkv_mi_test_shape_rows"):   # (librwkv_testhooks_shape.so only)
+            L.rwkv_mi_test_shape_rows.argtypes = [P_FLOAT, ctypes.c_int64, ctypes.c_int64, P_SAMPLE_PARAMS, ctypes.POINTER(ShapeParams), ctypes.POINTER(ctypes.c_uint64),
+                                                  ctypes.c_int, P_UINT32, P_FLOAT]
+            L.rwkv_mi_test_shape_rows.restype = ctypes.c_bool
         if hasattr(L, "rwkv_mi_test_guided_rows"):   # (librwkv_testhooks_guide.so only)
             L.rwkv_mi_test_guided_rows.argtypes = [P_FLOAT, ctypes.c_int64, ctypes.c_int64, ctypes.c_uint32, P_UINT32, P_UINT32, P_UINT32, P_UINT32, P_UINT32, P_UINT32,
                                                    P_SAMPLE_PARAMS, P_PENALTY_PARAMS, P_UINT32, P_FLOAT, ctypes.POINTER(ctypes.c_uint64), P_UINT32, P_UINT32, P_UINT32]
@@ -737,6 +757,18 @@ class RWKVModel:
         k, p = ctypes.c_uint32(0), ctypes.c_float(0.0)
         self._mi("rwkv_mi_truncation_get", ctypes.byref(k), ctypes.byref(p))
         return int(k.value), float(p.value)
+
+    def set_shaping(self, typical_p: float = 0.0, n_sigma: float = 0.0) -> None:
+        """The context's shaping setting, read by every draw from now on: n_sigma (0: off) masks the values below max - n_sigma * their
+        standard deviation to -inf, in front of top-k; typical_p (0 or 1: off) keeps, of what survives that and top-k, the tokens whose
+        surprise lies nearest the entropy until their mass exceeds typical_p, in front of the softmax. (0, 0) clears."""
+        self._mi("rwkv_mi_shaping_set", float(typical_p), float(n_sigma))
+
+    def shaping(self) -> Tuple[float, float]:
+        """The context's shaping setting (typical_p, n_sigma); (0.0, 0.0) is none."""
+        t, s = ctypes.c_float(0.0), ctypes.c_float(0.0)
+        self._mi("rwkv_mi_shaping_get", ctypes.byref(t), ctypes.byref(s))
+        return float(t.value), float(s.value)
 
     def set_repetition(self, decay: float = 1.0, repetition: float = 1.0) -> None:
         """The context's repetition setting, read by every PENALISED draw from now on: repetition (1: off) divides the positive and multiplies
@@ -1241,6 +1273,21 @@ class RWKVBatch:
         if not self._L.rwkv_mi_batch_truncation_get(self._ptr, slot, ctypes.byref(k), ctypes.byref(p)):
             self._fail("rwkv_mi_batch_truncation_get")
         return int(k.value), float(p.value)
+
+    def set_shaping(self, slot: int, typical_p: float = 0.0, n_sigma: float = 0.0) -> None:
+        """The slot's shaping setting, read by every draw of the slot that reads its truncation setting: n_sigma (0: off) masks the values
+        below max - n_sigma * their standard deviation to -inf, in front of top-k; typical_p (0 or 1: off) keeps, of what survives that and
+        top-k, the tokens whose surprise lies nearest the entropy until their mass exceeds typical_p, in front of the softmax. (0, 0)
+        clears. copy_state does not carry it, and a serve request does not read it. Rejected while a serve session is open."""
+        if not self._L.rwkv_mi_batch_shaping_set(self._ptr, slot, float(typical_p), float(n_sigma)):
+            self._fail("rwkv_mi_batch_shaping_set")
+
+    def shaping(self, slot: int) -> Tuple[float, float]:
+        """The slot's shaping setting (typical_p, n_sigma); (0.0, 0.0) is none."""
+        t, s = ctypes.c_float(0.0), ctypes.c_float(0.0)
+        if not self._L.rwkv_mi_batch_shaping_get(self._ptr, slot, ctypes.byref(t), ctypes.byref(s)):
+            self._fail("rwkv_mi_batch_shaping_get")
+        return float(t.value), float(s.value)
 
     def set_repetition(self, slot: int, decay: float = 1.0, repetition: float = 1.0) -> None:
         """The slot's repetition setting, read by every PENALISED draw of the slot from now on (eval_sample_penalized, the ragged form, the

@@ -72,6 +72,10 @@ of the vocabulary; records also go to --out:
   mode guide_host     (c) the way without guides: per token and row rwkv_mi_batch_logit_bias_set with -inf on every forbidden id, one
                       rwkv_mi_batch_eval_sample_penalized pass, the token read back, the automaton stepped on the host; host clock
 
+--sample --shape TYPICAL,NSIGMA times the sampled loop (temperature 1.0, top-p 0.8, seed = row) with no setting and with the shaping setting
+(rwkv_mi_batch_shaping_set) on every slot, in the same process, --tokens steps, HIP events around each device loop, the smallest and the largest
+of --reps runs; shape_ms_per_step is the shaped step minus the plain one.
+
 --sample --cut K[,K...] times the sampled loop (temperature 1.0, top-p 0.8, seed = row) under truncation settings (rwkv_mi_batch_truncation_set)
 in the same process, --tokens steps, HIP events around each device loop, the smallest of --reps runs (the loop without a setting also with its
 largest run: the run-to-run spread of the box); sampler_ms_per_step is a loop's step minus the greedy loop's of the same n and run; records
@@ -728,6 +732,42 @@ def cut(pkg, m, args):
         sink.close()
 
 
+def shape(pkg, m, args):
+    """--sample --shape TYPICAL,NSIGMA: the sampled loop with no setting and with the shaping setting on every slot, HIP events around each loop"""
+    V = m.n_vocab
+    typical_p, n_sigma = (float(x) for x in args.shape.split(","))
+    sink = open(args.out, "a") if args.out else None
+    steps = args.tokens
+    ns = [int(x) for x in args.n.split(",")]
+    b = pkg.RWKVBatch(m, max(ns))
+    for n in ns:
+        slots = list(range(n))
+        first = [(7 * i + 1) % V for i in slots]
+
+        def runs(setting):
+            out = []
+            for k in range(args.reps + 1):   # (run 0: warm-up)
+                for s in slots:
+                    b.state_load(s, None)
+                    b.set_shaping(s, *setting)
+                out.append(b.decode_sample(slots, first, steps, 1.0, 0.8, slots)[1])
+            return out[1:]
+
+        plain, shaped = runs((0.0, 0.0)), runs((typical_p, n_sigma))
+        rec = {"mode": "shape_device", "n": n, "typical_p": typical_p, "n_sigma": n_sigma, "ms_per_step": round(min(shaped) / steps, 4),
+               "ms_per_step_max": round(max(shaped) / steps, 4), "plain_ms_per_step": round(min(plain) / steps, 4),
+               "plain_ms_per_step_max": round(max(plain) / steps, 4), "shape_ms_per_step": round((min(shaped) - min(plain)) / steps, 4),
+               "steps": steps, "reps": args.reps, "temperature": 1.0, "top_p": 0.8, "config": args.config, "dtype": args.dtype}
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if sink:
+            sink.write(line + "\n")
+            sink.flush()
+    b.free()
+    if sink:
+        sink.close()
+
+
 def guide(pkg, m, args):
     import ctypes
 
@@ -1016,6 +1056,8 @@ def main():
                     help="with --sample: time the sampled loop plain, guided on the device, and masked from the host before every token (see above)")
     ap.add_argument("--cut", default=None, metavar="K[,K...]",
                     help="with --sample: time the sampled loop with no truncation setting, with top_k = each K, with min_p = 0.05, and with both (see above)")
+    ap.add_argument("--shape", default=None, metavar="TYPICAL,NSIGMA",
+                    help="with --sample: time the sampled loop with no setting and with the shaping setting {typical_p, n_sigma} on every slot")
     ap.add_argument("--decay", default=None, metavar="D[,D...]",
                     help="with --sample --penalties: time the penalised loop with no repetition setting, with decay = each D, with --repetition, and with both (see above)")
     ap.add_argument("--repetition", type=float, default=1.1, help="--decay: the repetition penalty of the arms that have one")
@@ -1075,6 +1117,12 @@ def main():
         if not args.sample:
             ap.error("--cut times the sampled loop: give --sample with it")
         cut(pkg, m, args)
+        m.free()
+        return
+    if args.shape is not None:
+        if not args.sample:
+            ap.error("--shape times the sampled loop: give --sample with it")
+        shape(pkg, m, args)
         m.free()
         return
     if args.decay is not None:

@@ -80,6 +80,19 @@ RWKV_API const char * rwkv_mi_persist_info(struct rwkv_context * ctx);
  * asynchronous copies, re-pack kernels; the reference reads one tensor at a time, rwkv_file_format.inc:302-313), and its bytes. */
 RWKV_API void rwkv_mi_load_stats(const struct rwkv_context * ctx, double * seconds, uint64_t * bytes);
 
+/* ---- quantising on the device (csrc/quant_w.hip): an FP32 / FP16 file as a Q4_0 | Q4_1 | Q5_0 | Q5_1 | Q8_0 model ----
+ * Both calls select the tensors rwkv_quantize_model_file selects and produce its bits; weights are finite. */
+
+/* rwkv_init_from_file of the file rwkv_quantize_model_file(model_file_path, .., format_name) would write, without writing it: the selected
+ * tensors are quantised piece by piece on their way into HBM (the FP32 / FP16 image never rests there), every other tensor loads as always.
+ * The context reports the quantised model: its weight bytes, bytes per token, decode path. Errors: RWKV_ERROR_ARGS (a NULL argument),
+ * RWKV_ERROR_ARGS | RWKV_ERROR_DATA_TYPE (format_name is not a quantised format), RWKV_ERROR_FILE (the file is not FP32 / FP16),
+ * RWKV_ERROR_MODEL_PARAMS | RWKV_ERROR_SHAPE (a selected tensor's rows are no multiple of 32), and those of rwkv_init_from_file. */
+RWKV_API struct rwkv_context * rwkv_mi_init_from_file_as(const char * model_file_path, uint32_t n_threads, uint32_t n_gpu_layers, const char * format_name);
+/* rwkv_quantize_model_file with the blocks made on the device: the same arguments, checks and error codes, and a byte-identical output
+ * file. Needs a gfx950 device (RWKV_ERROR_CTX | RWKV_ERROR_UNSUPPORTED without one); rwkv_quantize_model_file stays on the host. */
+RWKV_API bool rwkv_mi_quantize_model_file(const char * model_file_path_in, const char * model_file_path_out, const char * format_name);
+
 /* Waits for the context's stream and reports whether every persistent-kernel step so far completed (false: a poll timed out
  * because not all workgroups could be resident -- the device is shared, or other kernels held CUs for seconds; results since
  * then are invalid and the context should be re-created with RWKV_MI_NO_MEGA=1). Always true on paths 0 and 1. */

@@ -89,6 +89,18 @@ RWKV_API struct rwkv_context * rwkv_init_from_file(const char * file_path, const
     return ctx;  // on failure create_context has already released the model
 }
 
+RWKV_API struct rwkv_context * rwkv_mi_init_from_file_as(const char * file_path, const uint32_t n_threads, const uint32_t n_gpu_layers, const char * type_name) {
+    (void) n_gpu_layers;
+    g_last_error = RWKV_ERROR_NONE;
+    RW_CHECK(RWKV_ERROR_ARGS, nullptr, file_path != nullptr && type_name != nullptr, "NULL argument");
+    const int as_type = dtype_from_name(type_name);
+    RW_CHECK(RWKV_ERROR_ARGS | RWKV_ERROR_DATA_TYPE, nullptr, as_type >= 0 && dtype_quantized(as_type), "Unsupported data type to load as (%s)", type_name);
+    if (const char * devs = getenv("RWKV_MI_DEVICES")) { if (devs[0]) return pipeline_create(file_path, n_threads, devs, as_type); }
+    Model * m = load_model(file_path, 0, UINT32_MAX, as_type);
+    if (!m) return nullptr;
+    return create_context(m, n_threads);
+}
+
 RWKV_API struct rwkv_context * rwkv_clone_context(struct rwkv_context * ctx, const uint32_t n_threads) {
     RW_CHECK(RWKV_ERROR_ARGS, nullptr, ctx != nullptr, "ctx is NULL");
     if (!ctx->stages.empty()) return pipeline_clone(ctx, n_threads);

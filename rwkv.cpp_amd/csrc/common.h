@@ -73,6 +73,10 @@ bool read_file_header(FILE * f, FileHeader & h);
 bool read_tensor_info(FILE * f, TensorInfo & t);
 uint64_t tensor_nbytes(int type, int64_t n0, int64_t n1, int64_t n2);
 
+// The reference's selection rule of the file quantiser (quantize.cpp): which names it never quantises, and the tensors it takes.
+bool tensor_needs_quant(const std::string & name);
+inline bool quantizer_selects(const TensorInfo & t) { return (t.type == T_F32 || t.type == T_F16) && t.ndim == 2 && tensor_needs_quant(t.name); }
+
 // ---------------------------------------------------------------------------------------------------------------
 // Device-side tensors
 // ---------------------------------------------------------------------------------------------------------------

@@ -224,5 +224,10 @@ void launch_transpose_w2(const float * src, float * dst, int64_t D, int64_t R, h
 
 // load-time re-pack of quantised blocks (file layout) into planes; see DevTensor
 void launch_repack(int type, const uint8_t * raw, int64_t n_blocks, uint8_t * qs, uint32_t * qh, void * sc, hipStream_t st);
+// quant_w.hip: n_blocks blocks of 32 FP32 / FP16 weights (src_type T_F32 / T_F16, contiguous) quantised to `type` with the arithmetic of the
+// file quantiser (quantize.cpp, quantize_row), as the planes launch_repack leaves or as the file's block bytes. src and every
+// destination are 16-byte aligned.
+void launch_quant_w_planes(int type, int src_type, const void * src, int64_t n_blocks, uint8_t * qs, uint32_t * qh, void * sc, hipStream_t st);
+void launch_quant_w_blocks(int type, int src_type, const void * src, int64_t n_blocks, uint8_t * blocks, hipStream_t st);
 
 }  // namespace rwkvmi

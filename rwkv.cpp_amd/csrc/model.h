@@ -318,9 +318,11 @@ bool check_penalty(rwkv_context * ctx, float presence, float frequency, size_t i
 
 // Loads [layer_begin, layer_end) of the file (layer_end == UINT32_MAX: all layers) onto the current HIP device.
 // Returns nullptr with the thread-local error set, like the reference loader (rwkv_model_loading.inc:288-419).
-Model * load_model(const char * path, uint32_t layer_begin, uint32_t layer_end);
+// as_type >= 0 (a quantised type; the file is FP32 / FP16): every tensor the file quantiser selects is quantised to it on the way, and the
+// model is the model of the file rwkv_quantize_model_file would have written.
+Model * load_model(const char * path, uint32_t layer_begin, uint32_t layer_end, int as_type = -1);
 void    release_model(Model * m);
-bool    scan_stage_costs(const char * path, std::vector<uint64_t> & per_layer, uint64_t & head_bytes);
+bool    scan_stage_costs(const char * path, std::vector<uint64_t> & per_layer, uint64_t & head_bytes, int as_type = -1);
 
 }  // namespace rwkvmi
 
@@ -569,7 +571,7 @@ PersistentDecoder * p47_create(const Model & m);       // RWKV-4 / RWKV-7 (persi
 const char * persist_unavailable_reason(const Model & m);   // nullptr: a persistent kernel exists for this model on this device
 // ---- layer pipeline in one process (pipeline.cpp) ----
 bool upload_tokens(rwkv_context * ctx, const uint32_t * tokens, size_t n);   // api.cpp: pinned staging + async copy into ctx->d_tokens
-rwkv_context * pipeline_create(const char * path, uint32_t n_threads, const char * devices);
+rwkv_context * pipeline_create(const char * path, uint32_t n_threads, const char * devices, int as_type = -1);   // as_type: load_model's
 void pipeline_destroy(rwkv_context * front);
 bool pipeline_eval(rwkv_context * front, const uint32_t * tokens, size_t n, size_t chunk, const float * state_in, float * state_out, float * logits_out);
 rwkv_context * pipeline_clone(rwkv_context * front, uint32_t n_threads);

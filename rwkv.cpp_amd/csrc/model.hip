@@ -4,17 +4,12 @@
 // What is new: every parameter goes to one HBM arena; quantised tensors are re-packed into aligned planes on the GPU.
 #include "model.h"
 
-#include <atomic>
-#include <cerrno>
+#include "read_ring.h"
+
 #include <chrono>
 #include <cinttypes>
-#include <condition_variable>
 #include <cstring>
-#include <fcntl.h>
-#include <mutex>
 #include <sys/stat.h>
-#include <thread>
-#include <unistd.h>
 
 namespace rwkvmi {
 
@@ -198,7 +193,8 @@ static bool validate_shapes(Model & m) {
 }
 
 // Bytes a decoded token streams per layer / for the head, from the file's tensor directory alone (used to balance pipeline stages).
-bool scan_stage_costs(const char * path, std::vector<uint64_t> & per_layer, uint64_t & head_bytes) {
+// as_type >= 0: the costs of the file as load_model(.., as_type) holds it.
+bool scan_stage_costs(const char * path, std::vector<uint64_t> & per_layer, uint64_t & head_bytes, int as_type) {
     FILE * f = fopen(path, "rb");
     RW_CHECK(RWKV_ERROR_FILE | RWKV_ERROR_FILE_OPEN, false, f != nullptr, "Failed to open file %s", path);
     std::unique_ptr<FILE, int (*)(FILE *)> fguard(f, fclose);
@@ -212,14 +208,15 @@ bool scan_stage_costs(const char * path, std::vector<uint64_t> & per_layer, uint
         TensorInfo ti;
         if (!read_tensor_info(f, ti)) { global_fail(RWKV_ERROR_MODEL_PARAMS, __FILE__, __LINE__, "read_tensor_info", "Failed to read a model parameter"); return false; }
         uint32_t li;
-        if (layer_of(ti.name, li)) { if (li < h.n_layer) per_layer[li] += ti.nbytes; }
-        else if (ti.name != "emb.weight") head_bytes += ti.nbytes;
+        const uint64_t cost = as_type >= 0 && quantizer_selects(ti) ? tensor_nbytes(as_type, ti.ne[0], ti.ne[1], ti.ne[2]) : ti.nbytes;
+        if (layer_of(ti.name, li)) { if (li < h.n_layer) per_layer[li] += cost; }
+        else if (ti.name != "emb.weight") head_bytes += cost;
         RW_CHECK(RWKV_ERROR_MODEL_PARAMS | RWKV_ERROR_FILE_READ, false, fseeko(f, (off_t) ti.nbytes, SEEK_CUR) == 0, "Failed to seek past parameter %s", ti.name.c_str());
     }
     return true;
 }
 
-Model * load_model(const char * path, uint32_t layer_begin, uint32_t layer_end) {
+Model * load_model(const char * path, uint32_t layer_begin, uint32_t layer_end, int as_type) {
     FILE * f = fopen(path, "rb");
     RW_CHECK(RWKV_ERROR_FILE | RWKV_ERROR_FILE_OPEN, nullptr, f != nullptr, "Failed to open file %s", path);
     std::unique_ptr<FILE, int (*)(FILE *)> fguard(f, fclose);
@@ -232,6 +229,8 @@ Model * load_model(const char * path, uint32_t layer_begin, uint32_t layer_end) 
         global_fail(RWKV_ERROR_FILE, __FILE__, __LINE__, "read_file_header", "Invalid file header");
         return nullptr;
     }
+    RW_CHECK(RWKV_ERROR_FILE, nullptr, as_type < 0 || m->header.data_type == T_F32 || m->header.data_type == T_F16,
+             "Unsupported input data type (%s); needs to be FP32 or FP16", dtype_name((int) m->header.data_type));
 
     // No CPU path exists in this library: without a gfx950 device the load fails loudly.
     int n_dev = 0;
@@ -263,6 +262,20 @@ Model * load_model(const char * path, uint32_t layer_begin, uint32_t layer_end) 
                  "Failed to seek to next tensor after parameter %s", ti.name.c_str());
         infos.push_back(std::move(ti));
     }
+    // Loading as a quantised type: from here on a tensor the file quantiser selects IS the tensor that quantiser would have written -- its
+    // type, its bytes, the header's data type. Only its pieces know the source: they span the FP32 / FP16 payload and are quantised on
+    // the device (quant_w.hip).
+    std::vector<int> src_type(infos.size(), -1);
+    for (size_t i = 0; as_type >= 0 && i < infos.size(); i++) {
+        TensorInfo & ti = infos[i];
+        if (!quantizer_selects(ti)) continue;
+        RW_CHECK(RWKV_ERROR_MODEL_PARAMS | RWKV_ERROR_SHAPE, nullptr, ti.ne[0] % 32 == 0,
+                 "Tensor %s has rows of %" PRId64 " elements: quantised formats need a multiple of 32", ti.name.c_str(), ti.ne[0]);
+        src_type[i] = ti.type;
+        ti.type = as_type;
+        ti.nbytes = tensor_nbytes(as_type, ti.ne[0], ti.ne[1], ti.ne[2]);
+    }
+    if (as_type >= 0) { m->header.version = RWKV_FILE_VERSION; m->header.data_type = (uint32_t) as_type; }
 
     auto has = [&](const char * key) { for (const TensorInfo & t : infos) if (t.name == key) return true; return false; };
     m->arch_major = 4; m->arch_minor = 0;
@@ -307,12 +320,13 @@ Model * load_model(const char * path, uint32_t layer_begin, uint32_t layer_end) 
     // the runtime) and, for quantised payloads and the RWKV-6 mix matrix, the re-pack / transpose kernel out of a device staging
     // buffer. Reads, copies and kernels of different pieces overlap; a slot is refilled when the event behind its last use has completed.
     const auto t_load0 = std::chrono::steady_clock::now();
-    constexpr size_t k_piece = (size_t) 32 << 20;
-    constexpr int k_slots = 4, k_readers = 4;
-    struct Piece { const TensorInfo * t; DevTensor * dt; uint64_t off, bytes; int64_t blk0, nblk; int kind; };   // kind 0 plain, 1 quantised, 2 w2
+    constexpr size_t k_piece = ReadRing::k_piece;
+    // kind 0 plain, 1 quantised, 2 w2, 3 an FP32 / FP16 payload quantised on the device (src: its type in the file)
+    struct Piece { const TensorInfo * t; DevTensor * dt; uint64_t off, bytes; int64_t blk0, nblk; int kind, src; };
     std::vector<Piece> pieces;
     uint8_t * cursor = (uint8_t *) m->arena;
-    for (const TensorInfo & t : infos) {
+    for (size_t ti = 0; ti < infos.size(); ti++) {
+        const TensorInfo & t = infos[ti];
         if (!wanted(t)) continue;
         std::unique_ptr<DevTensor> dt(new DevTensor());
         dt->name = t.name; dt->type = t.type; dt->ndim = t.ndim; dt->nbytes = t.nbytes;
@@ -324,19 +338,22 @@ Model * load_model(const char * path, uint32_t layer_begin, uint32_t layer_end) 
             if (w2) {
                 // v6 mix matrix: stored transposed ([5][R][D]) so that the mix kernels read it coalesced -- one piece
                 RW_CHECK(RWKV_ERROR_MODEL_PARAMS | RWKV_ERROR_UNSUPPORTED, nullptr, t.nbytes <= k_piece, "Parameter %s is too large for the load pipeline", t.name.c_str());
-                pieces.push_back(Piece{&t, dt.get(), 0, t.nbytes, 0, 0, 2});
+                pieces.push_back(Piece{&t, dt.get(), 0, t.nbytes, 0, 0, 2, -1});
             } else {
-                for (uint64_t o = 0; o < t.nbytes; o += k_piece) pieces.push_back(Piece{&t, dt.get(), o, t.nbytes - o < k_piece ? t.nbytes - o : k_piece, 0, 0, 0});
+                for (uint64_t o = 0; o < t.nbytes; o += k_piece) pieces.push_back(Piece{&t, dt.get(), o, t.nbytes - o < k_piece ? t.nbytes - o : k_piece, 0, 0, 0, -1});
             }
         } else {
             dt->qs = cursor; cursor += p.qs;
             if (p.qh) { dt->qh = (uint32_t *) cursor; cursor += p.qh; }
             dt->sc = cursor; cursor += p.sc;
-            const uint64_t bsz = dtype_block_bytes(t.type);
+            // bytes of one block in the file: the block itself, or its 32 source elements (a piece of those is a whole number of the
+            // quantiser's 256-block tiles, so every piece's planes start 16-byte aligned)
+            const int src = src_type[ti];
+            const uint64_t bsz = src < 0 ? dtype_block_bytes(t.type) : 32 * dtype_block_bytes(src);
             const int64_t nblk = t.nelements() / 32, per = (int64_t) (k_piece / bsz);
             for (int64_t b0 = 0; b0 < nblk; b0 += per) {
                 const int64_t nb = nblk - b0 < per ? nblk - b0 : per;
-                pieces.push_back(Piece{&t, dt.get(), (uint64_t) b0 * bsz, (uint64_t) nb * bsz, b0, nb, 1});
+                pieces.push_back(Piece{&t, dt.get(), (uint64_t) b0 * bsz, (uint64_t) nb * bsz, b0, nb, src < 0 ? 1 : 3, src});
             }
         }
         m->weight_bytes += t.nbytes;
@@ -344,88 +361,33 @@ Model * load_model(const char * path, uint32_t layer_begin, uint32_t layer_end) 
         m->tensors.push_back(std::move(dt));
     }
 
-    struct Pipe {
-        int fd = -1;
-        void * h[k_slots] = {}; void * d[k_slots] = {}; hipEvent_t ev[k_slots] = {};
-        hipStream_t st = nullptr;
-        std::vector<std::thread> th;
-        std::mutex mu; std::condition_variable cv;
-        std::vector<int> state;          // per piece: 0 not read, 1 read (slot filled), 2 enqueued (event recorded), -1 read error
-        std::atomic<size_t> next{0};
-        bool stop = false;
-        ~Pipe() {
-            { std::lock_guard<std::mutex> lk(mu); stop = true; }
-            cv.notify_all();
-            for (std::thread & t : th) if (t.joinable()) t.join();
-            if (st) { (void) hipStreamSynchronize(st); (void) hipStreamDestroy(st); }
-            for (int i = 0; i < k_slots; i++) { if (h[i]) (void) hipHostFree(h[i]); if (d[i]) (void) hipFree(d[i]); if (ev[i]) (void) hipEventDestroy(ev[i]); }
-            if (fd >= 0) close(fd);
-        }
-    } pp;
-    pp.fd = open(path, O_RDONLY);
-    RW_CHECK(RWKV_ERROR_FILE | RWKV_ERROR_FILE_OPEN, nullptr, pp.fd >= 0, "Failed to open file %s", path);
-    (void) posix_fadvise(pp.fd, 0, 0, POSIX_FADV_SEQUENTIAL);
-    HIP_OK_OR(nullptr, RWKV_ERROR_CTX, hipStreamCreateWithFlags(&pp.st, hipStreamNonBlocking));
     bool any_staged = false;
-    for (const Piece & pc : pieces) any_staged = any_staged || pc.kind != 0;
-    for (int i = 0; i < k_slots && !pieces.empty(); i++) {
-        HIP_OK_OR(nullptr, RWKV_ERROR_MODEL | RWKV_ERROR_ALLOC, hipHostMalloc(&pp.h[i], k_piece, hipHostMallocDefault));
-        if (any_staged) HIP_OK_OR(nullptr, RWKV_ERROR_MODEL | RWKV_ERROR_ALLOC, hipMalloc(&pp.d[i], k_piece));
-        HIP_OK_OR(nullptr, RWKV_ERROR_CTX, hipEventCreateWithFlags(&pp.ev[i], hipEventDisableTiming));
-    }
-    pp.state.assign(pieces.size(), 0);
-    auto reader = [&pp, &pieces, device]() {
-        (void) hipSetDevice(device);
-        for (;;) {
-            const size_t i = pp.next.fetch_add(1);
-            if (i >= pieces.size()) return;
-            const int slot = (int) (i % k_slots);
-            if (i >= (size_t) k_slots) {
-                // the slot's previous piece must have been enqueued (event recorded) and its copy / kernel finished
-                std::unique_lock<std::mutex> lk(pp.mu);
-                pp.cv.wait(lk, [&] { return pp.stop || pp.state[i - k_slots] == 2; });
-                if (pp.stop) return;
-                lk.unlock();
-                if (hipEventSynchronize(pp.ev[slot]) != hipSuccess) { std::lock_guard<std::mutex> g(pp.mu); pp.state[i] = -1; pp.cv.notify_all(); return; }
-            }
-            const Piece & pc = pieces[i];
-            uint64_t done = 0;
-            bool ok = true;
-            while (done < pc.bytes) {
-                const ssize_t r = pread(pp.fd, (uint8_t *) pp.h[slot] + done, pc.bytes - done, (off_t) (pc.t->file_offset + pc.off + done));
-                if (r <= 0) { if (r < 0 && errno == EINTR) continue; ok = false; break; }
-                done += (uint64_t) r;
-            }
-            { std::lock_guard<std::mutex> g(pp.mu); pp.state[i] = ok ? 1 : -1; }
-            pp.cv.notify_all();
-            if (!ok) return;
-        }
-    };
-    for (int i = 0; i < k_readers && (size_t) i < pieces.size(); i++) pp.th.emplace_back(reader);
+    std::vector<ReadRing::Span> spans;
+    for (const Piece & pc : pieces) { any_staged = any_staged || pc.kind != 0; spans.push_back({pc.t->file_offset + pc.off, pc.bytes}); }
+    ReadRing pp;
+    if (!pp.start(path, std::move(spans), any_staged, device)) return nullptr;
     for (size_t i = 0; i < pieces.size(); i++) {
         const Piece & pc = pieces[i];
-        const int slot = (int) (i % k_slots);
-        {
-            std::unique_lock<std::mutex> lk(pp.mu);
-            pp.cv.wait(lk, [&] { return pp.state[i] != 0; });
-            RW_CHECK(RWKV_ERROR_FILE | RWKV_ERROR_FILE_READ, nullptr, pp.state[i] == 1, "Failed to read parameter %s from %s", pc.t->name.c_str(), path);
-        }
+        const int slot = ReadRing::slot(i);
+        RW_CHECK(RWKV_ERROR_FILE | RWKV_ERROR_FILE_READ, nullptr, pp.wait_read(i), "Failed to read parameter %s from %s", pc.t->name.c_str(), path);
         DevTensor * dt = pc.dt;
         if (pc.kind == 0) {
             HIP_OK_OR(nullptr, RWKV_ERROR_MODEL | RWKV_ERROR_DATA, hipMemcpyAsync((uint8_t *) dt->data + pc.off, pp.h[slot], pc.bytes, hipMemcpyHostToDevice, pp.st));
         } else {
             HIP_OK_OR(nullptr, RWKV_ERROR_MODEL | RWKV_ERROR_DATA, hipMemcpyAsync(pp.d[slot], pp.h[slot], pc.bytes, hipMemcpyHostToDevice, pp.st));
+            const int64_t qsb = pc.t->type == T_Q8_0 ? 32 : 16, scb = (pc.t->type == T_Q4_1 || pc.t->type == T_Q5_1) ? 4 : 2;
             if (pc.kind == 2) {
                 launch_transpose_w2((const float *) pp.d[slot], (float *) dt->data, pc.t->ne[1], pc.t->ne[0], pp.st);
+            } else if (pc.kind == 3) {
+                launch_quant_w_planes(dt->type, pc.src, pp.d[slot], pc.nblk, dt->qs + pc.blk0 * qsb, dt->qh ? dt->qh + pc.blk0 : nullptr,
+                                      (uint8_t *) dt->sc + pc.blk0 * scb, pp.st);
             } else {
-                const int64_t qsb = pc.t->type == T_Q8_0 ? 32 : 16, scb = (pc.t->type == T_Q4_1 || pc.t->type == T_Q5_1) ? 4 : 2;
                 launch_repack(pc.t->type, (const uint8_t *) pp.d[slot], pc.nblk, dt->qs + pc.blk0 * qsb, dt->qh ? dt->qh + pc.blk0 : nullptr,
                               (uint8_t *) dt->sc + pc.blk0 * scb, pp.st);
             }
         }
-        HIP_OK_OR(nullptr, RWKV_ERROR_MODEL | RWKV_ERROR_DATA, hipEventRecord(pp.ev[slot], pp.st));
-        { std::lock_guard<std::mutex> g(pp.mu); pp.state[i] = 2; }
-        pp.cv.notify_all();
+        HIP_OK_OR(nullptr, RWKV_ERROR_MODEL | RWKV_ERROR_DATA, pp.record(i));
+        pp.release(i);
     }
     HIP_OK_OR(nullptr, RWKV_ERROR_MODEL | RWKV_ERROR_DATA, hipStreamSynchronize(pp.st));
     HIP_OK_OR(nullptr, RWKV_ERROR_MODEL | RWKV_ERROR_DATA, hipGetLastError());

@@ -81,7 +81,7 @@ static bool finish_stage(rwkv_context * c) {
            hipEventCreateWithFlags(&c->consumed_ev, hipEventDisableTiming) == hipSuccess;
 }
 
-rwkv_context * pipeline_create(const char * path, uint32_t n_threads, const char * devices) {
+rwkv_context * pipeline_create(const char * path, uint32_t n_threads, const char * devices, int as_type) {
     std::vector<int> devs;
     RW_CHECK(RWKV_ERROR_ARGS, nullptr, parse_devices(devices, devs), "RWKV_MI_DEVICES=\"%s\" is not a device list (e.g. 0,1,2,3 or 0-3)", devices);
     int n_dev = 0;
@@ -89,7 +89,7 @@ rwkv_context * pipeline_create(const char * path, uint32_t n_threads, const char
     for (int d : devs) RW_CHECK(RWKV_ERROR_ARGS, nullptr, d < n_dev, "RWKV_MI_DEVICES names device %d, but only %d are visible", d, n_dev);
     std::vector<uint64_t> per_layer;
     uint64_t head = 0;
-    if (!scan_stage_costs(path, per_layer, head)) return nullptr;
+    if (!scan_stage_costs(path, per_layer, head, as_type)) return nullptr;
     std::vector<std::pair<uint32_t, uint32_t>> ranges;
     partition(per_layer, head, devs.size(), ranges);
     rwkv_context * front = make_front();
@@ -100,7 +100,7 @@ rwkv_context * pipeline_create(const char * path, uint32_t n_threads, const char
     for (size_t s = 1; s < devs.size(); s++) multi_device = multi_device || devs[s] != devs[0];
     for (size_t s = 0; s < ranges.size(); s++) {
         if (hipSetDevice(devs[s]) != hipSuccess) { pipeline_destroy(front); global_fail(RWKV_ERROR_CTX, __FILE__, __LINE__, "hipSetDevice", "cannot select device %d", devs[s]); return nullptr; }
-        Model * m = load_model(path, ranges[s].first, ranges[s].second);
+        Model * m = load_model(path, ranges[s].first, ranges[s].second, as_type);
         rwkv_context * c = m ? create_context(m, n_threads) : nullptr;
         if (!c || !finish_stage(c)) { if (c) front->stages.push_back(c); pipeline_destroy(front); (void) hipSetDevice(prev_dev); return nullptr; }
         front->stages.push_back(c);

@@ -20,7 +20,7 @@ static inline float f16_to_f32(uint16_t u) {
     _Float16 h; memcpy(&h, &u, 2); return (float) h;
 }
 
-static bool tensor_needs_quant(const std::string & name) {
+bool tensor_needs_quant(const std::string & name) {
     static const char * const never[] = {"att.v1", "att.v2", "att.g1", "att.g2", "att.a1", "att.a2", "att.w1", "att.w2", "att.r_k"};
     if (name == "emb.weight" || name == "head.weight") return false;
     for (const char * n : never) if (name.find(n) != std::string::npos) return false;

@@ -224,6 +224,10 @@ class RWKVSharedLibrary:
         L.rwkv_mi_get_arch.restype = None
         L.rwkv_mi_init_stage.argtypes = [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]
         L.rwkv_mi_init_stage.restype = c_ctx
+        L.rwkv_mi_init_from_file_as.argtypes = [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_char_p]
+        L.rwkv_mi_init_from_file_as.restype = c_ctx
+        L.rwkv_mi_quantize_model_file.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p]
+        L.rwkv_mi_quantize_model_file.restype = ctypes.c_bool
         L.rwkv_mi_set_stream.argtypes = [c_ctx, ctypes.c_void_p]
         L.rwkv_mi_set_stream.restype = ctypes.c_bool
         L.rwkv_mi_handoff_len.argtypes = [c_ctx]
@@ -506,6 +510,23 @@ class RWKVSharedLibrary:
         if not self.library.rwkv_quantize_model_file(model_file_path_in.encode("utf-8"), model_file_path_out.encode("utf-8"), format_name.encode("utf-8")):
             raise ValueError("rwkv_quantize_model_file failed, check stderr")
 
+    def rwkv_mi_quantize_model_file(self, model_file_path_in: str, model_file_path_out: str, format_name: str) -> None:
+        """rwkv_quantize_model_file with the blocks made on the device (csrc/quant_w.hip): the same file, byte for byte"""
+        if format_name not in QUANTIZED_FORMAT_NAMES:
+            raise ValueError(f"Unknown format name {format_name}, use one of {QUANTIZED_FORMAT_NAMES}")
+        if not self.library.rwkv_mi_quantize_model_file(model_file_path_in.encode("utf-8"), model_file_path_out.encode("utf-8"), format_name.encode("utf-8")):
+            raise ValueError("rwkv_mi_quantize_model_file failed, check stderr")
+
+    def rwkv_mi_init_from_file_as(self, model_file_path: str, thread_count: int, offload_layers: int, format_name: str) -> RWKVContext:
+        """an FP32 / FP16 file loaded as the model rwkv_quantize_model_file(.., format_name) would have written, quantised on the device"""
+        if format_name not in QUANTIZED_FORMAT_NAMES:
+            raise ValueError(f"Unknown format name {format_name}, use one of {QUANTIZED_FORMAT_NAMES}")
+        ptr = self.library.rwkv_mi_init_from_file_as(model_file_path.encode("utf-8"), ctypes.c_uint32(thread_count), ctypes.c_uint32(offload_layers),
+                                                     format_name.encode("utf-8"))
+        if not ptr:
+            raise ValueError("rwkv_mi_init_from_file_as failed, check stderr")
+        return RWKVContext(ptr)
+
     def rwkv_get_system_info_string(self) -> str:
         return self.library.rwkv_get_system_info_string().decode("utf-8")
 
@@ -543,7 +564,9 @@ def _ptr(a: Optional[np.ndarray]) -> int:
 class RWKVModel:
     """numpy flavour of the reference's RWKVModel (python/rwkv_cpp/rwkv_cpp_model.py:22-364)."""
 
-    def __init__(self, shared_library: RWKVSharedLibrary, model_path: str, thread_count: int = 1, gpu_layer_count: int = 0, **kwargs) -> None:
+    def __init__(self, shared_library: RWKVSharedLibrary, model_path: str, thread_count: int = 1, gpu_layer_count: int = 0, load_as: Optional[str] = None,
+                 **kwargs) -> None:
+        """load_as="Q5_1" (any quantised format): an FP32 / FP16 file is quantised on the device while it loads"""
         if "gpu_layers_count" in kwargs:
             gpu_layer_count = kwargs["gpu_layers_count"]
         if not os.path.isfile(model_path):
@@ -551,7 +574,8 @@ class RWKVModel:
         if thread_count <= 0:
             raise ValueError("Thread count must be > 0")
         self._library = shared_library
-        self._ctx = shared_library.rwkv_init_from_file(model_path, thread_count, gpu_layer_count)
+        self._ctx = (shared_library.rwkv_init_from_file(model_path, thread_count, gpu_layer_count) if load_as is None else
+                     shared_library.rwkv_mi_init_from_file_as(model_path, thread_count, gpu_layer_count, load_as))
         self._state_buffer_element_count = shared_library.rwkv_get_state_buffer_element_count(self._ctx)
         self._logits_buffer_element_count = shared_library.rwkv_get_logits_buffer_element_count(self._ctx)
         self._valid = True
